@@ -352,6 +352,29 @@ def _emit(out):
     print(json.dumps(out))
 
 
+DUMP_TABLE_ROWS = 65536      # --dump-outputs with --train-emb: the table's first rows (the Zipf-hot ids), 16 MB at D = 64
+
+
+def dump_outputs(path, m, tab, train_emb):
+    """--dump-outputs DIR: what the timed training path hands its caller after its last step -- every weight tensor of the
+    model and its two Adam moments, and with --train-emb the first DUMP_TABLE_ROWS rows of the trained table -- as
+    DIR/<name>.npy in float32.  The inputs, weights and dropout stream are seeded, so two builds run with the same arguments
+    can be compared file by file.  Returns the names written."""
+    from goctr_amd import capi
+    capi.sync()
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    for name in ("mlp0", "mlp1", "mlp2") + (("att0",) if CFG["KIND"] == "din" else ()):
+        arrays[name] = m.get_weights(name)
+        arrays[name + "_adam_m"] = m.get_moments(name, 0)
+        arrays[name + "_adam_v"] = m.get_moments(name, 1)
+    if train_emb:
+        arrays["emb_rows"] = tab.get_rows(0, min(tab.V, DUMP_TABLE_ROWS))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return sorted(arrays)
+
+
 def bench_mlp(args):
     """BASELINE configs[1] / SURVEY 8(d) cfg2: sklearn-port MLP [281,100,1] relu/adam (float64), B = 4096, rows resident
     in HBM; a step = forward, log-loss, backward, per-parameter Adam over one batch (nn/neural_network/basemlp64.go)."""
@@ -788,6 +811,7 @@ def bench_single_process(args):
     order = sorted(range(len(regions)), key=lambda i: regions[i])
     med = order[(len(order) - 1) // 2]
     dt = regions[med]
+    dumped = dump_outputs(args.dump_outputs, m, tab, args.train_emb > 0) if args.dump_outputs else None
     # replicas must hold the same bits (same all-reduced gradient, same Adam)
     import zlib
     crcs = []
@@ -807,6 +831,8 @@ def bench_single_process(args):
            "per_rank_ms_per_step": [round(x / args.steps * 1e3, 4) for x in per_rank[med]],
            "per_rank_basis": "device time of each rank's steps in the median region (events on the rank's own stream)",
            "replicas_bit_identical": len(set(crcs)) == 1}
+    if dumped:
+        out["dumped_outputs"] = dumped
     print(json.dumps(out), flush=True)
     if not out["replicas_bit_identical"]:
         print(f"bench.py: the {N} replicas DIVERGED (weight checksums {crcs})", file=sys.stderr)
@@ -844,7 +870,16 @@ def main():
     ap.add_argument("--train-emb", type=float, default=0.0, metavar="LR",
                     help="din / youtube: also train the embedding table (EXTENSION with no reference counterpart: SGD "
                          "scatter-add, csrc/emb_train.h).  Off by default: the headline metric keeps the reference's frozen table")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="din / youtube: after the timed steps write what the last one left the caller (weights, Adam moments; "
+                         "with --train-emb a fixed slice of the table) as DIR/<name>.npy, float32, for output-by-output comparison of two builds")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload not in ("din", "youtube"):
+        print(f"bench.py: --dump-outputs covers the din / youtube training path, not --workload {args.workload}", file=sys.stderr)
+        sys.exit(2)
+    if args.dump_outputs and args.phase == "predict":
+        print("bench.py: --dump-outputs needs the training steps (--phase all or train)", file=sys.stderr)
+        sys.exit(2)
     if args.workload == "mlp":
         return bench_mlp(args)
     if args.workload == "mlp100k":
@@ -990,6 +1025,8 @@ def main():
         gm.train_steps(m, ds, cfg, args.warmup, first_batch=cursor[0], emb=tab)
         cursor[0] += args.warmup
     regions, per_rank_regions = timed_regions()
+    # (before the serving and roofline legs below: the roofline re-runs K more training steps on this model)
+    dumped = dump_outputs(args.dump_outputs, m, tab, args.train_emb > 0) if args.dump_outputs and rank == 0 else None
     med = median_index(regions)
     dt = regions[med]
     per_rank_ms = [round(x / args.steps * 1e3, 4) for x in per_rank_regions[med]]
@@ -1032,6 +1069,8 @@ def main():
                             "taken before that pre-load, the protocol every N > 1 line follows"},
         "without_preload": without_preload,
     }
+    if dumped:
+        out["dumped_outputs"] = dumped
     if world > 1:
         import ctypes as C
         mode = C.c_int(0)

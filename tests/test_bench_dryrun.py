@@ -13,6 +13,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -104,6 +105,32 @@ def test_bench_gpus8_train_emb_line_carries_the_exchange_bytes(stub):
     assert d["config"]["train_embeddings"] is True and d["rccl_world"] == 8
     assert d["sparse_exchange_bytes_per_step_per_rank"] == 1000.0      # rank 0's own figure
     assert d["replicas_bit_identical"] is True            # (+ the first 65 536 table rows)
+
+
+def test_bench_dump_outputs_writes_the_models_arrays(stub, tmp_path):
+    """--dump-outputs DIR: rank 0 writes every weight tensor and its two Adam moments as float32 .npy (the stub leaves them
+    unset, so only names, shapes, dtypes and the size cap are checked here; the values are the GPU run's)"""
+    out = tmp_path / "out"
+    r = _run(stub, ["--no-roofline", "--dump-outputs", str(out)], gpus=2)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][0])
+    assert d["steps"] == 6 and d["ms_per_step"] > 0
+    shapes = {"mlp0": (52 + 2 * 16 + 53, 200), "mlp1": (200, 80), "mlp2": (80, 1), "att0": (1, 50)}
+    want = sorted(n + s for n in shapes for s in ("", "_adam_m", "_adam_v"))
+    assert d["dumped_outputs"] == want
+    assert sorted(os.listdir(out)) == [n + ".npy" for n in want]
+    total = 0
+    for n in want:
+        a = np.load(out / (n + ".npy"))
+        assert a.dtype == np.float32 and a.shape == shapes[n.split("_")[0]]
+        total += a.nbytes
+    assert total <= 64 << 20
+
+
+def test_bench_dump_outputs_refuses_a_workload_it_does_not_cover(stub, tmp_path):
+    r = _run(stub, ["--workload", "knn", "--dump-outputs", str(tmp_path / "out")], gpus=1)
+    assert r.returncode == 2 and "--dump-outputs" in r.stderr
+    assert not (tmp_path / "out").exists()
 
 
 def test_bench_fails_when_the_communicator_is_smaller_than_gpus(stub):
