@@ -239,9 +239,6 @@ int env_int(const char* name, int dflt) {
 // so the launch is sized to ONE equally expensive workgroup per CU: the 3-tile problems (dW0: ceil(Ip/48)
 // blocks, dW1: ceil(H2p/48) blocks per slab) take `rows` batch rows per workgroup, the one-tile problems
 // (dW2, datt0: a third of the MFMAs per row) take 3x as many.
-#ifndef GOCTR_TN_CH
-#define GOCTR_TN_CH 32
-#endif
 struct TnSchedule { int rows, S, rows_light, S_light; };
 TnSchedule tn_schedule(const goctr_model* m, int B) {
   TnSchedule t{};
@@ -325,8 +322,7 @@ bool dw_wide_path(const goctr_model* m, int B) {
   int nt_max = m->H1p / 16;
   if (m->H2p / 16 > nt_max) nt_max = m->H2p / 16;
   if (m->cfg.kind == GOCTR_DIN && m->Tp / 16 > nt_max) nt_max = m->Tp / 16;
-  const bool multi = nt_max <= 16 && gemm_tn_multi_fits<3, GOCTR_TN_CH>(nt_max);
-  return multi && GOCTR_TN_CH == 32 && tn_schedule_wide(m, B).ok;
+  return gemm_tn_multi_fits(nt_max) && tn_schedule_wide(m, B).ok;
 }
 
 int ensure_workspace(goctr_model* m, int B) {
@@ -481,7 +477,7 @@ int init_kernel_attrs() {
       allow_big_lds(ctr_chain_kernel<7, 5, 2>) || allow_big_lds(ctr_fwd16_kernel<4, 5>) || allow_big_lds(emb_grad_kernel<16, 0, true>) || allow_big_lds(emb_grad_kernel<16, 1, true>) || allow_big_lds(emb_grad_kernel<16, 2, true>) || allow_big_lds(emb_grad_kernel<32, 0, true>) ||
       allow_big_lds(emb_grad_kernel<32, 1, true>) || allow_big_lds(emb_grad_kernel<32, 2, true>) || allow_big_lds(emb_grad_kernel<64, 0, true>) || allow_big_lds(emb_grad_kernel<64, 1, true>) ||
       allow_big_lds(emb_grad_kernel<64, 2, true>) || allow_big_lds(gemm_tn_kernel<float, 4, 3, 16>) || allow_big_lds(gemm_tn_kernel<float, 4, 3, 32>) ||
-      allow_big_lds(gemm_tn_kernel<float, 3, 4, 32>) || allow_big_lds(gemm_tn_multi_kernel<3, 4, GOCTR_TN_CH>) ||
+      allow_big_lds(gemm_tn_kernel<float, 3, 4, 32>) ||
       allow_big_lds(gemm_tn_multi_x3_kernel<3, 4>) || allow_big_lds(gemm_tn_multi_x3w_kernel<9, 5>) || allow_big_lds(gemm_tn_multi_x3w_kernel<8, 5>) ||
       allow_big_lds(gemm_tn_multi_x3w_att0_kernel<9, 5>) || allow_big_lds(gemm_tn_multi_x3w_att0_kernel<8, 5>) || allow_big_lds(ctr_chain_x3_kernel<2>) || allow_big_lds(ctr_chain_x3_kernel<9>) ||
       allow_big_lds(ctr_chain_x3_kernel<15>) || chain_x3_fwd_attributes() || fwd4_attributes() ||
@@ -679,7 +675,6 @@ int launch_chain_x3(goctr_model* m, const RowSource& src, int B, const StepOpts&
     a.ab_T = c.T; a.ab_Tp = m->Tp;
   }
   a.yhat = fb.yhat; a.lossrow = m->lossrow.p;
-  a.xcd_affine = env_int("GOCTR_XCD_AFFINE", 1);
   // per-tile sums of dW2 and of the att0 terms instead of their operands -- where the wide weight-gradient launch follows (it
   // adds the tiles up; GOCTR_CHAIN_TILE_SUMS=0: the operands are stored and multiplied there, as until round 5)
   const bool tile_sums = o.train && dw_wide_path(m, B) && env_int("GOCTR_CHAIN_TILE_SUMS", 1) != 0;
@@ -851,11 +846,11 @@ FwdBufs train_bufs(goctr_model* m, int par) { return FwdBufs{m->h0.p, m->gate_p(
 // tail (DIN, frozen embeddings, id mode, the bf16-split chain: launch_chain_x3's attn_bwd_in_chain, which this predicate implies), the
 // attention forward leaves the one factor (g (1 - g)) w that backward multiplies with (AttnArgs::fac) instead of the two arrays.  The
 // producer -- the step's own attention launch, or the previous step's last launch -- and the consumer evaluate this with the same
-// (model, rows, options, batch); a start carried over from another call compares H0Carry::fac.  GOCTR_GATE_FAC=0: both arrays.
+// (model, rows, options, batch); a start carried over from another call compares H0Carry::fac.
 bool gate_fac_mode(const goctr_model* m, const RowSource& src, const StepOpts& o, int B) {
   const goctr_ctr_cfg& c = m->cfg;
   return o.train && c.kind == GOCTR_DIN && src.id_mode && m->emb_lr <= 0.f && c.D == 16 && c.T <= 64 && chain_ok(m) &&
-         chain_x3_ok(m, o, B) && env_int("GOCTR_CHAIN_ATTN_BWD", 1) != 0 && env_int("GOCTR_GATE_FAC", 1) != 0;
+         chain_x3_ok(m, o, B) && env_int("GOCTR_CHAIN_ATTN_BWD", 1) != 0;
 }
 // fac: gate_fac_mode() of the step that will consume the launch's rows
 AttnArgs make_attn_args(goctr_model* m, const RowSource& src, int B, const StepState* st, const FwdBufs& fb, bool fac) {
@@ -864,7 +859,6 @@ AttnArgs make_attn_args(goctr_model* m, const RowSource& src, int B, const StepS
   aa.src = src; aa.st = st; aa.B = B; aa.U = c.U; aa.T = c.T; aa.D = c.D; aa.C = c.C; aa.Ip = m->Ip;
   aa.kind = c.kind; aa.att = c.att; aa.att0 = m->W.p + m->offa; aa.h0 = fb.h0; aa.gate = fb.gate; aa.wgt = fb.wgt;
   aa.Tp_att = m->Tp;
-  aa.xcd_affine = env_int("GOCTR_XCD_AFFINE", 1);      // (ctr_kernels.h xcd_unit_of_block; a permutation of the workgroups' samples)
   aa.inv_T = 1.0f / (float)c.T;
   if (fac && fb.fac) { aa.fac = fb.fac; aa.gate = nullptr; aa.wgt = nullptr; }
   return aa;
@@ -1447,18 +1441,17 @@ int launch_backward(goctr_model* m, const RowSource& src, int B, const StepOpts&
   }
 
   // weight gradients: all GEMMs in one launch; dW1 and dW2 are posed transposed, datt0 is a ones-column
-  // product over the per-sample terms (see mfma_gemm.h: gemm_tn_multi_kernel)
+  // product over the per-sample terms (see mfma_gemm.h: gemm_tn_multi_x3_kernel)
   int nt_max = m->H1p / 16;
   if (m->H2p / 16 > nt_max) nt_max = m->H2p / 16;
   if (c.kind == GOCTR_DIN && m->Tp / 16 > nt_max) nt_max = m->Tp / 16;
-  const bool multi = nt_max <= 16 && gemm_tn_multi_fits<3, GOCTR_TN_CH>(nt_max);
-  const TnWide tw = (multi && GOCTR_TN_CH == 32)
-                        ? tn_schedule_wide(m, B, (m->dw2_from_chain ? 1 : 0) + (m->att0_from_chain ? 1 : 0)) : TnWide{};
+  const bool multi = gemm_tn_multi_fits(nt_max);
+  const TnWide tw = multi ? tn_schedule_wide(m, B, (m->dw2_from_chain ? 1 : 0) + (m->att0_from_chain ? 1 : 0)) : TnWide{};
   int S0 = S, S1 = S, SLx = SL;      // slabs per segment, for the reduce below
   int SL2x = -1, SL3x = -1;          // (wide launch: the dW2 / att0 segments' own slab counts)
   if (multi && tw.ok) {
     TnMulti tm{};
-    tm.M = B; tm.np = 3; tm.wt = env_int("GOCTR_TN_WT", 2);
+    tm.M = B; tm.np = 3;
     const int b0 = tw.kblocks0 * 2 * tw.S0, b1 = 2 * tw.S1;
     tm.p[0] = {m->h0.p, m->Ip, m->Ip / 16, m->dz0.p, m->H1p, m->H1p / 16, m->slabs0.p,
                (unsigned long long)m->Ip * m->H1p, 0, m->H1p, 0, tw.rows0, tw.S0, 2, tw.nbt};
@@ -1479,9 +1472,9 @@ int launch_backward(goctr_model* m, const RowSource& src, int B, const StepOpts&
     int nblk = b0 + b1 + SL2;
     // att0's update inside this launch (ctr_chain_x3.h att0_early_body): the single-GPU pipelined step with the per-tile sums of the
     // att0 terms, where the step's last launch also runs the next batch's attention -- which then needs no flag (launch_reduce_part).
-    // GOCTR_ATT0_EARLY=0: the sum problem below + the reduce block + the flag, as until round 6's last session.
+    // Other steps: the sum problem below + the reduce block + the flag.
     m->att0_early = c.kind == GOCTR_DIN && m->att0_from_chain && o.pipelined && fuse_update && stage == 0 && !e.comm_active() &&
-                    m->Tp % 32 == 0 && env_int("GOCTR_ATT0_EARLY", 1) != 0;
+                    m->Tp % 32 == 0;
     Att0EarlyArgs ae{};
     if (m->att0_early) {
       ae.tile_att0 = m->tile_att0.p; ae.ntiles = ntiles; ae.Tp = m->Tp; ae.tps = tps; ae.nslabs = (int)cdiv(ntiles, tps);
@@ -1544,19 +1537,14 @@ int launch_backward(goctr_model* m, const RowSource& src, int B, const StepOpts&
       tm.np = 4;
       nblk += SL;
     }
-    const size_t lds_tm = gemm_tn_multi_lds_bytes<3, 4, GOCTR_TN_CH>(nt_max);
     static DevBuf<unsigned long long> tndbg;
     const bool dbg = dbg_on("tn");
     if (dbg && !tndbg.p && tndbg.alloc(16)) return -1;
     tm.dbg = dbg ? tndbg.p : nullptr;
     {
       ProfScope ps(GOCTR_K_DW0);
-      if (ps.on) prof_note_kernel(GOCTR_K_DW0, (GOCTR_TN_CH == 32) ? "gemm_tn_multi_x3_kernel<3,4>" : "gemm_tn_multi_kernel<3,4,32>");
-      // default: the 6-product bf16 split (mfma_gemm.h); GOCTR_TN_F32=1 selects the v_mfma_f32_16x16x4_f32 body
-      if (GOCTR_TN_CH == 32)
-        hipLaunchKernelGGL((gemm_tn_multi_x3_kernel<3, 4>), dim3((unsigned)nblk), dim3(512), gemm_tn_multi_x3_lds_bytes<3>(nt_max), e.stream, tm);
-      else
-        hipLaunchKernelGGL((gemm_tn_multi_kernel<3, 4, GOCTR_TN_CH>), dim3((unsigned)nblk), dim3(256), lds_tm, e.stream, tm);
+      if (ps.on) prof_note_kernel(GOCTR_K_DW0, "gemm_tn_multi_x3_kernel<3,4>");
+      hipLaunchKernelGGL((gemm_tn_multi_x3_kernel<3, 4>), dim3((unsigned)nblk), dim3(512), gemm_tn_multi_x3_lds_bytes<3>(nt_max), e.stream, tm);
       GOCTR_HIP(hipGetLastError());
     }
     if (dbg) {
@@ -1565,13 +1553,6 @@ int launch_backward(goctr_model* m, const RowSource& src, int B, const StepOpts&
       fprintf(stderr, "dW x3 wg 0: multiplier wave: wait for chunk 0 %lld, in MFMA sections %lld, loop total %lld, epilogue %lld | stager wave: first chunk %lld, "
               "staging sections %lld, total %lld, chunks %lld (s_memtime ticks)\n", (long long)h[0], (long long)h[1], (long long)h[2], (long long)h[3],
               (long long)h[8], (long long)h[9], (long long)h[10], (long long)h[11]);
-    } else if (dbg) {
-      unsigned long long h[16];
-      if (tndbg.download(h, 16)) return -1;
-      for (int w = 0; w < 2; ++w)
-        fprintf(stderr, "dW wg %s: rows %d S %d nblk %d | prologue %lld, first chunk mma %lld, loop %lld, epilogue %lld, total %lld\n",
-                w ? "last" : "0", rpw, S, nblk, (long long)(h[8 * w + 1] - h[8 * w]), (long long)(h[8 * w + 2] - h[8 * w + 1]),
-                (long long)(h[8 * w + 3] - h[8 * w + 1]), (long long)(h[8 * w + 4] - h[8 * w + 3]), (long long)(h[8 * w + 4] - h[8 * w]));
     }
   } else {
     if (launch_tn(GOCTR_K_DW0, m->h0.p, m->Ip, m->Ip / 16, m->dz0.p, m->H1p, m->H1p / 16, B, rpw, m->slabs0.p,

@@ -62,7 +62,6 @@ struct ChainX3Args {
   // dz2[row] (then A1 and dz2 are not stored at all), tile_att0 [tiles][ab_Tp] = the tile's sum of the att0 terms (then ab_out is
   // not stored).  The weight-gradient launch adds the tiles up (mfma_gemm.h tn_tile_sum_body).
   float* tile_dw2; float* tile_att0;
-  int xcd_affine;     // training launches: workgroup -> tile by xcd_unit_of_block (GOCTR_XCD_AFFINE=0: workgroup b takes tile b)
 };
 
 constexpr int CX_NSTAMP = 16;
@@ -72,13 +71,6 @@ inline size_t chain_x3_lds_bytes() {
   // h0 fragment image | Z1 / dp exchange (8 partials) | dz1 fragment image | z2 partials
   return (size_t)NCH0 * 3 * 1024 + (size_t)8 * CX_NU * 4 * 1024 + (size_t)CX_NCH2 * 3 * 1024 + 8 * 32 * 4;
 }
-
-// Experiment switches of scripts/ubench/chain_x3_bench.hip (never set in the library build): CX_EXP bit 0 = no A-operand
-// loads after the first ring fill, bit 1 = no jobs under the MFMAs, bit 2 = no MFMAs.  Results are wrong, timings tell
-// which resource bounds a phase.
-#ifndef CX_EXP
-#define CX_EXP 0
-#endif
 
 // 6-product bf16-split MFMA step for one 32x32x16 block: ah += hi*hi ; ac += everything else (smallest terms first)
 #define CX_MMA6(AH, AC, A, B)                                                         \
@@ -90,10 +82,6 @@ inline size_t chain_x3_lds_bytes() {
     AC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[0], B[1], AC, 0, 0, 0);            \
     AH = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[0], B[0], AH, 0, 0, 0);            \
   } while (0)
-#if CX_EXP & 4
-#undef CX_MMA6
-#define CX_MMA6(AH, AC, A, B) do { AC[0] += (float)A[0][0] + (float)B[1][1]; AH[1] += (float)A[2][0] + (float)B[0][1] + (float)A[1][3] + (float)B[2][2]; } while (0)
-#endif
 
 // 8 consecutive accumulator values -> the three planes of one B-operand fragment (slot s = position)
 __device__ __forceinline__ void cx_split8(const float* v, cx_bf8 (&out)[3]) {
@@ -249,7 +237,7 @@ __global__ __launch_bounds__(512, 1) void ctr_chain_x3_kernel(ChainX3Args a) {
   // (FWD: the persistent workgroup's k-th tile is that of "workgroup" blockIdx + k * gridDim -- the same XCD when the grid is a
   // multiple of 8)
   int vblk = (int)blockIdx.x;
-  int tile = a.xcd_affine ? xcd_unit_of_block(vblk, ntiles, 4) : vblk;
+  int tile = xcd_unit_of_block(vblk, ntiles, 4);
   const int tile_first = tile;
   int row = tile * 32 + n;
   bool vrow = row < a.B;
@@ -275,7 +263,6 @@ __global__ __launch_bounds__(512, 1) void ctr_chain_x3_kernel(ChainX3Args a) {
 #pragma unroll
     for (int cq = 0; cq < NHQ; ++cq) {
       const int c = cq * 8 + w < NCH0 ? cq * 8 + w : NCH0 - 1;
-      if (CX_EXP & 8) { hv[cq][0] = cx_f4{(float)c, 1.f, (float)lane, 2.f}; hv[cq][1] = hv[cq][0]; continue; }   // (experiment: no h0 loads)
       hv[cq][0] = *reinterpret_cast<const cx_f4*>(hp + c * 16);
       hv[cq][1] = *reinterpret_cast<const cx_f4*>(hp + c * 16 + 4);
     }
@@ -407,7 +394,7 @@ __global__ __launch_bounds__(512, 1) void ctr_chain_x3_kernel(ChainX3Args a) {
     for (int p = 0; p < 3; ++p) bf[p] = *reinterpret_cast<const cx_bf8*>(h0img + ((size_t)(c * 3 + p) * 64 + lane) * 16);
 #pragma unroll
     for (int p = 0; p < 3; ++p) af[p] = __builtin_bit_cast(cx_bf8, ra0[c % CX_PF0][p]);
-    if (!(CX_EXP & 1) && c + CX_PF0 < NCH0) load0(c + CX_PF0, c % CX_PF0);
+    if (c + CX_PF0 < NCH0) load0(c + CX_PF0, c % CX_PF0);
     else if (c + CX_PF0 - NCH0 < 2 * CX_NU) load1_piece(c + CX_PF0 - NCH0);
     CX_MMA6(ah0, ac0, af, bf);
     if (ab) {
@@ -417,10 +404,8 @@ __global__ __launch_bounds__(512, 1) void ctr_chain_x3_kernel(ChainX3Args a) {
 #pragma unroll
       for (int k = (c - C0) * PER; c >= C0 && k < (c - C0 + 1) * PER && k < NE; ++k) cx_ab_gather_one(a, abid, lane, k >> 2, k & 3, abx);
     }
-    if (!(CX_EXP & 2)) {
 #pragma unroll
-      for (int e = c * QDRAW; e < (c + 1) * QDRAW && e < 24; ++e) draw_job(e);
-    }
+    for (int e = c * QDRAW; e < (c + 1) * QDRAW && e < 24; ++e) draw_job(e);
     // keep this chunk's draws with this chunk's MFMAs (instruction selection otherwise sinks them all behind the last
     // MFMA, where nothing hides them): the empty asm makes the bits so far an input of an ordered statement
     asm volatile("" : "+v"(dr0.bits), "+v"(dr1.bits));
@@ -494,7 +479,7 @@ __global__ __launch_bounds__(512, 1) void ctr_chain_x3_kernel(ChainX3Args a) {
     // accumulators have just left for LDS.  In program order BEHIND every other load of this trip (the output unit's weights
     // are fetched before the loop): a wait for an earlier load never waits for these
     vblk += (int)gridDim.x;
-    next_tile = vblk < ntiles ? (a.xcd_affine ? xcd_unit_of_block(vblk, ntiles, 4) : vblk) : ntiles;
+    next_tile = vblk < ntiles ? xcd_unit_of_block(vblk, ntiles, 4) : ntiles;
     if (next_tile < ntiles) {
       const int nrow = next_tile * 32 + n;
       load_hv(nrow < a.B ? nrow : a.B - 1);

@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256, 2) void ctr_fwd4_kernel(ChainX3Args a) {
   int n = lane & 31, h = lane >> 5;             // (not const: laundered per trip of the tile loop)
   const int ntiles = (a.B + 31) >> 5;
   int vblk = (int)blockIdx.x;
-  int tile = a.xcd_affine ? xcd_unit_of_block(vblk, ntiles, 4) : vblk;
+  int tile = xcd_unit_of_block(vblk, ntiles, 4);
   const int tile_first = tile;
   int row = tile * 32 + n;
   bool vrow = row < a.B;
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(256, 2) void ctr_fwd4_kernel(ChainX3Args a) {
     // the next tile's rows and first weight chunks (workgroup-uniform branch), in program order behind every other load
     auto prefetch_next = [&]() {
       vblk += (int)gridDim.x;
-      next_tile = vblk < ntiles ? (a.xcd_affine ? xcd_unit_of_block(vblk, ntiles, 4) : vblk) : ntiles;
+      next_tile = vblk < ntiles ? xcd_unit_of_block(vblk, ntiles, 4) : ntiles;
       if (next_tile < ntiles) {
         const int nrow = next_tile * 32 + n;
         load_hv(nrow < a.B ? nrow : a.B - 1);

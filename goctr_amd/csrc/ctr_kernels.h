@@ -107,7 +107,6 @@ struct AttnArgs {
   // are not written: 2 x 1.6 MB less written by this launch and read by the chain launch at cfg3
   float* fac;
   int Tp_att;   // (reduce_attn_kernel) padded length of the att0 segment of the flat parameter buffer
-  int xcd_affine;   // training launches: workgroup -> four-sample group by xcd_unit_of_block (below)
   float inv_T;      // 1.0f / (float)T, computed once on the host (the same IEEE division the kernels did per sample)
 };
 
@@ -473,7 +472,7 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a, int blk, long l
 
 template <int VEC, int LPR, int FAST>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
-  const int grp = a.xcd_affine ? xcd_unit_of_block((int)blockIdx.x, (a.B + 3) >> 2, 32) : (int)blockIdx.x;
+  const int grp = xcd_unit_of_block((int)blockIdx.x, (a.B + 3) >> 2, 32);
   attn_fwd_body<VEC, LPR, FAST>(a, grp, a.st->batch_idx, a.att0);
 }
 // serving passes: the rows come from (user, item, timestamp) keys (RowSource key mode) -- key assembly and attention in one launch
@@ -959,7 +958,7 @@ __global__ __launch_bounds__(256) void reduce_attn_kernel(ReduceAdamArgs p, Attn
   long long nb = r.st->batch_idx + 1;                          // advance_state()'s cursor
   if (nb >= r.st->n_batches) nb = 0;
   const RaCtx ctx{p.ra_flag, r.st->gstep + 1u, a.att0};
-  const int grp = a.xcd_affine ? xcd_unit_of_block_after((int)blockIdx.x, nred, (a.B + 3) >> 2, 32) : (int)blockIdx.x - nred;
+  const int grp = xcd_unit_of_block_after((int)blockIdx.x, nred, (a.B + 3) >> 2, 32);
   attn_fwd_body<VEC, LPR, FAST>(a, grp, nb, a.att0, FAST >= 2 ? &ctx : nullptr);      // (ctx.flag == null: att0 is already this step's, no wait)
 }
 
@@ -1006,7 +1005,7 @@ __global__ __launch_bounds__(256) void adam_attn_kernel(AdamArgs ad, unsigned in
     return;
   }
   const RaCtx ctx{ra_flag, ad.st->gstep, a.att0};
-  const int grp = a.xcd_affine ? xcd_unit_of_block_after(bi, nadam, (a.B + 3) >> 2, 32) : bi - nadam;
+  const int grp = xcd_unit_of_block_after(bi, nadam, (a.B + 3) >> 2, 32);
   attn_fwd_body<VEC, LPR, FAST>(a, grp, ad.st->batch_idx, a.att0, FAST >= 2 ? &ctx : nullptr);
 }
 

@@ -423,191 +423,16 @@ struct TnProblem {
   int nnb;     // (x3 wide blocks) n-blocks per k-block: the D tiles are split into nnb groups of nbt tiles; 0 = one group
   int nbt;
 };
-// wt (bf16-split bodies): slab stores go THROUGH the L2 (global_store ... sc1) instead of staying dirty in it until the launch
-// ends -- 1: the 16-byte stores of the transposed problems, 2: also the 4-byte stores of the untransposed ones
-struct TnMulti { TnProblem p[4]; int np; int M; unsigned long long* dbg; int wt; };
-
-// The multi-problem weight-gradient kernel.  Per workgroup: one problem, one block of KTW (3, or 1 for the
-// one-tile problems) 16-column tiles of A, ALL 16-column tiles of D split NTW = 4 per wavefront, one slab of
-// rows_per_wg batch rows.  The reduction index of  slab[k][n] = sum_m A[m][k] * D[m][n]  is the ROW of both
-// operands, so the staging transposes: a thread loads a 4-row x 4-column block (4 coalesced 16-byte loads),
-// and writes it as 4 ds_write_b128 into column-major LDS strips T[col][m] (row stride CH + 4 floats = 16 B
-// mod 128 B: the 16 lanes of a q-group read distinct bank groups).  One ds_read_b128 then holds the 4 rows a
-// lane feeds to 4 consecutive MFMAs: 7 LDS instructions per 48 MFMAs instead of 7 per 12 (on gfx950 every
-// LDS return stalls the fp32 MFMA stream of its SIMD, scripts/ubench/mfma_dma_overlap.hip).
-template <int KTW, int NTW, int CH>
-__device__ __forceinline__ void tn_multi_body(const TnMulti& a, const TnProblem& P, int kb, int split, unsigned char* smem) {
-  using MF = Mfma<float>;
-  typedef float acc_t __attribute__((ext_vector_type(4)));
-  typedef float vec_t __attribute__((ext_vector_type(4)));
-  constexpr int CHS = CH + 4;            // LDS floats per strip column
-  constexpr int MAXB = ((CH / 4) * (KTW * 4 + 16 * 4) + 255) / 256;   // 4x4 staging blocks per thread and chunk (NT <= 16)
-  const int kb0 = kb * KTW;
-  int kb_t = P.KT - kb0; if (kb_t > KTW) kb_t = KTW;
-  const int nb_t = P.NT;                 // <= 4*NTW (host-checked)
-  const int Kc = kb_t * 16, Nc = nb_t * 16;
-  const int kv = Kc >> 2, nv = Nc >> 2;
-  float* As = reinterpret_cast<float*>(smem);       // [2][KTW*16][CHS]
-  float* Ds = As + 2 * KTW * 16 * CHS;              // [2][Nc][CHS]
-  const int a_buf = KTW * 16 * CHS, d_buf = Nc * CHS;
-
-  const int tid = threadIdx.x, lane = tid & 63, wn = tid >> 6;
-  const int i = lane & 15, q = lane >> 4;
-  const int nt0 = wn * NTW;
-  int ncnt = nb_t - nt0; ncnt = ncnt < 0 ? 0 : (ncnt > NTW ? NTW : ncnt);
-  const int m_begin = split * P.rows;
-  int m_end = m_begin + P.rows;
-  if (m_end > a.M) m_end = a.M;
-
-  acc_t acc[KTW][NTW];
-#pragma unroll
-  for (int e = 0; e < KTW; ++e)
-#pragma unroll
-    for (int f = 0; f < NTW; ++f) acc[e][f] = acc_t{0, 0, 0, 0};
-
-  // staging slots of this thread: block b = tid + 256 s  ->  (strip, row group rg, column group cg)
-  const int nA = (CH / 4) * kv, nAll = nA + (CH / 4) * nv;
-  const float* gsrc[MAXB]; int ld[MAXB]; int rg[MAXB]; int lofs[MAXB];   // lofs < 0: slot unused
-  {
-    const float rkv = 1.0f / (float)kv, rnv = 1.0f / (float)nv;
-#pragma unroll
-    for (int s = 0; s < MAXB; ++s) {
-      const int b = tid + s * 256;
-      gsrc[s] = P.A; ld[s] = P.lda; rg[s] = 0; lofs[s] = -1;
-      if (b < nA) {
-        const int r = (int)(((float)b + 0.5f) * rkv), cg = b - r * kv;       // exact for b < 2^20
-        rg[s] = r; ld[s] = P.lda;
-        gsrc[s] = P.A + kb0 * 16 + cg * 4;
-        lofs[s] = (cg * 4) * CHS + 4 * r;
-      } else if (b < nAll) {
-        const int bb = b - nA;
-        const int r = (int)(((float)bb + 0.5f) * rnv), cg = bb - r * nv;
-        rg[s] = r; ld[s] = P.ldd;
-        gsrc[s] = P.D + cg * 4;
-        lofs[s] = 2 * a_buf + (cg * 4) * CHS + 4 * r;                         // relative to As
-      }
-    }
-  }
-  // Loads are unconditional (rows past the slab's end re-read its last row and are zeroed when the block is
-  // written to LDS): no predicate, no register merge, hence no s_waitcnt between the loads of a chunk.
-  vec_t st[MAXB][4];
-  auto gload = [&](int m0) {
-#pragma unroll
-    for (int s = 0; s < MAXB; ++s) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int rr = m0 + 4 * rg[s] + r;
-        rr = rr < m_end ? rr : m_end - 1;
-        st[s][r] = *reinterpret_cast<const vec_t*>(gsrc[s] + (size_t)rr * ld[s]);
-      }
-    }
-  };
-  auto lstore = [&](int buf, int m0) {
-#pragma unroll
-    for (int s = 0; s < MAXB; ++s) {
-      if (lofs[s] >= 0) {
-        float* d = As + lofs[s] + (lofs[s] >= 2 * a_buf ? buf * d_buf : buf * a_buf);
-        if (m0 + CH <= m_end) {                      // whole chunk inside the slab (wave-uniform)
-#pragma unroll
-          for (int c = 0; c < 4; ++c)
-            *reinterpret_cast<vec_t*>(d + c * CHS) = vec_t{st[s][0][c], st[s][1][c], st[s][2][c], st[s][3][c]};
-        } else {
-          const int left = m_end - (m0 + 4 * rg[s]);   // rows of this block that exist
-#pragma unroll
-          for (int c = 0; c < 4; ++c)
-            *reinterpret_cast<vec_t*>(d + c * CHS) = vec_t{left > 0 ? st[s][0][c] : 0.f, left > 1 ? st[s][1][c] : 0.f,
-                                                           left > 2 ? st[s][2][c] : 0.f, left > 3 ? st[s][3][c] : 0.f};
-        }
-      }
-    }
-  };
-  // per-lane LDS offsets of the operand columns (tiles past the problem's edge re-read the last column)
-  int aofs[KTW], dofs[NTW];
-#pragma unroll
-  for (int e = 0; e < KTW; ++e) { int c = e * 16 + i; c = c < Kc ? c : Kc - 1; aofs[e] = c * CHS + 4 * q; }
-#pragma unroll
-  for (int f = 0; f < NTW; ++f) { int c = (nt0 + f) * 16 + i; c = c < Nc ? c : Nc - 1; dofs[f] = c * CHS + 4 * q; }
-
-  unsigned long long ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0, tsm = 0;
-  if (a.dbg) ts0 = __builtin_amdgcn_s_memtime();
-  if (m_begin < m_end) {
-    gload(m_begin);
-    lstore(0, m_begin);
-    __syncthreads();
-    if (a.dbg) ts1 = __builtin_amdgcn_s_memtime();
-    int buf = 0;
-    for (int m0 = m_begin; m0 < m_end; m0 += CH) {
-      const bool more = m0 + CH < m_end;
-      if (more) gload(m0 + CH);
-      const float* as = As + buf * a_buf;
-      const float* ds = Ds + buf * d_buf;
-#pragma unroll
-      for (int g = 0; g < CH / 16; ++g) {
-        vec_t av[KTW], dv[NTW];
-#pragma unroll
-        for (int e = 0; e < KTW; ++e) av[e] = *reinterpret_cast<const vec_t*>(as + aofs[e] + g * 16);
-#pragma unroll
-        for (int f = 0; f < NTW; ++f) dv[f] = *reinterpret_cast<const vec_t*>(ds + dofs[f] + g * 16);
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-          for (int e = 0; e < KTW; ++e)
-#pragma unroll
-            for (int f = 0; f < NTW; ++f) acc[e][f] = MF::mma(av[e][r], dv[f][r], acc[e][f]);
-      }
-      if (a.dbg && m0 == m_begin) tsm = __builtin_amdgcn_s_memtime();
-      if (more) lstore(buf ^ 1, m0 + CH);
-      __syncthreads();
-      buf ^= 1;
-    }
-  }
-
-  if (a.dbg) ts2 = __builtin_amdgcn_s_memtime();
-  float* out = P.slabs + (size_t)split * P.slab_stride;
-#pragma unroll
-  for (int e = 0; e < KTW; ++e) {
-#pragma unroll
-    for (int f = 0; f < NTW; ++f) {
-      if (e < kb_t && f < ncnt) {
-        const int k = (kb0 + e) * 16 + 4 * q, n = (nt0 + f) * 16 + i;
-        if (P.transpose_out) {
-          *reinterpret_cast<acc_t*>(out + (size_t)n * P.ld_out + k) = acc[e][f];
-        } else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) out[(size_t)(k + r) * P.ld_out + n] = acc[e][f][r];
-        }
-      }
-    }
-  }
-  if (a.dbg && threadIdx.x == 0 && (blockIdx.x == 0 || blockIdx.x == gridDim.x - 1)) {
-    ts3 = __builtin_amdgcn_s_memtime();
-    unsigned long long* d = a.dbg + (blockIdx.x == 0 ? 0 : 8);
-    d[0] = ts0; d[1] = ts1; d[2] = tsm; d[3] = ts2; d[4] = ts3;
-  }
-}
-
-template <int KTW, int NTW, int CH>
-__global__ __launch_bounds__(256, 2) void gemm_tn_multi_kernel(TnMulti a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char goctr_smem[];
-  int pi = 0;
-#pragma unroll
-  for (int k = 1; k < 4; ++k) if (k < a.np && (int)blockIdx.x >= a.p[k].first) pi = k;
-  const TnProblem& P = a.p[pi];
-  const int local = blockIdx.x - P.first;
-  const int kb = local / P.S, split = local - kb * P.S;
-  if (P.KT == 1) tn_multi_body<1, NTW, CH>(a, P, kb, split, goctr_smem);   // one-tile problems: a third of the MFMAs
-  else tn_multi_body<KTW, NTW, CH>(a, P, kb, split, goctr_smem);
-}
-// LDS bytes for problems whose widest D operand has nt_max 16-column tiles
-template <int KTW, int NTW, int CH>
-inline size_t gemm_tn_multi_lds_bytes(int nt_max) {
-  return sizeof(float) * 2 * (CH + 4) * (size_t)(KTW * 16 + nt_max * 16);
-}
-template <int KTW, int CH>
+struct TnMulti { TnProblem p[4]; int np; int M; unsigned long long* dbg; };
+// does the multi-problem launch take problems whose widest D operand has nt_max 16-column tiles?
 inline bool gemm_tn_multi_fits(int nt_max) { return nt_max <= 16; }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The same weight-gradient kernel on the 6-product bf16 split (scripts/ubench/bf16x3.hip): every float32
+// The multi-problem weight-gradient kernel.  Per workgroup: one problem, one block of KTW 16-column tiles of A, a group of
+// 16-column tiles of D split NTW per multiplying wavefront, one slab of `rows` batch rows.  The reduction index of
+// slab[k][n] = sum_m A[m][k] * D[m][n]  is the ROW of both operands, so the staging transposes: a thread loads a 4-row x
+// 4-column block (4 coalesced 16-byte loads) and writes it into column-major LDS strips T[col][m].
+// Arithmetic: the 6-product bf16 split (scripts/ubench/bf16x3.hip): every float32
 // operand value x is staged as three bf16 planes  x = hi + mid + lo  (each the round-to-nearest-even bf16 of what the
 // previous ones left), and  a*b  is taken as  hi*hi + (hi*mid + mid*hi) + (hi*lo + lo*hi + mid*mid)  on
 // v_mfma_f32_16x16x32_bf16 with float32 accumulation — the dropped terms are below 2^-32 |a b|.  Measured against float64
@@ -632,7 +457,9 @@ __device__ __forceinline__ void tn_split3_pk(float x0, float x1, unsigned int& h
 
 // (n0t, nb_t): the block's D tiles [n0t, n0t + nb_t), nb_t <= 4 * NTW.  KTW > 3 ("wide" blocks, round 2): the A fragments
 // of one tile at a time stream through registers (KTW * NTW * 8 accumulator registers leave no room for all of them).
-template <int KTW, int NTW>
+// WT (the wide launch): every slab store goes THROUGH the L2 (global_store ... sc1) instead of staying dirty in it until the
+// launch ends.
+template <int KTW, int NTW, bool WT>
 __device__ __forceinline__ void tn_multi_body_x3(const TnMulti& a, const TnProblem& P, int kb, int n0t, int nb_t, int split,
                                                  unsigned char* smem) {
   typedef float acc_t __attribute__((ext_vector_type(4)));
@@ -865,11 +692,11 @@ __device__ __forceinline__ void tn_multi_body_x3(const TnMulti& a, const TnProbl
         const acc_t v = ac[e][f] + ah[e][f];
         if (P.transpose_out) {
           const unsigned o = o_t + (unsigned)(f * 16) * ldo + (unsigned)(e * 16);
-          if (a.wt) asm volatile("global_store_dwordx4 %0, %1, %2 sc1" : : "v"(o * 4u), "v"(v), "s"(out) : "memory");
+          if constexpr (WT) asm volatile("global_store_dwordx4 %0, %1, %2 sc1" : : "v"(o * 4u), "v"(v), "s"(out) : "memory");
           else *reinterpret_cast<acc_t*>(out + o) = v;
         } else {
           const unsigned o = o_n + (unsigned)(e * 16) * ldo + (unsigned)(f * 16);
-          if (a.wt >= 2) {
+          if constexpr (WT) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) asm volatile("global_store_dword %0, %1, %2 sc1" : : "v"((o + (unsigned)r * ldo) * 4u), "v"(v[r]), "s"(out) : "memory");
           } else {
@@ -894,8 +721,8 @@ __global__ __launch_bounds__(512) void gemm_tn_multi_x3_kernel(TnMulti a) {
   const TnProblem& P = a.p[pi];
   const int local = blockIdx.x - P.first;
   const int kb = local / P.S, split = local - kb * P.S;
-  if (P.KT == 1) tn_multi_body_x3<1, NTW>(a, P, kb, 0, P.NT, split, goctr_smem);
-  else tn_multi_body_x3<KTW, NTW>(a, P, kb, 0, P.NT, split, goctr_smem);
+  if (P.KT == 1) tn_multi_body_x3<1, NTW, false>(a, P, kb, 0, P.NT, split, goctr_smem);
+  else tn_multi_body_x3<KTW, NTW, false>(a, P, kb, 0, P.NT, split, goctr_smem);
 }
 
 // Round 6: "sum problems" (TnProblem::KT == 0).  Where the chain launch has already summed a gradient over the 32 rows of each of
@@ -944,13 +771,13 @@ __device__ __forceinline__ void tn_multi_x3w_block(const TnMulti& a, unsigned ch
   const int local = blockIdx.x - P.first;
   const int blk = local / P.S, split = local - blk * P.S;
   if (P.KT == 0) { tn_tile_sum_body(a, P, local); return; }
-  if (P.KT == 1) { tn_multi_body_x3<1, 4>(a, P, blk, 0, P.NT, split, goctr_smem); return; }
+  if (P.KT == 1) { tn_multi_body_x3<1, 4, true>(a, P, blk, 0, P.NT, split, goctr_smem); return; }
   const int nnb = P.nnb > 0 ? P.nnb : 1;
   const int kb = blk / nnb, nb = blk - kb * nnb;
   const int n0t = nb * P.nbt;
   int nb_t = P.NT - n0t; if (nb_t > P.nbt) nb_t = P.nbt;
-  if (pi == 0) tn_multi_body_x3<KTW0, 2>(a, P, kb, n0t, nb_t, split, goctr_smem);
-  else tn_multi_body_x3<KTW1, 2>(a, P, kb, n0t, nb_t, split, goctr_smem);
+  if (pi == 0) tn_multi_body_x3<KTW0, 2, true>(a, P, kb, n0t, nb_t, split, goctr_smem);
+  else tn_multi_body_x3<KTW1, 2, true>(a, P, kb, n0t, nb_t, split, goctr_smem);
 }
 template <int KTW0, int KTW1>
 __global__ __launch_bounds__(512) void gemm_tn_multi_x3w_kernel(TnMulti a) {

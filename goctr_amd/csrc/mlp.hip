@@ -958,8 +958,8 @@ __global__ __launch_bounds__(256) void mlp_chain_kernel(MlpChainArgs a) {
   }
 }
 
-// ---------------------------------------------------------------- weight-gradient GEMM, float64 (csrc/mfma_gemm.h
-// gemm_tn_multi_kernel's design with v_mfma_f64_16x16x4_f64):  slab[k][n] = sum over the slab's rows m of
+// ---------------------------------------------------------------- weight-gradient GEMM, float64 (the staging design of
+// csrc/mfma_gemm.h's multi-problem kernel on v_mfma_f64_16x16x4_f64):  slab[k][n] = sum over the slab's rows m of
 // A[m][k] * D[m][n].  Workgroup = one block of 3 16-column tiles of A, all tiles of D (2 per wavefront), one slab of
 // batch rows, in chunks of CH rows: a thread loads 4-row x 4-column blocks with 16-byte loads (unconditional:
 // clamped row, zeroed when written), transposes them in registers and writes the columns as 16-byte stores into

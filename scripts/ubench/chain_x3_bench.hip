@@ -1,6 +1,5 @@
 // Stand-alone timing of ctr_chain_x3_kernel<9> at cfg3 (B = 8192, Ip = 144, H1 = 200, H2 = 80, DIN) with random operands:
-// which resource bounds each phase?  Build variants with -DCX_EXP=n (bit 0: no A loads after the first ring fill, bit 1:
-// no jobs under the MFMAs, bit 2: no MFMAs); prints the kernel's average duration and the s_memtime phase stamps.
+// prints the kernel's average duration and the s_memtime phase stamps of each wavefront.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -44,7 +43,7 @@ int main() {
   hipLaunchKernelGGL(ctr_chain_x3_kernel<9>, dim3(B / 32), dim3(512), lds, 0, a);
   CK(hipDeviceSynchronize());
   unsigned long long h[8][16]; CK(hipMemcpy(h, dbg, sizeof h, hipMemcpyDeviceToHost));
-  printf("CX_EXP=%d: %.2f us/launch (back to back); per wavefront, cycles since the workgroup's first stamp at: b1(h0 image) F0 epi0 F1 b2(Z1 xchg) b4(dz1 image) B0 BP end\n", CX_EXP, ms * 1e3 / N);
+  printf("%.2f us/launch (back to back); per wavefront, cycles since the workgroup's first stamp at: b1(h0 image) F0 epi0 F1 b2(Z1 xchg) b4(dz1 image) B0 BP end\n", ms * 1e3 / N);
   unsigned long long t0 = ~0ull;
   for (int w = 0; w < 8; ++w) if (h[w][0] < t0) t0 = h[w][0];
   const int ks[] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9};
