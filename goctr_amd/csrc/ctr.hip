@@ -211,8 +211,9 @@ struct goctr_model {
     EmbPlanView view() const { return EmbPlanView{pair.p, pslot.p, pid.p, pair_off.p, slot_id.p, slot_off.p, slot_base.p}; }
   } plan;
   DevBuf<float> emb_dx, emb_gsum;  // emb_coef's per-pair row gradients [B, T, D] and item-row gradients [B, D]
-  // fixed-size exchange (emb_train.h, end): exact bounds from the plan, no host read-back between the collectives
-  bool ex_fixed = false; int ex_S = 0, ex_R = 0;
+  // fixed-size exchange (emb_train.h, end) of every plan built under a communicator: exact bounds from the plan, no host
+  // read-back between the collectives
+  int ex_S = 0, ex_R = 0;
   DevBuf<int> ex_bucket_off, ex_send_ids, ex_recv_ids; DevBuf<long long> ex_send_rows, ex_recv_rows;
   ReduceArgs pend_ra{};            // launch_backward(stage 1) -> (stage 2)
   bool pend_no_costs = false;      // goctr_train_steps: the caller does not read this call's costs
@@ -474,9 +475,9 @@ int init_kernel_attrs() {
                           allow_big_lds(gemm_nn_rows_kernel<float, E, 4>))
   if (GOCTR_NN_ATTR(EpiSigDrop) || GOCTR_NN_ATTR(EpiOut) || GOCTR_NN_ATTR(EpiDSig) || GOCTR_NN_ATTR(EpiStore) ||
       allow_big_lds(ctr_chain_kernel<7, 5, 0>) || allow_big_lds(ctr_chain_kernel<7, 5, 1>) ||
-      allow_big_lds(ctr_chain_kernel<7, 5, 2>) || allow_big_lds(ctr_fwd16_kernel<4, 5>) || allow_big_lds(emb_grad_kernel<16, 0, true>) || allow_big_lds(emb_grad_kernel<16, 1, true>) || allow_big_lds(emb_grad_kernel<16, 2, true>) || allow_big_lds(emb_grad_kernel<32, 0, true>) ||
-      allow_big_lds(emb_grad_kernel<32, 1, true>) || allow_big_lds(emb_grad_kernel<32, 2, true>) || allow_big_lds(emb_grad_kernel<64, 0, true>) || allow_big_lds(emb_grad_kernel<64, 1, true>) ||
-      allow_big_lds(emb_grad_kernel<64, 2, true>) || allow_big_lds(gemm_tn_kernel<float, 4, 3, 16>) || allow_big_lds(gemm_tn_kernel<float, 4, 3, 32>) ||
+      allow_big_lds(ctr_chain_kernel<7, 5, 2>) || allow_big_lds(ctr_fwd16_kernel<4, 5>) || allow_big_lds(emb_grad_kernel<16, 0>) || allow_big_lds(emb_grad_kernel<16, 1>) || allow_big_lds(emb_grad_kernel<16, 2>) || allow_big_lds(emb_grad_kernel<32, 0>) ||
+      allow_big_lds(emb_grad_kernel<32, 1>) || allow_big_lds(emb_grad_kernel<32, 2>) || allow_big_lds(emb_grad_kernel<64, 0>) || allow_big_lds(emb_grad_kernel<64, 1>) ||
+      allow_big_lds(emb_grad_kernel<64, 2>) || allow_big_lds(gemm_tn_kernel<float, 4, 3, 16>) || allow_big_lds(gemm_tn_kernel<float, 4, 3, 32>) ||
       allow_big_lds(gemm_tn_kernel<float, 3, 4, 32>) ||
       allow_big_lds(gemm_tn_multi_x3_kernel<3, 4>) || allow_big_lds(gemm_tn_multi_x3w_kernel<9, 5>) || allow_big_lds(gemm_tn_multi_x3w_kernel<8, 5>) ||
       allow_big_lds(gemm_tn_multi_x3w_att0_kernel<9, 5>) || allow_big_lds(gemm_tn_multi_x3w_att0_kernel<8, 5>) || allow_big_lds(ctr_chain_x3_kernel<2>) || allow_big_lds(ctr_chain_x3_kernel<9>) ||
@@ -980,16 +981,11 @@ int ensure_emb_workspace(goctr_model* m, long long V, int B) {
   return 0;
 }
 
-template <int GS, bool CACHE>
-void launch_emb_grad2(int mode, dim3 gb, size_t lds, hipStream_t s, const EmbTrainArgs& a, int nslot) {
-  if (mode == 0) hipLaunchKernelGGL((emb_grad_kernel<GS, 0, CACHE>), gb, dim3(EMB_GRAD_THREADS), lds, s, a, nslot);
-  else if (mode == 1) hipLaunchKernelGGL((emb_grad_kernel<GS, 1, CACHE>), gb, dim3(EMB_GRAD_THREADS), lds, s, a, nslot);
-  else hipLaunchKernelGGL((emb_grad_kernel<GS, 2, CACHE>), gb, dim3(EMB_GRAD_THREADS), lds, s, a, nslot);
-}
 template <int GS>
-void launch_emb_grad(int mode, bool cache, dim3 gb, size_t lds, hipStream_t s, const EmbTrainArgs& a, int nslot) {
-  if (cache) launch_emb_grad2<GS, true>(mode, gb, lds, s, a, nslot);
-  else launch_emb_grad2<GS, false>(mode, gb, 0, s, a, nslot);
+void launch_emb_grad(int mode, dim3 gb, size_t lds, hipStream_t s, const EmbTrainArgs& a, int nslot) {
+  if (mode == 0) hipLaunchKernelGGL((emb_grad_kernel<GS, 0>), gb, dim3(EMB_GRAD_THREADS), lds, s, a, nslot);
+  else if (mode == 1) hipLaunchKernelGGL((emb_grad_kernel<GS, 1>), gb, dim3(EMB_GRAD_THREADS), lds, s, a, nslot);
+  else hipLaunchKernelGGL((emb_grad_kernel<GS, 2>), gb, dim3(EMB_GRAD_THREADS), lds, s, a, nslot);
 }
 
 // Sparse embedding update of one step (emb_train.h).  Runs after every reader of the table in this step (attn_fwd,
@@ -1118,8 +1114,7 @@ int ensure_emb_plan(goctr_model* m, const goctr_dataset* d, const RowSource& src
   const long long max_pairs = tot[2], max_slots = tot[3];
   P.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build).count();
   if (c.kind == GOCTR_DIN && (m->emb_dx.ensure((size_t)B * c.T * c.D, false) || m->emb_gsum.ensure((size_t)B * c.D, false))) return -1;
-  m->ex_fixed = false;
-  if (e.comm_active() && env_int("GOCTR_EMB_FIXED_EXCHANGE", 1) != 0) {
+  if (e.comm_active()) {
     // bucket bounds of every batch, the largest bucket over batches, owners AND ranks (one small all-gather, here, once)
     GOCTR_CHECK(W <= 1023, "world %d too large for the bucket kernel", W);
     if (m->ex_bucket_off.alloc((size_t)nb * (W + 1), false)) return -1;
@@ -1145,7 +1140,6 @@ int ensure_emb_plan(goctr_model* m, const goctr_dataset* d, const RowSource& src
         m->ex_red_ids.alloc(std::max<size_t>((size_t)R, 1), false) || m->ex_delta.alloc(std::max<size_t>((size_t)R * c.D, 1), false) ||
         m->ex_gids.alloc(std::max<size_t>(wr, 1), false) || m->ex_gdelta.alloc(std::max<size_t>(wr * c.D, 1), false)) return -1;
     GOCTR_HIP(hipStreamSynchronize(s));
-    m->ex_fixed = true;
     // bytes this rank sends per step: W padded buckets of (id, fixed-point row) + its padded (id, delta) list to every rank
     m->ex_bytes_last = (double)W * S * (4 + 8.0 * c.D) + (double)W * (double)R * (4 + 4.0 * c.D);
   }
@@ -1179,9 +1173,6 @@ bool emb_slot_vec4(const goctr_model* m) {
   const int want = c.kind != GOCTR_DIN ? 4 : 1;
   return (c.D == 16 || c.D == 32 || c.D == 64) && want == 4;
 }
-
-int launch_emb_exchange(goctr_model* m, const EmbTrainArgs& a);
-
 
 // First half of the plan path, in attn_bwd's place in the backward: dpv = dz0 . W0[U:U+2D,:]^T and (DIN) the per-pair
 // coefficients -- the kernel gathers every behaviour row and forms dp . x_t like attn_bwd_kernel, so it writes attn_bwd's
@@ -1239,23 +1230,14 @@ int launch_emb_plan_step(goctr_model* m, const RowSource& src, int B, const Step
     if (rc) return -1;
   }
   if (direct) return 0;
+  // fixed-size buckets: pack the send buffers; the collectives and the owner's side follow from the step driver
+  // (emb_exchange_* below), with no host read-back anywhere
   const int cus = e.compute_units > 0 ? e.compute_units : 256;
-  if (m->ex_fixed) {
-    // fixed-size buckets: pack the send buffers; the collectives and the owner's side follow from the step driver
-    // (emb_exchange_* below), with no host read-back anywhere
-    const long long n = (long long)e.eff_world() * m->ex_S * c.D;
-    hipLaunchKernelGGL(emb_pack_send_kernel, dim3((unsigned)std::min<long long>(std::max<long long>(cdiv(n, 256), 1), 8 * cus)), dim3(256), 0, s,
-                       m->plan.view(), st, m->ex_bucket_off.p, e.eff_world(), m->ex_S, c.D, m->emb_accum.p, m->ex_send_ids.p, m->ex_send_rows.p);
-    GOCTR_HIP(hipGetLastError());
-    return 0;
-  }
-  // data parallel without fixed bounds: the exchange reads the batch's slot -> id list and count from fixed buffers
-  hipLaunchKernelGGL(emb_plan_select_kernel, dim3((unsigned)std::min<long long>(std::max<long long>(cdiv(m->plan.max_slots, 256), 1), 4 * cus)), dim3(256), 0, s,
-                     m->plan.view(), st, m->emb_slot_id.p, m->emb_total.p);
+  const long long n = (long long)e.eff_world() * m->ex_S * c.D;
+  hipLaunchKernelGGL(emb_pack_send_kernel, dim3((unsigned)std::min<long long>(std::max<long long>(cdiv(n, 256), 1), 8 * cus)), dim3(256), 0, s,
+                     m->plan.view(), st, m->ex_bucket_off.p, e.eff_world(), m->ex_S, c.D, m->emb_accum.p, m->ex_send_ids.p, m->ex_send_rows.p);
   GOCTR_HIP(hipGetLastError());
-  EmbTrainArgs ea{};
-  ea.D = c.D; ea.lr = m->emb_lr; ea.emb = const_cast<float*>(src.emb);
-  return launch_emb_exchange(m, ea);
+  return 0;
 }
 
 // Sparse embedding update of one step (emb_train.h).  Runs after every reader of the table in this step (attn_fwd,
@@ -1305,29 +1287,25 @@ int launch_emb_train(goctr_model* m, const RowSource& src, int B, const StepStat
   EpiStore sp{m->dpv.p, Np};
   if (launch_nn(GOCTR_K_EMB_TRAIN, m->dz0.p, m->H1p, m->W0pvT.p, Np, B, m->H1p, Np, sp)) return -1;
   // attention modes: one 1024-thread workgroup per CU (~90 VGPRs allow no second one) with a <= 136 KB LDS cache of hot
-  // rows; mean pooling fits two per CU (GOCTR_EMB_WGS=2, <= 72 KB each) but measured no faster (184 vs 178 us at cfg4)
+  // rows; mean pooling fits two per CU (<= 72 KB each) but measured no faster (184 vs 178 us at cfg4)
   const int mode = c.kind != GOCTR_DIN ? 0 : (c.att == GOCTR_ATT_COSINE ? 1 : 2);
-  const int wg_per_cu = 1;
-  const size_t budget = wg_per_cu > 1 ? 72u * 1024u : 136u * 1024u;
+  // (without the cache every add goes straight to HBM: 5x slower at cfg3 AND at cfg4 -- a Zipfian head is hot in a
+  // 10^7-row vocabulary too)
   int nslot = 1;
-  while ((size_t)nslot * 2 * (c.D * sizeof(long long) + sizeof(int)) <= budget) nslot *= 2;
+  while ((size_t)nslot * 2 * (c.D * sizeof(long long) + sizeof(int)) <= 136u * 1024u) nslot *= 2;
   const size_t lds = (size_t)nslot * (c.D * sizeof(long long) + sizeof(int));
   const int cus = e.compute_units > 0 ? e.compute_units : 256;
-  const dim3 gb((unsigned)std::min<long long>(cdiv(B, EMB_GRAD_THREADS / 64), (long long)wg_per_cu * cus));
-  // GOCTR_EMB_CACHE=0 (experiments) sends every add straight to HBM: 5x slower at cfg3 AND at cfg4 — a Zipfian head is
-  // hot in a 10^7-row vocabulary too
-  const bool cache = true;
-  const dim3 gg = cache ? gb : dim3((unsigned)std::min<long long>(cdiv(B, EMB_GRAD_THREADS / 64), 8 * cus));
+  const dim3 gb((unsigned)std::min<long long>(cdiv(B, EMB_GRAD_THREADS / 64), cus));
   {
     ProfScope ps(GOCTR_K_EMB_GRAD);
     if (ps.on) {
       static char sym[48];
-      snprintf(sym, sizeof sym, "emb_grad_kernel<%d,%d,%s>", c.D <= 16 ? 16 : c.D <= 32 ? 32 : 64, mode, cache ? "true" : "false");
+      snprintf(sym, sizeof sym, "emb_grad_kernel<%d,%d>", c.D <= 16 ? 16 : c.D <= 32 ? 32 : 64, mode);
       prof_note_kernel(GOCTR_K_EMB_GRAD, sym);
     }
-    if (c.D <= 16) launch_emb_grad<16>(mode, cache, gg, lds, s, a, nslot);
-    else if (c.D <= 32) launch_emb_grad<32>(mode, cache, gg, lds, s, a, nslot);
-    else launch_emb_grad<64>(mode, cache, gg, lds, s, a, nslot);
+    if (c.D <= 16) launch_emb_grad<16>(mode, gb, lds, s, a, nslot);
+    else if (c.D <= 32) launch_emb_grad<32>(mode, gb, lds, s, a, nslot);
+    else launch_emb_grad<64>(mode, gb, lds, s, a, nslot);
   }
   if (e.comm_active()) return launch_emb_exchange(m, a);
   ProfScope ps(GOCTR_K_EMB_TRAIN);
@@ -1341,7 +1319,7 @@ int launch_emb_train(goctr_model* m, const RowSource& src, int B, const StepStat
 // ---- the fixed-size exchange of a data-parallel step with trainable embeddings, piece by piece (emb_train.h, end):
 //   [graph 1: forward, backward, plan kernels, emb_pack_send]  ->  emb_exchange_a2a  ->  [graph 2: emb_exchange_owner, slab
 //   reduce]  ->  emb_exchange_gather + the dense all-reduce  ->  [graph 3: emb_exchange_apply, Adam]
-bool emb_split3(const goctr_model* m) { return engine().comm_active() && m->emb_lr > 0.f && m->plan.valid && m->ex_fixed; }
+bool emb_split3(const goctr_model* m) { return engine().comm_active() && m->emb_lr > 0.f && m->plan.valid; }
 // uniform all-to-all: S (id, row) entries to and from every rank
 int emb_exchange_a2a(goctr_model* m) {
   Engine& e = engine();

@@ -178,20 +178,16 @@ constexpr int EMB_GRAD_THREADS = 1024;   // 16 wavefronts share one cache, one w
 
 // MODE: 0 = YouTube mean pooling, 1 = DIN cosine, 2 = DIN euclid — compile-time, like the attention kernels: run-time mode
 // branches inside the unrolled stages put a branch (and a wait) around every shuffle.
-// CACHE: false = no LDS staging (vocabularies much larger than the batch: almost every lookup would miss, and the
-// claim + broadcast per slot is pure overhead)
-template <int GS, int MODE, bool CACHE>
+template <int GS, int MODE>
 __global__ __launch_bounds__(EMB_GRAD_THREADS) void emb_grad_kernel(EmbTrainArgs a, int nslot) {
   extern __shared__ __attribute__((aligned(16))) unsigned char emb_smem[];
   EmbCache c;
   c.nslot = nslot;
   c.acc = (emb_lds_u64*)emb_smem;
   c.tag = (emb_lds_int*)(emb_smem + (size_t)nslot * a.D * sizeof(long long));
-  if (CACHE) {
-    for (int i = threadIdx.x; i < nslot * a.D; i += EMB_GRAD_THREADS) c.acc[i] = 0;
-    for (int i = threadIdx.x; i < nslot; i += EMB_GRAD_THREADS) c.tag[i] = -1;
-    __syncthreads();
-  }
+  for (int i = threadIdx.x; i < nslot * a.D; i += EMB_GRAD_THREADS) c.acc[i] = 0;
+  for (int i = threadIdx.x; i < nslot; i += EMB_GRAD_THREADS) c.tag[i] = -1;
+  __syncthreads();
   constexpr int NG = 64 / GS;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l = lane % GS, grp = lane / GS;
@@ -259,7 +255,7 @@ __global__ __launch_bounds__(EMB_GRAD_THREADS) void emb_grad_kernel(EmbTrainArgs
           const bool in = sl < 64 && tb + sl < T;
           g[k] = (din && in) ? a.gate[(size_t)b * T + tb + sl] : 1.0f;
           att[k] = (din && in) ? a.att0[tb + sl] : 0.f;
-          tag[k] = (CACHE && l == 0 && ids[k] >= 0 && mk[k] == 0u && !(a.dbg & 32)) ? emb_cache_claim(c, emb_cache_slot(c, ids[k]), ids[k]) : -1;
+          tag[k] = (l == 0 && ids[k] >= 0 && mk[k] == 0u && !(a.dbg & 32)) ? emb_cache_claim(c, emb_cache_slot(c, ids[k]), ids[k]) : -1;
           const float df = xs[k] - v;
           s0[k] = dp * xs[k];
           s1[k] = cosine ? xs[k] * xs[k] : (act ? df * df : 0.f);
@@ -274,7 +270,7 @@ __global__ __launch_bounds__(EMB_GRAD_THREADS) void emb_grad_kernel(EmbTrainArgs
           }
         }
 #pragma unroll
-        for (int k = 0; k < PASS; ++k) tag[k] = CACHE ? emb_group_sum_int<GS>(l == 0 ? tag[k] + 1 : 0) - 1 : -1;   // broadcast of the group's lane 0
+        for (int k = 0; k < PASS; ++k) tag[k] = emb_group_sum_int<GS>(l == 0 ? tag[k] + 1 : 0) - 1;   // broadcast of the group's lane 0
 #pragma unroll
         for (int k = 0; k < PASS; ++k) {
           const int id = ids[k];
@@ -314,8 +310,8 @@ __global__ __launch_bounds__(EMB_GRAD_THREADS) void emb_grad_kernel(EmbTrainArgs
     if (grp == 0 && item_ok) {
       const bool single = a.mark[emb_pidx(a, item)] != 0u;
       const unsigned int slot = emb_cache_slot(c, item);
-      int tg = (CACHE && l == 0 && !single) ? emb_cache_claim(c, slot, item) : -1;
-      if (CACHE) tg = emb_group_sum_int<GS>(l == 0 ? tg + 1 : 0) - 1;
+      int tg = (l == 0 && !single) ? emb_cache_claim(c, slot, item) : -1;
+      tg = emb_group_sum_int<GS>(l == 0 ? tg + 1 : 0) - 1;
       if (act) {
         const float gsum = dv + a.dpv[(size_t)b * a.ldp + D + l];
         if (single) emb_apply_single(a, item, l, v, gsum);
@@ -323,7 +319,6 @@ __global__ __launch_bounds__(EMB_GRAD_THREADS) void emb_grad_kernel(EmbTrainArgs
       }
     }
   }
-  if (!CACHE) return;
   __syncthreads();
   // flush the cached rows: one HBM atomic per (row, component) per workgroup
   for (int i = threadIdx.x; i < nslot * D; i += EMB_GRAD_THREADS) {
@@ -727,14 +722,6 @@ __global__ __launch_bounds__(256) void emb_span_apply_kernel(EmbSlotArgs a, long
   const long long q = a.accum[(long long)s * D + l];
   a.accum[(long long)s * D + l] = 0;
   if (q) a.emb[(long long)id * D + l] -= a.lr * (float)((double)q * EMB_FIX_INV);
-}
-
-// data parallel: the exchange (ctr.hip: launch_emb_exchange) wants the batch's slot -> id list and slot count in fixed buffers
-__global__ void emb_plan_select_kernel(EmbPlanView plan, const StepState* st, int* slot_id_out, unsigned long long* n_slots_out) {
-  const long long k = st->batch_idx;
-  const long long sb = plan.slot_base[k], n = plan.slot_base[k + 1] - sb;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) slot_id_out[i] = plan.slot_id[sb + i];
-  if (blockIdx.x == 0 && threadIdx.x == 0) *n_slots_out = (unsigned long long)n;
 }
 
 // Sink of the rank scan (scan.h): rank of every id, slot -> id list of the touched ones (ascending ids), and the marks

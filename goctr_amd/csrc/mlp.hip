@@ -24,7 +24,6 @@ using namespace goctr;
 namespace {
 
 constexpr int MLP_LOSS_RING = 1 << 14;
-int env_int_mlp(const char* name, int dflt);
 
 struct MlpState {
   long long t;          // optimizer step counter (AdamOptimizer64.t)
@@ -207,7 +206,7 @@ struct MlpReduceArgs {
   int nblk;                   // blocks that own parameters; block nblk is the loss block
   const double* lossterm; int upL, no; double* ring; int advance;
   double* W0img; int up1_img; // LDS image of layer 0 for the fused forward (or null)
-  // blocks behind the loss block (GOCTR_MLP_PREFETCH): the NEXT batch's permutation entries, float32 rows and float64 image rows
+  // blocks behind the loss block: the NEXT batch's permutation entries, float32 rows and float64 image rows
   // requested one launch ahead of their readers (mlp_chain_kernel's prologue, mlp_tn64_kernel's cold gather); block j asks for the rows
   // of the chain workgroups w = (j + pf_xcd_shift) mod 8 (workgroup b of a launch runs on XCD b % 8 -- observed, not promised: nothing
   // but the next launches' first latencies depends on it)
@@ -966,20 +965,24 @@ __global__ __launch_bounds__(256) void mlp_chain_kernel(MlpChainArgs a) {
 // column-major LDS strips T[col][m] (stride CH + 2 doubles = 16 B mod 128 B); two ds_read_b128 then hold the 4
 // consecutive rows a lane feeds to 4 MFMAs.
 constexpr int TN64_CH = 32, TN64_CHS = TN64_CH + 2, TN64_NTW = 2;
+// A tiles per workgroup: 3.  Two (78 KB of LDS: two workgroups fit a CU, one workgroup's start-up, first loads and slab stores
+// under the other's MFMAs) measured slower at cfg2 (45.4 vs 42.3 us per step with two per CU, 42.8 with one): co-resident
+// f64-MFMA workgroups serialise
+constexpr int TN64_KTW = 3;
 
 // IDX: A is the float64 image of ALL resident rows (mlp_widen_rows_kernel) and batch row m is its row ridx[m] (written by
 // mlp_chain_kernel<.., true>; the buffer is padded with zeros past the batch, so the unconditional loads of a slab's last chunk
 // stay inside the image).  The indices of chunk c + 1 are requested with the rows of chunk c: no dependent pair of loads inside
 // the loop, one more memory latency at the launch's start.
-template <int TN64_KTW, bool IDX = false>
+template <int KTW, bool IDX = false>
 __global__ __launch_bounds__(256, 2) void mlp_tn64_kernel(const double* __restrict__ A, int lda, int KT,
                                                           const double* __restrict__ Dm, int ldd, int NT, int M, int rows,
-                                                          double* __restrict__ slabs, size_t slab_stride, int wt,
+                                                          double* __restrict__ slabs, size_t slab_stride,
                                                           const int* __restrict__ ridx) {
   typedef double d2 __attribute__((ext_vector_type(2)));
   typedef double d4 __attribute__((ext_vector_type(4)));
   typedef int i4u __attribute__((ext_vector_type(4), aligned(4)));
-  constexpr int CH = TN64_CH, CHS = TN64_CHS, KTW = TN64_KTW, NTW = TN64_NTW;
+  constexpr int CH = TN64_CH, CHS = TN64_CHS, NTW = TN64_NTW;
   constexpr int MAXB = ((CH / 4) * (KTW * 4 + 8 * 4) + 255) / 256;     // 4x4 blocks per thread and chunk (NT <= 8)
   extern __shared__ __attribute__((aligned(16))) double tn64_smem[];
   const int split = blockIdx.x, kb = blockIdx.y;
@@ -1116,15 +1119,13 @@ __global__ __launch_bounds__(256, 2) void mlp_tn64_kernel(const double* __restri
     for (int f = 0; f < NTW; ++f)
       if (e < kb_t && f < ncnt) {
         const int n = (nt0 + f) * 16 + i;
-        // wt: the slabs go THROUGH the L2 (global_store_dwordx2 ... sc1) instead of staying dirty in it until the launch ends --
+        // the slabs go THROUGH the L2 (global_store_dwordx2 ... sc1) instead of staying dirty in it until the launch ends --
         // what a launch leaves dirty is written back at its boundary, in front of the reduce launch that reads these very slabs
         // (the CTR weight-gradient launch gained 1.5 us of a 47 us step that way, profiles/r06_write_through.txt)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          double* o = out + (size_t)((kb0 + e) * 16 + q + 4 * r) * ld_out + n;
-          if (wt) __hip_atomic_store(o, acc[e][f][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          else *o = acc[e][f][r];
-        }
+        for (int r = 0; r < 4; ++r)
+          __hip_atomic_store(out + (size_t)((kb0 + e) * 16 + q + 4 * r) * ld_out + n, acc[e][f][r], __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
       }
 }
 
@@ -1158,27 +1159,18 @@ int launch_nn64(const double* A, int lda, const double* Bm, int ldb, int M, int 
   return 0;
 }
 
-// A tiles per workgroup of mlp_tn64_kernel: 3; GOCTR_MLP_TN_KTW=2 (78 KB of LDS: two workgroups fit a CU) exists for the
-// experiment "one workgroup's start-up, first loads and slab stores under the other's MFMAs" -- measured slower at cfg2
-// (45.4 vs 42.3 us per step with two per CU, 42.8 with one): co-resident f64-MFMA workgroups serialise
-int tn64_ktw() { return 3; }
 int launch_tn64(const double* A, int lda, int KT, const double* Dm, int ldd, int NT, int M, int rows_per_wg,
                 double* slabs, const int* ridx = nullptr) {
-  GOCTR_CHECK(!ridx || (NT <= 8 && tn64_ktw() == 3), "launch_tn64: indexed rows only on mlp_tn64_kernel<3>");
+  GOCTR_CHECK(!ridx || NT <= 8, "launch_tn64: indexed rows only on mlp_tn64_kernel");
   if (NT <= 8) {
-    const int Sn = (int)cdiv(M, rows_per_wg);
-    const int ktw = tn64_ktw();
-    const int wt = env_int_mlp("GOCTR_MLP_TN_WT", 1);
-    const size_t lds = sizeof(double) * 2 * TN64_CHS * (size_t)(ktw * 16 + NT * 16);
+    const dim3 grid((unsigned)cdiv(M, rows_per_wg), (unsigned)cdiv(KT, TN64_KTW));
+    const size_t lds = sizeof(double) * 2 * TN64_CHS * (size_t)(TN64_KTW * 16 + NT * 16);
     if (ridx)
-      hipLaunchKernelGGL((mlp_tn64_kernel<3, true>), dim3(Sn, (unsigned)cdiv(KT, 3)), dim3(256), lds, engine().stream, A, lda, KT,
-                         Dm, ldd, NT, M, rows_per_wg, slabs, (size_t)KT * 16 * NT * 16, wt, ridx);
-    else if (ktw == 2)
-      hipLaunchKernelGGL(mlp_tn64_kernel<2>, dim3(Sn, (unsigned)cdiv(KT, 2)), dim3(256), lds, engine().stream, A, lda, KT, Dm,
-                         ldd, NT, M, rows_per_wg, slabs, (size_t)KT * 16 * NT * 16, wt, (const int*)nullptr);
+      hipLaunchKernelGGL((mlp_tn64_kernel<TN64_KTW, true>), grid, dim3(256), lds, engine().stream, A, lda, KT, Dm, ldd, NT, M,
+                         rows_per_wg, slabs, (size_t)KT * 16 * NT * 16, ridx);
     else
-      hipLaunchKernelGGL(mlp_tn64_kernel<3>, dim3(Sn, (unsigned)cdiv(KT, 3)), dim3(256), lds, engine().stream, A, lda, KT, Dm,
-                         ldd, NT, M, rows_per_wg, slabs, (size_t)KT * 16 * NT * 16, wt, (const int*)nullptr);
+      hipLaunchKernelGGL(mlp_tn64_kernel<TN64_KTW>, grid, dim3(256), lds, engine().stream, A, lda, KT, Dm, ldd, NT, M,
+                         rows_per_wg, slabs, (size_t)KT * 16 * NT * 16, (const int*)nullptr);
     GOCTR_HIP(hipGetLastError());
     return 0;
   }
@@ -1201,7 +1193,8 @@ int init_attrs64() {
   if (allow_big_lds(gemm_nn_kernel<double, EpiMlpAct, 1>) || allow_big_lds(gemm_nn_kernel<double, EpiMlpAct, 2>) ||
       allow_big_lds(gemm_nn_kernel<double, EpiMlpAct, 4>) || allow_big_lds(gemm_nn_kernel<double, EpiMlpDAct, 1>) ||
       allow_big_lds(gemm_nn_kernel<double, EpiMlpDAct, 2>) || allow_big_lds(gemm_nn_kernel<double, EpiMlpDAct, 4>) ||
-      allow_big_lds(gemm_tn_kernel<double, 3, 2, 16>) || allow_big_lds(mlp_tn64_kernel<3>) || allow_big_lds(mlp_tn64_kernel<3, true>) || allow_big_lds(mlp_tn64_kernel<2>) || allow_big_lds(mlp_fwd_kernel<24>)) return -1;
+      allow_big_lds(gemm_tn_kernel<double, 3, 2, 16>) || allow_big_lds(mlp_tn64_kernel<TN64_KTW>) ||
+      allow_big_lds(mlp_tn64_kernel<TN64_KTW, true>) || allow_big_lds(mlp_fwd_kernel<24>)) return -1;
   done = true;
   return 0;
 }
@@ -1231,11 +1224,12 @@ struct goctr_mlp {
   // the resident rows as the float64 operand image of the weight-gradient GEMM (mlp_widen_rows_kernel; GOCTR_MLP_X64, default on
   // while the image stays under 64 GiB) and the running batch's row indices into it (batch + 64 ints, zero padded)
   DevBuf<double> X64; DevBuf<int> ridx;
-  DevBuf<float> pf_sink;         // GOCTR_MLP_PREFETCH (default on): scratch of the reduce launch's prefetch blocks
+  DevBuf<float> pf_sink;         // scratch of the reduce launch's prefetch blocks
   bool x64() const { return X64.p != nullptr && ridx.p != nullptr; }
   hipGraphExec_t step_graph = nullptr; int64_t step_graph_rows = 0; bool step_graph_perm = false;   // resident training step
   hipGraphExec_t multi_graph[2] = {nullptr, nullptr};           // the same step captured 8 / 2 times back to back
   const void* step_graph_x = nullptr; const void* step_graph_y = nullptr; const void* step_graph_p = nullptr; const void* step_graph_w = nullptr; const void* step_graph_x64 = nullptr;
+  const void* step_graph_ridx = nullptr;
   ~goctr_mlp() { if (step_graph) (void)hipGraphExecDestroy(step_graph); for (auto g : multi_graph) if (g) (void)hipGraphExecDestroy(g); }
   std::mutex mu;
 };
@@ -1249,7 +1243,7 @@ int tn_rows64(const goctr_mlp* p, int n) {
   int kb = 1;   // workgroups per slab of the widest layer (see launch_tn64)
   for (int l = 0; l < p->nl; ++l) {
     const int KT = p->up[l] / 16, NT = p->up[l + 1] / 16;
-    const int k = NT <= 8 ? (int)cdiv(KT, tn64_ktw()) : (int)cdiv(KT, KT >= 6 ? 6 : 3) * (int)cdiv(NT, NT >= 3 ? 4 : 2);
+    const int k = NT <= 8 ? (int)cdiv(KT, TN64_KTW) : (int)cdiv(KT, KT >= 6 ? 6 : 3) * (int)cdiv(NT, NT >= 3 ? 4 : 2);
     if (k > kb) kb = k;
   }
   int cus = engine().compute_units > 0 ? engine().compute_units : 256;
@@ -1408,7 +1402,7 @@ int backward(goctr_mlp* p, int n, bool do_update, bool advance, int valid = -1) 
   if (dbg && !rdbg.p && rdbg.alloc(18)) return -1;
   a.dbg = dbg ? rdbg.p : nullptr;
   int pf_blocks = 0;
-  if (chain && advance && p->rows > 0 && p->pf_sink.p) {
+  if (chain && advance && p->rows > 0) {
     a.pf_X = p->Xr.p; a.pf_Y = p->Yr.p; a.pf_perm = p->perm.n > 1 ? p->perm.p : nullptr; a.pf_rows = p->rows;
     a.pf_F = p->units[0]; a.pf_batch = p->cfg.batch; a.pf_sink = p->pf_sink.p;
     pf_blocks = MLP_PF_BLOCKS;
@@ -1686,17 +1680,17 @@ int goctr_mlp_upload(goctr_mlp* p, const float* X, const float* Y, int64_t rows)
   p->rows = rows;
   p->perm.release();
   // the float64 image of the rows for the weight-gradient launch (up0 doubles per row: 2.05 x the float32 rows at F = 281)
-  p->X64.release(); p->ridx.release();
+  // (ridx stays across uploads: a captured step holds its address)
+  p->X64.release();
   const size_t img_bytes = (size_t)rows * p->up[0] * sizeof(double);
-  if (p->chain_ok() && tn64_ktw() == 3 && p->up[1] / 16 <= 8 && rows < (1LL << 31) && env_int_mlp("GOCTR_MLP_X64", 1) &&
+  if (p->chain_ok() && p->up[1] / 16 <= 8 && rows < (1LL << 31) && env_int_mlp("GOCTR_MLP_X64", 1) &&
       img_bytes <= ((size_t)64 << 30)) {
-    if (p->X64.alloc((size_t)rows * p->up[0], false) || p->ridx.alloc((size_t)p->cfg.batch + 64, true)) return -1;
+    if (p->X64.alloc((size_t)rows * p->up[0], false) || p->ridx.ensure((size_t)p->cfg.batch + 64, true)) return -1;
     hipLaunchKernelGGL(mlp_widen_rows_kernel, dim3((unsigned)rows), dim3(256), 0, engine().stream, p->Xr.p, (long long)rows, F,
                        p->up[0], p->X64.p);
     GOCTR_HIP(hipGetLastError());
   }
-  if (env_int_mlp("GOCTR_MLP_PREFETCH", 1)) { if (p->pf_sink.ensure((size_t)MLP_PF_BLOCKS / 8 * 256, true)) return -1; }
-  else p->pf_sink.release();
+  if (p->pf_sink.ensure((size_t)MLP_PF_BLOCKS / 8 * 256, true)) return -1;
   return ensure_ws(p, p->cfg.batch);
 }
 
@@ -1711,7 +1705,7 @@ static int run_fused_steps(goctr_mlp* p, int n_steps) {
     if (p->fused_ok() && p->zpart.ensure((size_t)cdiv(p->up[1], 32) * p->cfg.batch, false)) return -1;
     if (!p->step_graph || p->step_graph_rows != p->rows || p->step_graph_perm != (p->perm.n > 1) ||
         p->step_graph_x != p->Xr.p || p->step_graph_y != p->Yr.p || p->step_graph_p != p->perm.p || p->step_graph_w != p->W0img.p ||
-        p->step_graph_x64 != p->X64.p) {
+        p->step_graph_x64 != p->X64.p || p->step_graph_ridx != p->ridx.p) {
       // (goctr_mlp_train_steps is asynchronous: replays of the old execs may still be queued -- never destroy one in flight)
       if (p->step_graph || p->multi_graph[0] || p->multi_graph[1]) GOCTR_HIP(hipStreamSynchronize(e.stream));
       if (p->step_graph) { (void)hipGraphExecDestroy(p->step_graph); p->step_graph = nullptr; }
@@ -1719,7 +1713,7 @@ static int run_fused_steps(goctr_mlp* p, int n_steps) {
       if (capture_graph(e.stream, &p->step_graph, [&] { return train_step_resident(p, true, 0); }, [] {})) return -1;
       p->step_graph_rows = p->rows; p->step_graph_perm = p->perm.n > 1;
       p->step_graph_x = p->Xr.p; p->step_graph_y = p->Yr.p; p->step_graph_p = p->perm.p; p->step_graph_w = p->W0img.p;
-      p->step_graph_x64 = p->X64.p;
+      p->step_graph_x64 = p->X64.p; p->step_graph_ridx = p->ridx.p;
     }
     // every per-step scalar is device state, so a graph may as well hold several steps: one graph launch per 8 (2) steps
     // instead of one per step (the boundary between two graph launches costs about two kernel-to-kernel edges inside one).

@@ -187,9 +187,9 @@ nb = m.sparse_exchange_bytes()
 import os
 if not %(comm)d:
     assert nb == 0
-elif os.environ.get("GOCTR_EMB_FIXED_EXCHANGE", "1") == "0":
-    # exact counts (two host read-backs per step): the last step's batch touches n ids: n x (4 + 8 D) bytes to the owner +
-    # n x (4 + 4 D) gathered back (world 1: all to self)
+elif os.environ.get("GOCTR_EMB_PLAN", "1") == "0":
+    # the atomics path's exchange, exact counts (two host read-backs per step): the last step's batch touches n ids:
+    # n x (4 + 8 D) bytes to the owner + n x (4 + 4 D) gathered back (world 1: all to self)
     ids = np.concatenate([ub[0:512].ravel(), it[0:512]])           # (5 steps over 4 batches: the last one is batch 0 again)
     n = np.unique(ids[ids >= 0]).size
     assert nb == n * (4 + 8 * D) + n * (4 + 4 * D), (nb, n)
@@ -212,20 +212,18 @@ def test_embedding_training_exchange_one_rank(tmp_path):
     run bit for bit; the bytes the exchange reports are exactly the touched ids' payload"""
     res = []
     # single GPU; one-rank RCCL with the fixed-size buckets (three captured graphs around the collectives, no host read-back);
-    # the same eager (GOCTR_NO_GRAPH); the exact-count exchange with its two read-backs per step; and the atomics path's exchange
+    # the same eager (GOCTR_NO_GRAPH); and the atomics path's exact-count exchange with its two read-backs per step
     for tag, comm, extra in (("single", 0, {}), ("fixed", 1, {}), ("fixed_eager", 1, {"GOCTR_NO_GRAPH": "1"}),
-                             ("exact", 1, {"GOCTR_EMB_FIXED_EXCHANGE": "0"}), ("atomics", 1, {"GOCTR_EMB_PLAN": "0"})):
+                             ("atomics", 1, {"GOCTR_EMB_PLAN": "0"})):
         out = str(tmp_path / f"emb_{tag}.npy")
         env = dict(os.environ, **extra)
         env["GOCTR_FORCE_COMM"] = str(comm)
-        if tag == "atomics":
-            env["GOCTR_EMB_FIXED_EXCHANGE"] = "0"
         r = subprocess.run([sys.executable, "-c", EMB_SCRIPT % dict(root=ROOT, comm=comm, out=out)], env=env,
                            capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, (tag, r.stderr[-2000:])
         res.append(np.load(out))
     assert np.isfinite(res[0]).all()
-    for k in (1, 2, 3):
+    for k in (1, 2):
         assert np.array_equal(res[0], res[k]), k                          # the plan path: identical integer sums whatever the exchange
     # (the atomics path associates the per-pair expression differently: float32 rounding apart, test_gpu_embtrain.py)
-    assert np.max(np.abs(res[0] - res[4])) <= 2e-6 * max(1.0, float(np.max(np.abs(res[0]))))
+    assert np.max(np.abs(res[0] - res[3])) <= 2e-6 * max(1.0, float(np.max(np.abs(res[0]))))
