@@ -83,11 +83,6 @@ int load_rccl() {
     }                                                                                             \
   } while (0)
 
-int env_int_comm(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v && *v ? atoi(v) : dflt;
-}
-
 // ---------------------------------------------------------------- loop-back kernels
 constexpr int kLoopMaxWorld = 64;
 struct LoopPtrs { const void* p[kLoopMaxWorld]; };
@@ -130,7 +125,7 @@ struct LoopGroup {
     if (aborted) { set_error("loop-back communicator: aborted by a failing rank"); return -1; }
     const uint64_t gen = generation;
     if (++arrived == world) { arrived = 0; ++generation; cv.notify_all(); return 0; }
-    const int timeout_s = std::max(1, env_int_comm("GOCTR_LOOP_TIMEOUT_S", 120));
+    const int timeout_s = std::max(1, env_int("GOCTR_LOOP_TIMEOUT_S", 120));
     const bool ok = cv.wait_for(lk, std::chrono::seconds(timeout_s), [&] { return generation != gen || aborted; });
     if (!ok) { aborted = true; cv.notify_all(); set_error("loop-back communicator: a rank did not reach the collective within %d s", timeout_s); return -1; }
     if (aborted && generation == gen) { set_error("loop-back communicator: aborted by a failing rank"); return -1; }
@@ -376,7 +371,7 @@ int comm_watch_stream(int timeout_override_s) {
   Engine& e = engine();
   if (!e.nccl_comm || !g_rccl.CommGetAsyncError) { GOCTR_HIP(hipStreamSynchronize(e.stream)); return 0; }
   const auto t0 = std::chrono::steady_clock::now();
-  const int timeout_s = timeout_override_s > 0 ? timeout_override_s : std::max(1, env_int_comm("GOCTR_COMM_TIMEOUT_S", 300));
+  const int timeout_s = timeout_override_s > 0 ? timeout_override_s : std::max(1, env_int("GOCTR_COMM_TIMEOUT_S", 300));
   for (unsigned spin = 0;; ++spin) {
     const hipError_t q = hipStreamQuery(e.stream);
     if (q == hipSuccess) return 0;
@@ -414,8 +409,7 @@ void comm_group_drop(int n) {
 }
 // is the group's communicator still there on every rank?  (n == 1 without GOCTR_FORCE_COMM has none by design)
 bool comm_group_live(int n) {
-  const char* force = getenv("GOCTR_FORCE_COMM");
-  if (n == 1 && !(force && *force && *force != '0')) return true;
+  if (n == 1 && !env_flag("GOCTR_FORCE_COMM", false)) return true;
   for (int k = 0; k < n; ++k) {
     Engine* e = engine_at(k);
     if (!e || (!e->nccl_comm && !e->loop)) return false;
@@ -427,9 +421,7 @@ bool comm_group_live(int n) {
 // other), the loop-back communicator when a device repeats (RCCL rejects duplicate GPUs).  n == 1: none, unless
 // GOCTR_FORCE_COMM=1 (a one-rank communicator exercises the split step path on a single GPU).
 int comm_group_init(int n) {
-  const char* force = getenv("GOCTR_FORCE_COMM");
-  const bool forced = force && *force && *force != '0';
-  if (n == 1 && !forced) return 0;
+  if (n == 1 && !env_flag("GOCTR_FORCE_COMM", false)) return 0;
   GOCTR_CHECK(n <= kLoopMaxWorld, "goctr_init_devices: more than %d ranks", kLoopMaxWorld);
   bool distinct = true;
   for (int a = 0; a < n; ++a)
@@ -498,8 +490,7 @@ int goctr_comm_init(int rank, int world, const uint8_t id[128]) {
   GOCTR_CHECK(!e.loop, "goctr_comm_init: this engine belongs to a goctr_init_devices group (loop-back communicator)");
   if (e.nccl_comm) goctr_comm_destroy();
   e.rank = rank; e.world = world;
-  const char* force = getenv("GOCTR_FORCE_COMM");
-  if (world == 1 && !(force && *force && *force != '0')) return 0;
+  if (world == 1 && !env_flag("GOCTR_FORCE_COMM", false)) return 0;
   if (load_rccl()) return -1;
   ncclUniqueId u;
   memcpy(&u, id, 128);
@@ -508,7 +499,7 @@ int goctr_comm_init(int rank, int world, const uint8_t id[128]) {
   e.nccl_comm = c;
   e.capture_state = 0;
   // may the data-parallel step graphs hold the all-reduce?  Decided HERE, where every rank is (comm_capture_selftest is a collective)
-  if (env_int_comm("GOCTR_DP_CAPTURE_COMM", 1) == 1 && comm_capture_selftest() < 0) return -1;   // (communicator lost: say so)
+  if (env_int("GOCTR_DP_CAPTURE_COMM", 1) == 1 && comm_capture_selftest() < 0) return -1;   // (communicator lost: say so)
   GOCTR_CHECK(e.nccl_comm, "goctr_comm_init: the communicator did not survive its first collectives");
   return 0;
 }
@@ -523,9 +514,8 @@ int goctr_comm_group_enable(int on) {
 
 int goctr_comm_capture_mode(int* mode) {
   GOCTR_CHECK(mode, "goctr_comm_capture_mode: null argument");
-  const char* v = getenv("GOCTR_DP_CAPTURE_COMM");
   const Engine& e = engine();
-  *mode = (v && *v == '0') || e.loop ? -1 : e.capture_state;
+  *mode = env_int("GOCTR_DP_CAPTURE_COMM", 1) == 0 || e.loop ? -1 : e.capture_state;
   return 0;
 }
 

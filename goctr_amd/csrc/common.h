@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <functional>
 #include <map>
@@ -59,13 +60,13 @@ struct Engine {
     std::mutex mu;
   } arena;
   bool kernel_attrs_done = false, mlp_attrs_done = false;   // hipFuncSetAttribute is per device: once per engine
-  void* serve_pool = nullptr;     // ctr.hip: this engine's serving slots (streams + pinned staging live on its device)
+  void* serve_pool = nullptr;     // serve.hip: this engine's serving slots (streams + pinned staging live on its device)
   int compute_units = 0;
   bool large_bar = false;      // the host can write device memory through the PCIe BAR (hipDeviceProp_t::isLargeBar)
   hipStream_t stream = nullptr;   // the engine's main stream
   hipStream_t side = nullptr;     // forked inside captured step graphs for independent kernels
   // stream the launch helpers of THE CALLING THREAD currently target: the main stream unless a StreamScope switched it
-  // (a serving slot's stream, ctr.hip).  Thread-local: serving calls of several host threads run beside each other
+  // (a serving slot's stream, serve.hip).  Thread-local: serving calls of several host threads run beside each other
   struct ActiveStream {
     operator hipStream_t() const;
     ActiveStream& operator=(hipStream_t s);
@@ -82,7 +83,7 @@ struct Engine {
   // of the group is a single-device call.  goctr_comm_init's communicator (one process per GPU) is always on.
   bool comm_enabled = true;
   int capture_state = 0;          // comm_capture_selftest: 0 not tested, 1 captured collectives work, -1 they do not
-  // goctr_engine_call_ms: events around this rank's part of the last multi-device training call (train_multi)
+  // goctr_engine_call_ms: events around this rank's part of the last multi-device training call (ctr_multi.hip: train_multi)
   hipEvent_t call_begin = nullptr, call_end = nullptr; bool call_timed = false;
   bool comm_active() const { return (nccl_comm != nullptr || loop != nullptr) && comm_enabled; }
   // rank / world of the CALL in flight: a group engine running a single-device call is rank 0 of 1
@@ -124,7 +125,7 @@ int run_on_engines(int n, const std::function<int(int)>& fn);
 // they use.  Recursive: entry points call each other (goctr_train_dense -> goctr_dataset_create_dense -> ...).
 // The serving entry points (goctr_batch_predict / goctr_rank / goctr_predict_dense: what concurrent gin handler goroutines
 // call, recommend/api.go:106-131) do NOT take the lock: each runs on a serving slot with its own stream, staging buffers and
-// forward workspace (ctr.hip: ServeSlot) under a shared lock of the model.
+// forward workspace (serve.hip: ServeSlot) under a shared lock of the model.
 #define GOCTR_ENTER_ON(eng_ptr)                                   \
   ::goctr::EngineScope _goctr_engine_scope(eng_ptr);              \
   if (::goctr::require_engine()) return -1;                       \
@@ -140,6 +141,27 @@ int run_on_engines(int n, const std::function<int(int)>& fn);
 inline bool dbg_on(const char* what) {
   const char* v = getenv("GOCTR_DBG");
   return v && *v && strstr(v, what) != nullptr;
+}
+
+// Environment switches, read at call time.  env_int: unset or empty -> dflt, else atoi (a value that is not a
+// number reads as 0); env_int64: the same for 64-bit values; env_flag: on / off -- unset or empty -> dflt, else off exactly when the
+// value starts with '0'.
+inline int env_int(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v && *v ? atoi(v) : dflt;
+}
+inline long long env_int64(const char* name, long long dflt) {
+  const char* v = getenv(name);
+  return v && *v ? atoll(v) : dflt;
+}
+inline bool env_flag(const char* name, bool dflt) {
+  const char* v = getenv(name);
+  return v && *v ? *v != '0' : dflt;
+}
+// env_int, except that a set but EMPTY value reads as 0 (atoi), not as dflt: the k-NN switches have always been read so
+inline int env_int_set(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
 }
 
 // generation ids for handles whose device pointers get baked into captured graphs (a freed handle's host address may be
@@ -169,7 +191,7 @@ inline void prof_note_kernel(int id, const char* symbol) { engine().prof_kernel[
 // separately-mapped allocations.  Requests that do not fit fall back to a plain hipMalloc.
 void* arena_alloc(size_t bytes);              // from the calling thread's engine
 // Fine-grained DEVICE memory that the host may store into through the PCIe BAR (a k-NN call's queries, a serving pass's keys:
-// search.hip, ctr.hip), or null: no large BAR, the runtime refuses, or the range is not mapped writable into this process
+// search.hip, serve.hip), or null: no large BAR, the runtime refuses, or the range is not mapped writable into this process
 // (checked in /proc/self/maps before anybody stores into it).  Freed with hipFree.
 void* bar_alloc(size_t bytes);
 void arena_free(Engine* owner, void* p);      // back to the engine it came from (any thread)

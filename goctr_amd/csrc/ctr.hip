@@ -1,240 +1,28 @@
-// ctr.hip -- host side of the DIN / YouTube-DNN engine + its C-ABI (include/goctr.h).
+// ctr.hip -- the training and forward step of the DIN / YouTube-DNN engine (host side).
 //
 // Replaces, behind the same operator surface, the gorgonia-executed training / predict loops of
 // model/model.go:27-352 for model/din and model/youtube (reference = auxten/go-ctr).  One step =
 //   attn_fwd -> 3 x gemm_nn(+epilogue) -> 3 x gemm_nn backward-data -> attn_bwd -> 3 x gemm_tn
 //   -> reduce -> [RCCL all-reduce] -> adam
 // all on one HIP stream; per-step varying values live in a device-side StepState so the sequence
-// can be captured once into a hipGraph and replayed.
-#include <atomic>
+// can be captured once into a hipGraph and replayed.  What the other CTR translation units call is declared in
+// ctr_model.h; the C ABI (include/goctr.h) lives in ctr_api.hip, ctr_multi.hip and serve.hip.
+#include <array>
 #include <chrono>
 #include <cmath>
-#include <condition_variable>
 #include <cstdlib>
-#include <deque>
-#include <memory>
-#include <array>
 #include <map>
-#include <shared_mutex>
+#include <memory>
 
-#include "common.h"
+#include "ctr_model.h"
 #include "ctr_chain.h"
 #include "ctr_chain_x3.h"
 #include "emb_train.h"
-#include "emb_plan.h"
 #include "scan.h"
-#include "ctr_kernels.h"
 #include "ctr_serve.h"
 #include "mfma_gemm.h"
 
-using namespace goctr;
-
-struct goctr_emb {
-  goctr::Engine* const eng = &goctr::engine();   // the engine (device, streams, arena) the handle was created on
-  const uint64_t uid = next_uid();   // what a captured step graph is keyed on (never reused, unlike the host address)
-  uint64_t version = 0;              // bumped whenever rows change (goctr_emb_set_rows, embedding training): H0Carry is keyed on it
-  int64_t V = 0; int D = 0;
-  DevBuf<float> rows;
-  // single-call multi-device training (goctr_train_cfg::devices): this table's replicas on engines 1 .. n-1 (owned), and the
-  // version of THIS table they were last made equal to
-  std::vector<goctr_emb*> reps; uint64_t reps_version = ~0ull;
-  // Rows are READ by serving passes on their slots' streams (shared) and WRITTEN on the main stream by goctr_emb_set_rows and
-  // by embedding training of any model that was given this table (exclusive).  ev_rows is recorded behind the last queued
-  // write: training is asynchronous, a serving pass waits for the event before its launches read the rows.
-  std::shared_mutex mu;
-  hipEvent_t ev_rows = nullptr; std::atomic<bool> rows_pending{false};
-};
-
-struct goctr_dataset {
-  goctr::Engine* const eng = &goctr::engine();   // the engine (device, streams, arena) the handle was created on
-  const uint64_t uid = next_uid();
-  bool id_mode = false;
-  int64_t rows = 0;
-  bool has_y = false;
-  // dense
-  DevBuf<float> X; int xcols = 0; int ranges[8] = {0};
-  // ids
-  DevBuf<int32_t> ub_ids, item_ids; DevBuf<float> ufeat, cfeat; int U = 0, C = 0, T = 0;
-  DevBuf<float> Y;
-  // single-call multi-device training: shards[r] (on engine r, owned) holds rank r's rows of every global batch of shard_B rows,
-  // batch-major, the short last batch zero-padded (model.go:357-371) -- local batch k of rank r = rows [r, r+1) * shard_B / n of
-  // global batch k
-  std::vector<goctr_dataset*> shards; int shard_B = 0;
-  // goctr_train_dense with cfg.devices = n > 1: the caller's HOST rows, valid for the duration of that call only.  Nothing is
-  // uploaded to engine 0 (X / Y stay empty): every rank copies ITS rows of every global batch straight from host memory into its
-  // shard, on its own device and stream (train_multi) -- round 4 staged all of X on engine 0 and scattered it over xGMI
-  const float* host_X = nullptr; const float* host_Y = nullptr;
-};
-
-struct StepGraph {
-  // One captured step per ping-pong parity of the step state (a step reads slot p and writes slot p^1).
-  // b[] only when a communicator splits the step (all-reduce between reduce and Adam).
-  hipGraphExec_t a[2] = {nullptr, nullptr}, b[2] = {nullptr, nullptr};
-  hipGraphExec_t mid[2] = {nullptr, nullptr};   // data parallel + trainable embeddings: owner side of the sparse exchange + slab reduce
-  // ba[p]: b[p] and the NEXT step's a[p ^ 1] as one graph (dense all-reduce only): a step inside a call is then all-reduce +
-  // ONE graph launch instead of two -- every boundary between host-issued items costs the GPU ~4 us
-  hipGraphExec_t ba[2] = {nullptr, nullptr};
-  // multi[p]: multi_steps (even) consecutive steps starting at parity p in ONE graph (single GPU): the boundary between
-  // two graph launches costs about two kernel-to-kernel edges; every per-step scalar is device state, so nothing else changes
-  // (built together with a[]: a first call in a timed region must not pay for a capture)
-  static constexpr int kNMulti = 3;
-  int kMulti[kNMulti] = {16, 4, 2};                                        // even, descending (GOCTR_GRAPH_SIZES=a,b,c: experiments)
-  hipGraphExec_t multi[kNMulti][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};   // [size][parity]
-  bool multi_on = false;
-  // cache key
-  // (the captured launches bake in the dataset's / table's device pointers and row count: keyed on the handles'
-  // generation ids, not their host addresses -- malloc readily hands a destroyed dataset's address to the next one)
-  uint64_t ds = 0, emb = 0; int B = 0; int mode = 0; float p0 = 0, p1 = 0;
-  uint32_t seed = 0; double lr = 0, l2 = 0, b1 = 0, b2 = 0, eps = 0; int flags = 0; int world = 1; bool comm = false;
-  bool pipelined = false;   // the captured steps are pipelined (StepOpts::pipelined): a replay needs h0 of its first step
-  bool fac = false;         // gate_fac_mode() when the steps were captured (their attention launches leave the one factor)
-  void destroy() {
-    // goctr_train_steps does not synchronise: replays of these execs may still be queued or running, and destroying an
-    // exec in flight is not something HIP documents as safe.  The capture that follows a destroy is host-heavy anyway.
-    bool any = false;
-    for (int k = 0; k < 2; ++k) {
-      any = any || a[k] || b[k] || mid[k] || ba[k];
-      for (int z = 0; z < kNMulti; ++z) any = any || multi[z][k];
-    }
-    if (any && engine().inited) (void)hipStreamSynchronize(engine().stream);
-    for (int k = 0; k < 2; ++k) {
-      if (a[k]) (void)hipGraphExecDestroy(a[k]);
-      if (b[k]) (void)hipGraphExecDestroy(b[k]);
-      if (mid[k]) (void)hipGraphExecDestroy(mid[k]);
-      if (ba[k]) (void)hipGraphExecDestroy(ba[k]);
-      for (int z = 0; z < kNMulti; ++z) { if (multi[z][k]) (void)hipGraphExecDestroy(multi[z][k]); multi[z][k] = nullptr; }
-      a[k] = b[k] = mid[k] = ba[k] = nullptr;
-    }
-    multi_on = false;
-  }
-};
-
-// Where a forward pass keeps its per-row buffers: the training workspace (parity copies of gate / wgt), the model's
-// predict workspace, or a serving slot's.  A forward-only launch touches nothing else (the fused chain kernels write
-// yhat only; the modular per-layer path also needs P0 / P1).
-struct FwdBufs { float* h0; float* gate; float* wgt; float* yhat; float* P0; float* P1; float* fac = nullptr; };
-struct FwdWs {
-  DevBuf<float> h0, gate, wgt, yhat, P0, P1;
-  int B = 0, Ip = 0, T = 0;
-  FwdBufs bufs() { return FwdBufs{h0.p, gate.p, wgt.p, yhat.p, P0.p, P1.p}; }
-  // (re)allocates for B rows on `st` (zeroed there: h0's pad columns must be 0, never NaN); modular: also P0 / P1
-  int ensure(int Bn, int Ipn, int Tn, int H1p, int H2p, bool modular, hipStream_t st) {
-    if (Bn <= B && Ipn == Ip && Tn == T && h0.p && (!modular || P0.p)) return 0;
-    GOCTR_HIP(hipStreamSynchronize(st));       // launches still reading the old buffers
-    B = 0;                                     // (a failure below must not leave the old size next to missing buffers)
-    auto z = [&](DevBuf<float>& b, size_t n) -> int {
-      if (b.alloc(n, false)) return -1;
-      GOCTR_HIP(hipMemsetAsync(b.p, 0, n * sizeof(float), st));
-      return 0;
-    };
-    const size_t Br = (size_t)round_up(Bn, 32);
-    if (z(h0, Br * Ipn) || z(gate, Br * Tn) || z(wgt, Br * Tn) || z(yhat, Br)) return -1;
-    if (modular && (z(P0, Br * H1p) || z(P1, Br * H2p))) return -1;
-    B = Bn; Ip = Ipn; T = Tn;
-    return 0;
-  }
-};
-
-struct goctr_model {
-  goctr::Engine* const eng = &goctr::engine();   // the engine (device, streams, arena) the handle was created on
-  goctr_ctr_cfg cfg{};
-  int I = 0, Ip = 0, H1p = 0, H2p = 0, Dp = 0, Tp = 0;
-  int off1 = 0, off2 = 0, offa = 0, nflat = 0;
-  DevBuf<float> W, G, Mo, Vo, W1T, W2T, W0sT;
-  DevBuf<float> Wimg;   // LDS images of W0 | W1 | W1^T | W0[U:U+D,:]^T (ctr_chain.h), kept in sync by Adam
-  // bf16-plane fragment images of the 6-product-split training chain (ctr_chain_x3.h), kept in sync by the Adam kernels
-  DevBuf<unsigned short> Wx3; int x3_nch0 = 0;
-  CxImages x3_images() {
-    CxImages im{nullptr, nullptr, nullptr, nullptr, 0};
-    if (!x3_nch0) return im;
-    im.nch0 = x3_nch0;
-    im.img0 = Wx3.p; im.img1 = im.img0 + cx_img0_elems(x3_nch0); im.img2 = im.img1 + cx_img1_elems(); im.img3 = im.img2 + cx_img2_elems();
-    return im;
-  }
-  float* img(int which) { return Wimg.p + (which == 0 ? 0 : which == 1 ? off1 : which == 2 ? off1 + H1p * H2p : off1 + 2 * H1p * H2p); }
-  // per-batch workspace
-  int wsB = 0, tnS = 0;
-  DevBuf<float> h0, P0, A0, P1, A1, yhat, lossrow, dz2, dz1, dz0, dp, gate, wgt, gfac, slabs0, slabs1, slabs2, attp;
-  DevBuf<float> mask0, mask1, slabs3, ones16;
-  size_t gw_stride = 0;           // floats between the two parity copies of gate / wgt
-  float* gate_p(int par) { return gate.p + (size_t)par * gw_stride; }
-  float* gfac_p(int par) { return gfac.p + (size_t)par * gw_stride; }
-  float* wgt_p(int par) { return wgt.p + (size_t)par * gw_stride; }
-  DevBuf<unsigned int> ra_flag;   // pipelined steps: gstep + 1 of the last step whose att0 update is visible device-wide (reduce_attn_kernel)
-  DevBuf<float> yall;          // scores of a whole predict call (one device-to-host copy at the end)
-  FwdWs pws;                   // forward-only workspace of goctr_predict_* (the training workspace and its graphs stay untouched)
-  DevBuf<StepState> st, pst;   // st: two ping-pong slots, stp = the one the next step reads
-  int stp = 0;
-  StepState* st_cur() { return st.p + stp; }
-  StepState* st_next() { return st.p + (stp ^ 1); }
-  DevBuf<float> costs;
-  // exclusive: everything that writes weights, optimizer state or the model's own workspaces (training, set_weights,
-  // goctr_predict_* on the model's predict workspace); shared: the serving slots' forward passes (ServeSlot below)
-  std::shared_mutex mu;
-  // recorded on the main stream behind the last queued launch that writes the weights (training is asynchronous): a
-  // serving slot's stream waits for it before it reads them
-  hipEvent_t ev_weights = nullptr; std::atomic<bool> weights_pending{false};
-  StepGraph graph;
-  int attp_blocks = 0;
-  // trainable-embedding extension (emb_train.h): off unless goctr_model_set_embedding_training(lr > 0)
-  float emb_lr = 0.f;
-  long long emb_V = 0; int emb_B = 0, emb_world = 0; bool emb_comm = false;
-  DevBuf<float> dpv, W0pvT;
-  bool w0pv_live = false;         // W0pvT holds the current W0[U:U+2D,:]^T and the Adam kernels keep it current
-  // The last launch of a pipelined step computes the NEXT batch's h0 / gates (reduce_attn_kernel); the last step of a
-  // goctr_train_steps call computes them for the batch the next call usually starts at.  That call skips its own first attn_fwd
-  // (8.5 us + a launch of a call's ~32 us fixed cost) if NOTHING could have touched what those rows were computed from:
-  // `gen` counts every entry that locks the model exclusively (weights, state, workspace -- and this model's own calls), the
-  // table's version its row updates; dataset and table are identified by their never-reused uids.
-  uint64_t gen = 0;
-  struct H0Carry { bool valid = false; uint64_t gen = 0, ds_uid = 0, emb_uid = 0, emb_version = 0; int B = 0, stp = 0; long long batch = -1;
-                   double beta1 = 0, beta2 = 0; /* (the bias corrections the last loss block left were made with these) */
-                   bool fac = false; /* (gate and weight left as one factor: gate_fac_mode) */ } carry;
-  bool attn_bwd_in_chain = false;  // launch_chain_x3 -> launch_backward: this step's chain launch wrote the att0 terms
-  bool dpv_from_chain = false;    // the step's chain launch wrote dpv itself (launch_chain_x3): no dpv GEMM in this step
-  // round 6: the step's chain launch left dW2 / the att0 terms as per-tile sums (tile_dw2 / tile_att0; ctr_chain_x3.h): the
-  // weight-gradient launch only adds the tiles up (mfma_gemm.h tn_tile_sum_body) and A1, dz2, attp are not written at all
-  bool dw2_from_chain = false, att0_from_chain = false;
-  bool att0_early = false;       // this step's weight-gradient launch has already updated att0 (ctr_chain_x3.h att0_early_body): launch_backward -> launch_reduce_part
-  DevBuf<float> tile_dw2, tile_att0;
-  DevBuf<unsigned int> emb_mark, emb_rank, emb_tiles;
-  DevBuf<unsigned long long> emb_total;
-  DevBuf<long long> emb_accum;
-  DevBuf<int> emb_slot_id;
-  long long emb_Vw = 0;           // rows of one owner's bucket in the (owner-major) mark / rank index space
-  // per-batch sparse plan of the id-major update (emb_train.h, "Round 3"): built once per (dataset, batch, vocabulary, world)
-  struct EmbPlan {
-    bool valid = false; uint64_t ds = 0; long long V = 0; int B = 0, W = 0, T = 0;
-    DevBuf<int> pair, pslot, pid, slot_id; DevBuf<unsigned int> slot_off; DevBuf<long long> pair_off, slot_base;
-    long long nb = 0, max_pairs = 0, max_slots = 0, total_pairs = 0, total_slots = 0;
-    double build_ms = 0;         // host wall time of the build (goctr_model_emb_plan_build_ms)
-    EmbPlanView view() const { return EmbPlanView{pair.p, pslot.p, pid.p, pair_off.p, slot_id.p, slot_off.p, slot_base.p}; }
-  } plan;
-  DevBuf<float> emb_dx, emb_gsum;  // emb_coef's per-pair row gradients [B, T, D] and item-row gradients [B, D]
-  // fixed-size exchange (emb_train.h, end) of every plan built under a communicator: exact bounds from the plan, no host
-  // read-back between the collectives
-  int ex_S = 0, ex_R = 0;
-  DevBuf<int> ex_bucket_off, ex_send_ids, ex_recv_ids; DevBuf<long long> ex_send_rows, ex_recv_rows;
-  ReduceArgs pend_ra{};            // launch_backward(stage 1) -> (stage 2)
-  bool pend_no_costs = false;      // goctr_train_steps: the caller does not read this call's costs
-  bool pend_retarget = false; long long pend_batch_idx = 0, pend_n_batches = 1;   // goctr_train_steps -> run_steps' state-preparation launch
-  // bucketed exchange (data parallel): bucket bounds / counts, received pairs, the owner's reduction, the gathered deltas
-  DevBuf<int> ex_off, ex_cnt, ex_allcnt, ex_rids, ex_red_ids, ex_nred, ex_allnred, ex_gids;
-  DevBuf<long long> ex_rrows, ex_red;
-  DevBuf<float> ex_delta, ex_gdelta;
-  DevBuf<unsigned long long> ex_red_total;
-  double ex_bytes_last = 0;       // bytes this rank SENT in the last step's exchange
-  // single-call multi-device training: replicas on engines 1 .. n-1 (owned; reps[0] unused) and this model's `gen` after the
-  // last call that left them bit-identical to it (anything else that locked the model since then forces a re-broadcast)
-  std::vector<goctr_model*> reps; uint64_t reps_gen = ~0ull;
-};
-
 namespace {
-
-int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v && *v ? atoi(v) : dflt;
-}
 
 // Slab heights of the weight-gradient launch.  fp32 MFMA work of co-resident workgroups serialises on a SIMD,
 // so the launch is sized to ONE equally expensive workgroup per CU: the 3-tile problems (dW0: ceil(Ip/48)
@@ -326,6 +114,7 @@ bool dw_wide_path(const goctr_model* m, int B) {
   return gemm_tn_multi_fits(nt_max) && tn_schedule_wide(m, B).ok;
 }
 
+}  // namespace
 int ensure_workspace(goctr_model* m, int B) {
   if (m->wsB >= B && m->tnS > 0) return 0;
   const int S = tn_max_slabs(B);   // upper bound over every schedule tn_schedule() can pick
@@ -379,6 +168,7 @@ RowSource make_source(const goctr_dataset* d, const goctr_emb* e) {
   }
   return s;
 }
+namespace {
 
 // dynamic LDS above 64 KiB needs an explicit opt-in per kernel
 template <class K>
@@ -466,6 +256,7 @@ int launch_tn(int kid, const float* A, int lda, int KT, const float* Dm, int ldd
   return launch_tn_cfg<3, 4, 32>(A, lda, KT, Dm, ldd, NT, M, rows_per_wg, 1, WN, slabs, slab_stride);
 }
 
+}  // namespace
 // opt every GEMM instantiation into > 64 KiB of dynamic LDS up front (never inside a stream capture)
 int init_kernel_attrs() {
   bool& done = engine().kernel_attrs_done;     // (function attributes are per device)
@@ -486,6 +277,7 @@ int init_kernel_attrs() {
   done = true;
   return 0;
 }
+namespace {
 
 int launch_attn_fwd(const AttnArgs& a) {
   ProfScope ps(GOCTR_K_ATTN_FWD);
@@ -596,16 +388,7 @@ int launch_attn_bwd(const AttnBwdArgs& a, int blocks) {
   return 0;
 }
 
-struct StepOpts {
-  bool train = true;        // false: forward only (predict)
-  bool update = true;       // false: stop after the reduce (parity entry)
-  int drop_mode = 0; float p0 = 0, p1 = 0; uint32_t seed = 0;
-  const goctr_train_cfg* tc = nullptr;
-  // pipelined steps (graph replay, single GPU): a step's h0 was computed by the PREVIOUS step's last launch
-  // (reduce_attn_kernel, ctr_kernels.h) -- launch_forward skips attn_fwd, launch_backward ends with the merged launch
-  bool pipelined = false;
-};
-
+}  // namespace
 // the fused chain kernel covers the reference's fixed hidden widths (200 -> 13 tiles, 80 -> 5 tiles)
 bool chain_ok(const goctr_model* m) {
   const int nt0 = m->H1p / 16;
@@ -614,14 +397,8 @@ bool chain_ok(const goctr_model* m) {
          chain_lds_bytes<5>(m->Ip, m->H1p, m->H2p) <= 160u * 1024u &&
          env_int("GOCTR_NO_CHAIN", 0) == 0;
 }
+namespace {
 
-// the bf16-split training chain (ctr_chain_x3.h) covers the reference's hidden widths with Ip in {144, 240} (cfg3 DIN /
-// the MovieLens-100k defaults, cfg4 YouTube) and the small test shape Ip = 32; hash dropout or none
-bool chain_x3_shape_ok(const goctr_model* m) {
-  const int nch0 = m->Ip / 16;
-  return m->H1p == 208 && m->H2p == 80 && (nch0 == 2 || nch0 == 9 || nch0 == 15) &&
-         (m->cfg.kind != GOCTR_DIN || m->Dp <= 32);
-}
 // training steps, and predict launches large enough to give every CU a 32-row tile (the forward-only variant; smaller
 // predict launches are latency-bound and keep ctr_fwd16_kernel)
 bool chain_x3_ok(const goctr_model* m, const StepOpts& o, int B) {
@@ -631,6 +408,7 @@ bool chain_x3_ok(const goctr_model* m, const StepOpts& o, int B) {
   return cdiv(B, 32) >= cus;
 }
 
+}  // namespace
 int rebuild_x3_images(goctr_model* m) {
   if (!m->x3_nch0) return 0;
   hipLaunchKernelGGL(x3_build_images_kernel, dim3((unsigned)cdiv(m->off2, 256)), dim3(256), 0, engine().stream, m->W.p, m->off1, m->off2,
@@ -638,6 +416,7 @@ int rebuild_x3_images(goctr_model* m) {
   GOCTR_HIP(hipGetLastError());
   return 0;
 }
+namespace {
 
 template <int NCH0>
 void launch_chain_x3_n(const ChainX3Args& a, dim3 grid, hipStream_t s, bool fwd) {
@@ -770,7 +549,7 @@ ChainArgs make_chain_args(goctr_model* m, const RowSource& src, int B, const Ste
 }
 
 AttnArgs make_attn_args(goctr_model* m, const RowSource& src, int B, const StepState* st, const FwdBufs& fb, bool fac);
-int attn_fast_mode(const goctr_model* m, const RowSource& src, int* groups);
+}  // namespace
 // A small serving pass in key mode as ONE launch (ctr_serve.h): the shapes with a compile-time attention variant at 8, 16
 // or 64 embedding columns, launches the 16-row forward kernel would take (too few rows for a 32-row tile per CU)
 bool serve16_ok(const goctr_model* m, const RowSource& src, int B) {
@@ -806,6 +585,7 @@ int launch_serve16(goctr_model* m, const RowSource& src, int B, const StepState*
   GOCTR_HIP(hipGetLastError());
   return 0;
 }
+namespace {
 
 int launch_chain(goctr_model* m, const RowSource& src, int B, const StepOpts& o, const StepState* st, const FwdBufs& fb) {
   if (chain_x3_ok(m, o, B)) return launch_chain_x3(m, src, B, o, st, fb);
@@ -868,6 +648,7 @@ AttnArgs make_attn_args(goctr_model* m, const RowSource& src, int B, const StepS
   return make_attn_args(m, src, B, st, train_bufs(m, par), fac);
 }
 
+}  // namespace
 // the compile-time mode launch_attn_fwd picks for this model's rows, or 0; `groups` = lanes per embedding row
 int attn_fast_mode(const goctr_model* m, const RowSource& src, int* groups) {
   const goctr_ctr_cfg& c = m->cfg;
@@ -877,6 +658,7 @@ int attn_fast_mode(const goctr_model* m, const RowSource& src, int* groups) {
   const bool small_table = (unsigned long long)(src.V + 1) * (unsigned long long)c.D * 4ull < (1ull << 32);   // (32-bit row offsets in those kernels)
   return !(vec4 && small_table && g * 4 == c.D && (g & (g - 1)) == 0) ? 0 : c.kind != GOCTR_DIN ? 1 : (c.att == GOCTR_ATT_COSINE ? 2 : 3);
 }
+namespace {
 // (Round 5 tried the next batch's attention on a second stream BESIDE the weight-gradient and reduce launches instead of inside
 // the step's last launch: it lost, 58.5 against 46.2 us per cfg3 step -- the two branches slow each other down by what they were
 // to hide, and a cross-stream edge in a captured graph costs ~6 us here; profiles/r05_fork_ab.txt, commits 0af81b4 .. ae775f3.)
@@ -917,9 +699,10 @@ int launch_reduce_attn(goctr_model* m, const RowSource& src, int B, const StepOp
   return 0;
 }
 
+}  // namespace
 // fbp: where a forward-only pass keeps its rows (null: the training workspace)
-int launch_forward(goctr_model* m, const RowSource& src, int B, const StepOpts& o, const StepState* st_override = nullptr,
-                   const FwdBufs* fbp = nullptr) {
+int launch_forward(goctr_model* m, const RowSource& src, int B, const StepOpts& o, const StepState* st_override,
+                   const FwdBufs* fbp) {
   const goctr_ctr_cfg& c = m->cfg;
   Engine& e = engine();
   const StepState* st = st_override ? st_override : m->st_cur();
@@ -949,6 +732,7 @@ int launch_forward(goctr_model* m, const RowSource& src, int B, const StepOpts& 
   if (launch_nn(GOCTR_K_GEMM_OUT, A1, m->H2p, m->W.p + m->off2, 16, B, m->H2p, 16, eo)) return -1;
   return 0;
 }
+namespace {
 
 // backward part up to and including the slab reduce: kernels 5-12
 AdamArgs make_adam_args(goctr_model* m, int B, const goctr_train_cfg& tc);
@@ -1372,11 +1156,12 @@ int emb_exchange_apply(goctr_model* m, const RowSource& src) {
 }
 
 int launch_reduce_part(goctr_model* m, const RowSource& src, int B, const StepOpts& o, bool advance, bool fuse_update, const ReduceArgs& ra);
+}  // namespace
 // stage 0: the whole backward; 1: everything before the slab reduce (the sparse embedding update ends with its send buffers
 // packed); 2: the slab reduce alone -- the two halves of a data-parallel step with trainable embeddings, whose all-to-all
 // runs between them (split3 below)
 int launch_backward(goctr_model* m, const RowSource& src, int B, const StepOpts& o, bool advance,
-                    bool fuse_update = false, int stage = 0) {
+                    bool fuse_update, int stage) {
   const goctr_ctr_cfg& c = m->cfg;
   Engine& e = engine();
   if (stage == 2) return launch_reduce_part(m, src, B, o, advance, fuse_update, m->pend_ra);
@@ -1558,6 +1343,7 @@ int launch_backward(goctr_model* m, const RowSource& src, int B, const StepOpts&
   if (stage == 1) { m->pend_ra = ra; return 0; }
   return launch_reduce_part(m, src, B, o, advance, fuse_update, ra);
 }
+namespace {
 
 int launch_reduce_part(goctr_model* m, const RowSource& src, int B, const StepOpts& o, bool advance, bool fuse_update, const ReduceArgs& ra) {
   const goctr_ctr_cfg& c = m->cfg;
@@ -1757,15 +1543,6 @@ int build_multi_graphs(goctr_model* m, const RowSource& src, int B, const StepOp
   return 0;
 }
 
-int set_state(goctr_model* m, unsigned gstep, unsigned slot, long long batch_idx, long long n_batches) {
-  StepState s{gstep, slot, batch_idx, n_batches};
-  m->pend_retarget = false;
-  if (m->ra_flag.p) GOCTR_HIP(hipMemsetAsync(m->ra_flag.p, 0, sizeof(unsigned int), engine().stream));   // (gstep may jump: no stale match)
-  GOCTR_HIP(hipMemcpyAsync(m->st_cur(), &s, sizeof s, hipMemcpyHostToDevice, engine().stream));
-  GOCTR_HIP(hipStreamSynchronize(engine().stream));
-  return 0;
-}
-
 // point the running state at another batch of another dataset without a host round trip (gstep stays on the device), and
 // give the state a call starts from its Adam bias corrections (ctr_kernels.h: StepState::corr1/2)
 __global__ void step_state_prepare_kernel(StepState* st, double beta1, double beta2, int retarget, long long batch_idx, long long n_batches) {
@@ -1774,21 +1551,8 @@ __global__ void step_state_prepare_kernel(StepState* st, double beta1, double be
   state_corrections(s, beta1, beta2);
   *st = s;
 }
-// (applied by run_steps' state-preparation launch: no kernel of its own)
-int retarget_state(goctr_model* m, long long batch_idx, long long n_batches) {
-  m->pend_retarget = true; m->pend_batch_idx = batch_idx; m->pend_n_batches = n_batches;
-  return 0;
-}
 
-int get_state(goctr_model* m, StepState* s) {
-  // (data parallel: the steps queued so far hold collectives -- wait for them under the communicator's watchdog, so that a peer
-  // that failed makes this rank's call fail instead of blocking in the copy below)
-  if (engine().comm_active() && comm_watch_stream()) return -1;
-  GOCTR_HIP(hipMemcpyAsync(s, m->st_cur(), sizeof *s, hipMemcpyDeviceToHost, engine().stream));
-  GOCTR_HIP(hipStreamSynchronize(engine().stream));
-  return 0;
-}
-
+}  // namespace
 StepOpts opts_from(const goctr_train_cfg* tc) {
   StepOpts o;
   o.tc = tc; o.drop_mode = tc->dropout_mode; o.p0 = tc->p0; o.p1 = tc->p1; o.seed = tc->seed;
@@ -1818,6 +1582,7 @@ int mark_weights_written(goctr_model* m) {
   m->weights_pending.store(true, std::memory_order_release);
   return 0;
 }
+namespace {
 
 // behind the last queued launch that writes the table's rows (embedding training): serve_wait_rows
 int emb_mark_written(goctr_emb* e) {
@@ -1840,8 +1605,10 @@ int ensure_w0pv(goctr_model* m) {
   return 0;
 }
 
-// queue n_steps training steps (graph replay unless profiling / disabled)
 int run_steps_impl(goctr_model* m, goctr_emb* emb, goctr_dataset* d, const goctr_train_cfg* tc, int n_steps);
+
+}  // namespace
+// queue n_steps training steps (graph replay unless profiling / disabled)
 int run_steps(goctr_model* m, goctr_emb* emb, goctr_dataset* d, const goctr_train_cfg* tc, int n_steps) {
   // A call that fails half way may already have queued launches that write the weights: the event is recorded on EVERY exit,
   // so a serving slot that takes the model's lock afterwards still waits for whatever was queued.
@@ -1855,6 +1622,8 @@ int run_steps(goctr_model* m, goctr_emb* emb, goctr_dataset* d, const goctr_trai
   }
   return rc;
 }
+namespace {
+
 int run_steps_impl(goctr_model* m, goctr_emb* emb, goctr_dataset* d, const goctr_train_cfg* tc, int n_steps) {
   Engine& e = engine();
   const int B = tc->batch;
@@ -1956,1564 +1725,4 @@ int run_steps_impl(goctr_model* m, goctr_emb* emb, goctr_dataset* d, const goctr
   return 0;
 }
 
-int upload_padded_weights(goctr_model* m, int tensor_id, const float* host, size_t n) {
-  const goctr_ctr_cfg& c = m->cfg;
-  std::vector<float> buf;
-  Engine& e = engine();
-  auto up = [&](float* dst, const std::vector<float>& v) -> int {
-    GOCTR_HIP(hipMemcpyAsync(dst, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice, e.stream));
-    GOCTR_HIP(hipStreamSynchronize(e.stream));
-    return 0;
-  };
-  switch (tensor_id) {
-    case GOCTR_W0: {
-      GOCTR_CHECK(n == (size_t)m->I * c.H1, "W0 expects %d floats, got %zu", m->I * c.H1, n);
-      buf.assign((size_t)m->Ip * m->H1p, 0.f);
-      for (int r = 0; r < m->I; ++r) for (int k = 0; k < c.H1; ++k) buf[(size_t)r * m->H1p + k] = host[(size_t)r * c.H1 + k];
-      if (up(m->W.p, buf)) return -1;
-      std::vector<float> t((size_t)m->H1p * m->Dp, 0.f), ti((size_t)m->H1p * m->Dp, 0.f), wi((size_t)m->Ip * m->H1p, 0.f);
-      for (int d = 0; d < c.D; ++d) for (int k = 0; k < c.H1; ++k) {
-        t[(size_t)k * m->Dp + d] = host[(size_t)(c.U + d) * c.H1 + k];
-        ti[img_index(k, d, m->Dp)] = host[(size_t)(c.U + d) * c.H1 + k];
-      }
-      for (int r = 0; r < m->I; ++r) for (int k = 0; k < c.H1; ++k) wi[img_index(r, k, m->H1p)] = host[(size_t)r * c.H1 + k];
-      if (up(m->img(0), wi) || up(m->img(3), ti)) return -1;
-      return up(m->W0sT.p, t);
-    }
-    case GOCTR_W1: {
-      GOCTR_CHECK(n == (size_t)c.H1 * c.H2, "W1 expects %d floats, got %zu", c.H1 * c.H2, n);
-      buf.assign((size_t)m->H1p * m->H2p, 0.f);
-      std::vector<float> t((size_t)m->H2p * m->H1p, 0.f);
-      for (int r = 0; r < c.H1; ++r) for (int k = 0; k < c.H2; ++k) {
-        buf[(size_t)r * m->H2p + k] = host[(size_t)r * c.H2 + k];
-        t[(size_t)k * m->H1p + r] = host[(size_t)r * c.H2 + k];
-      }
-      std::vector<float> wi((size_t)m->H1p * m->H2p, 0.f), ti((size_t)m->H2p * m->H1p, 0.f);
-      for (int r = 0; r < c.H1; ++r) for (int k = 0; k < c.H2; ++k) {
-        wi[img_index(r, k, m->H2p)] = host[(size_t)r * c.H2 + k];
-        ti[img_index(k, r, m->H1p)] = host[(size_t)r * c.H2 + k];
-      }
-      if (up(m->W.p + m->off1, buf) || up(m->img(1), wi) || up(m->img(2), ti)) return -1;
-      return up(m->W1T.p, t);
-    }
-    case GOCTR_W2: {
-      GOCTR_CHECK(n == (size_t)c.H2, "W2 expects %d floats, got %zu", c.H2, n);
-      buf.assign((size_t)m->H2p * 16, 0.f);
-      std::vector<float> t((size_t)16 * m->H2p, 0.f);
-      for (int r = 0; r < c.H2; ++r) { buf[(size_t)r * 16] = host[r]; t[r] = host[r]; }
-      if (up(m->W.p + m->off2, buf)) return -1;
-      return up(m->W2T.p, t);
-    }
-    case GOCTR_ATT0: {
-      GOCTR_CHECK(n == (size_t)c.T, "att0 expects %d floats, got %zu", c.T, n);
-      buf.assign((size_t)m->Tp, 0.f);
-      for (int t = 0; t < c.T; ++t) buf[t] = host[t];
-      return up(m->W.p + m->offa, buf);
-    }
-  }
-  set_error("unknown tensor id %d", tensor_id);
-  return -1;
-}
-
-int download_padded(goctr_model* m, const float* flat_dev, int tensor_id, float* host, size_t n) {
-  const goctr_ctr_cfg& c = m->cfg;
-  Engine& e = engine();
-  std::vector<float> buf;
-  auto down = [&](const float* src, size_t cnt) -> int {
-    buf.resize(cnt);
-    GOCTR_HIP(hipMemcpyAsync(buf.data(), src, cnt * sizeof(float), hipMemcpyDeviceToHost, e.stream));
-    GOCTR_HIP(hipStreamSynchronize(e.stream));
-    return 0;
-  };
-  switch (tensor_id) {
-    case GOCTR_W0:
-      GOCTR_CHECK(n == (size_t)m->I * c.H1, "W0 expects %d floats, got %zu", m->I * c.H1, n);
-      if (down(flat_dev, (size_t)m->Ip * m->H1p)) return -1;
-      for (int r = 0; r < m->I; ++r) for (int k = 0; k < c.H1; ++k) host[(size_t)r * c.H1 + k] = buf[(size_t)r * m->H1p + k];
-      return 0;
-    case GOCTR_W1:
-      GOCTR_CHECK(n == (size_t)c.H1 * c.H2, "W1 expects %d floats, got %zu", c.H1 * c.H2, n);
-      if (down(flat_dev + m->off1, (size_t)m->H1p * m->H2p)) return -1;
-      for (int r = 0; r < c.H1; ++r) for (int k = 0; k < c.H2; ++k) host[(size_t)r * c.H2 + k] = buf[(size_t)r * m->H2p + k];
-      return 0;
-    case GOCTR_W2:
-      GOCTR_CHECK(n == (size_t)c.H2, "W2 expects %d floats, got %zu", c.H2, n);
-      if (down(flat_dev + m->off2, (size_t)m->H2p * 16)) return -1;
-      for (int r = 0; r < c.H2; ++r) host[r] = buf[(size_t)r * 16];
-      return 0;
-    case GOCTR_ATT0:
-      GOCTR_CHECK(n == (size_t)c.T, "att0 expects %d floats, got %zu", c.T, n);
-      if (down(flat_dev + m->offa, (size_t)m->Tp)) return -1;
-      for (int t = 0; t < c.T; ++t) host[t] = buf[t];
-      return 0;
-  }
-  set_error("unknown tensor id %d", tensor_id);
-  return -1;
-}
-
 }  // namespace
-
-extern "C" {
-
-void goctr_train_cfg_default(goctr_train_cfg* c) {
-  memset(c, 0, sizeof *c);
-  c->batch = 200; c->epochs = 200; c->early_stop = 20;  // dinimpl_test.go:36-43
-  c->lr = 0.01; c->l2 = 0.0001;                           // model.go:88
-  c->beta1 = 0.9; c->beta2 = 0.999; c->eps = 1e-8;
-  c->adam_div_by_batch = 1; c->adam_l2_before_batch_div = 1;
-  c->dropout_mode = 2; c->p0 = 0.005f; c->p1 = 0.005f; c->seed = 42;   // din.go:204-205,307-312: Dropout is always on
-}
-
-int goctr_model_create(const goctr_ctr_cfg* cfg, goctr_model** out) {
-  GOCTR_ENTER();
-  GOCTR_CHECK(cfg && out, "goctr_model_create: null argument");
-  GOCTR_CHECK(cfg->kind == GOCTR_DIN || cfg->kind == GOCTR_YOUTUBE, "unknown model kind %d", cfg->kind);
-  GOCTR_CHECK(cfg->U >= 0 && cfg->T > 0 && cfg->D > 0 && cfg->C >= 0 && cfg->H1 > 0 && cfg->H2 > 0, "bad model dims");
-  GOCTR_CHECK(cfg->D <= 256, "embedding dim %d > 256 not supported", cfg->D);
-  if (init_kernel_attrs()) return -1;
-  std::unique_ptr<goctr_model> m(new goctr_model);
-  m->cfg = *cfg;
-  m->I = cfg->U + 2 * cfg->D + cfg->C;
-  m->Ip = round_up(m->I, 16); m->H1p = round_up(cfg->H1, 16); m->H2p = round_up(cfg->H2, 16);
-  m->Dp = round_up(cfg->D, 16); m->Tp = round_up(cfg->T, 16);
-  m->off1 = m->Ip * m->H1p; m->off2 = m->off1 + m->H1p * m->H2p; m->offa = m->off2 + m->H2p * 16;
-  m->nflat = m->offa + m->Tp;
-  if (m->W.alloc(m->nflat) || m->G.alloc((size_t)m->nflat + 1) || m->Mo.alloc(m->nflat) || m->Vo.alloc(m->nflat)) return -1;
-  if (m->W1T.alloc((size_t)m->H2p * m->H1p) || m->W2T.alloc((size_t)16 * m->H2p) || m->W0sT.alloc((size_t)m->H1p * m->Dp)) return -1;
-  if (m->Wimg.alloc((size_t)m->off1 + 2 * (size_t)m->H1p * m->H2p + (size_t)m->H1p * m->Dp)) return -1;
-  if (chain_x3_shape_ok(m.get())) {
-    m->x3_nch0 = m->Ip / 16;
-    if (m->Wx3.alloc(cx_images_elems(m->x3_nch0))) return -1;      // zero = the images of all-zero weights
-  }
-  if (m->st.alloc(2) || m->costs.alloc(COST_RING)) return -1;
-  std::vector<float> ones(cfg->T, 1.0f);  // din.go:181 att0 = 1
-  if (upload_padded_weights(m.get(), GOCTR_ATT0, ones.data(), ones.size())) return -1;
-  if (set_state(m.get(), 0, 0, 0, 1)) return -1;
-  *out = m.release();
-  return 0;
-}
-
-void goctr_model_destroy(goctr_model* m) {
-  if (!m) return;
-  for (goctr_model* r : m->reps) goctr_model_destroy(r);        // (replicas of the multi-device entry, on their own engines)
-  m->reps.clear();
-  EngineScope on(m->eng);
-  std::lock_guard<std::recursive_mutex> lk(m->eng->mu);
-  // (the engine's own streams, not hipDeviceSynchronize: a device-wide wait invalidates the stream capture of any OTHER thread
-  // that is building its step graphs on this device -- a second logical rank, or a training goroutine beside a serving one;
-  // serving passes are synchronous, none of this model's is in flight once its caller returned)
-  if (engine().inited) { (void)hipStreamSynchronize(engine().stream); (void)hipStreamSynchronize(engine().side); }
-  m->graph.destroy();
-  if (m->ev_weights) (void)hipEventDestroy(m->ev_weights);
-  delete m;
-}
-
-int goctr_model_set_weights(goctr_model* m, int tensor_id, const float* host, size_t n) {
-  GOCTR_ENTER_H(m);
-  GOCTR_CHECK(m && host, "goctr_model_set_weights: null argument");
-  std::unique_lock<std::shared_mutex> lk(m->mu); ++m->gen;
-  if (upload_padded_weights(m, tensor_id, host, n)) return -1;
-  if (tensor_id == GOCTR_W0) m->w0pv_live = false;
-  if ((tensor_id == GOCTR_W0 || tensor_id == GOCTR_W1) && rebuild_x3_images(m)) return -1;
-  return mark_weights_written(m);
-}
-
-int goctr_model_get_weights(goctr_model* m, int tensor_id, float* host, size_t n) {
-  GOCTR_ENTER_H(m);
-  GOCTR_CHECK(m && host, "goctr_model_get_weights: null argument");
-  std::unique_lock<std::shared_mutex> lk(m->mu); ++m->gen;
-  return download_padded(m, m->W.p, tensor_id, host, n);
-}
-
-// Adam moments of one tensor in the tensor's own (unpadded, row-major) shape: what a checkpoint needs next to the
-// weights to resume `model.Train` where it stopped.  which = 0: first moment, 1: second moment.
-int upload_padded_flat(goctr_model* m, float* flat_dev, int tensor_id, const float* host, size_t n) {
-  const goctr_ctr_cfg& c = m->cfg;
-  std::vector<float> buf;
-  size_t off = 0;
-  switch (tensor_id) {
-    case GOCTR_W0:
-      GOCTR_CHECK(n == (size_t)m->I * c.H1, "W0 expects %d floats, got %zu", m->I * c.H1, n);
-      buf.assign((size_t)m->Ip * m->H1p, 0.f);
-      for (int r = 0; r < m->I; ++r) for (int k = 0; k < c.H1; ++k) buf[(size_t)r * m->H1p + k] = host[(size_t)r * c.H1 + k];
-      break;
-    case GOCTR_W1:
-      GOCTR_CHECK(n == (size_t)c.H1 * c.H2, "W1 expects %d floats, got %zu", c.H1 * c.H2, n);
-      buf.assign((size_t)m->H1p * m->H2p, 0.f); off = m->off1;
-      for (int r = 0; r < c.H1; ++r) for (int k = 0; k < c.H2; ++k) buf[(size_t)r * m->H2p + k] = host[(size_t)r * c.H2 + k];
-      break;
-    case GOCTR_W2:
-      GOCTR_CHECK(n == (size_t)c.H2, "W2 expects %d floats, got %zu", c.H2, n);
-      buf.assign((size_t)m->H2p * 16, 0.f); off = m->off2;
-      for (int r = 0; r < c.H2; ++r) buf[(size_t)r * 16] = host[r];
-      break;
-    case GOCTR_ATT0:
-      GOCTR_CHECK(n == (size_t)c.T, "att0 expects %d floats, got %zu", c.T, n);
-      buf.assign((size_t)m->Tp, 0.f); off = m->offa;
-      for (int t = 0; t < c.T; ++t) buf[t] = host[t];
-      break;
-    default:
-      GOCTR_CHECK(false, "unknown tensor id %d", tensor_id);
-  }
-  GOCTR_HIP(hipMemcpyAsync(flat_dev + off, buf.data(), buf.size() * sizeof(float), hipMemcpyHostToDevice, engine().stream));
-  GOCTR_HIP(hipStreamSynchronize(engine().stream));
-  return 0;
-}
-
-int goctr_model_get_moments(goctr_model* m, int tensor_id, int which, float* host, size_t n) {
-  GOCTR_ENTER_H(m);
-  GOCTR_CHECK(m && host && (which == 0 || which == 1), "goctr_model_get_moments: bad argument");
-  std::unique_lock<std::shared_mutex> lk(m->mu); ++m->gen;
-  return download_padded(m, which ? m->Vo.p : m->Mo.p, tensor_id, host, n);
-}
-
-int goctr_model_set_moments(goctr_model* m, int tensor_id, int which, const float* host, size_t n) {
-  GOCTR_ENTER_H(m);
-  GOCTR_CHECK(m && host && (which == 0 || which == 1), "goctr_model_set_moments: bad argument");
-  std::unique_lock<std::shared_mutex> lk(m->mu); ++m->gen;
-  return upload_padded_flat(m, which ? m->Vo.p : m->Mo.p, tensor_id, host, n);
-}
-
-// Global step counter: Adam's iteration number and the dropout stream position.
-int goctr_model_get_step(goctr_model* m, uint32_t* step) {
-  GOCTR_ENTER_H(m);
-  GOCTR_CHECK(m && step, "goctr_model_get_step: null argument");
-  std::unique_lock<std::shared_mutex> lk(m->mu); ++m->gen;
-  StepState s;
-  if (get_state(m, &s)) return -1;
-  *step = s.gstep;
-  return 0;
-}
-
-int goctr_model_set_step(goctr_model* m, uint32_t step) {
-  GOCTR_ENTER_H(m);
-  GOCTR_CHECK(m, "goctr_model_set_step: null argument");
-  std::unique_lock<std::shared_mutex> lk(m->mu); ++m->gen;
-  return set_state(m, step, 0, 0, 1);
-}
-
-int goctr_model_set_embedding_training(goctr_model* m, double lr) {
-  GOCTR_ENTER_H(m);
-  GOCTR_CHECK(m && lr >= 0 && lr == lr, "goctr_model_set_embedding_training: bad arguments");
-  std::unique_lock<std::shared_mutex> lk(m->mu); ++m->gen;
-  GOCTR_CHECK(lr == 0 || m->cfg.D <= 64, "embedding training supports D <= 64 (got %d)", m->cfg.D);
-  m->emb_lr = (float)lr;
-  m->w0pv_live = false;            // (the Adam kernels only keep W0pvT current while embedding training is on)
-  m->graph.destroy();
-  return 0;
-}
-
-int goctr_model_get_emb_plan(goctr_model* m, int64_t* n_batches, int64_t* n_pairs, int64_t* n_slots, int32_t* pair, int32_t* pslot,
-                             int32_t* pid, int32_t* slot_id, uint32_t* slot_off, int64_t* pair_off, int64_t* slot_base) {
-  GOCTR_ENTER_H(m);
-  GOCTR_CHECK(m, "goctr_model_get_emb_plan: null argument");
-  std::unique_lock<std::shared_mutex> lk(m->mu); ++m->gen;
-  const auto& P = m->plan;
-  GOCTR_CHECK(P.valid, "goctr_model_get_emb_plan: no plan resident (run an embedding-training step first)");
-  if (n_batches) *n_batches = P.nb;
-  if (n_pairs) *n_pairs = P.total_pairs;
-  if (n_slots) *n_slots = P.total_slots;
-  const size_t np = (size_t)P.total_pairs, ns = (size_t)P.total_slots, nb = (size_t)P.nb;
-  if (pair && np && P.pair.download(pair, np)) return -1;
-  if (pslot && np && P.pslot.download(pslot, np)) return -1;
-  if (pid && np && P.pid.download(pid, np)) return -1;
-  if (slot_id && ns && P.slot_id.download(slot_id, ns)) return -1;
-  if (slot_off && P.slot_off.download(slot_off, ns + nb)) return -1;
-  if (pair_off && P.pair_off.download(reinterpret_cast<long long*>(pair_off), nb + 1)) return -1;
-  if (slot_base && P.slot_base.download(reinterpret_cast<long long*>(slot_base), nb + 1)) return -1;
-  return 0;
-}
-
-int goctr_model_emb_plan_build_ms(goctr_model* m, double* ms, int64_t* n_batches) {
-  GOCTR_ENTER_H(m);
-  GOCTR_CHECK(m, "goctr_model_emb_plan_build_ms: null argument");
-  std::unique_lock<std::shared_mutex> lk(m->mu); ++m->gen;
-  GOCTR_CHECK(m->plan.valid, "goctr_model_emb_plan_build_ms: no plan resident (run an embedding-training step first)");
-  if (ms) *ms = m->plan.build_ms;
-  if (n_batches) *n_batches = m->plan.nb;
-  return 0;
-}
-
-int goctr_model_sparse_exchange_bytes(goctr_model* m, double* bytes) {
-  GOCTR_ENTER_H(m);
-  GOCTR_CHECK(m && bytes, "goctr_model_sparse_exchange_bytes: null argument");
-  std::unique_lock<std::shared_mutex> lk(m->mu); ++m->gen;
-  *bytes = m->emb_comm ? m->ex_bytes_last : 0.0;      // (emb_comm: the last step's sparse update ran with a communicator)
-  return 0;
-}
-
-int goctr_emb_get_rows(goctr_emb* e, int64_t first, int64_t n, float* host_rows) {
-  GOCTR_ENTER_H(e);
-  GOCTR_CHECK(e && host_rows && first >= 0 && n >= 0 && first + n <= e->V, "goctr_emb_get_rows: range out of bounds");
-  return n ? e->rows.download(host_rows, (size_t)n * e->D, (size_t)first * e->D) : 0;
-}
-
-int goctr_model_reset_optimizer(goctr_model* m) {
-  GOCTR_ENTER_H(m);
-  std::unique_lock<std::shared_mutex> lk(m->mu); ++m->gen;
-  GOCTR_HIP(hipMemsetAsync(m->Mo.p, 0, sizeof(float) * m->nflat, engine().stream));
-  GOCTR_HIP(hipMemsetAsync(m->Vo.p, 0, sizeof(float) * m->nflat, engine().stream));
-  return set_state(m, 0, 0, 0, 1);
-}
-
-// ------------------------------------------------------------------ embedding table / gather
-int goctr_emb_create(int64_t V, int D, const float* host_rows, goctr_emb** out) {
-  GOCTR_ENTER();
-  GOCTR_CHECK(V > 0 && D > 0 && out, "goctr_emb_create: bad arguments");
-  std::unique_ptr<goctr_emb> e(new goctr_emb);
-  e->V = V; e->D = D;
-  if (e->rows.alloc((size_t)(V + 1) * D)) return -1;   // row V stays all-zero: where missing ids point (attention kernels)
-  if (host_rows && e->rows.upload(host_rows, (size_t)V * D)) return -1;
-  *out = e.release();
-  return 0;
-}
-int goctr_emb_set_rows(goctr_emb* e, int64_t first, int64_t n, const float* host_rows) {
-  GOCTR_ENTER_H(e);
-  GOCTR_CHECK(e && host_rows && first >= 0 && n >= 0 && first + n <= e->V, "goctr_emb_set_rows: range out of bounds");
-  std::unique_lock<std::shared_mutex> lk(e->mu);       // (serving passes read the rows under the shared lock; the upload below is synchronous)
-  ++e->version;
-  return n ? e->rows.upload(host_rows, (size_t)n * e->D, (size_t)first * e->D) : 0;
-}
-void goctr_emb_destroy(goctr_emb* e) {
-  if (!e) return;
-  for (goctr_emb* r : e->reps) goctr_emb_destroy(r);
-  e->reps.clear();
-  EngineScope on(e->eng);
-  std::lock_guard<std::recursive_mutex> lk(e->eng->mu);
-  if (engine().inited) (void)hipStreamSynchronize(engine().stream);
-  if (e->ev_rows) (void)hipEventDestroy(e->ev_rows);
-  delete e;
-}
-
-int goctr_gather_rows(goctr_emb* e, const int32_t* ub_ids, const int32_t* item_ids, const float* user_feat, int U,
-                      const float* ctx_feat, int C, int T, int64_t rows, float* X_out) {
-  GOCTR_ENTER_H(e);
-  GOCTR_CHECK(e && X_out && rows >= 0, "goctr_gather_rows: bad arguments");
-  if (rows == 0) return 0;
-  const int xcols = U + T * e->D + e->D + C;
-  DevBuf<int32_t> dub, dit; DevBuf<float> duf, dcf, dX;
-  if (dub.alloc((size_t)rows * T, false) || dit.alloc(rows, false) || duf.alloc((size_t)rows * U, false) ||
-      dcf.alloc((size_t)rows * C, false) || dX.alloc((size_t)rows * xcols, false)) return -1;
-  if (dub.upload(ub_ids, (size_t)rows * T) || dit.upload(item_ids, rows)) return -1;
-  if (U && duf.upload(user_feat, (size_t)rows * U)) return -1;
-  if (C && dcf.upload(ctx_feat, (size_t)rows * C)) return -1;
-  GatherArgs a{e->rows.p, e->V, e->D, T, U, C, dub.p, dit.p, duf.p, dcf.p, rows, dX.p, xcols};
-  hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, engine().stream, a);
-  GOCTR_HIP(hipGetLastError());
-  return dX.download(X_out, (size_t)rows * xcols);
-}
-
-// ------------------------------------------------------------------ datasets
-int goctr_dataset_create_dense(const float* X, const float* Y, int64_t rows, int xcols, const int ranges[8],
-                               goctr_dataset** out) {
-  GOCTR_ENTER();
-  GOCTR_CHECK(X && rows > 0 && xcols > 0 && ranges && out, "goctr_dataset_create_dense: bad arguments");
-  std::unique_ptr<goctr_dataset> d(new goctr_dataset);
-  d->id_mode = false; d->rows = rows; d->xcols = xcols;
-  memcpy(d->ranges, ranges, sizeof d->ranges);
-  if (d->X.alloc((size_t)rows * xcols, false) || d->X.upload(X, (size_t)rows * xcols)) return -1;
-  if (Y) { if (d->Y.alloc(rows, false) || d->Y.upload(Y, rows)) return -1; d->has_y = true; }
-  *out = d.release();
-  return 0;
-}
-
-int goctr_dataset_create_ids(const int32_t* ub_ids, const int32_t* item_ids, const float* user_feat, int U,
-                             const float* ctx_feat, int C, int T, const float* Y, int64_t rows, goctr_dataset** out) {
-  GOCTR_ENTER();
-  GOCTR_CHECK(ub_ids && item_ids && rows > 0 && T > 0 && out, "goctr_dataset_create_ids: bad arguments");
-  std::unique_ptr<goctr_dataset> d(new goctr_dataset);
-  d->id_mode = true; d->rows = rows; d->U = U; d->C = C; d->T = T;
-  if (d->ub_ids.alloc((size_t)rows * T, false) || d->ub_ids.upload(ub_ids, (size_t)rows * T)) return -1;
-  if (d->item_ids.alloc(rows, false) || d->item_ids.upload(item_ids, rows)) return -1;
-  if (d->ufeat.alloc((size_t)rows * U, false) || (U && d->ufeat.upload(user_feat, (size_t)rows * U))) return -1;
-  if (d->cfeat.alloc((size_t)rows * C, false) || (C && d->cfeat.upload(ctx_feat, (size_t)rows * C))) return -1;
-  if (Y) { if (d->Y.alloc(rows, false) || d->Y.upload(Y, rows)) return -1; d->has_y = true; }
-  *out = d.release();
-  return 0;
-}
-void goctr_dataset_destroy(goctr_dataset* d) {
-  if (!d) return;
-  for (goctr_dataset* s : d->shards) goctr_dataset_destroy(s);
-  d->shards.clear();
-  EngineScope on(d->eng);
-  std::lock_guard<std::recursive_mutex> lk(d->eng->mu);
-  if (engine().inited) (void)hipStreamSynchronize(engine().stream);   // queued (asynchronous) steps may still read the rows
-  delete d;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------ device-side sample assembly
-// ubcache.UserBehaviorCache (feature/ubcache/cache.go) as a CSR in HBM + the per-sample gather of GetSampleVector
-// (recommend/rcmd.go:460-536) as one kernel: keys (user, item, timestamp) -> behaviour ids, user / item feature rows.
-struct goctr_ubcache {
-  goctr::Engine* const eng = &goctr::engine();   // the engine (device, streams, arena) the handle was created on
-  int64_t n_users = 0, nnz = 0;
-  DevBuf<long long> off, ts;
-  DevBuf<int32_t> items;
-};
-
-namespace {
-// TimeSeq.Filter (cache.go:71-94) for one key: the sequence is newest-first, so "the first i with Ts[i] <= maxTs"
-// is a lower bound found by bisection; then up to T items from there.
-__global__ __launch_bounds__(256) void assemble_keys_kernel(const long long* __restrict__ off, const int32_t* __restrict__ seq_items,
-                                                            const long long* __restrict__ seq_ts, long long n_users,
-                                                            const float* __restrict__ user_table, int U,
-                                                            const float* __restrict__ item_table, long long n_items, int C,
-                                                            const int32_t* __restrict__ users, const int32_t* __restrict__ items,
-                                                            const long long* __restrict__ ts, long long rows, int T,
-                                                            int32_t* __restrict__ ub_ids, float* __restrict__ ufeat,
-                                                            float* __restrict__ cfeat, int32_t* __restrict__ item_out,
-                                                            unsigned char* __restrict__ failed) {
-  const int lane = threadIdx.x & 63;
-  const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);   // one wavefront per sample
-  if (r >= rows) return;
-  // the key's three fields first, back to back: in a small serving pass they sit in pinned HOST memory (zero-copy), and
-  // fetched one by one where they are used they were three PCIe round trips in a row (7.8 us for a 256-key pass)
-  const int u = users[r];
-  const int it_key = items ? items[r] : -1;
-  const long long ts_key = ts ? ts[r] : 0;
-  bool uok = u >= 0 && u < n_users;
-  if (failed) {
-    // BatchPredict (rcmd.go:291-307): a key whose GetUserFeature / GetItemFeature fails is scored as the ALL-zero row
-    // (user features, behaviours, item embedding and item features alike)
-    const int it = it_key;
-    const bool ok = uok && it >= 0 && it < n_items;
-    if (lane == 0) { failed[r] = ok ? 0 : 1; item_out[r] = ok ? it : -1; }
-    if (!ok) {
-      for (int j = lane; j < T; j += 64) ub_ids[r * T + j] = -1;
-      for (int j = lane; j < U; j += 64) ufeat[r * U + j] = 0.f;
-      for (int j = lane; j < C; j += 64) cfeat[r * C + j] = 0.f;
-      return;
-    }
-  }
-  long long first = 0, cnt = 0;
-  const long long b = (uok && off) ? off[u] : 0, len = (uok && off) ? off[u + 1] - b : 0;   // off == NULL: no behaviour cache
-  if (len > 0) {
-    const long long mts = ts_key;
-    // first i with seq_ts[b + i] <= mts (descending order); mts == 0 means "from the newest" (cache.go:72-74: maxTs = Ts[0])
-    long long lo = 0;
-    if (mts != 0) {
-      if (len <= 256) {
-        // short histories (the common case): 64 entries per coalesced load and one ballot instead of a chain of ~7 dependent
-        // loads -- the serving pass of a Rank call is latency, not work
-        lo = len;
-        for (long long base = 0; base < len; base += 64) {
-          const long long i = base + lane;
-          const unsigned long long le = __ballot(i < len && seq_ts[b + i] <= mts);
-          if (le) { lo = base + (long long)__builtin_ctzll(le); break; }
-        }
-      } else {
-        long long hi = len;
-        while (lo < hi) {
-          const long long mid = (lo + hi) >> 1;
-          if (seq_ts[b + mid] <= mts) hi = mid; else lo = mid + 1;
-        }
-      }
-    }
-    first = lo;
-    cnt = len - first < T ? len - first : T;
-  }
-  if (ub_ids)
-    for (int j = lane; j < T; j += 64) ub_ids[r * T + j] = j < cnt ? seq_items[b + first + j] : -1;
-  if (ufeat)
-    for (int j = lane; j < U; j += 64) ufeat[r * U + j] = uok ? user_table[(long long)u * U + j] : 0.f;
-  if (cfeat) {
-    const int it = it_key;
-    const bool iok = it >= 0 && it < n_items;
-    for (int j = lane; j < C; j += 64) cfeat[r * C + j] = iok ? item_table[(long long)it * C + j] : 0.f;
-  }
-}
-}  // namespace
-
-extern "C" {
-
-int goctr_ubcache_create(int64_t n_users, const int64_t* off, const int32_t* items, const int64_t* ts, goctr_ubcache** out) {
-  GOCTR_ENTER();
-  GOCTR_CHECK(n_users > 0 && off && out && off[0] == 0, "goctr_ubcache_create: bad arguments");
-  const int64_t nnz = off[n_users];
-  GOCTR_CHECK(nnz >= 0 && (nnz == 0 || (items && ts)), "goctr_ubcache_create: sequences missing");
-  for (int64_t u = 0; u < n_users; ++u) {
-    GOCTR_CHECK(off[u + 1] >= off[u], "goctr_ubcache_create: offsets must be non-decreasing");
-    for (int64_t k = off[u] + 1; k < off[u + 1]; ++k)
-      GOCTR_CHECK(ts[k] <= ts[k - 1], "goctr_ubcache_create: user %lld's sequence is not in timestamp-descending order "
-                  "(cache.go:8 TimeSeq)", (long long)u);
-  }
-  std::unique_ptr<goctr_ubcache> c(new goctr_ubcache);
-  c->n_users = n_users; c->nnz = nnz;
-  std::vector<long long> o(off, off + n_users + 1), t(ts, ts + nnz);
-  if (c->off.alloc(o.size(), false) || c->off.upload(o.data(), o.size())) return -1;
-  if (c->items.alloc((size_t)nnz, false) || (nnz && c->items.upload(items, (size_t)nnz))) return -1;
-  if (c->ts.alloc((size_t)nnz, false) || (nnz && c->ts.upload(t.data(), (size_t)nnz))) return -1;
-  *out = c.release();
-  return 0;
-}
-void goctr_ubcache_destroy(goctr_ubcache* c) { delete c; }
-
-int goctr_ubcache_get(goctr_ubcache* c, const int32_t* users, const int64_t* max_ts, int64_t rows, int T, int32_t* out_ids) {
-  GOCTR_ENTER_H(c);
-  GOCTR_CHECK(c && users && out_ids && rows > 0 && T > 0, "goctr_ubcache_get: bad arguments");
-  DevBuf<int32_t> du, dout; DevBuf<long long> dts;
-  std::vector<long long> t(rows, 0);
-  if (max_ts) for (int64_t i = 0; i < rows; ++i) t[i] = max_ts[i];
-  if (du.alloc(rows, false) || du.upload(users, rows) || dts.alloc(rows, false) || dts.upload(t.data(), rows) ||
-      dout.alloc((size_t)rows * T, false)) return -1;
-  hipLaunchKernelGGL(assemble_keys_kernel, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, engine().stream, c->off.p, c->items.p,
-                     c->ts.p, (long long)c->n_users, (const float*)nullptr, 0, (const float*)nullptr, 0LL, 0, du.p,
-                     (const int32_t*)nullptr, dts.p, (long long)rows, T, dout.p, (float*)nullptr, (float*)nullptr,
-                     (int32_t*)nullptr, (unsigned char*)nullptr);
-  GOCTR_HIP(hipGetLastError());
-  return dout.download(out_ids, (size_t)rows * T);
-}
-
-int goctr_dataset_create_keys(goctr_ubcache* c, const float* user_table, int64_t n_users, int U, const float* item_table,
-                              int64_t n_items, int C, const int32_t* users, const int32_t* items, const int64_t* ts,
-                              const float* Y, int64_t rows, int T, goctr_dataset** out) {
-  GOCTR_ENTER_H(c);
-  GOCTR_CHECK(c && users && items && rows > 0 && T > 0 && out && n_items >= 0 && U >= 0 && C >= 0,
-              "goctr_dataset_create_keys: bad arguments");
-  GOCTR_CHECK(n_users == c->n_users, "goctr_dataset_create_keys: user table has %lld rows, the behaviour cache %lld users",
-              (long long)n_users, (long long)c->n_users);
-  GOCTR_CHECK((U == 0 || user_table) && (C == 0 || item_table), "goctr_dataset_create_keys: feature table missing");
-  std::unique_ptr<goctr_dataset> d(new goctr_dataset);
-  d->id_mode = true; d->rows = rows; d->U = U; d->C = C; d->T = T;
-  DevBuf<float> dut, dit; DevBuf<int32_t> du; DevBuf<long long> dts;
-  std::vector<long long> t(rows, 0);
-  if (ts) for (int64_t i = 0; i < rows; ++i) t[i] = ts[i];
-  if (dut.alloc((size_t)n_users * U, false) || (U && dut.upload(user_table, (size_t)n_users * U))) return -1;
-  if (dit.alloc((size_t)n_items * C, false) || (C && dit.upload(item_table, (size_t)n_items * C))) return -1;
-  if (du.alloc(rows, false) || du.upload(users, rows) || dts.alloc(rows, false) || dts.upload(t.data(), rows)) return -1;
-  if (d->ub_ids.alloc((size_t)rows * T, false) || d->item_ids.alloc(rows, false) || d->item_ids.upload(items, rows)) return -1;
-  if (d->ufeat.alloc((size_t)rows * U, false) || d->cfeat.alloc((size_t)rows * C, false)) return -1;
-  hipLaunchKernelGGL(assemble_keys_kernel, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, engine().stream, c->off.p, c->items.p,
-                     c->ts.p, (long long)c->n_users, dut.p, U, dit.p, (long long)n_items, C, du.p, d->item_ids.p, dts.p,
-                     (long long)rows, T, d->ub_ids.p, d->ufeat.p, d->cfeat.p, (int32_t*)nullptr, (unsigned char*)nullptr);
-  GOCTR_HIP(hipGetLastError());
-  GOCTR_HIP(hipStreamSynchronize(engine().stream));   // the temporaries above are released on return
-  if (Y) { if (d->Y.alloc(rows, false) || d->Y.upload(Y, rows)) return -1; d->has_y = true; }
-  *out = d.release();
-  return 0;
-}
-
-// read back the assembled keys of an id-mode dataset (tests, debugging)
-int goctr_dataset_get_ids(goctr_dataset* d, int32_t* ub_ids, float* user_feat, float* ctx_feat) {
-  GOCTR_ENTER_H(d);
-  GOCTR_CHECK(d && d->id_mode, "goctr_dataset_get_ids: not an id-mode dataset");
-  if (ub_ids && d->ub_ids.download(ub_ids, (size_t)d->rows * d->T)) return -1;
-  if (user_feat && d->U && d->ufeat.download(user_feat, (size_t)d->rows * d->U)) return -1;
-  if (ctx_feat && d->C && d->cfeat.download(ctx_feat, (size_t)d->rows * d->C)) return -1;
-  return 0;
-}
-
-}  // extern "C"
-
-
-// ------------------------------------------------------------------ single-call multi-device training (goctr_train_cfg::devices)
-// recommend.Train -> Fitter.Fit -> model.Train is ONE call from ONE Go process (recommend/rcmd.go:196-246, model/model.go:27-213).
-// After goctr_init_devices(n, ids) a training call with cfg->devices = n runs that call data-parallel over the n engines: the
-// model / table / dataset handles the caller holds live on engine 0; replicas of the model (weights, Adam moments, step
-// state, operand images) and of the embedding table on engines 1 .. n-1 are made by broadcast, the dataset is cut into
-// per-rank shards (rank r owns rows [r, r+1) * B/n of every global batch of B rows), and n host threads -- one per engine --
-// each run the ordinary per-rank data-parallel step loop (the one a one-process-per-GPU run executes) on their replica with
-// the group's communicator switched on.  Replicas and shards are cached on the handles: a second call only re-broadcasts
-// what changed in between (set_weights, set_rows, ...).
-namespace {
-
-// out[r][b * Bl + i][c] = in[(b * B + r * Bl + i)][c], `fill` where that row does not exist (4-byte elements)
-__global__ __launch_bounds__(256) void shard_rows_kernel(const uint32_t* __restrict__ in, long long rows, int w, int B, int Bl, int W,
-                                                         long long nb, uint32_t fill, uint32_t* __restrict__ out) {
-  const long long per = nb * Bl * (long long)w, total = per * W;
-  for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
-    const long long r = idx / per, rem = idx - r * per;
-    const long long lr = rem / w; const int c = (int)(rem - lr * w);
-    const long long b = lr / Bl; const int i = (int)(lr - b * Bl);
-    const long long g = b * B + r * Bl + i;
-    out[idx] = g < rows ? in[g * w + c] : fill;
-  }
-}
-
-struct ShardPack {            // root-side staging of one array of the dataset: [W][nb * Bl][w]
-  DevBuf<uint32_t> buf; size_t per = 0;
-};
-
-int pack_array(ShardPack& p, const void* in, long long rows, int w, int B, int W, long long nb, uint32_t fill) {
-  const int Bl = B / W;
-  p.per = (size_t)nb * Bl * w;
-  if (!w || !in) { p.per = 0; return 0; }
-  if (p.buf.alloc(p.per * W, false)) return -1;
-  const long long total = (long long)p.per * W;
-  const int cus = engine().compute_units > 0 ? engine().compute_units : 256;
-  hipLaunchKernelGGL(shard_rows_kernel, dim3((unsigned)std::min<long long>(std::max<long long>(cdiv(total, 256), 1), 32 * cus)), dim3(256), 0,
-                     engine().stream, static_cast<const uint32_t*>(in), rows, w, B, Bl, W, nb, fill, p.buf.p);
-  GOCTR_HIP(hipGetLastError());
-  return 0;
-}
-
-// collective: rank 0's pack -> every rank's `dst` (its per-rank slice)
-int scatter_array(const ShardPack* root_pack, size_t per, void* dst) {
-  Engine& e = engine();
-  if (!per) return 0;
-  const int W = e.world;
-  std::vector<size_t> so((size_t)W, 0), sc((size_t)W, 0), ro((size_t)W, 0), rc((size_t)W, 0);
-  if (e.rank == 0) for (int p = 0; p < W; ++p) { so[p] = (size_t)p * per; sc[p] = per; }
-  rc[0] = per;
-  return comm_alltoallv(e.rank == 0 ? (const void*)root_pack->buf.p : (const void*)dst, so.data(), sc.data(), dst, ro.data(), rc.data(), 4);
-}
-
-// collective: rank 0's model state -> this rank's replica
-int model_broadcast(goctr_model* mk, int stp_root, float emb_lr_root) {
-  Engine& e = engine();
-  auto bc = [&](void* p, size_t bytes) -> int { return (p && bytes) ? comm_broadcast(p, bytes, 0) : 0; };
-  if (bc(mk->W.p, sizeof(float) * mk->nflat) || bc(mk->Mo.p, sizeof(float) * mk->nflat) || bc(mk->Vo.p, sizeof(float) * mk->nflat) ||
-      bc(mk->W1T.p, sizeof(float) * mk->W1T.n) || bc(mk->W2T.p, sizeof(float) * mk->W2T.n) || bc(mk->W0sT.p, sizeof(float) * mk->W0sT.n) ||
-      bc(mk->Wimg.p, sizeof(float) * mk->Wimg.n) || bc(mk->Wx3.p, mk->x3_nch0 ? sizeof(unsigned short) * mk->Wx3.n : 0) ||
-      bc(mk->st.p, sizeof(StepState) * 2)) return -1;
-  if (e.rank != 0) {
-    mk->stp = stp_root;
-    if (mk->emb_lr != emb_lr_root) { mk->emb_lr = emb_lr_root; mk->graph.destroy(); }
-    mk->w0pv_live = false;              // (rebuilt from the broadcast W0 by ensure_w0pv)
-    mk->carry.valid = false;
-    if (mk->ra_flag.p) GOCTR_HIP(hipMemsetAsync(mk->ra_flag.p, 0, sizeof(unsigned int), e.stream));
-  }
-  return 0;
-}
-
-struct CommCallScope {       // the group's communicator takes part in this call only
-  Engine& e; bool prev;
-  explicit CommCallScope(Engine& en) : e(en), prev(en.comm_enabled) { e.comm_enabled = true; }
-  ~CommCallScope() { e.comm_enabled = prev; }
-};
-
-// Does this training call take the multi-device entry?  devices = n > 1; or devices = 1 on a ONE-engine group that
-// goctr_init_devices built a communicator for (GOCTR_FORCE_COMM=1): the same entry with one rank -- ncclCommInitAll, the
-// broadcast, the scatter and the split step with a one-rank RCCL communicator, which is all of mode 2 that a one-GPU box can run
-bool multi_call(const goctr_model* m, const goctr_train_cfg* cfg) {
-  if (cfg->devices > 1) return true;
-  const Engine* e = m->eng;
-  return cfg->devices == 1 && engine_count() == 1 && e->index == 0 && (e->nccl_comm || e->loop) && !e->comm_enabled;
-}
-
-// per_rank(model, table, shard, local cfg, rank) is the ordinary per-rank call
-template <class Fn>
-int train_multi(goctr_model* m, goctr_emb* emb, goctr_dataset* d, const goctr_train_cfg* cfg, Fn per_rank) {
-  const int N = cfg->devices, B = cfg->batch;
-  Engine* e0 = engine_at(0);
-  GOCTR_CHECK(N == engine_count() && e0 && e0->world == N && (e0->loop || e0->nccl_comm),
-              "cfg.devices = %d, but goctr_init_devices set up %d engine(s)", N, (e0 && (e0->loop || e0->nccl_comm)) ? e0->world : 1);
-  GOCTR_CHECK(m->eng == e0 && (!emb || emb->eng == e0) && d->eng == e0, "multi-device training: the handles must live on engine 0");
-  GOCTR_CHECK(B % N == 0, "multi-device training: batch %d is not a multiple of devices %d", B, N);
-  if (comm_group_reset()) return -1;
-  const int Bl = B / N;
-  const long long nb = cdiv(d->rows, B);
-  // ---- handles on the other engines (no collectives yet)
-  bool new_model = false, new_emb = false;
-  if ((int)m->reps.size() != N) { for (auto* r : m->reps) goctr_model_destroy(r); m->reps.assign((size_t)N, nullptr); }
-  if (emb && (int)emb->reps.size() != N) { for (auto* r : emb->reps) goctr_emb_destroy(r); emb->reps.assign((size_t)N, nullptr); }
-  const bool need_shard = (int)d->shards.size() != N || d->shard_B != B;
-  if (need_shard) { for (auto* s : d->shards) goctr_dataset_destroy(s); d->shards.assign((size_t)N, nullptr); d->shard_B = 0; }
-  for (int k = 0; k < N; ++k) {
-    Engine* ek = engine_at(k);
-    EngineScope on(ek);
-    std::lock_guard<std::recursive_mutex> lk(ek->mu);
-    if (k > 0 && !m->reps[k]) { if (goctr_model_create(&m->cfg, &m->reps[k])) return -1; new_model = true; }
-    if (k > 0 && emb && !emb->reps[k]) { if (goctr_emb_create(emb->V, emb->D, nullptr, &emb->reps[k])) return -1; new_emb = true; }
-    if (need_shard) {
-      std::unique_ptr<goctr_dataset> s(new goctr_dataset);
-      s->id_mode = d->id_mode; s->rows = nb * Bl; s->has_y = d->has_y;
-      s->xcols = d->xcols; memcpy(s->ranges, d->ranges, sizeof s->ranges); s->U = d->U; s->C = d->C; s->T = d->T;
-      const size_t R = (size_t)s->rows;
-      if (d->id_mode) {
-        if (s->ub_ids.alloc(R * d->T, false) || s->item_ids.alloc(R, false) || s->ufeat.alloc(R * d->U, false) || s->cfeat.alloc(R * d->C, false)) return -1;
-      } else if (s->X.alloc(R * d->xcols, false)) return -1;
-      if (d->has_y && s->Y.alloc(R, false)) return -1;
-      GOCTR_HIP(hipStreamSynchronize(ek->stream));
-      d->shards[k] = s.release();
-    }
-  }
-  const bool model_sync = new_model || m->reps_gen + 1 != m->gen;
-  const bool emb_sync = emb && (new_emb || emb->reps_version != emb->version);
-  // ---- root-side staging of the shards
-  ShardPack pX, pY, pub, pit, puf, pcf;
-  const bool from_host = d->host_X != nullptr;
-  if (need_shard && !from_host) {
-    if (d->id_mode) {
-      if (pack_array(pub, d->ub_ids.p, d->rows, d->T, B, N, nb, 0xFFFFFFFFu) || pack_array(pit, d->item_ids.p, d->rows, 1, B, N, nb, 0xFFFFFFFFu) ||
-          pack_array(puf, d->ufeat.p, d->rows, d->U, B, N, nb, 0u) || pack_array(pcf, d->cfeat.p, d->rows, d->C, B, N, nb, 0u)) return -1;
-    } else if (pack_array(pX, d->X.p, d->rows, d->xcols, B, N, nb, 0u)) return -1;
-    if (d->has_y && pack_array(pY, d->Y.p, d->rows, 1, B, N, nb, 0u)) return -1;
-  }
-  goctr_train_cfg lcfg = *cfg;
-  lcfg.batch = Bl; lcfg.devices = 1;
-  const int stp_root = m->stp; const float emb_lr_root = m->emb_lr;
-  const int rc = run_on_engines(N, [&](int k) -> int {
-    Engine& e = engine();
-    std::lock_guard<std::recursive_mutex> elk(e.mu);
-    CommCallScope comm_on(e);
-    // (once per communicator; every rank is here.  < 0: the probe lost the communicator -- fail the call on this rank, the
-    // others see the abort in their next wait)
-    if (comm_capturable() && env_int("GOCTR_DP_CAPTURE_COMM", 1) == 1 && comm_capture_selftest() < 0) return -1;
-    goctr_model* mk = k == 0 ? m : m->reps[k];
-    goctr_emb* ek = !emb ? nullptr : (k == 0 ? emb : emb->reps[k]);
-    goctr_dataset* dk = d->shards[k];
-    std::unique_lock<std::shared_mutex> lk(mk->mu, std::defer_lock);
-    if (k > 0) { lk.lock(); ++mk->gen; }          // (rank 0: the caller holds its model's lock)
-    int r = 0;
-    if (model_sync) r = model_broadcast(mk, stp_root, emb_lr_root);
-    if (!r && emb_sync) { r = comm_broadcast(ek->rows.p, sizeof(float) * (size_t)(emb->V + 1) * emb->D, 0); if (k > 0) ++ek->version; }
-    if (!r && need_shard && from_host) {
-      // this rank's rows of global batch b are host rows [b B + k Bl, b B + (k + 1) Bl), clipped at the dataset's end; what is
-      // missing of a short last batch is zero rows (model.go:357-371 FillTensorRows pads it to the batch size)
-      hipStream_t st = e.stream;
-      auto rows_from_host = [&](float* dst, const float* src, int cols) -> int {
-        for (long long b = 0; b < nb; ++b) {
-          const long long g0 = b * B + (long long)k * Bl;
-          const long long have = std::max<long long>(0, std::min<long long>(Bl, d->rows - g0));
-          float* to = dst + (size_t)b * Bl * cols;
-          if (have > 0) GOCTR_HIP(hipMemcpyAsync(to, src + (size_t)g0 * cols, sizeof(float) * (size_t)have * cols, hipMemcpyHostToDevice, st));
-          if (have < Bl) GOCTR_HIP(hipMemsetAsync(to + (size_t)have * cols, 0, sizeof(float) * (size_t)(Bl - have) * cols, st));
-        }
-        return 0;
-      };
-      r = rows_from_host(dk->X.p, d->host_X, d->xcols);
-      if (!r && d->has_y) r = rows_from_host(dk->Y.p, d->host_Y, 1);
-      if (!r) { const hipError_t he = hipStreamSynchronize(st); if (he != hipSuccess) { set_error("per-rank upload: %s", hipGetErrorString(he)); r = -1; } }
-    } else if (!r && need_shard) {
-      if (d->id_mode) r = scatter_array(&pub, pub.per, dk->ub_ids.p) || scatter_array(&pit, pit.per, dk->item_ids.p) ||
-                          scatter_array(&puf, puf.per, dk->ufeat.p) || scatter_array(&pcf, pcf.per, dk->cfeat.p);
-      else r = scatter_array(&pX, pX.per, dk->X.p);
-      if (!r && d->has_y) r = scatter_array(&pY, pY.per, dk->Y.p);
-      if (!r && k == 0) r = hipStreamSynchronize(e.stream) == hipSuccess ? 0 : -1;     // (the staging buffers are released after the call)
-    }
-    // (goctr_engine_call_ms: this rank's own span of the call on its own stream -- bench.py --single-process reports it per rank)
-    if (!e.call_begin) { (void)hipEventCreate(&e.call_begin); (void)hipEventCreate(&e.call_end); }
-    e.call_timed = false;
-    if (!r && e.call_begin) (void)hipEventRecord(e.call_begin, e.stream);
-    if (!r) r = per_rank(mk, ek, dk, &lcfg, k);
-    if (!r && e.call_end) e.call_timed = hipEventRecord(e.call_end, e.stream) == hipSuccess;
-    if (r) {
-      const std::string msg = goctr_last_error();
-      comm_abort_on_failure();
-      set_error("%s", msg.c_str());
-    }
-    return r;
-  });
-  if (rc) { m->reps_gen = ~0ull; if (emb) emb->reps_version = ~0ull; return -1; }
-  if (need_shard) d->shard_B = B;
-  m->reps_gen = m->gen;
-  if (emb) emb->reps_version = emb->version;
-  return 0;
-}
-
-}  // namespace
-
-static int train_steps_locked(goctr_model* m, goctr_emb* emb, goctr_dataset* d, const goctr_train_cfg* cfg, int64_t first_batch, int n_steps,
-                              float* costs);
-static int train_dataset_locked(goctr_model* m, goctr_emb* emb, goctr_dataset* d, const goctr_train_cfg* cfg, float* epoch_costs,
-                                int* epochs_run);
-
-extern "C" {
-
-// ------------------------------------------------------------------ training
-int goctr_train_steps(goctr_model* m, goctr_emb* emb, goctr_dataset* d, const goctr_train_cfg* cfg,
-                      int64_t first_batch, int n_steps, float* costs) {
-  GOCTR_ENTER_H(m);
-  GOCTR_CHECK(m && d && cfg && cfg->batch > 0 && n_steps >= 0, "goctr_train_steps: bad arguments");
-  GOCTR_CHECK(d->has_y, "goctr_train_steps: dataset has no labels");
-  GOCTR_CHECK(cfg->dropout_mode == 0 || cfg->dropout_mode == 2, "multi-step training supports dropout_mode 0 or 2");
-  GOCTR_CHECK(n_steps <= COST_RING, "n_steps > %d per call", COST_RING);
-  GOCTR_SAME_ENGINE(m, d); GOCTR_SAME_ENGINE(m, emb);
-  std::unique_lock<std::shared_mutex> lk(m->mu); ++m->gen;
-  if (check_dataset(m, d, emb)) return -1;
-  if (multi_call(m, cfg))
-    return train_multi(m, emb, d, cfg, [&](goctr_model* mk, goctr_emb* ek, goctr_dataset* dk, const goctr_train_cfg* lc, int rank) {
-      return train_steps_locked(mk, ek, dk, lc, first_batch, n_steps, rank == 0 ? costs : nullptr);
-    });
-  return train_steps_locked(m, emb, d, cfg, first_batch, n_steps, costs);
-}
-
-}  // extern "C"
-
-static int train_steps_locked(goctr_model* m, goctr_emb* emb, goctr_dataset* d, const goctr_train_cfg* cfg, int64_t first_batch, int n_steps,
-                              float* costs) {
-  std::unique_lock<std::shared_mutex> rows_lk;          // embedding training writes the table: serving passes wait (lock order: model, table)
-  if (m->emb_lr > 0.f && emb) rows_lk = std::unique_lock<std::shared_mutex>(emb->mu);
-  const long long nb = cdiv(d->rows, cfg->batch);
-  if (retarget_state(m, first_batch % nb, nb)) return -1;      // no host synchronisation on this path
-  m->pend_no_costs = costs == nullptr;
-  const int rs = run_steps(m, emb, d, cfg, n_steps);
-  m->pend_no_costs = false;
-  if (rs) {
-    if (engine().comm_active()) {     // (keep this rank's error text; make the peers fail too instead of waiting in a collective)
-      const std::string msg = goctr_last_error();
-      comm_abort_on_failure();
-      set_error("%s [data-parallel step failed on this rank: communicator aborted]", msg.c_str());
-    }
-    return -1;
-  }
-  if (costs) {
-    if (comm_watch_stream()) return -1;
-    if (m->costs.download(costs, n_steps)) return -1;
-  }
-  return 0;
-}
-
-extern "C" {
-
-int goctr_model_replica(goctr_model* m, int rank, goctr_model** out) {
-  GOCTR_ENTER_H(m);
-  GOCTR_CHECK(m && out && rank >= 0, "goctr_model_replica: bad arguments");
-  std::unique_lock<std::shared_mutex> lk(m->mu);
-  *out = rank == 0 ? m : (rank < (int)m->reps.size() ? m->reps[rank] : nullptr);
-  return 0;
-}
-int goctr_emb_replica(goctr_emb* e, int rank, goctr_emb** out) {
-  GOCTR_ENTER_H(e);
-  GOCTR_CHECK(e && out && rank >= 0, "goctr_emb_replica: bad arguments");
-  *out = rank == 0 ? e : (rank < (int)e->reps.size() ? e->reps[rank] : nullptr);
-  return 0;
-}
-
-int goctr_train_dataset(goctr_model* m, goctr_emb* emb, goctr_dataset* d, const goctr_train_cfg* cfg,
-                        float* epoch_costs, int* epochs_run) {
-  GOCTR_ENTER_H(m);
-  GOCTR_CHECK(m && d && cfg && cfg->batch > 0 && cfg->epochs >= 0, "goctr_train_dataset: bad arguments");
-  GOCTR_CHECK(d->has_y, "goctr_train_dataset: dataset has no labels");
-  GOCTR_CHECK(cfg->dropout_mode == 0 || cfg->dropout_mode == 2, "multi-step training supports dropout_mode 0 or 2");
-  GOCTR_SAME_ENGINE(m, d); GOCTR_SAME_ENGINE(m, emb);
-  std::unique_lock<std::shared_mutex> lk(m->mu); ++m->gen;
-  if (check_dataset(m, d, emb)) return -1;
-  if (multi_call(m, cfg))
-    return train_multi(m, emb, d, cfg, [&](goctr_model* mk, goctr_emb* ek, goctr_dataset* dk, const goctr_train_cfg* lc, int rank) {
-      int ran = 0;
-      const int r = train_dataset_locked(mk, ek, dk, lc, rank == 0 ? epoch_costs : nullptr, &ran);
-      if (rank == 0 && epochs_run) *epochs_run = ran;
-      return r;
-    });
-  return train_dataset_locked(m, emb, d, cfg, epoch_costs, epochs_run);
-}
-
-}  // extern "C"
-
-static int train_dataset_locked(goctr_model* m, goctr_emb* emb, goctr_dataset* d, const goctr_train_cfg* cfg, float* epoch_costs,
-                                int* epochs_run) {
-  std::unique_lock<std::shared_mutex> rows_lk;          // embedding training writes the table: serving passes wait (lock order: model, table)
-  if (m->emb_lr > 0.f && emb) rows_lk = std::unique_lock<std::shared_mutex>(emb->mu);
-  // a fresh solver per model.Train call (model.go:88)
-  GOCTR_HIP(hipMemsetAsync(m->Mo.p, 0, sizeof(float) * m->nflat, engine().stream));
-  GOCTR_HIP(hipMemsetAsync(m->Vo.p, 0, sizeof(float) * m->nflat, engine().stream));
-  const long long nb = cdiv(d->rows, cfg->batch);
-  if (engine().comm_active()) {
-    // every rank issues one all-reduce per batch: unequal shard sizes would leave the shorter ranks' peers hanging
-    double v[2] = {(double)nb, (double)nb * (double)nb};
-    if (goctr_comm_allreduce_f64(v, 2)) return -1;
-    const double w = (double)engine().eff_world();
-    GOCTR_CHECK(v[0] == w * (double)nb && v[1] == w * (double)nb * (double)nb,
-                "goctr_train_dataset: the ranks' shards have different batch counts (this rank: %lld batches of %d); "
-                "shard the rows so that every rank steps the same number of times", nb, cfg->batch);
-  }
-  if (set_state(m, 0, 0, 0, nb)) return -1;
-  float best = 3.402823466e+38f;  // math.MaxFloat32 (model.go:103)
-  int no_improve = 0, e = 0;
-  for (e = 0; e < cfg->epochs; ++e) {
-    long long done = 0;
-    unsigned slot0 = 0;
-    while (done < nb) {  // keep each burst inside the cost ring
-      const int burst = (int)std::min<long long>(nb - done, COST_RING / 2);
-      if (run_steps(m, emb, d, cfg, burst)) {
-        if (engine().comm_active()) {
-          const std::string msg = goctr_last_error();
-          comm_abort_on_failure();
-          set_error("%s [data-parallel step failed on this rank: communicator aborted]", msg.c_str());
-        }
-        return -1;
-      }
-      done += burst;
-    }
-    (void)slot0;
-    StepState s;
-    if (get_state(m, &s)) return -1;
-    float cost = 0.f;
-    if (m->costs.download(&cost, 1, (s.slot - 1u) % COST_RING)) return -1;  // cost of the LAST batch (model.go:198)
-    if (epoch_costs) epoch_costs[e] = cost;
-    if (cost < best) { best = cost; no_improve = 0; } else no_improve++;
-    if (cfg->early_stop != 0 && no_improve >= cfg->early_stop) { e++; break; }
-  }
-  if (epochs_run) *epochs_run = e;
-  return 0;
-}
-
-extern "C" {
-
-int goctr_train_dense(goctr_model* m, const float* X, const float* Y, int64_t rows, int xcols, const int ranges[8],
-                      const goctr_train_cfg* cfg, float* epoch_costs, int* epochs_run) {
-  GOCTR_ENTER_H(m);
-  goctr_dataset* d = nullptr;
-  GOCTR_CHECK(m && cfg, "goctr_train_dense: null argument");
-  GOCTR_CHECK(Y != nullptr, "goctr_train_dense: labels required");
-  if (cfg->devices > 1) {
-    // n devices: no copy of X on engine 0 -- the ranks fetch their own rows from the caller's memory (goctr_dataset::host_X)
-    GOCTR_CHECK(X && rows > 0 && xcols > 0 && ranges, "goctr_train_dense: bad arguments");
-    d = new goctr_dataset;
-    d->id_mode = false; d->rows = rows; d->xcols = xcols; d->has_y = true;
-    memcpy(d->ranges, ranges, sizeof d->ranges);
-    d->host_X = X; d->host_Y = Y;
-  } else if (goctr_dataset_create_dense(X, Y, rows, xcols, ranges, &d)) return -1;
-  int rc = goctr_train_dataset(m, nullptr, d, cfg, epoch_costs, epochs_run);
-  if (!rc) rc = goctr_sync();
-  {
-    std::unique_lock<std::shared_mutex> lk(m->mu); ++m->gen;
-    m->graph.destroy();  // (keyed on the dataset's generation id, so it could never be replayed again anyway)
-  }
-  goctr_dataset_destroy(d);
-  return rc;
-}
-
-int goctr_loss_grad_dense(goctr_model* m, const float* X, const float* Y, int valid, int B, int xcols,
-                          const int ranges[8], const goctr_train_cfg* cfg, uint32_t step, const float* m0,
-                          const float* m1, float* cost, float* gW0, float* gW1, float* gW2, float* gatt0, float* y_out) {
-  GOCTR_ENTER_H(m);
-  GOCTR_CHECK(m && X && Y && cfg && valid > 0 && valid <= B, "goctr_loss_grad_dense: bad arguments");
-  goctr_dataset* d = nullptr;
-  if (goctr_dataset_create_dense(X, Y, valid, xcols, ranges, &d)) return -1;
-  std::unique_ptr<goctr_dataset> guard(d);
-  std::unique_lock<std::shared_mutex> lk(m->mu); ++m->gen;
-  if (check_dataset(m, d, nullptr)) return -1;
-  if (ensure_workspace(m, B)) return -1;
-  StepOpts o = opts_from(cfg);
-  o.update = false;
-  if (o.drop_mode == 1) {
-    GOCTR_CHECK(m0 && m1, "dropout_mode 1 needs explicit masks");
-    if (m->mask0.alloc((size_t)B * m->cfg.H1, false) || m->mask0.upload(m0, (size_t)B * m->cfg.H1)) return -1;
-    if (m->mask1.alloc((size_t)B * m->cfg.H2, false) || m->mask1.upload(m1, (size_t)B * m->cfg.H2)) return -1;
-  }
-  StepState saved;
-  if (get_state(m, &saved)) return -1;
-  struct Restore {   // the caller's step counter / dropout stream position survives every exit path
-    goctr_model* m; const StepState& s; bool armed = true;
-    ~Restore() { if (armed) (void)set_state(m, s.gstep, s.slot, s.batch_idx, s.n_batches); }
-  } restore{m, saved};
-  if (set_state(m, step, 0, 0, 1)) return -1;
-  RowSource src = make_source(d, nullptr);
-  int rc = launch_forward(m, src, B, o) || launch_backward(m, src, B, o, false);
-  if (rc) return -1;
-  GOCTR_HIP(hipStreamSynchronize(engine().stream));
-  if (gW0 && download_padded(m, m->G.p, GOCTR_W0, gW0, (size_t)m->I * m->cfg.H1)) return -1;
-  if (gW1 && download_padded(m, m->G.p, GOCTR_W1, gW1, (size_t)m->cfg.H1 * m->cfg.H2)) return -1;
-  if (gW2 && download_padded(m, m->G.p, GOCTR_W2, gW2, (size_t)m->cfg.H2)) return -1;
-  if (gatt0) {
-    if (m->cfg.kind == GOCTR_DIN) { if (download_padded(m, m->G.p, GOCTR_ATT0, gatt0, (size_t)m->cfg.T)) return -1; }
-    else memset(gatt0, 0, sizeof(float) * m->cfg.T);
-  }
-  if (cost) {
-    float s = 0.f;
-    if (m->G.download(&s, 1, m->nflat)) return -1;
-    *cost = -(s / (float)(B * engine().eff_world()));
-  }
-  if (y_out && m->yhat.download(y_out, B)) return -1;
-  restore.armed = false;
-  return set_state(m, saved.gstep, saved.slot, saved.batch_idx, saved.n_batches);
-}
-
-// ------------------------------------------------------------------ predict
-static int predict_batches(goctr_model* m, goctr_emb* emb, goctr_dataset* d, int batch, int64_t first_batch,
-                           int64_t n_batches, float* y_host) {
-  if (check_dataset(m, d, emb)) return -1;
-  // Rows are scored independently of their batch, so G consecutive batches can share launches (one gather and one forward
-  // chain over G * batch rows): fewer and fuller launches.  PredBatchSize keeps its meaning at the boundary -- which rows a
-  // call covers and how the short last batch is padded (model.go:337-347).  The scores agree with one-batch launches to
-  // float32 rounding, not bit for bit: 16 384 rows take the 32-row-tile forward kernel, 4096 rows the 16-row-tile one
-  // (322 instead of 418 M rows/s if the latter scored the groups too), and the two add the partial products of layer 1 in
-  // different orders (tests/test_gpu_ctr.py bounds the difference; both are inside the 1e-5 parity bar vs the oracle).
-  // Measured at DIN cfg3, PredBatchSize 4096: 250 / 351 / 416 / 444 M rows/s at G = 1 / 2 / 4 / 8 (GOCTR_PRED_GROUP) with one
-  // workgroup per 32-row tile; since the forward-only kernel walks its tiles as one persistent workgroup per CU (round 3,
-  // ctr_chain_x3.h: a tile's start hides behind its predecessor's tail) 516 / 573 M at G = 4 / 8 -- default 8.
-  int G = std::max(1, env_int("GOCTR_PRED_GROUP", 8));
-  while (G > 1 && (long long)batch * G > 32768) G /= 2;     // (a launch of 32 768 rows fills the chip; the workspace grows with G)
-  // forward-only workspace of its own (h0, gates, yhat): the training workspace -- sized for the training batch, with its
-  // slab buffers and captured step graphs -- is left alone
-  if (m->pws.ensure(batch * G, m->Ip, m->cfg.T, m->H1p, m->H2p, !chain_ok(m), engine().stream)) return -1;
-  const FwdBufs fb = m->pws.bufs();
-  RowSource src = make_source(d, emb);
-  StepOpts o;
-  o.train = false;
-  const long long nb = cdiv(d->rows, batch);
-  // per-batch states are written up front so that no host stack memory is read asynchronously
-  const int64_t CH = 4096;
-  if (m->pst.ensure((size_t)std::min<int64_t>(n_batches, CH), false)) return -1;
-  if (y_host && m->yall.ensure((size_t)d->rows, false)) return -1;
-  std::vector<StepState> hs;
-  for (int64_t k0 = 0; k0 < n_batches; k0 += CH) {
-    const int64_t cnt = std::min<int64_t>(CH, n_batches - k0);
-    hs.resize(cnt);
-    std::vector<int> grp((size_t)cnt, 1);
-    for (int64_t k = 0; k < cnt;) {
-      const long long b = (first_batch + k0 + k) % nb;
-      // a group: g whole batches that start at a multiple of g and do not run past the call or the dataset's last batch;
-      // g = G, or the largest G / 2^j that still fits (the tail of a dataset keeps to the large-launch kernel as long as
-      // two batches are left)
-      int g = 1;
-      for (int c = G; c > 1; c /= 2)
-        if (b % c == 0 && k + c <= cnt && b + c <= nb) { g = c; break; }
-      hs[k] = StepState{0u, 0u, b / g, nb};
-      grp[k] = g;
-      for (int j = 1; j < g; ++j) { hs[k + j] = hs[k]; grp[k + j] = 0; }
-      k += g;
-    }
-    if (m->pst.upload(hs.data(), (size_t)cnt)) return -1;
-    for (int64_t k = 0; k < cnt; ++k) {
-      if (grp[k] == 0) continue;                      // (covered by the group that started before it)
-      const int Bk = batch * grp[k];
-      if (launch_forward(m, src, Bk, o, m->pst.p + k, &fb)) return -1;
-      if (y_host) {
-        const long long b = hs[k].batch_idx;
-        const long long start = b * Bk, end = std::min<long long>(start + Bk, d->rows);
-        // first end-start outputs (model.go:344-347), collected on the device: one copy to the host per call
-        GOCTR_HIP(hipMemcpyAsync(m->yall.p + start, fb.yhat, sizeof(float) * (size_t)(end - start), hipMemcpyDeviceToDevice,
-                                 engine().stream));
-      }
-    }
-    if (k0 + CH < n_batches) GOCTR_HIP(hipStreamSynchronize(engine().stream));  // before the states are overwritten
-  }
-  if (y_host) {
-    // (callers always score from batch 0: every row of [0, min(rows, n_batches * batch)) was written above)
-    const long long n = std::min<long long>(d->rows, n_batches * (long long)batch);
-    if (m->yall.download(y_host, (size_t)n)) return -1;
-  }
-  return 0;
-}
-
-int goctr_predict_dataset(goctr_model* m, goctr_emb* emb, goctr_dataset* d, int batch, float* y_out) {
-  GOCTR_ENTER_H(m);
-  GOCTR_CHECK(m && d && y_out && batch > 0, "goctr_predict_dataset: bad arguments");
-  std::unique_lock<std::shared_mutex> lk(m->mu); ++m->gen;
-  return predict_batches(m, emb, d, batch, 0, cdiv(d->rows, batch), y_out);
-}
-
-int goctr_predict_steps(goctr_model* m, goctr_emb* emb, goctr_dataset* d, int batch, int64_t first_batch,
-                        int n_batches) {
-  GOCTR_ENTER_H(m);
-  GOCTR_CHECK(m && d && batch > 0 && n_batches >= 0, "goctr_predict_steps: bad arguments");
-  std::unique_lock<std::shared_mutex> lk(m->mu); ++m->gen;
-  return predict_batches(m, emb, d, batch, first_batch, n_batches, nullptr);
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------ serving: recommend.BatchPredict / Rank / Predict
-// recommend/rcmd.go:248-337: sample keys -> GetSampleVector rows -> PredictAbstract.Predict -> scores, called from concurrent
-// gin handler goroutines (recommend/api.go:106-131: one user, a short itemIdList per request).  Everything GetSampleVector
-// reads per key (rcmd.go:462-536) is resident in HBM -- the user / item feature tables (the contents of UserFeatureCache /
-// ItemFeatureCache), the behaviour cache, the item-embedding table -- so one call is: keys (16 B each) to the device, one
-// assembly launch, the forward launches, scores back.
-//
-// Concurrency.  These entry points do not take the engine lock and do not use the engine's main stream.  A call borrows a
-// SERVING SLOT: its own HIP stream, pinned host staging for keys and scores (one H2D and one D2H copy per pass, both
-// asynchronous on the slot's stream; no per-call allocation, no std::vector copies), the id-mode rows assembled from the
-// keys and a forward workspace.  It holds the model's lock SHARED (training holds it exclusive), and its stream waits for
-// the event the last weight-writing call recorded on the main stream -- training is asynchronous.  Slots: GOCTR_SERVE_SLOTS
-// (default 8), created on first use; further callers wait for a free one, first come first served (ServePool).
-//
-// Micro-batching.  A Rank request is tens to hundreds of rows: three small launches and two copies whose cost is latency,
-// not work.  Requests of <= GOCTR_SERVE_COALESCE rows (default 1024) go through a combining queue per recsys: the first
-// arrival becomes the leader and serves its own request; whatever arrives on the same model while that pass is in flight is
-// taken over as ONE pass (<= 4096 rows) by the next leader -- one of the waiting callers, so no thread serves others after
-// its own result is ready.  Rows are scored independently and passes of < 8192 rows all run the same forward kernel
-// (ctr_fwd16_kernel), so a request's scores are bit-identical whether or not, and with whatever, it was coalesced.
-struct goctr_recsys {
-  goctr::Engine* const eng = &goctr::engine();   // the engine (device, streams, arena) the handle was created on
-  goctr_ubcache* ub = nullptr;    // not owned
-  goctr_emb* emb = nullptr;       // not owned
-  int64_t n_users = 0, n_items = 0; int U = 0, C = 0;
-  DevBuf<float> user_table, item_table;
-  // combining queue of small requests (micro-batcher)
-  struct Req;
-  std::mutex qmu; std::condition_variable qcv;
-  std::vector<Req*> queue; std::atomic<bool> leader{false};
-};
-
-namespace {
-
-constexpr int64_t SERVE_PASS_ROWS = 65536;      // rows one pass of a slot scores (larger requests: several passes)
-constexpr int64_t SERVE_COALESCE_ROWS = 4096;   // rows one coalesced pass may hold (< 8192: always ctr_fwd16_kernel)
-
-// one request's keys and outputs (host pointers of the caller)
-struct KeySeg {
-  const int32_t* users; int32_t user_all;       // users == null: every key has user_all (Rank)
-  const int32_t* items;
-  const int64_t* ts; int64_t ts_all;            // ts == null: every key has ts_all
-  int64_t n;
-  float* scores; uint8_t* failed; int64_t n_failed;
-};
-
-struct ServeSlot {
-  hipStream_t stream = nullptr;
-  int64_t cap = 0; int T = 0, U = 0, C = 0;
-  // pinned staging: in = [ts i64 x N | users i32 x N | items i32 x N], out = [scores f32 x Br | failed u8 x N]
-  char* h_in = nullptr; char* h_out = nullptr;
-  unsigned* h_done = nullptr; unsigned epoch = 0;   // behind the failed flags in h_out: one word per 16-row workgroup (serve_keys_pass)
-  // the keys of a zero-copy pass in fine-grained DEVICE memory that the host stores into over the PCIe BAR (large-BAR systems): the
-  // kernel's first loads are local instead of a PCIe read round trip.  Null: the kernels read the pinned h_in.
-  char* in_bar = nullptr; std::vector<void*> retired_dev;
-  std::vector<void*> retired;      // outgrown pinned buffers (see ensure_keys)
-  DevBuf<char> d_in, d_out;
-  DevBuf<int32_t> ub_ids, item_ids; DevBuf<float> ufeat, cfeat;
-  FwdWs ws;
-  DevBuf<StepState> st;            // one all-zero state: "batch 0 of 1"
-  DevBuf<float> X; size_t capX = 0;   // dense rows (goctr_predict_dense)
-  ~ServeSlot() {
-    for (void* p : retired_dev) (void)hipFree(p);
-    if (in_bar) (void)hipFree(in_bar);
-    for (void* p : retired) (void)hipHostFree(p);
-    if (h_in) (void)hipHostFree(h_in);
-    if (h_out) (void)hipHostFree(h_out);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-  int init() {
-    GOCTR_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    if (st.alloc(1, false)) return -1;
-    const StepState z{0u, 0u, 0, 1};
-    GOCTR_HIP(hipMemcpyAsync(st.p, &z, sizeof z, hipMemcpyHostToDevice, stream));
-    GOCTR_HIP(hipStreamSynchronize(stream));
-    return 0;
-  }
-  // room for n keys of a model / recsys with these widths
-  int ensure_keys(int64_t n, int Tn, int Un, int Cn) {
-    if (n <= cap && Tn == T && Un == U && Cn == C) return 0;
-    GOCTR_HIP(hipStreamSynchronize(stream));
-    const int64_t want = std::max<int64_t>(std::max<int64_t>(n, 256), std::min<int64_t>(2 * cap, SERVE_PASS_ROWS));
-    const size_t Br = (size_t)round_up((int)want, 32);
-    cap = 0;                                   // (a failure below must not leave the old capacity next to missing buffers)
-    // (outgrown pinned buffers are kept until the slot goes: hipHostFree waits for the whole device, which would invalidate the
-    // stream capture of a thread that is building step graphs meanwhile -- a handful of geometric growths per slot at most)
-    if (h_in) { retired.push_back(h_in); h_in = nullptr; }
-    if (h_out) { retired.push_back(h_out); h_out = nullptr; }
-    GOCTR_HIP(hipHostMalloc((void**)&h_in, (size_t)want * 16, hipHostMallocDefault));
-    if (in_bar) { retired_dev.push_back(in_bar); in_bar = nullptr; }
-    if (env_int("GOCTR_SERVE_BAR", 1) != 0) in_bar = static_cast<char*>(bar_alloc((size_t)want * 16));   // (null: the pinned buffer serves)
-    const size_t done_off = (Br * 4 + (size_t)want + 63) / 64 * 64, done_n = (size_t)want / 16 + 1;
-    GOCTR_HIP(hipHostMalloc((void**)&h_out, done_off + 4 * done_n, hipHostMallocDefault));
-    h_done = reinterpret_cast<unsigned*>(h_out + done_off);
-    memset(h_done, 0, 4 * done_n); epoch = 0;
-    if (d_in.alloc((size_t)want * 16, false) || d_out.alloc(Br * 4 + (size_t)want, false) ||
-        ub_ids.alloc((size_t)want * Tn, false) || item_ids.alloc((size_t)want, false) ||
-        ufeat.alloc((size_t)want * Un, false) || cfeat.alloc((size_t)want * Cn, false)) return -1;
-    cap = want; T = Tn; U = Un; C = Cn;
-    return 0;
-  }
-};
-
-// Slots are handed out FAIRLY: a released slot goes straight to the longest-waiting caller (FIFO hand-off, no barging).  With a
-// plain condition variable a caller in a closed loop re-took the slot it had just released before the woken waiter was
-// scheduled, and waiters starved: 8 callers on 4 slots had a p99 of 300 - 870 us and a worst case of 50 ms against a p50 of
-// 40 us (round 3's serving tail; profiles/r04_serve_tail.txt).  A waiter first spins on its hand-off word for about one pass
-// (~50 us) -- a futex wake-up costs as much as the pass it waits for -- and only then blocks.
-struct ServePool {
-  std::mutex mu;
-  std::vector<std::unique_ptr<ServeSlot>> all; std::vector<ServeSlot*> idle;
-  struct Waiter { std::atomic<ServeSlot*> got{nullptr}; std::condition_variable cv; bool blocked = false; };
-  std::deque<Waiter*> waiters;
-  // try_only: null instead of waiting when every slot is busy (the micro-batcher's "is a slot free right now?")
-  ServeSlot* acquire(bool try_only = false) {
-    Waiter w;
-    {
-      std::unique_lock<std::mutex> lk(mu);
-      const size_t max_slots = (size_t)std::max(1, env_int("GOCTR_SERVE_SLOTS", 8));
-      if (waiters.empty()) {
-        if (!idle.empty()) { ServeSlot* s = idle.back(); idle.pop_back(); return s; }
-        if (all.size() < max_slots) {
-          std::unique_ptr<ServeSlot> s(new ServeSlot);
-          if (s->init()) return nullptr;
-          all.push_back(std::move(s));
-          return all.back().get();
-        }
-      }
-      if (try_only) return nullptr;
-      waiters.push_back(&w);
-    }
-    for (int spin = 0; spin < 20000; ++spin) {            // ~50 us
-      if (ServeSlot* s = w.got.load(std::memory_order_acquire)) return s;
-      __builtin_ia32_pause();
-    }
-    std::unique_lock<std::mutex> lk(mu);
-    w.blocked = true;
-    w.cv.wait(lk, [&] { return w.got.load(std::memory_order_acquire) != nullptr; });
-    return w.got.load(std::memory_order_acquire);
-  }
-  void release(ServeSlot* s) {
-    std::lock_guard<std::mutex> lk(mu);
-    if (waiters.empty()) { idle.push_back(s); return; }
-    Waiter* w = waiters.front();
-    waiters.pop_front();
-    // (w lives on the waiter's stack.  A SPINNING waiter returns the moment it sees `got`: nothing of w may be touched after
-    // the store.  A BLOCKED waiter cannot return before it re-takes `mu`, which we hold until after the notify.)
-    const bool blocked = w->blocked;
-    w->got.store(s, std::memory_order_release);
-    if (blocked) w->cv.notify_one();
-  }
-  // (goctr_*_destroy of something a slot may have buffers sized for: nothing to do -- slots hold no handle pointers)
-};
-// (never destroyed: a static destructor would release streams and pinned buffers after the HIP runtime has shut down)
-ServePool& serve_pool() {
-  Engine& e = engine();                        // (slots hold streams and buffers of this engine's device)
-  static std::mutex mu;
-  std::lock_guard<std::mutex> lk(mu);
-  if (!e.serve_pool) e.serve_pool = new ServePool;
-  return *static_cast<ServePool*>(e.serve_pool);
-}
-struct SlotLease {
-  ServePool& pool;
-  ServeSlot* s;
-  SlotLease() : pool(serve_pool()), s(pool.acquire()) {}
-  ~SlotLease() { if (s) pool.release(s); }
-};
-
-// A serving pass must see every weight write queued on the main stream so far (training is asynchronous).  The calling
-// thread waits for the event on the HOST: a hipStreamWaitEvent from the slot's stream fails ("dependency created on
-// uncaptured work in another stream") whenever another thread happens to be capturing a step graph on the main stream at
-// that moment -- HIP judges the event by its stream's current capture state.  The caller holds the model's lock shared, so
-// no new weight write can be queued while it waits; once the event has completed nothing is pending until the next one.
-int serve_wait_weights(goctr_model* m, ServeSlot* s) {
-  (void)s;
-  if (m->weights_pending.load(std::memory_order_acquire) && m->ev_weights) {
-    GOCTR_HIP(hipEventSynchronize(m->ev_weights));
-    m->weights_pending.store(false, std::memory_order_release);
-  }
-  return 0;
-}
-// the same for the embedding rows a pass gathers (written by embedding training of ANY model that was given the table);
-// the caller holds the table's lock shared
-int serve_wait_rows(goctr_emb* e) {
-  if (e && e->rows_pending.load(std::memory_order_acquire) && e->ev_rows) {
-    GOCTR_HIP(hipEventSynchronize(e->ev_rows));
-    e->rows_pending.store(false, std::memory_order_release);
-  }
-  return 0;
-}
-
-// One pass: the keys of `segs` (N rows in all, N <= SERVE_PASS_ROWS) -> scores / failed flags of every segment.
-// Caller holds m->mu shared and owns the slot.
-int serve_keys_pass(goctr_model* m, goctr_recsys* r, ServeSlot* s, KeySeg* const* segs, int nseg) {
-  int64_t N = 0;
-  for (int k = 0; k < nseg; ++k) N += segs[k]->n;
-  const int T = m->cfg.T;
-  // (sized for a full coalesced pass from the first call on: a slot that grew with every larger pass paid a pinned
-  // re-allocation + a stream synchronisation each time -- part of round 3's serving tail)
-  const int64_t cap_rows = std::max<int64_t>(N, SERVE_COALESCE_ROWS);
-  if (s->ensure_keys(cap_rows, T, r->U, r->C)) return -1;
-  if (s->ws.ensure((int)cap_rows, m->Ip, T, m->H1p, m->H2p, !chain_ok(m), s->stream)) return -1;
-  const size_t Br = (size_t)round_up((int)N, 32);
-  // Small passes read the keys and write the scores without copy commands on the stream (GOCTR_SERVE_ZEROCOPY=rows, default 4096;
-  // 0 = never): a pass is one launch (ctr_serve16_kernel) and one wait.  The keys (16 B per row) are stored by the host straight into
-  // device memory over the PCIe BAR where the system has a large BAR (GOCTR_SERVE_BAR=0: off), else the kernels read the pinned
-  // host buffer; the scores and flags (5 B per row) are written to pinned host memory from inside the kernels.  Larger passes keep
-  // the two DMA copies.
-  const bool zc = N <= 4096;
-  const bool bar = zc && s->in_bar != nullptr && env_int("GOCTR_SERVE_BAR", 1) != 0;
-  char* const key_dst = bar ? s->in_bar : s->h_in;      // (written only, front to back: fine for a write-combined mapping)
-  long long* hts = reinterpret_cast<long long*>(key_dst);
-  int32_t* hus = reinterpret_cast<int32_t*>(key_dst + 8 * N);
-  int32_t* hit = reinterpret_cast<int32_t*>(key_dst + 12 * N);
-  int64_t o = 0;
-  for (int k = 0; k < nseg; ++k) {
-    const KeySeg& g = *segs[k];
-    if (g.ts) memcpy(hts + o, g.ts, sizeof(int64_t) * (size_t)g.n);
-    else for (int64_t i = 0; i < g.n; ++i) hts[o + i] = g.ts_all;
-    if (g.users) memcpy(hus + o, g.users, sizeof(int32_t) * (size_t)g.n);
-    else for (int64_t i = 0; i < g.n; ++i) hus[o + i] = g.user_all;
-    memcpy(hit + o, g.items, sizeof(int32_t) * (size_t)g.n);
-    o += g.n;
-  }
-  if (bar) __builtin_ia32_sfence();                   // the key stores are out before the launch's doorbell
-  if (!zc) GOCTR_HIP(hipMemcpyAsync(s->d_in.p, s->h_in, (size_t)N * 16, hipMemcpyHostToDevice, s->stream));
-  if (serve_wait_weights(m, s) || serve_wait_rows(r->emb)) return -1;
-  const char* in_base = bar ? s->in_bar : (zc ? s->h_in : s->d_in.p);
-  char* out_base = zc ? s->h_out : s->d_out.p;
-  const long long* dts = reinterpret_cast<const long long*>(in_base);
-  const int32_t* dus = reinterpret_cast<const int32_t*>(in_base + 8 * N);
-  const int32_t* dit = reinterpret_cast<const int32_t*>(in_base + 12 * N);
-  float* dscore = reinterpret_cast<float*>(out_base);
-  unsigned char* dfail = reinterpret_cast<unsigned char*>(out_base + 4 * Br);
-  const goctr_ubcache* c = r->ub;
-  StreamScope on_slot(s->stream);
-  RowSource src{};
-  src.rows = N; src.id_mode = 1; src.emb = r->emb->rows.p; src.V = r->emb->V;
-  // Embedding widths with a compile-time attention variant (D = 4 .. 64, a power of two) look the keys up INSIDE attn_fwd
-  // (attn_fwd_keys_kernel, or the whole pass as ctr_serve16_kernel): the assembled rows (behaviour ids, feature rows) never
-  // exist in HBM.  Other widths, tables of 4 GB and more, or GOCTR_SERVE_FUSE=0, assemble first.
-  int fgroups = 0;
-  const bool fuse = env_int("GOCTR_SERVE_FUSE", 1) != 0 && attn_fast_mode(m, src, &fgroups) != 0 && fgroups <= 16;   // (D = 4 .. 64, table < 4 GB)
-  if (fuse) {
-    src.k_users = dus; src.k_items = dit; src.k_ts = dts; src.k_failed = dfail;
-    src.ub_off = c ? c->off.p : nullptr; src.ub_items = c ? c->items.p : nullptr; src.ub_ts = c ? c->ts.p : nullptr;
-    src.user_table = r->user_table.p; src.item_table = r->item_table.p; src.n_users = r->n_users; src.n_items = r->n_items;
-  } else {
-    hipLaunchKernelGGL(assemble_keys_kernel, dim3((unsigned)cdiv(N, 4)), dim3(256), 0, s->stream,
-                       c ? c->off.p : (const long long*)nullptr, c ? c->items.p : (const int32_t*)nullptr,
-                       c ? c->ts.p : (const long long*)nullptr, (long long)r->n_users, r->user_table.p, r->U, r->item_table.p,
-                       (long long)r->n_items, r->C, dus, dit, dts, (long long)N, T, s->ub_ids.p, s->ufeat.p, s->cfeat.p,
-                       s->item_ids.p, dfail);
-    GOCTR_HIP(hipGetLastError());
-    src.ub_ids = s->ub_ids.p; src.item_ids = s->item_ids.p; src.ufeat = s->ufeat.p; src.cfeat = s->cfeat.p;
-  }
-  FwdBufs fb = s->ws.bufs();
-  fb.yhat = dscore;
-  StepOpts op;
-  op.train = false;
-  // A zero-copy pass of one launch: the kernel's workgroups stamp this pass's number into the pinned buffer behind their scores,
-  // and the host watches the stamps instead of waiting for the stream's completion signal -- for passes of up to
-  // GOCTR_SERVE_POLL_ROWS rows (default 512; 0 = never): the release fence in front of a stamp writes back the rows' h0 from the
-  // L2, which costs a 2048-row pass more than the wait saves (profiles/r05_serve_poll.txt; 256 rows until the keys went over the BAR).
-  unsigned n_stamps = 0;
-  if (fuse && serve16_ok(m, src, (int)N)) {          // key lookup + attention + forward chain: one launch
-    const bool poll = zc && N <= (int64_t)env_int("GOCTR_SERVE_POLL_ROWS", 512);
-    if (poll) { if (++s->epoch == 0) s->epoch = 1; n_stamps = (unsigned)cdiv(N, 16); }
-    if (launch_serve16(m, src, (int)N, s->st.p, fb, poll ? s->h_done : nullptr, s->epoch)) return -1;
-  } else
-  if (launch_forward(m, src, (int)N, op, s->st.p, &fb)) return -1;
-  bool want_failed = false;
-  for (int k = 0; k < nseg; ++k) want_failed = want_failed || segs[k]->failed || segs[k]->n_failed >= 0;
-  // scores and flags are adjacent: one copy back (the gap between them is < 128 bytes)
-  const size_t out_bytes = want_failed ? 4 * Br + (size_t)N : 4 * (size_t)N;
-  if (!zc) GOCTR_HIP(hipMemcpyAsync(s->h_out, s->d_out.p, out_bytes, hipMemcpyDeviceToHost, s->stream));
-  bool stamped = false;
-  if (n_stamps) {                                    // (2 ms without the stamps: the stream wait, which also reports a fault)
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned done = 0, spins = 0;;) {
-      while (done < n_stamps && __atomic_load_n(s->h_done + done, __ATOMIC_ACQUIRE) == s->epoch) ++done;
-      if (done == n_stamps) { stamped = true; break; }
-      if ((++spins & 255) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-      __builtin_ia32_pause();
-    }
-  }
-  if (!stamped) GOCTR_HIP(hipStreamSynchronize(s->stream));
-  const float* hs = reinterpret_cast<const float*>(s->h_out);
-  const unsigned char* hf = reinterpret_cast<const unsigned char*>(s->h_out + 4 * Br);
-  o = 0;
-  for (int k = 0; k < nseg; ++k) {
-    KeySeg& g = *segs[k];
-    memcpy(g.scores, hs + o, sizeof(float) * (size_t)g.n);
-    if (want_failed) {
-      if (g.failed) memcpy(g.failed, hf + o, (size_t)g.n);
-      int64_t cnt = 0;
-      for (int64_t i = 0; i < g.n; ++i) cnt += hf[o + i] != 0;
-      g.n_failed = cnt;
-    }
-    o += g.n;
-  }
-  return 0;
-}
-
-}  // namespace
-
-struct goctr_recsys::Req {
-  goctr_model* m; KeySeg seg; int rc = 0; std::atomic<bool> done{false}; std::string err;
-  Req(goctr_model* mm, const KeySeg& s) : m(mm), seg(s) {}
-};
-
-namespace {
-
-// a request of any size on a slot of its own (several passes when it exceeds SERVE_PASS_ROWS)
-int serve_keys_direct(goctr_model* m, goctr_recsys* r, KeySeg& g) {
-  SlotLease lease;
-  if (!lease.s) return -1;
-  const int64_t want_failed = g.n_failed;
-  int64_t total_failed = 0;
-  for (int64_t o = 0; o < g.n; o += SERVE_PASS_ROWS) {
-    KeySeg part = g;
-    part.n = std::min<int64_t>(SERVE_PASS_ROWS, g.n - o);
-    if (g.users) part.users = g.users + o;
-    part.items = g.items + o;
-    if (g.ts) part.ts = g.ts + o;
-    part.scores = g.scores + o;
-    if (g.failed) part.failed = g.failed + o;
-    part.n_failed = want_failed;
-    KeySeg* one = &part;
-    if (serve_keys_pass(m, r, lease.s, &one, 1)) return -1;
-    if (part.n_failed > 0) total_failed += part.n_failed;
-  }
-  g.n_failed = total_failed;
-  return 0;
-}
-
-// the micro-batcher (see the section comment)
-int serve_keys_coalesced(goctr_model* m, goctr_recsys* r, KeySeg& g) {
-  goctr_recsys::Req me(m, g);
-  std::unique_lock<std::mutex> lk(r->qmu);
-  r->queue.push_back(&me);
-  while (!me.done) {
-    if (r->leader.load(std::memory_order_acquire)) {
-      // a pass is in flight: it ends within tens of microseconds -- spin for about that long before paying a futex sleep + wake
-      lk.unlock();
-      for (int spin = 0; spin < 30000; ++spin) {
-        if (me.done.load(std::memory_order_acquire) || !r->leader.load(std::memory_order_acquire)) break;
-        __builtin_ia32_pause();
-      }
-      lk.lock();
-      if (!me.done.load(std::memory_order_acquire) && r->leader.load(std::memory_order_acquire)) r->qcv.wait(lk);
-      continue;
-    }
-    // lead one pass: the longest prefix of the queue on one model that fits a pass (always contains the front)
-    r->leader = true;
-    std::vector<goctr_recsys::Req*> batch;
-    int64_t rows = 0;
-    goctr_model* bm = r->queue.front()->m;
-    size_t take = 0;
-    for (; take < r->queue.size(); ++take) {
-      goctr_recsys::Req* q = r->queue[take];
-      if (q->m != bm || (take > 0 && rows + q->seg.n > SERVE_COALESCE_ROWS)) break;
-      rows += q->seg.n;
-      batch.push_back(q);
-    }
-    r->queue.erase(r->queue.begin(), r->queue.begin() + (long)take);
-    lk.unlock();
-    int rc = 0;
-    std::string err;
-    {
-      SlotLease lease;
-      std::vector<KeySeg*> segs;
-      for (auto* q : batch) segs.push_back(&q->seg);
-      rc = lease.s ? serve_keys_pass(bm, r, lease.s, segs.data(), (int)segs.size()) : -1;
-      if (rc) err = goctr_last_error();
-    }
-    lk.lock();
-    for (auto* q : batch) { q->rc = rc; q->err = err; q->done.store(true, std::memory_order_release); }
-    r->leader.store(false, std::memory_order_release);
-    r->qcv.notify_all();
-  }
-  lk.unlock();
-  if (me.rc) set_error("%s", me.err.c_str());
-  g = me.seg;
-  return me.rc;
-}
-
-int serve_keys(goctr_model* m, goctr_recsys* r, KeySeg& g, int64_t* n_failed) {
-  std::shared_lock<std::shared_mutex> lm(m->mu);        // weights stay put while a slot reads them
-  std::shared_lock<std::shared_mutex> le(r->emb->mu);   // ... and so do the embedding rows (lock order: model, table)
-  const int64_t coalesce = std::min<int64_t>(std::max(0, env_int("GOCTR_SERVE_COALESCE", 1024)), SERVE_COALESCE_ROWS);
-  // Small requests: straight onto a slot when one is free RIGHT NOW (nothing to wait for, nothing to combine with: coalescing
-  // would only add the wait for the pass in flight -- it raised the 8-caller p50 at n = 256 from 38 to 63 us in round 3);
-  // when every slot is busy they join the combining queue, whose next leader scores everything that queued up in ONE pass.
-  int rc;
-  if (g.n <= coalesce) {
-    ServeSlot* free_slot = serve_pool().acquire(true);
-    if (free_slot) {
-      KeySeg* one = &g;
-      const int64_t want_failed = g.n_failed;
-      rc = serve_keys_pass(m, r, free_slot, &one, 1);
-      serve_pool().release(free_slot);
-      if (want_failed < 0) g.n_failed = -1;
-    } else rc = serve_keys_coalesced(m, r, g);
-  } else rc = serve_keys_direct(m, r, g);
-  if (!rc && n_failed) *n_failed = g.n_failed;
-  return rc;
-}
-
-}  // namespace
-
-extern "C" {
-
-int goctr_recsys_create(goctr_ubcache* c, goctr_emb* emb, const float* user_table, int64_t n_users, int U,
-                        const float* item_table, int64_t n_items, int C, goctr_recsys** out) {
-  GOCTR_ENTER_H(emb);
-  GOCTR_SAME_ENGINE(c, emb);
-  GOCTR_CHECK(emb && out && n_users > 0 && n_items > 0 && U >= 0 && C >= 0, "goctr_recsys_create: bad arguments");
-  GOCTR_CHECK((U == 0 || user_table) && (C == 0 || item_table), "goctr_recsys_create: feature table missing");
-  GOCTR_CHECK(!c || c->n_users == n_users, "goctr_recsys_create: user table has %lld rows, the behaviour cache %lld users",
-              (long long)n_users, c ? (long long)c->n_users : 0LL);
-  std::unique_ptr<goctr_recsys> r(new goctr_recsys);
-  r->ub = c; r->emb = emb; r->n_users = n_users; r->n_items = n_items; r->U = U; r->C = C;
-  if (r->user_table.alloc((size_t)n_users * U, false) || (U && r->user_table.upload(user_table, (size_t)n_users * U))) return -1;
-  if (r->item_table.alloc((size_t)n_items * C, false) || (C && r->item_table.upload(item_table, (size_t)n_items * C))) return -1;
-  *out = r.release();
-  return 0;
-}
-
-void goctr_recsys_destroy(goctr_recsys* r) {
-  if (!r) return;
-  EngineScope on(r->eng);
-  std::lock_guard<std::recursive_mutex> lk(r->eng->mu);
-  // (serving passes are synchronous: none is in flight once its caller returned; no device-wide wait -- see goctr_model_destroy)
-  if (engine().inited) { (void)hipStreamSynchronize(engine().stream); (void)hipStreamSynchronize(engine().side); }
-  delete r;
-}
-
-int goctr_batch_predict(goctr_model* m, goctr_recsys* r, const int32_t* users, const int32_t* items, const int64_t* ts,
-                        int64_t n, int batch, float* scores, uint8_t* failed, int64_t* n_failed) {
-  EngineScope on(handle_engine(m));
-  if (require_engine()) return -1;
-  GOCTR_CHECK(m && r && users && items && scores && n >= 0 && batch > 0, "goctr_batch_predict: bad arguments");
-  GOCTR_SAME_ENGINE(m, r);
-  GOCTR_CHECK(r->emb->D == m->cfg.D && r->U == m->cfg.U && r->C == m->cfg.C, "goctr_batch_predict: recsys dims (U=%d,C=%d,D=%d) != model (U=%d,C=%d,D=%d)",
-              r->U, r->C, r->emb->D, m->cfg.U, m->cfg.C, m->cfg.D);
-  if (n_failed) *n_failed = 0;
-  if (n == 0) return 0;
-  // rcmd.go:293-296: a failing FIRST key aborts the call (there is no row width to build a zero row from yet)
-  GOCTR_CHECK(users[0] >= 0 && users[0] < r->n_users && items[0] >= 0 && items[0] < r->n_items,
-              "get sample vector error: first key (user %d, item %d) has no features", users[0], items[0]);
-  // (PredBatchSize `batch` decides how model.Predict cuts the rows, model.go:337-347; a row's score does not depend on it)
-  KeySeg g{users, 0, items, ts, 0, n, scores, failed, (failed || n_failed) ? 0 : -1};
-  return serve_keys(m, r, g, n_failed);
-}
-
-int goctr_rank(goctr_model* m, goctr_recsys* r, int32_t user, const int32_t* items, int64_t n, int64_t ts, int batch,
-               float* scores, uint8_t* failed, int64_t* n_failed) {
-  EngineScope on(handle_engine(m));
-  if (require_engine()) return -1;
-  GOCTR_CHECK(m && r && items && scores && n >= 0 && batch > 0, "goctr_rank: bad arguments");
-  GOCTR_SAME_ENGINE(m, r);
-  GOCTR_CHECK(r->emb->D == m->cfg.D && r->U == m->cfg.U && r->C == m->cfg.C, "goctr_rank: recsys dims (U=%d,C=%d,D=%d) != model (U=%d,C=%d,D=%d)",
-              r->U, r->C, r->emb->D, m->cfg.U, m->cfg.C, m->cfg.D);
-  if (n_failed) *n_failed = 0;
-  if (n == 0) return 0;
-  GOCTR_CHECK(user >= 0 && user < r->n_users && items[0] >= 0 && items[0] < r->n_items,
-              "get sample vector error: first key (user %d, item %d) has no features", user, items[0]);
-  KeySeg g{nullptr, user, items, nullptr, ts, n, scores, failed, (failed || n_failed) ? 0 : -1};
-  return serve_keys(m, r, g, n_failed);
-}
-
-// model.Predict's own convention (model/model.go:242-352): `rows` dense TrainSample rows in HOST memory -> y_out [rows].
-// Concurrent like the two above (PredictAbstract.Predict is what the gin handlers end up in): a slot of its own, the rows
-// travel in passes of <= 64 MB.
-int goctr_predict_dense(goctr_model* m, const float* X, int64_t rows, int xcols, const int ranges[8], int batch,
-                        float* y_out) {
-  EngineScope on(handle_engine(m));
-  if (require_engine()) return -1;
-  GOCTR_CHECK(m && X && y_out && ranges && rows >= 0 && batch > 0 && xcols > 0, "goctr_predict_dense: bad arguments");
-  if (rows == 0) return 0;
-  goctr_dataset shape;                       // (only its ranges are looked at)
-  shape.id_mode = false; shape.rows = rows; shape.xcols = xcols;
-  memcpy(shape.ranges, ranges, sizeof shape.ranges);
-  std::shared_lock<std::shared_mutex> lm(m->mu);
-  if (check_dataset(m, &shape, nullptr)) return -1;
-  SlotLease lease;
-  ServeSlot* s = lease.s;
-  if (!s) return -1;
-  const int64_t pass = std::max<int64_t>(32, std::min<int64_t>(SERVE_PASS_ROWS, ((int64_t)64 << 20) / ((int64_t)xcols * 4) / 32 * 32));
-  StreamScope on_slot(s->stream);
-  for (int64_t o = 0; o < rows; o += pass) {
-    const int64_t N = std::min(pass, rows - o);
-    if (s->capX < (size_t)N * xcols) {
-      GOCTR_HIP(hipStreamSynchronize(s->stream));
-      if (s->X.alloc((size_t)std::min<int64_t>(pass, rows) * xcols, false)) return -1;
-      s->capX = (size_t)std::min<int64_t>(pass, rows) * xcols;
-    }
-    if (s->ensure_keys(N, m->cfg.T, m->cfg.U, m->cfg.C)) return -1;       // (for its pinned score staging and d_out)
-    if (s->ws.ensure((int)N, m->Ip, m->cfg.T, m->H1p, m->H2p, !chain_ok(m), s->stream)) return -1;
-    GOCTR_HIP(hipMemcpyAsync(s->X.p, X + (size_t)o * xcols, (size_t)N * xcols * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    if (serve_wait_weights(m, s)) return -1;
-    RowSource src{};
-    src.rows = N; src.id_mode = 0; src.X = s->X.p; src.xcols = xcols;
-    src.r_u = ranges[0]; src.r_ub = ranges[2]; src.r_v = ranges[4]; src.r_c = ranges[6];
-    FwdBufs fb = s->ws.bufs();
-    fb.yhat = reinterpret_cast<float*>(s->d_out.p);
-    StepOpts op;
-    op.train = false;
-    if (launch_forward(m, src, (int)N, op, s->st.p, &fb)) return -1;
-    GOCTR_HIP(hipMemcpyAsync(s->h_out, s->d_out.p, (size_t)N * 4, hipMemcpyDeviceToHost, s->stream));
-    GOCTR_HIP(hipStreamSynchronize(s->stream));
-    memcpy(y_out + o, s->h_out, (size_t)N * 4);
-  }
-  return 0;
-}
-
-}  // extern "C"

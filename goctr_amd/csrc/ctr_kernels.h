@@ -675,7 +675,7 @@ __device__ __forceinline__ void loss_sum_block(const float* lossrow, int B, floa
 // Every group of 4 consecutive gradient entries is summed by 8 adjacent lanes (lane p takes a
 // contiguous 1/8 of the slabs, 16-byte loads, all independent => deep memory-level parallelism),
 // partial sums are combined by xor-shuffles: a fixed association order => bitwise reproducible.
-#ifndef GOCTR_NO_PLAIN_KERNELS   // (a second translation unit includes this header for its templates only: ctr_fwd.hip)
+#ifndef GOCTR_NO_PLAIN_KERNELS   // (the other CTR translation units include this header for its types and templates only)
 __global__ __launch_bounds__(256) void reduce_kernel(ReduceArgs a) {
   if (blockIdx.x == gridDim.x - 1) {  // last block: deterministic loss sum
     __shared__ float red[256];
@@ -795,7 +795,7 @@ __device__ __forceinline__ void adam_apply_pre(const AdamArgs& a, int idx, float
 
 // (split path: the reduce kernel has already advanced the state.  This step's bias corrections are the new state's pcorr;
 // one extra block computes the new state's own -- the next step's -- off everybody's critical path)
-#ifndef GOCTR_NO_PLAIN_KERNELS   // (a second translation unit includes this header for its templates only: ctr_fwd.hip)
+#ifndef GOCTR_NO_PLAIN_KERNELS   // (the other CTR translation units include this header for its types and templates only)
 __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
   if (blockIdx.x == gridDim.x - 1) {
     if (threadIdx.x == 0) {
@@ -927,7 +927,7 @@ __device__ __forceinline__ void reduce_adam_body(const ReduceAdamArgs& p, int bl
 
 // the bias corrections of the state a call starts from (set_state / a restored checkpoint / a retargeted cursor leave them
 // to this launch; inside a call every step's loss block writes the next state's)
-#ifndef GOCTR_NO_PLAIN_KERNELS   // (a second translation unit includes this header for its templates only: ctr_fwd.hip)
+#ifndef GOCTR_NO_PLAIN_KERNELS   // (the other CTR translation units include this header for its types and templates only)
 __global__ void step_state_corr_kernel(StepState* st, double beta1, double beta2) {
   StepState s = *st;
   state_corrections(s, beta1, beta2);
@@ -935,7 +935,7 @@ __global__ void step_state_corr_kernel(StepState* st, double beta1, double beta2
 }
 #endif
 
-#ifndef GOCTR_NO_PLAIN_KERNELS   // (a second translation unit includes this header for its templates only: ctr_fwd.hip)
+#ifndef GOCTR_NO_PLAIN_KERNELS   // (the other CTR translation units include this header for its types and templates only)
 __global__ __launch_bounds__(256) void reduce_adam_kernel(ReduceAdamArgs p) {
   reduce_adam_body(p, (int)blockIdx.x, (int)gridDim.x);
 }
@@ -1008,29 +1008,5 @@ __global__ __launch_bounds__(256) void adam_attn_kernel(AdamArgs ad, unsigned in
   const int grp = xcd_unit_of_block_after(bi, nadam, (a.B + 3) >> 2, 32);
   attn_fwd_body<VEC, LPR, FAST>(a, grp, ad.st->batch_idx, a.att0, FAST >= 2 ? &ctx : nullptr);
 }
-
-// ---------------------------------------------------------------- standalone gather (bit-exact)
-struct GatherArgs {
-  const float* emb; long long V; int D, T, U, C;
-  const int32_t* ub_ids; const int32_t* item_ids; const float* ufeat; const float* cfeat;
-  long long rows; float* X; int xcols;
-};
-// rcmd.go:497-533: one wavefront per row; pure copies => bit-exact
-#ifndef GOCTR_NO_PLAIN_KERNELS   // (a second translation unit includes this header for its templates only: ctr_fwd.hip)
-__global__ __launch_bounds__(256) void gather_rows_kernel(GatherArgs a) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long long r = (long long)blockIdx.x * 4 + wave;
-  if (r >= a.rows) return;
-  float* row = a.X + r * a.xcols;
-  for (int j = lane; j < a.U; j += 64) row[j] = a.ufeat[r * a.U + j];
-  const int TD = a.T * a.D;
-  for (int j = lane; j < TD + a.D; j += 64) {
-    const int t = j / a.D, d = j - t * a.D;
-    const int id = t < a.T ? a.ub_ids[r * a.T + t] : a.item_ids[r];
-    row[a.U + j] = (id >= 0 && id < a.V) ? a.emb[(long long)id * a.D + d] : 0.f;
-  }
-  for (int j = lane; j < a.C; j += 64) row[a.U + TD + a.D + j] = a.cfeat[r * a.C + j];
-}
-#endif
 
 }  // namespace goctr

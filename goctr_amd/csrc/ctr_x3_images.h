@@ -103,7 +103,7 @@ __device__ __forceinline__ void cx_scatter_weight(const CxImages& im, float w, i
 
 // (re)build every image from the flat float32 weights: after a host upload of weights (the images start zeroed, and the
 // padded weight entries are zero, so only real entries need writing -- but writing all keeps it simple)
-#ifndef GOCTR_NO_PLAIN_KERNELS   // (a second translation unit includes this header for its templates only: ctr_fwd.hip)
+#ifndef GOCTR_NO_PLAIN_KERNELS   // (the other CTR translation units include this header for its types and templates only)
 __global__ __launch_bounds__(256) void x3_build_images_kernel(const float* __restrict__ W, int off1, int off2, int H1p, int H2p,
                                                               int U, int D, CxImages im) {
   const int idx = blockIdx.x * 256 + threadIdx.x;

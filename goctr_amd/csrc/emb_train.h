@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ctr_kernels.h"
+#include "emb_plan.h"
 
 namespace goctr {
 
@@ -353,15 +354,6 @@ __global__ __launch_bounds__(EMB_GRAD_THREADS) void emb_grad_kernel(EmbTrainArgs
 // float32 rounding, not bit for bit.  emb_grad_kernel stays for embedding widths the attention layout does not cover (DIN
 // with D not in {4, 8, 16, 32, 64}) and as the A/B reference (GOCTR_EMB_PLAN=0).
 
-struct EmbPlanView {
-  const int* pair;               // [pairs of all batches]  b << 12 | t   (t == T: the candidate item)
-  const int* pslot;              // slot of the pair inside its batch
-  const int* pid;                // embedding row of the pair
-  const long long* pair_off;     // [nb + 1]
-  const int* slot_id;            // [slots of all batches]
-  const unsigned int* slot_off;  // per batch n_slots + 1 entries (relative to the batch's pairs): batch k's start at slot_base[k] + k
-  const long long* slot_base;    // [nb + 1]
-};
 constexpr int EMB_PAIR_TBITS = 12;                 // t < 4096, b < 2^19
 constexpr int EMB_SEG = 16;                        // pairs per lane group (one component per lane): all of them in flight at once
 constexpr int EMB_SLOT_THREADS = 256;              // 16 lane groups at D = 16: 512 pairs per workgroup, several workgroups per CU

@@ -204,8 +204,7 @@ void* arena_alloc(size_t bytes) {
   std::lock_guard<std::mutex> lk(a.mu);
   const size_t need = (bytes + 255) / 256 * 256;
   if (!a.base) {
-    const char* ev = getenv("GOCTR_ARENA_MB");
-    size_t mb = ev && *ev ? (size_t)atoll(ev) : 2048;
+    size_t mb = (size_t)env_int64("GOCTR_ARENA_MB", 2048);
     if (mb > 0 && hipMalloc((void**)&a.base, mb << 20) == hipSuccess) {
       a.size = mb << 20;
       a.free_blocks[0] = a.size;

@@ -1253,7 +1253,6 @@ int tn_rows64(const goctr_mlp* p, int n) {
   return rows;
 }
 bool up1_le128(const goctr_mlp* p) { return p->up[1] <= 128; }
-int env_int_mlp(const char* name, int dflt) { const char* v = getenv(name); return v && *v ? atoi(v) : dflt; }
 
 int ensure_ws(goctr_mlp* p, int n) {
   if (p->wsN >= n) return 0;
@@ -1683,7 +1682,7 @@ int goctr_mlp_upload(goctr_mlp* p, const float* X, const float* Y, int64_t rows)
   // (ridx stays across uploads: a captured step holds its address)
   p->X64.release();
   const size_t img_bytes = (size_t)rows * p->up[0] * sizeof(double);
-  if (p->chain_ok() && p->up[1] / 16 <= 8 && rows < (1LL << 31) && env_int_mlp("GOCTR_MLP_X64", 1) &&
+  if (p->chain_ok() && p->up[1] / 16 <= 8 && rows < (1LL << 31) && env_int("GOCTR_MLP_X64", 1) &&
       img_bytes <= ((size_t)64 << 30)) {
     if (p->X64.alloc((size_t)rows * p->up[0], false) || p->ridx.ensure((size_t)p->cfg.batch + 64, true)) return -1;
     hipLaunchKernelGGL(mlp_widen_rows_kernel, dim3((unsigned)rows), dim3(256), 0, engine().stream, p->Xr.p, (long long)rows, F,
@@ -1699,7 +1698,7 @@ int goctr_mlp_upload(goctr_mlp* p, const float* X, const float* Y, int64_t rows)
 // on a communicator or with GOCTR_NO_GRAPH.  Asynchronous.  Caller holds p->mu.
 static int run_fused_steps(goctr_mlp* p, int n_steps) {
   Engine& e = engine();
-  const bool use_graph = !e.prof && !e.comm_active() && env_int_mlp("GOCTR_NO_GRAPH", 0) == 0 && n_steps > 1;
+  const bool use_graph = !e.prof && !e.comm_active() && env_int("GOCTR_NO_GRAPH", 0) == 0 && n_steps > 1;
   if (use_graph) {
     if (ensure_ws(p, p->cfg.batch)) return -1;                 // no allocation inside the capture
     if (p->fused_ok() && p->zpart.ensure((size_t)cdiv(p->up[1], 32) * p->cfg.batch, false)) return -1;

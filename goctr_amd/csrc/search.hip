@@ -914,12 +914,10 @@ static int64_t round_up64(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 // (profiles/r05_knn_scan_threshold.txt: 8 queries 44.4 vs 45.0 us, 16 46.8 vs 47.2, 24 49.9 vs 47.6, 32 53.6 vs 48.9, 47 63.6 vs
 // 51.2): from 12 queries on.  (The 48 of round 4 belonged to the float32 MFMA kernel.)  GOCTR_KNN_MFMA=0 / 1 forces either.
 static bool knn_scan_mfma(const goctr_searcher* s, int Q) {
-  const char* v = getenv("GOCTR_KNN_MFMA");
-  return (v && *v ? *v != '0' : Q >= 12) && knn_scan_tile(s->D) == 1024 && s->items_bf.p && (s->D == 16 || s->D == 32);
+  return env_flag("GOCTR_KNN_MFMA", Q >= 12) && knn_scan_tile(s->D) == 1024 && s->items_bf.p && (s->D == 16 || s->D == 32);
 }
 static bool knn_scan_usable(const goctr_searcher* s, int k) {
-  const char* v = getenv("GOCTR_KNN_SCAN");
-  if (v && *v == '0') return false;
+  if (!env_flag("GOCTR_KNN_SCAN", true)) return false;
   const int tile = knn_scan_tile(s->D);
   return tile > 0 && s->items32.p && k + 1 <= 64 && cdiv(s->V, tile) <= (1 << 20);
 }
@@ -956,8 +954,8 @@ static int knn_search_scan(goctr_searcher* s, const double* queries, int Q, int 
   const int qpad = nqb * KNN2_QB;
   // Where the kernels read the input from: device memory the host wrote through the BAR (a 14 KB store burst, ~3 us, instead of a
   // 4.4 us blit kernel on the stream in front of the scan: profiles/r05_knn_bar_input.txt), else the arena buffer behind a copy.
-  const char* bv = getenv("GOCTR_KNN_BAR");           // (0: the staged copy, for A/B runs and the tests' comparison)
-  const bool want_bar = e.large_bar && s->bar_state >= 0 && !(bv && atoi(bv) == 0);
+  // (GOCTR_KNN_BAR=0: the staged copy, for A/B runs and the tests' comparison)
+  const bool want_bar = e.large_bar && s->bar_state >= 0 && env_int_set("GOCTR_KNN_BAR", 1) != 0;
   if (want_bar && s->in_bar_bytes < in_bytes) {
     if (s->in_bar) s->retired_dev.push_back(s->in_bar);
     s->in_bar = nullptr; s->in_bar_bytes = 0;
@@ -996,11 +994,10 @@ static int knn_search_scan(goctr_searcher* s, const double* queries, int Q, int 
       h_qbf[i] = hi; h_qbf[plane + i] = f2bf(x - bf2f(hi));
     }
   }
-  const char* pv = getenv("GOCTR_KNN_POLL_MAXQ");
   // (profiles/r05_knn_poll.txt: with the input over the BAR polling pays up to 64 queries per call -- the bench line 1.18 -> 1.26 M
   // queries/s --, is even at 96 and costs 3 us at 128; with the staged copy it lost 9 us at 64)
   // Without the BAR input (GOCTR_KNN_BAR=0, or no large BAR) the same polling lost 9 us at 64 queries: the default follows `bar`.
-  const bool poll = Q <= (pv ? atoi(pv) : (bar ? 64 : 32));
+  const bool poll = Q <= env_int_set("GOCTR_KNN_POLL_MAXQ", bar ? 64 : 32);
   if (poll) {                                        // (the previous call returned after its kernels' last stores: nothing else writes here)
     int* h_pend = reinterpret_cast<int*>(static_cast<char*>(s->h_out) + o_idx + o_sim);
     for (int i = 0; i < Q; ++i) __atomic_store_n(h_pend + i, KNN_PENDING, __ATOMIC_RELEASE);

@@ -1,0 +1,695 @@
+// serve.hip -- the behaviour cache and key datasets (goctr_ubcache_*, goctr_dataset_create_keys) and serving
+// (goctr_recsys_*, goctr_batch_predict, goctr_rank, goctr_predict_dense) over the forward launches of the step (ctr.hip).
+#define GOCTR_NO_PLAIN_KERNELS      // the kernel headers' plain kernels belong to ctr.hip
+#include <algorithm>
+#include <atomic>
+#include <condition_variable>
+#include <deque>
+#include <memory>
+#include <mutex>
+#include <shared_mutex>
+
+#include "ctr_model.h"
+
+// ------------------------------------------------------------------ device-side sample assembly
+// ubcache.UserBehaviorCache (feature/ubcache/cache.go) as a CSR in HBM + the per-sample gather of GetSampleVector
+// (recommend/rcmd.go:460-536) as one kernel: keys (user, item, timestamp) -> behaviour ids, user / item feature rows.
+struct goctr_ubcache {
+  goctr::Engine* const eng = &goctr::engine();   // the engine (device, streams, arena) the handle was created on
+  int64_t n_users = 0, nnz = 0;
+  DevBuf<long long> off, ts;
+  DevBuf<int32_t> items;
+};
+
+namespace {
+// TimeSeq.Filter (cache.go:71-94) for one key: the sequence is newest-first, so "the first i with Ts[i] <= maxTs"
+// is a lower bound found by bisection; then up to T items from there.
+__global__ __launch_bounds__(256) void assemble_keys_kernel(const long long* __restrict__ off, const int32_t* __restrict__ seq_items,
+                                                            const long long* __restrict__ seq_ts, long long n_users,
+                                                            const float* __restrict__ user_table, int U,
+                                                            const float* __restrict__ item_table, long long n_items, int C,
+                                                            const int32_t* __restrict__ users, const int32_t* __restrict__ items,
+                                                            const long long* __restrict__ ts, long long rows, int T,
+                                                            int32_t* __restrict__ ub_ids, float* __restrict__ ufeat,
+                                                            float* __restrict__ cfeat, int32_t* __restrict__ item_out,
+                                                            unsigned char* __restrict__ failed) {
+  const int lane = threadIdx.x & 63;
+  const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);   // one wavefront per sample
+  if (r >= rows) return;
+  // the key's three fields first, back to back: in a small serving pass they sit in pinned HOST memory (zero-copy), and
+  // fetched one by one where they are used they were three PCIe round trips in a row (7.8 us for a 256-key pass)
+  const int u = users[r];
+  const int it_key = items ? items[r] : -1;
+  const long long ts_key = ts ? ts[r] : 0;
+  bool uok = u >= 0 && u < n_users;
+  if (failed) {
+    // BatchPredict (rcmd.go:291-307): a key whose GetUserFeature / GetItemFeature fails is scored as the ALL-zero row
+    // (user features, behaviours, item embedding and item features alike)
+    const int it = it_key;
+    const bool ok = uok && it >= 0 && it < n_items;
+    if (lane == 0) { failed[r] = ok ? 0 : 1; item_out[r] = ok ? it : -1; }
+    if (!ok) {
+      for (int j = lane; j < T; j += 64) ub_ids[r * T + j] = -1;
+      for (int j = lane; j < U; j += 64) ufeat[r * U + j] = 0.f;
+      for (int j = lane; j < C; j += 64) cfeat[r * C + j] = 0.f;
+      return;
+    }
+  }
+  long long first = 0, cnt = 0;
+  const long long b = (uok && off) ? off[u] : 0, len = (uok && off) ? off[u + 1] - b : 0;   // off == NULL: no behaviour cache
+  if (len > 0) {
+    const long long mts = ts_key;
+    // first i with seq_ts[b + i] <= mts (descending order); mts == 0 means "from the newest" (cache.go:72-74: maxTs = Ts[0])
+    long long lo = 0;
+    if (mts != 0) {
+      if (len <= 256) {
+        // short histories (the common case): 64 entries per coalesced load and one ballot instead of a chain of ~7 dependent
+        // loads -- the serving pass of a Rank call is latency, not work
+        lo = len;
+        for (long long base = 0; base < len; base += 64) {
+          const long long i = base + lane;
+          const unsigned long long le = __ballot(i < len && seq_ts[b + i] <= mts);
+          if (le) { lo = base + (long long)__builtin_ctzll(le); break; }
+        }
+      } else {
+        long long hi = len;
+        while (lo < hi) {
+          const long long mid = (lo + hi) >> 1;
+          if (seq_ts[b + mid] <= mts) hi = mid; else lo = mid + 1;
+        }
+      }
+    }
+    first = lo;
+    cnt = len - first < T ? len - first : T;
+  }
+  if (ub_ids)
+    for (int j = lane; j < T; j += 64) ub_ids[r * T + j] = j < cnt ? seq_items[b + first + j] : -1;
+  if (ufeat)
+    for (int j = lane; j < U; j += 64) ufeat[r * U + j] = uok ? user_table[(long long)u * U + j] : 0.f;
+  if (cfeat) {
+    const int it = it_key;
+    const bool iok = it >= 0 && it < n_items;
+    for (int j = lane; j < C; j += 64) cfeat[r * C + j] = iok ? item_table[(long long)it * C + j] : 0.f;
+  }
+}
+}  // namespace
+
+extern "C" {
+
+int goctr_ubcache_create(int64_t n_users, const int64_t* off, const int32_t* items, const int64_t* ts, goctr_ubcache** out) {
+  GOCTR_ENTER();
+  GOCTR_CHECK(n_users > 0 && off && out && off[0] == 0, "goctr_ubcache_create: bad arguments");
+  const int64_t nnz = off[n_users];
+  GOCTR_CHECK(nnz >= 0 && (nnz == 0 || (items && ts)), "goctr_ubcache_create: sequences missing");
+  for (int64_t u = 0; u < n_users; ++u) {
+    GOCTR_CHECK(off[u + 1] >= off[u], "goctr_ubcache_create: offsets must be non-decreasing");
+    for (int64_t k = off[u] + 1; k < off[u + 1]; ++k)
+      GOCTR_CHECK(ts[k] <= ts[k - 1], "goctr_ubcache_create: user %lld's sequence is not in timestamp-descending order "
+                  "(cache.go:8 TimeSeq)", (long long)u);
+  }
+  std::unique_ptr<goctr_ubcache> c(new goctr_ubcache);
+  c->n_users = n_users; c->nnz = nnz;
+  std::vector<long long> o(off, off + n_users + 1), t(ts, ts + nnz);
+  if (c->off.alloc(o.size(), false) || c->off.upload(o.data(), o.size())) return -1;
+  if (c->items.alloc((size_t)nnz, false) || (nnz && c->items.upload(items, (size_t)nnz))) return -1;
+  if (c->ts.alloc((size_t)nnz, false) || (nnz && c->ts.upload(t.data(), (size_t)nnz))) return -1;
+  *out = c.release();
+  return 0;
+}
+void goctr_ubcache_destroy(goctr_ubcache* c) { delete c; }
+
+int goctr_ubcache_get(goctr_ubcache* c, const int32_t* users, const int64_t* max_ts, int64_t rows, int T, int32_t* out_ids) {
+  GOCTR_ENTER_H(c);
+  GOCTR_CHECK(c && users && out_ids && rows > 0 && T > 0, "goctr_ubcache_get: bad arguments");
+  DevBuf<int32_t> du, dout; DevBuf<long long> dts;
+  std::vector<long long> t(rows, 0);
+  if (max_ts) for (int64_t i = 0; i < rows; ++i) t[i] = max_ts[i];
+  if (du.alloc(rows, false) || du.upload(users, rows) || dts.alloc(rows, false) || dts.upload(t.data(), rows) ||
+      dout.alloc((size_t)rows * T, false)) return -1;
+  hipLaunchKernelGGL(assemble_keys_kernel, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, engine().stream, c->off.p, c->items.p,
+                     c->ts.p, (long long)c->n_users, (const float*)nullptr, 0, (const float*)nullptr, 0LL, 0, du.p,
+                     (const int32_t*)nullptr, dts.p, (long long)rows, T, dout.p, (float*)nullptr, (float*)nullptr,
+                     (int32_t*)nullptr, (unsigned char*)nullptr);
+  GOCTR_HIP(hipGetLastError());
+  return dout.download(out_ids, (size_t)rows * T);
+}
+
+int goctr_dataset_create_keys(goctr_ubcache* c, const float* user_table, int64_t n_users, int U, const float* item_table,
+                              int64_t n_items, int C, const int32_t* users, const int32_t* items, const int64_t* ts,
+                              const float* Y, int64_t rows, int T, goctr_dataset** out) {
+  GOCTR_ENTER_H(c);
+  GOCTR_CHECK(c && users && items && rows > 0 && T > 0 && out && n_items >= 0 && U >= 0 && C >= 0,
+              "goctr_dataset_create_keys: bad arguments");
+  GOCTR_CHECK(n_users == c->n_users, "goctr_dataset_create_keys: user table has %lld rows, the behaviour cache %lld users",
+              (long long)n_users, (long long)c->n_users);
+  GOCTR_CHECK((U == 0 || user_table) && (C == 0 || item_table), "goctr_dataset_create_keys: feature table missing");
+  std::unique_ptr<goctr_dataset> d(new goctr_dataset);
+  d->id_mode = true; d->rows = rows; d->U = U; d->C = C; d->T = T;
+  DevBuf<float> dut, dit; DevBuf<int32_t> du; DevBuf<long long> dts;
+  std::vector<long long> t(rows, 0);
+  if (ts) for (int64_t i = 0; i < rows; ++i) t[i] = ts[i];
+  if (dut.alloc((size_t)n_users * U, false) || (U && dut.upload(user_table, (size_t)n_users * U))) return -1;
+  if (dit.alloc((size_t)n_items * C, false) || (C && dit.upload(item_table, (size_t)n_items * C))) return -1;
+  if (du.alloc(rows, false) || du.upload(users, rows) || dts.alloc(rows, false) || dts.upload(t.data(), rows)) return -1;
+  if (d->ub_ids.alloc((size_t)rows * T, false) || d->item_ids.alloc(rows, false) || d->item_ids.upload(items, rows)) return -1;
+  if (d->ufeat.alloc((size_t)rows * U, false) || d->cfeat.alloc((size_t)rows * C, false)) return -1;
+  hipLaunchKernelGGL(assemble_keys_kernel, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, engine().stream, c->off.p, c->items.p,
+                     c->ts.p, (long long)c->n_users, dut.p, U, dit.p, (long long)n_items, C, du.p, d->item_ids.p, dts.p,
+                     (long long)rows, T, d->ub_ids.p, d->ufeat.p, d->cfeat.p, (int32_t*)nullptr, (unsigned char*)nullptr);
+  GOCTR_HIP(hipGetLastError());
+  GOCTR_HIP(hipStreamSynchronize(engine().stream));   // the temporaries above are released on return
+  if (Y) { if (d->Y.alloc(rows, false) || d->Y.upload(Y, rows)) return -1; d->has_y = true; }
+  *out = d.release();
+  return 0;
+}
+
+// read back the assembled keys of an id-mode dataset (tests, debugging)
+int goctr_dataset_get_ids(goctr_dataset* d, int32_t* ub_ids, float* user_feat, float* ctx_feat) {
+  GOCTR_ENTER_H(d);
+  GOCTR_CHECK(d && d->id_mode, "goctr_dataset_get_ids: not an id-mode dataset");
+  if (ub_ids && d->ub_ids.download(ub_ids, (size_t)d->rows * d->T)) return -1;
+  if (user_feat && d->U && d->ufeat.download(user_feat, (size_t)d->rows * d->U)) return -1;
+  if (ctx_feat && d->C && d->cfeat.download(ctx_feat, (size_t)d->rows * d->C)) return -1;
+  return 0;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ serving: recommend.BatchPredict / Rank / Predict
+// recommend/rcmd.go:248-337: sample keys -> GetSampleVector rows -> PredictAbstract.Predict -> scores, called from concurrent
+// gin handler goroutines (recommend/api.go:106-131: one user, a short itemIdList per request).  Everything GetSampleVector
+// reads per key (rcmd.go:462-536) is resident in HBM -- the user / item feature tables (the contents of UserFeatureCache /
+// ItemFeatureCache), the behaviour cache, the item-embedding table -- so one call is: keys (16 B each) to the device, one
+// assembly launch, the forward launches, scores back.
+//
+// Concurrency.  These entry points do not take the engine lock and do not use the engine's main stream.  A call borrows a
+// SERVING SLOT: its own HIP stream, pinned host staging for keys and scores (one H2D and one D2H copy per pass, both
+// asynchronous on the slot's stream; no per-call allocation, no std::vector copies), the id-mode rows assembled from the
+// keys and a forward workspace.  It holds the model's lock SHARED (training holds it exclusive), and its stream waits for
+// the event the last weight-writing call recorded on the main stream -- training is asynchronous.  Slots: GOCTR_SERVE_SLOTS
+// (default 8), created on first use; further callers wait for a free one, first come first served (ServePool).
+//
+// Micro-batching.  A Rank request is tens to hundreds of rows: three small launches and two copies whose cost is latency,
+// not work.  Requests of <= GOCTR_SERVE_COALESCE rows (default 1024) go through a combining queue per recsys: the first
+// arrival becomes the leader and serves its own request; whatever arrives on the same model while that pass is in flight is
+// taken over as ONE pass (<= 4096 rows) by the next leader -- one of the waiting callers, so no thread serves others after
+// its own result is ready.  Rows are scored independently and passes of < 8192 rows all run the same forward kernel
+// (ctr_fwd16_kernel), so a request's scores are bit-identical whether or not, and with whatever, it was coalesced.
+struct goctr_recsys {
+  goctr::Engine* const eng = &goctr::engine();   // the engine (device, streams, arena) the handle was created on
+  goctr_ubcache* ub = nullptr;    // not owned
+  goctr_emb* emb = nullptr;       // not owned
+  int64_t n_users = 0, n_items = 0; int U = 0, C = 0;
+  DevBuf<float> user_table, item_table;
+  // combining queue of small requests (micro-batcher)
+  struct Req;
+  std::mutex qmu; std::condition_variable qcv;
+  std::vector<Req*> queue; std::atomic<bool> leader{false};
+};
+
+namespace {
+
+constexpr int64_t SERVE_PASS_ROWS = 65536;      // rows one pass of a slot scores (larger requests: several passes)
+constexpr int64_t SERVE_COALESCE_ROWS = 4096;   // rows one coalesced pass may hold (< 8192: always ctr_fwd16_kernel)
+
+// one request's keys and outputs (host pointers of the caller)
+struct KeySeg {
+  const int32_t* users; int32_t user_all;       // users == null: every key has user_all (Rank)
+  const int32_t* items;
+  const int64_t* ts; int64_t ts_all;            // ts == null: every key has ts_all
+  int64_t n;
+  float* scores; uint8_t* failed; int64_t n_failed;
+};
+
+struct ServeSlot {
+  hipStream_t stream = nullptr;
+  int64_t cap = 0; int T = 0, U = 0, C = 0;
+  // pinned staging: in = [ts i64 x N | users i32 x N | items i32 x N], out = [scores f32 x Br | failed u8 x N]
+  char* h_in = nullptr; char* h_out = nullptr;
+  unsigned* h_done = nullptr; unsigned epoch = 0;   // behind the failed flags in h_out: one word per 16-row workgroup (serve_keys_pass)
+  // the keys of a zero-copy pass in fine-grained DEVICE memory that the host stores into over the PCIe BAR (large-BAR systems): the
+  // kernel's first loads are local instead of a PCIe read round trip.  Null: the kernels read the pinned h_in.
+  char* in_bar = nullptr; std::vector<void*> retired_dev;
+  std::vector<void*> retired;      // outgrown pinned buffers (see ensure_keys)
+  DevBuf<char> d_in, d_out;
+  DevBuf<int32_t> ub_ids, item_ids; DevBuf<float> ufeat, cfeat;
+  FwdWs ws;
+  DevBuf<StepState> st;            // one all-zero state: "batch 0 of 1"
+  DevBuf<float> X; size_t capX = 0;   // dense rows (goctr_predict_dense)
+  ~ServeSlot() {
+    for (void* p : retired_dev) (void)hipFree(p);
+    if (in_bar) (void)hipFree(in_bar);
+    for (void* p : retired) (void)hipHostFree(p);
+    if (h_in) (void)hipHostFree(h_in);
+    if (h_out) (void)hipHostFree(h_out);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+  int init() {
+    GOCTR_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    if (st.alloc(1, false)) return -1;
+    const StepState z{0u, 0u, 0, 1};
+    GOCTR_HIP(hipMemcpyAsync(st.p, &z, sizeof z, hipMemcpyHostToDevice, stream));
+    GOCTR_HIP(hipStreamSynchronize(stream));
+    return 0;
+  }
+  // room for n keys of a model / recsys with these widths
+  int ensure_keys(int64_t n, int Tn, int Un, int Cn) {
+    if (n <= cap && Tn == T && Un == U && Cn == C) return 0;
+    GOCTR_HIP(hipStreamSynchronize(stream));
+    const int64_t want = std::max<int64_t>(std::max<int64_t>(n, 256), std::min<int64_t>(2 * cap, SERVE_PASS_ROWS));
+    const size_t Br = (size_t)round_up((int)want, 32);
+    cap = 0;                                   // (a failure below must not leave the old capacity next to missing buffers)
+    // (outgrown pinned buffers are kept until the slot goes: hipHostFree waits for the whole device, which would invalidate the
+    // stream capture of a thread that is building step graphs meanwhile -- a handful of geometric growths per slot at most)
+    if (h_in) { retired.push_back(h_in); h_in = nullptr; }
+    if (h_out) { retired.push_back(h_out); h_out = nullptr; }
+    GOCTR_HIP(hipHostMalloc((void**)&h_in, (size_t)want * 16, hipHostMallocDefault));
+    if (in_bar) { retired_dev.push_back(in_bar); in_bar = nullptr; }
+    if (env_int("GOCTR_SERVE_BAR", 1) != 0) in_bar = static_cast<char*>(bar_alloc((size_t)want * 16));   // (null: the pinned buffer serves)
+    const size_t done_off = (Br * 4 + (size_t)want + 63) / 64 * 64, done_n = (size_t)want / 16 + 1;
+    GOCTR_HIP(hipHostMalloc((void**)&h_out, done_off + 4 * done_n, hipHostMallocDefault));
+    h_done = reinterpret_cast<unsigned*>(h_out + done_off);
+    memset(h_done, 0, 4 * done_n); epoch = 0;
+    if (d_in.alloc((size_t)want * 16, false) || d_out.alloc(Br * 4 + (size_t)want, false) ||
+        ub_ids.alloc((size_t)want * Tn, false) || item_ids.alloc((size_t)want, false) ||
+        ufeat.alloc((size_t)want * Un, false) || cfeat.alloc((size_t)want * Cn, false)) return -1;
+    cap = want; T = Tn; U = Un; C = Cn;
+    return 0;
+  }
+};
+
+// Slots are handed out FAIRLY: a released slot goes straight to the longest-waiting caller (FIFO hand-off, no barging).  With a
+// plain condition variable a caller in a closed loop re-took the slot it had just released before the woken waiter was
+// scheduled, and waiters starved: 8 callers on 4 slots had a p99 of 300 - 870 us and a worst case of 50 ms against a p50 of
+// 40 us (round 3's serving tail; profiles/r04_serve_tail.txt).  A waiter first spins on its hand-off word for about one pass
+// (~50 us) -- a futex wake-up costs as much as the pass it waits for -- and only then blocks.
+struct ServePool {
+  std::mutex mu;
+  std::vector<std::unique_ptr<ServeSlot>> all; std::vector<ServeSlot*> idle;
+  struct Waiter { std::atomic<ServeSlot*> got{nullptr}; std::condition_variable cv; bool blocked = false; };
+  std::deque<Waiter*> waiters;
+  // try_only: null instead of waiting when every slot is busy (the micro-batcher's "is a slot free right now?")
+  ServeSlot* acquire(bool try_only = false) {
+    Waiter w;
+    {
+      std::unique_lock<std::mutex> lk(mu);
+      const size_t max_slots = (size_t)std::max(1, env_int("GOCTR_SERVE_SLOTS", 8));
+      if (waiters.empty()) {
+        if (!idle.empty()) { ServeSlot* s = idle.back(); idle.pop_back(); return s; }
+        if (all.size() < max_slots) {
+          std::unique_ptr<ServeSlot> s(new ServeSlot);
+          if (s->init()) return nullptr;
+          all.push_back(std::move(s));
+          return all.back().get();
+        }
+      }
+      if (try_only) return nullptr;
+      waiters.push_back(&w);
+    }
+    for (int spin = 0; spin < 20000; ++spin) {            // ~50 us
+      if (ServeSlot* s = w.got.load(std::memory_order_acquire)) return s;
+      __builtin_ia32_pause();
+    }
+    std::unique_lock<std::mutex> lk(mu);
+    w.blocked = true;
+    w.cv.wait(lk, [&] { return w.got.load(std::memory_order_acquire) != nullptr; });
+    return w.got.load(std::memory_order_acquire);
+  }
+  void release(ServeSlot* s) {
+    std::lock_guard<std::mutex> lk(mu);
+    if (waiters.empty()) { idle.push_back(s); return; }
+    Waiter* w = waiters.front();
+    waiters.pop_front();
+    // (w lives on the waiter's stack.  A SPINNING waiter returns the moment it sees `got`: nothing of w may be touched after
+    // the store.  A BLOCKED waiter cannot return before it re-takes `mu`, which we hold until after the notify.)
+    const bool blocked = w->blocked;
+    w->got.store(s, std::memory_order_release);
+    if (blocked) w->cv.notify_one();
+  }
+  // (goctr_*_destroy of something a slot may have buffers sized for: nothing to do -- slots hold no handle pointers)
+};
+// (never destroyed: a static destructor would release streams and pinned buffers after the HIP runtime has shut down)
+ServePool& serve_pool() {
+  Engine& e = engine();                        // (slots hold streams and buffers of this engine's device)
+  static std::mutex mu;
+  std::lock_guard<std::mutex> lk(mu);
+  if (!e.serve_pool) e.serve_pool = new ServePool;
+  return *static_cast<ServePool*>(e.serve_pool);
+}
+struct SlotLease {
+  ServePool& pool;
+  ServeSlot* s;
+  SlotLease() : pool(serve_pool()), s(pool.acquire()) {}
+  ~SlotLease() { if (s) pool.release(s); }
+};
+
+// A serving pass must see every weight write queued on the main stream so far (training is asynchronous).  The calling
+// thread waits for the event on the HOST: a hipStreamWaitEvent from the slot's stream fails ("dependency created on
+// uncaptured work in another stream") whenever another thread happens to be capturing a step graph on the main stream at
+// that moment -- HIP judges the event by its stream's current capture state.  The caller holds the model's lock shared, so
+// no new weight write can be queued while it waits; once the event has completed nothing is pending until the next one.
+int serve_wait_weights(goctr_model* m, ServeSlot* s) {
+  (void)s;
+  if (m->weights_pending.load(std::memory_order_acquire) && m->ev_weights) {
+    GOCTR_HIP(hipEventSynchronize(m->ev_weights));
+    m->weights_pending.store(false, std::memory_order_release);
+  }
+  return 0;
+}
+// the same for the embedding rows a pass gathers (written by embedding training of ANY model that was given the table);
+// the caller holds the table's lock shared
+int serve_wait_rows(goctr_emb* e) {
+  if (e && e->rows_pending.load(std::memory_order_acquire) && e->ev_rows) {
+    GOCTR_HIP(hipEventSynchronize(e->ev_rows));
+    e->rows_pending.store(false, std::memory_order_release);
+  }
+  return 0;
+}
+
+// One pass: the keys of `segs` (N rows in all, N <= SERVE_PASS_ROWS) -> scores / failed flags of every segment.
+// Caller holds m->mu shared and owns the slot.
+int serve_keys_pass(goctr_model* m, goctr_recsys* r, ServeSlot* s, KeySeg* const* segs, int nseg) {
+  int64_t N = 0;
+  for (int k = 0; k < nseg; ++k) N += segs[k]->n;
+  const int T = m->cfg.T;
+  // (sized for a full coalesced pass from the first call on: a slot that grew with every larger pass paid a pinned
+  // re-allocation + a stream synchronisation each time -- part of round 3's serving tail)
+  const int64_t cap_rows = std::max<int64_t>(N, SERVE_COALESCE_ROWS);
+  if (s->ensure_keys(cap_rows, T, r->U, r->C)) return -1;
+  if (s->ws.ensure((int)cap_rows, m->Ip, T, m->H1p, m->H2p, !chain_ok(m), s->stream)) return -1;
+  const size_t Br = (size_t)round_up((int)N, 32);
+  // Small passes read the keys and write the scores without copy commands on the stream (GOCTR_SERVE_ZEROCOPY=rows, default 4096;
+  // 0 = never): a pass is one launch (ctr_serve16_kernel) and one wait.  The keys (16 B per row) are stored by the host straight into
+  // device memory over the PCIe BAR where the system has a large BAR (GOCTR_SERVE_BAR=0: off), else the kernels read the pinned
+  // host buffer; the scores and flags (5 B per row) are written to pinned host memory from inside the kernels.  Larger passes keep
+  // the two DMA copies.
+  const bool zc = N <= 4096;
+  const bool bar = zc && s->in_bar != nullptr && env_int("GOCTR_SERVE_BAR", 1) != 0;
+  char* const key_dst = bar ? s->in_bar : s->h_in;      // (written only, front to back: fine for a write-combined mapping)
+  long long* hts = reinterpret_cast<long long*>(key_dst);
+  int32_t* hus = reinterpret_cast<int32_t*>(key_dst + 8 * N);
+  int32_t* hit = reinterpret_cast<int32_t*>(key_dst + 12 * N);
+  int64_t o = 0;
+  for (int k = 0; k < nseg; ++k) {
+    const KeySeg& g = *segs[k];
+    if (g.ts) memcpy(hts + o, g.ts, sizeof(int64_t) * (size_t)g.n);
+    else for (int64_t i = 0; i < g.n; ++i) hts[o + i] = g.ts_all;
+    if (g.users) memcpy(hus + o, g.users, sizeof(int32_t) * (size_t)g.n);
+    else for (int64_t i = 0; i < g.n; ++i) hus[o + i] = g.user_all;
+    memcpy(hit + o, g.items, sizeof(int32_t) * (size_t)g.n);
+    o += g.n;
+  }
+  if (bar) __builtin_ia32_sfence();                   // the key stores are out before the launch's doorbell
+  if (!zc) GOCTR_HIP(hipMemcpyAsync(s->d_in.p, s->h_in, (size_t)N * 16, hipMemcpyHostToDevice, s->stream));
+  if (serve_wait_weights(m, s) || serve_wait_rows(r->emb)) return -1;
+  const char* in_base = bar ? s->in_bar : (zc ? s->h_in : s->d_in.p);
+  char* out_base = zc ? s->h_out : s->d_out.p;
+  const long long* dts = reinterpret_cast<const long long*>(in_base);
+  const int32_t* dus = reinterpret_cast<const int32_t*>(in_base + 8 * N);
+  const int32_t* dit = reinterpret_cast<const int32_t*>(in_base + 12 * N);
+  float* dscore = reinterpret_cast<float*>(out_base);
+  unsigned char* dfail = reinterpret_cast<unsigned char*>(out_base + 4 * Br);
+  const goctr_ubcache* c = r->ub;
+  StreamScope on_slot(s->stream);
+  RowSource src{};
+  src.rows = N; src.id_mode = 1; src.emb = r->emb->rows.p; src.V = r->emb->V;
+  // Embedding widths with a compile-time attention variant (D = 4 .. 64, a power of two) look the keys up INSIDE attn_fwd
+  // (attn_fwd_keys_kernel, or the whole pass as ctr_serve16_kernel): the assembled rows (behaviour ids, feature rows) never
+  // exist in HBM.  Other widths, tables of 4 GB and more, or GOCTR_SERVE_FUSE=0, assemble first.
+  int fgroups = 0;
+  const bool fuse = env_int("GOCTR_SERVE_FUSE", 1) != 0 && attn_fast_mode(m, src, &fgroups) != 0 && fgroups <= 16;   // (D = 4 .. 64, table < 4 GB)
+  if (fuse) {
+    src.k_users = dus; src.k_items = dit; src.k_ts = dts; src.k_failed = dfail;
+    src.ub_off = c ? c->off.p : nullptr; src.ub_items = c ? c->items.p : nullptr; src.ub_ts = c ? c->ts.p : nullptr;
+    src.user_table = r->user_table.p; src.item_table = r->item_table.p; src.n_users = r->n_users; src.n_items = r->n_items;
+  } else {
+    hipLaunchKernelGGL(assemble_keys_kernel, dim3((unsigned)cdiv(N, 4)), dim3(256), 0, s->stream,
+                       c ? c->off.p : (const long long*)nullptr, c ? c->items.p : (const int32_t*)nullptr,
+                       c ? c->ts.p : (const long long*)nullptr, (long long)r->n_users, r->user_table.p, r->U, r->item_table.p,
+                       (long long)r->n_items, r->C, dus, dit, dts, (long long)N, T, s->ub_ids.p, s->ufeat.p, s->cfeat.p,
+                       s->item_ids.p, dfail);
+    GOCTR_HIP(hipGetLastError());
+    src.ub_ids = s->ub_ids.p; src.item_ids = s->item_ids.p; src.ufeat = s->ufeat.p; src.cfeat = s->cfeat.p;
+  }
+  FwdBufs fb = s->ws.bufs();
+  fb.yhat = dscore;
+  StepOpts op;
+  op.train = false;
+  // A zero-copy pass of one launch: the kernel's workgroups stamp this pass's number into the pinned buffer behind their scores,
+  // and the host watches the stamps instead of waiting for the stream's completion signal -- for passes of up to
+  // GOCTR_SERVE_POLL_ROWS rows (default 512; 0 = never): the release fence in front of a stamp writes back the rows' h0 from the
+  // L2, which costs a 2048-row pass more than the wait saves (profiles/r05_serve_poll.txt; 256 rows until the keys went over the BAR).
+  unsigned n_stamps = 0;
+  if (fuse && serve16_ok(m, src, (int)N)) {          // key lookup + attention + forward chain: one launch
+    const bool poll = zc && N <= (int64_t)env_int("GOCTR_SERVE_POLL_ROWS", 512);
+    if (poll) { if (++s->epoch == 0) s->epoch = 1; n_stamps = (unsigned)cdiv(N, 16); }
+    if (launch_serve16(m, src, (int)N, s->st.p, fb, poll ? s->h_done : nullptr, s->epoch)) return -1;
+  } else
+  if (launch_forward(m, src, (int)N, op, s->st.p, &fb)) return -1;
+  bool want_failed = false;
+  for (int k = 0; k < nseg; ++k) want_failed = want_failed || segs[k]->failed || segs[k]->n_failed >= 0;
+  // scores and flags are adjacent: one copy back (the gap between them is < 128 bytes)
+  const size_t out_bytes = want_failed ? 4 * Br + (size_t)N : 4 * (size_t)N;
+  if (!zc) GOCTR_HIP(hipMemcpyAsync(s->h_out, s->d_out.p, out_bytes, hipMemcpyDeviceToHost, s->stream));
+  bool stamped = false;
+  if (n_stamps) {                                    // (2 ms without the stamps: the stream wait, which also reports a fault)
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned done = 0, spins = 0;;) {
+      while (done < n_stamps && __atomic_load_n(s->h_done + done, __ATOMIC_ACQUIRE) == s->epoch) ++done;
+      if (done == n_stamps) { stamped = true; break; }
+      if ((++spins & 255) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
+      __builtin_ia32_pause();
+    }
+  }
+  if (!stamped) GOCTR_HIP(hipStreamSynchronize(s->stream));
+  const float* hs = reinterpret_cast<const float*>(s->h_out);
+  const unsigned char* hf = reinterpret_cast<const unsigned char*>(s->h_out + 4 * Br);
+  o = 0;
+  for (int k = 0; k < nseg; ++k) {
+    KeySeg& g = *segs[k];
+    memcpy(g.scores, hs + o, sizeof(float) * (size_t)g.n);
+    if (want_failed) {
+      if (g.failed) memcpy(g.failed, hf + o, (size_t)g.n);
+      int64_t cnt = 0;
+      for (int64_t i = 0; i < g.n; ++i) cnt += hf[o + i] != 0;
+      g.n_failed = cnt;
+    }
+    o += g.n;
+  }
+  return 0;
+}
+
+}  // namespace
+
+struct goctr_recsys::Req {
+  goctr_model* m; KeySeg seg; int rc = 0; std::atomic<bool> done{false}; std::string err;
+  Req(goctr_model* mm, const KeySeg& s) : m(mm), seg(s) {}
+};
+
+namespace {
+
+// a request of any size on a slot of its own (several passes when it exceeds SERVE_PASS_ROWS)
+int serve_keys_direct(goctr_model* m, goctr_recsys* r, KeySeg& g) {
+  SlotLease lease;
+  if (!lease.s) return -1;
+  const int64_t want_failed = g.n_failed;
+  int64_t total_failed = 0;
+  for (int64_t o = 0; o < g.n; o += SERVE_PASS_ROWS) {
+    KeySeg part = g;
+    part.n = std::min<int64_t>(SERVE_PASS_ROWS, g.n - o);
+    if (g.users) part.users = g.users + o;
+    part.items = g.items + o;
+    if (g.ts) part.ts = g.ts + o;
+    part.scores = g.scores + o;
+    if (g.failed) part.failed = g.failed + o;
+    part.n_failed = want_failed;
+    KeySeg* one = &part;
+    if (serve_keys_pass(m, r, lease.s, &one, 1)) return -1;
+    if (part.n_failed > 0) total_failed += part.n_failed;
+  }
+  g.n_failed = total_failed;
+  return 0;
+}
+
+// the micro-batcher (see the section comment)
+int serve_keys_coalesced(goctr_model* m, goctr_recsys* r, KeySeg& g) {
+  goctr_recsys::Req me(m, g);
+  std::unique_lock<std::mutex> lk(r->qmu);
+  r->queue.push_back(&me);
+  while (!me.done) {
+    if (r->leader.load(std::memory_order_acquire)) {
+      // a pass is in flight: it ends within tens of microseconds -- spin for about that long before paying a futex sleep + wake
+      lk.unlock();
+      for (int spin = 0; spin < 30000; ++spin) {
+        if (me.done.load(std::memory_order_acquire) || !r->leader.load(std::memory_order_acquire)) break;
+        __builtin_ia32_pause();
+      }
+      lk.lock();
+      if (!me.done.load(std::memory_order_acquire) && r->leader.load(std::memory_order_acquire)) r->qcv.wait(lk);
+      continue;
+    }
+    // lead one pass: the longest prefix of the queue on one model that fits a pass (always contains the front)
+    r->leader = true;
+    std::vector<goctr_recsys::Req*> batch;
+    int64_t rows = 0;
+    goctr_model* bm = r->queue.front()->m;
+    size_t take = 0;
+    for (; take < r->queue.size(); ++take) {
+      goctr_recsys::Req* q = r->queue[take];
+      if (q->m != bm || (take > 0 && rows + q->seg.n > SERVE_COALESCE_ROWS)) break;
+      rows += q->seg.n;
+      batch.push_back(q);
+    }
+    r->queue.erase(r->queue.begin(), r->queue.begin() + (long)take);
+    lk.unlock();
+    int rc = 0;
+    std::string err;
+    {
+      SlotLease lease;
+      std::vector<KeySeg*> segs;
+      for (auto* q : batch) segs.push_back(&q->seg);
+      rc = lease.s ? serve_keys_pass(bm, r, lease.s, segs.data(), (int)segs.size()) : -1;
+      if (rc) err = goctr_last_error();
+    }
+    lk.lock();
+    for (auto* q : batch) { q->rc = rc; q->err = err; q->done.store(true, std::memory_order_release); }
+    r->leader.store(false, std::memory_order_release);
+    r->qcv.notify_all();
+  }
+  lk.unlock();
+  if (me.rc) set_error("%s", me.err.c_str());
+  g = me.seg;
+  return me.rc;
+}
+
+int serve_keys(goctr_model* m, goctr_recsys* r, KeySeg& g, int64_t* n_failed) {
+  std::shared_lock<std::shared_mutex> lm(m->mu);        // weights stay put while a slot reads them
+  std::shared_lock<std::shared_mutex> le(r->emb->mu);   // ... and so do the embedding rows (lock order: model, table)
+  const int64_t coalesce = std::min<int64_t>(std::max(0, env_int("GOCTR_SERVE_COALESCE", 1024)), SERVE_COALESCE_ROWS);
+  // Small requests: straight onto a slot when one is free RIGHT NOW (nothing to wait for, nothing to combine with: coalescing
+  // would only add the wait for the pass in flight -- it raised the 8-caller p50 at n = 256 from 38 to 63 us in round 3);
+  // when every slot is busy they join the combining queue, whose next leader scores everything that queued up in ONE pass.
+  int rc;
+  if (g.n <= coalesce) {
+    ServeSlot* free_slot = serve_pool().acquire(true);
+    if (free_slot) {
+      KeySeg* one = &g;
+      const int64_t want_failed = g.n_failed;
+      rc = serve_keys_pass(m, r, free_slot, &one, 1);
+      serve_pool().release(free_slot);
+      if (want_failed < 0) g.n_failed = -1;
+    } else rc = serve_keys_coalesced(m, r, g);
+  } else rc = serve_keys_direct(m, r, g);
+  if (!rc && n_failed) *n_failed = g.n_failed;
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int goctr_recsys_create(goctr_ubcache* c, goctr_emb* emb, const float* user_table, int64_t n_users, int U,
+                        const float* item_table, int64_t n_items, int C, goctr_recsys** out) {
+  GOCTR_ENTER_H(emb);
+  GOCTR_SAME_ENGINE(c, emb);
+  GOCTR_CHECK(emb && out && n_users > 0 && n_items > 0 && U >= 0 && C >= 0, "goctr_recsys_create: bad arguments");
+  GOCTR_CHECK((U == 0 || user_table) && (C == 0 || item_table), "goctr_recsys_create: feature table missing");
+  GOCTR_CHECK(!c || c->n_users == n_users, "goctr_recsys_create: user table has %lld rows, the behaviour cache %lld users",
+              (long long)n_users, c ? (long long)c->n_users : 0LL);
+  std::unique_ptr<goctr_recsys> r(new goctr_recsys);
+  r->ub = c; r->emb = emb; r->n_users = n_users; r->n_items = n_items; r->U = U; r->C = C;
+  if (r->user_table.alloc((size_t)n_users * U, false) || (U && r->user_table.upload(user_table, (size_t)n_users * U))) return -1;
+  if (r->item_table.alloc((size_t)n_items * C, false) || (C && r->item_table.upload(item_table, (size_t)n_items * C))) return -1;
+  *out = r.release();
+  return 0;
+}
+
+void goctr_recsys_destroy(goctr_recsys* r) {
+  if (!r) return;
+  EngineScope on(r->eng);
+  std::lock_guard<std::recursive_mutex> lk(r->eng->mu);
+  // (serving passes are synchronous: none is in flight once its caller returned; no device-wide wait -- see goctr_model_destroy)
+  if (engine().inited) { (void)hipStreamSynchronize(engine().stream); (void)hipStreamSynchronize(engine().side); }
+  delete r;
+}
+
+int goctr_batch_predict(goctr_model* m, goctr_recsys* r, const int32_t* users, const int32_t* items, const int64_t* ts,
+                        int64_t n, int batch, float* scores, uint8_t* failed, int64_t* n_failed) {
+  EngineScope on(handle_engine(m));
+  if (require_engine()) return -1;
+  GOCTR_CHECK(m && r && users && items && scores && n >= 0 && batch > 0, "goctr_batch_predict: bad arguments");
+  GOCTR_SAME_ENGINE(m, r);
+  GOCTR_CHECK(r->emb->D == m->cfg.D && r->U == m->cfg.U && r->C == m->cfg.C, "goctr_batch_predict: recsys dims (U=%d,C=%d,D=%d) != model (U=%d,C=%d,D=%d)",
+              r->U, r->C, r->emb->D, m->cfg.U, m->cfg.C, m->cfg.D);
+  if (n_failed) *n_failed = 0;
+  if (n == 0) return 0;
+  // rcmd.go:293-296: a failing FIRST key aborts the call (there is no row width to build a zero row from yet)
+  GOCTR_CHECK(users[0] >= 0 && users[0] < r->n_users && items[0] >= 0 && items[0] < r->n_items,
+              "get sample vector error: first key (user %d, item %d) has no features", users[0], items[0]);
+  // (PredBatchSize `batch` decides how model.Predict cuts the rows, model.go:337-347; a row's score does not depend on it)
+  KeySeg g{users, 0, items, ts, 0, n, scores, failed, (failed || n_failed) ? 0 : -1};
+  return serve_keys(m, r, g, n_failed);
+}
+
+int goctr_rank(goctr_model* m, goctr_recsys* r, int32_t user, const int32_t* items, int64_t n, int64_t ts, int batch,
+               float* scores, uint8_t* failed, int64_t* n_failed) {
+  EngineScope on(handle_engine(m));
+  if (require_engine()) return -1;
+  GOCTR_CHECK(m && r && items && scores && n >= 0 && batch > 0, "goctr_rank: bad arguments");
+  GOCTR_SAME_ENGINE(m, r);
+  GOCTR_CHECK(r->emb->D == m->cfg.D && r->U == m->cfg.U && r->C == m->cfg.C, "goctr_rank: recsys dims (U=%d,C=%d,D=%d) != model (U=%d,C=%d,D=%d)",
+              r->U, r->C, r->emb->D, m->cfg.U, m->cfg.C, m->cfg.D);
+  if (n_failed) *n_failed = 0;
+  if (n == 0) return 0;
+  GOCTR_CHECK(user >= 0 && user < r->n_users && items[0] >= 0 && items[0] < r->n_items,
+              "get sample vector error: first key (user %d, item %d) has no features", user, items[0]);
+  KeySeg g{nullptr, user, items, nullptr, ts, n, scores, failed, (failed || n_failed) ? 0 : -1};
+  return serve_keys(m, r, g, n_failed);
+}
+
+// model.Predict's own convention (model/model.go:242-352): `rows` dense TrainSample rows in HOST memory -> y_out [rows].
+// Concurrent like the two above (PredictAbstract.Predict is what the gin handlers end up in): a slot of its own, the rows
+// travel in passes of <= 64 MB.
+int goctr_predict_dense(goctr_model* m, const float* X, int64_t rows, int xcols, const int ranges[8], int batch,
+                        float* y_out) {
+  EngineScope on(handle_engine(m));
+  if (require_engine()) return -1;
+  GOCTR_CHECK(m && X && y_out && ranges && rows >= 0 && batch > 0 && xcols > 0, "goctr_predict_dense: bad arguments");
+  if (rows == 0) return 0;
+  goctr_dataset shape;                       // (only its ranges are looked at)
+  shape.id_mode = false; shape.rows = rows; shape.xcols = xcols;
+  memcpy(shape.ranges, ranges, sizeof shape.ranges);
+  std::shared_lock<std::shared_mutex> lm(m->mu);
+  if (check_dataset(m, &shape, nullptr)) return -1;
+  SlotLease lease;
+  ServeSlot* s = lease.s;
+  if (!s) return -1;
+  const int64_t pass = std::max<int64_t>(32, std::min<int64_t>(SERVE_PASS_ROWS, ((int64_t)64 << 20) / ((int64_t)xcols * 4) / 32 * 32));
+  StreamScope on_slot(s->stream);
+  for (int64_t o = 0; o < rows; o += pass) {
+    const int64_t N = std::min(pass, rows - o);
+    if (s->capX < (size_t)N * xcols) {
+      GOCTR_HIP(hipStreamSynchronize(s->stream));
+      if (s->X.alloc((size_t)std::min<int64_t>(pass, rows) * xcols, false)) return -1;
+      s->capX = (size_t)std::min<int64_t>(pass, rows) * xcols;
+    }
+    if (s->ensure_keys(N, m->cfg.T, m->cfg.U, m->cfg.C)) return -1;       // (for its pinned score staging and d_out)
+    if (s->ws.ensure((int)N, m->Ip, m->cfg.T, m->H1p, m->H2p, !chain_ok(m), s->stream)) return -1;
+    GOCTR_HIP(hipMemcpyAsync(s->X.p, X + (size_t)o * xcols, (size_t)N * xcols * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    if (serve_wait_weights(m, s)) return -1;
+    RowSource src{};
+    src.rows = N; src.id_mode = 0; src.X = s->X.p; src.xcols = xcols;
+    src.r_u = ranges[0]; src.r_ub = ranges[2]; src.r_v = ranges[4]; src.r_c = ranges[6];
+    FwdBufs fb = s->ws.bufs();
+    fb.yhat = reinterpret_cast<float*>(s->d_out.p);
+    StepOpts op;
+    op.train = false;
+    if (launch_forward(m, src, (int)N, op, s->st.p, &fb)) return -1;
+    GOCTR_HIP(hipMemcpyAsync(s->h_out, s->d_out.p, (size_t)N * 4, hipMemcpyDeviceToHost, s->stream));
+    GOCTR_HIP(hipStreamSynchronize(s->stream));
+    memcpy(y_out + o, s->h_out, (size_t)N * 4);
+  }
+  return 0;
+}
+
+}  // extern "C"

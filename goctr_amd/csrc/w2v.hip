@@ -873,9 +873,7 @@ void build_huffman(const int64_t* counts, int64_t V, int max_depth, std::vector<
 // vocabularies from 50 000 words on are built with the device (huffman.hip); below that the host builder is faster than the
 // copies.  GOCTR_HUFFMAN_DEVICE=0 / 1 forces either.
 bool huffman_on_device(int64_t V) {
-  const char* f = getenv("GOCTR_HUFFMAN_DEVICE");
-  if (f && *f) return *f != '0';
-  return V >= 50000;
+  return env_flag("GOCTR_HUFFMAN_DEVICE", V >= 50000);
 }
 
 }  // namespace
@@ -983,11 +981,6 @@ int exchange_deltas(goctr_w2v* w, bool avg) {
   return 0;
 }
 
-int env_int_w2v(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v && *v ? atoi(v) : dflt;
-}
-
 int run_pass(goctr_w2v* w, int64_t corpus_len, double* lr_io) {
   Engine& e = engine();
   GOCTR_CHECK(w->n_words > 0, "goctr_w2v: no doc uploaded");
@@ -1008,7 +1001,7 @@ int run_pass(goctr_w2v* w, int64_t corpus_len, double* lr_io) {
     const long long dflt = std::max<long long>(w->cfg.update_lr_batch, mat_bytes / 1024);
     const long long every = w->cfg.exchange_every == 0 ? dflt : w->cfg.exchange_every;
     if (every > 0) nseg = (int)std::min<long long>(4096, std::max<long long>(1, cdiv(cdiv(corpus_len, e.eff_world()), every)));
-    nseg = std::max(1, env_int_w2v("GOCTR_W2V_SEGMENTS", nseg));
+    nseg = std::max(1, env_int("GOCTR_W2V_SEGMENTS", nseg));
   }
   auto snapshot = [&]() -> int {
     const size_t np = (size_t)w->V * w->cfg.dim, na = (size_t)w->aux_rows * w->cfg.dim;
@@ -1076,7 +1069,7 @@ int run_pass(goctr_w2v* w, int64_t corpus_len, double* lr_io) {
     //   JB 3, 16 lanes x 1, WPS 8, PF 2                     375 M           3.08                       0.5684
     //   JB 4,  8 lanes x 2, WPS 4, PF 8, 384 hot rows       426 M           1.55                       0.5695
     //   JB 4,  8 lanes x 2, WPS 4, PF 8, 256 hot rows       412 M                                      0.5654   <- default
-    const int jb = sg_hs ? env_int_w2v("GOCTR_W2V_JB", dimr >= 16 ? 4 : 3) : 0;
+    const int jb = sg_hs ? env_int("GOCTR_W2V_JB", dimr >= 16 ? 4 : 3) : 0;
     const int cpl = jb > 0 && dimr >= 16 ? 2 : 1;
     const int wps = jb > 0 && cpl > 1 ? 4 : 8;
     const int pf = cpl > 1 ? 8 : 2;
@@ -1089,7 +1082,7 @@ int run_pass(goctr_w2v* w, int64_t corpus_len, double* lr_io) {
     // words/s, 5.8 KB/word memory-side, HS loss 0.5651 (oracle 0.557-0.560); 192 rows 231 M, loss 0.5686; 256 rows 232 M, 4.8 KB,
     // loss 0.5716 -- hot rows are AVERAGED over the workgroups (see above), so every row that joins the hot set learns more slowly:
     // the last quarter buys 0.6 % of speed for 0.5 % of loss, against a 3 % gate.
-    const int hot_knob = env_int_w2v("GOCTR_W2V_HOT", 1);
+    const int hot_knob = env_int("GOCTR_W2V_HOT", 1);
     const int hot_cap = HOT / dimr;
     const int rows_cached = hot_knob == 0 ? 0 : (hot_knob == 1 ? (jb > 0 && wps <= 4 ? hot_cap / 2 : hot_cap * 3 / 4) : std::min(hot_knob, hot_cap));
     HogHot hot{};
