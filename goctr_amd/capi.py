@@ -38,7 +38,8 @@ class MlpCfg(C.Structure):
                 ("alpha", C.c_double), ("lr_init", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
                 ("eps", C.c_double), ("momentum", C.c_double), ("nesterov", C.c_int), ("batch_normalize", C.c_int),
                 ("weight_decay", C.c_double), ("batch", C.c_int), ("max_iter", C.c_int),
-                ("n_iter_no_change", C.c_int), ("tol", C.c_double)]
+                ("n_iter_no_change", C.c_int), ("tol", C.c_double), ("out_activation", C.c_int), ("lr_schedule", C.c_int),
+                ("power_t", C.c_double)]
 
 
 class W2vCfg(C.Structure):
@@ -60,7 +61,7 @@ SYMBOLS = [
     "goctr_train_steps", "goctr_predict_dataset", "goctr_predict_steps", "goctr_prof_enable", "goctr_prof_reset",
     "goctr_prof_get", "goctr_prof_name", "goctr_prof_kernel", "goctr_mlp_cfg_default", "goctr_mlp_create", "goctr_mlp_destroy",
     "goctr_mlp_nparams", "goctr_mlp_set_params", "goctr_mlp_get_params", "goctr_mlp_loss_grad", "goctr_mlp_fit", "goctr_mlp_fit_resident",
-    "goctr_mlp_upload", "goctr_mlp_train_steps", "goctr_mlp_predict", "goctr_w2v_cfg_default", "goctr_w2v_create",
+    "goctr_mlp_upload", "goctr_mlp_train_steps", "goctr_mlp_predict", "goctr_mlp_predict64", "goctr_w2v_cfg_default", "goctr_w2v_create",
     "goctr_w2v_destroy", "goctr_w2v_set_param", "goctr_w2v_set_aux", "goctr_w2v_get_param", "goctr_w2v_get_aux",
     "goctr_w2v_get_paths", "goctr_huffman_build", "goctr_w2v_train", "goctr_w2v_upload_doc", "goctr_w2v_shard_cuts", "goctr_w2v_train_resident",
     "goctr_w2v_export_f32", "goctr_searcher_create", "goctr_searcher_destroy", "goctr_searcher_search",

@@ -30,6 +30,8 @@ struct MlpState {
   long long batch_idx;  // next batch (for train_steps)
   long long n_batches;
   unsigned int slot;
+  double lr;            // SGD's LearningRate / Adam's LearningRateInit: the learning-rate schedule (goctr_mlp_fit_resident) moves
+                        // it between epochs, and a captured step reads it at replay
 };
 
 __device__ __forceinline__ double act_fwd(int kind, double z) {
@@ -139,6 +141,53 @@ __global__ __launch_bounds__(256) void mlp_delta_last_kernel(const double* H, co
   lossterm[idx] = l;
 }
 
+// the same for the softmax and identity heads (mlp_delta_last_kernel stays the logistic head's): delta = h - y for both
+// (basemlp64.go:369-381), loss terms of log_loss  y != 0 ? -y log(clamp(h)) : 0  (:162-177) and square_loss  (h - y)^2 / 2
+// (:151-160; a power-of-two scale, so the reduce's sum / n equals the reference's sum / 2 / h.Rows)
+__global__ __launch_bounds__(256) void mlp_delta_head_kernel(const double* H, const double* Yb, int n, int no, int upL, int head,
+                                                             double* delta, double* lossterm, int valid) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= n * upL) return;
+  const int c = idx % upL;
+  if (idx / upL >= valid) {        // short last batch (Q11), as in mlp_delta_last_kernel
+    lossterm[idx] = 0;
+    return;
+  }
+  double d = 0, l = 0;
+  if (c < no) {
+    const double h = H[idx], y = Yb[idx];
+    d = h - y;
+    if (head == GOCTR_OUT_IDENTITY) {
+      l = d * d / 2;
+    } else if (y != 0) {
+      const double hmin = 4.9406564584124654e-324, hmax = 0.99999999999999989;  // Nextafter(0,1), Nextafter(1,0)
+      const double hc = h < hmin ? hmin : (h > hmax ? hmax : h);
+      l = -y * log(hc);
+    }
+  }
+  delta[idx] = d;
+  lossterm[idx] = l;
+}
+
+// softmax output head (Activations64["softmax"], basemlp64.go:104-116) over the identity epilogue's pre-activations: exp of each
+// column in column order into one running sum, then the divide.  No max subtraction: the reference has none.  One wavefront per
+// row; every lane adds the same exps in the same order (so all hold the same sum); the ones column and the pad stay as they are.
+__global__ __launch_bounds__(256) void mlp_softmax_kernel(double* H, int n, int ld, int no) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n) return;
+  double* h = H + (size_t)row * ld;
+  double sum = 0;
+  for (int c0 = 0; c0 < no; c0 += 64) {
+    const int c = c0 + lane;
+    const double e = c < no ? exp(h[c]) : 0.0;
+    if (c < no) h[c] = e;
+    const int cnt = no - c0 < 64 ? no - c0 : 64;
+    for (int k = 0; k < cnt; ++k) sum += __shfl(e, k, 64);
+  }
+  for (int c = lane; c < no; c += 64) h[c] /= sum;
+}
+
 // max-abs column scaling of a hidden activation block (basemlp64.go:277-299); one block per column
 __global__ __launch_bounds__(256) void mlp_bn_kernel(double* A, int n, int ld, int ncols, double* bn) {
   const int o = blockIdx.x;
@@ -192,7 +241,7 @@ struct MlpReduceArgs {
                               // the penalty by the batch's rows n; 0 = n
   // optimizer
   int solver; int do_update;
-  double lr_init, beta1, beta2, eps, momentum; int nesterov;
+  double beta1, beta2, eps, momentum; int nesterov;   // (the learning rate is MlpState::lr)
   double pow_skip1, pow_skip2;   // exponents beyond which beta^ex < 2^-55 (a factor 2 inside the bound that matters)
   double weight_decay;
   const MlpState* st;         // the step's frozen state (mlp_gather_kernel / mlp_copy_f64_kernel)
@@ -256,6 +305,7 @@ __global__ __launch_bounds__(256) void mlp_reduce_update_kernel(MlpReduceArgs a)
   asm volatile("" : "+v"(st_va));
   const MlpState* stv = reinterpret_cast<const MlpState*>(st_va);
   const long long st_t = stv->t;
+  const double st_lr = stv->lr;
   if ((int)blockIdx.x == a.nblk) {
     // loss = sum(terms)/n + 0.5*alpha*sum(W^2)/n (basemlp64.go:359-361) over the weights the forward pass used: their
     // squares were summed per block by the launch that wrote them (parity `par`); closes the step
@@ -302,6 +352,7 @@ __global__ __launch_bounds__(256) void mlp_reduce_update_kernel(MlpReduceArgs a)
         ns.slot = st_slot + 1;
         ns.t = st_t + 1;
         ns.n_batches = st_nb;
+        ns.lr = stv->lr;
         const long long nb = st_bi + 1;
         ns.batch_idx = nb >= st_nb ? 0 : nb;
         *a.st_master = ns;
@@ -423,12 +474,12 @@ __global__ __launch_bounds__(256) void mlp_reduce_update_kernel(MlpReduceArgs a)
           // beta^ex < 2^-54 makes (1 - beta^ex) round to exactly 1: the two pow calls (most of this thread's instructions)
           // are only made where they can change a bit -- after t * n passes a few tens of thousands, nowhere
           const double b1t = ex > a.pow_skip1 ? 0.0 : pow(a.beta1, ex), b2t = ex > a.pow_skip2 ? 0.0 : pow(a.beta2, ex);
-          const double lr = a.lr_init * sqrt(1 - b2t) / (1. - b1t);
+          const double lr = st_lr * sqrt(1 - b2t) / (1. - b1t);
           wn = w + (-lr * m / (sqrt(v) + a.eps));
         } else {
-          const double upd = a.momentum * vel_pre - a.lr_init * g;
+          const double upd = a.momentum * vel_pre - st_lr * g;
           a.Vel[idx] = upd;
-          wn = a.nesterov ? w + (a.momentum * upd - a.lr_init * g) : w + upd;
+          wn = a.nesterov ? w + (a.momentum * upd - st_lr * g) : w + upd;
         }
         a.W[idx] = wn;
         if (is_w) { d.WT[(size_t)c * d.upi + r] = wn; sq = wn * wn; }   // squares of the NEW weights: next step's penalty
@@ -1214,7 +1265,11 @@ struct goctr_mlp {
   // mlp_chain_kernel: the [F, H, 1] shape of the fused forward, plus what the cooperative slab sum of the output layer needs
   bool chain_ok() const { return fused_ok() && 256 % up[2] == 0 && woff[1] % up[2] == 0; }
   DevBuf<double> W0img, zpart;   // fused [F,H,1] forward: LDS image of the first weight block, per-group output partials
-  bool fused_ok() const { return nl == 2 && units[2] == 1 && !cfg.batch_normalize && up[1] <= 128 && up[0] <= 16 * 24; }
+  // (logistic head only: the softmax and identity heads run on the per-layer kernels)
+  bool fused_ok() const {
+    return nl == 2 && units[2] == 1 && cfg.out_activation == GOCTR_OUT_LOGISTIC && !cfg.batch_normalize && up[1] <= 128 &&
+           up[0] <= 16 * 24;
+  }
   // batch workspace
   int wsN = 0, S = 0;
   DevBuf<double> A[8], D[8], Yb, lossterm, slabs[7], sumsq_part, ring;
@@ -1231,6 +1286,9 @@ struct goctr_mlp {
   const void* step_graph_x = nullptr; const void* step_graph_y = nullptr; const void* step_graph_p = nullptr; const void* step_graph_w = nullptr; const void* step_graph_x64 = nullptr;
   const void* step_graph_ridx = nullptr;
   ~goctr_mlp() { if (step_graph) (void)hipGraphExecDestroy(step_graph); for (auto g : multi_graph) if (g) (void)hipGraphExecDestroy(g); }
+  // the optimizer's schedule state (reset with the optimizer by goctr_mlp_set_params): the learning rate the next epoch's
+  // steps read (MlpState::lr) and the samples seen, mlp.t of basemlp64.go:814
+  double lr_cur = 0; long long samples_seen = 0;
   std::mutex mu;
 };
 
@@ -1304,7 +1362,7 @@ int forward(goctr_mlp* p, int n, bool train, bool generic = false, int valid = -
   p->fused_fwd_done = false;
   for (int l = 0; l < p->nl; ++l) {
     const bool last = l == p->nl - 1;
-    const int kind = last ? GOCTR_ACT_LOGISTIC : p->cfg.activation;
+    const int kind = !last ? p->cfg.activation : (p->cfg.out_activation == GOCTR_OUT_LOGISTIC ? GOCTR_ACT_LOGISTIC : GOCTR_ACT_IDENTITY);
     EpiMlpAct e{p->A[l + 1].p, p->up[l + 1], p->units[l + 1], kind};
     const int m = l == 0 ? valid : n;           // activations[l].Rows
     if (launch_nn64(p->A[l].p, p->up[l], p->W.p + p->woff[l], p->up[l + 1], m, p->up[l], p->up[l + 1], e)) return -1;
@@ -1314,6 +1372,11 @@ int forward(goctr_mlp* p, int n, bool train, bool generic = false, int valid = -
                          p->W.p + p->woff[0] + (long long)p->units[0] * p->up[1], m, n);
       GOCTR_HIP(hipGetLastError());
     }
+  }
+  if (p->cfg.out_activation == GOCTR_OUT_SOFTMAX) {   // over all n rows, the stale ones of a short batch included (Q11)
+    hipLaunchKernelGGL(mlp_softmax_kernel, dim3((unsigned)cdiv(n, 4)), dim3(256), 0, engine().stream, p->A[p->nl].p, n,
+                       p->up[p->nl], p->units[p->nl]);
+    GOCTR_HIP(hipGetLastError());
   }
   if (train && p->cfg.batch_normalize) {
     for (int l = 0; l < p->nl - 1; ++l) {
@@ -1337,9 +1400,14 @@ int backward(goctr_mlp* p, int n, bool do_update, bool advance, int valid = -1) 
   const int upL = p->up[L], no = p->units[L];
   const bool chain = p->chain_done;
   p->chain_done = false;
-  if (!p->fused_fwd_done && !chain)
-  hipLaunchKernelGGL(mlp_delta_last_kernel, dim3((unsigned)cdiv((int64_t)n * upL, 256)), dim3(256), 0, e.stream,
-                     p->A[L].p, p->Yb.p, n, no, upL, p->D[L].p, p->lossterm.p, valid);
+  if (!p->fused_fwd_done && !chain) {
+    if (p->cfg.out_activation == GOCTR_OUT_LOGISTIC)
+      hipLaunchKernelGGL(mlp_delta_last_kernel, dim3((unsigned)cdiv((int64_t)n * upL, 256)), dim3(256), 0, e.stream,
+                         p->A[L].p, p->Yb.p, n, no, upL, p->D[L].p, p->lossterm.p, valid);
+    else
+      hipLaunchKernelGGL(mlp_delta_head_kernel, dim3((unsigned)cdiv((int64_t)n * upL, 256)), dim3(256), 0, e.stream,
+                         p->A[L].p, p->Yb.p, n, no, upL, p->cfg.out_activation, p->D[L].p, p->lossterm.p, valid);
+  }
   GOCTR_HIP(hipGetLastError());
   const bool fused_bwd = chain || (p->fused_fwd_done && up1_le128(p));
   if (fused_bwd && !chain) {
@@ -1370,7 +1438,7 @@ int backward(goctr_mlp* p, int n, bool do_update, bool advance, int valid = -1) 
   a.W = p->W.p; a.G = p->G.p; a.Mo = p->Mo.p; a.Vo = p->Vo.p; a.Vel = p->Vel.p;
   a.alpha = p->cfg.alpha; a.n = valid; a.solver = p->cfg.solver; a.do_update = do_update ? 1 : 0;
   if (valid < n) { a.n_bias = n; a.n_loss = n; }
-  a.lr_init = p->cfg.lr_init; a.beta1 = p->cfg.beta1; a.beta2 = p->cfg.beta2; a.eps = p->cfg.eps;
+  a.beta1 = p->cfg.beta1; a.beta2 = p->cfg.beta2; a.eps = p->cfg.eps;
   {
     auto skip = [](double beta) { return (beta > 0.0 && beta < 1.0) ? 55.0 * 0.6931471805599453 / -std::log(beta) : 1e300; };
     a.pow_skip1 = skip(a.beta1); a.pow_skip2 = skip(a.beta2);
@@ -1456,7 +1524,7 @@ int weight_decay(goctr_mlp* p) {
 }
 
 int set_mstate(goctr_mlp* p, long long t, long long b, long long nb, unsigned slot) {
-  MlpState s{t, b, nb, slot};
+  MlpState s{t, b, nb, slot, p->lr_cur};
   GOCTR_HIP(hipMemcpyAsync(p->st.p, &s, sizeof s, hipMemcpyHostToDevice, engine().stream));
   GOCTR_HIP(hipMemcpyAsync(p->st_step.p, &s, sizeof s, hipMemcpyHostToDevice, engine().stream));
   GOCTR_HIP(hipStreamSynchronize(engine().stream));
@@ -1551,6 +1619,7 @@ void goctr_mlp_cfg_default(goctr_mlp_cfg* c) {
   c->activation = GOCTR_ACT_RELU; c->solver = GOCTR_SOLVER_ADAM; c->alpha = 0.0001;
   c->lr_init = 0.001; c->beta1 = 0.9; c->beta2 = 0.999; c->eps = 1e-8; c->momentum = 0.9; c->nesterov = 1;
   c->batch_normalize = 0; c->weight_decay = 0; c->batch = 200; c->max_iter = 200; c->n_iter_no_change = 10; c->tol = 1e-4;
+  c->out_activation = GOCTR_OUT_LOGISTIC; c->lr_schedule = GOCTR_LR_CONSTANT; c->power_t = 0.5;
 }
 
 int goctr_mlp_create(const goctr_mlp_cfg* cfg, goctr_mlp** out) {
@@ -1560,6 +1629,10 @@ int goctr_mlp_create(const goctr_mlp_cfg* cfg, goctr_mlp** out) {
   GOCTR_CHECK(cfg->activation >= 0 && cfg->activation <= 3, "unknown activation %d", cfg->activation);
   GOCTR_CHECK(cfg->solver == GOCTR_SOLVER_SGD || cfg->solver == GOCTR_SOLVER_ADAM, "solver must be sgd or adam");
   GOCTR_CHECK(cfg->alpha >= 0 && cfg->lr_init > 0 && cfg->batch > 0, "bad hyper-parameters");
+  GOCTR_CHECK(cfg->out_activation >= GOCTR_OUT_LOGISTIC && cfg->out_activation <= GOCTR_OUT_IDENTITY, "unknown output head %d",
+              cfg->out_activation);
+  GOCTR_CHECK(cfg->lr_schedule >= GOCTR_LR_CONSTANT && cfg->lr_schedule <= GOCTR_LR_ADAPTIVE, "unknown learning-rate schedule %d",
+              cfg->lr_schedule);
   for (int i = 0; i < cfg->n_layers; ++i) GOCTR_CHECK(cfg->units[i] > 0, "layer %d has %d units", i, cfg->units[i]);
   if (init_attrs64()) return -1;
   std::unique_ptr<goctr_mlp> p(new goctr_mlp);
@@ -1573,6 +1646,7 @@ int goctr_mlp_create(const goctr_mlp_cfg* cfg, goctr_mlp** out) {
     po += (long long)(1 + p->units[l]) * p->units[l + 1];
   }
   p->nflat = wo; p->nparams = po;
+  p->lr_cur = cfg->lr_init;
   if (p->W.alloc(wo) || p->G.alloc(wo + 1) || p->Mo.alloc(wo) || p->Vo.alloc(wo) || p->Vel.alloc(wo)) return -1;
   for (int l = 0; l < p->nl; ++l) {
     if (p->WT[l].alloc((size_t)p->up[l] * p->up[l + 1])) return -1;
@@ -1623,6 +1697,7 @@ int goctr_mlp_set_params(goctr_mlp* p, const double* theta, size_t n) {
   GOCTR_HIP(hipMemsetAsync(p->Mo.p, 0, sizeof(double) * p->nflat, engine().stream));
   GOCTR_HIP(hipMemsetAsync(p->Vo.p, 0, sizeof(double) * p->nflat, engine().stream));
   GOCTR_HIP(hipMemsetAsync(p->Vel.p, 0, sizeof(double) * p->nflat, engine().stream));
+  p->lr_cur = p->cfg.lr_init; p->samples_seen = 0;
   return set_mstate(p, 0, 0, 1, 0);
 }
 
@@ -1781,6 +1856,8 @@ int goctr_mlp_fit_resident(goctr_mlp* p, const int32_t* perm, double* loss_curve
   GOCTR_CHECK(nb <= MLP_LOSS_RING, "too many batches per epoch for the loss ring");
   GOCTR_CHECK(!(tail && engine().comm_active()), "goctr_mlp_fit: a short last batch is not supported on a data-parallel "
               "communicator (rows %lld, batch %d)", (long long)rows, B);
+  GOCTR_CHECK(!(p->cfg.lr_schedule != GOCTR_LR_CONSTANT && engine().comm_active()), "goctr_mlp_fit: the invscaling and adaptive "
+              "learning-rate schedules are not supported on a data-parallel communicator");
   if (perm && p->perm.alloc((size_t)rows, false)) return -1;
   MlpState s;
   if (get_mstate(p, &s)) return -1;
@@ -1804,23 +1881,45 @@ int goctr_mlp_fit_resident(goctr_mlp* p, const int32_t* perm, double* loss_curve
     if (loss_curve) loss_curve[it] = loss;
     if (loss > best - p->cfg.tol) no_improve++; else no_improve = 0;  // updateNoImprovementCount :859-895
     if (loss < best) best = loss;
-    if (no_improve > p->cfg.n_iter_no_change) { it++; break; }        // constant lr schedule: stop (:826-835)
+    p->samples_seen += rows;                                           // mlp.t += nSamples (:814)
+    const bool sgd = p->cfg.solver == GOCTR_SOLVER_SGD;
+    if (sgd && p->cfg.lr_schedule == GOCTR_LR_INVSCALING)             // SGDOptimizer64.iterationEnds (:999-1003)
+      p->lr_cur = p->cfg.lr_init / std::pow((double)p->samples_seen + 1, p->cfg.power_t);
+    if (no_improve > p->cfg.n_iter_no_change) {                       // triggerStopping (:826-835, :1004-1022, :1054-1070)
+      if (p->cfg.lr_schedule != GOCTR_LR_ADAPTIVE) { it++; break; }
+      double lr_now = p->lr_cur;                                       // SGD: LearningRate
+      if (!sgd) {
+        // Adam: LearningRate is the effective rate of the last parameter the last step updated -- exponent t * nparams of the
+        // per-parameter beta powers (quirk Q7), t = the steps taken, read back from the device state
+        MlpState cur;
+        if (get_mstate(p, &cur)) return -1;
+        const double ex = (double)cur.t * (double)p->nparams;
+        auto bpow = [ex](double beta) {       // the reduce launch's cut-off: beyond it beta^ex < 2^-55 counts as 0
+          const double skip = (beta > 0.0 && beta < 1.0) ? 55.0 * 0.6931471805599453 / -std::log(beta) : 1e300;
+          return ex > skip ? 0.0 : std::pow(beta, ex);
+        };
+        lr_now = p->lr_cur * std::sqrt(1 - bpow(p->cfg.beta2)) / (1. - bpow(p->cfg.beta1));
+      }
+      if (lr_now <= 1e-6) { it++; break; }
+      p->lr_cur *= 0.8;                                                 // SGD: LearningRate, Adam: LearningRateInit
+      no_improve = 0;
+    }
   }
   if (iters_run) *iters_run = it;
   p->perm.release();
   return 0;
 }
 
-int goctr_mlp_predict(goctr_mlp* p, const float* X, int64_t rows, float* y_out) {
-  GOCTR_ENTER_H(p);
-  GOCTR_CHECK(p && X && y_out && rows >= 0, "goctr_mlp_predict: bad arguments");
-  if (rows == 0) return 0;
-  std::lock_guard<std::mutex> lk(p->mu);
+}  // extern "C"
+
+// forwardPass over float32 rows in chunks; the head's values leave narrowed to float32 (y32) or as they are (y64)
+static int predict_rows(goctr_mlp* p, const float* X, int64_t rows, float* y32, double* y64) {
   const int L = p->nl, F = p->units[0], no = p->units[L];
   const int CHUNK = 16384;
   if (ensure_ws(p, (int)std::min<int64_t>(rows, CHUNK))) return -1;
   DevBuf<float> dX, dy;
-  if (dX.alloc((size_t)std::min<int64_t>(rows, CHUNK) * F, false) || dy.alloc((size_t)std::min<int64_t>(rows, CHUNK) * no, false)) return -1;
+  if (dX.alloc((size_t)std::min<int64_t>(rows, CHUNK) * F, false)) return -1;
+  if (y32 && dy.alloc((size_t)std::min<int64_t>(rows, CHUNK) * no, false)) return -1;
   for (int64_t s0 = 0; s0 < rows; s0 += CHUNK) {
     const int n = (int)std::min<int64_t>(CHUNK, rows - s0);
     if (dX.upload(X + s0 * F, (size_t)n * F)) return -1;
@@ -1829,12 +1928,36 @@ int goctr_mlp_predict(goctr_mlp* p, const float* X, int64_t rows, float* y_out) 
                        (MlpState*)nullptr, n);
     GOCTR_HIP(hipGetLastError());
     if (forward(p, n, false)) return -1;
-    hipLaunchKernelGGL(mlp_narrow_kernel, dim3((unsigned)cdiv((int64_t)n * no, 256)), dim3(256), 0, engine().stream,
-                       p->A[L].p, n, p->up[L], no, dy.p);
-    GOCTR_HIP(hipGetLastError());
-    if (dy.download(y_out + s0 * no, (size_t)n * no)) return -1;
+    if (y32) {
+      hipLaunchKernelGGL(mlp_narrow_kernel, dim3((unsigned)cdiv((int64_t)n * no, 256)), dim3(256), 0, engine().stream,
+                         p->A[L].p, n, p->up[L], no, dy.p);
+      GOCTR_HIP(hipGetLastError());
+      if (dy.download(y32 + s0 * no, (size_t)n * no)) return -1;
+    } else {
+      GOCTR_HIP(hipMemcpy2DAsync(y64 + s0 * no, sizeof(double) * no, p->A[L].p, sizeof(double) * p->up[L], sizeof(double) * no, n,
+                                 hipMemcpyDeviceToHost, engine().stream));
+      GOCTR_HIP(hipStreamSynchronize(engine().stream));
+    }
   }
   return 0;
+}
+
+extern "C" {
+
+int goctr_mlp_predict(goctr_mlp* p, const float* X, int64_t rows, float* y_out) {
+  GOCTR_ENTER_H(p);
+  GOCTR_CHECK(p && X && y_out && rows >= 0, "goctr_mlp_predict: bad arguments");
+  if (rows == 0) return 0;
+  std::lock_guard<std::mutex> lk(p->mu);
+  return predict_rows(p, X, rows, y_out, nullptr);
+}
+
+int goctr_mlp_predict64(goctr_mlp* p, const float* X, int64_t rows, double* y_out) {
+  GOCTR_ENTER_H(p);
+  GOCTR_CHECK(p && X && y_out && rows >= 0, "goctr_mlp_predict64: bad arguments");
+  if (rows == 0) return 0;
+  std::lock_guard<std::mutex> lk(p->mu);
+  return predict_rows(p, X, rows, nullptr, y_out);
 }
 
 }  // extern "C"

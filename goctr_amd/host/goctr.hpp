@@ -7,6 +7,7 @@
 // buffers only: every number comes out of libgoctr_hip.so.  Errors surface as std::runtime_error carrying
 // goctr_last_error() (the Go adapters log.Fatalf / return error at the same places).
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdint>
@@ -261,6 +262,74 @@ class MLPClassifier {
 
  private:
   goctr_mlp* h_ = nullptr;
+};
+
+// nn.MLPRegressor (multilayer_perceptron.go:9-58): identity head + square_loss, float64 predictions, Score = r2Score64
+class MLPRegressor {
+ public:
+  std::vector<int> HiddenLayerSizes{100};
+  int Activation = GOCTR_ACT_RELU, Solver = GOCTR_SOLVER_ADAM, LearningRate = GOCTR_LR_CONSTANT;
+  double Alpha = 1e-4, LearningRateInit = 1e-3, PowerT = 0.5;
+  int BatchSize = 200, MaxIter = 200;
+  uint64_t RandomState = 1;
+  std::vector<double> LossCurve;
+  ~MLPRegressor() { goctr_mlp_destroy(h_); }
+  void Fit(const float* X, const float* Y, int64_t rows, int xcols, int ycols = 1) {
+    ensure_init();
+    goctr_mlp_cfg cfg;
+    goctr_mlp_cfg_default(&cfg);
+    std::vector<int> units{xcols};
+    units.insert(units.end(), HiddenLayerSizes.begin(), HiddenLayerSizes.end());
+    units.push_back(ycols);
+    cfg.n_layers = (int)units.size();
+    for (size_t i = 0; i < units.size(); ++i) cfg.units[i] = units[i];
+    cfg.activation = Activation; cfg.solver = Solver; cfg.alpha = Alpha; cfg.lr_init = LearningRateInit;
+    cfg.out_activation = GOCTR_OUT_IDENTITY; cfg.lr_schedule = LearningRate; cfg.power_t = PowerT;
+    const int batch = (int)std::min<int64_t>(BatchSize, rows);   // basemlp64.go:516-527
+    cfg.batch = batch; cfg.max_iter = MaxIter;
+    goctr_mlp_destroy(h_);
+    h_ = nullptr;
+    check(goctr_mlp_create(&cfg, &h_));
+    std::mt19937_64 g(RandomState);
+    std::uniform_real_distribution<double> ud(0.0, 1.0);
+    std::vector<double> theta;
+    for (size_t i = 0; i + 1 < units.size(); ++i) {
+      const double bound = std::sqrt((Activation == GOCTR_ACT_LOGISTIC ? 2.0 : 6.0) / (units[i] + units[i + 1]));
+      for (int k = 0; k < (1 + units[i]) * units[i + 1]; ++k) theta.push_back(ud(g) * bound);
+    }
+    check(goctr_mlp_set_params(h_, theta.data(), theta.size()));
+    LossCurve.assign((size_t)MaxIter, 0.0);
+    int iters = 0;
+    check(goctr_mlp_fit(h_, X, Y, rows, nullptr, LossCurve.data(), &iters));
+    LossCurve.resize((size_t)iters);
+    ycols_ = ycols;
+  }
+  std::vector<double> Predict(const float* X, int64_t rows) {
+    std::vector<double> y((size_t)rows * ycols_);
+    check(goctr_mlp_predict64(h_, X, rows, y.data()));
+    return y;
+  }
+  // r2Score64 (basemlp64.go:1116-1141): mean over the output columns of 1 - SSres / SStot
+  double Score(const float* X, const float* Y, int64_t rows) {
+    const std::vector<double> h = Predict(X, rows);
+    double acc = 0;
+    for (int c = 0; c < ycols_; ++c) {
+      double avg = 0, num = 0, den = 0;
+      for (int64_t r = 0; r < rows; ++r) avg += Y[r * ycols_ + c];
+      avg /= (double)rows;
+      for (int64_t r = 0; r < rows; ++r) {
+        const double t = h[r * ycols_ + c] - Y[r * ycols_ + c], u = Y[r * ycols_ + c] - avg;
+        num += t * t; den += u * u;
+      }
+      if (den == 0) throw std::runtime_error("r2Score64: constant target column");
+      acc += 1 - num / den;
+    }
+    return acc / ycols_;
+  }
+
+ private:
+  goctr_mlp* h_ = nullptr;
+  int ycols_ = 1;
 };
 }  // namespace mlp
 

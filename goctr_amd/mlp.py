@@ -1,11 +1,11 @@
 """Host mirror of the sklearn-port MLP used by go-ctr's "simple 2-layer MLP" path.
 
-Reference: nn/neural_network/multilayer_perceptron.go:74-125 (MLPClassifier, NewMLPClassifier, Fit,
-Predict), nn/neural_network/basemlp64.go (hyper-parameters :25-51, defaults :228-254, init :408-482,
-validateHyperparameters :625-673) and the adapters model/mlp/mlp.go:15-65 (SimpleMlpFitWrap /
-SimpleMlpPredWrap).  Arithmetic is float64 on the device (include/goctr.h, goctr_mlp_*); this file keeps
-the reference's names, defaults and error behaviour and owns what is host-side in the reference too:
-the init RNG (Q8: one-sided U[0,bound)) and the per-epoch shuffle.
+Reference: nn/neural_network/multilayer_perceptron.go:9-134 (MLPRegressor, MLPClassifier, their constructors, Fit,
+Predict, Score), nn/neural_network/basemlp64.go (hyper-parameters :25-51, defaults :228-254, init :408-482, Fit :578-599,
+validateHyperparameters :625-673, scores :1116-1155, LabelBinarizer64 :1283-1375) and the adapters model/mlp/mlp.go:15-65
+(SimpleMlpFitWrap / SimpleMlpPredWrap).  Arithmetic is float64 on the device (include/goctr.h, goctr_mlp_*); this file
+keeps the reference's names, defaults and error behaviour and owns what is host-side in the reference too: the init RNG
+(Q8: one-sided U[0,bound)), the per-epoch shuffle, the label binarizer and the two score rules.
 """
 from __future__ import annotations
 
@@ -19,18 +19,94 @@ from .recommend import Fitter, PredictAbstract, TrainSample
 
 _ACT = {"identity": 0, "logistic": 1, "tanh": 2, "relu": 3}
 _SOLVER = {"sgd": 0, "adam": 1}
+_OUT = {"logistic": 0, "softmax": 1, "identity": 2}                 # include/goctr.h GOCTR_OUT_*
+_LR = {"constant": 0, "invscaling": 1, "adaptive": 2}               # include/goctr.h GOCTR_LR_*
 
 
-class MLPClassifier:
-    """nn.MLPClassifier (multilayer_perceptron.go:74-90) with BaseMultilayerPerceptron64's exported fields."""
+class LabelBinarizer64:
+    """LabelBinarizer64 (basemlp64.go:1283-1375) with NegLabel 0, PosLabel 1, as BaseMultilayerPerceptron64.Fit builds it:
+    each column's distinct values sorted ascending, one-hot over them (so one column holding two labels becomes two)."""
+
+    def __init__(self, NegLabel=0.0, PosLabel=1.0):
+        self.NegLabel, self.PosLabel = NegLabel, PosLabel
+        self.Classes = []
+
+    def Fit(self, Y):
+        Y = np.asarray(Y, np.float64).reshape(len(Y), -1)
+        self.Classes = [np.unique(Y[:, j]) for j in range(Y.shape[1])]
+        return self
+
+    def Transform(self, Y):
+        Y = np.asarray(Y, np.float64).reshape(len(Y), -1)
+        out = np.full((Y.shape[0], sum(len(c) for c in self.Classes)), self.NegLabel, np.float64)
+        base = 0
+        for j, cls in enumerate(self.Classes):
+            k = np.searchsorted(cls, Y[:, j])
+            hit = (k < len(cls)) & (cls[np.minimum(k, len(cls) - 1)] == Y[:, j])
+            out[np.nonzero(hit)[0], base + k[hit]] = self.PosLabel
+            base += len(cls)
+        return out
+
+    def FitTransform(self, Y):
+        return self.Fit(Y).Transform(Y)
+
+    def InverseTransform(self, Yb):
+        """per original column: the class at MaxIdx64 (the first maximum) of its block of columns"""
+        Yb = np.asarray(Yb, np.float64)
+        out = np.empty((Yb.shape[0], len(self.Classes)), np.float64)
+        base = 0
+        for j, cls in enumerate(self.Classes):
+            out[:, j] = cls[np.argmax(Yb[:, base:base + len(cls)], axis=1)]
+            base += len(cls)
+        return out
+
+
+def r2Score64(yTrue, yPred):
+    """r2Score64 (basemlp64.go:1116-1141): mean over the columns of 1 - sum (pred - true)^2 / sum (true - mean)^2"""
+    yTrue = np.asarray(yTrue, np.float64).reshape(len(yTrue), -1)
+    yPred = np.asarray(yPred, np.float64).reshape(yTrue.shape)
+    acc = 0.0
+    for c in range(yTrue.shape[1]):
+        t = yTrue[:, c]
+        avg = 0.0
+        for v in t:                       # the reference's running sums, in row order
+            avg += v
+        avg /= len(t)
+        num = den = 0.0
+        for a, b in zip(yPred[:, c], t):
+            num += (a - b) * (a - b)
+            den += (b - avg) * (b - avg)
+        if den == 0:
+            raise ValueError("yDen=0")
+        acc += 1 - num / den
+    return acc / yTrue.shape[1]
+
+
+def AccuracyScore64(Y, H):
+    """AccuracyScore64 (basemlp64.go:1143-1155): the share of rows whose every column is EXACTLY equal"""
+    Y = np.asarray(Y, np.float64).reshape(len(Y), -1)
+    H = np.asarray(H, np.float64).reshape(Y.shape)
+    return float(np.count_nonzero(np.all(H == Y, axis=1))) / Y.shape[0]
+
+
+class _BaseMLP:
+    """BaseMultilayerPerceptron64's exported fields and what Fit / Predict share on the device.
+
+    Not supported, and refused with ValueError by Fit: Solver "lbfgs" (no device path); WarmStart (every Fit starts from a fresh
+    initialisation and a fresh optimizer); EarlyStopping -- read literally, the reference scores a classifier's validation rows
+    by exact equality between probabilities and 0/1 labels and, with BestValidationScore starting at 0, can end by copying
+    never-written zero parameters back (basemlp64.go:852, :879-881, :933-942); whether to reproduce that is a separate decision."""
+
+    OutActivation = "logistic"
 
     def __init__(self, hiddenLayerSizes, activation="relu", solver="adam", Alpha=1e-4):
         # NewBaseMultilayerPerceptron64 defaults (basemlp64.go:228-254)
         self.HiddenLayerSizes = list(hiddenLayerSizes)
         self.Activation, self.Solver, self.Alpha = activation, solver, Alpha
         self.BatchSize = 200
-        self.LearningRate = "constant"
+        self.LearningRate = "constant"      # "invscaling" (SGD only, like the reference) | "adaptive"
         self.LearningRateInit = 0.001
+        self.PowerT = 0.5
         self.MaxIter = 200
         self.Shuffle = True
         self.RandomState = None          # numpy Generator; None => time-seeded like basemlp64.go:446-448
@@ -41,6 +117,9 @@ class MLPClassifier:
         self.NIterNoChange = 10
         self.BatchNormalize = False
         self.WeightDecay = 0.0
+        self.WarmStart = False
+        self.EarlyStopping = False
+        self.ValidationFraction = 0.1
         # fitted state
         self.LossCurve = []
         self.NIter = 0
@@ -57,8 +136,12 @@ class MLPClassifier:
             raise ValueError("invalid hyper-parameters")
         if any(s <= 0 for s in self.HiddenLayerSizes):
             raise ValueError(f"hiddenLayerSizes must be > 0, got {self.HiddenLayerSizes}.")
-        if self.LearningRate != "constant":
-            raise ValueError("only the constant learning-rate schedule has a device path")
+        if self.LearningRate not in _LR:
+            raise ValueError(f"learning rate {self.LearningRate} is not supported.")
+        if self.EarlyStopping:
+            raise ValueError("EarlyStopping is not supported (see the class docstring)")
+        if self.WarmStart:
+            raise ValueError("WarmStart is not supported: every Fit starts from a fresh initialisation")
 
     def _cfg(self, units, batch):
         c = capi.MlpCfg()
@@ -71,6 +154,7 @@ class MLPClassifier:
         c.momentum, c.nesterov = self.Momentum, int(self.NesterovsMomentum)
         c.batch_normalize, c.weight_decay = int(self.BatchNormalize), self.WeightDecay
         c.batch, c.max_iter, c.n_iter_no_change, c.tol = batch, self.MaxIter, self.NIterNoChange, self.Tol
+        c.out_activation, c.lr_schedule, c.power_t = _OUT[self.OutActivation], _LR[self.LearningRate], self.PowerT
         return c
 
     def init_params(self, units, rng):
@@ -111,9 +195,9 @@ class MLPClassifier:
                                                    C.c_int(X.shape[0]), C.byref(loss), capi.ptr(g, C.c_double)))
         return loss.value, g
 
-    def Fit(self, X, Y, theta0=None, perm=None):
-        """Base64.Fit (basemlp64.go:578-599) -> fit :484 -> fitStochastic :729.  X float32 rows (the adapter
-        widens them, mlp.go:46-53), Y in {0,1}.  Every row is trained: a sample count that is not a multiple of the batch
+    def _fit(self, X, Y, theta0=None, perm=None):
+        """fit :484 -> fitStochastic :729 on the device with self.OutActivation's head.  X float32 rows (the adapter
+        widens them, mlp.go:46-53).  Every row is trained: a sample count that is not a multiple of the batch
         ends each epoch with one short batch, computed the reference's way (quirk Q11, basemlp64.go:790-812 -- its hidden
         block and output deltas keep the previous batch's rows beyond the short batch; csrc/mlp.hip goctr_mlp_fit)."""
         self._validate()
@@ -157,8 +241,15 @@ class MLPClassifier:
         capi.check(capi.load().goctr_mlp_fit_resident(self._h, capi.ptr(pp, C.c_int32), capi.ptr(curve, C.c_double), C.byref(ran)))
         return self._fitted(curve, ran.value)
 
-    def Predict(self, X):
-        """predictProbas (basemlp64.go:897) for a binary classifier: probabilities, float32 like mlp.go:33-38"""
+    def _predict64(self, X):
+        """predictProbas (basemlp64.go:897-913) in float64: the head's values"""
+        X = capi.f32(X)
+        y = np.empty((X.shape[0], self._units[-1]), np.float64)
+        capi.check(capi.load().goctr_mlp_predict64(self._h, capi.ptr(X, C.c_float), C.c_int64(X.shape[0]),
+                                                   capi.ptr(y, C.c_double)))
+        return y
+
+    def _predict32(self, X):
         X = capi.f32(X)
         no = self._units[-1]
         y = np.empty((X.shape[0], no), np.float32)
@@ -185,6 +276,68 @@ class MLPClassifier:
             self.close()
         except Exception:
             pass
+
+
+class MLPClassifier(_BaseMLP):
+    """nn.MLPClassifier (multilayer_perceptron.go:74-134) with BaseMultilayerPerceptron64's exported fields.
+
+    The output head follows the reference's Fit (basemlp64.go:578-599, :503-511, initialize :416-429): targets that are all
+    0 / 1 are trained as they are -- one column: logistic + binary_log_loss; more than one column: softmax + log_loss, since
+    the reference's rule is isMulticlass = y.Cols > 1 (so 0 / 1 one-hot or multi-label targets select softmax too).  Any
+    other target values are label-binarized first (LabelBinarizer64) and Predict maps the softmax (or logistic) outputs back
+    to class labels by arg-max."""
+
+    def __init__(self, hiddenLayerSizes, activation="relu", solver="adam", Alpha=1e-4):
+        super().__init__(hiddenLayerSizes, activation, solver, Alpha)
+        self.lb = None
+
+    def Fit(self, X, Y, theta0=None, perm=None):
+        """Base64.Fit (basemlp64.go:578-599) -> fit :484 -> fitStochastic :729 (theta0 / perm: a given initialisation and
+        row order per epoch, [MaxIter][rows] int32)"""
+        Y = np.asarray(Y, np.float32).reshape(np.asarray(X).shape[0], -1)
+        self.lb = None
+        if not np.all((Y == 0) | (Y == 1)):
+            self.lb = LabelBinarizer64(0, 1)
+            Y = self.lb.FitTransform(Y).astype(np.float32)
+        self.OutActivation = "softmax" if Y.shape[1] > 1 else "logistic"
+        return self._fit(X, Y, theta0, perm)
+
+    def Predict(self, X):
+        """predict (basemlp64.go:915-929): class labels (float64, one column per original target column) when Fit
+        label-binarized the targets, else predictProbas' probabilities, float32 like mlp.go:33-38"""
+        if self.lb is not None:
+            return self.lb.InverseTransform(self._predict64(X))
+        return self._predict32(X)
+
+    def Score(self, X, Y):
+        """MLPClassifier.Score (multilayer_perceptron.go:126-134): AccuracyScore64 of Predict against Y.  Quirk kept: for 0 / 1
+        targets Predict returns probabilities, never thresholded, so a row only counts when its probabilities equal its
+        labels exactly (the reference compares the same way)."""
+        Y = np.asarray(Y, np.float64).reshape(np.asarray(X).shape[0], -1)
+        H = self.lb.InverseTransform(self._predict64(X)) if self.lb is not None else self._predict64(X)
+        return AccuracyScore64(Y, H)
+
+
+class MLPRegressor(_BaseMLP):
+    """nn.MLPRegressor (multilayer_perceptron.go:9-71): identity output + square_loss, float64 predictions, Score = r2Score64.
+    (The reference's fit picks the head from the target values, basemlp64.go:503-511, so a regressor handed only 0 / 1
+    targets would train a logistic head; this one always trains the identity head MLPRegressor stands for.)"""
+
+    OutActivation = "identity"
+
+    def Fit(self, X, Y, theta0=None, perm=None):
+        return self._fit(X, Y, theta0, perm)
+
+    def Predict(self, X):
+        return self._predict64(X)
+
+    def Score(self, X, Y):
+        return r2Score64(np.asarray(Y, np.float64).reshape(np.asarray(X).shape[0], -1), self.Predict(X))
+
+
+def NewMLPRegressor(hiddenLayerSizes, activation, solver, Alpha):
+    """multilayer_perceptron.go:19-28"""
+    return MLPRegressor(hiddenLayerSizes, activation, solver, Alpha)
 
 
 def NewMLPClassifier(hiddenLayerSizes, activation, solver, Alpha):

@@ -286,10 +286,15 @@ const char* goctr_prof_name(int kernel_id);
 const char* goctr_prof_kernel(int kernel_id);
 
 /* ---------------------------------------------------------------- sklearn-port MLP (f64) --- */
-/* replaces nn.NewMLPClassifier + Fit + Predict (nn/neural_network/multilayer_perceptron.go:81-125,
+/* replaces nn.NewMLPClassifier / NewMLPRegressor + Fit + Predict (nn/neural_network/multilayer_perceptron.go:9-125,
  * basemlp64.go) behind mlp.SimpleMlpFitWrap / SimpleMlpPredWrap (model/mlp/mlp.go:15-65). */
 enum { GOCTR_ACT_IDENTITY = 0, GOCTR_ACT_LOGISTIC = 1, GOCTR_ACT_TANH = 2, GOCTR_ACT_RELU = 3 };
 enum { GOCTR_SOLVER_SGD = 0, GOCTR_SOLVER_ADAM = 1 };
+/* output head (initialize, basemlp64.go:416-429): logistic + binary_log_loss (binary / multi-label classifier), softmax +
+ * log_loss (y.Cols > 1 after label binarizing, :503-511), identity + square_loss (MLPRegressor) */
+enum { GOCTR_OUT_LOGISTIC = 0, GOCTR_OUT_SOFTMAX = 1, GOCTR_OUT_IDENTITY = 2 };
+/* LearningRate (SGDOptimizer64.iterationEnds / triggerStopping, AdamOptimizer64.triggerStopping: basemlp64.go:999-1070) */
+enum { GOCTR_LR_CONSTANT = 0, GOCTR_LR_INVSCALING = 1, GOCTR_LR_ADAPTIVE = 2 };
 typedef struct {
   int n_layers;          /* len(layerUnits): input, hidden..., output */
   int units[8];
@@ -302,6 +307,14 @@ typedef struct {
   double weight_decay;   /* basemlp64.go:342-346 */
   int batch, max_iter, n_iter_no_change;
   double tol;
+  int out_activation;    /* GOCTR_OUT_*: OutActivation + LossFuncName (basemlp64.go:416-429); default logistic */
+  int lr_schedule;       /* GOCTR_LR_*, once per epoch in goctr_mlp_fit / _fit_resident (basemlp64.go:814-835); default
+                          * constant.  invscaling: SGD's rate = lr_init / (t + 1)^power_t, t = samples seen (:999-1003; Adam
+                          * ignores it).  adaptive: after n_iter_no_change epochs without improvement, stop when the rate is
+                          * <= 1e-6, else scale it by 0.8 (SGD: the rate, :1004-1022; Adam: lr_init, tested against its
+                          * last effective rate lr_init sqrt(1 - beta2^t) / (1 - beta1^t), :1054-1070).  Not on a
+                          * data-parallel communicator. */
+  double power_t;        /* PowerT (basemlp64.go:236); default 0.5 */
 } goctr_mlp_cfg;
 void goctr_mlp_cfg_default(goctr_mlp_cfg* c); /* NewBaseMultilayerPerceptron64 (basemlp64.go:228-254) */
 int goctr_mlp_create(const goctr_mlp_cfg* cfg, goctr_mlp** out);
@@ -329,8 +342,12 @@ int goctr_mlp_fit_resident(goctr_mlp* p, const int32_t* perm, double* loss_curve
  * float64 operand image of the weight-gradient GEMM (rows x round_up(F + 1, 16) x 8 B; skipped above 64 GiB or with GOCTR_MLP_X64=0) */
 int goctr_mlp_upload(goctr_mlp* p, const float* X, const float* Y, int64_t rows);
 int goctr_mlp_train_steps(goctr_mlp* p, int64_t first_batch, int n_steps);
-/* SimpleMlpPredWrap.Predict (mlp.go:15-39): f32 in, probabilities f32 out */
+/* SimpleMlpPredWrap.Predict (mlp.go:15-39): f32 in, the output head's values f32 out (probabilities for the logistic and
+ * softmax heads, raw values for the identity head) */
 int goctr_mlp_predict(goctr_mlp* p, const float* X, int64_t rows, float* y_out);
+/* predictProbas (basemlp64.go:897-913) without the narrowing: y_out [rows][units[last]] float64, what MLPRegressor.Predict
+ * and both Score rules (r2Score64 :1116-1141, AccuracyScore64 :1143-1155; computed by the host) read */
+int goctr_mlp_predict64(goctr_mlp* p, const float* X, int64_t rows, double* y_out);
 
 /* ---------------------------------------------------------------- item2vec (f64) ----------- */
 /* replaces embedding.TrainEmbedding (feature/embedding/wordemb.go:9-32) -> word2vec.Train
