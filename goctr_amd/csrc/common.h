@@ -269,6 +269,14 @@ inline int capture_graph(hipStream_t s, hipGraphExec_t* exec, Body body, Restore
   }
 }
 
+// dynamic LDS above 64 KiB needs an explicit opt-in per kernel
+template <class K>
+int allow_big_lds(K kernel) {
+  GOCTR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)(160 * 1024)));
+  return 0;
+}
+
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

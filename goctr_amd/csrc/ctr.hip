@@ -170,14 +170,6 @@ RowSource make_source(const goctr_dataset* d, const goctr_emb* e) {
 }
 namespace {
 
-// dynamic LDS above 64 KiB needs an explicit opt-in per kernel
-template <class K>
-int allow_big_lds(K kernel) {
-  GOCTR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(160 * 1024)));
-  return 0;
-}
-
 int serve16_attributes() {
 #define GOCTR_S16(L, H) (allow_big_lds(ctr_serve16_kernel<L, 1, H>) || allow_big_lds(ctr_serve16_kernel<L, 2, H>) || allow_big_lds(ctr_serve16_kernel<L, 3, H>))
   return (GOCTR_S16(2, 10) || GOCTR_S16(2, 15) || GOCTR_S16(4, 10) || GOCTR_S16(4, 15) || GOCTR_S16(16, 10) || GOCTR_S16(16, 15)) ? -1 : 0;

@@ -1,0 +1,255 @@
+// mlp_api.hip -- the float64 MLP's C ABI (mlp_model.h names the other MLP files): argument checks, locking, the parameter
+// layout and fitStochastic's epoch loop; the step functions of mlp.hip do the device work.
+#include <cmath>
+#include <memory>
+#include <vector>
+
+#include "mlp_model.h"
+
+// a padded flat parameter buffer (W or G) in the packed [ b_i | W_i ]... order of goctr_mlp_set_params
+static int unpack(goctr_mlp* p, const DevBuf<double>& src, double* theta) {
+  std::vector<double> w((size_t)p->nflat);
+  if (src.download(w.data(), w.size())) return -1;
+  for (int l = 0; l < p->nl; ++l) {
+    const int fi = p->units[l], fo = p->units[l + 1], upo = p->up[l + 1];
+    double* b = theta + p->poff[l];
+    double* W = b + fo;
+    for (int c = 0; c < fo; ++c) b[c] = w[(size_t)p->woff[l] + (size_t)fi * upo + c];
+    for (int r = 0; r < fi; ++r)
+      for (int c = 0; c < fo; ++c) W[(size_t)r * fo + c] = w[(size_t)p->woff[l] + (size_t)r * upo + c];
+  }
+  return 0;
+}
+
+extern "C" {
+
+void goctr_mlp_cfg_default(goctr_mlp_cfg* c) {
+  memset(c, 0, sizeof *c);  // NewBaseMultilayerPerceptron64 (basemlp64.go:228-254)
+  c->n_layers = 3; c->units[0] = 0; c->units[1] = 100; c->units[2] = 1;
+  c->activation = GOCTR_ACT_RELU; c->solver = GOCTR_SOLVER_ADAM; c->alpha = 0.0001;
+  c->lr_init = 0.001; c->beta1 = 0.9; c->beta2 = 0.999; c->eps = 1e-8; c->momentum = 0.9; c->nesterov = 1;
+  c->batch_normalize = 0; c->weight_decay = 0; c->batch = 200; c->max_iter = 200; c->n_iter_no_change = 10; c->tol = 1e-4;
+  c->out_activation = GOCTR_OUT_LOGISTIC; c->lr_schedule = GOCTR_LR_CONSTANT; c->power_t = 0.5;
+}
+
+int goctr_mlp_create(const goctr_mlp_cfg* cfg, goctr_mlp** out) {
+  GOCTR_ENTER();
+  GOCTR_CHECK(cfg && out && cfg->n_layers >= 2 && cfg->n_layers <= 8, "goctr_mlp_create: n_layers must be 2..8");
+  // validateHyperparameters panics on these (basemlp64.go:625-673)
+  GOCTR_CHECK(cfg->activation >= 0 && cfg->activation <= 3, "unknown activation %d", cfg->activation);
+  GOCTR_CHECK(cfg->solver == GOCTR_SOLVER_SGD || cfg->solver == GOCTR_SOLVER_ADAM, "solver must be sgd or adam");
+  GOCTR_CHECK(cfg->alpha >= 0 && cfg->lr_init > 0 && cfg->batch > 0, "bad hyper-parameters");
+  GOCTR_CHECK(cfg->out_activation >= GOCTR_OUT_LOGISTIC && cfg->out_activation <= GOCTR_OUT_IDENTITY, "unknown output head %d",
+              cfg->out_activation);
+  GOCTR_CHECK(cfg->lr_schedule >= GOCTR_LR_CONSTANT && cfg->lr_schedule <= GOCTR_LR_ADAPTIVE, "unknown learning-rate schedule %d",
+              cfg->lr_schedule);
+  for (int i = 0; i < cfg->n_layers; ++i) GOCTR_CHECK(cfg->units[i] > 0, "layer %d has %d units", i, cfg->units[i]);
+  if (init_attrs64()) return -1;
+  std::unique_ptr<goctr_mlp> p(new goctr_mlp);
+  p->cfg = *cfg;
+  p->nl = cfg->n_layers - 1;
+  long long wo = 0, po = 0;
+  for (int i = 0; i < cfg->n_layers; ++i) { p->units[i] = cfg->units[i]; p->up[i] = round_up(cfg->units[i] + 1, 16); }
+  for (int l = 0; l < p->nl; ++l) {
+    p->woff[l] = wo; p->poff[l] = po;
+    wo += (long long)p->up[l] * p->up[l + 1];
+    po += (long long)(1 + p->units[l]) * p->units[l + 1];
+  }
+  p->nflat = wo; p->nparams = po;
+  p->lr_cur = cfg->lr_init;
+  if (p->W.alloc(wo) || p->G.alloc(wo + 1) || p->Mo.alloc(wo) || p->Vo.alloc(wo) || p->Vel.alloc(wo)) return -1;
+  for (int l = 0; l < p->nl; ++l) {
+    if (p->WT[l].alloc((size_t)p->up[l] * p->up[l + 1])) return -1;
+    if (p->bn[l].alloc(p->up[l + 1])) return -1;
+  }
+  if (p->sumsq_part.alloc(2 * (size_t)cdiv(wo, 256)) || p->ring.alloc(MLP_LOSS_RING) || p->st.alloc(1) || p->st_step.alloc(1)) return -1;
+  if (set_mstate(p.get(), 0, 0, 1, 0)) return -1;
+  *out = p.release();
+  return 0;
+}
+
+void goctr_mlp_destroy(goctr_mlp* p) {
+  if (!p) return;
+  EngineScope on(p->eng);
+  std::lock_guard<std::recursive_mutex> lk(p->eng->mu);
+  if (engine().inited) (void)hipStreamSynchronize(engine().stream);   // queued (asynchronous) steps still use its buffers and graphs
+  delete p;
+}
+size_t goctr_mlp_nparams(const goctr_mlp* p) { return p ? (size_t)p->nparams : 0; }
+
+int goctr_mlp_set_params(goctr_mlp* p, const double* theta, size_t n) {
+  GOCTR_ENTER_H(p);
+  GOCTR_CHECK(p && theta && n == (size_t)p->nparams, "goctr_mlp_set_params: expected %lld values", p ? p->nparams : 0);
+  std::lock_guard<std::mutex> lk(p->mu);
+  std::vector<double> w((size_t)p->nflat, 0.0);
+  for (int l = 0; l < p->nl; ++l) {
+    const int fi = p->units[l], fo = p->units[l + 1], upo = p->up[l + 1];
+    const double* b = theta + p->poff[l];
+    const double* W = b + fo;
+    std::vector<double> wt((size_t)p->up[l] * upo, 0.0);
+    for (int c = 0; c < fo; ++c) w[(size_t)p->woff[l] + (size_t)fi * upo + c] = b[c];
+    for (int r = 0; r < fi; ++r)
+      for (int c = 0; c < fo; ++c) {
+        w[(size_t)p->woff[l] + (size_t)r * upo + c] = W[(size_t)r * fo + c];
+        wt[(size_t)c * p->up[l] + r] = W[(size_t)r * fo + c];
+      }
+    if (p->WT[l].upload(wt.data(), wt.size())) return -1;
+  }
+  if (p->W.upload(w.data(), w.size())) return -1;
+  if (p->fused_ok()) {
+    const int up0 = p->up[0], up1 = p->up[1];
+    std::vector<double> img((size_t)cdiv(up1, 32) * 32 * up0, 0.0);
+    for (int r = 0; r <= p->units[0]; ++r)            // coefficient rows + the intercept row
+      for (int c = 0; c < p->units[1]; ++c) img[mlp_img_index(r, c, up0)] = w[(size_t)p->woff[0] + (size_t)r * up1 + c];
+    if (p->W0img.alloc(img.size(), false) || p->W0img.upload(img.data(), img.size())) return -1;
+  }
+  // a fresh optimizer (fitStochastic builds one per Fit: basemlp64.go:731-752)
+  GOCTR_HIP(hipMemsetAsync(p->Mo.p, 0, sizeof(double) * p->nflat, engine().stream));
+  GOCTR_HIP(hipMemsetAsync(p->Vo.p, 0, sizeof(double) * p->nflat, engine().stream));
+  GOCTR_HIP(hipMemsetAsync(p->Vel.p, 0, sizeof(double) * p->nflat, engine().stream));
+  p->lr_cur = p->cfg.lr_init; p->samples_seen = 0;
+  return set_mstate(p, 0, 0, 1, 0);
+}
+
+int goctr_mlp_get_params(goctr_mlp* p, double* theta, size_t n) {
+  GOCTR_ENTER_H(p);
+  GOCTR_CHECK(p && theta && n == (size_t)p->nparams, "goctr_mlp_get_params: expected %lld values", p ? p->nparams : 0);
+  std::lock_guard<std::mutex> lk(p->mu);
+  return unpack(p, p->W, theta);
+}
+
+int goctr_mlp_loss_grad(goctr_mlp* p, const double* X, const double* Y, int n, double* loss, double* grads) {
+  GOCTR_ENTER_H(p);
+  GOCTR_CHECK(p && X && Y && n > 0, "goctr_mlp_loss_grad: bad arguments");
+  std::lock_guard<std::mutex> lk(p->mu);
+  unsigned slot = 0;
+  if (loss_grad_rows(p, X, Y, n, &slot)) return -1;
+  if (loss && p->ring.download(loss, 1, slot % MLP_LOSS_RING)) return -1;
+  if (grads && unpack(p, p->G, grads)) return -1;
+  return 0;
+}
+
+int goctr_mlp_upload(goctr_mlp* p, const float* X, const float* Y, int64_t rows) {
+  GOCTR_ENTER_H(p);
+  GOCTR_CHECK(p && X && Y && rows > 0, "goctr_mlp_upload: bad arguments");
+  std::lock_guard<std::mutex> lk(p->mu);
+  const int F = p->units[0], no = p->units[p->nl];
+  if (p->Xr.alloc((size_t)rows * F, false) || p->Xr.upload(X, (size_t)rows * F)) return -1;
+  if (p->Yr.alloc((size_t)rows * no, false) || p->Yr.upload(Y, (size_t)rows * no)) return -1;
+  p->rows = rows;
+  p->perm.release();
+  return prepare_resident(p);
+}
+
+int goctr_mlp_train_steps(goctr_mlp* p, int64_t first_batch, int n_steps) {
+  GOCTR_ENTER_H(p);
+  GOCTR_CHECK(p && p->rows > 0 && n_steps >= 0, "goctr_mlp_train_steps: upload rows first");
+  std::lock_guard<std::mutex> lk(p->mu);
+  const long long nb = p->rows / p->cfg.batch;
+  GOCTR_CHECK(nb > 0, "fewer rows than one batch");
+  if (retarget_mstate(p, first_batch % nb, nb)) return -1;
+  return run_fused_steps(p, n_steps);
+}
+
+int goctr_mlp_fit(goctr_mlp* p, const float* X, const float* Y, int64_t rows, const int32_t* perm, double* loss_curve,
+                  int* iters_run) {
+  {
+    GOCTR_ENTER_H(p);
+    GOCTR_CHECK(p && X && Y && rows > 0, "goctr_mlp_fit: bad arguments");
+    GOCTR_CHECK(rows >= p->cfg.batch, "goctr_mlp_fit: fewer rows (%lld) than one batch (%d) -- the reference clips BatchSize to the "
+                "sample count (basemlp64.go:517-520): create the handle with batch = rows", (long long)rows, p->cfg.batch);
+  }
+  if (goctr_mlp_upload(p, X, Y, rows)) return -1;
+  return goctr_mlp_fit_resident(p, perm, loss_curve, iters_run);
+}
+
+// fitStochastic over the rows goctr_mlp_upload left in HBM (what goctr_mlp_fit runs after its upload; bench.py times this part:
+// the metric's inputs are resident when the timed region starts)
+int goctr_mlp_fit_resident(goctr_mlp* p, const int32_t* perm, double* loss_curve, int* iters_run) {
+  GOCTR_ENTER_H(p);
+  GOCTR_CHECK(p && p->rows > 0, "goctr_mlp_fit_resident: upload rows first");
+  const int64_t rows = p->rows;
+  GOCTR_CHECK(rows >= p->cfg.batch, "goctr_mlp_fit_resident: fewer rows (%lld) than one batch (%d)", (long long)rows, p->cfg.batch);
+  std::lock_guard<std::mutex> lk(p->mu);
+  // fitStochastic's batch loop (basemlp64.go:790-793): whole batches, then ONE short batch of rows % batch samples when the
+  // sample count is not a multiple -- the reference's own flagship run has one (main.go:39-50: 79 948 rows at 200).  It is
+  // trained the reference's way (quirk Q11): the step before it runs on the per-layer kernels so that its hidden block and
+  // output deltas are in the workspace for the short step to inherit.
+  const int B = p->cfg.batch;
+  const long long nfull = rows / B;
+  const int tail = (int)(rows - nfull * B);
+  const long long nb = nfull + (tail ? 1 : 0);
+  GOCTR_CHECK(nb <= MLP_LOSS_RING, "too many batches per epoch for the loss ring");
+  GOCTR_CHECK(!(tail && engine().comm_active()), "goctr_mlp_fit: a short last batch is not supported on a data-parallel "
+              "communicator (rows %lld, batch %d)", (long long)rows, B);
+  GOCTR_CHECK(!(p->cfg.lr_schedule != GOCTR_LR_CONSTANT && engine().comm_active()), "goctr_mlp_fit: the invscaling and adaptive "
+              "learning-rate schedules are not supported on a data-parallel communicator");
+  if (perm && p->perm.alloc((size_t)rows, false)) return -1;
+  MlpState s;
+  if (get_mstate(p, &s)) return -1;
+  double best = INFINITY;
+  int no_improve = 0, it = 0;
+  std::vector<double> bl((size_t)nb);
+  for (it = 0; it < p->cfg.max_iter; ++it) {
+    if (perm && p->perm.upload(reinterpret_cast<const int*>(perm) + (int64_t)it * rows, (size_t)rows)) return -1;
+    if (set_mstate(p, s.t + (long long)it * nb, 0, nb, 0)) return -1;
+    // the whole batches replay from the captured step graphs (8 000 steps of three launches at the reference's own shape:
+    // launched one by one the host is the bottleneck); the step in front of a short batch runs on the per-layer kernels
+    const long long nfused = nfull - (tail ? 1 : 0);
+    if (nfused > 0 && run_fused_steps(p, (int)nfused)) return -1;
+    if (tail && train_step_resident(p, true, 0, true)) return -1;
+    if (tail && train_step_resident(p, true, 0, true, tail)) return -1;
+    GOCTR_HIP(hipStreamSynchronize(engine().stream));
+    if (p->ring.download(bl.data(), (size_t)nb)) return -1;
+    double acc = 0;
+    for (long long b = 0; b < nb; ++b) acc += bl[b] * (double)(b < nfull ? B : tail);  // basemlp64.go:806
+    const double loss = acc / (double)rows;                                           // :812
+    if (loss_curve) loss_curve[it] = loss;
+    if (loss > best - p->cfg.tol) no_improve++; else no_improve = 0;  // updateNoImprovementCount :859-895
+    if (loss < best) best = loss;
+    p->samples_seen += rows;                                           // mlp.t += nSamples (:814)
+    const bool sgd = p->cfg.solver == GOCTR_SOLVER_SGD;
+    if (sgd && p->cfg.lr_schedule == GOCTR_LR_INVSCALING)             // SGDOptimizer64.iterationEnds (:999-1003)
+      p->lr_cur = p->cfg.lr_init / std::pow((double)p->samples_seen + 1, p->cfg.power_t);
+    if (no_improve > p->cfg.n_iter_no_change) {                       // triggerStopping (:826-835, :1004-1022, :1054-1070)
+      if (p->cfg.lr_schedule != GOCTR_LR_ADAPTIVE) { it++; break; }
+      double lr_now = p->lr_cur;                                       // SGD: LearningRate
+      if (!sgd) {
+        // Adam: LearningRate is the effective rate of the last parameter the last step updated -- exponent t * nparams of the
+        // per-parameter beta powers (quirk Q7), t = the steps taken, read back from the device state
+        MlpState cur;
+        if (get_mstate(p, &cur)) return -1;
+        const double ex = (double)cur.t * (double)p->nparams;
+        auto bpow = [ex](double beta) {       // the reduce launch's cut-off: beyond it beta^ex < 2^-55 counts as 0
+          const double skip = (beta > 0.0 && beta < 1.0) ? 55.0 * 0.6931471805599453 / -std::log(beta) : 1e300;
+          return ex > skip ? 0.0 : std::pow(beta, ex);
+        };
+        lr_now = p->lr_cur * std::sqrt(1 - bpow(p->cfg.beta2)) / (1. - bpow(p->cfg.beta1));
+      }
+      if (lr_now <= 1e-6) { it++; break; }
+      p->lr_cur *= 0.8;                                                 // SGD: LearningRate, Adam: LearningRateInit
+      no_improve = 0;
+    }
+  }
+  if (iters_run) *iters_run = it;
+  p->perm.release();
+  return 0;
+}
+
+int goctr_mlp_predict(goctr_mlp* p, const float* X, int64_t rows, float* y_out) {
+  GOCTR_ENTER_H(p);
+  GOCTR_CHECK(p && X && y_out && rows >= 0, "goctr_mlp_predict: bad arguments");
+  if (rows == 0) return 0;
+  std::lock_guard<std::mutex> lk(p->mu);
+  return predict_rows(p, X, rows, y_out, nullptr);
+}
+
+int goctr_mlp_predict64(goctr_mlp* p, const float* X, int64_t rows, double* y_out) {
+  GOCTR_ENTER_H(p);
+  GOCTR_CHECK(p && X && y_out && rows >= 0, "goctr_mlp_predict64: bad arguments");
+  if (rows == 0) return 0;
+  std::lock_guard<std::mutex> lk(p->mu);
+  return predict_rows(p, X, rows, nullptr, y_out);
+}
+
+}  // extern "C"

@@ -199,7 +199,7 @@ class _BaseMLP:
         """fit :484 -> fitStochastic :729 on the device with self.OutActivation's head.  X float32 rows (the adapter
         widens them, mlp.go:46-53).  Every row is trained: a sample count that is not a multiple of the batch
         ends each epoch with one short batch, computed the reference's way (quirk Q11, basemlp64.go:790-812 -- its hidden
-        block and output deltas keep the previous batch's rows beyond the short batch; csrc/mlp.hip goctr_mlp_fit)."""
+        block and output deltas keep the previous batch's rows beyond the short batch; csrc/mlp_api.hip goctr_mlp_fit_resident)."""
         self._validate()
         X = capi.f32(X)
         Y = capi.f32(Y).reshape(X.shape[0], -1)
