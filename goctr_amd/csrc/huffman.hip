@@ -1,16 +1,21 @@
-// huffman.hip -- the Huffman tree of item2vec's hierarchical softmax built WITH the device.
+// huffman.hip -- the Huffman tree of item2vec's hierarchical softmax, built on the host or WITH the device.
 //
-// Replaces Dictionary.HuffnamTree + node.GetPath (feature/embedding/corpus/dictionary/huffman.go:23-57, node/node.go:26-43)
-// at vocabulary sizes where the host-only builder of w2v.hip (243 ms at V = 10^6, 1.6 s at V = 10^7 on 8 cores: a radix sort, the
-// merge loop and the path fill all walking 2 V-entry arrays in random order) is several training passes long.  Division of labour:
-//   device  stable radix sort of (count, word) by count                 rocprim::radix_sort_pairs; ties keep word order = the
-//                                                                        reference's sort.SliceStable (huffman.go:27-29)
-//   host    the two-queue merge, in SORTED-RANK space                    inherently sequential (V - 1 dependent steps), but with
-//           leaves numbered by sorted rank every access is a stream: ~5 ns per merge, not a cache miss per merge.  Same rule as
-//           w2v.hip's build_huffman: a merged node goes in FRONT of every node of equal value (huffman.go:44-52)
-//   device  per leaf (in sorted order: neighbours share their ancestors) the chain length, a prefix sum of the kept path
-//           lengths in word order, and the root-first (inner node, code) fill; the paths never exist on the host
-// The result is bit-identical to build_huffman's (tests/test_huffman_scale.py).
+// Replaces Dictionary.HuffnamTree + node.GetPath (feature/embedding/corpus/dictionary/huffman.go:23-57, node/node.go:26-43).
+// Both builders share ONE two-queue merge (huffman_merge), in SORTED-RANK space: leaf r is the word of sorted rank r, merged
+// node k is V + k, and a merged node goes in FRONT of every node of equal value (huffman.go:44-52).  With leaves numbered by
+// sorted rank every access of the merge is a stream: ~5 ns per merge, not a cache miss per merge.
+//   host builder    (build_huffman) stable sort of the words by count, the merge, then per leaf the chain length, the kept
+//                   path lengths in word order and the root-first (inner node, code) fill, threaded
+//   device builder  (huffman_build_device) for vocabularies where the host builder (round 3: 243 ms at V = 10^6, 1.6 s at
+//                   V = 10^7 on 8 cores) is several training passes long:
+//     device  stable radix sort of (count, word) by count                 rocprim::radix_sort_pairs; ties keep word order = the
+//                                                                          reference's sort.SliceStable (huffman.go:27-29)
+//     host    the merge                                                    inherently sequential (V - 1 dependent steps)
+//     device  per leaf (in sorted order: neighbours share their ancestors) the chain length, a prefix sum of the kept path
+//             lengths in word order, and the root-first (inner node, code) fill; the paths never exist on the host
+// The two builders' paths are bit-identical (tests/test_gpu_huffman.py); the host builder's match the literal restatement of
+// huffman.go (tests/test_huffman_scale.py).
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <string.h>
@@ -18,6 +23,7 @@
 
 #include <chrono>
 #include <numeric>
+#include <thread>
 
 #include "common.h"
 #include "huffman.h"
@@ -68,6 +74,127 @@ __global__ __launch_bounds__(256) void huff_fill_kernel(const int* __restrict__ 
 
 }  // namespace
 
+void huffman_merge(const long long* sval, int64_t V, std::vector<int>& parent, std::vector<unsigned char>& code) {
+  const int64_t total = 2 * V - 1;
+  // (built in vectors of this function's own, moved out at the end: stores into the caller's arrays, whose memory the compiler
+  // cannot tell apart from the run vectors' bookkeeping, made it reload that bookkeeping after every store)
+  std::vector<int> par((size_t)total, -1);
+  std::vector<unsigned char> cd((size_t)total, 0);
+  // merged nodes, in creation order; a RUN = the merged nodes of one value (values are non-decreasing, so a run is a
+  // contiguous range).  Only the last run grows, only the front run is consumed -- newest first (huffman.go inserts a merged
+  // node in FRONT of every node of equal value).  Flat arrays: round 2 kept one std::vector per run, a heap allocation per
+  // distinct merged value (10^6 of them on a Zipf tail).
+  std::vector<long long> mval((size_t)std::max<int64_t>(V - 1, 1));
+  std::vector<int> mq((size_t)V);
+  std::vector<long long> run_val; std::vector<int> run_beg, run_end;
+  run_val.reserve(1 << 16); run_beg.reserve(1 << 16); run_end.reserve(1 << 16);
+  size_t rfront = 0;
+  int mq_n = 0;
+  int64_t lq = 0;
+  for (int64_t k = 0; k + 1 < V; ++k) {
+    int pick[2];
+    for (int t = 0; t < 2; ++t) {
+      const bool have_leaf = lq < V, have_m = rfront < run_val.size();
+      const bool take_m = have_leaf && have_m ? run_val[rfront] <= sval[(size_t)lq] : have_m;
+      if (take_m) {
+        pick[t] = mq[--run_end[rfront]];
+        if (rfront + 1 == run_val.size()) mq_n = run_end[rfront];          // (front run == last run: it is a plain stack)
+        if (run_end[rfront] == run_beg[rfront]) ++rfront;
+      } else {
+        pick[t] = (int)lq++;
+      }
+    }
+    const int id = (int)(V + k);
+    const long long v = (pick[0] < V ? sval[(size_t)pick[0]] : mval[(size_t)(pick[0] - V)]) +
+                        (pick[1] < V ? sval[(size_t)pick[1]] : mval[(size_t)(pick[1] - V)]);
+    mval[(size_t)k] = v;
+    cd[pick[0]] = 0; cd[pick[1]] = 1;
+    par[pick[0]] = id; par[pick[1]] = id;
+    if (rfront < run_val.size() && run_val.back() == v) { mq[mq_n++] = id; run_end.back() = mq_n; }
+    else { run_val.push_back(v); run_beg.push_back(mq_n); mq[mq_n++] = id; run_end.push_back(mq_n); }
+  }
+  parent = std::move(par);
+  code = std::move(cd);
+}
+
+void build_huffman(const int64_t* counts, int64_t V, int max_depth, std::vector<long long>& off,
+                   std::vector<int>& nodes, std::vector<unsigned char>& codes) {
+  off.assign((size_t)V + 1, 0);
+  nodes.clear(); codes.clear();
+  if (V <= 0) return;
+  const int64_t total = 2 * V - 1;
+  std::vector<int> order((size_t)V);
+  std::iota(order.begin(), order.end(), 0);
+  {
+    // stable sort of the leaves by count: LSD radix on the count alone (the indices start in order, every pass is stable) --
+    // std::stable_sort with an indirect comparison took 70 of the 110 ms of the tree build at V = 10^6
+    int64_t mx = 0;
+    bool nonneg = true;
+    for (int64_t i = 0; i < V; ++i) { mx = std::max(mx, counts[i]); nonneg = nonneg && counts[i] >= 0; }
+    if (!nonneg || V < 4096) {
+      std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return counts[x] < counts[y]; });
+    } else {
+      constexpr int RB = 11, RN = 1 << RB;
+      std::vector<int> tmp((size_t)V);
+      std::vector<int64_t> hist((size_t)RN);
+      for (int shift = 0; shift < 63 && (mx >> shift) != 0; shift += RB) {
+        std::fill(hist.begin(), hist.end(), 0);
+        for (int64_t i = 0; i < V; ++i) hist[(size_t)((counts[order[i]] >> shift) & (RN - 1))]++;
+        int64_t run = 0;
+        for (int d = 0; d < RN; ++d) { const int64_t c = hist[d]; hist[d] = run; run += c; }
+        for (int64_t i = 0; i < V; ++i) tmp[(size_t)hist[(size_t)((counts[order[i]] >> shift) & (RN - 1))]++] = order[i];
+        order.swap(tmp);
+      }
+    }
+  }
+  std::vector<long long> sval((size_t)V);
+  for (int64_t r = 0; r < V; ++r) sval[(size_t)r] = counts[order[r]];
+  std::vector<int> parent;
+  std::vector<unsigned char> code;
+  huffman_merge(sval.data(), V, parent, code);
+  // depth of every node: a parent is created after its children, so one pass from the root down
+  std::vector<int> depth((size_t)total, 0);          // nodes on the leaf .. root chain, the node itself included
+  for (int64_t i = total - 1; i >= 0; --i) depth[i] = parent[i] < 0 ? 1 : depth[parent[i]] + 1;
+  // GetPath keeps cache[:depth] of the root-first chain (node.go:39-42): min(max_depth, len) - 1 (inner node, code) entries
+  for (int64_t r = 0; r < V; ++r) {
+    const int64_t d = std::min<int64_t>(max_depth, depth[r]);
+    off[(size_t)order[r] + 1] = d > 0 ? d - 1 : 0;
+  }
+  for (int64_t i = 0; i < V; ++i) off[i + 1] += off[i];
+  nodes.resize((size_t)off[V]); codes.resize((size_t)off[V]);
+  // fill: every leaf walks up to the root and writes its word's range back to front -- independent per leaf, so in parallel
+  // (leaves are visited in rank order: neighbours in that order share most of their ancestors, so the parent[] walks stay in
+  // cache; in word order every step of every walk was a miss)
+  auto fill = [&](int64_t lo, int64_t hi) {
+    for (int64_t r = lo; r < hi; ++r) {
+      const int64_t i = order[r];
+      const int len = depth[r];
+      const int64_t keep = off[i + 1] - off[i];
+      // chain (leaf .. root) position q = 0 .. len - 1; root-first index j = len - 1 - q; entry j (j < keep) = (chain[len-1-j] - V,
+      // code[chain[len-2-j]]): walking up, at chain position q >= 1 we know chain[q] and its predecessor chain[q-1]
+      int prev = (int)r;
+      int p = parent[r];
+      for (int q = 1; q < len; ++q) {
+        const int j = len - 1 - q;
+        if (j < keep) { nodes[(size_t)(off[i] + j)] = p - (int)V; codes[(size_t)(off[i] + j)] = code[prev]; }
+        prev = p; p = parent[p];
+      }
+    }
+  };
+  unsigned nt = std::thread::hardware_concurrency();
+  nt = nt == 0 ? 1 : (nt > 16 ? 16 : nt);
+  if (V < 20000 || nt == 1) fill(0, V);
+  else {
+    std::vector<std::thread> th;
+    for (unsigned t = 0; t < nt; ++t) th.emplace_back(fill, V * t / nt, V * (t + 1) / nt);
+    for (auto& x : th) x.join();
+  }
+}
+
+bool huffman_on_device(int64_t V) {
+  return env_flag("GOCTR_HUFFMAN_DEVICE", V >= 50000);
+}
+
 int huffman_build_device(const long long* counts_host, int64_t V, int max_depth, DevBuf<long long>& off, DevBuf<int>& nodes,
                          DevBuf<unsigned char>& codes, long long* total_out, double parts_ms[4]) {
   Engine& e = engine();
@@ -98,41 +225,11 @@ int huffman_build_device(const long long* counts_host, int64_t V, int max_depth,
   GOCTR_HIP(hipMemcpyAsync(sval.data(), key_out.p, sizeof(long long) * (size_t)V, hipMemcpyDeviceToHost, s));
   GOCTR_HIP(hipStreamSynchronize(s));
   const auto t1 = now();
-  // ---- host: the two-queue merge in sorted-rank space (leaf r = rank r, merged node k = V + k)
+  // ---- host: the merge (leaf r = rank r, merged node k = V + k)
   const int64_t total = 2 * V - 1;
-  std::vector<int> parent((size_t)total, -1);
-  std::vector<unsigned char> code((size_t)total, 0);
-  {
-    std::vector<long long> mval((size_t)std::max<int64_t>(V - 1, 1));
-    std::vector<int> mq((size_t)V);
-    std::vector<long long> run_val; std::vector<int> run_beg, run_end;
-    run_val.reserve(1 << 16); run_beg.reserve(1 << 16); run_end.reserve(1 << 16);
-    size_t rfront = 0;
-    int mq_n = 0;
-    int64_t lq = 0;
-    for (int64_t k = 0; k + 1 < V; ++k) {
-      int pick[2];
-      for (int t = 0; t < 2; ++t) {
-        const bool have_leaf = lq < V, have_m = rfront < run_val.size();
-        const bool take_m = have_leaf && have_m ? run_val[rfront] <= sval[(size_t)lq] : have_m;
-        if (take_m) {
-          pick[t] = mq[--run_end[rfront]];
-          if (rfront + 1 == run_val.size()) mq_n = run_end[rfront];          // (front run == last run: it is a plain stack)
-          if (run_end[rfront] == run_beg[rfront]) ++rfront;
-        } else {
-          pick[t] = (int)lq++;
-        }
-      }
-      const int id = (int)(V + k);
-      const long long v = (pick[0] < V ? sval[(size_t)pick[0]] : mval[(size_t)(pick[0] - V)]) +
-                          (pick[1] < V ? sval[(size_t)pick[1]] : mval[(size_t)(pick[1] - V)]);
-      mval[(size_t)k] = v;
-      code[(size_t)pick[0]] = 0; code[(size_t)pick[1]] = 1;
-      parent[(size_t)pick[0]] = id; parent[(size_t)pick[1]] = id;
-      if (rfront < run_val.size() && run_val.back() == v) { mq[mq_n++] = id; run_end.back() = mq_n; }
-      else { run_val.push_back(v); run_beg.push_back(mq_n); mq[mq_n++] = id; run_end.push_back(mq_n); }
-    }
-  }
+  std::vector<int> parent;
+  std::vector<unsigned char> code;
+  huffman_merge(sval.data(), V, parent, code);
   const auto t2 = now();
   // ---- device: chain lengths, offsets, fill
   DevBuf<int> d_parent, len_r;
@@ -162,3 +259,45 @@ int huffman_build_device(const long long* counts_host, int64_t V, int max_depth,
 }
 
 }  // namespace goctr
+
+using namespace goctr;
+
+extern "C" {
+
+int goctr_huffman_build(const int64_t* counts, int64_t V, int max_depth, int64_t* path_off, int32_t* nodes, uint8_t* codes,
+                        int64_t cap, int64_t* total, double* build_ms) {
+  GOCTR_CHECK(counts && V > 0 && path_off && max_depth > 0, "goctr_huffman_build: bad arguments");
+  GOCTR_CHECK(V <= 0x3fffffff, "goctr_huffman_build: V = %lld exceeds the 2^30 words the int32 node ids can number", (long long)V);
+  if (engine().inited && huffman_on_device(V)) {
+    // with a device bound: the build of huffman.hip.  *build_ms = until the paths are resident in HBM (what goctr_w2v_create
+    // pays); copying them out to the caller's arrays (1.2 GB at V = 10^7) comes on top and is not part of the build
+    GOCTR_ENTER();
+    DevBuf<long long> off; DevBuf<int> nd; DevBuf<unsigned char> cd;
+    long long tot = 0; double parts[4] = {0, 0, 0, 0};
+    std::vector<long long> c64(counts, counts + V);
+    if (huffman_build_device(c64.data(), V, max_depth, off, nd, cd, &tot, parts)) return -1;
+    if (build_ms) *build_ms = parts[3];
+    std::vector<long long> ho((size_t)V + 1);
+    if (off.download(ho.data(), ho.size())) return -1;
+    for (size_t i = 0; i < ho.size(); ++i) path_off[i] = ho[i];
+    if (total) *total = tot;
+    const int64_t n = std::min<int64_t>(cap, tot);
+    if (nodes && n > 0 && nd.download(nodes, (size_t)n)) return -1;
+    if (codes && n > 0 && cd.download(codes, (size_t)n)) return -1;
+    return 0;
+  }
+  std::vector<long long> off;
+  std::vector<int> nd;
+  std::vector<unsigned char> cd;
+  const auto t0 = std::chrono::steady_clock::now();
+  build_huffman(counts, V, max_depth, off, nd, cd);
+  if (build_ms) *build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  for (size_t i = 0; i < off.size(); ++i) path_off[i] = off[i];
+  if (total) *total = (int64_t)nd.size();
+  const int64_t n = std::min<int64_t>(cap, (int64_t)nd.size());
+  if (nodes && n > 0) memcpy(nodes, nd.data(), sizeof(int32_t) * (size_t)n);
+  if (codes && n > 0) memcpy(codes, cd.data(), (size_t)n);
+  return 0;
+}
+
+}  // extern "C"

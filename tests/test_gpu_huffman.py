@@ -1,6 +1,6 @@
 """The Huffman build WITH the device (csrc/huffman.hip: rocPRIM stable sort by count, the two-queue merge on the host in
 sorted-rank space, chain lengths + prefix sum + root-first path fill on the device) must give, bit for bit, the paths of the
-host-only builder (csrc/w2v.hip build_huffman), which tests/test_huffman_scale.py ties to the literal O(V^2) restatement of
+host-only builder (csrc/huffman.hip build_huffman), which tests/test_huffman_scale.py ties to the literal O(V^2) restatement of
 dictionary/huffman.go:23-57 and node/node.go:39-42."""
 import os
 

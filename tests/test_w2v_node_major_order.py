@@ -1,4 +1,4 @@
-"""CPU check of the claim behind the node-major Hogwild kernel (csrc/w2v.hip: w2v_hogwild_nm_kernel): walking the pairs
+"""CPU check of the claim behind the node-major Hogwild kernel (csrc/w2v_kernels.h: w2v_hogwild_nm_kernel): walking the pairs
 of a position JB at a time, node by node -- a node vector read once per chunk, pair j + 1 reading pair j's update from a local
 copy, the chunk's summed update written once, a context word that repeats inside a window starting a new chunk -- is the
 SEQUENTIAL pair-major arithmetic of the reference (model.go:48-78, optimizer.go:107-129) up to float64 rounding of the summed
