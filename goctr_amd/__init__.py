@@ -8,6 +8,7 @@ Package layout (only what the path needs):
   recommend.py     host mirror of recommend.SampleInfo / TrainSample / Fitter / PredictAbstract
   mlp.py           host mirror of nn.MLPClassifier behind model/mlp's Fit / Predict wrappers
   embedding.py     host mirror of feature/embedding.TrainEmbedding (item2vec)
+  metrics.py       host mirror of utils.RocAuc32 / RocAuc / Accuracy32 over the device metrics
 """
 from . import capi  # noqa: F401
 from .capi import GoctrError  # noqa: F401

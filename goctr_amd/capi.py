@@ -49,6 +49,13 @@ class W2vCfg(C.Structure):
                 ("streams", C.c_int), ("slices", C.c_int), ("devices", C.c_int), ("exchange_every", C.c_int64)]
 
 
+class BinaryMetrics(C.Structure):
+    """goctr_binary_metrics (include/goctr.h)"""
+    _fields_ = [("n", C.c_int64), ("positives", C.c_int64), ("negatives", C.c_int64), ("thresholds", C.c_int64),
+                ("auc_num", C.c_uint64), ("auc_den", C.c_uint64), ("auc", C.c_double), ("auc32", C.c_float),
+                ("correct", C.c_int64), ("logloss", C.c_double)]
+
+
 # every symbol include/goctr.h declares (tests/test_capi_symbols.py checks the list against the header)
 SYMBOLS = [
     "goctr_init", "goctr_init_devices", "goctr_engine_count", "goctr_engine_call_ms", "goctr_engine_select", "goctr_comm_group_enable", "goctr_device_count", "goctr_sync", "goctr_last_error", "goctr_version", "goctr_device_info",
@@ -69,7 +76,8 @@ SYMBOLS = [
     "goctr_recsys_create", "goctr_recsys_destroy", "goctr_batch_predict", "goctr_rank",
     "goctr_corpus_create", "goctr_corpus_destroy", "goctr_corpus_append", "goctr_corpus_build", "goctr_corpus_info",
     "goctr_corpus_get_dictionary", "goctr_corpus_get_doc", "goctr_w2v_create_from_corpus", "goctr_w2v_use_corpus",
-    "goctr_w2v_get_keep_mask",
+    "goctr_w2v_get_keep_mask", "goctr_metrics_binary", "goctr_metrics_binary_f64", "goctr_evaluate_dataset",
+    "goctr_mlp_evaluate_resident",
 ]
 
 _lib = None
@@ -92,6 +100,11 @@ def load() -> C.CDLL:
                      "goctr_w2v_destroy", "goctr_searcher_destroy", "goctr_ubcache_destroy", "goctr_recsys_destroy", "goctr_train_cfg_default", "goctr_mlp_cfg_default",
                      "goctr_w2v_cfg_default"):
             getattr(_lib, name).restype = None
+        _bm = C.POINTER(BinaryMetrics)
+        _lib.goctr_metrics_binary.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, _bm]
+        _lib.goctr_metrics_binary_f64.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64, _bm]
+        _lib.goctr_evaluate_dataset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _bm]
+        _lib.goctr_mlp_evaluate_resident.argtypes = [C.c_void_p, _bm]
     return _lib
 
 

@@ -6,6 +6,7 @@
 #include <shared_mutex>
 
 #include "ctr_model.h"
+#include "metrics.h"
 
 namespace goctr {
 
@@ -663,8 +664,10 @@ int goctr_loss_grad_dense(goctr_model* m, const float* X, const float* Y, int va
 }
 
 // ------------------------------------------------------------------ predict
+// collect: gather the scores of the call in m->yall (rows [0, min(rows, n_batches * batch)) when scoring from batch 0); y_host
+// (needs collect): then copy them to the host
 static int predict_batches(goctr_model* m, goctr_emb* emb, goctr_dataset* d, int batch, int64_t first_batch,
-                           int64_t n_batches, float* y_host) {
+                           int64_t n_batches, bool collect, float* y_host) {
   if (check_dataset(m, d, emb)) return -1;
   // Rows are scored independently of their batch, so G consecutive batches can share launches (one gather and one forward
   // chain over G * batch rows): fewer and fuller launches.  PredBatchSize keeps its meaning at the boundary -- which rows a
@@ -688,7 +691,7 @@ static int predict_batches(goctr_model* m, goctr_emb* emb, goctr_dataset* d, int
   // per-batch states are written up front so that no host stack memory is read asynchronously
   const int64_t CH = 4096;
   if (m->pst.ensure((size_t)std::min<int64_t>(n_batches, CH), false)) return -1;
-  if (y_host && m->yall.ensure((size_t)d->rows, false)) return -1;
+  if (collect && m->yall.ensure((size_t)d->rows, false)) return -1;
   std::vector<StepState> hs;
   for (int64_t k0 = 0; k0 < n_batches; k0 += CH) {
     const int64_t cnt = std::min<int64_t>(CH, n_batches - k0);
@@ -712,7 +715,7 @@ static int predict_batches(goctr_model* m, goctr_emb* emb, goctr_dataset* d, int
       if (grp[k] == 0) continue;                      // (covered by the group that started before it)
       const int Bk = batch * grp[k];
       if (launch_forward(m, src, Bk, o, m->pst.p + k, &fb)) return -1;
-      if (y_host) {
+      if (collect) {
         const long long b = hs[k].batch_idx;
         const long long start = b * Bk, end = std::min<long long>(start + Bk, d->rows);
         // first end-start outputs (model.go:344-347), collected on the device: one copy to the host per call
@@ -734,7 +737,7 @@ int goctr_predict_dataset(goctr_model* m, goctr_emb* emb, goctr_dataset* d, int 
   GOCTR_ENTER_H(m);
   GOCTR_CHECK(m && d && y_out && batch > 0, "goctr_predict_dataset: bad arguments");
   std::unique_lock<std::shared_mutex> lk(m->mu); ++m->gen;
-  return predict_batches(m, emb, d, batch, 0, cdiv(d->rows, batch), y_out);
+  return predict_batches(m, emb, d, batch, 0, cdiv(d->rows, batch), true, y_out);
 }
 
 int goctr_predict_steps(goctr_model* m, goctr_emb* emb, goctr_dataset* d, int batch, int64_t first_batch,
@@ -742,7 +745,18 @@ int goctr_predict_steps(goctr_model* m, goctr_emb* emb, goctr_dataset* d, int ba
   GOCTR_ENTER_H(m);
   GOCTR_CHECK(m && d && batch > 0 && n_batches >= 0, "goctr_predict_steps: bad arguments");
   std::unique_lock<std::shared_mutex> lk(m->mu); ++m->gen;
-  return predict_batches(m, emb, d, batch, first_batch, n_batches, nullptr);
+  return predict_batches(m, emb, d, batch, first_batch, n_batches, false, nullptr);
+}
+
+int goctr_evaluate_dataset(goctr_model* m, goctr_emb* emb, goctr_dataset* d, int batch, goctr_binary_metrics* out) {
+  GOCTR_ENTER_H(m);
+  GOCTR_CHECK(m && d && out && batch > 0, "goctr_evaluate_dataset: bad arguments");
+  GOCTR_CHECK(d->has_y && d->Y.p, "goctr_evaluate_dataset: the dataset has no labels");
+  if (metrics_check_rows(d->rows, "goctr_evaluate_dataset")) return -1;
+  std::unique_lock<std::shared_mutex> lk(m->mu); ++m->gen;
+  // goctr_predict_dataset's scoring, left in m->yall, then the metrics against the resident labels (metrics.hip)
+  if (predict_batches(m, emb, d, batch, 0, cdiv(d->rows, batch), true, nullptr)) return -1;
+  return metrics_binary_dev(m->yall.p, d->Y.p, d->rows, out, "goctr_evaluate_dataset");
 }
 
 }  // extern "C"

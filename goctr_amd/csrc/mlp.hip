@@ -428,3 +428,23 @@ int predict_rows(goctr_mlp* p, const float* X, int64_t rows, float* y32, double*
   }
   return 0;
 }
+
+// predict_rows' float64 path over the resident rows (p->Xr): the same chunks and kernels, so the same bits as goctr_mlp_predict64
+// on those rows; column 0 of the head lands in y_dev [p->rows] on the device
+int predict_resident64(goctr_mlp* p, double* y_dev) {
+  const int L = p->nl, F = p->units[0], no = p->units[L];
+  const int CHUNK = 16384;
+  const int64_t rows = p->rows;
+  if (ensure_ws(p, (int)std::min<int64_t>(rows, CHUNK))) return -1;
+  for (int64_t s0 = 0; s0 < rows; s0 += CHUNK) {
+    const int n = (int)std::min<int64_t>(CHUNK, rows - s0);
+    hipLaunchKernelGGL(mlp_gather_kernel, dim3(n), dim3(256), 0, engine().stream, (const float*)(p->Xr.p + s0 * F), (const float*)nullptr,
+                       (const int*)nullptr, p->st.p, 0LL, 0, n, F, p->up[0], no, p->up[L], p->A[0].p, (double*)nullptr,
+                       (MlpState*)nullptr, n);
+    GOCTR_HIP(hipGetLastError());
+    if (forward(p, n, false)) return -1;
+    GOCTR_HIP(hipMemcpy2DAsync(y_dev + s0, sizeof(double), p->A[L].p, sizeof(double) * p->up[L], sizeof(double), n,
+                               hipMemcpyDeviceToDevice, engine().stream));
+  }
+  return 0;
+}

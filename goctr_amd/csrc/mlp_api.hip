@@ -4,6 +4,7 @@
 #include <memory>
 #include <vector>
 
+#include "metrics.h"
 #include "mlp_model.h"
 
 // a padded flat parameter buffer (W or G) in the packed [ b_i | W_i ]... order of goctr_mlp_set_params
@@ -250,6 +251,20 @@ int goctr_mlp_predict64(goctr_mlp* p, const float* X, int64_t rows, double* y_ou
   if (rows == 0) return 0;
   std::lock_guard<std::mutex> lk(p->mu);
   return predict_rows(p, X, rows, nullptr, y_out);
+}
+
+int goctr_mlp_evaluate_resident(goctr_mlp* p, goctr_binary_metrics* out) {
+  GOCTR_ENTER_H(p);
+  GOCTR_CHECK(p && out, "goctr_mlp_evaluate_resident: bad arguments");
+  GOCTR_CHECK(p->rows > 0, "goctr_mlp_evaluate_resident: upload rows first");
+  GOCTR_CHECK(p->units[p->nl] == 1 && p->cfg.out_activation != GOCTR_OUT_SOFTMAX,
+              "goctr_mlp_evaluate_resident: binary metrics need a single-output head (this one has %d output units%s)",
+              p->units[p->nl], p->cfg.out_activation == GOCTR_OUT_SOFTMAX ? ", softmax" : "");
+  if (metrics_check_rows(p->rows, "goctr_mlp_evaluate_resident")) return -1;
+  std::lock_guard<std::mutex> lk(p->mu);
+  DevBuf<double> score;
+  if (score.alloc((size_t)p->rows, false) || predict_resident64(p, score.p)) return -1;
+  return metrics_binary_dev(score.p, p->Yr.p, p->rows, out, "goctr_mlp_evaluate_resident");
 }
 
 }  // extern "C"

@@ -69,6 +69,34 @@ struct Fitter {  // rcmd.go:95-97
 };
 }  // namespace recommend
 
+namespace utils {
+// utils.RocAuc32 / RocAuc / Accuracy32 (utils/util.go:105-148) over the device metrics (include/goctr.h goctr_metrics_binary):
+// the AUC exactly as S / (2 P N), rounded once
+inline goctr_binary_metrics BinaryMetrics(const float* score, const float* y, int64_t n) {
+  ensure_init();
+  goctr_binary_metrics m{};
+  check(goctr_metrics_binary(score, y, n, &m));
+  return m;
+}
+inline goctr_binary_metrics BinaryMetrics(const double* score, const double* y, int64_t n) {
+  ensure_init();
+  goctr_binary_metrics m{};
+  check(goctr_metrics_binary_f64(score, y, n, &m));
+  return m;
+}
+inline float RocAuc32(const std::vector<float>& pred, const std::vector<float>& y) {
+  return BinaryMetrics(pred.data(), y.data(), (int64_t)pred.size()).auc32;
+}
+inline double RocAuc(const std::vector<double>& pred, const std::vector<double>& y) {
+  return BinaryMetrics(pred.data(), y.data(), (int64_t)pred.size()).auc;
+}
+// Accuracy32's float32 hit counter stops growing at 2^24
+inline float Accuracy32(const std::vector<float>& pred, const std::vector<float>& y) {
+  const auto m = BinaryMetrics(pred.data(), y.data(), (int64_t)pred.size());
+  return (float)std::min<int64_t>(m.correct, int64_t(1) << 24) / (float)m.n;
+}
+}  // namespace utils
+
 namespace model {
 constexpr int mlp0_1 = 200, mlp1_2 = 80;  // din.go:17-18
 
@@ -141,6 +169,13 @@ inline std::vector<float> Predict(CtrNet& m, int numExamples, int batchSize, con
   auto r = si.ranges();
   check(goctr_predict_dense(m.Vm(), inputs, numExamples, xcols, r.data(), batchSize, y.data()));
   return y;
+}
+
+// model.Predict over a resident dataset, scored against its labels on the device (goctr_evaluate_dataset): no score leaves HBM
+inline goctr_binary_metrics EvaluateDataset(CtrNet& m, goctr_dataset* d, int batchSize, goctr_emb* emb = nullptr) {
+  goctr_binary_metrics r{};
+  check(goctr_evaluate_dataset(m.Vm(), emb, d, batchSize, &r));
+  return r;
 }
 }  // namespace model
 
@@ -258,6 +293,12 @@ class MLPClassifier {
     std::vector<float> y((size_t)rows);
     check(goctr_mlp_predict(h_, X, rows, y.data()));
     return y;
+  }
+  // the rows Fit left resident, predictProbas in float64 against their labels (goctr_mlp_evaluate_resident)
+  goctr_binary_metrics EvaluateResident() {
+    goctr_binary_metrics r{};
+    check(goctr_mlp_evaluate_resident(h_, &r));
+    return r;
   }
 
  private:

@@ -241,6 +241,14 @@ class _BaseMLP:
         capi.check(capi.load().goctr_mlp_fit_resident(self._h, capi.ptr(pp, C.c_int32), capi.ptr(curve, C.c_double), C.byref(ran)))
         return self._fitted(curve, ran.value)
 
+    def EvaluateResident(self):
+        """the resident rows (upload) scored by predictProbas in float64 against the resident Y, on the device
+        (goctr_mlp_evaluate_resident): a metrics.BinaryMetrics.  Single-output heads only."""
+        from .metrics import BinaryMetrics
+        out = capi.BinaryMetrics()
+        capi.check(capi.load().goctr_mlp_evaluate_resident(self._h, C.byref(out)))
+        return BinaryMetrics.from_c(out)
+
     def _predict64(self, X):
         """predictProbas (basemlp64.go:897-913) in float64: the head's values"""
         X = capi.f32(X)

@@ -447,6 +447,15 @@ def predict_dataset(m: _CtrNet, ds: Dataset, batch, emb: EmbeddingTable | None =
     return y
 
 
+def evaluate_dataset(m: _CtrNet, ds: Dataset, batch, emb: EmbeddingTable | None = None):
+    """predict_dataset's scores against the dataset's resident labels, on the device (goctr_evaluate_dataset): exact
+    ROC-AUC, Accuracy32's hits and the log-loss, as a metrics.BinaryMetrics; no score is copied to the host"""
+    from .metrics import BinaryMetrics
+    out = capi.BinaryMetrics()
+    capi.check(capi.load().goctr_evaluate_dataset(m._h, emb._h if emb else None, ds._h, C.c_int(batch), C.byref(out)))
+    return BinaryMetrics.from_c(out)
+
+
 def predict_steps(m: _CtrNet, ds: Dataset, batch, n_batches, first_batch=0, emb: EmbeddingTable | None = None):
     capi.check(capi.load().goctr_predict_steps(m._h, emb._h if emb else None, ds._h, C.c_int(batch),
                                                C.c_int64(first_batch), C.c_int(n_batches)))

@@ -453,6 +453,32 @@ void goctr_searcher_destroy(goctr_searcher* s);
 int goctr_searcher_search(goctr_searcher* s, const double* queries, int Q, int k, const int64_t* ignore,
                           int64_t* out_idx, double* out_sim, int* out_count);
 
+/* ---------------------------------------------------------------- binary metrics on the device
+ * Replaces utils.RocAuc32 / RocAuc (utils/util.go:116-148 -> metrics.ROCAUCScore(yTrue, yScore, "", nil),
+ * nn/metrics/ranking.go:13-149), utils.Accuracy32 / Accuracy (util.go:95-114) and the BinaryCrossEntropy32 formula
+ * (model/cost.go:9-17) over one column of scores, without sample weights.  A row is positive iff y > 0.5 (a NaN label is
+ * negative); equal scores are one threshold group (-0 ties with +0; subnormals and +-inf are ordinary values).  With P positives
+ * and N negatives, S = sum over groups g of neg_g (2 P_above_g + pos_g) and the AUC is S / (2 P N) exactly; the reference's
+ * trapezoid sum equals it up to its own float64 rounding.  A NaN score fails the call (-1, *out untouched).  1 <= n < 2^31.
+ * No CPU fallback: every call runs on the calling thread's engine (or the handle's). */
+typedef struct {
+  int64_t  n, positives, negatives, thresholds;  /* thresholds = distinct scores = groups */
+  uint64_t auc_num, auc_den;                     /* AUC = auc_num / auc_den exactly (den = 2 P N) */
+  double   auc;  float auc32;                    /* correctly rounded; NaN when P == 0 or N == 0 (then num = den = 0) */
+  int64_t  correct;                              /* utils.Accuracy32's hits (|fl32(p - y)| < 0.5), exact */
+  double   logloss;                              /* mean of -(y log p + (1 - y) log(1 - p)) in float64, not clamped */
+} goctr_binary_metrics;
+
+/* host arrays score [n], y [n] (copied to the device); the float64 form takes the difference of Accuracy in float64 */
+int goctr_metrics_binary(const float* score, const float* y, int64_t n, goctr_binary_metrics* out);
+int goctr_metrics_binary_f64(const double* score, const double* y, int64_t n, goctr_binary_metrics* out);
+/* the scores of goctr_predict_dataset(m, emb, d, batch, .) -- same batches, padding and kernels -- against d's resident
+ * labels; no score leaves the device */
+int goctr_evaluate_dataset(goctr_model* m, goctr_emb* emb, goctr_dataset* d, int batch, goctr_binary_metrics* out);
+/* the rows goctr_mlp_upload left resident: the output unit's float64 activation (goctr_mlp_predict64's values) against the
+ * resident Y; single-output heads only (a softmax head is refused) */
+int goctr_mlp_evaluate_resident(goctr_mlp* p, goctr_binary_metrics* out);
+
 #ifdef __cplusplus
 }
 #endif
