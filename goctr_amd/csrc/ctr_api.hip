@@ -1,5 +1,5 @@
 // ctr_api.hip -- the C ABI (include/goctr.h) of the DIN / YouTube-DNN engine: models, embedding tables, the standalone
-// gather and datasets, and the training and predict entry points above the step (ctr.hip, through ctr_model.h).
+// gather and datasets, and the training and predict entry points above the step (ctr.hip and ctr_run.hip, through ctr_model.h).
 #define GOCTR_NO_PLAIN_KERNELS      // the kernel headers' plain kernels belong to ctr.hip
 #include <algorithm>
 #include <memory>

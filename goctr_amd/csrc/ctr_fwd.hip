@@ -13,7 +13,7 @@
 
 namespace goctr {
 
-// dynamic LDS above 64 KiB needs an explicit opt-in per kernel (goctr_init -> ctr.hip: set_kernel_attributes)
+// dynamic LDS above 64 KiB needs an explicit opt-in per kernel (goctr_init -> ctr.hip: init_kernel_attrs)
 int chain_x3_fwd_attributes() {
   const void* const ks[3] = {reinterpret_cast<const void*>(ctr_chain_x3_kernel<2, true>),
                              reinterpret_cast<const void*>(ctr_chain_x3_kernel<9, true>),

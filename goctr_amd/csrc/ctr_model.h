@@ -1,12 +1,14 @@
 // ctr_model.h -- internal to the CTR translation units: the handles behind include/goctr.h (goctr_emb, goctr_dataset,
-// goctr_model) and the part of the training / forward step (ctr.hip) that the other CTR files call.  Everything else of the
-// step stays file-local in ctr.hip.
-//   ctr.hip         the step: schedules, launches, graph capture, run_steps
+// goctr_model) and the part of the training / forward step that the other CTR files call.  What only the step's own three
+// files share is in ctr_step.h; everything else of the step stays file-local.
+//   ctr.hip         the dense step: schedules, workspace, forward, backward, reduce, Adam
+//   ctr_emb.hip     the trainable-embedding step: workspace, sparse plan, the launches of emb_train.h, the exchange
+//   ctr_run.hip     the step driver: eager step, graph capture, run_steps
 //   ctr_api.hip     C ABI of models, tables, gather and datasets; the training and predict entry points
 //   ctr_multi.hip   single-call multi-device training (goctr_train_cfg::devices)
 //   serve.hip       behaviour cache, key datasets and serving (goctr_rank, goctr_batch_predict, goctr_predict_dense)
 // A translation unit other than ctr.hip defines GOCTR_NO_PLAIN_KERNELS before it includes this header: the plain kernels of
-// the kernel headers are compiled in ctr.hip only.
+// the kernel headers are compiled in ctr.hip only (those of emb_train.h, which only ctr_emb.hip includes, in ctr_emb.hip).
 #pragma once
 #include <atomic>
 #include <functional>
@@ -229,12 +231,10 @@ struct StepOpts {
   bool pipelined = false;
 };
 
-// ---------------------------------------------------------------- the step (ctr.hip)
+// ---------------------------------------------------------------- the dense step (ctr.hip)
 int init_kernel_attrs();
 int ensure_workspace(goctr_model* m, int B);
 RowSource make_source(const goctr_dataset* d, const goctr_emb* e);
-StepOpts opts_from(const goctr_train_cfg* tc);
-int check_dataset(const goctr_model* m, const goctr_dataset* d, const goctr_emb* e);
 bool chain_ok(const goctr_model* m);
 int rebuild_x3_images(goctr_model* m);
 int attn_fast_mode(const goctr_model* m, const RowSource& src, int* groups);
@@ -244,6 +244,10 @@ int launch_backward(goctr_model* m, const RowSource& src, int B, const StepOpts&
                     bool fuse_update = false, int stage = 0);
 bool serve16_ok(const goctr_model* m, const RowSource& src, int B);
 int launch_serve16(goctr_model* m, const RowSource& src, int B, const StepState* st, const FwdBufs& fb, unsigned* done, unsigned epoch);
+
+// ---------------------------------------------------------------- the step driver (ctr_run.hip)
+StepOpts opts_from(const goctr_train_cfg* tc);
+int check_dataset(const goctr_model* m, const goctr_dataset* d, const goctr_emb* e);
 int mark_weights_written(goctr_model* m);
 int run_steps(goctr_model* m, goctr_emb* emb, goctr_dataset* d, const goctr_train_cfg* tc, int n_steps);
 

@@ -47,7 +47,7 @@ struct EmbTrainArgs {
   // Data parallel (W ranks, replicated table): the mark / rank arrays are indexed OWNER-MAJOR, pidx(id) = (id % W) * Vw +
   // id / W with Vw = round_up(ceil(V / W), 4), so that the rank scan numbers the touched ids bucket after bucket
   // (owner = id % W) in ascending id order: a rank's gradient rows for owner o are one contiguous range of accum --
-  // the send buffer of the bucketed exchange (ctr.hip: launch_emb_exchange), no packing pass.  W == 1: pidx(id) == id.
+  // the send buffer of the bucketed exchange (ctr_emb.hip: launch_emb_exchange), no packing pass.  W == 1: pidx(id) == id.
   int W; long long Vw;
   long long* accum;                // [min(V, B (T+1)), D]
   float lr;

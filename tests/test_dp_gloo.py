@@ -270,7 +270,7 @@ def _emb_worker(rank, world, port, out, fixed=False):
     n = Bg // world
     sl = slice(rank * n, (rank + 1) * n)
     W, r = world, rank
-    # The device's bucketed exchange (csrc/emb_train.h + ctr.hip launch_emb_exchange), step by step in numpy:
+    # The device's bucketed exchange (csrc/emb_train.h + ctr_emb.hip launch_emb_exchange), step by step in numpy:
     #  0. local row gradients scaled by 1/B_global, 2^-44 fixed point, one accumulator row per touched id
     _, dE = m.emb_loss_grad(E, ub[sl], items[sl], uf[sl], cf[sl], y[sl])             # mean over n local rows
     dE = dE * (n / Bg)
@@ -287,7 +287,7 @@ def _emb_worker(rank, world, port, out, fixed=False):
     cnt = np.diff(off).astype(np.int32)
     assert np.all(np.diff(slot_id % W) >= 0) and all(np.all(np.diff(slot_id[off[o]:off[o + 1]]) > 0) for o in range(W))
     if fixed:
-        # Round 3, the graph-capturable form (csrc/emb_train.h, end; ctr.hip emb_exchange_*): every bucket padded to S = the
+        # Round 3, the graph-capturable form (csrc/emb_train.h, end; ctr_emb.hip emb_exchange_*): every bucket padded to S = the
         # largest bucket of any rank (ids -1, rows 0), the owners' lists to R = min(Vw, W S): uniform transfers whose sizes
         # the host knows beforehand; the counts travel in-band as the padding
         smax = torch.tensor([int(cnt.max()) if cnt.size else 0], dtype=torch.int32)
@@ -463,7 +463,7 @@ def _plan_worker(rank, world, port, out):
     W, n = world, Bg // world
     sl = slice(rank * n, (rank + 1) * n)
     per_batch = [_buckets(np.concatenate([ub[k, sl].ravel(), items[k, sl]]), V, W) for k in range(nb)]
-    # plan build: the bound is the largest bucket of ANY batch on ANY rank (ctr.hip: one all-gather of the local maxima)
+    # plan build: the bound is the largest bucket of ANY batch on ANY rank (ctr_emb.hip: one all-gather of the local maxima)
     smax = torch.tensor([max(int(np.diff(off).max()) for _, off, _ in per_batch)], dtype=torch.int32)
     dist.all_reduce(smax, op=dist.ReduceOp.MAX)
     S = max(4, -(-int(smax.item()) // 4) * 4)

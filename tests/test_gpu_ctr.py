@@ -241,7 +241,7 @@ def test_id_mode_equals_dense_mode(oracle, kind):
     assert np.max(np.abs(costs - ref)) <= COST_TOL_SMALL_SHAPES
 
 
-@pytest.mark.parametrize("steps", [7, 39])     # 4 + 2 + 1 and 16 + 16 + 4 + 2 + 1 steps per graph launch (ctr.hip run_steps)
+@pytest.mark.parametrize("steps", [7, 39])     # 4 + 2 + 1 and 16 + 16 + 4 + 2 + 1 steps per graph launch (ctr_run.hip run_steps)
 def test_graph_replay_equals_eager(oracle, steps):
     from goctr_amd import capi, model as gm
     U, T, D, Cc = 52, 10, 16, 53
