@@ -56,6 +56,20 @@ class BinaryMetrics(C.Structure):
                 ("correct", C.c_int64), ("logloss", C.c_double)]
 
 
+class GroupMetrics(C.Structure):
+    """goctr_group_metrics (include/goctr.h)"""
+    _fields_ = [("n", C.c_int64), ("k", C.c_int64), ("groups", C.c_int64), ("valid_groups", C.c_int64),
+                ("valid_rows", C.c_int64), ("pos_groups", C.c_int64), ("pair_num", C.c_uint64), ("pair_den", C.c_uint64),
+                ("pair_auc", C.c_double), ("gauc", C.c_double), ("gauc_macro", C.c_double), ("hits", C.c_int64),
+                ("hit_rate", C.c_double), ("mrr", C.c_double), ("ndcg", C.c_double)]
+
+
+class GroupStat(C.Structure):
+    """goctr_group_stat (include/goctr.h)"""
+    _fields_ = [("group", C.c_int32), ("rows", C.c_int32), ("positives", C.c_int32), ("first_pos", C.c_int32),
+                ("auc_num", C.c_uint64)]
+
+
 # every symbol include/goctr.h declares (tests/test_capi_symbols.py checks the list against the header)
 SYMBOLS = [
     "goctr_init", "goctr_init_devices", "goctr_engine_count", "goctr_engine_call_ms", "goctr_engine_select", "goctr_comm_group_enable", "goctr_device_count", "goctr_sync", "goctr_last_error", "goctr_version", "goctr_device_info",
@@ -77,7 +91,8 @@ SYMBOLS = [
     "goctr_corpus_create", "goctr_corpus_destroy", "goctr_corpus_append", "goctr_corpus_build", "goctr_corpus_info",
     "goctr_corpus_get_dictionary", "goctr_corpus_get_doc", "goctr_w2v_create_from_corpus", "goctr_w2v_use_corpus",
     "goctr_w2v_get_keep_mask", "goctr_metrics_binary", "goctr_metrics_binary_f64", "goctr_evaluate_dataset",
-    "goctr_mlp_evaluate_resident",
+    "goctr_mlp_evaluate_resident", "goctr_metrics_grouped", "goctr_metrics_grouped_f64", "goctr_evaluate_dataset_grouped",
+    "goctr_mlp_evaluate_resident_grouped",
 ]
 
 _lib = None
@@ -105,6 +120,13 @@ def load() -> C.CDLL:
         _lib.goctr_metrics_binary_f64.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64, _bm]
         _lib.goctr_evaluate_dataset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _bm]
         _lib.goctr_mlp_evaluate_resident.argtypes = [C.c_void_p, _bm]
+        _gm, _gs, _i32 = C.POINTER(GroupMetrics), C.POINTER(GroupStat), C.POINTER(C.c_int32)
+        _lib.goctr_metrics_grouped.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), _i32, C.c_int64, C.c_int, _gm, _gs,
+                                               C.c_int64]
+        _lib.goctr_metrics_grouped_f64.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), _i32, C.c_int64, C.c_int, _gm,
+                                                   _gs, C.c_int64]
+        _lib.goctr_evaluate_dataset_grouped.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _i32, C.c_int, _bm, _gm]
+        _lib.goctr_mlp_evaluate_resident_grouped.argtypes = [C.c_void_p, _i32, C.c_int, _bm, _gm]
     return _lib
 
 

@@ -759,4 +759,31 @@ int goctr_evaluate_dataset(goctr_model* m, goctr_emb* emb, goctr_dataset* d, int
   return metrics_binary_dev(m->yall.p, d->Y.p, d->rows, out, "goctr_evaluate_dataset");
 }
 
+int goctr_evaluate_dataset_grouped(goctr_model* m, goctr_emb* emb, goctr_dataset* d, int batch, const int32_t* group, int k,
+                                   goctr_binary_metrics* all, goctr_group_metrics* out) {
+  GOCTR_ENTER_H(m);
+  const char* who = "goctr_evaluate_dataset_grouped";
+  GOCTR_CHECK(m && d && out && batch > 0, "%s: bad arguments", who);
+  GOCTR_CHECK(d->has_y && d->Y.p, "%s: the dataset has no labels", who);
+  GOCTR_CHECK(group || d->users.p, "%s: group is NULL and the dataset keeps no users column (only goctr_dataset_create_keys "
+              "datasets do): pass the group of every row", who);
+  if (metrics_check_rows(d->rows, who)) return -1;
+  std::unique_lock<std::shared_mutex> lk(m->mu); ++m->gen;
+  DevBuf<int32_t> gdev;
+  const int32_t* g = d->users.p;
+  if (group) {
+    if (gdev.alloc((size_t)d->rows, false) || gdev.upload(group, (size_t)d->rows)) return -1;
+    g = gdev.p;
+  }
+  // one predict (goctr_predict_dataset's scoring, left in m->yall), both pipelines; nothing is written unless both succeed
+  if (predict_batches(m, emb, d, batch, 0, cdiv(d->rows, batch), true, nullptr)) return -1;
+  goctr_binary_metrics pooled;
+  goctr_group_metrics grouped;
+  if (all && metrics_binary_dev(m->yall.p, d->Y.p, d->rows, &pooled, who)) return -1;
+  if (metrics_grouped_dev(m->yall.p, d->Y.p, g, d->rows, k, &grouped, nullptr, 0, who)) return -1;
+  if (all) *all = pooled;
+  *out = grouped;
+  return 0;
+}
+
 }  // extern "C"

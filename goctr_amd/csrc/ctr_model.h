@@ -48,6 +48,8 @@ struct goctr_dataset {
   // ids
   DevBuf<int32_t> ub_ids, item_ids; DevBuf<float> ufeat, cfeat; int U = 0, C = 0, T = 0;
   DevBuf<float> Y;
+  DevBuf<int32_t> users;     // the key datasets' user of every row (goctr_dataset_create_keys): the default grouping of
+                             // goctr_evaluate_dataset_grouped; empty otherwise
   // single-call multi-device training: shards[r] (on engine r, owned) holds rank r's rows of every global batch of shard_B rows,
   // batch-major, the short last batch zero-padded (model.go:357-371) -- local batch k of rank r = rows [r, r+1) * shard_B / n of
   // global batch k

@@ -1,4 +1,5 @@
-// metrics.h -- interface of metrics.hip (exact binary ROC-AUC, accuracy and log-loss of scores resident on the device).
+// metrics.h -- interface of metrics.hip (exact binary ROC-AUC, accuracy and log-loss of scores resident on the device) and of
+// metrics_group.hip (the per-group ranking metrics over the same scores), and the device helpers the two pipelines share.
 #pragma once
 #include <cstdint>
 
@@ -15,7 +16,53 @@ int metrics_binary_dev(const float* score, const float* y, int64_t n, goctr_bina
 int metrics_binary_dev(const double* score, const double* y, int64_t n, goctr_binary_metrics* out, const char* who);
 int metrics_binary_dev(const double* score, const float* y, int64_t n, goctr_binary_metrics* out, const char* who);
 
+// Per-group ranking metrics (metrics_group.hip) of scores, labels and group ids already in device memory of the calling
+// thread's engine; k = 1 .. 256.  per_group (HOST, may be null): the first min(groups, cap) goctr_group_stat in ascending group
+// id.  Fills *out (and per_group) only on success; a NaN score or a negative group id fails the call.  The same three
+// instantiations as above (goctr_metrics_grouped / goctr_evaluate_dataset_grouped, goctr_metrics_grouped_f64,
+// goctr_mlp_evaluate_resident_grouped).
+int metrics_grouped_dev(const float* score, const float* y, const int32_t* group, int64_t n, int k, goctr_group_metrics* out,
+                        goctr_group_stat* per_group, int64_t cap, const char* who);
+int metrics_grouped_dev(const double* score, const double* y, const int32_t* group, int64_t n, int k, goctr_group_metrics* out,
+                        goctr_group_stat* per_group, int64_t cap, const char* who);
+int metrics_grouped_dev(const double* score, const float* y, const int32_t* group, int64_t n, int k, goctr_group_metrics* out,
+                        goctr_group_stat* per_group, int64_t cap, const char* who);
+
 // the row-count check every metrics entry point makes (0 < n < 2^31)
 int metrics_check_rows(int64_t n, const char* who);
+
+// correctly rounded num / den (num <= den, den > 0) in 128-bit integer arithmetic (metrics.hip)
+double div_rounded(uint64_t num, uint64_t den);
+
+#ifdef __HIPCC__
+namespace {
+
+constexpr int MB = 256;                 // threads per workgroup of every metrics kernel
+constexpr int MKEY_MAX_BLOCKS = 2048;   // grid-stride kernels over rows / groups run with at most this many workgroups
+
+// score bits -> order-preserving unsigned key: larger score -> larger key; subnormals and +-inf keep their place
+__device__ __forceinline__ unsigned int score_key(float s, bool* nan) {
+  unsigned int b = __float_as_uint(s);
+  *nan = (b & 0x7fffffffu) > 0x7f800000u;
+  if (b == 0x80000000u) b = 0u;                          // -0 ties with +0
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ unsigned long long score_key(double s, bool* nan) {
+  unsigned long long b = (unsigned long long)__double_as_longlong(s);
+  *nan = (b & 0x7fffffffffffffffull) > 0x7ff0000000000000ull;
+  if (b == 0x8000000000000000ull) b = 0ull;
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+// the wavefront's sum in a fixed order (lane tree); valid in lane 0
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;
+}
+
+}  // namespace
+#endif
 
 }  // namespace goctr

@@ -36,38 +36,15 @@
 namespace goctr {
 namespace {
 
-constexpr int MB = 256;                 // threads per workgroup of every metrics kernel
-constexpr int MKEY_MAX_BLOCKS = 2048;   // key build / terms: grid-stride over the rows with at most this many workgroups
-
 struct MetricsPart { unsigned long long pos, correct, nan; double ll; };
 // what the host reads back: P / G from the scans' totals, S from the terms, the rest from the key build's partials
 struct MetricsRes { unsigned long long P, G, S, pos, correct, nan; double ll; };
-
-__device__ __forceinline__ unsigned int score_key(float s, bool* nan) {
-  unsigned int b = __float_as_uint(s);
-  *nan = (b & 0x7fffffffu) > 0x7f800000u;
-  if (b == 0x80000000u) b = 0u;                          // -0 ties with +0
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);     // larger score -> larger key; subnormals and +-inf keep their place
-}
-__device__ __forceinline__ unsigned long long score_key(double s, bool* nan) {
-  unsigned long long b = (unsigned long long)__double_as_longlong(s);
-  *nan = (b & 0x7fffffffffffffffull) > 0x7ff0000000000000ull;
-  if (b == 0x8000000000000000ull) b = 0ull;
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
 
 // utils.Accuracy32: math.Round(float64(p - y)) == 0 with p - y in float32, i.e. |fl32(p - y)| < 0.5 (NaN: no hit); utils.Accuracy
 // (and the MLP's float64 head) take the difference in float64
 __device__ __forceinline__ bool hit(float p, float y) { const float d = p - y; return fabsf(d) < 0.5f; }
 __device__ __forceinline__ bool hit(double p, double y) { return fabs(p - y) < 0.5; }
 __device__ __forceinline__ bool hit(double p, float y) { return fabs(p - (double)y) < 0.5; }
-
-template <class T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
 
 // the workgroup's sums in a fixed order (lane tree, then the waves in order); valid in thread 0
 __device__ __forceinline__ MetricsPart block_sum(MetricsPart v) {
@@ -206,21 +183,6 @@ int ensure_ws(MetricsWs& w, int64_t n, size_t kb, size_t temp_bytes, const char*
   return 0;
 }
 
-// correctly rounded num / den (num <= den, den > 0) in 128-bit integer arithmetic
-double div_rounded(uint64_t num, uint64_t den) {
-  if (num == 0) return 0.0;
-  const int k = 64 + __builtin_clzll(num);             // num << k has its top bit at 127: the quotient has 64 .. 128 bits
-  const unsigned __int128 a = (unsigned __int128)num << k;
-  const unsigned __int128 q = a / den, r = a % den;
-  const uint64_t hi = (uint64_t)(q >> 64);
-  const int bits = hi ? 128 - __builtin_clzll(hi) : 64 - __builtin_clzll((uint64_t)q);
-  const int drop = bits - 53;                          // >= 11
-  unsigned __int128 mant = q >> drop;
-  const unsigned __int128 rest = q & (((unsigned __int128)1 << drop) - 1), half = (unsigned __int128)1 << (drop - 1);
-  if (rest > half || (rest == half && (r != 0 || (mant & 1)))) ++mant;   // to nearest, ties to even
-  return std::ldexp((double)(uint64_t)mant, drop - k);
-}
-
 template <class TS, class TL>
 int run(const TS* score, const TL* y, int64_t n, goctr_binary_metrics* out, const char* who, const TS* host_score = nullptr,
         const TL* host_y = nullptr) {
@@ -287,6 +249,21 @@ int run(const TS* score, const TL* y, int64_t n, goctr_binary_metrics* out, cons
 }
 
 }  // namespace
+
+// correctly rounded num / den (num <= den, den > 0) in 128-bit integer arithmetic
+double div_rounded(uint64_t num, uint64_t den) {
+  if (num == 0) return 0.0;
+  const int k = 64 + __builtin_clzll(num);             // num << k has its top bit at 127: the quotient has 64 .. 128 bits
+  const unsigned __int128 a = (unsigned __int128)num << k;
+  const unsigned __int128 q = a / den, r = a % den;
+  const uint64_t hi = (uint64_t)(q >> 64);
+  const int bits = hi ? 128 - __builtin_clzll(hi) : 64 - __builtin_clzll((uint64_t)q);
+  const int drop = bits - 53;                          // >= 11
+  unsigned __int128 mant = q >> drop;
+  const unsigned __int128 rest = q & (((unsigned __int128)1 << drop) - 1), half = (unsigned __int128)1 << (drop - 1);
+  if (rest > half || (rest == half && (r != 0 || (mant & 1)))) ++mant;   // to nearest, ties to even
+  return std::ldexp((double)(uint64_t)mant, drop - k);
+}
 
 int metrics_check_rows(int64_t n, const char* who) {
   GOCTR_CHECK(n > 0 && n < (int64_t(1) << 31), "%s: n = %lld rows (1 .. 2^31 - 1 are accepted)", who, (long long)n);

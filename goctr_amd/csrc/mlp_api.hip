@@ -267,4 +267,28 @@ int goctr_mlp_evaluate_resident(goctr_mlp* p, goctr_binary_metrics* out) {
   return metrics_binary_dev(score.p, p->Yr.p, p->rows, out, "goctr_mlp_evaluate_resident");
 }
 
+int goctr_mlp_evaluate_resident_grouped(goctr_mlp* p, const int32_t* group, int k, goctr_binary_metrics* all,
+                                        goctr_group_metrics* out) {
+  GOCTR_ENTER_H(p);
+  const char* who = "goctr_mlp_evaluate_resident_grouped";
+  GOCTR_CHECK(p && group && out, "%s: bad arguments", who);
+  GOCTR_CHECK(p->rows > 0, "%s: upload rows first", who);
+  GOCTR_CHECK(p->units[p->nl] == 1 && p->cfg.out_activation != GOCTR_OUT_SOFTMAX,
+              "%s: binary metrics need a single-output head (this one has %d output units%s)", who, p->units[p->nl],
+              p->cfg.out_activation == GOCTR_OUT_SOFTMAX ? ", softmax" : "");
+  if (metrics_check_rows(p->rows, who)) return -1;
+  std::lock_guard<std::mutex> lk(p->mu);
+  DevBuf<double> score;
+  DevBuf<int32_t> gdev;
+  if (gdev.alloc((size_t)p->rows, false) || gdev.upload(group, (size_t)p->rows)) return -1;
+  if (score.alloc((size_t)p->rows, false) || predict_resident64(p, score.p)) return -1;
+  goctr_binary_metrics pooled;
+  goctr_group_metrics grouped;
+  if (all && metrics_binary_dev(score.p, p->Yr.p, p->rows, &pooled, who)) return -1;
+  if (metrics_grouped_dev(score.p, p->Yr.p, gdev.p, p->rows, k, &grouped, nullptr, 0, who)) return -1;
+  if (all) *all = pooled;
+  *out = grouped;
+  return 0;
+}
+
 }  // extern "C"

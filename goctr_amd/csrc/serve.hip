@@ -145,7 +145,8 @@ int goctr_dataset_create_keys(goctr_ubcache* c, const float* user_table, int64_t
   GOCTR_CHECK((U == 0 || user_table) && (C == 0 || item_table), "goctr_dataset_create_keys: feature table missing");
   std::unique_ptr<goctr_dataset> d(new goctr_dataset);
   d->id_mode = true; d->rows = rows; d->U = U; d->C = C; d->T = T;
-  DevBuf<float> dut, dit; DevBuf<int32_t> du; DevBuf<long long> dts;
+  DevBuf<float> dut, dit; DevBuf<long long> dts;
+  DevBuf<int32_t>& du = d->users;      // stays resident: the rows' groups for goctr_evaluate_dataset_grouped
   std::vector<long long> t(rows, 0);
   if (ts) for (int64_t i = 0; i < rows; ++i) t[i] = ts[i];
   if (dut.alloc((size_t)n_users * U, false) || (U && dut.upload(user_table, (size_t)n_users * U))) return -1;

@@ -84,6 +84,30 @@ inline goctr_binary_metrics BinaryMetrics(const double* score, const double* y, 
   check(goctr_metrics_binary_f64(score, y, n, &m));
   return m;
 }
+// per-group (per-user) ranking metrics (goctr_metrics_grouped): GAUC -- the figure the reference's README quotes and its code never
+// computes --, the exact same-group pair AUC, HitRate@k, NDCG@k, MRR.  perGroup (may be null): every group's goctr_group_stat
+inline goctr_group_metrics GroupedMetrics(const float* score, const float* y, const int32_t* group, int64_t n, int k = 10,
+                                          std::vector<goctr_group_stat>* perGroup = nullptr) {
+  ensure_init();
+  goctr_group_metrics m{};
+  if (perGroup) perGroup->resize((size_t)std::max<int64_t>(n, 1));
+  check(goctr_metrics_grouped(score, y, group, n, k, &m, perGroup ? perGroup->data() : nullptr, perGroup ? n : 0));
+  if (perGroup) perGroup->resize((size_t)m.groups);
+  return m;
+}
+inline goctr_group_metrics GroupedMetrics(const double* score, const double* y, const int32_t* group, int64_t n, int k = 10,
+                                          std::vector<goctr_group_stat>* perGroup = nullptr) {
+  ensure_init();
+  goctr_group_metrics m{};
+  if (perGroup) perGroup->resize((size_t)std::max<int64_t>(n, 1));
+  check(goctr_metrics_grouped_f64(score, y, group, n, k, &m, perGroup ? perGroup->data() : nullptr, perGroup ? n : 0));
+  if (perGroup) perGroup->resize((size_t)m.groups);
+  return m;
+}
+inline double GAUC(const std::vector<float>& pred, const std::vector<float>& y, const std::vector<int32_t>& users) {
+  if (y.size() != pred.size() || users.size() != pred.size()) throw std::invalid_argument("GAUC: pred, y and users differ in length");
+  return GroupedMetrics(pred.data(), y.data(), users.data(), (int64_t)pred.size()).gauc;
+}
 inline float RocAuc32(const std::vector<float>& pred, const std::vector<float>& y) {
   return BinaryMetrics(pred.data(), y.data(), (int64_t)pred.size()).auc32;
 }
@@ -175,6 +199,14 @@ inline std::vector<float> Predict(CtrNet& m, int numExamples, int batchSize, con
 inline goctr_binary_metrics EvaluateDataset(CtrNet& m, goctr_dataset* d, int batchSize, goctr_emb* emb = nullptr) {
   goctr_binary_metrics r{};
   check(goctr_evaluate_dataset(m.Vm(), emb, d, batchSize, &r));
+  return r;
+}
+// the same scores grouped by group [rows] (null: the users a goctr_dataset_create_keys dataset keeps resident); all (may be
+// null): also EvaluateDataset's pooled metrics of the same predict (goctr_evaluate_dataset_grouped)
+inline goctr_group_metrics EvaluateDatasetGrouped(CtrNet& m, goctr_dataset* d, int batchSize, const int32_t* group = nullptr,
+                                                  int k = 10, goctr_emb* emb = nullptr, goctr_binary_metrics* all = nullptr) {
+  goctr_group_metrics r{};
+  check(goctr_evaluate_dataset_grouped(m.Vm(), emb, d, batchSize, group, k, all, &r));
   return r;
 }
 }  // namespace model
@@ -298,6 +330,12 @@ class MLPClassifier {
   goctr_binary_metrics EvaluateResident() {
     goctr_binary_metrics r{};
     check(goctr_mlp_evaluate_resident(h_, &r));
+    return r;
+  }
+  // the same scores grouped by group [resident rows] (goctr_mlp_evaluate_resident_grouped)
+  goctr_group_metrics EvaluateResidentGrouped(const int32_t* group, int k = 10, goctr_binary_metrics* all = nullptr) {
+    goctr_group_metrics r{};
+    check(goctr_mlp_evaluate_resident_grouped(h_, group, k, all, &r));
     return r;
   }
 

@@ -222,6 +222,7 @@ class _BaseMLP:
         pp = np.ascontiguousarray(perm, np.int32) if perm is not None else None
         capi.check(capi.load().goctr_mlp_fit(self._h, capi.ptr(X, C.c_float), capi.ptr(Y, C.c_float), C.c_int64(rows),
                                              capi.ptr(pp, C.c_int32), capi.ptr(curve, C.c_double), C.byref(ran)))
+        self._resident_rows = rows
         return self._fitted(curve, ran.value)
 
     def _fitted(self, curve, ran):
@@ -249,6 +250,22 @@ class _BaseMLP:
         capi.check(capi.load().goctr_mlp_evaluate_resident(self._h, C.byref(out)))
         return BinaryMetrics.from_c(out)
 
+    def EvaluateResidentGrouped(self, group, k=10, pooled=False):
+        """EvaluateResident's scores grouped by group [resident rows] (goctr_mlp_evaluate_resident_grouped): a
+        metrics.GroupMetrics, or (BinaryMetrics, GroupMetrics) with pooled=True.  Single-output heads only."""
+        from .metrics import BinaryMetrics, GroupMetrics
+        out, allm = capi.GroupMetrics(), capi.BinaryMetrics()
+        g = np.ascontiguousarray(group, np.int32).ravel()
+        rows = getattr(self, "_resident_rows", None)
+        if rows is None:
+            raise ValueError("EvaluateResidentGrouped: upload() the rows first (the group column is matched against them)")
+        if g.size != rows:
+            raise ValueError(f"{rows} resident rows but {g.size} group ids")
+        capi.check(capi.load().goctr_mlp_evaluate_resident_grouped(self._h, capi.ptr(g, C.c_int32), C.c_int(k),
+                                                                   C.byref(allm) if pooled else None, C.byref(out)))
+        gm = GroupMetrics.from_c(out)
+        return (BinaryMetrics.from_c(allm), gm) if pooled else gm
+
     def _predict64(self, X):
         """predictProbas (basemlp64.go:897-913) in float64: the head's values"""
         X = capi.f32(X)
@@ -270,6 +287,7 @@ class _BaseMLP:
         Y = capi.f32(Y).reshape(X.shape[0], -1)
         capi.check(capi.load().goctr_mlp_upload(self._h, capi.ptr(X, C.c_float), capi.ptr(Y, C.c_float),
                                                 C.c_int64(X.shape[0])))
+        self._resident_rows = X.shape[0]
 
     def train_steps(self, n_steps, first_batch=0):
         capi.check(capi.load().goctr_mlp_train_steps(self._h, C.c_int64(first_batch), C.c_int(n_steps)))

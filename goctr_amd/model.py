@@ -456,6 +456,21 @@ def evaluate_dataset(m: _CtrNet, ds: Dataset, batch, emb: EmbeddingTable | None 
     return BinaryMetrics.from_c(out)
 
 
+def evaluate_dataset_grouped(m: _CtrNet, ds: Dataset, batch, group=None, k=10, emb: EmbeddingTable | None = None,
+                             pooled=False):
+    """predict_dataset's scores, left on the device, grouped by `group` (the user of every row) against the resident labels
+    (goctr_evaluate_dataset_grouped): a metrics.GroupMetrics.  group=None: the users a Dataset.keys dataset keeps resident.
+    pooled=True: also evaluate_dataset's BinaryMetrics of the same scores -- returns (BinaryMetrics, GroupMetrics)."""
+    from .metrics import BinaryMetrics, GroupMetrics, group_ids
+    out, allm = capi.GroupMetrics(), capi.BinaryMetrics()
+    g = None if group is None else group_ids(group, ds.rows)
+    capi.check(capi.load().goctr_evaluate_dataset_grouped(m._h, emb._h if emb else None, ds._h, C.c_int(batch),
+                                                          capi.ptr(g, C.c_int32), C.c_int(k),
+                                                          C.byref(allm) if pooled else None, C.byref(out)))
+    gm = GroupMetrics.from_c(out)
+    return (BinaryMetrics.from_c(allm), gm) if pooled else gm
+
+
 def predict_steps(m: _CtrNet, ds: Dataset, batch, n_batches, first_batch=0, emb: EmbeddingTable | None = None):
     capi.check(capi.load().goctr_predict_steps(m._h, emb._h if emb else None, ds._h, C.c_int(batch),
                                                C.c_int64(first_batch), C.c_int(n_batches)))

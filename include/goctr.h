@@ -479,6 +479,51 @@ int goctr_evaluate_dataset(goctr_model* m, goctr_emb* emb, goctr_dataset* d, int
  * resident Y; single-output heads only (a softmax head is refused) */
 int goctr_mlp_evaluate_resident(goctr_mlp* p, goctr_binary_metrics* out);
 
+/* ---------------------------------------------------------------- per-group ranking metrics on the device
+ * The figure the reference's README quotes per model is GAUC (README.md:17,25,33), the per-user AUC of the DIN paper; its code
+ * has none (every example ends in the pooled utils.RocAuc32, utils/util.go:131-148).  These calls stand in for that missing
+ * evaluation, and for judging what Rank serves (one user, n candidates, recommend/rcmd.go:248-275): GAUC, HitRate@k, NDCG@k
+ * and MRR of one column of scores, grouped by an int32 key (the user of each row; any key >= 0).
+ * Rows, labels, ties and NaN scores as in goctr_metrics_binary; a negative group id fails the call the same way (-1, *out
+ * untouched).  Inside a group the rows are ordered by (score descending, row index ascending); rank = 0-based position.
+ * Per group u with n_u rows, P_u positives, N_u = n_u - P_u:  S_u = sum over its threshold groups of neg_g (2 P_above_g + pos_g)
+ * (the integer of goctr_binary_metrics restricted to u), auc_u = S_u / (2 P_u N_u); u is VALID iff 0 < P_u < n_u;
+ * first_u = rank of its first positive (-1: none); DCG_u@k = sum of d[rank] over the positives with rank < k,
+ * IDCG_u@k = sum of d[r], r < min(k, P_u), d[r] = 1 / log2(r + 2).  A mean over an empty set is NaN.  1 <= k <= 256. */
+typedef struct {
+  int64_t  n, k;
+  int64_t  groups, valid_groups, valid_rows;     /* valid_rows = sum of n_u over the valid groups */
+  int64_t  pos_groups;                           /* groups with P_u > 0 */
+  uint64_t pair_num, pair_den;                   /* sum of S_u / of 2 P_u N_u over the valid groups (< 2^62) */
+  double   pair_auc;                             /* pair_num / pair_den correctly rounded: the share of correctly ordered
+                                                    (positive, negative) pairs of the same group, ties one half */
+  double   gauc;                                 /* sum over valid u of n_u auc_u / valid_rows (DIN's impression-weighted GAUC) */
+  double   gauc_macro;                           /* sum over valid u of auc_u / valid_groups */
+  int64_t  hits;                                 /* groups with 0 <= first_u < k */
+  double   hit_rate;                             /* hits / pos_groups */
+  double   mrr;                                  /* sum over P_u > 0 of 1 / (first_u + 1) / pos_groups */
+  double   ndcg;                                 /* sum over P_u > 0 of DCG_u@k / IDCG_u@k / pos_groups */
+} goctr_group_metrics;
+typedef struct {
+  int32_t  group, rows, positives, first_pos;    /* first_pos = first_u */
+  uint64_t auc_num;                              /* S_u (0 when the group is not valid); auc_u = auc_num / (2 P_u N_u) */
+} goctr_group_stat;
+
+/* host arrays score [n], y [n], group [n] (copied to the device).  per_group (may be NULL): the first min(out->groups, cap)
+ * groups in ascending id; out->groups tells whether that was all of them */
+int goctr_metrics_grouped(const float* score, const float* y, const int32_t* group, int64_t n, int k,
+                          goctr_group_metrics* out, goctr_group_stat* per_group, int64_t cap);
+int goctr_metrics_grouped_f64(const double* score, const double* y, const int32_t* group, int64_t n, int k,
+                              goctr_group_metrics* out, goctr_group_stat* per_group, int64_t cap);
+/* goctr_predict_dataset's scores, left on the device, against d's resident labels.  group: host [rows], or NULL for a dataset
+ * made by goctr_dataset_create_keys, which keeps its `users` column resident (4 bytes per row).  all (may be NULL): also the
+ * pooled metrics goctr_evaluate_dataset returns, of the same scores (one predict, both pipelines) */
+int goctr_evaluate_dataset_grouped(goctr_model* m, goctr_emb* emb, goctr_dataset* d, int batch, const int32_t* group, int k,
+                                   goctr_binary_metrics* all, goctr_group_metrics* out);
+/* goctr_mlp_evaluate_resident's scores grouped by group [resident rows] (host); all as above */
+int goctr_mlp_evaluate_resident_grouped(goctr_mlp* p, const int32_t* group, int k, goctr_binary_metrics* all,
+                                        goctr_group_metrics* out);
+
 #ifdef __cplusplus
 }
 #endif
