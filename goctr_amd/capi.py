@@ -87,6 +87,8 @@ SYMBOLS = [
     "goctr_w2v_get_paths", "goctr_huffman_build", "goctr_w2v_train", "goctr_w2v_upload_doc", "goctr_w2v_shard_cuts", "goctr_w2v_train_resident",
     "goctr_w2v_export_f32", "goctr_searcher_create", "goctr_searcher_destroy", "goctr_searcher_search",
     "goctr_ubcache_create", "goctr_ubcache_destroy", "goctr_ubcache_get", "goctr_dataset_create_keys", "goctr_dataset_get_ids",
+    "goctr_ubcache_batch_set", "goctr_ubcache_delete", "goctr_ubcache_clear", "goctr_ubcache_append", "goctr_ubcache_info",
+    "goctr_ubcache_export",
     "goctr_recsys_create", "goctr_recsys_destroy", "goctr_batch_predict", "goctr_rank",
     "goctr_corpus_create", "goctr_corpus_destroy", "goctr_corpus_append", "goctr_corpus_build", "goctr_corpus_info",
     "goctr_corpus_get_dictionary", "goctr_corpus_get_doc", "goctr_w2v_create_from_corpus", "goctr_w2v_use_corpus",
@@ -127,6 +129,13 @@ def load() -> C.CDLL:
                                                    _gs, C.c_int64]
         _lib.goctr_evaluate_dataset_grouped.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _i32, C.c_int, _bm, _gm]
         _lib.goctr_mlp_evaluate_resident_grouped.argtypes = [C.c_void_p, _i32, C.c_int, _bm, _gm]
+        _i64 = C.POINTER(C.c_int64)
+        _lib.goctr_ubcache_batch_set.argtypes = [C.c_void_p, C.c_int64, _i32, _i64, _i32, _i64]
+        _lib.goctr_ubcache_delete.argtypes = [C.c_void_p, C.c_int64, _i32]
+        _lib.goctr_ubcache_clear.argtypes = [C.c_void_p]
+        _lib.goctr_ubcache_append.argtypes = [C.c_void_p, C.c_int64, _i32, _i32, _i64, C.c_int64]
+        _lib.goctr_ubcache_info.argtypes = [C.c_void_p, _i64, _i64, C.POINTER(C.c_uint64)]
+        _lib.goctr_ubcache_export.argtypes = [C.c_void_p, _i64, _i32, _i64]
     return _lib
 
 

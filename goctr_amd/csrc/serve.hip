@@ -10,16 +10,12 @@
 #include <shared_mutex>
 
 #include "ctr_model.h"
+#include "ubcache.h"
 
 // ------------------------------------------------------------------ device-side sample assembly
 // ubcache.UserBehaviorCache (feature/ubcache/cache.go) as a CSR in HBM + the per-sample gather of GetSampleVector
 // (recommend/rcmd.go:460-536) as one kernel: keys (user, item, timestamp) -> behaviour ids, user / item feature rows.
-struct goctr_ubcache {
-  goctr::Engine* const eng = &goctr::engine();   // the engine (device, streams, arena) the handle was created on
-  int64_t n_users = 0, nnz = 0;
-  DevBuf<long long> off, ts;
-  DevBuf<int32_t> items;
-};
+// (the handle: ubcache.h; its updates -- BatchSet / Delete / Clear / Append -- live in ubcache.hip)
 
 namespace {
 // TimeSeq.Filter (cache.go:71-94) for one key: the sequence is newest-first, so "the first i with Ts[i] <= maxTs"
@@ -113,10 +109,15 @@ int goctr_ubcache_create(int64_t n_users, const int64_t* off, const int32_t* ite
   if (c->off.alloc(o.size(), false) || c->off.upload(o.data(), o.size())) return -1;
   if (c->items.alloc((size_t)nnz, false) || (nnz && c->items.upload(items, (size_t)nnz))) return -1;
   if (c->ts.alloc((size_t)nnz, false) || (nnz && c->ts.upload(t.data(), (size_t)nnz))) return -1;
+  GOCTR_HIP(hipStreamCreateWithFlags(&c->ustream, hipStreamNonBlocking));
   *out = c.release();
   return 0;
 }
-void goctr_ubcache_destroy(goctr_ubcache* c) { delete c; }
+void goctr_ubcache_destroy(goctr_ubcache* c) {
+  if (!c) return;
+  EngineScope on(c->eng);
+  delete c;
+}
 
 int goctr_ubcache_get(goctr_ubcache* c, const int32_t* users, const int64_t* max_ts, int64_t rows, int T, int32_t* out_ids) {
   GOCTR_ENTER_H(c);
@@ -126,12 +127,15 @@ int goctr_ubcache_get(goctr_ubcache* c, const int32_t* users, const int64_t* max
   if (max_ts) for (int64_t i = 0; i < rows; ++i) t[i] = max_ts[i];
   if (du.alloc(rows, false) || du.upload(users, rows) || dts.alloc(rows, false) || dts.upload(t.data(), rows) ||
       dout.alloc((size_t)rows * T, false)) return -1;
+  UbRead image(c, engine().stream);                   // until the download's synchronisation
   hipLaunchKernelGGL(assemble_keys_kernel, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, engine().stream, c->off.p, c->items.p,
                      c->ts.p, (long long)c->n_users, (const float*)nullptr, 0, (const float*)nullptr, 0LL, 0, du.p,
                      (const int32_t*)nullptr, dts.p, (long long)rows, T, dout.p, (float*)nullptr, (float*)nullptr,
                      (int32_t*)nullptr, (unsigned char*)nullptr);
   GOCTR_HIP(hipGetLastError());
-  return dout.download(out_ids, (size_t)rows * T);
+  if (dout.download(out_ids, (size_t)rows * T)) return -1;
+  image.done();
+  return 0;
 }
 
 int goctr_dataset_create_keys(goctr_ubcache* c, const float* user_table, int64_t n_users, int U, const float* item_table,
@@ -154,11 +158,13 @@ int goctr_dataset_create_keys(goctr_ubcache* c, const float* user_table, int64_t
   if (du.alloc(rows, false) || du.upload(users, rows) || dts.alloc(rows, false) || dts.upload(t.data(), rows)) return -1;
   if (d->ub_ids.alloc((size_t)rows * T, false) || d->item_ids.alloc(rows, false) || d->item_ids.upload(items, rows)) return -1;
   if (d->ufeat.alloc((size_t)rows * U, false) || d->cfeat.alloc((size_t)rows * C, false)) return -1;
+  UbRead image(c, engine().stream);
   hipLaunchKernelGGL(assemble_keys_kernel, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, engine().stream, c->off.p, c->items.p,
                      c->ts.p, (long long)c->n_users, dut.p, U, dit.p, (long long)n_items, C, du.p, d->item_ids.p, dts.p,
                      (long long)rows, T, d->ub_ids.p, d->ufeat.p, d->cfeat.p, (int32_t*)nullptr, (unsigned char*)nullptr);
   GOCTR_HIP(hipGetLastError());
   GOCTR_HIP(hipStreamSynchronize(engine().stream));   // the temporaries above are released on return
+  image.done();
   if (Y) { if (d->Y.alloc(rows, false) || d->Y.upload(Y, rows)) return -1; d->has_y = true; }
   *out = d.release();
   return 0;
@@ -410,7 +416,8 @@ int serve_keys_pass(goctr_model* m, goctr_recsys* r, ServeSlot* s, KeySeg* const
   const int32_t* dit = reinterpret_cast<const int32_t*>(in_base + 12 * N);
   float* dscore = reinterpret_cast<float*>(out_base);
   unsigned char* dfail = reinterpret_cast<unsigned char*>(out_base + 4 * Br);
-  const goctr_ubcache* c = r->ub;
+  goctr_ubcache* const c = r->ub;
+  UbRead image(c, s->stream);                         // one pass, one image of the cache: held until the wait below
   StreamScope on_slot(s->stream);
   RowSource src{};
   src.rows = N; src.id_mode = 1; src.emb = r->emb->rows.p; src.V = r->emb->V;
@@ -463,6 +470,7 @@ int serve_keys_pass(goctr_model* m, goctr_recsys* r, ServeSlot* s, KeySeg* const
     }
   }
   if (!stamped) GOCTR_HIP(hipStreamSynchronize(s->stream));
+  image.done();
   const float* hs = reinterpret_cast<const float*>(s->h_out);
   const unsigned char* hf = reinterpret_cast<const unsigned char*>(s->h_out + 4 * Br);
   o = 0;

@@ -236,6 +236,22 @@ class RecSys {
   goctr_recsys* handle() const { return h_; }
   goctr_emb* embedding() const { return emb_; }
 
+  // UserBehaviorCache.Set / BatchSet / Delete / Clear (feature/ubcache/cache.go:27-55) on the live cache: users are dense user
+  // indices, `off` a CSR over `users` (each sequence timestamp-descending).  Any thread, beside BatchPredict / Rank calls;
+  // the next serving pass sees the whole update.
+  void BatchSet(const std::vector<int32_t>& users, const std::vector<int64_t>& off, const std::vector<int32_t>& items,
+                const std::vector<int64_t>& ts) {
+    check(goctr_ubcache_batch_set(ub_, (int64_t)users.size(), users.data(), off.data(), items.data(), ts.data()));
+  }
+  void Delete(const std::vector<int32_t>& users) { check(goctr_ubcache_delete(ub_, (int64_t)users.size(), users.data())); }
+  void Clear() { check(goctr_ubcache_clear(ub_)); }
+  // no reference counterpart: events (user, item, ts) in any order, merged into the users' sequences; maxLen > 0 keeps the
+  // newest maxLen entries of every touched user
+  void Append(const std::vector<int32_t>& users, const std::vector<int32_t>& items, const std::vector<int64_t>& ts,
+              int64_t maxLen = 0) {
+    check(goctr_ubcache_append(ub_, (int64_t)users.size(), users.data(), items.data(), ts.data(), maxLen));
+  }
+
  private:
   goctr_ubcache* ub_ = nullptr; goctr_emb* emb_ = nullptr; goctr_recsys* h_ = nullptr;
 };

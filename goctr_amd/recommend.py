@@ -161,6 +161,41 @@ class DeviceRecSys:
             dense.Set(u, TimeSeq(list(seq.Ts), [self._iidx.get(int(i), -1) for i in seq.Items]))
         self._dense_cache = dense
         assert dense.user_index() == {u: k for u, k in self._uidx.items() if k < len(dense.ub)}
+        dense._borrowed = True          # the goctr_recsys borrows this image's handle: it is updated in place, never rebuilt
+
+    # ---- "the user just clicked something": the behaviour cache of a recSys that is serving, updated in place
+    # (goctr_ubcache_batch_set / _delete / _append); the next BatchPredict / Rank through this object sees the new sequences
+    def _check_users(self, userIds):
+        if self.ubcache is None:
+            raise RuntimeError("this recSys has no behaviour cache (it does not implement UserBehavior, rcmd.go:512)")
+        for u in userIds:
+            if int(u) not in self._dense_cache._users:
+                raise KeyError(f"user {u} is not known to this recSys (its user table is fixed)")
+
+    def SetUserBehavior(self, ub: dict):
+        """UserBehaviorCache.Set / BatchSet (cache.go:27-41) for users of this recSys: {userId: TimeSeq}"""
+        from .ubcache import TimeSeq
+        ub = {int(u): seq for u, seq in ub.items()}
+        self._check_users(ub)
+        self._dense_cache.BatchSet({u: TimeSeq(list(seq.Ts), [self._iidx.get(int(i), -1) for i in seq.Items])
+                                    for u, seq in ub.items()})
+        self.ubcache.BatchSet(ub)
+
+    def DeleteUserBehavior(self, userIds):
+        """UserBehaviorCache.Delete (cache.go:43-48); the users stay known to the recSys, with an empty sequence"""
+        ids = [int(u) for u in userIds]
+        self._check_users(ids)
+        self._dense_cache.DeleteMany(ids, keepEmpty=True)
+        self.ubcache.DeleteMany(ids, keepEmpty=True)
+
+    def AppendUserBehavior(self, events, maxLen=0):
+        """new behaviours merged into the users' sequences (ubcache.merge_events): ``events`` are Samples or
+        (userId, itemId, ts) triples in any order; maxLen > 0 keeps the newest maxLen entries of every touched user"""
+        ev = [(e.UserId, e.ItemId, e.Timestamp) if isinstance(e, Sample) else tuple(e) for e in events]
+        ev = [(int(u), int(i), int(t)) for u, i, t in ev]
+        self._check_users(u for u, _, _ in ev)
+        self._dense_cache.Append([(u, self._iidx.get(i, -1), t) for u, i, t in ev], maxLen)
+        self.ubcache.Append(ev, maxLen)
 
     @property
     def _ub_h(self):

@@ -4,7 +4,11 @@
     UserBehaviorCache           cache.go:16-68     Set / BatchSet / Delete / Clear / Get
     TimeSeq.Filter              cache.go:71-94
 
-Set / BatchSet / Delete / Clear edit a host dictionary; the CSR image in HBM is rebuilt lazily on the next lookup.
+Set / BatchSet / Delete / Clear edit a host dictionary.  While no device image exists that is all; once one does, an update
+whose users are all rows of the image is applied to it IN PLACE (goctr_ubcache_batch_set / _delete / _clear: the device builds
+a second CSR and swaps it in, so a goctr_recsys that borrowed the handle serves the new sequences on its next call); an update
+that brings a user the image has no row for drops the image, and the next lookup rebuilds it.  `Append` (no reference
+counterpart) merges a batch of (user, item, ts) events into the users' sequences -- `merge_events` spells the rule out.
 `Get` answers one key like the reference; `get_batch` answers many keys per call (goctr_ubcache_get) and
 `model.Dataset.keys` assembles a whole training set on the device (goctr_dataset_create_keys) -- the replacement for
 the per-sample gather of recommend.GetSample / GetSampleVector (rcmd.go:339-536).
@@ -26,38 +30,124 @@ class TimeSeq:
     Items: list = field(default_factory=list)
 
 
+def merge_events(seq: TimeSeq, events, maxLen=0) -> TimeSeq:
+    """What Append does to ONE user's sequence.  ``events``: that user's (item, ts) pairs in call order.
+    1. the events in reverse call order in front of the old sequence; 2. stable sort by timestamp, descending;
+    3. keep the first maxLen entries if maxLen > 0.  So on equal timestamps a new event precedes the old entries and a later
+    event of the call an earlier one; nothing is de-duplicated."""
+    items = [int(i) for i, _ in reversed(events)] + [int(i) for i in seq.Items]
+    ts = [int(t) for _, t in reversed(events)] + [int(t) for t in seq.Ts]
+    order = sorted(range(len(ts)), key=lambda k: -ts[k])            # (sorted is stable)
+    if maxLen > 0:
+        order = order[:maxLen]
+    return TimeSeq([ts[k] for k in order], [items[k] for k in order])
+
+
 class UserBehaviorCache:
     def __init__(self):
         self.ub = {}
         self._h = None
         self._users = None      # user id -> dense row of the CSR
+        self._stale = False     # an in-place Delete / Clear left rows whose users the dictionary no longer has
+        self._borrowed = False  # a goctr_recsys holds the handle: the image must never be dropped (recommend.DeviceRecSys)
 
     # ---- cache.go:22-56
     def Set(self, userId, seq: TimeSeq):
-        self.ub[int(userId)] = seq
-        self._drop()
+        self.BatchSet({userId: seq})
 
     def BatchSet(self, ub: dict):
-        for k, v in ub.items():
-            self.ub[int(k)] = v
-        self._drop()
+        ub = {int(k): v for k, v in ub.items()}
+        if self._in_place(ub):
+            self._device_batch_set(ub)          # (a refused call -- an unsorted sequence -- leaves dictionary and image alone)
+        else:
+            self._drop()
+        self.ub.update(ub)
 
     def Delete(self, userId):
-        self.ub.pop(int(userId), None)
-        self._drop()
+        self.DeleteMany([userId])
+
+    def DeleteMany(self, userIds, keepEmpty=False):
+        """Delete for several users in one device call.  keepEmpty: the users stay in the dictionary with an empty sequence
+        (a DeviceRecSys's users are fixed) instead of leaving it like cache.go:43-48."""
+        ids = [int(u) for u in userIds]
+        if self._in_place(ids):
+            rows = np.array([self._users[u] for u in ids], np.int32)
+            capi.check(capi.load().goctr_ubcache_delete(self._h, C.c_int64(rows.size), capi.ptr(rows, C.c_int32)))
+            self._stale = self._stale or not keepEmpty
+        else:
+            self._drop()
+        for u in ids:
+            if keepEmpty:
+                self.ub[u] = TimeSeq([], [])
+            else:
+                self.ub.pop(u, None)
 
     def Clear(self):
+        if self._h:
+            capi.check(capi.load().goctr_ubcache_clear(self._h))
+            self._stale = True
         self.ub = {}
-        self._drop()
+
+    def Append(self, events, maxLen=0):
+        """EXTENSION: ``events`` = (userId, itemId, ts) triples in any order, merged into the users' sequences (merge_events);
+        maxLen > 0 keeps only the newest maxLen entries of every touched user.  A user the cache does not hold starts empty."""
+        ev = [(int(u), int(i), int(t)) for u, i, t in events]
+        per_user = {}
+        for u, i, t in ev:
+            per_user.setdefault(u, []).append((i, t))
+        if self._in_place(per_user):
+            users = np.array([self._users[u] for u, _, _ in ev], np.int32)
+            items = np.array([i for _, i, _ in ev], np.int32)
+            ts = np.array([t for _, _, t in ev], np.int64)
+            capi.check(capi.load().goctr_ubcache_append(self._h, C.c_int64(users.size), capi.ptr(users, C.c_int32),
+                                                        capi.ptr(items, C.c_int32), capi.ptr(ts, C.c_int64), C.c_int64(int(maxLen))))
+        else:
+            self._drop()
+        for u, e in per_user.items():
+            self.ub[u] = merge_events(self.ub.get(u, TimeSeq([], [])), e, maxLen)
 
     # ---- device image
-    def _drop(self):
+    def _in_place(self, users):
+        return bool(self._h) and all(u in self._users for u in users)
+
+    def _device_batch_set(self, ub):
+        for u, seq in ub.items():
+            if len(seq.Ts) != len(seq.Items):
+                raise ValueError(f"user {u}: {len(seq.Ts)} timestamps for {len(seq.Items)} items")
+        rows = np.array([self._users[u] for u in ub], np.int32)
+        off = np.zeros(len(ub) + 1, np.int64)
+        np.cumsum([len(seq.Ts) for seq in ub.values()], out=off[1:])
+        items = np.array([i for seq in ub.values() for i in seq.Items], np.int32)
+        ts = np.array([t for seq in ub.values() for t in seq.Ts], np.int64)
+        capi.check(capi.load().goctr_ubcache_batch_set(self._h, C.c_int64(rows.size), capi.ptr(rows, C.c_int32),
+                                                       capi.ptr(off, C.c_int64), capi.ptr(items, C.c_int32), capi.ptr(ts, C.c_int64)))
+
+    def _drop(self, closing=False):
         if self._h:
+            if self._borrowed and not closing:
+                raise RuntimeError("the device image of this behaviour cache is borrowed by a goctr_recsys and cannot be rebuilt")
             capi.load().goctr_ubcache_destroy(self._h)
         self._h = None
+        self._stale = False
+
+    def info(self):
+        """(users, entries, version) of the device image; the version grows by one with every update applied in place"""
+        n, nnz, ver = C.c_int64(0), C.c_int64(0), C.c_uint64(0)
+        capi.check(capi.load().goctr_ubcache_info(self.device(), C.byref(n), C.byref(nnz), C.byref(ver)))
+        return n.value, nnz.value, ver.value
+
+    def export(self):
+        """the device image's CSR: (off [users + 1] int64, items int32, ts int64)"""
+        n, nnz, _ = self.info()
+        off, items, ts = np.empty(n + 1, np.int64), np.empty(nnz, np.int32), np.empty(nnz, np.int64)
+        capi.check(capi.load().goctr_ubcache_export(self._h, capi.ptr(off, C.c_int64), capi.ptr(items, C.c_int32),
+                                                    capi.ptr(ts, C.c_int64)))
+        return off, items, ts
 
     def user_index(self):
         """dense index of every cached user id (order of the CSR rows)"""
+        if self._stale:             # rows of users that were deleted in place: the index is rebuilt from the dictionary
+            self._drop()
         if self._users is None or self._h is None:
             self.device()
         return self._users
@@ -109,7 +199,7 @@ class UserBehaviorCache:
 
     def __del__(self):
         try:
-            self._drop()
+            self._drop(closing=True)
         except Exception:
             pass
 

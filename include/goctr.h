@@ -219,6 +219,30 @@ void goctr_ubcache_destroy(goctr_ubcache* c);
 /* UserBehaviorCache.Get for `rows` keys at once; out_ids [rows, T] */
 int goctr_ubcache_get(goctr_ubcache* c, const int32_t* users, const int64_t* max_ts /* may be NULL = 0 */, int64_t rows,
                       int T, int32_t* out_ids);
+/* ---- updates of a live cache (feature/ubcache/cache.go:27-55).  Users are the dense indices [0, n_users) fixed by
+ * goctr_ubcache_create; a user outside that range refuses the whole call.  A refused call leaves the cache bit for bit as
+ * it was.  A successful call becomes visible as a whole: goctr_ubcache_get, goctr_dataset_create_keys and one serving pass
+ * of goctr_rank / goctr_batch_predict see all of a call's changes or none, and a goctr_recsys that borrowed the handle
+ * before the update serves the new sequences on its next call.  Any host thread may call these beside serving calls;
+ * host work and host<->device traffic are proportional to the update, never to n_users or the entries of the cache. */
+/* UserBehaviorCache.Set / BatchSet (cache.go:27-41): replace the sequences of n DISTINCT users.
+ * Payload is a CSR over the n users: off[0] = 0, each sequence timestamp-descending. */
+int goctr_ubcache_batch_set(goctr_ubcache* c, int64_t n, const int32_t* users, const int64_t* off /*[n+1]*/,
+                            const int32_t* items, const int64_t* ts);
+/* Delete (cache.go:43-48): the users' sequences become empty.  Duplicates allowed. */
+int goctr_ubcache_delete(goctr_ubcache* c, int64_t n, const int32_t* users);
+/* Clear (cache.go:50-55): every sequence becomes empty; n_users stays. */
+int goctr_ubcache_clear(goctr_ubcache* c);
+/* EXTENSION (no reference counterpart): n events (user, item, ts) in any order, merged into the users' sequences;
+ * max_len > 0 keeps only the newest max_len entries of every TOUCHED user.  A touched user's new sequence: the user's
+ * events in reverse call order in front of the old sequence, stable-sorted by timestamp descending, then truncated (on
+ * equal timestamps a new event precedes the old entries and a later event of the call an earlier one; no de-duplication). */
+int goctr_ubcache_append(goctr_ubcache* c, int64_t n, const int32_t* users, const int32_t* items, const int64_t* ts,
+                         int64_t max_len);
+/* users, entries, and a version that grows by one with every successful mutating call */
+int goctr_ubcache_info(goctr_ubcache* c, int64_t* n_users, int64_t* nnz, uint64_t* version);
+/* the current CSR back to the host (sizes from goctr_ubcache_info): tests, persistence */
+int goctr_ubcache_export(goctr_ubcache* c, int64_t* off /*[n_users+1]*/, int32_t* items, int64_t* ts);
 /* id-mode dataset assembled on the device from sample keys (rcmd.Sample{UserId, ItemId, Timestamp}, rcmd.go:65-71):
  * behaviour ids from the cache, user_table[user] and item_table[item] rows as the dense side features */
 int goctr_dataset_create_keys(goctr_ubcache* c, const float* user_table /*[n_users,U]*/, int64_t n_users, int U,
