@@ -95,6 +95,8 @@ SYMBOLS = [
     "goctr_w2v_get_keep_mask", "goctr_metrics_binary", "goctr_metrics_binary_f64", "goctr_evaluate_dataset",
     "goctr_mlp_evaluate_resident", "goctr_metrics_grouped", "goctr_metrics_grouped_f64", "goctr_evaluate_dataset_grouped",
     "goctr_mlp_evaluate_resident_grouped",
+    "goctr_emb_load_w2v", "goctr_w2v_copy_word_vectors", "goctr_searcher_create_from_w2v", "goctr_searcher_load_w2v",
+    "goctr_corpus_append_ubcache",
 ]
 
 _lib = None
@@ -136,6 +138,11 @@ def load() -> C.CDLL:
         _lib.goctr_ubcache_append.argtypes = [C.c_void_p, C.c_int64, _i32, _i32, _i64, C.c_int64]
         _lib.goctr_ubcache_info.argtypes = [C.c_void_p, _i64, _i64, C.POINTER(C.c_uint64)]
         _lib.goctr_ubcache_export.argtypes = [C.c_void_p, _i64, _i32, _i64]
+        _lib.goctr_emb_load_w2v.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _i64, _i64]
+        _lib.goctr_w2v_copy_word_vectors.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.goctr_searcher_create_from_w2v.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        _lib.goctr_searcher_load_w2v.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.goctr_corpus_append_ubcache.argtypes = [C.c_void_p, C.c_void_p, C.c_int, _i64]
     return _lib
 
 

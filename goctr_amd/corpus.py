@@ -26,6 +26,15 @@ class Corpus:
         self._built = False
         return self
 
+    def append_ubcache(self, cache, oldest_first=True):
+        """GetItemEmbeddingModelFromUb's stream (rcmd.go:538-545) when the item sequences are a behaviour cache: every entry
+        with item >= 0, user by user in the cache's row order, appended on the device (goctr_corpus_append_ubcache);
+        oldest_first reverses each user's timestamp-descending sequence.  Returns the number of tokens appended."""
+        n = C.c_int64(0)
+        capi.check(capi.load().goctr_corpus_append_ubcache(self._h, cache.device(), C.c_int(1 if oldest_first else 0), C.byref(n)))
+        self._built = False
+        return n.value
+
     def Load(self, batches):
         for b in batches:
             self.append(b)

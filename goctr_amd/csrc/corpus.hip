@@ -15,8 +15,13 @@
 //   5. doc_index   : idoc[pos] = id(slot_of[pos]);  keep flag from the two count filters
 //   6. scan + doc_compact : IndexedDoc
 // The result does not depend on the order the atomics land in: ids are a function of first positions only.
+//
+// goctr_corpus_append_ubcache fills the token buffer from the behaviour cache's CSR instead of from host batches
+// (GetItemEmbeddingModelFromUb, recommend/rcmd.go:538-545): per-user valid counts, their exclusive scan, one wavefront per user
+// compacting (and reversing) its segment -- ub_valid_count_kernel / ub_compact_kernel below.
 #include "corpus.h"
 #include "scan.h"
+#include "ubcache.h"
 
 #include <climits>
 #include <memory>
@@ -104,6 +109,48 @@ __global__ void doc_compact_kernel(const int* idoc, const unsigned int* keep, co
   if (pos < n && keep[pos]) indexed[off[pos]] = idoc[pos];
 }
 
+// ---- goctr_corpus_append_ubcache: the behaviour cache's CSR as a token stream, user by user
+// one wavefront per user: the entries of its segment with item >= 0 (an item unknown to every table is -1)
+__global__ __launch_bounds__(256) void ub_valid_count_kernel(const long long* __restrict__ off, const int* __restrict__ items,
+                                                             long long n_users, unsigned int* __restrict__ cnt) {
+  const long long u = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (u >= n_users) return;                 // (whole wavefronts leave: the ballots below see full ones)
+  const int lane = threadIdx.x & 63;
+  const long long lo = off[u], hi = off[u + 1];
+  unsigned int c = 0;
+  for (long long p0 = lo; p0 < hi; p0 += 64) {
+    const long long p = p0 + lane;
+    c += (unsigned int)__popcll(__ballot(p < hi && items[p] >= 0));
+  }
+  if (lane == 0) cnt[u] = c;
+}
+
+// the same walk again: a valid entry's place among its user's valid entries = the entries counted so far + the valid lanes
+// below it (ballot / popcount); keys[base + start[u] + place], or counted from the segment's end for oldest_first (the cache
+// is timestamp-descending).  One writer per token; a wavefront's tokens are contiguous.
+__global__ __launch_bounds__(256) void ub_compact_kernel(const long long* __restrict__ off, const int* __restrict__ items,
+                                                         long long n_users, const unsigned int* __restrict__ cnt,
+                                                         const unsigned int* __restrict__ start, int oldest_first,
+                                                         long long* __restrict__ keys, long long base, long long limit) {
+  const long long u = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (u >= n_users) return;
+  const int lane = threadIdx.x & 63;
+  const long long lo = off[u], hi = off[u + 1];
+  const long long n_u = cnt[u], first = base + start[u];
+  long long done = 0;
+  for (long long p0 = lo; p0 < hi; p0 += 64) {
+    const long long p = p0 + lane;
+    const int it = p < hi ? items[p] : -1;
+    const unsigned long long valid = __ballot(it >= 0);
+    if (it >= 0) {
+      const long long place = done + __popcll(valid & ((1ull << lane) - 1ull));
+      const long long dst = first + (oldest_first ? n_u - 1 - place : place);
+      if (dst >= base && dst < limit) keys[dst] = (long long)it;       // (limit = base + the scan's total <= capacity)
+    }
+    done += __popcll(valid);
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -130,6 +177,42 @@ int goctr_corpus_append(goctr_corpus* c, const int64_t* keys, int64_t n) {
   if (n && c->keys.upload(reinterpret_cast<const long long*>(keys), (size_t)n, (size_t)c->n_words)) return -1;
   c->n_words += n;
   c->built = false;
+  return 0;
+}
+
+int goctr_corpus_append_ubcache(goctr_corpus* c, goctr_ubcache* ub, int oldest_first, int64_t* n_appended) {
+  GOCTR_ENTER_H(c);
+  GOCTR_CHECK(c && ub, "goctr_corpus_append_ubcache: null argument");
+  GOCTR_SAME_ENGINE(c, ub);
+  std::lock_guard<std::mutex> lk(c->mu);
+  hipStream_t s = engine().stream;
+  UbRead image(ub, s);                        // one image of the cache: a concurrent update is seen whole or not at all
+  const long long nu = ub->n_users, nnz = ub->nnz;
+  unsigned long long total_h = 0;
+  GOCTR_CHECK(nnz < (1LL << 32), "goctr_corpus_append_ubcache: a cache of %lld entries (the counts are scanned in 32 bits)", nnz);
+  if (nnz > 0) {
+    DevBuf<unsigned int> cnt, start, tiles;
+    DevBuf<unsigned long long> total;
+    if (cnt.alloc((size_t)nu, false) || start.alloc((size_t)nu, false) || total.alloc(1)) return -1;
+    const dim3 g((unsigned)cdiv(nu, 4)), b(256);
+    hipLaunchKernelGGL(ub_valid_count_kernel, g, b, 0, s, ub->off.p, ub->items.p, nu, cnt.p);
+    GOCTR_HIP(hipGetLastError());
+    if (exclusive_scan(cnt.p, nu, start.p, tiles, total.p)) return -1;
+    if (total.download(&total_h, 1)) return -1;           // (the call's only host traffic)
+    GOCTR_CHECK(c->n_words + (long long)total_h <= c->capacity,
+                "goctr_corpus_append_ubcache: %lld + %llu words exceed the capacity %lld (the corpus is unchanged)",
+                (long long)c->n_words, total_h, (long long)c->capacity);
+    if (total_h) {
+      hipLaunchKernelGGL(ub_compact_kernel, g, b, 0, s, ub->off.p, ub->items.p, nu, cnt.p, start.p, oldest_first ? 1 : 0,
+                         c->keys.p, (long long)c->n_words, (long long)c->n_words + (long long)total_h);
+      GOCTR_HIP(hipGetLastError());
+    }
+    GOCTR_HIP(hipStreamSynchronize(s));                   // the scratch buffers go out of scope; the image is released
+  }
+  image.done();
+  c->n_words += (int64_t)total_h;
+  c->built = false;
+  if (n_appended) *n_appended = (int64_t)total_h;
   return 0;
 }
 

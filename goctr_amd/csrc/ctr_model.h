@@ -7,6 +7,7 @@
 //   ctr_api.hip     C ABI of models, tables, gather and datasets; the training and predict entry points
 //   ctr_multi.hip   single-call multi-device training (goctr_train_cfg::devices)
 //   serve.hip       behaviour cache, key datasets and serving (goctr_rank, goctr_batch_predict, goctr_predict_dense)
+//   emb_w2v.hip     goctr_emb_load_w2v: an item2vec model's vectors into a table, in HBM
 // A translation unit other than ctr.hip defines GOCTR_NO_PLAIN_KERNELS before it includes this header: the plain kernels of
 // the kernel headers are compiled in ctr.hip only (those of emb_train.h, which only ctr_emb.hip includes, in ctr_emb.hip).
 #pragma once
@@ -30,8 +31,8 @@ struct goctr_emb {
   // single-call multi-device training (goctr_train_cfg::devices): this table's replicas on engines 1 .. n-1 (owned), and the
   // version of THIS table they were last made equal to
   std::vector<goctr_emb*> reps; uint64_t reps_version = ~0ull;
-  // Rows are READ by serving passes on their slots' streams (shared) and WRITTEN on the main stream by goctr_emb_set_rows and
-  // by embedding training of any model that was given this table (exclusive).  ev_rows is recorded behind the last queued
+  // Rows are READ by serving passes on their slots' streams (shared) and WRITTEN on the main stream by goctr_emb_set_rows,
+  // goctr_emb_load_w2v and by embedding training of any model that was given this table (exclusive).  ev_rows is recorded behind the last queued
   // write: training is asynchronous, a serving pass waits for the event before its launches read the rows.
   std::shared_mutex mu;
   hipEvent_t ev_rows = nullptr; std::atomic<bool> rows_pending{false};
@@ -251,6 +252,7 @@ int launch_serve16(goctr_model* m, const RowSource& src, int B, const StepState*
 StepOpts opts_from(const goctr_train_cfg* tc);
 int check_dataset(const goctr_model* m, const goctr_dataset* d, const goctr_emb* e);
 int mark_weights_written(goctr_model* m);
+int emb_mark_written(goctr_emb* e);       // ev_rows behind the last queued launch that writes the table's rows
 int run_steps(goctr_model* m, goctr_emb* emb, goctr_dataset* d, const goctr_train_cfg* tc, int n_steps);
 
 // ---------------------------------------------------------------- multi-device training (ctr_multi.hip)

@@ -29,6 +29,14 @@ int check_dataset(const goctr_model* m, const goctr_dataset* d, const goctr_emb*
   return 0;
 }
 
+// behind the last queued launch that writes the table's rows (embedding training, goctr_emb_load_w2v): serve_wait_rows
+int emb_mark_written(goctr_emb* e) {
+  if (!e->ev_rows) GOCTR_HIP(hipEventCreateWithFlags(&e->ev_rows, hipEventDisableTiming));
+  GOCTR_HIP(hipEventRecord(e->ev_rows, engine().stream));
+  e->rows_pending.store(true, std::memory_order_release);
+  return 0;
+}
+
 namespace {
 
 int allreduce_grads(goctr_model* m) {
@@ -158,13 +166,6 @@ __global__ void step_state_prepare_kernel(StepState* st, double beta1, double be
   *st = s;
 }
 
-// behind the last queued launch that writes the table's rows (embedding training): serve_wait_rows
-int emb_mark_written(goctr_emb* e) {
-  if (!e->ev_rows) GOCTR_HIP(hipEventCreateWithFlags(&e->ev_rows, hipEventDisableTiming));
-  GOCTR_HIP(hipEventRecord(e->ev_rows, engine().stream));
-  e->rows_pending.store(true, std::memory_order_release);
-  return 0;
-}
 
 int run_steps_impl(goctr_model* m, goctr_emb* emb, goctr_dataset* d, const goctr_train_cfg* tc, int n_steps) {
   Engine& e = engine();

@@ -45,6 +45,7 @@
 #include <vector>
 
 #include "common.h"
+#include "w2v_model.h"
 
 using namespace goctr;
 
@@ -1070,28 +1071,69 @@ static int knn_search_scan(goctr_searcher* s, const double* queries, int Q, int 
   return 0;
 }
 
-extern "C" {
-
-int goctr_searcher_create(const double* items, int64_t V, int D, goctr_searcher** out) {
-  GOCTR_ENTER();
-  GOCTR_CHECK(items && out && V > 0 && D > 0, "goctr_searcher_create: bad arguments");
-  GOCTR_CHECK(D <= 1024, "goctr_searcher_create: dim %d > 1024", D);
-  GOCTR_CHECK(cdiv(V, KNN_TILE) <= 8192, "goctr_searcher_create: more than %d items", 8192 * KNN_TILE);
+// search.New's allocations for V items of D dimensions (the items themselves are not resident yet)
+static int searcher_alloc(int64_t V, int D, const char* who, goctr_searcher** out) {
+  GOCTR_CHECK(V > 0 && D > 0, "%s: bad arguments", who);
+  GOCTR_CHECK(D <= 1024, "%s: dim %d > 1024", who, D);
+  GOCTR_CHECK(cdiv(V, KNN_TILE) <= 8192, "%s: more than %d items", who, 8192 * KNN_TILE);
   goctr_searcher* s = new goctr_searcher;
   s->V = V; s->D = D;
-  if (s->items.alloc((size_t)V * D, false) || s->items.upload(items, (size_t)V * D) || s->norms.alloc((size_t)V, false) ||
+  if (s->items.alloc((size_t)V * D, false) || s->norms.alloc((size_t)V, false) ||
       (knn_scan_ipt(D) > 0 && s->items32.alloc((size_t)round_up64(V, 2048) * D, false)) ||
       ((D == 16 || D == 32) && s->items_bf.alloc((size_t)2 * round_up64(V, 2048) * D, true))) {      // (zeroed: the pad rows score 0)
     delete s;
     return -1;
   }
-  if (s->items32.p)      // (zero rows up to a whole tile: the matrix-core scan kernel reads whole tiles)
-    (void)hipMemsetAsync(s->items32.p + (size_t)V * D, 0, sizeof(float) * (size_t)(round_up64(V, 2048) - V) * D, engine().stream);
-  hipLaunchKernelGGL(knn_norm_kernel, dim3((unsigned)cdiv(V, 256)), dim3(256), 0, engine().stream, s->items.p, (long long)V, D,
-                     s->norms.p, s->items32.p, s->items_bf.p, (long long)(s->items_bf.n / 2));
-  if (hipGetLastError() != hipSuccess) { set_error("knn_norm_kernel launch failed"); delete s; return -1; }
   *out = s;
   return 0;
+}
+
+// everything behind "the items are resident" (queued on the main stream behind whatever put them there): norms and the scan
+// path's derived images.  Shared by goctr_searcher_create (host items) and the item2vec hand-over (device to device).
+static int searcher_derive(goctr_searcher* s) {
+  const int64_t V = s->V; const int D = s->D;
+  if (s->items32.p)      // (zero rows up to a whole tile: the matrix-core scan kernel reads whole tiles)
+    GOCTR_HIP(hipMemsetAsync(s->items32.p + (size_t)V * D, 0, sizeof(float) * (size_t)(round_up64(V, 2048) - V) * D, engine().stream));
+  hipLaunchKernelGGL(knn_norm_kernel, dim3((unsigned)cdiv(V, 256)), dim3(256), 0, engine().stream, s->items.p, (long long)V, D,
+                     s->norms.p, s->items32.p, s->items_bf.p, (long long)(s->items_bf.n / 2));
+  GOCTR_CHECK(hipGetLastError() == hipSuccess, "knn_norm_kernel launch failed");
+  return 0;
+}
+
+extern "C" {
+
+int goctr_searcher_create(const double* items, int64_t V, int D, goctr_searcher** out) {
+  GOCTR_ENTER();
+  GOCTR_CHECK(items && out, "goctr_searcher_create: bad arguments");
+  goctr_searcher* s = nullptr;
+  if (searcher_alloc(V, D, "goctr_searcher_create", &s)) return -1;
+  if (s->items.upload(items, (size_t)V * D) || searcher_derive(s)) { delete s; return -1; }
+  *out = s;
+  return 0;
+}
+
+int goctr_searcher_create_from_w2v(goctr_w2v* w, goctr_searcher** out) {
+  GOCTR_ENTER_H(w);
+  GOCTR_CHECK(w && out, "goctr_searcher_create_from_w2v: null argument");
+  GOCTR_W2V_SINGLE_DEVICE(w);
+  std::lock_guard<std::mutex> lw(w->mu);
+  goctr_searcher* s = nullptr;
+  if (searcher_alloc(w->V, w->cfg.dim, "goctr_searcher_create_from_w2v", &s)) return -1;
+  if (w2v_copy_word_vectors(w, s->items.p) || searcher_derive(s)) { delete s; return -1; }
+  *out = s;
+  return 0;
+}
+
+int goctr_searcher_load_w2v(goctr_searcher* s, goctr_w2v* w) {
+  GOCTR_ENTER_H(s);
+  GOCTR_CHECK(s && w, "goctr_searcher_load_w2v: null argument");
+  GOCTR_SAME_ENGINE(s, w);
+  GOCTR_W2V_SINGLE_DEVICE(w);
+  std::lock_guard<std::mutex> lw(w->mu);
+  std::lock_guard<std::mutex> lk(s->mu);           // (a search holds it for the whole call: it sees the old items or the new)
+  GOCTR_CHECK(s->V == w->V && s->D == w->cfg.dim, "goctr_searcher_load_w2v: the searcher holds %lld x %d items, the model %lld x %d",
+              (long long)s->V, s->D, (long long)w->V, w->cfg.dim);
+  return w2v_copy_word_vectors(w, s->items.p) || searcher_derive(s) ? -1 : 0;
 }
 
 void goctr_searcher_destroy(goctr_searcher* s) { delete s; }

@@ -239,6 +239,15 @@ int export_param_f32(goctr_w2v* w, float* out) {
   return d.download(out, (size_t)n);
 }
 
+int w2v_copy_word_vectors(goctr_w2v* w, double* dev_out) {
+  const long long n = (long long)w->V * w->cfg.dim;
+  const long long blocks = std::min<long long>(cdiv(std::max<long long>(n >> 1, 1), 256), 8192);   // (grid-stride)
+  hipLaunchKernelGGL(w2v_agg_copy_kernel, dim3((unsigned)blocks), dim3(256), 0, engine().stream, w->param.p,
+                     w->cfg.optimizer == 1 ? w->aux.p : nullptr, n, dev_out);
+  GOCTR_HIP(hipGetLastError());
+  return 0;
+}
+
 // ---- single-call multi-device passes (goctr_w2v_cfg::devices)
 // cut[r] .. cut[r + 1] = rank r's words: slices [r, r + 1) * S / N of IndexPerThread's cut (modelutil.go:32-41) when the slices
 // divide evenly, else an equal contiguous range

@@ -205,4 +205,12 @@ int goctr_w2v_export_f32(goctr_w2v* w, float* out) {
   return export_param_f32(w, out);
 }
 
+int goctr_w2v_copy_word_vectors(goctr_w2v* w, double* dev_out) {
+  GOCTR_ENTER_H(w);
+  GOCTR_CHECK(w && dev_out, "goctr_w2v_copy_word_vectors: null argument");
+  GOCTR_W2V_SINGLE_DEVICE(w);
+  std::lock_guard<std::mutex> lk(w->mu);
+  return w2v_copy_word_vectors(w, dev_out);
+}
+
 }  // extern "C"

@@ -736,6 +736,21 @@ __global__ void w2v_narrow_kernel(const double* p, long long n, float* out) {
   if (i < n) out[i] = (float)p[i];  // word2vec.go:315-318
 }
 
+// WordVector(vector.Agg) (word2vec.go:249-271) of every word into out [n = V x dim]: param, + ctx when the optimizer keeps
+// context vectors (negative sampling; ctx == nullptr: hierarchical softmax).  A streaming pass, 16 or 32 bytes in and 16 out
+// per thread and step (every buffer is 256-byte aligned); the odd last element goes to thread 0.
+__global__ __launch_bounds__(256) void w2v_agg_copy_kernel(const double* __restrict__ param, const double* __restrict__ ctx,
+                                                           long long n, double* __restrict__ out) {
+  typedef double d2 __attribute__((ext_vector_type(2)));
+  const long long pairs = n >> 1;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < pairs; i += (long long)gridDim.x * 256) {
+    d2 v = reinterpret_cast<const d2*>(param)[i];
+    if (ctx) v += reinterpret_cast<const d2*>(ctx)[i];
+    reinterpret_cast<d2*>(out)[i] = v;
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) out[n - 1] = ctx ? param[n - 1] + ctx[n - 1] : param[n - 1];
+}
+
 // Subsampler (modelutil/subsample/subsample.go:28-52): samples[id] = max(0, 1 - sqrt(threshold / cfs[id])) (raw counts,
 // quirk Q14); a word is trained when samples[id] > u, u uniform in [0,1).  The reference draws u from Go's global
 // math/rand stream, which cannot be regenerated outside Go; here u is a counter-based hash of (seed, position), so the

@@ -6,6 +6,7 @@
 //                   multi-device pass and its shards, the subsampling mask and the float32 export
 //   w2v_api.hip     C ABI: create / destroy, vectors, paths, doc upload, training, the corpus hand-over, export
 //   huffman.hip     the Huffman tree, on the host or with the device (huffman.h)
+//   emb_w2v.hip     goctr_emb_load_w2v: a trained model's vectors into the CTR embedding table without leaving HBM
 //
 // item2vec engine (float64, like the reference).
 //
@@ -74,3 +75,13 @@ int w2v_multi_shards(goctr_w2v* w, int64_t n_words, const std::function<int(goct
 int subsample_doc(goctr_w2v* w, long long n, const long long* cfs, double threshold, unsigned long long seed);
 // the input vectors narrowed to float32 (GenEmbeddingMap32) into out [V x dim] on the host
 int export_param_f32(goctr_w2v* w, float* out);
+// WordVector(vector.Agg) of every word (word2vec.go:249-271: param; negative sampling: param + ctx, summed in float64) into
+// dev_out [V x dim] in HBM, queued on the engine's main stream; the caller holds w->mu.  What goctr_w2v_copy_word_vectors
+// and the k-NN searcher's goctr_searcher_create_from_w2v / _load_w2v (search.hip) run; goctr_emb_load_w2v (emb_w2v.hip) applies
+// the same rule row by row inside its gather
+int w2v_copy_word_vectors(goctr_w2v* w, double* dev_out);
+// the three calls that read a trained model in place take single-device handles only: after a cfg.devices = n pass
+// (w2v_multi_pass) every rank has applied the same exchanged deltas, but nothing here checks that rank 0's matrices ARE the
+// combined model, so they refuse instead of assuming it
+#define GOCTR_W2V_SINGLE_DEVICE(w) \
+  GOCTR_CHECK((w)->cfg.devices <= 1, "%s: a multi-device item2vec handle (cfg.devices = %d) is not supported here", __func__, (w)->cfg.devices)

@@ -90,6 +90,7 @@ class Word2Vec:
     def create(self, counts, param0=None, aux0=None):
         capi.init()
         self.close()
+        self.corpus = None                                                  # (word i's key is i: load_table, search.Searcher.from_model)
         counts = np.ascontiguousarray(counts, np.int64)
         self.V = counts.size
         self._h = C.c_void_p()
@@ -175,7 +176,16 @@ class Word2Vec:
         HBM as they arrive, dictionary / IndexedDoc / subsampling masks are built there (csrc/corpus.hip) and only the
         counts come back (for the host-side Huffman build)."""
         from .corpus import Corpus
-        cps = Corpus(capacity_words, self.min_count, self.max_count).Load(batches)
+        return self.TrainCorpus(Corpus(capacity_words, self.min_count, self.max_count).Load(batches), seed)
+
+    def TrainCorpus(self, cps, seed=0, param0=None, aux0=None):
+        """TrainIds over a built ``corpus.Corpus`` (however its tokens arrived: batches, or a behaviour cache appended on the
+        device).  param0 / aux0 ([V, dim] arrays, or callables V -> array): the initial vectors, which the reference draws
+        from host RNG (word2vec.go:103-111, optimizer.go:38-48), injected for parity runs."""
+        def init(x0):
+            if x0 is None:
+                return (self.rng.random((self.V, self.dim)) - 0.5) / self.dim
+            return x0(self.V) if callable(x0) else x0
         self.corpus = cps
         capi.init()
         self.close()
@@ -183,9 +193,9 @@ class Word2Vec:
         self._h = C.c_void_p()
         cfg = self._cfg()
         capi.check(capi.load().goctr_w2v_create_from_corpus(C.byref(cfg), cps._h, C.byref(self._h)))
-        self.set_param((self.rng.random((self.V, self.dim)) - 0.5) / self.dim)          # word2vec.go:103-111
+        self.set_param(init(param0))                                                    # word2vec.go:103-111
         if self.optimizer != "hs":
-            self.set_aux((self.rng.random((self.V, self.dim)) - 0.5) / self.dim)        # optimizer.go:38-48
+            self.set_aux(init(aux0))                                                    # optimizer.go:38-48
         for it in range(self.iter):
             capi.check(capi.load().goctr_w2v_use_corpus(self._h, cps._h, C.c_double(self.threshold),
                                                         C.c_uint64(seed + it)))
@@ -209,6 +219,21 @@ class Word2Vec:
         """word2vec.go:298-324: param rows narrowed to float32, keyed by word"""
         out = self.export_f32()
         return {w: out[i] for i, w in enumerate(self.dic.id2word)}
+
+    def load_table(self, table, row_keys=None):
+        """GenEmbeddingMap32 + the per-item map lookup (rcmd.go:502-505) into ``table`` (model.EmbeddingTable) without
+        leaving HBM (goctr_emb_load_w2v): row r becomes float32(WordVector(vector.Agg)) of the word whose key is
+        row_keys[r] (None: r), or zeros when the dictionary has no such word.  The dictionary is the resident corpus' after
+        TrainIds / TrainCorpus, else word i's key is i.  Unlike export_f32 / GenEmbeddingMap32 above, which narrow ``param``
+        only, a negative-sampling model contributes param + ctx summed in float64.  Returns the number of rows filled."""
+        rk = None if row_keys is None else np.ascontiguousarray(row_keys, np.int64)
+        if rk is not None and rk.size != table.V:
+            raise ValueError(f"{rk.size} row keys for a table of {table.V} rows")
+        cps = getattr(self, "corpus", None)
+        n = C.c_int64(0)
+        capi.check(capi.load().goctr_emb_load_w2v(table._h, self._h, cps._h if cps is not None else None,
+                                                  capi.ptr(rk, C.c_int64), C.byref(n)))
+        return n.value
 
     def close(self):
         if self._h:

@@ -497,6 +497,71 @@ inline IdModel TrainEmbeddingIds(const std::vector<std::vector<int64_t>>& batche
   goctr_corpus_destroy(c);
   return m;
 }
+
+// A trained model that STAYS on the device (the handle and its corpus): what the in-HBM hand-overs take.  LoadTable is
+// GenEmbeddingMap32 + itemEmbeddingMap's lookups (rcmd.go:213, :502-505) into a CTR embedding table (goctr_emb_load_w2v: row r
+// = float32(WordVector(vector.Agg)) of the word whose key is row_keys[r], or zeros; unlike Model::vectors above, which is
+// goctr_w2v_export_f32's param-only narrowing, a negative-sampling model contributes param + ctx summed in float64).
+class ResidentModel {
+ public:
+  ResidentModel(goctr_w2v* h, goctr_corpus* c, int64_t V, int dim) : V(V), dim(dim), h_(h), c_(c) {}
+  ~ResidentModel() { if (h_) goctr_w2v_destroy(h_); if (c_) goctr_corpus_destroy(c_); }
+  ResidentModel(const ResidentModel&) = delete;
+  ResidentModel& operator=(const ResidentModel&) = delete;
+  ResidentModel(ResidentModel&& o) noexcept : V(o.V), dim(o.dim), h_(o.h_), c_(o.c_) { o.h_ = nullptr; o.c_ = nullptr; }
+  int64_t LoadTable(goctr_emb* table, const std::vector<int64_t>* row_keys = nullptr) const {
+    int64_t filled = 0;
+    check(goctr_emb_load_w2v(table, h_, c_, row_keys ? row_keys->data() : nullptr, &filled));
+    return filled;
+  }
+  std::vector<int64_t> Ids() const {                      // Dictionary.id2word (8 bytes per word: the only download)
+    std::vector<int64_t> ids((size_t)V);
+    if (c_) check(goctr_corpus_get_dictionary(c_, ids.data(), nullptr));
+    else for (int64_t i = 0; i < V; ++i) ids[(size_t)i] = i;
+    return ids;
+  }
+  goctr_w2v* handle() const { return h_; }
+  int64_t V; int dim;
+
+ private:
+  goctr_w2v* h_; goctr_corpus* c_;
+};
+
+// GetItemEmbeddingModelFromUb (rcmd.go:538-545) over a device-resident behaviour cache holding raw item ids: the cache is the
+// corpus (goctr_corpus_append_ubcache, every user's sequence oldest first), nothing but counts crosses the bus.
+inline ResidentModel GetItemEmbeddingModelFromUb(goctr_ubcache* ub, int64_t capacity_words, int window = 5, int dim = 16, int iter = 1,
+                                                 int64_t min_count = 5, int64_t max_count = -1, double subsample = 1e-3,
+                                                 uint64_t seed = 1) {
+  ensure_init();
+  goctr_corpus* c = nullptr;
+  check(goctr_corpus_create(std::max<int64_t>(capacity_words, 1), &c));
+  int64_t appended = 0, n_words = 0, V = 0;
+  goctr_w2v* h = nullptr;
+  try {
+    check(goctr_corpus_append_ubcache(c, ub, 1, &appended));
+    check(goctr_corpus_build(c, min_count, max_count));
+    check(goctr_corpus_info(c, &n_words, &V, nullptr));
+    goctr_w2v_cfg cfg;
+    goctr_w2v_cfg_default(&cfg);
+    cfg.dim = dim; cfg.window = window;
+    check(goctr_w2v_create_from_corpus(&cfg, c, &h));
+    std::mt19937_64 g(seed);
+    std::uniform_real_distribution<double> ud(0.0, 1.0);
+    std::vector<double> param((size_t)V * (size_t)dim);
+    for (auto& v : param) v = (ud(g) - 0.5) / dim;          // word2vec.go:103-111
+    check(goctr_w2v_set_param(h, param.data()));
+    double lr = cfg.init_lr;
+    for (int it = 0; it < iter; ++it) {
+      check(goctr_w2v_use_corpus(h, c, subsample, seed + (uint64_t)it));
+      check(goctr_w2v_train_resident(h, n_words, &lr));
+    }
+  } catch (...) {
+    if (h) goctr_w2v_destroy(h);
+    goctr_corpus_destroy(c);
+    throw;
+  }
+  return ResidentModel(h, c, V, dim);
+}
 }  // namespace embedding
 
 namespace search {
@@ -511,11 +576,20 @@ class Searcher {
     ensure_init();
     check(goctr_searcher_create(vec_.data(), (int64_t)words_.size(), dim, &h_));
   }
+  // search.New over a resident model's WordVector(vector.Agg) rows, copied device to device; the words are its ids.
+  // SearchInternal needs the query row on the host: use SearchVector, or a Searcher made from host vectors.
+  explicit Searcher(const embedding::ResidentModel& m) : dim_(m.dim) {
+    for (int64_t id : m.Ids()) words_.push_back(std::to_string(id));
+    check(goctr_searcher_create_from_w2v(m.handle(), &h_));
+  }
+  // the items replaced by the model's current vectors (same V and dim), under the searcher's lock
+  void Refresh(const embedding::ResidentModel& m) { check(goctr_searcher_load_w2v(h_, m.handle())); vec_.clear(); }
   ~Searcher() { if (h_) goctr_searcher_destroy(h_); }
   Searcher(const Searcher&) = delete;
   Searcher& operator=(const Searcher&) = delete;
   Neighbors SearchVector(const std::vector<double>& query, int k) { return search(query.data(), k, -1); }
   Neighbors SearchInternal(const std::string& word, int k) {
+    if (vec_.empty()) throw std::runtime_error("this searcher's items live on the device only: query by vector");
     for (size_t i = 0; i < words_.size(); ++i)
       if (words_[i] == word) return search(vec_.data() + i * (size_t)dim_, k, (int64_t)i);
     throw std::runtime_error(word + " is not found in searcher");   // search.go:73-75

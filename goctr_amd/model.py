@@ -307,6 +307,16 @@ class EmbeddingTable:
         capi.check(capi.load().goctr_emb_create(C.c_int64(self.V), C.c_int(self.D), capi.ptr(rows, C.c_float),
                                                 C.byref(self._h)))
 
+    @classmethod
+    def zeros(cls, V: int, D: int):
+        """an all-zero table made on the device (nothing is uploaded): what embedding.Word2Vec.load_table fills in place"""
+        t = object.__new__(cls)
+        t.V, t.D = int(V), int(D)
+        t._h = C.c_void_p()
+        capi.init()
+        capi.check(capi.load().goctr_emb_create(C.c_int64(t.V), C.c_int(t.D), None, C.byref(t._h)))
+        return t
+
     def replica(self, rank):
         """this table's replica on engine `rank` (multi-device training), borrowed; None before the first such call"""
         h = C.c_void_p()

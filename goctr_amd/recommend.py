@@ -6,6 +6,7 @@ Names, argument order and error behaviour follow the Go code:
     Fitter / PredictAbstract                           rcmd.go:87-97
     GetSample                                          rcmd.go:339-460   (keys -> training rows; failing keys dropped)
     Train                                              rcmd.go:187-246
+    GetItemEmbeddingModelFromUb / TrainChain           rcmd.go:538-545, 196-246 (the whole chain, embedding model first)
     BatchPredict / Rank                                rcmd.go:277-337, 248-275
 
 The reference assembles every row on the host (string-keyed map lookups per embedding).  Here a
@@ -100,6 +101,8 @@ class DeviceRecSys:
     item_features : {itemId: feature vector [C]}   (GetItemFeature, ItemFeatureCache)
     item_embedding: {itemId: vector [D]}           (itemEmbeddingMap, rcmd.go:31-32; an item without one scores with zeros,
                                                     rcmd.go:504-507)
+                    or a trained embedding.Word2Vec (GetItemEmbeddingModelFromUb): the same table, filled in HBM by
+                    goctr_emb_load_w2v -- only the dictionary's keys (8 bytes per word) come to the host, for the item order
     ubcache       : goctr_amd.ubcache.UserBehaviorCache or None (the recSys does not implement UserBehavior, rcmd.go:512)
 
     Ids are arbitrary ints like in the reference; the dense row indices the device tables use are internal.
@@ -125,7 +128,10 @@ class DeviceRecSys:
                 self._uidx[int(u)] = len(self._uidx)
         self.U = len(next(iter(user_features.values())))
         self.C = len(next(iter(item_features.values())))
-        self.D = len(next(iter(item_embedding.values())))
+        from .embedding import Word2Vec
+        mod = item_embedding if isinstance(item_embedding, Word2Vec) else None
+        emb_keys = _model_keys(mod) if mod is not None else sorted(int(i) for i in item_embedding)
+        self.D = mod.dim if mod is not None else len(next(iter(item_embedding.values())))
         ut = np.zeros((len(self._uidx), self.U), np.float32)
         self._has_user = np.zeros(len(self._uidx), bool)
         for u, v in user_features.items():
@@ -135,17 +141,23 @@ class DeviceRecSys:
         # dense item order: every item that has features first (rows of the feature table), then embedding-only items
         self._iidx = {int(i): k for k, i in enumerate(sorted(item_features))}
         n_feat = len(self._iidx)
-        for i in sorted(item_embedding):
+        for i in emb_keys:
             if int(i) not in self._iidx:
                 self._iidx[int(i)] = len(self._iidx)
         it = np.zeros((n_feat, self.C), np.float32)
         for i, v in item_features.items():
             it[self._iidx[int(i)]] = v
-        emb = np.zeros((len(self._iidx), self.D), np.float32)
-        for i, v in item_embedding.items():
-            emb[self._iidx[int(i)]] = v
         self.user_table, self.item_table = ut, it
-        self.emb = gm.EmbeddingTable(emb)
+        # the raw item id of every dense row (dict insertion order = dense order): goctr_emb_load_w2v's row_keys
+        self._row_keys = np.fromiter(self._iidx, np.int64, len(self._iidx))
+        if mod is not None:
+            self.emb = gm.EmbeddingTable.zeros(len(self._iidx), self.D)
+            mod.load_table(self.emb, self._row_keys)
+        else:
+            emb = np.zeros((len(self._iidx), self.D), np.float32)
+            for i, v in item_embedding.items():
+                emb[self._iidx[int(i)]] = v
+            self.emb = gm.EmbeddingTable(emb)
         if ubcache is not None:
             self._remap_cache_items()
         self._h = C.c_void_p()
@@ -197,6 +209,13 @@ class DeviceRecSys:
         self._dense_cache.Append([(u, self._iidx.get(i, -1), t) for u, i, t in ev], maxLen)
         self.ubcache.Append(ev, maxLen)
 
+    def RefreshItemEmbedding(self, mod):
+        """the item-embedding table replaced by ``mod``'s vectors (a retrained embedding.Word2Vec of the same dim), in place
+        and in HBM while this recSys may be serving: a concurrent BatchPredict / Rank scores with the old table or the new
+        one.  The item set stays fixed, as the user table is: a word of ``mod`` that is no row of the table is ignored, a row
+        whose item ``mod`` does not know becomes zeros (rcmd.go:504-507).  Returns the number of rows filled."""
+        return mod.load_table(self.emb, self._row_keys)
+
     @property
     def _ub_h(self):
         return self._dense_cache.device() if self.ubcache is not None else None
@@ -227,6 +246,42 @@ class DeviceRecSys:
             self.close()
         except Exception:
             pass
+
+
+def _model_keys(mod):
+    """the dictionary keys of a trained embedding.Word2Vec as sorted ints (the words are decimal item ids, feature.go:78)"""
+    cps = getattr(mod, "corpus", None)
+    if cps is not None:
+        return sorted(int(k) for k in cps.Dictionary()[0])
+    if mod.dic.id2word:
+        return sorted(int(w) for w in mod.dic.id2word)
+    return list(range(mod.V))            # (a model made from bare counts: word i's key is i)
+
+
+def GetItemEmbeddingModelFromUb(source, capacity_words=None, seed=0, param0=None, **kw):
+    """rcmd.go:538-545: item2vec (SkipGram + hierarchical softmax, wordemb.go:9-32) over the users' item sequences with the
+    reference's constants ItemEmbWindow = 5, ItemEmbDim = 16, iter = 1 (rcmd.go:21-23, :543).
+
+    ``source``: an iterable of int64 id batches (the ItemSeqGenerator stream, feature.go:63-84), or a
+    ``ubcache.UserBehaviorCache`` holding raw item ids -- its device image is appended to the corpus on the device, every
+    user's sequence oldest first (goctr_corpus_append_ubcache).  ``kw``: embedding.Word2Vec options (min_count,
+    deterministic, subsample_threshold, ...); ``param0``: injected initial vectors (Word2Vec.TrainCorpus)."""
+    from .corpus import Corpus
+    from .embedding import Word2Vec
+    from .ubcache import UserBehaviorCache
+    opts = dict(window=ItemEmbWindow, dim=ItemEmbDim, iter=1, optimizer="hs")
+    opts.update(kw)
+    mod = Word2Vec(**opts)
+    if isinstance(source, UserBehaviorCache):
+        cap = source.info()[1] if capacity_words is None else capacity_words
+        cps = Corpus(max(int(cap), 1), mod.min_count, mod.max_count)
+        cps.append_ubcache(source, oldest_first=True)
+        cps.build()
+    else:
+        batches = [np.ascontiguousarray(b, np.int64) for b in source]
+        cap = sum(b.size for b in batches) if capacity_words is None else capacity_words
+        cps = Corpus(max(int(cap), 1), mod.min_count, mod.max_count).Load(batches)
+    return mod.TrainCorpus(cps, seed, param0=param0)
 
 
 def GetSample(recSys: DeviceRecSys, samples):
@@ -274,6 +329,19 @@ def Train(recSys: DeviceRecSys, samples, net, batchSize=200, epochs=200, earlySt
         cfg.dropout_mode, cfg.p0, cfg.p1, cfg.seed = 2, net.d0, net.d1, dropout_seed
     costs = gm.train_dataset(net, ds, cfg, emb=recSys.emb)
     return Predictor(recSys, net, predBatchSize), costs
+
+
+def TrainChain(user_features, item_features, ubcache, samples, net, itemEmbedding=None, T=UserBehaviorLen, emb_kw=None,
+               **train_kw):
+    """recommend.Train as the reference runs it (rcmd.go:196-246), every link on the device: the item-embedding model
+    (GetItemEmbeddingModelFromUb over ``ubcache`` unless ``itemEmbedding`` brings a trained one, rcmd.go:199-211) -> the
+    embedding table (GenEmbeddingMap32, :213) -> GetSample (:218) -> model.Train (:229) -> Predictor.  Returns
+    (Predictor, per-epoch costs); the model is ``predictor.itemEmbedding``, the recSys ``predictor.recSys``."""
+    mod = itemEmbedding if itemEmbedding is not None else GetItemEmbeddingModelFromUb(ubcache, **(emb_kw or {}))
+    recSys = DeviceRecSys(user_features, item_features, mod, ubcache, T)
+    pred, costs = Train(recSys, samples, net, **train_kw)
+    pred.itemEmbedding = mod
+    return pred, costs
 
 
 def BatchPredict(model: Predictor, sampleKeys):

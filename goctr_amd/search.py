@@ -43,6 +43,39 @@ class Searcher:
         capi.check(capi.load().goctr_searcher_create(capi.ptr(vec, C.c_double), C.c_int64(vec.shape[0]), C.c_int(self.dim),
                                                      C.byref(self._h)))
 
+    @classmethod
+    def from_model(cls, mod):
+        """search.New over a trained embedding.Word2Vec's WordVector(vector.Agg) rows, copied device to device
+        (goctr_searcher_create_from_w2v); the words are the model's dictionary in id order"""
+        capi.init()
+        s = cls.__new__(cls)
+        cps = getattr(mod, "corpus", None)
+        if cps is not None:
+            s.words = [str(int(k)) for k in cps.Dictionary()[0]]
+        else:               # (a model made from bare counts has no words: word i is "i")
+            s.words = list(mod.dic.id2word) if mod.dic.id2word else [str(i) for i in range(mod.V)]
+        s.dim = mod.dim
+        s._index = {}
+        for i, w in enumerate(s.words):
+            s._index.setdefault(w, i)
+        s._vec = None                   # (SearchInternal fetches the query row from the model's matrices when it needs one)
+        s._mod = mod
+        s._h = C.c_void_p()
+        capi.check(capi.load().goctr_searcher_create_from_w2v(mod._h, C.byref(s._h)))
+        return s
+
+    def refresh(self, mod):
+        """the items of this searcher replaced by ``mod``'s current vectors (same V and dim), in HBM (goctr_searcher_load_w2v)"""
+        capi.check(capi.load().goctr_searcher_load_w2v(self._h, mod._h))
+        self._vec, self._mod = None, mod
+        return self
+
+    def _vectors(self):
+        if self._vec is None:
+            m = self._mod
+            self._vec = m.get_param() + m.get_aux() if m.optimizer != "hs" else m.get_param()
+        return self._vec
+
     # ---- batched core
     def search_vectors(self, queries, k, ignore=None):
         """Q queries at once -> (idx [Q,k] int64, sim [Q,k] float64, count [Q]); idx -1 = empty neighbour."""
@@ -80,7 +113,7 @@ class Searcher:
     def SearchInternal(self, word, k):
         if word not in self._index:
             raise KeyError(f"{word} is not found in searcher")                     # search.go:73-75
-        return self.Search(self._vec[self._index[word]], k, word)
+        return self.Search(self._vectors()[self._index[word]], k, word)
 
     def close(self):
         if getattr(self, "_h", None):

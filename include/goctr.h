@@ -436,6 +436,13 @@ int goctr_w2v_upload_doc(goctr_w2v* w, const int32_t* doc, int64_t n_words, cons
 int goctr_w2v_train_resident(goctr_w2v* w, int64_t corpus_len, double* lr);
 /* GenEmbeddingMap32 (word2vec.go:298-324): param rows narrowed to float32 */
 int goctr_w2v_export_f32(goctr_w2v* w, float* out /*[V,dim]*/);
+/* WordVector(vector.Agg) (word2vec.go:249-271) of every word, float64, into dev_out [V,dim] -- a DEVICE buffer of the handle's
+ * engine; queued on the engine's main stream (goctr_sync, or any later call on that stream, orders behind it).  Hierarchical
+ * softmax: param[i]; negative sampling: param[i] + ctx[i], summed in float64.  This is the rule the three in-HBM hand-overs
+ * follow (goctr_emb_load_w2v, goctr_searcher_create_from_w2v, goctr_searcher_load_w2v).  goctr_w2v_export_f32 above narrows
+ * PARAM ONLY whatever the optimizer and keeps doing so: for a negative-sampling model the two differ.  Handles with
+ * cfg.devices > 1 are refused by all four. */
+int goctr_w2v_copy_word_vectors(goctr_w2v* w, double* dev_out /*[V,dim] device*/);
 
 /* ---------------------------------------------------------------- corpus / dictionary --------- */
 /* replaces memory.New + Corpus.Load (feature/embedding/corpus/memory/memory.go:36-102), dictionary.Add
@@ -460,6 +467,25 @@ int goctr_w2v_create_from_corpus(const goctr_w2v_cfg* cfg, goctr_corpus* c, goct
  * (subsample.go:28-52; threshold < 0: no subsampling).  Follow with goctr_w2v_train_resident(w, n_words, &lr). */
 int goctr_w2v_use_corpus(goctr_w2v* w, goctr_corpus* c, double subsample_threshold, uint64_t seed);
 int goctr_w2v_get_keep_mask(goctr_w2v* w, uint8_t* keep, int64_t n);
+/* GetItemEmbeddingModelFromUb (rcmd.go:538-545) when the item sequences ARE the behaviour cache: appends, user by user in
+ * index order, every entry of the cache with item >= 0 as an int64 token; oldest_first = 1 reverses each user's sequence
+ * (the cache is timestamp-descending, cache.go:8; ItemSeqGenerator streams ascending, example/movielens/feature.go:63).
+ * Reads ONE image of the cache (a concurrent goctr_ubcache_append is seen whole or not at all); nothing but the count crosses
+ * the bus.  Tokens that would exceed the capacity: the call is refused and the corpus is unchanged.  *n_appended may be NULL. */
+int goctr_corpus_append_ubcache(goctr_corpus* c, goctr_ubcache* ub, int oldest_first, int64_t* n_appended);
+/* GenEmbeddingMap32 (word2vec.go:298-324) + itemEmbeddingMap (rcmd.go:213, :502-505) without leaving HBM:
+ * EVERY row r of e is replaced.  key(r) = row_keys[r] (row_keys NULL: key(r) = r).  If key(r) is word i of the model's
+ * dictionary, row r = float32(WordVector(vector.Agg) row i); else row r = 0 ("item embedding not found, using zeros").
+ * The dictionary is c's id2key; c == NULL (a model made by goctr_w2v_create from host counts): word i's key is i.
+ * Vector.Agg: hierarchical softmax param[i]; negative sampling param[i] + ctx[i] summed in float64 and narrowed ONCE (Go's
+ * float32(x)) -- goctr_w2v_export_f32 narrows param only and is unchanged, so for negative sampling this call is the one that
+ * follows the reference's map.  Words under MinCount are dictionary words and keep their initial vectors; duplicate keys fill
+ * both rows; *n_filled (may be NULL) = rows that found a word; row V (the zero row missing ids gather) stays zero.
+ * Refused with the table untouched: e->D != cfg.dim, handles of different engines, c not built, c->V != the model's V,
+ * cfg.devices > 1.  Same visibility as goctr_emb_set_rows: a concurrent goctr_rank / goctr_batch_predict through a goctr_recsys
+ * that borrows e sees the old table or the new one, never a mixture.  Host traffic: row_keys in, one counter out. */
+int goctr_emb_load_w2v(goctr_emb* e, goctr_w2v* w, goctr_corpus* c /* may be NULL */,
+                       const int64_t* row_keys /* [e->V] host, or NULL */, int64_t* n_filled /* may be NULL */);
 
 /* ---------------------------------------------------------------- embedding k-NN search
  * Replaces search.Searcher (feature/embedding/search/search.go:52-134): brute-force cosine top-k over all items,
@@ -469,6 +495,13 @@ typedef struct goctr_searcher goctr_searcher;
 /* search.New (:57-63): items [V, D] float64 row-major (emb.Embedding.Vector); the norms (emb.Embedding.Norm =
  * embutil.Norm, embutil.go:21-27) are computed on the device */
 int goctr_searcher_create(const double* items, int64_t V, int D, goctr_searcher** out);
+/* search.New over a trained item2vec model's WordVector(vector.Agg) rows (float64, row index = dictionary id), copied device
+ * to device (goctr_w2v_copy_word_vectors) -- everything behind the copy is what goctr_searcher_create does, so the results
+ * are identical to a searcher made from goctr_w2v_get_param (+ goctr_w2v_get_aux for negative sampling) on the host.
+ * goctr_searcher_load_w2v: the same refresh of an EXISTING searcher of equal V and D, under the searcher's lock (a search in
+ * flight finishes on the old items). */
+int goctr_searcher_create_from_w2v(goctr_w2v* w, goctr_searcher** out);
+int goctr_searcher_load_w2v(goctr_searcher* s, goctr_w2v* w);
 void goctr_searcher_destroy(goctr_searcher* s);
 /* Searcher.Search (:92-134) for Q queries per call: queries [Q, D]; ignore [Q] = item index to skip or -1 (may be
  * NULL).  out_idx [Q, k] (-1 = the Go zero-value neighbour), out_sim [Q, k]; Rank = position + 1.  out_count [Q] =
