@@ -70,6 +70,17 @@ class GroupStat(C.Structure):
                 ("auc_num", C.c_uint64)]
 
 
+class NegSampleCfg(C.Structure):
+    """goctr_negsample_cfg (include/goctr.h)"""
+    _fields_ = [("n_neg", C.c_int32), ("weighting", C.c_int32), ("which", C.c_int32), ("max_tries", C.c_int32),
+                ("distinct", C.c_int32), ("min_history", C.c_int32), ("ts_lo", C.c_int64), ("ts_hi", C.c_int64),
+                ("seed", C.c_uint64)]
+
+
+NS_UNIFORM, NS_POPULARITY, NS_POPULARITY_075 = 0, 1, 2      # goctr_negsample_cfg.weighting
+NS_ALL, NS_NEWEST, NS_ALL_BUT_NEWEST = 0, 1, 2              # goctr_negsample_cfg.which
+
+
 # every symbol include/goctr.h declares (tests/test_capi_symbols.py checks the list against the header)
 SYMBOLS = [
     "goctr_init", "goctr_init_devices", "goctr_engine_count", "goctr_engine_call_ms", "goctr_engine_select", "goctr_comm_group_enable", "goctr_device_count", "goctr_sync", "goctr_last_error", "goctr_version", "goctr_device_info",
@@ -97,6 +108,8 @@ SYMBOLS = [
     "goctr_mlp_evaluate_resident_grouped",
     "goctr_emb_load_w2v", "goctr_w2v_copy_word_vectors", "goctr_searcher_create_from_w2v", "goctr_searcher_load_w2v",
     "goctr_corpus_append_ubcache",
+    "goctr_negsample_cfg_default", "goctr_samples_create", "goctr_samples_destroy", "goctr_samples_info", "goctr_samples_export",
+    "goctr_samples_get_weights", "goctr_dataset_create_samples",
 ]
 
 _lib = None
@@ -117,7 +130,7 @@ def load() -> C.CDLL:
         _lib.goctr_mlp_nparams.restype = C.c_size_t
         for name in ("goctr_model_destroy", "goctr_emb_destroy", "goctr_dataset_destroy", "goctr_mlp_destroy",
                      "goctr_w2v_destroy", "goctr_searcher_destroy", "goctr_ubcache_destroy", "goctr_recsys_destroy", "goctr_train_cfg_default", "goctr_mlp_cfg_default",
-                     "goctr_w2v_cfg_default"):
+                     "goctr_w2v_cfg_default", "goctr_negsample_cfg_default", "goctr_samples_destroy"):
             getattr(_lib, name).restype = None
         _bm = C.POINTER(BinaryMetrics)
         _lib.goctr_metrics_binary.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, _bm]
@@ -143,6 +156,15 @@ def load() -> C.CDLL:
         _lib.goctr_searcher_create_from_w2v.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
         _lib.goctr_searcher_load_w2v.argtypes = [C.c_void_p, C.c_void_p]
         _lib.goctr_corpus_append_ubcache.argtypes = [C.c_void_p, C.c_void_p, C.c_int, _i64]
+        _f32, _u64 = C.POINTER(C.c_float), C.POINTER(C.c_uint64)
+        _lib.goctr_negsample_cfg_default.argtypes = [C.POINTER(NegSampleCfg)]
+        _lib.goctr_samples_create.argtypes = [C.c_void_p, C.c_int64, C.POINTER(NegSampleCfg), C.POINTER(C.c_void_p)]
+        _lib.goctr_samples_destroy.argtypes = [C.c_void_p]
+        _lib.goctr_samples_info.argtypes = [C.c_void_p, _i64, _i64, _i64, _i64, _u64]
+        _lib.goctr_samples_export.argtypes = [C.c_void_p, _i32, _i32, _i64, _f32]
+        _lib.goctr_samples_get_weights.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), _u64]
+        _lib.goctr_dataset_create_samples.argtypes = [C.c_void_p, _f32, C.c_int64, C.c_int, _f32, C.c_int64, C.c_int, C.c_void_p,
+                                                      C.c_int, C.POINTER(C.c_void_p)]
     return _lib
 
 
@@ -236,6 +258,14 @@ def device_info():
 def default_train_cfg(**kw) -> TrainCfg:
     c = TrainCfg()
     load().goctr_train_cfg_default(C.byref(c))
+    for k, v in kw.items():
+        setattr(c, k, v)
+    return c
+
+
+def default_negsample_cfg(**kw) -> NegSampleCfg:
+    c = NegSampleCfg()
+    load().goctr_negsample_cfg_default(C.byref(c))
     for k, v in kw.items():
         setattr(c, k, v)
     return c

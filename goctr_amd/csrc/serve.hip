@@ -1,4 +1,4 @@
-// serve.hip -- the behaviour cache and key datasets (goctr_ubcache_*, goctr_dataset_create_keys) and serving
+// serve.hip -- the behaviour cache and key datasets (goctr_ubcache_*, goctr_dataset_create_keys / _create_samples) and serving
 // (goctr_recsys_*, goctr_batch_predict, goctr_rank, goctr_predict_dense) over the forward launches of the step (ctr.hip).
 #define GOCTR_NO_PLAIN_KERNELS      // the kernel headers' plain kernels belong to ctr.hip
 #include <algorithm>
@@ -10,6 +10,7 @@
 #include <shared_mutex>
 
 #include "ctr_model.h"
+#include "negsample.h"
 #include "ubcache.h"
 
 // ------------------------------------------------------------------ device-side sample assembly
@@ -88,6 +89,26 @@ __global__ __launch_bounds__(256) void assemble_keys_kernel(const long long* __r
     for (int j = lane; j < C; j += 64) cfeat[r * C + j] = iok ? item_table[(long long)it * C + j] : 0.f;
   }
 }
+
+// The body goctr_dataset_create_keys and goctr_dataset_create_samples share: the keys are on the device (d->users,
+// d->item_ids, key_ts), the feature tables come from the host; one assembly launch over one image of the cache.
+int assemble_key_dataset(goctr_ubcache* c, const float* user_table, int64_t n_users, int U, const float* item_table,
+                         int64_t n_items, int C, goctr_dataset* d, const long long* key_ts, int64_t rows, int T) {
+  d->id_mode = true; d->rows = rows; d->U = U; d->C = C; d->T = T;
+  DevBuf<float> dut, dit;
+  if (dut.alloc((size_t)n_users * U, false) || (U && dut.upload(user_table, (size_t)n_users * U))) return -1;
+  if (dit.alloc((size_t)n_items * C, false) || (C && dit.upload(item_table, (size_t)n_items * C))) return -1;
+  if (d->ub_ids.alloc((size_t)rows * T, false)) return -1;
+  if (d->ufeat.alloc((size_t)rows * U, false) || d->cfeat.alloc((size_t)rows * C, false)) return -1;
+  UbRead image(c, engine().stream);
+  hipLaunchKernelGGL(assemble_keys_kernel, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, engine().stream, c->off.p, c->items.p,
+                     c->ts.p, (long long)c->n_users, dut.p, U, dit.p, (long long)n_items, C, d->users.p, d->item_ids.p, key_ts,
+                     (long long)rows, T, d->ub_ids.p, d->ufeat.p, d->cfeat.p, (int32_t*)nullptr, (unsigned char*)nullptr);
+  GOCTR_HIP(hipGetLastError());
+  GOCTR_HIP(hipStreamSynchronize(engine().stream));   // the temporaries above are released on return
+  image.done();
+  return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -148,24 +169,38 @@ int goctr_dataset_create_keys(goctr_ubcache* c, const float* user_table, int64_t
               (long long)n_users, (long long)c->n_users);
   GOCTR_CHECK((U == 0 || user_table) && (C == 0 || item_table), "goctr_dataset_create_keys: feature table missing");
   std::unique_ptr<goctr_dataset> d(new goctr_dataset);
-  d->id_mode = true; d->rows = rows; d->U = U; d->C = C; d->T = T;
-  DevBuf<float> dut, dit; DevBuf<long long> dts;
-  DevBuf<int32_t>& du = d->users;      // stays resident: the rows' groups for goctr_evaluate_dataset_grouped
+  DevBuf<long long> dts;
   std::vector<long long> t(rows, 0);
   if (ts) for (int64_t i = 0; i < rows; ++i) t[i] = ts[i];
-  if (dut.alloc((size_t)n_users * U, false) || (U && dut.upload(user_table, (size_t)n_users * U))) return -1;
-  if (dit.alloc((size_t)n_items * C, false) || (C && dit.upload(item_table, (size_t)n_items * C))) return -1;
-  if (du.alloc(rows, false) || du.upload(users, rows) || dts.alloc(rows, false) || dts.upload(t.data(), rows)) return -1;
-  if (d->ub_ids.alloc((size_t)rows * T, false) || d->item_ids.alloc(rows, false) || d->item_ids.upload(items, rows)) return -1;
-  if (d->ufeat.alloc((size_t)rows * U, false) || d->cfeat.alloc((size_t)rows * C, false)) return -1;
-  UbRead image(c, engine().stream);
-  hipLaunchKernelGGL(assemble_keys_kernel, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, engine().stream, c->off.p, c->items.p,
-                     c->ts.p, (long long)c->n_users, dut.p, U, dit.p, (long long)n_items, C, du.p, d->item_ids.p, dts.p,
-                     (long long)rows, T, d->ub_ids.p, d->ufeat.p, d->cfeat.p, (int32_t*)nullptr, (unsigned char*)nullptr);
-  GOCTR_HIP(hipGetLastError());
-  GOCTR_HIP(hipStreamSynchronize(engine().stream));   // the temporaries above are released on return
-  image.done();
+  // (d->users stays resident: the rows' groups for goctr_evaluate_dataset_grouped)
+  if (d->users.alloc(rows, false) || d->users.upload(users, rows) || dts.alloc(rows, false) || dts.upload(t.data(), rows) ||
+      d->item_ids.alloc(rows, false) || d->item_ids.upload(items, rows)) return -1;
+  if (assemble_key_dataset(c, user_table, n_users, U, item_table, n_items, C, d.get(), dts.p, rows, T)) return -1;
   if (Y) { if (d->Y.alloc(rows, false) || d->Y.upload(Y, rows)) return -1; d->has_y = true; }
+  *out = d.release();
+  return 0;
+}
+
+// the same dataset from key columns that are already in HBM (goctr_samples_create): three device-to-device copies instead of
+// the key uploads; only the feature tables come from the host
+int goctr_dataset_create_samples(goctr_ubcache* c, const float* user_table, int64_t n_users, int U, const float* item_table,
+                                 int64_t n_items, int C, goctr_samples* s, int T, goctr_dataset** out) {
+  GOCTR_ENTER_H(c);
+  GOCTR_CHECK(c && s && T > 0 && out && n_items >= 0 && U >= 0 && C >= 0, "goctr_dataset_create_samples: bad arguments");
+  GOCTR_SAME_ENGINE(c, s);
+  GOCTR_CHECK(s->rows > 0, "goctr_dataset_create_samples: the samples hold no row");
+  GOCTR_CHECK(n_users == c->n_users, "goctr_dataset_create_samples: user table has %lld rows, the behaviour cache %lld users",
+              (long long)n_users, (long long)c->n_users);
+  GOCTR_CHECK((U == 0 || user_table) && (C == 0 || item_table), "goctr_dataset_create_samples: feature table missing");
+  const int64_t rows = s->rows;
+  std::unique_ptr<goctr_dataset> d(new goctr_dataset);
+  if (d->users.alloc(rows, false) || d->item_ids.alloc(rows, false) || d->Y.alloc(rows, false)) return -1;
+  hipStream_t st = engine().stream;
+  GOCTR_HIP(hipMemcpyAsync(d->users.p, s->users.p, sizeof(int32_t) * (size_t)rows, hipMemcpyDeviceToDevice, st));
+  GOCTR_HIP(hipMemcpyAsync(d->item_ids.p, s->items.p, sizeof(int32_t) * (size_t)rows, hipMemcpyDeviceToDevice, st));
+  GOCTR_HIP(hipMemcpyAsync(d->Y.p, s->y.p, sizeof(float) * (size_t)rows, hipMemcpyDeviceToDevice, st));
+  d->has_y = true;
+  if (assemble_key_dataset(c, user_table, n_users, U, item_table, n_items, C, d.get(), s->ts.p, rows, T)) return -1;
   *out = d.release();
   return 0;
 }

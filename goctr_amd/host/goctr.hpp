@@ -229,12 +229,21 @@ class RecSys {
     check(goctr_ubcache_create(n_users, ub_off.data(), ub_items.data(), ub_ts.data(), &ub_));
     check(goctr_emb_create((int64_t)item_emb.size() / D, D, item_emb.data(), &emb_));
     check(goctr_recsys_create(ub_, emb_, user_table.data(), n_users, U, item_table.data(), n_items, C, &h_));
+    user_table_ = user_table; item_table_ = item_table; n_users_ = n_users; n_items_ = n_items; U_ = U; C_ = C;
   }
   ~RecSys() { goctr_recsys_destroy(h_); goctr_emb_destroy(emb_); goctr_ubcache_destroy(ub_); }
   RecSys(const RecSys&) = delete;
   RecSys& operator=(const RecSys&) = delete;
   goctr_recsys* handle() const { return h_; }
   goctr_emb* embedding() const { return emb_; }
+  goctr_ubcache* cache() const { return ub_; }
+  int64_t n_items() const { return n_items_; }
+  // goctr_dataset_create_samples over this recSys's cache and feature tables (the caller owns the dataset)
+  goctr_dataset* DatasetFromSamples(goctr_samples* s, int T) const {
+    goctr_dataset* d = nullptr;
+    check(goctr_dataset_create_samples(ub_, user_table_.data(), n_users_, U_, item_table_.data(), n_items_, C_, s, T, &d));
+    return d;
+  }
 
   // UserBehaviorCache.Set / BatchSet / Delete / Clear (feature/ubcache/cache.go:27-55) on the live cache: users are dense user
   // indices, `off` a CSR over `users` (each sequence timestamp-descending).  Any thread, beside BatchPredict / Rank calls;
@@ -254,7 +263,80 @@ class RecSys {
 
  private:
   goctr_ubcache* ub_ = nullptr; goctr_emb* emb_ = nullptr; goctr_recsys* h_ = nullptr;
+  std::vector<float> user_table_, item_table_; int64_t n_users_ = 0, n_items_ = 0; int U_ = 0, C_ = 0;
 };
+
+// goctr_samples: labelled sample keys drawn on the device from one image of a behaviour cache (no reference counterpart: the
+// reference leaves SampleGenerator to the user); include/goctr.h states every output bit for bit
+class Samples {
+ public:
+  static goctr_negsample_cfg DefaultCfg() { goctr_negsample_cfg c; goctr_negsample_cfg_default(&c); return c; }
+  Samples(goctr_ubcache* ub, int64_t n_items, const goctr_negsample_cfg& cfg) : n_items_(n_items) {
+    ensure_init();
+    check(goctr_samples_create(ub, n_items, &cfg, &h_));
+  }
+  ~Samples() { goctr_samples_destroy(h_); }
+  Samples(const Samples&) = delete;
+  Samples& operator=(const Samples&) = delete;
+  Samples(Samples&& o) noexcept : h_(o.h_), n_items_(o.n_items_) { o.h_ = nullptr; }
+  goctr_samples* handle() const { return h_; }
+  struct Info { int64_t rows = 0, positives = 0, negatives = 0, dropped = 0; uint64_t cache_version = 0; };
+  Info info() const {
+    Info i;
+    check(goctr_samples_info(h_, &i.rows, &i.positives, &i.negatives, &i.dropped, &i.cache_version));
+    return i;
+  }
+  void Export(std::vector<int32_t>& users, std::vector<int32_t>& items, std::vector<int64_t>& ts, std::vector<float>& y) const {
+    const size_t n = (size_t)info().rows;
+    users.resize(n); items.resize(n); ts.resize(n); y.resize(n);
+    check(goctr_samples_export(h_, users.data(), items.data(), ts.data(), y.data()));
+  }
+  std::vector<uint32_t> Weights(uint64_t* total = nullptr) const {
+    std::vector<uint32_t> w((size_t)n_items_);
+    check(goctr_samples_get_weights(h_, w.data(), total));
+    return w;
+  }
+
+ private:
+  goctr_samples* h_ = nullptr; int64_t n_items_ = 0;
+};
+
+// the recSys's own cache sampled over the rows of its item feature table
+inline Samples SampleFromBehavior(RecSys& rs, const goctr_negsample_cfg& cfg) { return Samples(rs.cache(), rs.n_items(), cfg); }
+
+// Train for implicit feedback: every cache entry but each user's newest with n_neg sampled negatives, then model.Train's
+// step over the assembled dataset; returns the per-epoch costs
+inline std::vector<float> TrainImplicit(RecSys& rs, model::CtrNet& net, int n_neg = 4, uint64_t seed = 0, int batchSize = 200,
+                                        int epochs = 200, int earlyStop = 20) {
+  goctr_negsample_cfg sc = Samples::DefaultCfg();
+  sc.n_neg = n_neg; sc.seed = seed; sc.which = GOCTR_NS_ALL_BUT_NEWEST;
+  Samples smp = SampleFromBehavior(rs, sc);
+  goctr_dataset* d = rs.DatasetFromSamples(smp.handle(), net.T);
+  goctr_train_cfg cfg;
+  goctr_train_cfg_default(&cfg);
+  cfg.batch = batchSize; cfg.epochs = epochs; cfg.early_stop = earlyStop;
+  std::vector<float> costs((size_t)std::max(epochs, 1));
+  int ran = 0;
+  const int rc = goctr_train_dataset(net.Vm(), rs.embedding(), d, &cfg, costs.data(), &ran);
+  goctr_dataset_destroy(d);
+  check(rc);
+  costs.resize((size_t)ran);
+  return costs;
+}
+
+// leave-one-out ranking evaluation: every user's newest entry against n_neg sampled negatives, judged per user on the device
+inline goctr_group_metrics EvaluateLeaveOneOut(RecSys& rs, model::CtrNet& net, int n_neg = 99, int k = 10, uint64_t seed = 1,
+                                               int predBatch = 4096) {
+  goctr_negsample_cfg sc = Samples::DefaultCfg();
+  sc.n_neg = n_neg; sc.seed = seed; sc.which = GOCTR_NS_NEWEST;
+  Samples smp = SampleFromBehavior(rs, sc);
+  goctr_dataset* d = rs.DatasetFromSamples(smp.handle(), net.T);
+  goctr_group_metrics r{};
+  const int rc = goctr_evaluate_dataset_grouped(net.Vm(), rs.embedding(), d, predBatch, nullptr, k, nullptr, &r);
+  goctr_dataset_destroy(d);
+  check(rc);
+  return r;
+}
 
 // rcmd.go:277-337.  Throws when the first key fails (rcmd.go:293-296) and -- the reference's named-result quirk -- when
 // the last one does (rcmd.go:291,325-336); keys failing in between score as the all-zero row (rcmd.go:299-302).

@@ -412,8 +412,24 @@ class Dataset:
         d._dims = (T, ut.shape[1], it.shape[1])
         return d
 
+    @staticmethod
+    def samples(ubc, user_table, item_table, samples, T):
+        """keys() with the key columns and labels taken from a sampling.Samples handle, on the device
+        (goctr_dataset_create_samples): only the two feature tables cross PCIe"""
+        ut = capi.f32(user_table)
+        it = capi.f32(item_table)
+        h = C.c_void_p()
+        rows = samples.rows
+        capi.check(capi.load().goctr_dataset_create_samples(ubc.device() if hasattr(ubc, "device") else ubc,
+                                                            capi.ptr(ut, C.c_float), C.c_int64(ut.shape[0]), C.c_int(ut.shape[1]),
+                                                            capi.ptr(it, C.c_float), C.c_int64(it.shape[0]), C.c_int(it.shape[1]),
+                                                            samples._h, C.c_int(T), C.byref(h)))
+        d = Dataset(h, rows)
+        d._dims = (T, ut.shape[1], it.shape[1])
+        return d
+
     def get_ids(self):
-        """(ub_ids [rows,T], user_feat [rows,U], ctx_feat [rows,C]) of a dataset built by keys()"""
+        """(ub_ids [rows,T], user_feat [rows,U], ctx_feat [rows,C]) of a dataset built by keys() or samples()"""
         T, U, Cc = self._dims
         ub = np.empty((self.rows, T), np.int32)
         uf = np.empty((self.rows, U), np.float32)

@@ -7,6 +7,7 @@ Names, argument order and error behaviour follow the Go code:
     GetSample                                          rcmd.go:339-460   (keys -> training rows; failing keys dropped)
     Train                                              rcmd.go:187-246
     GetItemEmbeddingModelFromUb / TrainChain           rcmd.go:538-545, 196-246 (the whole chain, embedding model first)
+    SampleFromBehavior / TrainImplicit / EvaluateLeaveOneOut   (no counterpart: samples drawn on the device from the cache)
     BatchPredict / Rank                                rcmd.go:277-337, 248-275
 
 The reference assembles every row on the host (string-keyed map lookups per embedding).  Here a
@@ -322,8 +323,13 @@ def Train(recSys: DeviceRecSys, samples, net, batchSize=200, epochs=200, earlySt
     """rcmd.go:187-246 for a DIN / YouTube net (``net`` = model.NewDinNet(...) / NewYoutubeDnn(...)): GetSample ->
     model.Train -> Predictor.  Returns (Predictor, per-epoch costs).  ``devices=n`` (after ``capi.init_devices``): the same call
     data-parallel over n engines, batchSize staying the global batch (no reference counterpart)."""
-    from . import model as gm
     ds, _si, _kept = GetSample(recSys, samples)
+    return _train_on(recSys, ds, net, batchSize, epochs, earlyStop, dropout_seed, predBatchSize, devices)
+
+
+def _train_on(recSys, ds, net, batchSize, epochs, earlyStop, dropout_seed, predBatchSize, devices):
+    """model.Train over an assembled dataset -> (Predictor, per-epoch costs): what Train and TrainImplicit share"""
+    from . import model as gm
     cfg = capi.default_train_cfg(batch=batchSize, epochs=epochs, early_stop=earlyStop, dropout_mode=0, devices=devices)
     if dropout_seed is not None and (net.d0 > 0 or net.d1 > 0):
         cfg.dropout_mode, cfg.p0, cfg.p1, cfg.seed = 2, net.d0, net.d1, dropout_seed
@@ -342,6 +348,48 @@ def TrainChain(user_features, item_features, ubcache, samples, net, itemEmbeddin
     pred, costs = Train(recSys, samples, net, **train_kw)
     pred.itemEmbedding = mod
     return pred, costs
+
+
+def SampleFromBehavior(recSys: DeviceRecSys, **cfg):
+    """EXTENSION (the reference leaves SampleGenerator to the user): labelled samples drawn on the device from the recSys's own
+    behaviour cache -- every selected entry a positive with the history strictly before it, followed by sampled items the
+    user never interacted with (sampling.Samples; ``cfg``: goctr_negsample_cfg fields, weighting / which also by name).
+    Items are drawn among the rows of the item feature table.  Returns (model.Dataset, SampleInfo, Samples); no key and
+    no label passes through the host."""
+    from . import model as gm
+    from .sampling import Samples
+    if recSys.ubcache is None:
+        raise RuntimeError("this recSys has no behaviour cache to sample from (it does not implement UserBehavior, rcmd.go:512)")
+    smp = Samples(recSys._dense_cache, recSys.item_table.shape[0], **cfg)
+    if smp.rows == 0:
+        raise SampleVectorError("the behaviour cache holds no entry that qualifies as a positive")
+    ds = gm.Dataset.samples(recSys._dense_cache, recSys.user_table, recSys.item_table, smp, recSys.T)
+    return ds, SampleInfo.from_dims(recSys.U, recSys.T, recSys.D, recSys.C), smp
+
+
+def TrainImplicit(recSys: DeviceRecSys, net, n_neg=4, seed=0, sample_kw=None, batchSize=200, epochs=200, earlyStop=20,
+                  dropout_seed=42, predBatchSize=4096, devices=0):
+    """Train for implicit feedback: the samples are every cache entry but each user's newest (which EvaluateLeaveOneOut holds
+    out) with ``n_neg`` sampled negatives each (SampleFromBehavior; ``sample_kw``: further goctr_negsample_cfg fields), then
+    Train's own path.  Returns (Predictor, per-epoch costs); the sampled keys are ``predictor.samples``."""
+    kw = dict(n_neg=n_neg, seed=seed, which="all_but_newest")
+    kw.update(sample_kw or {})
+    ds, _si, smp = SampleFromBehavior(recSys, **kw)
+    pred, costs = _train_on(recSys, ds, net, batchSize, epochs, earlyStop, dropout_seed, predBatchSize, devices)
+    pred.samples = smp
+    return pred, costs
+
+
+def EvaluateLeaveOneOut(model: Predictor, n_neg=99, k=10, seed=1, sample_kw=None, details=False):
+    """leave-one-out ranking evaluation: every user's newest entry against ``n_neg`` sampled negatives, scored and judged on
+    the device (goctr_evaluate_dataset_grouped over the users the dataset keeps resident): a metrics.GroupMetrics with
+    HitRate@k / NDCG@k / MRR / GAUC.  details=True: (GroupMetrics, Dataset, Samples)."""
+    from . import model as gm
+    kw = dict(n_neg=n_neg, seed=seed, which="newest")
+    kw.update(sample_kw or {})
+    ds, _si, smp = SampleFromBehavior(model.recSys, **kw)
+    out = gm.evaluate_dataset_grouped(model.net, ds, model.PredBatchSize, group=None, k=k, emb=model.recSys.emb)
+    return (out, ds, smp) if details else out
 
 
 def BatchPredict(model: Predictor, sampleKeys):

@@ -251,6 +251,55 @@ int goctr_dataset_create_keys(goctr_ubcache* c, const float* user_table /*[n_use
                               goctr_dataset** out);
 int goctr_dataset_get_ids(goctr_dataset* d, int32_t* ub_ids, float* user_feat, float* ctx_feat);
 
+/* ---- negative sampling on the device (no reference counterpart: the reference leaves SampleGenerator to the user).
+ * Labelled sample keys from ONE image of the behaviour cache: every selected entry is a positive (label 1) followed by up to
+ * n_neg sampled items the user never interacted with (label 0).  Every output is defined bit for bit (tests/negsample_ref.py
+ * is the host restatement):
+ *   valid entry    0 <= item < n_items; other entries are never positives, never counted, never drawn
+ *   count[i]       valid entries with item i over the whole image
+ *   weight w[i]    UNIFORM 1; POPULARITY count[i]; POPULARITY_075 floor((count[i]^3 * 2^16)^(1/4)) = floor(16 count^0.75)
+ *   cdf            cdf[0] = 0, cdf[i+1] = cdf[i] + w[i] in 64 bits; total = cdf[n_items]
+ *   positive       entry p (0 = newest) of user u's L entries: valid, selected by `which`, L - 1 - p >= min_history,
+ *                  ts_lo <= ts <= ts_hi
+ *   key timestamp  ts - 1 for the positive and its negatives (TimeSeq.Filter keeps Ts <= maxTs: the labelled event itself
+ *                  must stay out of the history); an entry with ts == 1 gets the key 0, which Filter reads as "from the
+ *                  newest" (cache.go:72-74)
+ *   random word    x(u,p,j,a) = mix(seed ^ mix(((uint64)u << 32 | p) ^ mix((uint64)j << 32 | a))), mix = one splitmix64 step
+ *   draw           r = floor(x * total / 2^64); the candidate is the i with cdf[i] <= r < cdf[i+1]
+ *   slot j         takes the first attempt a < max_tries whose candidate is no valid item of user u's whole sequence and,
+ *                  with `distinct`, not the accepted candidate of a lower slot; no such attempt (or total == 0): the slot
+ *                  is dropped -- counted, no row
+ *   order          users ascending, positions ascending, each positive followed by its kept negatives in slot order */
+enum { GOCTR_NS_UNIFORM = 0, GOCTR_NS_POPULARITY = 1, GOCTR_NS_POPULARITY_075 = 2 };   /* weighting */
+enum { GOCTR_NS_ALL = 0, GOCTR_NS_NEWEST = 1, GOCTR_NS_ALL_BUT_NEWEST = 2 };            /* which   */
+typedef struct {
+  int32_t  n_neg;        /* negatives per positive, 0 .. 256            default 4  */
+  int32_t  weighting;    /*                                              default GOCTR_NS_POPULARITY_075 */
+  int32_t  which;        /*                                              default GOCTR_NS_ALL */
+  int32_t  max_tries;    /* attempts per negative slot, 1 .. 64          default 16 */
+  int32_t  distinct;     /* negatives of one positive pairwise distinct  default 1  */
+  int32_t  min_history;  /* a positive needs >= this many entries BEHIND it in its sequence; default 0 */
+  int64_t  ts_lo, ts_hi; /* positives with ts_lo <= ts <= ts_hi          default INT64_MIN, INT64_MAX */
+  uint64_t seed;         /*                                              default 0 */
+} goctr_negsample_cfg;
+void goctr_negsample_cfg_default(goctr_negsample_cfg* c);
+
+typedef struct goctr_samples goctr_samples;            /* key columns resident in HBM */
+/* A cfg outside the stated ranges, n_items <= 0 or a result of >= 2^31 rows refuses the call (*out untouched).  No positive
+ * at all is not an error: rows = 0. */
+int  goctr_samples_create(goctr_ubcache* c, int64_t n_items, const goctr_negsample_cfg* cfg, goctr_samples** out);
+void goctr_samples_destroy(goctr_samples* s);
+/* each may be NULL; cache_version: the version of the image that was sampled */
+int  goctr_samples_info(goctr_samples* s, int64_t* rows, int64_t* positives, int64_t* negatives, int64_t* dropped,
+                        uint64_t* cache_version);
+int  goctr_samples_export(goctr_samples* s, int32_t* users, int32_t* items, int64_t* ts, float* y);   /* each may be NULL */
+int  goctr_samples_get_weights(goctr_samples* s, uint32_t* w /*[n_items]*/, uint64_t* total);
+/* goctr_dataset_create_keys with the key columns and labels taken from s, on the device: only the feature tables cross
+ * PCIe.  The histories come from the cache's image at THIS call.  rows == 0 refuses. */
+int  goctr_dataset_create_samples(goctr_ubcache* c, const float* user_table, int64_t n_users, int U,
+                                  const float* item_table, int64_t n_items, int C, goctr_samples* s, int T,
+                                  goctr_dataset** out);
+
 /* ---- recommend.BatchPredict / Rank (recommend/rcmd.go:277-337, 248-275) over resident feature tables.
  * A goctr_recsys bundles what GetSampleVector (rcmd.go:462-536) reads per key: the user / item feature tables (the
  * contents of UserFeatureCache / ItemFeatureCache, rcmd.go:474-491; rows indexed by DENSE user / item index), the behaviour
