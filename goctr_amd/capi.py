@@ -77,6 +77,12 @@ class NegSampleCfg(C.Structure):
                 ("seed", C.c_uint64)]
 
 
+class TopnCfg(C.Structure):
+    """goctr_topn_cfg (include/goctr.h)"""
+    _fields_ = [("k", C.c_int32), ("exclude", C.c_int32), ("pass_rows", C.c_int64)]
+
+
+TOPN_KEEP_SEEN, TOPN_DROP_ALL_SEEN, TOPN_DROP_SEEN_BEFORE = 0, 1, 2   # goctr_topn_cfg.exclude
 NS_UNIFORM, NS_POPULARITY, NS_POPULARITY_075 = 0, 1, 2      # goctr_negsample_cfg.weighting
 NS_ALL, NS_NEWEST, NS_ALL_BUT_NEWEST = 0, 1, 2              # goctr_negsample_cfg.which
 
@@ -110,6 +116,7 @@ SYMBOLS = [
     "goctr_corpus_append_ubcache",
     "goctr_negsample_cfg_default", "goctr_samples_create", "goctr_samples_destroy", "goctr_samples_info", "goctr_samples_export",
     "goctr_samples_get_weights", "goctr_dataset_create_samples",
+    "goctr_topn_cfg_default", "goctr_recommend_topn",
 ]
 
 _lib = None
@@ -130,7 +137,7 @@ def load() -> C.CDLL:
         _lib.goctr_mlp_nparams.restype = C.c_size_t
         for name in ("goctr_model_destroy", "goctr_emb_destroy", "goctr_dataset_destroy", "goctr_mlp_destroy",
                      "goctr_w2v_destroy", "goctr_searcher_destroy", "goctr_ubcache_destroy", "goctr_recsys_destroy", "goctr_train_cfg_default", "goctr_mlp_cfg_default",
-                     "goctr_w2v_cfg_default", "goctr_negsample_cfg_default", "goctr_samples_destroy"):
+                     "goctr_w2v_cfg_default", "goctr_negsample_cfg_default", "goctr_samples_destroy", "goctr_topn_cfg_default"):
             getattr(_lib, name).restype = None
         _bm = C.POINTER(BinaryMetrics)
         _lib.goctr_metrics_binary.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, _bm]
@@ -165,6 +172,10 @@ def load() -> C.CDLL:
         _lib.goctr_samples_get_weights.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), _u64]
         _lib.goctr_dataset_create_samples.argtypes = [C.c_void_p, _f32, C.c_int64, C.c_int, _f32, C.c_int64, C.c_int, C.c_void_p,
                                                       C.c_int, C.POINTER(C.c_void_p)]
+        _u8 = C.POINTER(C.c_uint8)
+        _lib.goctr_topn_cfg_default.argtypes = [C.POINTER(TopnCfg)]
+        _lib.goctr_recommend_topn.argtypes = [C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32, C.c_int64, _i32,
+                                              C.POINTER(TopnCfg), _i32, _f32, _i32, _i64, _f32, _u8, _i64]
     return _lib
 
 
@@ -266,6 +277,14 @@ def default_train_cfg(**kw) -> TrainCfg:
 def default_negsample_cfg(**kw) -> NegSampleCfg:
     c = NegSampleCfg()
     load().goctr_negsample_cfg_default(C.byref(c))
+    for k, v in kw.items():
+        setattr(c, k, v)
+    return c
+
+
+def default_topn_cfg(**kw) -> TopnCfg:
+    c = TopnCfg()
+    load().goctr_topn_cfg_default(C.byref(c))
     for k, v in kw.items():
         setattr(c, k, v)
     return c

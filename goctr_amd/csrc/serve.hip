@@ -1,5 +1,6 @@
 // serve.hip -- the behaviour cache and key datasets (goctr_ubcache_*, goctr_dataset_create_keys / _create_samples) and serving
-// (goctr_recsys_*, goctr_batch_predict, goctr_rank, goctr_predict_dense) over the forward launches of the step (ctr.hip).
+// (goctr_recsys_*, goctr_batch_predict, goctr_rank, goctr_recommend_topn's entry, goctr_predict_dense) over the forward launches
+// of the step (ctr.hip).
 #define GOCTR_NO_PLAIN_KERNELS      // the kernel headers' plain kernels belong to ctr.hip
 #include <algorithm>
 #include <atomic>
@@ -11,6 +12,7 @@
 
 #include "ctr_model.h"
 #include "negsample.h"
+#include "topn.h"
 #include "ubcache.h"
 
 // ------------------------------------------------------------------ device-side sample assembly
@@ -408,6 +410,55 @@ int serve_wait_rows(goctr_emb* e) {
   return 0;
 }
 
+// Score N keys at these pointers: the key columns dts / dus / dit (device memory, or host memory the device reads: the zero-copy
+// and BAR branches of serve_keys_pass) -> dscore [N] and the failed flags dfail [N], all launches on the slot's stream, nothing
+// waited for.  serve_keys_pass stages a request's keys and calls this; goctr_recommend_topn (topn.hip) calls it on keys its own
+// kernel wrote.  Caller: holds m->mu and the table's lock shared and ONE image of the cache (UbRead) until it has synchronised,
+// owns the slot, has called ensure_keys / ws.ensure for N rows and waited for pending weight / row writes.  host_visible: dscore
+// is pinned host memory, so a one-launch pass may stamp its workgroups' completion there (*n_stamps of them; 0: wait on the stream).
+int serve_score_keys(goctr_model* m, goctr_recsys* r, ServeSlot* s, const long long* dts, const int32_t* dus, const int32_t* dit,
+                     int64_t N, float* dscore, unsigned char* dfail, bool host_visible, unsigned* n_stamps) {
+  const int T = m->cfg.T;
+  goctr_ubcache* const c = r->ub;
+  StreamScope on_slot(s->stream);
+  RowSource src{};
+  src.rows = N; src.id_mode = 1; src.emb = r->emb->rows.p; src.V = r->emb->V;
+  // Embedding widths with a compile-time attention variant (D = 4 .. 64, a power of two) look the keys up INSIDE attn_fwd
+  // (attn_fwd_keys_kernel, or the whole pass as ctr_serve16_kernel): the assembled rows (behaviour ids, feature rows) never
+  // exist in HBM.  Other widths, tables of 4 GB and more, or GOCTR_SERVE_FUSE=0, assemble first.
+  int fgroups = 0;
+  const bool fuse = env_int("GOCTR_SERVE_FUSE", 1) != 0 && attn_fast_mode(m, src, &fgroups) != 0 && fgroups <= 16;   // (D = 4 .. 64, table < 4 GB)
+  if (fuse) {
+    src.k_users = dus; src.k_items = dit; src.k_ts = dts; src.k_failed = dfail;
+    src.ub_off = c ? c->off.p : nullptr; src.ub_items = c ? c->items.p : nullptr; src.ub_ts = c ? c->ts.p : nullptr;
+    src.user_table = r->user_table.p; src.item_table = r->item_table.p; src.n_users = r->n_users; src.n_items = r->n_items;
+  } else {
+    hipLaunchKernelGGL(assemble_keys_kernel, dim3((unsigned)cdiv(N, 4)), dim3(256), 0, s->stream,
+                       c ? c->off.p : (const long long*)nullptr, c ? c->items.p : (const int32_t*)nullptr,
+                       c ? c->ts.p : (const long long*)nullptr, (long long)r->n_users, r->user_table.p, r->U, r->item_table.p,
+                       (long long)r->n_items, r->C, dus, dit, dts, (long long)N, T, s->ub_ids.p, s->ufeat.p, s->cfeat.p,
+                       s->item_ids.p, dfail);
+    GOCTR_HIP(hipGetLastError());
+    src.ub_ids = s->ub_ids.p; src.item_ids = s->item_ids.p; src.ufeat = s->ufeat.p; src.cfeat = s->cfeat.p;
+  }
+  FwdBufs fb = s->ws.bufs();
+  fb.yhat = dscore;
+  StepOpts op;
+  op.train = false;
+  // A zero-copy pass of one launch: the kernel's workgroups stamp this pass's number into the pinned buffer behind their scores,
+  // and the host watches the stamps instead of waiting for the stream's completion signal -- for passes of up to
+  // GOCTR_SERVE_POLL_ROWS rows (default 512; 0 = never): the release fence in front of a stamp writes back the rows' h0 from the
+  // L2, which costs a 2048-row pass more than the wait saves (profiles/r05_serve_poll.txt; 256 rows until the keys went over the BAR).
+  *n_stamps = 0;
+  if (fuse && serve16_ok(m, src, (int)N)) {          // key lookup + attention + forward chain: one launch
+    const bool poll = host_visible && N <= (int64_t)env_int("GOCTR_SERVE_POLL_ROWS", 512);
+    if (poll) { if (++s->epoch == 0) s->epoch = 1; *n_stamps = (unsigned)cdiv(N, 16); }
+    if (launch_serve16(m, src, (int)N, s->st.p, fb, poll ? s->h_done : nullptr, s->epoch)) return -1;
+  } else
+  if (launch_forward(m, src, (int)N, op, s->st.p, &fb)) return -1;
+  return 0;
+}
+
 // One pass: the keys of `segs` (N rows in all, N <= SERVE_PASS_ROWS) -> scores / failed flags of every segment.
 // Caller holds m->mu shared and owns the slot.
 int serve_keys_pass(goctr_model* m, goctr_recsys* r, ServeSlot* s, KeySeg* const* segs, int nseg) {
@@ -451,44 +502,9 @@ int serve_keys_pass(goctr_model* m, goctr_recsys* r, ServeSlot* s, KeySeg* const
   const int32_t* dit = reinterpret_cast<const int32_t*>(in_base + 12 * N);
   float* dscore = reinterpret_cast<float*>(out_base);
   unsigned char* dfail = reinterpret_cast<unsigned char*>(out_base + 4 * Br);
-  goctr_ubcache* const c = r->ub;
-  UbRead image(c, s->stream);                         // one pass, one image of the cache: held until the wait below
-  StreamScope on_slot(s->stream);
-  RowSource src{};
-  src.rows = N; src.id_mode = 1; src.emb = r->emb->rows.p; src.V = r->emb->V;
-  // Embedding widths with a compile-time attention variant (D = 4 .. 64, a power of two) look the keys up INSIDE attn_fwd
-  // (attn_fwd_keys_kernel, or the whole pass as ctr_serve16_kernel): the assembled rows (behaviour ids, feature rows) never
-  // exist in HBM.  Other widths, tables of 4 GB and more, or GOCTR_SERVE_FUSE=0, assemble first.
-  int fgroups = 0;
-  const bool fuse = env_int("GOCTR_SERVE_FUSE", 1) != 0 && attn_fast_mode(m, src, &fgroups) != 0 && fgroups <= 16;   // (D = 4 .. 64, table < 4 GB)
-  if (fuse) {
-    src.k_users = dus; src.k_items = dit; src.k_ts = dts; src.k_failed = dfail;
-    src.ub_off = c ? c->off.p : nullptr; src.ub_items = c ? c->items.p : nullptr; src.ub_ts = c ? c->ts.p : nullptr;
-    src.user_table = r->user_table.p; src.item_table = r->item_table.p; src.n_users = r->n_users; src.n_items = r->n_items;
-  } else {
-    hipLaunchKernelGGL(assemble_keys_kernel, dim3((unsigned)cdiv(N, 4)), dim3(256), 0, s->stream,
-                       c ? c->off.p : (const long long*)nullptr, c ? c->items.p : (const int32_t*)nullptr,
-                       c ? c->ts.p : (const long long*)nullptr, (long long)r->n_users, r->user_table.p, r->U, r->item_table.p,
-                       (long long)r->n_items, r->C, dus, dit, dts, (long long)N, T, s->ub_ids.p, s->ufeat.p, s->cfeat.p,
-                       s->item_ids.p, dfail);
-    GOCTR_HIP(hipGetLastError());
-    src.ub_ids = s->ub_ids.p; src.item_ids = s->item_ids.p; src.ufeat = s->ufeat.p; src.cfeat = s->cfeat.p;
-  }
-  FwdBufs fb = s->ws.bufs();
-  fb.yhat = dscore;
-  StepOpts op;
-  op.train = false;
-  // A zero-copy pass of one launch: the kernel's workgroups stamp this pass's number into the pinned buffer behind their scores,
-  // and the host watches the stamps instead of waiting for the stream's completion signal -- for passes of up to
-  // GOCTR_SERVE_POLL_ROWS rows (default 512; 0 = never): the release fence in front of a stamp writes back the rows' h0 from the
-  // L2, which costs a 2048-row pass more than the wait saves (profiles/r05_serve_poll.txt; 256 rows until the keys went over the BAR).
+  UbRead image(r->ub, s->stream);                     // one pass, one image of the cache: held until the wait below
   unsigned n_stamps = 0;
-  if (fuse && serve16_ok(m, src, (int)N)) {          // key lookup + attention + forward chain: one launch
-    const bool poll = zc && N <= (int64_t)env_int("GOCTR_SERVE_POLL_ROWS", 512);
-    if (poll) { if (++s->epoch == 0) s->epoch = 1; n_stamps = (unsigned)cdiv(N, 16); }
-    if (launch_serve16(m, src, (int)N, s->st.p, fb, poll ? s->h_done : nullptr, s->epoch)) return -1;
-  } else
-  if (launch_forward(m, src, (int)N, op, s->st.p, &fb)) return -1;
+  if (serve_score_keys(m, r, s, dts, dus, dit, N, dscore, dfail, zc, &n_stamps)) return -1;
   bool want_failed = false;
   for (int k = 0; k < nseg; ++k) want_failed = want_failed || segs[k]->failed || segs[k]->n_failed >= 0;
   // scores and flags are adjacent: one copy back (the gap between them is < 128 bytes)
@@ -689,6 +705,50 @@ int goctr_rank(goctr_model* m, goctr_recsys* r, int32_t user, const int32_t* ite
               "get sample vector error: first key (user %d, item %d) has no features", user, items[0]);
   KeySeg g{nullptr, user, items, nullptr, ts, n, scores, failed, (failed || n_failed) ? 0 : -1};
   return serve_keys(m, r, g, n_failed);
+}
+
+// Top-N recommendation (topn.hip has the key generator, the seen test, the selection and the driver): this entry checks the
+// handles, takes what a serving entry takes -- the model's and the table's lock shared, a slot -- and ONE image of the cache for
+// the whole call, and lends the driver the slot's device buffers and serve_score_keys.
+int goctr_recommend_topn(goctr_model* m, goctr_recsys* r, const int32_t* users, const int64_t* ts, int64_t n_users_req,
+                         const int32_t* pool, int64_t n_pool, const int32_t* targets, const goctr_topn_cfg* cfg,
+                         int32_t* out_items, float* out_scores, int32_t* out_count, int64_t* out_target_rank, float* all_scores,
+                         uint8_t* all_flags, int64_t* n_failed) {
+  EngineScope on(handle_engine(m));
+  if (require_engine()) return -1;
+  GOCTR_CHECK(m && r && cfg, "goctr_recommend_topn: bad arguments");
+  GOCTR_SAME_ENGINE(m, r);
+  GOCTR_CHECK(r->emb->D == m->cfg.D && r->U == m->cfg.U && r->C == m->cfg.C, "goctr_recommend_topn: recsys dims (U=%d,C=%d,D=%d) != model (U=%d,C=%d,D=%d)",
+              r->U, r->C, r->emb->D, m->cfg.U, m->cfg.C, m->cfg.D);
+  const TopnArgs a{users, ts, n_users_req, pool, n_pool, targets, *cfg, out_items, out_scores, out_count, out_target_rank,
+                   all_scores, all_flags, n_failed};
+  if (topn_check_args(a, r->n_users)) return -1;
+  std::shared_lock<std::shared_mutex> lm(m->mu);        // as serve_keys: weights, then embedding rows, stay put
+  std::shared_lock<std::shared_mutex> le(r->emb->mu);
+  SlotLease lease;
+  ServeSlot* s = lease.s;
+  if (!s) return -1;
+  const int64_t pass = cfg->pass_rows ? cfg->pass_rows : TOPN_DEFAULT_PASS_ROWS;
+  const int64_t cap_rows = std::max<int64_t>(pass, SERVE_COALESCE_ROWS);
+  if (s->ensure_keys(cap_rows, m->cfg.T, r->U, r->C)) return -1;
+  if (s->ws.ensure((int)cap_rows, m->Ip, m->cfg.T, m->H1p, m->H2p, !chain_ok(m), s->stream)) return -1;
+  if (serve_wait_weights(m, s) || serve_wait_rows(r->emb)) return -1;
+  goctr_ubcache* const c = r->ub;
+  UbRead image(c, s->stream);                           // one image for every pass: held until topn_run has synchronised
+  TopnScorer sc;
+  sc.stream = s->stream; sc.n_users = r->n_users; sc.n_items = r->n_items;
+  sc.ub_off = c ? c->off.p : nullptr; sc.ub_items = c ? c->items.p : nullptr; sc.ub_ts = c ? c->ts.p : nullptr;
+  sc.max_rows = s->cap; sc.keys = s->d_in.p; sc.out = s->d_out.p;
+  sc.score = [&](int64_t N) {
+    const size_t Br = (size_t)round_up((int)N, 32);
+    unsigned n_stamps = 0;
+    return serve_score_keys(m, r, s, reinterpret_cast<const long long*>(sc.keys), reinterpret_cast<const int32_t*>(sc.keys + 8 * N),
+                            reinterpret_cast<const int32_t*>(sc.keys + 12 * N), N, reinterpret_cast<float*>(sc.out),
+                            reinterpret_cast<unsigned char*>(sc.out + 4 * Br), false, &n_stamps);
+  };
+  if (topn_run(sc, a)) return -1;
+  image.done();
+  return 0;
 }
 
 // model.Predict's own convention (model/model.go:242-352): `rows` dense TrainSample rows in HOST memory -> y_out [rows].

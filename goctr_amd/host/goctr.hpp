@@ -367,6 +367,43 @@ inline std::vector<ItemScore> Rank(model::CtrNet& net, RecSys& rs, int userId, c
   for (size_t i = 0; i < itemIds.size(); ++i) out[i] = ItemScore{itemIds[i], y[i]};
   return out;
 }
+
+// Top-N recommendation (goctr_recommend_topn; no reference counterpart -- what the endpoint's empty-itemIdList branch,
+// recommend/api.go:115-118, would call): the pool (empty = every item of the feature table) is scored for each user on the
+// device and the best n come back, items the user has seen left out.  Users and items are dense indices like Rank's.
+struct TopN {
+  std::vector<std::vector<ItemScore>> lists;     // per request row: min(n, eligible) entries, best first
+  std::vector<int64_t> target_rank;              // per request row when targets were given: 0-based rank, -1 = not ranked
+  int64_t n_failed = 0;
+};
+inline TopN RecommendBatch(model::CtrNet& net, RecSys& rs, const std::vector<int32_t>& users, int n = 10,
+                           const std::vector<int64_t>& ts = {}, const std::vector<int32_t>& pool = {},
+                           int exclude = GOCTR_TOPN_DROP_ALL_SEEN, const std::vector<int32_t>& targets = {}, int64_t pass_rows = 0) {
+  goctr_topn_cfg cfg;
+  goctr_topn_cfg_default(&cfg);
+  cfg.k = n; cfg.exclude = exclude; cfg.pass_rows = pass_rows;
+  const int64_t nq = (int64_t)users.size(), np = pool.empty() ? rs.n_items() : (int64_t)pool.size();
+  if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("RecommendBatch: one timestamp per user");
+  if (!targets.empty() && targets.size() != users.size()) throw std::invalid_argument("RecommendBatch: one target per user");
+  if (n < 1) throw std::invalid_argument("RecommendBatch: n must be positive");
+  std::vector<int32_t> items((size_t)nq * n), count((size_t)nq);
+  std::vector<float> scores((size_t)nq * n);
+  TopN out;
+  if (!targets.empty()) out.target_rank.resize((size_t)nq);
+  check(goctr_recommend_topn(net.Vm(), rs.handle(), users.data(), ts.empty() ? nullptr : ts.data(), nq,
+                             pool.empty() ? nullptr : pool.data(), np, targets.empty() ? nullptr : targets.data(), &cfg,
+                             items.data(), scores.data(), count.data(), targets.empty() ? nullptr : out.target_rank.data(),
+                             nullptr, nullptr, &out.n_failed));
+  out.lists.resize((size_t)nq);
+  for (int64_t q = 0; q < nq; ++q)
+    for (int j = 0; j < count[(size_t)q]; ++j)
+      out.lists[(size_t)q].push_back(ItemScore{items[(size_t)q * n + j], scores[(size_t)q * n + j]});
+  return out;
+}
+inline std::vector<ItemScore> Recommend(model::CtrNet& net, RecSys& rs, int userId, int n, int64_t now,
+                                        const std::vector<int32_t>& pool = {}, int exclude = GOCTR_TOPN_DROP_ALL_SEEN) {
+  return RecommendBatch(net, rs, {userId}, n, {now}, pool, exclude).lists[0];
+}
 }  // namespace recommend
 
 namespace din {

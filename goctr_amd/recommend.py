@@ -9,6 +9,8 @@ Names, argument order and error behaviour follow the Go code:
     GetItemEmbeddingModelFromUb / TrainChain           rcmd.go:538-545, 196-246 (the whole chain, embedding model first)
     SampleFromBehavior / TrainImplicit / EvaluateLeaveOneOut   (no counterpart: samples drawn on the device from the cache)
     BatchPredict / Rank                                rcmd.go:277-337, 248-275
+    Recommend / RecommendBatch / EvaluateLeaveOneOutFull   (no counterpart: recommend/api.go:115-118 leaves "some default recall
+                                                       algorithm" as a todo; the whole catalogue scored and selected on the device)
 
 The reference assembles every row on the host (string-keyed map lookups per embedding).  Here a
 ``DeviceRecSys`` keeps what GetSampleVector reads -- user / item feature tables, the behaviour cache, the item-embedding
@@ -383,7 +385,12 @@ def TrainImplicit(recSys: DeviceRecSys, net, n_neg=4, seed=0, sample_kw=None, ba
 def EvaluateLeaveOneOut(model: Predictor, n_neg=99, k=10, seed=1, sample_kw=None, details=False):
     """leave-one-out ranking evaluation: every user's newest entry against ``n_neg`` sampled negatives, scored and judged on
     the device (goctr_evaluate_dataset_grouped over the users the dataset keeps resident): a metrics.GroupMetrics with
-    HitRate@k / NDCG@k / MRR / GAUC.  details=True: (GroupMetrics, Dataset, Samples)."""
+    HitRate@k / NDCG@k / MRR / GAUC.  details=True: (GroupMetrics, Dataset, Samples).
+
+    The figures are those of the SAMPLED protocol: the held-out item competes with n_neg drawn items, so its rank is at most
+    n_neg and HitRate@k / NDCG@k come out higher than against the catalogue -- an optimistic proxy whose size depends on n_neg
+    and on the sampling weights.  EvaluateLeaveOneOutFull ranks the same held-out items against every item the user has not
+    seen before and returns the exact figures; the two differ by that protocol, not by the model."""
     from . import model as gm
     kw = dict(n_neg=n_neg, seed=seed, which="newest")
     kw.update(sample_kw or {})
@@ -424,3 +431,108 @@ def Rank(model: Predictor, userId: int, itemIds, now=None):
     ts = int(time.time()) if now is None else int(now)
     y = BatchPredict(model, [Sample(userId, i, 0.0, ts) for i in itemIds])      # (an error drops the scores, :258-260)
     return [ItemScore(int(i), float(y[k, 0])) for k, i in enumerate(itemIds)]
+
+
+EXCLUDE = {"keep": capi.TOPN_KEEP_SEEN, "all": capi.TOPN_DROP_ALL_SEEN, "before": capi.TOPN_DROP_SEEN_BEFORE}
+
+
+def topn(model: Predictor, users, ts=None, pool=None, targets=None, k=10, exclude="all", pass_rows=0, validate=False):
+    """goctr_recommend_topn over DENSE indices (users [nq], ts [nq] or None, pool [np] or None = every row of the item feature
+    table, targets [nq] or None): dict(items [nq, k], scores [nq, k], count [nq], n_failed, target_rank [nq] when targets are
+    given, all_scores / all_flags [nq, np] when ``validate``).  What Recommend / RecommendBatch / EvaluateLeaveOneOutFull call."""
+    rs = model.recSys
+    users = capi.i32(users).ravel()
+    nq = users.size
+    ts = None if ts is None else np.ascontiguousarray(ts, np.int64).ravel()
+    pool = None if pool is None else capi.i32(pool).ravel()
+    targets = None if targets is None else capi.i32(targets).ravel()
+    n_pool = rs.item_table.shape[0] if pool is None else pool.size
+    if (ts is not None and ts.size != nq) or (targets is not None and targets.size != nq):
+        raise ValueError("ts and targets take one entry per request row")
+    cfg = capi.default_topn_cfg(k=int(k), exclude=EXCLUDE[exclude] if isinstance(exclude, str) else int(exclude),
+                                pass_rows=int(pass_rows))
+    kk = max(int(k), 1)
+    out = dict(items=np.full((nq, kk), -2, np.int32), scores=np.full((nq, kk), np.nan, np.float32), count=np.full(nq, -2, np.int32))
+    rank = np.full(nq, -2, np.int64) if targets is not None else None
+    all_scores = np.full((nq, n_pool), np.nan, np.float32) if validate else None
+    all_flags = np.full((nq, n_pool), 255, np.uint8) if validate else None
+    nf = C.c_int64(-2)
+    capi.check(capi.load().goctr_recommend_topn(
+        model.net._h, rs._h, capi.ptr(users, C.c_int32), capi.ptr(ts, C.c_int64), C.c_int64(nq), capi.ptr(pool, C.c_int32),
+        C.c_int64(n_pool), capi.ptr(targets, C.c_int32), C.byref(cfg), capi.ptr(out["items"], C.c_int32),
+        capi.ptr(out["scores"], C.c_float), capi.ptr(out["count"], C.c_int32), capi.ptr(rank, C.c_int64),
+        capi.ptr(all_scores, C.c_float), capi.ptr(all_flags, C.c_uint8), C.byref(nf)))
+    out["n_failed"] = nf.value
+    if rank is not None:
+        out["target_rank"] = rank
+    if validate:
+        out["all_scores"], out["all_flags"] = all_scores, all_flags
+    return out
+
+
+def RecommendBatch(model: Predictor, userIds, n=10, now=None, pool=None, exclude="all"):
+    """Recommend for several users in one device call: [[ItemScore]] in the order of userIds.  ``now``: one timestamp for all,
+    or one per user.  An unknown user raises SampleVectorError like Rank's failing first key."""
+    rs = model.recSys
+    userIds = list(userIds)
+    users = np.array([rs.user_index(u) for u in userIds], np.int32)
+    if users.size == 0:
+        return []
+    if (users < 0).any():
+        bad = userIds[int(np.flatnonzero(users < 0)[0])]
+        raise SampleVectorError(f"get sample vector error: user {bad} has no features")
+    ts = np.broadcast_to(np.asarray(int(time.time()) if now is None else now, np.int64), users.shape)
+    # an id unknown to the item feature table becomes a position that fails (index -1), like Rank's zero row
+    dense_pool = None if pool is None else np.array([rs.item_index(i) for i in pool], np.int32)
+    if dense_pool is not None and dense_pool.size == 0:
+        return [[] for _ in userIds]
+    try:
+        r = topn(model, users, ts, dense_pool, None, n, exclude)
+    except capi.GoctrError as e:
+        raise SampleVectorError(str(e)) from None
+    raw = rs._row_keys
+    return [[ItemScore(int(raw[r["items"][q, j]]), float(r["scores"][q, j])) for j in range(int(r["count"][q]))]
+            for q in range(users.size)]
+
+
+def Recommend(model: Predictor, userId: int, n=10, now=None, pool=None, exclude="all"):
+    """EXTENSION -- what the endpoint's empty-itemIdList branch (recommend/api.go:115-118, "todo: some default recall
+    algorithm") would call: the ``n`` best items for the user among ``pool`` (item ids; None = every item with a feature row),
+    scored by the model and selected on the device (goctr_recommend_topn), best first, ties by pool position.
+    ``exclude``: "all" leaves out every item of the user's behaviour sequence, "before" those at or before ``now``
+    (TimeSeq.Filter's entries), "keep" none.  Ids are mapped through the DeviceRecSys like Rank's."""
+    return RecommendBatch(model, [userId], n, now, pool, exclude)[0]
+
+
+def EvaluateLeaveOneOutFull(model: Predictor, k=10, sample_kw=None, details=False, pass_rows=0):
+    """EvaluateLeaveOneOut's held-out items -- every user's newest entry, goctr_samples with n_neg = 0, which = newest, whose key
+    timestamp is already ts - 1 -- ranked against the WHOLE catalogue instead of sampled negatives: one goctr_recommend_topn
+    call in DROP_SEEN_BEFORE mode (the items of the history the key sees are left out, the target itself stays in) returns
+    each user's exact integer rank; from those, in float64 on the host,
+        hit_rate = mean(rank < k)    ndcg = mean(1 / log2(rank + 2) if rank < k else 0)    mrr = mean(1 / (rank + 1))
+    over the users that have a rank; users whose rank is -1 (the target is no row of the item table) are left out and counted.
+    Returns dict(users, skipped, k, hit_rate, ndcg, mrr); details=True adds ranks, user and target columns (dense indices).
+    ``pass_rows``: goctr_topn_cfg.pass_rows (0 = full serving passes)."""
+    from .sampling import Samples
+    rs = model.recSys
+    if rs.ubcache is None:
+        raise RuntimeError("this recSys has no behaviour cache to hold items out of (it does not implement UserBehavior, rcmd.go:512)")
+    kw = dict(n_neg=0, which="newest")
+    kw.update(sample_kw or {})
+    smp = Samples(rs._dense_cache, rs.item_table.shape[0], **kw)
+    if smp.rows == 0:
+        raise SampleVectorError("the behaviour cache holds no entry that qualifies as a positive")
+    users, targets, ts, _y = smp.export()
+    r = topn(model, users, ts, None, targets, k, "before", pass_rows)
+    rank = r["target_rank"].astype(np.int64)
+    ok = rank >= 0
+    rk = rank[ok].astype(np.float64)
+    n = int(ok.sum())
+    nan = float("nan")
+    out = dict(users=n, skipped=int((~ok).sum()), k=int(k),
+               hit_rate=float(np.mean(rk < k)) if n else nan,
+               ndcg=float(np.mean(np.where(rk < k, 1.0 / np.log2(rk + 2.0), 0.0))) if n else nan,
+               mrr=float(np.mean(1.0 / (rk + 1.0))) if n else nan)
+    if details:
+        out.update(rank=rank, user_index=users, target_index=targets, ts=ts)
+    return out

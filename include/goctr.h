@@ -322,6 +322,62 @@ int goctr_batch_predict(goctr_model* m, goctr_recsys* r, const int32_t* users, c
 int goctr_rank(goctr_model* m, goctr_recsys* r, int32_t user, const int32_t* items, int64_t n, int64_t ts, int batch,
                float* scores, uint8_t* failed, int64_t* n_failed);
 
+/* ---- top-N recommendation on the device (no reference counterpart: recommend/api.go:115-118 answers an empty itemIdList
+ * with HTTP 400 and "todo: some default recall algorithm").  Scores a pool of items -- by default the whole catalogue -- for
+ * n_users_req request rows and keeps the best k of each; keys, scores and flags stay in HBM, the n_users_req * k results come
+ * back.  Every output is defined bit for bit (tests/topn_ref.py is the host restatement of the selection):
+ *   row space      request row q and pool position p form the key (users[q], item(p), ts[q]); item(p) = pool[p], or p when
+ *                  pool is NULL; ts NULL = every ts[q] is 0.  Duplicate pool entries are separate candidates, a user may
+ *                  appear in several request rows
+ *   refused        (-1, goctr_last_error, no output touched) a users[q] outside [0, n_users); recsys dims that differ from
+ *                  the model's; k outside 1 .. 256; exclude no GOCTR_TOPN_* value; pass_rows neither 0 nor in 16 .. 65536;
+ *                  n_users_req <= 0 or n_pool <= 0; n_users_req * n_pool >= 2^40; and the limits of the implementation,
+ *                  n_pool >= 2^31 (positions are ordered as 32-bit numbers) or n_users_req > 2^24
+ *   failed         item(p) outside [0, n_items): flag bit 0; the position is never returned, and it adds one to *n_failed
+ *                  for every request row (*n_failed = failed positions of the pool * n_users_req)
+ *   seen           item(p) equals a valid item (0 <= item < n_items) among the entries of users[q]'s sequence that the mode
+ *                  looks at, in the ONE image of the cache the call holds: DROP_ALL_SEEN the whole sequence,
+ *                  DROP_SEEN_BEFORE exactly the entries TimeSeq.Filter(ts[q], 0) keeps (cache.go:71-94: those with
+ *                  Ts <= ts[q]; ts[q] == 0 = from the newest = all), KEEP_SEEN none.  A seen position gets flag bit 1.
+ *                  A recsys without a cache has no seen position
+ *   eligible       not failed, and not seen unless item(p) == targets[q] (every position that holds the target stays in)
+ *   score          the model's prediction for the key as goctr_batch_predict computes it.  A pass of fewer than 8192 rows
+ *                  runs the kernel a goctr_batch_predict pass of that size runs (ctr_fwd16_kernel or its one-launch form)
+ *                  and rows are scored independently: bit-identical to goctr_batch_predict on the same keys.  Larger
+ *                  passes may take the 32-row-tile kernel: within the serving path's bound (1e-5 against the oracle)
+ *   order          eligible positions by score descending, then position ascending; -0 ties with +0; a NaN score sorts
+ *                  below every number, NaNs among themselves by position
+ *   outputs        out_count[q] = min(k, eligible positions of q); the first out_count[q] entries of row q of out_items /
+ *                  out_scores are item(p) and the score (its own bits: a -0 stays -0) in that order, the rest item -1,
+ *                  score +0
+ *   target rank    out_target_rank[q] = eligible positions strictly in front of the FIRST position that holds targets[q];
+ *                  -1 when targets is NULL, no position holds it, or that position failed
+ *   all_scores,    validation outputs [n_users_req, n_pool], each may be NULL: every row's score (a failed row scores as
+ *   all_flags      the all-zero row) and flag byte.  When both are NULL nothing per row crosses PCIe
+ *   pass size      the row space is scored pass_rows rows at a time (0 = 65536, a full serving pass), the target's key of
+ *                  every request row a pass touches included in that count; passes may straddle request rows.  No output
+ *                  depends on pass_rows beyond the kernel choice above: any two values below 8192 give identical bytes
+ *   concurrency    a serving entry: no engine lock, a serving slot, the model's and the table's lock shared for the call.
+ *                  A concurrent goctr_ubcache_* update is seen whole or not at all
+ * Memory beside the slot: n_items / 8 bytes per request row for the seen test (request rows are taken in groups of at most
+ * 256 MiB of it), 16 k bytes per request row for the running lists. */
+enum { GOCTR_TOPN_KEEP_SEEN = 0, GOCTR_TOPN_DROP_ALL_SEEN = 1, GOCTR_TOPN_DROP_SEEN_BEFORE = 2 };
+typedef struct {
+  int32_t k;          /* 1 .. 256 */
+  int32_t exclude;    /* GOCTR_TOPN_* */
+  int64_t pass_rows;  /* 0 = the serving default; else 16 .. 65536 rows per scoring pass */
+} goctr_topn_cfg;
+void goctr_topn_cfg_default(goctr_topn_cfg* c);   /* k 10, DROP_ALL_SEEN, 0 */
+int goctr_recommend_topn(goctr_model* m, goctr_recsys* r,
+                         const int32_t* users, const int64_t* ts /* NULL = 0 */, int64_t n_users_req,
+                         const int32_t* pool /* NULL = every item 0 .. n_items-1 */, int64_t n_pool,
+                         const int32_t* targets /* [n_users_req] or NULL */,
+                         const goctr_topn_cfg* cfg,
+                         int32_t* out_items /* [n_users_req,k] */, float* out_scores /* [n_users_req,k] */,
+                         int32_t* out_count /* [n_users_req] */, int64_t* out_target_rank /* [n_users_req] or NULL */,
+                         float* all_scores /* [n_users_req,n_pool] or NULL */, uint8_t* all_flags /* same shape or NULL */,
+                         int64_t* n_failed);
+
 /* The replica a multi-device training call (cfg.devices = n) keeps on engine `rank` (rank 0: the handle itself); NULL before
  * the first such call.  Borrowed: owned by the handle it was asked from.  For checks that the replicas are bit-identical
  * (tests, bench.py's replica checksum) -- every entry point works on it, on its own engine. */
