@@ -232,6 +232,16 @@ struct DevBuf {
   }
 };
 
+// The calling thread's engine's instance of the scratch type Ws (device buffers that grow to a high-water mark and stay), created
+// on first use.  Never destroyed: the engines' arenas may be gone by the time static destructors run at exit.
+template <class Ws>
+Ws& engine_scratch() {
+  static std::mutex mu;
+  static auto* const all = new std::map<Engine*, Ws>;
+  std::lock_guard<std::mutex> lk(mu);
+  return (*all)[&engine()];
+}
+
 // Capture `body`'s launches on stream s into an executable graph (uploaded, so that its first launch inside a timed call does not).
 // A device-wide wait from ANOTHER host thread invalidates an open capture, ThreadLocal mode notwithstanding (seen once in 14 runs
 // of tests/test_gpu_multi.py::test_missing_rank_fails_instead_of_hanging: a peer rank's thread dropping its handles --

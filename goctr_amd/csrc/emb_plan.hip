@@ -11,7 +11,7 @@
 // batches in one sort are bandwidth), temporaries bounded by 1 GiB (EMB_PLAN_TMP_MB).
 //   keys     key[p] = batch-in-chunk << bits | owner-major index of pair p's row (sentinel Vp for pad slots / missing ids:
 //            sorts behind the batch's real rows), val[p] = b << 12 | t
-//   sort     rocprim::radix_sort_pairs over the significant bits (stable); batch kb then occupies keys [kb P, (kb + 1) P)
+//   sort     radix_sort.h's radix_sort_pairs over the significant bits (stable); batch kb then occupies keys [kb P, (kb + 1) P)
 //   heads    flag[i] = key[i] starts a run of a real row; npairs[kb]
 //   scan     scan.h's exclusive prefix sum of the flags -> rank[i]
 //   offsets  one thread appends the chunk's batches to pair_off / slot_base, closes their run-start lists, tracks the maxima
@@ -19,10 +19,10 @@
 #include <cstdlib>
 #include <cstring>
 #include <string.h>
-#include <rocprim/device/device_radix_sort.hpp>
 
 #include "common.h"
 #include "emb_plan.h"
+#include "radix_sort.h"
 #include "scan.h"
 
 namespace goctr {
@@ -136,8 +136,8 @@ int emb_plan_build(const EmbPlanSource& src, int B, int T, int W, long long Vw, 
   unsigned int kbits = 0;
   while ((1ll << kbits) < chunk) ++kbits;
   size_t temp_bytes = 0;
-  GOCTR_HIP(rocprim::radix_sort_pairs(nullptr, temp_bytes, key_in.p, key_out.p, val_in.p, val_out.p, (size_t)nmax, 0u, bits + kbits, s));
-  if (temp.alloc(std::max<size_t>(temp_bytes, 16), false)) return -1;
+  if (radix_sort_pairs_bytes<false, unsigned int, unsigned int>((size_t)nmax, bits + kbits, s, &temp_bytes) ||
+      radix_sort_scratch(temp, temp_bytes)) return -1;       // sized once for the largest chunk: the sorts below find it large enough
   GOCTR_HIP(hipMemsetAsync(out.pair_off, 0, sizeof(long long), s));
   GOCTR_HIP(hipMemsetAsync(out.slot_base, 0, sizeof(long long), s));
   for (long long k0 = 0; k0 < nb; k0 += chunk) {
@@ -147,8 +147,7 @@ int emb_plan_build(const EmbPlanSource& src, int B, int T, int W, long long Vw, 
     GOCTR_HIP(hipMemsetAsync(npairs.p, 0, sizeof(unsigned int) * (size_t)kc, s));
     hipLaunchKernelGGL(emb_plan_keys_kernel, g, dim3(256), 0, s, ka, n, key_in.p, val_in.p);
     GOCTR_HIP(hipGetLastError());
-    size_t tb = temp_bytes;
-    GOCTR_HIP(rocprim::radix_sort_pairs(temp.p, tb, key_in.p, key_out.p, val_in.p, val_out.p, (size_t)n, 0u, bits + kbits, s));
+    if (radix_sort_pairs(temp, key_in.p, key_out.p, val_in.p, val_out.p, (size_t)n, bits + kbits, s)) return -1;
     hipLaunchKernelGGL(emb_plan_heads_kernel, g, dim3(256), 0, s, key_out.p, n, P, bits, sentinel, flag.p, npairs.p);
     GOCTR_HIP(hipGetLastError());
     if (exclusive_scan(flag.p, n, rank.p, tiles, scan_total.p)) return -1;

@@ -8,7 +8,7 @@
 //                   path lengths in word order and the root-first (inner node, code) fill, threaded
 //   device builder  (huffman_build_device) for vocabularies where the host builder (round 3: 243 ms at V = 10^6, 1.6 s at
 //                   V = 10^7 on 8 cores) is several training passes long:
-//     device  stable radix sort of (count, word) by count                 rocprim::radix_sort_pairs; ties keep word order = the
+//     device  stable radix sort of (count, word) by count                 radix_sort.h (rocPRIM); ties keep word order = the  
 //                                                                          reference's sort.SliceStable (huffman.go:27-29)
 //     host    the merge                                                    inherently sequential (V - 1 dependent steps)
 //     device  per leaf (in sorted order: neighbours share their ancestors) the chain length, a prefix sum of the kept path
@@ -19,7 +19,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <string.h>
-#include <rocprim/device/device_radix_sort.hpp>
 
 #include <chrono>
 #include <numeric>
@@ -27,6 +26,7 @@
 
 #include "common.h"
 #include "huffman.h"
+#include "radix_sort.h"
 #include "scan.h"
 
 namespace goctr {
@@ -217,10 +217,7 @@ int huffman_build_device(const long long* counts_host, int64_t V, int max_depth,
   for (int64_t i = 0; i < V; ++i) { GOCTR_CHECK(counts_host[i] >= 0, "huffman_build_device: negative count"); mx = std::max(mx, counts_host[i]); }
   unsigned int bits = 1;
   while (bits < 63 && (mx >> bits) != 0) ++bits;
-  size_t temp_bytes = 0;
-  GOCTR_HIP(rocprim::radix_sort_pairs(nullptr, temp_bytes, key_in.p, key_out.p, idx_in.p, order.p, (size_t)V, 0u, bits, s));
-  if (temp.alloc(std::max<size_t>(temp_bytes, 16), false)) return -1;
-  GOCTR_HIP(rocprim::radix_sort_pairs(temp.p, temp_bytes, key_in.p, key_out.p, idx_in.p, order.p, (size_t)V, 0u, bits, s));
+  if (radix_sort_pairs(temp, key_in.p, key_out.p, idx_in.p, order.p, (size_t)V, bits, s)) return -1;
   std::vector<long long> sval((size_t)V);
   GOCTR_HIP(hipMemcpyAsync(sval.data(), key_out.p, sizeof(long long) * (size_t)V, hipMemcpyDeviceToHost, s));
   GOCTR_HIP(hipStreamSynchronize(s));

@@ -12,7 +12,7 @@
 //   key build      score bits -> order-preserving unsigned key (-0 -> +0), label byte (y > 0.5), and per workgroup the
 //                  partials of P, Accuracy32's hits, the log-loss sum and the NaN-score count (a fixed array, reduced in a
 //                  fixed order: the same bits on every call)
-//   sort           rocprim::radix_sort_pairs_desc (key, label byte); the order inside a tie group does not matter
+//   sort           radix_sort.h, descending, (key, label byte); the order inside a tie group does not matter
 //   scan 1         exclusive prefix sum of the sorted labels (scan.h over the label bytes as 32-bit words of 4 rows); its sink
 //                  writes E[i] | head[i] << 31 over the sort's (now free) key input, head[i] = key[i] != key[i-1]
 //   scan 2         exclusive prefix sum of the head bits; its sink writes the row of every head at its group rank over the
@@ -24,13 +24,10 @@
 // entry points stage the caller's arrays into the two key buffers (scores over the sort input: the key build overwrites each
 // score with its own key; labels over the sort output), so they need no more.
 #include <cmath>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <rocprim/device/device_radix_sort.hpp>
 
 #include "common.h"
 #include "metrics.h"
+#include "radix_sort.h"
 #include "scan.h"
 
 namespace goctr {
@@ -156,16 +153,6 @@ struct MetricsWs {
   DevBuf<MetricsRes> res;
   void release() { kin.release(); kout.release(); temp.release(); lin.release(); lout.release(); tiles.release(); part.release(); res.release(); }
 };
-std::mutex g_ws_mu;
-// (never destroyed: the engines' arenas may be gone by the time static destructors run at exit)
-auto* const g_ws = new std::map<Engine*, std::unique_ptr<MetricsWs>>;
-
-MetricsWs& workspace() {
-  std::lock_guard<std::mutex> lk(g_ws_mu);
-  auto& w = (*g_ws)[&engine()];
-  if (!w) w.reset(new MetricsWs);
-  return *w;
-}
 
 // high-water growth of the scratch for n rows of kb-byte keys and a sort that needs temp_bytes; on failure nothing is kept
 int ensure_ws(MetricsWs& w, int64_t n, size_t kb, size_t temp_bytes, const char* who) {
@@ -173,7 +160,7 @@ int ensure_ws(MetricsWs& w, int64_t n, size_t kb, size_t temp_bytes, const char*
   const size_t want = (w.kin.n < kbytes ? kbytes : 0) + (w.kout.n < kbytes ? kbytes : 0) + (w.lin.n < lbytes ? lbytes : 0) +
                       (w.lout.n < lbytes ? lbytes : 0) + (w.temp.n < temp_bytes ? temp_bytes : 0);
   if (w.kin.ensure(kbytes, false) || w.kout.ensure(kbytes, false) || w.lin.ensure(lbytes, false) || w.lout.ensure(lbytes, false) ||
-      w.temp.ensure(std::max<size_t>(temp_bytes, 16), false) || w.tiles.ensure((size_t)cdiv(n, SCAN_TILE), false) ||
+      radix_sort_scratch(w.temp, temp_bytes) || w.tiles.ensure((size_t)cdiv(n, SCAN_TILE), false) ||
       w.part.ensure(MKEY_MAX_BLOCKS, false) || w.res.ensure(1, false)) {
     w.release();
     (void)hipGetLastError();
@@ -191,10 +178,9 @@ int run(const TS* score, const TL* y, int64_t n, goctr_binary_metrics* out, cons
   if (metrics_check_rows(n, who)) return -1;
   Engine& e = engine();
   hipStream_t s = e.stream;
-  MetricsWs& w = workspace();
+  MetricsWs& w = engine_scratch<MetricsWs>();
   size_t temp_bytes = 0;
-  GOCTR_HIP(rocprim::radix_sort_pairs_desc(nullptr, temp_bytes, (K*)nullptr, (K*)nullptr, (unsigned char*)nullptr,
-                                           (unsigned char*)nullptr, (size_t)n, 0u, 8u * (unsigned)sizeof(K), s));
+  if (radix_sort_pairs_bytes<true, K, unsigned char>((size_t)n, 8u * (unsigned)sizeof(K), s, &temp_bytes)) return -1;
   if (ensure_ws(w, n, sizeof(K), temp_bytes, who)) return -1;
   K* kin = reinterpret_cast<K*>(w.kin.p);
   K* kout = reinterpret_cast<K*>(w.kout.p);
@@ -210,7 +196,7 @@ int run(const TS* score, const TL* y, int64_t n, goctr_binary_metrics* out, cons
   hipLaunchKernelGGL((metrics_key_kernel<TS, TL, K>), dim3((unsigned)nparts), dim3(MB), 0, s, score, y, (long long)n, kin, w.lin.p,
                      w.part.p);
   GOCTR_HIP(hipGetLastError());
-  GOCTR_HIP(rocprim::radix_sort_pairs_desc(w.temp.p, temp_bytes, kin, kout, w.lin.p, w.lout.p, (size_t)n, 0u, 8u * (unsigned)sizeof(K), s));
+  if (radix_sort_pairs<true>(w.temp, kin, kout, w.lin.p, w.lout.p, (size_t)n, 8u * (unsigned)sizeof(K), s)) return -1;
   const int64_t words = cdiv(n, 4);
   if (words * 4 > n) GOCTR_HIP(hipMemsetAsync(w.lout.p + n, 0, (size_t)(words * 4 - n), s));
   unsigned int* eh = reinterpret_cast<unsigned int*>(w.kin.p);      // the sort's input is free now

@@ -12,8 +12,8 @@
 // Pipeline (all on the engine's main stream; two small copies to the host on the way, one at the end):
 //   key build      score -> order-preserving key (metrics.h score_key), word = label << 31 | group; NaN-score / negative-id counts
 //                  and the largest id (integer atomics, one set per workgroup)                        -> host: refusals, id bits
-//   sort 1         rocprim::radix_sort_pairs_desc (key, word): all key bits
-//   sort 2         rocprim::radix_sort_pairs (word, key) over bits [0, bits(max id)): group ascending; skipped for max id 0.  (The
+//   sort 1         radix_sort.h, descending, (key, word): all key bits
+//   sort 2         radix_sort.h, ascending, (word, key) over bits [0, bits(max id)): group ascending; skipped for max id 0.  (The
 //                  label sits ABOVE the id, not below it: rocPRIM's merge-sort path for mid-sized inputs builds its bit mask as
 //                  (1 << end_bit) - 1 in the key type, which is wrong for end_bit = 32 with begin_bit > 0 -- ids of 31 bits under
 //                  a low label bit would hit it; a range that starts at bit 0 and ends at most at 31 never does.)
@@ -31,13 +31,10 @@
 // Scratch per row: 2 keys + 2 words + 3 x 4 bytes (group-head flags, group heads, and E | tie head over the free word buffer; ties
 // and gidx reuse the key buffers) + rocPRIM's; per engine with a high-water mark, released whole on a failed allocation.
 #include <cmath>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <rocprim/device/device_radix_sort.hpp>
 
 #include "common.h"
 #include "metrics.h"
+#include "radix_sort.h"
 #include "scan.h"
 
 namespace goctr {
@@ -278,16 +275,6 @@ struct GroupWs {
     S.release(); stat.release(); part.release(); res.release(); disc.release();
   }
 };
-std::mutex g_ws_mu;
-// (never destroyed: the engines' arenas may be gone by the time static destructors run at exit)
-auto* const g_ws = new std::map<Engine*, std::unique_ptr<GroupWs>>;
-
-GroupWs& workspace() {
-  std::lock_guard<std::mutex> lk(g_ws_mu);
-  auto& w = (*g_ws)[&engine()];
-  if (!w) w.reset(new GroupWs);
-  return *w;
-}
 
 int ws_failed(GroupWs& w, size_t want, int64_t n, const char* who) {
   w.release();
@@ -301,7 +288,7 @@ int ensure_rows(GroupWs& w, int64_t n, size_t kb, size_t temp_bytes, const char*
   const size_t kbytes = (size_t)n * kb, rows = (size_t)n;
   const size_t want = 2 * kbytes + 4 * rows * sizeof(unsigned int) + temp_bytes;
   if (w.ka.ensure(kbytes, false) || w.kb.ensure(kbytes, false) || w.wa.ensure(rows, false) || w.wb.ensure(rows, false) ||
-      w.gflag.ensure(rows, false) || w.gheads.ensure(rows, false) || w.temp.ensure(std::max<size_t>(temp_bytes, 16), false) ||
+      w.gflag.ensure(rows, false) || w.gheads.ensure(rows, false) || radix_sort_scratch(w.temp, temp_bytes) ||
       w.tiles.ensure((size_t)cdiv(n, SCAN_TILE), false) || w.part.ensure(MKEY_MAX_BLOCKS + 1, false) || w.res.ensure(1, false) ||
       w.disc.ensure(2 * GM_KMAX, false))
     return ws_failed(w, want, n, who);
@@ -321,10 +308,9 @@ int run(const TS* score, const TL* y, const int32_t* group, int64_t n, int k, go
   if (!per_group) cap = 0;
   Engine& e = engine();
   hipStream_t s = e.stream;
-  GroupWs& w = workspace();
+  GroupWs& w = engine_scratch<GroupWs>();
   size_t temp1 = 0;
-  GOCTR_HIP(rocprim::radix_sort_pairs_desc(nullptr, temp1, (K*)nullptr, (K*)nullptr, (unsigned int*)nullptr, (unsigned int*)nullptr,
-                                           (size_t)n, 0u, 8u * (unsigned)sizeof(K), s));
+  if (radix_sort_pairs_bytes<true, K, unsigned int>((size_t)n, 8u * (unsigned)sizeof(K), s, &temp1)) return -1;
   if (ensure_rows(w, n, sizeof(K), temp1, who)) return -1;
   K* ka = reinterpret_cast<K*>(w.ka.p);
   K* kb = reinterpret_cast<K*>(w.kb.p);
@@ -359,17 +345,16 @@ int run(const TS* score, const TL* y, const int32_t* group, int64_t n, int k, go
   GOCTR_CHECK(h.nan == 0, "%s: %llu of the %lld scores are NaN (a NaN score has no place in the ranking)", who, h.nan, (long long)n);
   GOCTR_CHECK(h.neg == 0, "%s: %llu of the %lld group ids are negative", who, h.neg, (long long)n);
 
-  GOCTR_HIP(rocprim::radix_sort_pairs_desc(w.temp.p, temp1, ka, kb, w.wa.p, w.wb.p, (size_t)n, 0u, 8u * (unsigned)sizeof(K), s));
+  if (radix_sort_pairs<true>(w.temp, ka, kb, w.wa.p, w.wb.p, (size_t)n, 8u * (unsigned)sizeof(K), s)) return -1;
   unsigned bits = 0;
   while (bits < 31 && (h.maxid >> bits) != 0) ++bits;   // ceil(log2(max id + 1))
   const K* ks = kb; const unsigned int* ws = w.wb.p;    // the sorted rows
   K* kf = ka; unsigned int* wf = w.wa.p;                // the free pair
   if (bits > 0) {
     size_t temp2 = 0;
-    GOCTR_HIP(rocprim::radix_sort_pairs(nullptr, temp2, (unsigned int*)nullptr, (unsigned int*)nullptr, (K*)nullptr, (K*)nullptr,
-                                        (size_t)n, 0u, bits, s));
-    if (w.temp.ensure(std::max<size_t>(temp2, 16), false)) return ws_failed(w, temp2, n, who);
-    GOCTR_HIP(rocprim::radix_sort_pairs(w.temp.p, temp2, w.wb.p, w.wa.p, kb, ka, (size_t)n, 0u, bits, s));
+    if (radix_sort_pairs_bytes<false, unsigned int, K>((size_t)n, bits, s, &temp2)) return -1;
+    if (radix_sort_scratch(w.temp, temp2)) return ws_failed(w, temp2, n, who);
+    if (radix_sort_pairs(w.temp, w.wb.p, w.wa.p, kb, ka, (size_t)n, bits, s)) return -1;
     ks = ka; ws = w.wa.p; kf = kb; wf = w.wb.p;
   }
   unsigned int* eh = wf;                                           // E | tie head

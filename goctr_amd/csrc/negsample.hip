@@ -4,11 +4,12 @@
 // Launches of one goctr_samples_create, all on the engine's stream under the engine lock, the cache's image held (UbRead):
 //   ns_scan_users_kernel     one wavefront per user: the user's positives (ballot / popcount), the membership keys
 //                            (user << 32 | item) of its entries and their items as sort keys
-//   rocprim::radix_sort_keys + ns_run_count_kernel   the items ascending -> count[i] from the run bounds
+//   radix_sort_keys + ns_run_count_kernel   the items ascending (radix_sort.h) -> count[i] from the run bounds
 //   ns_weights_kernel        count -> uint32 weight (POPULARITY_075: a float64 estimate corrected by +-1 in 128-bit integers)
-//   scan64 (3 launches)      weights -> the 64-bit CDF; the same scan gives every user's first positive and every positive's
+//   exclusive_scan<NsAcc> (scan.h, 3 launches)   weights -> the 64-bit CDF (a POPULARITY_075 total passes 2^32 once the cache
+//                            holds a few 10^8 entries); the same scan gives every user's first positive and every positive's
 //                            first output row
-//   rocprim::radix_sort_keys the membership keys: every user's items ascending inside the user's own CSR segment
+//   radix_sort_keys          the membership keys: every user's items ascending inside the user's own CSR segment
 //   ns_fill_positives_kernel (user, position) of every positive, in output order
 //   ns_draw_small_kernel     n_neg <= 64: lanes = negative slots, 64 / G positives per wavefront (below)
 //   ns_draw_kernel           n_neg > 64: one wavefront per positive, several slots per lane
@@ -16,10 +17,11 @@
 // The host reads back two 8-byte totals (positives, rows); nothing else crosses PCIe.
 #include <climits>
 #include <memory>
-
-#include <rocprim/device/device_radix_sort.hpp>
+#include <type_traits>
 
 #include "negsample.h"
+#include "radix_sort.h"
+#include "scan.h"
 #include "ubcache.h"
 
 using namespace goctr;
@@ -96,86 +98,6 @@ __global__ __launch_bounds__(256) void ns_weights_kernel(const unsigned int* __r
   if (i >= n_items) return;
   const unsigned int c = count[i];
   w[i] = weighting == GOCTR_NS_UNIFORM ? 1u : weighting == GOCTR_NS_POPULARITY ? c : ns_weight075(c);
-}
-
-// ---- exclusive prefix sum of 32-bit values into 64 bits (scan.h sums in 32 bits; a POPULARITY_075 total passes 2^32 once the
-// cache holds a few 10^8 entries): tile sums / scan of the tile sums by one block / apply.  out[n] = the total.
-constexpr int NS_SCAN_BLOCK = 256, NS_SCAN_TILE = NS_SCAN_BLOCK * 4;
-
-__device__ __forceinline__ unsigned long long ns_block_scan(unsigned long long v, unsigned long long* total) {
-  __shared__ unsigned long long wsum[NS_SCAN_BLOCK / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned long long inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned long long t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  unsigned long long base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < NS_SCAN_BLOCK / 64; ++w) {
-    if (w < wave) base += wsum[w];
-    tot += wsum[w];
-  }
-  __syncthreads();
-  *total = tot;
-  return base + inc - v;
-}
-
-__device__ __forceinline__ void ns_scan_load(const unsigned int* in, long long i, long long n, unsigned int v[4]) {
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v[k] = i + k < n ? in[i + k] : 0u;
-}
-
-__global__ __launch_bounds__(NS_SCAN_BLOCK) void ns_scan_sums_kernel(const unsigned int* __restrict__ in, long long n,
-                                                                     unsigned long long* __restrict__ tile_sum) {
-  unsigned int v[4];
-  ns_scan_load(in, (long long)blockIdx.x * NS_SCAN_TILE + (long long)threadIdx.x * 4, n, v);
-  unsigned long long tot;
-  ns_block_scan((unsigned long long)v[0] + v[1] + v[2] + v[3], &tot);
-  if (threadIdx.x == 0) tile_sum[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(NS_SCAN_BLOCK) void ns_scan_offsets_kernel(unsigned long long* __restrict__ tile_sum, long long tiles,
-                                                                        unsigned long long* __restrict__ total) {
-  unsigned long long carry = 0;
-  for (long long t0 = 0; t0 < tiles; t0 += NS_SCAN_BLOCK) {
-    const long long t = t0 + threadIdx.x;
-    const unsigned long long v = t < tiles ? tile_sum[t] : 0ull;
-    unsigned long long tot;
-    const unsigned long long ex = ns_block_scan(v, &tot);
-    if (t < tiles) tile_sum[t] = carry + ex;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) *total = carry;
-}
-
-__global__ __launch_bounds__(NS_SCAN_BLOCK) void ns_scan_apply_kernel(const unsigned int* __restrict__ in, long long n,
-                                                                      const unsigned long long* __restrict__ tile_off,
-                                                                      unsigned long long* __restrict__ out) {
-  const long long i = (long long)blockIdx.x * NS_SCAN_TILE + (long long)threadIdx.x * 4;
-  unsigned int v[4];
-  ns_scan_load(in, i, n, v);
-  unsigned long long tot;
-  unsigned long long run = tile_off[blockIdx.x] + ns_block_scan((unsigned long long)v[0] + v[1] + v[2] + v[3], &tot);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if (i + k < n) out[i + k] = run;
-    run += v[k];
-  }
-}
-
-// out [n + 1]: out[i] = in[0] + .. + in[i - 1]
-int scan64(const unsigned int* in, long long n, unsigned long long* out, DevBuf<unsigned long long>& tiles_buf, hipStream_t s) {
-  const long long tiles = std::max<long long>(1, cdiv(n, NS_SCAN_TILE));
-  if (tiles_buf.ensure((size_t)tiles, false)) return -1;
-  hipLaunchKernelGGL(ns_scan_sums_kernel, dim3((unsigned)tiles), dim3(NS_SCAN_BLOCK), 0, s, in, n, tiles_buf.p);
-  hipLaunchKernelGGL(ns_scan_offsets_kernel, dim3(1), dim3(NS_SCAN_BLOCK), 0, s, tiles_buf.p, tiles, out + n);
-  hipLaunchKernelGGL(ns_scan_apply_kernel, dim3((unsigned)tiles), dim3(NS_SCAN_BLOCK), 0, s, in, n, tiles_buf.p, out);
-  GOCTR_HIP(hipGetLastError());
-  return 0;
 }
 
 // positive k of the output order = the (k - first[u])-th positive of its user u
@@ -437,6 +359,11 @@ struct NsScratch {
   DevBuf<char> temp;
   DevBuf<int32_t> pos_u, pos_p, cand;
 };
+using NsAcc = unsigned long long;   // running sum of the three scans: out [n + 1], out[i] = in[0] + .. + in[i - 1], out[n] the total
+static_assert(std::is_same<decltype(NsScratch::cdf.p), NsAcc*>::value, "the CDF is summed in the width it is stored in");
+int ns_scan(const unsigned int* in, long long n, NsAcc* out, DevBuf<NsAcc>& tiles) {
+  return exclusive_scan<NsAcc>(in, n, out, tiles, out + n);
+}
 
 int bits_for(long long n) {     // bits that hold 0 .. n - 1
   int b = 0;
@@ -488,17 +415,14 @@ int goctr_samples_create(goctr_ubcache* c, int64_t n_items, const goctr_negsampl
   GOCTR_HIP(hipGetLastError());
   if (nnz > 0) {
     const unsigned int end_bit = (unsigned int)bits_for(n_items + 1);
-    size_t temp_bytes = 0;
-    GOCTR_HIP(rocprim::radix_sort_keys(nullptr, temp_bytes, ws.ikeys.p, ws.ikeys_sorted.p, (size_t)nnz, 0u, end_bit, s));
-    if (ws.temp.ensure(std::max<size_t>(temp_bytes, 16), false)) return -1;
-    GOCTR_HIP(rocprim::radix_sort_keys(ws.temp.p, temp_bytes, ws.ikeys.p, ws.ikeys_sorted.p, (size_t)nnz, 0u, end_bit, s));
+    if (radix_sort_keys(ws.temp, ws.ikeys.p, ws.ikeys_sorted.p, (size_t)nnz, end_bit, s)) return -1;
     hipLaunchKernelGGL(ns_run_count_kernel, dim3((unsigned)cdiv(nnz, 256)), b256, 0, s, ws.ikeys_sorted.p, nnz, (long long)n_items,
                        ws.count.p);
   }
   hipLaunchKernelGGL(ns_weights_kernel, dim3((unsigned)cdiv(n_items, 256)), b256, 0, s, ws.count.p, (long long)n_items,
                      cfg->weighting, r->w.p);
   GOCTR_HIP(hipGetLastError());
-  if (scan64(r->w.p, n_items, ws.cdf.p, ws.tiles, s) || scan64(ws.n_pos.p, nu, ws.first.p, ws.tiles, s)) return -1;
+  if (ns_scan(r->w.p, n_items, ws.cdf.p, ws.tiles) || ns_scan(ws.n_pos.p, nu, ws.first.p, ws.tiles)) return -1;
   unsigned long long n_pos = 0;
   if (ws.first.download(&n_pos, 1, (size_t)nu) || ws.cdf.download(&r->total, 1, (size_t)n_items)) return -1;
   GOCTR_CHECK(n_pos <= (unsigned long long)INT32_MAX, "goctr_samples_create: %llu positives: rows must stay below 2^31", n_pos);
@@ -510,10 +434,7 @@ int goctr_samples_create(goctr_ubcache* c, int64_t n_items, const goctr_negsampl
     if (want_keys && r->total) {
       // every user's items ascending inside the user's own segment: the user is the key's high word
       const unsigned int end_bit = 32u + (unsigned int)bits_for(nu);
-      size_t temp_bytes = 0;
-      GOCTR_HIP(rocprim::radix_sort_keys(nullptr, temp_bytes, ws.keys.p, ws.keys_sorted.p, (size_t)nnz, 0u, end_bit, s));
-      if (ws.temp.ensure(std::max<size_t>(temp_bytes, 16), false)) return -1;
-      GOCTR_HIP(rocprim::radix_sort_keys(ws.temp.p, temp_bytes, ws.keys.p, ws.keys_sorted.p, (size_t)nnz, 0u, end_bit, s));
+      if (radix_sort_keys(ws.temp, ws.keys.p, ws.keys_sorted.p, (size_t)nnz, end_bit, s)) return -1;
       hist = ws.keys_sorted.p;
     }
     hipLaunchKernelGGL(ns_fill_positives_kernel, per_user, b256, 0, s, c->off.p, c->items.p, c->ts.p, nu, sel, ws.first.p,
@@ -530,7 +451,7 @@ int goctr_samples_create(goctr_ubcache* c, int64_t n_items, const goctr_negsampl
                          ws.pos_u.p, ws.pos_p.p, (long long)n_pos, n_neg, cfg->max_tries, cfg->distinct,
                          (unsigned long long)cfg->seed, ws.cand.p, ws.kept.p);
     GOCTR_HIP(hipGetLastError());
-    if (scan64(ws.kept.p, (long long)n_pos, ws.row0.p, ws.tiles, s)) return -1;
+    if (ns_scan(ws.kept.p, (long long)n_pos, ws.row0.p, ws.tiles)) return -1;
     if (ws.row0.download(&rows, 1, (size_t)n_pos)) return -1;
     GOCTR_CHECK(rows <= (unsigned long long)INT32_MAX, "goctr_samples_create: %llu rows: rows must stay below 2^31", rows);
     if (r->users.alloc((size_t)rows, false) || r->items.alloc((size_t)rows, false) || r->ts.alloc((size_t)rows, false) ||

@@ -1,6 +1,12 @@
-// Exclusive prefix sum of 32-bit counters in HBM (three launches: tile sums / scan of the tile sums / apply).
-// Used by the dictionary build (corpus.hip) and the sparse embedding update (emb_train.h).
+// Exclusive prefix sum of 32-bit words in HBM (three launches: tile sums / scan of the tile sums / apply), with the running sum
+// in Acc: unsigned int, or unsigned long long where a total may pass 2^32.  block_exclusive_scan is the workgroup scan under it.
+// Users: the dictionary build (corpus.hip), the sparse embedding update (emb_train.h, compiled in ctr_emb.hip), the embedding plan
+// (emb_plan.hip), the Huffman path offsets (huffman.hip), the metrics' label / tie / group scans (metrics.hip, metrics_group.hip)
+// and, in 64 bits, the sampler's CDF and row offsets (negsample.hip); ubcache.hip's ub_plan_kernel uses the workgroup scan alone,
+// on signed 64-bit deltas.
 #pragma once
+#include <algorithm>
+
 #include "common.h"
 
 namespace goctr {
@@ -8,18 +14,20 @@ namespace {
 
 constexpr int SCAN_ITEMS = 16, SCAN_BLOCK = 256, SCAN_TILE = SCAN_ITEMS * SCAN_BLOCK;
 
-__device__ __forceinline__ unsigned int block_exclusive_scan(unsigned int v, unsigned int* total) {
-  __shared__ unsigned int wsum[SCAN_BLOCK / 64];
+// every thread of a SCAN_BLOCK-wide workgroup calls it; T is unsigned int, unsigned long long or (signed) long long
+template <class T>
+__device__ __forceinline__ T block_exclusive_scan(T v, T* total) {
+  __shared__ T wsum[SCAN_BLOCK / 64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned int inc = v;
+  T inc = v;
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
-    const unsigned int t = __shfl_up(inc, o, 64);
+    const T t = __shfl_up(inc, o, 64);
     if (lane >= o) inc += t;
   }
   if (lane == 63) wsum[wave] = inc;
   __syncthreads();
-  unsigned int base = 0, tot = 0;
+  T base = 0, tot = 0;
 #pragma unroll
   for (int w = 0; w < SCAN_BLOCK / 64; ++w) {
     if (w < wave) base += wsum[w];
@@ -47,29 +55,32 @@ struct ScanIdentity {
   __device__ __forceinline__ unsigned int operator()(unsigned int v) const { return v; }
 };
 
-// map(v) is what gets summed (identity for 0 / 1 flags)
-template <class Map>
-__global__ __launch_bounds__(SCAN_BLOCK) void scan_tile_sums_kernel(const unsigned int* in, long long n, unsigned int* tile_sum, Map map) {
+// map(v) is what gets summed (identity for 0 / 1 flags), in Acc
+template <class Acc, class Map>
+__device__ __forceinline__ Acc scan_sum4(const uint4& v, Map map) {
+  return (Acc)map(v.x) + (Acc)map(v.y) + (Acc)map(v.z) + (Acc)map(v.w);
+}
+
+template <class Acc, class Map>
+__global__ __launch_bounds__(SCAN_BLOCK) void scan_tile_sums_kernel(const unsigned int* in, long long n, Acc* tile_sum, Map map) {
   const long long base = (long long)blockIdx.x * SCAN_TILE + (long long)threadIdx.x * 4;
-  unsigned int s = 0;
+  Acc s = 0;
 #pragma unroll
-  for (int j = 0; j < SCAN_SUB; ++j) {
-    const uint4 v = scan_load4(in, base + (long long)j * SCAN_BLOCK * 4, n);
-    s += map(v.x) + map(v.y) + map(v.z) + map(v.w);
-  }
-  unsigned int tot;
+  for (int j = 0; j < SCAN_SUB; ++j) s += scan_sum4<Acc>(scan_load4(in, base + (long long)j * SCAN_BLOCK * 4, n), map);
+  Acc tot;
   block_exclusive_scan(s, &tot);
   if (threadIdx.x == 0) tile_sum[blockIdx.x] = tot;
 }
 
 // one block walks the tile sums in chunks of SCAN_BLOCK; tile_sum becomes the exclusive scan, total[0] the grand total
-__global__ __launch_bounds__(SCAN_BLOCK) void scan_tile_offsets_kernel(unsigned int* tile_sum, long long tiles, unsigned long long* total) {
-  unsigned int carry = 0;
+template <class Acc>
+__global__ __launch_bounds__(SCAN_BLOCK) void scan_tile_offsets_kernel(Acc* tile_sum, long long tiles, unsigned long long* total) {
+  Acc carry = 0;
   for (long long t0 = 0; t0 < tiles; t0 += SCAN_BLOCK) {
     const long long t = t0 + threadIdx.x;
-    const unsigned int v = t < tiles ? tile_sum[t] : 0u;
-    unsigned int tot;
-    const unsigned int ex = block_exclusive_scan(v, &tot);
+    const Acc v = t < tiles ? tile_sum[t] : Acc(0);
+    Acc tot;
+    const Acc ex = block_exclusive_scan(v, &tot);
     if (t < tiles) tile_sum[t] = carry + ex;
     carry += tot;
   }
@@ -77,18 +88,18 @@ __global__ __launch_bounds__(SCAN_BLOCK) void scan_tile_offsets_kernel(unsigned 
 }
 
 // sink(i, value, rank) sees every element once with its exclusive prefix sum
-template <class Map, class Sink>
-__global__ __launch_bounds__(SCAN_BLOCK) void scan_apply_kernel(const unsigned int* in, long long n, const unsigned int* tile_off, Map map, Sink sink) {
+template <class Acc, class Map, class Sink>
+__global__ __launch_bounds__(SCAN_BLOCK) void scan_apply_kernel(const unsigned int* in, long long n, const Acc* tile_off, Map map, Sink sink) {
   const long long base = (long long)blockIdx.x * SCAN_TILE + (long long)threadIdx.x * 4;
   uint4 v[SCAN_SUB];
 #pragma unroll
   for (int j = 0; j < SCAN_SUB; ++j) v[j] = scan_load4(in, base + (long long)j * SCAN_BLOCK * 4, n);
-  unsigned int carry = tile_off[blockIdx.x];
+  Acc carry = tile_off[blockIdx.x];
 #pragma unroll
   for (int j = 0; j < SCAN_SUB; ++j) {
     const long long i = base + (long long)j * SCAN_BLOCK * 4;
-    unsigned int tot;
-    unsigned int run = carry + block_exclusive_scan(map(v[j].x) + map(v[j].y) + map(v[j].z) + map(v[j].w), &tot);
+    Acc tot;
+    Acc run = carry + block_exclusive_scan(scan_sum4<Acc>(v[j], map), &tot);
     carry += tot;
     if (i < n) sink(i, v[j].x, run);
     run += map(v[j].x);
@@ -100,26 +111,29 @@ __global__ __launch_bounds__(SCAN_BLOCK) void scan_apply_kernel(const unsigned i
   }
 }
 
+template <class Acc>
 struct ScanStore {
-  unsigned int* out;
-  __device__ __forceinline__ void operator()(long long i, unsigned int, unsigned int rank) const { out[i] = rank; }
+  Acc* out;
+  __device__ __forceinline__ void operator()(long long i, unsigned int, Acc rank) const { out[i] = rank; }
 };
 
-template <class Map, class Sink>
-int exclusive_scan_sink(const unsigned int* in, long long n, DevBuf<unsigned int>& tiles_buf, unsigned long long* total_dev, Map map, Sink sink) {
-  const long long tiles = cdiv(n, SCAN_TILE);
+// On the engine's main stream.  n == 0 still runs one (empty) tile: no sink call, *total_dev = 0.
+template <class Acc = unsigned int, class Map, class Sink>
+int exclusive_scan_sink(const unsigned int* in, long long n, DevBuf<Acc>& tiles_buf, unsigned long long* total_dev, Map map, Sink sink) {
+  const long long tiles = std::max<long long>(1, cdiv(n, SCAN_TILE));
   if (tiles_buf.ensure((size_t)tiles, false)) return -1;
   hipStream_t s = engine().stream;
-  hipLaunchKernelGGL((scan_tile_sums_kernel<Map>), dim3((unsigned)tiles), dim3(SCAN_BLOCK), 0, s, in, n, tiles_buf.p, map);
-  hipLaunchKernelGGL(scan_tile_offsets_kernel, dim3(1), dim3(SCAN_BLOCK), 0, s, tiles_buf.p, tiles, total_dev);
-  hipLaunchKernelGGL((scan_apply_kernel<Map, Sink>), dim3((unsigned)tiles), dim3(SCAN_BLOCK), 0, s, in, n, tiles_buf.p, map, sink);
+  hipLaunchKernelGGL((scan_tile_sums_kernel<Acc, Map>), dim3((unsigned)tiles), dim3(SCAN_BLOCK), 0, s, in, n, tiles_buf.p, map);
+  hipLaunchKernelGGL(scan_tile_offsets_kernel<Acc>, dim3(1), dim3(SCAN_BLOCK), 0, s, tiles_buf.p, tiles, total_dev);
+  hipLaunchKernelGGL((scan_apply_kernel<Acc, Map, Sink>), dim3((unsigned)tiles), dim3(SCAN_BLOCK), 0, s, in, n, tiles_buf.p, map, sink);
   GOCTR_HIP(hipGetLastError());
   return 0;
 }
 
-int exclusive_scan(const unsigned int* in, long long n, unsigned int* out, DevBuf<unsigned int>& tiles_buf,
-                   unsigned long long* total_dev) {
-  return exclusive_scan_sink(in, n, tiles_buf, total_dev, ScanIdentity{}, ScanStore{out});
+// out[i] = in[0] + .. + in[i - 1] for i < n
+template <class Acc = unsigned int>
+int exclusive_scan(const unsigned int* in, long long n, Acc* out, DevBuf<Acc>& tiles_buf, unsigned long long* total_dev) {
+  return exclusive_scan_sink(in, n, tiles_buf, total_dev, ScanIdentity{}, ScanStore<Acc>{out});
 }
 
 }  // namespace

@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <numeric>
 
+#include "scan.h"
 #include "ubcache.h"
 
 using namespace goctr;
@@ -39,10 +40,9 @@ struct UbPlan {
 };
 
 // One workgroup walks the touched users in chunks of 256 (k is payload-sized; a chunk is one gather of old bounds and one scan).
+static_assert(SCAN_BLOCK == 256, "a chunk of ub_plan_kernel is one workgroup scan");
 __global__ __launch_bounds__(256) void ub_plan_kernel(const long long* __restrict__ old_off, long long old_nnz, UbPlan p, int mode,
                                                       long long max_len) {
-  __shared__ long long wsum[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   long long carry = 0;
   for (long long j0 = 0; j0 < p.k; j0 += 256) {
     const long long j = j0 + threadIdx.x;
@@ -55,22 +55,8 @@ __global__ __launch_bounds__(256) void ub_plan_kernel(const long long* __restric
       if (mode == UB_APPEND && max_len > 0 && nl > max_len) nl = max_len;
       d = nl - la;
     }
-    long long inc = d;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const long long t = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += t;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    long long base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      if (w < wave) base += wsum[w];
-      tot += wsum[w];
-    }
-    __syncthreads();
-    const long long ex = carry + base + inc - d;
+    long long tot;
+    const long long ex = carry + block_exclusive_scan<long long>(d, &tot);
     if (j < p.k) { p.cum[j] = ex; p.nb[j] = b + ex; p.ne[j] = b + ex + nl; }
     carry += tot;
   }

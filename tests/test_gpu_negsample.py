@@ -166,6 +166,33 @@ def test_one_long_user():
     assert ref.positives == 5010
 
 
+@pytest.fixture(scope="module")
+def wide_cache():
+    """a catalogue of 257 tiles + 5 items of the 4096-item scan tile (the tile-offsets pass takes a second chunk of 256 tiles) and
+    9001 users with 0..2 entries each (more than two tiles of positives); none of the three scanned sizes is a multiple of 4"""
+    n_items, n_users = 257 * 4096 + 5, 9001
+    rng = np.random.default_rng(21)                         # (9059 entries, all of them positives)
+    lens = rng.integers(0, 3, n_users)
+    off = np.zeros(n_users + 1, np.int64)
+    np.cumsum(lens, out=off[1:])
+    items = rng.integers(0, n_items, int(off[-1])).astype(np.int32)
+    items[::11] = 4097                                      # one repeated item: a weight that is not 0 or 1
+    user = np.repeat(np.arange(n_users), lens)
+    pos = np.arange(int(off[-1])) - off[user]
+    ts = (1000 + 10 * (lens[user] - pos) + user % 13).astype(np.int64)     # descending inside a user
+    return off, items, ts, n_items, Cache(off, items, ts)
+
+
+@pytest.mark.parametrize("weighting", [R.UNIFORM, R.POPULARITY_075])
+def test_scans_over_many_tiles(wide_cache, weighting):
+    """the 64-bit scans (weights -> CDF, positives per user -> first, kept -> row0) over several tiles with ragged tails"""
+    off, items, ts, n_items, cache = wide_cache
+    ref, smp, _, _ = check(off, items, ts, n_items, R.Cfg(n_neg=2, weighting=weighting, seed=19), cache)
+    assert ref.positives > 2 * 4096 and ref.positives % 4 != 0 and n_items % 4 != 0 and cache.n_users % 4 != 0
+    assert ref.dropped == 0 and ref.rows == 3 * ref.positives
+    smp.close()
+
+
 def test_no_valid_entry():
     from goctr_amd import capi
     from goctr_amd.sampling import Samples
