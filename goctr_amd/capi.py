@@ -82,6 +82,17 @@ class TopnCfg(C.Structure):
     _fields_ = [("k", C.c_int32), ("exclude", C.c_int32), ("pass_rows", C.c_int64)]
 
 
+class ItemcfCfg(C.Structure):
+    """goctr_itemcf_cfg (include/goctr.h)"""
+    _fields_ = [("window", C.c_int32), ("max_len", C.c_int32), ("n_nbr", C.c_int32), ("min_co", C.c_int32),
+                ("pair_budget", C.c_int64)]
+
+
+class RecallCfg(C.Structure):
+    """goctr_recall_cfg (include/goctr.h)"""
+    _fields_ = [("history", C.c_int32), ("n_cand", C.c_int32), ("exclude", C.c_int32)]
+
+
 TOPN_KEEP_SEEN, TOPN_DROP_ALL_SEEN, TOPN_DROP_SEEN_BEFORE = 0, 1, 2   # goctr_topn_cfg.exclude
 NS_UNIFORM, NS_POPULARITY, NS_POPULARITY_075 = 0, 1, 2      # goctr_negsample_cfg.weighting
 NS_ALL, NS_NEWEST, NS_ALL_BUT_NEWEST = 0, 1, 2              # goctr_negsample_cfg.which
@@ -117,6 +128,8 @@ SYMBOLS = [
     "goctr_negsample_cfg_default", "goctr_samples_create", "goctr_samples_destroy", "goctr_samples_info", "goctr_samples_export",
     "goctr_samples_get_weights", "goctr_dataset_create_samples",
     "goctr_topn_cfg_default", "goctr_recommend_topn",
+    "goctr_itemcf_cfg_default", "goctr_itemcf_build", "goctr_itemcf_destroy", "goctr_itemcf_info", "goctr_itemcf_export",
+    "goctr_recall_cfg_default", "goctr_itemcf_recall", "goctr_recommend_itemcf",
 ]
 
 _lib = None
@@ -137,7 +150,8 @@ def load() -> C.CDLL:
         _lib.goctr_mlp_nparams.restype = C.c_size_t
         for name in ("goctr_model_destroy", "goctr_emb_destroy", "goctr_dataset_destroy", "goctr_mlp_destroy",
                      "goctr_w2v_destroy", "goctr_searcher_destroy", "goctr_ubcache_destroy", "goctr_recsys_destroy", "goctr_train_cfg_default", "goctr_mlp_cfg_default",
-                     "goctr_w2v_cfg_default", "goctr_negsample_cfg_default", "goctr_samples_destroy", "goctr_topn_cfg_default"):
+                     "goctr_w2v_cfg_default", "goctr_negsample_cfg_default", "goctr_samples_destroy", "goctr_topn_cfg_default",
+                     "goctr_itemcf_cfg_default", "goctr_recall_cfg_default", "goctr_itemcf_destroy"):
             getattr(_lib, name).restype = None
         _bm = C.POINTER(BinaryMetrics)
         _lib.goctr_metrics_binary.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, _bm]
@@ -176,6 +190,18 @@ def load() -> C.CDLL:
         _lib.goctr_topn_cfg_default.argtypes = [C.POINTER(TopnCfg)]
         _lib.goctr_recommend_topn.argtypes = [C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32, C.c_int64, _i32,
                                               C.POINTER(TopnCfg), _i32, _f32, _i32, _i64, _f32, _u8, _i64]
+        _u32 = C.POINTER(C.c_uint32)
+        _lib.goctr_itemcf_cfg_default.argtypes = [C.POINTER(ItemcfCfg)]
+        _lib.goctr_recall_cfg_default.argtypes = [C.POINTER(RecallCfg)]
+        _lib.goctr_itemcf_build.argtypes = [C.c_void_p, C.c_int64, C.POINTER(ItemcfCfg), C.POINTER(C.c_void_p)]
+        _lib.goctr_itemcf_destroy.argtypes = [C.c_void_p]
+        _lib.goctr_itemcf_info.argtypes = [C.c_void_p, _i64, _i32, _u64, _u64, _u64]
+        _lib.goctr_itemcf_export.argtypes = [C.c_void_p, _u32, _i32, _u32, _u32]
+        _lib.goctr_itemcf_recall.argtypes = [C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, C.POINTER(RecallCfg), _i32, _u32, _i32,
+                                             _i32, _i32]
+        _lib.goctr_recommend_itemcf.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32,
+                                                C.POINTER(RecallCfg), C.c_int32, C.c_int64, _i32, _f32, _i32, _i32, _i32, _i64,
+                                                _i32, _u32, _f32, _i64]
     return _lib
 
 
@@ -285,6 +311,22 @@ def default_negsample_cfg(**kw) -> NegSampleCfg:
 def default_topn_cfg(**kw) -> TopnCfg:
     c = TopnCfg()
     load().goctr_topn_cfg_default(C.byref(c))
+    for k, v in kw.items():
+        setattr(c, k, v)
+    return c
+
+
+def default_itemcf_cfg(**kw) -> ItemcfCfg:
+    c = ItemcfCfg()
+    load().goctr_itemcf_cfg_default(C.byref(c))
+    for k, v in kw.items():
+        setattr(c, k, v)
+    return c
+
+
+def default_recall_cfg(**kw) -> RecallCfg:
+    c = RecallCfg()
+    load().goctr_recall_cfg_default(C.byref(c))
     for k, v in kw.items():
         setattr(c, k, v)
     return c

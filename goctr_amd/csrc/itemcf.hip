@@ -1,0 +1,765 @@
+// itemcf.hip -- goctr_itemcf_*: item-to-item collaborative filtering over one image of the behaviour cache, the recall of a
+// request row's candidates from the neighbour lists, and goctr_recommend_itemcf's driver (include/goctr.h states the semantics;
+// tests/itemcf_ref.py restates them on the host, bit for bit).
+//
+// Build (goctr_itemcf_build; engine stream, engine lock, the cache's image held):
+//   icf_compact_kernel    one wavefront per user: the considered entries, compacted in sequence order; cnt[]; the user's
+//                         position pairs ("slots": a < b, b - a <= window, whatever the items)
+//   per pass of users whose slots fit the budget
+//     icf_pairs_kernel    every slot's two directed keys (i << 32 | j); a slot with v_a == v_b writes a key behind every item
+//     radix_sort_keys     + icf_heads_kernel + exclusive_scan + icf_runs_kernel: the pass's distinct keys and their counts (a
+//                         run's length, from a bisection for its end)
+//     the pass's list is appended to the list so far, sorted by key with the counts as values, and reduced the same way: a key
+//     occurs at most twice there
+//   icf_weight_kernel     co, cnt -> w; the sort key (i << 24 | 2^24 - 1 - w) -- one stable sort leaves every item's pairs by w
+//                         descending and, among equal w, in the order they had: j ascending
+//   icf_starts_kernel, icf_emit_kernel   the first n_nbr pairs of every item with w > 0
+// Recall (icf_recall_kernel): one workgroup per request row, below.  Recommend: itemcf_recommend_run at the end of the file.
+#include <algorithm>
+#include <climits>
+#include <memory>
+
+#include "itemcf.h"
+#include "radix_sort.h"
+#include "scan.h"
+#include "ubcache.h"
+
+using namespace goctr;
+
+namespace {
+
+using u64 = unsigned long long;
+
+// ---------------------------------------------------------------------------------------------------------------- build
+// position pairs of a sequence of L considered entries: sum over a of min(W, L - 1 - a)
+__host__ __device__ inline u64 icf_slots(u64 L, u64 W) {
+  return L > W ? (L - W) * W + W * (W - 1) / 2 : L * (L - (L ? 1 : 0)) / 2;
+}
+// slots of the positions in front of a
+__device__ inline u64 icf_slot_base(u64 a, u64 L, u64 W) {
+  const u64 n_full = L > W ? L - W : 0;                  // positions with W partners
+  if (a <= n_full) return a * W;
+  const u64 m = a - n_full;                              // position n_full + t has L - 1 - n_full - t partners
+  return n_full * W + m * (L - 1 - n_full) - m * (m - 1) / 2;
+}
+
+__global__ __launch_bounds__(256) void icf_compact_kernel(const long long* __restrict__ off, const int32_t* __restrict__ items,
+                                                          long long n_users, long long n_items, long long max_len, int window,
+                                                          int32_t* __restrict__ v, unsigned int* __restrict__ vlen,
+                                                          u64* __restrict__ slots, unsigned int* __restrict__ cnt) {
+  const long long u = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (u >= n_users) return;                 // (whole wavefronts leave: the ballots below see full ones)
+  const int lane = threadIdx.x & 63;
+  const long long lo = off[u], len = off[u + 1] - lo;
+  const long long cap = max_len > 0 ? max_len : LLONG_MAX;
+  long long k = 0;
+  for (long long p0 = 0; p0 < len && k < cap; p0 += 64) {
+    const long long p = p0 + lane;
+    const int it = p < len ? items[lo + p] : -1;
+    const bool valid = it >= 0 && it < n_items;
+    const u64 b = __ballot(valid);
+    const long long r = k + __popcll(b & ((1ull << lane) - 1ull));
+    if (valid && r < cap) {
+      v[lo + r] = it;                       // (r <= p: inside the user's own segment)
+      atomicAdd(cnt + it, 1u);
+    }
+    k += __popcll(b);
+  }
+  if (lane == 0) {
+    const long long L = k < cap ? k : cap;
+    vlen[u] = (unsigned int)L;
+    slots[u] = icf_slots((u64)L, (u64)window);
+  }
+}
+
+// users u0 .. u0 + nu of one pass; pre[] = exclusive prefix of slots[]; keys [2 * (pre[u0 + nu] - pre[u0])]
+__global__ __launch_bounds__(256) void icf_pairs_kernel(const long long* __restrict__ off, const int32_t* __restrict__ v,
+                                                        const unsigned int* __restrict__ vlen, const u64* __restrict__ pre,
+                                                        long long u0, long long nu, int window, u64 sentinel,
+                                                        u64* __restrict__ keys, u64* __restrict__ n_pairs) {
+  const long long k = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (k >= nu) return;
+  const long long u = u0 + k;
+  const int lane = threadIdx.x & 63;
+  const long long lo = off[u];
+  const u64 L = vlen[u], W = (u64)window;
+  const u64 base = pre[u] - pre[u0];
+  unsigned int real = 0;
+  for (u64 a = lane; a + 1 < L; a += 64) {
+    const u64 nd = L - 1 - a < W ? L - 1 - a : W;
+    const u64 at = base + icf_slot_base(a, L, W);
+    const unsigned int va = (unsigned int)v[lo + a];
+    for (u64 d = 1; d <= nd; ++d) {
+      const unsigned int vb = (unsigned int)v[lo + a + d];
+      const bool pair = va != vb;
+      keys[2 * (at + d - 1)] = pair ? ((u64)va << 32) | vb : sentinel;
+      keys[2 * (at + d - 1) + 1] = pair ? ((u64)vb << 32) | va : sentinel;
+      real += pair ? 1u : 0u;
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) real += __shfl_down(real, o, 64);
+  if (lane == 0 && real) atomicAdd(n_pairs, (u64)real);
+}
+
+// head[i] = 1 where a run of equal keys below the sentinel starts (keys ascending)
+__global__ __launch_bounds__(256) void icf_heads_kernel(const u64* __restrict__ keys, long long n, u64 sentinel,
+                                                        unsigned int* __restrict__ head) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const u64 key = keys[i];
+  head[i] = key < sentinel && (i == 0 || keys[i - 1] != key) ? 1u : 0u;
+}
+
+// run r (the ex[i]-th head) -> okeys[r], ocnt[r].  vals == null: every key counts 1, the run's end comes from a bisection;
+// else a key occurs at most twice and its values are added
+__global__ __launch_bounds__(256) void icf_runs_kernel(const u64* __restrict__ keys, const u64* __restrict__ vals, long long n,
+                                                       const unsigned int* __restrict__ head, const u64* __restrict__ ex,
+                                                       u64* __restrict__ okeys, u64* __restrict__ ocnt) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n || !head[i]) return;
+  const u64 key = keys[i], r = ex[i];
+  okeys[r] = key;
+  if (vals) {
+    ocnt[r] = vals[i] + (i + 1 < n && keys[i + 1] == key ? vals[i + 1] : 0ull);
+  } else {
+    long long lo = i + 1, hi = n;                          // first index whose key is larger
+    while (lo < hi) {
+      const long long mid = (lo + hi) >> 1;
+      if (keys[mid] > key) hi = mid; else lo = mid + 1;
+    }
+    ocnt[r] = (u64)(lo - i);
+  }
+}
+
+__global__ __launch_bounds__(256) void icf_weight_kernel(const u64* __restrict__ keys, const u64* __restrict__ co, long long n,
+                                                         const unsigned int* __restrict__ cnt, unsigned long long min_co,
+                                                         u64* __restrict__ skey, u64* __restrict__ sval) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n) return;
+  const u64 key = keys[e], c = co[e];
+  const unsigned int i = (unsigned int)(key >> 32), j = (unsigned int)key;
+  const u64 prod = (u64)cnt[i] * (u64)cnt[j];              // (both > 0: the pair was counted)
+  const double q = __ddiv_rn((double)c, __dsqrt_rn((double)prod));
+  unsigned int w = (unsigned int)floor(q * 65536.0);       // (a power of two: the product is exact; w <= 2^23)
+  if (c < min_co) w = 0u;
+  skey[e] = ((u64)i << 24) | (u64)(0xffffffu - w);
+  sval[e] = ((u64)j << 32) | (c > 0xffffffffull ? 0xffffffffull : c);
+}
+
+__global__ __launch_bounds__(256) void icf_starts_kernel(const u64* __restrict__ skey, long long n, u64* __restrict__ start) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n) return;
+  const u64 i = skey[e] >> 24;
+  if (e == 0 || (skey[e - 1] >> 24) != i) start[i] = (u64)e;
+}
+
+__global__ __launch_bounds__(256) void icf_emit_kernel(const u64* __restrict__ skey, const u64* __restrict__ sval, long long n,
+                                                       const u64* __restrict__ start, int M, int32_t* __restrict__ nbr_items,
+                                                       unsigned int* __restrict__ nbr_w, unsigned int* __restrict__ nbr_co) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n) return;
+  const u64 key = skey[e], i = key >> 24, r = (u64)e - start[i];
+  const unsigned int w = 0xffffffu - (unsigned int)(key & 0xffffffu);
+  if (r >= (u64)M || w == 0u) return;
+  const u64 val = sval[e];
+  nbr_items[i * M + r] = (int32_t)(val >> 32);
+  nbr_w[i * M + r] = w;
+  nbr_co[i * M + r] = (unsigned int)val;
+}
+
+int bits_for(long long n) {     // bits that hold 0 .. n - 1
+  int b = 0;
+  while (b < 63 && (1LL << b) < n) ++b;
+  return b;
+}
+
+template <class T>
+void swap_bufs(DevBuf<T>& a, DevBuf<T>& b) { std::swap(a.p, b.p); std::swap(a.n, b.n); std::swap(a.owner, b.owner); }
+
+// scratch of one build (declared in front of the cache hold, so that an error return drains the stream before it is freed)
+struct IcfScratch {
+  DevBuf<int32_t> v;
+  DevBuf<unsigned int> vlen, head;
+  DevBuf<u64> slots, pre, keys, keys_sorted, ex, tiles, total, n_pairs;
+  DevBuf<u64> a_keys, a_cnt, p_keys, p_cnt, m_keys, m_cnt, m_keys_sorted, m_cnt_sorted, start;
+  DevBuf<char> temp;
+};
+
+// keys [n] ascending (+ vals) -> the distinct keys below the sentinel and their counts in okeys / ocnt; *n_out = how many
+int icf_reduce(IcfScratch& ws, const u64* keys, const u64* vals, long long n, u64 sentinel, DevBuf<u64>& okeys, DevBuf<u64>& ocnt,
+               u64* n_out, hipStream_t s) {
+  if (ws.head.ensure((size_t)n, false) || ws.ex.ensure((size_t)n, false)) return -1;
+  hipLaunchKernelGGL(icf_heads_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, keys, n, sentinel, ws.head.p);
+  GOCTR_HIP(hipGetLastError());
+  if (exclusive_scan<u64>(ws.head.p, n, ws.ex.p, ws.tiles, ws.total.p)) return -1;
+  if (ws.total.download(n_out, 1)) return -1;
+  if (okeys.ensure((size_t)*n_out, false) || ocnt.ensure((size_t)*n_out, false)) return -1;
+  hipLaunchKernelGGL(icf_runs_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, keys, vals, n, ws.head.p, ws.ex.p, okeys.p, ocnt.p);
+  GOCTR_HIP(hipGetLastError());
+  return 0;
+}
+
+// --------------------------------------------------------------------------------------------------------------- recall
+// One workgroup per request row.
+//   1. the history: the first H valid entries the timestamp filter keeps, in sequence order (ballots + a scan of the wave counts)
+//   2. the row's n_h * M list entries are summed per candidate in an LDS hash table (RC_TABLE slots, linear probing, the item
+//      claimed by a compare-and-swap, the weight added by an atomic: an integer sum, so the arrival order cannot show).  The
+//      table holds at most RC_LIMIT candidates, so the candidates are taken in TILES, ranges [lo, hi) of item ids: a range is
+//      accumulated whole -- every entry of the row's lists whose item falls in it -- and a range that overflows is dropped and
+//      split in two.  A candidate's sum is complete whatever range it came in, so no output depends on the tiling.
+//   3. the sequence entries the exclusion mode looks at mark their table slot (bit 31 of the slot's item)
+//   4. the table's candidates join the row's running list by the key (S << 32) | ~item (topn.h: sel_append / sel_sort_trim)
+constexpr int RC_TABLE = 8192, RC_TABLE_BITS = 13, RC_LIMIT = 6144, RC_STACK = 48;
+constexpr unsigned int RC_EMPTY = 0xffffffffu;
+constexpr int RC_MAX_H = 256, RC_MAX_CAND = 1024;
+static_assert(SEL_CAP >= RC_MAX_CAND + SEL_THREADS, "a trimmed list and one tile of the table must fit");
+static_assert(RC_LIMIT + SEL_THREADS < RC_TABLE, "threads that pass the limit together must still find free slots");
+static_assert(RC_TABLE % SEL_THREADS == 0, "the table is read in whole tiles");
+
+struct RecallArgs {
+  const long long* off; const int32_t* seq_items; const long long* seq_ts;   // the cache's image (null: no cache)
+  long long n_items; int M;
+  const int32_t* nbr_items; const unsigned int* nbr_w;
+  const int32_t* users; const long long* ts; const int32_t* targets;          // device; targets may be null
+  int H, n_cand, exclude;
+  int32_t* out_items; unsigned int* out_w; int32_t* out_count; int32_t* out_tpos;   // device; out_tpos may be null
+};
+
+__device__ inline unsigned int rc_hash(unsigned int j) { return (j * 2654435761u) >> (32 - RC_TABLE_BITS); }
+
+__global__ __launch_bounds__(SEL_THREADS) void icf_recall_kernel(RecallArgs a) {
+  __shared__ unsigned int tkey[RC_TABLE], tsum[RC_TABLE];
+  __shared__ unsigned long long skey[SEL_CAP];
+  __shared__ unsigned sraw[SEL_CAP];
+  __shared__ int hist[RC_MAX_H];
+  __shared__ int wcnt[SEL_THREADS / 64];
+  __shared__ int st_lo[RC_STACK], st_hi[RC_STACK];
+  __shared__ int s_sp, s_fill, s_distinct, s_over, s_tpos;
+  __shared__ unsigned long long s_thr;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long q = blockIdx.x;
+  const bool has_t = a.targets != nullptr;
+  const int tgt = has_t ? a.targets[q] : -1;
+  long long lo_e = 0, len = 0;
+  if (a.off) { const int u = a.users[q]; lo_e = a.off[u]; len = a.off[u + 1] - lo_e; }
+  const long long mts = a.ts[q];
+
+  // 1. history
+  int nh = 0;
+  for (long long p0 = 0; p0 < len && nh < a.H; p0 += SEL_THREADS) {
+    const long long p = p0 + tid;
+    int it = -1;
+    if (p < len && (mts == 0 || a.seq_ts[lo_e + p] <= mts)) it = a.seq_items[lo_e + p];
+    const bool valid = it >= 0 && it < a.n_items;
+    const unsigned long long b = __ballot(valid);
+    if (lane == 0) wcnt[wave] = __popcll(b);
+    __syncthreads();
+    int base = nh, tot = 0;
+    for (int w = 0; w < SEL_THREADS / 64; ++w) { if (w < wave) base += wcnt[w]; tot += wcnt[w]; }
+    const int r = base + __popcll(b & ((1ull << lane) - 1ull));
+    if (valid && r < a.H) hist[r] = it;
+    nh += tot;
+    __syncthreads();
+  }
+  if (nh > a.H) nh = a.H;
+  const int n_entries = nh * a.M;
+  const int step_t = SEL_THREADS / a.M, step_c = SEL_THREADS - step_t * a.M;
+  if (tid == 0) {
+    s_fill = 0; s_thr = 0ull; s_sp = 0; s_tpos = -1;
+    if (n_entries > 0) {                       // the first tiles: equal ranges, few enough entries each on average
+      const int parts = (n_entries + RC_LIMIT - 1) / RC_LIMIT;
+      const long long width = (a.n_items + parts - 1) / parts;
+      for (int p = parts - 1; p >= 0; --p) {
+        const long long lo = p * width, hi = lo + width < a.n_items ? lo + width : a.n_items;
+        if (lo < hi) { st_lo[s_sp] = (int)lo; st_hi[s_sp] = (int)hi; ++s_sp; }
+      }
+    }
+  }
+  __syncthreads();
+
+  while (s_sp > 0) {                           // (uniform: read behind a barrier)
+    const int lo = st_lo[s_sp - 1], hi = st_hi[s_sp - 1];
+    __syncthreads();                           // everyone has read the top
+    if (tid == 0) { --s_sp; s_distinct = 0; s_over = 0; }
+    for (int i = tid; i < RC_TABLE; i += SEL_THREADS) { tkey[i] = RC_EMPTY; tsum[i] = 0u; }
+    __syncthreads();
+    // 2. accumulate the range
+    // entry e = list position c of history entry t; (t, c) advance by the stride's quotient and remainder: no division per entry
+    int t = tid / a.M, c = tid - t * a.M;
+    for (int e = tid; e < n_entries; e += SEL_THREADS, t += step_t, c += step_c) {
+      if (c >= a.M) { c -= a.M; ++t; }
+      if (*(volatile int*)&s_over) break;
+      const long long at = (long long)hist[t] * a.M + c;
+      const int j = a.nbr_items[at];
+      if (j < lo || j >= hi) continue;         // (padding is -1 < lo)
+      const unsigned int w = a.nbr_w[at];
+      unsigned int slot = rc_hash((unsigned int)j);
+      for (;;) {
+        const unsigned int prev = atomicCAS(&tkey[slot], RC_EMPTY, (unsigned int)j);
+        if (prev == RC_EMPTY) {
+          if (atomicAdd(&s_distinct, 1) >= RC_LIMIT) s_over = 1;
+          atomicAdd(&tsum[slot], w);
+          break;
+        }
+        if (prev == (unsigned int)j) { atomicAdd(&tsum[slot], w); break; }
+        slot = (slot + 1) & (RC_TABLE - 1);
+      }
+    }
+    __syncthreads();
+    if (s_over) {                              // (uniform) too many candidates for one tile: halve the range
+      if (tid == 0) {                          // (hi - lo >= 2: one item is one candidate; depth <= 31 + the first tiles)
+        const int mid = lo + (hi - lo) / 2;
+        st_lo[s_sp] = mid; st_hi[s_sp] = hi; ++s_sp;
+        st_lo[s_sp] = lo; st_hi[s_sp] = mid; ++s_sp;
+      }
+      __syncthreads();
+      continue;
+    }
+    // 3. seen
+    if (a.exclude != GOCTR_TOPN_KEEP_SEEN) {
+      const bool before = a.exclude == GOCTR_TOPN_DROP_SEEN_BEFORE;
+      for (long long p = tid; p < len; p += SEL_THREADS) {
+        const int it = a.seq_items[lo_e + p];
+        if (it < lo || it >= hi || it >= a.n_items) continue;
+        if (before && mts != 0 && a.seq_ts[lo_e + p] > mts) continue;
+        unsigned int slot = rc_hash((unsigned int)it);
+        for (;;) {
+          const unsigned int k = tkey[slot];
+          if (k == RC_EMPTY) break;
+          if ((k & 0x7fffffffu) == (unsigned int)it) { atomicOr(&tkey[slot], 0x80000000u); break; }
+          slot = (slot + 1) & (RC_TABLE - 1);
+        }
+      }
+      __syncthreads();
+    }
+    // 4. the tile's candidates join the running list
+    for (int s0 = 0; s0 < RC_TABLE; s0 += SEL_THREADS) {
+      const unsigned long long thr = s_thr;
+      const unsigned int k = tkey[s0 + tid];
+      unsigned long long key = 0ull;
+      if (k != RC_EMPTY) {
+        const unsigned int j = k & 0x7fffffffu;
+        if (!(k >> 31) || (has_t && (int)j == tgt)) {
+          key = ((unsigned long long)tsum[s0 + tid] << 32) | (unsigned long long)(~j);
+          if (key <= thr) key = 0ull;
+        }
+      }
+      sel_append(skey, sraw, &s_fill, &s_thr, a.n_cand, key, 0u);
+    }
+    __syncthreads();
+  }
+
+  sel_sort_trim(skey, sraw, &s_fill, &s_thr, a.n_cand);
+  const int fill = s_fill;
+  for (int i = tid; i < a.n_cand; i += SEL_THREADS) {
+    const long long o = q * a.n_cand + i;
+    if (i < fill) {
+      const int item = (int)~(unsigned int)skey[i];
+      a.out_items[o] = item;
+      a.out_w[o] = (unsigned int)(skey[i] >> 32);
+      if (has_t && item == tgt) s_tpos = i;                          // (items are distinct: one writer at most)
+    } else {
+      a.out_items[o] = -1;
+      a.out_w[o] = 0u;
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    a.out_count[q] = fill;
+    if (a.out_tpos) a.out_tpos[q] = s_tpos;
+  }
+}
+
+int recall_check_cfg(const goctr_recall_cfg* cfg, const char* who) {
+  GOCTR_CHECK(cfg->history >= 1 && cfg->history <= RC_MAX_H, "%s: history = %d is outside 1 .. %d", who, cfg->history, RC_MAX_H);
+  GOCTR_CHECK(cfg->n_cand >= 1 && cfg->n_cand <= RC_MAX_CAND, "%s: n_cand = %d is outside 1 .. %d", who, cfg->n_cand, RC_MAX_CAND);
+  GOCTR_CHECK(cfg->exclude >= GOCTR_TOPN_KEEP_SEEN && cfg->exclude <= GOCTR_TOPN_DROP_SEEN_BEFORE,
+              "%s: exclude = %d is no GOCTR_TOPN_* mode", who, cfg->exclude);
+  return 0;
+}
+
+int recall_check_users(const int32_t* users, int64_t n_req, int64_t n_users, const char* who) {
+  GOCTR_CHECK(n_req > 0 && n_req <= ((int64_t)1 << 24), "%s: n_req = %lld is outside 1 .. 2^24", who, (long long)n_req);
+  for (int64_t q = 0; q < n_req; ++q)
+    GOCTR_CHECK(users[q] >= 0 && users[q] < n_users, "%s: request row %lld: user %d is outside [0, %lld)", who, (long long)q,
+                users[q], (long long)n_users);
+  return 0;
+}
+
+// the device-side inputs of a call: users, ts (zeros when the caller gave none), targets
+struct RecallInputs {
+  DevBuf<int32_t> users, targets;
+  DevBuf<long long> ts;
+  int stage(const int32_t* h_users, const int64_t* h_ts, const int32_t* h_targets, int64_t nq, hipStream_t st) {
+    if (users.alloc((size_t)nq, false) || ts.alloc((size_t)nq, false) || (h_targets && targets.alloc((size_t)nq, false))) return -1;
+    GOCTR_HIP(hipMemcpyAsync(users.p, h_users, sizeof(int32_t) * (size_t)nq, hipMemcpyHostToDevice, st));
+    if (h_ts) GOCTR_HIP(hipMemcpyAsync(ts.p, h_ts, sizeof(int64_t) * (size_t)nq, hipMemcpyHostToDevice, st));
+    else GOCTR_HIP(hipMemsetAsync(ts.p, 0, sizeof(int64_t) * (size_t)nq, st));
+    if (h_targets) GOCTR_HIP(hipMemcpyAsync(targets.p, h_targets, sizeof(int32_t) * (size_t)nq, hipMemcpyHostToDevice, st));
+    return 0;
+  }
+};
+
+int recall_launch(const goctr_itemcf* h, const long long* off, const int32_t* seq_items, const long long* seq_ts,
+                  const RecallInputs& in, bool has_targets, int64_t nq, const goctr_recall_cfg& cfg, int32_t* o_items,
+                  unsigned int* o_w, int32_t* o_count, int32_t* o_tpos, hipStream_t st) {
+  RecallArgs a{};
+  a.off = off; a.seq_items = seq_items; a.seq_ts = seq_ts;
+  a.n_items = h->n_items; a.M = h->M; a.nbr_items = h->nbr_items.p; a.nbr_w = h->nbr_w.p;
+  a.users = in.users.p; a.ts = in.ts.p; a.targets = has_targets ? in.targets.p : nullptr;
+  a.H = cfg.history; a.n_cand = cfg.n_cand; a.exclude = cfg.exclude;
+  a.out_items = o_items; a.out_w = o_w; a.out_count = o_count; a.out_tpos = o_tpos;
+  hipLaunchKernelGGL(icf_recall_kernel, dim3((unsigned)nq), dim3(SEL_THREADS), 0, st, a);
+  GOCTR_HIP(hipGetLastError());
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------ recommend
+// flat row r of the call = candidate c of request row q, r = pre[q] + c (pre = exclusive prefix of the recall's counts)
+__global__ __launch_bounds__(256) void icf_keys_kernel(const long long* __restrict__ pre, long long nq, const int32_t* __restrict__ cand,
+                                                       int n_cand, const int32_t* __restrict__ users, const long long* __restrict__ ts,
+                                                       long long r0, long long N, long long* __restrict__ k_ts,
+                                                       int32_t* __restrict__ k_users, int32_t* __restrict__ k_items) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= N) return;
+  const long long r = r0 + i;
+  long long lo = 0, hi = nq;                               // the q with pre[q] <= r < pre[q + 1]
+  while (hi - lo > 1) {
+    const long long mid = (lo + hi) >> 1;
+    if (pre[mid] <= r) lo = mid; else hi = mid;
+  }
+  k_ts[i] = ts[lo]; k_users[i] = users[lo]; k_items[i] = cand[lo * n_cand + (r - pre[lo])];
+}
+
+struct IcfSelArgs {
+  const long long* pre; const int32_t* cand; const int32_t* count; const int32_t* tpos;   // tpos may be null
+  const float* scores; const unsigned char* failed;                                       // flat [total]
+  int n_cand, k;
+  int32_t* out_items; unsigned* out_scores; int32_t* out_count; long long* out_rank;
+  float* cand_scores;                                                                     // [nq, n_cand] or null
+  unsigned long long* n_failed;
+};
+
+// one workgroup per request row, one thread per recalled candidate: topn's order rule over at most 1024 keys
+__global__ __launch_bounds__(SEL_THREADS) void icf_select_kernel(IcfSelArgs a) {
+  __shared__ unsigned long long skey[SEL_CAP];
+  __shared__ unsigned sraw[SEL_CAP];
+  __shared__ int s_fill;
+  __shared__ unsigned long long s_thr;
+  const int tid = threadIdx.x;
+  const long long q = blockIdx.x;
+  const int cnt = a.count[q];
+  const long long base = a.pre[q];
+  if (tid == 0) { s_fill = 0; s_thr = 0ull; }
+  __syncthreads();
+  unsigned long long key = 0ull;
+  unsigned raw = 0u;
+  bool fail = false;
+  if (tid < cnt) {
+    const float s = a.scores[base + tid];
+    fail = a.failed[base + tid] != 0;
+    raw = __float_as_uint(s);
+    if (!fail) key = order_key(s, (unsigned)tid);
+  }
+  if (a.cand_scores && tid < a.n_cand) a.cand_scores[q * a.n_cand + tid] = tid < cnt ? __uint_as_float(raw) : 0.f;
+  const int tp = a.tpos ? a.tpos[q] : -1;
+  const bool ranked = tp >= 0 && !a.failed[base + tp];
+  const unsigned long long tkey = ranked ? order_key(a.scores[base + tp], (unsigned)tp) : ~0ull;
+  const int before = __syncthreads_count(key > tkey);
+  const int n_fail = __syncthreads_count(fail);
+  sel_append(skey, sraw, &s_fill, &s_thr, a.k, key, raw);
+  sel_sort_trim(skey, sraw, &s_fill, &s_thr, a.k);
+  const int fill = s_fill;
+  for (int i = tid; i < a.k; i += SEL_THREADS) {
+    const long long o = q * a.k + i;
+    if (i < fill) {
+      a.out_items[o] = a.cand[q * a.n_cand + (int)~(unsigned)skey[i]];
+      a.out_scores[o] = sraw[i];
+    } else {
+      a.out_items[o] = -1;
+      a.out_scores[o] = 0u;
+    }
+  }
+  if (tid == 0) {
+    a.out_count[q] = fill;
+    a.out_rank[q] = ranked ? (long long)before : -1;
+    if (n_fail) atomicAdd(a.n_failed, (unsigned long long)n_fail);
+  }
+}
+
+// drains the stream before the call's device buffers go back to the arena, on every path out of the call
+struct Drain {
+  hipStream_t s;
+  ~Drain() { (void)hipStreamSynchronize(s); }
+};
+
+}  // namespace
+
+namespace goctr {
+
+int itemcf_check_recommend(const goctr_itemcf* h, const ItemcfRecArgs& a, int64_t n_users, int64_t n_items) {
+  const char* who = "goctr_recommend_itemcf";
+  GOCTR_CHECK(h && a.users && a.out_items && a.out_scores && a.out_count, "%s: bad arguments", who);
+  GOCTR_CHECK(h->n_items == n_items, "%s: the neighbour lists cover %lld items, the recsys %lld", who, (long long)h->n_items,
+              (long long)n_items);
+  if (recall_check_cfg(&a.rcfg, who)) return -1;
+  GOCTR_CHECK(a.k >= 1 && a.k <= 256, "%s: k = %d is outside 1 .. 256", who, a.k);
+  GOCTR_CHECK(a.pass_rows == 0 || (a.pass_rows >= 16 && a.pass_rows <= TOPN_DEFAULT_PASS_ROWS),
+              "%s: pass_rows = %lld is neither 0 nor in 16 .. 65536", who, (long long)a.pass_rows);
+  return recall_check_users(a.users, a.n_req, n_users, who);
+}
+
+int itemcf_recommend_run(const TopnScorer& sc, const goctr_itemcf* h, const ItemcfRecArgs& a) {
+  const char* who = "goctr_recommend_itemcf";
+  const int64_t nq = a.n_req;
+  const int nc = a.rcfg.n_cand, k = a.k;
+  const int64_t P = a.pass_rows ? a.pass_rows : TOPN_DEFAULT_PASS_ROWS;
+  GOCTR_CHECK(P <= sc.max_rows, "%s: the serving slot holds %lld rows, the pass needs %lld", who, (long long)sc.max_rows, (long long)P);
+  hipStream_t st = sc.stream;
+  RecallInputs in;
+  DevBuf<int32_t> c_items, c_count, c_tpos, o_items, o_count;
+  DevBuf<unsigned int> c_w, o_scores;
+  DevBuf<long long> d_pre, o_rank;
+  DevBuf<float> f_scores, c_scores;
+  DevBuf<unsigned char> f_failed;
+  DevBuf<unsigned long long> d_nfailed;
+  std::vector<int32_t> h_count((size_t)nq), h_tpos((size_t)nq), h_items((size_t)nq * k), h_ocount((size_t)nq), h_citems;
+  std::vector<unsigned> h_scores((size_t)nq * k), h_cw;
+  std::vector<float> h_cscores;
+  std::vector<long long> h_pre((size_t)nq + 1), h_rank((size_t)nq);
+  unsigned long long h_nfailed = 0;
+  Drain drain{st};                                        // (declared behind the buffers: runs before they are released)
+  if (in.stage(a.users, a.ts, a.targets, nq, st)) return -1;
+  if (c_items.alloc((size_t)nq * nc, false) || c_w.alloc((size_t)nq * nc, false) || c_count.alloc((size_t)nq, false) ||
+      c_tpos.alloc((size_t)nq, false) || d_pre.alloc((size_t)nq + 1, false) || o_items.alloc((size_t)nq * k, false) ||
+      o_scores.alloc((size_t)nq * k, false) || o_count.alloc((size_t)nq, false) || o_rank.alloc((size_t)nq, false) ||
+      d_nfailed.alloc(1, false)) return -1;
+  if (a.cand_scores && c_scores.alloc((size_t)nq * nc, false)) return -1;
+  GOCTR_HIP(hipMemsetAsync(d_nfailed.p, 0, sizeof(unsigned long long), st));
+  // 1. recall on the slot's stream; its counts decide the key space, so they come back before the passes are cut
+  if (recall_launch(h, sc.ub_off, sc.ub_items, sc.ub_ts, in, a.targets != nullptr, nq, a.rcfg, c_items.p, c_w.p, c_count.p, c_tpos.p, st))
+    return -1;
+  GOCTR_HIP(hipMemcpyAsync(h_count.data(), c_count.p, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, st));
+  GOCTR_HIP(hipStreamSynchronize(st));
+  h_pre[0] = 0;
+  for (int64_t q = 0; q < nq; ++q) h_pre[q + 1] = h_pre[q] + h_count[q];
+  const int64_t total = h_pre[nq];
+  GOCTR_HIP(hipMemcpyAsync(d_pre.p, h_pre.data(), sizeof(long long) * ((size_t)nq + 1), hipMemcpyHostToDevice, st));
+  if (f_scores.alloc((size_t)total, false) || f_failed.alloc((size_t)total, false)) return -1;
+  // 2. + 3. the kept candidates' keys, scored P rows at a time
+  for (int64_t r = 0; r < total;) {
+    const int64_t N = std::min(P, total - r);
+    long long* k_ts = reinterpret_cast<long long*>(sc.keys);
+    int32_t* k_users = reinterpret_cast<int32_t*>(sc.keys + 8 * N);
+    int32_t* k_items = reinterpret_cast<int32_t*>(sc.keys + 12 * N);
+    hipLaunchKernelGGL(icf_keys_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, st, d_pre.p, (long long)nq, c_items.p, nc,
+                       in.users.p, in.ts.p, (long long)r, (long long)N, k_ts, k_users, k_items);
+    GOCTR_HIP(hipGetLastError());
+    if (sc.score(N)) return -1;
+    const size_t Br = (size_t)round_up((int)N, 32);
+    GOCTR_HIP(hipMemcpyAsync(f_scores.p + r, sc.out, sizeof(float) * (size_t)N, hipMemcpyDeviceToDevice, st));
+    GOCTR_HIP(hipMemcpyAsync(f_failed.p + r, sc.out + 4 * Br, (size_t)N, hipMemcpyDeviceToDevice, st));
+    r += N;
+  }
+  // 4. the best k of every row
+  IcfSelArgs s{};
+  s.pre = d_pre.p; s.cand = c_items.p; s.count = c_count.p; s.tpos = a.targets ? c_tpos.p : nullptr;
+  s.scores = f_scores.p; s.failed = f_failed.p; s.n_cand = nc; s.k = k;
+  s.out_items = o_items.p; s.out_scores = o_scores.p; s.out_count = o_count.p; s.out_rank = o_rank.p;
+  s.cand_scores = a.cand_scores ? c_scores.p : nullptr; s.n_failed = d_nfailed.p;
+  hipLaunchKernelGGL(icf_select_kernel, dim3((unsigned)nq), dim3(SEL_THREADS), 0, st, s);
+  GOCTR_HIP(hipGetLastError());
+  // the results are staged on the host so that a failing copy leaves the caller's arrays as they were
+  GOCTR_HIP(hipMemcpyAsync(h_items.data(), o_items.p, sizeof(int32_t) * h_items.size(), hipMemcpyDeviceToHost, st));
+  GOCTR_HIP(hipMemcpyAsync(h_scores.data(), o_scores.p, sizeof(unsigned) * h_scores.size(), hipMemcpyDeviceToHost, st));
+  GOCTR_HIP(hipMemcpyAsync(h_ocount.data(), o_count.p, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, st));
+  GOCTR_HIP(hipMemcpyAsync(h_rank.data(), o_rank.p, sizeof(long long) * (size_t)nq, hipMemcpyDeviceToHost, st));
+  GOCTR_HIP(hipMemcpyAsync(h_tpos.data(), c_tpos.p, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, st));
+  GOCTR_HIP(hipMemcpyAsync(&h_nfailed, d_nfailed.p, sizeof h_nfailed, hipMemcpyDeviceToHost, st));
+  if (a.cand_items) { h_citems.resize((size_t)nq * nc); GOCTR_HIP(hipMemcpyAsync(h_citems.data(), c_items.p, sizeof(int32_t) * h_citems.size(), hipMemcpyDeviceToHost, st)); }
+  if (a.cand_w) { h_cw.resize((size_t)nq * nc); GOCTR_HIP(hipMemcpyAsync(h_cw.data(), c_w.p, sizeof(unsigned) * h_cw.size(), hipMemcpyDeviceToHost, st)); }
+  if (a.cand_scores) { h_cscores.resize((size_t)nq * nc); GOCTR_HIP(hipMemcpyAsync(h_cscores.data(), c_scores.p, sizeof(float) * h_cscores.size(), hipMemcpyDeviceToHost, st)); }
+  GOCTR_HIP(hipStreamSynchronize(st));
+  memcpy(a.out_items, h_items.data(), sizeof(int32_t) * h_items.size());
+  memcpy(a.out_scores, h_scores.data(), sizeof(unsigned) * h_scores.size());
+  memcpy(a.out_count, h_ocount.data(), sizeof(int32_t) * (size_t)nq);
+  if (a.out_cand_count) memcpy(a.out_cand_count, h_count.data(), sizeof(int32_t) * (size_t)nq);
+  if (a.out_target_pos) for (int64_t q = 0; q < nq; ++q) a.out_target_pos[q] = a.targets ? h_tpos[q] : -1;
+  if (a.out_target_rank) memcpy(a.out_target_rank, h_rank.data(), sizeof(long long) * (size_t)nq);
+  if (a.cand_items) memcpy(a.cand_items, h_citems.data(), sizeof(int32_t) * h_citems.size());
+  if (a.cand_w) memcpy(a.cand_w, h_cw.data(), sizeof(unsigned) * h_cw.size());
+  if (a.cand_scores) memcpy(a.cand_scores, h_cscores.data(), sizeof(float) * h_cscores.size());
+  if (a.n_failed) *a.n_failed = (int64_t)h_nfailed;
+  return 0;
+}
+
+}  // namespace goctr
+
+extern "C" {
+
+void goctr_itemcf_cfg_default(goctr_itemcf_cfg* c) {
+  if (!c) return;
+  c->window = 5; c->max_len = 0; c->n_nbr = 64; c->min_co = 1; c->pair_budget = 0;
+}
+
+void goctr_recall_cfg_default(goctr_recall_cfg* c) {
+  if (!c) return;
+  c->history = 50; c->n_cand = 256; c->exclude = GOCTR_TOPN_DROP_ALL_SEEN;
+}
+
+int goctr_itemcf_build(goctr_ubcache* c, int64_t n_items, const goctr_itemcf_cfg* cfg, goctr_itemcf** out) {
+  GOCTR_ENTER_H(c);
+  GOCTR_CHECK(c && cfg && out, "goctr_itemcf_build: null argument");
+  GOCTR_CHECK(n_items > 0 && n_items <= INT32_MAX, "goctr_itemcf_build: n_items = %lld (1 .. 2^31 - 1)", (long long)n_items);
+  GOCTR_CHECK(cfg->window >= 1 && cfg->window <= 64, "goctr_itemcf_build: window = %d (1 .. 64)", cfg->window);
+  GOCTR_CHECK(cfg->max_len >= 0, "goctr_itemcf_build: max_len = %d (>= 0)", cfg->max_len);
+  GOCTR_CHECK(cfg->n_nbr >= 1 && cfg->n_nbr <= 256, "goctr_itemcf_build: n_nbr = %d (1 .. 256)", cfg->n_nbr);
+  GOCTR_CHECK(cfg->min_co >= 1, "goctr_itemcf_build: min_co = %d (>= 1)", cfg->min_co);
+  GOCTR_CHECK(cfg->pair_budget == 0 || (cfg->pair_budget >= ((int64_t)1 << 10) && cfg->pair_budget <= ((int64_t)1 << 30)),
+              "goctr_itemcf_build: pair_budget = %lld (0, or 2^10 .. 2^30)", (long long)cfg->pair_budget);
+  hipStream_t s = engine().stream;
+  std::unique_ptr<goctr_itemcf> r(new goctr_itemcf);
+  IcfScratch ws;
+  UbRead image(c, s);                         // one image of the cache for the whole build
+  const long long nu = c->n_users, nnz = c->nnz;
+  const int M = cfg->n_nbr, W = cfg->window;
+  const u64 budget = cfg->pair_budget ? (u64)cfg->pair_budget : (u64)1 << 26;
+  const u64 sentinel = (u64)n_items << 32;    // behind every pair of valid items
+  r->n_items = n_items; r->M = M; r->cache_version = c->version;
+  if (r->cnt.alloc((size_t)n_items) || r->nbr_items.alloc((size_t)n_items * M, false) || r->nbr_w.alloc((size_t)n_items * M) ||
+      r->nbr_co.alloc((size_t)n_items * M)) return -1;
+  GOCTR_HIP(hipMemsetAsync(r->nbr_items.p, 0xff, sizeof(int32_t) * (size_t)n_items * M, s));
+  if (ws.v.alloc((size_t)nnz, false) || ws.vlen.alloc((size_t)nu, false) || ws.slots.alloc((size_t)nu, false) ||
+      ws.pre.alloc((size_t)nu + 1, false) || ws.total.alloc(1, false) || ws.n_pairs.alloc(1)) return -1;
+  if (nu > 0)
+    hipLaunchKernelGGL(icf_compact_kernel, dim3((unsigned)cdiv(nu, 4)), dim3(256), 0, s, c->off.p, c->items.p, nu, (long long)n_items,
+                     (long long)cfg->max_len, W, ws.v.p, ws.vlen.p, ws.slots.p, r->cnt.p);
+  GOCTR_HIP(hipGetLastError());
+  std::vector<u64> pre((size_t)nu + 1);
+  if (ws.slots.download(pre.data() + 1, (size_t)nu)) return -1;
+  pre[0] = 0;
+  for (long long u = 0; u < nu; ++u) pre[u + 1] += pre[u];
+  if (ws.pre.upload(pre.data(), (size_t)nu + 1)) return -1;
+  const unsigned int key_bits = 32u + (unsigned int)bits_for(n_items + 1);
+  u64 n_acc = 0;                              // distinct directed pairs so far: ws.a_keys / ws.a_cnt [n_acc], keys ascending
+  for (long long u0 = 0; u0 < nu;) {
+    long long u1 = u0 + 1;                    // a pass holds at least one user
+    while (u1 < nu && pre[u1 + 1] - pre[u0] <= budget) ++u1;
+    const u64 n_slots = pre[u1] - pre[u0];
+    if (n_slots) {
+      GOCTR_CHECK(n_slots < ((u64)1 << 36), "goctr_itemcf_build: the pass from user %lld has %llu position pairs (limit 2^36)", u0, n_slots);
+      const long long nk = (long long)(2 * n_slots);
+      if (ws.keys.ensure((size_t)nk, false) || ws.keys_sorted.ensure((size_t)nk, false)) return -1;
+      hipLaunchKernelGGL(icf_pairs_kernel, dim3((unsigned)cdiv(u1 - u0, 4)), dim3(256), 0, s, c->off.p, ws.v.p, ws.vlen.p, ws.pre.p,
+                         u0, u1 - u0, W, sentinel, ws.keys.p, ws.n_pairs.p);
+      GOCTR_HIP(hipGetLastError());
+      if (radix_sort_keys(ws.temp, ws.keys.p, ws.keys_sorted.p, (size_t)nk, key_bits, s)) return -1;
+      u64 n_p = 0;
+      if (icf_reduce(ws, ws.keys_sorted.p, nullptr, nk, sentinel, ws.p_keys, ws.p_cnt, &n_p, s)) return -1;
+      if (n_acc == 0) {
+        swap_bufs(ws.a_keys, ws.p_keys); swap_bufs(ws.a_cnt, ws.p_cnt);
+        n_acc = n_p;
+      } else if (n_p) {
+        const size_t n_m = (size_t)(n_acc + n_p);
+        if (ws.m_keys.ensure(n_m, false) || ws.m_cnt.ensure(n_m, false) || ws.m_keys_sorted.ensure(n_m, false) ||
+            ws.m_cnt_sorted.ensure(n_m, false)) return -1;
+        GOCTR_HIP(hipMemcpyAsync(ws.m_keys.p, ws.a_keys.p, 8 * (size_t)n_acc, hipMemcpyDeviceToDevice, s));
+        GOCTR_HIP(hipMemcpyAsync(ws.m_keys.p + n_acc, ws.p_keys.p, 8 * (size_t)n_p, hipMemcpyDeviceToDevice, s));
+        GOCTR_HIP(hipMemcpyAsync(ws.m_cnt.p, ws.a_cnt.p, 8 * (size_t)n_acc, hipMemcpyDeviceToDevice, s));
+        GOCTR_HIP(hipMemcpyAsync(ws.m_cnt.p + n_acc, ws.p_cnt.p, 8 * (size_t)n_p, hipMemcpyDeviceToDevice, s));
+        if (radix_sort_pairs(ws.temp, ws.m_keys.p, ws.m_keys_sorted.p, ws.m_cnt.p, ws.m_cnt_sorted.p, n_m, key_bits, s)) return -1;
+        if (icf_reduce(ws, ws.m_keys_sorted.p, ws.m_cnt_sorted.p, (long long)n_m, sentinel, ws.a_keys, ws.a_cnt, &n_acc, s)) return -1;
+      }
+    }
+    GOCTR_HIP(hipStreamSynchronize(s));       // the next pass may grow the buffers this one's launches read
+    u0 = u1;
+  }
+  u64 n_pairs = 0;
+  if (ws.n_pairs.download(&n_pairs, 1)) return -1;
+  if (n_acc) {
+    const long long n = (long long)n_acc;
+    const dim3 grid((unsigned)cdiv(n, 256)), b256(256);
+    if (ws.m_keys.ensure((size_t)n, false) || ws.m_cnt.ensure((size_t)n, false) || ws.m_keys_sorted.ensure((size_t)n, false) ||
+        ws.m_cnt_sorted.ensure((size_t)n, false) || ws.start.alloc((size_t)n_items, false)) return -1;
+    hipLaunchKernelGGL(icf_weight_kernel, grid, b256, 0, s, ws.a_keys.p, ws.a_cnt.p, n, r->cnt.p, (u64)cfg->min_co, ws.m_keys.p, ws.m_cnt.p);
+    GOCTR_HIP(hipGetLastError());
+    if (radix_sort_pairs(ws.temp, ws.m_keys.p, ws.m_keys_sorted.p, ws.m_cnt.p, ws.m_cnt_sorted.p, (size_t)n,
+                         24u + (unsigned int)bits_for(n_items), s)) return -1;
+    hipLaunchKernelGGL(icf_starts_kernel, grid, b256, 0, s, ws.m_keys_sorted.p, n, ws.start.p);
+    GOCTR_HIP(hipGetLastError());
+    hipLaunchKernelGGL(icf_emit_kernel, grid, b256, 0, s, ws.m_keys_sorted.p, ws.m_cnt_sorted.p, n, ws.start.p, M, r->nbr_items.p,
+                       r->nbr_w.p, r->nbr_co.p);
+    GOCTR_HIP(hipGetLastError());
+  }
+  GOCTR_HIP(hipStreamSynchronize(s));         // the scratch goes out of scope; the image is released
+  image.done();
+  r->n_distinct = n_acc; r->total_pairs = n_pairs;
+  *out = r.release();
+  return 0;
+}
+
+void goctr_itemcf_destroy(goctr_itemcf* h) {
+  if (!h) return;
+  EngineScope on(h->eng);
+  std::lock_guard<std::recursive_mutex> lk(h->eng->mu);
+  delete h;
+}
+
+int goctr_itemcf_info(goctr_itemcf* h, int64_t* n_items, int32_t* n_nbr, uint64_t* distinct_pairs, uint64_t* total_pairs,
+                      uint64_t* cache_version) {
+  GOCTR_ENTER_H(h);
+  GOCTR_CHECK(h, "goctr_itemcf_info: null handle");
+  if (n_items) *n_items = h->n_items;
+  if (n_nbr) *n_nbr = h->M;
+  if (distinct_pairs) *distinct_pairs = h->n_distinct;
+  if (total_pairs) *total_pairs = h->total_pairs;
+  if (cache_version) *cache_version = h->cache_version;
+  return 0;
+}
+
+int goctr_itemcf_export(goctr_itemcf* h, uint32_t* cnt, int32_t* nbr_items, uint32_t* nbr_w, uint32_t* nbr_co) {
+  GOCTR_ENTER_H(h);
+  GOCTR_CHECK(h, "goctr_itemcf_export: null handle");
+  const size_t n = (size_t)h->n_items, nm = n * (size_t)h->M;
+  if (cnt && h->cnt.download(cnt, n)) return -1;
+  if (nbr_items && h->nbr_items.download(nbr_items, nm)) return -1;
+  if (nbr_w && h->nbr_w.download(nbr_w, nm)) return -1;
+  if (nbr_co && h->nbr_co.download(nbr_co, nm)) return -1;
+  return 0;
+}
+
+int goctr_itemcf_recall(goctr_itemcf* h, goctr_ubcache* c, const int32_t* users, const int64_t* ts, int64_t n_req,
+                        const goctr_recall_cfg* cfg, int32_t* out_items, uint32_t* out_w, int32_t* out_count,
+                        const int32_t* targets, int32_t* out_target_pos) {
+  GOCTR_ENTER_H(h);
+  const char* who = "goctr_itemcf_recall";
+  GOCTR_CHECK(h && c && users && cfg && out_items && out_w && out_count, "%s: null argument", who);
+  GOCTR_SAME_ENGINE(h, c);
+  if (recall_check_cfg(cfg, who) || recall_check_users(users, n_req, c->n_users, who)) return -1;
+  hipStream_t s = engine().stream;
+  const size_t nq = (size_t)n_req, nc = (size_t)cfg->n_cand;
+  RecallInputs in;
+  DevBuf<int32_t> o_items, o_count, o_tpos;
+  DevBuf<unsigned int> o_w;
+  // the results are staged on the host so that a failing copy leaves the caller's arrays as they were
+  std::vector<int32_t> h_items(nq * nc), h_count(nq), h_tpos(nq);
+  std::vector<unsigned int> h_w(nq * nc);
+  UbRead image(c, s);                         // (behind the buffers: an error return drains the stream before they are freed)
+  if (in.stage(users, ts, targets, n_req, s)) return -1;
+  if (o_items.alloc(nq * nc, false) || o_w.alloc(nq * nc, false) || o_count.alloc(nq, false) || o_tpos.alloc(nq, false)) return -1;
+  if (recall_launch(h, c->off.p, c->items.p, c->ts.p, in, targets != nullptr, n_req, *cfg, o_items.p, o_w.p, o_count.p, o_tpos.p, s))
+    return -1;
+  GOCTR_HIP(hipMemcpyAsync(h_items.data(), o_items.p, sizeof(int32_t) * nq * nc, hipMemcpyDeviceToHost, s));
+  GOCTR_HIP(hipMemcpyAsync(h_w.data(), o_w.p, sizeof(unsigned int) * nq * nc, hipMemcpyDeviceToHost, s));
+  GOCTR_HIP(hipMemcpyAsync(h_count.data(), o_count.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));
+  GOCTR_HIP(hipMemcpyAsync(h_tpos.data(), o_tpos.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));
+  GOCTR_HIP(hipStreamSynchronize(s));
+  image.done();
+  memcpy(out_items, h_items.data(), sizeof(int32_t) * nq * nc);
+  memcpy(out_w, h_w.data(), sizeof(unsigned int) * nq * nc);
+  memcpy(out_count, h_count.data(), sizeof(int32_t) * nq);
+  if (out_target_pos) for (size_t q = 0; q < nq; ++q) out_target_pos[q] = targets ? h_tpos[q] : -1;
+  return 0;
+}
+
+}  // extern "C"

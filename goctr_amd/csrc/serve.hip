@@ -12,6 +12,7 @@
 
 #include "ctr_model.h"
 #include "negsample.h"
+#include "itemcf.h"
 #include "topn.h"
 #include "ubcache.h"
 
@@ -747,6 +748,51 @@ int goctr_recommend_topn(goctr_model* m, goctr_recsys* r, const int32_t* users, 
                             reinterpret_cast<unsigned char*>(sc.out + 4 * Br), false, &n_stamps);
   };
   if (topn_run(sc, a)) return -1;
+  image.done();
+  return 0;
+}
+
+// Recall, then rank (itemcf.hip has the recall, the key generator, the selection and the driver): the same slot lease, locks and
+// ONE image of the cache for the whole call as goctr_recommend_topn above.
+int goctr_recommend_itemcf(goctr_model* m, goctr_recsys* r, goctr_itemcf* h, const int32_t* users, const int64_t* ts, int64_t n_req,
+                           const int32_t* targets, const goctr_recall_cfg* recall_cfg, int32_t k, int64_t pass_rows,
+                           int32_t* out_items, float* out_scores, int32_t* out_count, int32_t* out_cand_count,
+                           int32_t* out_target_pos, int64_t* out_target_rank, int32_t* cand_items, uint32_t* cand_w,
+                           float* cand_scores, int64_t* n_failed) {
+  EngineScope on(handle_engine(m));
+  if (require_engine()) return -1;
+  GOCTR_CHECK(m && r && h && recall_cfg, "goctr_recommend_itemcf: bad arguments");
+  GOCTR_SAME_ENGINE(m, r);
+  GOCTR_SAME_ENGINE(m, h);
+  GOCTR_CHECK(r->emb->D == m->cfg.D && r->U == m->cfg.U && r->C == m->cfg.C, "goctr_recommend_itemcf: recsys dims (U=%d,C=%d,D=%d) != model (U=%d,C=%d,D=%d)",
+              r->U, r->C, r->emb->D, m->cfg.U, m->cfg.C, m->cfg.D);
+  const ItemcfRecArgs a{users, ts, n_req, targets, *recall_cfg, k, pass_rows, out_items, out_scores, out_count, out_cand_count,
+                        out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed};
+  if (itemcf_check_recommend(h, a, r->n_users, r->n_items)) return -1;
+  std::shared_lock<std::shared_mutex> lm(m->mu);        // as serve_keys: weights, then embedding rows, stay put
+  std::shared_lock<std::shared_mutex> le(r->emb->mu);
+  SlotLease lease;
+  ServeSlot* s = lease.s;
+  if (!s) return -1;
+  const int64_t pass = pass_rows ? pass_rows : TOPN_DEFAULT_PASS_ROWS;
+  const int64_t cap_rows = std::max<int64_t>(pass, SERVE_COALESCE_ROWS);
+  if (s->ensure_keys(cap_rows, m->cfg.T, r->U, r->C)) return -1;
+  if (s->ws.ensure((int)cap_rows, m->Ip, m->cfg.T, m->H1p, m->H2p, !chain_ok(m), s->stream)) return -1;
+  if (serve_wait_weights(m, s) || serve_wait_rows(r->emb)) return -1;
+  goctr_ubcache* const c = r->ub;
+  UbRead image(c, s->stream);                           // one image for the recall and every pass
+  TopnScorer sc;
+  sc.stream = s->stream; sc.n_users = r->n_users; sc.n_items = r->n_items;
+  sc.ub_off = c ? c->off.p : nullptr; sc.ub_items = c ? c->items.p : nullptr; sc.ub_ts = c ? c->ts.p : nullptr;
+  sc.max_rows = s->cap; sc.keys = s->d_in.p; sc.out = s->d_out.p;
+  sc.score = [&](int64_t N) {
+    const size_t Br = (size_t)round_up((int)N, 32);
+    unsigned n_stamps = 0;
+    return serve_score_keys(m, r, s, reinterpret_cast<const long long*>(sc.keys), reinterpret_cast<const int32_t*>(sc.keys + 8 * N),
+                            reinterpret_cast<const int32_t*>(sc.keys + 12 * N), N, reinterpret_cast<float*>(sc.out),
+                            reinterpret_cast<unsigned char*>(sc.out + 4 * Br), false, &n_stamps);
+  };
+  if (itemcf_recommend_run(sc, h, a)) return -1;
   image.done();
   return 0;
 }

@@ -26,22 +26,8 @@
 namespace goctr {
 namespace {
 
-constexpr int SEL_THREADS = 1024;               // one position per thread and tile
-constexpr int SEL_CAP = 2048;                   // LDS candidates: the running list (<= 256) + at least one whole tile
 constexpr int SEL_CHUNK = 2048;                 // positions of one request row a workgroup scans
 constexpr size_t TOPN_BITMAP_BYTES = (size_t)256 << 20;
-static_assert(SEL_CAP >= 256 + SEL_THREADS, "a trimmed list and one tile must fit");
-
-__device__ inline unsigned score_order(float s) {
-  unsigned b = __float_as_uint(s);
-  if ((b & 0x7fffffffu) > 0x7f800000u) return 0u;        // NaN: below every number (-inf maps to 0x007fffff)
-  if (b == 0x80000000u) b = 0u;                          // -0 ties with +0
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-// position < 2^31, so the low word is >= 0x80000000: no key is 0
-__device__ inline unsigned long long order_key(float s, unsigned pos) {
-  return ((unsigned long long)score_order(s) << 32) | (unsigned long long)(~pos);
-}
 
 __global__ __launch_bounds__(256) void topn_keys_kernel(const int32_t* __restrict__ users, const long long* __restrict__ ts,
                                                         const int32_t* __restrict__ pool, const int32_t* __restrict__ targets,
@@ -113,48 +99,6 @@ struct SelArgs {
   int cmax;                                                // chunks per request row in this pass; > 1: partial lists
   unsigned long long* pkey; unsigned* praw; int* pcount;   // [segments, cmax, k] / [segments, cmax]
 };
-
-// sorts the candidates in LDS by key, descending, and keeps the first k; *s_thr = the k-th key once the list is full: keys are
-// distinct, so a later candidate at or under it is out for good
-__device__ inline void sel_sort_trim(unsigned long long* skey, unsigned* sraw, int* s_fill, unsigned long long* s_thr, int k) {
-  const int tid = threadIdx.x;
-  const int fill = *s_fill;
-  int n2 = 64;
-  while (n2 < fill) n2 <<= 1;
-  for (int i = fill + tid; i < n2; i += SEL_THREADS) skey[i] = 0ull;
-  __syncthreads();
-  for (int size = 2; size <= n2; size <<= 1)
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = tid; t < (n2 >> 1); t += SEL_THREADS) {
-        const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
-        const bool desc = (lo & size) == 0;
-        const unsigned long long a = skey[lo], b = skey[hi];
-        if (desc ? a < b : a > b) {
-          skey[lo] = b; skey[hi] = a;
-          const unsigned ra = sraw[lo]; sraw[lo] = sraw[hi]; sraw[hi] = ra;
-        }
-      }
-      __syncthreads();
-    }
-  if (tid == 0) { *s_fill = fill < k ? fill : k; *s_thr = fill >= k ? skey[k - 1] : 0ull; }
-  __syncthreads();
-}
-
-// appends the block's candidates of one tile (key 0: none) to the LDS list, sorting and trimming first when they would not fit;
-// returns whether there was any (the same in every thread)
-__device__ inline bool sel_append(unsigned long long* skey, unsigned* sraw, int* s_fill, unsigned long long* s_thr, int k,
-                                  unsigned long long key, unsigned raw) {
-  const int fill = *s_fill;
-  const int n_new = __syncthreads_count(key != 0ull);
-  if (n_new == 0) return false;
-  if (fill + n_new > SEL_CAP) sel_sort_trim(skey, sraw, s_fill, s_thr, k);
-  if (key != 0ull) {
-    const int slot = atomicAdd(s_fill, 1);
-    skey[slot] = key; sraw[slot] = raw;
-  }
-  __syncthreads();
-  return true;
-}
 
 // One workgroup per (touched request row, chunk of SEL_CHUNK of its positions in the pass).  cmax == 1: the workgroup starts from
 // the row's running list and writes it back.  cmax > 1 (a row's part of the pass is longer than a chunk): it starts empty, filters

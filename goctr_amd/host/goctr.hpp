@@ -404,6 +404,70 @@ inline std::vector<ItemScore> Recommend(model::CtrNet& net, RecSys& rs, int user
                                         const std::vector<int32_t>& pool = {}, int exclude = GOCTR_TOPN_DROP_ALL_SEEN) {
   return RecommendBatch(net, rs, {userId}, n, {now}, pool, exclude).lists[0];
 }
+
+// ItemCF recall (goctr_itemcf_*; the "default recall algorithm" recommend/api.go:115-118 leaves open): neighbour lists built
+// from the recSys's own cache over the rows of its item feature table, resident in HBM and independent of the cache afterwards
+class ItemCF {
+ public:
+  static goctr_itemcf_cfg DefaultCfg() { goctr_itemcf_cfg c; goctr_itemcf_cfg_default(&c); return c; }
+  static goctr_recall_cfg DefaultRecallCfg() { goctr_recall_cfg c; goctr_recall_cfg_default(&c); return c; }
+  ItemCF(goctr_ubcache* cache, int64_t n_items, const goctr_itemcf_cfg& cfg = DefaultCfg()) : n_items_(n_items), n_nbr_(cfg.n_nbr) {
+    check(goctr_itemcf_build(cache, n_items, &cfg, &h_));
+  }
+  ItemCF(RecSys& rs, const goctr_itemcf_cfg& cfg = DefaultCfg()) : ItemCF(rs.cache(), rs.n_items(), cfg) {}
+  ItemCF(const ItemCF&) = delete;
+  ItemCF& operator=(const ItemCF&) = delete;
+  ItemCF(ItemCF&& o) noexcept : h_(o.h_), n_items_(o.n_items_), n_nbr_(o.n_nbr_) { o.h_ = nullptr; }
+  ~ItemCF() { goctr_itemcf_destroy(h_); }
+  goctr_itemcf* handle() const { return h_; }
+  int64_t n_items() const { return n_items_; }
+  int n_nbr() const { return n_nbr_; }
+  // neighbour lists [n_items, n_nbr]: items (-1 = unused) and weights
+  void Export(std::vector<int32_t>& nbr_items, std::vector<uint32_t>& nbr_w) const {
+    nbr_items.resize((size_t)n_items_ * n_nbr_); nbr_w.resize((size_t)n_items_ * n_nbr_);
+    check(goctr_itemcf_export(h_, nullptr, nbr_items.data(), nbr_w.data(), nullptr));
+  }
+  // the candidates of every request row (dense user rows of `cache`'s image): row q's first count[q] entries of items / w
+  void Recall(goctr_ubcache* cache, const std::vector<int32_t>& users, const std::vector<int64_t>& ts, const goctr_recall_cfg& cfg,
+              std::vector<int32_t>& items, std::vector<uint32_t>& w, std::vector<int32_t>& count) const {
+    if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("ItemCF::Recall: one timestamp per user");
+    const size_t nq = users.size(), nc = (size_t)std::max(cfg.n_cand, 1);
+    items.resize(nq * nc); w.resize(nq * nc); count.resize(nq);
+    check(goctr_itemcf_recall(h_, cache, users.data(), ts.empty() ? nullptr : ts.data(), (int64_t)nq, &cfg, items.data(), w.data(),
+                              count.data(), nullptr, nullptr));
+  }
+
+ private:
+  goctr_itemcf* h_ = nullptr; int64_t n_items_ = 0; int n_nbr_ = 0;
+};
+
+// recall, then rank (goctr_recommend_itemcf): the model scores the recalled candidates only, so the cost of a request does not
+// grow with the catalogue.  A user without history gets an empty list: fall back to RecommendBatch.
+inline TopN RecommendItemCFBatch(model::CtrNet& net, RecSys& rs, const ItemCF& icf, const std::vector<int32_t>& users, int n = 10,
+                                 const std::vector<int64_t>& ts = {}, const goctr_recall_cfg& rcfg = ItemCF::DefaultRecallCfg(),
+                                 const std::vector<int32_t>& targets = {}, int64_t pass_rows = 0) {
+  const int64_t nq = (int64_t)users.size();
+  if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("RecommendItemCFBatch: one timestamp per user");
+  if (!targets.empty() && targets.size() != users.size()) throw std::invalid_argument("RecommendItemCFBatch: one target per user");
+  if (n < 1) throw std::invalid_argument("RecommendItemCFBatch: n must be positive");
+  std::vector<int32_t> items((size_t)nq * n), count((size_t)nq);
+  std::vector<float> scores((size_t)nq * n);
+  TopN out;
+  if (!targets.empty()) out.target_rank.resize((size_t)nq);
+  check(goctr_recommend_itemcf(net.Vm(), rs.handle(), icf.handle(), users.data(), ts.empty() ? nullptr : ts.data(), nq,
+                               targets.empty() ? nullptr : targets.data(), &rcfg, n, pass_rows, items.data(), scores.data(),
+                               count.data(), nullptr, nullptr, targets.empty() ? nullptr : out.target_rank.data(), nullptr, nullptr,
+                               nullptr, &out.n_failed));
+  out.lists.resize((size_t)nq);
+  for (int64_t q = 0; q < nq; ++q)
+    for (int j = 0; j < count[(size_t)q]; ++j)
+      out.lists[(size_t)q].push_back(ItemScore{items[(size_t)q * n + j], scores[(size_t)q * n + j]});
+  return out;
+}
+inline std::vector<ItemScore> RecommendItemCF(model::CtrNet& net, RecSys& rs, const ItemCF& icf, int userId, int n, int64_t now,
+                                              const goctr_recall_cfg& rcfg = ItemCF::DefaultRecallCfg()) {
+  return RecommendItemCFBatch(net, rs, icf, {userId}, n, {now}, rcfg).lists[0];
+}
 }  // namespace recommend
 
 namespace din {

@@ -1,0 +1,116 @@
+"""recall -- ItemCF recall on the device (goctr_itemcf_*, include/goctr.h).
+
+The reference answers a request without candidates with "todo: some default recall algorithm" (recommend/api.go:115-118).
+``ItemCF`` is that algorithm: item-to-item collaborative filtering over one image of the behaviour cache gives every item a list of
+neighbours (build), and a request row's candidates are the neighbours of its history, summed and ordered on the device (recall).
+``recommend.RecommendItemCF`` ranks them with the model.  Every output is defined bit for bit (tests/itemcf_ref.py is the host
+restatement).
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import capi
+
+EXCLUDE = {"keep": capi.TOPN_KEEP_SEEN, "all": capi.TOPN_DROP_ALL_SEEN, "before": capi.TOPN_DROP_SEEN_BEFORE}
+_BUILD_FIELDS = {"window", "max_len", "n_nbr", "min_co", "pair_budget"}
+_RECALL_FIELDS = {"history", "n_cand", "exclude"}
+
+
+def make_cfg(**kw) -> capi.ItemcfCfg:
+    """goctr_itemcf_cfg from keywords (integers; the ranges are the library's to refuse)"""
+    unknown = set(kw) - _BUILD_FIELDS
+    if unknown:
+        raise TypeError(f"goctr_itemcf_cfg has no field {sorted(unknown)}")
+    return capi.default_itemcf_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
+
+
+def make_recall_cfg(**kw) -> capi.RecallCfg:
+    """goctr_recall_cfg from keywords; ``exclude`` may be given by name ("keep", "all", "before")"""
+    unknown = set(kw) - _RECALL_FIELDS
+    if unknown:
+        raise TypeError(f"goctr_recall_cfg has no field {sorted(unknown)}")
+    if isinstance(kw.get("exclude"), str):
+        if kw["exclude"] not in EXCLUDE:
+            raise ValueError(f"exclude = {kw['exclude']!r} is none of {sorted(EXCLUDE)}")
+        kw["exclude"] = EXCLUDE[kw["exclude"]]
+    return capi.default_recall_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
+
+
+def _as_int(name, v):
+    if isinstance(v, bool) or int(v) != v:
+        raise TypeError(f"{name} = {v!r} is not an integer")
+    return int(v)
+
+
+def request_columns(users, ts, targets):
+    """the request columns as the C-ABI takes them: users int32 [nq], ts int64 [nq] or None, targets int32 [nq] or None"""
+    users = capi.i32(users).ravel()
+    ts = None if ts is None else np.ascontiguousarray(ts, np.int64).ravel()
+    targets = None if targets is None else capi.i32(targets).ravel()
+    if users.size == 0:
+        raise ValueError("no request row")
+    if (ts is not None and ts.size != users.size) or (targets is not None and targets.size != users.size):
+        raise ValueError("ts and targets take one entry per request row")
+    return users, ts, targets
+
+
+class ItemCF:
+    """goctr_itemcf: neighbour lists resident in HBM, immutable after the build and independent of the cache"""
+
+    def __init__(self, ubc, n_items: int, cfg: capi.ItemcfCfg | None = None, **kw):
+        """ubc: a ubcache.UserBehaviorCache (its device image is read) or a raw goctr_ubcache handle"""
+        if cfg is not None and kw:
+            raise TypeError("give either cfg or keywords")
+        cfg = cfg if cfg is not None else make_cfg(**kw)
+        self.n_items = int(n_items)
+        self._h = C.c_void_p()
+        h = ubc.device() if hasattr(ubc, "device") else ubc
+        capi.check(capi.load().goctr_itemcf_build(h, C.c_int64(self.n_items), C.byref(cfg), C.byref(self._h)))
+        self.n_nbr = self.info()["n_nbr"]
+
+    def info(self) -> dict:
+        n, m, d, t, v = C.c_int64(0), C.c_int32(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        capi.check(capi.load().goctr_itemcf_info(self._h, C.byref(n), C.byref(m), C.byref(d), C.byref(t), C.byref(v)))
+        return dict(n_items=n.value, n_nbr=m.value, distinct_pairs=d.value, total_pairs=t.value, cache_version=v.value)
+
+    def export(self) -> dict:
+        """dict(cnt uint32 [n_items], nbr_items int32 [n_items, n_nbr], nbr_w, nbr_co uint32 [n_items, n_nbr])"""
+        n, m = self.n_items, self.n_nbr
+        out = dict(cnt=np.empty(n, np.uint32), nbr_items=np.empty((n, m), np.int32), nbr_w=np.empty((n, m), np.uint32),
+                   nbr_co=np.empty((n, m), np.uint32))
+        capi.check(capi.load().goctr_itemcf_export(self._h, capi.ptr(out["cnt"], C.c_uint32), capi.ptr(out["nbr_items"], C.c_int32),
+                                                   capi.ptr(out["nbr_w"], C.c_uint32), capi.ptr(out["nbr_co"], C.c_uint32)))
+        return out
+
+    def recall(self, ubc, users, ts=None, targets=None, cfg: capi.RecallCfg | None = None, **kw) -> dict:
+        """goctr_itemcf_recall over DENSE user rows of ``ubc``'s image: dict(items int32 [nq, n_cand] (-1 = unused), w uint32
+        [nq, n_cand], count int32 [nq], target_pos int32 [nq] when targets are given)"""
+        if cfg is not None and kw:
+            raise TypeError("give either cfg or keywords")
+        cfg = cfg if cfg is not None else make_recall_cfg(**kw)
+        users, ts, targets = request_columns(users, ts, targets)
+        nq, nc = users.size, max(int(cfg.n_cand), 1)
+        out = dict(items=np.full((nq, nc), -2, np.int32), w=np.full((nq, nc), 0xffffffff, np.uint32), count=np.full(nq, -2, np.int32))
+        tpos = np.full(nq, -2, np.int32) if targets is not None else None
+        h = ubc.device() if hasattr(ubc, "device") else ubc
+        capi.check(capi.load().goctr_itemcf_recall(self._h, h, capi.ptr(users, C.c_int32), capi.ptr(ts, C.c_int64), C.c_int64(nq),
+                                                   C.byref(cfg), capi.ptr(out["items"], C.c_int32), capi.ptr(out["w"], C.c_uint32),
+                                                   capi.ptr(out["count"], C.c_int32), capi.ptr(targets, C.c_int32),
+                                                   capi.ptr(tpos, C.c_int32)))
+        if tpos is not None:
+            out["target_pos"] = tpos
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            capi.load().goctr_itemcf_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -536,3 +536,114 @@ def EvaluateLeaveOneOutFull(model: Predictor, k=10, sample_kw=None, details=Fals
     if details:
         out.update(rank=rank, user_index=users, target_index=targets, ts=ts)
     return out
+
+
+def BuildItemCF(recSys: DeviceRecSys, **cfg):
+    """EXTENSION: the ItemCF neighbour lists (recall.ItemCF; ``cfg``: goctr_itemcf_cfg fields) of the recSys's own behaviour cache
+    over the rows of its item feature table -- what RecommendItemCF recalls from.  The lists are those of the cache's image at
+    THIS call; rebuild them when enough new behaviour has come in."""
+    from .recall import ItemCF
+    if recSys.ubcache is None:
+        raise RuntimeError("this recSys has no behaviour cache to build neighbour lists from (it does not implement UserBehavior, rcmd.go:512)")
+    return ItemCF(recSys._dense_cache, recSys.item_table.shape[0], **cfg)
+
+
+def itemcf(model: Predictor, icf, users, ts=None, targets=None, k=10, pass_rows=0, validate=False, recall_cfg=None, **recall_kw):
+    """goctr_recommend_itemcf over DENSE indices (users [nq], ts [nq] or None, targets [nq] or None): dict(items [nq, k], scores
+    [nq, k], count [nq], cand_count [nq], n_failed, target_pos / target_rank [nq] when targets are given, cand_items / cand_w /
+    cand_scores [nq, n_cand] when ``validate``).  ``recall_kw``: goctr_recall_cfg fields (history, n_cand, exclude -- also by
+    name).  What RecommendItemCF / RecommendItemCFBatch / EvaluateLeaveOneOutRecall call."""
+    from .recall import make_recall_cfg, request_columns
+    if recall_cfg is not None and recall_kw:
+        raise TypeError("give either recall_cfg or keywords")
+    cfg = recall_cfg if recall_cfg is not None else make_recall_cfg(**recall_kw)
+    rs = model.recSys
+    users, ts, targets = request_columns(users, ts, targets)
+    nq, kk, nc = users.size, max(int(k), 1), max(int(cfg.n_cand), 1)
+    out = dict(items=np.full((nq, kk), -2, np.int32), scores=np.full((nq, kk), np.nan, np.float32), count=np.full(nq, -2, np.int32),
+               cand_count=np.full(nq, -2, np.int32))
+    tpos = np.full(nq, -2, np.int32) if targets is not None else None
+    rank = np.full(nq, -2, np.int64) if targets is not None else None
+    cand_items = np.full((nq, nc), -2, np.int32) if validate else None
+    cand_w = np.full((nq, nc), 0xffffffff, np.uint32) if validate else None
+    cand_scores = np.full((nq, nc), np.nan, np.float32) if validate else None
+    nf = C.c_int64(-2)
+    capi.check(capi.load().goctr_recommend_itemcf(
+        model.net._h, rs._h, icf._h, capi.ptr(users, C.c_int32), capi.ptr(ts, C.c_int64), C.c_int64(nq),
+        capi.ptr(targets, C.c_int32), C.byref(cfg), C.c_int32(int(k)), C.c_int64(int(pass_rows)), capi.ptr(out["items"], C.c_int32),
+        capi.ptr(out["scores"], C.c_float), capi.ptr(out["count"], C.c_int32), capi.ptr(out["cand_count"], C.c_int32),
+        capi.ptr(tpos, C.c_int32), capi.ptr(rank, C.c_int64), capi.ptr(cand_items, C.c_int32), capi.ptr(cand_w, C.c_uint32),
+        capi.ptr(cand_scores, C.c_float), C.byref(nf)))
+    out["n_failed"] = nf.value
+    if targets is not None:
+        out["target_pos"], out["target_rank"] = tpos, rank
+    if validate:
+        out["cand_items"], out["cand_w"], out["cand_scores"] = cand_items, cand_w, cand_scores
+    return out
+
+
+def RecommendItemCFBatch(model: Predictor, icf, userIds, n=10, now=None, **recall_kw):
+    """RecommendItemCF for several users in one device call: [[ItemScore]] in the order of userIds.  ``now``: one timestamp for
+    all, or one per user.  An unknown user raises SampleVectorError like Rank's failing first key; a user without history gets
+    an empty list (there is no popularity fill: fall back to RecommendBatch)."""
+    rs = model.recSys
+    userIds = list(userIds)
+    users = np.array([rs.user_index(u) for u in userIds], np.int32)
+    if users.size == 0:
+        return []
+    if (users < 0).any():
+        bad = userIds[int(np.flatnonzero(users < 0)[0])]
+        raise SampleVectorError(f"get sample vector error: user {bad} has no features")
+    ts = np.broadcast_to(np.asarray(int(time.time()) if now is None else now, np.int64), users.shape)
+    try:
+        r = itemcf(model, icf, users, ts, None, n, **recall_kw)
+    except capi.GoctrError as e:
+        raise SampleVectorError(str(e)) from None
+    raw = rs._row_keys
+    return [[ItemScore(int(raw[r["items"][q, j]]), float(r["scores"][q, j])) for j in range(int(r["count"][q]))]
+            for q in range(users.size)]
+
+
+def RecommendItemCF(model: Predictor, icf, userId: int, n=10, now=None, **recall_kw):
+    """EXTENSION -- recall, then rank: the candidates are the ItemCF neighbours (``icf``: BuildItemCF) of the user's newest
+    ``history`` behaviours at or before ``now``, at most ``n_cand`` of them by summed neighbour weight; the model scores those and
+    the ``n`` best come back, best first, ties by the candidate's place in the recalled list.  ``exclude`` as Recommend's.  Unlike
+    Recommend the cost does not grow with the catalogue."""
+    return RecommendItemCFBatch(model, icf, [userId], n, now, **recall_kw)[0]
+
+
+def EvaluateLeaveOneOutRecall(model: Predictor, icf, k=10, sample_kw=None, details=False, pass_rows=0, **recall_kw):
+    """EvaluateLeaveOneOutFull's protocol over RECALLED candidates: every user's newest entry is held out (key timestamp ts - 1,
+    DROP_SEEN_BEFORE unless ``exclude`` says otherwise), the ItemCF recall proposes ``n_cand`` candidates from the history the key
+    sees and the model ranks them.  In float64 on the host, over the users whose held-out item is a row of the item table,
+        recall = mean(target_pos >= 0)        the recall stage alone: recall@n_cand
+        hit_rate = mean(0 <= rank < k)    ndcg = mean(1 / log2(rank + 2) if 0 <= rank < k else 0)
+    where rank is the target's rank among the recalled candidates (-1: not recalled -- a miss, unlike EvaluateLeaveOneOutFull,
+    where every target has a rank).  ``icf`` should be built without the held-out entries for an honest figure; that is the
+    caller's choice.  Returns dict(users, skipped, k, n_cand, recall, hit_rate, ndcg); details=True adds the columns."""
+    from .recall import make_recall_cfg
+    from .sampling import Samples
+    rs = model.recSys
+    if rs.ubcache is None:
+        raise RuntimeError("this recSys has no behaviour cache to hold items out of (it does not implement UserBehavior, rcmd.go:512)")
+    kw = dict(n_neg=0, which="newest")
+    kw.update(sample_kw or {})
+    smp = Samples(rs._dense_cache, rs.item_table.shape[0], **kw)
+    if smp.rows == 0:
+        raise SampleVectorError("the behaviour cache holds no entry that qualifies as a positive")
+    users, targets, ts, _y = smp.export()
+    recall_kw.setdefault("exclude", "before")
+    cfg = make_recall_cfg(**recall_kw)
+    r = itemcf(model, icf, users, ts, targets, k, pass_rows, recall_cfg=cfg)
+    ok = (targets >= 0) & (targets < rs.item_table.shape[0])
+    pos, rank = r["target_pos"][ok].astype(np.int64), r["target_rank"][ok].astype(np.float64)
+    n = int(ok.sum())
+    hit = (rank >= 0) & (rank < k)
+    nan = float("nan")
+    out = dict(users=n, skipped=int((~ok).sum()), k=int(k), n_cand=int(cfg.n_cand),
+               recall=float(np.mean(pos >= 0)) if n else nan,
+               hit_rate=float(np.mean(hit)) if n else nan,
+               ndcg=float(np.mean(np.where(hit, 1.0 / np.log2(np.where(hit, rank, 0.0) + 2.0), 0.0))) if n else nan)
+    if details:
+        out.update(target_pos=r["target_pos"], rank=r["target_rank"], user_index=users, target_index=targets, ts=ts)
+    return out

@@ -378,6 +378,104 @@ int goctr_recommend_topn(goctr_model* m, goctr_recsys* r,
                          float* all_scores /* [n_users_req,n_pool] or NULL */, uint8_t* all_flags /* same shape or NULL */,
                          int64_t* n_failed);
 
+/* ---- ItemCF recall on the device (no reference counterpart: the "default recall algorithm" recommend/api.go:115-118 leaves
+ * open).  Item-to-item collaborative filtering over ONE image of the behaviour cache gives every item a list of neighbours;
+ * a request row's candidates are the neighbours of its history, and goctr_recommend_itemcf ranks them with the model.  Every
+ * output is defined bit for bit (tests/itemcf_ref.py is the host restatement); all arithmetic that decides an output is
+ * integer except the weight formula, which is pinned to correctly rounded IEEE double operations.
+ *
+ * goctr_itemcf_build:
+ *   considered     of every user, the valid entries (0 <= item < n_items) in sequence order, newest first; with max_len > 0
+ *                  only the first max_len of them: v_0 .. v_{L-1}
+ *   cnt[i]         considered entries that hold item i, over all users
+ *   pair           positions a < b of one user with b - a <= window and v_a != v_b; it adds 1 to co(v_a, v_b) and 1 to
+ *                  co(v_b, v_a) (64-bit counts; repeats are not de-duplicated)
+ *   weight         w(i,j) = (uint32) floor((double)co / sqrt((double)(cnt_i * cnt_j)) * 65536.0): the product exact in
+ *                  uint64, the conversions round to nearest, sqrt and division correctly rounded, nothing contracted.
+ *                  co <= 2 window min(cnt_i, cnt_j), so w <= 2^23
+ *   neighbours     of i: every j with co(i,j) >= min_co and w(i,j) > 0, by w descending, then j ascending; the first n_nbr
+ *                  are stored: nbr_items [n_items, n_nbr] (padding -1), nbr_w and nbr_co (co saturated at 2^32 - 1; padding 0)
+ *   passes         users are taken in consecutive groups whose position pairs (a < b, b - a <= window, whatever the items)
+ *                  fit pair_budget; a group holds at least one user, so a user with more pairs than the budget gets a pass
+ *                  alone.  Scratch is bounded by the budget plus the distinct pairs so far; no output byte depends on it.
+ *                  Every pass waits for the device once or twice, and every pass after the first sorts the whole list of
+ *                  distinct pairs so far again: P passes over D distinct pairs cost O(P D) on top of the pairs' own sort,
+ *                  so a small budget on a large cache is slow -- keep the default unless memory forces a smaller one
+ *   refused        (-1, *out untouched) a cfg outside its ranges, n_items <= 0; and the limits of the implementation,
+ *                  n_items > 2^31 - 1 (items are 32-bit) or a single pass of 2^36 or more position pairs (one user with
+ *                  that many, or a pair_budget that lets a pass grow so far)
+ * An empty cache is not an error: every list is empty.  The handle is immutable and independent of the cache. */
+typedef struct {
+  int32_t window;       /* 1 .. 64                       default 5  */
+  int32_t max_len;      /* >= 0; 0 = all                 default 0  */
+  int32_t n_nbr;        /* 1 .. 256                      default 64 */
+  int32_t min_co;       /* >= 1                          default 1  */
+  int64_t pair_budget;  /* 0 = 2^26, else 2^10 .. 2^30   default 0  */
+} goctr_itemcf_cfg;
+void goctr_itemcf_cfg_default(goctr_itemcf_cfg* c);
+typedef struct goctr_itemcf goctr_itemcf;
+int  goctr_itemcf_build(goctr_ubcache* c, int64_t n_items, const goctr_itemcf_cfg* cfg, goctr_itemcf** out);
+void goctr_itemcf_destroy(goctr_itemcf* h);
+/* each may be NULL; distinct_pairs: directed pairs (i,j) with co > 0; total_pairs: pairs counted; cache_version: of the image */
+int  goctr_itemcf_info(goctr_itemcf* h, int64_t* n_items, int32_t* n_nbr, uint64_t* distinct_pairs, uint64_t* total_pairs,
+                       uint64_t* cache_version);
+/* each may be NULL */
+int  goctr_itemcf_export(goctr_itemcf* h, uint32_t* cnt /*[n_items]*/, int32_t* nbr_items /*[n_items,n_nbr]*/,
+                         uint32_t* nbr_w /*same*/, uint32_t* nbr_co /*same*/);
+
+/* goctr_itemcf_recall: the candidates of n_req request rows, one workgroup per row.
+ *   history        of row q: the entries of users[q]'s sequence that TimeSeq.Filter(ts[q], 0) keeps (those with
+ *                  Ts <= ts[q]; ts NULL or ts[q] == 0 = all) in the ONE image of the cache the call holds; of these the
+ *                  valid ones (0 <= item < the handle's n_items), and of those the first `history`.  A repeated item
+ *                  counts each time
+ *   score          S(q,j) = the sum of w(h_t, j) over the history entries h_t whose stored list holds j: a uint32 sum,
+ *                  at most 2^31, exact
+ *   seen           candidate j equals a valid item among the entries of users[q]'s sequence that the mode looks at:
+ *                  DROP_ALL_SEEN the whole sequence, DROP_SEEN_BEFORE exactly the entries TimeSeq.Filter(ts[q], 0) keeps,
+ *                  KEEP_SEEN none.  A seen candidate is dropped unless it is targets[q] (targets may be NULL)
+ *   order          S descending, then item ascending
+ *   outputs        out_count[q] = min(n_cand, candidates); row q of out_items / out_w holds them in that order, the rest
+ *                  item -1, weight 0; out_target_pos[q] (may be NULL) = the target's place in the kept list, or -1
+ *   refused        (-1, nothing touched) a users[q] outside [0, n_users); history outside 1 .. 256; n_cand outside
+ *                  1 .. 1024; exclude no GOCTR_TOPN_* value; n_req <= 0; and the limit of the implementation,
+ *                  n_req > 2^24
+ * A row with an empty history returns count 0: there is no popularity fill, callers fall back to goctr_recommend_topn.
+ * A row's lists may be processed in tiles (ranges of candidate items); no output depends on the tiling. */
+typedef struct {
+  int32_t history;      /* 1 .. 256                      default 50  */
+  int32_t n_cand;       /* 1 .. 1024                     default 256 */
+  int32_t exclude;      /* GOCTR_TOPN_*                  default GOCTR_TOPN_DROP_ALL_SEEN */
+} goctr_recall_cfg;
+void goctr_recall_cfg_default(goctr_recall_cfg* c);
+int  goctr_itemcf_recall(goctr_itemcf* h, goctr_ubcache* c, const int32_t* users, const int64_t* ts /* NULL = 0 */,
+                         int64_t n_req, const goctr_recall_cfg* cfg, int32_t* out_items /*[n_req,n_cand]*/,
+                         uint32_t* out_w /*[n_req,n_cand]*/, int32_t* out_count /*[n_req]*/,
+                         const int32_t* targets /*[n_req] or NULL*/, int32_t* out_target_pos /*[n_req] or NULL*/);
+
+/* goctr_recommend_itemcf: recall, then rank.  A serving entry like goctr_recommend_topn (slot, locks, one image of the cache
+ * for the whole call): the recall runs on the slot's stream, the keys (users[q], candidate, ts[q]) of the kept candidates
+ * are written and scored in HBM pass_rows rows at a time (0 = 65536, else 16 .. 65536), and one workgroup per row keeps the
+ * best k (1 .. 256) by goctr_recommend_topn's order rule with the candidate's place in the recalled list as the position:
+ * score descending, then place ascending; -0 ties with +0; NaN last.
+ *   score          as goctr_recommend_topn: a pass of fewer than 8192 rows is bit-identical to goctr_batch_predict on the
+ *                  same keys, larger passes are within the serving path's bound
+ *   failed         a candidate whose item has no feature row is never returned and adds one to *n_failed
+ *   outputs        out_items / out_scores [n_req,k] and out_count [n_req] as goctr_recommend_topn's; out_cand_count [n_req]
+ *                  the recall's count; out_target_pos [n_req] the recall's; out_target_rank [n_req] = the eligible
+ *                  candidates in front of the target, or -1 (no targets, target not recalled, or it failed).  The last
+ *                  three and the validation outputs cand_items / cand_w / cand_scores [n_req,n_cand] (unused slots -1 /
+ *                  0 / +0) may each be NULL
+ *   refused        goctr_recommend_topn's refusals (n_req > 2^24 among them), a recall cfg outside its ranges, and a handle
+ *                  whose n_items differs from the recsys's
+ * A recsys without a cache has no history: every row comes back empty. */
+int goctr_recommend_itemcf(goctr_model* m, goctr_recsys* r, goctr_itemcf* h,
+                           const int32_t* users, const int64_t* ts /* NULL = 0 */, int64_t n_req,
+                           const int32_t* targets /* [n_req] or NULL */, const goctr_recall_cfg* recall_cfg,
+                           int32_t k, int64_t pass_rows,
+                           int32_t* out_items /* [n_req,k] */, float* out_scores /* [n_req,k] */, int32_t* out_count,
+                           int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank,
+                           int32_t* cand_items, uint32_t* cand_w, float* cand_scores, int64_t* n_failed);
+
 /* The replica a multi-device training call (cfg.devices = n) keeps on engine `rank` (rank 0: the handle itself); NULL before
  * the first such call.  Borrowed: owned by the handle it was asked from.  For checks that the replicas are bit-identical
  * (tests, bench.py's replica checksum) -- every entry point works on it, on its own engine. */
