@@ -60,7 +60,7 @@ struct Engine {
     std::mutex mu;
   } arena;
   bool kernel_attrs_done = false, mlp_attrs_done = false;   // hipFuncSetAttribute is per device: once per engine
-  void* serve_pool = nullptr;     // serve.hip: this engine's serving slots (streams + pinned staging live on its device)
+  void* serve_pool = nullptr;     // serve.hip: this engine's serving slots (streams + staging buffers, staging.h, live on its device)
   int compute_units = 0;
   bool large_bar = false;      // the host can write device memory through the PCIe BAR (hipDeviceProp_t::isLargeBar)
   hipStream_t stream = nullptr;   // the engine's main stream
@@ -191,8 +191,8 @@ inline void prof_note_kernel(int id, const char* symbol) { engine().prof_kernel[
 // separately-mapped allocations.  Requests that do not fit fall back to a plain hipMalloc.
 void* arena_alloc(size_t bytes);              // from the calling thread's engine
 // Fine-grained DEVICE memory that the host may store into through the PCIe BAR (a k-NN call's queries, a serving pass's keys:
-// search.hip, serve.hip), or null: no large BAR, the runtime refuses, or the range is not mapped writable into this process
-// (checked in /proc/self/maps before anybody stores into it).  Freed with hipFree.
+// search.hip, serve.hip, both through staging.h's BarBuf), or null: no large BAR, the runtime refuses, or the range is not mapped
+// writable into this process (checked in /proc/self/maps before anybody stores into it).  Freed with hipFree.
 void* bar_alloc(size_t bytes);
 void arena_free(Engine* owner, void* p);      // back to the engine it came from (any thread)
 

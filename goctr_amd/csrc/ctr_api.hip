@@ -1,5 +1,6 @@
 // ctr_api.hip -- the C ABI (include/goctr.h) of the DIN / YouTube-DNN engine: models, embedding tables, the standalone
-// gather and datasets, and the training and predict entry points above the step (ctr.hip and ctr_run.hip, through ctr_model.h).
+// gather and datasets (the key datasets too), and the training and predict entry points above the step (ctr.hip and ctr_run.hip,
+// through ctr_model.h).
 #define GOCTR_NO_PLAIN_KERNELS      // the kernel headers' plain kernels belong to ctr.hip
 #include <algorithm>
 #include <memory>
@@ -7,6 +8,8 @@
 
 #include "ctr_model.h"
 #include "metrics.h"
+#include "negsample.h"
+#include "ubcache.h"
 
 namespace goctr {
 
@@ -161,6 +164,24 @@ int download_padded(goctr_model* m, const float* flat_dev, int tensor_id, float*
   }
   set_error("unknown tensor id %d", tensor_id);
   return -1;
+}
+
+// The body goctr_dataset_create_keys and goctr_dataset_create_samples share: the keys are on the device (d->users,
+// d->item_ids, key_ts), the feature tables come from the host; one assembly launch over one image of the cache.
+int assemble_key_dataset(goctr_ubcache* c, const float* user_table, int64_t n_users, int U, const float* item_table,
+                         int64_t n_items, int C, goctr_dataset* d, const long long* key_ts, int64_t rows, int T) {
+  d->id_mode = true; d->rows = rows; d->U = U; d->C = C; d->T = T;
+  DevBuf<float> dut, dit;
+  if (dut.alloc((size_t)n_users * U, false) || (U && dut.upload(user_table, (size_t)n_users * U))) return -1;
+  if (dit.alloc((size_t)n_items * C, false) || (C && dit.upload(item_table, (size_t)n_items * C))) return -1;
+  if (d->ub_ids.alloc((size_t)rows * T, false)) return -1;
+  if (d->ufeat.alloc((size_t)rows * U, false) || d->cfeat.alloc((size_t)rows * C, false)) return -1;
+  UbRead image(c, engine().stream);
+  if (launch_assemble_keys(engine().stream, c->off.p, c->items.p, c->ts.p, c->n_users, dut.p, U, dit.p, n_items, C, d->users.p,
+                           d->item_ids.p, key_ts, rows, T, d->ub_ids.p, d->ufeat.p, d->cfeat.p, nullptr, nullptr)) return -1;
+  GOCTR_HIP(hipStreamSynchronize(engine().stream));   // the temporaries above are released on return
+  image.done();
+  return 0;
 }
 
 }  // namespace
@@ -443,6 +464,63 @@ int goctr_dataset_create_ids(const int32_t* ub_ids, const int32_t* item_ids, con
   *out = d.release();
   return 0;
 }
+// assembled on the device from sample keys and the behaviour cache
+int goctr_dataset_create_keys(goctr_ubcache* c, const float* user_table, int64_t n_users, int U, const float* item_table,
+                              int64_t n_items, int C, const int32_t* users, const int32_t* items, const int64_t* ts,
+                              const float* Y, int64_t rows, int T, goctr_dataset** out) {
+  GOCTR_ENTER_H(c);
+  GOCTR_CHECK(c && users && items && rows > 0 && T > 0 && out && n_items >= 0 && U >= 0 && C >= 0,
+              "goctr_dataset_create_keys: bad arguments");
+  GOCTR_CHECK(n_users == c->n_users, "goctr_dataset_create_keys: user table has %lld rows, the behaviour cache %lld users",
+              (long long)n_users, (long long)c->n_users);
+  GOCTR_CHECK((U == 0 || user_table) && (C == 0 || item_table), "goctr_dataset_create_keys: feature table missing");
+  std::unique_ptr<goctr_dataset> d(new goctr_dataset);
+  DevBuf<long long> dts;
+  std::vector<long long> t(rows, 0);
+  if (ts) for (int64_t i = 0; i < rows; ++i) t[i] = ts[i];
+  // (d->users stays resident: the rows' groups for goctr_evaluate_dataset_grouped)
+  if (d->users.alloc(rows, false) || d->users.upload(users, rows) || dts.alloc(rows, false) || dts.upload(t.data(), rows) ||
+      d->item_ids.alloc(rows, false) || d->item_ids.upload(items, rows)) return -1;
+  if (assemble_key_dataset(c, user_table, n_users, U, item_table, n_items, C, d.get(), dts.p, rows, T)) return -1;
+  if (Y) { if (d->Y.alloc(rows, false) || d->Y.upload(Y, rows)) return -1; d->has_y = true; }
+  *out = d.release();
+  return 0;
+}
+
+// the same dataset from key columns that are already in HBM (goctr_samples_create): three device-to-device copies instead of
+// the key uploads; only the feature tables come from the host
+int goctr_dataset_create_samples(goctr_ubcache* c, const float* user_table, int64_t n_users, int U, const float* item_table,
+                                 int64_t n_items, int C, goctr_samples* s, int T, goctr_dataset** out) {
+  GOCTR_ENTER_H(c);
+  GOCTR_CHECK(c && s && T > 0 && out && n_items >= 0 && U >= 0 && C >= 0, "goctr_dataset_create_samples: bad arguments");
+  GOCTR_SAME_ENGINE(c, s);
+  GOCTR_CHECK(s->rows > 0, "goctr_dataset_create_samples: the samples hold no row");
+  GOCTR_CHECK(n_users == c->n_users, "goctr_dataset_create_samples: user table has %lld rows, the behaviour cache %lld users",
+              (long long)n_users, (long long)c->n_users);
+  GOCTR_CHECK((U == 0 || user_table) && (C == 0 || item_table), "goctr_dataset_create_samples: feature table missing");
+  const int64_t rows = s->rows;
+  std::unique_ptr<goctr_dataset> d(new goctr_dataset);
+  if (d->users.alloc(rows, false) || d->item_ids.alloc(rows, false) || d->Y.alloc(rows, false)) return -1;
+  hipStream_t st = engine().stream;
+  GOCTR_HIP(hipMemcpyAsync(d->users.p, s->users.p, sizeof(int32_t) * (size_t)rows, hipMemcpyDeviceToDevice, st));
+  GOCTR_HIP(hipMemcpyAsync(d->item_ids.p, s->items.p, sizeof(int32_t) * (size_t)rows, hipMemcpyDeviceToDevice, st));
+  GOCTR_HIP(hipMemcpyAsync(d->Y.p, s->y.p, sizeof(float) * (size_t)rows, hipMemcpyDeviceToDevice, st));
+  d->has_y = true;
+  if (assemble_key_dataset(c, user_table, n_users, U, item_table, n_items, C, d.get(), s->ts.p, rows, T)) return -1;
+  *out = d.release();
+  return 0;
+}
+
+// read back the assembled keys of an id-mode dataset (tests, debugging)
+int goctr_dataset_get_ids(goctr_dataset* d, int32_t* ub_ids, float* user_feat, float* ctx_feat) {
+  GOCTR_ENTER_H(d);
+  GOCTR_CHECK(d && d->id_mode, "goctr_dataset_get_ids: not an id-mode dataset");
+  if (ub_ids && d->ub_ids.download(ub_ids, (size_t)d->rows * d->T)) return -1;
+  if (user_feat && d->U && d->ufeat.download(user_feat, (size_t)d->rows * d->U)) return -1;
+  if (ctx_feat && d->C && d->cfeat.download(ctx_feat, (size_t)d->rows * d->C)) return -1;
+  return 0;
+}
+
 void goctr_dataset_destroy(goctr_dataset* d) {
   if (!d) return;
   for (goctr_dataset* s : d->shards) goctr_dataset_destroy(s);

@@ -4,9 +4,9 @@
 //   ctr.hip         the dense step: schedules, workspace, forward, backward, reduce, Adam
 //   ctr_emb.hip     the trainable-embedding step: workspace, sparse plan, the launches of emb_train.h, the exchange
 //   ctr_run.hip     the step driver: eager step, graph capture, run_steps
-//   ctr_api.hip     C ABI of models, tables, gather and datasets; the training and predict entry points
+//   ctr_api.hip     C ABI of models, tables, gather and datasets (key datasets included); the training and predict entry points
 //   ctr_multi.hip   single-call multi-device training (goctr_train_cfg::devices)
-//   serve.hip       behaviour cache, key datasets and serving (goctr_rank, goctr_batch_predict, goctr_predict_dense)
+//   serve.hip       serving (goctr_rank, goctr_batch_predict, goctr_predict_dense, the goctr_recommend_* entries)
 //   emb_w2v.hip     goctr_emb_load_w2v: an item2vec model's vectors into a table, in HBM
 // A translation unit other than ctr.hip defines GOCTR_NO_PLAIN_KERNELS before it includes this header: the plain kernels of
 // the kernel headers are compiled in ctr.hip only (those of emb_train.h, which only ctr_emb.hip includes, in ctr_emb.hip).

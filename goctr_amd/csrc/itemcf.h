@@ -1,6 +1,6 @@
-// itemcf.h -- the handle of goctr_itemcf_build (itemcf.hip) and what goctr_recommend_itemcf's two halves share: serve.hip owns
-// the serving slot, the locks and the scoring path (topn.h: TopnScorer), itemcf.hip the recall, the key generator, the selection
-// and the call's driver.
+// itemcf.h -- the handle of goctr_itemcf_build (itemcf.hip) and what goctr_recommend_itemcf's two halves share: serve.hip has
+// the entry point and lends the same TopnScorer as to top-N (topn.h; with_scorer: the serving slot, the locks, the cache image,
+// the scoring path); itemcf.hip has the recall, the key generator, the selection and the call's driver.
 #pragma once
 #include "topn.h"
 

@@ -1,4 +1,4 @@
-// negsample.h -- the handle of goctr_samples_create (negsample.hip), read by goctr_dataset_create_samples (serve.hip).
+// negsample.h -- the handle of goctr_samples_create (negsample.hip), read by goctr_dataset_create_samples (ctr_api.hip).
 #pragma once
 #include "common.h"
 

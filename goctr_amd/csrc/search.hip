@@ -45,6 +45,7 @@
 #include <vector>
 
 #include "common.h"
+#include "staging.h"
 #include "w2v_model.h"
 
 using namespace goctr;
@@ -61,15 +62,12 @@ struct goctr_searcher {
   DevBuf<unsigned short> items_bf;           // the same rows as two bf16 planes [2][rows padded][D]: hi = bf16(x), lo = bf16(x - hi)
   DevBuf<float> bmax;                        // per (tile, sub-block, query) maxima [tiles][sub-blocks][padded queries]
   DevBuf<unsigned char> in_pack, out_pack;
-  void* h_in = nullptr; void* h_out = nullptr; size_t h_in_bytes = 0, h_out_bytes = 0;
+  PinnedBuf h_in, h_out;                     // (staging.h: grown to twice what a call needs, outgrown ones freed with the handle)
   // the call's input in fine-grained DEVICE memory that the host writes through the PCIe BAR (large-BAR systems): no copy command
   // in front of the scan kernel.  bar_state: 0 untried, 1 allocated, -1 refused by the runtime (the staged copy stays)
-  unsigned char* in_bar = nullptr; size_t in_bar_bytes = 0; int bar_state = 0;
-  std::vector<void*> retired_dev;            // outgrown in_bar buffers (hipFree waits for the whole device: with the handle)
+  BarBuf in_bar; int bar_state = 0;
   bool lds_ok = false;
   std::mutex mu;
-  std::vector<void*> retired;                // outgrown pinned buffers: freed with the handle (hipHostFree waits for the whole device)
-  ~goctr_searcher() { for (void* p : retired_dev) (void)hipFree(p); if (in_bar) (void)hipFree(in_bar); for (void* p : retired) (void)hipHostFree(p); if (h_in) (void)hipHostFree(h_in); if (h_out) (void)hipHostFree(h_out); }
 };
 
 namespace {
@@ -354,11 +352,6 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const double* __restrict
 // ------------------------------------------------------------------------------------------------------------- scan path
 constexpr int KNN2_QB = 64;        // queries per workgroup (the rows are read once per block: once per call up to 64 queries)
 constexpr int KNN2_CAP = 2048;     // candidates per query the replay kernel takes
-
-template <int CTRL>
-__device__ __forceinline__ float knn_dpp_f32(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
 
 // knn_scan_kernel<D, IPT>: a thread keeps IPT normalised float32 rows in registers (read ONCE) and walks the block's queries; a
 // query's components are wavefront-uniform and arrive by SCALAR loads (constant address space) straight into the SGPR operands of
@@ -940,37 +933,22 @@ static int knn_search_scan(goctr_searcher* s, const double* queries, int Q, int 
   const bool bf = knn_scan_mfma(s, Q);               // the bf16-plane matrix-core filter (from 12 queries per call on, D = 16 / 32)
   const size_t in_qbf = bf ? sizeof(unsigned short) * 2 * (size_t)nqb * KNN2_QB * D : 0, in_bytes = in_q + in_ig + in_q32 + in_qbf;
   const size_t o_idx = sizeof(long long) * (size_t)Q * k, o_sim = sizeof(double) * (size_t)Q * k, out_bytes = o_idx + o_sim + sizeof(int) * (size_t)Q;
-  if (s->h_in_bytes < in_bytes) {
-    if (s->h_in) s->retired.push_back(s->h_in);
-    s->h_in = nullptr; s->h_in_bytes = 0;
-    GOCTR_HIP(hipHostMalloc(&s->h_in, in_bytes * 2, hipHostMallocDefault));
-    s->h_in_bytes = in_bytes * 2;
-  }
-  if (s->h_out_bytes < out_bytes) {
-    if (s->h_out) s->retired.push_back(s->h_out);
-    s->h_out = nullptr; s->h_out_bytes = 0;
-    GOCTR_HIP(hipHostMalloc(&s->h_out, out_bytes * 2, hipHostMallocDefault));
-    s->h_out_bytes = out_bytes * 2;
-  }
+  if (s->h_in.bytes < in_bytes && s->h_in.grow(in_bytes * 2)) return -1;
+  if (s->h_out.bytes < out_bytes && s->h_out.grow(out_bytes * 2)) return -1;
   const int qpad = nqb * KNN2_QB;
   // Where the kernels read the input from: device memory the host wrote through the BAR (a 14 KB store burst, ~3 us, instead of a
   // 4.4 us blit kernel on the stream in front of the scan: profiles/r05_knn_bar_input.txt), else the arena buffer behind a copy.
   // (GOCTR_KNN_BAR=0: the staged copy, for A/B runs and the tests' comparison)
   const bool want_bar = e.large_bar && s->bar_state >= 0 && env_int_set("GOCTR_KNN_BAR", 1) != 0;
-  if (want_bar && s->in_bar_bytes < in_bytes) {
-    if (s->in_bar) s->retired_dev.push_back(s->in_bar);
-    s->in_bar = nullptr; s->in_bar_bytes = 0;
-    s->in_bar = static_cast<unsigned char*>(bar_alloc(in_bytes * 2));
-    if (!s->in_bar) s->bar_state = -1;                 // not on this system: the staged copy from now on
-    else { s->in_bar_bytes = in_bytes * 2; s->bar_state = 1; }
-  }
-  const bool bar = want_bar && s->in_bar != nullptr;
+  if (want_bar && s->in_bar.bytes < in_bytes)
+    s->bar_state = s->in_bar.grow(in_bytes * 2) ? -1 : 1;     // (-1: not on this system: the staged copy from now on)
+  const bool bar = want_bar && s->in_bar.p != nullptr;
   if ((!bar && s->in_pack.ensure(in_bytes, false)) || s->tmax.ensure((size_t)Q * nt, false) || s->bmax.ensure((size_t)nt * 32 * qpad, false)) return -1;
-  unsigned char* const d_in = bar ? s->in_bar : s->in_pack.p;
-  memcpy(s->h_in, queries, in_q);
-  long long* h_ig = reinterpret_cast<long long*>(static_cast<char*>(s->h_in) + in_q);
+  unsigned char* const d_in = bar ? reinterpret_cast<unsigned char*>(s->in_bar.p) : s->in_pack.p;
+  memcpy(s->h_in.p, queries, in_q);
+  long long* h_ig = reinterpret_cast<long long*>(s->h_in.p + in_q);
   for (int i = 0; i < Q; ++i) h_ig[i] = ignore ? (long long)ignore[i] : -1;
-  float* h_q32 = reinterpret_cast<float*>(static_cast<char*>(s->h_in) + in_q + in_ig);
+  float* h_q32 = reinterpret_cast<float*>(s->h_in.p + in_q + in_ig);
   memset(h_q32, 0, in_q32);
   for (int i = 0; i < Q; ++i) {
     double qn = 0;
@@ -980,7 +958,7 @@ static int knn_search_scan(goctr_searcher* s, const double* queries, int Q, int 
       for (int d = 0; d < D; ++d) h_q32[(size_t)i * D + d] = (float)(queries[(size_t)i * D + d] / qn);
   }
   if (bf) {                                          // the normalised queries as two bf16 planes (round to nearest even, like the device's casts)
-    unsigned short* h_qbf = reinterpret_cast<unsigned short*>(static_cast<char*>(s->h_in) + in_q + in_ig + in_q32);
+    unsigned short* h_qbf = reinterpret_cast<unsigned short*>(s->h_in.p + in_q + in_ig + in_q32);
     const size_t plane = (size_t)nqb * KNN2_QB * D;
     auto f2bf = [](float x) -> unsigned short {
       uint32_t u; memcpy(&u, &x, 4);
@@ -1000,20 +978,20 @@ static int knn_search_scan(goctr_searcher* s, const double* queries, int Q, int 
   // Without the BAR input (GOCTR_KNN_BAR=0, or no large BAR) the same polling lost 9 us at 64 queries: the default follows `bar`.
   const bool poll = Q <= env_int_set("GOCTR_KNN_POLL_MAXQ", bar ? 64 : 32);
   if (poll) {                                        // (the previous call returned after its kernels' last stores: nothing else writes here)
-    int* h_pend = reinterpret_cast<int*>(static_cast<char*>(s->h_out) + o_idx + o_sim);
+    int* h_pend = reinterpret_cast<int*>(s->h_out.p + o_idx + o_sim);
     for (int i = 0; i < Q; ++i) __atomic_store_n(h_pend + i, KNN_PENDING, __ATOMIC_RELEASE);
   }
   if (bar) {                                         // (the previous call's kernels have finished: the host waited for them)
-    memcpy(d_in, s->h_in, in_bytes);
+    memcpy(d_in, s->h_in.p, in_bytes);
     __builtin_ia32_sfence();                         // write-combined stores out before the doorbell of the launch below
-  } else GOCTR_HIP(hipMemcpyAsync(d_in, s->h_in, in_bytes, hipMemcpyHostToDevice, e.stream));
+  } else GOCTR_HIP(hipMemcpyAsync(d_in, s->h_in.p, in_bytes, hipMemcpyHostToDevice, e.stream));
   const double* d_q = reinterpret_cast<const double*>(d_in);
   const long long* d_ig = reinterpret_cast<const long long*>(d_in + in_q);
   const float* d_q32 = reinterpret_cast<const float*>(d_in + in_q + in_ig);
   // the filter's error bound |a - sim|: float32 arithmetic (D + 8) 2^-23; bf16-plane arithmetic 2^-14 (knn_scan_bf16_kernel)
   const float E = bf ? 6.103515625e-05f : (float)(D + 8) * 1.1920929e-07f;
   char* d_out = nullptr;                              // the device's view of the pinned output buffer (zero-copy: 10 KB per call)
-  GOCTR_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&d_out), s->h_out, 0));
+  GOCTR_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&d_out), s->h_out.p, 0));
   long long* d_oi = reinterpret_cast<long long*>(d_out);
   double* d_os = reinterpret_cast<double*>(d_out + o_idx);
   int* d_oc = reinterpret_cast<int*>(d_out + o_idx + o_sim);
@@ -1048,22 +1026,15 @@ static int knn_search_scan(goctr_searcher* s, const double* queries, int Q, int 
             "(%llu candidates, %llu sub-blocks)\n", h[1] - h[0], h[2] - h[1], h[3] - h[2], h[4] - h[3], h[5] - h[4], h[6] - h[5], h[7] - h[6],
             h[7] - h[0], h[8], h[9]);
   }
-  const long long* h_oi = static_cast<const long long*>(s->h_out);
-  const double* h_os = reinterpret_cast<const double*>(static_cast<const char*>(s->h_out) + o_idx);
-  const int* h_oc = reinterpret_cast<const int*>(static_cast<const char*>(s->h_out) + o_idx + o_sim);
+  const long long* h_oi = reinterpret_cast<const long long*>(s->h_out.p);
+  const double* h_os = reinterpret_cast<const double*>(s->h_out.p + o_idx);
+  const int* h_oc = reinterpret_cast<const int*>(s->h_out.p + o_idx + o_sim);
   // The collect kernel wrote the pinned host buffer itself (no copy command), each query's count last, behind a system-scope
   // release: the host watches the counts turn from the sentinel instead of waiting for the stream's completion signal.  A call
   // that has not finished after 2 ms (a long queue ahead of it, or a fault) falls back to the stream wait, which reports errors.
-  bool polled = false;
-  if (poll) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (int done = 0, spins = 0; !polled;) {
-      while (done < Q && __atomic_load_n(h_oc + done, __ATOMIC_ACQUIRE) != KNN_PENDING) ++done;
-      if (done == Q) { polled = true; break; }
-      if ((++spins & 255) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-      __builtin_ia32_pause();
-    }
-  }
+  const bool polled = poll && poll_ready((size_t)Q, std::chrono::milliseconds(2), [&](size_t i) {
+    return __atomic_load_n(h_oc + i, __ATOMIC_ACQUIRE) != KNN_PENDING;
+  });
   if (!polled) GOCTR_HIP(hipStreamSynchronize(e.stream));
   for (int i = 0; i < Q; ++i) if (h_oc[i] < 0) return 1;
   for (size_t i = 0; i < (size_t)Q * k; ++i) { out_idx[i] = h_oi[i]; out_sim[i] = h_os[i]; }
@@ -1097,6 +1068,40 @@ static int searcher_derive(goctr_searcher* s) {
   hipLaunchKernelGGL(knn_norm_kernel, dim3((unsigned)cdiv(V, 256)), dim3(256), 0, engine().stream, s->items.p, (long long)V, D,
                      s->norms.p, s->items32.p, s->items_bf.p, (long long)(s->items_bf.n / 2));
   GOCTR_CHECK(hipGetLastError() == hipSuccess, "knn_norm_kernel launch failed");
+  return 0;
+}
+
+// one device pass of Q <= KNN_PASS_MAXQ queries: the scan path, or (not usable / it handed a query back) the exact tile kernels
+static int searcher_search_pass(goctr_searcher* s, const double* queries, int Q, int k, const int64_t* ignore, int64_t* out_idx,
+                                double* out_sim, int* out_count) {
+  Engine& e = engine();
+  if (knn_scan_usable(s, k)) {
+    const int rc = knn_search_scan(s, queries, Q, k, ignore, out_idx, out_sim, out_count);
+    if (rc <= 0) return rc;                  // (1: a query had more candidates than the replay takes -- the tile kernels below)
+  }
+  const int ntiles = (int)cdiv(s->V, KNN_TILE);
+  if (s->q.ensure((size_t)Q * s->D, false) || s->q.upload(queries, (size_t)Q * s->D)) return -1;
+  if (s->ignore.ensure((size_t)Q, false)) return -1;
+  {
+    std::vector<long long> ig(Q, -1);
+    if (ignore) for (int i = 0; i < Q; ++i) ig[i] = ignore[i];
+    if (s->ignore.upload(ig.data(), Q)) return -1;
+  }
+  if (s->cand_sim.ensure((size_t)Q * ntiles * k, false) || s->cand_idx.ensure((size_t)Q * ntiles * k, false) ||
+      s->cand_cut.ensure((size_t)Q * ntiles, false)) return -1;
+  if (s->out_sim.ensure((size_t)Q * k, false) || s->out_idx.ensure((size_t)Q * k, false) || s->out_cnt.ensure(Q, false)) return -1;
+  const size_t lds = sizeof(double) * ((size_t)s->D + KNN_TILE);
+  hipLaunchKernelGGL(knn_tile_kernel, dim3(ntiles, Q), dim3(256), lds, e.stream, s->items.p, s->norms.p, (long long)s->V, s->D,
+                     s->q.p, s->ignore.p, k, ntiles, s->cand_sim.p, s->cand_idx.p, s->cand_cut.p);
+  GOCTR_HIP(hipGetLastError());
+  const size_t lds_m = sizeof(double) * ((size_t)s->D + KNN_TILE + 4 * (size_t)k);
+  hipLaunchKernelGGL(knn_merge_kernel, dim3(Q), dim3(256), lds_m, e.stream, s->items.p, s->norms.p, (long long)s->V, s->D, s->q.p,
+                     s->ignore.p, s->cand_sim.p, s->cand_idx.p, s->cand_cut.p, ntiles, k, s->out_idx.p, s->out_sim.p, s->out_cnt.p);
+  GOCTR_HIP(hipGetLastError());
+  std::vector<long long> oi((size_t)Q * k);
+  if (s->out_idx.download(oi.data(), oi.size()) || s->out_sim.download(out_sim, (size_t)Q * k) || s->out_cnt.download(out_count, Q))
+    return -1;
+  for (size_t i = 0; i < oi.size(); ++i) out_idx[i] = oi[i];
   return 0;
 }
 
@@ -1142,8 +1147,6 @@ void goctr_searcher_destroy(goctr_searcher* s) { delete s; }
 // lists Q x tiles x k) -- V = 16 M with 4096 queries in one pass would need 8 GB that is never shrunk; a call with more
 // queries is served in passes of this many (the queries are independent: same answers)
 constexpr int KNN_PASS_MAXQ = 1024;
-static int searcher_search_pass(goctr_searcher* s, const double* queries, int Q, int k, const int64_t* ignore, int64_t* out_idx,
-                                double* out_sim, int* out_count);
 
 int goctr_searcher_search(goctr_searcher* s, const double* queries, int Q, int k, const int64_t* ignore, int64_t* out_idx,
                           double* out_sim, int* out_count) {
@@ -1156,39 +1159,6 @@ int goctr_searcher_search(goctr_searcher* s, const double* queries, int Q, int k
     if (searcher_search_pass(s, queries + (size_t)q0 * s->D, n, k, ignore ? ignore + q0 : nullptr, out_idx + (size_t)q0 * k,
                              out_sim + (size_t)q0 * k, out_count + q0)) return -1;
   }
-  return 0;
-}
-
-static int searcher_search_pass(goctr_searcher* s, const double* queries, int Q, int k, const int64_t* ignore, int64_t* out_idx,
-                                double* out_sim, int* out_count) {
-  Engine& e = engine();
-  if (knn_scan_usable(s, k)) {
-    const int rc = knn_search_scan(s, queries, Q, k, ignore, out_idx, out_sim, out_count);
-    if (rc <= 0) return rc;                  // (1: a query had more candidates than the replay takes -- the tile kernels below)
-  }
-  const int ntiles = (int)cdiv(s->V, KNN_TILE);
-  if (s->q.ensure((size_t)Q * s->D, false) || s->q.upload(queries, (size_t)Q * s->D)) return -1;
-  if (s->ignore.ensure((size_t)Q, false)) return -1;
-  {
-    std::vector<long long> ig(Q, -1);
-    if (ignore) for (int i = 0; i < Q; ++i) ig[i] = ignore[i];
-    if (s->ignore.upload(ig.data(), Q)) return -1;
-  }
-  if (s->cand_sim.ensure((size_t)Q * ntiles * k, false) || s->cand_idx.ensure((size_t)Q * ntiles * k, false) ||
-      s->cand_cut.ensure((size_t)Q * ntiles, false)) return -1;
-  if (s->out_sim.ensure((size_t)Q * k, false) || s->out_idx.ensure((size_t)Q * k, false) || s->out_cnt.ensure(Q, false)) return -1;
-  const size_t lds = sizeof(double) * ((size_t)s->D + KNN_TILE);
-  hipLaunchKernelGGL(knn_tile_kernel, dim3(ntiles, Q), dim3(256), lds, e.stream, s->items.p, s->norms.p, (long long)s->V, s->D,
-                     s->q.p, s->ignore.p, k, ntiles, s->cand_sim.p, s->cand_idx.p, s->cand_cut.p);
-  GOCTR_HIP(hipGetLastError());
-  const size_t lds_m = sizeof(double) * ((size_t)s->D + KNN_TILE + 4 * (size_t)k);
-  hipLaunchKernelGGL(knn_merge_kernel, dim3(Q), dim3(256), lds_m, e.stream, s->items.p, s->norms.p, (long long)s->V, s->D, s->q.p,
-                     s->ignore.p, s->cand_sim.p, s->cand_idx.p, s->cand_cut.p, ntiles, k, s->out_idx.p, s->out_sim.p, s->out_cnt.p);
-  GOCTR_HIP(hipGetLastError());
-  std::vector<long long> oi((size_t)Q * k);
-  if (s->out_idx.download(oi.data(), oi.size()) || s->out_sim.download(out_sim, (size_t)Q * k) || s->out_cnt.download(out_count, Q))
-    return -1;
-  for (size_t i = 0; i < oi.size(); ++i) out_idx[i] = oi[i];
   return 0;
 }
 

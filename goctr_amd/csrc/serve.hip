@@ -1,6 +1,6 @@
-// serve.hip -- the behaviour cache and key datasets (goctr_ubcache_*, goctr_dataset_create_keys / _create_samples) and serving
-// (goctr_recsys_*, goctr_batch_predict, goctr_rank, goctr_recommend_topn's entry, goctr_predict_dense) over the forward launches
-// of the step (ctr.hip).
+// serve.hip -- serving (goctr_recsys_*, goctr_batch_predict, goctr_rank, goctr_predict_dense, and the entries of goctr_recommend_topn
+// and goctr_recommend_itemcf, whose drivers are topn.hip and itemcf.hip) over the forward launches of the step (ctr.hip): the recsys
+// handle, the serving slots and their pool, the passes, the micro-batcher.  The behaviour cache the passes read: ubcache.hip.
 #define GOCTR_NO_PLAIN_KERNELS      // the kernel headers' plain kernels belong to ctr.hip
 #include <algorithm>
 #include <atomic>
@@ -11,214 +11,10 @@
 #include <shared_mutex>
 
 #include "ctr_model.h"
-#include "negsample.h"
 #include "itemcf.h"
+#include "staging.h"
 #include "topn.h"
 #include "ubcache.h"
-
-// ------------------------------------------------------------------ device-side sample assembly
-// ubcache.UserBehaviorCache (feature/ubcache/cache.go) as a CSR in HBM + the per-sample gather of GetSampleVector
-// (recommend/rcmd.go:460-536) as one kernel: keys (user, item, timestamp) -> behaviour ids, user / item feature rows.
-// (the handle: ubcache.h; its updates -- BatchSet / Delete / Clear / Append -- live in ubcache.hip)
-
-namespace {
-// TimeSeq.Filter (cache.go:71-94) for one key: the sequence is newest-first, so "the first i with Ts[i] <= maxTs"
-// is a lower bound found by bisection; then up to T items from there.
-__global__ __launch_bounds__(256) void assemble_keys_kernel(const long long* __restrict__ off, const int32_t* __restrict__ seq_items,
-                                                            const long long* __restrict__ seq_ts, long long n_users,
-                                                            const float* __restrict__ user_table, int U,
-                                                            const float* __restrict__ item_table, long long n_items, int C,
-                                                            const int32_t* __restrict__ users, const int32_t* __restrict__ items,
-                                                            const long long* __restrict__ ts, long long rows, int T,
-                                                            int32_t* __restrict__ ub_ids, float* __restrict__ ufeat,
-                                                            float* __restrict__ cfeat, int32_t* __restrict__ item_out,
-                                                            unsigned char* __restrict__ failed) {
-  const int lane = threadIdx.x & 63;
-  const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);   // one wavefront per sample
-  if (r >= rows) return;
-  // the key's three fields first, back to back: in a small serving pass they sit in pinned HOST memory (zero-copy), and
-  // fetched one by one where they are used they were three PCIe round trips in a row (7.8 us for a 256-key pass)
-  const int u = users[r];
-  const int it_key = items ? items[r] : -1;
-  const long long ts_key = ts ? ts[r] : 0;
-  bool uok = u >= 0 && u < n_users;
-  if (failed) {
-    // BatchPredict (rcmd.go:291-307): a key whose GetUserFeature / GetItemFeature fails is scored as the ALL-zero row
-    // (user features, behaviours, item embedding and item features alike)
-    const int it = it_key;
-    const bool ok = uok && it >= 0 && it < n_items;
-    if (lane == 0) { failed[r] = ok ? 0 : 1; item_out[r] = ok ? it : -1; }
-    if (!ok) {
-      for (int j = lane; j < T; j += 64) ub_ids[r * T + j] = -1;
-      for (int j = lane; j < U; j += 64) ufeat[r * U + j] = 0.f;
-      for (int j = lane; j < C; j += 64) cfeat[r * C + j] = 0.f;
-      return;
-    }
-  }
-  long long first = 0, cnt = 0;
-  const long long b = (uok && off) ? off[u] : 0, len = (uok && off) ? off[u + 1] - b : 0;   // off == NULL: no behaviour cache
-  if (len > 0) {
-    const long long mts = ts_key;
-    // first i with seq_ts[b + i] <= mts (descending order); mts == 0 means "from the newest" (cache.go:72-74: maxTs = Ts[0])
-    long long lo = 0;
-    if (mts != 0) {
-      if (len <= 256) {
-        // short histories (the common case): 64 entries per coalesced load and one ballot instead of a chain of ~7 dependent
-        // loads -- the serving pass of a Rank call is latency, not work
-        lo = len;
-        for (long long base = 0; base < len; base += 64) {
-          const long long i = base + lane;
-          const unsigned long long le = __ballot(i < len && seq_ts[b + i] <= mts);
-          if (le) { lo = base + (long long)__builtin_ctzll(le); break; }
-        }
-      } else {
-        long long hi = len;
-        while (lo < hi) {
-          const long long mid = (lo + hi) >> 1;
-          if (seq_ts[b + mid] <= mts) hi = mid; else lo = mid + 1;
-        }
-      }
-    }
-    first = lo;
-    cnt = len - first < T ? len - first : T;
-  }
-  if (ub_ids)
-    for (int j = lane; j < T; j += 64) ub_ids[r * T + j] = j < cnt ? seq_items[b + first + j] : -1;
-  if (ufeat)
-    for (int j = lane; j < U; j += 64) ufeat[r * U + j] = uok ? user_table[(long long)u * U + j] : 0.f;
-  if (cfeat) {
-    const int it = it_key;
-    const bool iok = it >= 0 && it < n_items;
-    for (int j = lane; j < C; j += 64) cfeat[r * C + j] = iok ? item_table[(long long)it * C + j] : 0.f;
-  }
-}
-
-// The body goctr_dataset_create_keys and goctr_dataset_create_samples share: the keys are on the device (d->users,
-// d->item_ids, key_ts), the feature tables come from the host; one assembly launch over one image of the cache.
-int assemble_key_dataset(goctr_ubcache* c, const float* user_table, int64_t n_users, int U, const float* item_table,
-                         int64_t n_items, int C, goctr_dataset* d, const long long* key_ts, int64_t rows, int T) {
-  d->id_mode = true; d->rows = rows; d->U = U; d->C = C; d->T = T;
-  DevBuf<float> dut, dit;
-  if (dut.alloc((size_t)n_users * U, false) || (U && dut.upload(user_table, (size_t)n_users * U))) return -1;
-  if (dit.alloc((size_t)n_items * C, false) || (C && dit.upload(item_table, (size_t)n_items * C))) return -1;
-  if (d->ub_ids.alloc((size_t)rows * T, false)) return -1;
-  if (d->ufeat.alloc((size_t)rows * U, false) || d->cfeat.alloc((size_t)rows * C, false)) return -1;
-  UbRead image(c, engine().stream);
-  hipLaunchKernelGGL(assemble_keys_kernel, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, engine().stream, c->off.p, c->items.p,
-                     c->ts.p, (long long)c->n_users, dut.p, U, dit.p, (long long)n_items, C, d->users.p, d->item_ids.p, key_ts,
-                     (long long)rows, T, d->ub_ids.p, d->ufeat.p, d->cfeat.p, (int32_t*)nullptr, (unsigned char*)nullptr);
-  GOCTR_HIP(hipGetLastError());
-  GOCTR_HIP(hipStreamSynchronize(engine().stream));   // the temporaries above are released on return
-  image.done();
-  return 0;
-}
-}  // namespace
-
-extern "C" {
-
-int goctr_ubcache_create(int64_t n_users, const int64_t* off, const int32_t* items, const int64_t* ts, goctr_ubcache** out) {
-  GOCTR_ENTER();
-  GOCTR_CHECK(n_users > 0 && off && out && off[0] == 0, "goctr_ubcache_create: bad arguments");
-  const int64_t nnz = off[n_users];
-  GOCTR_CHECK(nnz >= 0 && (nnz == 0 || (items && ts)), "goctr_ubcache_create: sequences missing");
-  for (int64_t u = 0; u < n_users; ++u) {
-    GOCTR_CHECK(off[u + 1] >= off[u], "goctr_ubcache_create: offsets must be non-decreasing");
-    for (int64_t k = off[u] + 1; k < off[u + 1]; ++k)
-      GOCTR_CHECK(ts[k] <= ts[k - 1], "goctr_ubcache_create: user %lld's sequence is not in timestamp-descending order "
-                  "(cache.go:8 TimeSeq)", (long long)u);
-  }
-  std::unique_ptr<goctr_ubcache> c(new goctr_ubcache);
-  c->n_users = n_users; c->nnz = nnz;
-  std::vector<long long> o(off, off + n_users + 1), t(ts, ts + nnz);
-  if (c->off.alloc(o.size(), false) || c->off.upload(o.data(), o.size())) return -1;
-  if (c->items.alloc((size_t)nnz, false) || (nnz && c->items.upload(items, (size_t)nnz))) return -1;
-  if (c->ts.alloc((size_t)nnz, false) || (nnz && c->ts.upload(t.data(), (size_t)nnz))) return -1;
-  GOCTR_HIP(hipStreamCreateWithFlags(&c->ustream, hipStreamNonBlocking));
-  *out = c.release();
-  return 0;
-}
-void goctr_ubcache_destroy(goctr_ubcache* c) {
-  if (!c) return;
-  EngineScope on(c->eng);
-  delete c;
-}
-
-int goctr_ubcache_get(goctr_ubcache* c, const int32_t* users, const int64_t* max_ts, int64_t rows, int T, int32_t* out_ids) {
-  GOCTR_ENTER_H(c);
-  GOCTR_CHECK(c && users && out_ids && rows > 0 && T > 0, "goctr_ubcache_get: bad arguments");
-  DevBuf<int32_t> du, dout; DevBuf<long long> dts;
-  std::vector<long long> t(rows, 0);
-  if (max_ts) for (int64_t i = 0; i < rows; ++i) t[i] = max_ts[i];
-  if (du.alloc(rows, false) || du.upload(users, rows) || dts.alloc(rows, false) || dts.upload(t.data(), rows) ||
-      dout.alloc((size_t)rows * T, false)) return -1;
-  UbRead image(c, engine().stream);                   // until the download's synchronisation
-  hipLaunchKernelGGL(assemble_keys_kernel, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, engine().stream, c->off.p, c->items.p,
-                     c->ts.p, (long long)c->n_users, (const float*)nullptr, 0, (const float*)nullptr, 0LL, 0, du.p,
-                     (const int32_t*)nullptr, dts.p, (long long)rows, T, dout.p, (float*)nullptr, (float*)nullptr,
-                     (int32_t*)nullptr, (unsigned char*)nullptr);
-  GOCTR_HIP(hipGetLastError());
-  if (dout.download(out_ids, (size_t)rows * T)) return -1;
-  image.done();
-  return 0;
-}
-
-int goctr_dataset_create_keys(goctr_ubcache* c, const float* user_table, int64_t n_users, int U, const float* item_table,
-                              int64_t n_items, int C, const int32_t* users, const int32_t* items, const int64_t* ts,
-                              const float* Y, int64_t rows, int T, goctr_dataset** out) {
-  GOCTR_ENTER_H(c);
-  GOCTR_CHECK(c && users && items && rows > 0 && T > 0 && out && n_items >= 0 && U >= 0 && C >= 0,
-              "goctr_dataset_create_keys: bad arguments");
-  GOCTR_CHECK(n_users == c->n_users, "goctr_dataset_create_keys: user table has %lld rows, the behaviour cache %lld users",
-              (long long)n_users, (long long)c->n_users);
-  GOCTR_CHECK((U == 0 || user_table) && (C == 0 || item_table), "goctr_dataset_create_keys: feature table missing");
-  std::unique_ptr<goctr_dataset> d(new goctr_dataset);
-  DevBuf<long long> dts;
-  std::vector<long long> t(rows, 0);
-  if (ts) for (int64_t i = 0; i < rows; ++i) t[i] = ts[i];
-  // (d->users stays resident: the rows' groups for goctr_evaluate_dataset_grouped)
-  if (d->users.alloc(rows, false) || d->users.upload(users, rows) || dts.alloc(rows, false) || dts.upload(t.data(), rows) ||
-      d->item_ids.alloc(rows, false) || d->item_ids.upload(items, rows)) return -1;
-  if (assemble_key_dataset(c, user_table, n_users, U, item_table, n_items, C, d.get(), dts.p, rows, T)) return -1;
-  if (Y) { if (d->Y.alloc(rows, false) || d->Y.upload(Y, rows)) return -1; d->has_y = true; }
-  *out = d.release();
-  return 0;
-}
-
-// the same dataset from key columns that are already in HBM (goctr_samples_create): three device-to-device copies instead of
-// the key uploads; only the feature tables come from the host
-int goctr_dataset_create_samples(goctr_ubcache* c, const float* user_table, int64_t n_users, int U, const float* item_table,
-                                 int64_t n_items, int C, goctr_samples* s, int T, goctr_dataset** out) {
-  GOCTR_ENTER_H(c);
-  GOCTR_CHECK(c && s && T > 0 && out && n_items >= 0 && U >= 0 && C >= 0, "goctr_dataset_create_samples: bad arguments");
-  GOCTR_SAME_ENGINE(c, s);
-  GOCTR_CHECK(s->rows > 0, "goctr_dataset_create_samples: the samples hold no row");
-  GOCTR_CHECK(n_users == c->n_users, "goctr_dataset_create_samples: user table has %lld rows, the behaviour cache %lld users",
-              (long long)n_users, (long long)c->n_users);
-  GOCTR_CHECK((U == 0 || user_table) && (C == 0 || item_table), "goctr_dataset_create_samples: feature table missing");
-  const int64_t rows = s->rows;
-  std::unique_ptr<goctr_dataset> d(new goctr_dataset);
-  if (d->users.alloc(rows, false) || d->item_ids.alloc(rows, false) || d->Y.alloc(rows, false)) return -1;
-  hipStream_t st = engine().stream;
-  GOCTR_HIP(hipMemcpyAsync(d->users.p, s->users.p, sizeof(int32_t) * (size_t)rows, hipMemcpyDeviceToDevice, st));
-  GOCTR_HIP(hipMemcpyAsync(d->item_ids.p, s->items.p, sizeof(int32_t) * (size_t)rows, hipMemcpyDeviceToDevice, st));
-  GOCTR_HIP(hipMemcpyAsync(d->Y.p, s->y.p, sizeof(float) * (size_t)rows, hipMemcpyDeviceToDevice, st));
-  d->has_y = true;
-  if (assemble_key_dataset(c, user_table, n_users, U, item_table, n_items, C, d.get(), s->ts.p, rows, T)) return -1;
-  *out = d.release();
-  return 0;
-}
-
-// read back the assembled keys of an id-mode dataset (tests, debugging)
-int goctr_dataset_get_ids(goctr_dataset* d, int32_t* ub_ids, float* user_feat, float* ctx_feat) {
-  GOCTR_ENTER_H(d);
-  GOCTR_CHECK(d && d->id_mode, "goctr_dataset_get_ids: not an id-mode dataset");
-  if (ub_ids && d->ub_ids.download(ub_ids, (size_t)d->rows * d->T)) return -1;
-  if (user_feat && d->U && d->ufeat.download(user_feat, (size_t)d->rows * d->U)) return -1;
-  if (ctx_feat && d->C && d->cfeat.download(ctx_feat, (size_t)d->rows * d->C)) return -1;
-  return 0;
-}
-
-}  // extern "C"
 
 // ------------------------------------------------------------------ serving: recommend.BatchPredict / Rank / Predict
 // recommend/rcmd.go:248-337: sample keys -> GetSampleVector rows -> PredictAbstract.Predict -> scores, called from concurrent
@@ -270,25 +66,17 @@ struct ServeSlot {
   hipStream_t stream = nullptr;
   int64_t cap = 0; int T = 0, U = 0, C = 0;
   // pinned staging: in = [ts i64 x N | users i32 x N | items i32 x N], out = [scores f32 x Br | failed u8 x N]
-  char* h_in = nullptr; char* h_out = nullptr;
+  PinnedBuf h_in, h_out;
   unsigned* h_done = nullptr; unsigned epoch = 0;   // behind the failed flags in h_out: one word per 16-row workgroup (serve_keys_pass)
   // the keys of a zero-copy pass in fine-grained DEVICE memory that the host stores into over the PCIe BAR (large-BAR systems): the
   // kernel's first loads are local instead of a PCIe read round trip.  Null: the kernels read the pinned h_in.
-  char* in_bar = nullptr; std::vector<void*> retired_dev;
-  std::vector<void*> retired;      // outgrown pinned buffers (see ensure_keys)
+  BarBuf in_bar;
   DevBuf<char> d_in, d_out;
   DevBuf<int32_t> ub_ids, item_ids; DevBuf<float> ufeat, cfeat;
   FwdWs ws;
   DevBuf<StepState> st;            // one all-zero state: "batch 0 of 1"
   DevBuf<float> X; size_t capX = 0;   // dense rows (goctr_predict_dense)
-  ~ServeSlot() {
-    for (void* p : retired_dev) (void)hipFree(p);
-    if (in_bar) (void)hipFree(in_bar);
-    for (void* p : retired) (void)hipHostFree(p);
-    if (h_in) (void)hipHostFree(h_in);
-    if (h_out) (void)hipHostFree(h_out);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
+  ~ServeSlot() { if (stream) (void)hipStreamDestroy(stream); }
   int init() {
     GOCTR_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     if (st.alloc(1, false)) return -1;
@@ -304,16 +92,12 @@ struct ServeSlot {
     const int64_t want = std::max<int64_t>(std::max<int64_t>(n, 256), std::min<int64_t>(2 * cap, SERVE_PASS_ROWS));
     const size_t Br = (size_t)round_up((int)want, 32);
     cap = 0;                                   // (a failure below must not leave the old capacity next to missing buffers)
-    // (outgrown pinned buffers are kept until the slot goes: hipHostFree waits for the whole device, which would invalidate the
-    // stream capture of a thread that is building step graphs meanwhile -- a handful of geometric growths per slot at most)
-    if (h_in) { retired.push_back(h_in); h_in = nullptr; }
-    if (h_out) { retired.push_back(h_out); h_out = nullptr; }
-    GOCTR_HIP(hipHostMalloc((void**)&h_in, (size_t)want * 16, hipHostMallocDefault));
-    if (in_bar) { retired_dev.push_back(in_bar); in_bar = nullptr; }
-    if (env_int("GOCTR_SERVE_BAR", 1) != 0) in_bar = static_cast<char*>(bar_alloc((size_t)want * 16));   // (null: the pinned buffer serves)
+    // (the outgrown staging buffers stay until the slot goes, staging.h: a handful of geometric growths per slot at most)
     const size_t done_off = (Br * 4 + (size_t)want + 63) / 64 * 64, done_n = (size_t)want / 16 + 1;
-    GOCTR_HIP(hipHostMalloc((void**)&h_out, done_off + 4 * done_n, hipHostMallocDefault));
-    h_done = reinterpret_cast<unsigned*>(h_out + done_off);
+    if (h_in.grow((size_t)want * 16) || h_out.grow(done_off + 4 * done_n)) return -1;
+    in_bar.retire();
+    if (env_int("GOCTR_SERVE_BAR", 1) != 0) (void)in_bar.grow((size_t)want * 16);   // (refused: the pinned buffer serves; asked again at the next growth)
+    h_done = reinterpret_cast<unsigned*>(h_out.p + done_off);
     memset(h_done, 0, 4 * done_n); epoch = 0;
     if (d_in.alloc((size_t)want * 16, false) || d_out.alloc(Br * 4 + (size_t)want, false) ||
         ub_ids.alloc((size_t)want * Tn, false) || item_ids.alloc((size_t)want, false) ||
@@ -413,10 +197,11 @@ int serve_wait_rows(goctr_emb* e) {
 
 // Score N keys at these pointers: the key columns dts / dus / dit (device memory, or host memory the device reads: the zero-copy
 // and BAR branches of serve_keys_pass) -> dscore [N] and the failed flags dfail [N], all launches on the slot's stream, nothing
-// waited for.  serve_keys_pass stages a request's keys and calls this; goctr_recommend_topn (topn.hip) calls it on keys its own
-// kernel wrote.  Caller: holds m->mu and the table's lock shared and ONE image of the cache (UbRead) until it has synchronised,
-// owns the slot, has called ensure_keys / ws.ensure for N rows and waited for pending weight / row writes.  host_visible: dscore
-// is pinned host memory, so a one-launch pass may stamp its workgroups' completion there (*n_stamps of them; 0: wait on the stream).
+// waited for.  serve_keys_pass stages a request's keys and calls this; the drivers of goctr_recommend_topn (topn.hip) and
+// goctr_recommend_itemcf (itemcf.hip) call it, through with_scorer's TopnScorer, on keys their own kernels wrote.  Caller: holds
+// m->mu and the table's lock shared and ONE image of the cache (UbRead) until it has synchronised, owns the slot, has called
+// ensure_keys / ws.ensure for N rows and waited for pending weight / row writes.  host_visible: dscore is pinned host memory, so
+// a one-launch pass may stamp its workgroups' completion there (*n_stamps of them; 0: wait on the stream).
 int serve_score_keys(goctr_model* m, goctr_recsys* r, ServeSlot* s, const long long* dts, const int32_t* dus, const int32_t* dit,
                      int64_t N, float* dscore, unsigned char* dfail, bool host_visible, unsigned* n_stamps) {
   const int T = m->cfg.T;
@@ -434,12 +219,9 @@ int serve_score_keys(goctr_model* m, goctr_recsys* r, ServeSlot* s, const long l
     src.ub_off = c ? c->off.p : nullptr; src.ub_items = c ? c->items.p : nullptr; src.ub_ts = c ? c->ts.p : nullptr;
     src.user_table = r->user_table.p; src.item_table = r->item_table.p; src.n_users = r->n_users; src.n_items = r->n_items;
   } else {
-    hipLaunchKernelGGL(assemble_keys_kernel, dim3((unsigned)cdiv(N, 4)), dim3(256), 0, s->stream,
-                       c ? c->off.p : (const long long*)nullptr, c ? c->items.p : (const int32_t*)nullptr,
-                       c ? c->ts.p : (const long long*)nullptr, (long long)r->n_users, r->user_table.p, r->U, r->item_table.p,
-                       (long long)r->n_items, r->C, dus, dit, dts, (long long)N, T, s->ub_ids.p, s->ufeat.p, s->cfeat.p,
-                       s->item_ids.p, dfail);
-    GOCTR_HIP(hipGetLastError());
+    if (launch_assemble_keys(s->stream, c ? c->off.p : nullptr, c ? c->items.p : nullptr, c ? c->ts.p : nullptr, r->n_users,
+                             r->user_table.p, r->U, r->item_table.p, r->n_items, r->C, dus, dit, dts, N, T, s->ub_ids.p, s->ufeat.p,
+                             s->cfeat.p, s->item_ids.p, dfail)) return -1;
     src.ub_ids = s->ub_ids.p; src.item_ids = s->item_ids.p; src.ufeat = s->ufeat.p; src.cfeat = s->cfeat.p;
   }
   FwdBufs fb = s->ws.bufs();
@@ -478,8 +260,8 @@ int serve_keys_pass(goctr_model* m, goctr_recsys* r, ServeSlot* s, KeySeg* const
   // host buffer; the scores and flags (5 B per row) are written to pinned host memory from inside the kernels.  Larger passes keep
   // the two DMA copies.
   const bool zc = N <= 4096;
-  const bool bar = zc && s->in_bar != nullptr && env_int("GOCTR_SERVE_BAR", 1) != 0;
-  char* const key_dst = bar ? s->in_bar : s->h_in;      // (written only, front to back: fine for a write-combined mapping)
+  const bool bar = zc && s->in_bar.p != nullptr && env_int("GOCTR_SERVE_BAR", 1) != 0;
+  char* const key_dst = bar ? s->in_bar.p : s->h_in.p;      // (written only, front to back: fine for a write-combined mapping)
   long long* hts = reinterpret_cast<long long*>(key_dst);
   int32_t* hus = reinterpret_cast<int32_t*>(key_dst + 8 * N);
   int32_t* hit = reinterpret_cast<int32_t*>(key_dst + 12 * N);
@@ -494,10 +276,10 @@ int serve_keys_pass(goctr_model* m, goctr_recsys* r, ServeSlot* s, KeySeg* const
     o += g.n;
   }
   if (bar) __builtin_ia32_sfence();                   // the key stores are out before the launch's doorbell
-  if (!zc) GOCTR_HIP(hipMemcpyAsync(s->d_in.p, s->h_in, (size_t)N * 16, hipMemcpyHostToDevice, s->stream));
+  if (!zc) GOCTR_HIP(hipMemcpyAsync(s->d_in.p, s->h_in.p, (size_t)N * 16, hipMemcpyHostToDevice, s->stream));
   if (serve_wait_weights(m, s) || serve_wait_rows(r->emb)) return -1;
-  const char* in_base = bar ? s->in_bar : (zc ? s->h_in : s->d_in.p);
-  char* out_base = zc ? s->h_out : s->d_out.p;
+  const char* in_base = bar ? s->in_bar.p : (zc ? s->h_in.p : s->d_in.p);
+  char* out_base = zc ? s->h_out.p : s->d_out.p;
   const long long* dts = reinterpret_cast<const long long*>(in_base);
   const int32_t* dus = reinterpret_cast<const int32_t*>(in_base + 8 * N);
   const int32_t* dit = reinterpret_cast<const int32_t*>(in_base + 12 * N);
@@ -510,21 +292,15 @@ int serve_keys_pass(goctr_model* m, goctr_recsys* r, ServeSlot* s, KeySeg* const
   for (int k = 0; k < nseg; ++k) want_failed = want_failed || segs[k]->failed || segs[k]->n_failed >= 0;
   // scores and flags are adjacent: one copy back (the gap between them is < 128 bytes)
   const size_t out_bytes = want_failed ? 4 * Br + (size_t)N : 4 * (size_t)N;
-  if (!zc) GOCTR_HIP(hipMemcpyAsync(s->h_out, s->d_out.p, out_bytes, hipMemcpyDeviceToHost, s->stream));
-  bool stamped = false;
-  if (n_stamps) {                                    // (2 ms without the stamps: the stream wait, which also reports a fault)
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned done = 0, spins = 0;;) {
-      while (done < n_stamps && __atomic_load_n(s->h_done + done, __ATOMIC_ACQUIRE) == s->epoch) ++done;
-      if (done == n_stamps) { stamped = true; break; }
-      if ((++spins & 255) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-      __builtin_ia32_pause();
-    }
-  }
+  if (!zc) GOCTR_HIP(hipMemcpyAsync(s->h_out.p, s->d_out.p, out_bytes, hipMemcpyDeviceToHost, s->stream));
+  // (2 ms without the stamps: the stream wait, which also reports a fault)
+  const bool stamped = n_stamps && poll_ready(n_stamps, std::chrono::milliseconds(2), [&](size_t i) {
+    return __atomic_load_n(s->h_done + i, __ATOMIC_ACQUIRE) == s->epoch;
+  });
   if (!stamped) GOCTR_HIP(hipStreamSynchronize(s->stream));
   image.done();
-  const float* hs = reinterpret_cast<const float*>(s->h_out);
-  const unsigned char* hf = reinterpret_cast<const unsigned char*>(s->h_out + 4 * Br);
+  const float* hs = reinterpret_cast<const float*>(s->h_out.p);
+  const unsigned char* hf = reinterpret_cast<const unsigned char*>(s->h_out.p + 4 * Br);
   o = 0;
   for (int k = 0; k < nseg; ++k) {
     KeySeg& g = *segs[k];
@@ -645,6 +421,46 @@ int serve_keys(goctr_model* m, goctr_recsys* r, KeySeg& g, int64_t* n_failed) {
   return rc;
 }
 
+// the recsys was made for a model of these widths (`who`: the entry's name)
+int check_recsys_dims(const char* who, const goctr_model* m, const goctr_recsys* r) {
+  GOCTR_CHECK(r->emb->D == m->cfg.D && r->U == m->cfg.U && r->C == m->cfg.C, "%s: recsys dims (U=%d,C=%d,D=%d) != model (U=%d,C=%d,D=%d)",
+              who, r->U, r->C, r->emb->D, m->cfg.U, m->cfg.C, m->cfg.D);
+  return 0;
+}
+
+// What the recommend entries (top-N, ItemCF, a further recall source) do around their drivers, which do not see goctr_model: the
+// model's and the table's lock shared, a slot sized for passes of `pass_rows` rows (0: the default) and ONE image of the cache, then
+// run(sc) -- it returns after it has synchronised the slot's stream -- with the slot's buffers and serve_score_keys as a TopnScorer.
+template <class Run>
+int with_scorer(goctr_model* m, goctr_recsys* r, int64_t pass_rows, Run run) {
+  std::shared_lock<std::shared_mutex> lm(m->mu);        // as serve_keys: weights, then embedding rows, stay put
+  std::shared_lock<std::shared_mutex> le(r->emb->mu);
+  SlotLease lease;
+  ServeSlot* const s = lease.s;
+  if (!s) return -1;
+  const int64_t pass = pass_rows ? pass_rows : TOPN_DEFAULT_PASS_ROWS;
+  const int64_t cap_rows = std::max<int64_t>(pass, SERVE_COALESCE_ROWS);
+  if (s->ensure_keys(cap_rows, m->cfg.T, r->U, r->C)) return -1;
+  if (s->ws.ensure((int)cap_rows, m->Ip, m->cfg.T, m->H1p, m->H2p, !chain_ok(m), s->stream)) return -1;
+  if (serve_wait_weights(m, s) || serve_wait_rows(r->emb)) return -1;
+  goctr_ubcache* const c = r->ub;
+  UbRead image(c, s->stream);                           // one image for every pass: held until run has synchronised
+  TopnScorer sc;
+  sc.stream = s->stream; sc.n_users = r->n_users; sc.n_items = r->n_items;
+  sc.ub_off = c ? c->off.p : nullptr; sc.ub_items = c ? c->items.p : nullptr; sc.ub_ts = c ? c->ts.p : nullptr;
+  sc.max_rows = s->cap; sc.keys = s->d_in.p; sc.out = s->d_out.p;
+  sc.score = [&](int64_t N) {
+    const size_t Br = (size_t)round_up((int)N, 32);
+    unsigned n_stamps = 0;
+    return serve_score_keys(m, r, s, reinterpret_cast<const long long*>(sc.keys), reinterpret_cast<const int32_t*>(sc.keys + 8 * N),
+                            reinterpret_cast<const int32_t*>(sc.keys + 12 * N), N, reinterpret_cast<float*>(sc.out),
+                            reinterpret_cast<unsigned char*>(sc.out + 4 * Br), false, &n_stamps);
+  };
+  if (run(sc)) return -1;
+  image.done();
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -680,8 +496,7 @@ int goctr_batch_predict(goctr_model* m, goctr_recsys* r, const int32_t* users, c
   if (require_engine()) return -1;
   GOCTR_CHECK(m && r && users && items && scores && n >= 0 && batch > 0, "goctr_batch_predict: bad arguments");
   GOCTR_SAME_ENGINE(m, r);
-  GOCTR_CHECK(r->emb->D == m->cfg.D && r->U == m->cfg.U && r->C == m->cfg.C, "goctr_batch_predict: recsys dims (U=%d,C=%d,D=%d) != model (U=%d,C=%d,D=%d)",
-              r->U, r->C, r->emb->D, m->cfg.U, m->cfg.C, m->cfg.D);
+  if (check_recsys_dims("goctr_batch_predict", m, r)) return -1;
   if (n_failed) *n_failed = 0;
   if (n == 0) return 0;
   // rcmd.go:293-296: a failing FIRST key aborts the call (there is no row width to build a zero row from yet)
@@ -698,8 +513,7 @@ int goctr_rank(goctr_model* m, goctr_recsys* r, int32_t user, const int32_t* ite
   if (require_engine()) return -1;
   GOCTR_CHECK(m && r && items && scores && n >= 0 && batch > 0, "goctr_rank: bad arguments");
   GOCTR_SAME_ENGINE(m, r);
-  GOCTR_CHECK(r->emb->D == m->cfg.D && r->U == m->cfg.U && r->C == m->cfg.C, "goctr_rank: recsys dims (U=%d,C=%d,D=%d) != model (U=%d,C=%d,D=%d)",
-              r->U, r->C, r->emb->D, m->cfg.U, m->cfg.C, m->cfg.D);
+  if (check_recsys_dims("goctr_rank", m, r)) return -1;
   if (n_failed) *n_failed = 0;
   if (n == 0) return 0;
   GOCTR_CHECK(user >= 0 && user < r->n_users && items[0] >= 0 && items[0] < r->n_items,
@@ -709,8 +523,7 @@ int goctr_rank(goctr_model* m, goctr_recsys* r, int32_t user, const int32_t* ite
 }
 
 // Top-N recommendation (topn.hip has the key generator, the seen test, the selection and the driver): this entry checks the
-// handles, takes what a serving entry takes -- the model's and the table's lock shared, a slot -- and ONE image of the cache for
-// the whole call, and lends the driver the slot's device buffers and serve_score_keys.
+// handles and the arguments -- before any lock or slot is taken -- and runs the driver inside with_scorer.
 int goctr_recommend_topn(goctr_model* m, goctr_recsys* r, const int32_t* users, const int64_t* ts, int64_t n_users_req,
                          const int32_t* pool, int64_t n_pool, const int32_t* targets, const goctr_topn_cfg* cfg,
                          int32_t* out_items, float* out_scores, int32_t* out_count, int64_t* out_target_rank, float* all_scores,
@@ -719,41 +532,15 @@ int goctr_recommend_topn(goctr_model* m, goctr_recsys* r, const int32_t* users, 
   if (require_engine()) return -1;
   GOCTR_CHECK(m && r && cfg, "goctr_recommend_topn: bad arguments");
   GOCTR_SAME_ENGINE(m, r);
-  GOCTR_CHECK(r->emb->D == m->cfg.D && r->U == m->cfg.U && r->C == m->cfg.C, "goctr_recommend_topn: recsys dims (U=%d,C=%d,D=%d) != model (U=%d,C=%d,D=%d)",
-              r->U, r->C, r->emb->D, m->cfg.U, m->cfg.C, m->cfg.D);
+  if (check_recsys_dims("goctr_recommend_topn", m, r)) return -1;
   const TopnArgs a{users, ts, n_users_req, pool, n_pool, targets, *cfg, out_items, out_scores, out_count, out_target_rank,
                    all_scores, all_flags, n_failed};
   if (topn_check_args(a, r->n_users)) return -1;
-  std::shared_lock<std::shared_mutex> lm(m->mu);        // as serve_keys: weights, then embedding rows, stay put
-  std::shared_lock<std::shared_mutex> le(r->emb->mu);
-  SlotLease lease;
-  ServeSlot* s = lease.s;
-  if (!s) return -1;
-  const int64_t pass = cfg->pass_rows ? cfg->pass_rows : TOPN_DEFAULT_PASS_ROWS;
-  const int64_t cap_rows = std::max<int64_t>(pass, SERVE_COALESCE_ROWS);
-  if (s->ensure_keys(cap_rows, m->cfg.T, r->U, r->C)) return -1;
-  if (s->ws.ensure((int)cap_rows, m->Ip, m->cfg.T, m->H1p, m->H2p, !chain_ok(m), s->stream)) return -1;
-  if (serve_wait_weights(m, s) || serve_wait_rows(r->emb)) return -1;
-  goctr_ubcache* const c = r->ub;
-  UbRead image(c, s->stream);                           // one image for every pass: held until topn_run has synchronised
-  TopnScorer sc;
-  sc.stream = s->stream; sc.n_users = r->n_users; sc.n_items = r->n_items;
-  sc.ub_off = c ? c->off.p : nullptr; sc.ub_items = c ? c->items.p : nullptr; sc.ub_ts = c ? c->ts.p : nullptr;
-  sc.max_rows = s->cap; sc.keys = s->d_in.p; sc.out = s->d_out.p;
-  sc.score = [&](int64_t N) {
-    const size_t Br = (size_t)round_up((int)N, 32);
-    unsigned n_stamps = 0;
-    return serve_score_keys(m, r, s, reinterpret_cast<const long long*>(sc.keys), reinterpret_cast<const int32_t*>(sc.keys + 8 * N),
-                            reinterpret_cast<const int32_t*>(sc.keys + 12 * N), N, reinterpret_cast<float*>(sc.out),
-                            reinterpret_cast<unsigned char*>(sc.out + 4 * Br), false, &n_stamps);
-  };
-  if (topn_run(sc, a)) return -1;
-  image.done();
-  return 0;
+  return with_scorer(m, r, cfg->pass_rows, [&](const TopnScorer& sc) { return topn_run(sc, a); });
 }
 
-// Recall, then rank (itemcf.hip has the recall, the key generator, the selection and the driver): the same slot lease, locks and
-// ONE image of the cache for the whole call as goctr_recommend_topn above.
+// Recall, then rank (itemcf.hip has the recall, the key generator, the selection and the driver): as goctr_recommend_topn above,
+// the recall and every pass under with_scorer's ONE image of the cache.
 int goctr_recommend_itemcf(goctr_model* m, goctr_recsys* r, goctr_itemcf* h, const int32_t* users, const int64_t* ts, int64_t n_req,
                            const int32_t* targets, const goctr_recall_cfg* recall_cfg, int32_t k, int64_t pass_rows,
                            int32_t* out_items, float* out_scores, int32_t* out_count, int32_t* out_cand_count,
@@ -764,37 +551,11 @@ int goctr_recommend_itemcf(goctr_model* m, goctr_recsys* r, goctr_itemcf* h, con
   GOCTR_CHECK(m && r && h && recall_cfg, "goctr_recommend_itemcf: bad arguments");
   GOCTR_SAME_ENGINE(m, r);
   GOCTR_SAME_ENGINE(m, h);
-  GOCTR_CHECK(r->emb->D == m->cfg.D && r->U == m->cfg.U && r->C == m->cfg.C, "goctr_recommend_itemcf: recsys dims (U=%d,C=%d,D=%d) != model (U=%d,C=%d,D=%d)",
-              r->U, r->C, r->emb->D, m->cfg.U, m->cfg.C, m->cfg.D);
+  if (check_recsys_dims("goctr_recommend_itemcf", m, r)) return -1;
   const ItemcfRecArgs a{users, ts, n_req, targets, *recall_cfg, k, pass_rows, out_items, out_scores, out_count, out_cand_count,
                         out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed};
   if (itemcf_check_recommend(h, a, r->n_users, r->n_items)) return -1;
-  std::shared_lock<std::shared_mutex> lm(m->mu);        // as serve_keys: weights, then embedding rows, stay put
-  std::shared_lock<std::shared_mutex> le(r->emb->mu);
-  SlotLease lease;
-  ServeSlot* s = lease.s;
-  if (!s) return -1;
-  const int64_t pass = pass_rows ? pass_rows : TOPN_DEFAULT_PASS_ROWS;
-  const int64_t cap_rows = std::max<int64_t>(pass, SERVE_COALESCE_ROWS);
-  if (s->ensure_keys(cap_rows, m->cfg.T, r->U, r->C)) return -1;
-  if (s->ws.ensure((int)cap_rows, m->Ip, m->cfg.T, m->H1p, m->H2p, !chain_ok(m), s->stream)) return -1;
-  if (serve_wait_weights(m, s) || serve_wait_rows(r->emb)) return -1;
-  goctr_ubcache* const c = r->ub;
-  UbRead image(c, s->stream);                           // one image for the recall and every pass
-  TopnScorer sc;
-  sc.stream = s->stream; sc.n_users = r->n_users; sc.n_items = r->n_items;
-  sc.ub_off = c ? c->off.p : nullptr; sc.ub_items = c ? c->items.p : nullptr; sc.ub_ts = c ? c->ts.p : nullptr;
-  sc.max_rows = s->cap; sc.keys = s->d_in.p; sc.out = s->d_out.p;
-  sc.score = [&](int64_t N) {
-    const size_t Br = (size_t)round_up((int)N, 32);
-    unsigned n_stamps = 0;
-    return serve_score_keys(m, r, s, reinterpret_cast<const long long*>(sc.keys), reinterpret_cast<const int32_t*>(sc.keys + 8 * N),
-                            reinterpret_cast<const int32_t*>(sc.keys + 12 * N), N, reinterpret_cast<float*>(sc.out),
-                            reinterpret_cast<unsigned char*>(sc.out + 4 * Br), false, &n_stamps);
-  };
-  if (itemcf_recommend_run(sc, h, a)) return -1;
-  image.done();
-  return 0;
+  return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return itemcf_recommend_run(sc, h, a); });
 }
 
 // model.Predict's own convention (model/model.go:242-352): `rows` dense TrainSample rows in HOST memory -> y_out [rows].
@@ -835,9 +596,9 @@ int goctr_predict_dense(goctr_model* m, const float* X, int64_t rows, int xcols,
     StepOpts op;
     op.train = false;
     if (launch_forward(m, src, (int)N, op, s->st.p, &fb)) return -1;
-    GOCTR_HIP(hipMemcpyAsync(s->h_out, s->d_out.p, (size_t)N * 4, hipMemcpyDeviceToHost, s->stream));
+    GOCTR_HIP(hipMemcpyAsync(s->h_out.p, s->d_out.p, (size_t)N * 4, hipMemcpyDeviceToHost, s->stream));
     GOCTR_HIP(hipStreamSynchronize(s->stream));
-    memcpy(y_out + o, s->h_out, (size_t)N * 4);
+    memcpy(y_out + o, s->h_out.p, (size_t)N * 4);
   }
   return 0;
 }

@@ -1,5 +1,5 @@
-// topn.h -- what goctr_recommend_topn's two halves share: serve.hip owns the serving slot, the locks and the scoring path
-// ("score N keys at these device pointers"), topn.hip the key generator, the seen test, the selection and the call's driver.
+// topn.h -- what goctr_recommend_topn's two halves share: serve.hip has the entry and (with_scorer) the serving slot, the locks and
+// the scoring path ("score N keys at these device pointers"), topn.hip the key generator, the seen test, the selection and the driver.
 #pragma once
 #include <functional>
 

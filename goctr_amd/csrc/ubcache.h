@@ -1,5 +1,7 @@
-// ubcache.h -- the behaviour cache handle (feature/ubcache/cache.go as a CSR in HBM) shared by its readers (serve.hip: the key
-// lookups of assembly and serving) and its updaters (ubcache.hip: BatchSet / Delete / Clear / Append).
+// ubcache.h -- the behaviour cache handle (feature/ubcache/cache.go as a CSR in HBM) and the launcher of its reader.  ubcache.hip
+// has the constructor, the assembly kernel (keys -> behaviour ids and feature rows) and the updaters (BatchSet / Delete / Clear /
+// Append); the key datasets (ctr_api.hip) and the serving passes (serve.hip, which also reads the arrays inside its fused
+// kernels) read the cache under a UbRead hold.
 #pragma once
 #include <mutex>
 #include <shared_mutex>
@@ -41,4 +43,12 @@ struct UbRead {
   void done() { if (lk.owns_lock()) lk.unlock(); }
   ~UbRead() { if (lk.owns_lock()) (void)hipStreamSynchronize(reads_on); }
 };
+
+// The reader (assemble_keys_kernel, ubcache.hip), one wavefront per key, cdiv(rows, 4) workgroups of 256 on `stream`, nothing
+// waited for.  Null is allowed for the three cache arrays together (no behaviour cache), items, ts (0: "from the newest") and every
+// output; `failed` selects BatchPredict's rule for keys without features.  The caller holds a UbRead until it has synchronised.
+int launch_assemble_keys(hipStream_t stream, const long long* off, const int32_t* seq_items, const long long* seq_ts,
+                         int64_t n_users, const float* user_table, int U, const float* item_table, int64_t n_items, int C,
+                         const int32_t* users, const int32_t* items, const long long* ts, int64_t rows, int T, int32_t* ub_ids,
+                         float* ufeat, float* cfeat, int32_t* item_out, unsigned char* failed);
 }  // namespace goctr

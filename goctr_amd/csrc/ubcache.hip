@@ -1,7 +1,8 @@
-// ubcache.hip -- updates of a live behaviour cache: UserBehaviorCache.Set / BatchSet / Delete / Clear (feature/ubcache/cache.go:27-55)
-// and Append (no reference counterpart) on the device, plus goctr_ubcache_info / _export.
+// ubcache.hip -- the behaviour cache (ubcache.UserBehaviorCache, feature/ubcache/cache.go, as a CSR in HBM: ubcache.h): its
+// constructor, its reader -- the per-sample gather of GetSampleVector (recommend/rcmd.go:460-536) as one kernel, SURVEY 8(f) rank 1
+// -- and the updates of a live cache: Set / BatchSet / Delete / Clear (cache.go:27-55), Append (no reference counterpart), _info, _export.
 //
-// The cache stays a CSR (ubcache.h) and its readers stay as they are.  An update of k users builds a SECOND CSR on the cache's own
+// The cache stays a CSR and its readers stay as they are.  An update of k users builds a SECOND CSR on the cache's own
 // stream and swaps the three pointers:
 //   - the host sorts / groups the payload by user (it is host data and small) and uploads it in ONE copy: the k touched users
 //     ascending, a CSR of their payload;
@@ -15,6 +16,7 @@
 //     lists by rank (position = own index + entries of the other list that go before it, by bisection).
 // Host work and host<->device traffic are proportional to the payload; nothing on the host walks n_users or the entries.
 #include <algorithm>
+#include <memory>
 #include <numeric>
 
 #include "scan.h"
@@ -23,6 +25,77 @@
 using namespace goctr;
 
 namespace {
+
+// TimeSeq.Filter (cache.go:71-94) for one key: the sequence is newest-first, so "the first i with Ts[i] <= maxTs"
+// is a lower bound found by bisection; then up to T items from there.
+__global__ __launch_bounds__(256) void assemble_keys_kernel(const long long* __restrict__ off, const int32_t* __restrict__ seq_items,
+                                                            const long long* __restrict__ seq_ts, long long n_users,
+                                                            const float* __restrict__ user_table, int U,
+                                                            const float* __restrict__ item_table, long long n_items, int C,
+                                                            const int32_t* __restrict__ users, const int32_t* __restrict__ items,
+                                                            const long long* __restrict__ ts, long long rows, int T,
+                                                            int32_t* __restrict__ ub_ids, float* __restrict__ ufeat,
+                                                            float* __restrict__ cfeat, int32_t* __restrict__ item_out,
+                                                            unsigned char* __restrict__ failed) {
+  const int lane = threadIdx.x & 63;
+  const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);   // one wavefront per sample
+  if (r >= rows) return;
+  // the key's three fields first, back to back: in a small serving pass they sit in pinned HOST memory (zero-copy), and
+  // fetched one by one where they are used they were three PCIe round trips in a row (7.8 us for a 256-key pass)
+  const int u = users[r];
+  const int it_key = items ? items[r] : -1;
+  const long long ts_key = ts ? ts[r] : 0;
+  bool uok = u >= 0 && u < n_users;
+  if (failed) {
+    // BatchPredict (rcmd.go:291-307): a key whose GetUserFeature / GetItemFeature fails is scored as the ALL-zero row
+    // (user features, behaviours, item embedding and item features alike)
+    const int it = it_key;
+    const bool ok = uok && it >= 0 && it < n_items;
+    if (lane == 0) { failed[r] = ok ? 0 : 1; item_out[r] = ok ? it : -1; }
+    if (!ok) {
+      for (int j = lane; j < T; j += 64) ub_ids[r * T + j] = -1;
+      for (int j = lane; j < U; j += 64) ufeat[r * U + j] = 0.f;
+      for (int j = lane; j < C; j += 64) cfeat[r * C + j] = 0.f;
+      return;
+    }
+  }
+  long long first = 0, cnt = 0;
+  const long long b = (uok && off) ? off[u] : 0, len = (uok && off) ? off[u + 1] - b : 0;   // off == NULL: no behaviour cache
+  if (len > 0) {
+    const long long mts = ts_key;
+    // first i with seq_ts[b + i] <= mts (descending order); mts == 0 means "from the newest" (cache.go:72-74: maxTs = Ts[0])
+    long long lo = 0;
+    if (mts != 0) {
+      if (len <= 256) {
+        // short histories (the common case): 64 entries per coalesced load and one ballot instead of a chain of ~7 dependent
+        // loads -- the serving pass of a Rank call is latency, not work
+        lo = len;
+        for (long long base = 0; base < len; base += 64) {
+          const long long i = base + lane;
+          const unsigned long long le = __ballot(i < len && seq_ts[b + i] <= mts);
+          if (le) { lo = base + (long long)__builtin_ctzll(le); break; }
+        }
+      } else {
+        long long hi = len;
+        while (lo < hi) {
+          const long long mid = (lo + hi) >> 1;
+          if (seq_ts[b + mid] <= mts) hi = mid; else lo = mid + 1;
+        }
+      }
+    }
+    first = lo;
+    cnt = len - first < T ? len - first : T;
+  }
+  if (ub_ids)
+    for (int j = lane; j < T; j += 64) ub_ids[r * T + j] = j < cnt ? seq_items[b + first + j] : -1;
+  if (ufeat)
+    for (int j = lane; j < U; j += 64) ufeat[r * U + j] = uok ? user_table[(long long)u * U + j] : 0.f;
+  if (cfeat) {
+    const int it = it_key;
+    const bool iok = it >= 0 && it < n_items;
+    for (int j = lane; j < C; j += 64) cfeat[r * C + j] = iok ? item_table[(long long)it * C + j] : 0.f;
+  }
+}
 
 enum { UB_SET = 0, UB_APPEND = 1 };
 
@@ -248,9 +321,63 @@ bool users_in_range(const goctr_ubcache* c, int64_t n, const int32_t* users, con
 
 }  // namespace
 
+int goctr::launch_assemble_keys(hipStream_t stream, const long long* off, const int32_t* seq_items, const long long* seq_ts,
+                                int64_t n_users, const float* user_table, int U, const float* item_table, int64_t n_items, int C,
+                                const int32_t* users, const int32_t* items, const long long* ts, int64_t rows, int T,
+                                int32_t* ub_ids, float* ufeat, float* cfeat, int32_t* item_out, unsigned char* failed) {
+  hipLaunchKernelGGL(assemble_keys_kernel, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, stream, off, seq_items, seq_ts,
+                     (long long)n_users, user_table, U, item_table, (long long)n_items, C, users, items, ts, (long long)rows, T,
+                     ub_ids, ufeat, cfeat, item_out, failed);
+  GOCTR_HIP(hipGetLastError());
+  return 0;
+}
+
 extern "C" {
 
-// (these do not take the engine lock and do not touch the main stream: an update must not queue behind training)
+int goctr_ubcache_create(int64_t n_users, const int64_t* off, const int32_t* items, const int64_t* ts, goctr_ubcache** out) {
+  GOCTR_ENTER();
+  GOCTR_CHECK(n_users > 0 && off && out && off[0] == 0, "goctr_ubcache_create: bad arguments");
+  const int64_t nnz = off[n_users];
+  GOCTR_CHECK(nnz >= 0 && (nnz == 0 || (items && ts)), "goctr_ubcache_create: sequences missing");
+  for (int64_t u = 0; u < n_users; ++u) {
+    GOCTR_CHECK(off[u + 1] >= off[u], "goctr_ubcache_create: offsets must be non-decreasing");
+    for (int64_t k = off[u] + 1; k < off[u + 1]; ++k)
+      GOCTR_CHECK(ts[k] <= ts[k - 1], "goctr_ubcache_create: user %lld's sequence is not in timestamp-descending order "
+                  "(cache.go:8 TimeSeq)", (long long)u);
+  }
+  std::unique_ptr<goctr_ubcache> c(new goctr_ubcache);
+  c->n_users = n_users; c->nnz = nnz;
+  std::vector<long long> o(off, off + n_users + 1), t(ts, ts + nnz);
+  if (c->off.alloc(o.size(), false) || c->off.upload(o.data(), o.size())) return -1;
+  if (c->items.alloc((size_t)nnz, false) || (nnz && c->items.upload(items, (size_t)nnz))) return -1;
+  if (c->ts.alloc((size_t)nnz, false) || (nnz && c->ts.upload(t.data(), (size_t)nnz))) return -1;
+  GOCTR_HIP(hipStreamCreateWithFlags(&c->ustream, hipStreamNonBlocking));
+  *out = c.release();
+  return 0;
+}
+void goctr_ubcache_destroy(goctr_ubcache* c) {
+  if (!c) return;
+  EngineScope on(c->eng);
+  delete c;
+}
+
+int goctr_ubcache_get(goctr_ubcache* c, const int32_t* users, const int64_t* max_ts, int64_t rows, int T, int32_t* out_ids) {
+  GOCTR_ENTER_H(c);
+  GOCTR_CHECK(c && users && out_ids && rows > 0 && T > 0, "goctr_ubcache_get: bad arguments");
+  DevBuf<int32_t> du, dout; DevBuf<long long> dts;
+  std::vector<long long> t(rows, 0);
+  if (max_ts) for (int64_t i = 0; i < rows; ++i) t[i] = max_ts[i];
+  if (du.alloc(rows, false) || du.upload(users, rows) || dts.alloc(rows, false) || dts.upload(t.data(), rows) ||
+      dout.alloc((size_t)rows * T, false)) return -1;
+  UbRead image(c, engine().stream);                   // until the download's synchronisation
+  if (launch_assemble_keys(engine().stream, c->off.p, c->items.p, c->ts.p, c->n_users, nullptr, 0, nullptr, 0, 0, du.p, nullptr,
+                           dts.p, rows, T, dout.p, nullptr, nullptr, nullptr, nullptr)) return -1;
+  if (dout.download(out_ids, (size_t)rows * T)) return -1;
+  image.done();
+  return 0;
+}
+
+// (the updates do not take the engine lock and do not touch the main stream: an update must not queue behind training)
 int goctr_ubcache_batch_set(goctr_ubcache* c, int64_t n, const int32_t* users, const int64_t* off, const int32_t* items,
                             const int64_t* ts) {
   UB_ENTER(c);

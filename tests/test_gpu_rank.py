@@ -117,6 +117,32 @@ def test_key_lookup_inside_the_attention_kernel_equals_assembled_rows(oracle, mo
     assert np.max(np.abs(ys[0] - ref)) <= 1e-5
 
 
+def test_staging_grows_on_a_live_slot(oracle, monkeypatch):
+    """one recsys, one model, BatchPredict of 8, 300, 5000 and 8 keys in that order: 5000 is above the 4096 rows a zero-copy /
+    coalesced pass may hold, so the serving slot grows its pinned, BAR and device buffers past their first capacity (retiring
+    the outgrown ones) and the pass takes the two DMA copies; the last call goes back through the zero-copy path on the grown
+    buffers.  Each result equals, bit for bit, the same keys scored with the rows assembled first (GOCTR_SERVE_FUSE=0, the
+    path the test above pins the fused passes on) -- scored afterwards, so that the reference does not grow the slot before
+    the calls under test; the 5000 rows also against the oracle."""
+    from goctr_amd import recommend as gr
+    rng = np.random.default_rng(77)
+    rs, om, net, uids, iids, extra = build(oracle, rng, 0)
+    keys = [gr.Sample(int(rng.choice(uids)), int(rng.choice(iids)), 0.0, int(rng.integers(0, 1100))) for _ in range(5000)]
+    keys[3] = gr.Sample(4242, keys[3].ItemId, 0.0, 50)                # unknown user: a failed flag in every call
+    keys[4100] = gr.Sample(keys[4100].UserId, extra[0], 0.0, 50)      # ... and one behind the first capacity
+    model = gr.Predictor(rs, net, predBatchSize=256)
+    sizes = (8, 300, 5000, 8)
+    got = [gr.BatchPredict(model, keys[:n])[:, 0].copy() for n in sizes]
+    monkeypatch.setenv("GOCTR_SERVE_FUSE", "0")
+    want = {n: gr.BatchPredict(model, keys[:n])[:, 0].copy() for n in set(sizes)}
+    monkeypatch.delenv("GOCTR_SERVE_FUSE")
+    for n, y in zip(sizes, got):
+        assert y.shape == (n,) and np.array_equal(y, want[n]), n
+    ref, failed = oracle_scores(oracle, rs, om, keys, 256)
+    assert failed.sum() == 2
+    assert np.max(np.abs(got[2] - ref)) <= 1e-5
+
+
 def test_rank_and_error_behaviour(oracle):
     from goctr_amd import recommend as gr
     rng = np.random.default_rng(31)

@@ -83,6 +83,48 @@ def test_scan_path_query_blocks(oracle, V, D, k, Q):
         assert np.array_equal(idx0, idx) and np.array_equal(sim0, sim) and np.array_equal(cnt0, cnt), (var, val)
 
 
+_GROWTH = {}
+
+
+def _growth_case(oracle):
+    """items, queries, ignore indices and the oracle's answers for test_staging_grows_on_a_live_searcher, computed once"""
+    if not _GROWTH:
+        rng = np.random.default_rng(3000 + 16 + 5)
+        V, D, k = 3000, 16, 5
+        items = rng.standard_normal((V, D))
+        queries = rng.standard_normal((200, D))
+        ignore = np.full(200, -1, np.int64)
+        own = rng.integers(0, V, size=len(queries[::7]))
+        queries[::7] = items[own]                               # every seventh query is an item: its own row is ignored
+        ignore[::7] = own
+        want = [oracle.knn_search(items, queries[q], k, ignore=int(ignore[q])) for q in range(200)]
+        _GROWTH.update(items=items, queries=queries, ignore=ignore, want=want, k=k)
+    return _GROWTH
+
+
+@pytest.mark.parametrize("bar", [None, "0"])
+def test_staging_grows_on_a_live_searcher(oracle, bar):
+    """one searcher (V = 3000, D = 16, k = 5), calls of 1, 70, 1 and 200 queries on the same handle: the pinned input and
+    output staging -- and, over a large BAR, the device input buffer -- grow twice and retire their outgrown predecessors while
+    the handle lives; 70 and 200 cross a 64-query block, 12 queries and more take the matrix-core filter; with GOCTR_KNN_BAR=0
+    the input goes through the staged copy.  Every call equals the oracle bit for bit: indices, similarities, counts."""
+    from goctr_amd import search as gs
+    c = _growth_case(oracle)
+    k = c["k"]
+    if bar is not None:
+        os.environ["GOCTR_KNN_BAR"] = bar
+    try:
+        s = gs.Searcher([str(i) for i in range(c["items"].shape[0])], c["items"])
+        for Q in (1, 70, 1, 200):
+            idx, sim, cnt = s.search_vectors(c["queries"][:Q], k, c["ignore"][:Q])
+            for q in range(Q):
+                ri, rs, _ = c["want"][q]
+                assert cnt[q] == ri.size, (Q, q)
+                assert np.array_equal(idx[q, :cnt[q]], ri) and np.array_equal(sim[q, :cnt[q]], rs), (Q, q)
+    finally:
+        os.environ.pop("GOCTR_KNN_BAR", None)
+
+
 @pytest.mark.parametrize("V,k,D", [(5000, 3, 8), (5000, 25, 8), (9000, 256, 8), (9000, 25, 16), (40000, 10, 16)])
 def test_heavy_ties_replay(oracle, V, k, D):
     """items drawn from a pool of a few distinct vectors: thousands of exactly equal similarities, tie groups cut by

@@ -1,4 +1,4 @@
-"""The claim behind the wave-parallel replay of csrc/search.hip (knn_replay_body): ONE insertion of search.go:104-121 --
+"""The claim behind the wave-parallel replay of csrc/search.hip (knn_collect_kernel's replay phase): ONE insertion of search.go:104-121 --
 
     if score > low { carry = (score, item); for i in 0..k-1: if carry.sim > nb[i].sim { swap(carry, nb[i]) }; low = nb[k-1].sim }
 
