@@ -70,6 +70,32 @@ class GroupStat(C.Structure):
                 ("auc_num", C.c_uint64)]
 
 
+class CurveCfg(C.Structure):
+    """goctr_curve_cfg (include/goctr.h)"""
+    _fields_ = [("bins", C.c_int32), ("reserved", C.c_int32), ("threshold", C.c_double)]
+
+
+class CurveMetrics(C.Structure):
+    """goctr_curve_metrics (include/goctr.h)"""
+    _fields_ = [("base", BinaryMetrics), ("threshold", C.c_double), ("tp", C.c_int64), ("fp", C.c_int64), ("tn", C.c_int64),
+                ("fn", C.c_int64), ("precision", C.c_double), ("recall", C.c_double), ("f1", C.c_double),
+                ("average_precision", C.c_double), ("ks_num", C.c_uint64), ("ks_den", C.c_uint64), ("ks", C.c_double),
+                ("ks_group", C.c_int64), ("ks_threshold", C.c_double), ("best_f1_group", C.c_int64),
+                ("best_f1_threshold", C.c_double), ("best_f1_tp", C.c_int64), ("best_f1_fp", C.c_int64), ("best_f1", C.c_double),
+                ("bins", C.c_int64), ("score_sum", C.c_double), ("mean_score", C.c_double), ("calibration_ratio", C.c_double),
+                ("ece", C.c_double), ("ne", C.c_double), ("points", C.c_int64)]
+
+
+class CurvePoints(C.Structure):
+    """goctr_curve_points (include/goctr.h): host arrays of cap entries"""
+    _fields_ = [("cap", C.c_int64), ("thr", C.POINTER(C.c_double)), ("tps", C.POINTER(C.c_int64)), ("fps", C.POINTER(C.c_int64))]
+
+
+class CalibBins(C.Structure):
+    """goctr_calib_bins (include/goctr.h): host arrays of cfg.bins entries"""
+    _fields_ = [("count", C.POINTER(C.c_int64)), ("pos", C.POINTER(C.c_int64)), ("score_sum", C.POINTER(C.c_double))]
+
+
 class NegSampleCfg(C.Structure):
     """goctr_negsample_cfg (include/goctr.h)"""
     _fields_ = [("n_neg", C.c_int32), ("weighting", C.c_int32), ("which", C.c_int32), ("max_tries", C.c_int32),
@@ -123,6 +149,8 @@ SYMBOLS = [
     "goctr_w2v_get_keep_mask", "goctr_metrics_binary", "goctr_metrics_binary_f64", "goctr_evaluate_dataset",
     "goctr_mlp_evaluate_resident", "goctr_metrics_grouped", "goctr_metrics_grouped_f64", "goctr_evaluate_dataset_grouped",
     "goctr_mlp_evaluate_resident_grouped",
+    "goctr_curve_cfg_default", "goctr_metrics_curve", "goctr_metrics_curve_f64", "goctr_evaluate_dataset_curve",
+    "goctr_mlp_evaluate_resident_curve",
     "goctr_emb_load_w2v", "goctr_w2v_copy_word_vectors", "goctr_searcher_create_from_w2v", "goctr_searcher_load_w2v",
     "goctr_corpus_append_ubcache",
     "goctr_negsample_cfg_default", "goctr_samples_create", "goctr_samples_destroy", "goctr_samples_info", "goctr_samples_export",
@@ -151,7 +179,7 @@ def load() -> C.CDLL:
         for name in ("goctr_model_destroy", "goctr_emb_destroy", "goctr_dataset_destroy", "goctr_mlp_destroy",
                      "goctr_w2v_destroy", "goctr_searcher_destroy", "goctr_ubcache_destroy", "goctr_recsys_destroy", "goctr_train_cfg_default", "goctr_mlp_cfg_default",
                      "goctr_w2v_cfg_default", "goctr_negsample_cfg_default", "goctr_samples_destroy", "goctr_topn_cfg_default",
-                     "goctr_itemcf_cfg_default", "goctr_recall_cfg_default", "goctr_itemcf_destroy"):
+                     "goctr_itemcf_cfg_default", "goctr_recall_cfg_default", "goctr_itemcf_destroy", "goctr_curve_cfg_default"):
             getattr(_lib, name).restype = None
         _bm = C.POINTER(BinaryMetrics)
         _lib.goctr_metrics_binary.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, _bm]
@@ -165,6 +193,12 @@ def load() -> C.CDLL:
                                                    _gs, C.c_int64]
         _lib.goctr_evaluate_dataset_grouped.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _i32, C.c_int, _bm, _gm]
         _lib.goctr_mlp_evaluate_resident_grouped.argtypes = [C.c_void_p, _i32, C.c_int, _bm, _gm]
+        _cc, _cm, _cp, _cb = C.POINTER(CurveCfg), C.POINTER(CurveMetrics), C.POINTER(CurvePoints), C.POINTER(CalibBins)
+        _lib.goctr_curve_cfg_default.argtypes = [_cc]
+        _lib.goctr_metrics_curve.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, _cc, _cm, _cp, _cb]
+        _lib.goctr_metrics_curve_f64.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64, _cc, _cm, _cp, _cb]
+        _lib.goctr_evaluate_dataset_curve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _cc, _cm, _cp, _cb]
+        _lib.goctr_mlp_evaluate_resident_curve.argtypes = [C.c_void_p, _cc, _cm, _cp, _cb]
         _i64 = C.POINTER(C.c_int64)
         _lib.goctr_ubcache_batch_set.argtypes = [C.c_void_p, C.c_int64, _i32, _i64, _i32, _i64]
         _lib.goctr_ubcache_delete.argtypes = [C.c_void_p, C.c_int64, _i32]
@@ -295,6 +329,14 @@ def device_info():
 def default_train_cfg(**kw) -> TrainCfg:
     c = TrainCfg()
     load().goctr_train_cfg_default(C.byref(c))
+    for k, v in kw.items():
+        setattr(c, k, v)
+    return c
+
+
+def default_curve_cfg(**kw) -> CurveCfg:
+    c = CurveCfg()
+    load().goctr_curve_cfg_default(C.byref(c))
     for k, v in kw.items():
         setattr(c, k, v)
     return c

@@ -837,6 +837,19 @@ int goctr_evaluate_dataset(goctr_model* m, goctr_emb* emb, goctr_dataset* d, int
   return metrics_binary_dev(m->yall.p, d->Y.p, d->rows, out, "goctr_evaluate_dataset");
 }
 
+int goctr_evaluate_dataset_curve(goctr_model* m, goctr_emb* emb, goctr_dataset* d, int batch, const goctr_curve_cfg* cfg,
+                                 goctr_curve_metrics* out, goctr_curve_points* pts, goctr_calib_bins* bins) {
+  GOCTR_ENTER_H(m);
+  const char* who = "goctr_evaluate_dataset_curve";
+  GOCTR_CHECK(m && d && out && batch > 0, "%s: bad arguments", who);
+  GOCTR_CHECK(d->has_y && d->Y.p, "%s: the dataset has no labels", who);
+  if (metrics_check_rows(d->rows, who) || metrics_curve_check(cfg, pts, bins, who)) return -1;
+  std::unique_lock<std::shared_mutex> lk(m->mu); ++m->gen;
+  // goctr_evaluate_dataset's predict, then the curve pipeline over the same resident scores and labels (metrics_curve.hip)
+  if (predict_batches(m, emb, d, batch, 0, cdiv(d->rows, batch), true, nullptr)) return -1;
+  return metrics_curve_dev(m->yall.p, d->Y.p, d->rows, cfg, out, pts, bins, who);
+}
+
 int goctr_evaluate_dataset_grouped(goctr_model* m, goctr_emb* emb, goctr_dataset* d, int batch, const int32_t* group, int k,
                                    goctr_binary_metrics* all, goctr_group_metrics* out) {
   GOCTR_ENTER_H(m);

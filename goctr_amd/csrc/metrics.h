@@ -1,5 +1,6 @@
-// metrics.h -- interface of metrics.hip (exact binary ROC-AUC, accuracy and log-loss of scores resident on the device) and of
-// metrics_group.hip (the per-group ranking metrics over the same scores), and the device helpers the two pipelines share.
+// metrics.h -- interface of metrics.hip (exact binary ROC-AUC, accuracy and log-loss of scores resident on the device), of
+// metrics_group.hip (the per-group ranking metrics over the same scores) and of metrics_curve.hip (curve points, AP, KS, best F1
+// and calibration bins out of metrics.hip's sorted order), and the device helpers the pipelines share.
 #pragma once
 #include <cstdint>
 
@@ -28,6 +29,39 @@ int metrics_grouped_dev(const double* score, const double* y, const int32_t* gro
 int metrics_grouped_dev(const double* score, const float* y, const int32_t* group, int64_t n, int k, goctr_group_metrics* out,
                         goctr_group_stat* per_group, int64_t cap, const char* who);
 
+// Curve metrics (metrics_curve.hip) of scores and labels already in device memory of the calling thread's engine: everything
+// goctr_curve_metrics holds, out of ONE sort (metrics_sorted_dev below).  cfg / pts / bins as goctr_metrics_curve takes them (pts and
+// bins point at HOST arrays; either may be null); the arguments are checked here.  Fills *out and the arrays only on success.
+int metrics_curve_dev(const float* score, const float* y, int64_t n, const goctr_curve_cfg* cfg, goctr_curve_metrics* out,
+                      goctr_curve_points* pts, goctr_calib_bins* bins, const char* who);
+int metrics_curve_dev(const double* score, const double* y, int64_t n, const goctr_curve_cfg* cfg, goctr_curve_metrics* out,
+                      goctr_curve_points* pts, goctr_calib_bins* bins, const char* who);
+int metrics_curve_dev(const double* score, const float* y, int64_t n, const goctr_curve_cfg* cfg, goctr_curve_metrics* out,
+                      goctr_curve_points* pts, goctr_calib_bins* bins, const char* who);
+// the argument checks alone (bins, threshold, cap, array pointers): for entry points that predict before they measure
+int metrics_curve_check(const goctr_curve_cfg* cfg, const goctr_curve_points* pts, const goctr_calib_bins* bins, const char* who);
+
+// The front both pooled pipelines share (metrics.hip): key build, sort, the two scans, the AUC terms and the key build's partials,
+// all queued on the engine's main stream, nothing copied back.  What it leaves on the device stays valid until the engine's next
+// metrics call.
+struct MetricsPart { unsigned long long pos, correct, nan; double ll; };
+// P / G from the scans' totals, S from the terms, the rest from the key build's partials
+struct MetricsRes { unsigned long long P, G, S, pos, correct, nan; double ll; };
+struct MetricsSorted {
+  const void* keys;            // the sorted keys, score descending (one per row, the score's width); only with keep_keys
+  const unsigned int* eh;      // E[i] | head[i] << 31: the positives in the rows before i; whether row i opens a threshold group
+  const unsigned int* heads;   // heads[g] = first row of threshold group g
+  const MetricsRes* res;       // (device)
+  int nparts;                  // the workgroups the grid-stride kernels over rows / groups ran with
+};
+// score / y on the device, or null with host_score / host_y (staged through the key buffers).  keep_keys: heads[] gets a buffer
+// of its own (4 bytes per row) in place of overwriting the sorted keys.  Instantiated for the three (score, label) pairs above.
+template <class TS, class TL>
+int metrics_sorted_dev(const TS* score, const TL* y, int64_t n, const char* who, const TS* host_score, const TL* host_y,
+                       bool keep_keys, MetricsSorted* out);
+// goctr_binary_metrics from the host copy of MetricsRes; refuses a NaN score (nothing written then)
+int metrics_binary_finish(const MetricsRes& h, int64_t n, const char* who, goctr_binary_metrics* out);
+
 // the row-count check every metrics entry point makes (0 < n < 2^31)
 int metrics_check_rows(int64_t n, const char* who);
 
@@ -52,6 +86,14 @@ __device__ __forceinline__ unsigned long long score_key(double s, bool* nan) {
   *nan = (b & 0x7fffffffffffffffull) > 0x7ff0000000000000ull;
   if (b == 0x8000000000000000ull) b = 0ull;
   return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+// a key back to its score, widened exactly to double (the key of -0 is +0's)
+__device__ __forceinline__ double key_score(unsigned int k) {
+  return (double)__uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+__device__ __forceinline__ double key_score(unsigned long long k) {
+  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
 }
 
 // the wavefront's sum in a fixed order (lane tree); valid in lane 0

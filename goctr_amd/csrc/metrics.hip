@@ -23,6 +23,8 @@
 // Scratch per row: keys 2 x sizeof(key) + labels 2 x 1 byte (+ rocPRIM's scratch), per engine with a high-water mark.  The host
 // entry points stage the caller's arrays into the two key buffers (scores over the sort input: the key build overwrites each
 // score with its own key; labels over the sort output), so they need no more.
+// Everything up to the copy is metrics_sorted_dev, which metrics_curve.hip runs too: there heads[] gets 4 bytes per row of its own
+// and the sorted keys stay (a key decodes back to its score).
 #include <cmath>
 
 #include "common.h"
@@ -32,10 +34,6 @@
 
 namespace goctr {
 namespace {
-
-struct MetricsPart { unsigned long long pos, correct, nan; double ll; };
-// what the host reads back: P / G from the scans' totals, S from the terms, the rest from the key build's partials
-struct MetricsRes { unsigned long long P, G, S, pos, correct, nan; double ll; };
 
 // utils.Accuracy32: math.Round(float64(p - y)) == 0 with p - y in float32, i.e. |fl32(p - y)| < 0.5 (NaN: no hit); utils.Accuracy
 // (and the MLP's float64 head) take the difference in float64
@@ -148,18 +146,21 @@ __global__ __launch_bounds__(MB) void metrics_finish_kernel(const MetricsPart* _
 struct MetricsWs {
   DevBuf<char> kin, kout, temp;          // sort input keys (then E | head), sorted keys (then heads); rocPRIM's scratch
   DevBuf<unsigned char> lin, lout;       // label bytes before / after the sort (lout rounded up to whole 32-bit words)
+  DevBuf<unsigned int> heads;            // heads[] where the sorted keys are kept (metrics_curve.hip); empty otherwise
   DevBuf<unsigned int> tiles;            // scan.h's tile sums
   DevBuf<MetricsPart> part;
   DevBuf<MetricsRes> res;
-  void release() { kin.release(); kout.release(); temp.release(); lin.release(); lout.release(); tiles.release(); part.release(); res.release(); }
+  void release() { kin.release(); kout.release(); temp.release(); lin.release(); lout.release(); heads.release(); tiles.release(); part.release(); res.release(); }
 };
 
 // high-water growth of the scratch for n rows of kb-byte keys and a sort that needs temp_bytes; on failure nothing is kept
-int ensure_ws(MetricsWs& w, int64_t n, size_t kb, size_t temp_bytes, const char* who) {
-  const size_t kbytes = (size_t)n * kb, lbytes = (size_t)cdiv(n, 4) * 4;
+int ensure_ws(MetricsWs& w, int64_t n, size_t kb, size_t temp_bytes, bool keep_keys, const char* who) {
+  const size_t kbytes = (size_t)n * kb, lbytes = (size_t)cdiv(n, 4) * 4, hrows = keep_keys ? (size_t)n : 0;
   const size_t want = (w.kin.n < kbytes ? kbytes : 0) + (w.kout.n < kbytes ? kbytes : 0) + (w.lin.n < lbytes ? lbytes : 0) +
-                      (w.lout.n < lbytes ? lbytes : 0) + (w.temp.n < temp_bytes ? temp_bytes : 0);
+                      (w.lout.n < lbytes ? lbytes : 0) + (w.temp.n < temp_bytes ? temp_bytes : 0) +
+                      (w.heads.n < hrows ? 4 * hrows : 0);
   if (w.kin.ensure(kbytes, false) || w.kout.ensure(kbytes, false) || w.lin.ensure(lbytes, false) || w.lout.ensure(lbytes, false) ||
+      (keep_keys && w.heads.ensure(hrows, false)) ||
       radix_sort_scratch(w.temp, temp_bytes) || w.tiles.ensure((size_t)cdiv(n, SCAN_TILE), false) ||
       w.part.ensure(MKEY_MAX_BLOCKS, false) || w.res.ensure(1, false)) {
     w.release();
@@ -173,6 +174,35 @@ int ensure_ws(MetricsWs& w, int64_t n, size_t kb, size_t temp_bytes, const char*
 template <class TS, class TL>
 int run(const TS* score, const TL* y, int64_t n, goctr_binary_metrics* out, const char* who, const TS* host_score = nullptr,
         const TL* host_y = nullptr) {
+  MetricsSorted m;
+  if (metrics_sorted_dev(score, y, n, who, host_score, host_y, false, &m)) return -1;
+  hipStream_t s = engine().stream;
+  MetricsRes h{};
+  GOCTR_HIP(hipMemcpyAsync(&h, m.res, sizeof(h), hipMemcpyDeviceToHost, s));
+  GOCTR_HIP(hipStreamSynchronize(s));
+  return metrics_binary_finish(h, n, who, out);
+}
+
+}  // namespace
+
+// correctly rounded num / den (num <= den, den > 0) in 128-bit integer arithmetic
+double div_rounded(uint64_t num, uint64_t den) {
+  if (num == 0) return 0.0;
+  const int k = 64 + __builtin_clzll(num);             // num << k has its top bit at 127: the quotient has 64 .. 128 bits
+  const unsigned __int128 a = (unsigned __int128)num << k;
+  const unsigned __int128 q = a / den, r = a % den;
+  const uint64_t hi = (uint64_t)(q >> 64);
+  const int bits = hi ? 128 - __builtin_clzll(hi) : 64 - __builtin_clzll((uint64_t)q);
+  const int drop = bits - 53;                          // >= 11
+  unsigned __int128 mant = q >> drop;
+  const unsigned __int128 rest = q & (((unsigned __int128)1 << drop) - 1), half = (unsigned __int128)1 << (drop - 1);
+  if (rest > half || (rest == half && (r != 0 || (mant & 1)))) ++mant;   // to nearest, ties to even
+  return std::ldexp((double)(uint64_t)mant, drop - k);
+}
+
+template <class TS, class TL>
+int metrics_sorted_dev(const TS* score, const TL* y, int64_t n, const char* who, const TS* host_score, const TL* host_y,
+                       bool keep_keys, MetricsSorted* out) {
   using K = typename std::conditional<sizeof(TS) == 4, unsigned int, unsigned long long>::type;
   static_assert(sizeof(K) == sizeof(TS), "one key per score");
   if (metrics_check_rows(n, who)) return -1;
@@ -181,7 +211,7 @@ int run(const TS* score, const TL* y, int64_t n, goctr_binary_metrics* out, cons
   MetricsWs& w = engine_scratch<MetricsWs>();
   size_t temp_bytes = 0;
   if (radix_sort_pairs_bytes<true, K, unsigned char>((size_t)n, 8u * (unsigned)sizeof(K), s, &temp_bytes)) return -1;
-  if (ensure_ws(w, n, sizeof(K), temp_bytes, who)) return -1;
+  if (ensure_ws(w, n, sizeof(K), temp_bytes, keep_keys, who)) return -1;
   K* kin = reinterpret_cast<K*>(w.kin.p);
   K* kout = reinterpret_cast<K*>(w.kout.p);
   if (host_score) {        // scores over the sort input, labels over the sort output (see the top of the file)
@@ -200,7 +230,8 @@ int run(const TS* score, const TL* y, int64_t n, goctr_binary_metrics* out, cons
   const int64_t words = cdiv(n, 4);
   if (words * 4 > n) GOCTR_HIP(hipMemsetAsync(w.lout.p + n, 0, (size_t)(words * 4 - n), s));
   unsigned int* eh = reinterpret_cast<unsigned int*>(w.kin.p);      // the sort's input is free now
-  unsigned int* heads = reinterpret_cast<unsigned int*>(w.kout.p);  // the sorted keys are free after scan 1
+  // the sorted keys are free after scan 1, unless the caller reads them
+  unsigned int* heads = keep_keys ? w.heads.p : reinterpret_cast<unsigned int*>(w.kout.p);
   MetricsRes* res = w.res.p;
   if (exclusive_scan_sink(reinterpret_cast<const unsigned int*>(w.lout.p), words, w.tiles, &res->P, LabelCount{},
                           PrefixHeadSink<K>{kout, eh, (long long)n}))
@@ -209,9 +240,17 @@ int run(const TS* score, const TL* y, int64_t n, goctr_binary_metrics* out, cons
   hipLaunchKernelGGL(metrics_terms_kernel, dim3((unsigned)nparts), dim3(MB), 0, s, heads, eh, (long long)n, res);
   hipLaunchKernelGGL(metrics_finish_kernel, dim3(1), dim3(MB), 0, s, w.part.p, nparts, res);
   GOCTR_HIP(hipGetLastError());
-  MetricsRes h{};
-  GOCTR_HIP(hipMemcpyAsync(&h, res, sizeof(h), hipMemcpyDeviceToHost, s));
-  GOCTR_HIP(hipStreamSynchronize(s));
+  *out = MetricsSorted{kout, eh, heads, res, nparts};
+  return 0;
+}
+template int metrics_sorted_dev<float, float>(const float*, const float*, int64_t, const char*, const float*, const float*, bool,
+                                              MetricsSorted*);
+template int metrics_sorted_dev<double, double>(const double*, const double*, int64_t, const char*, const double*, const double*,
+                                                bool, MetricsSorted*);
+template int metrics_sorted_dev<double, float>(const double*, const float*, int64_t, const char*, const double*, const float*, bool,
+                                               MetricsSorted*);
+
+int metrics_binary_finish(const MetricsRes& h, int64_t n, const char* who, goctr_binary_metrics* out) {
   GOCTR_CHECK(h.nan == 0, "%s: %llu of the %lld scores are NaN (a NaN score has no place in the ranking)", who, h.nan, (long long)n);
   GOCTR_CHECK(h.P == h.pos, "%s: internal error: label scan counted %llu positives, the key build %llu", who, h.P, h.pos);
   goctr_binary_metrics r{};
@@ -232,23 +271,6 @@ int run(const TS* score, const TL* y, int64_t n, goctr_binary_metrics* out, cons
   r.logloss = h.ll / (double)n;
   *out = r;
   return 0;
-}
-
-}  // namespace
-
-// correctly rounded num / den (num <= den, den > 0) in 128-bit integer arithmetic
-double div_rounded(uint64_t num, uint64_t den) {
-  if (num == 0) return 0.0;
-  const int k = 64 + __builtin_clzll(num);             // num << k has its top bit at 127: the quotient has 64 .. 128 bits
-  const unsigned __int128 a = (unsigned __int128)num << k;
-  const unsigned __int128 q = a / den, r = a % den;
-  const uint64_t hi = (uint64_t)(q >> 64);
-  const int bits = hi ? 128 - __builtin_clzll(hi) : 64 - __builtin_clzll((uint64_t)q);
-  const int drop = bits - 53;                          // >= 11
-  unsigned __int128 mant = q >> drop;
-  const unsigned __int128 rest = q & (((unsigned __int128)1 << drop) - 1), half = (unsigned __int128)1 << (drop - 1);
-  if (rest > half || (rest == half && (r != 0 || (mant & 1)))) ++mant;   // to nearest, ties to even
-  return std::ldexp((double)(uint64_t)mant, drop - k);
 }
 
 int metrics_check_rows(int64_t n, const char* who) {

@@ -267,6 +267,22 @@ int goctr_mlp_evaluate_resident(goctr_mlp* p, goctr_binary_metrics* out) {
   return metrics_binary_dev(score.p, p->Yr.p, p->rows, out, "goctr_mlp_evaluate_resident");
 }
 
+int goctr_mlp_evaluate_resident_curve(goctr_mlp* p, const goctr_curve_cfg* cfg, goctr_curve_metrics* out, goctr_curve_points* pts,
+                                      goctr_calib_bins* bins) {
+  GOCTR_ENTER_H(p);
+  const char* who = "goctr_mlp_evaluate_resident_curve";
+  GOCTR_CHECK(p && out, "%s: bad arguments", who);
+  GOCTR_CHECK(p->rows > 0, "%s: upload rows first", who);
+  GOCTR_CHECK(p->units[p->nl] == 1 && p->cfg.out_activation != GOCTR_OUT_SOFTMAX,
+              "%s: binary metrics need a single-output head (this one has %d output units%s)", who, p->units[p->nl],
+              p->cfg.out_activation == GOCTR_OUT_SOFTMAX ? ", softmax" : "");
+  if (metrics_check_rows(p->rows, who) || metrics_curve_check(cfg, pts, bins, who)) return -1;
+  std::lock_guard<std::mutex> lk(p->mu);
+  DevBuf<double> score;
+  if (score.alloc((size_t)p->rows, false) || predict_resident64(p, score.p)) return -1;
+  return metrics_curve_dev(score.p, p->Yr.p, p->rows, cfg, out, pts, bins, who);
+}
+
 int goctr_mlp_evaluate_resident_grouped(goctr_mlp* p, const int32_t* group, int k, goctr_binary_metrics* all,
                                         goctr_group_metrics* out) {
   GOCTR_ENTER_H(p);

@@ -104,6 +104,41 @@ inline goctr_group_metrics GroupedMetrics(const double* score, const double* y, 
   if (perGroup) perGroup->resize((size_t)m.groups);
   return m;
 }
+// the curve pipeline (goctr_metrics_curve): BinaryMetrics' figures as .base plus tp / fp / precision / recall / f1 at cfg.threshold,
+// average precision, KS, the F1-optimal cut and calibration bins; with `points` >= 2 also binaryClfCurve's arrays (every group, or
+// an even decimation down to `points` of them)
+struct CurveResult {
+  goctr_curve_metrics m{};
+  std::vector<double> thr, binScoreSum;
+  std::vector<int64_t> tps, fps, binCount, binPos;
+};
+template <class Call>
+inline CurveResult curveCall(const goctr_curve_cfg* cfg, int64_t points, Call call) {
+  goctr_curve_cfg c;
+  goctr_curve_cfg_default(&c);
+  if (cfg) c = *cfg;
+  CurveResult r;
+  const size_t room = (size_t)std::max<int64_t>(points, 1), nb = (size_t)std::min(std::max(c.bins, 1), 1024);
+  r.thr.resize(room); r.tps.resize(room); r.fps.resize(room);
+  r.binCount.resize(nb); r.binPos.resize(nb); r.binScoreSum.resize(nb);
+  goctr_curve_points pts{points, r.thr.data(), r.tps.data(), r.fps.data()};
+  goctr_calib_bins bins{r.binCount.data(), r.binPos.data(), r.binScoreSum.data()};
+  check(call(&c, &r.m, points ? &pts : nullptr, &bins));
+  r.thr.resize((size_t)r.m.points); r.tps.resize((size_t)r.m.points); r.fps.resize((size_t)r.m.points);
+  return r;
+}
+inline CurveResult CurveMetrics(const float* score, const float* y, int64_t n, const goctr_curve_cfg* cfg = nullptr, int64_t points = 0) {
+  ensure_init();
+  return curveCall(cfg, points, [&](const goctr_curve_cfg* c, goctr_curve_metrics* m, goctr_curve_points* p, goctr_calib_bins* b) {
+    return goctr_metrics_curve(score, y, n, c, m, p, b);
+  });
+}
+inline CurveResult CurveMetrics(const double* score, const double* y, int64_t n, const goctr_curve_cfg* cfg = nullptr, int64_t points = 0) {
+  ensure_init();
+  return curveCall(cfg, points, [&](const goctr_curve_cfg* c, goctr_curve_metrics* m, goctr_curve_points* p, goctr_calib_bins* b) {
+    return goctr_metrics_curve_f64(score, y, n, c, m, p, b);
+  });
+}
 inline double GAUC(const std::vector<float>& pred, const std::vector<float>& y, const std::vector<int32_t>& users) {
   if (y.size() != pred.size() || users.size() != pred.size()) throw std::invalid_argument("GAUC: pred, y and users differ in length");
   return GroupedMetrics(pred.data(), y.data(), users.data(), (int64_t)pred.size()).gauc;
@@ -200,6 +235,13 @@ inline goctr_binary_metrics EvaluateDataset(CtrNet& m, goctr_dataset* d, int bat
   goctr_binary_metrics r{};
   check(goctr_evaluate_dataset(m.Vm(), emb, d, batchSize, &r));
   return r;
+}
+// the same scores through the curve pipeline (goctr_evaluate_dataset_curve)
+inline utils::CurveResult EvaluateDatasetCurve(CtrNet& m, goctr_dataset* d, int batchSize, goctr_emb* emb = nullptr,
+                                               const goctr_curve_cfg* cfg = nullptr, int64_t points = 0) {
+  return utils::curveCall(cfg, points, [&](const goctr_curve_cfg* c, goctr_curve_metrics* r, goctr_curve_points* p, goctr_calib_bins* b) {
+    return goctr_evaluate_dataset_curve(m.Vm(), emb, d, batchSize, c, r, p, b);
+  });
 }
 // the same scores grouped by group [rows] (null: the users a goctr_dataset_create_keys dataset keeps resident); all (may be
 // null): also EvaluateDataset's pooled metrics of the same predict (goctr_evaluate_dataset_grouped)
@@ -530,6 +572,12 @@ class MLPClassifier {
     goctr_binary_metrics r{};
     check(goctr_mlp_evaluate_resident(h_, &r));
     return r;
+  }
+  // the same scores through the curve pipeline (goctr_mlp_evaluate_resident_curve)
+  utils::CurveResult EvaluateResidentCurve(const goctr_curve_cfg* cfg = nullptr, int64_t points = 0) {
+    return utils::curveCall(cfg, points, [&](const goctr_curve_cfg* c, goctr_curve_metrics* r, goctr_curve_points* p, goctr_calib_bins* b) {
+      return goctr_mlp_evaluate_resident_curve(h_, c, r, p, b);
+    });
   }
   // the same scores grouped by group [resident rows] (goctr_mlp_evaluate_resident_grouped)
   goctr_group_metrics EvaluateResidentGrouped(const int32_t* group, int k = 10, goctr_binary_metrics* all = nullptr) {

@@ -250,6 +250,14 @@ class _BaseMLP:
         capi.check(capi.load().goctr_mlp_evaluate_resident(self._h, C.byref(out)))
         return BinaryMetrics.from_c(out)
 
+    def EvaluateResidentCurve(self, bins=10, threshold=0.5, points=0):
+        """EvaluateResident's scores through the curve pipeline (goctr_mlp_evaluate_resident_curve): a metrics.CurveMetrics.
+        Single-output heads only."""
+        from .metrics import CurveCall
+        call = CurveCall(bins, threshold, points)
+        capi.check(capi.load().goctr_mlp_evaluate_resident_curve(self._h, *call.args()))
+        return call.result()
+
     def EvaluateResidentGrouped(self, group, k=10, pooled=False):
         """EvaluateResident's scores grouped by group [resident rows] (goctr_mlp_evaluate_resident_grouped): a
         metrics.GroupMetrics, or (BinaryMetrics, GroupMetrics) with pooled=True.  Single-output heads only."""

@@ -482,6 +482,16 @@ def evaluate_dataset(m: _CtrNet, ds: Dataset, batch, emb: EmbeddingTable | None 
     return BinaryMetrics.from_c(out)
 
 
+def evaluate_dataset_curve(m: _CtrNet, ds: Dataset, batch, emb: EmbeddingTable | None = None, bins=10, threshold=0.5, points=0):
+    """evaluate_dataset's scores, left on the device, through the curve pipeline (goctr_evaluate_dataset_curve): a
+    metrics.CurveMetrics -- the BinaryMetrics as `base`, tp / fp / precision / recall / f1 at `threshold`, average precision, KS,
+    the F1-optimal cut, calibration bins, and up to `points` curve entries"""
+    from .metrics import CurveCall
+    call = CurveCall(bins, threshold, points)
+    capi.check(capi.load().goctr_evaluate_dataset_curve(m._h, emb._h if emb else None, ds._h, C.c_int(batch), *call.args()))
+    return call.result()
+
+
 def evaluate_dataset_grouped(m: _CtrNet, ds: Dataset, batch, group=None, k=10, emb: EmbeddingTable | None = None,
                              pooled=False):
     """predict_dataset's scores, left on the device, grouped by `group` (the user of every row) against the resident labels

@@ -784,6 +784,71 @@ int goctr_evaluate_dataset_grouped(goctr_model* m, goctr_emb* emb, goctr_dataset
 int goctr_mlp_evaluate_resident_grouped(goctr_mlp* p, const int32_t* group, int k, goctr_binary_metrics* all,
                                         goctr_group_metrics* out);
 
+/* ---------------------------------------------------------------- binary curves on the device
+ * The rest of the reference's metrics package over one column of scores: ROCCurve, PrecisionRecallCurve, AveragePrecisionScore
+ * (nn/metrics/ranking.go:71-222; binaryClfCurve's arrays, :13-58) and binary precision / recall / F1
+ * (nn/metrics/classification.go:39-72), plus KS, the F1-optimal cut and calibration bins, out of the ONE sort that
+ * goctr_metrics_binary makes.  Without sample weights.
+ * Rows, labels, ties and NaN scores exactly as in goctr_metrics_binary: a row is positive iff y > 0.5; equal scores form one
+ * threshold group (-0 == +0); a NaN score refuses the call with *out and every array untouched; 1 <= n < 2^31.
+ * Groups g = 0 .. G-1 in score-descending order with pos_g positives and neg_g negatives; tps_g = sum_{h<=g} pos_h,
+ * fps_g = sum_{h<=g} neg_h (binaryClfCurve's tps / fps); thr_g = the group's score widened exactly to double (a zero is +0).
+ * P = positives, N = negatives.  "Rounded" below means the correctly rounded quotient of the two integers.
+ *   base       equal byte for byte to what goctr_metrics_binary(_f64) returns for the same input
+ *   curve      pts (may be NULL; cap == 0: no curve): G <= cap -> all G groups; else (cap >= 2) exactly cap groups
+ *              g_j = floor(j (G-1) / (cap-1)), j = 0 .. cap-1, in integer arithmetic (the first and the last group always among
+ *              them); out->points = entries written to thr / tps / fps, entries beyond stay untouched.  Nothing per row is copied
+ *              to the host either way.
+ *   at cfg.threshold t: a row is predicted positive iff (double)score >= t;  tp, fp, tn, fn exact;  precision = tp / (tp + fp),
+ *              recall = tp / (tp + fn), f1 = 2 tp / (2 tp + fp + fn), each rounded; a zero denominator gives NaN
+ *   average_precision = (sum_g term_g) / P, term_g = (double)pos_g * ((double)tps_g / (double)(tps_g + fps_g)), every operation one
+ *              IEEE double operation (AveragePrecisionScore's uninterpolated sum, ranking.go:212-222); the terms are summed in a
+ *              fixed order (same bits on every call), within (G + 64) 2^-53 of the exact rational; NaN when P == 0
+ *   ks         ks_num = max_g |tps_g N - fps_g P| (exact, < 2^62), ks_den = P N, ks rounded; ks_group = the smallest g attaining it,
+ *              ks_threshold = thr_g.  P == 0 or N == 0: num = den = 0, ks NaN, group -1 (threshold NaN)
+ *   best F1    the g maximising F1_g = 2 tps_g / (tps_g + fps_g + P), compared exactly (128-bit cross-multiplication), ties to the
+ *              smallest g (the highest threshold): best_f1_group, best_f1_threshold = thr_g, best_f1_tp = tps_g, best_f1_fp = fps_g,
+ *              best_f1 rounded.  P == 0: group -1, best_f1 and threshold NaN, tp = fp = 0
+ *   bins       B = cfg.bins (1 .. 1024).  Bin of a score: pd = (double)score; pd < 0 -> 0; pd >= 1 -> B-1; else
+ *              min(B-1, (int)floor(pd * B)) (one double multiplication).  Per bin (goctr_calib_bins, may be NULL; three arrays
+ *              of B entries, all required): count and pos (exact) and score_sum = the double sum of pd over the bin in a fixed
+ *              order (an infinite score is not special: IEEE decides).  Derived on the host from those arrays, in bin order, in
+ *              double:  score_sum = sum_b score_sum_b;  mean_score = score_sum / n;  calibration_ratio = score_sum / P;
+ *              ece = (sum_b |score_sum_b - (double)pos_b|) / n;  ne = base.logloss / H(P / n),
+ *              H(q) = -(q log q + (1-q) log(1-q)), NaN when P == 0 or N == 0
+ * Two calls on the same input return the same bytes in every field and array (no floating-point atomics anywhere).
+ * Refused (-1, goctr_last_error, nothing written): bins outside 1 .. 1024; a NaN threshold; cap == 1 or cap < 0; cap > 0 with a
+ * NULL curve array; a goctr_calib_bins with a NULL array; everything goctr_metrics_binary refuses. */
+typedef struct {
+  int32_t bins;        /* calibration bins, 1 .. 1024 (default 10) */
+  int32_t reserved;    /* 0 */
+  double  threshold;   /* the operating point of tp / fp / precision / recall / f1 (default 0.5) */
+} goctr_curve_cfg;
+typedef struct {
+  goctr_binary_metrics base;
+  double   threshold;  int64_t tp, fp, tn, fn;  double precision, recall, f1;
+  double   average_precision;
+  uint64_t ks_num, ks_den;  double ks;  int64_t ks_group;  double ks_threshold;
+  int64_t  best_f1_group;  double best_f1_threshold;  int64_t best_f1_tp, best_f1_fp;  double best_f1;
+  int64_t  bins;  double score_sum, mean_score, calibration_ratio, ece, ne;
+  int64_t  points;     /* curve entries written (0 without a curve) */
+} goctr_curve_metrics;
+typedef struct { int64_t cap; double* thr; int64_t* tps; int64_t* fps; } goctr_curve_points;     /* host arrays of cap entries */
+typedef struct { int64_t* count; int64_t* pos; double* score_sum; } goctr_calib_bins;            /* host arrays of cfg.bins entries */
+
+void goctr_curve_cfg_default(goctr_curve_cfg* cfg);    /* bins 10, threshold 0.5 */
+/* host arrays score [n], y [n] (copied to the device); cfg NULL = the defaults; pts and bins may be NULL */
+int goctr_metrics_curve(const float* score, const float* y, int64_t n, const goctr_curve_cfg* cfg, goctr_curve_metrics* out,
+                        goctr_curve_points* pts, goctr_calib_bins* bins);
+int goctr_metrics_curve_f64(const double* score, const double* y, int64_t n, const goctr_curve_cfg* cfg, goctr_curve_metrics* out,
+                            goctr_curve_points* pts, goctr_calib_bins* bins);
+/* goctr_evaluate_dataset's scores, left on the device, against d's resident labels */
+int goctr_evaluate_dataset_curve(goctr_model* m, goctr_emb* emb, goctr_dataset* d, int batch, const goctr_curve_cfg* cfg,
+                                 goctr_curve_metrics* out, goctr_curve_points* pts, goctr_calib_bins* bins);
+/* goctr_mlp_evaluate_resident's scores (float64) against the resident Y; a softmax head is refused */
+int goctr_mlp_evaluate_resident_curve(goctr_mlp* p, const goctr_curve_cfg* cfg, goctr_curve_metrics* out, goctr_curve_points* pts,
+                                      goctr_calib_bins* bins);
+
 #ifdef __cplusplus
 }
 #endif
