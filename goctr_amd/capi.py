@@ -96,6 +96,47 @@ class CalibBins(C.Structure):
     _fields_ = [("count", C.POINTER(C.c_int64)), ("pos", C.POINTER(C.c_int64)), ("score_sum", C.POINTER(C.c_double))]
 
 
+class RegressionMetrics(C.Structure):
+    """goctr_regression_metrics (include/goctr.h)"""
+    _fields_ = [("n", C.c_int64), ("k", C.c_int64), ("constant_columns", C.c_int64), ("mse_uniform", C.c_double),
+                ("mae_uniform", C.c_double), ("r2_uniform", C.c_double), ("r2_mlp_uniform", C.c_double),
+                ("r2_variance_weighted", C.c_double), ("max_abs", C.c_double)]
+
+
+class RegressionCol(C.Structure):
+    """goctr_regression_col (include/goctr.h)"""
+    _fields_ = [(f, C.c_double) for f in ("sum_y", "mean_y", "ss_res", "sum_abs", "ss_tot", "max_abs", "mse", "mae", "r2",
+                                          "r2_mlp")]
+
+
+class ConfusionMetrics(C.Structure):
+    """goctr_confusion_metrics (include/goctr.h)"""
+    _fields_ = [("n", C.c_int64), ("classes", C.c_int64), ("correct", C.c_int64), ("beta", C.c_double), ("accuracy", C.c_double),
+                ("precision_macro", C.c_double), ("recall_macro", C.c_double), ("f_macro", C.c_double),
+                ("precision_micro", C.c_double), ("recall_micro", C.c_double), ("f_micro", C.c_double),
+                ("precision_weighted", C.c_double), ("recall_weighted", C.c_double), ("f_weighted", C.c_double)]
+
+
+class ClassStat(C.Structure):
+    """goctr_class_stat (include/goctr.h)"""
+    _fields_ = [("support", C.c_int64), ("predicted", C.c_int64), ("tp", C.c_int64), ("precision", C.c_double),
+                ("recall", C.c_double), ("f", C.c_double), ("auc_num", C.c_uint64), ("auc_den", C.c_uint64), ("auc", C.c_double),
+                ("ap", C.c_double)]
+
+
+class MulticlassCfg(C.Structure):
+    """goctr_multiclass_cfg (include/goctr.h)"""
+    _fields_ = [("top_k", C.c_int32), ("ovr", C.c_int32), ("beta", C.c_double)]
+
+
+class MulticlassMetrics(C.Structure):
+    """goctr_multiclass_metrics (include/goctr.h)"""
+    _fields_ = [("conf", ConfusionMetrics), ("top_k", C.c_int64), ("topk_correct", C.c_int64), ("topk_accuracy", C.c_double),
+                ("logloss", C.c_double), ("multi_label_rows", C.c_int64), ("ovr", C.c_int64), ("auc_classes", C.c_int64),
+                ("auc_macro", C.c_double), ("auc_weighted", C.c_double), ("auc_micro", C.c_double), ("ap_macro", C.c_double),
+                ("ap_weighted", C.c_double), ("ap_micro", C.c_double)]
+
+
 class NegSampleCfg(C.Structure):
     """goctr_negsample_cfg (include/goctr.h)"""
     _fields_ = [("n_neg", C.c_int32), ("weighting", C.c_int32), ("which", C.c_int32), ("max_tries", C.c_int32),
@@ -151,6 +192,9 @@ SYMBOLS = [
     "goctr_mlp_evaluate_resident_grouped",
     "goctr_curve_cfg_default", "goctr_metrics_curve", "goctr_metrics_curve_f64", "goctr_evaluate_dataset_curve",
     "goctr_mlp_evaluate_resident_curve",
+    "goctr_metrics_regression", "goctr_metrics_regression_f64", "goctr_metrics_confusion", "goctr_multiclass_cfg_default",
+    "goctr_metrics_multiclass", "goctr_metrics_multiclass_f64", "goctr_mlp_evaluate_resident_regression",
+    "goctr_mlp_evaluate_resident_multiclass",
     "goctr_emb_load_w2v", "goctr_w2v_copy_word_vectors", "goctr_searcher_create_from_w2v", "goctr_searcher_load_w2v",
     "goctr_corpus_append_ubcache",
     "goctr_negsample_cfg_default", "goctr_samples_create", "goctr_samples_destroy", "goctr_samples_info", "goctr_samples_export",
@@ -179,7 +223,8 @@ def load() -> C.CDLL:
         for name in ("goctr_model_destroy", "goctr_emb_destroy", "goctr_dataset_destroy", "goctr_mlp_destroy",
                      "goctr_w2v_destroy", "goctr_searcher_destroy", "goctr_ubcache_destroy", "goctr_recsys_destroy", "goctr_train_cfg_default", "goctr_mlp_cfg_default",
                      "goctr_w2v_cfg_default", "goctr_negsample_cfg_default", "goctr_samples_destroy", "goctr_topn_cfg_default",
-                     "goctr_itemcf_cfg_default", "goctr_recall_cfg_default", "goctr_itemcf_destroy", "goctr_curve_cfg_default"):
+                     "goctr_itemcf_cfg_default", "goctr_recall_cfg_default", "goctr_itemcf_destroy", "goctr_curve_cfg_default",
+                     "goctr_multiclass_cfg_default"):
             getattr(_lib, name).restype = None
         _bm = C.POINTER(BinaryMetrics)
         _lib.goctr_metrics_binary.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, _bm]
@@ -199,6 +244,16 @@ def load() -> C.CDLL:
         _lib.goctr_metrics_curve_f64.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64, _cc, _cm, _cp, _cb]
         _lib.goctr_evaluate_dataset_curve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _cc, _cm, _cp, _cb]
         _lib.goctr_mlp_evaluate_resident_curve.argtypes = [C.c_void_p, _cc, _cm, _cp, _cb]
+        _rm, _rc, _fm, _cs = C.POINTER(RegressionMetrics), C.POINTER(RegressionCol), C.POINTER(ConfusionMetrics), C.POINTER(ClassStat)
+        _mc, _mm, _cells = C.POINTER(MulticlassCfg), C.POINTER(MulticlassMetrics), C.POINTER(C.c_uint64)
+        _lib.goctr_metrics_regression.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, C.c_int, _rm, _rc]
+        _lib.goctr_metrics_regression_f64.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64, C.c_int, _rm, _rc]
+        _lib.goctr_metrics_confusion.argtypes = [_i32, _i32, C.c_int64, C.c_int, C.c_double, _fm, _cs, _cells]
+        _lib.goctr_multiclass_cfg_default.argtypes = [_mc]
+        _lib.goctr_metrics_multiclass.argtypes = [C.POINTER(C.c_float), _i32, C.c_int64, C.c_int, _mc, _mm, _cs, _cells]
+        _lib.goctr_metrics_multiclass_f64.argtypes = [C.POINTER(C.c_double), _i32, C.c_int64, C.c_int, _mc, _mm, _cs, _cells]
+        _lib.goctr_mlp_evaluate_resident_regression.argtypes = [C.c_void_p, _rm, _rc]
+        _lib.goctr_mlp_evaluate_resident_multiclass.argtypes = [C.c_void_p, _mc, _mm, _cs, _cells]
         _i64 = C.POINTER(C.c_int64)
         _lib.goctr_ubcache_batch_set.argtypes = [C.c_void_p, C.c_int64, _i32, _i64, _i32, _i64]
         _lib.goctr_ubcache_delete.argtypes = [C.c_void_p, C.c_int64, _i32]
@@ -337,6 +392,14 @@ def default_train_cfg(**kw) -> TrainCfg:
 def default_curve_cfg(**kw) -> CurveCfg:
     c = CurveCfg()
     load().goctr_curve_cfg_default(C.byref(c))
+    for k, v in kw.items():
+        setattr(c, k, v)
+    return c
+
+
+def default_multiclass_cfg(**kw) -> MulticlassCfg:
+    c = MulticlassCfg()
+    load().goctr_multiclass_cfg_default(C.byref(c))
     for k, v in kw.items():
         setattr(c, k, v)
     return c

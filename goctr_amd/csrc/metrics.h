@@ -1,6 +1,7 @@
 // metrics.h -- interface of metrics.hip (exact binary ROC-AUC, accuracy and log-loss of scores resident on the device), of
 // metrics_group.hip (the per-group ranking metrics over the same scores) and of metrics_curve.hip (curve points, AP, KS, best F1
-// and calibration bins out of metrics.hip's sorted order), and the device helpers the pipelines share.
+// and calibration bins out of metrics.hip's sorted order) and of metrics_multi.hip (regression sums per column, the confusion matrix
+// and the multi-class row metrics), and the device helpers the pipelines share.
 #pragma once
 #include <cstdint>
 
@@ -40,6 +41,28 @@ int metrics_curve_dev(const double* score, const float* y, int64_t n, const goct
                       goctr_curve_points* pts, goctr_calib_bins* bins, const char* who);
 // the argument checks alone (bins, threshold, cap, array pointers): for entry points that predict before they measure
 int metrics_curve_check(const goctr_curve_cfg* cfg, const goctr_curve_points* pts, const goctr_calib_bins* bins, const char* who);
+
+// Multi-output metrics (metrics_multi.hip) of arrays already in device memory of the calling thread's engine; the arguments are
+// checked here and the outputs (HOST; per_col / per_class / cm may be null) are filled only on success.
+// regression: pred, y [n][K] row-major.  The three instantiations: float / float (goctr_metrics_regression), double / double
+// (goctr_metrics_regression_f64), double / float (goctr_mlp_evaluate_resident_regression).
+int metrics_regression_dev(const float* pred, const float* y, int64_t n, int K, goctr_regression_metrics* out,
+                           goctr_regression_col* per_col, const char* who);
+int metrics_regression_dev(const double* pred, const double* y, int64_t n, int K, goctr_regression_metrics* out,
+                           goctr_regression_col* per_col, const char* who);
+int metrics_regression_dev(const double* pred, const float* y, int64_t n, int K, goctr_regression_metrics* out,
+                           goctr_regression_col* per_col, const char* who);
+// multi-class: proba [n][C] row-major, label [n]; multi_label_rows goes into out as it is
+int metrics_multiclass_dev(const float* proba, const int32_t* label, int64_t n, int C, const goctr_multiclass_cfg* cfg,
+                           int64_t multi_label_rows, goctr_multiclass_metrics* out, goctr_class_stat* per_class, uint64_t* cm,
+                           const char* who);
+int metrics_multiclass_dev(const double* proba, const int32_t* label, int64_t n, int C, const goctr_multiclass_cfg* cfg,
+                           int64_t multi_label_rows, goctr_multiclass_metrics* out, goctr_class_stat* per_class, uint64_t* cm,
+                           const char* who);
+// the argument checks of the multi-class call alone: for entry points that predict before they measure
+int metrics_multiclass_check(int C, const goctr_multiclass_cfg* cfg, const char* who);
+// label[r] = the first maximum of Y's row r (Y [n][C] on the device); *multi_label_rows = rows that are not exactly one-hot
+int metrics_onehot_labels_dev(const float* Y, int64_t n, int C, int32_t* label, int64_t* multi_label_rows, const char* who);
 
 // The front both pooled pipelines share (metrics.hip): key build, sort, the two scans, the AUC terms and the key build's partials,
 // all queued on the engine's main stream, nothing copied back.  What it leaves on the device stays valid until the engine's next

@@ -430,9 +430,10 @@ int predict_rows(goctr_mlp* p, const float* X, int64_t rows, float* y32, double*
 }
 
 // predict_rows' float64 path over the resident rows (p->Xr): the same chunks and kernels, so the same bits as goctr_mlp_predict64
-// on those rows; column 0 of the head lands in y_dev [p->rows] on the device
-int predict_resident64(goctr_mlp* p, double* y_dev) {
-  const int L = p->nl, F = p->units[0], no = p->units[L];
+// on those rows; column 0 of the head lands in y_dev [p->rows] on the device, or with all_columns every column in
+// y_dev [p->rows][units[last]]
+int predict_resident64(goctr_mlp* p, double* y_dev, bool all_columns) {
+  const int L = p->nl, F = p->units[0], no = p->units[L], cols = all_columns ? no : 1;
   const int CHUNK = 16384;
   const int64_t rows = p->rows;
   if (ensure_ws(p, (int)std::min<int64_t>(rows, CHUNK))) return -1;
@@ -443,7 +444,7 @@ int predict_resident64(goctr_mlp* p, double* y_dev) {
                        (MlpState*)nullptr, n);
     GOCTR_HIP(hipGetLastError());
     if (forward(p, n, false)) return -1;
-    GOCTR_HIP(hipMemcpy2DAsync(y_dev + s0, sizeof(double), p->A[L].p, sizeof(double) * p->up[L], sizeof(double), n,
+    GOCTR_HIP(hipMemcpy2DAsync(y_dev + s0 * cols, sizeof(double) * cols, p->A[L].p, sizeof(double) * p->up[L], sizeof(double) * cols, n,
                                hipMemcpyDeviceToDevice, engine().stream));
   }
   return 0;

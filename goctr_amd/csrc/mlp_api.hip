@@ -307,4 +307,35 @@ int goctr_mlp_evaluate_resident_grouped(goctr_mlp* p, const int32_t* group, int 
   return 0;
 }
 
+int goctr_mlp_evaluate_resident_regression(goctr_mlp* p, goctr_regression_metrics* out, goctr_regression_col* per_col) {
+  GOCTR_ENTER_H(p);
+  const char* who = "goctr_mlp_evaluate_resident_regression";
+  GOCTR_CHECK(p && out, "%s: bad arguments", who);
+  GOCTR_CHECK(p->rows > 0, "%s: upload rows first", who);
+  if (metrics_check_rows(p->rows, who)) return -1;
+  std::lock_guard<std::mutex> lk(p->mu);
+  const int no = p->units[p->nl];
+  DevBuf<double> score;
+  if (score.alloc((size_t)p->rows * no, false) || predict_resident64(p, score.p, true)) return -1;
+  return metrics_regression_dev(score.p, p->Yr.p, p->rows, no, out, per_col, who);
+}
+
+int goctr_mlp_evaluate_resident_multiclass(goctr_mlp* p, const goctr_multiclass_cfg* cfg, goctr_multiclass_metrics* out,
+                                           goctr_class_stat* per_class, uint64_t* cm) {
+  GOCTR_ENTER_H(p);
+  const char* who = "goctr_mlp_evaluate_resident_multiclass";
+  GOCTR_CHECK(p && out, "%s: bad arguments", who);
+  GOCTR_CHECK(p->rows > 0, "%s: upload rows first", who);
+  const int no = p->units[p->nl];
+  GOCTR_CHECK(no >= 2, "%s: multi-class metrics need at least 2 output units (this head has %d)", who, no);
+  if (metrics_check_rows(p->rows, who) || metrics_multiclass_check(no, cfg, who)) return -1;
+  std::lock_guard<std::mutex> lk(p->mu);
+  DevBuf<double> score;
+  DevBuf<int32_t> label;
+  int64_t multi = 0;
+  if (label.alloc((size_t)p->rows, false) || metrics_onehot_labels_dev(p->Yr.p, p->rows, no, label.p, &multi, who)) return -1;
+  if (score.alloc((size_t)p->rows * no, false) || predict_resident64(p, score.p, true)) return -1;
+  return metrics_multiclass_dev(score.p, label.p, p->rows, no, cfg, multi, out, per_class, cm, who);
+}
+
 }  // extern "C"

@@ -97,5 +97,6 @@ int prepare_resident(goctr_mlp* p);
 int train_step_resident(goctr_mlp* p, bool use_state, long long start, bool generic = false, int valid = -1);
 int run_fused_steps(goctr_mlp* p, int n_steps);
 int predict_rows(goctr_mlp* p, const float* X, int64_t rows, float* y32, double* y64);
-// the resident rows' head column 0 in float64, left on the device in y_dev [p->rows] (goctr_mlp_evaluate_resident)
-int predict_resident64(goctr_mlp* p, double* y_dev);
+// the resident rows' head column 0 in float64, left on the device in y_dev [p->rows] (goctr_mlp_evaluate_resident); all_columns:
+// every column, y_dev [p->rows][units[last]] (goctr_mlp_evaluate_resident_regression / _multiclass)
+int predict_resident64(goctr_mlp* p, double* y_dev, bool all_columns = false);

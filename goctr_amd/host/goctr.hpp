@@ -139,6 +139,67 @@ inline CurveResult CurveMetrics(const double* score, const double* y, int64_t n,
     return goctr_metrics_curve_f64(score, y, n, c, m, p, b);
   });
 }
+// the multi-output metrics (goctr_metrics_regression / _confusion / _multiclass) with their arrays
+struct RegressionResult {
+  goctr_regression_metrics m{};
+  std::vector<goctr_regression_col> cols;
+};
+struct ConfusionResult {
+  goctr_confusion_metrics m{};
+  std::vector<goctr_class_stat> perClass;
+  std::vector<uint64_t> cm;                    // [classes][classes], cm[t * classes + p]
+};
+struct MulticlassResult {
+  goctr_multiclass_metrics m{};
+  std::vector<goctr_class_stat> perClass;
+  std::vector<uint64_t> cm;
+};
+inline size_t classRoom(int classes) { return (size_t)std::min(std::max(classes, 1), 1024); }
+template <class Call>
+inline RegressionResult regressionCall(int k, Call call) {
+  RegressionResult r;
+  r.cols.resize(classRoom(k));
+  check(call(&r.m, r.cols.data()));
+  return r;
+}
+template <class Call>
+inline MulticlassResult multiclassCall(int classes, const goctr_multiclass_cfg* cfg, Call call) {
+  MulticlassResult r;
+  r.perClass.resize(classRoom(classes));
+  r.cm.resize(classRoom(classes) * classRoom(classes));
+  check(call(cfg, &r.m, r.perClass.data(), r.cm.data()));
+  return r;
+}
+inline RegressionResult RegressionMetrics(const float* pred, const float* y, int64_t n, int k) {
+  ensure_init();
+  return regressionCall(k, [&](goctr_regression_metrics* m, goctr_regression_col* c) { return goctr_metrics_regression(pred, y, n, k, m, c); });
+}
+inline RegressionResult RegressionMetrics(const double* pred, const double* y, int64_t n, int k) {
+  ensure_init();
+  return regressionCall(k, [&](goctr_regression_metrics* m, goctr_regression_col* c) { return goctr_metrics_regression_f64(pred, y, n, k, m, c); });
+}
+inline ConfusionResult ConfusionMetrics(const int32_t* label, const int32_t* pred, int64_t n, int classes, double beta = 1.0) {
+  ensure_init();
+  ConfusionResult r;
+  r.perClass.resize(classRoom(classes));
+  r.cm.resize(classRoom(classes) * classRoom(classes));
+  check(goctr_metrics_confusion(label, pred, n, classes, beta, &r.m, r.perClass.data(), r.cm.data()));
+  return r;
+}
+inline MulticlassResult MulticlassMetrics(const float* proba, const int32_t* label, int64_t n, int classes,
+                                          const goctr_multiclass_cfg* cfg = nullptr) {
+  ensure_init();
+  return multiclassCall(classes, cfg, [&](const goctr_multiclass_cfg* c, goctr_multiclass_metrics* m, goctr_class_stat* pc, uint64_t* cm) {
+    return goctr_metrics_multiclass(proba, label, n, classes, c, m, pc, cm);
+  });
+}
+inline MulticlassResult MulticlassMetrics(const double* proba, const int32_t* label, int64_t n, int classes,
+                                          const goctr_multiclass_cfg* cfg = nullptr) {
+  ensure_init();
+  return multiclassCall(classes, cfg, [&](const goctr_multiclass_cfg* c, goctr_multiclass_metrics* m, goctr_class_stat* pc, uint64_t* cm) {
+    return goctr_metrics_multiclass_f64(proba, label, n, classes, c, m, pc, cm);
+  });
+}
 inline double GAUC(const std::vector<float>& pred, const std::vector<float>& y, const std::vector<int32_t>& users) {
   if (y.size() != pred.size() || users.size() != pred.size()) throw std::invalid_argument("GAUC: pred, y and users differ in length");
   return GroupedMetrics(pred.data(), y.data(), users.data(), (int64_t)pred.size()).gauc;
@@ -584,6 +645,18 @@ class MLPClassifier {
     goctr_group_metrics r{};
     check(goctr_mlp_evaluate_resident_grouped(h_, group, k, all, &r));
     return r;
+  }
+  // every column of the head against the resident Y (goctr_mlp_evaluate_resident_regression; `units` = the head's output units)
+  utils::RegressionResult EvaluateResidentRegression(int units) {
+    return utils::regressionCall(units, [&](goctr_regression_metrics* m, goctr_regression_col* c) {
+      return goctr_mlp_evaluate_resident_regression(h_, m, c);
+    });
+  }
+  // the head's probabilities against the first maximum of each resident Y row (goctr_mlp_evaluate_resident_multiclass)
+  utils::MulticlassResult EvaluateResidentMulticlass(int units, const goctr_multiclass_cfg* cfg = nullptr) {
+    return utils::multiclassCall(units, cfg, [&](const goctr_multiclass_cfg* c, goctr_multiclass_metrics* m, goctr_class_stat* pc, uint64_t* cm) {
+      return goctr_mlp_evaluate_resident_multiclass(h_, c, m, pc, cm);
+    });
   }
 
  private:

@@ -8,6 +8,11 @@ Float32 scores take the float32 ABI (RocAuc32's inputs), anything else the float
 The rest of nn/metrics -- ROCCurve, PrecisionRecallCurve, AveragePrecisionScore (ranking.go:71-222), PrecisionScore / RecallScore /
 F1Score (classification.go:39-72) -- and KS / ECE sit over goctr_metrics_curve: the device returns binaryClfCurve's integer
 arrays (tps, fps, thresholds), the reference's float post-processing of them is restated here operation for operation.
+
+The multi-output functions -- R2Score / MeanSquaredError / MeanAbsoluteError (regression.go), AccuracyScore / ConfusionMatrix /
+PrecisionRecallFScoreSupport / FBetaScore (classification.go) and the `average` argument of ROCAUCScore / AveragePrecisionScore
+(base.go:12-87) -- sit over goctr_metrics_regression / _confusion / _multiclass: the device returns the column sums and the integer
+confusion matrix, the post-processing is the pure *_from_* functions below.  sampleWeight is not supported anywhere (ValueError).
 """
 from __future__ import annotations
 
@@ -203,33 +208,49 @@ def PrecisionRecallCurve(yTrue, probasPred, posLabel=1.0):
     return pr_from_curve(*_full_curve(yTrue, probasPred, posLabel))
 
 
-def AveragePrecisionScore(yTrue, yScore) -> float:
-    """metrics.AveragePrecisionScore (ranking.go:212-222) of one column: the reference's own float sum over its PR curve (the
-    device's average_precision is the same quantity summed per group in a fixed order)"""
-    p, r, _ = PrecisionRecallCurve(yTrue, yScore, 1.0)
-    return ap_from_pr(p, r)
+def AveragePrecisionScore(yTrue, yScore, average=None, sampleWeight=None) -> float:
+    """metrics.AveragePrecisionScore (ranking.go:212-222).  average=None: one column, the reference's own float sum over its PR
+    curve (the device's average_precision is the same quantity summed per group in a fixed order).  average = "macro" /
+    "weighted" / "micro": averageBinaryScore (base.go:12-87) over the columns of an indicator matrix yTrue, each column's AP from
+    the device."""
+    _no_weights(sampleWeight)
+    if average is None:
+        p, r, _ = PrecisionRecallCurve(yTrue, yScore, 1.0)
+        return ap_from_pr(p, r)
+    return _average_binary_score("ap", yTrue, yScore, average)
 
 
 def _at_labels(yTrue, yPred):
     return curve_metrics(np.asarray(yPred, np.float64), np.asarray(yTrue, np.float64), threshold=0.5)
 
 
-def PrecisionScore(yTrue, yPred) -> float:
-    """metrics.PrecisionScore for the binary case (the positive class; predicted labels 0 / 1): tp / (tp + fp), 0 when nothing
-    is predicted positive (classification.go:84-86)"""
+def PrecisionScore(yTrue, yPred, average=None, sampleWeight=None) -> float:
+    """metrics.PrecisionScore.  average=None: the binary case (the positive class; predicted labels 0 / 1): tp / (tp + fp), 0 when
+    nothing is predicted positive (classification.go:84-86).  average = "macro" / "micro" / "weighted": classification.go:39-42."""
+    _no_weights(sampleWeight)
+    if average is not None:
+        return PrecisionRecallFScoreSupport(yTrue, yPred, 1.0, None, -1, average)[0]
     m = _at_labels(yTrue, yPred)
     return m.precision if m.tp + m.fp else 0.0
 
 
-def RecallScore(yTrue, yPred) -> float:
-    """metrics.RecallScore for the binary case: tp / (tp + fn), 0 without positives (classification.go:87-89)"""
+def RecallScore(yTrue, yPred, average=None, sampleWeight=None) -> float:
+    """metrics.RecallScore.  average=None: the binary case, tp / (tp + fn), 0 without positives (classification.go:87-89);
+    else classification.go:46-49"""
+    _no_weights(sampleWeight)
+    if average is not None:
+        return PrecisionRecallFScoreSupport(yTrue, yPred, 1.0, None, -1, average)[1]
     m = _at_labels(yTrue, yPred)
     return m.recall if m.tp + m.fn else 0.0
 
 
-def F1Score(yTrue, yPred) -> float:
-    """metrics.F1Score for the binary case, by the reference's float formula 2 p r / (p + r) over the rounded precision and
-    recall (classification.go:91-95); CurveMetrics.f1 is the correctly rounded 2 tp / (2 tp + fp + fn)"""
+def F1Score(yTrue, yPred, average=None, sampleWeight=None) -> float:
+    """metrics.F1Score.  average=None: the binary case, by the reference's float formula 2 p r / (p + r) over the rounded
+    precision and recall (classification.go:91-95); CurveMetrics.f1 is the correctly rounded 2 tp / (2 tp + fp + fn).  Else
+    FBetaScore with beta 1 (classification.go:53-56)."""
+    _no_weights(sampleWeight)
+    if average is not None:
+        return FBetaScore(yTrue, yPred, 1.0, average)
     m = _at_labels(yTrue, yPred)
     p = m.precision if m.tp + m.fp else 0.0
     r = m.recall if m.tp + m.fn else 0.0
@@ -341,3 +362,371 @@ def Accuracy32(pred, y) -> np.float32:
     """utils.Accuracy32: the share of rows with math.Round(float64(p - y)) == 0, p - y in float32"""
     m = binary_metrics(np.asarray(pred, np.float32), np.asarray(y, np.float32))
     return accuracy32_from_hits(m.correct, m.n)
+
+
+# ---------------------------------------------------------------- multi-output metrics (goctr_metrics_regression / _confusion / _multiclass)
+REGRESSION_COL_DTYPE = np.dtype([(f, np.float64) for f, _ in capi.RegressionCol._fields_])          # goctr_regression_col
+CLASS_STAT_DTYPE = np.dtype([("support", np.int64), ("predicted", np.int64), ("tp", np.int64), ("precision", np.float64),
+                             ("recall", np.float64), ("f", np.float64), ("auc_num", np.uint64), ("auc_den", np.uint64),
+                             ("auc", np.float64), ("ap", np.float64)])                               # goctr_class_stat
+
+
+def _no_weights(sampleWeight):
+    if sampleWeight is not None:
+        raise ValueError("sampleWeight is not supported by the device metrics")
+
+
+@dataclass(frozen=True, eq=False)
+class RegressionMetrics:
+    """goctr_regression_metrics with its per-column array `cols` (REGRESSION_COL_DTYPE: the device's sum_y, mean_y, ss_res,
+    sum_abs, ss_tot, max_abs and the derived mse, mae, r2, r2_mlp).  raw: the C struct's bytes."""
+    n: int
+    k: int
+    constant_columns: int
+    mse_uniform: float
+    mae_uniform: float
+    r2_uniform: float
+    r2_mlp_uniform: float
+    r2_variance_weighted: float
+    max_abs: float
+    cols: np.ndarray
+    raw: bytes
+
+    def tobytes(self) -> bytes:
+        return self.raw + self.cols.tobytes()
+
+
+def _regression_result(out, cols) -> RegressionMetrics:
+    return RegressionMetrics(*(getattr(out, f) for f, _ in capi.RegressionMetrics._fields_), cols, bytes(out))
+
+
+def regression_metrics(pred, y) -> RegressionMetrics:
+    """the column sums of pred, y [n][K] (one-dimensional input: one column) on the device and what regression.go / r2Score64
+    derive from them (goctr_metrics_regression for float32 pred, else _f64)"""
+    pred = np.asarray(pred)
+    L = capi.load()
+    if pred.dtype == np.float32:
+        fn, ty, dt = L.goctr_metrics_regression, C.c_float, np.float32
+    else:
+        fn, ty, dt = L.goctr_metrics_regression_f64, C.c_double, np.float64
+    p = np.ascontiguousarray(pred, dt)
+    p = p.reshape(p.shape[0], -1) if p.ndim else p.reshape(1, 1)
+    t = np.ascontiguousarray(y, dt).reshape(-1) if np.ndim(y) <= 1 else np.ascontiguousarray(y, dt)
+    t = t.reshape(t.shape[0], -1)
+    if p.shape != t.shape:
+        raise ValueError(f"pred is {p.shape} but y is {t.shape}")
+    out = capi.RegressionMetrics()
+    cols = np.zeros(max(p.shape[1], 1), REGRESSION_COL_DTYPE)
+    capi.check(fn(capi.ptr(p, ty), capi.ptr(t, ty), p.shape[0], C.c_int(p.shape[1]), C.byref(out),
+                  cols.ctypes.data_as(C.POINTER(capi.RegressionCol))))
+    return _regression_result(out, cols)
+
+
+@dataclass(frozen=True, eq=False)
+class ConfusionMetrics:
+    """goctr_confusion_metrics with per_class (CLASS_STAT_DTYPE, C entries) and cm (uint64 [C][C], cm[t][p]).  raw: the C
+    struct's bytes."""
+    n: int
+    classes: int
+    correct: int
+    beta: float
+    accuracy: float
+    precision_macro: float
+    recall_macro: float
+    f_macro: float
+    precision_micro: float
+    recall_micro: float
+    f_micro: float
+    precision_weighted: float
+    recall_weighted: float
+    f_weighted: float
+    per_class: np.ndarray
+    cm: np.ndarray
+    raw: bytes
+
+    def tobytes(self) -> bytes:
+        return self.raw + self.per_class.tobytes() + self.cm.tobytes()
+
+
+def _confusion_result(out, per_class, cm) -> ConfusionMetrics:
+    return ConfusionMetrics(*(getattr(out, f) for f, _ in capi.ConfusionMetrics._fields_), per_class, cm, bytes(out))
+
+
+def class_ids(a, n, what) -> np.ndarray:
+    """a class column as the contiguous int32 [n] the C ABI takes (values outside int32 are refused, not wrapped)"""
+    g = np.asarray(a).ravel()
+    if g.size != n:
+        raise ValueError(f"{n} rows but {g.size} {what}")
+    if g.dtype != np.int32:
+        if g.size and (g.min() < -2 ** 31 or g.max() > 2 ** 31 - 1):
+            raise ValueError(f"{what} must fit int32")
+        g = g.astype(np.int32)
+    return np.ascontiguousarray(g)
+
+
+def confusion_metrics(label, pred, classes, beta=1.0) -> ConfusionMetrics:
+    """the confusion matrix of class indices label, pred [n] in [0, classes) on the device (goctr_metrics_confusion) with the
+    per-class precision / recall / F-beta / support and their macro, micro and support-weighted means"""
+    lab = class_ids(label, np.asarray(label).size, "labels")
+    prd = class_ids(pred, lab.size, "predictions")
+    Cn = int(classes)
+    room = min(max(Cn, 1), 1024)
+    out, per_class, cm = capi.ConfusionMetrics(), np.zeros(room, CLASS_STAT_DTYPE), np.zeros((room, room), np.uint64)
+    capi.check(capi.load().goctr_metrics_confusion(capi.ptr(lab, C.c_int32), capi.ptr(prd, C.c_int32), lab.size, C.c_int(Cn),
+                                                   C.c_double(beta), C.byref(out),
+                                                   per_class.ctypes.data_as(C.POINTER(capi.ClassStat)), capi.ptr(cm, C.c_uint64)))
+    return _confusion_result(out, per_class, cm)
+
+
+@dataclass(frozen=True, eq=False)
+class MulticlassMetrics:
+    """goctr_multiclass_metrics: conf (a ConfusionMetrics of (label, arg-max) with per_class and cm; per_class carries the
+    one-vs-rest auc_num / auc_den / auc / ap with ovr), top-k accuracy, log-loss and the averaged one-vs-rest AUC / AP (NaN
+    without ovr).  raw: the C struct's bytes."""
+    conf: ConfusionMetrics
+    top_k: int
+    topk_correct: int
+    topk_accuracy: float
+    logloss: float
+    multi_label_rows: int
+    ovr: int
+    auc_classes: int
+    auc_macro: float
+    auc_weighted: float
+    auc_micro: float
+    ap_macro: float
+    ap_weighted: float
+    ap_micro: float
+    raw: bytes
+
+    def tobytes(self) -> bytes:
+        return self.raw + self.conf.per_class.tobytes() + self.conf.cm.tobytes()
+
+
+class MulticlassCall:
+    """the cfg / out / per_class / cm arguments of one goctr_*_multiclass call over `classes` classes, and its result"""
+
+    def __init__(self, classes, top_k=1, beta=1.0, ovr=False):
+        self.cfg = capi.default_multiclass_cfg(top_k=int(top_k), beta=float(beta), ovr=1 if ovr else 0)
+        self.out = capi.MulticlassMetrics()
+        room = min(max(int(classes), 1), 1024)
+        self.per_class, self.cm = np.zeros(room, CLASS_STAT_DTYPE), np.zeros((room, room), np.uint64)
+
+    def args(self):
+        return (C.byref(self.cfg), C.byref(self.out), self.per_class.ctypes.data_as(C.POINTER(capi.ClassStat)),
+                capi.ptr(self.cm, C.c_uint64))
+
+    def result(self) -> MulticlassMetrics:
+        o = self.out
+        scalars = [getattr(o, f) for f, _ in capi.MulticlassMetrics._fields_[1:]]
+        return MulticlassMetrics(_confusion_result(o.conf, self.per_class, self.cm), *scalars, bytes(o))
+
+
+def multiclass_metrics(proba, label, top_k=1, beta=1.0, ovr=False) -> MulticlassMetrics:
+    """arg-max accuracy, top-k accuracy, log-loss and the confusion figures of probabilities proba [n][C] against class indices
+    label [n] on the device (goctr_metrics_multiclass for float32 proba, else _f64); ovr: also the one-vs-rest AUC / AP of
+    every class and their macro / weighted / micro means"""
+    proba = np.asarray(proba)
+    L = capi.load()
+    if proba.dtype == np.float32:
+        fn, ty, dt = L.goctr_metrics_multiclass, C.c_float, np.float32
+    else:
+        fn, ty, dt = L.goctr_metrics_multiclass_f64, C.c_double, np.float64
+    p = np.ascontiguousarray(proba, dt)
+    if p.ndim != 2:
+        raise ValueError("proba must be [n][C]")
+    lab = class_ids(label, p.shape[0], "labels")
+    call = MulticlassCall(p.shape[1], top_k, beta, ovr)
+    capi.check(fn(capi.ptr(p, ty), capi.ptr(lab, C.c_int32), p.shape[0], C.c_int(p.shape[1]), *call.args()))
+    return call.result()
+
+
+# --- pure post-processing: functions of the device's integers and sums alone
+def multioutput_from_scores(scores, multioutput, weights=None):
+    """regression.go's `multioutput` switch over per-column scores: "raw_values" -> the array; "variance_weighted" (R2Score only:
+    weights = the columns' ss_tot) -> sum w x / sum w; anything else -> the uniform average, summed in column order"""
+    scores = np.asarray(scores, np.float64)
+    if multioutput == "raw_values":
+        return scores.copy()
+    if multioutput == "variance_weighted" and weights is not None:
+        num = den = 0.0
+        for x, w_ in zip(scores, np.asarray(weights, np.float64)):
+            num += float(w_) * float(x)
+            den += float(w_)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return float(np.float64(num) / np.float64(den))
+    acc = 0.0
+    for x in scores:
+        acc += float(x)
+    return acc / scores.size
+
+
+def r2_from_sums(ss_res, ss_tot, multioutput="uniform_average"):
+    """R2Score (regression.go:110-127) from the columns' ss_res and ss_tot: 1 - ss_res / max(ss_tot, 1e-20) per column"""
+    ss_res, ss_tot = np.asarray(ss_res, np.float64).ravel(), np.asarray(ss_tot, np.float64).ravel()
+    r2 = 1.0 - ss_res / np.maximum(ss_tot, 1e-20)
+    return multioutput_from_scores(r2, multioutput, ss_tot)
+
+
+def fbeta_from_pr(beta, precision, recall) -> float:
+    """classification.go:91-95 operation for operation"""
+    beta2 = float(beta) * float(beta)
+    d = beta2 * precision + recall
+    return (1.0 + beta2) * precision * recall / d if d > 0.0 else 0.0
+
+
+def prfs_from_cm(cm, beta=1.0, average="macro", posLabel=-1):
+    """PrecisionRecallFScoreSupport (classification.go:74-145) from an integer confusion matrix cm[t][p]: (precision, recall,
+    fscore, support).  posLabel >= 0: that class alone.  "macro" and -- the reference's quirk, stat.Mean(p, nil) at :130 --
+    "weighted" both return the plain mean over the classes; "micro" works on the totals; support is 0 for an average."""
+    cm = np.asarray(cm)
+    n_cls = cm.shape[0]
+    per = []
+    for c in range(n_cls):
+        tp, true_sum, pred_sum = float(cm[c, c]), float(cm[c, :].sum()), float(cm[:, c].sum())
+        p = tp / pred_sum if pred_sum > 0.0 else 0.0
+        r = tp / true_sum if true_sum > 0.0 else 0.0
+        per.append((p, r, fbeta_from_pr(beta, p, r), true_sum))
+    if posLabel >= 0:
+        if posLabel >= n_cls:
+            raise ValueError(f"posLabel>=NClasses {posLabel},{n_cls}")
+        return per[posLabel]
+    if average in ("macro", "weighted"):
+        sums = [0.0, 0.0, 0.0]
+        for row in per:                              # stat.Mean: the sum in class order, then one division
+            for j in range(3):
+                sums[j] += row[j]
+        return sums[0] / n_cls, sums[1] / n_cls, sums[2] / n_cls, 0.0
+    if average == "micro":
+        tp, true_sum, pred_sum = float(np.trace(cm)), float(cm.sum()), float(cm.sum())
+        p = tp / pred_sum if pred_sum > 0.0 else 0.0
+        r = tp / true_sum if true_sum > 0.0 else 0.0
+        return p, r, fbeta_from_pr(beta, p, r), 0.0
+    raise ValueError(f"average must be macro|micro|weighted, got {average!r}")
+
+
+def average_from_scores(scores, weights=None) -> float:
+    """stat.Mean(scores, weights) as averageBinaryScore ends (base.go:86): sum w x / sum w in class order (weights None: 1);
+    "weighted" with no positive at all returns 0 (base.go:60-62)"""
+    scores = np.asarray(scores, np.float64)
+    if weights is None:
+        weights = np.ones(scores.size)
+    weights = np.asarray(weights, np.float64)
+    if float(weights.sum()) == 0.0:
+        return 0.0
+    num = den = 0.0
+    for x, w_ in zip(scores, weights):
+        num += float(x) * float(w_)
+        den += float(w_)
+    return num / den
+
+
+# --- the reference's names
+def _columns(a):
+    a = np.asarray(a, np.float64)
+    return a.reshape(-1, 1) if a.ndim <= 1 else a.reshape(a.shape[0], -1)
+
+
+def R2Score(yTrue, yPred, sampleWeight=None, multioutput="uniform_average"):
+    """metrics.R2Score (regression.go:83-128): an array for "raw_values", else a float"""
+    _no_weights(sampleWeight)
+    m = regression_metrics(_columns(yPred), _columns(yTrue))
+    return r2_from_sums(m.cols["ss_res"], m.cols["ss_tot"], multioutput)
+
+
+def MeanSquaredError(yTrue, yPred, sampleWeight=None, multioutput="uniform_average"):
+    """metrics.MeanSquaredError (regression.go:153-176)"""
+    _no_weights(sampleWeight)
+    m = regression_metrics(_columns(yPred), _columns(yTrue))
+    return multioutput_from_scores(m.cols["ss_res"] / float(m.n), "raw_values" if multioutput == "raw_values" else "")
+
+
+def MeanAbsoluteError(yTrue, yPred, sampleWeight=None, multioutput="uniform_average"):
+    """metrics.MeanAbsoluteError (regression.go:220-244)"""
+    _no_weights(sampleWeight)
+    m = regression_metrics(_columns(yPred), _columns(yTrue))
+    return multioutput_from_scores(m.cols["sum_abs"] / float(m.n), "raw_values" if multioutput == "raw_values" else "")
+
+
+def encode_classes(yTrue, yPred, union=False):
+    """LabelEncoder as internalConfusionMatrix uses it (classification.go:154-159): the classes are the sorted unique values of
+    yTrue's one column (union: of both columns); a predicted value outside them raises ValueError.  (classes, true, pred)"""
+    yt, yp = np.asarray(yTrue, np.float64), np.asarray(yPred, np.float64)
+    for a in (yt, yp):
+        if a.ndim > 1 and a.shape[1] != 1:
+            raise ValueError("one target column only")
+    yt, yp = yt.ravel(), yp.ravel()
+    if yt.size != yp.size:
+        raise ValueError(f"{yt.size} true values but {yp.size} predictions")
+    classes = np.unique(np.concatenate([yt, yp]) if union else yt)
+    it, ip = np.searchsorted(classes, yt), np.searchsorted(classes, yp)
+    bad = (ip >= classes.size) | (classes[np.minimum(ip, classes.size - 1)] != yp)
+    if bad.any():
+        raise ValueError(f"{int(bad.sum())} predicted values are not among yTrue's classes")
+    return classes, it.astype(np.int32), ip.astype(np.int32)
+
+
+def _confusion_of(YTrue, YPred, beta=1.0, union=False):
+    classes, it, ip = encode_classes(YTrue, YPred, union)
+    m = confusion_metrics(it, ip, max(classes.size, 2), beta)          # (the device takes 2 classes at least)
+    return m, classes.size
+
+
+def AccuracyScore(Ytrue, Ypred, normalize=True, sampleWeight=None):
+    """metrics.AccuracyScore (classification.go:12-35) for ONE target column: the share (normalize) or the count of equal rows"""
+    _no_weights(sampleWeight)
+    m, _ = _confusion_of(Ytrue, Ypred, union=True)
+    return m.accuracy if normalize else float(m.correct)
+
+
+def ConfusionMatrix(YTrue, YPred, sampleWeight=None) -> np.ndarray:
+    """metrics.ConfusionMatrix (classification.go:150-178): float64 [classes][classes], classes = sorted unique yTrue"""
+    _no_weights(sampleWeight)
+    m, k = _confusion_of(YTrue, YPred)
+    return m.cm[:k, :k].astype(np.float64)
+
+
+def PrecisionRecallFScoreSupport(YTrue, YPred, beta=1.0, labels=None, posLabel=-1, average="macro", warnFor=(), sampleWeight=None):
+    """metrics.PrecisionRecallFScoreSupport (classification.go:74-145): (precision, recall, fscore, support)"""
+    _no_weights(sampleWeight)
+    m, k = _confusion_of(YTrue, YPred, beta)
+    return prfs_from_cm(m.cm[:k, :k], beta, average, posLabel)
+
+
+def FBetaScore(Ytrue, Ypred, beta, average, sampleWeight=None) -> float:
+    """metrics.FBetaScore (classification.go:65-68)"""
+    _no_weights(sampleWeight)
+    return PrecisionRecallFScoreSupport(Ytrue, Ypred, beta, None, -1, average)[2]
+
+
+def _average_binary_score(which, Ytrue, Yscore, average):
+    """averageBinaryScore (base.go:12-87): one column -> the binary metric; an indicator matrix -> the metric per column, averaged.
+    One-hot rows take the one multi-class call (goctr_metrics_multiclass with ovr); other indicator matrices one curve call per
+    column.  An undefined column's NaN propagates, as in the reference."""
+    yt, ys = _columns(Ytrue), _columns(Yscore)
+    if yt.shape != ys.shape:
+        raise ValueError(f"Ytrue is {yt.shape} but Yscore is {ys.shape}")
+    if yt.shape[1] == 1:
+        m = curve_metrics(ys.ravel(), yt.ravel())
+        return m.base.auc if which == "auc" else m.average_precision
+    if average not in ("macro", "", "weighted", "micro"):
+        raise ValueError(f"average {average!r} is not supported")
+    if average == "micro":
+        m = curve_metrics(ys.ravel(), (yt.ravel() == 1.0).astype(np.float64))
+        return m.base.auc if which == "auc" else m.average_precision
+    onehot = bool(np.all((yt == 0) | (yt == 1)) and np.all(yt.sum(axis=1) == 1))
+    if onehot:
+        pc = multiclass_metrics(ys, np.argmax(yt, axis=1), ovr=True).conf.per_class
+        scores, support = pc["auc" if which == "auc" else "ap"], pc["support"].astype(np.float64)
+    else:
+        cols = [curve_metrics(ys[:, c].copy(), (yt[:, c] == 1.0).astype(np.float64)) for c in range(yt.shape[1])]
+        scores = np.array([m.base.auc if which == "auc" else m.average_precision for m in cols])
+        support = np.array([float(m.base.positives) for m in cols])
+    return average_from_scores(scores, support if average == "weighted" else None)
+
+
+def ROCAUCScore(Ytrue, Yscore, average="macro", sampleWeight=None) -> float:
+    """metrics.ROCAUCScore (ranking.go:106-149 over averageBinaryScore): the exact binary AUC of one column, or the macro /
+    weighted / micro average over the columns of an indicator matrix"""
+    _no_weights(sampleWeight)
+    return _average_binary_score("auc", Ytrue, Yscore, average)

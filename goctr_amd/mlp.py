@@ -274,6 +274,24 @@ class _BaseMLP:
         gm = GroupMetrics.from_c(out)
         return (BinaryMetrics.from_c(allm), gm) if pooled else gm
 
+    def EvaluateResidentRegression(self):
+        """every column of the head over the resident rows against the resident Y, on the device
+        (goctr_mlp_evaluate_resident_regression): a metrics.RegressionMetrics.  Any head."""
+        from . import metrics
+        out = capi.RegressionMetrics()
+        cols = np.zeros(self._units[-1], metrics.REGRESSION_COL_DTYPE)
+        capi.check(capi.load().goctr_mlp_evaluate_resident_regression(self._h, C.byref(out),
+                                                                      cols.ctypes.data_as(C.POINTER(capi.RegressionCol))))
+        return metrics._regression_result(out, cols)
+
+    def EvaluateResidentMulticlass(self, top_k=1, beta=1.0, ovr=False):
+        """the head's probabilities over the resident rows against the first maximum of each resident Y row, on the device
+        (goctr_mlp_evaluate_resident_multiclass): a metrics.MulticlassMetrics.  Heads with two output units at least."""
+        from .metrics import MulticlassCall
+        call = MulticlassCall(self._units[-1], top_k, beta, ovr)
+        capi.check(capi.load().goctr_mlp_evaluate_resident_multiclass(self._h, *call.args()))
+        return call.result()
+
     def _predict64(self, X):
         """predictProbas (basemlp64.go:897-913) in float64: the head's values"""
         X = capi.f32(X)
@@ -351,6 +369,15 @@ class MLPClassifier(_BaseMLP):
         H = self.lb.InverseTransform(self._predict64(X)) if self.lb is not None else self._predict64(X)
         return AccuracyScore64(Y, H)
 
+    def ScoreResident(self):
+        """Score over the rows Fit left resident, without a download: the arg-max accuracy
+        (goctr_mlp_evaluate_resident_multiclass) when Fit label-binarized ONE target column into two classes at least.  Otherwise
+        ValueError: on 0 / 1 targets the reference's rule is exact equality between probabilities and labels, which has no meaning
+        on this path -- use EvaluateResidentMulticlass (or EvaluateResident for the logistic head)."""
+        if self.lb is None or len(self.lb.Classes) != 1 or self._units[-1] < 2:
+            raise ValueError("ScoreResident needs one label-binarized target column; use EvaluateResidentMulticlass")
+        return self.EvaluateResidentMulticlass().conf.accuracy
+
 
 class MLPRegressor(_BaseMLP):
     """nn.MLPRegressor (multilayer_perceptron.go:9-71): identity output + square_loss, float64 predictions, Score = r2Score64.
@@ -367,6 +394,14 @@ class MLPRegressor(_BaseMLP):
 
     def Score(self, X, Y):
         return r2Score64(np.asarray(Y, np.float64).reshape(np.asarray(X).shape[0], -1), self.Predict(X))
+
+    def ScoreResident(self):
+        """r2Score64 over the rows Fit left resident, from the device's column sums (goctr_mlp_evaluate_resident_regression:
+        r2_mlp_uniform); ValueError("yDen=0") when a column is constant, as r2Score64"""
+        m = self.EvaluateResidentRegression()
+        if m.constant_columns:
+            raise ValueError("yDen=0")
+        return m.r2_mlp_uniform
 
 
 def NewMLPRegressor(hiddenLayerSizes, activation, solver, Alpha):

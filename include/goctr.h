@@ -573,7 +573,8 @@ int goctr_mlp_train_steps(goctr_mlp* p, int64_t first_batch, int n_steps);
  * softmax heads, raw values for the identity head) */
 int goctr_mlp_predict(goctr_mlp* p, const float* X, int64_t rows, float* y_out);
 /* predictProbas (basemlp64.go:897-913) without the narrowing: y_out [rows][units[last]] float64, what MLPRegressor.Predict
- * and both Score rules (r2Score64 :1116-1141, AccuracyScore64 :1143-1155; computed by the host) read */
+ * and both Score rules (r2Score64 :1116-1141, AccuracyScore64 :1143-1155; computed by the host) read.  Over the resident rows
+ * goctr_mlp_evaluate_resident_regression / _multiclass compute the same figures on the device, without this download */
 int goctr_mlp_predict64(goctr_mlp* p, const float* X, int64_t rows, double* y_out);
 
 /* ---------------------------------------------------------------- item2vec (f64) ----------- */
@@ -736,7 +737,7 @@ int goctr_metrics_binary_f64(const double* score, const double* y, int64_t n, go
  * labels; no score leaves the device */
 int goctr_evaluate_dataset(goctr_model* m, goctr_emb* emb, goctr_dataset* d, int batch, goctr_binary_metrics* out);
 /* the rows goctr_mlp_upload left resident: the output unit's float64 activation (goctr_mlp_predict64's values) against the
- * resident Y; single-output heads only (a softmax head is refused) */
+ * resident Y; single-output heads only (a softmax head is refused: goctr_mlp_evaluate_resident_multiclass is for those) */
 int goctr_mlp_evaluate_resident(goctr_mlp* p, goctr_binary_metrics* out);
 
 /* ---------------------------------------------------------------- per-group ranking metrics on the device
@@ -848,6 +849,120 @@ int goctr_evaluate_dataset_curve(goctr_model* m, goctr_emb* emb, goctr_dataset* 
 /* goctr_mlp_evaluate_resident's scores (float64) against the resident Y; a softmax head is refused */
 int goctr_mlp_evaluate_resident_curve(goctr_mlp* p, const goctr_curve_cfg* cfg, goctr_curve_metrics* out, goctr_curve_points* pts,
                                       goctr_calib_bins* bins);
+
+/* ---------------------------------------------------------------- multi-output metrics on the device
+ * The reference's remaining metric functions, over [n][K] predictions and [n][C] probabilities: R2Score / MeanSquaredError /
+ * MeanAbsoluteError (nn/metrics/regression.go) and r2Score64 (basemlp64.go:1116-1141); AccuracyScore, ConfusionMatrix,
+ * PrecisionRecallFScoreSupport and its averages, FBetaScore (nn/metrics/classification.go); the `average` argument of ROCAUCScore /
+ * AveragePrecisionScore (nn/metrics/base.go:12-87).  Without sample weights.  1 <= n < 2^31 as everywhere.  The rule of the
+ * other metrics holds: integers exact, quotients of integers correctly rounded ("rounded" below), every float sum in an order
+ * that depends on the shape alone, the same bytes on every call, nothing per row copied back.  Every call fills its outputs only
+ * on success (-1, goctr_last_error naming the entry point, nothing written otherwise).
+ *
+ * --- regression: pred, y [n][K] row-major, 1 <= K <= 1024; float inputs are widened exactly, then the same arithmetic.
+ * "fl" is one IEEE double operation (the library is built without contraction).  Per column c, FROM THE DEVICE:
+ *   sum_y    = sum_r y                          mean_y  = sum_y / n  (one IEEE division: bit-equal to the caller's sum_y / n)
+ *   ss_res   = sum_r fl(fl(p - y)^2)            sum_abs = sum_r |fl(p - y)|         max_abs = max_r |fl(p - y)| (exact)
+ *   ss_tot   = sum_r fl(fl(y - mean_y)^2), a second pass over y against the returned mean_y (never sum y^2 - n mean^2)
+ * Each sum is within (n + 64) 2^-53 sum|term| of the exact sum of its rounded terms.  DERIVED ON THE HOST from those, in double:
+ *   mse = ss_res / n      mae = sum_abs / n      r2 = 1 - ss_res / max(ss_tot, 1e-20)  (regression.go:112)
+ *   r2_mlp = 1 - ss_res / ss_tot  (r2Score64; NaN or -inf when ss_tot == 0)
+ * and in the head, sums in column order:  x_uniform = (sum_c x_c) / K for mse, mae, r2, r2_mlp;
+ *   r2_variance_weighted = (sum_c fl(ss_tot_c * r2_c)) / (sum_c ss_tot_c)  (regression.go:118-123; NaN when every column is constant)
+ *   constant_columns = columns with ss_tot == 0;  max_abs = the largest column max_abs.
+ * Refused: a NaN or infinite value in pred or y; K outside 1 .. 1024; bad n; NULL pred / y / out. */
+typedef struct {
+  int64_t n, k, constant_columns;
+  double  mse_uniform, mae_uniform, r2_uniform, r2_mlp_uniform, r2_variance_weighted, max_abs;
+} goctr_regression_metrics;
+typedef struct {
+  double sum_y, mean_y, ss_res, sum_abs, ss_tot, max_abs;   /* from the device */
+  double mse, mae, r2, r2_mlp;                              /* derived on the host */
+} goctr_regression_col;
+/* host arrays pred, y [n][K]; per_col (may be NULL): K entries */
+int goctr_metrics_regression(const float* pred, const float* y, int64_t n, int k, goctr_regression_metrics* out,
+                             goctr_regression_col* per_col);
+int goctr_metrics_regression_f64(const double* pred, const double* y, int64_t n, int k, goctr_regression_metrics* out,
+                                 goctr_regression_col* per_col);
+
+/* --- confusion: label, pred [n] int32 class indices in [0, C), 2 <= C <= 1024; cm[t * C + p] = rows with label t and prediction p.
+ * Per class c (goctr_class_stat):  support = row sum of cm, predicted = column sum, tp = cm[c][c];
+ *   precision = tp / predicted rounded (0 when predicted == 0);  recall = tp / support rounded (0 when support == 0);
+ *   f: b2 = fl(beta * beta); d = fl(fl(b2 * precision) + recall); f = d > 0 ? fl(fl(fl(fl(1 + b2) * precision) * recall) / d) : 0
+ *   (classification.go:91-95, operation for operation, on the host).
+ * Head:  correct = trace of cm;  accuracy = correct / n rounded;
+ *   x_macro = (sum_c x_c) / C for precision, recall, f, in class order (PrecisionRecallFScoreSupport's "macro");
+ *   micro (classification.go:134-141 on the integer totals: tp total = correct, both other totals = n):
+ *     precision_micro = recall_micro = correct / n rounded, f_micro by the formula of f over them;
+ *   x_weighted = (sum_c fl((double)support_c * x_c)) / n in class order: the TRUE support-weighted mean.  The reference's
+ *     average == "weighted" returns the macro mean (stat.Mean(p, nil), classification.go:130); metrics.py keeps that quirk.
+ * The auc / ap fields of goctr_class_stat belong to goctr_metrics_multiclass with cfg.ovr; elsewhere auc_num = auc_den = 0 and
+ * auc = ap = NaN.
+ * Refused: a label or prediction outside [0, C); C outside 2 .. 1024; a negative or NaN beta; bad n; NULL label / pred / out. */
+typedef struct {
+  int64_t n, classes, correct;
+  double  beta, accuracy;
+  double  precision_macro, recall_macro, f_macro;
+  double  precision_micro, recall_micro, f_micro;
+  double  precision_weighted, recall_weighted, f_weighted;
+} goctr_confusion_metrics;
+typedef struct {
+  int64_t  support, predicted, tp;
+  double   precision, recall, f;
+  uint64_t auc_num, auc_den;  double auc, ap;    /* one-vs-rest (goctr_metrics_multiclass with cfg.ovr) */
+} goctr_class_stat;
+/* host arrays label, pred [n]; per_class (may be NULL): C entries; cm (may be NULL): C * C entries */
+int goctr_metrics_confusion(const int32_t* label, const int32_t* pred, int64_t n, int classes, double beta,
+                            goctr_confusion_metrics* out, goctr_class_stat* per_class, uint64_t* cm);
+
+/* --- multi-class: proba [n][C] row-major against label [n] (int32 in [0, C)), 2 <= C <= 1024.  Values compare as numbers: -0 ties
+ * with +0, +-inf and subnormals are ordinary values; the rows need not sum to 1.  With t = label[r] and p = proba[r]:
+ *   pred[r]  = the smallest c with p_c equal to the row's maximum (MaxIdx64's first maximum)
+ *   rank[r]  = #{c : p_c > p_t} + #{c < t : p_c == p_t}
+ *   topk_correct = rows with rank < cfg.top_k (top_k == 1: equal to conf.correct);  topk_accuracy = topk_correct / n rounded
+ *   logloss  = (sum_r -log(min(max((double)p_t, Nextafter(0, 1)), Nextafter(1, 0)))) / n: the reference's log_loss of a one-hot
+ *              row (basemlp64.go:151-195), summed in a fixed order
+ *   conf, per_class, cm = goctr_metrics_confusion of (label, pred) with cfg.beta, byte for byte; pred never leaves the device
+ * One-vs-rest (cfg.ovr != 0): ROCAUCScore / AveragePrecisionScore with average = macro / weighted / micro (base.go:12-87).
+ *   per_class[c].auc_num, auc_den, auc, ap = base.auc_num, base.auc_den, base.auc, average_precision of goctr_metrics_curve(_f64)
+ *   over column c of proba and the 0 / 1 indicator label == c, byte for byte.  Class c is DEFINED iff 0 < support_c < n.
+ *   auc_classes = defined classes;  auc_macro / ap_macro = (sum over the defined c, in class order) / auc_classes;
+ *   auc_weighted / ap_weighted = (sum over the defined c of fl((double)support_c * x_c)) / (double)(sum of their supports);
+ *   auc_micro / ap_micro = the same two fields over the n C pairs (proba[r][c], label[r] == c) in row-major order (base.go:38-45);
+ *   NaN when n C >= 2^31.  A mean over no class is NaN.
+ *   With cfg.ovr == 0 all six are NaN, auc_classes is 0 and the per_class fields are 0 / 0 / NaN / NaN.
+ * multi_label_rows: only goctr_mlp_evaluate_resident_multiclass sets it (0 elsewhere).
+ * Refused: a NaN in proba; a label outside [0, C); C outside 2 .. 1024; top_k outside 1 .. C; a negative or NaN beta; bad n;
+ * NULL proba / label / out. */
+typedef struct {
+  int32_t top_k;       /* 1 .. C (default 1) */
+  int32_t ovr;         /* != 0: the one-vs-rest AUC / AP figures (default 0) */
+  double  beta;        /* F-beta's beta >= 0 (default 1) */
+} goctr_multiclass_cfg;
+typedef struct {
+  goctr_confusion_metrics conf;
+  int64_t top_k, topk_correct;  double topk_accuracy;
+  double  logloss;
+  int64_t multi_label_rows;
+  int64_t ovr, auc_classes;
+  double  auc_macro, auc_weighted, auc_micro, ap_macro, ap_weighted, ap_micro;
+} goctr_multiclass_metrics;
+void goctr_multiclass_cfg_default(goctr_multiclass_cfg* cfg);   /* top_k 1, ovr 0, beta 1 */
+/* host arrays proba [n][C], label [n]; cfg NULL = the defaults; per_class (C entries) and cm (C * C entries) may be NULL */
+int goctr_metrics_multiclass(const float* proba, const int32_t* label, int64_t n, int classes, const goctr_multiclass_cfg* cfg,
+                             goctr_multiclass_metrics* out, goctr_class_stat* per_class, uint64_t* cm);
+int goctr_metrics_multiclass_f64(const double* proba, const int32_t* label, int64_t n, int classes, const goctr_multiclass_cfg* cfg,
+                                 goctr_multiclass_metrics* out, goctr_class_stat* per_class, uint64_t* cm);
+
+/* --- the MLP's resident rows (goctr_mlp_upload): every column of the head in float64, left on the device, with goctr_mlp_predict64's
+ * values, against the resident Y.  Both equal, byte for byte, the _f64 entry points above fed with goctr_mlp_predict64's output
+ * and the uploaded Y.
+ * regression: any head; K = units[last].
+ * multiclass: units[last] >= 2; the true class of a row is the first maximum of its resident Y row; multi_label_rows counts the
+ * rows that are not exactly one-hot (one entry 1, the others 0) -- for information only. */
+int goctr_mlp_evaluate_resident_regression(goctr_mlp* p, goctr_regression_metrics* out, goctr_regression_col* per_col);
+int goctr_mlp_evaluate_resident_multiclass(goctr_mlp* p, const goctr_multiclass_cfg* cfg, goctr_multiclass_metrics* out,
+                                           goctr_class_stat* per_class, uint64_t* cm);
 
 #ifdef __cplusplus
 }
