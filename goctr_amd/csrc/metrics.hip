@@ -10,8 +10,8 @@
 //
 // Pipeline (all on the engine's main stream; one small copy to the host at the end):
 //   key build      score bits -> order-preserving unsigned key (-0 -> +0), label byte (y > 0.5), and per workgroup the
-//                  partials of P, Accuracy32's hits, the log-loss sum and the NaN-score count (a fixed array, reduced in a
-//                  fixed order: the same bits on every call)
+//                  partials of P, Accuracy32's hits, the log-loss sum and the NaN-score count (a fixed array, reduced in
+//                  metrics_reduce.h's fixed order: the same bits on every call)
 //   sort           radix_sort.h, descending, (key, label byte); the order inside a tie group does not matter
 //   scan 1         exclusive prefix sum of the sorted labels (scan.h over the label bytes as 32-bit words of 4 rows); its sink
 //                  writes E[i] | head[i] << 31 over the sort's (now free) key input, head[i] = key[i] != key[i-1]
@@ -19,13 +19,15 @@
 //                  sorted keys (read by nobody any more): heads[g]
 //   terms          per group g: pos_g = E[heads[g+1]] - E[heads[g]], size_g = heads[g+1] - heads[g]; the u64 term, summed
 //                  per workgroup, one integer atomic per workgroup
-//   finish         the key build's partials, in a fixed order
+//   finish         the key build's partials, in the fixed order (metrics_reduce.h, as every sum here)
 // Scratch per row: keys 2 x sizeof(key) + labels 2 x 1 byte (+ rocPRIM's scratch), per engine with a high-water mark.  The host
 // entry points stage the caller's arrays into the two key buffers (scores over the sort input: the key build overwrites each
 // score with its own key; labels over the sort output), so they need no more.
 // Everything up to the copy is metrics_sorted_dev, which metrics_curve.hip runs too: there heads[] gets 4 bytes per row of its own
 // and the sorted keys stay (a key decodes back to its score).
 #include <cmath>
+#include <cstdarg>
+#include <cstdio>
 
 #include "common.h"
 #include "metrics.h"
@@ -41,25 +43,20 @@ __device__ __forceinline__ bool hit(float p, float y) { const float d = p - y; r
 __device__ __forceinline__ bool hit(double p, double y) { return fabs(p - y) < 0.5; }
 __device__ __forceinline__ bool hit(double p, float y) { return fabs(p - (double)y) < 0.5; }
 
-// the workgroup's sums in a fixed order (lane tree, then the waves in order); valid in thread 0
-__device__ __forceinline__ MetricsPart block_sum(MetricsPart v) {
-  __shared__ MetricsPart wp[MB / 64];
-  v.pos = wave_sum(v.pos); v.correct = wave_sum(v.correct); v.nan = wave_sum(v.nan); v.ll = wave_sum(v.ll);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) wp[wave] = v;
-  __syncthreads();
-  MetricsPart s{0, 0, 0, 0.0};
-  if (threadIdx.x == 0)
-    for (int w = 0; w < MB / 64; ++w) { s.pos += wp[w].pos; s.correct += wp[w].correct; s.nan += wp[w].nan; s.ll += wp[w].ll; }
-  return s;
-}
+// the key build's sums per workgroup
+struct MetricsPart {
+  unsigned long long pos, correct, nan;
+  double ll;
+  static __device__ __forceinline__ MetricsPart identity() { return MetricsPart{0, 0, 0, 0.0}; }
+  __device__ __forceinline__ void join(const MetricsPart& b) { pos += b.pos; correct += b.correct; nan += b.nan; ll += b.ll; }
+};
 
 // score may alias key (the host entry points stage the scores in the key buffer): each thread reads its row's score before
 // it writes that row's key, which is computed from it
 template <class TS, class TL, class K>
 __global__ __launch_bounds__(MB) void metrics_key_kernel(const TS* score, const TL* __restrict__ y, long long n, K* key,
                                                          unsigned char* __restrict__ lab, MetricsPart* __restrict__ part) {
-  MetricsPart a{0, 0, 0, 0.0};
+  MetricsPart a = MetricsPart::identity();
   for (long long i = (long long)blockIdx.x * MB + threadIdx.x; i < n; i += (long long)gridDim.x * MB) {
     const TS p = score[i];
     const TL t = y[i];
@@ -74,7 +71,7 @@ __global__ __launch_bounds__(MB) void metrics_key_kernel(const TS* score, const 
     key[i] = k;
     lab[i] = positive ? 1 : 0;
   }
-  const MetricsPart s = block_sum(a);
+  const MetricsPart s = block_join(a);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
@@ -121,24 +118,13 @@ __global__ __launch_bounds__(MB) void metrics_terms_kernel(const unsigned int* _
     const unsigned long long pos = below - above, neg = (h1 - h) - pos;
     s += neg * (2 * above + pos);
   }
-  __shared__ unsigned long long ws[MB / 64];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long t = 0;
-    for (int w = 0; w < MB / 64; ++w) t += ws[w];
-    if (t) atomicAdd(&res->S, t);
-  }
+  const unsigned long long t = block_join(Sums<unsigned long long>{{s}}).v[0];
+  if (threadIdx.x == 0 && t) atomicAdd(&res->S, t);
 }
 
-// the key build's partials in a fixed order: thread t sums t, t + MB, ..., then block_sum
+// the key build's partials in the fixed order, into the result block
 __global__ __launch_bounds__(MB) void metrics_finish_kernel(const MetricsPart* __restrict__ part, int nparts, MetricsRes* res) {
-  MetricsPart a{0, 0, 0, 0.0};
-  for (int i = threadIdx.x; i < nparts; i += MB) {
-    a.pos += part[i].pos; a.correct += part[i].correct; a.nan += part[i].nan; a.ll += part[i].ll;
-  }
-  const MetricsPart s = block_sum(a);
+  const MetricsPart s = block_join(join_strided(part, nparts));
   if (threadIdx.x == 0) { res->pos = s.pos; res->correct = s.correct; res->nan = s.nan; res->ll = s.ll; }
 }
 
@@ -162,12 +148,8 @@ int ensure_ws(MetricsWs& w, int64_t n, size_t kb, size_t temp_bytes, bool keep_k
   if (w.kin.ensure(kbytes, false) || w.kout.ensure(kbytes, false) || w.lin.ensure(lbytes, false) || w.lout.ensure(lbytes, false) ||
       (keep_keys && w.heads.ensure(hrows, false)) ||
       radix_sort_scratch(w.temp, temp_bytes) || w.tiles.ensure((size_t)cdiv(n, SCAN_TILE), false) ||
-      w.part.ensure(MKEY_MAX_BLOCKS, false) || w.res.ensure(1, false)) {
-    w.release();
-    (void)hipGetLastError();
-    set_error("%s: could not allocate %zu bytes of device scratch for %lld rows", who, want, (long long)n);
-    return -1;
-  }
+      w.part.ensure(MKEY_MAX_BLOCKS, false) || w.res.ensure(1, false))
+    return metrics_rows_alloc_failed(w, want, n, who);
   return 0;
 }
 
@@ -222,7 +204,7 @@ int metrics_sorted_dev(const TS* score, const TL* y, int64_t n, const char* who,
     y = reinterpret_cast<const TL*>(kout);
   }
   GOCTR_HIP(hipMemsetAsync(w.res.p, 0, sizeof(MetricsRes), s));
-  const int nparts = (int)std::min<int64_t>(cdiv(n, MB), MKEY_MAX_BLOCKS);
+  const int nparts = metrics_grid(n, MB);
   hipLaunchKernelGGL((metrics_key_kernel<TS, TL, K>), dim3((unsigned)nparts), dim3(MB), 0, s, score, y, (long long)n, kin, w.lin.p,
                      w.part.p);
   GOCTR_HIP(hipGetLastError());
@@ -278,15 +260,24 @@ int metrics_check_rows(int64_t n, const char* who) {
   return 0;
 }
 
-int metrics_binary_dev(const float* score, const float* y, int64_t n, goctr_binary_metrics* out, const char* who) {
+int metrics_alloc_failed(const char* who, const char* what, ...) {
+  (void)hipGetLastError();
+  char buf[256];
+  va_list ap;
+  va_start(ap, what);
+  vsnprintf(buf, sizeof(buf), what, ap);
+  va_end(ap);
+  set_error("%s: could not allocate %s", who, buf);
+  return -1;
+}
+
+template <class TS, class TL>
+int metrics_binary_dev(const TS* score, const TL* y, int64_t n, goctr_binary_metrics* out, const char* who) {
   return run(score, y, n, out, who);
 }
-int metrics_binary_dev(const double* score, const double* y, int64_t n, goctr_binary_metrics* out, const char* who) {
-  return run(score, y, n, out, who);
-}
-int metrics_binary_dev(const double* score, const float* y, int64_t n, goctr_binary_metrics* out, const char* who) {
-  return run(score, y, n, out, who);
-}
+template int metrics_binary_dev<float, float>(const float*, const float*, int64_t, goctr_binary_metrics*, const char*);
+template int metrics_binary_dev<double, double>(const double*, const double*, int64_t, goctr_binary_metrics*, const char*);
+template int metrics_binary_dev<double, float>(const double*, const float*, int64_t, goctr_binary_metrics*, const char*);
 
 }  // namespace goctr
 

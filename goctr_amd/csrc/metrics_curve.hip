@@ -9,17 +9,17 @@
 // tps_g = E[heads[g+1]] (P for the last), fps_g = heads[g+1] - tps_g, pos_g = tps_g - E[heads[g]].
 //
 // Pipeline behind the front (engine's main stream):
-//   groups         one pass over the groups: AP's terms (per-thread in grid-stride order, then the workgroup's fixed tree, one
-//                  partial per workgroup); KS as (integer value, smallest g) and the best F1 as (exact 128-bit comparison,
-//                  smallest g) -- both total orders, so the reduction order cannot matter; the group's curve point, if it is one
-//                  of the min(G, cap) kept, straight into the packed points array
+//   groups         one pass over the groups: AP's terms (metrics_reduce.h's fixed order, one partial per workgroup); KS as
+//                  (integer value, smallest g) and the best F1 as (exact 128-bit comparison, smallest g) -- both total orders,
+//                  so the reduction order cannot matter; the group's curve point, if it is one of the min(G, cap) kept, straight
+//                  into the packed points array
 //   bounds         the bin index is monotone in the score, so in sorted order every bin is one contiguous run: bound[b] = rows
 //                  with bin >= b, a binary search in the sorted keys per bin.  Counts and positives follow from E[] exactly.
 //   bin sums       every wavefront owns a contiguous range of sorted rows and sums, per bin that crosses its range, the decoded
 //                  scores (lane-strided, then the lane tree) into slot[wave + (B-1-bin)] -- wave rises and bin falls along the
 //                  sorted order, so every (wave, bin) pair has a slot of its own
 //   bins           one wavefront per bin: its slots in wave order (lane-strided, lane tree), its count and positives
-//   finish         the groups' partials in a fixed order; tp / fp at the threshold (a binary search in the sorted keys); the
+//   finish         the groups' partials in the fixed order; tp / fp at the threshold (a binary search in the sorted keys); the
 //                  front's MetricsRes next to them, so that the host reads one block
 // No atomics at all; every float sum has a fixed order that depends on n and the bin boundaries only: two calls, same bytes.
 // To the host: that block with the 3 B bin values (one copy), then the `points` packed curve entries (a second one, only with a
@@ -40,25 +40,31 @@ constexpr int CURVE_WAVE_ROWS = 1024;   // a bin-sum wavefront owns at least thi
 constexpr int CURVE_MAX_WAVES = 8192;   // ... and there are at most this many of them
 
 // a candidate of an arg-max over groups: g < 0 = none.  KS: value = num, den = 1.  F1: num / den = 2 tps / (tps + fps + P).
-struct Best { unsigned long long num, den; long long g; };
-// a beats b: larger num / den (exactly, by cross-multiplication), ties to the smaller g -- a total order
+struct Best;
+__device__ __forceinline__ bool beats(const Best& a, const Best& b);
+struct Best {
+  unsigned long long num, den;
+  long long g;
+  __device__ __forceinline__ void join(const Best& b) { if (beats(b, *this)) *this = b; }
+};
+// a beats b: larger num / den (exactly, by cross-multiplication), ties to the smaller g -- a total order, so a join does not
+// depend on which operand is which
 __device__ __forceinline__ bool beats(const Best& a, const Best& b) {
   if (a.g < 0) return false;
   if (b.g < 0) return true;
   const unsigned __int128 l = (unsigned __int128)a.num * b.den, r = (unsigned __int128)b.num * a.den;
   return l > r || (l == r && a.g < b.g);
 }
-__device__ __forceinline__ Best wave_best(Best v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    Best t;
-    t.num = __shfl_down(v.num, o, 64); t.den = __shfl_down(v.den, o, 64); t.g = __shfl_down(v.g, o, 64);
-    if (beats(t, v)) v = t;
-  }
-  return v;
-}
 
-struct CurvePart { double ap; Best ks, f1; };
+// a workgroup's partial of the groups pass.  The identity's ap is +0.0, and joining a wavefront's ap onto it returns that ap's own
+// bits: +0.0 + x differs from x only for x = -0.0, which no ap is -- every lane's accumulator starts at +0.0 and +0.0 + x is never
+// -0.0 (the terms are >= 0).
+struct CurvePart {
+  double ap;
+  Best ks, f1;
+  static __device__ __forceinline__ CurvePart identity() { return CurvePart{0.0, Best{0, 1, -1}, Best{0, 1, -1}}; }
+  __device__ __forceinline__ void join(const CurvePart& b) { ap += b.ap; ks.join(b.ks); f1.join(b.f1); }
+};
 // what the host reads back, followed by count [B], pos [B] (64-bit integers) and sum [B] (double)
 struct CurveHead {
   MetricsRes base;
@@ -68,22 +74,6 @@ struct CurveHead {
   unsigned long long f1_tps, f1_fps;
   unsigned long long at_rows, at_tp;          // rows with (double)score >= t, and the positives among them
 };
-
-// the workgroup's partial in a fixed order (lane tree, then the waves in order); valid in thread 0
-__device__ __forceinline__ CurvePart block_part(CurvePart v) {
-  __shared__ CurvePart wp[MB / 64];
-  v.ap = wave_sum(v.ap); v.ks = wave_best(v.ks); v.f1 = wave_best(v.f1);
-  if ((threadIdx.x & 63) == 0) wp[threadIdx.x >> 6] = v;
-  __syncthreads();
-  CurvePart s = wp[0];
-  if (threadIdx.x == 0)
-    for (int w = 1; w < MB / 64; ++w) {
-      s.ap += wp[w].ap;
-      if (beats(wp[w].ks, s.ks)) s.ks = wp[w].ks;
-      if (beats(wp[w].f1, s.f1)) s.f1 = wp[w].f1;
-    }
-  return s;
-}
 
 // E of a row count c = positives in the first c sorted rows
 __device__ __forceinline__ unsigned long long pos_before(const unsigned int* __restrict__ eh, long long c, long long n,
@@ -100,7 +90,7 @@ __global__ __launch_bounds__(MB) void curve_groups_kernel(const K* __restrict__ 
   const long long G = (long long)res->G;
   const unsigned long long P = res->P, N = (unsigned long long)n - P;
   const long long points = G < cap ? G : cap;
-  CurvePart a{0.0, Best{0, 1, -1}, Best{0, 1, -1}};
+  CurvePart a = CurvePart::identity();
   for (long long g = (long long)blockIdx.x * MB + threadIdx.x; g < G; g += (long long)gridDim.x * MB) {
     const long long h = heads[g], h1 = g + 1 < G ? (long long)heads[g + 1] : n;
     const unsigned long long above = eh[h] & 0x7fffffffu, tps = pos_before(eh, h1, n, P), fps = (unsigned long long)h1 - tps;
@@ -123,7 +113,7 @@ __global__ __launch_bounds__(MB) void curve_groups_kernel(const K* __restrict__ 
       }
     }
   }
-  const CurvePart s = block_part(a);
+  const CurvePart s = block_join(a);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
@@ -193,19 +183,13 @@ __global__ __launch_bounds__(MB) void curve_bins_kernel(const unsigned int* __re
   }
 }
 
-// the groups' partials in a fixed order (thread t takes t, t + MB, ..., then block_part), the threshold's rows, the front's result
+// the groups' partials in the fixed order, the threshold's rows, the front's result
 template <class K>
 __global__ __launch_bounds__(MB) void curve_finish_kernel(const K* __restrict__ skey, const unsigned int* __restrict__ heads,
                                                           const unsigned int* __restrict__ eh, long long n,
                                                           const MetricsRes* __restrict__ res, const CurvePart* __restrict__ part,
                                                           int nparts, double t, CurveHead* __restrict__ head) {
-  CurvePart a{0.0, Best{0, 1, -1}, Best{0, 1, -1}};
-  for (int i = threadIdx.x; i < nparts; i += MB) {
-    a.ap += part[i].ap;
-    if (beats(part[i].ks, a.ks)) a.ks = part[i].ks;
-    if (beats(part[i].f1, a.f1)) a.f1 = part[i].f1;
-  }
-  const CurvePart s = block_part(a);
+  const CurvePart s = block_join(join_strided(part, nparts));
   if (threadIdx.x != 0) return;
   const long long G = (long long)res->G;
   const unsigned long long P = res->P;
@@ -244,9 +228,7 @@ int run(const TS* score, const TL* y, int64_t n, const goctr_curve_cfg* cfg, goc
         goctr_calib_bins* bins, const char* who, const TS* host_score = nullptr, const TL* host_y = nullptr) {
   using K = typename std::conditional<sizeof(TS) == 4, unsigned int, unsigned long long>::type;
   if (metrics_curve_check(cfg, pts, bins, who)) return -1;
-  goctr_curve_cfg c;
-  goctr_curve_cfg_default(&c);
-  if (cfg) c = *cfg;
+  const goctr_curve_cfg c = cfg_or_default(cfg, goctr_curve_cfg_default);
   const int B = c.bins;
   if (metrics_check_rows(n, who)) return -1;
   const int64_t cap = pts ? std::min<int64_t>(pts->cap, n) : 0;   // G <= n: a larger cap keeps every group just the same
@@ -259,11 +241,8 @@ int run(const TS* score, const TL* y, int64_t n, const goctr_curve_cfg* cfg, goc
   const size_t nslot = (size_t)nwaves + (size_t)B, out_words = HEAD_WORDS + 3 * (size_t)B;
   if (w.part.ensure(MKEY_MAX_BLOCKS, false) || w.bound.ensure(CURVE_MAX_BINS + 1, false) ||
       w.slot.ensure((size_t)CURVE_MAX_WAVES + CURVE_MAX_BINS, false) || w.out.ensure(HEAD_WORDS + 3 * (size_t)CURVE_MAX_BINS, false) ||
-      w.pts.ensure(3 * (size_t)std::max<int64_t>(cap, 1), false)) {
-    (void)hipGetLastError();
-    set_error("%s: could not allocate the device scratch of %lld curve points", who, (long long)cap);
-    return -1;
-  }
+      w.pts.ensure(3 * (size_t)std::max<int64_t>(cap, 1), false))
+    return metrics_alloc_failed(who, "the device scratch of %lld curve points", (long long)cap);
   const K* skey = static_cast<const K*>(m.keys);
   CurveHead* head = reinterpret_cast<CurveHead*>(w.out.p);
   unsigned long long* bin_out = w.out.p + HEAD_WORDS;
@@ -364,18 +343,17 @@ int metrics_curve_check(const goctr_curve_cfg* cfg, const goctr_curve_points* pt
   return 0;
 }
 
-int metrics_curve_dev(const float* score, const float* y, int64_t n, const goctr_curve_cfg* cfg, goctr_curve_metrics* out,
+template <class TS, class TL>
+int metrics_curve_dev(const TS* score, const TL* y, int64_t n, const goctr_curve_cfg* cfg, goctr_curve_metrics* out,
                       goctr_curve_points* pts, goctr_calib_bins* bins, const char* who) {
   return run(score, y, n, cfg, out, pts, bins, who);
 }
-int metrics_curve_dev(const double* score, const double* y, int64_t n, const goctr_curve_cfg* cfg, goctr_curve_metrics* out,
-                      goctr_curve_points* pts, goctr_calib_bins* bins, const char* who) {
-  return run(score, y, n, cfg, out, pts, bins, who);
-}
-int metrics_curve_dev(const double* score, const float* y, int64_t n, const goctr_curve_cfg* cfg, goctr_curve_metrics* out,
-                      goctr_curve_points* pts, goctr_calib_bins* bins, const char* who) {
-  return run(score, y, n, cfg, out, pts, bins, who);
-}
+template int metrics_curve_dev<float, float>(const float*, const float*, int64_t, const goctr_curve_cfg*, goctr_curve_metrics*,
+                                             goctr_curve_points*, goctr_calib_bins*, const char*);
+template int metrics_curve_dev<double, double>(const double*, const double*, int64_t, const goctr_curve_cfg*, goctr_curve_metrics*,
+                                               goctr_curve_points*, goctr_calib_bins*, const char*);
+template int metrics_curve_dev<double, float>(const double*, const float*, int64_t, const goctr_curve_cfg*, goctr_curve_metrics*,
+                                              goctr_curve_points*, goctr_calib_bins*, const char*);
 
 }  // namespace goctr
 

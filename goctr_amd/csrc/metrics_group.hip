@@ -26,8 +26,9 @@
 //                  (segmented shuffle scan, the open run carried along the wavefront's contiguous range) and each finished run
 //                  issues ONE 64-bit integer atomic into S[g]
 //   groups         per group: P_u, n_u, first_u (binary search in E), DCG over its first min(k, n_u) rows (compensated sum),
-//                  auc_u = S_u / (2 P_u N_u) in float64, the optional goctr_group_stat; workgroup partials in a fixed order
-//   finish         the partials in a fixed order: two calls return the same bits.  No float atomics anywhere.
+//                  auc_u = S_u / (2 P_u N_u) in float64, the optional goctr_group_stat; one partial per workgroup
+//   finish         the partials folded by one workgroup.  Every sum in metrics_reduce.h's fixed order: two calls return the same
+//                  bits.  No float atomics anywhere.
 // Scratch per row: 2 keys + 2 words + 3 x 4 bytes (group-head flags, group heads, and E | tie head over the free word buffer; ties
 // and gidx reuse the key buffers) + rocPRIM's; per engine with a high-water mark, released whole on a failed allocation.
 #include <cmath>
@@ -46,6 +47,18 @@ struct GroupRes { unsigned long long P, T, G, nan, neg; unsigned int maxid, pad;
 struct GroupPart {
   unsigned long long valid_groups, valid_rows, pos_groups, hits, pair_num, pair_den;
   double gauc, macro, mrr, ndcg;
+  static __device__ __forceinline__ GroupPart identity() { return GroupPart{0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0}; }
+  __device__ __forceinline__ void join(const GroupPart& b) {
+    valid_groups += b.valid_groups; valid_rows += b.valid_rows; pos_groups += b.pos_groups; hits += b.hits;
+    pair_num += b.pair_num; pair_den += b.pair_den; gauc += b.gauc; macro += b.macro; mrr += b.mrr; ndcg += b.ndcg;
+  }
+};
+// the key build's counts and largest id per workgroup (20 bytes, not 24: four of them in LDS)
+struct __attribute__((packed, aligned(4))) KeyPart {
+  unsigned long long nan, neg;
+  unsigned int maxid;
+  static __device__ __forceinline__ KeyPart identity() { return KeyPart{0, 0, 0}; }
+  __device__ __forceinline__ void join(const KeyPart& b) { nan += b.nan; neg += b.neg; maxid = b.maxid > maxid ? b.maxid : maxid; }
 };
 
 // score may alias key (the host entry points stage the scores in the key buffer): each thread reads its row's score before it
@@ -68,19 +81,11 @@ __global__ __launch_bounds__(MB) void gm_key_kernel(const TS* score, const TL* _
     key[i] = k;
     word[i] = (unsigned int)g | (positive ? 0x80000000u : 0u);
   }
-  __shared__ unsigned long long wn[MB / 64], wg[MB / 64];
-  __shared__ unsigned int wm[MB / 64];
-  nan = wave_sum(nan); neg = wave_sum(neg);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const unsigned int t = __shfl_down(mx, o, 64); mx = t > mx ? t : mx; }
-  if ((threadIdx.x & 63) == 0) { wn[threadIdx.x >> 6] = nan; wg[threadIdx.x >> 6] = neg; wm[threadIdx.x >> 6] = mx; }
-  __syncthreads();
+  const KeyPart s = block_join(KeyPart{nan, neg, mx});
   if (threadIdx.x == 0) {
-    unsigned long long a = 0, b = 0; unsigned int c = 0;
-    for (int w = 0; w < MB / 64; ++w) { a += wn[w]; b += wg[w]; c = wm[w] > c ? wm[w] : c; }
-    if (a) atomicAdd(&res->nan, a);
-    if (b) atomicAdd(&res->neg, b);
-    if (c) atomicMax(&res->maxid, c);
+    if (s.nan) atomicAdd(&res->nan, s.nan);
+    if (s.neg) atomicAdd(&res->neg, s.neg);
+    if (s.maxid) atomicMax(&res->maxid, s.maxid);
   }
 }
 
@@ -169,28 +174,6 @@ __global__ __launch_bounds__(MB) void gm_terms_kernel(const unsigned int* __rest
   if (lane == 0 && carry_g != NONE && carry) atomicAdd(&S[carry_g], carry);
 }
 
-// the workgroup's sums in a fixed order (lane tree, then the waves in order); valid in thread 0
-__device__ __forceinline__ GroupPart group_block_sum(GroupPart v) {
-  __shared__ GroupPart wp[MB / 64];
-  v.valid_groups = wave_sum(v.valid_groups); v.valid_rows = wave_sum(v.valid_rows); v.pos_groups = wave_sum(v.pos_groups);
-  v.hits = wave_sum(v.hits); v.pair_num = wave_sum(v.pair_num); v.pair_den = wave_sum(v.pair_den);
-  v.gauc = wave_sum(v.gauc); v.macro = wave_sum(v.macro); v.mrr = wave_sum(v.mrr); v.ndcg = wave_sum(v.ndcg);
-  if ((threadIdx.x & 63) == 0) wp[threadIdx.x >> 6] = v;
-  __syncthreads();
-  GroupPart s{0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0};
-  if (threadIdx.x == 0)
-    for (int w = 0; w < MB / 64; ++w) {
-      s.valid_groups += wp[w].valid_groups; s.valid_rows += wp[w].valid_rows; s.pos_groups += wp[w].pos_groups;
-      s.hits += wp[w].hits; s.pair_num += wp[w].pair_num; s.pair_den += wp[w].pair_den;
-      s.gauc += wp[w].gauc; s.macro += wp[w].macro; s.mrr += wp[w].mrr; s.ndcg += wp[w].ndcg;
-    }
-  return s;
-}
-__device__ __forceinline__ void part_add(GroupPart& a, const GroupPart& b) {
-  a.valid_groups += b.valid_groups; a.valid_rows += b.valid_rows; a.pos_groups += b.pos_groups; a.hits += b.hits;
-  a.pair_num += b.pair_num; a.pair_den += b.pair_den; a.gauc += b.gauc; a.macro += b.macro; a.mrr += b.mrr; a.ndcg += b.ndcg;
-}
-
 // group g = sorted rows gheads[g] .. gheads[g+1) (the last one ends at n).  disc[r] = 1 / log2(r + 2), idcg[j] = sum of disc[0..j]
 __global__ __launch_bounds__(MB) void gm_groups_kernel(const unsigned int* __restrict__ gheads, const unsigned int* __restrict__ eh,
                                                        const unsigned int* __restrict__ word, const unsigned long long* __restrict__ S,
@@ -199,7 +182,7 @@ __global__ __launch_bounds__(MB) void gm_groups_kernel(const unsigned int* __res
                                                        goctr_group_stat* stat, long long cap, GroupPart* __restrict__ part) {
   const long long G = (long long)res->G;
   const unsigned long long P = res->P;
-  GroupPart a{0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0};
+  GroupPart a = GroupPart::identity();
   for (long long g = (long long)blockIdx.x * MB + threadIdx.x; g < G; g += (long long)gridDim.x * MB) {
     const long long gs = gheads[g];
     const unsigned long long e0 = eh[gs] & 0x7fffffffu;
@@ -247,16 +230,8 @@ __global__ __launch_bounds__(MB) void gm_groups_kernel(const unsigned int* __res
       stat[g] = st;
     }
   }
-  const GroupPart s = group_block_sum(a);
+  const GroupPart s = block_join(a);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
-}
-
-// the groups kernel's partials in a fixed order: thread t sums t, t + MB, ..., then group_block_sum
-__global__ __launch_bounds__(MB) void gm_finish_kernel(const GroupPart* __restrict__ part, int nparts, GroupPart* out) {
-  GroupPart a{0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0};
-  for (int i = threadIdx.x; i < nparts; i += MB) part_add(a, part[i]);
-  const GroupPart s = group_block_sum(a);
-  if (threadIdx.x == 0) *out = s;
 }
 
 // ---------------------------------------------------------------- per-engine scratch
@@ -276,13 +251,6 @@ struct GroupWs {
   }
 };
 
-int ws_failed(GroupWs& w, size_t want, int64_t n, const char* who) {
-  w.release();
-  (void)hipGetLastError();
-  set_error("%s: could not allocate %zu bytes of device scratch for %lld rows", who, want, (long long)n);
-  return -1;
-}
-
 // high-water growth of the per-row scratch for n rows of kb-byte keys and sorts that need temp_bytes
 int ensure_rows(GroupWs& w, int64_t n, size_t kb, size_t temp_bytes, const char* who) {
   const size_t kbytes = (size_t)n * kb, rows = (size_t)n;
@@ -291,7 +259,7 @@ int ensure_rows(GroupWs& w, int64_t n, size_t kb, size_t temp_bytes, const char*
       w.gflag.ensure(rows, false) || w.gheads.ensure(rows, false) || radix_sort_scratch(w.temp, temp_bytes) ||
       w.tiles.ensure((size_t)cdiv(n, SCAN_TILE), false) || w.part.ensure(MKEY_MAX_BLOCKS + 1, false) || w.res.ensure(1, false) ||
       w.disc.ensure(2 * GM_KMAX, false))
-    return ws_failed(w, want, n, who);
+    return metrics_rows_alloc_failed(w, want, n, who);
   return 0;
 }
 
@@ -335,7 +303,7 @@ int run(const TS* score, const TL* y, const int32_t* group, int64_t n, int k, go
   GOCTR_HIP(hipMemcpyAsync(w.disc.p, table, sizeof(table), hipMemcpyHostToDevice, s));
   GroupRes* res = w.res.p;
   GOCTR_HIP(hipMemsetAsync(res, 0, sizeof(GroupRes), s));
-  const int nblocks = (int)std::min<int64_t>(cdiv(n, MB), MKEY_MAX_BLOCKS);
+  const int nblocks = metrics_grid(n, MB);
   hipLaunchKernelGGL((gm_key_kernel<TS, TL, K>), dim3((unsigned)nblocks), dim3(MB), 0, s, score, y, group, (long long)n, ka, w.wa.p,
                      res);
   GOCTR_HIP(hipGetLastError());
@@ -353,7 +321,7 @@ int run(const TS* score, const TL* y, const int32_t* group, int64_t n, int k, go
   if (bits > 0) {
     size_t temp2 = 0;
     if (radix_sort_pairs_bytes<false, unsigned int, K>((size_t)n, bits, s, &temp2)) return -1;
-    if (radix_sort_scratch(w.temp, temp2)) return ws_failed(w, temp2, n, who);
+    if (radix_sort_scratch(w.temp, temp2)) return metrics_rows_alloc_failed(w, temp2, n, who);
     if (radix_sort_pairs(w.temp, w.wb.p, w.wa.p, kb, ka, (size_t)n, bits, s)) return -1;
     ks = ka; ws = w.wa.p; kf = kb; wf = w.wb.p;
   }
@@ -369,14 +337,14 @@ int run(const TS* score, const TL* y, const int32_t* group, int64_t n, int k, go
               who, h.G, h.T, (long long)n);
   const int64_t G = (int64_t)h.G, T = (int64_t)h.T, nstat = std::min<int64_t>(G, cap);
   if (w.S.ensure((size_t)G, false) || w.stat.ensure((size_t)std::max<int64_t>(nstat, 1), false))
-    return ws_failed(w, (size_t)G * 8 + (size_t)nstat * sizeof(goctr_group_stat), n, who);
+    return metrics_rows_alloc_failed(w, (size_t)G * 8 + (size_t)nstat * sizeof(goctr_group_stat), n, who);
   GOCTR_HIP(hipMemsetAsync(w.S.p, 0, sizeof(unsigned long long) * (size_t)G, s));
-  const int tblocks = (int)std::min<int64_t>(cdiv(T, MB), MKEY_MAX_BLOCKS);
-  const int gblocks = (int)std::min<int64_t>(cdiv(G, MB), MKEY_MAX_BLOCKS);
+  const int tblocks = metrics_grid(T, MB), gblocks = metrics_grid(G, MB);
   hipLaunchKernelGGL(gm_terms_kernel, dim3((unsigned)tblocks), dim3(MB), 0, s, ties, eh, gidx, w.gheads.p, (long long)n, res, w.S.p);
   hipLaunchKernelGGL(gm_groups_kernel, dim3((unsigned)gblocks), dim3(MB), 0, s, w.gheads.p, eh, ws, w.S.p, (long long)n, k, w.disc.p,
                      w.disc.p + GM_KMAX, res, w.stat.p, (long long)nstat, w.part.p);
-  hipLaunchKernelGGL(gm_finish_kernel, dim3(1), dim3(MB), 0, s, w.part.p, gblocks, w.part.p + MKEY_MAX_BLOCKS);
+  hipLaunchKernelGGL(metrics_fold_kernel<GroupPart>, dim3(1), dim3(MB), 0, s, (const GroupPart*)w.part.p, gblocks,
+                     w.part.p + MKEY_MAX_BLOCKS);
   GOCTR_HIP(hipGetLastError());
   GroupPart t{};
   std::vector<goctr_group_stat> stats((size_t)nstat);
@@ -403,18 +371,17 @@ int run(const TS* score, const TL* y, const int32_t* group, int64_t n, int k, go
 
 }  // namespace
 
-int metrics_grouped_dev(const float* score, const float* y, const int32_t* group, int64_t n, int k, goctr_group_metrics* out,
+template <class TS, class TL>
+int metrics_grouped_dev(const TS* score, const TL* y, const int32_t* group, int64_t n, int k, goctr_group_metrics* out,
                         goctr_group_stat* per_group, int64_t cap, const char* who) {
   return run(score, y, group, n, k, out, per_group, cap, who);
 }
-int metrics_grouped_dev(const double* score, const double* y, const int32_t* group, int64_t n, int k, goctr_group_metrics* out,
-                        goctr_group_stat* per_group, int64_t cap, const char* who) {
-  return run(score, y, group, n, k, out, per_group, cap, who);
-}
-int metrics_grouped_dev(const double* score, const float* y, const int32_t* group, int64_t n, int k, goctr_group_metrics* out,
-                        goctr_group_stat* per_group, int64_t cap, const char* who) {
-  return run(score, y, group, n, k, out, per_group, cap, who);
-}
+template int metrics_grouped_dev<float, float>(const float*, const float*, const int32_t*, int64_t, int, goctr_group_metrics*,
+                                               goctr_group_stat*, int64_t, const char*);
+template int metrics_grouped_dev<double, double>(const double*, const double*, const int32_t*, int64_t, int, goctr_group_metrics*,
+                                                 goctr_group_stat*, int64_t, const char*);
+template int metrics_grouped_dev<double, float>(const double*, const float*, const int32_t*, int64_t, int, goctr_group_metrics*,
+                                                goctr_group_stat*, int64_t, const char*);
 
 }  // namespace goctr
 

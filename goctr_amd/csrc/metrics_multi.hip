@@ -9,9 +9,8 @@
 //              over gridDim.y): consecutive lanes read consecutive columns of a row, and a thread meets ONE column only.  Every
 //              thread sums its column's terms over its rows in grid-stride order (sum_y, ss_res, sum_abs; max_abs; the count of
 //              non-finite values); then the lanes of a wavefront that share the column (lane tree from 32 down to Kt), then the
-//              wavefronts / row groups in order through LDS: one partial per (row block, column)
-//   finish 1   one workgroup per column: thread t adds partials t, t + MB, ... in order, then the lane tree, then the waves in
-//              order; mean_y = sum_y / n by one IEEE division
+//              wavefronts / row groups in order through LDS (reg_block): one partial per (row block, column)
+//   finish 1   one workgroup per column: its partials in metrics_reduce.h's fixed order; mean_y = sum_y / n by one IEEE division
 //   pass 2     the same walk over y against the device's mean_y: ss_tot's terms;  finish 2 as finish 1
 //   Every order is a function of (n, K) alone; no atomics.
 // Confusion (label, pred [n]; cells of C x C 64-bit counters on the device, zeroed per call):
@@ -25,8 +24,8 @@
 //   All integer: the order cannot matter.
 // Multi-class rows (proba [n][C], label [n]; one read of proba): a row is owned by G = 1 .. 64 consecutive lanes (a power of two near
 //   C / 4), which stride over its columns; (maximum, smallest index), the rank count and the NaN flag are combined by a butterfly
-//   inside the group.  pred[r] stays on the device for the confusion stage; per workgroup one partial of (top-k hits, log-loss sum
-//   in thread / lane-tree / wave order, NaN count, bad labels), reduced by one workgroup in a fixed order.
+//   inside the group.  pred[r] stays on the device for the confusion stage; per workgroup one partial of (top-k hits, log-loss sum,
+//   NaN count, bad labels), folded by one workgroup: metrics_reduce.h's fixed order.
 // One-vs-rest: per class a kernel writes the column and the 0 / 1 indicator contiguously and metrics_curve_dev runs on them; micro
 //   is the same call over proba itself with an [n][C] indicator.
 // Scratch (engine_scratch<MultiWs>, high-water): the host entry points' staged inputs; at most 2^18 x 40 bytes of regression
@@ -48,31 +47,27 @@ constexpr int CONF_LDS_CLASSES = 128;     // the LDS table while C x C 32-bit ce
 constexpr int REG_MAX_PARTS = 1 << 18;    // (row block, column) partials of a regression pass at most
 
 // ---------------------------------------------------------------- regression
-struct RegPart { double sy, sr, sa, mx; unsigned long long bad; };
+struct RegPart {
+  double sy, sr, sa, mx;
+  unsigned long long bad;
+  static __device__ __forceinline__ RegPart identity() { return RegPart{0.0, 0.0, 0.0, 0.0, 0}; }   // mx: a maximum of |d| >= 0
+  __device__ __forceinline__ void join(const RegPart& b) { sy += b.sy; sr += b.sr; sa += b.sa; mx = fmax(mx, b.mx); bad += b.bad; }
+};
 // what the host reads per column
 struct RegCol { double sum_y, mean_y, ss_res, sum_abs, ss_tot, max_abs; unsigned long long bad; };
 
-__device__ __forceinline__ void reg_add(RegPart& s, const RegPart& v) {
-  s.sy += v.sy; s.sr += v.sr; s.sa += v.sa; s.mx = fmax(s.mx, v.mx); s.bad += v.bad;
-}
-__device__ __forceinline__ RegPart reg_shfl_down(const RegPart& v, int o) {
-  RegPart t;
-  t.sy = __shfl_down(v.sy, o, 64); t.sr = __shfl_down(v.sr, o, 64); t.sa = __shfl_down(v.sa, o, 64);
-  t.mx = __shfl_down(v.mx, o, 64); t.bad = __shfl_down(v.bad, o, 64);
-  return t;
-}
-
 // threads that share threadIdx.x % period hold the same column: their sum in a fixed order (lane tree down to the period, then the
-// wavefronts / row groups in order); valid in threads 0 .. period - 1.  period: a power of two, 1 .. MB.
+// wavefronts / row groups in order); valid in threads 0 .. period - 1.  period: a power of two, 1 .. MB.  At period 1 this is
+// metrics_reduce.h's block_join; it is not folded into it because it needs MB slots of LDS where block_join needs MB / 64.
 __device__ __forceinline__ RegPart reg_block(RegPart v, int period) {
   __shared__ RegPart sh[MB];
-  for (int o = 32; o >= period; o >>= 1) reg_add(v, reg_shfl_down(v, o));
+  for (int o = 32; o >= period; o >>= 1) v.join(part_shfl_down(v, o));
   sh[threadIdx.x] = v;
   __syncthreads();
-  RegPart s{0.0, 0.0, 0.0, 0.0, 0};
+  RegPart s = RegPart::identity();
   if ((int)threadIdx.x < period) {
-    if (period < 64) for (int w = 0; w < MB / 64; ++w) reg_add(s, sh[w * 64 + threadIdx.x]);
-    else for (int j = threadIdx.x; j < MB; j += period) reg_add(s, sh[j]);
+    if (period < 64) for (int w = 0; w < MB / 64; ++w) s.join(sh[w * 64 + threadIdx.x]);
+    else for (int j = threadIdx.x; j < MB; j += period) s.join(sh[j]);
   }
   return s;
 }
@@ -83,7 +78,7 @@ __global__ __launch_bounds__(MB) void reg_pass_kernel(const TP* __restrict__ pre
                                                       const RegCol* __restrict__ col, RegPart* __restrict__ part) {
   const int R = MB / Kt, ct = threadIdx.x % Kt, rs = threadIdx.x / Kt;
   const int c = blockIdx.y * Kt + ct;
-  RegPart a{0.0, 0.0, 0.0, 0.0, 0};
+  RegPart a = RegPart::identity();
   if (c < K) {
     const double m = col ? col[c].mean_y : 0.0;
     for (long long r = (long long)blockIdx.x * R + rs; r < n; r += (long long)gridDim.x * R) {
@@ -103,13 +98,11 @@ __global__ __launch_bounds__(MB) void reg_pass_kernel(const TP* __restrict__ pre
   if ((int)threadIdx.x < Kt && c < K) part[(size_t)blockIdx.x * K + c] = s;
 }
 
-// one workgroup per column: the nbx partials in a fixed order
+// one workgroup per column: the nbx partials in the fixed order
 __global__ __launch_bounds__(MB) void reg_finish_kernel(const RegPart* __restrict__ part, int nbx, int K, long long n, int second,
                                                         RegCol* __restrict__ col) {
   const int c = blockIdx.x;
-  RegPart a{0.0, 0.0, 0.0, 0.0, 0};
-  for (int i = threadIdx.x; i < nbx; i += MB) reg_add(a, part[(size_t)i * K + c]);
-  const RegPart s = reg_block(a, 1);
+  const RegPart s = reg_block(join_strided(part + c, nbx, (size_t)K), 1);
   if (threadIdx.x != 0) return;
   if (second) {
     col[c].ss_tot = s.sr;
@@ -197,31 +190,17 @@ __global__ __launch_bounds__(MB) void conf_stats_kernel(const unsigned long long
   const int c = blockIdx.x;
   unsigned long long row = 0, colsum = 0;
   for (int j = threadIdx.x; j < C; j += MB) { row += cm[(size_t)c * C + j]; colsum += cm[(size_t)j * C + c]; }
-  __shared__ unsigned long long ws[2][MB / 64];
-  row = wave_sum(row); colsum = wave_sum(colsum);
-  if ((threadIdx.x & 63) == 0) { ws[0][threadIdx.x >> 6] = row; ws[1][threadIdx.x >> 6] = colsum; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    ClassCount s{0, 0, cm[(size_t)c * C + c]};
-    for (int w = 0; w < MB / 64; ++w) { s.support += ws[0][w]; s.predicted += ws[1][w]; }
-    stats[c] = s;
-  }
+  const Sums<unsigned long long, 2> s = block_join(Sums<unsigned long long, 2>{{row, colsum}});
+  if (threadIdx.x == 0) stats[c] = ClassCount{s.v[0], s.v[1], cm[(size_t)c * C + c]};
 }
 
 // ---------------------------------------------------------------- multi-class rows
-struct RowPart { unsigned long long topk, nan, bad; double ll; };
-
-// the workgroup's sums in a fixed order (lane tree, then the waves in order); valid in thread 0
-__device__ __forceinline__ RowPart row_block(RowPart v) {
-  __shared__ RowPart wp[MB / 64];
-  v.topk = wave_sum(v.topk); v.nan = wave_sum(v.nan); v.bad = wave_sum(v.bad); v.ll = wave_sum(v.ll);
-  if ((threadIdx.x & 63) == 0) wp[threadIdx.x >> 6] = v;
-  __syncthreads();
-  RowPart s{0, 0, 0, 0.0};
-  if (threadIdx.x == 0)
-    for (int w = 0; w < MB / 64; ++w) { s.topk += wp[w].topk; s.nan += wp[w].nan; s.bad += wp[w].bad; s.ll += wp[w].ll; }
-  return s;
-}
+struct RowPart {
+  unsigned long long topk, nan, bad;
+  double ll;
+  static __device__ __forceinline__ RowPart identity() { return RowPart{0, 0, 0, 0.0}; }
+  __device__ __forceinline__ void join(const RowPart& b) { topk += b.topk; nan += b.nan; bad += b.bad; ll += b.ll; }
+};
 
 // G consecutive lanes own a row (G: a power of two, 1 .. 64).  The row loop is uniform over the workgroup: the shuffles need every lane.
 template <class TP>
@@ -229,7 +208,7 @@ __global__ __launch_bounds__(MB) void mc_row_kernel(const TP* __restrict__ proba
                                                     int top_k, int* __restrict__ pred, RowPart* __restrict__ part) {
   const int gl = threadIdx.x & (G - 1), rows = MB / G;
   const double hmin = __longlong_as_double(1ll), hmax = __longlong_as_double(0x3fefffffffffffffll);   // Nextafter(0, 1), Nextafter(1, 0)
-  RowPart a{0, 0, 0, 0.0};
+  RowPart a = RowPart::identity();
   for (long long base = (long long)blockIdx.x * rows; base < n; base += (long long)gridDim.x * rows) {
     const long long r = base + threadIdx.x / G;
     const bool live = r < n;
@@ -266,16 +245,8 @@ __global__ __launch_bounds__(MB) void mc_row_kernel(const TP* __restrict__ proba
       }
     }
   }
-  const RowPart s = row_block(a);
+  const RowPart s = block_join(a);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
-}
-
-// the row kernel's partials in a fixed order: thread t takes t, t + MB, ..., then row_block
-__global__ __launch_bounds__(MB) void mc_finish_kernel(const RowPart* __restrict__ part, int nparts, RowPart* __restrict__ head) {
-  RowPart a{0, 0, 0, 0.0};
-  for (int i = threadIdx.x; i < nparts; i += MB) { a.topk += part[i].topk; a.nan += part[i].nan; a.bad += part[i].bad; a.ll += part[i].ll; }
-  const RowPart s = row_block(a);
-  if (threadIdx.x == 0) *head = s;
 }
 
 // column c of proba and the indicator label == c, contiguously
@@ -334,14 +305,6 @@ struct MultiWs {
   DevBuf<unsigned long long> multi;
 };
 
-int grid_for(int64_t items, int per_block) { return (int)std::min<int64_t>(cdiv(items, per_block), MKEY_MAX_BLOCKS); }
-
-int alloc_failed(const char* who, const char* what) {
-  (void)hipGetLastError();
-  set_error("%s: could not allocate the device scratch of %s", who, what);
-  return -1;
-}
-
 // ---------------------------------------------------------------- regression: host side
 int regression_check(int64_t n, int K, const char* who) {
   GOCTR_CHECK(K >= 1 && K <= MULTI_MAX_COLS, "%s: k = %d columns (1 .. %d are accepted)", who, K, MULTI_MAX_COLS);
@@ -361,7 +324,7 @@ int run_regression(const TP* pred, const TY* y, int64_t n, int K, goctr_regressi
   const size_t elems = (size_t)n * (size_t)K;
   if ((host_pred && (w.in_a.ensure(elems * sizeof(TP), false) || w.in_b.ensure(elems * sizeof(TY), false))) ||
       w.rpart.ensure((size_t)nbx * K, false) || w.rcol.ensure((size_t)K, false))
-    return alloc_failed(who, "the regression sums");
+    return metrics_alloc_failed(who, "the device scratch of the regression sums");
   if (host_pred) {
     GOCTR_HIP(hipMemcpyAsync(w.in_a.p, host_pred, elems * sizeof(TP), hipMemcpyHostToDevice, s));
     GOCTR_HIP(hipMemcpyAsync(w.in_b.p, host_y, elems * sizeof(TY), hipMemcpyHostToDevice, s));
@@ -416,7 +379,7 @@ int confusion_check(int C, double beta, const char* who) {
 int confusion_ensure(MultiWs& w, int64_t n, int C, const char* who) {
   if (w.cm.ensure((size_t)C * C + 1, false) || w.stats.ensure((size_t)C, false) ||
       (C > CONF_LDS_CLASSES && (w.kin.ensure((size_t)n, false) || w.kout.ensure((size_t)n, false))))
-    return alloc_failed(who, "the confusion matrix");
+    return metrics_alloc_failed(who, "the device scratch of the confusion matrix");
   return 0;
 }
 
@@ -433,10 +396,10 @@ int confusion_queue(MultiWs& w, const int* label, const int* pred, int64_t n, in
   } else {
     unsigned int bits = 1;
     while ((1u << bits) <= (unsigned int)(C * C)) ++bits;          // the keys 0 .. C x C
-    hipLaunchKernelGGL(conf_key_kernel, dim3((unsigned)grid_for(n, MB)), dim3(MB), 0, s, label, pred, (long long)n, C, w.kin.p, w.cm.p);
+    hipLaunchKernelGGL(conf_key_kernel, dim3((unsigned)metrics_grid(n, MB)), dim3(MB), 0, s, label, pred, (long long)n, C, w.kin.p, w.cm.p);
     GOCTR_HIP(hipGetLastError());
     if (radix_sort_keys(w.temp, w.kin.p, w.kout.p, (size_t)n, bits, s)) return -1;
-    hipLaunchKernelGGL(conf_bounds_kernel, dim3((unsigned)grid_for(n, MB)), dim3(MB), 0, s, (const unsigned int*)w.kout.p, (long long)n, C,
+    hipLaunchKernelGGL(conf_bounds_kernel, dim3((unsigned)metrics_grid(n, MB)), dim3(MB), 0, s, (const unsigned int*)w.kout.p, (long long)n, C,
                        w.cm.p);
   }
   hipLaunchKernelGGL(conf_stats_kernel, dim3((unsigned)C), dim3(MB), 0, s, (const unsigned long long*)w.cm.p, C, w.stats.p);
@@ -505,7 +468,8 @@ int run_confusion(const int32_t* host_label, const int32_t* host_pred, int64_t n
   if (confusion_check(C, beta, who) || metrics_check_rows(n, who)) return -1;
   hipStream_t s = engine().stream;
   MultiWs& w = engine_scratch<MultiWs>();
-  if (w.in_a.ensure((size_t)n * 4, false) || w.in_b.ensure((size_t)n * 4, false)) return alloc_failed(who, "the labels");
+  if (w.in_a.ensure((size_t)n * 4, false) || w.in_b.ensure((size_t)n * 4, false))
+    return metrics_alloc_failed(who, "the device scratch of the labels");
   if (confusion_ensure(w, n, C, who)) return -1;
   GOCTR_HIP(hipMemcpyAsync(w.in_a.p, host_label, (size_t)n * 4, hipMemcpyHostToDevice, s));
   GOCTR_HIP(hipMemcpyAsync(w.in_b.p, host_pred, (size_t)n * 4, hipMemcpyHostToDevice, s));
@@ -536,9 +500,7 @@ int run_multiclass(const TP* proba, const int* label, int64_t n, int C, const go
                    goctr_multiclass_metrics* out, goctr_class_stat* per_class, uint64_t* cm, const char* who,
                    const TP* host_proba = nullptr, const int32_t* host_label = nullptr) {
   if (metrics_multiclass_check(C, cfg, who) || metrics_check_rows(n, who)) return -1;
-  goctr_multiclass_cfg c;
-  goctr_multiclass_cfg_default(&c);
-  if (cfg) c = *cfg;
+  const goctr_multiclass_cfg c = cfg_or_default(cfg, goctr_multiclass_cfg_default);
   hipStream_t s = engine().stream;
   MultiWs& w = engine_scratch<MultiWs>();
   const size_t elems = (size_t)n * (size_t)C;
@@ -546,7 +508,7 @@ int run_multiclass(const TP* proba, const int* label, int64_t n, int C, const go
   if ((host_proba && (w.in_a.ensure(elems * sizeof(TP), false) || w.in_b.ensure((size_t)n * 4, false))) ||
       w.pred.ensure((size_t)n, false) || w.mpart.ensure(MKEY_MAX_BLOCKS + 1, false) ||
       (c.ovr && (w.col.ensure((size_t)n * sizeof(TP), false) || w.ind.ensure((micro ? elems : (size_t)n) * sizeof(TP), false))))
-    return alloc_failed(who, "the rows");
+    return metrics_alloc_failed(who, "the device scratch of the rows");
   if (confusion_ensure(w, n, C, who)) return -1;
   if (host_proba) {
     GOCTR_HIP(hipMemcpyAsync(w.in_a.p, host_proba, elems * sizeof(TP), hipMemcpyHostToDevice, s));
@@ -554,11 +516,11 @@ int run_multiclass(const TP* proba, const int* label, int64_t n, int C, const go
     proba = reinterpret_cast<const TP*>(w.in_a.p);
     label = reinterpret_cast<const int*>(w.in_b.p);
   }
-  const int G = row_group(C), nparts = grid_for(n, MB / G);
+  const int G = row_group(C), nparts = metrics_grid(n, MB / G);
   RowPart* head = w.mpart.p + MKEY_MAX_BLOCKS;
   hipLaunchKernelGGL(mc_row_kernel<TP>, dim3((unsigned)nparts), dim3(MB), 0, s, proba, label, (long long)n, C, G, (int)c.top_k, w.pred.p,
                      w.mpart.p);
-  hipLaunchKernelGGL(mc_finish_kernel, dim3(1), dim3(MB), 0, s, (const RowPart*)w.mpart.p, nparts, head);
+  hipLaunchKernelGGL(metrics_fold_kernel<RowPart>, dim3(1), dim3(MB), 0, s, (const RowPart*)w.mpart.p, nparts, head);
   GOCTR_HIP(hipGetLastError());
   if (confusion_queue(w, label, w.pred.p, n, C)) return -1;
   RowPart h{};
@@ -581,7 +543,7 @@ int run_multiclass(const TP* proba, const int* label, int64_t n, int C, const go
   const double nanv = std::nan("");
   r.auc_macro = r.auc_weighted = r.auc_micro = r.ap_macro = r.ap_weighted = r.ap_micro = nanv;
   if (c.ovr) {
-    const int blocks = grid_for(n, MB);
+    const int blocks = metrics_grid(n, MB);
     TP* col = reinterpret_cast<TP*>(w.col.p);
     TP* ind = reinterpret_cast<TP*>(w.ind.p);
     goctr_curve_metrics cv;
@@ -605,7 +567,7 @@ int run_multiclass(const TP* proba, const int* label, int64_t n, int C, const go
     r.auc_macro = am / (double)r.auc_classes; r.ap_macro = pm / (double)r.auc_classes;
     r.auc_weighted = aw / (double)sup; r.ap_weighted = pw / (double)sup;
     if (micro) {
-      hipLaunchKernelGGL(mc_indicator_kernel<TP>, dim3((unsigned)grid_for((int64_t)elems, MB)), dim3(MB), 0, s, label, (long long)n, C, ind);
+      hipLaunchKernelGGL(mc_indicator_kernel<TP>, dim3((unsigned)metrics_grid((int64_t)elems, MB)), dim3(MB), 0, s, label, (long long)n, C, ind);
       GOCTR_HIP(hipGetLastError());
       if (metrics_curve_dev(proba, ind, (int64_t)elems, nullptr, &cv, nullptr, nullptr, who)) return -1;
       r.auc_micro = cv.base.auc; r.ap_micro = cv.average_precision;
@@ -619,46 +581,43 @@ int run_multiclass(const TP* proba, const int* label, int64_t n, int C, const go
 }  // namespace
 
 int metrics_multiclass_check(int C, const goctr_multiclass_cfg* cfg, const char* who) {
-  goctr_multiclass_cfg c;
-  goctr_multiclass_cfg_default(&c);
-  if (cfg) c = *cfg;
+  const goctr_multiclass_cfg c = cfg_or_default(cfg, goctr_multiclass_cfg_default);
   if (confusion_check(C, c.beta, who)) return -1;
   GOCTR_CHECK(c.top_k >= 1 && c.top_k <= C, "%s: top_k = %d (1 .. %d, the classes, are accepted)", who, c.top_k, C);
   return 0;
 }
 
-int metrics_regression_dev(const float* pred, const float* y, int64_t n, int K, goctr_regression_metrics* out,
+template <class TP, class TY>
+int metrics_regression_dev(const TP* pred, const TY* y, int64_t n, int K, goctr_regression_metrics* out,
                            goctr_regression_col* per_col, const char* who) {
   return run_regression(pred, y, n, K, out, per_col, who);
 }
-int metrics_regression_dev(const double* pred, const double* y, int64_t n, int K, goctr_regression_metrics* out,
-                           goctr_regression_col* per_col, const char* who) {
-  return run_regression(pred, y, n, K, out, per_col, who);
-}
-int metrics_regression_dev(const double* pred, const float* y, int64_t n, int K, goctr_regression_metrics* out,
-                           goctr_regression_col* per_col, const char* who) {
-  return run_regression(pred, y, n, K, out, per_col, who);
-}
+template int metrics_regression_dev<float, float>(const float*, const float*, int64_t, int, goctr_regression_metrics*,
+                                                  goctr_regression_col*, const char*);
+template int metrics_regression_dev<double, double>(const double*, const double*, int64_t, int, goctr_regression_metrics*,
+                                                    goctr_regression_col*, const char*);
+template int metrics_regression_dev<double, float>(const double*, const float*, int64_t, int, goctr_regression_metrics*,
+                                                   goctr_regression_col*, const char*);
 
-int metrics_multiclass_dev(const float* proba, const int32_t* label, int64_t n, int C, const goctr_multiclass_cfg* cfg,
+template <class TP>
+int metrics_multiclass_dev(const TP* proba, const int32_t* label, int64_t n, int C, const goctr_multiclass_cfg* cfg,
                            int64_t multi_label_rows, goctr_multiclass_metrics* out, goctr_class_stat* per_class, uint64_t* cm,
                            const char* who) {
   return run_multiclass(proba, label, n, C, cfg, multi_label_rows, out, per_class, cm, who);
 }
-int metrics_multiclass_dev(const double* proba, const int32_t* label, int64_t n, int C, const goctr_multiclass_cfg* cfg,
-                           int64_t multi_label_rows, goctr_multiclass_metrics* out, goctr_class_stat* per_class, uint64_t* cm,
-                           const char* who) {
-  return run_multiclass(proba, label, n, C, cfg, multi_label_rows, out, per_class, cm, who);
-}
+template int metrics_multiclass_dev<float>(const float*, const int32_t*, int64_t, int, const goctr_multiclass_cfg*, int64_t,
+                                           goctr_multiclass_metrics*, goctr_class_stat*, uint64_t*, const char*);
+template int metrics_multiclass_dev<double>(const double*, const int32_t*, int64_t, int, const goctr_multiclass_cfg*, int64_t,
+                                            goctr_multiclass_metrics*, goctr_class_stat*, uint64_t*, const char*);
 
 int metrics_onehot_labels_dev(const float* Y, int64_t n, int C, int32_t* label, int64_t* multi_label_rows, const char* who) {
   if (metrics_check_rows(n, who)) return -1;
   GOCTR_CHECK(C >= 1, "%s: %d target columns", who, C);
   hipStream_t s = engine().stream;
   MultiWs& w = engine_scratch<MultiWs>();
-  if (w.multi.ensure(1, false)) return alloc_failed(who, "the label count");
+  if (w.multi.ensure(1, false)) return metrics_alloc_failed(who, "the device scratch of the label count");
   GOCTR_HIP(hipMemsetAsync(w.multi.p, 0, sizeof(unsigned long long), s));
-  hipLaunchKernelGGL(mc_onehot_kernel, dim3((unsigned)grid_for(n, MB)), dim3(MB), 0, s, Y, (long long)n, C, label, w.multi.p);
+  hipLaunchKernelGGL(mc_onehot_kernel, dim3((unsigned)metrics_grid(n, MB)), dim3(MB), 0, s, Y, (long long)n, C, label, w.multi.p);
   GOCTR_HIP(hipGetLastError());
   unsigned long long m = 0;
   GOCTR_HIP(hipMemcpyAsync(&m, w.multi.p, sizeof(m), hipMemcpyDeviceToHost, s));

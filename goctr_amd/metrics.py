@@ -46,23 +46,30 @@ class BinaryMetrics:
                              np.float32(m.auc32), m.correct, m.logloss)
 
 
+def _abi(first, name):
+    """the ABI of a device metric by its first array's dtype -- float32 takes goctr_<name>, anything else goctr_<name>_f64:
+    (the C function, the ctypes element type, the numpy dtype both arrays are passed in)"""
+    L = capi.load()
+    if np.asarray(first).dtype == np.float32:
+        return getattr(L, "goctr_" + name), C.c_float, np.float32
+    return getattr(L, "goctr_" + name + "_f64"), C.c_double, np.float64
+
+
+def _score_label(score, y, dt):
+    """one column of scores and its labels as contiguous [n] arrays of dtype dt, the same length"""
+    s = np.ascontiguousarray(score, dt).ravel()
+    t = np.ascontiguousarray(y, dt).ravel()
+    if s.size != t.size:
+        raise ValueError(f"{s.size} scores but {t.size} labels")
+    return s, t
+
+
 def binary_metrics(score, y) -> BinaryMetrics:
     """exact ROC-AUC, Accuracy hits and log-loss of one column of scores against labels (positive iff y > 0.5)"""
-    score = np.asarray(score)
-    L = capi.load()
+    fn, ty, dt = _abi(score, "metrics_binary")
+    s, t = _score_label(score, y, dt)
     out = capi.BinaryMetrics()
-    if score.dtype == np.float32:
-        s = np.ascontiguousarray(score, np.float32).ravel()
-        t = np.ascontiguousarray(y, np.float32).ravel()
-        if s.size != t.size:
-            raise ValueError(f"{s.size} scores but {t.size} labels")
-        capi.check(L.goctr_metrics_binary(capi.ptr(s, C.c_float), capi.ptr(t, C.c_float), s.size, C.byref(out)))
-    else:
-        s = np.ascontiguousarray(score, np.float64).ravel()
-        t = np.ascontiguousarray(y, np.float64).ravel()
-        if s.size != t.size:
-            raise ValueError(f"{s.size} scores but {t.size} labels")
-        capi.check(L.goctr_metrics_binary_f64(capi.ptr(s, C.c_double), capi.ptr(t, C.c_double), s.size, C.byref(out)))
+    capi.check(fn(capi.ptr(s, ty), capi.ptr(t, ty), s.size, C.byref(out)))
     return BinaryMetrics.from_c(out)
 
 
@@ -143,16 +150,8 @@ def curve_metrics(score, y, bins=10, threshold=0.5, points=0) -> CurveMetrics:
     """binary_metrics plus, out of the same sort on the device (goctr_metrics_curve / _f64): tp / fp / precision / recall / f1 at
     `threshold`, average precision, KS, the F1-optimal cut, `bins` calibration bins with ECE and normalised entropy, and up to
     `points` curve entries (0: none; at least the group count, e.g. the row count: every group)."""
-    score = np.asarray(score)
-    L = capi.load()
-    if score.dtype == np.float32:
-        fn, ty, dt = L.goctr_metrics_curve, C.c_float, np.float32
-    else:
-        fn, ty, dt = L.goctr_metrics_curve_f64, C.c_double, np.float64
-    s = np.ascontiguousarray(score, dt).ravel()
-    t = np.ascontiguousarray(y, dt).ravel()
-    if s.size != t.size:
-        raise ValueError(f"{s.size} scores but {t.size} labels")
+    fn, ty, dt = _abi(score, "metrics_curve")
+    s, t = _score_label(score, y, dt)
     call = CurveCall(bins, threshold, points)
     capi.check(fn(capi.ptr(s, ty), capi.ptr(t, ty), s.size, *call.args()))
     return call.result()
@@ -293,36 +292,32 @@ class GroupMetrics:
         return GroupMetrics(*(getattr(m, f) for f, _ in capi.GroupMetrics._fields_))
 
 
-def group_ids(group, n) -> np.ndarray:
-    """the group column as the contiguous int32 [n] the C ABI takes (values outside int32 are refused, not wrapped)"""
-    g = np.asarray(group).ravel()
+def class_ids(a, n, what, rows="rows") -> np.ndarray:
+    """a column of ids (`what`: "labels", "group ids", ...) as the contiguous int32 [n] the C ABI takes; values outside int32 are
+    refused, not wrapped"""
+    g = np.asarray(a).ravel()
     if g.size != n:
-        raise ValueError(f"{n} scores but {g.size} group ids")
+        raise ValueError(f"{n} {rows} but {g.size} {what}")
     if g.dtype != np.int32:
         if g.size and (g.min() < -2 ** 31 or g.max() > 2 ** 31 - 1):
-            raise ValueError("group ids must fit int32")
+            raise ValueError(f"{what} must fit int32")
         g = g.astype(np.int32)
     return np.ascontiguousarray(g)
+
+
+def group_ids(group, n) -> np.ndarray:
+    """the group column of n scores (class_ids)"""
+    return class_ids(group, n, "group ids", "scores")
 
 
 def grouped_metrics(score, y, group, k=10, per_group=False):
     """GAUC, the exact same-group pair AUC, HitRate@k, NDCG@k and MRR of one column of scores grouped by `group` (the user of
     every row), on the device (goctr_metrics_grouped / _f64).  per_group: also a structured array (group, rows, positives,
     first_pos, auc_num) of every group in ascending id -- returns (GroupMetrics, array)."""
-    score = np.asarray(score)
-    L = capi.load()
-    out = capi.GroupMetrics()
-    if score.dtype == np.float32:
-        s = np.ascontiguousarray(score, np.float32).ravel()
-        t = np.ascontiguousarray(y, np.float32).ravel()
-        fn, ty = L.goctr_metrics_grouped, C.c_float
-    else:
-        s = np.ascontiguousarray(score, np.float64).ravel()
-        t = np.ascontiguousarray(y, np.float64).ravel()
-        fn, ty = L.goctr_metrics_grouped_f64, C.c_double
-    if s.size != t.size:
-        raise ValueError(f"{s.size} scores but {t.size} labels")
+    fn, ty, dt = _abi(score, "metrics_grouped")
+    s, t = _score_label(score, y, dt)
     g = group_ids(group, s.size)
+    out = capi.GroupMetrics()
     stats, cap = None, 0
     if per_group:
         cap = int(np.unique(g).size)
@@ -403,12 +398,7 @@ def _regression_result(out, cols) -> RegressionMetrics:
 def regression_metrics(pred, y) -> RegressionMetrics:
     """the column sums of pred, y [n][K] (one-dimensional input: one column) on the device and what regression.go / r2Score64
     derive from them (goctr_metrics_regression for float32 pred, else _f64)"""
-    pred = np.asarray(pred)
-    L = capi.load()
-    if pred.dtype == np.float32:
-        fn, ty, dt = L.goctr_metrics_regression, C.c_float, np.float32
-    else:
-        fn, ty, dt = L.goctr_metrics_regression_f64, C.c_double, np.float64
+    fn, ty, dt = _abi(pred, "metrics_regression")
     p = np.ascontiguousarray(pred, dt)
     p = p.reshape(p.shape[0], -1) if p.ndim else p.reshape(1, 1)
     t = np.ascontiguousarray(y, dt).reshape(-1) if np.ndim(y) <= 1 else np.ascontiguousarray(y, dt)
@@ -450,18 +440,6 @@ class ConfusionMetrics:
 
 def _confusion_result(out, per_class, cm) -> ConfusionMetrics:
     return ConfusionMetrics(*(getattr(out, f) for f, _ in capi.ConfusionMetrics._fields_), per_class, cm, bytes(out))
-
-
-def class_ids(a, n, what) -> np.ndarray:
-    """a class column as the contiguous int32 [n] the C ABI takes (values outside int32 are refused, not wrapped)"""
-    g = np.asarray(a).ravel()
-    if g.size != n:
-        raise ValueError(f"{n} rows but {g.size} {what}")
-    if g.dtype != np.int32:
-        if g.size and (g.min() < -2 ** 31 or g.max() > 2 ** 31 - 1):
-            raise ValueError(f"{what} must fit int32")
-        g = g.astype(np.int32)
-    return np.ascontiguousarray(g)
 
 
 def confusion_metrics(label, pred, classes, beta=1.0) -> ConfusionMetrics:
@@ -526,12 +504,7 @@ def multiclass_metrics(proba, label, top_k=1, beta=1.0, ovr=False) -> Multiclass
     """arg-max accuracy, top-k accuracy, log-loss and the confusion figures of probabilities proba [n][C] against class indices
     label [n] on the device (goctr_metrics_multiclass for float32 proba, else _f64); ovr: also the one-vs-rest AUC / AP of
     every class and their macro / weighted / micro means"""
-    proba = np.asarray(proba)
-    L = capi.load()
-    if proba.dtype == np.float32:
-        fn, ty, dt = L.goctr_metrics_multiclass, C.c_float, np.float32
-    else:
-        fn, ty, dt = L.goctr_metrics_multiclass_f64, C.c_double, np.float64
+    fn, ty, dt = _abi(proba, "metrics_multiclass")
     p = np.ascontiguousarray(proba, dt)
     if p.ndim != 2:
         raise ValueError("proba must be [n][C]")
