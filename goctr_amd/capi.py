@@ -160,6 +160,11 @@ class RecallCfg(C.Structure):
     _fields_ = [("history", C.c_int32), ("n_cand", C.c_int32), ("exclude", C.c_int32)]
 
 
+class PopularCfg(C.Structure):
+    """goctr_popular_cfg (include/goctr.h)"""
+    _fields_ = [("half_life", C.c_int64), ("ts_ref", C.c_int64), ("ts_lo", C.c_int64), ("ts_hi", C.c_int64), ("n_list", C.c_int32)]
+
+
 TOPN_KEEP_SEEN, TOPN_DROP_ALL_SEEN, TOPN_DROP_SEEN_BEFORE = 0, 1, 2   # goctr_topn_cfg.exclude
 NS_UNIFORM, NS_POPULARITY, NS_POPULARITY_075 = 0, 1, 2      # goctr_negsample_cfg.weighting
 NS_ALL, NS_NEWEST, NS_ALL_BUT_NEWEST = 0, 1, 2              # goctr_negsample_cfg.which
@@ -202,6 +207,8 @@ SYMBOLS = [
     "goctr_topn_cfg_default", "goctr_recommend_topn",
     "goctr_itemcf_cfg_default", "goctr_itemcf_build", "goctr_itemcf_destroy", "goctr_itemcf_info", "goctr_itemcf_export",
     "goctr_recall_cfg_default", "goctr_itemcf_recall", "goctr_recommend_itemcf",
+    "goctr_popular_cfg_default", "goctr_popular_build", "goctr_popular_destroy", "goctr_popular_info", "goctr_popular_export",
+    "goctr_blend_recall", "goctr_recommend_blend",
 ]
 
 _lib = None
@@ -224,7 +231,7 @@ def load() -> C.CDLL:
                      "goctr_w2v_destroy", "goctr_searcher_destroy", "goctr_ubcache_destroy", "goctr_recsys_destroy", "goctr_train_cfg_default", "goctr_mlp_cfg_default",
                      "goctr_w2v_cfg_default", "goctr_negsample_cfg_default", "goctr_samples_destroy", "goctr_topn_cfg_default",
                      "goctr_itemcf_cfg_default", "goctr_recall_cfg_default", "goctr_itemcf_destroy", "goctr_curve_cfg_default",
-                     "goctr_multiclass_cfg_default"):
+                     "goctr_multiclass_cfg_default", "goctr_popular_cfg_default", "goctr_popular_destroy"):
             getattr(_lib, name).restype = None
         _bm = C.POINTER(BinaryMetrics)
         _lib.goctr_metrics_binary.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, _bm]
@@ -291,6 +298,16 @@ def load() -> C.CDLL:
         _lib.goctr_recommend_itemcf.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32,
                                                 C.POINTER(RecallCfg), C.c_int32, C.c_int64, _i32, _f32, _i32, _i32, _i32, _i64,
                                                 _i32, _u32, _f32, _i64]
+        _lib.goctr_popular_cfg_default.argtypes = [C.POINTER(PopularCfg)]
+        _lib.goctr_popular_build.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PopularCfg), C.POINTER(C.c_void_p)]
+        _lib.goctr_popular_destroy.argtypes = [C.c_void_p]
+        _lib.goctr_popular_info.argtypes = [C.c_void_p, _i64, _i32, _i32, _u64, _i64, _u64]
+        _lib.goctr_popular_export.argtypes = [C.c_void_p, _u32, _u64, _i32, _u64]
+        _lib.goctr_blend_recall.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32, C.c_int32,
+                                            C.POINTER(RecallCfg), C.c_int32, _i32, _u32, _u8, _i32, _i32, _i32]
+        _lib.goctr_recommend_blend.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32, _i32,
+                                               C.c_int32, C.POINTER(RecallCfg), C.c_int32, C.c_int32, C.c_int64, _i32, _f32, _i32,
+                                               _u8, _i32, _i32, _i64, _i32, _u32, _f32, _u8, _i64]
     return _lib
 
 
@@ -432,6 +449,14 @@ def default_itemcf_cfg(**kw) -> ItemcfCfg:
 def default_recall_cfg(**kw) -> RecallCfg:
     c = RecallCfg()
     load().goctr_recall_cfg_default(C.byref(c))
+    for k, v in kw.items():
+        setattr(c, k, v)
+    return c
+
+
+def default_popular_cfg(**kw) -> PopularCfg:
+    c = PopularCfg()
+    load().goctr_popular_cfg_default(C.byref(c))
     for k, v in kw.items():
         setattr(c, k, v)
     return c

@@ -27,11 +27,40 @@ struct ItemcfRecArgs {
   int32_t* out_cand_count; int32_t* out_target_pos; int64_t* out_target_rank;
   int32_t* cand_items; uint32_t* cand_w; float* cand_scores;
   int64_t* n_failed;
+  uint8_t* out_src = nullptr; uint8_t* cand_src = nullptr;   // goctr_recommend_blend's alone: [n_req, k], [n_req, n_cand]
 };
 
 // the refusals that need no slot: cfg ranges, sizes, users against n_users (sets the error text)
 int itemcf_check_recommend(const goctr_itemcf* h, const ItemcfRecArgs& a, int64_t n_users, int64_t n_items);
 // the whole call over a prepared slot; returns after the results are in the caller's arrays (the stream is drained on every path)
 int itemcf_recommend_run(const TopnScorer& sc, const goctr_itemcf* h, const ItemcfRecArgs& a);
+
+// ---- what a further recall source (popular.hip: the blend) shares with the ItemCF entries
+int recall_check_cfg(const goctr_recall_cfg* cfg, const char* who);
+int recall_check_users(const int32_t* users, int64_t n_req, int64_t n_users, const char* who);
+// itemcf_check_recommend without the handle: the output pointers, the recall cfg, k, pass_rows, the users
+int recall_check_recommend(const char* who, const ItemcfRecArgs& a, int64_t n_users);
+
+// the device-side inputs of a call: users, ts (zeros when the caller gave none), targets
+struct RecallInputs {
+  DevBuf<int32_t> users, targets;
+  DevBuf<long long> ts;
+  int stage(const int32_t* h_users, const int64_t* h_ts, const int32_t* h_targets, int64_t nq, hipStream_t st);
+};
+
+// icf_recall_kernel over nq rows on `st`: row q's first cfg.n_cand slots at q * stride (stride >= cfg.n_cand) of o_items / o_w.
+// The cache arrays may be null together (no cache: every row comes back empty)
+int recall_launch(const goctr_itemcf* h, const long long* off, const int32_t* seq_items, const long long* seq_ts,
+                  const RecallInputs& in, bool has_targets, int64_t nq, const goctr_recall_cfg& cfg, int stride, int32_t* o_items,
+                  unsigned int* o_w, int32_t* o_count, int32_t* o_tpos, hipStream_t st);
+
+// the device arrays a recall stage fills for every request row: [nq, n_cand] candidates (padding -1 / 0 / 255), the row's count and
+// the target's place (-1: none); src is null unless the driver was asked for sources
+struct RecallRows { int32_t* items; unsigned int* w; int32_t* count; int32_t* tpos; unsigned char* src; };
+using RecallStage = std::function<int(const RecallInputs&, const RecallRows&, hipStream_t)>;
+// recall, then rank, over a prepared slot: stages the request columns, runs `recall` on the slot's stream, writes and scores the
+// candidates' keys pass_rows at a time and keeps every row's best k (icf_keys_kernel, icf_select_kernel); with_src: a.out_src and
+// a.cand_src are served from the stage's src column.  Returns after the results are in the caller's arrays
+int recall_rank_run(const TopnScorer& sc, const char* who, const ItemcfRecArgs& a, bool with_src, const RecallStage& recall);
 
 }  // namespace goctr

@@ -14,7 +14,8 @@
 //   icf_weight_kernel     co, cnt -> w; the sort key (i << 24 | 2^24 - 1 - w) -- one stable sort leaves every item's pairs by w
 //                         descending and, among equal w, in the order they had: j ascending
 //   icf_starts_kernel, icf_emit_kernel   the first n_nbr pairs of every item with w > 0
-// Recall (icf_recall_kernel): one workgroup per request row, below.  Recommend: itemcf_recommend_run at the end of the file.
+// Recall (icf_recall_kernel): one workgroup per request row, below.  Recommend: recall_rank_run at the end of the file, the driver
+// goctr_recommend_itemcf and goctr_recommend_blend (popular.hip) share: they differ in the recall stage alone.
 #include <algorithm>
 #include <climits>
 #include <memory>
@@ -222,6 +223,7 @@ struct RecallArgs {
   const int32_t* nbr_items; const unsigned int* nbr_w;
   const int32_t* users; const long long* ts; const int32_t* targets;          // device; targets may be null
   int H, n_cand, exclude;
+  int stride;                                                                 // row q's slots start at q * stride (>= n_cand)
   int32_t* out_items; unsigned int* out_w; int32_t* out_count; int32_t* out_tpos;   // device; out_tpos may be null
 };
 
@@ -352,7 +354,7 @@ __global__ __launch_bounds__(SEL_THREADS) void icf_recall_kernel(RecallArgs a) {
   sel_sort_trim(skey, sraw, &s_fill, &s_thr, a.n_cand);
   const int fill = s_fill;
   for (int i = tid; i < a.n_cand; i += SEL_THREADS) {
-    const long long o = q * a.n_cand + i;
+    const long long o = q * a.stride + i;
     if (i < fill) {
       const int item = (int)~(unsigned int)skey[i];
       a.out_items[o] = item;
@@ -368,50 +370,6 @@ __global__ __launch_bounds__(SEL_THREADS) void icf_recall_kernel(RecallArgs a) {
     a.out_count[q] = fill;
     if (a.out_tpos) a.out_tpos[q] = s_tpos;
   }
-}
-
-int recall_check_cfg(const goctr_recall_cfg* cfg, const char* who) {
-  GOCTR_CHECK(cfg->history >= 1 && cfg->history <= RC_MAX_H, "%s: history = %d is outside 1 .. %d", who, cfg->history, RC_MAX_H);
-  GOCTR_CHECK(cfg->n_cand >= 1 && cfg->n_cand <= RC_MAX_CAND, "%s: n_cand = %d is outside 1 .. %d", who, cfg->n_cand, RC_MAX_CAND);
-  GOCTR_CHECK(cfg->exclude >= GOCTR_TOPN_KEEP_SEEN && cfg->exclude <= GOCTR_TOPN_DROP_SEEN_BEFORE,
-              "%s: exclude = %d is no GOCTR_TOPN_* mode", who, cfg->exclude);
-  return 0;
-}
-
-int recall_check_users(const int32_t* users, int64_t n_req, int64_t n_users, const char* who) {
-  GOCTR_CHECK(n_req > 0 && n_req <= ((int64_t)1 << 24), "%s: n_req = %lld is outside 1 .. 2^24", who, (long long)n_req);
-  for (int64_t q = 0; q < n_req; ++q)
-    GOCTR_CHECK(users[q] >= 0 && users[q] < n_users, "%s: request row %lld: user %d is outside [0, %lld)", who, (long long)q,
-                users[q], (long long)n_users);
-  return 0;
-}
-
-// the device-side inputs of a call: users, ts (zeros when the caller gave none), targets
-struct RecallInputs {
-  DevBuf<int32_t> users, targets;
-  DevBuf<long long> ts;
-  int stage(const int32_t* h_users, const int64_t* h_ts, const int32_t* h_targets, int64_t nq, hipStream_t st) {
-    if (users.alloc((size_t)nq, false) || ts.alloc((size_t)nq, false) || (h_targets && targets.alloc((size_t)nq, false))) return -1;
-    GOCTR_HIP(hipMemcpyAsync(users.p, h_users, sizeof(int32_t) * (size_t)nq, hipMemcpyHostToDevice, st));
-    if (h_ts) GOCTR_HIP(hipMemcpyAsync(ts.p, h_ts, sizeof(int64_t) * (size_t)nq, hipMemcpyHostToDevice, st));
-    else GOCTR_HIP(hipMemsetAsync(ts.p, 0, sizeof(int64_t) * (size_t)nq, st));
-    if (h_targets) GOCTR_HIP(hipMemcpyAsync(targets.p, h_targets, sizeof(int32_t) * (size_t)nq, hipMemcpyHostToDevice, st));
-    return 0;
-  }
-};
-
-int recall_launch(const goctr_itemcf* h, const long long* off, const int32_t* seq_items, const long long* seq_ts,
-                  const RecallInputs& in, bool has_targets, int64_t nq, const goctr_recall_cfg& cfg, int32_t* o_items,
-                  unsigned int* o_w, int32_t* o_count, int32_t* o_tpos, hipStream_t st) {
-  RecallArgs a{};
-  a.off = off; a.seq_items = seq_items; a.seq_ts = seq_ts;
-  a.n_items = h->n_items; a.M = h->M; a.nbr_items = h->nbr_items.p; a.nbr_w = h->nbr_w.p;
-  a.users = in.users.p; a.ts = in.ts.p; a.targets = has_targets ? in.targets.p : nullptr;
-  a.H = cfg.history; a.n_cand = cfg.n_cand; a.exclude = cfg.exclude;
-  a.out_items = o_items; a.out_w = o_w; a.out_count = o_count; a.out_tpos = o_tpos;
-  hipLaunchKernelGGL(icf_recall_kernel, dim3((unsigned)nq), dim3(SEL_THREADS), 0, st, a);
-  GOCTR_HIP(hipGetLastError());
-  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------------------ recommend
@@ -438,6 +396,7 @@ struct IcfSelArgs {
   int32_t* out_items; unsigned* out_scores; int32_t* out_count; long long* out_rank;
   float* cand_scores;                                                                     // [nq, n_cand] or null
   unsigned long long* n_failed;
+  const unsigned char* src; unsigned char* out_src;                                       // [nq, n_cand] -> [nq, k]; both or neither
 };
 
 // one workgroup per request row, one thread per recalled candidate: topn's order rule over at most 1024 keys
@@ -475,9 +434,11 @@ __global__ __launch_bounds__(SEL_THREADS) void icf_select_kernel(IcfSelArgs a) {
     if (i < fill) {
       a.out_items[o] = a.cand[q * a.n_cand + (int)~(unsigned)skey[i]];
       a.out_scores[o] = sraw[i];
+      if (a.out_src) a.out_src[o] = a.src[q * a.n_cand + (int)~(unsigned)skey[i]];
     } else {
       a.out_items[o] = -1;
       a.out_scores[o] = 0u;
+      if (a.out_src) a.out_src[o] = 255;
     }
   }
   if (tid == 0) {
@@ -497,11 +458,47 @@ struct Drain {
 
 namespace goctr {
 
-int itemcf_check_recommend(const goctr_itemcf* h, const ItemcfRecArgs& a, int64_t n_users, int64_t n_items) {
-  const char* who = "goctr_recommend_itemcf";
-  GOCTR_CHECK(h && a.users && a.out_items && a.out_scores && a.out_count, "%s: bad arguments", who);
-  GOCTR_CHECK(h->n_items == n_items, "%s: the neighbour lists cover %lld items, the recsys %lld", who, (long long)h->n_items,
-              (long long)n_items);
+int recall_check_cfg(const goctr_recall_cfg* cfg, const char* who) {
+  GOCTR_CHECK(cfg->history >= 1 && cfg->history <= RC_MAX_H, "%s: history = %d is outside 1 .. %d", who, cfg->history, RC_MAX_H);
+  GOCTR_CHECK(cfg->n_cand >= 1 && cfg->n_cand <= RC_MAX_CAND, "%s: n_cand = %d is outside 1 .. %d", who, cfg->n_cand, RC_MAX_CAND);
+  GOCTR_CHECK(cfg->exclude >= GOCTR_TOPN_KEEP_SEEN && cfg->exclude <= GOCTR_TOPN_DROP_SEEN_BEFORE,
+              "%s: exclude = %d is no GOCTR_TOPN_* mode", who, cfg->exclude);
+  return 0;
+}
+
+int recall_check_users(const int32_t* users, int64_t n_req, int64_t n_users, const char* who) {
+  GOCTR_CHECK(n_req > 0 && n_req <= ((int64_t)1 << 24), "%s: n_req = %lld is outside 1 .. 2^24", who, (long long)n_req);
+  for (int64_t q = 0; q < n_req; ++q)
+    GOCTR_CHECK(users[q] >= 0 && users[q] < n_users, "%s: request row %lld: user %d is outside [0, %lld)", who, (long long)q,
+                users[q], (long long)n_users);
+  return 0;
+}
+
+int RecallInputs::stage(const int32_t* h_users, const int64_t* h_ts, const int32_t* h_targets, int64_t nq, hipStream_t st) {
+  if (users.alloc((size_t)nq, false) || ts.alloc((size_t)nq, false) || (h_targets && targets.alloc((size_t)nq, false))) return -1;
+  GOCTR_HIP(hipMemcpyAsync(users.p, h_users, sizeof(int32_t) * (size_t)nq, hipMemcpyHostToDevice, st));
+  if (h_ts) GOCTR_HIP(hipMemcpyAsync(ts.p, h_ts, sizeof(int64_t) * (size_t)nq, hipMemcpyHostToDevice, st));
+  else GOCTR_HIP(hipMemsetAsync(ts.p, 0, sizeof(int64_t) * (size_t)nq, st));
+  if (h_targets) GOCTR_HIP(hipMemcpyAsync(targets.p, h_targets, sizeof(int32_t) * (size_t)nq, hipMemcpyHostToDevice, st));
+  return 0;
+}
+
+int recall_launch(const goctr_itemcf* h, const long long* off, const int32_t* seq_items, const long long* seq_ts,
+                  const RecallInputs& in, bool has_targets, int64_t nq, const goctr_recall_cfg& cfg, int stride, int32_t* o_items,
+                  unsigned int* o_w, int32_t* o_count, int32_t* o_tpos, hipStream_t st) {
+  RecallArgs a{};
+  a.off = off; a.seq_items = seq_items; a.seq_ts = seq_ts;
+  a.n_items = h->n_items; a.M = h->M; a.nbr_items = h->nbr_items.p; a.nbr_w = h->nbr_w.p;
+  a.users = in.users.p; a.ts = in.ts.p; a.targets = has_targets ? in.targets.p : nullptr;
+  a.H = cfg.history; a.n_cand = cfg.n_cand; a.exclude = cfg.exclude; a.stride = stride;
+  a.out_items = o_items; a.out_w = o_w; a.out_count = o_count; a.out_tpos = o_tpos;
+  hipLaunchKernelGGL(icf_recall_kernel, dim3((unsigned)nq), dim3(SEL_THREADS), 0, st, a);
+  GOCTR_HIP(hipGetLastError());
+  return 0;
+}
+
+int recall_check_recommend(const char* who, const ItemcfRecArgs& a, int64_t n_users) {
+  GOCTR_CHECK(a.users && a.out_items && a.out_scores && a.out_count, "%s: bad arguments", who);
   if (recall_check_cfg(&a.rcfg, who)) return -1;
   GOCTR_CHECK(a.k >= 1 && a.k <= 256, "%s: k = %d is outside 1 .. 256", who, a.k);
   GOCTR_CHECK(a.pass_rows == 0 || (a.pass_rows >= 16 && a.pass_rows <= TOPN_DEFAULT_PASS_ROWS),
@@ -509,8 +506,15 @@ int itemcf_check_recommend(const goctr_itemcf* h, const ItemcfRecArgs& a, int64_
   return recall_check_users(a.users, a.n_req, n_users, who);
 }
 
-int itemcf_recommend_run(const TopnScorer& sc, const goctr_itemcf* h, const ItemcfRecArgs& a) {
+int itemcf_check_recommend(const goctr_itemcf* h, const ItemcfRecArgs& a, int64_t n_users, int64_t n_items) {
   const char* who = "goctr_recommend_itemcf";
+  GOCTR_CHECK(h, "%s: bad arguments", who);
+  GOCTR_CHECK(h->n_items == n_items, "%s: the neighbour lists cover %lld items, the recsys %lld", who, (long long)h->n_items,
+              (long long)n_items);
+  return recall_check_recommend(who, a, n_users);
+}
+
+int recall_rank_run(const TopnScorer& sc, const char* who, const ItemcfRecArgs& a, bool with_src, const RecallStage& recall) {
   const int64_t nq = a.n_req;
   const int nc = a.rcfg.n_cand, k = a.k;
   const int64_t P = a.pass_rows ? a.pass_rows : TOPN_DEFAULT_PASS_ROWS;
@@ -521,11 +525,12 @@ int itemcf_recommend_run(const TopnScorer& sc, const goctr_itemcf* h, const Item
   DevBuf<unsigned int> c_w, o_scores;
   DevBuf<long long> d_pre, o_rank;
   DevBuf<float> f_scores, c_scores;
-  DevBuf<unsigned char> f_failed;
+  DevBuf<unsigned char> f_failed, c_src, o_src;
   DevBuf<unsigned long long> d_nfailed;
   std::vector<int32_t> h_count((size_t)nq), h_tpos((size_t)nq), h_items((size_t)nq * k), h_ocount((size_t)nq), h_citems;
   std::vector<unsigned> h_scores((size_t)nq * k), h_cw;
   std::vector<float> h_cscores;
+  std::vector<unsigned char> h_osrc, h_csrc;
   std::vector<long long> h_pre((size_t)nq + 1), h_rank((size_t)nq);
   unsigned long long h_nfailed = 0;
   Drain drain{st};                                        // (declared behind the buffers: runs before they are released)
@@ -535,10 +540,10 @@ int itemcf_recommend_run(const TopnScorer& sc, const goctr_itemcf* h, const Item
       o_scores.alloc((size_t)nq * k, false) || o_count.alloc((size_t)nq, false) || o_rank.alloc((size_t)nq, false) ||
       d_nfailed.alloc(1, false)) return -1;
   if (a.cand_scores && c_scores.alloc((size_t)nq * nc, false)) return -1;
+  if (with_src && (c_src.alloc((size_t)nq * nc, false) || o_src.alloc((size_t)nq * k, false))) return -1;
   GOCTR_HIP(hipMemsetAsync(d_nfailed.p, 0, sizeof(unsigned long long), st));
   // 1. recall on the slot's stream; its counts decide the key space, so they come back before the passes are cut
-  if (recall_launch(h, sc.ub_off, sc.ub_items, sc.ub_ts, in, a.targets != nullptr, nq, a.rcfg, c_items.p, c_w.p, c_count.p, c_tpos.p, st))
-    return -1;
+  if (recall(in, RecallRows{c_items.p, c_w.p, c_count.p, c_tpos.p, with_src ? c_src.p : nullptr}, st)) return -1;
   GOCTR_HIP(hipMemcpyAsync(h_count.data(), c_count.p, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, st));
   GOCTR_HIP(hipStreamSynchronize(st));
   h_pre[0] = 0;
@@ -567,6 +572,7 @@ int itemcf_recommend_run(const TopnScorer& sc, const goctr_itemcf* h, const Item
   s.scores = f_scores.p; s.failed = f_failed.p; s.n_cand = nc; s.k = k;
   s.out_items = o_items.p; s.out_scores = o_scores.p; s.out_count = o_count.p; s.out_rank = o_rank.p;
   s.cand_scores = a.cand_scores ? c_scores.p : nullptr; s.n_failed = d_nfailed.p;
+  s.src = with_src ? c_src.p : nullptr; s.out_src = with_src ? o_src.p : nullptr;
   hipLaunchKernelGGL(icf_select_kernel, dim3((unsigned)nq), dim3(SEL_THREADS), 0, st, s);
   GOCTR_HIP(hipGetLastError());
   // the results are staged on the host so that a failing copy leaves the caller's arrays as they were
@@ -579,6 +585,8 @@ int itemcf_recommend_run(const TopnScorer& sc, const goctr_itemcf* h, const Item
   if (a.cand_items) { h_citems.resize((size_t)nq * nc); GOCTR_HIP(hipMemcpyAsync(h_citems.data(), c_items.p, sizeof(int32_t) * h_citems.size(), hipMemcpyDeviceToHost, st)); }
   if (a.cand_w) { h_cw.resize((size_t)nq * nc); GOCTR_HIP(hipMemcpyAsync(h_cw.data(), c_w.p, sizeof(unsigned) * h_cw.size(), hipMemcpyDeviceToHost, st)); }
   if (a.cand_scores) { h_cscores.resize((size_t)nq * nc); GOCTR_HIP(hipMemcpyAsync(h_cscores.data(), c_scores.p, sizeof(float) * h_cscores.size(), hipMemcpyDeviceToHost, st)); }
+  if (with_src && a.out_src) { h_osrc.resize((size_t)nq * k); GOCTR_HIP(hipMemcpyAsync(h_osrc.data(), o_src.p, h_osrc.size(), hipMemcpyDeviceToHost, st)); }
+  if (with_src && a.cand_src) { h_csrc.resize((size_t)nq * nc); GOCTR_HIP(hipMemcpyAsync(h_csrc.data(), c_src.p, h_csrc.size(), hipMemcpyDeviceToHost, st)); }
   GOCTR_HIP(hipStreamSynchronize(st));
   memcpy(a.out_items, h_items.data(), sizeof(int32_t) * h_items.size());
   memcpy(a.out_scores, h_scores.data(), sizeof(unsigned) * h_scores.size());
@@ -589,8 +597,17 @@ int itemcf_recommend_run(const TopnScorer& sc, const goctr_itemcf* h, const Item
   if (a.cand_items) memcpy(a.cand_items, h_citems.data(), sizeof(int32_t) * h_citems.size());
   if (a.cand_w) memcpy(a.cand_w, h_cw.data(), sizeof(unsigned) * h_cw.size());
   if (a.cand_scores) memcpy(a.cand_scores, h_cscores.data(), sizeof(float) * h_cscores.size());
+  if (!h_osrc.empty()) memcpy(a.out_src, h_osrc.data(), h_osrc.size());
+  if (!h_csrc.empty()) memcpy(a.cand_src, h_csrc.data(), h_csrc.size());
   if (a.n_failed) *a.n_failed = (int64_t)h_nfailed;
   return 0;
+}
+
+int itemcf_recommend_run(const TopnScorer& sc, const goctr_itemcf* h, const ItemcfRecArgs& a) {
+  return recall_rank_run(sc, "goctr_recommend_itemcf", a, false, [&](const RecallInputs& in, const RecallRows& o, hipStream_t st) {
+    return recall_launch(h, sc.ub_off, sc.ub_items, sc.ub_ts, in, a.targets != nullptr, a.n_req, a.rcfg, a.rcfg.n_cand, o.items, o.w,
+                         o.count, o.tpos, st);
+  });
 }
 
 }  // namespace goctr
@@ -747,8 +764,8 @@ int goctr_itemcf_recall(goctr_itemcf* h, goctr_ubcache* c, const int32_t* users,
   UbRead image(c, s);                         // (behind the buffers: an error return drains the stream before they are freed)
   if (in.stage(users, ts, targets, n_req, s)) return -1;
   if (o_items.alloc(nq * nc, false) || o_w.alloc(nq * nc, false) || o_count.alloc(nq, false) || o_tpos.alloc(nq, false)) return -1;
-  if (recall_launch(h, c->off.p, c->items.p, c->ts.p, in, targets != nullptr, n_req, *cfg, o_items.p, o_w.p, o_count.p, o_tpos.p, s))
-    return -1;
+  if (recall_launch(h, c->off.p, c->items.p, c->ts.p, in, targets != nullptr, n_req, *cfg, cfg->n_cand, o_items.p, o_w.p, o_count.p,
+                    o_tpos.p, s)) return -1;
   GOCTR_HIP(hipMemcpyAsync(h_items.data(), o_items.p, sizeof(int32_t) * nq * nc, hipMemcpyDeviceToHost, s));
   GOCTR_HIP(hipMemcpyAsync(h_w.data(), o_w.p, sizeof(unsigned int) * nq * nc, hipMemcpyDeviceToHost, s));
   GOCTR_HIP(hipMemcpyAsync(h_count.data(), o_count.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));

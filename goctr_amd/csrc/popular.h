@@ -1,0 +1,33 @@
+// popular.h -- the handle of goctr_popular_build (popular.hip) and what goctr_recommend_blend's two halves share: serve.hip has
+// the entry point and lends the same TopnScorer as to top-N and ItemCF (with_scorer); popular.hip has the popularity build, the
+// blend of the recall channels and the call's driver, which is itemcf.h's recall_rank_run with the blend as its recall stage.
+#pragma once
+#include "itemcf.h"
+
+// time-decayed item popularity resident in HBM; immutable after the build, independent of the cache it was built from
+struct goctr_popular {
+  goctr::Engine* const eng = &goctr::engine();   // the engine (device, streams, arena) the handle was created on
+  int64_t n_items = 0;
+  int n_list = 0, n_listed = 0;                  // stored list length (goctr_popular_cfg.n_list); entries in use
+  uint64_t counted = 0;                          // counted entries
+  int64_t ts_ref_used = 0;
+  uint64_t cache_version = 0;                    // version of the cache image the list was built from
+  goctr::DevBuf<unsigned int> cnt;               // [n_items]
+  goctr::DevBuf<unsigned long long> score;       // [n_items]
+  goctr::DevBuf<int32_t> list_items;             // [n_list], -1 = unused
+  goctr::DevBuf<unsigned long long> list_score;  // [n_list], 0 = unused
+};
+
+namespace goctr {
+
+struct BlendArgs {
+  const goctr_itemcf* icf; const goctr_popular* pop;   // each may be null
+  const int32_t* extra; int n_extra, quota_pop;
+};
+
+// the refusals that need no slot (sets the error text)
+int blend_check_recommend(const BlendArgs& b, const ItemcfRecArgs& a, int64_t n_users, int64_t n_items);
+// the whole call over a prepared slot; returns after the results are in the caller's arrays (the stream is drained on every path)
+int blend_recommend_run(const TopnScorer& sc, const BlendArgs& b, const ItemcfRecArgs& a);
+
+}  // namespace goctr

@@ -1,5 +1,6 @@
-// serve.hip -- serving (goctr_recsys_*, goctr_batch_predict, goctr_rank, goctr_predict_dense, and the entries of goctr_recommend_topn
-// and goctr_recommend_itemcf, whose drivers are topn.hip and itemcf.hip) over the forward launches of the step (ctr.hip): the recsys
+// serve.hip -- serving (goctr_recsys_*, goctr_batch_predict, goctr_rank, goctr_predict_dense, and the entries of goctr_recommend_topn,
+// goctr_recommend_itemcf and goctr_recommend_blend, whose drivers are topn.hip, itemcf.hip and popular.hip) over the forward launches
+// of the step (ctr.hip): the recsys
 // handle, the serving slots and their pool, the passes, the micro-batcher.  The behaviour cache the passes read: ubcache.hip.
 #define GOCTR_NO_PLAIN_KERNELS      // the kernel headers' plain kernels belong to ctr.hip
 #include <algorithm>
@@ -12,6 +13,7 @@
 
 #include "ctr_model.h"
 #include "itemcf.h"
+#include "popular.h"
 #include "staging.h"
 #include "topn.h"
 #include "ubcache.h"
@@ -556,6 +558,29 @@ int goctr_recommend_itemcf(goctr_model* m, goctr_recsys* r, goctr_itemcf* h, con
                         out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed};
   if (itemcf_check_recommend(h, a, r->n_users, r->n_items)) return -1;
   return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return itemcf_recommend_run(sc, h, a); });
+}
+
+// Recall from several channels, then rank (popular.hip has the blend and the driver, which is the ItemCF call's with another recall
+// stage): as goctr_recommend_itemcf above.
+int goctr_recommend_blend(goctr_model* m, goctr_recsys* r, goctr_itemcf* icf, goctr_popular* pop, const int32_t* users,
+                          const int64_t* ts, int64_t n_req, const int32_t* targets, const int32_t* extra, int32_t n_extra,
+                          const goctr_recall_cfg* recall_cfg, int32_t quota_pop, int32_t k, int64_t pass_rows, int32_t* out_items,
+                          float* out_scores, int32_t* out_count, uint8_t* out_src, int32_t* out_cand_count, int32_t* out_target_pos,
+                          int64_t* out_target_rank, int32_t* cand_items, uint32_t* cand_w, float* cand_scores, uint8_t* cand_src,
+                          int64_t* n_failed) {
+  EngineScope on(handle_engine(m));
+  if (require_engine()) return -1;
+  GOCTR_CHECK(m && r && recall_cfg, "goctr_recommend_blend: bad arguments");
+  GOCTR_SAME_ENGINE(m, r);
+  GOCTR_SAME_ENGINE(m, icf);
+  GOCTR_SAME_ENGINE(m, pop);
+  if (check_recsys_dims("goctr_recommend_blend", m, r)) return -1;
+  GOCTR_CHECK(n_extra >= 0 && n_extra <= 1024, "goctr_recommend_blend: n_extra = %d is outside 0 .. 1024", n_extra);
+  const ItemcfRecArgs a{users, ts, n_req, targets, *recall_cfg, k, pass_rows, out_items, out_scores, out_count, out_cand_count,
+                        out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed, out_src, cand_src};
+  const BlendArgs b{icf, pop, extra, extra ? n_extra : 0, quota_pop};
+  if (blend_check_recommend(b, a, r->n_users, r->n_items)) return -1;
+  return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return blend_recommend_run(sc, b, a); });
 }
 
 // model.Predict's own convention (model/model.go:242-352): `rows` dense TrainSample rows in HOST memory -> y_out [rows].

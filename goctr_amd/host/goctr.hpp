@@ -545,7 +545,7 @@ class ItemCF {
 };
 
 // recall, then rank (goctr_recommend_itemcf): the model scores the recalled candidates only, so the cost of a request does not
-// grow with the catalogue.  A user without history gets an empty list: fall back to RecommendBatch.
+// grow with the catalogue.  A user without history gets an empty list: fall back to RecommendBatch, or use RecommendBlendBatch.
 inline TopN RecommendItemCFBatch(model::CtrNet& net, RecSys& rs, const ItemCF& icf, const std::vector<int32_t>& users, int n = 10,
                                  const std::vector<int64_t>& ts = {}, const goctr_recall_cfg& rcfg = ItemCF::DefaultRecallCfg(),
                                  const std::vector<int32_t>& targets = {}, int64_t pass_rows = 0) {
@@ -570,6 +570,80 @@ inline TopN RecommendItemCFBatch(model::CtrNet& net, RecSys& rs, const ItemCF& i
 inline std::vector<ItemScore> RecommendItemCF(model::CtrNet& net, RecSys& rs, const ItemCF& icf, int userId, int n, int64_t now,
                                               const goctr_recall_cfg& rcfg = ItemCF::DefaultRecallCfg()) {
   return RecommendItemCFBatch(net, rs, icf, {userId}, n, {now}, rcfg).lists[0];
+}
+
+// Popularity recall (goctr_popular_*): per-item counts, time-decayed scores and the popularity list of the recSys's own cache,
+// resident in HBM and independent of the cache afterwards -- the channel RecommendBlendBatch fills short or empty recalls from
+class Popular {
+ public:
+  static goctr_popular_cfg DefaultCfg() { goctr_popular_cfg c; goctr_popular_cfg_default(&c); return c; }
+  Popular(goctr_ubcache* cache, int64_t n_items, const goctr_popular_cfg& cfg = DefaultCfg()) : n_items_(n_items), n_list_(cfg.n_list) {
+    check(goctr_popular_build(cache, n_items, &cfg, &h_));
+  }
+  Popular(RecSys& rs, const goctr_popular_cfg& cfg = DefaultCfg()) : Popular(rs.cache(), rs.n_items(), cfg) {}
+  Popular(const Popular&) = delete;
+  Popular& operator=(const Popular&) = delete;
+  Popular(Popular&& o) noexcept : h_(o.h_), n_items_(o.n_items_), n_list_(o.n_list_) { o.h_ = nullptr; }
+  ~Popular() { goctr_popular_destroy(h_); }
+  goctr_popular* handle() const { return h_; }
+  int64_t n_items() const { return n_items_; }
+  int n_list() const { return n_list_; }
+  int n_listed() const { int32_t n = 0; check(goctr_popular_info(h_, nullptr, nullptr, &n, nullptr, nullptr, nullptr)); return n; }
+  // the stored list [n_list]: items (-1 = unused) and scores
+  void Export(std::vector<int32_t>& list_items, std::vector<uint64_t>& list_score) const {
+    list_items.resize((size_t)n_list_); list_score.resize((size_t)n_list_);
+    check(goctr_popular_export(h_, nullptr, nullptr, list_items.data(), list_score.data()));
+  }
+
+ private:
+  goctr_popular* h_ = nullptr; int64_t n_items_ = 0; int n_list_ = 0;
+};
+
+// the blended candidates of every request row (goctr_blend_recall): ItemCF's (icf may be null), the caller's `extra` rows
+// ([users.size(), n_extra], may be empty), then the popularity list (pop may be null); row q's first count[q] entries of
+// items / w / src (0 ItemCF, 1 extra, 2 popularity)
+inline void BlendRecall(const ItemCF* icf, const Popular* pop, goctr_ubcache* cache, const std::vector<int32_t>& users,
+                        const std::vector<int64_t>& ts, const std::vector<int32_t>& extra, int n_extra, const goctr_recall_cfg& cfg,
+                        int quota_pop, std::vector<int32_t>& items, std::vector<uint32_t>& w, std::vector<uint8_t>& src,
+                        std::vector<int32_t>& count) {
+  if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("BlendRecall: one timestamp per user");
+  if (extra.size() != users.size() * (size_t)std::max(n_extra, 0)) throw std::invalid_argument("BlendRecall: n_extra entries per user");
+  const size_t nq = users.size(), nc = (size_t)std::max(cfg.n_cand, 1);
+  items.resize(nq * nc); w.resize(nq * nc); src.resize(nq * nc); count.resize(nq);
+  check(goctr_blend_recall(icf ? icf->handle() : nullptr, pop ? pop->handle() : nullptr, cache, users.data(),
+                           ts.empty() ? nullptr : ts.data(), (int64_t)nq, extra.empty() ? nullptr : extra.data(), n_extra, &cfg,
+                           quota_pop, items.data(), w.data(), src.data(), count.data(), nullptr, nullptr));
+}
+
+// multi-channel recall, then rank (goctr_recommend_blend): as RecommendItemCFBatch, but a row whose ItemCF recall is short or
+// empty -- a new user -- is filled from `extra` and the popularity list, so it gets n items at the same cost
+inline TopN RecommendBlendBatch(model::CtrNet& net, RecSys& rs, const ItemCF* icf, const Popular* pop, const std::vector<int32_t>& users,
+                                int n = 10, const std::vector<int64_t>& ts = {}, const goctr_recall_cfg& rcfg = ItemCF::DefaultRecallCfg(),
+                                int quota_pop = 0, const std::vector<int32_t>& extra = {}, int n_extra = 0,
+                                const std::vector<int32_t>& targets = {}, int64_t pass_rows = 0) {
+  const int64_t nq = (int64_t)users.size();
+  if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("RecommendBlendBatch: one timestamp per user");
+  if (!targets.empty() && targets.size() != users.size()) throw std::invalid_argument("RecommendBlendBatch: one target per user");
+  if (extra.size() != users.size() * (size_t)std::max(n_extra, 0)) throw std::invalid_argument("RecommendBlendBatch: n_extra entries per user");
+  if (n < 1) throw std::invalid_argument("RecommendBlendBatch: n must be positive");
+  std::vector<int32_t> items((size_t)nq * n), count((size_t)nq);
+  std::vector<float> scores((size_t)nq * n);
+  TopN out;
+  if (!targets.empty()) out.target_rank.resize((size_t)nq);
+  check(goctr_recommend_blend(net.Vm(), rs.handle(), icf ? icf->handle() : nullptr, pop ? pop->handle() : nullptr, users.data(),
+                              ts.empty() ? nullptr : ts.data(), nq, targets.empty() ? nullptr : targets.data(),
+                              extra.empty() ? nullptr : extra.data(), n_extra, &rcfg, quota_pop, n, pass_rows, items.data(), scores.data(),
+                              count.data(), nullptr, nullptr, nullptr, targets.empty() ? nullptr : out.target_rank.data(), nullptr,
+                              nullptr, nullptr, nullptr, &out.n_failed));
+  out.lists.resize((size_t)nq);
+  for (int64_t q = 0; q < nq; ++q)
+    for (int j = 0; j < count[(size_t)q]; ++j)
+      out.lists[(size_t)q].push_back(ItemScore{items[(size_t)q * n + j], scores[(size_t)q * n + j]});
+  return out;
+}
+inline std::vector<ItemScore> RecommendBlend(model::CtrNet& net, RecSys& rs, const ItemCF* icf, const Popular* pop, int userId, int n,
+                                             int64_t now, const goctr_recall_cfg& rcfg = ItemCF::DefaultRecallCfg(), int quota_pop = 0) {
+  return RecommendBlendBatch(net, rs, icf, pop, {userId}, n, {now}, rcfg, quota_pop).lists[0];
 }
 }  // namespace recommend
 

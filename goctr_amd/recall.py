@@ -1,10 +1,15 @@
-"""recall -- ItemCF recall on the device (goctr_itemcf_*, include/goctr.h).
+"""recall -- ItemCF recall, popularity recall and the blend of recall channels on the device (goctr_itemcf_*, goctr_popular_*,
+goctr_blend_recall; include/goctr.h).
 
 The reference answers a request without candidates with "todo: some default recall algorithm" (recommend/api.go:115-118).
 ``ItemCF`` is that algorithm: item-to-item collaborative filtering over one image of the behaviour cache gives every item a list of
 neighbours (build), and a request row's candidates are the neighbours of its history, summed and ordered on the device (recall).
 ``recommend.RecommendItemCF`` ranks them with the model.  Every output is defined bit for bit (tests/itemcf_ref.py is the host
 restatement).
+
+``Popular`` is the second channel: a time-decayed popularity list of the same image, and ``blend`` merges the channels for every
+request row -- ItemCF's candidates, a list of the caller's, then the popularity list -- de-duplicated and seen-filtered on the
+device, so that a row without history still gets candidates (tests/popular_ref.py is the host restatement).
 """
 from __future__ import annotations
 
@@ -17,6 +22,7 @@ from . import capi
 EXCLUDE = {"keep": capi.TOPN_KEEP_SEEN, "all": capi.TOPN_DROP_ALL_SEEN, "before": capi.TOPN_DROP_SEEN_BEFORE}
 _BUILD_FIELDS = {"window", "max_len", "n_nbr", "min_co", "pair_budget"}
 _RECALL_FIELDS = {"history", "n_cand", "exclude"}
+_POPULAR_FIELDS = {"half_life", "ts_ref", "ts_lo", "ts_hi", "n_list"}
 
 
 def make_cfg(**kw) -> capi.ItemcfCfg:
@@ -37,6 +43,14 @@ def make_recall_cfg(**kw) -> capi.RecallCfg:
             raise ValueError(f"exclude = {kw['exclude']!r} is none of {sorted(EXCLUDE)}")
         kw["exclude"] = EXCLUDE[kw["exclude"]]
     return capi.default_recall_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
+
+
+def make_popular_cfg(**kw) -> capi.PopularCfg:
+    """goctr_popular_cfg from keywords (integers; the ranges are the library's to refuse)"""
+    unknown = set(kw) - _POPULAR_FIELDS
+    if unknown:
+        raise TypeError(f"goctr_popular_cfg has no field {sorted(unknown)}")
+    return capi.default_popular_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
 
 
 def _as_int(name, v):
@@ -114,3 +128,78 @@ class ItemCF:
             self.close()
         except Exception:
             pass
+
+
+class Popular:
+    """goctr_popular: per-item counts, decayed scores and the popularity list, resident in HBM, immutable after the build and
+    independent of the cache"""
+
+    def __init__(self, ubc, n_items: int, cfg: capi.PopularCfg | None = None, **kw):
+        """ubc: a ubcache.UserBehaviorCache (its device image is read) or a raw goctr_ubcache handle"""
+        if cfg is not None and kw:
+            raise TypeError("give either cfg or keywords")
+        cfg = cfg if cfg is not None else make_popular_cfg(**kw)
+        self.n_items = int(n_items)
+        self._h = C.c_void_p()
+        h = ubc.device() if hasattr(ubc, "device") else ubc
+        capi.check(capi.load().goctr_popular_build(h, C.c_int64(self.n_items), C.byref(cfg), C.byref(self._h)))
+        self.n_list = self.info()["n_list"]
+
+    def info(self) -> dict:
+        n, nl, nd, cn, tr, v = C.c_int64(0), C.c_int32(0), C.c_int32(0), C.c_uint64(0), C.c_int64(0), C.c_uint64(0)
+        capi.check(capi.load().goctr_popular_info(self._h, C.byref(n), C.byref(nl), C.byref(nd), C.byref(cn), C.byref(tr), C.byref(v)))
+        return dict(n_items=n.value, n_list=nl.value, n_listed=nd.value, counted=cn.value, ts_ref_used=tr.value, cache_version=v.value)
+
+    def export(self) -> dict:
+        """dict(cnt uint32 [n_items], score uint64 [n_items], list_items int32 [n_list] (-1 = unused), list_score uint64 [n_list])"""
+        n, nl = self.n_items, self.n_list
+        out = dict(cnt=np.empty(n, np.uint32), score=np.empty(n, np.uint64), list_items=np.empty(nl, np.int32),
+                   list_score=np.empty(nl, np.uint64))
+        capi.check(capi.load().goctr_popular_export(self._h, capi.ptr(out["cnt"], C.c_uint32), capi.ptr(out["score"], C.c_uint64),
+                                                    capi.ptr(out["list_items"], C.c_int32), capi.ptr(out["list_score"], C.c_uint64)))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            capi.load().goctr_popular_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def extra_columns(extra, nq):
+    """the caller's candidate lists as the C-ABI takes them: (int32 [nq, n_extra] or None, n_extra)"""
+    if extra is None:
+        return None, 0
+    extra = capi.i32(extra)
+    if extra.ndim != 2 or extra.shape[0] != nq:
+        raise ValueError("extra takes one row of candidates per request row")
+    return (extra, extra.shape[1]) if extra.shape[1] else (None, 0)
+
+
+def blend(icf, pop, ubc, users, ts=None, targets=None, extra=None, quota_pop=0, cfg: capi.RecallCfg | None = None, **kw) -> dict:
+    """goctr_blend_recall over DENSE user rows of ``ubc``'s image (``icf``, ``pop`` and ``ubc`` may each be None; ``extra`` int32
+    [nq, n_extra] or None): dict(items int32 [nq, n_cand] (-1 = unused), w uint32 [nq, n_cand], src uint8 [nq, n_cand] (0 ItemCF,
+    1 extra, 2 popularity, 255 = unused), count int32 [nq], target_pos int32 [nq] when targets are given)"""
+    if cfg is not None and kw:
+        raise TypeError("give either cfg or keywords")
+    cfg = cfg if cfg is not None else make_recall_cfg(**kw)
+    users, ts, targets = request_columns(users, ts, targets)
+    nq, nc = users.size, max(int(cfg.n_cand), 1)
+    extra, n_extra = extra_columns(extra, nq)
+    out = dict(items=np.full((nq, nc), -2, np.int32), w=np.full((nq, nc), 0xffffffff, np.uint32), src=np.full((nq, nc), 254, np.uint8),
+               count=np.full(nq, -2, np.int32))
+    tpos = np.full(nq, -2, np.int32) if targets is not None else None
+    h = None if ubc is None else ubc.device() if hasattr(ubc, "device") else ubc
+    capi.check(capi.load().goctr_blend_recall(
+        icf._h if icf is not None else None, pop._h if pop is not None else None, h, capi.ptr(users, C.c_int32),
+        capi.ptr(ts, C.c_int64), C.c_int64(nq), capi.ptr(extra, C.c_int32), C.c_int32(n_extra), C.byref(cfg),
+        C.c_int32(_as_int("quota_pop", quota_pop)), capi.ptr(out["items"], C.c_int32), capi.ptr(out["w"], C.c_uint32),
+        capi.ptr(out["src"], C.c_uint8), capi.ptr(out["count"], C.c_int32), capi.ptr(targets, C.c_int32), capi.ptr(tpos, C.c_int32)))
+    if tpos is not None:
+        out["target_pos"] = tpos
+    return out

@@ -585,7 +585,7 @@ def itemcf(model: Predictor, icf, users, ts=None, targets=None, k=10, pass_rows=
 def RecommendItemCFBatch(model: Predictor, icf, userIds, n=10, now=None, **recall_kw):
     """RecommendItemCF for several users in one device call: [[ItemScore]] in the order of userIds.  ``now``: one timestamp for
     all, or one per user.  An unknown user raises SampleVectorError like Rank's failing first key; a user without history gets
-    an empty list (there is no popularity fill: fall back to RecommendBatch)."""
+    an empty list (there is no popularity fill: fall back to RecommendBatch, or use RecommendBlendBatch)."""
     rs = model.recSys
     userIds = list(userIds)
     users = np.array([rs.user_index(u) for u in userIds], np.int32)
@@ -646,4 +646,133 @@ def EvaluateLeaveOneOutRecall(model: Predictor, icf, k=10, sample_kw=None, detai
                ndcg=float(np.mean(np.where(hit, 1.0 / np.log2(np.where(hit, rank, 0.0) + 2.0), 0.0))) if n else nan)
     if details:
         out.update(target_pos=r["target_pos"], rank=r["target_rank"], user_index=users, target_index=targets, ts=ts)
+    return out
+
+
+def BuildPopular(recSys: DeviceRecSys, **cfg):
+    """EXTENSION: the popularity list (recall.Popular; ``cfg``: goctr_popular_cfg fields) of the recSys's own behaviour cache over the
+    rows of its item feature table -- the channel RecommendBlend fills a short or empty ItemCF recall from.  The list is that of
+    the cache's image at THIS call; rebuild it when enough new behaviour has come in."""
+    from .recall import Popular
+    if recSys.ubcache is None:
+        raise RuntimeError("this recSys has no behaviour cache to count popularity from (it does not implement UserBehavior, rcmd.go:512)")
+    return Popular(recSys._dense_cache, recSys.item_table.shape[0], **cfg)
+
+
+def blend(model: Predictor, icf, pop, users, ts=None, targets=None, extra=None, quota_pop=0, k=10, pass_rows=0, validate=False,
+          recall_cfg=None, **recall_kw):
+    """goctr_recommend_blend over DENSE indices (``icf`` / ``pop``: recall.ItemCF / recall.Popular or None; users [nq], ts [nq] or
+    None, targets [nq] or None, extra int32 [nq, n_extra] or None): dict(items [nq, k], scores [nq, k], src uint8 [nq, k] (0 ItemCF,
+    1 extra, 2 popularity, 255 = unused), count [nq], cand_count [nq], n_failed, target_pos / target_rank [nq] when targets are
+    given, cand_items / cand_w / cand_scores / cand_src [nq, n_cand] when ``validate``).  ``recall_kw``: goctr_recall_cfg fields.
+    What RecommendBlend / RecommendBlendBatch / EvaluateLeaveOneOutBlend call."""
+    from .recall import _as_int, extra_columns, make_recall_cfg, request_columns
+    if recall_cfg is not None and recall_kw:
+        raise TypeError("give either recall_cfg or keywords")
+    cfg = recall_cfg if recall_cfg is not None else make_recall_cfg(**recall_kw)
+    rs = model.recSys
+    users, ts, targets = request_columns(users, ts, targets)
+    nq, kk, nc = users.size, max(int(k), 1), max(int(cfg.n_cand), 1)
+    extra, n_extra = extra_columns(extra, nq)
+    out = dict(items=np.full((nq, kk), -2, np.int32), scores=np.full((nq, kk), np.nan, np.float32), src=np.full((nq, kk), 254, np.uint8),
+               count=np.full(nq, -2, np.int32), cand_count=np.full(nq, -2, np.int32))
+    tpos = np.full(nq, -2, np.int32) if targets is not None else None
+    rank = np.full(nq, -2, np.int64) if targets is not None else None
+    cand_items = np.full((nq, nc), -2, np.int32) if validate else None
+    cand_w = np.full((nq, nc), 0xffffffff, np.uint32) if validate else None
+    cand_scores = np.full((nq, nc), np.nan, np.float32) if validate else None
+    cand_src = np.full((nq, nc), 254, np.uint8) if validate else None
+    nf = C.c_int64(-2)
+    capi.check(capi.load().goctr_recommend_blend(
+        model.net._h, rs._h, icf._h if icf is not None else None, pop._h if pop is not None else None, capi.ptr(users, C.c_int32),
+        capi.ptr(ts, C.c_int64), C.c_int64(nq), capi.ptr(targets, C.c_int32), capi.ptr(extra, C.c_int32), C.c_int32(n_extra),
+        C.byref(cfg), C.c_int32(_as_int("quota_pop", quota_pop)), C.c_int32(int(k)), C.c_int64(int(pass_rows)),
+        capi.ptr(out["items"], C.c_int32), capi.ptr(out["scores"], C.c_float), capi.ptr(out["count"], C.c_int32),
+        capi.ptr(out["src"], C.c_uint8), capi.ptr(out["cand_count"], C.c_int32), capi.ptr(tpos, C.c_int32), capi.ptr(rank, C.c_int64),
+        capi.ptr(cand_items, C.c_int32), capi.ptr(cand_w, C.c_uint32), capi.ptr(cand_scores, C.c_float), capi.ptr(cand_src, C.c_uint8),
+        C.byref(nf)))
+    out["n_failed"] = nf.value
+    if targets is not None:
+        out["target_pos"], out["target_rank"] = tpos, rank
+    if validate:
+        out["cand_items"], out["cand_w"], out["cand_scores"], out["cand_src"] = cand_items, cand_w, cand_scores, cand_src
+    return out
+
+
+def RecommendBlendBatch(model: Predictor, icf, pop, userIds, n=10, now=None, extra=None, quota_pop=0, **recall_kw):
+    """RecommendBlend for several users in one device call: [[ItemScore]] in the order of userIds.  ``now``: one timestamp for all,
+    or one per user; ``extra``: one list of item ids per user (equal lengths), or None.  An unknown user raises SampleVectorError
+    like Rank's failing first key; a user without history gets the popularity channel's items, not an empty list."""
+    rs = model.recSys
+    userIds = list(userIds)
+    users = np.array([rs.user_index(u) for u in userIds], np.int32)
+    if users.size == 0:
+        return []
+    if (users < 0).any():
+        bad = userIds[int(np.flatnonzero(users < 0)[0])]
+        raise SampleVectorError(f"get sample vector error: user {bad} has no features")
+    ts = np.broadcast_to(np.asarray(int(time.time()) if now is None else now, np.int64), users.shape)
+    # an id unknown to the item feature table becomes an entry out of range (index -1), which the blend skips
+    dense_extra = None if extra is None else np.array([[rs.item_index(i) for i in row] for row in extra], np.int32).reshape(users.size, -1)
+    try:
+        r = blend(model, icf, pop, users, ts, None, dense_extra, quota_pop, n, **recall_kw)
+    except capi.GoctrError as e:
+        raise SampleVectorError(str(e)) from None
+    raw = rs._row_keys
+    return [[ItemScore(int(raw[r["items"][q, j]]), float(r["scores"][q, j])) for j in range(int(r["count"][q]))]
+            for q in range(users.size)]
+
+
+def RecommendBlend(model: Predictor, icf, pop, userId: int, n=10, now=None, extra=None, quota_pop=0, **recall_kw):
+    """EXTENSION -- multi-channel recall, then rank: the candidates are RecommendItemCF's (``icf``: BuildItemCF, or None), at most
+    ``n_cand - quota_pop`` of them, then the caller's ``extra`` item ids, then the popularity list (``pop``: BuildPopular, or
+    None) up to ``n_cand``; seen items (``exclude`` as Recommend's) and repeats are left out on the device.  The model scores the
+    blended list and the ``n`` best come back, best first, ties by the place in the list.  A new user, whose ItemCF recall is
+    empty, is served from the popularity channel at the same cost -- no full-catalogue pass."""
+    return RecommendBlendBatch(model, icf, pop, [userId], n, now, None if extra is None else [extra], quota_pop, **recall_kw)[0]
+
+
+def EvaluateLeaveOneOutBlend(model: Predictor, icf, pop=None, k=10, sample_kw=None, details=False, pass_rows=0, quota_pop=0,
+                             pop_kw=None, **recall_kw):
+    """EvaluateLeaveOneOutRecall's protocol over the BLENDED candidates (goctr_recommend_blend): every user's newest entry is held
+    out (key timestamp ts - 1, DROP_SEEN_BEFORE unless ``exclude`` says otherwise), the ItemCF recall proposes at most
+    ``n_cand - quota_pop`` candidates from the history the key sees, the popularity list fills the row up to ``n_cand`` and the
+    model ranks the blended list.  ``pop`` None: the popularity list is built here with ``ts_hi`` BELOW the held-out events -- the
+    smallest held-out key timestamp, so no held-out entry (and nothing newer) is counted -- from ``pop_kw`` (goctr_popular_cfg
+    fields); a caller's own ``pop`` is used as it is.  Figures and return value as EvaluateLeaveOneOutRecall's; with
+    ``quota_pop`` = 0 the ItemCF part is a prefix of the blended list, so ``recall`` is never below EvaluateLeaveOneOutRecall's."""
+    from .recall import make_recall_cfg
+    from .sampling import Samples
+    rs = model.recSys
+    if rs.ubcache is None:
+        raise RuntimeError("this recSys has no behaviour cache to hold items out of (it does not implement UserBehavior, rcmd.go:512)")
+    kw = dict(n_neg=0, which="newest")
+    kw.update(sample_kw or {})
+    smp = Samples(rs._dense_cache, rs.item_table.shape[0], **kw)
+    if smp.rows == 0:
+        raise SampleVectorError("the behaviour cache holds no entry that qualifies as a positive")
+    users, targets, ts, _y = smp.export()
+    own = pop is None
+    if own:
+        pkw = dict(pop_kw or {})
+        pkw.setdefault("ts_hi", int(ts.min()))            # the keys carry ts - 1: at or below every held-out event's predecessor
+        pop = BuildPopular(rs, **pkw)
+    recall_kw.setdefault("exclude", "before")
+    cfg = make_recall_cfg(**recall_kw)
+    try:
+        r = blend(model, icf, pop, users, ts, targets, None, quota_pop, k, pass_rows, recall_cfg=cfg)
+    finally:
+        if own:
+            pop.close()
+    ok = (targets >= 0) & (targets < rs.item_table.shape[0])
+    pos, rank = r["target_pos"][ok].astype(np.int64), r["target_rank"][ok].astype(np.float64)
+    n = int(ok.sum())
+    hit = (rank >= 0) & (rank < k)
+    nan = float("nan")
+    out = dict(users=n, skipped=int((~ok).sum()), k=int(k), n_cand=int(cfg.n_cand),
+               recall=float(np.mean(pos >= 0)) if n else nan,
+               hit_rate=float(np.mean(hit)) if n else nan,
+               ndcg=float(np.mean(np.where(hit, 1.0 / np.log2(np.where(hit, rank, 0.0) + 2.0), 0.0))) if n else nan)
+    if details:
+        out.update(target_pos=r["target_pos"], rank=r["target_rank"], src=r["src"], user_index=users, target_index=targets, ts=ts)
     return out

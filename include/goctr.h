@@ -439,7 +439,8 @@ int  goctr_itemcf_export(goctr_itemcf* h, uint32_t* cnt /*[n_items]*/, int32_t* 
  *   refused        (-1, nothing touched) a users[q] outside [0, n_users); history outside 1 .. 256; n_cand outside
  *                  1 .. 1024; exclude no GOCTR_TOPN_* value; n_req <= 0; and the limit of the implementation,
  *                  n_req > 2^24
- * A row with an empty history returns count 0: there is no popularity fill, callers fall back to goctr_recommend_topn.
+ * A row with an empty history returns count 0: there is no popularity fill, callers fall back to goctr_recommend_topn
+ * (goctr_recommend_blend fills such rows from a popularity list).
  * A row's lists may be processed in tiles (ranges of candidate items); no output depends on the tiling. */
 typedef struct {
   int32_t history;      /* 1 .. 256                      default 50  */
@@ -475,6 +476,91 @@ int goctr_recommend_itemcf(goctr_model* m, goctr_recsys* r, goctr_itemcf* h,
                            int32_t* out_items /* [n_req,k] */, float* out_scores /* [n_req,k] */, int32_t* out_count,
                            int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank,
                            int32_t* cand_items, uint32_t* cand_w, float* cand_scores, int64_t* n_failed);
+
+/* ---- Popularity recall and the blend of recall channels (no reference counterpart, like ItemCF above).  goctr_popular_build
+ * makes a time-decayed popularity list from ONE image of the behaviour cache; goctr_blend_recall merges, for every request row,
+ * the ItemCF recall, a list of the caller's and the popularity list, de-duplicated and seen-filtered on the device; and
+ * goctr_recommend_blend ranks the blended list with the model.  Every output is defined bit for bit (tests/popular_ref.py is the
+ * host restatement); all arithmetic is integer, so the order in which entries arrive cannot show.
+ *
+ * goctr_popular_build:
+ *   valid entry    0 <= item < n_items
+ *   counted entry  valid and ts_lo <= ts <= ts_hi; `counted` = how many there are, cnt[i] (uint32) = those that hold item i
+ *   ts_ref used    cfg.ts_ref, or when that is 0 the largest ts of a counted entry; with no counted entry every list is empty
+ *                  and ts_ref_used is 0
+ *   bucket         b = 0 when half_life == 0 or ts >= ts_ref, else floor((ts_ref - ts) / half_life), the difference taken as a
+ *                  mathematical integer (it fits uint64 whatever the two int64 values are)
+ *   contribution   2^(32 - b) for b <= 32, else 0 (an entry older than 32 half-lives still counts in cnt)
+ *   score[i]       the sum of the contributions of the counted entries that hold item i: uint64, below 2^63
+ *   list           the items with score > 0 by score descending, then item ascending; the first n_list are stored: list_items
+ *                  [n_list] (padding -1), list_score [n_list] (padding 0); n_listed = how many are stored
+ *   refused        (-1, *out untouched) a cfg outside its ranges, ts_lo > ts_hi, n_items <= 0 or n_items > 2^31 - 1, and a
+ *                  cache image of 2^31 or more entries (which keeps every sum below 2^63)
+ * An empty cache is not an error.  The handle is immutable and independent of the cache, like goctr_itemcf. */
+typedef struct {
+  int64_t half_life;     /* >= 0; 0 = no decay                                default 0 */
+  int64_t ts_ref;        /* 0 = the largest ts among counted entries          default 0 */
+  int64_t ts_lo, ts_hi;  /* entries with ts_lo <= ts <= ts_hi are counted     default INT64_MIN, INT64_MAX */
+  int32_t n_list;        /* 1 .. 65536 stored items                           default 1024 */
+} goctr_popular_cfg;
+void goctr_popular_cfg_default(goctr_popular_cfg* c);
+typedef struct goctr_popular goctr_popular;
+int  goctr_popular_build(goctr_ubcache* c, int64_t n_items, const goctr_popular_cfg* cfg, goctr_popular** out);
+void goctr_popular_destroy(goctr_popular* h);
+/* each may be NULL; cache_version: of the image */
+int  goctr_popular_info(goctr_popular* h, int64_t* n_items, int32_t* n_list, int32_t* n_listed, uint64_t* counted,
+                        int64_t* ts_ref_used, uint64_t* cache_version);
+/* each may be NULL */
+int  goctr_popular_export(goctr_popular* h, uint32_t* cnt /*[n_items]*/, uint64_t* score /*[n_items]*/,
+                          int32_t* list_items /*[n_list]*/, uint64_t* list_score /*[n_list]*/);
+
+/* goctr_blend_recall: the blended candidate list of n_req request rows, one workgroup per row.  Row q's list is three parts in
+ * this order; n_items is the handles' (they must agree), and with neither handle 2^31 - 1, the largest a handle can have.
+ *   part A         (source 0) exactly what goctr_itemcf_recall returns for the row with n_cand - quota_pop in place of n_cand:
+ *                  same items, same weights, same order.  Empty when icf is NULL, c is NULL or n_cand == quota_pop
+ *   part X         (source 1) the row's `extra` entries in their given order; an entry is skipped if it is outside
+ *                  [0, n_items), if it is seen (below) unless it equals targets[q], or if it is already in the list (of equal
+ *                  entries the first wins).  The part stops when the list holds n_cand - quota_pop entries.  extra NULL = none
+ *   part P         (source 2) the entries of pop's stored list in list order; an entry is skipped if it is seen, with the same
+ *                  target exemption, or already in the list.  The part stops when the list holds n_cand entries or the stored
+ *                  list ends.  Empty when pop is NULL
+ *   seen           as goctr_itemcf_recall's: the item equals a valid item among the entries of users[q]'s sequence that
+ *                  cfg->exclude looks at (DROP_ALL_SEEN the whole sequence, DROP_SEEN_BEFORE the entries TimeSeq.Filter(ts[q], 0)
+ *                  keeps, KEEP_SEEN none), in the ONE image of the cache the call holds.  c == NULL: nothing is seen
+ *   outputs        out_count[q] = the list's length; row q of out_items / out_w / out_src holds item, weight (ItemCF's sum for
+ *                  source 0, 0 for sources 1 and 2) and source in list order, the rest item -1, weight 0, source 255;
+ *                  out_target_pos[q] (may be NULL) = the target's place in the blended list, or -1
+ *   refused        (-1, nothing touched) goctr_itemcf_recall's refusals (users are checked against the cache's rows, with
+ *                  c == NULL only for users[q] >= 0); quota_pop outside 0 .. n_cand; n_extra outside 0 .. 1024; icf and pop
+ *                  both NULL with no extra entry; handles whose n_items differ
+ * The sequence is streamed past the row's list once per tile of 1024 source positions: it may have any length.  No output
+ * depends on the tiling or on the order in which threads arrive. */
+int  goctr_blend_recall(goctr_itemcf* icf /* may be NULL */, goctr_popular* pop /* may be NULL */, goctr_ubcache* c /* may be NULL */,
+                        const int32_t* users, const int64_t* ts /* NULL = 0 */, int64_t n_req,
+                        const int32_t* extra /* [n_req,n_extra] or NULL */, int32_t n_extra /* 0 .. 1024 */,
+                        const goctr_recall_cfg* cfg, int32_t quota_pop /* 0 .. cfg->n_cand */,
+                        int32_t* out_items /*[n_req,n_cand]*/, uint32_t* out_w /*same*/, uint8_t* out_src /*same*/,
+                        int32_t* out_count /*[n_req]*/, const int32_t* targets /* or NULL */, int32_t* out_target_pos /* or NULL */);
+
+/* goctr_recommend_blend: recall from the channels, blend, then rank.  A serving entry beside goctr_recommend_itemcf (slot, locks,
+ * one image of the cache -- the recsys's -- for the whole call): the blended list of goctr_blend_recall (n_items = the recsys's)
+ * is built on the slot's stream, the keys (users[q], candidate, ts[q]) are written and scored pass_rows rows at a time and one
+ * workgroup per row keeps the best k by goctr_recommend_topn's order rule with the place in the blended list as the position.
+ * Scores, failed candidates, n_failed, out_cand_count (the blended list's length), out_target_pos and out_target_rank are as
+ * documented for goctr_recommend_itemcf: below 8192 rows per pass the scores are bit-identical to goctr_batch_predict.
+ *   out_src        [n_req,k], may be NULL: the source (0, 1, 2) of every returned item, padding 255
+ *   cand_src       [n_req,n_cand], may be NULL: the blended list's sources, beside cand_items / cand_w / cand_scores
+ *   refused        goctr_recommend_itemcf's refusals, goctr_blend_recall's, and a handle whose n_items differs from the recsys's
+ * A recsys without a cache has no history and nothing seen: it still serves parts X and P. */
+int goctr_recommend_blend(goctr_model* m, goctr_recsys* r, goctr_itemcf* icf /* may be NULL */, goctr_popular* pop /* may be NULL */,
+                          const int32_t* users, const int64_t* ts /* NULL = 0 */, int64_t n_req,
+                          const int32_t* targets /* [n_req] or NULL */,
+                          const int32_t* extra /* [n_req,n_extra] or NULL */, int32_t n_extra /* 0 .. 1024 */,
+                          const goctr_recall_cfg* recall_cfg, int32_t quota_pop /* 0 .. recall_cfg->n_cand */,
+                          int32_t k, int64_t pass_rows,
+                          int32_t* out_items /* [n_req,k] */, float* out_scores /* [n_req,k] */, int32_t* out_count,
+                          uint8_t* out_src, int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank,
+                          int32_t* cand_items, uint32_t* cand_w, float* cand_scores, uint8_t* cand_src, int64_t* n_failed);
 
 /* The replica a multi-device training call (cfg.devices = n) keeps on engine `rank` (rank 0: the handle itself); NULL before
  * the first such call.  Borrowed: owned by the handle it was asked from.  For checks that the replicas are bit-identical
