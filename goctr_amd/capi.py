@@ -165,6 +165,11 @@ class PopularCfg(C.Structure):
     _fields_ = [("half_life", C.c_int64), ("ts_ref", C.c_int64), ("ts_lo", C.c_int64), ("ts_hi", C.c_int64), ("n_list", C.c_int32)]
 
 
+class ItemnbrCfg(C.Structure):
+    """goctr_itemnbr_cfg (include/goctr.h)"""
+    _fields_ = [("n_nbr", C.c_int32), ("min_w", C.c_int32), ("pass_items", C.c_int64)]
+
+
 TOPN_KEEP_SEEN, TOPN_DROP_ALL_SEEN, TOPN_DROP_SEEN_BEFORE = 0, 1, 2   # goctr_topn_cfg.exclude
 NS_UNIFORM, NS_POPULARITY, NS_POPULARITY_075 = 0, 1, 2      # goctr_negsample_cfg.weighting
 NS_ALL, NS_NEWEST, NS_ALL_BUT_NEWEST = 0, 1, 2              # goctr_negsample_cfg.which
@@ -209,6 +214,7 @@ SYMBOLS = [
     "goctr_recall_cfg_default", "goctr_itemcf_recall", "goctr_recommend_itemcf",
     "goctr_popular_cfg_default", "goctr_popular_build", "goctr_popular_destroy", "goctr_popular_info", "goctr_popular_export",
     "goctr_blend_recall", "goctr_recommend_blend",
+    "goctr_itemnbr_cfg_default", "goctr_itemcf_build_vectors", "goctr_itemcf_build_emb", "goctr_itemcf_merge",
 ]
 
 _lib = None
@@ -231,7 +237,8 @@ def load() -> C.CDLL:
                      "goctr_w2v_destroy", "goctr_searcher_destroy", "goctr_ubcache_destroy", "goctr_recsys_destroy", "goctr_train_cfg_default", "goctr_mlp_cfg_default",
                      "goctr_w2v_cfg_default", "goctr_negsample_cfg_default", "goctr_samples_destroy", "goctr_topn_cfg_default",
                      "goctr_itemcf_cfg_default", "goctr_recall_cfg_default", "goctr_itemcf_destroy", "goctr_curve_cfg_default",
-                     "goctr_multiclass_cfg_default", "goctr_popular_cfg_default", "goctr_popular_destroy"):
+                     "goctr_multiclass_cfg_default", "goctr_popular_cfg_default", "goctr_popular_destroy",
+                     "goctr_itemnbr_cfg_default"):
             getattr(_lib, name).restype = None
         _bm = C.POINTER(BinaryMetrics)
         _lib.goctr_metrics_binary.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, _bm]
@@ -298,6 +305,11 @@ def load() -> C.CDLL:
         _lib.goctr_recommend_itemcf.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32,
                                                 C.POINTER(RecallCfg), C.c_int32, C.c_int64, _i32, _f32, _i32, _i32, _i32, _i64,
                                                 _i32, _u32, _f32, _i64]
+        _lib.goctr_itemnbr_cfg_default.argtypes = [C.POINTER(ItemnbrCfg)]
+        _lib.goctr_itemcf_build_vectors.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int32, C.POINTER(ItemnbrCfg),
+                                                    C.POINTER(C.c_void_p)]
+        _lib.goctr_itemcf_build_emb.argtypes = [C.c_void_p, C.c_int64, C.POINTER(ItemnbrCfg), C.POINTER(C.c_void_p)]
+        _lib.goctr_itemcf_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         _lib.goctr_popular_cfg_default.argtypes = [C.POINTER(PopularCfg)]
         _lib.goctr_popular_build.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PopularCfg), C.POINTER(C.c_void_p)]
         _lib.goctr_popular_destroy.argtypes = [C.c_void_p]
@@ -449,6 +461,14 @@ def default_itemcf_cfg(**kw) -> ItemcfCfg:
 def default_recall_cfg(**kw) -> RecallCfg:
     c = RecallCfg()
     load().goctr_recall_cfg_default(C.byref(c))
+    for k, v in kw.items():
+        setattr(c, k, v)
+    return c
+
+
+def default_itemnbr_cfg(**kw) -> ItemnbrCfg:
+    c = ItemnbrCfg()
+    load().goctr_itemnbr_cfg_default(C.byref(c))
     for k, v in kw.items():
         setattr(c, k, v)
     return c

@@ -518,6 +518,28 @@ class ItemCF {
     check(goctr_itemcf_build(cache, n_items, &cfg, &h_));
   }
   ItemCF(RecSys& rs, const goctr_itemcf_cfg& cfg = DefaultCfg()) : ItemCF(rs.cache(), rs.n_items(), cfg) {}
+  // neighbour lists from item VECTORS (goctr_itemcf_build_vectors / _emb): quantised cosine in units of 2^-16, the scale of the
+  // co-occurrence weights, so every consumer takes either kind of handle
+  static goctr_itemnbr_cfg DefaultNbrCfg() { goctr_itemnbr_cfg c; goctr_itemnbr_cfg_default(&c); return c; }
+  static ItemCF FromVectors(const std::vector<double>& rows, int64_t n_items, int D, const goctr_itemnbr_cfg& cfg = DefaultNbrCfg()) {
+    if (n_items <= 0 || D <= 0 || rows.size() != (size_t)n_items * D) throw std::invalid_argument("ItemCF::FromVectors: rows is [n_items, D]");
+    goctr_itemcf* h = nullptr;
+    check(goctr_itemcf_build_vectors(rows.data(), n_items, D, &cfg, &h));
+    return ItemCF(h);
+  }
+  static ItemCF FromEmbedding(goctr_emb* table, int64_t n_items, const goctr_itemnbr_cfg& cfg = DefaultNbrCfg()) {
+    goctr_itemcf* h = nullptr;
+    check(goctr_itemcf_build_emb(table, n_items, &cfg, &h));
+    return ItemCF(h);
+  }
+  // the recSys's embedding table over the rows of its item feature table: the n_items ItemCF(rs) uses
+  static ItemCF FromEmbedding(RecSys& rs, const goctr_itemnbr_cfg& cfg = DefaultNbrCfg()) { return FromEmbedding(rs.embedding(), rs.n_items(), cfg); }
+  // one handle from the STORED lists of two (goctr_itemcf_merge): w = (mul_a w_a + mul_b w_b) >> 8, a missing side as 0
+  static ItemCF Merge(const ItemCF& a, const ItemCF& b, int mul_a = 128, int mul_b = 128, int n_nbr = 64) {
+    goctr_itemcf* h = nullptr;
+    check(goctr_itemcf_merge(a.h_, b.h_, mul_a, mul_b, n_nbr, &h));
+    return ItemCF(h);
+  }
   ItemCF(const ItemCF&) = delete;
   ItemCF& operator=(const ItemCF&) = delete;
   ItemCF(ItemCF&& o) noexcept : h_(o.h_), n_items_(o.n_items_), n_nbr_(o.n_nbr_) { o.h_ = nullptr; }
@@ -541,6 +563,11 @@ class ItemCF {
   }
 
  private:
+  explicit ItemCF(goctr_itemcf* h) : h_(h) {             // adopts a built handle
+    int32_t m = 0;
+    check(goctr_itemcf_info(h_, &n_items_, &m, nullptr, nullptr, nullptr));
+    n_nbr_ = m;
+  }
   goctr_itemcf* h_ = nullptr; int64_t n_items_ = 0; int n_nbr_ = 0;
 };
 

@@ -23,6 +23,7 @@ EXCLUDE = {"keep": capi.TOPN_KEEP_SEEN, "all": capi.TOPN_DROP_ALL_SEEN, "before"
 _BUILD_FIELDS = {"window", "max_len", "n_nbr", "min_co", "pair_budget"}
 _RECALL_FIELDS = {"history", "n_cand", "exclude"}
 _POPULAR_FIELDS = {"half_life", "ts_ref", "ts_lo", "ts_hi", "n_list"}
+_NBR_FIELDS = {"n_nbr", "min_w", "pass_items"}
 
 
 def make_cfg(**kw) -> capi.ItemcfCfg:
@@ -43,6 +44,14 @@ def make_recall_cfg(**kw) -> capi.RecallCfg:
             raise ValueError(f"exclude = {kw['exclude']!r} is none of {sorted(EXCLUDE)}")
         kw["exclude"] = EXCLUDE[kw["exclude"]]
     return capi.default_recall_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
+
+
+def make_nbr_cfg(**kw) -> capi.ItemnbrCfg:
+    """goctr_itemnbr_cfg from keywords (integers; the ranges are the library's to refuse)"""
+    unknown = set(kw) - _NBR_FIELDS
+    if unknown:
+        raise TypeError(f"goctr_itemnbr_cfg has no field {sorted(unknown)}")
+    return capi.default_itemnbr_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
 
 
 def make_popular_cfg(**kw) -> capi.PopularCfg:
@@ -84,6 +93,42 @@ class ItemCF:
         h = ubc.device() if hasattr(ubc, "device") else ubc
         capi.check(capi.load().goctr_itemcf_build(h, C.c_int64(self.n_items), C.byref(cfg), C.byref(self._h)))
         self.n_nbr = self.info()["n_nbr"]
+
+    @classmethod
+    def _adopt(cls, handle: C.c_void_p) -> "ItemCF":
+        self = cls.__new__(cls)
+        self._h = handle
+        i = self.info()
+        self.n_items, self.n_nbr = i["n_items"], i["n_nbr"]
+        return self
+
+    @classmethod
+    def from_vectors(cls, rows, cfg: capi.ItemnbrCfg | None = None, **kw) -> "ItemCF":
+        """goctr_itemcf_build_vectors: neighbour lists from item vectors (``rows`` [n_items, D], taken as float64) by quantised
+        cosine; ``kw``: goctr_itemnbr_cfg fields.  Every method works on the result as on a co-occurrence build"""
+        if cfg is not None and kw:
+            raise TypeError("give either cfg or keywords")
+        cfg = cfg if cfg is not None else make_nbr_cfg(**kw)
+        rows = np.ascontiguousarray(rows, np.float64)
+        if rows.ndim != 2:
+            raise ValueError("rows takes one vector per item: [n_items, D]")
+        h = C.c_void_p()
+        capi.init()
+        capi.check(capi.load().goctr_itemcf_build_vectors(capi.ptr(rows, C.c_double), C.c_int64(rows.shape[0]), C.c_int32(rows.shape[1]),
+                                                          C.byref(cfg), C.byref(h)))
+        return cls._adopt(h)
+
+    @classmethod
+    def from_embedding(cls, table, n_items: int, cfg: capi.ItemnbrCfg | None = None, **kw) -> "ItemCF":
+        """goctr_itemcf_build_emb: the same over rows 0 .. n_items - 1 of an embedding table resident in HBM (a model.EmbeddingTable
+        or a raw goctr_emb handle), read as a serving pass reads them"""
+        if cfg is not None and kw:
+            raise TypeError("give either cfg or keywords")
+        cfg = cfg if cfg is not None else make_nbr_cfg(**kw)
+        h = C.c_void_p()
+        e = table._h if hasattr(table, "_h") else table
+        capi.check(capi.load().goctr_itemcf_build_emb(e, C.c_int64(_as_int("n_items", n_items)), C.byref(cfg), C.byref(h)))
+        return cls._adopt(h)
 
     def info(self) -> dict:
         n, m, d, t, v = C.c_int64(0), C.c_int32(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
@@ -128,6 +173,15 @@ class ItemCF:
             self.close()
         except Exception:
             pass
+
+
+def merge(a: ItemCF, b: ItemCF, mul_a=128, mul_b=128, n_nbr=64) -> ItemCF:
+    """goctr_itemcf_merge: one handle from the STORED lists of two (say a co-occurrence build and a vector build):
+    w = (mul_a * w_a + mul_b * w_b) >> 8, a missing side as 0, the first n_nbr by w descending, then item ascending"""
+    mul_a, mul_b, n_nbr = _as_int("mul_a", mul_a), _as_int("mul_b", mul_b), _as_int("n_nbr", n_nbr)
+    h = C.c_void_p()
+    capi.check(capi.load().goctr_itemcf_merge(a._h, b._h, C.c_int32(mul_a), C.c_int32(mul_b), C.c_int32(n_nbr), C.byref(h)))
+    return ItemCF._adopt(h)
 
 
 class Popular:

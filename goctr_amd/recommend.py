@@ -548,6 +548,22 @@ def BuildItemCF(recSys: DeviceRecSys, **cfg):
     return ItemCF(recSys._dense_cache, recSys.item_table.shape[0], **cfg)
 
 
+def BuildItemNeighbours(recSys: DeviceRecSys, **cfg):
+    """EXTENSION: neighbour lists from the recSys's item VECTORS (recall.ItemCF.from_embedding; ``cfg``: goctr_itemnbr_cfg fields):
+    the rows of its embedding table in HBM, over the rows of its item feature table -- the n_items BuildItemCF uses, so every
+    RecommendItemCF / RecommendBlend call takes either handle.  An item that never occurs in the behaviour cache has no
+    co-occurrence neighbours; it has these.  The lists are those of the table's rows at THIS call."""
+    from .recall import ItemCF
+    return ItemCF.from_embedding(recSys.emb, recSys.item_table.shape[0], **cfg)
+
+
+def MergeItemCF(a, b, mul_a=128, mul_b=128, n_nbr=64):
+    """EXTENSION: one handle from two (recall.merge), say BuildItemCF's and BuildItemNeighbours's, so that a request recalls from
+    both sources in one call; the weights are mixed as (mul_a * w_a + mul_b * w_b) >> 8 over the stored lists"""
+    from .recall import merge
+    return merge(a, b, mul_a, mul_b, n_nbr)
+
+
 def itemcf(model: Predictor, icf, users, ts=None, targets=None, k=10, pass_rows=0, validate=False, recall_cfg=None, **recall_kw):
     """goctr_recommend_itemcf over DENSE indices (users [nq], ts [nq] or None, targets [nq] or None): dict(items [nq, k], scores
     [nq, k], count [nq], cand_count [nq], n_failed, target_pos / target_rank [nq] when targets are given, cand_items / cand_w /

@@ -562,6 +562,58 @@ int goctr_recommend_blend(goctr_model* m, goctr_recsys* r, goctr_itemcf* icf /* 
                           uint8_t* out_src, int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank,
                           int32_t* cand_items, uint32_t* cand_w, float* cand_scores, uint8_t* cand_src, int64_t* n_failed);
 
+/* ---- Item neighbours from vectors: a second source of goctr_itemcf handles (no reference counterpart).  An item without
+ * co-occurrence has an empty ItemCF list; its vector (the item2vec rows goctr_emb_load_w2v leaves in the embedding table) still
+ * has neighbours.  The result is a goctr_itemcf like goctr_itemcf_build's: recall, blend, recommend, info, export and destroy take
+ * it unchanged.  Every output is defined bit for bit (tests/itemnbr_ref.py is the host restatement): rows are quantised once with
+ * pinned float64 operations, everything after that is integer.
+ *
+ * goctr_itemcf_build_vectors / goctr_itemcf_build_emb:
+ *   row            item i's vector v[0..D) as doubles; from a goctr_emb every float32 is widened exactly first
+ *   s              the float64 sum of v_d * v_d over d ascending: every product and every sum rounded once, nothing contracted
+ *   valid          iff s is finite and s > 0.  A NaN or Inf component makes the row invalid, and so does a vector whose squares
+ *                  overflow (components near 1e200) or all underflow to 0 (components near 1e-200)
+ *   q_d            (int16) rint((v_d / r) * 16384.0) with r = sqrt(s) correctly rounded, the division and the product rounded to
+ *                  nearest, rint ties to even; an invalid row has q = 0.  |q_d| <= 16384
+ *   dot(i,j)       the sum over d of q_i,d * q_j,d as a mathematical integer; |q| <= 16384 + 0.5 sqrt(D), so |dot| < 2.7e8 for
+ *                  D <= 1024: it fits int32
+ *   w(i,j)         dot >> 12 when dot > 0, else 0: a cosine in units of 2^-16, the scale of ItemCF's weights, at most 2^17 (far
+ *                  under the 2^23 the recall's uint32 sum relies on).  |w - 65536 cos(v_i, v_j)| <= 4 sqrt(D) + 2
+ *   neighbours     of a valid i: every j != i with w(i,j) >= min_w, by w descending, then j ascending; the first n_nbr are
+ *                  stored: nbr_w = w, nbr_co = (uint32) dot, padding -1 / 0 / 0.  An invalid row has an empty list and is nobody's
+ *                  neighbour (its dot is 0)
+ *   cnt[i]         1 for a valid row, else 0
+ *   info           distinct_pairs = the directed pairs (i, j != i) with w >= min_w over ALL pairs, not only the stored ones;
+ *                  total_pairs = the valid rows; cache_version = 0
+ *   passes         column items are taken pass_items at a time, one launch per pass; the running lists carry over in HBM.  No
+ *                  N x N array exists at any time and no output byte depends on pass_items or on a tile size
+ *   refused        (-1, *out untouched) a cfg outside its ranges, n_items <= 0 or > 2^31 - 1, D outside 1 .. 1024; for _emb,
+ *                  n_items > the table's V (its D is checked like D), or a table on another engine than the calling thread's
+ * goctr_itemcf_build_emb reads the table as a serving pass does: under the table's shared lock and behind its pending writes.
+ * It sees the rows before a concurrent goctr_emb_set_rows or after it, never a mixture. */
+typedef struct {
+  int32_t n_nbr;       /* 1 .. 256                          default 64 */
+  int32_t min_w;       /* 1 .. 65536, units of 2^-16        default 1  */
+  int64_t pass_items;  /* 0 = 65536, else 64 .. 2^22: column items one launch covers   default 0 */
+} goctr_itemnbr_cfg;
+void goctr_itemnbr_cfg_default(goctr_itemnbr_cfg* c);
+int  goctr_itemcf_build_vectors(const double* rows /* host [n_items, D] */, int64_t n_items, int32_t D,
+                                const goctr_itemnbr_cfg* cfg, goctr_itemcf** out);
+int  goctr_itemcf_build_emb(goctr_emb* e, int64_t n_items /* rows 0 .. n_items-1, <= e->V */,
+                            const goctr_itemnbr_cfg* cfg, goctr_itemcf** out);
+
+/* goctr_itemcf_merge: one handle from two, so that a request uses both sources in one call.  The merge is over the STORED,
+ * already truncated lists of a and b: this is not the truncation of a full merge (a pair that one side cut off counts as
+ * missing on that side).
+ *   entries        for every item i, the union of a's and b's stored neighbours of i; w = (mul_a * w_a + mul_b * w_b) >> 8 with
+ *                  a missing side as 0; entries with w = 0 are dropped
+ *   order          w descending, then j ascending; the first n_nbr are stored (padding -1 / 0 / 0)
+ *   nbr_co, cnt    the saturating uint32 sums of the two sides
+ *   info           distinct_pairs = the stored entries of the result; total_pairs = a's + b's; cache_version = the larger
+ *   refused        (-1, *out untouched) handles of different n_items or engines; mul_a or mul_b outside 0 .. 256;
+ *                  mul_a + mul_b outside 1 .. 256 (which keeps w <= 2^23); n_nbr outside 1 .. 256 */
+int  goctr_itemcf_merge(goctr_itemcf* a, goctr_itemcf* b, int32_t mul_a, int32_t mul_b, int32_t n_nbr, goctr_itemcf** out);
+
 /* The replica a multi-device training call (cfg.devices = n) keeps on engine `rank` (rank 0: the handle itself); NULL before
  * the first such call.  Borrowed: owned by the handle it was asked from.  For checks that the replicas are bit-identical
  * (tests, bench.py's replica checksum) -- every entry point works on it, on its own engine. */
