@@ -170,6 +170,11 @@ class ItemnbrCfg(C.Structure):
     _fields_ = [("n_nbr", C.c_int32), ("min_w", C.c_int32), ("pass_items", C.c_int64)]
 
 
+class MmrCfg(C.Structure):
+    """goctr_mmr_cfg (include/goctr.h)"""
+    _fields_ = [("k", C.c_int32), ("pool", C.c_int32), ("lambda_q", C.c_int32), ("max_per_group", C.c_int32)]
+
+
 TOPN_KEEP_SEEN, TOPN_DROP_ALL_SEEN, TOPN_DROP_SEEN_BEFORE = 0, 1, 2   # goctr_topn_cfg.exclude
 NS_UNIFORM, NS_POPULARITY, NS_POPULARITY_075 = 0, 1, 2      # goctr_negsample_cfg.weighting
 NS_ALL, NS_NEWEST, NS_ALL_BUT_NEWEST = 0, 1, 2              # goctr_negsample_cfg.which
@@ -215,6 +220,8 @@ SYMBOLS = [
     "goctr_popular_cfg_default", "goctr_popular_build", "goctr_popular_destroy", "goctr_popular_info", "goctr_popular_export",
     "goctr_blend_recall", "goctr_recommend_blend",
     "goctr_itemnbr_cfg_default", "goctr_itemcf_build_vectors", "goctr_itemcf_build_emb", "goctr_itemcf_merge",
+    "goctr_mmr_cfg_default", "goctr_itemvec_build_vectors", "goctr_itemvec_build_emb", "goctr_itemvec_destroy", "goctr_itemvec_info",
+    "goctr_itemvec_export", "goctr_rerank_mmr", "goctr_recommend_blend_mmr",
 ]
 
 _lib = None
@@ -238,7 +245,7 @@ def load() -> C.CDLL:
                      "goctr_w2v_cfg_default", "goctr_negsample_cfg_default", "goctr_samples_destroy", "goctr_topn_cfg_default",
                      "goctr_itemcf_cfg_default", "goctr_recall_cfg_default", "goctr_itemcf_destroy", "goctr_curve_cfg_default",
                      "goctr_multiclass_cfg_default", "goctr_popular_cfg_default", "goctr_popular_destroy",
-                     "goctr_itemnbr_cfg_default"):
+                     "goctr_itemnbr_cfg_default", "goctr_mmr_cfg_default", "goctr_itemvec_destroy"):
             getattr(_lib, name).restype = None
         _bm = C.POINTER(BinaryMetrics)
         _lib.goctr_metrics_binary.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, _bm]
@@ -320,6 +327,17 @@ def load() -> C.CDLL:
         _lib.goctr_recommend_blend.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32, _i32,
                                                C.c_int32, C.POINTER(RecallCfg), C.c_int32, C.c_int32, C.c_int64, _i32, _f32, _i32,
                                                _u8, _i32, _i32, _i64, _i32, _u32, _f32, _u8, _i64]
+        _mmr = C.POINTER(MmrCfg)
+        _lib.goctr_mmr_cfg_default.argtypes = [_mmr]
+        _lib.goctr_itemvec_build_vectors.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int32, _i32, C.POINTER(C.c_void_p)]
+        _lib.goctr_itemvec_build_emb.argtypes = [C.c_void_p, C.c_int64, _i32, C.POINTER(C.c_void_p)]
+        _lib.goctr_itemvec_destroy.argtypes = [C.c_void_p]
+        _lib.goctr_itemvec_info.argtypes = [C.c_void_p, _i64, _i32, _i64, _i32]
+        _lib.goctr_itemvec_export.argtypes = [C.c_void_p, C.POINTER(C.c_int16), _u8, _i32]
+        _lib.goctr_rerank_mmr.argtypes = [C.c_void_p, _i32, _f32, _i32, C.c_int64, C.c_int32, _mmr, _i32, _i32, _u32, _i32, _i64]
+        _lib.goctr_recommend_blend_mmr.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32, _i32,
+                                                   C.c_int32, C.POINTER(RecallCfg), C.c_int32, C.c_void_p, _mmr, C.c_int64, _i32, _f32,
+                                                   _i32, _u8, _i32, _i32, _i64, _i32, _u32, _f32, _u8, _i64, _i32, _u32, _i32]
     return _lib
 
 
@@ -469,6 +487,14 @@ def default_recall_cfg(**kw) -> RecallCfg:
 def default_itemnbr_cfg(**kw) -> ItemnbrCfg:
     c = ItemnbrCfg()
     load().goctr_itemnbr_cfg_default(C.byref(c))
+    for k, v in kw.items():
+        setattr(c, k, v)
+    return c
+
+
+def default_mmr_cfg(**kw) -> MmrCfg:
+    c = MmrCfg()
+    load().goctr_mmr_cfg_default(C.byref(c))
     for k, v in kw.items():
         setattr(c, k, v)
     return c

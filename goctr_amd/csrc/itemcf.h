@@ -5,6 +5,8 @@
 #include "topn.h"
 
 // item-to-item neighbour lists resident in HBM; immutable after the build, independent of the cache it was built from
+struct goctr_itemvec;                              // itemvec.h
+
 struct goctr_itemcf {
   goctr::Engine* const eng = &goctr::engine();   // the engine (device, streams, arena) the handle was created on
   int64_t n_items = 0;
@@ -58,9 +60,39 @@ int recall_launch(const goctr_itemcf* h, const long long* off, const int32_t* se
 // the target's place (-1: none); src is null unless the driver was asked for sources
 struct RecallRows { int32_t* items; unsigned int* w; int32_t* count; int32_t* tpos; unsigned char* src; };
 using RecallStage = std::function<int(const RecallInputs&, const RecallRows&, hipStream_t)>;
+// the device arrays of a selection launch (icf_select_kernel, or rerank.hip's mmr_select_kernel in its place): one workgroup per
+// request row over the row's scored candidates
+struct IcfSelArgs {
+  const long long* pre; const int32_t* cand; const int32_t* count; const int32_t* tpos;   // tpos may be null
+  const float* scores; const unsigned char* failed;                                       // flat [total]
+  int n_cand, k;
+  int32_t* out_items; unsigned* out_scores; int32_t* out_count; long long* out_rank;
+  float* cand_scores;                                                                     // [nq, n_cand] or null
+  unsigned long long* n_failed;
+  const unsigned char* src; unsigned char* out_src;                                       // [nq, n_cand] -> [nq, k]; both or neither
+};
+
+// a re-rank in place of the driver's last step (goctr_recommend_blend_mmr): the handle, the cfg and the host outputs the selection
+// adds, [n_req, k], [n_req, k], [n_req], each may be null
+struct RerankStage {
+  const goctr_itemvec* v; goctr_mmr_cfg cfg;
+  int32_t* out_obj; uint32_t* out_pen; int32_t* out_target_place;
+};
+// the device outputs mmr_select_kernel adds to IcfSelArgs's: [nq, k] places, obj, pen and [nq] the target's place in the returned
+// list; each may be null
+struct MmrOut { int32_t* pos; int32_t* obj; unsigned int* pen; int32_t* tplace; };
+// rerank.hip: the MMR selection over nq rows on `st`, s.k = cfg.k.  With s.pre null row q's scores start at q * s.n_cand; s.failed,
+// s.out_items, s.out_scores and s.out_rank may be null here (the standalone entry has none of them)
+int mmr_launch(const goctr_itemvec* v, const goctr_mmr_cfg& cfg, const IcfSelArgs& s, const MmrOut& o, int64_t nq, hipStream_t st);
+// the cfg's ranges, and groups when a cap asks for them (sets the error text)
+int mmr_check_cfg(const goctr_itemvec* v, const goctr_mmr_cfg* cfg, const char* who);
+
 // recall, then rank, over a prepared slot: stages the request columns, runs `recall` on the slot's stream, writes and scores the
 // candidates' keys pass_rows at a time and keeps every row's best k (icf_keys_kernel, icf_select_kernel); with_src: a.out_src and
-// a.cand_src are served from the stage's src column.  Returns after the results are in the caller's arrays
-int recall_rank_run(const TopnScorer& sc, const char* who, const ItemcfRecArgs& a, bool with_src, const RecallStage& recall);
+// a.cand_src are served from the stage's src column.  With `rerank` the last launch is mmr_launch instead of icf_select_kernel
+// (a.k = rerank->cfg.k); without it nothing differs from a call before there was one.  Returns after the results are in the
+// caller's arrays
+int recall_rank_run(const TopnScorer& sc, const char* who, const ItemcfRecArgs& a, bool with_src, const RecallStage& recall,
+                    const RerankStage* rerank = nullptr);
 
 }  // namespace goctr

@@ -15,7 +15,8 @@
 //                         descending and, among equal w, in the order they had: j ascending
 //   icf_starts_kernel, icf_emit_kernel   the first n_nbr pairs of every item with w > 0
 // Recall (icf_recall_kernel): one workgroup per request row, below.  Recommend: recall_rank_run at the end of the file, the driver
-// goctr_recommend_itemcf and goctr_recommend_blend (popular.hip) share: they differ in the recall stage alone.
+// goctr_recommend_itemcf and goctr_recommend_blend (popular.hip) share: they differ in the recall stage alone.  goctr_recommend_blend_mmr
+// hands the driver a re-rank stage: rerank.hip's selection then runs in place of icf_select_kernel.
 #include <algorithm>
 #include <climits>
 #include <memory>
@@ -389,16 +390,6 @@ __global__ __launch_bounds__(256) void icf_keys_kernel(const long long* __restri
   k_ts[i] = ts[lo]; k_users[i] = users[lo]; k_items[i] = cand[lo * n_cand + (r - pre[lo])];
 }
 
-struct IcfSelArgs {
-  const long long* pre; const int32_t* cand; const int32_t* count; const int32_t* tpos;   // tpos may be null
-  const float* scores; const unsigned char* failed;                                       // flat [total]
-  int n_cand, k;
-  int32_t* out_items; unsigned* out_scores; int32_t* out_count; long long* out_rank;
-  float* cand_scores;                                                                     // [nq, n_cand] or null
-  unsigned long long* n_failed;
-  const unsigned char* src; unsigned char* out_src;                                       // [nq, n_cand] -> [nq, k]; both or neither
-};
-
 // one workgroup per request row, one thread per recalled candidate: topn's order rule over at most 1024 keys
 __global__ __launch_bounds__(SEL_THREADS) void icf_select_kernel(IcfSelArgs a) {
   __shared__ unsigned long long skey[SEL_CAP];
@@ -514,7 +505,8 @@ int itemcf_check_recommend(const goctr_itemcf* h, const ItemcfRecArgs& a, int64_
   return recall_check_recommend(who, a, n_users);
 }
 
-int recall_rank_run(const TopnScorer& sc, const char* who, const ItemcfRecArgs& a, bool with_src, const RecallStage& recall) {
+int recall_rank_run(const TopnScorer& sc, const char* who, const ItemcfRecArgs& a, bool with_src, const RecallStage& recall,
+                    const RerankStage* rerank) {
   const int64_t nq = a.n_req;
   const int nc = a.rcfg.n_cand, k = a.k;
   const int64_t P = a.pass_rows ? a.pass_rows : TOPN_DEFAULT_PASS_ROWS;
@@ -527,8 +519,10 @@ int recall_rank_run(const TopnScorer& sc, const char* who, const ItemcfRecArgs& 
   DevBuf<float> f_scores, c_scores;
   DevBuf<unsigned char> f_failed, c_src, o_src;
   DevBuf<unsigned long long> d_nfailed;
-  std::vector<int32_t> h_count((size_t)nq), h_tpos((size_t)nq), h_items((size_t)nq * k), h_ocount((size_t)nq), h_citems;
-  std::vector<unsigned> h_scores((size_t)nq * k), h_cw;
+  DevBuf<int32_t> r_obj, r_tplace;                        // the re-rank's own outputs
+  DevBuf<unsigned int> r_pen;
+  std::vector<int32_t> h_count((size_t)nq), h_tpos((size_t)nq), h_items((size_t)nq * k), h_ocount((size_t)nq), h_citems, h_robj, h_rtplace;
+  std::vector<unsigned> h_scores((size_t)nq * k), h_cw, h_rpen;
   std::vector<float> h_cscores;
   std::vector<unsigned char> h_osrc, h_csrc;
   std::vector<long long> h_pre((size_t)nq + 1), h_rank((size_t)nq);
@@ -541,6 +535,7 @@ int recall_rank_run(const TopnScorer& sc, const char* who, const ItemcfRecArgs& 
       d_nfailed.alloc(1, false)) return -1;
   if (a.cand_scores && c_scores.alloc((size_t)nq * nc, false)) return -1;
   if (with_src && (c_src.alloc((size_t)nq * nc, false) || o_src.alloc((size_t)nq * k, false))) return -1;
+  if (rerank && (r_obj.alloc((size_t)nq * k, false) || r_pen.alloc((size_t)nq * k, false) || r_tplace.alloc((size_t)nq, false))) return -1;
   GOCTR_HIP(hipMemsetAsync(d_nfailed.p, 0, sizeof(unsigned long long), st));
   // 1. recall on the slot's stream; its counts decide the key space, so they come back before the passes are cut
   if (recall(in, RecallRows{c_items.p, c_w.p, c_count.p, c_tpos.p, with_src ? c_src.p : nullptr}, st)) return -1;
@@ -573,8 +568,12 @@ int recall_rank_run(const TopnScorer& sc, const char* who, const ItemcfRecArgs& 
   s.out_items = o_items.p; s.out_scores = o_scores.p; s.out_count = o_count.p; s.out_rank = o_rank.p;
   s.cand_scores = a.cand_scores ? c_scores.p : nullptr; s.n_failed = d_nfailed.p;
   s.src = with_src ? c_src.p : nullptr; s.out_src = with_src ? o_src.p : nullptr;
-  hipLaunchKernelGGL(icf_select_kernel, dim3((unsigned)nq), dim3(SEL_THREADS), 0, st, s);
-  GOCTR_HIP(hipGetLastError());
+  if (rerank) {
+    if (mmr_launch(rerank->v, rerank->cfg, s, MmrOut{nullptr, r_obj.p, r_pen.p, r_tplace.p}, nq, st)) return -1;
+  } else {
+    hipLaunchKernelGGL(icf_select_kernel, dim3((unsigned)nq), dim3(SEL_THREADS), 0, st, s);
+    GOCTR_HIP(hipGetLastError());
+  }
   // the results are staged on the host so that a failing copy leaves the caller's arrays as they were
   GOCTR_HIP(hipMemcpyAsync(h_items.data(), o_items.p, sizeof(int32_t) * h_items.size(), hipMemcpyDeviceToHost, st));
   GOCTR_HIP(hipMemcpyAsync(h_scores.data(), o_scores.p, sizeof(unsigned) * h_scores.size(), hipMemcpyDeviceToHost, st));
@@ -587,6 +586,9 @@ int recall_rank_run(const TopnScorer& sc, const char* who, const ItemcfRecArgs& 
   if (a.cand_scores) { h_cscores.resize((size_t)nq * nc); GOCTR_HIP(hipMemcpyAsync(h_cscores.data(), c_scores.p, sizeof(float) * h_cscores.size(), hipMemcpyDeviceToHost, st)); }
   if (with_src && a.out_src) { h_osrc.resize((size_t)nq * k); GOCTR_HIP(hipMemcpyAsync(h_osrc.data(), o_src.p, h_osrc.size(), hipMemcpyDeviceToHost, st)); }
   if (with_src && a.cand_src) { h_csrc.resize((size_t)nq * nc); GOCTR_HIP(hipMemcpyAsync(h_csrc.data(), c_src.p, h_csrc.size(), hipMemcpyDeviceToHost, st)); }
+  if (rerank && rerank->out_obj) { h_robj.resize((size_t)nq * k); GOCTR_HIP(hipMemcpyAsync(h_robj.data(), r_obj.p, sizeof(int32_t) * h_robj.size(), hipMemcpyDeviceToHost, st)); }
+  if (rerank && rerank->out_pen) { h_rpen.resize((size_t)nq * k); GOCTR_HIP(hipMemcpyAsync(h_rpen.data(), r_pen.p, sizeof(unsigned) * h_rpen.size(), hipMemcpyDeviceToHost, st)); }
+  if (rerank && rerank->out_target_place) { h_rtplace.resize((size_t)nq); GOCTR_HIP(hipMemcpyAsync(h_rtplace.data(), r_tplace.p, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, st)); }
   GOCTR_HIP(hipStreamSynchronize(st));
   memcpy(a.out_items, h_items.data(), sizeof(int32_t) * h_items.size());
   memcpy(a.out_scores, h_scores.data(), sizeof(unsigned) * h_scores.size());
@@ -599,6 +601,9 @@ int recall_rank_run(const TopnScorer& sc, const char* who, const ItemcfRecArgs& 
   if (a.cand_scores) memcpy(a.cand_scores, h_cscores.data(), sizeof(float) * h_cscores.size());
   if (!h_osrc.empty()) memcpy(a.out_src, h_osrc.data(), h_osrc.size());
   if (!h_csrc.empty()) memcpy(a.cand_src, h_csrc.data(), h_csrc.size());
+  if (!h_robj.empty()) memcpy(rerank->out_obj, h_robj.data(), sizeof(int32_t) * h_robj.size());
+  if (!h_rpen.empty()) memcpy(rerank->out_pen, h_rpen.data(), sizeof(unsigned) * h_rpen.size());
+  if (!h_rtplace.empty()) memcpy(rerank->out_target_place, h_rtplace.data(), sizeof(int32_t) * (size_t)nq);
   if (a.n_failed) *a.n_failed = (int64_t)h_nfailed;
   return 0;
 }

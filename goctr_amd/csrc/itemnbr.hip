@@ -2,8 +2,8 @@
 // and from two handles (include/goctr.h states the semantics; tests/itemnbr_ref.py restates them on the host, bit for bit).
 //
 // Build (engine stream, engine lock; _emb: the table's shared lock while the rows are read):
-//   inb_quant_kernel    one row per thread: s, r, q (pinned float64 operations), written once as two int8 planes hi / lo with
-//                       q = 256 hi + lo, lo in [-128, 127], hi in [-64, 64]; D is padded with zeros to the MFMA's K = 64
+//   iv_quant_kernel     (itemvec.h, shared with goctr_itemvec) one row per thread: s, r, q, written once as two int8 planes hi / lo
+//                       with q = 256 hi + lo; D is padded with zeros to the MFMA's K = 64
 //   per pass of pass_items column items
 //     inb_pairs_kernel  a workgroup owns 32 query rows (two 16-row MFMA tiles per wavefront) and walks the pass's columns 128 at a
 //                       time, 32 per wavefront.  dot = 65536 hi.hi + 256 (hi.lo + lo.hi) + lo.lo from four
@@ -22,8 +22,8 @@
 #include <shared_mutex>
 
 #define GOCTR_NO_PLAIN_KERNELS      // the kernel headers' plain kernels belong to ctr.hip
-#include "ctr_model.h"
 #include "itemcf.h"
+#include "itemvec.h"
 
 using namespace goctr;
 
@@ -32,7 +32,7 @@ namespace {
 using u64 = unsigned long long;
 using i32x4 = __attribute__((ext_vector_type(4))) int;
 
-constexpr int NB_K = 64;                       // the MFMA's K: D is padded to a multiple
+constexpr int NB_K = IV_K;                     // the MFMA's K: D is padded to a multiple
 constexpr int NB_ROWS = 32;                    // query rows of a workgroup
 constexpr int NB_THREADS = 256;
 constexpr int NB_WAVES = NB_THREADS / 64;
@@ -44,33 +44,6 @@ static_assert(NB_ROWS % NB_WAVES == 0, "the trim gives every wavefront whole row
 // list capacity in LDS for lists of n_nbr: a trimmed list and one step's appends fit in each half
 inline int nb_cap(int n_nbr) { return n_nbr <= NB_STEP ? 2 * NB_STEP : 2 * 256; }
 static_assert(NB_STEP <= 256 && (2 * 256 * 8 + 12) * NB_ROWS <= 160 * 1024, "the largest lists fit in LDS");
-
-// ------------------------------------------------------------------------------------------------------------ quantise
-template <class T>
-__global__ __launch_bounds__(256) void inb_quant_kernel(const T* __restrict__ rows, long long n, int D, int Dp,
-                                                        signed char* __restrict__ hi, signed char* __restrict__ lo,
-                                                        unsigned int* __restrict__ cnt, u64* __restrict__ n_valid) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const T* v = rows + (size_t)i * D;
-  double s = 0.0;
-  for (int d = 0; d < D; ++d) {
-    const double x = (double)v[d];
-    s = __dadd_rn(s, __dmul_rn(x, x));
-  }
-  const bool finite = ((u64)__double_as_longlong(s) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
-  const bool valid = finite && s > 0.0;
-  cnt[i] = valid ? 1u : 0u;
-  if (!valid) return;                          // (the planes were zeroed: q = 0)
-  atomicAdd(n_valid, 1ull);
-  const double r = __dsqrt_rn(s);
-  for (int d = 0; d < D; ++d) {
-    const int q = (int)rint(__dmul_rn(__ddiv_rn((double)v[d], r), 16384.0));
-    const int l = ((q + 128) & 255) - 128;
-    hi[(size_t)i * Dp + d] = (signed char)((q - l) >> 8);
-    lo[(size_t)i * Dp + d] = (signed char)l;
-  }
-}
 
 // ----------------------------------------------------------------------------------------------------------- all pairs
 struct PairsArgs {
@@ -285,12 +258,6 @@ int check_cfg(const goctr_itemnbr_cfg* cfg, const char* who) {
   return 0;
 }
 
-int check_shape(int64_t n_items, int64_t D, const char* who) {
-  GOCTR_CHECK(n_items > 0 && n_items <= INT32_MAX, "%s: n_items = %lld (1 .. 2^31 - 1)", who, (long long)n_items);
-  GOCTR_CHECK(D >= 1 && D <= 1024, "%s: D = %lld (1 .. 1024)", who, (long long)D);
-  return 0;
-}
-
 // the planes, the counters and the handle's arrays of one build; `quantise` queues the quantise launch and returns once the
 // source rows are no longer needed
 struct NbrBuild {
@@ -307,9 +274,7 @@ int build_from_rows(const T* d_rows, int64_t n_items, int D, const goctr_itemnbr
   r->n_items = n_items; r->M = M; r->cache_version = 0;
   if (r->cnt.alloc((size_t)n_items, false) || r->nbr_items.alloc(nm, false) || r->nbr_w.alloc(nm, false) ||
       r->nbr_co.alloc(nm, false) || ws.hi.alloc(plane) || ws.lo.alloc(plane) || ws.lists.alloc(nm) || ws.counters.alloc(2)) return -1;
-  hipLaunchKernelGGL(inb_quant_kernel<T>, dim3((unsigned)cdiv(n_items, 256)), dim3(256), 0, s, d_rows, (long long)n_items, D, Dp,
-                     ws.hi.p, ws.lo.p, r->cnt.p, ws.counters.p);
-  GOCTR_HIP(hipGetLastError());
+  if (iv_quantise<T>(d_rows, n_items, D, Dp, ws.hi.p, ws.lo.p, r->cnt.p, ws.counters.p)) return -1;
   if (rows_done()) return -1;
   PairsArgs a{};
   a.hi = ws.hi.p; a.lo = ws.lo.p; a.Dp = Dp; a.n_items = n_items; a.n_nbr = M; a.cap = cap; a.min_w = (unsigned int)cfg->min_w;
@@ -337,11 +302,6 @@ int build_from_rows(const T* d_rows, int64_t n_items, int D, const goctr_itemnbr
   return 0;
 }
 
-// drains the engine stream before a failing build's device buffers go back to the arena
-struct DrainMain {
-  ~DrainMain() { (void)hipStreamSynchronize(engine().stream); }
-};
-
 }  // namespace
 
 extern "C" {
@@ -355,7 +315,7 @@ int goctr_itemcf_build_vectors(const double* rows, int64_t n_items, int32_t D, c
   GOCTR_ENTER();
   const char* who = "goctr_itemcf_build_vectors";
   GOCTR_CHECK(rows && cfg && out, "%s: null argument", who);
-  if (check_cfg(cfg, who) || check_shape(n_items, D, who)) return -1;
+  if (check_cfg(cfg, who) || iv_check_shape(n_items, D, who)) return -1;
   std::unique_ptr<goctr_itemcf> r(new goctr_itemcf);
   NbrBuild ws;
   DevBuf<double> d_rows;
@@ -371,22 +331,13 @@ int goctr_itemcf_build_emb(goctr_emb* e, int64_t n_items, const goctr_itemnbr_cf
   const char* who = "goctr_itemcf_build_emb";
   GOCTR_CHECK(e && cfg && out, "%s: null argument", who);
   GOCTR_CHECK(e->eng == &engine(), "%s: the table was created on another engine (device)", who);
-  if (check_cfg(cfg, who) || check_shape(n_items, e->D, who)) return -1;
+  if (check_cfg(cfg, who) || iv_check_shape(n_items, e->D, who)) return -1;
   GOCTR_CHECK(n_items <= e->V, "%s: n_items = %lld, the table has %lld rows", who, (long long)n_items, (long long)e->V);
   std::unique_ptr<goctr_itemcf> r(new goctr_itemcf);
   NbrBuild ws;
-  // the rows are read as a serving pass reads them: under the shared lock, behind the last queued write; the lock goes once the
-  // quantise launch, the only reader, has finished -- on an error path too: it is declared in front of the drain, so the stream
-  // is drained before the lock is released
-  std::shared_lock<std::shared_mutex> le(e->mu);
-  DrainMain drain;
-  if (e->rows_pending.load(std::memory_order_acquire) && e->ev_rows) GOCTR_HIP(hipEventSynchronize(e->ev_rows));
-  const auto rows_done = [&]() -> int {
-    GOCTR_HIP(hipStreamSynchronize(engine().stream));
-    le.unlock();
-    return 0;
-  };
-  if (build_from_rows<float>(e->rows.p, n_items, e->D, cfg, ws, r.get(), rows_done)) return -1;
+  EmbRowsRead rd(e);                           // (behind the buffers: itemvec.h says what it holds and in which order it lets go)
+  if (rd.wait(e)) return -1;
+  if (build_from_rows<float>(e->rows.p, n_items, e->D, cfg, ws, r.get(), [&] { return rd.done(); })) return -1;
   *out = r.release();
   return 0;
 }

@@ -25,9 +25,11 @@ struct BlendArgs {
   const int32_t* extra; int n_extra, quota_pop;
 };
 
-// the refusals that need no slot (sets the error text)
-int blend_check_recommend(const BlendArgs& b, const ItemcfRecArgs& a, int64_t n_users, int64_t n_items);
-// the whole call over a prepared slot; returns after the results are in the caller's arrays (the stream is drained on every path)
-int blend_recommend_run(const TopnScorer& sc, const BlendArgs& b, const ItemcfRecArgs& a);
+// the refusals that need no slot (sets the error text); `who`: the entry's name, goctr_recommend_blend or goctr_recommend_blend_mmr
+int blend_check_recommend(const char* who, const BlendArgs& b, const ItemcfRecArgs& a, int64_t n_users, int64_t n_items);
+// the whole call over a prepared slot; returns after the results are in the caller's arrays (the stream is drained on every path).
+// rerank: recall_rank_run's, null for goctr_recommend_blend
+int blend_recommend_run(const TopnScorer& sc, const char* who, const BlendArgs& b, const ItemcfRecArgs& a,
+                        const RerankStage* rerank = nullptr);
 
 }  // namespace goctr

@@ -295,8 +295,7 @@ int blend_check(const char* who, const BlendArgs& b, const goctr_recall_cfg& cfg
 
 namespace goctr {
 
-int blend_check_recommend(const BlendArgs& b, const ItemcfRecArgs& a, int64_t n_users, int64_t n_items) {
-  const char* who = "goctr_recommend_blend";
+int blend_check_recommend(const char* who, const BlendArgs& b, const ItemcfRecArgs& a, int64_t n_users, int64_t n_items) {
   if (recall_check_recommend(who, a, n_users)) return -1;
   long long n = 0;
   if (blend_check(who, b, a.rcfg, n_items, &n)) return -1;
@@ -304,9 +303,9 @@ int blend_check_recommend(const BlendArgs& b, const ItemcfRecArgs& a, int64_t n_
   return 0;
 }
 
-int blend_recommend_run(const TopnScorer& sc, const BlendArgs& b, const ItemcfRecArgs& a) {
+int blend_recommend_run(const TopnScorer& sc, const char* who, const BlendArgs& b, const ItemcfRecArgs& a, const RerankStage* rerank) {
   DevBuf<int32_t> d_extra;                    // (outlives the run, which drains the stream on every path)
-  return recall_rank_run(sc, "goctr_recommend_blend", a, true, [&](const RecallInputs& in, const RecallRows& o, hipStream_t st) {
+  return recall_rank_run(sc, who, a, true, [&](const RecallInputs& in, const RecallRows& o, hipStream_t st) {
     if (b.n_extra > 0) {
       const size_t n = (size_t)a.n_req * (size_t)b.n_extra;
       if (d_extra.alloc(n, false)) return -1;
@@ -314,7 +313,7 @@ int blend_recommend_run(const TopnScorer& sc, const BlendArgs& b, const ItemcfRe
     }
     return blend_launch(b, CacheImage{sc.ub_off, sc.ub_items, sc.ub_ts}, sc.n_items, in, a.targets != nullptr, a.n_req, a.rcfg,
                         d_extra.p, o, st);
-  });
+  }, rerank);
 }
 
 }  // namespace goctr

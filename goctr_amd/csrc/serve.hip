@@ -1,5 +1,6 @@
 // serve.hip -- serving (goctr_recsys_*, goctr_batch_predict, goctr_rank, goctr_predict_dense, and the entries of goctr_recommend_topn,
-// goctr_recommend_itemcf and goctr_recommend_blend, whose drivers are topn.hip, itemcf.hip and popular.hip) over the forward launches
+// goctr_recommend_itemcf, goctr_recommend_blend and goctr_recommend_blend_mmr, whose drivers are topn.hip, itemcf.hip, popular.hip and
+// -- the last step of the last one -- rerank.hip) over the forward launches
 // of the step (ctr.hip): the recsys
 // handle, the serving slots and their pool, the passes, the micro-batcher.  The behaviour cache the passes read: ubcache.hip.
 #define GOCTR_NO_PLAIN_KERNELS      // the kernel headers' plain kernels belong to ctr.hip
@@ -13,6 +14,7 @@
 
 #include "ctr_model.h"
 #include "itemcf.h"
+#include "itemvec.h"
 #include "popular.h"
 #include "staging.h"
 #include "topn.h"
@@ -579,8 +581,37 @@ int goctr_recommend_blend(goctr_model* m, goctr_recsys* r, goctr_itemcf* icf, go
   const ItemcfRecArgs a{users, ts, n_req, targets, *recall_cfg, k, pass_rows, out_items, out_scores, out_count, out_cand_count,
                         out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed, out_src, cand_src};
   const BlendArgs b{icf, pop, extra, extra ? n_extra : 0, quota_pop};
-  if (blend_check_recommend(b, a, r->n_users, r->n_items)) return -1;
-  return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return blend_recommend_run(sc, b, a); });
+  if (blend_check_recommend("goctr_recommend_blend", b, a, r->n_users, r->n_items)) return -1;
+  return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return blend_recommend_run(sc, "goctr_recommend_blend", b, a); });
+}
+
+// goctr_recommend_blend with the MMR selection (rerank.hip) as the driver's last step; everything in front of it is the call above
+int goctr_recommend_blend_mmr(goctr_model* m, goctr_recsys* r, goctr_itemcf* icf, goctr_popular* pop, const int32_t* users,
+                              const int64_t* ts, int64_t n_req, const int32_t* targets, const int32_t* extra, int32_t n_extra,
+                              const goctr_recall_cfg* recall_cfg, int32_t quota_pop, goctr_itemvec* v, const goctr_mmr_cfg* cfg,
+                              int64_t pass_rows, int32_t* out_items, float* out_scores, int32_t* out_count, uint8_t* out_src,
+                              int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank, int32_t* cand_items,
+                              uint32_t* cand_w, float* cand_scores, uint8_t* cand_src, int64_t* n_failed, int32_t* out_obj,
+                              uint32_t* out_pen, int32_t* out_target_place) {
+  EngineScope on(handle_engine(m));
+  if (require_engine()) return -1;
+  const char* who = "goctr_recommend_blend_mmr";
+  GOCTR_CHECK(m && r && recall_cfg && v && cfg, "%s: bad arguments", who);
+  GOCTR_SAME_ENGINE(m, r);
+  GOCTR_SAME_ENGINE(m, icf);
+  GOCTR_SAME_ENGINE(m, pop);
+  GOCTR_SAME_ENGINE(m, v);
+  if (check_recsys_dims(who, m, r)) return -1;
+  GOCTR_CHECK(n_extra >= 0 && n_extra <= 1024, "%s: n_extra = %d is outside 0 .. 1024", who, n_extra);
+  if (mmr_check_cfg(v, cfg, who)) return -1;
+  GOCTR_CHECK(v->n_items == r->n_items, "%s: the item vectors cover %lld items, the recsys %lld", who, (long long)v->n_items,
+              (long long)r->n_items);
+  const ItemcfRecArgs a{users, ts, n_req, targets, *recall_cfg, cfg->k, pass_rows, out_items, out_scores, out_count, out_cand_count,
+                        out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed, out_src, cand_src};
+  const BlendArgs b{icf, pop, extra, extra ? n_extra : 0, quota_pop};
+  if (blend_check_recommend(who, b, a, r->n_users, r->n_items)) return -1;
+  const RerankStage rr{v, *cfg, out_obj, out_pen, out_target_place};
+  return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return blend_recommend_run(sc, who, b, a, &rr); });
 }
 
 // model.Predict's own convention (model/model.go:242-352): `rows` dense TrainSample rows in HOST memory -> y_out [rows].

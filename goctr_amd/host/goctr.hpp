@@ -672,6 +672,60 @@ inline std::vector<ItemScore> RecommendBlend(model::CtrNet& net, RecSys& rs, con
                                              int64_t now, const goctr_recall_cfg& rcfg = ItemCF::DefaultRecallCfg(), int quota_pop = 0) {
   return RecommendBlendBatch(net, rs, icf, pop, {userId}, n, {now}, rcfg, quota_pop).lists[0];
 }
+
+// Quantised item vectors and optional group ids resident in HBM (goctr_itemvec_*): what RecommendDiverseBatch measures similarity
+// with.  `groups`: one id per item (negative = none), or empty
+class ItemVectors {
+ public:
+  ItemVectors(goctr_emb* table, int64_t n_items, const std::vector<int32_t>& groups = {}) {
+    if (!groups.empty() && (int64_t)groups.size() != n_items) throw std::invalid_argument("ItemVectors: one group per item");
+    check(goctr_itemvec_build_emb(table, n_items, groups.empty() ? nullptr : groups.data(), &h_));
+  }
+  ItemVectors(const std::vector<double>& rows, int64_t n_items, int D, const std::vector<int32_t>& groups = {}) {
+    if ((int64_t)rows.size() != n_items * D) throw std::invalid_argument("ItemVectors: n_items rows of D");
+    if (!groups.empty() && (int64_t)groups.size() != n_items) throw std::invalid_argument("ItemVectors: one group per item");
+    check(goctr_itemvec_build_vectors(rows.data(), n_items, D, groups.empty() ? nullptr : groups.data(), &h_));
+  }
+  ItemVectors(const ItemVectors&) = delete;
+  ItemVectors& operator=(const ItemVectors&) = delete;
+  ItemVectors(ItemVectors&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  ~ItemVectors() { goctr_itemvec_destroy(h_); }
+  goctr_itemvec* handle() const { return h_; }
+  static goctr_mmr_cfg DefaultCfg() { goctr_mmr_cfg c; goctr_mmr_cfg_default(&c); return c; }
+
+ private:
+  goctr_itemvec* h_ = nullptr;
+};
+
+// RecommendBlendBatch with the diversity re-rank as its last step (goctr_recommend_blend_mmr): mcfg.k items per row in the order
+// of selection; mcfg.lambda_q = 256 without a cap returns RecommendBlendBatch's lists
+inline TopN RecommendDiverseBatch(model::CtrNet& net, RecSys& rs, const ItemCF* icf, const Popular* pop, const ItemVectors& vec,
+                                  const std::vector<int32_t>& users, const goctr_mmr_cfg& mcfg = ItemVectors::DefaultCfg(),
+                                  const std::vector<int64_t>& ts = {}, const goctr_recall_cfg& rcfg = ItemCF::DefaultRecallCfg(),
+                                  int quota_pop = 0, const std::vector<int32_t>& extra = {}, int n_extra = 0,
+                                  const std::vector<int32_t>& targets = {}, int64_t pass_rows = 0) {
+  const int64_t nq = (int64_t)users.size();
+  const int n = mcfg.k;
+  if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("RecommendDiverseBatch: one timestamp per user");
+  if (!targets.empty() && targets.size() != users.size()) throw std::invalid_argument("RecommendDiverseBatch: one target per user");
+  if (extra.size() != users.size() * (size_t)std::max(n_extra, 0)) throw std::invalid_argument("RecommendDiverseBatch: n_extra entries per user");
+  if (n < 1) throw std::invalid_argument("RecommendDiverseBatch: k must be positive");
+  std::vector<int32_t> items((size_t)nq * n), count((size_t)nq);
+  std::vector<float> scores((size_t)nq * n);
+  TopN out;
+  if (!targets.empty()) out.target_rank.resize((size_t)nq);
+  check(goctr_recommend_blend_mmr(net.Vm(), rs.handle(), icf ? icf->handle() : nullptr, pop ? pop->handle() : nullptr, users.data(),
+                                  ts.empty() ? nullptr : ts.data(), nq, targets.empty() ? nullptr : targets.data(),
+                                  extra.empty() ? nullptr : extra.data(), n_extra, &rcfg, quota_pop, vec.handle(), &mcfg, pass_rows,
+                                  items.data(), scores.data(), count.data(), nullptr, nullptr, nullptr,
+                                  targets.empty() ? nullptr : out.target_rank.data(), nullptr, nullptr, nullptr, nullptr, &out.n_failed,
+                                  nullptr, nullptr, nullptr));
+  out.lists.resize((size_t)nq);
+  for (int64_t q = 0; q < nq; ++q)
+    for (int j = 0; j < count[(size_t)q]; ++j)
+      out.lists[(size_t)q].push_back(ItemScore{items[(size_t)q * n + j], scores[(size_t)q * n + j]});
+  return out;
+}
 }  // namespace recommend
 
 namespace din {

@@ -1,5 +1,5 @@
-"""recall -- ItemCF recall, popularity recall and the blend of recall channels on the device (goctr_itemcf_*, goctr_popular_*,
-goctr_blend_recall; include/goctr.h).
+"""recall -- ItemCF recall, popularity recall, the blend of recall channels and the diversity re-rank on the device (goctr_itemcf_*,
+goctr_popular_*, goctr_blend_recall, goctr_itemvec_*, goctr_rerank_mmr; include/goctr.h).
 
 The reference answers a request without candidates with "todo: some default recall algorithm" (recommend/api.go:115-118).
 ``ItemCF`` is that algorithm: item-to-item collaborative filtering over one image of the behaviour cache gives every item a list of
@@ -10,6 +10,10 @@ restatement).
 ``Popular`` is the second channel: a time-decayed popularity list of the same image, and ``blend`` merges the channels for every
 request row -- ItemCF's candidates, a list of the caller's, then the popularity list -- de-duplicated and seen-filtered on the
 device, so that a row without history still gets candidates (tests/popular_ref.py is the host restatement).
+
+``ItemVectors`` holds the catalogue's quantised vectors (and optionally a group id per item) in HBM, and ``rerank_mmr`` picks k of
+every row's scored candidates greedily, trading relevance against similarity to what it has picked, with a cap per group
+(tests/mmr_ref.py is the host restatement).  ``recommend.RecommendDiverse`` runs it as the last step of RecommendBlend.
 """
 from __future__ import annotations
 
@@ -24,6 +28,7 @@ _BUILD_FIELDS = {"window", "max_len", "n_nbr", "min_co", "pair_budget"}
 _RECALL_FIELDS = {"history", "n_cand", "exclude"}
 _POPULAR_FIELDS = {"half_life", "ts_ref", "ts_lo", "ts_hi", "n_list"}
 _NBR_FIELDS = {"n_nbr", "min_w", "pass_items"}
+_MMR_FIELDS = {"k", "pool", "lambda_q", "max_per_group"}
 
 
 def make_cfg(**kw) -> capi.ItemcfCfg:
@@ -52,6 +57,14 @@ def make_nbr_cfg(**kw) -> capi.ItemnbrCfg:
     if unknown:
         raise TypeError(f"goctr_itemnbr_cfg has no field {sorted(unknown)}")
     return capi.default_itemnbr_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
+
+
+def make_mmr_cfg(**kw) -> capi.MmrCfg:
+    """goctr_mmr_cfg from keywords (integers; the ranges are the library's to refuse)"""
+    unknown = set(kw) - _MMR_FIELDS
+    if unknown:
+        raise TypeError(f"goctr_mmr_cfg has no field {sorted(unknown)}")
+    return capi.default_mmr_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
 
 
 def make_popular_cfg(**kw) -> capi.PopularCfg:
@@ -256,4 +269,98 @@ def blend(icf, pop, ubc, users, ts=None, targets=None, extra=None, quota_pop=0, 
         capi.ptr(out["src"], C.c_uint8), capi.ptr(out["count"], C.c_int32), capi.ptr(targets, C.c_int32), capi.ptr(tpos, C.c_int32)))
     if tpos is not None:
         out["target_pos"] = tpos
+    return out
+
+
+def _groups_column(groups, n_items):
+    if groups is None:
+        return None
+    groups = capi.i32(groups).ravel()
+    if groups.size != n_items:
+        raise ValueError("groups takes one id per item")
+    return groups
+
+
+class ItemVectors:
+    """goctr_itemvec: the items' quantised vectors (and optional group ids) resident in HBM, immutable after the build"""
+
+    def __init__(self, handle: C.c_void_p):
+        self._h = handle
+        i = self.info()
+        self.n_items, self.D, self.has_groups = i["n_items"], i["D"], i["has_groups"]
+
+    @classmethod
+    def from_vectors(cls, rows, groups=None) -> "ItemVectors":
+        """goctr_itemvec_build_vectors: ``rows`` [n_items, D], taken as float64; ``groups`` int32 [n_items] or None (a category id
+        per item, negative = no group)"""
+        rows = np.ascontiguousarray(rows, np.float64)
+        if rows.ndim != 2:
+            raise ValueError("rows takes one vector per item: [n_items, D]")
+        groups = _groups_column(groups, rows.shape[0])
+        h = C.c_void_p()
+        capi.init()
+        capi.check(capi.load().goctr_itemvec_build_vectors(capi.ptr(rows, C.c_double), C.c_int64(rows.shape[0]), C.c_int32(rows.shape[1]),
+                                                           capi.ptr(groups, C.c_int32), C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_embedding(cls, table, n_items: int, groups=None) -> "ItemVectors":
+        """goctr_itemvec_build_emb: the same over rows 0 .. n_items - 1 of an embedding table resident in HBM (a model.EmbeddingTable
+        or a raw goctr_emb handle), read as a serving pass reads them"""
+        n_items = _as_int("n_items", n_items)
+        groups = _groups_column(groups, n_items)
+        h = C.c_void_p()
+        e = table._h if hasattr(table, "_h") else table
+        capi.check(capi.load().goctr_itemvec_build_emb(e, C.c_int64(n_items), capi.ptr(groups, C.c_int32), C.byref(h)))
+        return cls(h)
+
+    def info(self) -> dict:
+        n, d, nv, g = C.c_int64(0), C.c_int32(0), C.c_int64(0), C.c_int32(0)
+        capi.check(capi.load().goctr_itemvec_info(self._h, C.byref(n), C.byref(d), C.byref(nv), C.byref(g)))
+        return dict(n_items=n.value, D=d.value, n_valid=nv.value, has_groups=bool(g.value))
+
+    def export(self) -> dict:
+        """dict(q int16 [n_items, D], valid uint8 [n_items], groups int32 [n_items] when the handle has groups)"""
+        out = dict(q=np.empty((self.n_items, self.D), np.int16), valid=np.empty(self.n_items, np.uint8))
+        if self.has_groups:
+            out["groups"] = np.empty(self.n_items, np.int32)
+        capi.check(capi.load().goctr_itemvec_export(self._h, capi.ptr(out["q"], C.c_int16), capi.ptr(out["valid"], C.c_uint8),
+                                                    capi.ptr(out.get("groups"), C.c_int32)))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            capi.load().goctr_itemvec_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def rerank_mmr(vectors: ItemVectors, items, scores, count=None, cfg: capi.MmrCfg | None = None, **kw) -> dict:
+    """goctr_rerank_mmr over host arrays: ``items`` int32 [nq, n_cand], ``scores`` float32 [nq, n_cand], ``count`` int32 [nq] (None:
+    every row is full); ``kw``: goctr_mmr_cfg fields.  dict(pos int32 [nq, k] (the selected candidates' places, -1 = unused), obj
+    int32 [nq, k], pen uint32 [nq, k], count int32 [nq], n_failed)"""
+    if cfg is not None and kw:
+        raise TypeError("give either cfg or keywords")
+    cfg = cfg if cfg is not None else make_mmr_cfg(**kw)
+    items, scores = capi.i32(items), capi.f32(scores)
+    if items.ndim != 2 or items.shape != scores.shape or items.size == 0:
+        raise ValueError("items and scores take one row of candidates per request row: [nq, n_cand]")
+    nq, nc = items.shape
+    count = np.full(nq, nc, np.int32) if count is None else capi.i32(count).ravel()
+    if count.size != nq:
+        raise ValueError("count takes one entry per request row")
+    kk = max(int(cfg.k), 1)
+    out = dict(pos=np.full((nq, kk), -2, np.int32), obj=np.full((nq, kk), -2, np.int32), pen=np.full((nq, kk), 0xffffffff, np.uint32),
+               count=np.full(nq, -2, np.int32))
+    nf = C.c_int64(-2)
+    capi.check(capi.load().goctr_rerank_mmr(vectors._h, capi.ptr(items, C.c_int32), capi.ptr(scores, C.c_float), capi.ptr(count, C.c_int32),
+                                            C.c_int64(nq), C.c_int32(nc), C.byref(cfg), capi.ptr(out["pos"], C.c_int32),
+                                            capi.ptr(out["obj"], C.c_int32), capi.ptr(out["pen"], C.c_uint32),
+                                            capi.ptr(out["count"], C.c_int32), C.byref(nf)))
+    out["n_failed"] = nf.value
     return out

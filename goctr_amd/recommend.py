@@ -682,6 +682,23 @@ def blend(model: Predictor, icf, pop, users, ts=None, targets=None, extra=None, 
     1 extra, 2 popularity, 255 = unused), count [nq], cand_count [nq], n_failed, target_pos / target_rank [nq] when targets are
     given, cand_items / cand_w / cand_scores / cand_src [nq, n_cand] when ``validate``).  ``recall_kw``: goctr_recall_cfg fields.
     What RecommendBlend / RecommendBlendBatch / EvaluateLeaveOneOutBlend call."""
+    return _blend_call(model, icf, pop, users, ts, targets, extra, quota_pop, k, pass_rows, validate, recall_cfg, recall_kw, None)
+
+
+def diverse(model: Predictor, icf, pop, vectors, users, ts=None, targets=None, extra=None, quota_pop=0, k=10, pool=64, lambda_q=192,
+            max_per_group=0, pass_rows=0, validate=False, recall_cfg=None, **recall_kw):
+    """goctr_recommend_blend_mmr over DENSE indices: ``blend`` with the MMR selection over ``vectors`` (recall.ItemVectors) as its
+    last step.  blend's dict plus obj int32 [nq, k], pen uint32 [nq, k] and, when targets are given, target_place int32 [nq] (the
+    target's index in the returned list, or -1; target_rank stays the model's rank among the eligible candidates).  What
+    RecommendDiverse / RecommendDiverseBatch / EvaluateLeaveOneOutDiverse call."""
+    from .recall import make_mmr_cfg
+    mmr = (vectors, make_mmr_cfg(k=k, pool=pool, lambda_q=lambda_q, max_per_group=max_per_group))
+    return _blend_call(model, icf, pop, users, ts, targets, extra, quota_pop, k, pass_rows, validate, recall_cfg, recall_kw, mmr)
+
+
+def _blend_call(model, icf, pop, users, ts, targets, extra, quota_pop, k, pass_rows, validate, recall_cfg, recall_kw, mmr):
+    """goctr_recommend_blend, or with ``mmr`` = (recall.ItemVectors, capi.MmrCfg) goctr_recommend_blend_mmr: the two differ in the
+    selection arguments and the latter's three further outputs"""
     from .recall import _as_int, extra_columns, make_recall_cfg, request_columns
     if recall_cfg is not None and recall_kw:
         raise TypeError("give either recall_cfg or keywords")
@@ -699,14 +716,24 @@ def blend(model: Predictor, icf, pop, users, ts=None, targets=None, extra=None, 
     cand_scores = np.full((nq, nc), np.nan, np.float32) if validate else None
     cand_src = np.full((nq, nc), 254, np.uint8) if validate else None
     nf = C.c_int64(-2)
-    capi.check(capi.load().goctr_recommend_blend(
-        model.net._h, rs._h, icf._h if icf is not None else None, pop._h if pop is not None else None, capi.ptr(users, C.c_int32),
-        capi.ptr(ts, C.c_int64), C.c_int64(nq), capi.ptr(targets, C.c_int32), capi.ptr(extra, C.c_int32), C.c_int32(n_extra),
-        C.byref(cfg), C.c_int32(_as_int("quota_pop", quota_pop)), C.c_int32(int(k)), C.c_int64(int(pass_rows)),
-        capi.ptr(out["items"], C.c_int32), capi.ptr(out["scores"], C.c_float), capi.ptr(out["count"], C.c_int32),
-        capi.ptr(out["src"], C.c_uint8), capi.ptr(out["cand_count"], C.c_int32), capi.ptr(tpos, C.c_int32), capi.ptr(rank, C.c_int64),
-        capi.ptr(cand_items, C.c_int32), capi.ptr(cand_w, C.c_uint32), capi.ptr(cand_scores, C.c_float), capi.ptr(cand_src, C.c_uint8),
-        C.byref(nf)))
+    head = (model.net._h, rs._h, icf._h if icf is not None else None, pop._h if pop is not None else None, capi.ptr(users, C.c_int32),
+            capi.ptr(ts, C.c_int64), C.c_int64(nq), capi.ptr(targets, C.c_int32), capi.ptr(extra, C.c_int32), C.c_int32(n_extra),
+            C.byref(cfg), C.c_int32(_as_int("quota_pop", quota_pop)))
+    outs = (capi.ptr(out["items"], C.c_int32), capi.ptr(out["scores"], C.c_float), capi.ptr(out["count"], C.c_int32),
+            capi.ptr(out["src"], C.c_uint8), capi.ptr(out["cand_count"], C.c_int32), capi.ptr(tpos, C.c_int32), capi.ptr(rank, C.c_int64),
+            capi.ptr(cand_items, C.c_int32), capi.ptr(cand_w, C.c_uint32), capi.ptr(cand_scores, C.c_float), capi.ptr(cand_src, C.c_uint8),
+            C.byref(nf))
+    if mmr is None:
+        capi.check(capi.load().goctr_recommend_blend(*head, C.c_int32(int(k)), C.c_int64(int(pass_rows)), *outs))
+    else:
+        vectors, mcfg = mmr
+        out["obj"], out["pen"] = np.full((nq, kk), -2, np.int32), np.full((nq, kk), 0xffffffff, np.uint32)
+        tplace = np.full(nq, -2, np.int32) if targets is not None else None
+        capi.check(capi.load().goctr_recommend_blend_mmr(*head, vectors._h, C.byref(mcfg), C.c_int64(int(pass_rows)), *outs,
+                                                         capi.ptr(out["obj"], C.c_int32), capi.ptr(out["pen"], C.c_uint32),
+                                                         capi.ptr(tplace, C.c_int32)))
+        if targets is not None:
+            out["target_place"] = tplace
     out["n_failed"] = nf.value
     if targets is not None:
         out["target_pos"], out["target_rank"] = tpos, rank
@@ -791,4 +818,99 @@ def EvaluateLeaveOneOutBlend(model: Predictor, icf, pop=None, k=10, sample_kw=No
                ndcg=float(np.mean(np.where(hit, 1.0 / np.log2(np.where(hit, rank, 0.0) + 2.0), 0.0))) if n else nan)
     if details:
         out.update(target_pos=r["target_pos"], rank=r["target_rank"], src=r["src"], user_index=users, target_index=targets, ts=ts)
+    return out
+
+
+def BuildItemVectors(recSys: DeviceRecSys, groups=None):
+    """EXTENSION: the recSys's item VECTORS, quantised and resident (recall.ItemVectors.from_embedding): the rows of its embedding
+    table in HBM over the rows of its item feature table -- what RecommendDiverse measures similarity with.  ``groups``: one
+    category id per item-table row (negative = none) for ``max_per_group``, or None.  The vectors are those of the table's rows at
+    THIS call."""
+    from .recall import ItemVectors
+    return ItemVectors.from_embedding(recSys.emb, recSys.item_table.shape[0], groups)
+
+
+def RecommendDiverseBatch(model: Predictor, icf, pop, vectors, userIds, n=10, now=None, extra=None, quota_pop=0, lambda_q=192, pool=64,
+                          max_per_group=0, **recall_kw):
+    """RecommendDiverse for several users in one device call: [[ItemScore]] in the order of userIds, in the order of selection (not
+    by score).  Arguments as RecommendBlendBatch's plus the re-rank's."""
+    rs = model.recSys
+    userIds = list(userIds)
+    users = np.array([rs.user_index(u) for u in userIds], np.int32)
+    if users.size == 0:
+        return []
+    if (users < 0).any():
+        bad = userIds[int(np.flatnonzero(users < 0)[0])]
+        raise SampleVectorError(f"get sample vector error: user {bad} has no features")
+    ts = np.broadcast_to(np.asarray(int(time.time()) if now is None else now, np.int64), users.shape)
+    # an id unknown to the item feature table becomes an entry out of range (index -1), which the blend skips
+    dense_extra = None if extra is None else np.array([[rs.item_index(i) for i in row] for row in extra], np.int32).reshape(users.size, -1)
+    try:
+        r = diverse(model, icf, pop, vectors, users, ts, None, dense_extra, quota_pop, n, pool, lambda_q, max_per_group, **recall_kw)
+    except capi.GoctrError as e:
+        raise SampleVectorError(str(e)) from None
+    raw = rs._row_keys
+    return [[ItemScore(int(raw[r["items"][q, j]]), float(r["scores"][q, j])) for j in range(int(r["count"][q]))]
+            for q in range(users.size)]
+
+
+def RecommendDiverse(model: Predictor, icf, pop, vectors, userId: int, n=10, now=None, extra=None, quota_pop=0, lambda_q=192, pool=64,
+                     max_per_group=0, **recall_kw):
+    """EXTENSION -- RecommendBlend with a diversity re-rank between "rank" and "answer": of the ``pool`` best-scored candidates the
+    ``n`` returned are picked greedily by lambda_q * relevance - (256 - lambda_q) * (largest similarity to an item already picked),
+    in units of 1/256, similarity being the quantised cosine of the items' vectors (``vectors``: BuildItemVectors); at most
+    ``max_per_group`` items of one group come back (0 = no cap).  ``lambda_q`` = 256 without a cap is RecommendBlend."""
+    return RecommendDiverseBatch(model, icf, pop, vectors, [userId], n, now, None if extra is None else [extra], quota_pop, lambda_q,
+                                 pool, max_per_group, **recall_kw)[0]
+
+
+def EvaluateLeaveOneOutDiverse(model: Predictor, icf, vectors, pop=None, k=10, lambda_q=192, pool=64, max_per_group=0, sample_kw=None,
+                               details=False, pass_rows=0, quota_pop=0, pop_kw=None, **recall_kw):
+    """EvaluateLeaveOneOutBlend's protocol with the re-rank as the last step (goctr_recommend_blend_mmr): the same held-out entries,
+    candidates and popularity list.  In float64 on the host, over the users whose held-out item is a row of the item table,
+        recall = mean(target_pos >= 0)
+        hit_rate = mean(target_place >= 0)    ndcg = mean(1 / log2(target_place + 2) if target_place >= 0 else 0)
+    where target_place is the target's index in the RETURNED list, and
+        list_similarity = mean(pen / 65536) over the returned places >= 1
+    the mean over all returned items but every list's first of the largest similarity to an item in front of it (nan when no list
+    has two items).  Compare with EvaluateLeaveOneOutBlend's figures for what the diversity costs in accuracy.  Returns dict(users,
+    skipped, k, n_cand, recall, hit_rate, ndcg, list_similarity); details=True adds the columns."""
+    from .recall import make_recall_cfg
+    from .sampling import Samples
+    rs = model.recSys
+    if rs.ubcache is None:
+        raise RuntimeError("this recSys has no behaviour cache to hold items out of (it does not implement UserBehavior, rcmd.go:512)")
+    kw = dict(n_neg=0, which="newest")
+    kw.update(sample_kw or {})
+    smp = Samples(rs._dense_cache, rs.item_table.shape[0], **kw)
+    if smp.rows == 0:
+        raise SampleVectorError("the behaviour cache holds no entry that qualifies as a positive")
+    users, targets, ts, _y = smp.export()
+    own = pop is None
+    if own:
+        pkw = dict(pop_kw or {})
+        pkw.setdefault("ts_hi", int(ts.min()))            # as EvaluateLeaveOneOutBlend: nothing at or after a held-out event counts
+        pop = BuildPopular(rs, **pkw)
+    recall_kw.setdefault("exclude", "before")
+    cfg = make_recall_cfg(**recall_kw)
+    try:
+        r = diverse(model, icf, pop, vectors, users, ts, targets, None, quota_pop, k, pool, lambda_q, max_per_group, pass_rows,
+                    recall_cfg=cfg)
+    finally:
+        if own:
+            pop.close()
+    ok = (targets >= 0) & (targets < rs.item_table.shape[0])
+    pos, place = r["target_pos"][ok].astype(np.int64), r["target_place"][ok].astype(np.float64)
+    n = int(ok.sum())
+    hit = place >= 0
+    later = (np.arange(r["pen"].shape[1])[None, :] >= 1) & (np.arange(r["pen"].shape[1])[None, :] < r["count"][:, None])
+    nan = float("nan")
+    out = dict(users=n, skipped=int((~ok).sum()), k=int(k), n_cand=int(cfg.n_cand),
+               recall=float(np.mean(pos >= 0)) if n else nan,
+               hit_rate=float(np.mean(hit)) if n else nan,
+               ndcg=float(np.mean(np.where(hit, 1.0 / np.log2(np.where(hit, place, 0.0) + 2.0), 0.0))) if n else nan,
+               list_similarity=float(np.mean(r["pen"][later].astype(np.float64) / 65536.0)) if later.any() else nan)
+    if details:
+        out.update(target_pos=r["target_pos"], rank=r["target_rank"], target_place=r["target_place"], items=r["items"], pen=r["pen"],
+                   count=r["count"], src=r["src"], user_index=users, target_index=targets, ts=ts)
     return out

@@ -614,6 +614,88 @@ int  goctr_itemcf_build_emb(goctr_emb* e, int64_t n_items /* rows 0 .. n_items-1
  *                  mul_a + mul_b outside 1 .. 256 (which keeps w <= 2^23); n_nbr outside 1 .. 256 */
 int  goctr_itemcf_merge(goctr_itemcf* a, goctr_itemcf* b, int32_t mul_a, int32_t mul_b, int32_t n_nbr, goctr_itemcf** out);
 
+/* ---- Diversity re-rank: maximal marginal relevance over item vectors, with group caps (no reference counterpart).  The recall
+ * channels above return items close to the user's history, so the best k by score are typically one cluster.  A goctr_itemvec holds
+ * the catalogue's quantised vectors (and optionally a group id per item) in HBM; goctr_rerank_mmr picks k of a row's scored
+ * candidates greedily, trading relevance against similarity to what it has picked, one workgroup per request row and all k steps in
+ * ONE launch; goctr_recommend_blend_mmr is goctr_recommend_blend with that selection as its last step.  Every output is defined
+ * bit for bit (tests/mmr_ref.py is the host restatement): all arithmetic that decides an output is integer.
+ *
+ * goctr_itemvec_build_vectors / goctr_itemvec_build_emb: rows are quantised by the rule of goctr_itemcf_build_vectors above (s,
+ * valid, q_d -- the same kernel); the handle keeps q as two int8 planes (q = 256 hi + lo, lo in [-128, 127]), valid[n_items] and,
+ * when `groups` is given, groups[n_items] (a category id; negative = no group).  goctr_itemvec_build_emb reads the table as
+ * goctr_itemcf_build_emb does: under the table's shared lock and behind its pending writes.
+ *   refused        (-1, *out untouched) n_items <= 0 or > 2^31 - 1, D outside 1 .. 1024; for _emb, n_items > the table's V, or a
+ *                  table on another engine than the calling thread's
+ * The handle is immutable and independent of what it was built from.  export: q [n_items,D] int16, valid 1 / 0, groups (refused when
+ * the handle has none).
+ *
+ * The selection rule, for one request row with candidates at places c = 0 .. count-1, item i_c, float32 score s_c:
+ *   eligible       not failed (the serving path's flag), and 0 <= i_c < the handle's n_items.  In goctr_rerank_mmr a candidate
+ *                  outside that range is not eligible and adds one to *n_failed
+ *   head           the first min(pool, eligible) eligible candidates in goctr_recommend_topn's order (score descending, place
+ *                  ascending, -0 ties with +0, NaN last); head index h = a candidate's place in that order.  Only head candidates
+ *                  can be returned
+ *   rel_c          clamp(rint((double)s_c * 65536.0), 0, 65536) as an integer: the product is exact, rint ties to even; NaN 0,
+ *                  +Inf 65536, -Inf 0.  rel is monotone in the order rule, so lambda_q = 256 reproduces the plain selection
+ *   sim(c,j)       w(i_c, i_j) of the section above: dot(q[i_c], q[i_j]) >> 12 when the dot is positive, else 0.  An invalid row
+ *                  has q = 0 and sim 0.  Two candidates that hold the same item are two candidates; their sim is about 65536
+ *   step           t = 0, 1, ...; S = the head indices selected so far.  Among the head candidates neither in S nor capped:
+ *                  pen_c = the largest sim(c, j) over j in S (0 for empty S); obj_c = lambda_q * rel_c - (256 - lambda_q) * pen_c,
+ *                  an int32 with |obj| < 2^26; the largest obj wins, ties go to the smaller head index; the winner joins S
+ *   capped         (max_per_group > 0) a candidate whose item's group g >= 0 already has max_per_group members in S is skipped,
+ *                  and stays skipped.  A negative group is never capped
+ *   stop           after k selections, when no candidate is left, or when every remaining one is capped
+ *   outputs        out_count[q] = the selections; row q of out_pos holds the selected candidates' places in selection order, of
+ *                  out_obj / out_pen (each may be NULL) obj and pen at the moment of selection; padding -1 / 0 / 0
+ *   refused        (-1, nothing touched) a cfg outside its ranges; max_per_group > 0 with a handle without groups; for
+ *                  goctr_rerank_mmr null required pointers, n_req <= 0 or > 2^24, n_cand outside 1 .. 1024, a count[q] outside
+ *                  0 .. n_cand
+ * A thread keeps its own row in registers for D <= 32 and reads it from the planes every step above that; no output depends on it. */
+typedef struct {
+  int32_t k;              /* 1 .. 256                          default 10  */
+  int32_t pool;           /* 1 .. 1024: the head's length      default 64  */
+  int32_t lambda_q;       /* 0 .. 256: relevance's share / 256 default 192 */
+  int32_t max_per_group;  /* 0 .. 256, 0 = no cap              default 0   */
+} goctr_mmr_cfg;
+void goctr_mmr_cfg_default(goctr_mmr_cfg* c);
+typedef struct goctr_itemvec goctr_itemvec;
+int  goctr_itemvec_build_vectors(const double* rows /* host [n_items, D] */, int64_t n_items, int32_t D,
+                                 const int32_t* groups /* host [n_items] or NULL */, goctr_itemvec** out);
+int  goctr_itemvec_build_emb(goctr_emb* e, int64_t n_items /* rows 0 .. n_items-1, <= e->V */,
+                             const int32_t* groups /* host [n_items] or NULL */, goctr_itemvec** out);
+void goctr_itemvec_destroy(goctr_itemvec* h);
+/* each may be NULL; n_valid: the valid rows */
+int  goctr_itemvec_info(goctr_itemvec* h, int64_t* n_items, int32_t* D, int64_t* n_valid, int32_t* has_groups);
+/* each may be NULL */
+int  goctr_itemvec_export(goctr_itemvec* h, int16_t* q /*[n_items,D]*/, uint8_t* valid /*[n_items]*/, int32_t* groups /*[n_items]*/);
+/* the standalone stage: host arrays, the engine stream and the engine lock, like goctr_blend_recall */
+int  goctr_rerank_mmr(goctr_itemvec* v, const int32_t* items /*[n_req,n_cand]*/, const float* scores /*[n_req,n_cand]*/,
+                      const int32_t* count /*[n_req], each 0 .. n_cand*/, int64_t n_req, int32_t n_cand /* 1 .. 1024 */,
+                      const goctr_mmr_cfg* cfg, int32_t* out_pos /*[n_req,k]*/, int32_t* out_obj /*[n_req,k] or NULL*/,
+                      uint32_t* out_pen /*[n_req,k] or NULL*/, int32_t* out_count /*[n_req]*/, int64_t* n_failed /* or NULL */);
+
+/* goctr_recommend_blend_mmr: goctr_recommend_blend with the rule above in place of "the best k by score" (k = cfg->k); the place
+ * in the blended list is the candidate's place, the call's scores are s_c.  Recall, blend, scores, failed candidates, n_failed,
+ * out_cand_count, out_target_pos, out_src, the validation outputs and the concurrency rules are as documented there, and
+ * out_target_rank keeps its meaning: the model's rank among the eligible candidates, not the place in the diversified list.
+ *   out_obj, out_pen   [n_req,k], may be NULL: as goctr_rerank_mmr's
+ *   out_target_place   [n_req], may be NULL: the target's index in the returned list, or -1
+ *   refused            goctr_recommend_blend's refusals, the cfg refusals above, and item vectors whose n_items differs from the
+ *                      recsys's
+ * With icf alone and quota_pop = 0 this is the ItemCF call with the same last step.  goctr_recommend_topn has no such variant: its
+ * passes carry running lists of k, not of pool. */
+int goctr_recommend_blend_mmr(goctr_model* m, goctr_recsys* r, goctr_itemcf* icf /* may be NULL */, goctr_popular* pop /* may be NULL */,
+                              const int32_t* users, const int64_t* ts /* NULL = 0 */, int64_t n_req,
+                              const int32_t* targets /* [n_req] or NULL */,
+                              const int32_t* extra /* [n_req,n_extra] or NULL */, int32_t n_extra /* 0 .. 1024 */,
+                              const goctr_recall_cfg* recall_cfg, int32_t quota_pop /* 0 .. recall_cfg->n_cand */,
+                              goctr_itemvec* v, const goctr_mmr_cfg* cfg, int64_t pass_rows,
+                              int32_t* out_items /* [n_req,k] */, float* out_scores /* [n_req,k] */, int32_t* out_count,
+                              uint8_t* out_src, int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank,
+                              int32_t* cand_items, uint32_t* cand_w, float* cand_scores, uint8_t* cand_src, int64_t* n_failed,
+                              int32_t* out_obj, uint32_t* out_pen, int32_t* out_target_place);
+
 /* The replica a multi-device training call (cfg.devices = n) keeps on engine `rank` (rank 0: the handle itself); NULL before
  * the first such call.  Borrowed: owned by the handle it was asked from.  For checks that the replicas are bit-identical
  * (tests, bench.py's replica checksum) -- every entry point works on it, on its own engine. */
