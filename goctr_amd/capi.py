@@ -175,6 +175,27 @@ class MmrCfg(C.Structure):
     _fields_ = [("k", C.c_int32), ("pool", C.c_int32), ("lambda_q", C.c_int32), ("max_per_group", C.c_int32)]
 
 
+class ListCfg(C.Structure):
+    """goctr_list_cfg (include/goctr.h)"""
+    _fields_ = [("k", C.c_int32), ("tail_cnt", C.c_int32)]
+
+
+class ListRow(C.Structure):
+    """goctr_list_row (include/goctr.h)"""
+    _fields_ = [("listed", C.c_uint32), ("usable", C.c_uint32), ("pairs", C.c_uint32), ("sim_max", C.c_uint32),
+                ("sim_sum", C.c_uint64), ("nov_sum", C.c_uint64), ("tail", C.c_uint32), ("groups", C.c_uint32),
+                ("group_max", C.c_uint32), ("ungrouped", C.c_uint32)]
+
+
+class ListMetrics(C.Structure):
+    """goctr_list_metrics (include/goctr.h)"""
+    _fields_ = [("n_req", C.c_int64), ("n_items", C.c_int64), ("entries", C.c_uint64), ("listed", C.c_uint64),
+                ("usable", C.c_uint64), ("pairs", C.c_uint64), ("sim_sum", C.c_uint64), ("nov_sum", C.c_uint64),
+                ("tail", C.c_uint64), ("sim_max", C.c_uint32), ("covered", C.c_int64), ("gini_num", C.c_int64),
+                ("ild", C.c_double), ("coverage", C.c_double), ("gini", C.c_double), ("novelty", C.c_double),
+                ("tail_share", C.c_double)]
+
+
 TOPN_KEEP_SEEN, TOPN_DROP_ALL_SEEN, TOPN_DROP_SEEN_BEFORE = 0, 1, 2   # goctr_topn_cfg.exclude
 NS_UNIFORM, NS_POPULARITY, NS_POPULARITY_075 = 0, 1, 2      # goctr_negsample_cfg.weighting
 NS_ALL, NS_NEWEST, NS_ALL_BUT_NEWEST = 0, 1, 2              # goctr_negsample_cfg.which
@@ -222,6 +243,7 @@ SYMBOLS = [
     "goctr_itemnbr_cfg_default", "goctr_itemcf_build_vectors", "goctr_itemcf_build_emb", "goctr_itemcf_merge",
     "goctr_mmr_cfg_default", "goctr_itemvec_build_vectors", "goctr_itemvec_build_emb", "goctr_itemvec_destroy", "goctr_itemvec_info",
     "goctr_itemvec_export", "goctr_rerank_mmr", "goctr_recommend_blend_mmr",
+    "goctr_list_cfg_default", "goctr_metrics_lists",
 ]
 
 _lib = None
@@ -245,7 +267,7 @@ def load() -> C.CDLL:
                      "goctr_w2v_cfg_default", "goctr_negsample_cfg_default", "goctr_samples_destroy", "goctr_topn_cfg_default",
                      "goctr_itemcf_cfg_default", "goctr_recall_cfg_default", "goctr_itemcf_destroy", "goctr_curve_cfg_default",
                      "goctr_multiclass_cfg_default", "goctr_popular_cfg_default", "goctr_popular_destroy",
-                     "goctr_itemnbr_cfg_default", "goctr_mmr_cfg_default", "goctr_itemvec_destroy"):
+                     "goctr_itemnbr_cfg_default", "goctr_mmr_cfg_default", "goctr_itemvec_destroy", "goctr_list_cfg_default"):
             getattr(_lib, name).restype = None
         _bm = C.POINTER(BinaryMetrics)
         _lib.goctr_metrics_binary.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, _bm]
@@ -338,6 +360,9 @@ def load() -> C.CDLL:
         _lib.goctr_recommend_blend_mmr.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32, _i32,
                                                    C.c_int32, C.POINTER(RecallCfg), C.c_int32, C.c_void_p, _mmr, C.c_int64, _i32, _f32,
                                                    _i32, _u8, _i32, _i32, _i64, _i32, _u32, _f32, _u8, _i64, _i32, _u32, _i32]
+        _lib.goctr_list_cfg_default.argtypes = [C.POINTER(ListCfg)]
+        _lib.goctr_metrics_lists.argtypes = [C.c_void_p, C.c_void_p, _i32, _i32, C.c_int64, C.c_int64, C.POINTER(ListCfg),
+                                             C.POINTER(ListMetrics), C.POINTER(ListRow), _u32, _u32]
     return _lib
 
 
@@ -495,6 +520,14 @@ def default_itemnbr_cfg(**kw) -> ItemnbrCfg:
 def default_mmr_cfg(**kw) -> MmrCfg:
     c = MmrCfg()
     load().goctr_mmr_cfg_default(C.byref(c))
+    for k, v in kw.items():
+        setattr(c, k, v)
+    return c
+
+
+def default_list_cfg(**kw) -> ListCfg:
+    c = ListCfg()
+    load().goctr_list_cfg_default(C.byref(c))
     for k, v in kw.items():
         setattr(c, k, v)
     return c

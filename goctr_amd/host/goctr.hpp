@@ -726,6 +726,32 @@ inline TopN RecommendDiverseBatch(model::CtrNet& net, RecSys& rs, const ItemCF* 
       out.lists[(size_t)q].push_back(ItemScore{items[(size_t)q * n + j], scores[(size_t)q * n + j]});
   return out;
 }
+
+// List-quality figures of returned lists (goctr_metrics_lists): `items` holds nq rows of k entries, `count` the entries in use
+// per row (empty: every row is full); vec / pop may be null (include/goctr.h says which figures are then 0 or NaN)
+struct ListQuality {
+  goctr_list_metrics metrics{};
+  std::vector<goctr_list_row> rows;      // per request row
+  std::vector<uint32_t> expo;            // per item: the listed entries that hold it
+};
+inline ListQuality ListMetrics(const ItemVectors* vec, const Popular* pop, const std::vector<int32_t>& items, int k,
+                               int64_t n_items, const std::vector<int32_t>& count = {}, int tail_cnt = 0) {
+  if (k < 1 || items.empty() || items.size() % (size_t)k) throw std::invalid_argument("ListMetrics: rows of k entries");
+  const int64_t nq = (int64_t)(items.size() / (size_t)k);
+  if (!count.empty() && (int64_t)count.size() != nq) throw std::invalid_argument("ListMetrics: one count per row");
+  const std::vector<int32_t> full(count.empty() ? (size_t)nq : 0, k);
+  if (n_items < 1) throw std::invalid_argument("ListMetrics: n_items must be positive");
+  goctr_list_cfg cfg;
+  goctr_list_cfg_default(&cfg);
+  cfg.k = k; cfg.tail_cnt = tail_cnt;
+  ListQuality out;
+  out.rows.resize((size_t)nq);
+  out.expo.resize((size_t)n_items);
+  check(goctr_metrics_lists(vec ? vec->handle() : nullptr, pop ? pop->handle() : nullptr, items.data(),
+                            count.empty() ? full.data() : count.data(), nq, n_items, &cfg, &out.metrics, out.rows.data(),
+                            out.expo.data(), nullptr));
+  return out;
+}
 }  // namespace recommend
 
 namespace din {

@@ -13,6 +13,10 @@ The multi-output functions -- R2Score / MeanSquaredError / MeanAbsoluteError (re
 PrecisionRecallFScoreSupport / FBetaScore (classification.go) and the `average` argument of ROCAUCScore / AveragePrecisionScore
 (base.go:12-87) -- sit over goctr_metrics_regression / _confusion / _multiclass: the device returns the column sums and the integer
 confusion matrix, the post-processing is the pure *_from_* functions below.  sampleWeight is not supported anywhere (ValueError).
+
+List quality (no reference counterpart) sits over goctr_metrics_lists: ``list_metrics`` returns the batch struct's integers and
+correctly rounded quotients for the lists a recommend call returned -- intra-list diversity, catalogue coverage, the Gini index of the
+exposure, novelty, tail share -- and IntraListDiversity / CatalogCoverage / GiniIndex / Novelty are one figure each.
 """
 from __future__ import annotations
 
@@ -703,3 +707,69 @@ def ROCAUCScore(Ytrue, Yscore, average="macro", sampleWeight=None) -> float:
     weighted / micro average over the columns of an indicator matrix"""
     _no_weights(sampleWeight)
     return _average_binary_score("auc", Ytrue, Yscore, average)
+
+
+# ------------------------------------------------------------------------------------------------------ list quality
+# goctr_list_row as a numpy record (the C layout: 48 bytes, no padding)
+LIST_ROW_DTYPE = np.dtype([("listed", np.uint32), ("usable", np.uint32), ("pairs", np.uint32), ("sim_max", np.uint32),
+                           ("sim_sum", np.uint64), ("nov_sum", np.uint64), ("tail", np.uint32), ("groups", np.uint32),
+                           ("group_max", np.uint32), ("ungrouped", np.uint32)])
+LIST_FIELDS = tuple(name for name, _ in capi.ListMetrics._fields_)
+
+
+def list_metrics(items, count=None, vectors=None, pop=None, n_items=None, tail_cnt=0, rows=False, expo=False, sim=False) -> dict:
+    """goctr_metrics_lists over the lists a recommend call returned: ``items`` int32 [nq, k], ``count`` int32 [nq] (None: every
+    row is full), ``vectors`` a recall.ItemVectors or None, ``pop`` a recall.Popular or None, ``n_items`` the catalogue (None: the
+    handles').  A dict of goctr_list_metrics' fields -- the integers as Python ints, ild / coverage / gini / novelty / tail_share as
+    floats (NaN where include/goctr.h says so) -- plus, on request, ``rows`` (records of LIST_ROW_DTYPE [nq]), ``expo`` (uint32
+    [n_items]) and ``sim`` (uint32 [nq, k, k], needs ``vectors``)."""
+    from .recall import make_list_cfg
+    items = capi.i32(items)
+    if items.ndim != 2 or items.size == 0:
+        raise ValueError("items takes one row of entries per request row: [nq, k]")
+    nq, k = items.shape
+    count = np.full(nq, k, np.int32) if count is None else capi.i32(count).ravel()
+    if count.size != nq:
+        raise ValueError("count takes one entry per request row")
+    if n_items is None:
+        if vectors is None and pop is None:
+            raise ValueError("n_items is needed without a handle")
+        n_items = vectors.n_items if vectors is not None else pop.n_items
+    cfg = make_list_cfg(k=k, tail_cnt=tail_cnt)
+    out = capi.ListMetrics()
+    h_rows = np.zeros(nq, LIST_ROW_DTYPE) if rows else None
+    h_expo = np.zeros(int(n_items), np.uint32) if expo and n_items > 0 else None
+    h_sim = np.zeros((nq, k, k), np.uint32) if sim else None
+    capi.check(capi.load().goctr_metrics_lists(
+        vectors._h if vectors is not None else None, pop._h if pop is not None else None, capi.ptr(items, C.c_int32),
+        capi.ptr(count, C.c_int32), C.c_int64(nq), C.c_int64(int(n_items)), C.byref(cfg), C.byref(out),
+        None if h_rows is None else h_rows.ctypes.data_as(C.POINTER(capi.ListRow)), capi.ptr(h_expo, C.c_uint32),
+        capi.ptr(h_sim, C.c_uint32)))
+    r = {name: getattr(out, name) for name in LIST_FIELDS}
+    if rows:
+        r["rows"] = h_rows
+    if expo:
+        r["expo"] = h_expo
+    if sim:
+        r["sim"] = h_sim
+    return r
+
+
+def IntraListDiversity(items, vectors, count=None) -> float:
+    """1 - the mean pair similarity (quantised cosine, negative cosines as 0) of the lists' usable pairs; NaN without a pair"""
+    return list_metrics(items, count, vectors=vectors)["ild"]
+
+
+def CatalogCoverage(items, n_items, count=None) -> float:
+    """the share of the catalogue's ``n_items`` items that some list holds"""
+    return list_metrics(items, count, n_items=n_items)["coverage"]
+
+
+def GiniIndex(items, n_items, count=None) -> float:
+    """the Gini index of the items' exposure (0: every item listed equally often; towards 1: a few items take all places)"""
+    return list_metrics(items, count, n_items=n_items)["gini"]
+
+
+def Novelty(items, pop, count=None) -> float:
+    """the mean of log2((counted + n_items) / (cnt[item] + 1)) over the listed entries, in the device's fixed-point log"""
+    return list_metrics(items, count, pop=pop)["novelty"]

@@ -29,6 +29,7 @@ _RECALL_FIELDS = {"history", "n_cand", "exclude"}
 _POPULAR_FIELDS = {"half_life", "ts_ref", "ts_lo", "ts_hi", "n_list"}
 _NBR_FIELDS = {"n_nbr", "min_w", "pass_items"}
 _MMR_FIELDS = {"k", "pool", "lambda_q", "max_per_group"}
+_LIST_FIELDS = {"k", "tail_cnt"}
 
 
 def make_cfg(**kw) -> capi.ItemcfCfg:
@@ -65,6 +66,14 @@ def make_mmr_cfg(**kw) -> capi.MmrCfg:
     if unknown:
         raise TypeError(f"goctr_mmr_cfg has no field {sorted(unknown)}")
     return capi.default_mmr_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
+
+
+def make_list_cfg(**kw) -> capi.ListCfg:
+    """goctr_list_cfg from keywords (integers; the ranges are the library's to refuse)"""
+    unknown = set(kw) - _LIST_FIELDS
+    if unknown:
+        raise TypeError(f"goctr_list_cfg has no field {sorted(unknown)}")
+    return capi.default_list_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
 
 
 def make_popular_cfg(**kw) -> capi.PopularCfg:

@@ -914,3 +914,112 @@ def EvaluateLeaveOneOutDiverse(model: Predictor, icf, vectors, pop=None, k=10, l
         out.update(target_pos=r["target_pos"], rank=r["target_rank"], target_place=r["target_place"], items=r["items"], pen=r["pen"],
                    count=r["count"], src=r["src"], user_index=users, target_index=targets, ts=ts)
     return out
+
+
+def _held_out_rows(model, sample_kw):
+    """the leave-one-out protocol's request rows: every user's newest entry held out -> (users, targets, ts), dense indices"""
+    from .sampling import Samples
+    rs = model.recSys
+    if rs.ubcache is None:
+        raise RuntimeError("this recSys has no behaviour cache to hold items out of (it does not implement UserBehavior, rcmd.go:512)")
+    kw = dict(n_neg=0, which="newest")
+    kw.update(sample_kw or {})
+    smp = Samples(rs._dense_cache, rs.item_table.shape[0], **kw)
+    if smp.rows == 0:
+        raise SampleVectorError("the behaviour cache holds no entry that qualifies as a positive")
+    users, targets, ts, _y = smp.export()
+    return users, targets, ts
+
+
+def _list_quality(model, icf, vectors, pop, users, ts, targets, cfg, k, lambda_q, pool, max_per_group, pass_rows, quota_pop, tail_cnt,
+                  details):
+    """one evaluation over prepared request rows: EvaluateLeaveOneOutBlend's figures (lambda_q = 256 without a cap, through
+    ``blend``) or EvaluateLeaveOneOutDiverse's (anything else, through ``diverse``), each by that function's own expressions, plus
+    metrics.list_metrics over the returned lists"""
+    from .metrics import list_metrics
+    rs = model.recSys
+    plain = int(lambda_q) == 256 and int(max_per_group) == 0
+    ok = (targets >= 0) & (targets < rs.item_table.shape[0])
+    n = int(ok.sum())
+    nan = float("nan")
+    if plain:
+        r = blend(model, icf, pop, users, ts, targets, None, quota_pop, k, pass_rows, recall_cfg=cfg)
+        pos, rank = r["target_pos"][ok].astype(np.int64), r["target_rank"][ok].astype(np.float64)
+        hit = (rank >= 0) & (rank < k)
+        out = dict(users=n, skipped=int((~ok).sum()), k=int(k), n_cand=int(cfg.n_cand),
+                   recall=float(np.mean(pos >= 0)) if n else nan,
+                   hit_rate=float(np.mean(hit)) if n else nan,
+                   ndcg=float(np.mean(np.where(hit, 1.0 / np.log2(np.where(hit, rank, 0.0) + 2.0), 0.0))) if n else nan)
+    else:
+        r = diverse(model, icf, pop, vectors, users, ts, targets, None, quota_pop, k, pool, lambda_q, max_per_group, pass_rows,
+                    recall_cfg=cfg)
+        pos, place = r["target_pos"][ok].astype(np.int64), r["target_place"][ok].astype(np.float64)
+        hit = place >= 0
+        later = (np.arange(r["pen"].shape[1])[None, :] >= 1) & (np.arange(r["pen"].shape[1])[None, :] < r["count"][:, None])
+        out = dict(users=n, skipped=int((~ok).sum()), k=int(k), n_cand=int(cfg.n_cand),
+                   recall=float(np.mean(pos >= 0)) if n else nan,
+                   hit_rate=float(np.mean(hit)) if n else nan,
+                   ndcg=float(np.mean(np.where(hit, 1.0 / np.log2(np.where(hit, place, 0.0) + 2.0), 0.0))) if n else nan,
+                   list_similarity=float(np.mean(r["pen"][later].astype(np.float64) / 65536.0)) if later.any() else nan)
+    out.update(lambda_q=int(lambda_q), pool=int(pool), max_per_group=int(max_per_group))
+    lm = list_metrics(r["items"], r["count"], vectors, pop, rs.item_table.shape[0], tail_cnt, rows=details, expo=details)
+    rows, expo = lm.pop("rows", None), lm.pop("expo", None)
+    lm.pop("n_req"), lm.pop("n_items")
+    out.update(lm)
+    if details:
+        out.update(items=r["items"], count=r["count"], src=r["src"], target_pos=r["target_pos"], rank=r["target_rank"],
+                   list_rows=rows, expo=expo, user_index=users, target_index=targets, ts=ts)
+        if not plain:
+            out.update(target_place=r["target_place"], pen=r["pen"])
+    return out
+
+
+def EvaluateListQuality(model: Predictor, icf, vectors, pop=None, k=10, lambda_q=256, pool=64, max_per_group=0, sample_kw=None,
+                        details=False, pass_rows=0, quota_pop=0, pop_kw=None, tail_cnt=0, **recall_kw):
+    """EXTENSION -- what a re-rank setting buys and costs, on one measure: EvaluateLeaveOneOutDiverse's protocol (the same held-out
+    entries, candidates and popularity list), the accuracy figures of EvaluateLeaveOneOutBlend (``lambda_q`` = 256 without a cap:
+    the plain selection, goctr_recommend_blend) or of EvaluateLeaveOneOutDiverse (anything else), computed as those functions
+    compute them, and goctr_metrics_lists' figures over the RETURNED lists (metrics.list_metrics; include/goctr.h defines them):
+        ild         1 - the mean quantised cosine (negative as 0) over the lists' item pairs
+        coverage    the share of the catalogue some list reaches;    gini   the concentration of the items' exposure
+        novelty     the mean log2((counted + n_items) / (cnt + 1)) of the listed items under ``pop``'s counts
+        tail_share  the share of listed items whose count is at most ``tail_cnt``
+    together with the integers they are quotients of.  ``vectors`` (BuildItemVectors) measures the similarity whatever the path;
+    ``pop`` None: built here below the held-out events, as EvaluateLeaveOneOutBlend does.  details=True adds the columns, the
+    per-row records (``list_rows``) and the exposure histogram (``expo``)."""
+    from .recall import make_recall_cfg
+    users, targets, ts = _held_out_rows(model, sample_kw)
+    own = pop is None
+    if own:
+        pkw = dict(pop_kw or {})
+        pkw.setdefault("ts_hi", int(ts.min()))            # as EvaluateLeaveOneOutBlend: nothing at or after a held-out event counts
+        pop = BuildPopular(model.recSys, **pkw)
+    recall_kw.setdefault("exclude", "before")
+    cfg = make_recall_cfg(**recall_kw)
+    try:
+        return _list_quality(model, icf, vectors, pop, users, ts, targets, cfg, k, lambda_q, pool, max_per_group, pass_rows, quota_pop,
+                             tail_cnt, details)
+    finally:
+        if own:
+            pop.close()
+
+
+def DiversityTradeoff(model: Predictor, icf, vectors, lambdas=(256, 224, 192, 128), pop=None, k=10, pool=64, max_per_group=0,
+                      sample_kw=None, pass_rows=0, quota_pop=0, pop_kw=None, tail_cnt=0, **recall_kw):
+    """EXTENSION: EvaluateListQuality's figures for every ``lambda_q`` of ``lambdas`` -- one dict per value, in their order -- over
+    ONE set of held-out rows and ONE popularity list, so that the rows differ in the re-rank alone"""
+    from .recall import make_recall_cfg
+    users, targets, ts = _held_out_rows(model, sample_kw)
+    own = pop is None
+    if own:
+        pkw = dict(pop_kw or {})
+        pkw.setdefault("ts_hi", int(ts.min()))
+        pop = BuildPopular(model.recSys, **pkw)
+    recall_kw.setdefault("exclude", "before")
+    cfg = make_recall_cfg(**recall_kw)
+    try:
+        return [_list_quality(model, icf, vectors, pop, users, ts, targets, cfg, k, lam, pool, max_per_group, pass_rows, quota_pop,
+                              tail_cnt, False) for lam in lambdas]
+    finally:
+        if own:
+            pop.close()

@@ -696,6 +696,74 @@ int goctr_recommend_blend_mmr(goctr_model* m, goctr_recsys* r, goctr_itemcf* icf
                               int32_t* cand_items, uint32_t* cand_w, float* cand_scores, uint8_t* cand_src, int64_t* n_failed,
                               int32_t* out_obj, uint32_t* out_pen, int32_t* out_target_place);
 
+/* ---- List-quality metrics: intra-list diversity, catalogue coverage, exposure concentration, novelty, groups (no reference
+ * counterpart).  goctr_metrics_lists judges the lists a recommend call returned -- row q of `items` with count[q] entries in use --
+ * against the item vectors the re-rank used and the popularity counts the blend fills from.  Every integer output is defined
+ * exactly and every double is the correctly rounded quotient of two of them (tests/listq_ref.py is the host restatement); two
+ * calls over the same arguments return the same bytes.  Host arrays, the engine stream and the engine lock, like goctr_rerank_mmr.
+ *
+ *   entries        a row's entries are its places p < count[q].  An entry is LISTED when 0 <= item < n_items (others are skipped
+ *                  everywhere) and USABLE when it is listed, v is given and v's valid[item] = 1.  A repeated item counts at
+ *                  every place it occurs
+ *   sim(a,b)       for two places a != b of a row that are both usable: dot(q[item_a], q[item_b]) >> 12 when the dot is
+ *                  positive, else 0, over v's quantised int16 rows (65536 = cosine 1) -- the MMR rule above.  0 when a = b or
+ *                  either place is not usable.  A row's pairs are its places a < b that are both usable
+ *   sim output     [n_req,k,k], may be NULL (must be NULL without v): row q's matrix sim(a,b), symmetric, 0 on the diagonal and
+ *                  in every row and column of a place that is not usable (places >= count[q] included)
+ *   ilog2_q16(x)   for a 64-bit x >= 1, in integers: e = floor(log2 x); m = the top 32 bits of x << (63 - e); sixteen times
+ *                  m2 = (m * m) >> 31, and when m2 >= 2^32 the next bit is 1 and m = m2 >> 1, else the bit is 0 and m = m2;
+ *                  the value is e * 65536 + the sixteen bits, first bit highest.  It is monotone, and value / 65536 is never
+ *                  above log2 x and at most 2^-15 below it
+ *   nov(i)         ilog2_q16(counted + n_items) - ilog2_q16(cnt[i] + 1) with pop's per-item cnt and its counted (what
+ *                  goctr_popular_export / _info return); never negative.  An item is TAIL when cnt[i] <= cfg->tail_cnt
+ *   goctr_list_row listed, usable: the row's listed / usable entries; pairs = usable (usable - 1) / 2; sim_sum, sim_max: the sum
+ *                  and the largest of sim over the pairs (0 without a pair); nov_sum: the sum of nov(item) over the listed
+ *                  entries; tail: the listed entries whose item is tail; over the listed entries and v's group ids: groups = the
+ *                  distinct ids >= 0, group_max = the most entries sharing one id >= 0, ungrouped = the entries with a negative id
+ *   expo           [n_items], may be NULL: expo[i] = the listed entries of the batch that hold item i
+ *   out            n_req, n_items as given; entries = the sum of count; listed, usable, pairs, sim_sum, nov_sum, tail: the rows'
+ *                  sums; sim_max: the rows' largest; covered = the items with expo > 0;
+ *                  gini_num = sum over i = 1 .. n_items of (2 i - n_items - 1) x_(i), x_(1) <= x_(2) <= .. being expo in
+ *                  ascending order (ties cannot change it); never negative
+ *   doubles        each the quotient of two integers rounded once to the nearest double, ties to even, NaN when the denominator
+ *                  is 0:  coverage = covered / n_items;  gini = gini_num / (n_items * listed);
+ *                  novelty = nov_sum / (65536 * listed);  tail_share = tail / listed;
+ *                  ild = 1.0 - (sim_sum / (65536 * pairs)): the rounded quotient first, then one float64 subtraction (a repeated
+ *                  item's sim may pass 65536 by the quantisation's error, so ild may fall a hair below 0)
+ *   v == NULL      usable, pairs, sim_sum, sim_max and the three group fields are 0 and ild is NaN
+ *   pop == NULL    nov_sum and tail are 0, novelty and tail_share are NaN
+ *   no groups      a v built without groups: the three group fields are 0
+ *   refused        (-1, nothing touched) null items, count, cfg or out; n_req <= 0 or > 2^24; k outside 1 .. 256; a negative
+ *                  tail_cnt; a count[q] outside 0 .. k; n_req * k >= 2^31; n_items <= 0 or > 2^31 - 1 or different from a
+ *                  handle's; sim given without v; v and pop on different engines
+ * A row is one workgroup: the usable entries' int8 planes are gathered into LDS and all pair dot products come out of the int8
+ * matrix instruction, exact in integers. */
+typedef struct {
+  int32_t k;          /* 1 .. 256: row stride of `items`                                      default 10 */
+  int32_t tail_cnt;   /* >= 0: an item is "tail" when pop's cnt[i] <= tail_cnt                 default 0  */
+} goctr_list_cfg;
+void goctr_list_cfg_default(goctr_list_cfg* c);
+typedef struct {                  /* per request row */
+  uint32_t listed, usable, pairs;
+  uint32_t sim_max;
+  uint64_t sim_sum;
+  uint64_t nov_sum;
+  uint32_t tail, groups, group_max, ungrouped;
+} goctr_list_row;
+typedef struct {                  /* the batch */
+  int64_t n_req, n_items;
+  uint64_t entries, listed, usable, pairs, sim_sum, nov_sum, tail;
+  uint32_t sim_max;
+  int64_t covered;
+  int64_t gini_num;
+  double ild, coverage, gini, novelty, tail_share;
+} goctr_list_metrics;
+int goctr_metrics_lists(goctr_itemvec* v /* may be NULL */, goctr_popular* pop /* may be NULL */,
+                        const int32_t* items /* [n_req,k] */, const int32_t* count /* [n_req], each 0 .. k */,
+                        int64_t n_req, int64_t n_items, const goctr_list_cfg* cfg,
+                        goctr_list_metrics* out, goctr_list_row* rows /* [n_req] or NULL */,
+                        uint32_t* expo /* [n_items] or NULL */, uint32_t* sim /* [n_req,k,k] or NULL */);
+
 /* The replica a multi-device training call (cfg.devices = n) keeps on engine `rank` (rank 0: the handle itself); NULL before
  * the first such call.  Borrowed: owned by the handle it was asked from.  For checks that the replicas are bit-identical
  * (tests, bench.py's replica checksum) -- every entry point works on it, on its own engine. */
