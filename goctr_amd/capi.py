@@ -170,6 +170,12 @@ class ItemnbrCfg(C.Structure):
     _fields_ = [("n_nbr", C.c_int32), ("min_w", C.c_int32), ("pass_items", C.c_int64)]
 
 
+class SwingCfg(C.Structure):
+    """goctr_swing_cfg (include/goctr.h)"""
+    _fields_ = [("max_len", C.c_int32), ("max_users", C.c_int32), ("alpha_q", C.c_int32), ("n_nbr", C.c_int32),
+                ("min_pairs", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64), ("pair_budget", C.c_int64)]
+
+
 class MmrCfg(C.Structure):
     """goctr_mmr_cfg (include/goctr.h)"""
     _fields_ = [("k", C.c_int32), ("pool", C.c_int32), ("lambda_q", C.c_int32), ("max_per_group", C.c_int32)]
@@ -244,6 +250,7 @@ SYMBOLS = [
     "goctr_mmr_cfg_default", "goctr_itemvec_build_vectors", "goctr_itemvec_build_emb", "goctr_itemvec_destroy", "goctr_itemvec_info",
     "goctr_itemvec_export", "goctr_rerank_mmr", "goctr_recommend_blend_mmr",
     "goctr_list_cfg_default", "goctr_metrics_lists",
+    "goctr_swing_cfg_default", "goctr_itemcf_build_swing",
 ]
 
 _lib = None
@@ -267,7 +274,8 @@ def load() -> C.CDLL:
                      "goctr_w2v_cfg_default", "goctr_negsample_cfg_default", "goctr_samples_destroy", "goctr_topn_cfg_default",
                      "goctr_itemcf_cfg_default", "goctr_recall_cfg_default", "goctr_itemcf_destroy", "goctr_curve_cfg_default",
                      "goctr_multiclass_cfg_default", "goctr_popular_cfg_default", "goctr_popular_destroy",
-                     "goctr_itemnbr_cfg_default", "goctr_mmr_cfg_default", "goctr_itemvec_destroy", "goctr_list_cfg_default"):
+                     "goctr_itemnbr_cfg_default", "goctr_mmr_cfg_default", "goctr_itemvec_destroy", "goctr_list_cfg_default",
+                     "goctr_swing_cfg_default"):
             getattr(_lib, name).restype = None
         _bm = C.POINTER(BinaryMetrics)
         _lib.goctr_metrics_binary.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, _bm]
@@ -349,6 +357,8 @@ def load() -> C.CDLL:
         _lib.goctr_recommend_blend.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32, _i32,
                                                C.c_int32, C.POINTER(RecallCfg), C.c_int32, C.c_int32, C.c_int64, _i32, _f32, _i32,
                                                _u8, _i32, _i32, _i64, _i32, _u32, _f32, _u8, _i64]
+        _lib.goctr_swing_cfg_default.argtypes = [C.POINTER(SwingCfg)]
+        _lib.goctr_itemcf_build_swing.argtypes = [C.c_void_p, C.c_int64, C.POINTER(SwingCfg), C.POINTER(C.c_void_p)]
         _mmr = C.POINTER(MmrCfg)
         _lib.goctr_mmr_cfg_default.argtypes = [_mmr]
         _lib.goctr_itemvec_build_vectors.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int32, _i32, C.POINTER(C.c_void_p)]
@@ -512,6 +522,14 @@ def default_recall_cfg(**kw) -> RecallCfg:
 def default_itemnbr_cfg(**kw) -> ItemnbrCfg:
     c = ItemnbrCfg()
     load().goctr_itemnbr_cfg_default(C.byref(c))
+    for k, v in kw.items():
+        setattr(c, k, v)
+    return c
+
+
+def default_swing_cfg(**kw) -> SwingCfg:
+    c = SwingCfg()
+    load().goctr_swing_cfg_default(C.byref(c))
     for k, v in kw.items():
         setattr(c, k, v)
     return c

@@ -1,4 +1,5 @@
-// negsample.h -- the handle of goctr_samples_create (negsample.hip), read by goctr_dataset_create_samples (ctr_api.hip).
+// negsample.h -- the handle of goctr_samples_create (negsample.hip), read by goctr_dataset_create_samples (ctr_api.hip), and the
+// sampler's hash step, which swing.hip keys its holder sample with.
 #pragma once
 #include "common.h"
 
@@ -13,3 +14,12 @@ struct goctr_samples {
   goctr::DevBuf<float> y;
   goctr::DevBuf<unsigned int> w;                 // the sampling weights [n_items]
 };
+
+namespace goctr {
+__device__ __forceinline__ unsigned long long ns_mix(unsigned long long x) {   // one splitmix64 step
+  x += 0x9E3779B97F4A7C15ULL;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ULL;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBULL;
+  return x ^ (x >> 31);
+}
+}  // namespace goctr

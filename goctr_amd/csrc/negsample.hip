@@ -39,13 +39,6 @@ __device__ __forceinline__ bool ns_positive(int item, long long ts, long long p,
          len - 1 - p >= s.min_history && ts >= s.ts_lo && ts <= s.ts_hi;
 }
 
-__device__ __forceinline__ unsigned long long ns_mix(unsigned long long x) {   // one splitmix64 step
-  x += 0x9E3779B97F4A7C15ULL;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ULL;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBULL;
-  return x ^ (x >> 31);
-}
-
 // floor((c^3 * 2^16)^(1/4)): sqrt is correctly rounded and c^3 * 2^16 < 2^112 carries a relative error of 2^-52 at most, so the
 // float64 estimate of a result below 2^28 is off by less than one; the integer comparisons settle it
 __device__ __forceinline__ unsigned int ns_weight075(unsigned int c) {

@@ -518,6 +518,15 @@ class ItemCF {
     check(goctr_itemcf_build(cache, n_items, &cfg, &h_));
   }
   ItemCF(RecSys& rs, const goctr_itemcf_cfg& cfg = DefaultCfg()) : ItemCF(rs.cache(), rs.n_items(), cfg) {}
+  // Swing neighbour lists (goctr_itemcf_build_swing): item similarity from user-pair overlap, all integer, weights on ItemCF's
+  // scale (a list's first weight is 65536)
+  static goctr_swing_cfg DefaultSwingCfg() { goctr_swing_cfg c; goctr_swing_cfg_default(&c); return c; }
+  static ItemCF Swing(goctr_ubcache* cache, int64_t n_items, const goctr_swing_cfg& cfg = DefaultSwingCfg()) {
+    goctr_itemcf* h = nullptr;
+    check(goctr_itemcf_build_swing(cache, n_items, &cfg, &h));
+    return ItemCF(h);
+  }
+  static ItemCF Swing(RecSys& rs, const goctr_swing_cfg& cfg = DefaultSwingCfg()) { return Swing(rs.cache(), rs.n_items(), cfg); }
   // neighbour lists from item VECTORS (goctr_itemcf_build_vectors / _emb): quantised cosine in units of 2^-16, the scale of the
   // co-occurrence weights, so every consumer takes either kind of handle
   static goctr_itemnbr_cfg DefaultNbrCfg() { goctr_itemnbr_cfg c; goctr_itemnbr_cfg_default(&c); return c; }

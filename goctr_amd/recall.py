@@ -11,6 +11,9 @@ restatement).
 request row -- ItemCF's candidates, a list of the caller's, then the popularity list -- de-duplicated and seen-filtered on the
 device, so that a row without history still gets candidates (tests/popular_ref.py is the host restatement).
 
+``ItemCF.swing`` is a third source of neighbour lists: Swing, item similarity from user-pair overlap, in integers throughout
+(tests/swing_ref.py is the host restatement).
+
 ``ItemVectors`` holds the catalogue's quantised vectors (and optionally a group id per item) in HBM, and ``rerank_mmr`` picks k of
 every row's scored candidates greedily, trading relevance against similarity to what it has picked, with a cap per group
 (tests/mmr_ref.py is the host restatement).  ``recommend.RecommendDiverse`` runs it as the last step of RecommendBlend.
@@ -28,6 +31,7 @@ _BUILD_FIELDS = {"window", "max_len", "n_nbr", "min_co", "pair_budget"}
 _RECALL_FIELDS = {"history", "n_cand", "exclude"}
 _POPULAR_FIELDS = {"half_life", "ts_ref", "ts_lo", "ts_hi", "n_list"}
 _NBR_FIELDS = {"n_nbr", "min_w", "pass_items"}
+_SWING_FIELDS = {"max_len", "max_users", "alpha_q", "n_nbr", "min_pairs", "seed", "pair_budget"}
 _MMR_FIELDS = {"k", "pool", "lambda_q", "max_per_group"}
 _LIST_FIELDS = {"k", "tail_cnt"}
 
@@ -58,6 +62,14 @@ def make_nbr_cfg(**kw) -> capi.ItemnbrCfg:
     if unknown:
         raise TypeError(f"goctr_itemnbr_cfg has no field {sorted(unknown)}")
     return capi.default_itemnbr_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
+
+
+def make_swing_cfg(**kw) -> capi.SwingCfg:
+    """goctr_swing_cfg from keywords (integers; the ranges are the library's to refuse)"""
+    unknown = set(kw) - _SWING_FIELDS
+    if unknown:
+        raise TypeError(f"goctr_swing_cfg has no field {sorted(unknown)}")
+    return capi.default_swing_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
 
 
 def make_mmr_cfg(**kw) -> capi.MmrCfg:
@@ -150,6 +162,19 @@ class ItemCF:
         h = C.c_void_p()
         e = table._h if hasattr(table, "_h") else table
         capi.check(capi.load().goctr_itemcf_build_emb(e, C.c_int64(_as_int("n_items", n_items)), C.byref(cfg), C.byref(h)))
+        return cls._adopt(h)
+
+    @classmethod
+    def swing(cls, ubc, n_items: int, cfg: capi.SwingCfg | None = None, **kw) -> "ItemCF":
+        """goctr_itemcf_build_swing: neighbour lists from user-pair overlap (Swing) over ``ubc``'s device image (a
+        ubcache.UserBehaviorCache or a raw goctr_ubcache handle); ``kw``: goctr_swing_cfg fields.  Every method works on the result
+        as on a co-occurrence build; nbr_co holds np, the user pairs that voted"""
+        if cfg is not None and kw:
+            raise TypeError("give either cfg or keywords")
+        cfg = cfg if cfg is not None else make_swing_cfg(**kw)
+        h = C.c_void_p()
+        c = ubc.device() if hasattr(ubc, "device") else ubc
+        capi.check(capi.load().goctr_itemcf_build_swing(c, C.c_int64(_as_int("n_items", n_items)), C.byref(cfg), C.byref(h)))
         return cls._adopt(h)
 
     def info(self) -> dict:

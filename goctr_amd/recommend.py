@@ -548,6 +548,17 @@ def BuildItemCF(recSys: DeviceRecSys, **cfg):
     return ItemCF(recSys._dense_cache, recSys.item_table.shape[0], **cfg)
 
 
+def BuildSwing(recSys: DeviceRecSys, **cfg):
+    """EXTENSION: Swing neighbour lists (recall.ItemCF.swing; ``cfg``: goctr_swing_cfg fields) of the recSys's own behaviour cache
+    over the rows of its item feature table: item similarity from user-pair overlap, which a pair that many heavy users touched by
+    accident does not win.  Every RecommendItemCF / RecommendBlend / MergeItemCF call takes the handle like BuildItemCF's.  The
+    lists are those of the cache's image at THIS call."""
+    from .recall import ItemCF
+    if recSys.ubcache is None:
+        raise RuntimeError("this recSys has no behaviour cache to build neighbour lists from (it does not implement UserBehavior, rcmd.go:512)")
+    return ItemCF.swing(recSys._dense_cache, recSys.item_table.shape[0], **cfg)
+
+
 def BuildItemNeighbours(recSys: DeviceRecSys, **cfg):
     """EXTENSION: neighbour lists from the recSys's item VECTORS (recall.ItemCF.from_embedding; ``cfg``: goctr_itemnbr_cfg fields):
     the rows of its embedding table in HBM, over the rows of its item feature table -- the n_items BuildItemCF uses, so every

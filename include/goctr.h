@@ -614,6 +614,61 @@ int  goctr_itemcf_build_emb(goctr_emb* e, int64_t n_items /* rows 0 .. n_items-1
  *                  mul_a + mul_b outside 1 .. 256 (which keeps w <= 2^23); n_nbr outside 1 .. 256 */
 int  goctr_itemcf_merge(goctr_itemcf* a, goctr_itemcf* b, int32_t mul_a, int32_t mul_b, int32_t n_nbr, goctr_itemcf** out);
 
+/* ---- Swing: item neighbours from user-pair overlap, a third source of goctr_itemcf handles (no reference counterpart).  A
+ * co-occurrence count does not ask who produced it; Swing (Yang et al.) sums over every PAIR of users who hold both items and
+ * divides each pair's vote by how much the two users have in common altogether, so a pair a few focused users share outranks one
+ * that many heavy users touched by accident.  The result is a goctr_itemcf like goctr_itemcf_build's: recall, blend, recommend,
+ * merge, info, export and destroy take it unchanged.  Every output is defined bit for bit (tests/swing_ref.py is the host
+ * restatement); all arithmetic is integer, and no output byte depends on pair_budget, on a tile or pass size or on the arrival
+ * order of atomics.
+ *
+ * goctr_itemcf_build_swing:
+ *   considered     exactly goctr_itemcf_build's rule: of every user the valid entries (0 <= item < n_items), newest first; with
+ *                  max_len > 0 only the first max_len of them
+ *   I_u            the set of distinct items among user u's considered entries; u is the dense row of the cache image
+ *   cnt[i]         the users with i in I_u, counted before any cap (the handle's cnt)
+ *   holders U'_i   all users that hold i when there are at most max_users; otherwise the max_users holders with the smallest
+ *                  key(i,u) = mix(seed ^ mix(((uint64) i << 32) | u)) >> 32, mix = one splitmix64 step (x += 0x9E3779B97F4A7C15;
+ *                  x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^ x >> 31, as the negative
+ *                  sampler's), equal keys by the smaller u: a pinned pseudo-random sample that favours neither old nor active users
+ *   ov(u,v)        for u < v the number of items i with both u and v in U'_i.  Without a cap in effect this is |I_u n I_v|; with
+ *                  one it is the overlap seen through the capped lists, on purpose
+ *   term           a user pair with ov >= 2 has t = floor(2^28 / (alpha_q + 256 ov)) in 64-bit integers: t <= 2^19, and t = 0
+ *                  is possible for ov > 2^20 (the pair still counts in np)
+ *   s, np          for every ordered pair i != j of the user pair's shared items (those i with u, v in U'_i): s(i,j) += t,
+ *                  np(i,j) += 1.  np <= C(1024, 2) < 2^19, s < 2^38; both are symmetric
+ *   weight         w(i,j) = (uint32) ((s(i,j) << 16) / rowmax_i) with rowmax_i = the maximum of s(i,j) over ALL j, 0 when
+ *                  rowmax_i = 0.  With min_pairs = 1 a non-empty list's first weight is 65536, the scale of ItemCF's and the
+ *                  vector source's weights, so goctr_itemcf_merge mixes them at par (with min_pairs > 1 the row's maximum may
+ *                  itself be filtered and the first stored weight be smaller)
+ *   neighbours     of i: every j with np(i,j) >= min_pairs and w(i,j) > 0, by w descending, then j ascending; the first n_nbr are
+ *                  stored: nbr_w = w, nbr_co = np, padding -1 / 0 / 0
+ *   info           distinct_pairs = the directed pairs with np > 0; total_pairs = the user pairs with ov >= 2; cache_version =
+ *                  that of the image read (one image for the whole build)
+ *   passes         pair_budget bounds the keys of any one sort: user-pair keys and emitted item-pair keys.  Users are taken in
+ *                  consecutive groups by the SMALLER user of a pair whose user-pair keys (the sum over items of the pairs of its
+ *                  holders) fit the budget, so a group's ov values are final; a group's user pairs are emitted in chunks of
+ *                  whole pairs whose ov (ov - 1) keys fit it.  A group holds at least one user and a chunk at least one user
+ *                  pair.  Partial (s, np) lists are merged as goctr_itemcf_build merges its passes, at the same cost: keep the
+ *                  default unless memory forces a smaller budget
+ *   cost           sum_i C(|U'_i|, 2) user-pair keys plus sum over user pairs of ov (ov - 1) emitted keys, each sorted once
+ *   refused        (-1, *out untouched) a cfg outside its ranges or reserved != 0; n_items <= 0 or > 2^31 - 1; a cache with 2^31 or
+ *                  more users; a single group or chunk of 2^36 or more keys
+ * An empty cache, or one in which no two users share two items, is not an error: every list is empty and cnt is still filled.
+ * Not covered: per-user activity weights, timestamps, an incremental rebuild after goctr_ubcache_append. */
+typedef struct {
+  int32_t  max_len;      /* >= 0; 0 = all                                   default 0   */
+  int32_t  max_users;    /* 2 .. 1024: holders of one item that take part   default 256 */
+  int32_t  alpha_q;      /* 0 .. 2^20, alpha in units of 1/256              default 256 */
+  int32_t  n_nbr;        /* 1 .. 256                                        default 64  */
+  int32_t  min_pairs;    /* >= 1                                            default 1   */
+  int32_t  reserved;     /* must be 0 */
+  uint64_t seed;         /* of the holder sample                            default 0   */
+  int64_t  pair_budget;  /* 0 = 2^26, else 2^10 .. 2^30                     default 0   */
+} goctr_swing_cfg;
+void goctr_swing_cfg_default(goctr_swing_cfg* c);
+int  goctr_itemcf_build_swing(goctr_ubcache* c, int64_t n_items, const goctr_swing_cfg* cfg, goctr_itemcf** out);
+
 /* ---- Diversity re-rank: maximal marginal relevance over item vectors, with group caps (no reference counterpart).  The recall
  * channels above return items close to the user's history, so the best k by score are typically one cluster.  A goctr_itemvec holds
  * the catalogue's quantised vectors (and optionally a group id per item) in HBM; goctr_rerank_mmr picks k of a row's scored
