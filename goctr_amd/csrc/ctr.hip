@@ -327,6 +327,7 @@ int goctr::launch_attn_fwd(const AttnArgs& a) {
     while (L < groups) L *= 2;
     if (!vec4 && L < 8) L = 8;
     if (a.src.k_users) snprintf(sym, sizeof sym, "attn_fwd_keys_kernel<%d,%d>", std::min(L, 64), fast);
+    else if (!vec4 && groups > 64) snprintf(sym, sizeof sym, "attn_fwd_wide_kernel<%d>", groups <= 128 ? 2 : 4);
     else snprintf(sym, sizeof sym, "attn_fwd_kernel<%d,%d,%d>", vec4 ? 4 : 1, std::min(L, 64), (fast && groups <= 16) ? fast : 0);
     prof_note_kernel(GOCTR_K_ATTN_FWD, sym);
   }
@@ -374,7 +375,10 @@ int goctr::launch_attn_fwd(const AttnArgs& a) {
     if (groups <= 8) GOCTR_ATTN_FWD(1, 8);
     else if (groups <= 16) GOCTR_ATTN_FWD(1, 16);
     else if (groups <= 32) GOCTR_ATTN_FWD(1, 32);
-    else GOCTR_ATTN_FWD(1, 64);
+    else if (groups <= 64) GOCTR_ATTN_FWD(1, 64);
+    // more than 64 scalar columns (dense rows, or ids with D % 4 != 0): a lane owns columns l, l + 64, ... (D <= 256: goctr_model_create)
+    else if (groups <= 128) hipLaunchKernelGGL((attn_fwd_wide_kernel<2>), grid, blk, 0, st, a);
+    else hipLaunchKernelGGL((attn_fwd_wide_kernel<4>), grid, blk, 0, st, a);
   }
 #undef GOCTR_ATTN_FWD_FAST
 #undef GOCTR_ATTN_FWD
@@ -653,6 +657,15 @@ int launch_attn_bwd(const AttnBwdArgs& a, int blocks) {
   const bool vec4 = a.src.id_mode && a.D % 4 == 0;
   const int groups = vec4 ? a.D / 4 : a.D;
   const bool fast = vec4 && groups * 4 == a.D && (groups & (groups - 1)) == 0 && groups <= 16;
+  if (ps.on) {   // the symbol the dispatch below selects (goctr_prof_kernel)
+    static char sym[48];
+    int L = 1;
+    while (L < groups) L *= 2;
+    if (!vec4 && L < 8) L = 8;
+    if (!vec4 && groups > 64) snprintf(sym, sizeof sym, "attn_bwd_kernel<%d,64,2>", groups <= 128 ? 2 : 4);
+    else snprintf(sym, sizeof sym, "attn_bwd_kernel<%d,%d,%d>", vec4 ? 4 : 1, std::min(L, 64), fast ? 1 : 0);
+    prof_note_kernel(GOCTR_K_ATTN_BWD, sym);
+  }
 #define GOCTR_ATTN_BWD(V, L) hipLaunchKernelGGL((attn_bwd_kernel<V, L, 0>), grid, blk, lds, st, a)
 #define GOCTR_ATTN_BWD_FAST(L) hipLaunchKernelGGL((attn_bwd_kernel<4, L, 1>), grid, blk, lds, st, a)
   if (fast) {
@@ -674,7 +687,9 @@ int launch_attn_bwd(const AttnBwdArgs& a, int blocks) {
     if (groups <= 8) GOCTR_ATTN_BWD(1, 8);
     else if (groups <= 16) GOCTR_ATTN_BWD(1, 16);
     else if (groups <= 32) GOCTR_ATTN_BWD(1, 32);
-    else GOCTR_ATTN_BWD(1, 64);
+    else if (groups <= 64) GOCTR_ATTN_BWD(1, 64);
+    else if (groups <= 128) hipLaunchKernelGGL((attn_bwd_kernel<2, 64, 2>), grid, blk, lds, st, a);   // (wide rows, as in launch_attn_fwd)
+    else hipLaunchKernelGGL((attn_bwd_kernel<4, 64, 2>), grid, blk, lds, st, a);
   }
 #undef GOCTR_ATTN_BWD_FAST
 #undef GOCTR_ATTN_BWD

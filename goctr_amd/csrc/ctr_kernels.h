@@ -168,31 +168,32 @@ __device__ __forceinline__ float cross_row_sum(float v) {
   return v;
 }
 
-// load VEC consecutive embedding lanes of one row (all-zero when the row pointer is null)
-template <int VEC>
+// load VEC embedding lanes of one row, columns d0 + e * CS (all-zero when the row pointer is null); CS = 1: consecutive
+// columns, CS = 64: the strided ownership of the wide scalar-lane kernels (attn_fwd_wide_kernel)
+template <int VEC, int CS = 1>
 __device__ __forceinline__ void load_row(const float* row, int d0, int D, float x[VEC]) {
 #pragma unroll
   for (int e = 0; e < VEC; ++e) x[e] = 0.f;
   if (row && d0 < D) {
-    if (VEC == 4) {
+    if (VEC == 4 && CS == 1) {
       float4 t4 = *reinterpret_cast<const float4*>(row + d0);
       x[0] = t4.x; x[1] = t4.y; x[2] = t4.z; x[3] = t4.w;
     } else {
 #pragma unroll
-      for (int e = 0; e < VEC; ++e) x[e] = d0 + e < D ? row[d0 + e] : 0.f;
+      for (int e = 0; e < VEC; ++e) x[e] = d0 + e * CS < D ? row[d0 + e * CS] : 0.f;
     }
   }
 }
 
 // same for a row pointer that is never null (id mode points missing ids at the all-zero row V of the device
 // table, so the load needs no predicate and no zero-initialised destination); `full` = every lane's d0 < D
-template <int VEC>
+template <int VEC, int CS = 1>
 __device__ __forceinline__ void load_row_nn(const float* row, int d0, int D, bool full, float x[VEC]) {
-  if (VEC == 4 && full) {
+  if (VEC == 4 && CS == 1 && full) {
     float4 t4 = *reinterpret_cast<const float4*>(row + d0);
     x[0] = t4.x; x[1] = t4.y; x[2] = t4.z; x[3] = t4.w;
   } else {
-    load_row<VEC>(row, d0, D, x);
+    load_row<VEC, CS>(row, d0, D, x);
   }
 }
 
@@ -212,6 +213,8 @@ __device__ __forceinline__ void load_row_off32(const float* base, int row, int D
 // 64 behaviour slots are fetched with ONE coalesced load and handed to the row lanes by shuffle, then
 // the row loads of NPB passes are issued back to back before any arithmetic, so the dependent chain
 // is state -> ids -> rows (3 memory latencies) regardless of T.
+// WIDE (rows of more than 64 columns that cannot take 16-byte loads: dense TrainSample rows, id mode with D % 4 != 0): LPR = 64 and
+// lane l owns the VEC columns l, l + 64, ... -- a lane of the <1, 64, 0> instantiation owns column l alone, which covers D <= 64.
 // FAST: 0 = every mode decided at run time; 1 / 2 / 3 = id mode with D == LPR * VEC and the model kind fixed at
 // compile time (YouTube mean pooling / DIN cosine / DIN euclid): the kernel is VALU-bound (rocprofv3: ~500 VALU
 // instructions per sample against 10 loads and 6 stores), and run-time mode branches inside its unrolled loops cost
@@ -225,7 +228,7 @@ struct RaCtx { const unsigned int* flag; unsigned int expect; const float* att0;
 // sample: the launch's row this wavefront takes, or -1 = workgroup `blk`'s row of its wavefront index (4 per workgroup)
 // key: (KEYS) the sample's key if its workgroup has already fetched it (ctr_serve16_kernel), else null = read it here
 struct AttnKey { int user, item; long long ts; };
-template <int VEC, int LPR, int FAST, bool KEYS = false>
+template <int VEC, int LPR, int FAST, bool KEYS = false, bool WIDE = false>
 __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a, int blk, long long batch_idx, const float* att0w,
                                               const RaCtx* ra = nullptr, int sample = -1, const AttnKey* key = nullptr) {
   // (round 6: this body's sums of products may contract to fused multiply-adds -- one rounding instead of two per term, and 4 v_fma_f32
@@ -245,7 +248,8 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a, int blk, long l
   const long long gr = batch_idx * (long long)a.B + b;
   const bool valid = gr < s.rows;
   const int dl = lane % LPR, rl = lane / LPR;
-  const int d0 = dl * VEC;
+  constexpr int CS = WIDE ? LPR : 1;      // lane element e is column d0 + e * CS
+  const int d0 = WIDE ? dl : dl * VEC;
   const int D = a.D, T = a.T;
 
   // key mode: the sample's key -> its user / item feature rows and the window of its behaviour sequence
@@ -307,14 +311,14 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a, int blk, long l
   if (KEYS) { if (lane < kcnt) ids64_first = s.ub_items[kb + lane]; }
   else if (idm && valid && lane < T) ids64_first = s.ub_ids[gr * T + lane];
   // candidate item embedding v
-  const bool full = FAST ? true : D == LPR * VEC;   // every lane owns VEC in-range embedding columns (wave-uniform)
+  const bool full = FAST ? true : (!WIDE && D == LPR * VEC);   // every lane owns VEC in-range embedding columns (wave-uniform)
   float vv[VEC];
   if (idm) {
     const int it = KEYS ? kitem : (valid ? s.item_ids[gr] : -1);
     if (FAST) load_row_off32<VEC>(s.emb, (it >= 0 && it < s.V) ? it : (int)s.V, D, d0, vv);
-    else load_row_nn<VEC>(s.emb + (long long)((it >= 0 && it < s.V) ? it : s.V) * D, d0, D, full, vv);
+    else load_row_nn<VEC, CS>(s.emb + (long long)((it >= 0 && it < s.V) ? it : s.V) * D, d0, D, full, vv);
   } else {
-    load_row<VEC>(valid ? s.X + gr * (long long)s.xcols + s.r_v : nullptr, d0, D, vv);
+    load_row<VEC, CS>(valid ? s.X + gr * (long long)s.xcols + s.r_v : nullptr, d0, D, vv);
   }
   float syy = 0.f;
 #pragma unroll
@@ -346,9 +350,9 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a, int blk, long l
       if (idm) {
         const int id = __shfl(ids64, (tbx - tb0) + p * RPP + rl, 64);
         if (FAST) load_row_off32<VEC>(s.emb, id, D, d0, xx[p]);
-        else load_row_nn<VEC>(s.emb + (long long)((t < T && id >= 0 && id < s.V) ? id : s.V) * D, d0, D, full, xx[p]);
+        else load_row_nn<VEC, CS>(s.emb + (long long)((t < T && id >= 0 && id < s.V) ? id : s.V) * D, d0, D, full, xx[p]);
       } else {
-        load_row<VEC>((valid && t < T) ? s.X + gr * (long long)s.xcols + s.r_ub + t * D : nullptr, d0, D, xx[p]);
+        load_row<VEC, CS>((valid && t < T) ? s.X + gr * (long long)s.xcols + s.r_ub + t * D : nullptr, d0, D, xx[p]);
       }
     }
   };
@@ -379,7 +383,7 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a, int blk, long l
           u1 = group_sum<LPR>(u1);
         } else {
 #pragma unroll
-          for (int e = 0; e < VEC; ++e) { float df = x[p][e] - vv[e]; u0 += (d0 + e < D) ? df * df : 0.f; }
+          for (int e = 0; e < VEC; ++e) { float df = x[p][e] - vv[e]; u0 += (d0 + e * CS < D) ? df * df : 0.f; }
           u0 = group_sum<LPR>(u0);
         }
         const float v0 = __shfl(u0, src, 64), v1 = __shfl(u1, src, 64);
@@ -437,7 +441,7 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a, int blk, long l
   // mean over T as a multiply by 1/T (one division per sample instead of one per column; <= 1 ulp from x / T)
   const float invT = a.inv_T;
   float* hrow = a.h0 + (size_t)b * a.Ip;
-  if (VEC == 4 && (a.U & 3) == 0 && (a.Ip & 3) == 0 && (D & 3) == 0) {
+  if (VEC == 4 && !WIDE && (a.U & 3) == 0 && (a.Ip & 3) == 0 && (D & 3) == 0) {
     // pooled sum and candidate embedding as two 16-byte stores from the first row group
     typedef float v4 __attribute__((ext_vector_type(4)));
     v4 pv;
@@ -451,9 +455,9 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a, int blk, long l
 #pragma unroll
     for (int e = 0; e < VEC; ++e) {
       float p = cross_row_sum<LPR>(psum[e]) * invT;
-      if (rl == 0 && d0 + e < D) {
-        hrow[a.U + d0 + e] = p;
-        hrow[a.U + D + d0 + e] = vv[e];
+      if (rl == 0 && d0 + e * CS < D) {
+        hrow[a.U + d0 + e * CS] = p;
+        hrow[a.U + D + d0 + e * CS] = vv[e];
       }
     }
   }
@@ -474,6 +478,12 @@ template <int VEC, int LPR, int FAST>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
   const int grp = xcd_unit_of_block((int)blockIdx.x, (a.B + 3) >> 2, 32);
   attn_fwd_body<VEC, LPR, FAST>(a, grp, a.st->batch_idx, a.att0);
+}
+// rows of 65 .. 64 NC columns on scalar lanes (see WIDE at attn_fwd_body)
+template <int NC>
+__global__ __launch_bounds__(256) void attn_fwd_wide_kernel(AttnArgs a) {
+  const int grp = xcd_unit_of_block((int)blockIdx.x, (a.B + 3) >> 2, 32);
+  attn_fwd_body<NC, 64, 0, false, true>(a, grp, a.st->batch_idx, a.att0);
 }
 // serving passes: the rows come from (user, item, timestamp) keys (RowSource key mode) -- key assembly and attention in one launch
 template <int LPR, int FAST>
@@ -498,15 +508,19 @@ constexpr int ATTN_BWD_WAVES = 16;  // samples per workgroup (one wavefront each
 // (SURVEY A.1).  One wavefront per sample, all row gathers in flight at once; the terms go to
 // dgs [B, Tp] and the sum over the batch is done by the weight-gradient GEMM launch as a ones-column
 // product (same deterministic slab reduction as every other gradient).
+// FAST: 0 = modes decided at run time; 1 = id mode with D == LPR * VEC; 2 = run-time modes on WIDE rows as in attn_fwd_body
+// (LPR = 64, lane l owns the VEC columns l, l + 64, ...)
 template <int VEC, int LPR, int FAST>
 __global__ __launch_bounds__(64 * ATTN_BWD_WAVES) void attn_bwd_kernel(AttnBwdArgs a) {
-  const bool idm = FAST ? true : (bool)a.src.id_mode;
+  constexpr bool WIDE = FAST == 2;
+  const bool idm = FAST == 1 ? true : (bool)a.src.id_mode;
   constexpr int RPP = 64 / LPR;
   constexpr int NPB = LPR < 4 ? LPR : 4;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const RowSource& s = a.src;
-  const int dl = lane % LPR, rl = lane / LPR, d0 = dl * VEC;
+  constexpr int CS = WIDE ? LPR : 1;
+  const int dl = lane % LPR, rl = lane / LPR, d0 = WIDE ? dl : dl * VEC;
   const int D = a.D, T = a.T;
   const int b = blockIdx.x * ATTN_BWD_WAVES + wave;
   if (b >= a.B) return;
@@ -514,7 +528,7 @@ __global__ __launch_bounds__(64 * ATTN_BWD_WAVES) void attn_bwd_kernel(AttnBwdAr
   const bool valid = gr < s.rows;
   float dpt[VEC];
 #pragma unroll
-  for (int e = 0; e < VEC; ++e) dpt[e] = d0 + e < D ? a.dp[(size_t)b * a.Dp + d0 + e] / (float)T : 0.f;
+  for (int e = 0; e < VEC; ++e) dpt[e] = d0 + e * CS < D ? a.dp[(size_t)b * a.Dp + d0 + e * CS] / (float)T : 0.f;
   float* out = a.partial + (size_t)b * a.Tp;
   for (int t = T + lane; t < a.Tp; t += 64) out[t] = 0.f;
   for (int tb = 0; tb < T; tb += NPB * RPP) {
@@ -532,9 +546,9 @@ __global__ __launch_bounds__(64 * ATTN_BWD_WAVES) void attn_bwd_kernel(AttnBwdAr
       const int t = tb + p * RPP + rl;
       if (idm) {
         const int id = __shfl(myid, p * RPP + rl, 64);
-        load_row_nn<VEC>(s.emb + (long long)((t < T && id >= 0 && id < s.V) ? id : s.V) * D, d0, D, FAST ? true : D == LPR * VEC, x[p]);
+        load_row_nn<VEC, CS>(s.emb + (long long)((t < T && id >= 0 && id < s.V) ? id : s.V) * D, d0, D, FAST == 1 ? true : (!WIDE && D == LPR * VEC), x[p]);
       } else {
-        load_row<VEC>((valid && t < T) ? s.X + gr * (long long)s.xcols + s.r_ub + t * D : nullptr, d0, D, x[p]);
+        load_row<VEC, CS>((valid && t < T) ? s.X + gr * (long long)s.xcols + s.r_ub + t * D : nullptr, d0, D, x[p]);
       }
     }
     const float gw = (gl * (1.0f - gl));     // g (1 - g) of slot tb + lane

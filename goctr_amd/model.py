@@ -33,14 +33,16 @@ class _CtrNet:
     kind = DIN
 
     def __init__(self, uProfileDim, uBehaviorSize, uBehaviorDim, iFeatureDim, cFeatureDim, att=ATT_COSINE,
-                 d0=0.0, d1=0.0):
+                 d0=0.0, d1=0.0, hidden=None):
+        """hidden=(H1, H2): widths of the two hidden layers (default: the reference's mlp0_1, mlp1_2)"""
         self.uProfileDim, self.uBehaviorSize, self.uBehaviorDim = uProfileDim, uBehaviorSize, uBehaviorDim
         self.iFeatureDim, self.cFeatureDim = iFeatureDim, cFeatureDim
         self.d0, self.d1 = d0, d1
         self.att = att
+        self.H1, self.H2 = (int(h) for h in (hidden if hidden is not None else (mlp0_1, mlp1_2)))
         self._h = C.c_void_p()
         L = capi.init()
-        self.cfg = capi.CtrCfg(self.kind, att, uProfileDim, uBehaviorSize, uBehaviorDim, cFeatureDim, mlp0_1, mlp1_2)
+        self.cfg = capi.CtrCfg(self.kind, att, uProfileDim, uBehaviorSize, uBehaviorDim, cFeatureDim, self.H1, self.H2)
         capi.check(L.goctr_model_create(C.byref(self.cfg), C.byref(self._h)))
         self.predBatchSize = None
 
@@ -59,7 +61,7 @@ class _CtrNet:
         return self.uProfileDim + self.uBehaviorDim + self.iFeatureDim + self.cFeatureDim
 
     def _shape(self, name):
-        return {"mlp0": (self.I, mlp0_1), "mlp1": (mlp0_1, mlp1_2), "mlp2": (mlp1_2, 1),
+        return {"mlp0": (self.I, self.H1), "mlp1": (self.H1, self.H2), "mlp2": (self.H2, 1),
                 "att0": (1, self.uBehaviorSize)}[name]
 
     def set_weights(self, name, arr):
@@ -206,7 +208,15 @@ def NewYoutubeDnn(uProfileDim, uBehaviorSize, uBehaviorDim, iFeatureDim, cFeatur
 
 def _from_json(cls, data):
     d = json.loads(data)
-    m = cls(d["uProfileDim"], d["uBehaviorSize"], d["uBehaviorDim"], d["iFeatureDim"], d["cFeatureDim"])
+    # the JSON carries no widths (din.go:41-52): mlp1 is [H1, H2] and mlp2 is [H2, 1], both flat
+    H2 = len(d["mlp2"])
+    if H2 == 0 or len(d["mlp1"]) % H2:
+        raise ValueError(f"mlp1 ({len(d['mlp1'])} values) is not a whole number of rows of mlp2's {H2}")
+    m = cls(d["uProfileDim"], d["uBehaviorSize"], d["uBehaviorDim"], d["iFeatureDim"], d["cFeatureDim"],
+            hidden=(len(d["mlp1"]) // H2, H2))
+    for n in m.Learnable():
+        if len(d[n]) != int(np.prod(m._shape(n))):
+            raise ValueError(f"{n}: {len(d[n])} values, the dims ask for {m._shape(n)}")
     for n in m.Learnable():
         m.set_weights(n, np.asarray(d[n], np.float32))
     if "adamStep" in d:  # written by Marshal(optimizer=True): resume Adam where it stopped
@@ -287,6 +297,9 @@ def loss_grad(m: _CtrNet, si: SampleInfo, X, Y, B=None, cfg=None, step=0, m0=Non
     r = si.as_ranges()
     m0 = capi.f32(m0) if m0 is not None else None
     m1 = capi.f32(m1) if m1 is not None else None
+    for mask, H in ((m0, m.H1), (m1, m.H2)):      # explicit dropout masks (dropout_mode 1): [B, H1] and [B, H2]
+        if mask is not None and mask.shape != (B, H):
+            raise ValueError(f"dropout mask of shape {mask.shape}, the model's layer is {(B, H)}")
     capi.check(capi.load().goctr_loss_grad_dense(
         m._h, capi.ptr(X, C.c_float), capi.ptr(Y, C.c_float), C.c_int(valid), C.c_int(B), C.c_int(X.shape[1]),
         capi.ptr(r, C.c_int), C.byref(cfg), C.c_uint32(step), capi.ptr(m0, C.c_float), capi.ptr(m1, C.c_float),

@@ -98,6 +98,10 @@ typedef struct {
                      -- the arguments of din.NewDinNet (din.go:171-175) */
   int H1, H2;     /* hidden widths; 200 / 80 in the reference (din.go:17-18) */
 } goctr_ctr_cfg;
+/* Any cfg with D <= 256 and positive T, H1, H2 computes the same function; only H1 = 200, H2 = 80 with I = U + 2 D + C <= 240
+ * (DIN: D <= 32) takes the tuned launches (the fused chain kernel, and for id-mode rows with D a power of two in 4 .. 64 the
+ * compile-time attention kernels), every other shape the generic ones: one GEMM launch per layer, one weight-gradient launch
+ * per tensor once a padded width of H1, H2 or (DIN) T exceeds 256, and for dense rows or D % 4 != 0 scalar-lane attention. */
 
 /* replaces din.NewDinNet / youtube.NewYoutubeDnn (din.go:171, dnn.go:119).  Weights start at zero
  * with att0 = 1; the host sets the N(0,1) init (din.go:187-191) or JSON weights through

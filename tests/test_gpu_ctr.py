@@ -6,61 +6,18 @@ most twice as far from that truth as the float32 oracle itself is (float32 summa
 k-order and slab sums vs the oracle's sequential loops; the weight-gradient GEMM runs on the 6-product bf16
 split).  The dropout cases, which the float64 evaluation does not cover, keep 1e-6 + 2e-4*max|g| vs the oracle."""
 import os
+import sys
 
 import numpy as np
 import pytest
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from ctr_ref import COST_TOL_SMALL_SHAPES, LOGIT_TOL, LOSS_TOL, grad_bound, grad_close, make_data, pair  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
-# Multi-epoch training COSTS of the reduced-size shapes below are held to 5e-5, not to the 1e-5 of logits / loss / the full-size
-# tests (tests/test_gpu_fullsize.py holds 1e-5 at the benchmark's shapes).  Why: these tests use 0.15-0.3 N(0,1) weights on a few
-# dozen inputs, which puts single rows at |z2| ~ 10.  There one float32 ulp of the pre-activation (|z2| 2^-23 ~ 1.2e-6, and device
-# and oracle sum z2 in different orders) moves log p = -softplus(-z2) by ~1e-6 for that row; a batch of 20-50 rows holds a few such
-# rows, their signs do not cancel inside one mean, and after 2-4 epochs of updates that each saw such a cost the epoch means drift
-# by a few 1e-5 (round 3 tightened these from 1e-4 and found 1e-5 too tight for exactly these shapes, DESIGN.md 3).  5e-5 = that
-# drift with margin; a real defect (a wrong mask, a missing 1/B) shows up at 1e-3 and above.
-COST_TOL_SMALL_SHAPES = 5e-5
-
-LOGIT_TOL = 1e-5
-LOSS_TOL = 1e-5
-
-
-def grad_close(g, ref):
-    return np.max(np.abs(g - ref)) <= 1e-6 + 2e-4 * np.max(np.abs(ref))
-
-
-def grad_bound(g_dev, g_orc, g64):
-    """|g_dev - truth|_max <= 2 |g_orc32 - truth|_max + one float32 ulp of the largest entry"""
-    g_dev, g_orc, g64 = (np.asarray(a, np.float64).ravel() for a in (g_dev, g_orc, g64))
-    return np.max(np.abs(g_dev - g64)) <= 2 * np.max(np.abs(g_orc - g64)) + 6e-8 * np.max(np.abs(g64))
-
-
-def make_data(rng, rows, U, T, D, Cc, pad_frac=0.3):
-    X = rng.random((rows, U + T * D + D + Cc), dtype=np.float32)
-    ub = X[:, U:U + T * D].reshape(rows, T, D)
-    ub[rng.random((rows, T)) < pad_frac] = 0.0
-    Y = (rng.random(rows) < 0.5).astype(np.float32)
-    return X, Y
-
-
-def pair(oracle, kind, U, T, D, Cc, rng, att=0, scale=None):
-    """an oracle model and a device model with identical weights"""
-    from goctr_amd import model as gm
-    from goctr_amd.recommend import SampleInfo
-    om = oracle.CtrModel(kind, U, T, D, Cc, att=att)
-    if scale is None:
-        om.init_gaussian(rng)            # the reference's N(0,1) init (din.go:187-191)
-    else:
-        om.W0[:] = (rng.standard_normal(om.W0.shape) * scale).astype(np.float32)
-        om.W1[:] = (rng.standard_normal(om.W1.shape) * scale).astype(np.float32)
-        om.W2[:] = (rng.standard_normal(om.W2.shape) * scale).astype(np.float32)
-    om.att0[:] = (1 + 0.3 * rng.standard_normal(om.att0.shape)).astype(np.float32) if kind == 0 else 1.0
-    cls = gm.DinNet if kind == 0 else gm.YoutubeDnn
-    dm = cls(U, T, D, D, Cc, att=att) if kind == 0 else cls(U, T, D, D, Cc)
-    dm.set_weights("mlp0", om.W0); dm.set_weights("mlp1", om.W1); dm.set_weights("mlp2", om.W2)
-    if kind == 0:
-        dm.set_weights("att0", om.att0)
-    return om, dm, SampleInfo.from_dims(U, T, D, Cc)
+# (the tolerance constants with their derivations, grad_close / grad_bound, make_data and pair live in tests/ctr_ref.py, shared with
+# tests/test_gpu_ctr_shapes.py)
 
 
 DIMS = [(5, 3, 7, 5), (52, 10, 16, 53), (52, 50, 16, 53), (52, 50, 64, 53)]   # last: BASELINE cfg4 (D=64, I=233)
