@@ -181,6 +181,11 @@ class MmrCfg(C.Structure):
     _fields_ = [("k", C.c_int32), ("pool", C.c_int32), ("lambda_q", C.c_int32), ("max_per_group", C.c_int32)]
 
 
+class UservecCfg(C.Structure):
+    """goctr_uservec_cfg (include/goctr.h)"""
+    _fields_ = [("min_w", C.c_int32), ("reserved", C.c_int32), ("chunk_items", C.c_int64)]
+
+
 class ListCfg(C.Structure):
     """goctr_list_cfg (include/goctr.h)"""
     _fields_ = [("k", C.c_int32), ("tail_cnt", C.c_int32)]
@@ -251,6 +256,7 @@ SYMBOLS = [
     "goctr_itemvec_export", "goctr_rerank_mmr", "goctr_recommend_blend_mmr",
     "goctr_list_cfg_default", "goctr_metrics_lists",
     "goctr_swing_cfg_default", "goctr_itemcf_build_swing",
+    "goctr_uservec_cfg_default", "goctr_uservec_recall", "goctr_recommend_uservec", "goctr_recommend_blend_uservec",
 ]
 
 _lib = None
@@ -275,7 +281,7 @@ def load() -> C.CDLL:
                      "goctr_itemcf_cfg_default", "goctr_recall_cfg_default", "goctr_itemcf_destroy", "goctr_curve_cfg_default",
                      "goctr_multiclass_cfg_default", "goctr_popular_cfg_default", "goctr_popular_destroy",
                      "goctr_itemnbr_cfg_default", "goctr_mmr_cfg_default", "goctr_itemvec_destroy", "goctr_list_cfg_default",
-                     "goctr_swing_cfg_default"):
+                     "goctr_swing_cfg_default", "goctr_uservec_cfg_default"):
             getattr(_lib, name).restype = None
         _bm = C.POINTER(BinaryMetrics)
         _lib.goctr_metrics_binary.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, _bm]
@@ -370,6 +376,17 @@ def load() -> C.CDLL:
         _lib.goctr_recommend_blend_mmr.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32, _i32,
                                                    C.c_int32, C.POINTER(RecallCfg), C.c_int32, C.c_void_p, _mmr, C.c_int64, _i32, _f32,
                                                    _i32, _u8, _i32, _i32, _i64, _i32, _u32, _f32, _u8, _i64, _i32, _u32, _i32]
+        _uv = C.POINTER(UservecCfg)
+        _lib.goctr_uservec_cfg_default.argtypes = [_uv]
+        _lib.goctr_uservec_recall.argtypes = [C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, C.POINTER(RecallCfg), _uv, _i32, _u32, _i32,
+                                              _i32, _i32, C.POINTER(C.c_int16), _u64]
+        _lib.goctr_recommend_uservec.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32,
+                                                 C.POINTER(RecallCfg), _uv, C.c_int32, C.c_int64, _i32, _f32, _i32, _i32, _i32, _i64,
+                                                 _i32, _u32, _f32, _i64]
+        _lib.goctr_recommend_blend_uservec.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32,
+                                                       C.c_void_p, _uv, C.c_int32, C.POINTER(RecallCfg), C.c_int32, C.c_void_p, _mmr,
+                                                       C.c_int32, C.c_int64, _i32, _f32, _i32, _u8, _i32, _i32, _i64, _i32, _u32, _f32,
+                                                       _u8, _i64, _i32, _u32, _i32]
         _lib.goctr_list_cfg_default.argtypes = [C.POINTER(ListCfg)]
         _lib.goctr_metrics_lists.argtypes = [C.c_void_p, C.c_void_p, _i32, _i32, C.c_int64, C.c_int64, C.POINTER(ListCfg),
                                              C.POINTER(ListMetrics), C.POINTER(ListRow), _u32, _u32]
@@ -538,6 +555,14 @@ def default_swing_cfg(**kw) -> SwingCfg:
 def default_mmr_cfg(**kw) -> MmrCfg:
     c = MmrCfg()
     load().goctr_mmr_cfg_default(C.byref(c))
+    for k, v in kw.items():
+        setattr(c, k, v)
+    return c
+
+
+def default_uservec_cfg(**kw) -> UservecCfg:
+    c = UservecCfg()
+    load().goctr_uservec_cfg_default(C.byref(c))
     for k, v in kw.items():
         setattr(c, k, v)
     return c

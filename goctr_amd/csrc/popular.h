@@ -3,6 +3,7 @@
 // blend of the recall channels and the call's driver, which is itemcf.h's recall_rank_run with the blend as its recall stage.
 #pragma once
 #include "itemcf.h"
+#include "uservec.h"
 
 // time-decayed item popularity resident in HBM; immutable after the build, independent of the cache it was built from
 struct goctr_popular {
@@ -23,6 +24,8 @@ namespace goctr {
 struct BlendArgs {
   const goctr_itemcf* icf; const goctr_popular* pop;   // each may be null
   const int32_t* extra; int n_extra, quota_pop;
+  // goctr_recommend_blend_uservec's alone: part X's list is the user-vector recall's (n_extra entries a row), written on the device
+  const goctr_itemvec* uv = nullptr; goctr_uservec_cfg ucfg{};
 };
 
 // the refusals that need no slot (sets the error text); `who`: the entry's name, goctr_recommend_blend or goctr_recommend_blend_mmr

@@ -1,0 +1,33 @@
+// uservec.h -- what goctr_uservec_recall's launches (uservec.hip) lend to the serving entries: goctr_recommend_uservec runs them as
+// the recall stage of itemcf.h's recall_rank_run, and goctr_recommend_blend_uservec (popular.hip's driver) has them write the list
+// the blend's part X reads.  include/goctr.h states the semantics ("User-vector recall"); tests/uservec_ref.py restates them.
+#pragma once
+#include "itemcf.h"
+
+namespace goctr {
+
+// device scratch of one call: the request planes, and a row group's seen bitmaps and per-chunk partial lists.  Declared by the
+// caller in front of whatever drains the stream, so that an error return drains before the buffers go back to the arena
+struct UvScratch {
+  DevBuf<signed char> p_hi, p_lo;               // [n_req + 32, Dp], laid out like the item planes
+  DevBuf<unsigned int> bitmap;                  // [group rows, ceil(n_items / 32)]
+  DevBuf<unsigned long long> lists;             // [group rows, chunks, n_cand] keys descending, 0 = unused
+};
+
+// the cfg's ranges (sets the error text)
+int uservec_check_cfg(const goctr_uservec_cfg* ucfg, const char* who);
+
+// pool, seen, scan and merge over nq rows on `st`: row q's first cfg.n_cand slots at q * stride (stride >= cfg.n_cand) of o_items /
+// o_w, o_count[q], o_tpos[q].  o_p [nq, D] and o_s [nq] may be null.  The cache arrays may be null together (no cache: every row
+// comes back empty).  Waits for nothing
+int uservec_launch(const goctr_itemvec* v, const long long* off, const int32_t* seq_items, const long long* seq_ts,
+                   const RecallInputs& in, bool has_targets, int64_t nq, const goctr_recall_cfg& cfg, const goctr_uservec_cfg& ucfg,
+                   int stride, int32_t* o_items, unsigned int* o_w, int32_t* o_count, int32_t* o_tpos, int16_t* o_p,
+                   unsigned long long* o_s, UvScratch& ws, hipStream_t st);
+
+// goctr_recommend_uservec's refusals that need no slot, and the whole call over a prepared slot
+int uservec_check_recommend(const goctr_itemvec* v, const goctr_uservec_cfg* ucfg, const ItemcfRecArgs& a, int64_t n_users,
+                            int64_t n_items);
+int uservec_recommend_run(const TopnScorer& sc, const goctr_itemvec* v, const goctr_uservec_cfg& ucfg, const ItemcfRecArgs& a);
+
+}  // namespace goctr

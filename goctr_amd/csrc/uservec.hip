@@ -1,0 +1,527 @@
+// uservec.hip -- goctr_uservec_recall: user-to-item recall.  A request row's history is pooled into one interest vector, quantised
+// like an item row, and matched against the WHOLE catalogue of a goctr_itemvec; goctr_recommend_uservec ranks the result with the
+// model (include/goctr.h states the semantics; tests/uservec_ref.py restates them on the host, bit for bit).  After the one pinned
+// float64 quantisation all arithmetic is integer.
+//
+// Launches (the caller's stream; request rows are taken in groups whose bitmaps and partial lists fit a scratch budget):
+//   uv_pool_kernel    one workgroup per request row: the history as icf_recall_kernel's step 1 takes it, u_d = the int32 sum of the
+//                     history items' q_d from the planes, s = the sum of u_d^2 (an exact integer), p_d by iv_quant_kernel's pinned
+//                     operations, written as two int8 planes laid out exactly like the item planes
+//   uv_seen_kernel    one workgroup per row of the group: a bitmap over [0, n_items) of the sequence entries the mode looks at
+//   uv_scan_kernel    grid = column chunks x row tiles, so that one request row still spreads the catalogue over the whole chip.
+//                     Four mfma_i32_16x16x64_i8 per K step as in inb_pairs_kernel (itemnbr.hip), A from the request planes and B
+//                     from the item planes by ONE fragment rule, so the k order of the instruction cannot show.  The keys
+//                     (w << 32 | ~item) of the columns that pass min_w, the row's threshold and the seen test join the row's list
+//                     in LDS; a list that could overflow in the next step is sorted and trimmed to n_cand.  The rows of a
+//                     workgroup follow from n_cand and the call's rows (32 .. 4) so that the lists take 64 KiB at most.  Every (row, chunk) list
+//                     goes to HBM
+//   uv_merge_kernel   one workgroup per row: the best n_cand keys of the row's chunk lists (topn.h's list), taken place by place
+//                     across the chunks until a place brings nothing above the threshold; then items, w, count and the target's
+//                     place
+// Keys of one row are distinct (the item is in the key), so the kept set depends on no arrival order, chunk size, row grouping or
+// tile size.
+#include <algorithm>
+#include <climits>
+#include <memory>
+
+#define GOCTR_NO_PLAIN_KERNELS      // the kernel headers' plain kernels belong to ctr.hip
+#include "itemvec.h"
+#include "ubcache.h"
+#include "uservec.h"
+
+using namespace goctr;
+
+namespace {
+
+using u64 = unsigned long long;
+using i32x4 = __attribute__((ext_vector_type(4))) int;
+
+constexpr int UV_K = IV_K;                     // the MFMA's K
+constexpr int UV_THREADS = 256;
+constexpr int UV_WAVES = UV_THREADS / 64;
+constexpr int UV_CT = 2;                       // 16-column tiles per wavefront and step
+constexpr int UV_STEP = UV_WAVES * UV_CT * 16; // columns per step: the most one row's list can grow by between two checks
+constexpr int UV_PAD_ROWS = 32;                // zero rows behind the request planes: partial row tiles read them
+constexpr int UV_MAX_H = 256, UV_MAX_D = 1024;
+constexpr int UV_GROUP_ALIGN = 32;             // a row group holds a multiple (the last one excepted): whole row tiles
+constexpr int UV_MIN_CHUNK = 512;              // the implementation's choice of chunk_items is at least this
+constexpr int UV_LIST_BYTES = 64 * 1024;       // the lists of a workgroup: two workgroups and more to a CU
+constexpr int UV_ROUNDS = 4;                   // workgroups per resident slot the chunk count aims at: a short tail
+
+// list capacity in LDS for lists of n_cand: a trimmed list and one step's appends fit in each half
+inline int uv_cap(int n_cand) {
+  int c = UV_STEP;
+  while (c < n_cand) c <<= 1;
+  return 2 * c;
+}
+// rows of a workgroup: what the lists leave room for, and no more than the call has (one request row keeps 8: small workgroups,
+// many to a CU)
+inline int uv_rows(int cap, int64_t nq) {
+  const int fit = std::min(32, UV_LIST_BYTES / (cap * (int)sizeof(u64)));
+  return std::min(fit, nq <= 8 ? 8 : nq <= 16 ? 16 : 32);
+}
+static_assert(UV_LIST_BYTES / (2 * 1024 * 8) == UV_WAVES, "lists of 1024 leave the trim one row per wavefront");
+static_assert(UV_LIST_BYTES + 32 * 16 <= 160 * 1024 - 1024, "the lists, thresholds, fills and targets fit in LDS");
+
+// ---------------------------------------------------------------------------------------------------------------- pool
+struct PoolArgs {
+  const long long* off; const int32_t* seq_items; const long long* seq_ts;   // the cache's image (null: no cache)
+  long long n_items;
+  const int32_t* users; const long long* ts;
+  int H, D, Dp;
+  const signed char* hi; const signed char* lo;                              // the item planes [n_items, Dp]
+  signed char* p_hi; signed char* p_lo;                                      // the request planes [nq + UV_PAD_ROWS, Dp], zeroed
+  int16_t* out_p; u64* out_s;                                                // [nq, D], [nq]; each may be null
+};
+
+__global__ __launch_bounds__(UV_THREADS) void uv_pool_kernel(PoolArgs a) {
+  __shared__ int hist[UV_MAX_H];
+  __shared__ int s_u[UV_MAX_D];
+  __shared__ int wcnt[UV_WAVES];
+  __shared__ u64 s_sum;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long q = blockIdx.x;
+  long long lo_e = 0, len = 0;
+  if (a.off) { const int u = a.users[q]; lo_e = a.off[u]; len = a.off[u + 1] - lo_e; }
+  const long long mts = a.ts[q];
+  if (tid == 0) s_sum = 0ull;
+
+  // the history: icf_recall_kernel's step 1
+  int nh = 0;
+  for (long long p0 = 0; p0 < len && nh < a.H; p0 += UV_THREADS) {
+    const long long p = p0 + tid;
+    int it = -1;
+    if (p < len && (mts == 0 || a.seq_ts[lo_e + p] <= mts)) it = a.seq_items[lo_e + p];
+    const bool valid = it >= 0 && it < a.n_items;
+    const u64 b = __ballot(valid);
+    if (lane == 0) wcnt[wave] = __popcll(b);
+    __syncthreads();
+    int base = nh, tot = 0;
+    for (int w = 0; w < UV_WAVES; ++w) { if (w < wave) base += wcnt[w]; tot += wcnt[w]; }
+    const int r = base + __popcll(b & ((1ull << lane) - 1ull));
+    if (valid && r < a.H) hist[r] = it;
+    nh += tot;
+    __syncthreads();
+  }
+  if (nh > a.H) nh = a.H;
+  __syncthreads();
+
+  // u_d: |u_d| <= 256 * 16384 = 2^22; the sum of squares below 2^45
+  u64 part = 0ull;
+  for (int d = tid; d < a.Dp; d += UV_THREADS) {
+    int u = 0;
+    for (int t = 0; t < nh; ++t) {
+      const size_t at = (size_t)hist[t] * a.Dp + d;
+      u += 256 * (int)a.hi[at] + (int)a.lo[at];
+    }
+    s_u[d] = u;
+    part += (u64)((long long)u * (long long)u);
+  }
+  for (int o = 32; o > 0; o >>= 1) part += __shfl_down(part, o, 64);
+  if (lane == 0 && part) atomicAdd(&s_sum, part);
+  __syncthreads();
+  const u64 s = s_sum;
+  if (tid == 0 && a.out_s) a.out_s[q] = s;
+  const bool valid = s > 0ull;
+  const double r = __dsqrt_rn((double)s);      // (s < 2^53: the conversion is exact)
+  for (int d = tid; d < a.Dp; d += UV_THREADS) {
+    const int p = valid ? (int)rint(__dmul_rn(__ddiv_rn((double)s_u[d], r), 16384.0)) : 0;
+    const int l = ((p + 128) & 255) - 128;
+    a.p_hi[(size_t)q * a.Dp + d] = (signed char)((p - l) >> 8);
+    a.p_lo[(size_t)q * a.Dp + d] = (signed char)l;
+    if (a.out_p && d < a.D) a.out_p[(size_t)q * a.D + d] = (int16_t)p;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- seen
+// bitmap [rows, words] was zeroed; row r of the group is request row q0 + r
+__global__ __launch_bounds__(UV_THREADS) void uv_seen_kernel(const long long* __restrict__ off, const int32_t* __restrict__ seq_items,
+                                                             const long long* __restrict__ seq_ts, long long n_items,
+                                                             const int32_t* __restrict__ users, const long long* __restrict__ ts,
+                                                             long long q0, int before, long long words,
+                                                             unsigned int* __restrict__ bitmap) {
+  const long long r = blockIdx.x, q = q0 + r;
+  const int u = users[q];
+  const long long lo_e = off[u], len = off[u + 1] - lo_e, mts = ts[q];
+  unsigned int* bm = bitmap + (size_t)r * words;
+  for (long long p = threadIdx.x; p < len; p += UV_THREADS) {
+    const int it = seq_items[lo_e + p];
+    if (it < 0 || it >= n_items) continue;
+    if (before && mts != 0 && seq_ts[lo_e + p] > mts) continue;
+    atomicOr(&bm[it >> 5], 1u << (it & 31));
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- scan
+struct ScanArgs {
+  const signed char* p_hi; const signed char* p_lo;   // request planes [nq + UV_PAD_ROWS, Dp]
+  const signed char* hi; const signed char* lo;       // item planes [n_items, Dp]
+  int Dp;
+  long long n_items, chunk;                            // chunk c covers the columns [c * chunk, min(n_items, (c + 1) * chunk))
+  long long q0; int g_rows;                            // the group's request rows [q0, q0 + g_rows)
+  int n_chunks, n_cand, cap, R; unsigned int min_w;
+  const unsigned int* bitmap; long long words;         // [g_rows, words]; null: nothing is seen
+  const int32_t* targets;                              // [nq] or null
+  u64* lists;                                          // [g_rows, n_chunks, n_cand]
+};
+
+__device__ inline i32x4 uv_frag(const signed char* plane, long long row, int Dp, int ks, int lane) {
+  return *reinterpret_cast<const i32x4*>(plane + (size_t)row * Dp + ks * UV_K + (lane >> 4) * 16);
+}
+
+// inb_trim (itemnbr.hip) for R rows: every wavefront sorts one row of each group of UV_WAVES rows that holds a row in need
+// (force: a row with an entry), descending, and trims it to n_cand
+__device__ inline void uv_trim(u64* keys, int* s_fill, u64* s_thr, int R, int cap, int n_cand, bool force) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int g = 0; g < R / UV_WAVES; ++g) {
+    bool need = false;
+    for (int w = 0; w < UV_WAVES; ++w) need = need || s_fill[g * UV_WAVES + w] > (force ? 0 : cap - UV_STEP);
+    if (!need) continue;                       // (uniform: s_fill is read behind a barrier and not written in between)
+    const int row = g * UV_WAVES + wave;
+    u64* k = keys + (size_t)row * cap;
+    const int fill = s_fill[row];
+    for (int t = fill + lane; t < cap; t += 64) k[t] = 0ull;
+    __syncthreads();
+    for (int size = 2; size <= cap; size <<= 1)
+      for (int stride = size >> 1; stride > 0; stride >>= 1) {
+        for (int t = lane; t < (cap >> 1); t += 64) {
+          const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
+          const bool desc = (lo & size) == 0;
+          const u64 x = k[lo], y = k[hi];
+          if (desc ? x < y : x > y) { k[lo] = y; k[hi] = x; }
+        }
+        __syncthreads();
+      }
+    if (lane == 0) { s_fill[row] = fill < n_cand ? fill : n_cand; s_thr[row] = fill >= n_cand ? k[n_cand - 1] : 0ull; }
+    __syncthreads();
+  }
+}
+
+// MT: 16-row MFMA tiles of a workgroup (R = 32: 2; R <= 16: 1 -- the tile's rows from R on are not used).  With one K step the
+// next step's column fragments are fetched before this step's barriers, so their latency hides behind this step's work
+template <bool ONE_K, int MT>
+__global__ __launch_bounds__(UV_THREADS) void uv_scan_kernel(ScanArgs a) {
+  // all of the kernel's LDS is dynamic (the opt-in above 64 KiB covers dynamic LDS alone): keys [R, cap], then the rows'
+  // thresholds, fill counts and targets
+  extern __shared__ u64 keys[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int R = a.R, cap = a.cap, KS = a.Dp / UV_K;
+  const long long chunk = blockIdx.x;
+  const int i0 = (int)blockIdx.y * R;                  // first row of the tile, within the group
+  const long long c0 = chunk * a.chunk, c1 = c0 + a.chunk < a.n_items ? c0 + a.chunk : a.n_items;
+  const int n_rows = a.g_rows - i0 < R ? a.g_rows - i0 : R;   // (>= 1)
+  u64* const s_thr = keys + (size_t)R * cap;
+  int* const s_fill = reinterpret_cast<int*>(s_thr + R);
+  int* const s_tgt = s_fill + R;
+  if (tid < R) {
+    s_fill[tid] = 0; s_thr[tid] = 0ull;
+    s_tgt[tid] = a.targets && tid < n_rows ? a.targets[a.q0 + i0 + tid] : -1;
+  }
+
+  const long long arow = a.q0 + i0 + (lane & 15);      // (rows behind the last request row are zero: UV_PAD_ROWS)
+  i32x4 a_hi[MT], a_lo[MT];
+  if (ONE_K)
+    for (int m = 0; m < MT; ++m) {
+      a_hi[m] = uv_frag(a.p_hi, arow + 16 * m, a.Dp, 0, lane);
+      a_lo[m] = uv_frag(a.p_lo, arow + 16 * m, a.Dp, 0, lane);
+    }
+  // (rows behind n_items are clamped, not skipped: a fetch past the chunk's end reads in bounds and is never used)
+  const long long jw = (long long)(wave * UV_CT) * 16 + (lane & 15), j_last = a.n_items - 1;
+  i32x4 n_hi[UV_CT], n_lo[UV_CT];
+  if (ONE_K)
+    for (int ct = 0; ct < UV_CT; ++ct) {
+      const long long j = c0 + jw + ct * 16, jl = j < j_last ? j : j_last;
+      n_hi[ct] = uv_frag(a.hi, jl, a.Dp, 0, lane); n_lo[ct] = uv_frag(a.lo, jl, a.Dp, 0, lane);
+    }
+  for (long long cs = c0; cs < c1; cs += UV_STEP) {
+    i32x4 c_hi[UV_CT], c_lo[UV_CT];
+    if (ONE_K)
+      for (int ct = 0; ct < UV_CT; ++ct) {
+        c_hi[ct] = n_hi[ct]; c_lo[ct] = n_lo[ct];
+        const long long j = cs + UV_STEP + jw + ct * 16, jl = j < j_last ? j : j_last;
+        n_hi[ct] = uv_frag(a.hi, jl, a.Dp, 0, lane); n_lo[ct] = uv_frag(a.lo, jl, a.Dp, 0, lane);
+      }
+    // every wavefront's appends of the last step are in LDS before the fills are looked at: the decision below is taken on the
+    // fills' final values, and its own barrier keeps this step's appends behind the look
+    __syncthreads();
+    if (__syncthreads_or(tid < R && s_fill[tid] > cap - UV_STEP)) uv_trim(keys, s_fill, s_thr, R, cap, a.n_cand, false);
+    for (int ct = 0; ct < UV_CT; ++ct) {
+      const long long jt = cs + (wave * UV_CT + ct) * 16;
+      if (jt >= c1) break;                     // (the wavefront's tiles ascend)
+      const long long j = jt + (lane & 15);
+      const long long jl = j < a.n_items ? j : a.n_items - 1;   // (the item planes have no rows behind n_items)
+      // the bitmap words of the tile's (row, column) pairs, asked for in front of the products: independent loads in flight
+      // together, not one dependent load per passing key
+      unsigned int seen_w[MT][4];
+      for (int m = 0; m < MT; ++m)
+        for (int r = 0; r < 4; ++r) {
+          const int row = 16 * m + (lane >> 4) * 4 + r;
+          seen_w[m][r] = a.bitmap && row < n_rows && j < c1 ? a.bitmap[(size_t)(i0 + row) * a.words + (j >> 5)] : 0u;
+        }
+      i32x4 hh[MT], x[MT], ll[MT];
+      for (int m = 0; m < MT; ++m) hh[m] = x[m] = ll[m] = i32x4{0, 0, 0, 0};
+      for (int ks = 0; ks < KS; ++ks) {
+        const i32x4 b_hi = ONE_K ? c_hi[ct] : uv_frag(a.hi, jl, a.Dp, ks, lane);
+        const i32x4 b_lo = ONE_K ? c_lo[ct] : uv_frag(a.lo, jl, a.Dp, ks, lane);
+        for (int m = 0; m < MT; ++m) {
+          if (!ONE_K) {
+            a_hi[m] = uv_frag(a.p_hi, arow + 16 * m, a.Dp, ks, lane);
+            a_lo[m] = uv_frag(a.p_lo, arow + 16 * m, a.Dp, ks, lane);
+          }
+          hh[m] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_hi[m], b_hi, hh[m], 0, 0, 0);
+          x[m] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_hi[m], b_lo, x[m], 0, 0, 0);
+          x[m] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_lo[m], b_hi, x[m], 0, 0, 0);
+          ll[m] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_lo[m], b_lo, ll[m], 0, 0, 0);
+        }
+      }
+      // C/D: register r of lane l is row 4 (l >> 4) + r, column l & 15
+      for (int m = 0; m < MT; ++m)
+        for (int r = 0; r < 4; ++r) {
+          const int row = 16 * m + (lane >> 4) * 4 + r;
+          const int dot = (int)((unsigned int)hh[m][r] * 65536u + (unsigned int)x[m][r] * 256u + (unsigned int)ll[m][r]);
+          const unsigned int w = dot > 0 ? (unsigned int)dot >> 12 : 0u;
+          if (w < a.min_w || row >= n_rows || j >= c1) continue;
+          const u64 key = ((u64)w << 32) | (u64)(~(unsigned int)j);
+          if (key <= s_thr[row]) continue;
+          if (((seen_w[m][r] >> (j & 31)) & 1u) && (int)j != s_tgt[row]) continue;
+          keys[(size_t)row * cap + atomicAdd(&s_fill[row], 1)] = key;   // (< cap: checked per step)
+        }
+    }
+  }
+  __syncthreads();
+  uv_trim(keys, s_fill, s_thr, R, cap, a.n_cand, true);
+  for (int e = tid; e < n_rows * a.n_cand; e += UV_THREADS) {
+    const int row = e / a.n_cand, t = e - row * a.n_cand;
+    a.lists[((size_t)(i0 + row) * a.n_chunks + chunk) * a.n_cand + t] = t < s_fill[row] ? keys[(size_t)row * cap + t] : 0ull;
+  }
+}
+
+// --------------------------------------------------------------------------------------------------------------- merge
+struct MergeArgs {
+  const u64* lists; int n_chunks, n_cand;
+  long long q0;
+  const int32_t* targets;                                                     // [nq] or null
+  int stride;                                                                 // row q's slots start at q * stride (>= n_cand)
+  int32_t* out_items; unsigned int* out_w; int32_t* out_count; int32_t* out_tpos;   // out_tpos may be null
+};
+static_assert(SEL_CAP >= 1024 + SEL_THREADS, "a trimmed list and one tile of keys must fit");
+
+__global__ __launch_bounds__(SEL_THREADS) void uv_merge_kernel(MergeArgs a) {
+  __shared__ u64 skey[SEL_CAP];
+  __shared__ unsigned sraw[SEL_CAP];
+  __shared__ int s_fill, s_tpos;
+  __shared__ u64 s_thr;
+  const int tid = threadIdx.x;
+  const long long r = blockIdx.x, q = a.q0 + r;
+  const u64* mine = a.lists + (size_t)r * a.n_chunks * a.n_cand;
+  const bool has_t = a.targets != nullptr;
+  const int tgt = has_t ? a.targets[q] : -1;
+  if (tid == 0) { s_fill = 0; s_thr = 0ull; s_tpos = -1; }
+  __syncthreads();
+  // a tile takes CH chunks x P places of their lists; a sweep is the tiles of all chunks over the same P places.  The lists
+  // descend, so once a whole sweep has brought no key above the threshold no later place can: with many chunks the merge ends
+  // after a few places
+  int CH = 1;
+  while (CH < a.n_chunks && CH < SEL_THREADS) CH <<= 1;
+  const int P = SEL_THREADS / CH, lc = tid & (CH - 1), lp = tid / CH;
+  for (int t = 0; t < a.n_cand; t += P) {
+    bool any = false;
+    for (long long cb = 0; cb < a.n_chunks; cb += CH) {
+      const u64 thr = s_thr;
+      const long long c = cb + lc;
+      const int pos = t + lp;
+      u64 key = c < a.n_chunks && pos < a.n_cand ? mine[(size_t)c * a.n_cand + pos] : 0ull;
+      if (key <= thr) key = 0ull;
+      any = sel_append(skey, sraw, &s_fill, &s_thr, a.n_cand, key, 0u) || any;
+    }
+    if (!any) break;                           // (uniform: sel_append returns the same in every thread)
+  }
+  sel_sort_trim(skey, sraw, &s_fill, &s_thr, a.n_cand);
+  const int fill = s_fill;
+  for (int i = tid; i < a.n_cand; i += SEL_THREADS) {
+    const long long o = q * a.stride + i;
+    if (i < fill) {
+      const int item = (int)~(unsigned int)skey[i];
+      a.out_items[o] = item;
+      a.out_w[o] = (unsigned int)(skey[i] >> 32);
+      if (has_t && item == tgt) s_tpos = i;                          // (items are distinct: one writer at most)
+    } else {
+      a.out_items[o] = -1;
+      a.out_w[o] = 0u;
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    a.out_count[q] = fill;
+    if (a.out_tpos) a.out_tpos[q] = s_tpos;
+  }
+}
+
+template <class Kern>
+int scan_launch(Kern kern, dim3 grid, size_t lds, hipStream_t st, const ScanArgs& a) {
+  // the opt-in for the largest lists, whatever this call's are; below the CU's 160 KiB, because the workgroup reductions keep a
+  // few bytes of static LDS beside the dynamic block
+  GOCTR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, UV_LIST_BYTES + 32 * 16));
+  hipLaunchKernelGGL(kern, grid, dim3(UV_THREADS), lds, st, a);
+  GOCTR_HIP(hipGetLastError());
+  return 0;
+}
+
+}  // namespace
+
+namespace goctr {
+
+int uservec_check_cfg(const goctr_uservec_cfg* ucfg, const char* who) {
+  GOCTR_CHECK(ucfg->min_w >= 1 && ucfg->min_w <= 65536, "%s: min_w = %d (1 .. 65536)", who, ucfg->min_w);
+  GOCTR_CHECK(ucfg->reserved == 0, "%s: reserved = %d (must be 0)", who, ucfg->reserved);
+  GOCTR_CHECK(ucfg->chunk_items == 0 || (ucfg->chunk_items >= 64 && ucfg->chunk_items <= ((int64_t)1 << 22)),
+              "%s: chunk_items = %lld (0, or 64 .. 2^22)", who, (long long)ucfg->chunk_items);
+  return 0;
+}
+
+int uservec_launch(const goctr_itemvec* v, const long long* off, const int32_t* seq_items, const long long* seq_ts,
+                   const RecallInputs& in, bool has_targets, int64_t nq, const goctr_recall_cfg& cfg, const goctr_uservec_cfg& ucfg,
+                   int stride, int32_t* o_items, unsigned int* o_w, int32_t* o_count, int32_t* o_tpos, int16_t* o_p,
+                   unsigned long long* o_s, UvScratch& ws, hipStream_t st) {
+  const int Dp = v->Dp, nc = cfg.n_cand, cap = uv_cap(nc), R = uv_rows(cap, nq);
+  const int64_t V = v->n_items;
+  const bool seen = cfg.exclude != GOCTR_TOPN_KEEP_SEEN && off != nullptr;
+  const int64_t words = cdiv(V, 32);
+  // the request planes
+  const size_t plane = ((size_t)nq + UV_PAD_ROWS) * Dp;
+  if (ws.p_hi.alloc(plane, false) || ws.p_lo.alloc(plane, false)) return -1;
+  GOCTR_HIP(hipMemsetAsync(ws.p_hi.p + (size_t)nq * Dp, 0, (size_t)UV_PAD_ROWS * Dp, st));
+  GOCTR_HIP(hipMemsetAsync(ws.p_lo.p + (size_t)nq * Dp, 0, (size_t)UV_PAD_ROWS * Dp, st));
+  PoolArgs p{};
+  p.off = off; p.seq_items = seq_items; p.seq_ts = seq_ts; p.n_items = V; p.users = in.users.p; p.ts = in.ts.p;
+  p.H = cfg.history; p.D = v->D; p.Dp = Dp; p.hi = v->hi.p; p.lo = v->lo.p; p.p_hi = ws.p_hi.p; p.p_lo = ws.p_lo.p;
+  p.out_p = o_p; p.out_s = o_s;
+  hipLaunchKernelGGL(uv_pool_kernel, dim3((unsigned)nq), dim3(UV_THREADS), 0, st, p);
+  GOCTR_HIP(hipGetLastError());
+
+  // the scratch budget decides the rows of a group; the chunks follow from the row tiles the first group brings, so that a
+  // single request row still fills the chip
+  const int64_t budget = (int64_t)std::max(0, env_int("GOCTR_USERVEC_SCRATCH_MB", 256)) << 20;
+  const int64_t bm_row = seen ? words * 4 : 0;
+  auto group_rows = [&](int64_t per_row) {
+    int64_t g = budget / std::max<int64_t>(1, per_row) / UV_GROUP_ALIGN * UV_GROUP_ALIGN;
+    g = std::max<int64_t>(g, UV_GROUP_ALIGN);
+    g = std::min<int64_t>(g, (int64_t)65535 * 4);                 // (row tiles are the grid's y)
+    return std::min<int64_t>(g, nq);
+  };
+  int64_t chunk = ucfg.chunk_items;
+  if (!chunk) {
+    const int64_t tiles = cdiv(group_rows(bm_row + (int64_t)nc * 8), R);
+    const int64_t resident = std::max<int64_t>(1, std::min<int64_t>(8, (160 * 1024) / ((int64_t)R * cap * 8 + 1024)));   // workgroups a CU holds
+    const int64_t want = std::max<int64_t>(1, cdiv(UV_ROUNDS * resident * std::max(1, engine().compute_units), tiles));
+    chunk = std::max<int64_t>(UV_MIN_CHUNK, cdiv(cdiv(V, want), UV_STEP) * UV_STEP);
+  }
+  const int64_t n_chunks = cdiv(V, chunk);
+  GOCTR_CHECK(n_chunks <= INT32_MAX / nc, "goctr_uservec_recall: %lld chunks of %lld items are too many (raise chunk_items)",
+              (long long)n_chunks, (long long)chunk);
+  const int64_t G = group_rows(bm_row + n_chunks * nc * 8);
+  if (ws.lists.alloc((size_t)G * n_chunks * nc, false) || (seen && ws.bitmap.alloc((size_t)G * words, false))) return -1;
+
+  const size_t lds = (size_t)R * ((size_t)cap * sizeof(u64) + sizeof(u64) + 2 * sizeof(int));
+  if (lds > UV_LIST_BYTES + 32 * 16) return -1;           // (cannot happen: uv_rows)
+  for (int64_t q0 = 0; q0 < nq; q0 += G) {
+    const int g_rows = (int)std::min<int64_t>(G, nq - q0);
+    if (seen) {
+      GOCTR_HIP(hipMemsetAsync(ws.bitmap.p, 0, (size_t)g_rows * words * 4, st));
+      hipLaunchKernelGGL(uv_seen_kernel, dim3((unsigned)g_rows), dim3(UV_THREADS), 0, st, off, seq_items, seq_ts, (long long)V,
+                         in.users.p, in.ts.p, (long long)q0, cfg.exclude == GOCTR_TOPN_DROP_SEEN_BEFORE ? 1 : 0, (long long)words,
+                         ws.bitmap.p);
+      GOCTR_HIP(hipGetLastError());
+    }
+    ScanArgs a{};
+    a.p_hi = ws.p_hi.p; a.p_lo = ws.p_lo.p; a.hi = v->hi.p; a.lo = v->lo.p; a.Dp = Dp; a.n_items = V; a.chunk = chunk;
+    a.q0 = q0; a.g_rows = g_rows; a.n_chunks = (int)n_chunks; a.n_cand = nc; a.cap = cap; a.R = R; a.min_w = (unsigned int)ucfg.min_w;
+    a.bitmap = seen ? ws.bitmap.p : nullptr; a.words = words; a.targets = has_targets ? in.targets.p : nullptr;
+    a.lists = ws.lists.p;
+    const dim3 grid((unsigned)n_chunks, (unsigned)cdiv(g_rows, R));
+    const bool one_k = Dp == UV_K;
+    int rc;
+    if (R == 32) rc = one_k ? scan_launch(uv_scan_kernel<true, 2>, grid, lds, st, a) : scan_launch(uv_scan_kernel<false, 2>, grid, lds, st, a);
+    else rc = one_k ? scan_launch(uv_scan_kernel<true, 1>, grid, lds, st, a) : scan_launch(uv_scan_kernel<false, 1>, grid, lds, st, a);
+    if (rc) return -1;
+    MergeArgs m{};
+    m.lists = ws.lists.p; m.n_chunks = (int)n_chunks; m.n_cand = nc; m.q0 = q0; m.targets = has_targets ? in.targets.p : nullptr;
+    m.stride = stride; m.out_items = o_items; m.out_w = o_w; m.out_count = o_count; m.out_tpos = o_tpos;
+    hipLaunchKernelGGL(uv_merge_kernel, dim3((unsigned)g_rows), dim3(SEL_THREADS), 0, st, m);
+    GOCTR_HIP(hipGetLastError());
+  }
+  return 0;
+}
+
+int uservec_check_recommend(const goctr_itemvec* v, const goctr_uservec_cfg* ucfg, const ItemcfRecArgs& a, int64_t n_users,
+                            int64_t n_items) {
+  const char* who = "goctr_recommend_uservec";
+  GOCTR_CHECK(v && ucfg, "%s: bad arguments", who);
+  if (uservec_check_cfg(ucfg, who)) return -1;
+  GOCTR_CHECK(v->n_items == n_items, "%s: the item vectors cover %lld items, the recsys %lld", who, (long long)v->n_items,
+              (long long)n_items);
+  return recall_check_recommend(who, a, n_users);
+}
+
+int uservec_recommend_run(const TopnScorer& sc, const goctr_itemvec* v, const goctr_uservec_cfg& ucfg, const ItemcfRecArgs& a) {
+  UvScratch ws;                               // (outlives the run, which drains the stream on every path)
+  return recall_rank_run(sc, "goctr_recommend_uservec", a, false, [&](const RecallInputs& in, const RecallRows& o, hipStream_t st) {
+    return uservec_launch(v, sc.ub_off, sc.ub_items, sc.ub_ts, in, a.targets != nullptr, a.n_req, a.rcfg, ucfg, a.rcfg.n_cand,
+                          o.items, o.w, o.count, o.tpos, nullptr, nullptr, ws, st);
+  });
+}
+
+}  // namespace goctr
+
+extern "C" {
+
+void goctr_uservec_cfg_default(goctr_uservec_cfg* c) {
+  if (!c) return;
+  c->min_w = 1; c->reserved = 0; c->chunk_items = 0;
+}
+
+int goctr_uservec_recall(goctr_itemvec* v, goctr_ubcache* c, const int32_t* users, const int64_t* ts, int64_t n_req,
+                         const goctr_recall_cfg* cfg, const goctr_uservec_cfg* ucfg, int32_t* out_items, uint32_t* out_w,
+                         int32_t* out_count, const int32_t* targets, int32_t* out_target_pos, int16_t* out_p, uint64_t* out_s) {
+  GOCTR_ENTER_H(v);
+  const char* who = "goctr_uservec_recall";
+  GOCTR_CHECK(v && c && users && cfg && ucfg && out_items && out_w && out_count, "%s: null argument", who);
+  GOCTR_SAME_ENGINE(v, c);
+  if (recall_check_cfg(cfg, who) || uservec_check_cfg(ucfg, who) || recall_check_users(users, n_req, c->n_users, who)) return -1;
+  hipStream_t s = engine().stream;
+  const size_t nq = (size_t)n_req, nc = (size_t)cfg->n_cand, D = (size_t)v->D;
+  RecallInputs in;
+  UvScratch ws;
+  DevBuf<int32_t> o_items, o_count, o_tpos;
+  DevBuf<unsigned int> o_w;
+  DevBuf<int16_t> o_p;
+  DevBuf<u64> o_s;
+  // the results are staged on the host so that a failing copy leaves the caller's arrays as they were
+  std::vector<int32_t> h_items(nq * nc), h_count(nq), h_tpos(nq);
+  std::vector<unsigned int> h_w(nq * nc);
+  std::vector<int16_t> h_p(out_p ? nq * D : 0);
+  std::vector<u64> h_s(out_s ? nq : 0);
+  UbRead image(c, s);                         // (behind the buffers: an error return drains the stream before they are freed)
+  if (in.stage(users, ts, targets, n_req, s)) return -1;
+  if (o_items.alloc(nq * nc, false) || o_w.alloc(nq * nc, false) || o_count.alloc(nq, false) || o_tpos.alloc(nq, false) ||
+      (out_p && o_p.alloc(nq * D, false)) || (out_s && o_s.alloc(nq, false))) return -1;
+  if (uservec_launch(v, c->off.p, c->items.p, c->ts.p, in, targets != nullptr, n_req, *cfg, *ucfg, cfg->n_cand, o_items.p, o_w.p,
+                     o_count.p, o_tpos.p, out_p ? o_p.p : nullptr, out_s ? o_s.p : nullptr, ws, s)) return -1;
+  GOCTR_HIP(hipMemcpyAsync(h_items.data(), o_items.p, sizeof(int32_t) * nq * nc, hipMemcpyDeviceToHost, s));
+  GOCTR_HIP(hipMemcpyAsync(h_w.data(), o_w.p, sizeof(unsigned int) * nq * nc, hipMemcpyDeviceToHost, s));
+  GOCTR_HIP(hipMemcpyAsync(h_count.data(), o_count.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));
+  GOCTR_HIP(hipMemcpyAsync(h_tpos.data(), o_tpos.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));
+  if (out_p) GOCTR_HIP(hipMemcpyAsync(h_p.data(), o_p.p, sizeof(int16_t) * nq * D, hipMemcpyDeviceToHost, s));
+  if (out_s) GOCTR_HIP(hipMemcpyAsync(h_s.data(), o_s.p, sizeof(u64) * nq, hipMemcpyDeviceToHost, s));
+  GOCTR_HIP(hipStreamSynchronize(s));
+  image.done();
+  memcpy(out_items, h_items.data(), sizeof(int32_t) * nq * nc);
+  memcpy(out_w, h_w.data(), sizeof(unsigned int) * nq * nc);
+  memcpy(out_count, h_count.data(), sizeof(int32_t) * nq);
+  if (out_target_pos) for (size_t q = 0; q < nq; ++q) out_target_pos[q] = targets ? h_tpos[q] : -1;
+  if (out_p) memcpy(out_p, h_p.data(), sizeof(int16_t) * nq * D);
+  if (out_s) memcpy(out_s, h_s.data(), sizeof(u64) * nq);
+  return 0;
+}
+
+}  // extern "C"

@@ -736,6 +736,79 @@ inline TopN RecommendDiverseBatch(model::CtrNet& net, RecSys& rs, const ItemCF* 
   return out;
 }
 
+// user-to-item recall (goctr_uservec_recall): every row's history pooled into one interest vector and matched against the whole
+// catalogue of `vec`; row q's first count[q] entries of items / w
+inline goctr_uservec_cfg DefaultUservecCfg() { goctr_uservec_cfg c; goctr_uservec_cfg_default(&c); return c; }
+inline void UservecRecall(const ItemVectors& vec, goctr_ubcache* cache, const std::vector<int32_t>& users, const std::vector<int64_t>& ts,
+                          const goctr_recall_cfg& cfg, std::vector<int32_t>& items, std::vector<uint32_t>& w, std::vector<int32_t>& count,
+                          const goctr_uservec_cfg& ucfg = DefaultUservecCfg()) {
+  if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("UservecRecall: one timestamp per user");
+  const size_t nq = users.size(), nc = (size_t)std::max(cfg.n_cand, 1);
+  items.resize(nq * nc); w.resize(nq * nc); count.resize(nq);
+  check(goctr_uservec_recall(vec.handle(), cache, users.data(), ts.empty() ? nullptr : ts.data(), (int64_t)nq, &cfg, &ucfg, items.data(),
+                             w.data(), count.data(), nullptr, nullptr, nullptr, nullptr));
+}
+
+// RecommendItemCFBatch with the user-vector recall as the recall stage (goctr_recommend_uservec): a candidate need not be in any
+// history item's stored list
+inline TopN RecommendVectorBatch(model::CtrNet& net, RecSys& rs, const ItemVectors& vec, const std::vector<int32_t>& users, int n = 10,
+                                 const std::vector<int64_t>& ts = {}, const goctr_recall_cfg& rcfg = ItemCF::DefaultRecallCfg(),
+                                 const goctr_uservec_cfg& ucfg = DefaultUservecCfg(), const std::vector<int32_t>& targets = {},
+                                 int64_t pass_rows = 0) {
+  const int64_t nq = (int64_t)users.size();
+  if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("RecommendVectorBatch: one timestamp per user");
+  if (!targets.empty() && targets.size() != users.size()) throw std::invalid_argument("RecommendVectorBatch: one target per user");
+  if (n < 1) throw std::invalid_argument("RecommendVectorBatch: n must be positive");
+  std::vector<int32_t> items((size_t)nq * n), count((size_t)nq);
+  std::vector<float> scores((size_t)nq * n);
+  TopN out;
+  if (!targets.empty()) out.target_rank.resize((size_t)nq);
+  check(goctr_recommend_uservec(net.Vm(), rs.handle(), vec.handle(), users.data(), ts.empty() ? nullptr : ts.data(), nq,
+                                targets.empty() ? nullptr : targets.data(), &rcfg, &ucfg, n, pass_rows, items.data(), scores.data(),
+                                count.data(), nullptr, nullptr, targets.empty() ? nullptr : out.target_rank.data(), nullptr, nullptr,
+                                nullptr, &out.n_failed));
+  out.lists.resize((size_t)nq);
+  for (int64_t q = 0; q < nq; ++q)
+    for (int j = 0; j < count[(size_t)q]; ++j)
+      out.lists[(size_t)q].push_back(ItemScore{items[(size_t)q * n + j], scores[(size_t)q * n + j]});
+  return out;
+}
+inline std::vector<ItemScore> RecommendVector(model::CtrNet& net, RecSys& rs, const ItemVectors& vec, int userId, int n, int64_t now,
+                                              const goctr_recall_cfg& rcfg = ItemCF::DefaultRecallCfg()) {
+  return RecommendVectorBatch(net, rs, vec, {userId}, n, {now}, rcfg).lists[0];
+}
+
+// RecommendBlendBatch with the user-vector recall as the caller's list (goctr_recommend_blend_uservec): ItemCF's candidates, the
+// n_vec items nearest the pooled history (written and read in HBM), then the popularity list; with `rerank` and `mcfg` the diversity
+// re-rank picks the mcfg->k returned
+inline TopN RecommendBlendVectorBatch(model::CtrNet& net, RecSys& rs, const ItemCF* icf, const Popular* pop, const ItemVectors& uv,
+                                      const std::vector<int32_t>& users, int n = 10, int n_vec = 64, const std::vector<int64_t>& ts = {},
+                                      const goctr_recall_cfg& rcfg = ItemCF::DefaultRecallCfg(), int quota_pop = 0,
+                                      const goctr_uservec_cfg& ucfg = DefaultUservecCfg(), const ItemVectors* rerank = nullptr,
+                                      const goctr_mmr_cfg* mcfg = nullptr, const std::vector<int32_t>& targets = {}, int64_t pass_rows = 0) {
+  const int64_t nq = (int64_t)users.size();
+  const int k = rerank && mcfg ? mcfg->k : n;
+  if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("RecommendBlendVectorBatch: one timestamp per user");
+  if (!targets.empty() && targets.size() != users.size()) throw std::invalid_argument("RecommendBlendVectorBatch: one target per user");
+  if ((rerank == nullptr) != (mcfg == nullptr)) throw std::invalid_argument("RecommendBlendVectorBatch: the re-rank takes vectors and cfg");
+  if (k < 1) throw std::invalid_argument("RecommendBlendVectorBatch: n must be positive");
+  std::vector<int32_t> items((size_t)nq * k), count((size_t)nq);
+  std::vector<float> scores((size_t)nq * k);
+  TopN out;
+  if (!targets.empty()) out.target_rank.resize((size_t)nq);
+  check(goctr_recommend_blend_uservec(net.Vm(), rs.handle(), icf ? icf->handle() : nullptr, pop ? pop->handle() : nullptr, users.data(),
+                                      ts.empty() ? nullptr : ts.data(), nq, targets.empty() ? nullptr : targets.data(), uv.handle(), &ucfg,
+                                      n_vec, &rcfg, quota_pop, rerank ? rerank->handle() : nullptr, mcfg, k, pass_rows, items.data(),
+                                      scores.data(), count.data(), nullptr, nullptr, nullptr,
+                                      targets.empty() ? nullptr : out.target_rank.data(), nullptr, nullptr, nullptr, nullptr, &out.n_failed,
+                                      nullptr, nullptr, nullptr));
+  out.lists.resize((size_t)nq);
+  for (int64_t q = 0; q < nq; ++q)
+    for (int j = 0; j < count[(size_t)q]; ++j)
+      out.lists[(size_t)q].push_back(ItemScore{items[(size_t)q * k + j], scores[(size_t)q * k + j]});
+  return out;
+}
+
 // List-quality figures of returned lists (goctr_metrics_lists): `items` holds nq rows of k entries, `count` the entries in use
 // per row (empty: every row is full); vec / pop may be null (include/goctr.h says which figures are then 0 or NaN)
 struct ListQuality {

@@ -17,6 +17,10 @@ device, so that a row without history still gets candidates (tests/popular_ref.p
 ``ItemVectors`` holds the catalogue's quantised vectors (and optionally a group id per item) in HBM, and ``rerank_mmr`` picks k of
 every row's scored candidates greedily, trading relevance against similarity to what it has picked, with a cap per group
 (tests/mmr_ref.py is the host restatement).  ``recommend.RecommendDiverse`` runs it as the last step of RecommendBlend.
+
+``ItemVectors.recall_users`` is the user-to-item channel: a request row's history is pooled into one interest vector and matched
+against the whole catalogue, so an item close to many history items but in no single item's stored list is still found
+(tests/uservec_ref.py is the host restatement).  ``recommend.RecommendVector`` ranks the result with the model.
 """
 from __future__ import annotations
 
@@ -34,6 +38,7 @@ _NBR_FIELDS = {"n_nbr", "min_w", "pass_items"}
 _SWING_FIELDS = {"max_len", "max_users", "alpha_q", "n_nbr", "min_pairs", "seed", "pair_budget"}
 _MMR_FIELDS = {"k", "pool", "lambda_q", "max_per_group"}
 _LIST_FIELDS = {"k", "tail_cnt"}
+_USERVEC_FIELDS = {"min_w", "chunk_items"}
 
 
 def make_cfg(**kw) -> capi.ItemcfCfg:
@@ -78,6 +83,14 @@ def make_mmr_cfg(**kw) -> capi.MmrCfg:
     if unknown:
         raise TypeError(f"goctr_mmr_cfg has no field {sorted(unknown)}")
     return capi.default_mmr_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
+
+
+def make_uservec_cfg(**kw) -> capi.UservecCfg:
+    """goctr_uservec_cfg from keywords (integers; the ranges are the library's to refuse)"""
+    unknown = set(kw) - _USERVEC_FIELDS
+    if unknown:
+        raise TypeError(f"goctr_uservec_cfg has no field {sorted(unknown)}")
+    return capi.default_uservec_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
 
 
 def make_list_cfg(**kw) -> capi.ListCfg:
@@ -360,6 +373,35 @@ class ItemVectors:
             out["groups"] = np.empty(self.n_items, np.int32)
         capi.check(capi.load().goctr_itemvec_export(self._h, capi.ptr(out["q"], C.c_int16), capi.ptr(out["valid"], C.c_uint8),
                                                     capi.ptr(out.get("groups"), C.c_int32)))
+        return out
+
+    def recall_users(self, ubc, users, ts=None, targets=None, cfg: capi.RecallCfg | None = None,
+                     ucfg: capi.UservecCfg | None = None, validate=False, **kw) -> dict:
+        """goctr_uservec_recall over DENSE user rows of ``ubc``'s image: the pooled history vector of every row against the whole
+        catalogue.  ``kw``: goctr_recall_cfg fields and goctr_uservec_cfg's (min_w, chunk_items).  dict(items int32 [nq, n_cand]
+        (-1 = unused), w uint32 [nq, n_cand], count int32 [nq], target_pos int32 [nq] when targets are given; with ``validate``
+        p int16 [nq, D] (the request vectors) and s uint64 [nq] (the pooled vectors' squared lengths))"""
+        ukw = {k: kw.pop(k) for k in list(kw) if k in _USERVEC_FIELDS}
+        if (cfg is not None and kw) or (ucfg is not None and ukw):
+            raise TypeError("give either a cfg or its keywords")
+        cfg = cfg if cfg is not None else make_recall_cfg(**kw)
+        ucfg = ucfg if ucfg is not None else make_uservec_cfg(**ukw)
+        users, ts, targets = request_columns(users, ts, targets)
+        nq, nc = users.size, max(int(cfg.n_cand), 1)
+        out = dict(items=np.full((nq, nc), -2, np.int32), w=np.full((nq, nc), 0xffffffff, np.uint32), count=np.full(nq, -2, np.int32))
+        tpos = np.full(nq, -2, np.int32) if targets is not None else None
+        p = np.full((nq, self.D), -2, np.int16) if validate else None
+        s = np.full(nq, 0xffffffffffffffff, np.uint64) if validate else None
+        h = None if ubc is None else ubc.device() if hasattr(ubc, "device") else ubc
+        capi.check(capi.load().goctr_uservec_recall(self._h, h, capi.ptr(users, C.c_int32), capi.ptr(ts, C.c_int64), C.c_int64(nq),
+                                                    C.byref(cfg), C.byref(ucfg), capi.ptr(out["items"], C.c_int32),
+                                                    capi.ptr(out["w"], C.c_uint32), capi.ptr(out["count"], C.c_int32),
+                                                    capi.ptr(targets, C.c_int32), capi.ptr(tpos, C.c_int32), capi.ptr(p, C.c_int16),
+                                                    capi.ptr(s, C.c_uint64)))
+        if tpos is not None:
+            out["target_pos"] = tpos
+        if validate:
+            out["p"], out["s"] = p, s
         return out
 
     def close(self):

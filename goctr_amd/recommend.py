@@ -1034,3 +1034,196 @@ def DiversityTradeoff(model: Predictor, icf, vectors, lambdas=(256, 224, 192, 12
     finally:
         if own:
             pop.close()
+
+
+def _split_uservec_kw(recall_cfg, ucfg, kw):
+    """(goctr_recall_cfg, goctr_uservec_cfg) from cfgs or keywords (min_w and chunk_items are the latter's)"""
+    from .recall import _USERVEC_FIELDS, make_recall_cfg, make_uservec_cfg
+    ukw = {k: kw.pop(k) for k in list(kw) if k in _USERVEC_FIELDS}
+    if (recall_cfg is not None and kw) or (ucfg is not None and ukw):
+        raise TypeError("give either a cfg or its keywords")
+    return (recall_cfg if recall_cfg is not None else make_recall_cfg(**kw)), (ucfg if ucfg is not None else make_uservec_cfg(**ukw))
+
+
+def uservec(model: Predictor, vectors, users, ts=None, targets=None, k=10, pass_rows=0, validate=False, recall_cfg=None, ucfg=None,
+            **recall_kw):
+    """goctr_recommend_uservec over DENSE indices: ``itemcf`` with the user-vector recall over ``vectors`` (recall.ItemVectors) as the
+    recall stage; the same dict.  ``recall_kw``: goctr_recall_cfg fields and goctr_uservec_cfg's (min_w, chunk_items).  What
+    RecommendVector / RecommendVectorBatch / EvaluateLeaveOneOutVector call."""
+    from .recall import request_columns
+    cfg, ucfg = _split_uservec_kw(recall_cfg, ucfg, recall_kw)
+    rs = model.recSys
+    users, ts, targets = request_columns(users, ts, targets)
+    nq, kk, nc = users.size, max(int(k), 1), max(int(cfg.n_cand), 1)
+    out = dict(items=np.full((nq, kk), -2, np.int32), scores=np.full((nq, kk), np.nan, np.float32), count=np.full(nq, -2, np.int32),
+               cand_count=np.full(nq, -2, np.int32))
+    tpos = np.full(nq, -2, np.int32) if targets is not None else None
+    rank = np.full(nq, -2, np.int64) if targets is not None else None
+    cand_items = np.full((nq, nc), -2, np.int32) if validate else None
+    cand_w = np.full((nq, nc), 0xffffffff, np.uint32) if validate else None
+    cand_scores = np.full((nq, nc), np.nan, np.float32) if validate else None
+    nf = C.c_int64(-2)
+    capi.check(capi.load().goctr_recommend_uservec(
+        model.net._h, rs._h, vectors._h, capi.ptr(users, C.c_int32), capi.ptr(ts, C.c_int64), C.c_int64(nq),
+        capi.ptr(targets, C.c_int32), C.byref(cfg), C.byref(ucfg), C.c_int32(int(k)), C.c_int64(int(pass_rows)),
+        capi.ptr(out["items"], C.c_int32), capi.ptr(out["scores"], C.c_float), capi.ptr(out["count"], C.c_int32),
+        capi.ptr(out["cand_count"], C.c_int32), capi.ptr(tpos, C.c_int32), capi.ptr(rank, C.c_int64), capi.ptr(cand_items, C.c_int32),
+        capi.ptr(cand_w, C.c_uint32), capi.ptr(cand_scores, C.c_float), C.byref(nf)))
+    out["n_failed"] = nf.value
+    if targets is not None:
+        out["target_pos"], out["target_rank"] = tpos, rank
+    if validate:
+        out["cand_items"], out["cand_w"], out["cand_scores"] = cand_items, cand_w, cand_scores
+    return out
+
+
+def blend_uservec(model: Predictor, icf, pop, uv, users, ts=None, targets=None, n_vec=64, quota_pop=0, k=10, vectors=None, pool=64,
+                  lambda_q=192, max_per_group=0, pass_rows=0, validate=False, recall_cfg=None, ucfg=None, **recall_kw):
+    """goctr_recommend_blend_uservec over DENSE indices: ``blend`` whose part X is the user-vector recall over ``uv``
+    (recall.ItemVectors), ``n_vec`` entries a row, written and read on the device; with ``vectors`` the MMR selection of ``diverse``
+    is the last step (pool, lambda_q, max_per_group).  The dict of ``blend``, or of ``diverse``.  What RecommendBlendVectorBatch
+    and EvaluateLeaveOneOutBlendVector call."""
+    from .recall import _as_int, make_mmr_cfg, request_columns
+    cfg, ucfg = _split_uservec_kw(recall_cfg, ucfg, recall_kw)
+    rs = model.recSys
+    users, ts, targets = request_columns(users, ts, targets)
+    nq, kk, nc = users.size, max(int(k), 1), max(int(cfg.n_cand), 1)
+    mcfg = None if vectors is None else make_mmr_cfg(k=k, pool=pool, lambda_q=lambda_q, max_per_group=max_per_group)
+    out = dict(items=np.full((nq, kk), -2, np.int32), scores=np.full((nq, kk), np.nan, np.float32), src=np.full((nq, kk), 254, np.uint8),
+               count=np.full(nq, -2, np.int32), cand_count=np.full(nq, -2, np.int32))
+    tpos = np.full(nq, -2, np.int32) if targets is not None else None
+    rank = np.full(nq, -2, np.int64) if targets is not None else None
+    cand_items = np.full((nq, nc), -2, np.int32) if validate else None
+    cand_w = np.full((nq, nc), 0xffffffff, np.uint32) if validate else None
+    cand_scores = np.full((nq, nc), np.nan, np.float32) if validate else None
+    cand_src = np.full((nq, nc), 254, np.uint8) if validate else None
+    obj = np.full((nq, kk), -2, np.int32) if mcfg is not None else None
+    pen = np.full((nq, kk), 0xffffffff, np.uint32) if mcfg is not None else None
+    tplace = np.full(nq, -2, np.int32) if mcfg is not None and targets is not None else None
+    nf = C.c_int64(-2)
+    capi.check(capi.load().goctr_recommend_blend_uservec(
+        model.net._h, rs._h, icf._h if icf is not None else None, pop._h if pop is not None else None, capi.ptr(users, C.c_int32),
+        capi.ptr(ts, C.c_int64), C.c_int64(nq), capi.ptr(targets, C.c_int32), uv._h, C.byref(ucfg), C.c_int32(_as_int("n_vec", n_vec)),
+        C.byref(cfg), C.c_int32(_as_int("quota_pop", quota_pop)), vectors._h if vectors is not None else None,
+        C.byref(mcfg) if mcfg is not None else None, C.c_int32(int(k)), C.c_int64(int(pass_rows)),
+        capi.ptr(out["items"], C.c_int32), capi.ptr(out["scores"], C.c_float), capi.ptr(out["count"], C.c_int32),
+        capi.ptr(out["src"], C.c_uint8), capi.ptr(out["cand_count"], C.c_int32), capi.ptr(tpos, C.c_int32), capi.ptr(rank, C.c_int64),
+        capi.ptr(cand_items, C.c_int32), capi.ptr(cand_w, C.c_uint32), capi.ptr(cand_scores, C.c_float), capi.ptr(cand_src, C.c_uint8),
+        C.byref(nf), capi.ptr(obj, C.c_int32), capi.ptr(pen, C.c_uint32), capi.ptr(tplace, C.c_int32)))
+    out["n_failed"] = nf.value
+    if mcfg is not None:
+        out["obj"], out["pen"] = obj, pen
+        if targets is not None:
+            out["target_place"] = tplace
+    if targets is not None:
+        out["target_pos"], out["target_rank"] = tpos, rank
+    if validate:
+        out["cand_items"], out["cand_w"], out["cand_scores"], out["cand_src"] = cand_items, cand_w, cand_scores, cand_src
+    return out
+
+
+def _request_rows(model, userIds, now):
+    """dense user rows and one timestamp per row for a batch of user ids (an unknown user raises like Rank's failing first key)"""
+    rs = model.recSys
+    userIds = list(userIds)
+    users = np.array([rs.user_index(u) for u in userIds], np.int32)
+    if users.size and (users < 0).any():
+        bad = userIds[int(np.flatnonzero(users < 0)[0])]
+        raise SampleVectorError(f"get sample vector error: user {bad} has no features")
+    ts = np.broadcast_to(np.asarray(int(time.time()) if now is None else now, np.int64), users.shape)
+    return users, ts
+
+
+def _item_scores(model, r, nq):
+    raw = model.recSys._row_keys
+    return [[ItemScore(int(raw[r["items"][q, j]]), float(r["scores"][q, j])) for j in range(int(r["count"][q]))] for q in range(nq)]
+
+
+def RecommendVectorBatch(model: Predictor, vectors, userIds, n=10, now=None, **recall_kw):
+    """RecommendVector for several users in one device call: [[ItemScore]] in the order of userIds.  ``now``: one timestamp for all,
+    or one per user.  A user without history (or whose history's vectors cancel) gets an empty list."""
+    users, ts = _request_rows(model, userIds, now)
+    if users.size == 0:
+        return []
+    try:
+        r = uservec(model, vectors, users, ts, None, n, **recall_kw)
+    except capi.GoctrError as e:
+        raise SampleVectorError(str(e)) from None
+    return _item_scores(model, r, users.size)
+
+
+def RecommendVector(model: Predictor, vectors, userId: int, n=10, now=None, **recall_kw):
+    """EXTENSION -- user-to-item recall, then rank: the vectors (``vectors``: BuildItemVectors) of the user's newest ``history``
+    behaviours at or before ``now`` are summed into one interest vector, EVERY item of the catalogue is a candidate by its quantised
+    cosine to it (at least ``min_w`` / 65536), the ``n_cand`` closest are scored by the model and the ``n`` best come back.  Unlike
+    RecommendItemCF a candidate need not be in any history item's stored neighbour list; unlike Recommend the model scores n_cand
+    rows, not the catalogue."""
+    return RecommendVectorBatch(model, vectors, [userId], n, now, **recall_kw)[0]
+
+
+def _loo_figures(r, targets, n_items, k, n_cand):
+    """EvaluateLeaveOneOutRecall's figures from a call's target_pos / target_rank"""
+    ok = (targets >= 0) & (targets < n_items)
+    pos, rank = r["target_pos"][ok].astype(np.int64), r["target_rank"][ok].astype(np.float64)
+    n = int(ok.sum())
+    hit = (rank >= 0) & (rank < k)
+    nan = float("nan")
+    return dict(users=n, skipped=int((~ok).sum()), k=int(k), n_cand=int(n_cand),
+                recall=float(np.mean(pos >= 0)) if n else nan,
+                hit_rate=float(np.mean(hit)) if n else nan,
+                ndcg=float(np.mean(np.where(hit, 1.0 / np.log2(np.where(hit, rank, 0.0) + 2.0), 0.0))) if n else nan)
+
+
+def EvaluateLeaveOneOutVector(model: Predictor, vectors, k=10, sample_kw=None, details=False, pass_rows=0, **recall_kw):
+    """EvaluateLeaveOneOutRecall's protocol and figures with the user-vector recall as the recall stage (goctr_recommend_uservec):
+    every user's newest entry is held out (key timestamp ts - 1, DROP_SEEN_BEFORE unless ``exclude`` says otherwise) and the pooled
+    vector of the history the key sees proposes ``n_cand`` candidates from the whole catalogue.  ``vectors`` should come from an
+    embedding trained without the held-out entries for an honest figure; that is the caller's choice."""
+    users, targets, ts = _held_out_rows(model, sample_kw)
+    recall_kw.setdefault("exclude", "before")
+    cfg, ucfg = _split_uservec_kw(None, None, recall_kw)
+    r = uservec(model, vectors, users, ts, targets, k, pass_rows, recall_cfg=cfg, ucfg=ucfg)
+    out = _loo_figures(r, targets, model.recSys.item_table.shape[0], k, cfg.n_cand)
+    if details:
+        out.update(target_pos=r["target_pos"], rank=r["target_rank"], user_index=users, target_index=targets, ts=ts)
+    return out
+
+
+def RecommendBlendVectorBatch(model: Predictor, icf, pop, uv, userIds, n=10, now=None, n_vec=64, quota_pop=0, vectors=None, pool=64,
+                              lambda_q=192, max_per_group=0, **recall_kw):
+    """EXTENSION -- RecommendBlendBatch with the user-vector recall as the caller's list: ItemCF's candidates, then the ``n_vec``
+    items closest to the user's pooled history vector (``uv``: BuildItemVectors), then the popularity list; with ``vectors`` the
+    diversity re-rank of RecommendDiverse picks the ``n`` returned.  One device call; the vector channel's list never leaves HBM."""
+    users, ts = _request_rows(model, userIds, now)
+    if users.size == 0:
+        return []
+    try:
+        r = blend_uservec(model, icf, pop, uv, users, ts, None, n_vec, quota_pop, n, vectors, pool, lambda_q, max_per_group, **recall_kw)
+    except capi.GoctrError as e:
+        raise SampleVectorError(str(e)) from None
+    return _item_scores(model, r, users.size)
+
+
+def EvaluateLeaveOneOutBlendVector(model: Predictor, icf, uv, pop=None, k=10, n_vec=64, sample_kw=None, details=False, pass_rows=0,
+                                   quota_pop=0, pop_kw=None, **recall_kw):
+    """EvaluateLeaveOneOutBlend's protocol and figures with the user-vector recall (``uv``, ``n_vec`` entries a row) as the blend's
+    second channel (goctr_recommend_blend_uservec, best k by score); ``pop`` None builds the popularity list below the held-out
+    events as there."""
+    rs = model.recSys
+    users, targets, ts = _held_out_rows(model, sample_kw)
+    own = pop is None
+    if own:
+        pkw = dict(pop_kw or {})
+        pkw.setdefault("ts_hi", int(ts.min()))            # as EvaluateLeaveOneOutBlend: nothing at or after a held-out event counts
+        pop = BuildPopular(rs, **pkw)
+    recall_kw.setdefault("exclude", "before")
+    cfg, ucfg = _split_uservec_kw(None, None, recall_kw)
+    try:
+        r = blend_uservec(model, icf, pop, uv, users, ts, targets, n_vec, quota_pop, k, pass_rows=pass_rows, recall_cfg=cfg, ucfg=ucfg)
+    finally:
+        if own:
+            pop.close()
+    out = _loo_figures(r, targets, rs.item_table.shape[0], k, cfg.n_cand)
+    if details:
+        out.update(target_pos=r["target_pos"], rank=r["target_rank"], src=r["src"], user_index=users, target_index=targets, ts=ts)
+    return out

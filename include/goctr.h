@@ -823,6 +823,82 @@ int goctr_metrics_lists(goctr_itemvec* v /* may be NULL */, goctr_popular* pop /
                         goctr_list_metrics* out, goctr_list_row* rows /* [n_req] or NULL */,
                         uint32_t* expo /* [n_items] or NULL */, uint32_t* sim /* [n_req,k,k] or NULL */);
 
+/* ---- User-vector recall: one interest vector per request row against the whole catalogue (no reference counterpart).  The three
+ * item-to-item sources reach a user through the stored lists of the history items, so a candidate must sit in the stored top n_nbr
+ * of at least one of them.  Here the history is pooled into ONE vector and every item of a goctr_itemvec is a candidate: an item
+ * moderately close to many history items, but in no single item's list, is found.  Every output is defined bit for bit
+ * (tests/uservec_ref.py is the host restatement): after one pinned float64 quantisation all arithmetic is integer.
+ *
+ * goctr_uservec_recall, for request row q over the ONE image of the cache the call holds:
+ *   history        exactly goctr_itemcf_recall's with n_items = the vector handle's: the entries TimeSeq.Filter(ts[q], 0) keeps
+ *                  (ts NULL or 0 = all), of those the valid ones (0 <= item < n_items), of those the first `history` in sequence
+ *                  order.  A repeated item counts each time; an item whose vector is invalid takes a place, its q is 0
+ *   pooled vector  u_d = the sum over the history entries of q[item][d] (q: the handle's int16 rows, 256 hi + lo) as a
+ *                  mathematical integer: |u_d| <= 2^22, and the sum of u_d^2 stays below 2^45
+ *   request vector p = the quantisation rule of "Item neighbours from vectors" (s, valid, q_d) applied to u as a vector of
+ *                  doubles, with the same pinned operations.  s is exact, so the row has a vector iff u != 0; r = sqrt(s) >=
+ *                  |u_d|, hence |p_d| <= 16384.  A row with an empty history or with u = 0 has no vector and returns count 0 (a
+ *                  history of v and -v cancels exactly: rint is odd)
+ *   weight         w(q,j) = dot(p, q_j) >> 12 when the dot is positive, else 0: the rule and the scale of
+ *                  goctr_itemcf_build_vectors and of the MMR similarity; |dot| < 2.7e8 fits int32
+ *   candidates     every j with w >= ucfg->min_w that is not seen.  An invalid item row has w = 0 and never qualifies.  Seen is
+ *                  goctr_itemcf_recall's rule under cfg->exclude, the target exemption included; under KEEP_SEEN a history item
+ *                  is a candidate like any other
+ *   order          w descending, then item ascending; the first cfg->n_cand are kept
+ *   outputs        out_items / out_w [n_req,n_cand] (padding -1 / 0), out_count, out_target_pos (may be NULL) as
+ *                  goctr_itemcf_recall's; the validation outputs out_p [n_req,D] int16 (the request vector, zeros for a row
+ *                  without one) and out_s [n_req] (the sum of u_d^2) may each be NULL
+ *   refused        (-1, nothing touched) goctr_itemcf_recall's refusals; a NULL handle or a NULL cache; min_w outside 1 .. 65536;
+ *                  reserved != 0; chunk_items neither 0 nor in 64 .. 2^22; a handle on another engine than the cache's
+ * The catalogue is scanned in column chunks by row tiles, and request rows are taken in groups whose seen bitmaps and partial
+ * lists fit a scratch budget; no output byte depends on chunk_items, on how rows are grouped, on the arrival order of threads or
+ * on a tile size.  Host arrays, the engine stream and the engine lock, like goctr_itemcf_recall. */
+typedef struct {
+  int32_t min_w;        /* 1 .. 65536, units of 2^-16                          default 1 */
+  int32_t reserved;     /* must be 0 */
+  int64_t chunk_items;  /* 0 = the implementation's choice, else 64 .. 2^22:
+                           catalogue items per column chunk (a tiling knob)    default 0 */
+} goctr_uservec_cfg;
+void goctr_uservec_cfg_default(goctr_uservec_cfg* c);
+int  goctr_uservec_recall(goctr_itemvec* v, goctr_ubcache* c, const int32_t* users, const int64_t* ts /* NULL = 0 */,
+                          int64_t n_req, const goctr_recall_cfg* cfg, const goctr_uservec_cfg* ucfg,
+                          int32_t* out_items /*[n_req,n_cand]*/, uint32_t* out_w /*[n_req,n_cand]*/, int32_t* out_count /*[n_req]*/,
+                          const int32_t* targets /*[n_req] or NULL*/, int32_t* out_target_pos /*[n_req] or NULL*/,
+                          int16_t* out_p /*[n_req,D] or NULL*/, uint64_t* out_s /*[n_req] or NULL*/);
+
+/* goctr_recommend_uservec: goctr_recommend_itemcf with the recall above as its recall stage, over the recsys's cache image.  The
+ * outputs and every documented property of that call hold unchanged: scores bit-identical to goctr_batch_predict below 8192 rows
+ * per pass, failed candidates, out_target_rank, and a recsys without a cache returns empty rows.
+ *   refused        goctr_recommend_itemcf's refusals, the ucfg refusals above, and item vectors whose n_items differs from the
+ *                  recsys's */
+int goctr_recommend_uservec(goctr_model* m, goctr_recsys* r, goctr_itemvec* v,
+                            const int32_t* users, const int64_t* ts /* NULL = 0 */, int64_t n_req,
+                            const int32_t* targets /* [n_req] or NULL */, const goctr_recall_cfg* recall_cfg,
+                            const goctr_uservec_cfg* ucfg, int32_t k, int64_t pass_rows,
+                            int32_t* out_items /* [n_req,k] */, float* out_scores /* [n_req,k] */, int32_t* out_count,
+                            int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank,
+                            int32_t* cand_items, uint32_t* cand_w, float* cand_scores, int64_t* n_failed);
+
+/* goctr_recommend_blend_uservec: the blend with the user-vector recall as its part X, defined by composition.  The result equals
+ * goctr_recommend_blend (v and cfg both NULL: the best k by score) or goctr_recommend_blend_mmr (v and cfg both given; k is then
+ * ignored, cfg->k holds) called with n_extra = n_vec and extra row q = the items of goctr_uservec_recall's row q for the same
+ * users, ts and targets under {recall_cfg->history, n_cand = n_vec, recall_cfg->exclude} and ucfg, over the same cache image,
+ * padded with -1.  The list never leaves the device: the recall writes into the buffer the blend's part X reads.  Items from this
+ * channel carry source 1.  Without the re-rank out_obj, out_pen and out_target_place are not touched.
+ *   refused        goctr_recommend_blend's (or _blend_mmr's) refusals; the ucfg refusals above; a NULL uv or ucfg; n_vec outside
+ *                  1 .. 1024; v without cfg or cfg without v; uv's n_items different from the recsys's
+ * A recsys without a cache has no history: part X is empty. */
+int goctr_recommend_blend_uservec(goctr_model* m, goctr_recsys* r, goctr_itemcf* icf /* may be NULL */, goctr_popular* pop /* may be NULL */,
+                                  const int32_t* users, const int64_t* ts /* NULL = 0 */, int64_t n_req,
+                                  const int32_t* targets /* [n_req] or NULL */,
+                                  goctr_itemvec* uv, const goctr_uservec_cfg* ucfg, int32_t n_vec /* 1 .. 1024 */,
+                                  const goctr_recall_cfg* recall_cfg, int32_t quota_pop /* 0 .. recall_cfg->n_cand */,
+                                  goctr_itemvec* v /* or NULL */, const goctr_mmr_cfg* cfg /* or NULL */, int32_t k, int64_t pass_rows,
+                                  int32_t* out_items /* [n_req,k] */, float* out_scores /* [n_req,k] */, int32_t* out_count,
+                                  uint8_t* out_src, int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank,
+                                  int32_t* cand_items, uint32_t* cand_w, float* cand_scores, uint8_t* cand_src, int64_t* n_failed,
+                                  int32_t* out_obj, uint32_t* out_pen, int32_t* out_target_place);
+
 /* The replica a multi-device training call (cfg.devices = n) keeps on engine `rank` (rank 0: the handle itself); NULL before
  * the first such call.  Borrowed: owned by the handle it was asked from.  For checks that the replicas are bit-identical
  * (tests, bench.py's replica checksum) -- every entry point works on it, on its own engine. */
