@@ -186,6 +186,12 @@ class UservecCfg(C.Structure):
     _fields_ = [("min_w", C.c_int32), ("reserved", C.c_int32), ("chunk_items", C.c_int64)]
 
 
+class UservecMultiCfg(C.Structure):
+    """goctr_uservec_multi_cfg (include/goctr.h)"""
+    _fields_ = [("min_w", C.c_int32), ("max_interests", C.c_int32), ("iters", C.c_int32), ("split_w", C.c_int32),
+                ("mix", C.c_int32), ("reserved", C.c_int32), ("chunk_items", C.c_int64)]
+
+
 class ListCfg(C.Structure):
     """goctr_list_cfg (include/goctr.h)"""
     _fields_ = [("k", C.c_int32), ("tail_cnt", C.c_int32)]
@@ -210,6 +216,7 @@ class ListMetrics(C.Structure):
 TOPN_KEEP_SEEN, TOPN_DROP_ALL_SEEN, TOPN_DROP_SEEN_BEFORE = 0, 1, 2   # goctr_topn_cfg.exclude
 NS_UNIFORM, NS_POPULARITY, NS_POPULARITY_075 = 0, 1, 2      # goctr_negsample_cfg.weighting
 NS_ALL, NS_NEWEST, NS_ALL_BUT_NEWEST = 0, 1, 2              # goctr_negsample_cfg.which
+UVMIX_MAX, UVMIX_QUOTA = 0, 1                               # goctr_uservec_multi_cfg.mix
 
 
 # every symbol include/goctr.h declares (tests/test_capi_symbols.py checks the list against the header)
@@ -257,6 +264,7 @@ SYMBOLS = [
     "goctr_list_cfg_default", "goctr_metrics_lists",
     "goctr_swing_cfg_default", "goctr_itemcf_build_swing",
     "goctr_uservec_cfg_default", "goctr_uservec_recall", "goctr_recommend_uservec", "goctr_recommend_blend_uservec",
+    "goctr_uservec_multi_cfg_default", "goctr_uservec_interests", "goctr_uservec_recall_multi", "goctr_recommend_uservec_multi",
 ]
 
 _lib = None
@@ -281,7 +289,7 @@ def load() -> C.CDLL:
                      "goctr_itemcf_cfg_default", "goctr_recall_cfg_default", "goctr_itemcf_destroy", "goctr_curve_cfg_default",
                      "goctr_multiclass_cfg_default", "goctr_popular_cfg_default", "goctr_popular_destroy",
                      "goctr_itemnbr_cfg_default", "goctr_mmr_cfg_default", "goctr_itemvec_destroy", "goctr_list_cfg_default",
-                     "goctr_swing_cfg_default", "goctr_uservec_cfg_default"):
+                     "goctr_swing_cfg_default", "goctr_uservec_cfg_default", "goctr_uservec_multi_cfg_default"):
             getattr(_lib, name).restype = None
         _bm = C.POINTER(BinaryMetrics)
         _lib.goctr_metrics_binary.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, _bm]
@@ -387,6 +395,15 @@ def load() -> C.CDLL:
                                                        C.c_void_p, _uv, C.c_int32, C.POINTER(RecallCfg), C.c_int32, C.c_void_p, _mmr,
                                                        C.c_int32, C.c_int64, _i32, _f32, _i32, _u8, _i32, _i32, _i64, _i32, _u32, _f32,
                                                        _u8, _i64, _i32, _u32, _i32]
+        _um = C.POINTER(UservecMultiCfg)
+        _lib.goctr_uservec_multi_cfg_default.argtypes = [_um]
+        _lib.goctr_uservec_interests.argtypes = [C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, C.POINTER(RecallCfg), _um, _i32,
+                                                 C.POINTER(C.c_int8), _i32, C.POINTER(C.c_int16), _u64]
+        _lib.goctr_uservec_recall_multi.argtypes = [C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, C.POINTER(RecallCfg), _um, _i32, _u32,
+                                                    _i32, _i32, _i32, C.POINTER(C.c_int16), _u64, _u8, _i32]
+        _lib.goctr_recommend_uservec_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32,
+                                                       C.POINTER(RecallCfg), _um, C.c_int32, C.c_int64, _i32, _f32, _i32, _i32, _i32,
+                                                       _i64, _i32, _u32, _f32, _i64, _u8, _i32]
         _lib.goctr_list_cfg_default.argtypes = [C.POINTER(ListCfg)]
         _lib.goctr_metrics_lists.argtypes = [C.c_void_p, C.c_void_p, _i32, _i32, C.c_int64, C.c_int64, C.POINTER(ListCfg),
                                              C.POINTER(ListMetrics), C.POINTER(ListRow), _u32, _u32]
@@ -563,6 +580,14 @@ def default_mmr_cfg(**kw) -> MmrCfg:
 def default_uservec_cfg(**kw) -> UservecCfg:
     c = UservecCfg()
     load().goctr_uservec_cfg_default(C.byref(c))
+    for k, v in kw.items():
+        setattr(c, k, v)
+    return c
+
+
+def default_uservec_multi_cfg(**kw) -> UservecMultiCfg:
+    c = UservecMultiCfg()
+    load().goctr_uservec_multi_cfg_default(C.byref(c))
     for k, v in kw.items():
         setattr(c, k, v)
     return c

@@ -20,6 +20,7 @@
 #include "topn.h"
 #include "ubcache.h"
 #include "uservec.h"
+#include "uservec_multi.h"
 
 // ------------------------------------------------------------------ serving: recommend.BatchPredict / Rank / Predict
 // recommend/rcmd.go:248-337: sample keys -> GetSampleVector rows -> PredictAbstract.Predict -> scores, called from concurrent
@@ -631,6 +632,26 @@ int goctr_recommend_uservec(goctr_model* m, goctr_recsys* r, goctr_itemvec* v, c
                         out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed};
   if (uservec_check_recommend(v, ucfg, a, r->n_users, r->n_items)) return -1;
   return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return uservec_recommend_run(sc, v, *ucfg, a); });
+}
+
+// goctr_recommend_uservec with the multi-interest recall (uservec_multi.hip) as the recall stage; the candidates' owner ranks ride
+// in the driver's source column
+int goctr_recommend_uservec_multi(goctr_model* m, goctr_recsys* r, goctr_itemvec* v, const int32_t* users, const int64_t* ts,
+                                  int64_t n_req, const int32_t* targets, const goctr_recall_cfg* recall_cfg,
+                                  const goctr_uservec_multi_cfg* mcfg, int32_t k, int64_t pass_rows, int32_t* out_items,
+                                  float* out_scores, int32_t* out_count, int32_t* out_cand_count, int32_t* out_target_pos,
+                                  int64_t* out_target_rank, int32_t* cand_items, uint32_t* cand_w, float* cand_scores,
+                                  int64_t* n_failed, uint8_t* cand_interest, int32_t* out_n_int) {
+  EngineScope on(handle_engine(m));
+  if (require_engine()) return -1;
+  GOCTR_CHECK(m && r && v && recall_cfg && mcfg, "goctr_recommend_uservec_multi: bad arguments");
+  GOCTR_SAME_ENGINE(m, r);
+  GOCTR_SAME_ENGINE(m, v);
+  if (check_recsys_dims("goctr_recommend_uservec_multi", m, r)) return -1;
+  const ItemcfRecArgs a{users, ts, n_req, targets, *recall_cfg, k, pass_rows, out_items, out_scores, out_count, out_cand_count,
+                        out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed, nullptr, cand_interest};
+  if (uservec_multi_check_recommend(v, mcfg, a, r->n_users, r->n_items)) return -1;
+  return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return uservec_multi_recommend_run(sc, v, *mcfg, a, out_n_int); });
 }
 
 // goctr_recommend_blend / _blend_mmr with the user-vector recall writing part X's list on the device

@@ -14,10 +14,31 @@ struct UvScratch {
   DevBuf<unsigned long long> lists;             // [group rows, chunks, n_cand] keys descending, 0 = unused
 };
 
+constexpr int UV_K = 64;                        // the MFMA's K: itemvec.h's IV_K, a plane row's padding (uservec.hip asserts it)
+constexpr int UV_PAD_ROWS = 32;                 // zero rows behind the request planes: partial row tiles read them
+using uv_i32x4 = __attribute__((ext_vector_type(4))) int;
+
+// THE fragment rule of every int8 product over planes laid out like the item planes: lane l takes the 16 bytes of `row` at K step
+// ks from (l >> 4) * 16 on, as the A and as the B operand alike, so the k order of the instruction cannot show
+__device__ inline uv_i32x4 uv_frag(const signed char* plane, long long row, int Dp, int ks, int lane) {
+  return *reinterpret_cast<const uv_i32x4*>(plane + (size_t)row * Dp + ks * UV_K + (lane >> 4) * 16);
+}
+
 // the cfg's ranges (sets the error text)
 int uservec_check_cfg(const goctr_uservec_cfg* ucfg, const char* who);
 
-// pool, seen, scan and merge over nq rows on `st`: row q's first cfg.n_cand slots at q * stride (stride >= cfg.n_cand) of o_items /
+// the device columns of the rows a scan runs over: one user, ts and (targets may be null) target per request plane
+struct UvCols { const int32_t* users; const long long* ts; const int32_t* targets; };
+
+// uservec_launch's second half -- seen, scan and merge over the nq request planes given, [nq + UV_PAD_ROWS, Dp] laid out like the
+// item planes with the pad rows zero: what the multi-interest recall (uservec_multi.hip) runs over its n_req x max_interests
+// virtual rows.  A zero plane row comes back empty
+int uservec_scan_planes(const goctr_itemvec* v, const long long* off, const int32_t* seq_items, const long long* seq_ts,
+                        const UvCols& in, int64_t nq, const goctr_recall_cfg& cfg, const goctr_uservec_cfg& ucfg,
+                        const signed char* p_hi, const signed char* p_lo, int stride, int32_t* o_items, unsigned int* o_w,
+                        int32_t* o_count, int32_t* o_tpos, UvScratch& ws, hipStream_t st);
+
+// pool, then uservec_scan_planes, over nq rows on `st`: row q's first cfg.n_cand slots at q * stride (stride >= cfg.n_cand) of o_items /
 // o_w, o_count[q], o_tpos[q].  o_p [nq, D] and o_s [nq] may be null.  The cache arrays may be null together (no cache: every row
 // comes back empty).  Waits for nothing
 int uservec_launch(const goctr_itemvec* v, const long long* off, const int32_t* seq_items, const long long* seq_ts,

@@ -34,14 +34,13 @@ using namespace goctr;
 namespace {
 
 using u64 = unsigned long long;
-using i32x4 = __attribute__((ext_vector_type(4))) int;
+using i32x4 = uv_i32x4;
 
-constexpr int UV_K = IV_K;                     // the MFMA's K
+static_assert(UV_K == IV_K, "a plane row is padded to the MFMA's K");
 constexpr int UV_THREADS = 256;
 constexpr int UV_WAVES = UV_THREADS / 64;
 constexpr int UV_CT = 2;                       // 16-column tiles per wavefront and step
 constexpr int UV_STEP = UV_WAVES * UV_CT * 16; // columns per step: the most one row's list can grow by between two checks
-constexpr int UV_PAD_ROWS = 32;                // zero rows behind the request planes: partial row tiles read them
 constexpr int UV_MAX_H = 256, UV_MAX_D = 1024;
 constexpr int UV_GROUP_ALIGN = 32;             // a row group holds a multiple (the last one excepted): whole row tiles
 constexpr int UV_MIN_CHUNK = 512;              // the implementation's choice of chunk_items is at least this
@@ -164,10 +163,6 @@ struct ScanArgs {
   const int32_t* targets;                              // [nq] or null
   u64* lists;                                          // [g_rows, n_chunks, n_cand]
 };
-
-__device__ inline i32x4 uv_frag(const signed char* plane, long long row, int Dp, int ks, int lane) {
-  return *reinterpret_cast<const i32x4*>(plane + (size_t)row * Dp + ks * UV_K + (lane >> 4) * 16);
-}
 
 // inb_trim (itemnbr.hip) for R rows: every wavefront sorts one row of each group of UV_WAVES rows that holds a row in need
 // (force: a row with an entry), descending, and trims it to n_cand
@@ -383,22 +378,30 @@ int uservec_launch(const goctr_itemvec* v, const long long* off, const int32_t* 
                    const RecallInputs& in, bool has_targets, int64_t nq, const goctr_recall_cfg& cfg, const goctr_uservec_cfg& ucfg,
                    int stride, int32_t* o_items, unsigned int* o_w, int32_t* o_count, int32_t* o_tpos, int16_t* o_p,
                    unsigned long long* o_s, UvScratch& ws, hipStream_t st) {
-  const int Dp = v->Dp, nc = cfg.n_cand, cap = uv_cap(nc), R = uv_rows(cap, nq);
-  const int64_t V = v->n_items;
-  const bool seen = cfg.exclude != GOCTR_TOPN_KEEP_SEEN && off != nullptr;
-  const int64_t words = cdiv(V, 32);
+  const int Dp = v->Dp;
   // the request planes
   const size_t plane = ((size_t)nq + UV_PAD_ROWS) * Dp;
   if (ws.p_hi.alloc(plane, false) || ws.p_lo.alloc(plane, false)) return -1;
   GOCTR_HIP(hipMemsetAsync(ws.p_hi.p + (size_t)nq * Dp, 0, (size_t)UV_PAD_ROWS * Dp, st));
   GOCTR_HIP(hipMemsetAsync(ws.p_lo.p + (size_t)nq * Dp, 0, (size_t)UV_PAD_ROWS * Dp, st));
   PoolArgs p{};
-  p.off = off; p.seq_items = seq_items; p.seq_ts = seq_ts; p.n_items = V; p.users = in.users.p; p.ts = in.ts.p;
+  p.off = off; p.seq_items = seq_items; p.seq_ts = seq_ts; p.n_items = v->n_items; p.users = in.users.p; p.ts = in.ts.p;
   p.H = cfg.history; p.D = v->D; p.Dp = Dp; p.hi = v->hi.p; p.lo = v->lo.p; p.p_hi = ws.p_hi.p; p.p_lo = ws.p_lo.p;
   p.out_p = o_p; p.out_s = o_s;
   hipLaunchKernelGGL(uv_pool_kernel, dim3((unsigned)nq), dim3(UV_THREADS), 0, st, p);
   GOCTR_HIP(hipGetLastError());
+  return uservec_scan_planes(v, off, seq_items, seq_ts, UvCols{in.users.p, in.ts.p, has_targets ? in.targets.p : nullptr}, nq, cfg, ucfg,
+                             ws.p_hi.p, ws.p_lo.p, stride, o_items, o_w, o_count, o_tpos, ws, st);
+}
 
+int uservec_scan_planes(const goctr_itemvec* v, const long long* off, const int32_t* seq_items, const long long* seq_ts,
+                        const UvCols& in, int64_t nq, const goctr_recall_cfg& cfg, const goctr_uservec_cfg& ucfg,
+                        const signed char* p_hi, const signed char* p_lo, int stride, int32_t* o_items, unsigned int* o_w,
+                        int32_t* o_count, int32_t* o_tpos, UvScratch& ws, hipStream_t st) {
+  const int Dp = v->Dp, nc = cfg.n_cand, cap = uv_cap(nc), R = uv_rows(cap, nq);
+  const int64_t V = v->n_items;
+  const bool seen = cfg.exclude != GOCTR_TOPN_KEEP_SEEN && off != nullptr;
+  const int64_t words = cdiv(V, 32);
   // the scratch budget decides the rows of a group; the chunks follow from the row tiles the first group brings, so that a
   // single request row still fills the chip
   const int64_t budget = (int64_t)std::max(0, env_int("GOCTR_USERVEC_SCRATCH_MB", 256)) << 20;
@@ -429,14 +432,14 @@ int uservec_launch(const goctr_itemvec* v, const long long* off, const int32_t* 
     if (seen) {
       GOCTR_HIP(hipMemsetAsync(ws.bitmap.p, 0, (size_t)g_rows * words * 4, st));
       hipLaunchKernelGGL(uv_seen_kernel, dim3((unsigned)g_rows), dim3(UV_THREADS), 0, st, off, seq_items, seq_ts, (long long)V,
-                         in.users.p, in.ts.p, (long long)q0, cfg.exclude == GOCTR_TOPN_DROP_SEEN_BEFORE ? 1 : 0, (long long)words,
+                         in.users, in.ts, (long long)q0, cfg.exclude == GOCTR_TOPN_DROP_SEEN_BEFORE ? 1 : 0, (long long)words,
                          ws.bitmap.p);
       GOCTR_HIP(hipGetLastError());
     }
     ScanArgs a{};
-    a.p_hi = ws.p_hi.p; a.p_lo = ws.p_lo.p; a.hi = v->hi.p; a.lo = v->lo.p; a.Dp = Dp; a.n_items = V; a.chunk = chunk;
+    a.p_hi = p_hi; a.p_lo = p_lo; a.hi = v->hi.p; a.lo = v->lo.p; a.Dp = Dp; a.n_items = V; a.chunk = chunk;
     a.q0 = q0; a.g_rows = g_rows; a.n_chunks = (int)n_chunks; a.n_cand = nc; a.cap = cap; a.R = R; a.min_w = (unsigned int)ucfg.min_w;
-    a.bitmap = seen ? ws.bitmap.p : nullptr; a.words = words; a.targets = has_targets ? in.targets.p : nullptr;
+    a.bitmap = seen ? ws.bitmap.p : nullptr; a.words = words; a.targets = in.targets;
     a.lists = ws.lists.p;
     const dim3 grid((unsigned)n_chunks, (unsigned)cdiv(g_rows, R));
     const bool one_k = Dp == UV_K;
@@ -445,7 +448,7 @@ int uservec_launch(const goctr_itemvec* v, const long long* off, const int32_t* 
     else rc = one_k ? scan_launch(uv_scan_kernel<true, 1>, grid, lds, st, a) : scan_launch(uv_scan_kernel<false, 1>, grid, lds, st, a);
     if (rc) return -1;
     MergeArgs m{};
-    m.lists = ws.lists.p; m.n_chunks = (int)n_chunks; m.n_cand = nc; m.q0 = q0; m.targets = has_targets ? in.targets.p : nullptr;
+    m.lists = ws.lists.p; m.n_chunks = (int)n_chunks; m.n_cand = nc; m.q0 = q0; m.targets = in.targets;
     m.stride = stride; m.out_items = o_items; m.out_w = o_w; m.out_count = o_count; m.out_tpos = o_tpos;
     hipLaunchKernelGGL(uv_merge_kernel, dim3((unsigned)g_rows), dim3(SEL_THREADS), 0, st, m);
     GOCTR_HIP(hipGetLastError());

@@ -778,6 +778,57 @@ inline std::vector<ItemScore> RecommendVector(model::CtrNet& net, RecSys& rs, co
   return RecommendVectorBatch(net, rs, vec, {userId}, n, {now}, rcfg).lists[0];
 }
 
+// multi-interest user-to-item recall: the history clustered into up to mcfg.max_interests vectors (goctr_uservec_interests: the
+// clustering alone -- n_int per row, the entries' interest ranks [nq, cfg.history] and the member counts [nq, max_interests]), one
+// list each against the whole catalogue, mixed into one (goctr_uservec_recall_multi; `owner`: the candidates' interest ranks)
+inline goctr_uservec_multi_cfg DefaultUservecMultiCfg() { goctr_uservec_multi_cfg c; goctr_uservec_multi_cfg_default(&c); return c; }
+inline void UservecInterests(const ItemVectors& vec, goctr_ubcache* cache, const std::vector<int32_t>& users, const std::vector<int64_t>& ts,
+                             const goctr_recall_cfg& cfg, std::vector<int32_t>& n_int, std::vector<int8_t>& assign,
+                             std::vector<int32_t>& cnt, const goctr_uservec_multi_cfg& mcfg = DefaultUservecMultiCfg()) {
+  if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("UservecInterests: one timestamp per user");
+  const size_t nq = users.size();
+  n_int.resize(nq); assign.resize(nq * (size_t)std::max(cfg.history, 1)); cnt.resize(nq * (size_t)std::max(mcfg.max_interests, 1));
+  check(goctr_uservec_interests(vec.handle(), cache, users.data(), ts.empty() ? nullptr : ts.data(), (int64_t)nq, &cfg, &mcfg,
+                                n_int.data(), assign.data(), cnt.data(), nullptr, nullptr));
+}
+inline void UservecRecallMulti(const ItemVectors& vec, goctr_ubcache* cache, const std::vector<int32_t>& users,
+                               const std::vector<int64_t>& ts, const goctr_recall_cfg& cfg, std::vector<int32_t>& items,
+                               std::vector<uint32_t>& w, std::vector<uint8_t>& owner, std::vector<int32_t>& count,
+                               const goctr_uservec_multi_cfg& mcfg = DefaultUservecMultiCfg()) {
+  if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("UservecRecallMulti: one timestamp per user");
+  const size_t nq = users.size(), nc = (size_t)std::max(cfg.n_cand, 1);
+  items.resize(nq * nc); w.resize(nq * nc); owner.resize(nq * nc); count.resize(nq);
+  check(goctr_uservec_recall_multi(vec.handle(), cache, users.data(), ts.empty() ? nullptr : ts.data(), (int64_t)nq, &cfg, &mcfg,
+                                   items.data(), w.data(), count.data(), nullptr, nullptr, nullptr, nullptr, owner.data(), nullptr));
+}
+
+// RecommendVectorBatch with the multi-interest recall as the recall stage (goctr_recommend_uservec_multi): a user's smaller tastes
+// get their turns in the candidate list
+inline TopN RecommendMultiInterestBatch(model::CtrNet& net, RecSys& rs, const ItemVectors& vec, const std::vector<int32_t>& users,
+                                        int n = 10, const std::vector<int64_t>& ts = {},
+                                        const goctr_recall_cfg& rcfg = ItemCF::DefaultRecallCfg(),
+                                        const goctr_uservec_multi_cfg& mcfg = DefaultUservecMultiCfg(),
+                                        const std::vector<int32_t>& targets = {}, int64_t pass_rows = 0) {
+  const int64_t nq = (int64_t)users.size();
+  if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("RecommendMultiInterestBatch: one timestamp per user");
+  if (!targets.empty() && targets.size() != users.size()) throw std::invalid_argument("RecommendMultiInterestBatch: one target per user");
+  if (n < 1) throw std::invalid_argument("RecommendMultiInterestBatch: n must be positive");
+  std::vector<int32_t> items((size_t)nq * n), count((size_t)nq);
+  std::vector<float> scores((size_t)nq * n);
+  TopN out;
+  if (!targets.empty()) out.target_rank.resize((size_t)nq);
+  check(goctr_recommend_uservec_multi(net.Vm(), rs.handle(), vec.handle(), users.data(), ts.empty() ? nullptr : ts.data(), nq,
+                                      targets.empty() ? nullptr : targets.data(), &rcfg, &mcfg, n, pass_rows, items.data(),
+                                      scores.data(), count.data(), nullptr, nullptr,
+                                      targets.empty() ? nullptr : out.target_rank.data(), nullptr, nullptr, nullptr, &out.n_failed,
+                                      nullptr, nullptr));
+  out.lists.resize((size_t)nq);
+  for (int64_t q = 0; q < nq; ++q)
+    for (int j = 0; j < count[(size_t)q]; ++j)
+      out.lists[(size_t)q].push_back(ItemScore{items[(size_t)q * n + j], scores[(size_t)q * n + j]});
+  return out;
+}
+
 // RecommendBlendBatch with the user-vector recall as the caller's list (goctr_recommend_blend_uservec): ItemCF's candidates, the
 // n_vec items nearest the pooled history (written and read in HBM), then the popularity list; with `rerank` and `mcfg` the diversity
 // re-rank picks the mcfg->k returned

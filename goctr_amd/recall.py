@@ -39,6 +39,8 @@ _SWING_FIELDS = {"max_len", "max_users", "alpha_q", "n_nbr", "min_pairs", "seed"
 _MMR_FIELDS = {"k", "pool", "lambda_q", "max_per_group"}
 _LIST_FIELDS = {"k", "tail_cnt"}
 _USERVEC_FIELDS = {"min_w", "chunk_items"}
+_USERVEC_MULTI_FIELDS = {"min_w", "max_interests", "iters", "split_w", "mix", "chunk_items"}
+MIX = {"max": capi.UVMIX_MAX, "quota": capi.UVMIX_QUOTA}
 
 
 def make_cfg(**kw) -> capi.ItemcfCfg:
@@ -91,6 +93,16 @@ def make_uservec_cfg(**kw) -> capi.UservecCfg:
     if unknown:
         raise TypeError(f"goctr_uservec_cfg has no field {sorted(unknown)}")
     return capi.default_uservec_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
+
+
+def make_uservec_multi_cfg(**kw) -> capi.UservecMultiCfg:
+    """goctr_uservec_multi_cfg from keywords (integers; ``mix`` also "max" / "quota"; the ranges are the library's to refuse)"""
+    unknown = set(kw) - _USERVEC_MULTI_FIELDS
+    if unknown:
+        raise TypeError(f"goctr_uservec_multi_cfg has no field {sorted(unknown)}")
+    if isinstance(kw.get("mix"), str):
+        kw["mix"] = MIX[kw["mix"]]
+    return capi.default_uservec_multi_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
 
 
 def make_list_cfg(**kw) -> capi.ListCfg:
@@ -398,6 +410,55 @@ class ItemVectors:
                                                     capi.ptr(out["w"], C.c_uint32), capi.ptr(out["count"], C.c_int32),
                                                     capi.ptr(targets, C.c_int32), capi.ptr(tpos, C.c_int32), capi.ptr(p, C.c_int16),
                                                     capi.ptr(s, C.c_uint64)))
+        if tpos is not None:
+            out["target_pos"] = tpos
+        if validate:
+            out["p"], out["s"] = p, s
+        return out
+
+    def _multi_cfgs(self, cfg, mcfg, kw):
+        mkw = {k: kw.pop(k) for k in list(kw) if k in _USERVEC_MULTI_FIELDS}
+        if (cfg is not None and kw) or (mcfg is not None and mkw):
+            raise TypeError("give either a cfg or its keywords")
+        return (cfg if cfg is not None else make_recall_cfg(**kw)), (mcfg if mcfg is not None else make_uservec_multi_cfg(**mkw))
+
+    def interests(self, ubc, users, ts=None, cfg: capi.RecallCfg | None = None, mcfg: capi.UservecMultiCfg | None = None, **kw) -> dict:
+        """goctr_uservec_interests over DENSE user rows of ``ubc``'s image: the clustering of every row's history alone.  ``kw``:
+        goctr_recall_cfg fields (history is the one read) and goctr_uservec_multi_cfg's.  dict(n_int int32 [nq], assign int8
+        [nq, history] (the entry's interest rank, -1 = none), cnt int32 [nq, max_interests], p int16 [nq, max_interests, D],
+        s uint64 [nq, max_interests]), interests in rank order"""
+        cfg, mcfg = self._multi_cfgs(cfg, mcfg, kw)
+        users, ts, _ = request_columns(users, ts, None)
+        nq, K, H = users.size, max(int(mcfg.max_interests), 1), max(int(cfg.history), 1)
+        out = dict(n_int=np.full(nq, -2, np.int32), assign=np.full((nq, H), -2, np.int8), cnt=np.full((nq, K), -2, np.int32),
+                   p=np.full((nq, K, self.D), -2, np.int16), s=np.full((nq, K), 0xffffffffffffffff, np.uint64))
+        h = None if ubc is None else ubc.device() if hasattr(ubc, "device") else ubc
+        capi.check(capi.load().goctr_uservec_interests(self._h, h, capi.ptr(users, C.c_int32), capi.ptr(ts, C.c_int64), C.c_int64(nq),
+                                                       C.byref(cfg), C.byref(mcfg), capi.ptr(out["n_int"], C.c_int32),
+                                                       capi.ptr(out["assign"], C.c_int8), capi.ptr(out["cnt"], C.c_int32),
+                                                       capi.ptr(out["p"], C.c_int16), capi.ptr(out["s"], C.c_uint64)))
+        return out
+
+    def recall_users_multi(self, ubc, users, ts=None, targets=None, cfg: capi.RecallCfg | None = None,
+                           mcfg: capi.UservecMultiCfg | None = None, validate=False, **kw) -> dict:
+        """goctr_uservec_recall_multi over DENSE user rows of ``ubc``'s image: the history clustered into up to max_interests
+        vectors, one list each against the whole catalogue, mixed into one.  ``kw``: goctr_recall_cfg fields and
+        goctr_uservec_multi_cfg's.  ``recall_users``'s dict plus interest uint8 [nq, n_cand] (the owner's rank, 255 = unused) and
+        n_int int32 [nq]; with ``validate`` p is int16 [nq, max_interests, D] and s uint64 [nq, max_interests]"""
+        cfg, mcfg = self._multi_cfgs(cfg, mcfg, kw)
+        users, ts, targets = request_columns(users, ts, targets)
+        nq, nc, K = users.size, max(int(cfg.n_cand), 1), max(int(mcfg.max_interests), 1)
+        out = dict(items=np.full((nq, nc), -2, np.int32), w=np.full((nq, nc), 0xffffffff, np.uint32), count=np.full(nq, -2, np.int32),
+                   interest=np.full((nq, nc), 254, np.uint8), n_int=np.full(nq, -2, np.int32))
+        tpos = np.full(nq, -2, np.int32) if targets is not None else None
+        p = np.full((nq, K, self.D), -2, np.int16) if validate else None
+        s = np.full((nq, K), 0xffffffffffffffff, np.uint64) if validate else None
+        h = None if ubc is None else ubc.device() if hasattr(ubc, "device") else ubc
+        capi.check(capi.load().goctr_uservec_recall_multi(
+            self._h, h, capi.ptr(users, C.c_int32), capi.ptr(ts, C.c_int64), C.c_int64(nq), C.byref(cfg), C.byref(mcfg),
+            capi.ptr(out["items"], C.c_int32), capi.ptr(out["w"], C.c_uint32), capi.ptr(out["count"], C.c_int32),
+            capi.ptr(targets, C.c_int32), capi.ptr(tpos, C.c_int32), capi.ptr(p, C.c_int16), capi.ptr(s, C.c_uint64),
+            capi.ptr(out["interest"], C.c_uint8), capi.ptr(out["n_int"], C.c_int32)))
         if tpos is not None:
             out["target_pos"] = tpos
         if validate:

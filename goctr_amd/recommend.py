@@ -1189,6 +1189,85 @@ def EvaluateLeaveOneOutVector(model: Predictor, vectors, k=10, sample_kw=None, d
     return out
 
 
+def _split_uservec_multi_kw(recall_cfg, mcfg, kw):
+    """(goctr_recall_cfg, goctr_uservec_multi_cfg) from cfgs or keywords"""
+    from .recall import _USERVEC_MULTI_FIELDS, make_recall_cfg, make_uservec_multi_cfg
+    mkw = {k: kw.pop(k) for k in list(kw) if k in _USERVEC_MULTI_FIELDS}
+    if (recall_cfg is not None and kw) or (mcfg is not None and mkw):
+        raise TypeError("give either a cfg or its keywords")
+    return (recall_cfg if recall_cfg is not None else make_recall_cfg(**kw)), (mcfg if mcfg is not None else make_uservec_multi_cfg(**mkw))
+
+
+def uservec_multi(model: Predictor, vectors, users, ts=None, targets=None, k=10, pass_rows=0, validate=False, recall_cfg=None,
+                  mcfg=None, **recall_kw):
+    """goctr_recommend_uservec_multi over DENSE indices: ``uservec`` with the multi-interest recall as the recall stage; the same
+    dict plus n_int int32 [nq] and, with ``validate``, cand_interest uint8 [nq, n_cand].  ``recall_kw``: goctr_recall_cfg fields and
+    goctr_uservec_multi_cfg's (min_w, max_interests, iters, split_w, mix, chunk_items).  What RecommendMultiInterest /
+    RecommendMultiInterestBatch / EvaluateLeaveOneOutMultiInterest call."""
+    from .recall import request_columns
+    cfg, mcfg = _split_uservec_multi_kw(recall_cfg, mcfg, recall_kw)
+    rs = model.recSys
+    users, ts, targets = request_columns(users, ts, targets)
+    nq, kk, nc = users.size, max(int(k), 1), max(int(cfg.n_cand), 1)
+    out = dict(items=np.full((nq, kk), -2, np.int32), scores=np.full((nq, kk), np.nan, np.float32), count=np.full(nq, -2, np.int32),
+               cand_count=np.full(nq, -2, np.int32), n_int=np.full(nq, -2, np.int32))
+    tpos = np.full(nq, -2, np.int32) if targets is not None else None
+    rank = np.full(nq, -2, np.int64) if targets is not None else None
+    cand_items = np.full((nq, nc), -2, np.int32) if validate else None
+    cand_w = np.full((nq, nc), 0xffffffff, np.uint32) if validate else None
+    cand_scores = np.full((nq, nc), np.nan, np.float32) if validate else None
+    cand_interest = np.full((nq, nc), 254, np.uint8) if validate else None
+    nf = C.c_int64(-2)
+    capi.check(capi.load().goctr_recommend_uservec_multi(
+        model.net._h, rs._h, vectors._h, capi.ptr(users, C.c_int32), capi.ptr(ts, C.c_int64), C.c_int64(nq),
+        capi.ptr(targets, C.c_int32), C.byref(cfg), C.byref(mcfg), C.c_int32(int(k)), C.c_int64(int(pass_rows)),
+        capi.ptr(out["items"], C.c_int32), capi.ptr(out["scores"], C.c_float), capi.ptr(out["count"], C.c_int32),
+        capi.ptr(out["cand_count"], C.c_int32), capi.ptr(tpos, C.c_int32), capi.ptr(rank, C.c_int64), capi.ptr(cand_items, C.c_int32),
+        capi.ptr(cand_w, C.c_uint32), capi.ptr(cand_scores, C.c_float), C.byref(nf), capi.ptr(cand_interest, C.c_uint8),
+        capi.ptr(out["n_int"], C.c_int32)))
+    out["n_failed"] = nf.value
+    if targets is not None:
+        out["target_pos"], out["target_rank"] = tpos, rank
+    if validate:
+        out["cand_items"], out["cand_w"], out["cand_scores"], out["cand_interest"] = cand_items, cand_w, cand_scores, cand_interest
+    return out
+
+
+def RecommendMultiInterestBatch(model: Predictor, vectors, userIds, n=10, now=None, **recall_kw):
+    """RecommendMultiInterest for several users in one device call: [[ItemScore]] in the order of userIds.  ``now``: one timestamp
+    for all, or one per user.  A user without history (or whose history's vectors are all invalid) gets an empty list."""
+    users, ts = _request_rows(model, userIds, now)
+    if users.size == 0:
+        return []
+    try:
+        r = uservec_multi(model, vectors, users, ts, None, n, **recall_kw)
+    except capi.GoctrError as e:
+        raise SampleVectorError(str(e)) from None
+    return _item_scores(model, r, users.size)
+
+
+def RecommendMultiInterest(model: Predictor, vectors, userId: int, n=10, now=None, **recall_kw):
+    """EXTENSION -- RecommendVector for a user with several tastes: the history's vectors are clustered into up to
+    ``max_interests`` interest vectors (a new one starts where an entry's quantised cosine to every centre so far is below
+    ``split_w`` / 65536), each proposes its closest items of the whole catalogue, and the lists are mixed into ``n_cand``
+    candidates -- by turns in proportion to the interests' sizes (``mix="quota"``, the default) or by the best weight
+    (``mix="max"``) -- before the model scores them and the ``n`` best come back."""
+    return RecommendMultiInterestBatch(model, vectors, [userId], n, now, **recall_kw)[0]
+
+
+def EvaluateLeaveOneOutMultiInterest(model: Predictor, vectors, k=10, sample_kw=None, details=False, pass_rows=0, **recall_kw):
+    """EvaluateLeaveOneOutVector's protocol and figures with the multi-interest recall as the recall stage
+    (goctr_recommend_uservec_multi); ``details`` adds n_int, the interests every row's history was split into."""
+    users, targets, ts = _held_out_rows(model, sample_kw)
+    recall_kw.setdefault("exclude", "before")
+    cfg, mcfg = _split_uservec_multi_kw(None, None, recall_kw)
+    r = uservec_multi(model, vectors, users, ts, targets, k, pass_rows, recall_cfg=cfg, mcfg=mcfg)
+    out = _loo_figures(r, targets, model.recSys.item_table.shape[0], k, cfg.n_cand)
+    if details:
+        out.update(target_pos=r["target_pos"], rank=r["target_rank"], user_index=users, target_index=targets, ts=ts, n_int=r["n_int"])
+    return out
+
+
 def RecommendBlendVectorBatch(model: Predictor, icf, pop, uv, userIds, n=10, now=None, n_vec=64, quota_pop=0, vectors=None, pool=64,
                               lambda_q=192, max_per_group=0, **recall_kw):
     """EXTENSION -- RecommendBlendBatch with the user-vector recall as the caller's list: ItemCF's candidates, then the ``n_vec``

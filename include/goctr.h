@@ -899,6 +899,89 @@ int goctr_recommend_blend_uservec(goctr_model* m, goctr_recsys* r, goctr_itemcf*
                                   int32_t* cand_items, uint32_t* cand_w, float* cand_scores, uint8_t* cand_src, int64_t* n_failed,
                                   int32_t* out_obj, uint32_t* out_pen, int32_t* out_target_place);
 
+/* ---- Multi-interest user-vector recall: the history clustered into up to 8 interest vectors, one list each, mixed into one (no
+ * reference counterpart).  A user with two tastes pools to a vector between them and the larger taste takes the whole list; here
+ * every taste gets a vector of its own and a share of the list.  Every output is defined bit for bit
+ * (tests/uservec_multi_ref.py is the host restatement): the only float64 operations are goctr_uservec_recall's pinned quantisation.
+ *
+ * For request row q, the history h_0 .. h_{n-1} is exactly goctr_uservec_recall's.  x_t is the handle's int16 row of h_t, zeros
+ * for an item whose vector is invalid; an entry with x_t = 0 is NULL.  w(a,b) = dot(a,b) >> 12 when the dot is positive, else 0;
+ * every dot product below fits int32 as goctr_uservec_recall's do (|x| and |p| entries <= 16384, rows of length 2^14).
+ *   seeds          farthest point, in integers.  Seed 0 is the first non-null entry; without one the row has no interests and
+ *                  returns count 0.  cover[t] = the maximum over the chosen seeds s of w(x_t, x_s).  While fewer than
+ *                  max_interests seeds are chosen: take the non-null entry with the smallest cover, ties to the lowest t (an
+ *                  entry that is a seed already is not exempt); if its cover >= split_w stop, else it is the next seed.  K is
+ *                  the number of seeds, and the first centres are p_m = x_seed_m, all live
+ *   assign         every non-null entry goes to the live centre with the largest signed dot(x_t, p_m), ties to the lowest m.
+ *                  Null entries are assigned to nothing (-1); without a live centre so is every entry
+ *   re-centre      u_m = the integer sum of the members' rows, s_m = the sum of u_{m,d}^2, p_m = the request-vector quantisation
+ *                  of goctr_uservec_recall applied to u_m, unchanged.  A cluster without members or with s_m = 0 is dead: it
+ *                  stays dead and attracts nothing
+ *   order          assign; `iters` times {re-centre, assign}; one last re-centre.  (Stopping once an assignment repeats changes
+ *                  no byte, and the implementation does.)
+ *   interests      the live clusters, by member count descending, then seed order ascending; that place is the interest's RANK,
+ *                  n_int their number.  An entry whose cluster died in the last re-centre is reported as unassigned
+ *   lists          per interest exactly goctr_uservec_recall's weight against p_m, min_w, seen rule, target exemption and order:
+ *                  at most cfg->n_cand candidates each
+ *   mix            GOCTR_UVMIX_MAX: w(j) = the maximum over the interests of w_m(j), the owner is the lowest rank that reaches
+ *                  it; by w descending, then item ascending; the first n_cand.  (Taken over the per-interest lists this equals
+ *                  the same rule over the whole catalogue: an item of the global first n_cand is in its owner's.)
+ *                  GOCTR_UVMIX_QUOTA: place t of the interest of rank r with cnt_r members gets vt = ((t + 1) << 16) / cnt_r
+ *                  (integer division); the entries are taken by (vt, r) ascending, an item keeps its first occurrence with that
+ *                  interest's weight and that owner, and the first n_cand distinct items are kept: turns in proportion to the
+ *                  member counts.  This list is not sorted by weight
+ *   outputs        goctr_uservec_recall's, over the mixed list (the target's place is its place in the mixed list), and
+ *                  out_interest [n_req,n_cand] uint8: the owner's rank, padding 255; out_n_int [n_req]; the validation outputs
+ *                  out_p [n_req,max_interests,D] int16 and out_s [n_req,max_interests] uint64 in rank order, zeros beyond n_int.
+ *                  out_interest, out_n_int, out_target_pos, out_p and out_s may each be NULL
+ *   one interest   with max_interests = 1 every output that goctr_uservec_recall also has (items, w, count, target_pos, p, s) is
+ *                  byte-equal to that call's over the same arguments: all non-null entries are one cluster, and null rows add 0
+ *   refused        (-1, nothing touched) goctr_uservec_recall's refusals; max_interests outside 1 .. 8; iters outside 0 .. 16;
+ *                  split_w outside 1 .. 65536; mix neither 0 nor 1; reserved != 0; n_req > 2^21
+ * goctr_uservec_interests is the clustering alone, for validation and inspection (cfg->history is what it reads of cfg):
+ *   out_n_int [n_req]; out_assign [n_req,history] int8: the entry's rank, -1 for null, unassigned and padding; out_cnt
+ *   [n_req,max_interests]: member counts in rank order, 0 beyond n_int; out_p, out_s as above.  All but out_n_int may be NULL.
+ * One workgroup clusters a row; the scan of goctr_uservec_recall then runs over n_req x max_interests vectors, and one workgroup
+ * mixes a row's lists.  No output byte depends on chunk_items, on how rows are grouped, on the arrival order of threads, on a
+ * tile size, or on whether a history's planes were staged on chip.  Host arrays, the engine stream and the engine lock, like
+ * goctr_uservec_recall. */
+#define GOCTR_UVMIX_MAX   0
+#define GOCTR_UVMIX_QUOTA 1
+typedef struct {
+  int32_t min_w;          /* 1 .. 65536, units of 2^-16                                         default 1     */
+  int32_t max_interests;  /* 1 .. 8                                                             default 4     */
+  int32_t iters;          /* 0 .. 16: {re-centre, assign} rounds                                default 4     */
+  int32_t split_w;        /* 1 .. 65536: an entry covered this well starts no interest          default 49152 */
+  int32_t mix;            /* GOCTR_UVMIX_MAX / GOCTR_UVMIX_QUOTA                                default QUOTA */
+  int32_t reserved;       /* must be 0 */
+  int64_t chunk_items;    /* as goctr_uservec_cfg's                                             default 0     */
+} goctr_uservec_multi_cfg;
+void goctr_uservec_multi_cfg_default(goctr_uservec_multi_cfg* c);
+int  goctr_uservec_interests(goctr_itemvec* v, goctr_ubcache* c, const int32_t* users, const int64_t* ts /* NULL = 0 */,
+                             int64_t n_req, const goctr_recall_cfg* cfg, const goctr_uservec_multi_cfg* mcfg,
+                             int32_t* out_n_int /*[n_req]*/, int8_t* out_assign /*[n_req,history] or NULL*/,
+                             int32_t* out_cnt /*[n_req,max_interests] or NULL*/,
+                             int16_t* out_p /*[n_req,max_interests,D] or NULL*/, uint64_t* out_s /*[n_req,max_interests] or NULL*/);
+int  goctr_uservec_recall_multi(goctr_itemvec* v, goctr_ubcache* c, const int32_t* users, const int64_t* ts /* NULL = 0 */,
+                                int64_t n_req, const goctr_recall_cfg* cfg, const goctr_uservec_multi_cfg* mcfg,
+                                int32_t* out_items /*[n_req,n_cand]*/, uint32_t* out_w /*[n_req,n_cand]*/,
+                                int32_t* out_count /*[n_req]*/, const int32_t* targets /*[n_req] or NULL*/,
+                                int32_t* out_target_pos /*[n_req] or NULL*/, int16_t* out_p, uint64_t* out_s,
+                                uint8_t* out_interest /*[n_req,n_cand] or NULL*/, int32_t* out_n_int /*[n_req] or NULL*/);
+
+/* goctr_recommend_uservec_multi: goctr_recommend_uservec with the recall above as its recall stage.  Every documented property of
+ * that call holds unchanged.  cand_interest [n_req,n_cand] (the candidates' owner ranks, padding 255) and out_n_int [n_req] may
+ * each be NULL.
+ *   refused        goctr_recommend_uservec's refusals with the mcfg refusals above in place of the ucfg ones */
+int goctr_recommend_uservec_multi(goctr_model* m, goctr_recsys* r, goctr_itemvec* v,
+                                  const int32_t* users, const int64_t* ts /* NULL = 0 */, int64_t n_req,
+                                  const int32_t* targets /* [n_req] or NULL */, const goctr_recall_cfg* recall_cfg,
+                                  const goctr_uservec_multi_cfg* mcfg, int32_t k, int64_t pass_rows,
+                                  int32_t* out_items /* [n_req,k] */, float* out_scores /* [n_req,k] */, int32_t* out_count,
+                                  int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank,
+                                  int32_t* cand_items, uint32_t* cand_w, float* cand_scores, int64_t* n_failed,
+                                  uint8_t* cand_interest, int32_t* out_n_int);
+
 /* The replica a multi-device training call (cfg.devices = n) keeps on engine `rank` (rank 0: the handle itself); NULL before
  * the first such call.  Borrowed: owned by the handle it was asked from.  For checks that the replicas are bit-identical
  * (tests, bench.py's replica checksum) -- every entry point works on it, on its own engine. */
