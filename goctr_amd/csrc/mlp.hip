@@ -4,9 +4,17 @@
 
 namespace {
 
-// slab height of the weight-gradient GEMMs: the widest layer's k-blocks x slabs should not exceed the CUs (f64 MFMA
-// work of co-resident workgroups serialises per SIMD like the f32 one does)
-int tn_rows64(const goctr_mlp* p, int n) {
+// The slabs of the weight-gradient GEMMs over n batch rows -- the ONE place that says how many there are: the workspace
+// (ensure_ws), the launches (backward: mlp_bwd_hidden_kernel, launch_tn64) and the reduce launch's slab counts all read it.
+//   rows   slab height: the widest layer's k-blocks x slabs should not exceed the CUs (f64 MFMA work of co-resident
+//          workgroups serialises per SIMD like the f32 one does); an even number, 32 at least
+//   count  slabs a launch over n rows writes, ceil(n / rows)
+//   most   the largest count ANY n' <= n gives.  count is not monotone in n (rows is rounded up to an even number >= 32:
+//          at 256 CUs [281,100,1] has 40 slabs at n = 1345 and 42 at 1344), so a workspace sized by count(n) alone is too
+//          small for some smaller batch.  rows(n') >= ceil(n' / cap) gives count(n') <= ceil(n' / ceil(n' / cap)) <= cap, and
+//          rows(n') >= 32 gives count(n') <= ceil(n' / 32) <= ceil(n / 32).
+struct TnSlabs64 { int rows, count, most; };
+TnSlabs64 tn_slabs64(const goctr_mlp* p, int n) {
   int kb = 1;   // workgroups per slab of the widest layer (see launch_tn64)
   for (int l = 0; l < p->nl; ++l) {
     const int KT = p->up[l] / 16, NT = p->up[l + 1] / 16;
@@ -14,15 +22,27 @@ int tn_rows64(const goctr_mlp* p, int n) {
     if (k > kb) kb = k;
   }
   int cus = engine().compute_units > 0 ? engine().compute_units : 256;
-  const int S = cus / kb > 0 ? cus / kb : 1;
-  int rows = (int)cdiv(n, S);
+  const int cap = cus / kb > 0 ? cus / kb : 1;
+  int rows = (int)cdiv(n, cap);
   rows = rows < 32 ? 32 : round_up(rows, 2);
-  return rows;
+  return {rows, (int)cdiv(n, rows), std::min(cap, (int)cdiv(n, 32))};
+}
+
+// the captured training steps (run_fused_steps) hold device addresses by value: whatever moves one of them drops the graphs
+// (goctr_mlp_train_steps is asynchronous: replays of the old execs may still be queued -- never destroy one in flight)
+int drop_step_graphs(goctr_mlp* p) {
+  if (p->step_graph || p->multi_graph[0] || p->multi_graph[1]) GOCTR_HIP(hipStreamSynchronize(engine().stream));
+  if (p->step_graph) { (void)hipGraphExecDestroy(p->step_graph); p->step_graph = nullptr; }
+  for (auto& mg : p->multi_graph) { if (mg) (void)hipGraphExecDestroy(mg); mg = nullptr; }
+  return 0;
 }
 
 int ensure_ws(goctr_mlp* p, int n) {
   if (p->wsN >= n) return 0;
-  p->S = (int)cdiv(n, tn_rows64(p, n));
+  // a loss_grad or predict call on more rows than any before (a validation pass between two goctr_mlp_train_steps) moves the
+  // activation, delta and slab buffers a captured step writes
+  if (drop_step_graphs(p)) return -1;
+  p->S = tn_slabs64(p, n).most;   // every later call with n' <= n fits (backward checks it)
   for (int i = 0; i <= p->nl; ++i) {
     if (p->A[i].alloc((size_t)n * p->up[i])) return -1;
     if (i > 0 && p->D[i].alloc((size_t)n * p->up[i])) return -1;
@@ -106,6 +126,9 @@ int backward(goctr_mlp* p, int n, bool do_update, bool advance, int valid = -1) 
   const int upL = p->up[L], no = p->units[L];
   const bool chain = p->chain_done;
   p->chain_done = false;
+  const TnSlabs64 ts = tn_slabs64(p, n);
+  GOCTR_CHECK(n <= p->wsN && ts.count <= p->S, "mlp backward: %d rows in %d slabs, workspace holds %d rows in %d slabs", n,
+              ts.count, p->wsN, p->S);
   if (!p->fused_fwd_done && !chain) {
     if (p->cfg.out_activation == GOCTR_OUT_LOGISTIC)
       hipLaunchKernelGGL(mlp_delta_last_kernel, dim3((unsigned)cdiv((int64_t)n * upL, 256)), dim3(256), 0, e.stream,
@@ -117,8 +140,8 @@ int backward(goctr_mlp* p, int n, bool do_update, bool advance, int valid = -1) 
   GOCTR_HIP(hipGetLastError());
   const bool fused_bwd = chain || (p->fused_fwd_done && p->up[1] <= 128);
   if (fused_bwd && !chain) {
-    const int rows = tn_rows64(p, n);
-    hipLaunchKernelGGL(mlp_bwd_hidden_kernel, dim3((unsigned)cdiv(n, rows), (unsigned)cdiv(p->up[1], 32)), dim3(256),
+    const int rows = ts.rows;
+    hipLaunchKernelGGL(mlp_bwd_hidden_kernel, dim3((unsigned)ts.count, (unsigned)cdiv(p->up[1], 32)), dim3(256),
                        sizeof(double) * ((size_t)rows + 256), e.stream, p->A[1].p, p->D[2].p,
                        p->W.p + p->woff[1], n, rows, p->units[1], p->up[1], p->up[2], p->cfg.activation, p->D[1].p,
                        p->slabs[1].p, p->zpart.p, (int)cdiv(p->up[1], 32), p->Yb.p, p->A[2].p, p->D[2].p, p->lossterm.p);
@@ -127,7 +150,7 @@ int backward(goctr_mlp* p, int n, bool do_update, bool advance, int valid = -1) 
   for (int l = fused_bwd ? 0 : L - 1; l >= 0; --l) {
     const bool img = l == 0 && chain && p->x64();     // the chain launch left row indices, not a copy of the rows
     if (launch_tn64(img ? p->X64.p : p->A[l].p, p->up[l], p->up[l] / 16, p->D[l + 1].p, p->up[l + 1], p->up[l + 1] / 16, n,
-                    tn_rows64(p, n), p->slabs[l].p, img ? p->ridx.p : nullptr)) return -1;
+                    ts.rows, p->slabs[l].p, img ? p->ridx.p : nullptr)) return -1;
     if (l >= 1) {
       EpiMlpDAct d{p->D[l].p, p->A[l].p, p->up[l], p->units[l], p->cfg.activation,
                    p->cfg.batch_normalize ? p->bn[l - 1].p : nullptr};
@@ -138,7 +161,7 @@ int backward(goctr_mlp* p, int n, bool do_update, bool advance, int valid = -1) 
   a.nl = L;
   for (int l = 0; l < L; ++l)
     a.L[l] = {p->units[l], p->units[l + 1], p->up[l], p->up[l + 1], p->woff[l], p->poff[l], p->slabs[l].p,
-              (int)cdiv(n, tn_rows64(p, n)), p->WT[l].p, 0};
+              ts.count, p->WT[l].p, 0};
   if (chain) { a.L[1].nslabs = (int)cdiv(n, 16); a.L[1].coop = 1; }
   a.nflat = p->nflat; a.nparams = p->nparams;
   a.W = p->W.p; a.G = p->G.p; a.Mo = p->Mo.p; a.Vo = p->Vo.p; a.Vel = p->Vel.p;
@@ -364,10 +387,7 @@ int run_fused_steps(goctr_mlp* p, int n_steps) {
     if (!p->step_graph || p->step_graph_rows != p->rows || p->step_graph_perm != (p->perm.n > 1) ||
         p->step_graph_x != p->Xr.p || p->step_graph_y != p->Yr.p || p->step_graph_p != p->perm.p || p->step_graph_w != p->W0img.p ||
         p->step_graph_x64 != p->X64.p || p->step_graph_ridx != p->ridx.p) {
-      // (goctr_mlp_train_steps is asynchronous: replays of the old execs may still be queued -- never destroy one in flight)
-      if (p->step_graph || p->multi_graph[0] || p->multi_graph[1]) GOCTR_HIP(hipStreamSynchronize(e.stream));
-      if (p->step_graph) { (void)hipGraphExecDestroy(p->step_graph); p->step_graph = nullptr; }
-      for (auto& mg : p->multi_graph) { if (mg) (void)hipGraphExecDestroy(mg); mg = nullptr; }
+      if (drop_step_graphs(p)) return -1;
       if (capture_graph(e.stream, &p->step_graph, [&] { return train_step_resident(p, true, 0); }, [] {})) return -1;
       p->step_graph_rows = p->rows; p->step_graph_perm = p->perm.n > 1;
       p->step_graph_x = p->Xr.p; p->step_graph_y = p->Yr.p; p->step_graph_p = p->perm.p; p->step_graph_w = p->W0img.p;

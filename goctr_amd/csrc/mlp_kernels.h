@@ -329,8 +329,9 @@ __global__ __launch_bounds__(256) void mlp_reduce_update_kernel(MlpReduceArgs a)
     return;
   }
   double sq = 0;
-  // all 256 parameters of a block belong to ONE layer (every layer's offset is a multiple of 256: padded sizes are multiples of 16,
-  // goctr_mlp_create checks it), so the layer descriptor is the block's, not the lane's: slab base, stride and count stay scalar and a
+  // all 256 parameters of a block belong to ONE layer (every layer's offset is a multiple of 256 by construction: a block holds
+  // up_l x up_{l+1} values and both padded sizes are multiples of 16 -- goctr_mlp_create rounds them, nothing has to check it), so
+  // the layer descriptor is the block's, not the lane's: slab base, stride and count stay scalar and a
   // slab load is base + lane offset.  Taken per lane they made every load's address a 64-bit vector computation (four registers per
   // load in flight), and the compiler issued the 42 slab loads of cfg2 four at a time with a full wait between the groups: three
   // dependent round trips (10.5 k cycles) where one was meant.

@@ -17,8 +17,12 @@ and the learning-rate schedules -- what the softmax / identity heads and the sch
                               tests the last effective rate
 
 Matrix products are numpy's (summation order differs from the reference's): compare at 1e-9-ish relative, never bit-exact.
-Batch normalisation and weight decay are not restated (the new heads share that code with the logistic head)."""
+Batch normalisation and weight decay are not restated (the new heads share that code with the logistic head).
+
+The last part (SHAPE_CASES, plan) is the table of shapes of tests/test_mlp_shapes_host.py and tests/test_gpu_mlp_shapes.py and a
+restatement of the host's launch arithmetic, so that the tests can say which kernel and grid a shape reaches."""
 import math
+import types
 
 import numpy as np
 
@@ -80,9 +84,9 @@ def nparams(units):
     return sum((1 + units[i]) * units[i + 1] for i in range(len(units) - 1))
 
 
-def blocks(units, B):
+def blocks(units, B, dtype=np.float64):
     """fit's activation / delta blocks (basemlp64.go:529-545): B rows per layer, zero-filled"""
-    return ([None] + [np.zeros((B, u)) for u in units[1:]], [np.zeros((B, u)) for u in units[1:]])
+    return ([None] + [np.zeros((B, u), dtype) for u in units[1:]], [np.zeros((B, u), dtype) for u in units[1:]])
 
 
 def forward(units, hidden, out, theta, X, acts=None):
@@ -219,3 +223,113 @@ def fit(units, hidden, out, alpha, theta, opt, X, Y, batch, max_iter, tol=1e-4, 
                 break
             no_improve = 0
     return np.array(curve), len(curve)
+
+
+# ---------------------------------------------------------------- shapes off the handful the other MLP tests use
+# (tests/test_mlp_shapes_host.py, tests/test_gpu_mlp_shapes.py).  name -> (output head, layer units, what the shape reaches on the
+# device; the arithmetic behind each note is plan() below and is asserted by the host test)
+SHAPE_CASES = {
+    "a": ("logistic", [20, 31, 1], "up1 = 32: one full wavefront of hidden columns, the ones column in its last lane column"),
+    "b": ("logistic", [16, 40, 1], "F % 16 == 0: the tail chunk holds the ones column alone; up1 = 48: ng = 2, second wavefront half filled"),
+    "c": ("logistic", [47, 70, 1], "F % 16 == 15; up1 = 80: ng = 3"),
+    "d": ("logistic", [383, 127, 1], "the largest fused shape: up0 = 384 (24 chunks), up1 = 128 (ng = 4, all full), mlp_tn64_kernel at NT = 8"),
+    "e": ("logistic", [384, 20, 1], "up0 = 400 > 384: a binary net on the per-layer kernels; K phases 128, 128, 128, 16; mlp_tn64_kernel with KT = 25"),
+    "f": ("logistic", [20, 128, 1], "NT = 9: gemm_tn_kernel<double,3,2,16> with WK = 1, grid.z = 3; gemm_nn_kernel<double> with grid.y = 2"),
+    "g": ("logistic", [100, 200, 80, 1], "the DIN widths: NT = 13, KT = 7 -> WK = 2, grid.y = 2, grid.z = 4; layer 1 in two K phases (128 + 80)"),
+    "h": ("softmax", [30, 150, 70], "70 classes: two 64-column rounds of mlp_softmax_kernel; upL = 80; layer 0 on gemm_tn_kernel (NT = 10)"),
+    "i": ("identity", [12, 9, 130], "the output layer on gemm_tn_kernel with KT = 1; upL = 144"),
+    "j": ("logistic", [9, 17, 5, 33, 3, 16, 15, 1], "eight layers, goctr_mlp_create's limit: seven blocks in the reduce launch's layer lookup"),
+}
+SHAPE_HIDDEN = ("relu", "logistic", "tanh", "identity")
+SHAPE_ALPHA = 1e-2
+
+
+def _case_rng(name, stream):
+    return np.random.default_rng([20, ord(name), stream])
+
+
+def case_theta(name, hidden):
+    """the case's parameters: initialize's one-sided draw (goctr_amd.mlp init_params, quirk Q8) halved, as tests/test_gpu_mlp.py does"""
+    from goctr_amd import mlp as gmlp
+    _, units, _ = SHAPE_CASES[name]
+    return gmlp.MLPClassifier(units[1:-1], hidden).init_params(units, _case_rng(name, 0)) * 0.5
+
+
+def case_data(name, rows, stream=1):
+    """float32 rows and targets of a case.  The inputs are CENTRED ([-0.5, 0.5)): with [0, 1) inputs and one-sided weights the relu
+    net of [383,127,1] saturates its logistic head, and the clamped log-loss then differs by 4e-5 relative between float64 and
+    extended precision -- a property of the data, not of a kernel"""
+    head, units, _ = SHAPE_CASES[name]
+    rng = _case_rng(name, stream)
+    X = (rng.random((rows, units[0])) - 0.5).astype(np.float32)
+    return X, targets(rng, rows, units[-1], head)
+
+
+def targets(rng, rows, no, head):
+    if head == "softmax":
+        return np.eye(no, dtype=np.float32)[rng.integers(0, no, rows)]
+    if head == "identity":
+        return rng.standard_normal((rows, no)).astype(np.float32)
+    return (rng.random((rows, no)) < 0.5).astype(np.float32)
+
+
+# ---- the host's dispatch, restated (csrc/mlp.hip: forward, backward, tn_slabs64; csrc/mlp_kernels.h: launch_nn64, launch_tn64;
+# csrc/mlp_model.h: fused_ok, chain_ok; csrc/mfma_gemm.h: gemm_nn_phase_rows)
+def up(u):
+    """padded width of a layer: its units and the ones column, rounded up to 16"""
+    return (u + 16) // 16 * 16
+
+
+def cdiv(a, b):
+    return -(-a // b)
+
+
+def nn_launch(Kp, Np):
+    """launch_nn64 -> gemm_nn_kernel<double, Epi, ntw>: C[M, Np] = A[M, Kp] . B[Kp, Np]"""
+    NT = Np // 16
+    WN = 2 if NT >= 2 else 1
+    ntw = cdiv(NT, WN)
+    ntw = 1 if ntw <= 1 else (2 if ntw <= 2 else 4)
+    blk = WN * ntw                                           # tiles per column block
+    grid_y = cdiv(NT, blk)
+    kph = min(152 * 1024 // ((blk * 16 + 4) * 8) // 16 * 16, 8 * 16, Kp)      # rows of B per LDS phase
+    return types.SimpleNamespace(
+        NT=NT, WN=WN, ntw=ntw, grid_y=grid_y, phases=[min(kph, Kp - k0) for k0 in range(0, Kp, kph)],
+        # tiles[y][wn]: 16-column tiles wavefront column wn of column block y stores
+        tiles=[[max(0, min(ntw, min(blk, NT - y * blk) - wn * ntw)) for wn in range(WN)] for y in range(grid_y)])
+
+
+def tn_launch(KT, NT):
+    """launch_tn64: the weight-gradient product of a layer with KT x NT 16-wide tiles"""
+    if NT <= 8:
+        gy = cdiv(KT, 3)
+        return types.SimpleNamespace(kernel="mlp_tn64_kernel", KT=KT, NT=NT, grid_y=gy, grid_z=1, workgroups=gy,
+                                     kcnt=[[min(3, KT - 3 * y)] for y in range(gy)], ncnt=[[min(2, max(0, NT - 2 * w)) for w in range(4)]])
+    WK, WN = (2 if KT >= 6 else 1), min(2, cdiv(NT, 2))
+    gy, gz = cdiv(KT, WK * 3), cdiv(NT, WN * 2)
+    return types.SimpleNamespace(
+        kernel="gemm_tn_kernel<double,3,2,16>", KT=KT, NT=NT, WK=WK, WN=WN, grid_y=gy, grid_z=gz, workgroups=gy * gz,
+        # kcnt[y][wk] / ncnt[z][wn]: tiles of A's / D's columns wavefront row wk / column wn of block y / z owns
+        kcnt=[[max(0, min(3, min(WK * 3, KT - y * WK * 3) - wk * 3)) for wk in range(WK)] for y in range(gy)],
+        ncnt=[[max(0, min(2, min(WN * 2, NT - z * WN * 2) - wn * 2)) for wn in range(WN)] for z in range(gz)])
+
+
+def plan(head, units, cus=256):
+    """what the host launches for a net: the fused / chain kernels or the per-layer GEMMs, and every GEMM's grid"""
+    ups = [up(u) for u in units]
+    nl = len(units) - 1
+    fused = nl == 2 and units[2] == 1 and head == "logistic" and ups[1] <= 128 and ups[0] <= 16 * 24
+    p = types.SimpleNamespace(units=list(units), up=ups, nl=nl, fused=fused, chain=fused,    # (chain_ok's two divisibility tests
+                              ng=cdiv(ups[1], 32) if fused else 0, nch=ups[0] // 16,         # hold for every up[2] = 16)
+                              tn=[tn_launch(ups[l] // 16, ups[l + 1] // 16) for l in range(nl)],
+                              fwd=[nn_launch(ups[l], ups[l + 1]) for l in range(nl)],
+                              bwd={l: nn_launch(ups[l + 1], ups[l]) for l in range(1, nl)})
+    p.cap = max(1, cus // max(t.workgroups for t in p.tn))
+    return p
+
+
+def slabs(p, n):
+    """tn_slabs64: (rows per slab, slabs over n rows, the most slabs any n' <= n has)"""
+    rows = cdiv(n, p.cap)
+    rows = 32 if rows < 32 else rows + rows % 2
+    return rows, cdiv(n, rows), min(p.cap, cdiv(n, 32))
