@@ -232,6 +232,13 @@ struct DevBuf {
   }
 };
 
+// Drains stream s on every way out of the scope, an error return included.  Declared BEHIND the call's device buffers (and behind
+// the locks that guard what its launches read): the drain runs first, then the locks go, then the buffers return to the arena
+struct StreamDrain {
+  hipStream_t s;
+  ~StreamDrain() { (void)hipStreamSynchronize(s); }
+};
+
 // The calling thread's engine's instance of the scratch type Ws (device buffers that grow to a high-water mark and stay), created
 // on first use.  Never destroyed: the engines' arenas may be gone by the time static destructors run at exit.
 template <class Ws>

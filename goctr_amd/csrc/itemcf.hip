@@ -126,16 +126,18 @@ struct IcfScratch : IcfReduceScratch {
 
 // --------------------------------------------------------------------------------------------------------------- recall
 // One workgroup per request row.
-//   1. the history: the first H valid entries the timestamp filter keeps, in sequence order (ballots + a scan of the wave counts)
+//   1. the history: the first H valid entries the timestamp filter keeps, in sequence order (lds_gather_history)
 //   2. the row's n_h * M list entries are summed per candidate in an LDS hash table (RC_TABLE slots, linear probing, the item
 //      claimed by a compare-and-swap, the weight added by an atomic: an integer sum, so the arrival order cannot show).  The
 //      table holds at most RC_LIMIT candidates, so the candidates are taken in TILES, ranges [lo, hi) of item ids: a range is
 //      accumulated whole -- every entry of the row's lists whose item falls in it -- and a range that overflows is dropped and
 //      split in two.  A candidate's sum is complete whatever range it came in, so no output depends on the tiling.
 //   3. the sequence entries the exclusion mode looks at mark their table slot (bit 31 of the slot's item)
-//   4. the table's candidates join the row's running list by the key (S << 32) | ~item (topn.h: sel_append / sel_sort_trim)
-constexpr int RC_TABLE = 8192, RC_TABLE_BITS = 13, RC_LIMIT = 6144, RC_STACK = 48;
-constexpr unsigned int RC_EMPTY = 0xffffffffu;
+//   4. the table's candidates join the row's running list by the key (S << 32) | ~item (lds_lists.h: sel_append / sel_sort_trim)
+constexpr int RC_TABLE_BITS = 13, RC_LIMIT = 6144, RC_STACK = 48;
+using RcTable = LdsItemTable<RC_TABLE_BITS>;
+constexpr int RC_TABLE = RcTable::SIZE;
+constexpr unsigned int RC_EMPTY = RcTable::EMPTY;
 constexpr int RC_MAX_H = 256, RC_MAX_CAND = 1024;
 static_assert(SEL_CAP >= RC_MAX_CAND + SEL_THREADS, "a trimmed list and one tile of the table must fit");
 static_assert(RC_LIMIT + SEL_THREADS < RC_TABLE, "threads that pass the limit together must still find free slots");
@@ -151,8 +153,6 @@ struct RecallArgs {
   int32_t* out_items; unsigned int* out_w; int32_t* out_count; int32_t* out_tpos;   // device; out_tpos may be null
 };
 
-__device__ inline unsigned int rc_hash(unsigned int j) { return (j * 2654435761u) >> (32 - RC_TABLE_BITS); }
-
 __global__ __launch_bounds__(SEL_THREADS) void icf_recall_kernel(RecallArgs a) {
   __shared__ unsigned int tkey[RC_TABLE], tsum[RC_TABLE];
   __shared__ unsigned long long skey[SEL_CAP];
@@ -162,7 +162,7 @@ __global__ __launch_bounds__(SEL_THREADS) void icf_recall_kernel(RecallArgs a) {
   __shared__ int st_lo[RC_STACK], st_hi[RC_STACK];
   __shared__ int s_sp, s_fill, s_distinct, s_over, s_tpos;
   __shared__ unsigned long long s_thr;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const long long q = blockIdx.x;
   const bool has_t = a.targets != nullptr;
   const int tgt = has_t ? a.targets[q] : -1;
@@ -171,23 +171,7 @@ __global__ __launch_bounds__(SEL_THREADS) void icf_recall_kernel(RecallArgs a) {
   const long long mts = a.ts[q];
 
   // 1. history
-  int nh = 0;
-  for (long long p0 = 0; p0 < len && nh < a.H; p0 += SEL_THREADS) {
-    const long long p = p0 + tid;
-    int it = -1;
-    if (p < len && (mts == 0 || a.seq_ts[lo_e + p] <= mts)) it = a.seq_items[lo_e + p];
-    const bool valid = it >= 0 && it < a.n_items;
-    const unsigned long long b = __ballot(valid);
-    if (lane == 0) wcnt[wave] = __popcll(b);
-    __syncthreads();
-    int base = nh, tot = 0;
-    for (int w = 0; w < SEL_THREADS / 64; ++w) { if (w < wave) base += wcnt[w]; tot += wcnt[w]; }
-    const int r = base + __popcll(b & ((1ull << lane) - 1ull));
-    if (valid && r < a.H) hist[r] = it;
-    nh += tot;
-    __syncthreads();
-  }
-  if (nh > a.H) nh = a.H;
+  const int nh = lds_gather_history<SEL_THREADS / 64>(a.seq_items, a.seq_ts, lo_e, len, mts, a.n_items, a.H, hist, wcnt);
   const int n_entries = nh * a.M;
   const int step_t = SEL_THREADS / a.M, step_c = SEL_THREADS - step_t * a.M;
   if (tid == 0) {
@@ -219,17 +203,10 @@ __global__ __launch_bounds__(SEL_THREADS) void icf_recall_kernel(RecallArgs a) {
       const int j = a.nbr_items[at];
       if (j < lo || j >= hi) continue;         // (padding is -1 < lo)
       const unsigned int w = a.nbr_w[at];
-      unsigned int slot = rc_hash((unsigned int)j);
-      for (;;) {
-        const unsigned int prev = atomicCAS(&tkey[slot], RC_EMPTY, (unsigned int)j);
-        if (prev == RC_EMPTY) {
-          if (atomicAdd(&s_distinct, 1) >= RC_LIMIT) s_over = 1;
-          atomicAdd(&tsum[slot], w);
-          break;
-        }
-        if (prev == (unsigned int)j) { atomicAdd(&tsum[slot], w); break; }
-        slot = (slot + 1) & (RC_TABLE - 1);
-      }
+      bool fresh;
+      const unsigned int slot = RcTable::claim(tkey, (unsigned int)j, &fresh);
+      if (fresh && atomicAdd(&s_distinct, 1) >= RC_LIMIT) s_over = 1;
+      atomicAdd(&tsum[slot], w);
     }
     __syncthreads();
     if (s_over) {                              // (uniform) too many candidates for one tile: halve the range
@@ -248,13 +225,7 @@ __global__ __launch_bounds__(SEL_THREADS) void icf_recall_kernel(RecallArgs a) {
         const int it = a.seq_items[lo_e + p];
         if (it < lo || it >= hi || it >= a.n_items) continue;
         if (before && mts != 0 && a.seq_ts[lo_e + p] > mts) continue;
-        unsigned int slot = rc_hash((unsigned int)it);
-        for (;;) {
-          const unsigned int k = tkey[slot];
-          if (k == RC_EMPTY) break;
-          if ((k & 0x7fffffffu) == (unsigned int)it) { atomicOr(&tkey[slot], 0x80000000u); break; }
-          slot = (slot + 1) & (RC_TABLE - 1);
-        }
+        RcTable::mark_seen(tkey, (unsigned int)it);
       }
       __syncthreads();
     }
@@ -276,24 +247,7 @@ __global__ __launch_bounds__(SEL_THREADS) void icf_recall_kernel(RecallArgs a) {
   }
 
   sel_sort_trim(skey, sraw, &s_fill, &s_thr, a.n_cand);
-  const int fill = s_fill;
-  for (int i = tid; i < a.n_cand; i += SEL_THREADS) {
-    const long long o = q * a.stride + i;
-    if (i < fill) {
-      const int item = (int)~(unsigned int)skey[i];
-      a.out_items[o] = item;
-      a.out_w[o] = (unsigned int)(skey[i] >> 32);
-      if (has_t && item == tgt) s_tpos = i;                          // (items are distinct: one writer at most)
-    } else {
-      a.out_items[o] = -1;
-      a.out_w[o] = 0u;
-    }
-  }
-  __syncthreads();
-  if (tid == 0) {
-    a.out_count[q] = fill;
-    if (a.out_tpos) a.out_tpos[q] = s_tpos;
-  }
+  sel_write_row(skey, s_fill, a.n_cand, q * a.stride, q, has_t, tgt, &s_tpos, a.out_items, a.out_w, a.out_count, a.out_tpos);
 }
 
 // ------------------------------------------------------------------------------------------------------------ recommend
@@ -361,12 +315,6 @@ __global__ __launch_bounds__(SEL_THREADS) void icf_select_kernel(IcfSelArgs a) {
     if (n_fail) atomicAdd(a.n_failed, (unsigned long long)n_fail);
   }
 }
-
-// drains the stream before the call's device buffers go back to the arena, on every path out of the call
-struct Drain {
-  hipStream_t s;
-  ~Drain() { (void)hipStreamSynchronize(s); }
-};
 
 }  // namespace
 
@@ -450,7 +398,7 @@ int recall_rank_run(const TopnScorer& sc, const char* who, const ItemcfRecArgs& 
   std::vector<unsigned char> h_osrc, h_csrc;
   std::vector<long long> h_pre((size_t)nq + 1), h_rank((size_t)nq);
   unsigned long long h_nfailed = 0;
-  Drain drain{st};                                        // (declared behind the buffers: runs before they are released)
+  StreamDrain drain{st};                                  // (declared behind the buffers: runs before they are released)
   if (in.stage(a.users, a.ts, a.targets, nq, st)) return -1;
   if (c_items.alloc((size_t)nq * nc, false) || c_w.alloc((size_t)nq * nc, false) || c_count.alloc((size_t)nq, false) ||
       c_tpos.alloc((size_t)nq, false) || d_pre.alloc((size_t)nq + 1, false) || o_items.alloc((size_t)nq * k, false) ||

@@ -9,8 +9,6 @@
 namespace goctr {
 namespace {
 
-using u64 = unsigned long long;
-
 // head[i] = 1 where a run of equal keys below the sentinel starts (keys ascending)
 __global__ __launch_bounds__(256) void icf_heads_kernel(const u64* __restrict__ keys, long long n, u64 sentinel,
                                                         unsigned int* __restrict__ head) {

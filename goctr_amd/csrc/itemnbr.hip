@@ -9,11 +9,11 @@
 //                       time, 32 per wavefront.  dot = 65536 hi.hi + 256 (hi.lo + lo.hi) + lo.lo from four
 //                       mfma_i32_16x16x64_i8 per K step, combined in wrapping 32-bit arithmetic (the total fits).  The order keys
 //                       (w << 32 | ~j) above a row's threshold join the row's list in LDS; a list that could overflow in the next
-//                       step is sorted and trimmed to n_nbr first (topn.h's scheme with an integer key, one list per row).  The
+//                       step is sorted and trimmed to n_nbr first (inb_trim: lds_lists.h's row trim, one list per row).  The
 //                       lists are read from and written back to HBM once per pass
 //   inb_emit_kernel     key -> nbr_items, nbr_w; nbr_co = the dot again from the planes
-// A and B fragments come from the same planes by the same rule (lane l: row l & 15, 16 consecutive bytes of k from 16 (l >> 4)), so
-// whatever order the instruction takes k in, both operands agree on it.  Keys of one row are distinct (j is in the key), so the
+// A and B fragments come from the same planes by the same rule (itemvec.h: iv_frag), so whatever order the instruction takes k in,
+// both operands agree on it.  Keys of one row are distinct (j is in the key), so the
 // kept set depends on no arrival order, tile size or pass size.
 // Merge (inb_merge_kernel): one workgroup per item, both stored lists in LDS, the union de-duplicated by item, one sort by key.
 #include <algorithm>
@@ -29,10 +29,8 @@ using namespace goctr;
 
 namespace {
 
-using u64 = unsigned long long;
-using i32x4 = __attribute__((ext_vector_type(4))) int;
+using i32x4 = iv_i32x4;
 
-constexpr int NB_K = IV_K;                     // the MFMA's K: D is padded to a multiple
 constexpr int NB_ROWS = 32;                    // query rows of a workgroup
 constexpr int NB_THREADS = 256;
 constexpr int NB_WAVES = NB_THREADS / 64;
@@ -55,11 +53,9 @@ struct PairsArgs {
   u64* n_pairs;
 };
 
-__device__ inline i32x4 inb_frag(const signed char* plane, long long row, int Dp, int ks, int lane) {
-  return *reinterpret_cast<const i32x4*>(plane + (size_t)row * Dp + ks * NB_K + (lane >> 4) * 16);
-}
-
-// every wavefront sorts one row of each group of NB_WAVES rows that holds a row in need (force: all), descending, and trims it
+// lds_lists.h's lds_rows_trim in this kernel's own text (with the shared function the build takes 4 % longer:
+// profiles/recall_refactor.txt): every wavefront sorts one row of each group of NB_WAVES rows that holds a row in need (force: all),
+// descending, and trims it
 __device__ inline void inb_trim(u64* keys, int* s_fill, u64* s_thr, int cap, int n_nbr, bool force) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int g = 0; g < NB_ROWS / NB_WAVES; ++g) {
@@ -71,16 +67,7 @@ __device__ inline void inb_trim(u64* keys, int* s_fill, u64* s_thr, int cap, int
     const int fill = s_fill[row];
     for (int t = fill + lane; t < cap; t += 64) k[t] = 0ull;
     __syncthreads();
-    for (int size = 2; size <= cap; size <<= 1)
-      for (int stride = size >> 1; stride > 0; stride >>= 1) {
-        for (int t = lane; t < (cap >> 1); t += 64) {
-          const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
-          const bool desc = (lo & size) == 0;
-          const u64 a = k[lo], b = k[hi];
-          if (desc ? a < b : a > b) { k[lo] = b; k[hi] = a; }
-        }
-        __syncthreads();
-      }
+    lds_sort_desc(k, cap, lane, 64);
     if (lane == 0) { s_fill[row] = fill < n_nbr ? fill : n_nbr; s_thr[row] = fill >= n_nbr ? k[n_nbr - 1] : 0ull; }
     __syncthreads();
   }
@@ -93,7 +80,7 @@ __global__ __launch_bounds__(NB_THREADS) void inb_pairs_kernel(PairsArgs a) {
   extern __shared__ u64 keys[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long long i0 = (long long)blockIdx.x * NB_ROWS;
-  const int cap = a.cap, KS = a.Dp / NB_K;
+  const int cap = a.cap, KS = a.Dp / IV_K;
   u64* const s_thr = keys + (size_t)NB_ROWS * cap;
   int* const s_fill = reinterpret_cast<int*>(s_thr + NB_ROWS);
 
@@ -111,8 +98,8 @@ __global__ __launch_bounds__(NB_THREADS) void inb_pairs_kernel(PairsArgs a) {
   i32x4 a_hi[2], a_lo[2];
   if (ONE_K)
     for (int m = 0; m < 2; ++m) {
-      a_hi[m] = inb_frag(a.hi, i0 + 16 * m + (lane & 15), a.Dp, 0, lane);
-      a_lo[m] = inb_frag(a.lo, i0 + 16 * m + (lane & 15), a.Dp, 0, lane);
+      a_hi[m] = iv_frag(a.hi, i0 + 16 * m + (lane & 15), a.Dp, 0, lane);
+      a_lo[m] = iv_frag(a.lo, i0 + 16 * m + (lane & 15), a.Dp, 0, lane);
     }
   unsigned int n_ok = 0;
   for (long long cs = a.c0; cs < a.c1; cs += NB_STEP) {
@@ -124,14 +111,16 @@ __global__ __launch_bounds__(NB_THREADS) void inb_pairs_kernel(PairsArgs a) {
       const long long jt = cs + (wave * NB_CT + ct) * 16;
       if (jt >= a.c1) break;                   // (the wavefront's tiles ascend)
       const long long j = jt + (lane & 15);
+      // itemvec.h's product (IvAcc, iv_mfma4, iv_dot) in this kernel's own text: with the accumulators in an IvAcc the compiler moves
+      // them between AGPRs and VGPRs around the MFMAs here, and the build takes 5 % longer (profiles/recall_refactor.txt)
       i32x4 hh[2], x[2], ll[2];
       for (int m = 0; m < 2; ++m) hh[m] = x[m] = ll[m] = i32x4{0, 0, 0, 0};
       for (int ks = 0; ks < KS; ++ks) {
-        const i32x4 b_hi = inb_frag(a.hi, j, a.Dp, ks, lane), b_lo = inb_frag(a.lo, j, a.Dp, ks, lane);
+        const i32x4 b_hi = iv_frag(a.hi, j, a.Dp, ks, lane), b_lo = iv_frag(a.lo, j, a.Dp, ks, lane);
         for (int m = 0; m < 2; ++m) {
           if (!ONE_K) {
-            a_hi[m] = inb_frag(a.hi, i0 + 16 * m + (lane & 15), a.Dp, ks, lane);
-            a_lo[m] = inb_frag(a.lo, i0 + 16 * m + (lane & 15), a.Dp, ks, lane);
+            a_hi[m] = iv_frag(a.hi, i0 + 16 * m + (lane & 15), a.Dp, ks, lane);
+            a_lo[m] = iv_frag(a.lo, i0 + 16 * m + (lane & 15), a.Dp, ks, lane);
           }
           hh[m] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_hi[m], b_hi, hh[m], 0, 0, 0);
           x[m] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_hi[m], b_lo, x[m], 0, 0, 0);
@@ -139,12 +128,11 @@ __global__ __launch_bounds__(NB_THREADS) void inb_pairs_kernel(PairsArgs a) {
           ll[m] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_lo[m], b_lo, ll[m], 0, 0, 0);
         }
       }
-      // C/D: register r of lane l is row 4 (l >> 4) + r, column l & 15
       for (int m = 0; m < 2; ++m)
         for (int r = 0; r < 4; ++r) {
-          const int row = 16 * m + (lane >> 4) * 4 + r;
+          const int row = 16 * m + (lane >> 4) * 4 + r;   // (itemvec.h: the C/D layout)
           const int dot = (int)((unsigned int)hh[m][r] * 65536u + (unsigned int)x[m][r] * 256u + (unsigned int)ll[m][r]);
-          const unsigned int w = dot > 0 ? (unsigned int)dot >> 12 : 0u;
+          const unsigned int w = iv_weight(dot);
           if (w < a.min_w || j == i0 + row || j >= a.c1) continue;      // (rows and columns behind n_items are zero: w = 0)
           ++n_ok;
           const u64 key = ((u64)w << 32) | (u64)(~(unsigned int)j);
@@ -223,17 +211,7 @@ __global__ __launch_bounds__(256) void inb_merge_kernel(MergeArgs a) {
     skey[t] = key; sco[t] = c;
   }
   __syncthreads();
-  for (int size = 2; size <= MG_CAP; size <<= 1)
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      const int t = tid, lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
-      const bool desc = (lo & size) == 0;
-      const u64 ka = skey[lo], kb = skey[hi];
-      if (desc ? ka < kb : ka > kb) {
-        skey[lo] = kb; skey[hi] = ka;
-        const unsigned int ca = sco[lo]; sco[lo] = sco[hi]; sco[hi] = ca;
-      }
-      __syncthreads();
-    }
+  lds_sort_desc(skey, sco, MG_CAP, tid, 256);
   unsigned int stored = 0;
   for (int t = tid; t < a.M; t += 256) {
     const u64 key = skey[t];
@@ -269,7 +247,7 @@ template <class T>
 int build_from_rows(const T* d_rows, int64_t n_items, int D, const goctr_itemnbr_cfg* cfg, NbrBuild& ws, goctr_itemcf* r,
                     const std::function<int()>& rows_done) {
   hipStream_t s = engine().stream;
-  const int M = cfg->n_nbr, Dp = round_up(D, NB_K), cap = nb_cap(M);
+  const int M = cfg->n_nbr, Dp = round_up(D, IV_K), cap = nb_cap(M);
   const size_t plane = ((size_t)n_items + NB_PAD_ROWS) * Dp, nm = (size_t)n_items * M;
   r->n_items = n_items; r->M = M; r->cache_version = 0;
   if (r->cnt.alloc((size_t)n_items, false) || r->nbr_items.alloc(nm, false) || r->nbr_w.alloc(nm, false) ||
@@ -289,7 +267,7 @@ int build_from_rows(const T* d_rows, int64_t n_items, int D, const goctr_itemnbr
   const dim3 grid((unsigned)cdiv(n_items, NB_ROWS));
   for (int64_t c0 = 0; c0 < n_items; c0 += P) {
     a.c0 = c0; a.c1 = std::min(n_items, c0 + P);
-    if (Dp == NB_K) hipLaunchKernelGGL(inb_pairs_kernel<true>, grid, dim3(NB_THREADS), lds, s, a);
+    if (Dp == IV_K) hipLaunchKernelGGL(inb_pairs_kernel<true>, grid, dim3(NB_THREADS), lds, s, a);
     else hipLaunchKernelGGL(inb_pairs_kernel<false>, grid, dim3(NB_THREADS), lds, s, a);
     GOCTR_HIP(hipGetLastError());
   }
@@ -319,7 +297,7 @@ int goctr_itemcf_build_vectors(const double* rows, int64_t n_items, int32_t D, c
   std::unique_ptr<goctr_itemcf> r(new goctr_itemcf);
   NbrBuild ws;
   DevBuf<double> d_rows;
-  DrainMain drain;                             // (behind the buffers: runs before they are released)
+  StreamDrain drain{engine().stream};          // (behind the buffers: runs before they are released)
   if (d_rows.alloc((size_t)n_items * D, false) || d_rows.upload(rows, (size_t)n_items * D)) return -1;
   if (build_from_rows<double>(d_rows.p, n_items, D, cfg, ws, r.get(), [] { return 0; })) return -1;
   *out = r.release();
@@ -354,7 +332,7 @@ int goctr_itemcf_merge(goctr_itemcf* a, goctr_itemcf* b, int32_t mul_a, int32_t 
   hipStream_t s = engine().stream;
   std::unique_ptr<goctr_itemcf> r(new goctr_itemcf);
   DevBuf<u64> n_stored;
-  DrainMain drain;
+  StreamDrain drain{engine().stream};
   const int64_t n = a->n_items;
   const size_t nm = (size_t)n * n_nbr;
   r->n_items = n; r->M = n_nbr; r->total_pairs = a->total_pairs + b->total_pairs;

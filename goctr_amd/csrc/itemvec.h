@@ -1,6 +1,8 @@
-// itemvec.h -- quantised item vectors: the quantise kernel and the table read that goctr_itemcf_build_vectors / _emb (itemnbr.hip)
-// and goctr_itemvec_build_vectors / _emb (rerank.hip) share, and the handle of the latter.  include/goctr.h states the
-// quantisation rule (s, valid, q_d: "Item neighbours from vectors"); tests/itemnbr_ref.py restates it.
+// itemvec.h -- quantised item vectors, the one home of the int8 planes: the quantisation and the hi / lo split, the fragment rule and
+// the four-MFMA product over the planes (itemnbr.hip, uservec.hip, uservec_multi.hip, metrics_list.hip), the quantise kernel and the
+// table read that goctr_itemcf_build_vectors / _emb (itemnbr.hip) and goctr_itemvec_build_vectors / _emb (rerank.hip) share, and the
+// handle of the latter.  include/goctr.h states the quantisation rule (s, valid, q_d: "Item neighbours from vectors");
+// tests/itemnbr_ref.py restates it.
 // A translation unit defines GOCTR_NO_PLAIN_KERNELS in front of this header unless it is ctr.hip (ctr_model.h says why).
 #pragma once
 #include <climits>
@@ -21,7 +23,40 @@ struct goctr_itemvec {
 
 namespace goctr {
 
-constexpr int IV_K = 64;                         // rows of a plane are padded to a multiple: the int8 MFMA's K (itemnbr.hip)
+constexpr int IV_K = 64;                         // rows of a plane are padded to a multiple: the int8 MFMA's K
+using iv_i32x4 = __attribute__((ext_vector_type(4))) int;
+
+// q = rint(x / r * 16384) by pinned float64 operations, and its planes: q = 256 hi + lo, lo in [-128, 127]
+__device__ inline int iv_quant(double x, double r) { return (int)rint(__dmul_rn(__ddiv_rn(x, r), 16384.0)); }
+__device__ inline void iv_split(int q, signed char& hi, signed char& lo) {
+  const int l = ((q + 128) & 255) - 128;
+  hi = (signed char)((q - l) >> 8);
+  lo = (signed char)l;
+}
+
+// THE fragment rule of every int8 product over planes laid out like the item planes: lane l takes the 16 bytes of `row` at K step
+// ks from (l >> 4) * 16 on, as the A and as the B operand alike, so the k order of the instruction cannot show
+__device__ inline iv_i32x4 iv_frag(const signed char* plane, long long row, int Dp, int ks, int lane) {
+  return *reinterpret_cast<const iv_i32x4*>(plane + (size_t)row * Dp + ks * IV_K + (lane >> 4) * 16);
+}
+
+// One 16 x 16 tile of dots of rows a against rows b, q = 256 hi + lo each: dot = 65536 hi.hi + 256 (hi.lo + lo.hi) + lo.lo.
+// C/D: register r of lane l is row 4 (l >> 4) + r, column l & 15
+struct IvAcc {
+  iv_i32x4 hh{0, 0, 0, 0}, x{0, 0, 0, 0}, ll{0, 0, 0, 0};
+};
+// one K step of 64
+__device__ __forceinline__ void iv_mfma4(IvAcc& c, iv_i32x4 a_hi, iv_i32x4 a_lo, iv_i32x4 b_hi, iv_i32x4 b_lo) {
+  c.hh = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_hi, b_hi, c.hh, 0, 0, 0);
+  c.x = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_hi, b_lo, c.x, 0, 0, 0);
+  c.x = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_lo, b_hi, c.x, 0, 0, 0);
+  c.ll = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_lo, b_lo, c.ll, 0, 0, 0);
+}
+// register r's dot, combined in wrapping 32-bit arithmetic (the total fits), and the similarity weight of a dot
+__device__ inline int iv_dot(const IvAcc& c, int r) {
+  return (int)((unsigned int)c.hh[r] * 65536u + (unsigned int)c.x[r] * 256u + (unsigned int)c.ll[r]);
+}
+__device__ inline unsigned int iv_weight(int dot) { return dot > 0 ? (unsigned int)dot >> 12 : 0u; }
 
 // one row per thread: s, r, q (pinned float64 operations), written once as two int8 planes hi / lo with q = 256 hi + lo, lo in
 // [-128, 127], hi in [-64, 64].  The planes were zeroed: an invalid row and the padding behind D keep q = 0
@@ -43,12 +78,7 @@ __global__ __launch_bounds__(256) void iv_quant_kernel(const T* __restrict__ row
   if (!valid) return;                          // (the planes were zeroed: q = 0)
   atomicAdd(n_valid, 1ull);
   const double r = __dsqrt_rn(s);
-  for (int d = 0; d < D; ++d) {
-    const int q = (int)rint(__dmul_rn(__ddiv_rn((double)v[d], r), 16384.0));
-    const int l = ((q + 128) & 255) - 128;
-    hi[(size_t)i * Dp + d] = (signed char)((q - l) >> 8);
-    lo[(size_t)i * Dp + d] = (signed char)l;
-  }
+  for (int d = 0; d < D; ++d) iv_split(iv_quant((double)v[d], r), hi[(size_t)i * Dp + d], lo[(size_t)i * Dp + d]);
 }
 
 // queues the quantise launch over n_items rows at d_rows on the engine stream
@@ -67,17 +97,12 @@ inline int iv_check_shape(int64_t n_items, int64_t D, const char* who) {
   return 0;
 }
 
-// drains the engine stream before a failing build's device buffers go back to the arena
-struct DrainMain {
-  ~DrainMain() { (void)hipStreamSynchronize(engine().stream); }
-};
-
 // An embedding table's rows as a serving pass reads them: under the table's shared lock, behind the last queued write.  Declared
 // behind the build's device buffers: on every path out the stream is drained first, then the lock goes, then the buffers.
 // done() is for the moment the quantise launch, the only reader, has finished: the rest of a build runs without the lock
 struct EmbRowsRead {
   std::shared_lock<std::shared_mutex> lock;
-  DrainMain drain;
+  StreamDrain drain{engine().stream};
   explicit EmbRowsRead(goctr_emb* e) : lock(e->mu) {}
   int wait(goctr_emb* e) {
     if (e->rows_pending.load(std::memory_order_acquire) && e->ev_rows) GOCTR_HIP(hipEventSynchronize(e->ev_rows));

@@ -49,8 +49,7 @@ using namespace goctr;
 
 namespace {
 
-using u64 = unsigned long long;
-using i32x4 = __attribute__((ext_vector_type(4))) int;
+using i32x4 = iv_i32x4;
 
 constexpr int LQ_MAX_K = 256;                  // places of a row: one thread each
 constexpr int LQ_WAVES = MB / 64;
@@ -174,7 +173,7 @@ __global__ __launch_bounds__(MB) void list_row_kernel(ListArgs a) {
     unsigned int* const S = a.sim ? a.sim + (size_t)q * k * k : nullptr;
     for (int t0 = 0; t0 < n_tiles; t0 += LQ_PASS) {
       int ti[LQ_TPW], tj[LQ_TPW];
-      i32x4 hh[LQ_TPW], x[LQ_TPW], ll[LQ_TPW];
+      IvAcc acc[LQ_TPW];                                 // (zero)
 #pragma unroll
       for (int s = 0; s < LQ_TPW; ++s) {                 // tile t of the upper half, row by row: (ti, tj), ti <= tj
         int rem = t0 + wave * LQ_TPW + s, r = 0;
@@ -183,7 +182,6 @@ __global__ __launch_bounds__(MB) void list_row_kernel(ListArgs a) {
           while (rem >= kT - r) { rem -= kT - r; ++r; }
           ti[s] = r; tj[s] = r + rem;
         }
-        hh[s] = x[s] = ll[s] = i32x4{0, 0, 0, 0};
       }
       for (int c = 0; c < chunks; ++c) {
         __syncthreads();                                 // the last chunk has been read
@@ -204,13 +202,10 @@ __global__ __launch_bounds__(MB) void list_row_kernel(ListArgs a) {
           if (ti[s] < 0) continue;                       // (uniform in the wavefront: the MFMAs run with every lane on)
           const i32x4 a_hi = lq_frag(s_hi, ti[s], lane), a_lo = lq_frag(s_lo, ti[s], lane);
           const i32x4 b_hi = lq_frag(s_hi, tj[s], lane), b_lo = lq_frag(s_lo, tj[s], lane);
-          hh[s] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_hi, b_hi, hh[s], 0, 0, 0);
-          x[s] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_hi, b_lo, x[s], 0, 0, 0);
-          x[s] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_lo, b_hi, x[s], 0, 0, 0);
-          ll[s] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_lo, b_lo, ll[s], 0, 0, 0);
+          iv_mfma4(acc[s], a_hi, a_lo, b_hi, b_lo);
         }
       }
-      // C/D: register r of lane l is row 4 (l >> 4) + r of the A tile, column l & 15 (a row of the B tile)
+      // (itemvec.h's C/D layout: the row is one of the A tile, the column a row of the B tile)
 #pragma unroll
       for (int s = 0; s < LQ_TPW; ++s) {
         if (ti[s] < 0) continue;
@@ -218,9 +213,8 @@ __global__ __launch_bounds__(MB) void list_row_kernel(ListArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int pa = 16 * ti[s] + (lane >> 4) * 4 + r;
-          const int dot = (int)((unsigned int)hh[s][r] * 65536u + (unsigned int)x[s][r] * 256u + (unsigned int)ll[s][r]);
           // (an unusable place and a place behind k are rows of zeros: w = 0)
-          const unsigned int w = dot > 0 && pa != pb ? (unsigned int)dot >> 12 : 0u;
+          const unsigned int w = pa != pb ? iv_weight(iv_dot(acc[s], r)) : 0u;
           if (pa < pb) {                                 // every pair once: a diagonal tile holds both halves
             p.sim_sum += w;
             p.sim_max = w > p.sim_max ? w : p.sim_max;
@@ -319,7 +313,7 @@ int goctr_metrics_lists(goctr_itemvec* v, goctr_popular* pop, const int32_t* ite
   std::vector<goctr_list_row> h_rows(rows ? nq : 0);
   ListTotals h_tot{};
   GiniPart h_gini{};
-  DrainMain drain;                             // (behind the buffers: an error return drains the stream before d_sim is freed)
+  StreamDrain drain{engine().stream};          // (behind the buffers: an error return drains the stream before d_sim is freed)
   const int gblocks = metrics_grid(n_items, MB);
   if (w.items.ensure(nq * k, false) || w.count.ensure(nq, false) || (rows && w.rows.ensure(nq, false)) || w.expo.ensure(n, false) ||
       w.sorted.ensure(n, false) || w.part.ensure(MKEY_MAX_BLOCKS + 1, false) || w.totals.ensure(LQ_SLOTS + 1, false) ||

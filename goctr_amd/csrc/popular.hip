@@ -22,8 +22,6 @@ using namespace goctr;
 
 namespace {
 
-using u64 = unsigned long long;
-
 // ---------------------------------------------------------------------------------------------------------------- build
 constexpr int POP_BLOCK = 256, POP_MAX_GRID = 2048;
 
@@ -126,10 +124,12 @@ int bit_length(u64 v) {
 //      exclusion mode looks at mark their item's slot (bit 31), as icf_recall_kernel's step 3 does
 //   3. a position is accepted when it is its item's first, not seen (or the target) and not in the list so far (a second LDS
 //      table of the accepted items, at most n_cand <= 1024 in BL_TABLE slots); its place is the list's fill + the accepted
-//      positions in front of it in the tile, from ballots and a prefix over the wave counts -- never from an atomic counter
+//      positions in front of it in the tile (lds_block_rank) -- never from an atomic counter
 // A part ends when the list reaches its limit or its source ends.  No output depends on the tile size or on arrival order.
-constexpr int BL_TABLE = 2048, BL_BITS = 11;
-constexpr unsigned int BL_EMPTY = 0xffffffffu;
+constexpr int BL_BITS = 11;
+using BlTable = LdsItemTable<BL_BITS>;
+constexpr int BL_TABLE = BlTable::SIZE;
+constexpr unsigned int BL_EMPTY = BlTable::EMPTY;
 static_assert(BL_TABLE >= 2 * SEL_THREADS, "a tile's items, and a full list, fill at most half a table");
 
 struct BlendFillArgs {
@@ -143,28 +143,11 @@ struct BlendFillArgs {
   int32_t* out_items; unsigned int* out_w; unsigned char* out_src; int32_t* out_count; int32_t* out_tpos;   // device
 };
 
-__device__ inline unsigned int bl_hash(unsigned int j) { return (j * 2654435761u) >> (32 - BL_BITS); }
-
-__device__ inline void bl_insert(unsigned int* tab, unsigned int j) {      // j is not in the table
-  unsigned int slot = bl_hash(j);
-  while (atomicCAS(&tab[slot], BL_EMPTY, j) != BL_EMPTY) slot = (slot + 1) & (BL_TABLE - 1);
-}
-
-__device__ inline bool bl_contains(const unsigned int* tab, unsigned int j) {
-  unsigned int slot = bl_hash(j);
-  for (;;) {
-    const unsigned int k = tab[slot];
-    if (k == BL_EMPTY) return false;
-    if (k == j) return true;
-    slot = (slot + 1) & (BL_TABLE - 1);
-  }
-}
-
 __global__ __launch_bounds__(SEL_THREADS) void blend_fill_kernel(BlendFillArgs a) {
   __shared__ unsigned int in_list[BL_TABLE], tkey[BL_TABLE], tpos[BL_TABLE];
   __shared__ int wcnt[SEL_THREADS / 64];
   __shared__ int s_tpos;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const long long q = blockIdx.x, row = q * a.n_cand;
   const bool has_t = a.targets != nullptr;
   const int tgt = has_t ? a.targets[q] : -1;
@@ -177,7 +160,7 @@ __global__ __launch_bounds__(SEL_THREADS) void blend_fill_kernel(BlendFillArgs a
   for (int i = tid; i < BL_TABLE; i += SEL_THREADS) in_list[i] = BL_EMPTY;
   __syncthreads();
   for (int i = tid; i < fill; i += SEL_THREADS) {                    // part A: distinct items
-    bl_insert(in_list, (unsigned int)a.out_items[row + i]);
+    BlTable::insert(in_list, (unsigned int)a.out_items[row + i]);
     a.out_src[row + i] = 0;
   }
   __syncthreads();
@@ -193,12 +176,8 @@ __global__ __launch_bounds__(SEL_THREADS) void blend_fill_kernel(BlendFillArgs a
       const int item = t0 + tid < n_src ? src[t0 + tid] : -1;
       const bool valid = item >= 0 && item < a.n_items;
       if (valid) {
-        unsigned int slot = bl_hash((unsigned int)item);
-        for (;;) {
-          const unsigned int prev = atomicCAS(&tkey[slot], BL_EMPTY, (unsigned int)item);
-          if (prev == BL_EMPTY || prev == (unsigned int)item) { atomicMin(&tpos[slot], (unsigned int)tid); break; }
-          slot = (slot + 1) & (BL_TABLE - 1);
-        }
+        bool fresh;
+        atomicMin(&tpos[BlTable::claim(tkey, (unsigned int)item, &fresh)], (unsigned int)tid);
       }
       __syncthreads();
       // 2. seen
@@ -207,35 +186,25 @@ __global__ __launch_bounds__(SEL_THREADS) void blend_fill_kernel(BlendFillArgs a
           const int it = a.seq_items[lo_e + p];
           if (it < 0 || it >= a.n_items) continue;
           if (before && a.seq_ts[lo_e + p] > mts) continue;
-          unsigned int slot = bl_hash((unsigned int)it);
-          for (;;) {
-            const unsigned int k = tkey[slot];
-            if (k == BL_EMPTY) break;
-            if ((k & 0x7fffffffu) == (unsigned int)it) { atomicOr(&tkey[slot], 0x80000000u); break; }
-            slot = (slot + 1) & (BL_TABLE - 1);
-          }
+          BlTable::mark_seen(tkey, (unsigned int)it);
         }
         __syncthreads();
       }
       // 3. accept in position order
       bool ok = false;
       if (valid) {
-        unsigned int slot = bl_hash((unsigned int)item);
-        while ((tkey[slot] & 0x7fffffffu) != (unsigned int)item) slot = (slot + 1) & (BL_TABLE - 1);   // (it is there)
+        const int slot = BlTable::find(tkey, (unsigned int)item);                                      // (it is there)
         const bool seen = (tkey[slot] >> 31) != 0u;
-        ok = tpos[slot] == (unsigned int)tid && (!seen || (has_t && item == tgt)) && !bl_contains(in_list, (unsigned int)item);
+        ok = tpos[slot] == (unsigned int)tid && (!seen || (has_t && item == tgt)) && !BlTable::contains(in_list, (unsigned int)item);
       }
-      const unsigned long long b = __ballot(ok);
-      if (lane == 0) wcnt[wave] = __popcll(b);
-      __syncthreads();                                               // (every bl_contains above is done: the inserts below may start)
-      int base = fill, tot = 0;
-      for (int w = 0; w < SEL_THREADS / 64; ++w) { if (w < wave) base += wcnt[w]; tot += wcnt[w]; }
-      const int r = base + __popcll(b & ((1ull << lane) - 1ull));
+      // (the rank's barrier: every contains above is done, the inserts below may start; the loop's last barrier frees wcnt)
+      int tot;
+      const int r = fill + lds_block_rank<SEL_THREADS / 64>(ok, wcnt, &tot);
       if (ok && r < limit) {
         a.out_items[row + r] = item;
         a.out_w[row + r] = 0u;
         a.out_src[row + r] = (unsigned char)part;
-        bl_insert(in_list, (unsigned int)item);
+        BlTable::insert(in_list, (unsigned int)item);
         if (has_t && item == tgt) s_tpos = r;                        // (items are distinct: one writer at most)
       }
       fill = fill + tot < limit ? fill + tot : limit;

@@ -6,7 +6,7 @@
 // Build (engine stream, engine lock; _emb: the table's shared lock while the rows are read): itemvec.h's iv_quant_kernel, the one
 // itemnbr.hip quantises with, into the handle's two int8 planes.
 // Selection (mmr_select_kernel): ONE launch for all request rows, one workgroup per row, the k dependent steps inside it.
-//   head     the eligible candidates join topn.h's LDS list by the order key and sel_sort_trim keeps the first `pool`: thread h owns
+//   head     the eligible candidates join lds_lists.h's LDS list by the order key and sel_sort_trim keeps the first `pool`: thread h owns
 //            head candidate h from here on (its place, item, rel, group, pen, its group's count -- all in registers)
 //   step     every remaining thread's key ((uint32)(obj + 2^31) << 32) | ~h is reduced to its maximum per wavefront by shuffles,
 //            then across the 16 wavefronts through LDS (barrier 1).  The winner writes the step's outputs; the workgroup copies the
@@ -28,7 +28,6 @@ using namespace goctr;
 
 namespace {
 
-using u64 = unsigned long long;
 using s16x2 = __attribute__((ext_vector_type(2))) short;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
 
@@ -272,7 +271,7 @@ int goctr_itemvec_build_vectors(const double* rows, int64_t n_items, int32_t D, 
   if (iv_check_shape(n_items, D, who)) return -1;
   std::unique_ptr<goctr_itemvec> r(new goctr_itemvec);
   DevBuf<double> d_rows;
-  DrainMain drain;                             // (behind the buffers: runs before they are released)
+  StreamDrain drain{engine().stream};          // (behind the buffers: runs before they are released)
   if (d_rows.alloc((size_t)n_items * D, false) || d_rows.upload(rows, (size_t)n_items * D)) return -1;
   if (build_from_rows<double>(d_rows.p, n_items, D, groups, r.get(), [] { return 0; })) return -1;
   *out = r.release();
@@ -353,7 +352,7 @@ int goctr_rerank_mmr(goctr_itemvec* v, const int32_t* items, const float* scores
   std::vector<int32_t> h_pos(nq * k), h_obj(nq * k), h_count(nq);
   std::vector<unsigned int> h_pen(nq * k);
   u64 h_nfailed = 0;
-  DrainMain drain;                             // (behind the buffers: an error return drains the stream before they are freed)
+  StreamDrain drain{engine().stream};          // (behind the buffers: an error return drains the stream before they are freed)
   if (d_items.alloc(nq * nc, false) || d_scores.alloc(nq * nc, false) || d_count.alloc(nq, false) || o_pos.alloc(nq * k, false) ||
       o_obj.alloc(nq * k, false) || o_pen.alloc(nq * k, false) || o_count.alloc(nq, false) || d_nfailed.alloc(1)) return -1;
   GOCTR_HIP(hipMemcpyAsync(d_items.p, items, sizeof(int32_t) * nq * nc, hipMemcpyHostToDevice, st));

@@ -250,13 +250,15 @@ __global__ __launch_bounds__(256) void topn_finish_kernel(const unsigned long lo
 // request rows a pass of N rows from flat row r touches
 inline int64_t pass_segments(int64_t r, int64_t N, int64_t n_pool) { return (r + N - 1) / n_pool - r / n_pool + 1; }
 
-// drains the stream before the call's device buffers go back to the arena, on every path out of topn_run
-struct Drain {
-  hipStream_t s;
-  ~Drain() { (void)hipStreamSynchronize(s); }
-};
-
 }  // namespace
+
+int topn_seen_launch(const long long* off, const int32_t* seq_items, const long long* seq_ts, const int32_t* users, const long long* ts,
+                     long long q0, long long n_rows, long long n_items, long long W, bool before, unsigned* bitmap, hipStream_t st) {
+  hipLaunchKernelGGL(topn_seen_kernel, dim3((unsigned)n_rows), dim3(256), 0, st, off, seq_items, seq_ts, users, ts, q0, n_items, W,
+                     before ? 1 : 0, bitmap);
+  GOCTR_HIP(hipGetLastError());
+  return 0;
+}
 
 int topn_check_args(const TopnArgs& a, int64_t n_users) {
   GOCTR_CHECK(a.users && a.out_items && a.out_scores && a.out_count, "goctr_recommend_topn: bad arguments");
@@ -300,7 +302,7 @@ int topn_run(const TopnScorer& sc, const TopnArgs& a) {
   std::vector<unsigned> h_scores;
   std::vector<long long> h_rank;
   unsigned long long h_nfailed = 0;
-  Drain drain{st};                                        // (declared behind the buffers: runs before they are released)
+  StreamDrain drain{st};                                  // (declared behind the buffers: runs before they are released)
   if (d_users.alloc(nq, false) || d_ts.alloc(nq, false) || r_key.alloc((size_t)nq * k, false) || r_raw.alloc((size_t)nq * k, false) ||
       r_count.alloc(nq, false) || d_rank.alloc(nq, false) || d_nfailed.alloc(1, false) || o_items.alloc((size_t)nq * k, false) ||
       o_scores.alloc((size_t)nq * k, false) || o_count.alloc(nq, false) || o_rank.alloc(nq, false)) return -1;
@@ -332,10 +334,8 @@ int topn_run(const TopnScorer& sc, const TopnArgs& a) {
     const int64_t gq1 = std::min(nq, gq0 + group_rows);
     if (seen_test) {
       GOCTR_HIP(hipMemsetAsync(d_bitmap.p, 0, (size_t)(gq1 - gq0) * W * 4, st));
-      hipLaunchKernelGGL(topn_seen_kernel, dim3((unsigned)(gq1 - gq0)), dim3(256), 0, st, sc.ub_off, sc.ub_items, sc.ub_ts, d_users.p,
-                         d_ts.p, (long long)gq0, (long long)sc.n_items, (long long)W,
-                         a.cfg.exclude == GOCTR_TOPN_DROP_SEEN_BEFORE ? 1 : 0, d_bitmap.p);
-      GOCTR_HIP(hipGetLastError());
+      if (topn_seen_launch(sc.ub_off, sc.ub_items, sc.ub_ts, d_users.p, d_ts.p, gq0, gq1 - gq0, sc.n_items, W,
+                           a.cfg.exclude == GOCTR_TOPN_DROP_SEEN_BEFORE, d_bitmap.p, st)) return -1;
     }
     for (int64_t r = gq0 * np, rend = gq1 * np; r < rend;) {
       // the rows a pass scores -- catalogue rows and the target rows behind them -- never exceed P: which forward kernel runs

@@ -247,12 +247,6 @@ struct Payload {
 template <class T>
 void swap_buf(DevBuf<T>& a, DevBuf<T>& b) { std::swap(a.p, b.p); std::swap(a.n, b.n); std::swap(a.owner, b.owner); }
 
-// the stream is idle before the buffers declared in front of this go back to the arena, whichever way the function is left
-struct SyncOnExit {
-  hipStream_t s;
-  ~SyncOnExit() { (void)hipStreamSynchronize(s); }
-};
-
 // a successful call with nothing to change still counts as one
 int ub_bump(goctr_ubcache* c) {
   std::lock_guard<std::mutex> one(c->upd);
@@ -269,7 +263,7 @@ int ub_apply(goctr_ubcache* c, int mode, Payload& pl, int64_t max_len) {
   DevBuf<char> dev;
   DevBuf<long long> noff, nts;
   DevBuf<int32_t> nitems;
-  SyncOnExit idle{s};
+  StreamDrain idle{s};                         // (behind the buffers: the stream is idle before they go back to the arena)
   if (dev.alloc(pl.bytes, false) || noff.alloc((size_t)c->n_users + 1, false) || nitems.alloc((size_t)cap, false) ||
       nts.alloc((size_t)cap, false)) return -1;
   GOCTR_HIP(hipMemcpyAsync(dev.p, pl.buf.data(), pl.upload, hipMemcpyHostToDevice, s));
@@ -436,7 +430,7 @@ int goctr_ubcache_clear(goctr_ubcache* c) {
   std::lock_guard<std::mutex> one(c->upd);
   DevBuf<long long> noff, nts;
   DevBuf<int32_t> nitems;
-  SyncOnExit idle{c->ustream};
+  StreamDrain idle{c->ustream};
   if (noff.alloc((size_t)c->n_users + 1, false) || nitems.alloc(0, false) || nts.alloc(0, false)) return -1;
   GOCTR_HIP(hipMemsetAsync(noff.p, 0, sizeof(long long) * ((size_t)c->n_users + 1), c->ustream));
   GOCTR_HIP(hipStreamSynchronize(c->ustream));

@@ -14,15 +14,7 @@ struct UvScratch {
   DevBuf<unsigned long long> lists;             // [group rows, chunks, n_cand] keys descending, 0 = unused
 };
 
-constexpr int UV_K = 64;                        // the MFMA's K: itemvec.h's IV_K, a plane row's padding (uservec.hip asserts it)
 constexpr int UV_PAD_ROWS = 32;                 // zero rows behind the request planes: partial row tiles read them
-using uv_i32x4 = __attribute__((ext_vector_type(4))) int;
-
-// THE fragment rule of every int8 product over planes laid out like the item planes: lane l takes the 16 bytes of `row` at K step
-// ks from (l >> 4) * 16 on, as the A and as the B operand alike, so the k order of the instruction cannot show
-__device__ inline uv_i32x4 uv_frag(const signed char* plane, long long row, int Dp, int ks, int lane) {
-  return *reinterpret_cast<const uv_i32x4*>(plane + (size_t)row * Dp + ks * UV_K + (lane >> 4) * 16);
-}
 
 // the cfg's ranges (sets the error text)
 int uservec_check_cfg(const goctr_uservec_cfg* ucfg, const char* who);

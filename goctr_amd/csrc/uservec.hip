@@ -4,18 +4,19 @@
 // float64 quantisation all arithmetic is integer.
 //
 // Launches (the caller's stream; request rows are taken in groups whose bitmaps and partial lists fit a scratch budget):
-//   uv_pool_kernel    one workgroup per request row: the history as icf_recall_kernel's step 1 takes it, u_d = the int32 sum of the
-//                     history items' q_d from the planes, s = the sum of u_d^2 (an exact integer), p_d by iv_quant_kernel's pinned
-//                     operations, written as two int8 planes laid out exactly like the item planes
-//   uv_seen_kernel    one workgroup per row of the group: a bitmap over [0, n_items) of the sequence entries the mode looks at
+//   uv_pool_kernel    one workgroup per request row: the history by lds_gather_history, u_d = the int32 sum of the history
+//                     items' q_d from the planes, s = the sum of u_d^2 (an exact integer), p_d by iv_quant's pinned operations,
+//                     written as two int8 planes laid out exactly like the item planes
+//   topn_seen_kernel  (topn.hip) one workgroup per row of the group: a bitmap over [0, n_items) of the sequence entries the mode
+//                     looks at
 //   uv_scan_kernel    grid = column chunks x row tiles, so that one request row still spreads the catalogue over the whole chip.
-//                     Four mfma_i32_16x16x64_i8 per K step as in inb_pairs_kernel (itemnbr.hip), A from the request planes and B
-//                     from the item planes by ONE fragment rule, so the k order of the instruction cannot show.  The keys
+//                     iv_mfma4 per K step as in inb_pairs_kernel (itemnbr.hip), A from the request planes and B from the item
+//                     planes by ONE fragment rule (iv_frag), so the k order of the instruction cannot show.  The keys
 //                     (w << 32 | ~item) of the columns that pass min_w, the row's threshold and the seen test join the row's list
-//                     in LDS; a list that could overflow in the next step is sorted and trimmed to n_cand.  The rows of a
+//                     in LDS; a list that could overflow in the next step is sorted and trimmed to n_cand (lds_rows_trim).  The rows of a
 //                     workgroup follow from n_cand and the call's rows (32 .. 4) so that the lists take 64 KiB at most.  Every (row, chunk) list
 //                     goes to HBM
-//   uv_merge_kernel   one workgroup per row: the best n_cand keys of the row's chunk lists (topn.h's list), taken place by place
+//   uv_merge_kernel   one workgroup per row: the best n_cand keys of the row's chunk lists (lds_lists.h's list), taken place by place
 //                     across the chunks until a place brings nothing above the threshold; then items, w, count and the target's
 //                     place
 // Keys of one row are distinct (the item is in the key), so the kept set depends on no arrival order, chunk size, row grouping or
@@ -33,10 +34,8 @@ using namespace goctr;
 
 namespace {
 
-using u64 = unsigned long long;
-using i32x4 = uv_i32x4;
+using i32x4 = iv_i32x4;
 
-static_assert(UV_K == IV_K, "a plane row is padded to the MFMA's K");
 constexpr int UV_THREADS = 256;
 constexpr int UV_WAVES = UV_THREADS / 64;
 constexpr int UV_CT = 2;                       // 16-column tiles per wavefront and step
@@ -78,31 +77,14 @@ __global__ __launch_bounds__(UV_THREADS) void uv_pool_kernel(PoolArgs a) {
   __shared__ int s_u[UV_MAX_D];
   __shared__ int wcnt[UV_WAVES];
   __shared__ u64 s_sum;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
   const long long q = blockIdx.x;
   long long lo_e = 0, len = 0;
   if (a.off) { const int u = a.users[q]; lo_e = a.off[u]; len = a.off[u + 1] - lo_e; }
   const long long mts = a.ts[q];
   if (tid == 0) s_sum = 0ull;
 
-  // the history: icf_recall_kernel's step 1
-  int nh = 0;
-  for (long long p0 = 0; p0 < len && nh < a.H; p0 += UV_THREADS) {
-    const long long p = p0 + tid;
-    int it = -1;
-    if (p < len && (mts == 0 || a.seq_ts[lo_e + p] <= mts)) it = a.seq_items[lo_e + p];
-    const bool valid = it >= 0 && it < a.n_items;
-    const u64 b = __ballot(valid);
-    if (lane == 0) wcnt[wave] = __popcll(b);
-    __syncthreads();
-    int base = nh, tot = 0;
-    for (int w = 0; w < UV_WAVES; ++w) { if (w < wave) base += wcnt[w]; tot += wcnt[w]; }
-    const int r = base + __popcll(b & ((1ull << lane) - 1ull));
-    if (valid && r < a.H) hist[r] = it;
-    nh += tot;
-    __syncthreads();
-  }
-  if (nh > a.H) nh = a.H;
+  const int nh = lds_gather_history<UV_WAVES>(a.seq_items, a.seq_ts, lo_e, len, mts, a.n_items, a.H, hist, wcnt);
   __syncthreads();
 
   // u_d: |u_d| <= 256 * 16384 = 2^22; the sum of squares below 2^45
@@ -124,30 +106,9 @@ __global__ __launch_bounds__(UV_THREADS) void uv_pool_kernel(PoolArgs a) {
   const bool valid = s > 0ull;
   const double r = __dsqrt_rn((double)s);      // (s < 2^53: the conversion is exact)
   for (int d = tid; d < a.Dp; d += UV_THREADS) {
-    const int p = valid ? (int)rint(__dmul_rn(__ddiv_rn((double)s_u[d], r), 16384.0)) : 0;
-    const int l = ((p + 128) & 255) - 128;
-    a.p_hi[(size_t)q * a.Dp + d] = (signed char)((p - l) >> 8);
-    a.p_lo[(size_t)q * a.Dp + d] = (signed char)l;
+    const int p = valid ? iv_quant((double)s_u[d], r) : 0;
+    iv_split(p, a.p_hi[(size_t)q * a.Dp + d], a.p_lo[(size_t)q * a.Dp + d]);
     if (a.out_p && d < a.D) a.out_p[(size_t)q * a.D + d] = (int16_t)p;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------------- seen
-// bitmap [rows, words] was zeroed; row r of the group is request row q0 + r
-__global__ __launch_bounds__(UV_THREADS) void uv_seen_kernel(const long long* __restrict__ off, const int32_t* __restrict__ seq_items,
-                                                             const long long* __restrict__ seq_ts, long long n_items,
-                                                             const int32_t* __restrict__ users, const long long* __restrict__ ts,
-                                                             long long q0, int before, long long words,
-                                                             unsigned int* __restrict__ bitmap) {
-  const long long r = blockIdx.x, q = q0 + r;
-  const int u = users[q];
-  const long long lo_e = off[u], len = off[u + 1] - lo_e, mts = ts[q];
-  unsigned int* bm = bitmap + (size_t)r * words;
-  for (long long p = threadIdx.x; p < len; p += UV_THREADS) {
-    const int it = seq_items[lo_e + p];
-    if (it < 0 || it >= n_items) continue;
-    if (before && mts != 0 && seq_ts[lo_e + p] > mts) continue;
-    atomicOr(&bm[it >> 5], 1u << (it & 31));
   }
 }
 
@@ -164,34 +125,6 @@ struct ScanArgs {
   u64* lists;                                          // [g_rows, n_chunks, n_cand]
 };
 
-// inb_trim (itemnbr.hip) for R rows: every wavefront sorts one row of each group of UV_WAVES rows that holds a row in need
-// (force: a row with an entry), descending, and trims it to n_cand
-__device__ inline void uv_trim(u64* keys, int* s_fill, u64* s_thr, int R, int cap, int n_cand, bool force) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int g = 0; g < R / UV_WAVES; ++g) {
-    bool need = false;
-    for (int w = 0; w < UV_WAVES; ++w) need = need || s_fill[g * UV_WAVES + w] > (force ? 0 : cap - UV_STEP);
-    if (!need) continue;                       // (uniform: s_fill is read behind a barrier and not written in between)
-    const int row = g * UV_WAVES + wave;
-    u64* k = keys + (size_t)row * cap;
-    const int fill = s_fill[row];
-    for (int t = fill + lane; t < cap; t += 64) k[t] = 0ull;
-    __syncthreads();
-    for (int size = 2; size <= cap; size <<= 1)
-      for (int stride = size >> 1; stride > 0; stride >>= 1) {
-        for (int t = lane; t < (cap >> 1); t += 64) {
-          const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
-          const bool desc = (lo & size) == 0;
-          const u64 x = k[lo], y = k[hi];
-          if (desc ? x < y : x > y) { k[lo] = y; k[hi] = x; }
-        }
-        __syncthreads();
-      }
-    if (lane == 0) { s_fill[row] = fill < n_cand ? fill : n_cand; s_thr[row] = fill >= n_cand ? k[n_cand - 1] : 0ull; }
-    __syncthreads();
-  }
-}
-
 // MT: 16-row MFMA tiles of a workgroup (R = 32: 2; R <= 16: 1 -- the tile's rows from R on are not used).  With one K step the
 // next step's column fragments are fetched before this step's barriers, so their latency hides behind this step's work
 template <bool ONE_K, int MT>
@@ -200,7 +133,7 @@ __global__ __launch_bounds__(UV_THREADS) void uv_scan_kernel(ScanArgs a) {
   // thresholds, fill counts and targets
   extern __shared__ u64 keys[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int R = a.R, cap = a.cap, KS = a.Dp / UV_K;
+  const int R = a.R, cap = a.cap, KS = a.Dp / IV_K;
   const long long chunk = blockIdx.x;
   const int i0 = (int)blockIdx.y * R;                  // first row of the tile, within the group
   const long long c0 = chunk * a.chunk, c1 = c0 + a.chunk < a.n_items ? c0 + a.chunk : a.n_items;
@@ -217,8 +150,8 @@ __global__ __launch_bounds__(UV_THREADS) void uv_scan_kernel(ScanArgs a) {
   i32x4 a_hi[MT], a_lo[MT];
   if (ONE_K)
     for (int m = 0; m < MT; ++m) {
-      a_hi[m] = uv_frag(a.p_hi, arow + 16 * m, a.Dp, 0, lane);
-      a_lo[m] = uv_frag(a.p_lo, arow + 16 * m, a.Dp, 0, lane);
+      a_hi[m] = iv_frag(a.p_hi, arow + 16 * m, a.Dp, 0, lane);
+      a_lo[m] = iv_frag(a.p_lo, arow + 16 * m, a.Dp, 0, lane);
     }
   // (rows behind n_items are clamped, not skipped: a fetch past the chunk's end reads in bounds and is never used)
   const long long jw = (long long)(wave * UV_CT) * 16 + (lane & 15), j_last = a.n_items - 1;
@@ -226,7 +159,7 @@ __global__ __launch_bounds__(UV_THREADS) void uv_scan_kernel(ScanArgs a) {
   if (ONE_K)
     for (int ct = 0; ct < UV_CT; ++ct) {
       const long long j = c0 + jw + ct * 16, jl = j < j_last ? j : j_last;
-      n_hi[ct] = uv_frag(a.hi, jl, a.Dp, 0, lane); n_lo[ct] = uv_frag(a.lo, jl, a.Dp, 0, lane);
+      n_hi[ct] = iv_frag(a.hi, jl, a.Dp, 0, lane); n_lo[ct] = iv_frag(a.lo, jl, a.Dp, 0, lane);
     }
   for (long long cs = c0; cs < c1; cs += UV_STEP) {
     i32x4 c_hi[UV_CT], c_lo[UV_CT];
@@ -234,12 +167,13 @@ __global__ __launch_bounds__(UV_THREADS) void uv_scan_kernel(ScanArgs a) {
       for (int ct = 0; ct < UV_CT; ++ct) {
         c_hi[ct] = n_hi[ct]; c_lo[ct] = n_lo[ct];
         const long long j = cs + UV_STEP + jw + ct * 16, jl = j < j_last ? j : j_last;
-        n_hi[ct] = uv_frag(a.hi, jl, a.Dp, 0, lane); n_lo[ct] = uv_frag(a.lo, jl, a.Dp, 0, lane);
+        n_hi[ct] = iv_frag(a.hi, jl, a.Dp, 0, lane); n_lo[ct] = iv_frag(a.lo, jl, a.Dp, 0, lane);
       }
     // every wavefront's appends of the last step are in LDS before the fills are looked at: the decision below is taken on the
     // fills' final values, and its own barrier keeps this step's appends behind the look
     __syncthreads();
-    if (__syncthreads_or(tid < R && s_fill[tid] > cap - UV_STEP)) uv_trim(keys, s_fill, s_thr, R, cap, a.n_cand, false);
+    if (__syncthreads_or(tid < R && s_fill[tid] > cap - UV_STEP))
+      lds_rows_trim<UV_WAVES, UV_STEP>(keys, s_fill, s_thr, R, cap, a.n_cand, false);
     for (int ct = 0; ct < UV_CT; ++ct) {
       const long long jt = cs + (wave * UV_CT + ct) * 16;
       if (jt >= c1) break;                     // (the wavefront's tiles ascend)
@@ -253,28 +187,22 @@ __global__ __launch_bounds__(UV_THREADS) void uv_scan_kernel(ScanArgs a) {
           const int row = 16 * m + (lane >> 4) * 4 + r;
           seen_w[m][r] = a.bitmap && row < n_rows && j < c1 ? a.bitmap[(size_t)(i0 + row) * a.words + (j >> 5)] : 0u;
         }
-      i32x4 hh[MT], x[MT], ll[MT];
-      for (int m = 0; m < MT; ++m) hh[m] = x[m] = ll[m] = i32x4{0, 0, 0, 0};
+      IvAcc acc[MT];
       for (int ks = 0; ks < KS; ++ks) {
-        const i32x4 b_hi = ONE_K ? c_hi[ct] : uv_frag(a.hi, jl, a.Dp, ks, lane);
-        const i32x4 b_lo = ONE_K ? c_lo[ct] : uv_frag(a.lo, jl, a.Dp, ks, lane);
+        const i32x4 b_hi = ONE_K ? c_hi[ct] : iv_frag(a.hi, jl, a.Dp, ks, lane);
+        const i32x4 b_lo = ONE_K ? c_lo[ct] : iv_frag(a.lo, jl, a.Dp, ks, lane);
         for (int m = 0; m < MT; ++m) {
           if (!ONE_K) {
-            a_hi[m] = uv_frag(a.p_hi, arow + 16 * m, a.Dp, ks, lane);
-            a_lo[m] = uv_frag(a.p_lo, arow + 16 * m, a.Dp, ks, lane);
+            a_hi[m] = iv_frag(a.p_hi, arow + 16 * m, a.Dp, ks, lane);
+            a_lo[m] = iv_frag(a.p_lo, arow + 16 * m, a.Dp, ks, lane);
           }
-          hh[m] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_hi[m], b_hi, hh[m], 0, 0, 0);
-          x[m] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_hi[m], b_lo, x[m], 0, 0, 0);
-          x[m] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_lo[m], b_hi, x[m], 0, 0, 0);
-          ll[m] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_lo[m], b_lo, ll[m], 0, 0, 0);
+          iv_mfma4(acc[m], a_hi[m], a_lo[m], b_hi, b_lo);
         }
       }
-      // C/D: register r of lane l is row 4 (l >> 4) + r, column l & 15
       for (int m = 0; m < MT; ++m)
         for (int r = 0; r < 4; ++r) {
-          const int row = 16 * m + (lane >> 4) * 4 + r;
-          const int dot = (int)((unsigned int)hh[m][r] * 65536u + (unsigned int)x[m][r] * 256u + (unsigned int)ll[m][r]);
-          const unsigned int w = dot > 0 ? (unsigned int)dot >> 12 : 0u;
+          const int row = 16 * m + (lane >> 4) * 4 + r;   // (itemvec.h: the C/D layout)
+          const unsigned int w = iv_weight(iv_dot(acc[m], r));
           if (w < a.min_w || row >= n_rows || j >= c1) continue;
           const u64 key = ((u64)w << 32) | (u64)(~(unsigned int)j);
           if (key <= s_thr[row]) continue;
@@ -284,7 +212,7 @@ __global__ __launch_bounds__(UV_THREADS) void uv_scan_kernel(ScanArgs a) {
     }
   }
   __syncthreads();
-  uv_trim(keys, s_fill, s_thr, R, cap, a.n_cand, true);
+  lds_rows_trim<UV_WAVES, UV_STEP>(keys, s_fill, s_thr, R, cap, a.n_cand, true);
   for (int e = tid; e < n_rows * a.n_cand; e += UV_THREADS) {
     const int row = e / a.n_cand, t = e - row * a.n_cand;
     a.lists[((size_t)(i0 + row) * a.n_chunks + chunk) * a.n_cand + t] = t < s_fill[row] ? keys[(size_t)row * cap + t] : 0ull;
@@ -332,24 +260,7 @@ __global__ __launch_bounds__(SEL_THREADS) void uv_merge_kernel(MergeArgs a) {
     if (!any) break;                           // (uniform: sel_append returns the same in every thread)
   }
   sel_sort_trim(skey, sraw, &s_fill, &s_thr, a.n_cand);
-  const int fill = s_fill;
-  for (int i = tid; i < a.n_cand; i += SEL_THREADS) {
-    const long long o = q * a.stride + i;
-    if (i < fill) {
-      const int item = (int)~(unsigned int)skey[i];
-      a.out_items[o] = item;
-      a.out_w[o] = (unsigned int)(skey[i] >> 32);
-      if (has_t && item == tgt) s_tpos = i;                          // (items are distinct: one writer at most)
-    } else {
-      a.out_items[o] = -1;
-      a.out_w[o] = 0u;
-    }
-  }
-  __syncthreads();
-  if (tid == 0) {
-    a.out_count[q] = fill;
-    if (a.out_tpos) a.out_tpos[q] = s_tpos;
-  }
+  sel_write_row(skey, s_fill, a.n_cand, q * a.stride, q, has_t, tgt, &s_tpos, a.out_items, a.out_w, a.out_count, a.out_tpos);
 }
 
 template <class Kern>
@@ -431,10 +342,8 @@ int uservec_scan_planes(const goctr_itemvec* v, const long long* off, const int3
     const int g_rows = (int)std::min<int64_t>(G, nq - q0);
     if (seen) {
       GOCTR_HIP(hipMemsetAsync(ws.bitmap.p, 0, (size_t)g_rows * words * 4, st));
-      hipLaunchKernelGGL(uv_seen_kernel, dim3((unsigned)g_rows), dim3(UV_THREADS), 0, st, off, seq_items, seq_ts, (long long)V,
-                         in.users, in.ts, (long long)q0, cfg.exclude == GOCTR_TOPN_DROP_SEEN_BEFORE ? 1 : 0, (long long)words,
-                         ws.bitmap.p);
-      GOCTR_HIP(hipGetLastError());
+      if (topn_seen_launch(off, seq_items, seq_ts, in.users, in.ts, q0, g_rows, V, words, cfg.exclude == GOCTR_TOPN_DROP_SEEN_BEFORE,
+                           ws.bitmap.p, st)) return -1;
     }
     ScanArgs a{};
     a.p_hi = p_hi; a.p_lo = p_lo; a.hi = v->hi.p; a.lo = v->lo.p; a.Dp = Dp; a.n_items = V; a.chunk = chunk;
@@ -442,7 +351,7 @@ int uservec_scan_planes(const goctr_itemvec* v, const long long* off, const int3
     a.bitmap = seen ? ws.bitmap.p : nullptr; a.words = words; a.targets = in.targets;
     a.lists = ws.lists.p;
     const dim3 grid((unsigned)n_chunks, (unsigned)cdiv(g_rows, R));
-    const bool one_k = Dp == UV_K;
+    const bool one_k = Dp == IV_K;
     int rc;
     if (R == 32) rc = one_k ? scan_launch(uv_scan_kernel<true, 2>, grid, lds, st, a) : scan_launch(uv_scan_kernel<false, 2>, grid, lds, st, a);
     else rc = one_k ? scan_launch(uv_scan_kernel<true, 1>, grid, lds, st, a) : scan_launch(uv_scan_kernel<false, 1>, grid, lds, st, a);

@@ -4,9 +4,9 @@
 // them on the host, bit for bit).  goctr_recommend_uservec_multi (serve.hip) ranks the result with the model.
 //
 // Launches (the caller's stream; request rows are taken in blocks whose virtual rows fit the scratch budget of uservec.hip):
-//   uv_interests_kernel  one workgroup per request row: the history as uv_pool_kernel takes it; farthest-point seeds, then
+//   uv_interests_kernel  one workgroup per request row: the history by lds_gather_history; farthest-point seeds, then
 //                        {assign, re-centre} rounds.  The products -- history rows [n <= 256, Dp] against the 8 centres -- come out
-//                        of mfma_i32_16x16x64_i8 over the two int8 planes by uv_frag's rule: a wavefront takes 16 history rows at a
+//                        of iv_mfma4 over the two int8 planes by iv_frag's rule: a wavefront takes 16 history rows at a
 //                        time as A and the centres (LDS, columns 8 .. 15 zero) as B.  The history's planes are staged in LDS when
 //                        they fit UM_STAGE_BYTES and read from the item planes otherwise; the arithmetic is the same integers
 //                        either way.  (A plain-integer form of the products -- a thread per (row, centre) pair -- gives the same
@@ -18,7 +18,7 @@
 //   uv_mix_kernel        one workgroup per request row over the row's <= 8 x 1024 merged candidates, as u64 keys in LDS.  MAX: a
 //                        sort on (item, w, rank) folds an item's occurrences to its largest weight and lowest such rank, a second
 //                        on (w, ~item) orders the survivors.  QUOTA: a sort on (vt, rank, place) gives every entry its turn o, a
-//                        second on (item, o) marks first occurrences, and a ballot scan over the turns compacts them.  Items, w,
+//                        second on (item, o) marks first occurrences, and lds_block_rank over the turns compacts them.  Items, w,
 //                        owner, count and the target's place go to the caller's stride
 // Sort keys of one row are distinct, the sums are integer and each LDS word has one writer between barriers (the atomics are
 // integer adds, mins and ors), so no output byte depends on an arrival order.
@@ -35,8 +35,7 @@ using namespace goctr;
 
 namespace {
 
-using u64 = unsigned long long;
-using i32x4 = uv_i32x4;
+using i32x4 = iv_i32x4;
 
 constexpr int UM_THREADS = 256;
 constexpr int UM_WAVES = UM_THREADS / 64;
@@ -82,28 +81,24 @@ struct IntLds {
   IntSmall* s; int* u; signed char* c_hi; signed char* c_lo; signed char* h_hi; signed char* h_lo;
 };
 
-// dots[t][m] for every history row t < n and centre m < UM_MAX_K.  C/D: register r of lane l is row 4 (l >> 4) + r, column l & 15
+// dots[t][m] for every history row t < n and centre m < UM_MAX_K (itemvec.h: the product and its C/D layout)
 __device__ inline void um_products(const IntArgs& a, const IntLds& L, int n) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, KS = a.Dp / UV_K, m = lane & 15;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, KS = a.Dp / IV_K, m = lane & 15;
   for (int tile = wave; tile * 16 < n; tile += UM_WAVES) {
     const int t = tile * 16 + (lane & 15), tc = t < n ? t : n - 1;            // (rows behind n repeat the last one and are not kept)
     const signed char* a_hi_p = a.stage ? L.h_hi : a.hi;
     const signed char* a_lo_p = a.stage ? L.h_lo : a.lo;
     const long long arow = a.stage ? tc : L.s->hist[tc];
-    i32x4 hh{0, 0, 0, 0}, x{0, 0, 0, 0}, ll{0, 0, 0, 0};
+    IvAcc acc;
     for (int ks = 0; ks < KS; ++ks) {
-      const i32x4 a_hi = uv_frag(a_hi_p, arow, a.Dp, ks, lane), a_lo = uv_frag(a_lo_p, arow, a.Dp, ks, lane);
+      const i32x4 a_hi = iv_frag(a_hi_p, arow, a.Dp, ks, lane), a_lo = iv_frag(a_lo_p, arow, a.Dp, ks, lane);
       i32x4 b_hi{0, 0, 0, 0}, b_lo{0, 0, 0, 0};
-      if (m < UM_MAX_K) { b_hi = uv_frag(L.c_hi, m, a.Dp, ks, lane); b_lo = uv_frag(L.c_lo, m, a.Dp, ks, lane); }
-      hh = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_hi, b_hi, hh, 0, 0, 0);
-      x = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_hi, b_lo, x, 0, 0, 0);
-      x = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_lo, b_hi, x, 0, 0, 0);
-      ll = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_lo, b_lo, ll, 0, 0, 0);
+      if (m < UM_MAX_K) { b_hi = iv_frag(L.c_hi, m, a.Dp, ks, lane); b_lo = iv_frag(L.c_lo, m, a.Dp, ks, lane); }
+      iv_mfma4(acc, a_hi, a_lo, b_hi, b_lo);
     }
     for (int r = 0; r < 4; ++r) {
       const int row = tile * 16 + (lane >> 4) * 4 + r;
-      if (m < UM_MAX_K && row < n)
-        L.s->dots[row * UM_MAX_K + m] = (int)((unsigned int)hh[r] * 65536u + (unsigned int)x[r] * 256u + (unsigned int)ll[r]);
+      if (m < UM_MAX_K && row < n) L.s->dots[row * UM_MAX_K + m] = iv_dot(acc, r);
     }
   }
 }
@@ -166,12 +161,8 @@ __device__ inline void um_recentre(const IntArgs& a, const IntLds& L, int n, int
   for (int m = 0; m < K; ++m) {
     const bool live = (alive >> m) & 1;
     const double r = __dsqrt_rn((double)L.s->s_s[m]);      // uv_pool_kernel's operations (s < 2^53: the conversion is exact)
-    for (int d = tid; d < a.Dp; d += UM_THREADS) {
-      const int p = live ? (int)rint(__dmul_rn(__ddiv_rn((double)L.u[m * a.Dp + d], r), 16384.0)) : 0;
-      const int l = ((p + 128) & 255) - 128;
-      L.c_hi[m * a.Dp + d] = (signed char)((p - l) >> 8);
-      L.c_lo[m * a.Dp + d] = (signed char)l;
-    }
+    for (int d = tid; d < a.Dp; d += UM_THREADS)
+      iv_split(live ? iv_quant((double)L.u[m * a.Dp + d], r) : 0, L.c_hi[m * a.Dp + d], L.c_lo[m * a.Dp + d]);
   }
   __syncthreads();
 }
@@ -186,7 +177,7 @@ __global__ __launch_bounds__(UM_THREADS) void uv_interests_kernel(IntArgs a) {
   L.h_hi = L.c_lo + (size_t)UM_MAX_K * a.Dp;
   L.h_lo = L.h_hi + (size_t)a.H * a.Dp;
   IntSmall* const S = L.s;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const long long q = blockIdx.x;
   long long lo_e = 0, len = 0;
   if (a.off) { const int u = a.users[q]; lo_e = a.off[u]; len = a.off[u + 1] - lo_e; }
@@ -196,24 +187,7 @@ __global__ __launch_bounds__(UM_THREADS) void uv_interests_kernel(IntArgs a) {
   S->asg[tid] = -2; S->cover[tid] = 0u; S->nonnull[tid] = 0;
   for (int e = tid; e < UM_MAX_K * a.Dp; e += UM_THREADS) { L.c_hi[e] = 0; L.c_lo[e] = 0; }
 
-  // the history: uv_pool_kernel's, which is icf_recall_kernel's step 1
-  int nh = 0;
-  for (long long p0 = 0; p0 < len && nh < a.H; p0 += UM_THREADS) {
-    const long long p = p0 + tid;
-    int it = -1;
-    if (p < len && (mts == 0 || a.seq_ts[lo_e + p] <= mts)) it = a.seq_items[lo_e + p];
-    const bool valid = it >= 0 && it < a.n_items;
-    const u64 b = __ballot(valid);
-    if (lane == 0) S->wcnt[wave] = __popcll(b);
-    __syncthreads();
-    int base = nh, tot = 0;
-    for (int w = 0; w < UM_WAVES; ++w) { if (w < wave) base += S->wcnt[w]; tot += S->wcnt[w]; }
-    const int r = base + __popcll(b & ((1ull << lane) - 1ull));
-    if (valid && r < a.H) S->hist[r] = it;
-    nh += tot;
-    __syncthreads();
-  }
-  const int n = nh > a.H ? a.H : nh;
+  const int n = lds_gather_history<UM_WAVES>(a.seq_items, a.seq_ts, lo_e, len, mts, a.n_items, a.H, S->hist, S->wcnt);
   __syncthreads();
   if (tid < n) {
     const int nn = a.valid[S->hist[tid]] != 0u;            // (a valid row has an entry of at least 16384 / sqrt(D): x != 0)
@@ -236,11 +210,7 @@ __global__ __launch_bounds__(UM_THREADS) void uv_interests_kernel(IntArgs a) {
   if (pick != 0xffffffffu) {
     for (;;) {
       const int seed = (int)(pick & 511u);
-      for (int d = tid; d < a.Dp; d += UM_THREADS) {
-        const int xv = um_x(a, L, seed, d), l = ((xv + 128) & 255) - 128;
-        L.c_hi[K * a.Dp + d] = (signed char)((xv - l) >> 8);
-        L.c_lo[K * a.Dp + d] = (signed char)l;
-      }
+      for (int d = tid; d < a.Dp; d += UM_THREADS) iv_split(um_x(a, L, seed, d), L.c_hi[K * a.Dp + d], L.c_lo[K * a.Dp + d]);
       if (tid == 0) S->s_min = 0xffffffffu;
       ++K;
       __syncthreads();
@@ -249,7 +219,7 @@ __global__ __launch_bounds__(UM_THREADS) void uv_interests_kernel(IntArgs a) {
       if (K == a.K) break;
       if (tid < n && S->nonnull[tid]) {
         const int dot = S->dots[tid * UM_MAX_K + K - 1];
-        const unsigned int w = dot > 0 ? (unsigned int)dot >> 12 : 0u;
+        const unsigned int w = iv_weight(dot);
         const unsigned int cv = w > S->cover[tid] ? w : S->cover[tid];
         S->cover[tid] = cv;
         atomicMin(&S->s_min, (cv << 9) | (unsigned int)tid);   // (cv < 2^17: the smallest cover, then the lowest t)
@@ -321,19 +291,8 @@ struct MixArgs {
   int32_t* out_count; int32_t* out_tpos;                                     // out_tpos may be null
 };
 
-// descending bitonic sort of k[0, n), n a power of two, by the whole workgroup
-__device__ inline void um_sort(u64* k, int n) {
-  for (int size = 2; size <= n; size <<= 1)
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = threadIdx.x; t < (n >> 1); t += UM_THREADS) {
-        const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
-        const bool desc = (lo & size) == 0;
-        const u64 x = k[lo], y = k[hi];
-        if (desc ? x < y : x > y) { k[lo] = y; k[hi] = x; }
-      }
-      __syncthreads();
-    }
-}
+// descending sort of k[0, n), n a power of two, by the whole workgroup
+__device__ inline void um_sort(u64* k, int n) { lds_sort_desc(k, n, threadIdx.x, UM_THREADS); }
 
 constexpr u64 UM_TURN_TOP = (1ull << 41) - 1ull;   // a turn's value (vt:27, rank:3, place:10) is below 2^40: the key is never 0
 
@@ -344,7 +303,7 @@ __global__ __launch_bounds__(UM_THREADS) void uv_mix_kernel(MixArgs a) {
   int& s_tpos = s_small[0];
   int& s_total = s_small[1];
   int* const s_wcnt = s_small + 4;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const long long q = blockIdx.x;
   const int nc = a.n_cand, ni = a.n_int[q];
   const size_t v0 = (size_t)q * a.K;
@@ -448,12 +407,8 @@ __global__ __launch_bounds__(UM_THREADS) void uv_mix_kernel(MixArgs a) {
   for (int o0 = 0; o0 < N && base < nc; o0 += UM_THREADS) {
     const int o = o0 + tid;
     const bool f = o < N && first[o] != 0;
-    const u64 b = __ballot(f);
-    if (lane == 0) s_wcnt[wave] = __popcll(b);
-    __syncthreads();
-    int pos = base, tot = 0;
-    for (int w = 0; w < UM_WAVES; ++w) { if (w < wave) pos += s_wcnt[w]; tot += s_wcnt[w]; }
-    pos += __popcll(b & ((1ull << lane) - 1ull));
+    int tot;
+    const int pos = base + lds_block_rank<UM_WAVES>(f, s_wcnt, &tot);
     if (f && pos < nc) {
       const u64 turn = UM_TURN_TOP - A[o];
       const int r = (int)((turn >> 10) & 7ull), t = (int)(turn & 1023ull);

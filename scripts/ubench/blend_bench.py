@@ -78,7 +78,7 @@ def main():
         build()
         t.append(time.perf_counter() - t0)
     pop = keep[0]
-    print(json.dumps(dict(bench="popular_build", **head, n_list=1024, **{k: v for k, v in pop.info().items() if k != "cache_version"},
+    print(json.dumps(dict(bench="popular_build", **head, **{k: v for k, v in pop.info().items() if k != "cache_version"},
                           **stats(t))), flush=True)
 
     # ---- requests

@@ -123,9 +123,9 @@ def kernel_stats(out_dir, items, D, rows):
     for path in glob.glob(os.path.join(out_dir, "**", "*kernel_stats.csv"), recursive=True):
         for row in csv.DictReader(open(path)):
             name = row.get("Name", "")
-            for k in ("uv_pool_kernel", "uv_seen_kernel", "uv_scan_kernel", "uv_merge_kernel"):
+            for k in ("uv_pool_kernel", "topn_seen_kernel", "uv_scan_kernel", "uv_merge_kernel"):
                 if k in name:
-                    ms[k[3:-7]] = ms.get(k[3:-7], 0.0) + float(row["TotalDurationNs"]) * 1e-6
+                    ms[k.split("_")[1]] = ms.get(k.split("_")[1], 0.0) + float(row["TotalDurationNs"]) * 1e-6
     if "scan" not in ms:
         return None
     Dp = -(-D // 64) * 64

@@ -38,7 +38,7 @@ from uservec_bench import DIMS, HISTORY, N_CAND, N_USERS, ROWS, scene, timed  # 
 
 PRODUCTS = "mfma_i32_16x16x64_i8"
 INTERESTS = (1, 4)
-KERNELS = ("uv_interests_kernel", "uv_seen_kernel", "uv_scan_kernel", "uv_merge_kernel", "uv_mix_kernel", "uv_pool_kernel")
+KERNELS = ("uv_interests_kernel", "topn_seen_kernel", "uv_scan_kernel", "uv_merge_kernel", "uv_mix_kernel", "uv_pool_kernel")
 
 
 def step_call(a):
@@ -121,7 +121,7 @@ def kernel_stats(out_dir, items, D, rows, K):
             name = row.get("Name", "")
             for k in KERNELS:
                 if k in name:
-                    ms[k[3:-7]] = ms.get(k[3:-7], 0.0) + float(row["TotalDurationNs"]) * 1e-6
+                    ms[k.split("_")[1]] = ms.get(k.split("_")[1], 0.0) + float(row["TotalDurationNs"]) * 1e-6
     if "scan" not in ms:
         return None
     total = sum(ms.values())

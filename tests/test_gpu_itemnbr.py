@@ -68,7 +68,7 @@ def test_build_of_4096_items_with_full_lists():
     check_build(rows, want, n_nbr=256).close()
 
 
-@pytest.mark.parametrize("n_nbr", [64, 256])
+@pytest.mark.parametrize("n_nbr", [1, 64, 65, 256])
 def test_columns_in_ascending_similarity_fill_every_step(n_nbr):
     """item 0 = (1, 0), item j at an angle to it that falls with j: every column is nearer to item 0 than all before it, so each of its
     128 columns a step passes the row's threshold and the list takes the most a step can append, step after step (9 steps, and

@@ -161,7 +161,7 @@ def test_ties_straddle_the_cut(n_cand):
     s.vec.close()
 
 
-@pytest.mark.parametrize("n_cand", [64, 256, 1024])
+@pytest.mark.parametrize("n_cand", [64, 65, 256, 1024])
 def test_columns_in_ascending_similarity_fill_every_step(n_cand):
     """the user's one history item is (1, 0) and item j sits at an angle to it that falls with j: every column is nearer than all
     before it, so each of a step's 128 columns passes the row's threshold and the list takes the most a step can append, step
