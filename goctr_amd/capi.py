@@ -192,6 +192,17 @@ class UservecMultiCfg(C.Structure):
                 ("mix", C.c_int32), ("reserved", C.c_int32), ("chunk_items", C.c_int64)]
 
 
+class IvfCfg(C.Structure):
+    """goctr_ivf_cfg (include/goctr.h)"""
+    _fields_ = [("n_lists", C.c_int32), ("iters", C.c_int32), ("train_items", C.c_int64), ("pass_items", C.c_int64),
+                ("reserved", C.c_int32)]
+
+
+class UservecIvfCfg(C.Structure):
+    """goctr_uservec_ivf_cfg (include/goctr.h)"""
+    _fields_ = [("min_w", C.c_int32), ("nprobe", C.c_int32), ("chunk_items", C.c_int64), ("reserved", C.c_int32)]
+
+
 class ListCfg(C.Structure):
     """goctr_list_cfg (include/goctr.h)"""
     _fields_ = [("k", C.c_int32), ("tail_cnt", C.c_int32)]
@@ -265,6 +276,8 @@ SYMBOLS = [
     "goctr_swing_cfg_default", "goctr_itemcf_build_swing",
     "goctr_uservec_cfg_default", "goctr_uservec_recall", "goctr_recommend_uservec", "goctr_recommend_blend_uservec",
     "goctr_uservec_multi_cfg_default", "goctr_uservec_interests", "goctr_uservec_recall_multi", "goctr_recommend_uservec_multi",
+    "goctr_ivf_cfg_default", "goctr_itemvec_index_build", "goctr_itemvec_index_destroy", "goctr_itemvec_index_info",
+    "goctr_itemvec_index_export", "goctr_uservec_ivf_cfg_default", "goctr_uservec_recall_ivf", "goctr_recommend_uservec_ivf",
 ]
 
 _lib = None
@@ -289,7 +302,8 @@ def load() -> C.CDLL:
                      "goctr_itemcf_cfg_default", "goctr_recall_cfg_default", "goctr_itemcf_destroy", "goctr_curve_cfg_default",
                      "goctr_multiclass_cfg_default", "goctr_popular_cfg_default", "goctr_popular_destroy",
                      "goctr_itemnbr_cfg_default", "goctr_mmr_cfg_default", "goctr_itemvec_destroy", "goctr_list_cfg_default",
-                     "goctr_swing_cfg_default", "goctr_uservec_cfg_default", "goctr_uservec_multi_cfg_default"):
+                     "goctr_swing_cfg_default", "goctr_uservec_cfg_default", "goctr_uservec_multi_cfg_default",
+                     "goctr_ivf_cfg_default", "goctr_uservec_ivf_cfg_default", "goctr_itemvec_index_destroy"):
             getattr(_lib, name).restype = None
         _bm = C.POINTER(BinaryMetrics)
         _lib.goctr_metrics_binary.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, _bm]
@@ -404,6 +418,18 @@ def load() -> C.CDLL:
         _lib.goctr_recommend_uservec_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32,
                                                        C.POINTER(RecallCfg), _um, C.c_int32, C.c_int64, _i32, _f32, _i32, _i32, _i32,
                                                        _i64, _i32, _u32, _f32, _i64, _u8, _i32]
+        _ib, _ui = C.POINTER(IvfCfg), C.POINTER(UservecIvfCfg)
+        _lib.goctr_ivf_cfg_default.argtypes = [_ib]
+        _lib.goctr_uservec_ivf_cfg_default.argtypes = [_ui]
+        _lib.goctr_itemvec_index_build.argtypes = [C.c_void_p, _ib, C.POINTER(C.c_void_p)]
+        _lib.goctr_itemvec_index_destroy.argtypes = [C.c_void_p]
+        _lib.goctr_itemvec_index_info.argtypes = [C.c_void_p, _i64, _i32, _i64, _i32, _i32, _i32, _i64]
+        _lib.goctr_itemvec_index_export.argtypes = [C.c_void_p, _i32, C.POINTER(C.c_int16), _u8, _i64]
+        _lib.goctr_uservec_recall_ivf.argtypes = [C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, C.POINTER(RecallCfg), _ui, _i32, _u32,
+                                                  _i32, _i32, _i32, C.POINTER(C.c_int16), _u64, _i32, _i64]
+        _lib.goctr_recommend_uservec_ivf.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32,
+                                                     C.POINTER(RecallCfg), _ui, C.c_int32, C.c_int64, _i32, _f32, _i32, _i32, _i32,
+                                                     _i64, _i32, _u32, _f32, _i64]
         _lib.goctr_list_cfg_default.argtypes = [C.POINTER(ListCfg)]
         _lib.goctr_metrics_lists.argtypes = [C.c_void_p, C.c_void_p, _i32, _i32, C.c_int64, C.c_int64, C.POINTER(ListCfg),
                                              C.POINTER(ListMetrics), C.POINTER(ListRow), _u32, _u32]
@@ -588,6 +614,22 @@ def default_uservec_cfg(**kw) -> UservecCfg:
 def default_uservec_multi_cfg(**kw) -> UservecMultiCfg:
     c = UservecMultiCfg()
     load().goctr_uservec_multi_cfg_default(C.byref(c))
+    for k, v in kw.items():
+        setattr(c, k, v)
+    return c
+
+
+def default_ivf_cfg(**kw) -> IvfCfg:
+    c = IvfCfg()
+    load().goctr_ivf_cfg_default(C.byref(c))
+    for k, v in kw.items():
+        setattr(c, k, v)
+    return c
+
+
+def default_uservec_ivf_cfg(**kw) -> UservecIvfCfg:
+    c = UservecIvfCfg()
+    load().goctr_uservec_ivf_cfg_default(C.byref(c))
     for k, v in kw.items():
         setattr(c, k, v)
     return c

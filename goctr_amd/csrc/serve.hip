@@ -20,6 +20,7 @@
 #include "topn.h"
 #include "ubcache.h"
 #include "uservec.h"
+#include "uservec_ivf.h"
 #include "uservec_multi.h"
 
 // ------------------------------------------------------------------ serving: recommend.BatchPredict / Rank / Predict
@@ -632,6 +633,24 @@ int goctr_recommend_uservec(goctr_model* m, goctr_recsys* r, goctr_itemvec* v, c
                         out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed};
   if (uservec_check_recommend(v, ucfg, a, r->n_users, r->n_items)) return -1;
   return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return uservec_recommend_run(sc, v, *ucfg, a); });
+}
+
+// goctr_recommend_uservec with the indexed recall (uservec_ivf.hip) as the recall stage
+int goctr_recommend_uservec_ivf(goctr_model* m, goctr_recsys* r, goctr_itemvec_index* x, const int32_t* users, const int64_t* ts,
+                                int64_t n_req, const int32_t* targets, const goctr_recall_cfg* recall_cfg,
+                                const goctr_uservec_ivf_cfg* icfg, int32_t k, int64_t pass_rows, int32_t* out_items, float* out_scores,
+                                int32_t* out_count, int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank,
+                                int32_t* cand_items, uint32_t* cand_w, float* cand_scores, int64_t* n_failed) {
+  EngineScope on(handle_engine(m));
+  if (require_engine()) return -1;
+  GOCTR_CHECK(m && r && x && recall_cfg && icfg, "goctr_recommend_uservec_ivf: bad arguments");
+  GOCTR_SAME_ENGINE(m, r);
+  GOCTR_SAME_ENGINE(m, x);
+  if (check_recsys_dims("goctr_recommend_uservec_ivf", m, r)) return -1;
+  const ItemcfRecArgs a{users, ts, n_req, targets, *recall_cfg, k, pass_rows, out_items, out_scores, out_count, out_cand_count,
+                        out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed};
+  if (uservec_ivf_check_recommend(x, icfg, a, r->n_users, r->n_items)) return -1;
+  return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return uservec_ivf_recommend_run(sc, x, *icfg, a); });
 }
 
 // goctr_recommend_uservec with the multi-interest recall (uservec_multi.hip) as the recall stage; the candidates' owner ranks ride

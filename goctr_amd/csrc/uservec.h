@@ -22,6 +22,21 @@ int uservec_check_cfg(const goctr_uservec_cfg* ucfg, const char* who);
 // the device columns of the rows a scan runs over: one user, ts and (targets may be null) target per request plane
 struct UvCols { const int32_t* users; const long long* ts; const int32_t* targets; };
 
+// planes a pool reads: [rows, Dp] laid out like the item planes.  row_of null: item i is row i; else row_of[i], negative = the
+// item has no row and adds nothing (uservec_ivf.hip: the list-ordered copy of an index)
+struct UvPlanes { const signed char* hi; const signed char* lo; const int32_t* row_of; int64_t n_items; int D, Dp; };
+
+// uservec_launch's first half -- sizes ws.p_hi / p_lo for nq rows, zeroes the pad rows and pools every row's history into them.
+// o_p [nq, D] and o_s [nq] may be null
+int uservec_pool_launch(const UvPlanes& pl, const long long* off, const int32_t* seq_items, const long long* seq_ts,
+                        const int32_t* users, const long long* ts, int64_t nq, int history, int16_t* o_p, unsigned long long* o_s,
+                        UvScratch& ws, hipStream_t st);
+
+// uv_merge_kernel over g_rows rows: row r's n_chunks descending lists of n_cand keys at lists + r * n_chunks * n_cand (0 = unused)
+// into the outputs of request row q0 + r
+int uservec_merge_launch(const unsigned long long* lists, int n_chunks, int n_cand, long long q0, int g_rows, const int32_t* targets,
+                         int stride, int32_t* o_items, unsigned int* o_w, int32_t* o_count, int32_t* o_tpos, hipStream_t st);
+
 // uservec_launch's second half -- seen, scan and merge over the nq request planes given, [nq + UV_PAD_ROWS, Dp] laid out like the
 // item planes with the pad rows zero: what the multi-interest recall (uservec_multi.hip) runs over its n_req x max_interests
 // virtual rows.  A zero plane row comes back empty

@@ -68,6 +68,7 @@ struct PoolArgs {
   const int32_t* users; const long long* ts;
   int H, D, Dp;
   const signed char* hi; const signed char* lo;                              // the item planes [n_items, Dp]
+  const int32_t* row_of;                                                     // null: item i is row i of the planes; else row_of[i], < 0: no row
   signed char* p_hi; signed char* p_lo;                                      // the request planes [nq + UV_PAD_ROWS, Dp], zeroed
   int16_t* out_p; u64* out_s;                                                // [nq, D], [nq]; each may be null
 };
@@ -86,12 +87,17 @@ __global__ __launch_bounds__(UV_THREADS) void uv_pool_kernel(PoolArgs a) {
 
   const int nh = lds_gather_history<UV_WAVES>(a.seq_items, a.seq_ts, lo_e, len, mts, a.n_items, a.H, hist, wcnt);
   __syncthreads();
+  if (a.row_of) {                              // planes in another row order (uservec_ivf.hip): an item without a row adds nothing
+    if (tid < nh) hist[tid] = a.row_of[hist[tid]];
+    __syncthreads();
+  }
 
   // u_d: |u_d| <= 256 * 16384 = 2^22; the sum of squares below 2^45
   u64 part = 0ull;
   for (int d = tid; d < a.Dp; d += UV_THREADS) {
     int u = 0;
     for (int t = 0; t < nh; ++t) {
+      if (hist[t] < 0) continue;
       const size_t at = (size_t)hist[t] * a.Dp + d;
       u += 256 * (int)a.hi[at] + (int)a.lo[at];
     }
@@ -289,20 +295,38 @@ int uservec_launch(const goctr_itemvec* v, const long long* off, const int32_t* 
                    const RecallInputs& in, bool has_targets, int64_t nq, const goctr_recall_cfg& cfg, const goctr_uservec_cfg& ucfg,
                    int stride, int32_t* o_items, unsigned int* o_w, int32_t* o_count, int32_t* o_tpos, int16_t* o_p,
                    unsigned long long* o_s, UvScratch& ws, hipStream_t st) {
-  const int Dp = v->Dp;
+  if (uservec_pool_launch(UvPlanes{v->hi.p, v->lo.p, nullptr, v->n_items, v->D, v->Dp}, off, seq_items, seq_ts, in.users.p, in.ts.p,
+                          nq, cfg.history, o_p, o_s, ws, st)) return -1;
+  return uservec_scan_planes(v, off, seq_items, seq_ts, UvCols{in.users.p, in.ts.p, has_targets ? in.targets.p : nullptr}, nq, cfg, ucfg,
+                             ws.p_hi.p, ws.p_lo.p, stride, o_items, o_w, o_count, o_tpos, ws, st);
+}
+
+int uservec_pool_launch(const UvPlanes& pl, const long long* off, const int32_t* seq_items, const long long* seq_ts,
+                        const int32_t* users, const long long* ts, int64_t nq, int history, int16_t* o_p, unsigned long long* o_s,
+                        UvScratch& ws, hipStream_t st) {
+  const int Dp = pl.Dp;
   // the request planes
   const size_t plane = ((size_t)nq + UV_PAD_ROWS) * Dp;
   if (ws.p_hi.alloc(plane, false) || ws.p_lo.alloc(plane, false)) return -1;
   GOCTR_HIP(hipMemsetAsync(ws.p_hi.p + (size_t)nq * Dp, 0, (size_t)UV_PAD_ROWS * Dp, st));
   GOCTR_HIP(hipMemsetAsync(ws.p_lo.p + (size_t)nq * Dp, 0, (size_t)UV_PAD_ROWS * Dp, st));
   PoolArgs p{};
-  p.off = off; p.seq_items = seq_items; p.seq_ts = seq_ts; p.n_items = v->n_items; p.users = in.users.p; p.ts = in.ts.p;
-  p.H = cfg.history; p.D = v->D; p.Dp = Dp; p.hi = v->hi.p; p.lo = v->lo.p; p.p_hi = ws.p_hi.p; p.p_lo = ws.p_lo.p;
+  p.off = off; p.seq_items = seq_items; p.seq_ts = seq_ts; p.n_items = pl.n_items; p.users = users; p.ts = ts;
+  p.H = history; p.D = pl.D; p.Dp = Dp; p.hi = pl.hi; p.lo = pl.lo; p.row_of = pl.row_of; p.p_hi = ws.p_hi.p; p.p_lo = ws.p_lo.p;
   p.out_p = o_p; p.out_s = o_s;
   hipLaunchKernelGGL(uv_pool_kernel, dim3((unsigned)nq), dim3(UV_THREADS), 0, st, p);
   GOCTR_HIP(hipGetLastError());
-  return uservec_scan_planes(v, off, seq_items, seq_ts, UvCols{in.users.p, in.ts.p, has_targets ? in.targets.p : nullptr}, nq, cfg, ucfg,
-                             ws.p_hi.p, ws.p_lo.p, stride, o_items, o_w, o_count, o_tpos, ws, st);
+  return 0;
+}
+
+int uservec_merge_launch(const unsigned long long* lists, int n_chunks, int n_cand, long long q0, int g_rows, const int32_t* targets,
+                         int stride, int32_t* o_items, unsigned int* o_w, int32_t* o_count, int32_t* o_tpos, hipStream_t st) {
+  MergeArgs m{};
+  m.lists = lists; m.n_chunks = n_chunks; m.n_cand = n_cand; m.q0 = q0; m.targets = targets;
+  m.stride = stride; m.out_items = o_items; m.out_w = o_w; m.out_count = o_count; m.out_tpos = o_tpos;
+  hipLaunchKernelGGL(uv_merge_kernel, dim3((unsigned)g_rows), dim3(SEL_THREADS), 0, st, m);
+  GOCTR_HIP(hipGetLastError());
+  return 0;
 }
 
 int uservec_scan_planes(const goctr_itemvec* v, const long long* off, const int32_t* seq_items, const long long* seq_ts,
@@ -356,11 +380,7 @@ int uservec_scan_planes(const goctr_itemvec* v, const long long* off, const int3
     if (R == 32) rc = one_k ? scan_launch(uv_scan_kernel<true, 2>, grid, lds, st, a) : scan_launch(uv_scan_kernel<false, 2>, grid, lds, st, a);
     else rc = one_k ? scan_launch(uv_scan_kernel<true, 1>, grid, lds, st, a) : scan_launch(uv_scan_kernel<false, 1>, grid, lds, st, a);
     if (rc) return -1;
-    MergeArgs m{};
-    m.lists = ws.lists.p; m.n_chunks = (int)n_chunks; m.n_cand = nc; m.q0 = q0; m.targets = in.targets;
-    m.stride = stride; m.out_items = o_items; m.out_w = o_w; m.out_count = o_count; m.out_tpos = o_tpos;
-    hipLaunchKernelGGL(uv_merge_kernel, dim3((unsigned)g_rows), dim3(SEL_THREADS), 0, st, m);
-    GOCTR_HIP(hipGetLastError());
+    if (uservec_merge_launch(ws.lists.p, (int)n_chunks, nc, q0, g_rows, in.targets, stride, o_items, o_w, o_count, o_tpos, st)) return -1;
   }
   return 0;
 }

@@ -778,6 +778,75 @@ inline std::vector<ItemScore> RecommendVector(model::CtrNet& net, RecSys& rs, co
   return RecommendVectorBatch(net, rs, vec, {userId}, n, {now}, rcfg).lists[0];
 }
 
+// an inverted-file index over the valid rows of an ItemVectors (goctr_itemvec_index_build): self-contained, `vec` may go afterwards
+class VectorIndex {
+ public:
+  static goctr_ivf_cfg DefaultCfg() { goctr_ivf_cfg c; goctr_ivf_cfg_default(&c); return c; }
+  static goctr_uservec_ivf_cfg DefaultRecallCfg() { goctr_uservec_ivf_cfg c; goctr_uservec_ivf_cfg_default(&c); return c; }
+  static VectorIndex Build(const ItemVectors& vec, const goctr_ivf_cfg& cfg = DefaultCfg()) {
+    VectorIndex x;
+    check(goctr_itemvec_index_build(vec.handle(), &cfg, &x.h_));
+    return x;
+  }
+  VectorIndex(const VectorIndex&) = delete;
+  VectorIndex& operator=(const VectorIndex&) = delete;
+  VectorIndex(VectorIndex&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  ~VectorIndex() { goctr_itemvec_index_destroy(h_); }
+  goctr_itemvec_index* handle() const { return h_; }
+  struct Info { int64_t n_items, n_valid, longest; int32_t D, n_lists, live, non_empty; };
+  Info info() const {
+    Info i{};
+    check(goctr_itemvec_index_info(h_, &i.n_items, &i.D, &i.n_valid, &i.n_lists, &i.live, &i.non_empty, &i.longest));
+    return i;
+  }
+
+ private:
+  VectorIndex() = default;
+  goctr_itemvec_index* h_ = nullptr;
+};
+
+// UservecRecall over the icfg.nprobe lists nearest every row's request vector (goctr_uservec_recall_ivf); `lists` [nq, nprobe]: the
+// probed lists in rank order, -1 behind them
+inline void UservecRecallIvf(const VectorIndex& index, goctr_ubcache* cache, const std::vector<int32_t>& users,
+                             const std::vector<int64_t>& ts, const goctr_recall_cfg& cfg, std::vector<int32_t>& items,
+                             std::vector<uint32_t>& w, std::vector<int32_t>& count, std::vector<int32_t>& lists,
+                             const goctr_uservec_ivf_cfg& icfg = VectorIndex::DefaultRecallCfg()) {
+  if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("UservecRecallIvf: one timestamp per user");
+  const size_t nq = users.size(), nc = (size_t)std::max(cfg.n_cand, 1), np = (size_t)std::max(icfg.nprobe, 1);
+  items.resize(nq * nc); w.resize(nq * nc); count.resize(nq); lists.resize(nq * np);
+  check(goctr_uservec_recall_ivf(index.handle(), cache, users.data(), ts.empty() ? nullptr : ts.data(), (int64_t)nq, &cfg, &icfg,
+                                 items.data(), w.data(), count.data(), nullptr, nullptr, nullptr, nullptr, lists.data(), nullptr));
+}
+
+// RecommendVectorBatch with the indexed recall as the recall stage (goctr_recommend_uservec_ivf)
+inline TopN RecommendVectorIndexedBatch(model::CtrNet& net, RecSys& rs, const VectorIndex& index, const std::vector<int32_t>& users,
+                                        int n = 10, const std::vector<int64_t>& ts = {},
+                                        const goctr_recall_cfg& rcfg = ItemCF::DefaultRecallCfg(),
+                                        const goctr_uservec_ivf_cfg& icfg = VectorIndex::DefaultRecallCfg(),
+                                        const std::vector<int32_t>& targets = {}, int64_t pass_rows = 0) {
+  const int64_t nq = (int64_t)users.size();
+  if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("RecommendVectorIndexedBatch: one timestamp per user");
+  if (!targets.empty() && targets.size() != users.size()) throw std::invalid_argument("RecommendVectorIndexedBatch: one target per user");
+  if (n < 1) throw std::invalid_argument("RecommendVectorIndexedBatch: n must be positive");
+  std::vector<int32_t> items((size_t)nq * n), count((size_t)nq);
+  std::vector<float> scores((size_t)nq * n);
+  TopN out;
+  if (!targets.empty()) out.target_rank.resize((size_t)nq);
+  check(goctr_recommend_uservec_ivf(net.Vm(), rs.handle(), index.handle(), users.data(), ts.empty() ? nullptr : ts.data(), nq,
+                                    targets.empty() ? nullptr : targets.data(), &rcfg, &icfg, n, pass_rows, items.data(), scores.data(),
+                                    count.data(), nullptr, nullptr, targets.empty() ? nullptr : out.target_rank.data(), nullptr,
+                                    nullptr, nullptr, &out.n_failed));
+  out.lists.resize((size_t)nq);
+  for (int64_t q = 0; q < nq; ++q)
+    for (int j = 0; j < count[(size_t)q]; ++j)
+      out.lists[(size_t)q].push_back(ItemScore{items[(size_t)q * n + j], scores[(size_t)q * n + j]});
+  return out;
+}
+inline std::vector<ItemScore> RecommendVectorIndexed(model::CtrNet& net, RecSys& rs, const VectorIndex& index, int userId, int n,
+                                                     int64_t now, const goctr_recall_cfg& rcfg = ItemCF::DefaultRecallCfg()) {
+  return RecommendVectorIndexedBatch(net, rs, index, {userId}, n, {now}, rcfg).lists[0];
+}
+
 // multi-interest user-to-item recall: the history clustered into up to mcfg.max_interests vectors (goctr_uservec_interests: the
 // clustering alone -- n_int per row, the entries' interest ranks [nq, cfg.history] and the member counts [nq, max_interests]), one
 // list each against the whole catalogue, mixed into one (goctr_uservec_recall_multi; `owner`: the candidates' interest ranks)

@@ -21,6 +21,10 @@ every row's scored candidates greedily, trading relevance against similarity to 
 ``ItemVectors.recall_users`` is the user-to-item channel: a request row's history is pooled into one interest vector and matched
 against the whole catalogue, so an item close to many history items but in no single item's stored list is still found
 (tests/uservec_ref.py is the host restatement).  ``recommend.RecommendVector`` ranks the result with the model.
+
+``ItemVectors.build_index`` clusters the valid vectors into an inverted file, and ``VectorIndex.recall_users`` is the same channel
+over the ``nprobe`` lists whose centres lie nearest the request vector instead of over the whole catalogue
+(tests/uservec_ivf_ref.py is the host restatement).  ``recommend.RecommendVectorIndexed`` ranks the result with the model.
 """
 from __future__ import annotations
 
@@ -40,6 +44,8 @@ _MMR_FIELDS = {"k", "pool", "lambda_q", "max_per_group"}
 _LIST_FIELDS = {"k", "tail_cnt"}
 _USERVEC_FIELDS = {"min_w", "chunk_items"}
 _USERVEC_MULTI_FIELDS = {"min_w", "max_interests", "iters", "split_w", "mix", "chunk_items"}
+_IVF_FIELDS = {"n_lists", "iters", "train_items", "pass_items"}
+_USERVEC_IVF_FIELDS = {"min_w", "nprobe", "chunk_items"}
 MIX = {"max": capi.UVMIX_MAX, "quota": capi.UVMIX_QUOTA}
 
 
@@ -103,6 +109,22 @@ def make_uservec_multi_cfg(**kw) -> capi.UservecMultiCfg:
     if isinstance(kw.get("mix"), str):
         kw["mix"] = MIX[kw["mix"]]
     return capi.default_uservec_multi_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
+
+
+def make_ivf_cfg(**kw) -> capi.IvfCfg:
+    """goctr_ivf_cfg from keywords (integers; the ranges are the library's to refuse)"""
+    unknown = set(kw) - _IVF_FIELDS
+    if unknown:
+        raise TypeError(f"goctr_ivf_cfg has no field {sorted(unknown)}")
+    return capi.default_ivf_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
+
+
+def make_uservec_ivf_cfg(**kw) -> capi.UservecIvfCfg:
+    """goctr_uservec_ivf_cfg from keywords (integers; the ranges are the library's to refuse)"""
+    unknown = set(kw) - _USERVEC_IVF_FIELDS
+    if unknown:
+        raise TypeError(f"goctr_uservec_ivf_cfg has no field {sorted(unknown)}")
+    return capi.default_uservec_ivf_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
 
 
 def make_list_cfg(**kw) -> capi.ListCfg:
@@ -465,9 +487,85 @@ class ItemVectors:
             out["p"], out["s"] = p, s
         return out
 
+    def build_index(self, cfg: capi.IvfCfg | None = None, **kw) -> "VectorIndex":
+        """goctr_itemvec_index_build: a k-means inverted file over the valid rows.  ``kw``: goctr_ivf_cfg fields (n_lists, iters,
+        train_items, pass_items).  The index is self-contained: it outlives this handle"""
+        if cfg is not None and kw:
+            raise TypeError("give either cfg or keywords")
+        cfg = cfg if cfg is not None else make_ivf_cfg(**kw)
+        h = C.c_void_p()
+        capi.check(capi.load().goctr_itemvec_index_build(self._h, C.byref(cfg), C.byref(h)))
+        return VectorIndex(h)
+
     def close(self):
         if getattr(self, "_h", None):
             capi.load().goctr_itemvec_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class VectorIndex:
+    """goctr_itemvec_index: the valid rows of an ItemVectors clustered into lists, resident in HBM, immutable after the build"""
+
+    def __init__(self, handle: C.c_void_p):
+        self._h = handle
+        i = self.info()
+        self.n_items, self.D, self.n_lists = i["n_items"], i["D"], i["n_lists"]
+
+    def info(self) -> dict:
+        n, d, nv, nl = C.c_int64(0), C.c_int32(0), C.c_int64(0), C.c_int32(0)
+        live, ne, longest = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+        capi.check(capi.load().goctr_itemvec_index_info(self._h, C.byref(n), C.byref(d), C.byref(nv), C.byref(nl), C.byref(live),
+                                                        C.byref(ne), C.byref(longest)))
+        return dict(n_items=n.value, D=d.value, n_valid=nv.value, n_lists=nl.value, live=live.value, non_empty=ne.value,
+                    longest=longest.value)
+
+    def export(self) -> dict:
+        """dict(list_of int32 [n_items] (-1 = in no list), centres int16 [n_lists, D], live uint8 [n_lists], sizes int64 [n_lists])"""
+        out = dict(list_of=np.empty(self.n_items, np.int32), centres=np.empty((self.n_lists, self.D), np.int16),
+                   live=np.empty(self.n_lists, np.uint8), sizes=np.empty(self.n_lists, np.int64))
+        capi.check(capi.load().goctr_itemvec_index_export(self._h, capi.ptr(out["list_of"], C.c_int32), capi.ptr(out["centres"], C.c_int16),
+                                                          capi.ptr(out["live"], C.c_uint8), capi.ptr(out["sizes"], C.c_int64)))
+        return out
+
+    def recall_users(self, ubc, users, ts=None, targets=None, cfg: capi.RecallCfg | None = None,
+                     icfg: capi.UservecIvfCfg | None = None, validate=False, **kw) -> dict:
+        """goctr_uservec_recall_ivf over DENSE user rows of ``ubc``'s image: ``ItemVectors.recall_users`` over the ``nprobe`` lists
+        nearest every row's request vector.  ``kw``: goctr_recall_cfg fields and goctr_uservec_ivf_cfg's (min_w, nprobe,
+        chunk_items).  That call's dict plus lists int32 [nq, nprobe] (the probed lists in rank order, -1 = unused) and scanned
+        int64 [nq] (the items in them)"""
+        ikw = {k: kw.pop(k) for k in list(kw) if k in _USERVEC_IVF_FIELDS}
+        if (cfg is not None and kw) or (icfg is not None and ikw):
+            raise TypeError("give either a cfg or its keywords")
+        cfg = cfg if cfg is not None else make_recall_cfg(**kw)
+        icfg = icfg if icfg is not None else make_uservec_ivf_cfg(**ikw)
+        users, ts, targets = request_columns(users, ts, targets)
+        nq, nc, npr = users.size, max(int(cfg.n_cand), 1), min(max(int(icfg.nprobe), 1), 1024)
+        out = dict(items=np.full((nq, nc), -2, np.int32), w=np.full((nq, nc), 0xffffffff, np.uint32), count=np.full(nq, -2, np.int32),
+                   lists=np.full((nq, npr), -2, np.int32), scanned=np.full(nq, -2, np.int64))
+        tpos = np.full(nq, -2, np.int32) if targets is not None else None
+        p = np.full((nq, self.D), -2, np.int16) if validate else None
+        s = np.full(nq, 0xffffffffffffffff, np.uint64) if validate else None
+        h = None if ubc is None else ubc.device() if hasattr(ubc, "device") else ubc
+        capi.check(capi.load().goctr_uservec_recall_ivf(
+            self._h, h, capi.ptr(users, C.c_int32), capi.ptr(ts, C.c_int64), C.c_int64(nq), C.byref(cfg), C.byref(icfg),
+            capi.ptr(out["items"], C.c_int32), capi.ptr(out["w"], C.c_uint32), capi.ptr(out["count"], C.c_int32),
+            capi.ptr(targets, C.c_int32), capi.ptr(tpos, C.c_int32), capi.ptr(p, C.c_int16), capi.ptr(s, C.c_uint64),
+            capi.ptr(out["lists"], C.c_int32), capi.ptr(out["scanned"], C.c_int64)))
+        if tpos is not None:
+            out["target_pos"] = tpos
+        if validate:
+            out["p"], out["s"] = p, s
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            capi.load().goctr_itemvec_index_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -1189,6 +1189,86 @@ def EvaluateLeaveOneOutVector(model: Predictor, vectors, k=10, sample_kw=None, d
     return out
 
 
+def _split_uservec_ivf_kw(recall_cfg, icfg, kw):
+    """(goctr_recall_cfg, goctr_uservec_ivf_cfg) from cfgs or keywords (min_w, nprobe and chunk_items are the latter's)"""
+    from .recall import _USERVEC_IVF_FIELDS, make_recall_cfg, make_uservec_ivf_cfg
+    ikw = {k: kw.pop(k) for k in list(kw) if k in _USERVEC_IVF_FIELDS}
+    if (recall_cfg is not None and kw) or (icfg is not None and ikw):
+        raise TypeError("give either a cfg or its keywords")
+    return (recall_cfg if recall_cfg is not None else make_recall_cfg(**kw)), (icfg if icfg is not None else make_uservec_ivf_cfg(**ikw))
+
+
+def uservec_ivf(model: Predictor, index, users, ts=None, targets=None, k=10, pass_rows=0, validate=False, recall_cfg=None, icfg=None,
+                **recall_kw):
+    """goctr_recommend_uservec_ivf over DENSE indices: ``uservec`` with the recall over ``index`` (recall.VectorIndex) as the recall
+    stage; the same dict.  ``recall_kw``: goctr_recall_cfg fields and goctr_uservec_ivf_cfg's (min_w, nprobe, chunk_items).  What
+    RecommendVectorIndexed / RecommendVectorIndexedBatch / EvaluateLeaveOneOutVectorIndexed call."""
+    from .recall import request_columns
+    cfg, icfg = _split_uservec_ivf_kw(recall_cfg, icfg, recall_kw)
+    rs = model.recSys
+    users, ts, targets = request_columns(users, ts, targets)
+    nq, kk, nc = users.size, max(int(k), 1), max(int(cfg.n_cand), 1)
+    out = dict(items=np.full((nq, kk), -2, np.int32), scores=np.full((nq, kk), np.nan, np.float32), count=np.full(nq, -2, np.int32),
+               cand_count=np.full(nq, -2, np.int32))
+    tpos = np.full(nq, -2, np.int32) if targets is not None else None
+    rank = np.full(nq, -2, np.int64) if targets is not None else None
+    cand_items = np.full((nq, nc), -2, np.int32) if validate else None
+    cand_w = np.full((nq, nc), 0xffffffff, np.uint32) if validate else None
+    cand_scores = np.full((nq, nc), np.nan, np.float32) if validate else None
+    nf = C.c_int64(-2)
+    capi.check(capi.load().goctr_recommend_uservec_ivf(
+        model.net._h, rs._h, index._h, capi.ptr(users, C.c_int32), capi.ptr(ts, C.c_int64), C.c_int64(nq),
+        capi.ptr(targets, C.c_int32), C.byref(cfg), C.byref(icfg), C.c_int32(int(k)), C.c_int64(int(pass_rows)),
+        capi.ptr(out["items"], C.c_int32), capi.ptr(out["scores"], C.c_float), capi.ptr(out["count"], C.c_int32),
+        capi.ptr(out["cand_count"], C.c_int32), capi.ptr(tpos, C.c_int32), capi.ptr(rank, C.c_int64), capi.ptr(cand_items, C.c_int32),
+        capi.ptr(cand_w, C.c_uint32), capi.ptr(cand_scores, C.c_float), C.byref(nf)))
+    out["n_failed"] = nf.value
+    if targets is not None:
+        out["target_pos"], out["target_rank"] = tpos, rank
+    if validate:
+        out["cand_items"], out["cand_w"], out["cand_scores"] = cand_items, cand_w, cand_scores
+    return out
+
+
+def BuildVectorIndex(vectors, **index_kw):
+    """EXTENSION: an inverted-file index over ``vectors`` (BuildItemVectors): the valid vectors clustered into ``n_lists`` lists by
+    ``iters`` rounds of integer k-means over ``train_items`` of them (recall.ItemVectors.build_index).  The index keeps its own copy
+    of the vectors: ``vectors`` may be closed afterwards."""
+    return vectors.build_index(**index_kw)
+
+
+def RecommendVectorIndexedBatch(model: Predictor, index, userIds, n=10, now=None, **recall_kw):
+    """RecommendVectorIndexed for several users in one device call: [[ItemScore]] in the order of userIds."""
+    users, ts = _request_rows(model, userIds, now)
+    if users.size == 0:
+        return []
+    try:
+        r = uservec_ivf(model, index, users, ts, None, n, **recall_kw)
+    except capi.GoctrError as e:
+        raise SampleVectorError(str(e)) from None
+    return _item_scores(model, r, users.size)
+
+
+def RecommendVectorIndexed(model: Predictor, index, userId: int, n=10, now=None, **recall_kw):
+    """EXTENSION -- RecommendVector over an index (``index``: BuildVectorIndex): the candidates come from the ``nprobe`` lists whose
+    centres lie nearest the user's interest vector, not from the whole catalogue, so a request's cost follows the lists it scans.
+    With ``nprobe`` at or above the number of non-empty lists the result is RecommendVector's."""
+    return RecommendVectorIndexedBatch(model, index, [userId], n, now, **recall_kw)[0]
+
+
+def EvaluateLeaveOneOutVectorIndexed(model: Predictor, index, k=10, sample_kw=None, details=False, pass_rows=0, **recall_kw):
+    """EvaluateLeaveOneOutVector's protocol and figures with the indexed recall as the recall stage (goctr_recommend_uservec_ivf):
+    what the index costs in recall shows as the difference between the two."""
+    users, targets, ts = _held_out_rows(model, sample_kw)
+    recall_kw.setdefault("exclude", "before")
+    cfg, icfg = _split_uservec_ivf_kw(None, None, recall_kw)
+    r = uservec_ivf(model, index, users, ts, targets, k, pass_rows, recall_cfg=cfg, icfg=icfg)
+    out = _loo_figures(r, targets, model.recSys.item_table.shape[0], k, cfg.n_cand)
+    if details:
+        out.update(target_pos=r["target_pos"], rank=r["target_rank"], user_index=users, target_index=targets, ts=ts)
+    return out
+
+
 def _split_uservec_multi_kw(recall_cfg, mcfg, kw):
     """(goctr_recall_cfg, goctr_uservec_multi_cfg) from cfgs or keywords"""
     from .recall import _USERVEC_MULTI_FIELDS, make_recall_cfg, make_uservec_multi_cfg

@@ -982,6 +982,103 @@ int goctr_recommend_uservec_multi(goctr_model* m, goctr_recsys* r, goctr_itemvec
                                   int32_t* cand_items, uint32_t* cand_w, float* cand_scores, int64_t* n_failed,
                                   uint8_t* cand_interest, int32_t* out_n_int);
 
+/* ---- Inverted-file index for user-vector recall: probe a few lists, not the whole catalogue (no reference counterpart).
+ * goctr_uservec_recall multiplies every request vector against every item.  A goctr_itemvec_index is a k-means inverted file over
+ * the valid rows of a goctr_itemvec; goctr_uservec_recall_ivf ranks its lists by the request vector's dot product with their
+ * centres and scans only the first nprobe of them.  The index is approximate as a recall, but every byte it returns is defined
+ * exactly (tests/uservec_ivf_ref.py is the host restatement): after the pinned float64 quantisation all arithmetic is integer.
+ *
+ * goctr_itemvec_index_build, over the handle's int16 rows q (256 hi + lo):
+ *   sample         the valid items are numbered 0 .. n_valid - 1 in ascending id order.  T = n_valid, or min(train_items, n_valid)
+ *                  when train_items is set; sample element t is valid item number (t * n_valid) / T in 64-bit integers
+ *   seeds          L' = min(n_lists, T); centre c < L' starts as the int16 row of sample element (c * T) / L', live.  Centres
+ *                  c >= L' do not exist
+ *   assign         a row goes to the live centre with the largest signed int32 dot product, ties to the lowest c (the rule of the
+ *                  multi-interest recall above); without a live centre it goes nowhere
+ *   re-centre      u_c = the int64 sum of the members' int16 rows, m = max_d |u_c,d|.  A centre without members or with m = 0 is
+ *                  dead for good: its row is zero and it takes no part in later assignments.  Otherwise sh = max(0,
+ *                  bitlength(m) - 21) and u' = u_c >> sh, an arithmetic shift (it floors).  |u'_d| < 2^21 and the sum of u'^2 is
+ *                  below 2^52 for D <= 1024, so every partial sum is an exact double; the new centre is the quantisation rule of
+ *                  "Item neighbours from vectors" (s, r, q_d) applied to u' as doubles by the same pinned operations
+ *   rounds         `iters` times {assign the sample, re-centre from the sample}; then ALL valid rows are assigned to the live
+ *                  centres.  Those are the lists; inside a list the items ascend by id.  With iters = 0 the lists are "nearest
+ *                  seed".  A live centre may end with an empty list; an invalid row is in no list; a valid row is in exactly one
+ *                  as long as one centre is live (opposite rows can cancel the last one: then there are no lists)
+ *   no vectors     n_valid = 0 is not an error: the index has no lists and every recall over it returns empty rows
+ *   refused        (-1, *out untouched) a NULL v, cfg or out; n_lists outside 1 .. 16384; iters outside 0 .. 32; train_items < 0;
+ *                  pass_items neither 0 nor in 64 .. 2^22; reserved != 0; a handle on another engine than the calling thread's
+ * The handle is immutable and self-contained: it keeps a copy of both int8 planes in list order, so that a list is one contiguous
+ * run of operand rows, the item of every row, the row of every item, the list starts, and the centres as planes laid out like the
+ * item planes.  That costs 2 * n_valid * Dp bytes for the copy (Dp = D rounded up to 64) plus 8 * n_items bytes for the two id
+ * arrays; the goctr_itemvec may be destroyed once the build has returned.  No byte depends on pass_items (the rows one assign
+ * launch takes) or on the order in which threads arrive: every sum is an integer one.
+ *
+ * goctr_itemvec_index_info    each pointer may be NULL: n_items, D, n_valid, n_lists, the live centres, the non-empty lists, the
+ *                             longest list
+ * goctr_itemvec_index_export  each pointer may be NULL: list_of [n_items] int32 (-1: in no list); centres [n_lists,D] int16 (zeros
+ *                             for a centre that is dead or does not exist); live [n_lists] 1 / 0; sizes [n_lists]
+ *
+ * goctr_uservec_recall_ivf, for request row q:
+ *   vectors        the history, the pooled vector, the request vector p and s are exactly goctr_uservec_recall's
+ *   probed lists   the non-empty lists, ordered by dot(p, centre_c) as a signed int32 descending, then c ascending; the first
+ *                  icfg->nprobe are probed.  A row without a vector probes nothing
+ *   candidates     the items of the probed lists that pass goctr_uservec_recall's candidate rule (w = dot(p, q_j) >> 12 when
+ *                  positive, w >= min_w, not seen under cfg->exclude, the target exempt), by w descending, then item ascending;
+ *                  the first cfg->n_cand.  Outputs and padding as in that call
+ *   out_lists      [n_req,nprobe], may be NULL: the probed list ids in rank order, padded with -1
+ *   out_scanned    [n_req], may be NULL: the sum of the probed lists' sizes
+ *   all lists      when nprobe >= the number of non-empty lists every output goctr_uservec_recall also has (items, w, count,
+ *                  target_pos, p, s) is byte-equal to that call over the handle the index was built from: every valid item is in
+ *                  exactly one list (as long as a centre is live) and an invalid item never qualifies.  Below that the kept list
+ *                  is a subsequence of the exact call's list taken to full length
+ *   refused        (-1, nothing touched) goctr_uservec_recall's refusals with the index in the handle's place; nprobe outside
+ *                  1 .. 1024; an index on another engine than the cache's
+ * A work item of the scan is (list, up to 16 of the rows that probe it, column chunk of the list); the rows of a list are found
+ * by sorting (list, row) pairs, never by an atomic counter.  The seen bitmap is over item ids, goctr_uservec_recall's.  No output
+ * byte depends on chunk_items, on the scratch budget, on how rows are grouped or tiled, or on the order in which threads arrive.
+ * Host arrays, the engine stream and the engine lock, like goctr_uservec_recall. */
+typedef struct goctr_itemvec_index goctr_itemvec_index;
+typedef struct {
+  int32_t n_lists;      /* 1 .. 16384: centres                                          default 1024 */
+  int32_t iters;        /* 0 .. 32: {assign, re-centre} rounds over the sample          default 8    */
+  int64_t train_items;  /* 0 = all valid rows, else >= 1: the sample's size             default 0    */
+  int64_t pass_items;   /* 0 = 65536, else 64 .. 2^22: rows one assign launch covers    default 0    */
+  int32_t reserved;     /* must be 0 */
+} goctr_ivf_cfg;
+void goctr_ivf_cfg_default(goctr_ivf_cfg* c);
+int  goctr_itemvec_index_build(goctr_itemvec* v, const goctr_ivf_cfg* cfg, goctr_itemvec_index** out);
+void goctr_itemvec_index_destroy(goctr_itemvec_index* x);
+int  goctr_itemvec_index_info(goctr_itemvec_index* x, int64_t* n_items, int32_t* D, int64_t* n_valid, int32_t* n_lists,
+                              int32_t* n_live, int32_t* n_nonempty, int64_t* longest);
+int  goctr_itemvec_index_export(goctr_itemvec_index* x, int32_t* list_of /*[n_items]*/, int16_t* centres /*[n_lists,D]*/,
+                                uint8_t* live /*[n_lists]*/, int64_t* sizes /*[n_lists]*/);
+typedef struct {
+  int32_t min_w;        /* 1 .. 65536, units of 2^-16                          default 1  */
+  int32_t nprobe;       /* 1 .. 1024: lists a row scans                        default 16 */
+  int64_t chunk_items;  /* 0 = the implementation's choice, else 64 .. 2^22:
+                           items of a list per column chunk (a tiling knob)    default 0  */
+  int32_t reserved;     /* must be 0 */
+} goctr_uservec_ivf_cfg;
+void goctr_uservec_ivf_cfg_default(goctr_uservec_ivf_cfg* c);
+int  goctr_uservec_recall_ivf(goctr_itemvec_index* x, goctr_ubcache* c, const int32_t* users, const int64_t* ts /* NULL = 0 */,
+                              int64_t n_req, const goctr_recall_cfg* cfg, const goctr_uservec_ivf_cfg* icfg,
+                              int32_t* out_items /*[n_req,n_cand]*/, uint32_t* out_w /*[n_req,n_cand]*/, int32_t* out_count /*[n_req]*/,
+                              const int32_t* targets /*[n_req] or NULL*/, int32_t* out_target_pos /*[n_req] or NULL*/,
+                              int16_t* out_p /*[n_req,D] or NULL*/, uint64_t* out_s /*[n_req] or NULL*/,
+                              int32_t* out_lists /*[n_req,nprobe] or NULL*/, int64_t* out_scanned /*[n_req] or NULL*/);
+
+/* goctr_recommend_uservec_ivf: goctr_recommend_uservec with the recall above as its recall stage.  Arguments, outputs and every
+ * documented property of that call hold unchanged.
+ *   refused        goctr_recommend_uservec's refusals with the icfg refusals above in place of the ucfg ones, and an index whose
+ *                  n_items differs from the recsys's */
+int goctr_recommend_uservec_ivf(goctr_model* m, goctr_recsys* r, goctr_itemvec_index* x,
+                                const int32_t* users, const int64_t* ts /* NULL = 0 */, int64_t n_req,
+                                const int32_t* targets /* [n_req] or NULL */, const goctr_recall_cfg* recall_cfg,
+                                const goctr_uservec_ivf_cfg* icfg, int32_t k, int64_t pass_rows,
+                                int32_t* out_items /* [n_req,k] */, float* out_scores /* [n_req,k] */, int32_t* out_count,
+                                int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank,
+                                int32_t* cand_items, uint32_t* cand_w, float* cand_scores, int64_t* n_failed);
+
 /* The replica a multi-device training call (cfg.devices = n) keeps on engine `rank` (rank 0: the handle itself); NULL before
  * the first such call.  Borrowed: owned by the handle it was asked from.  For checks that the replicas are bit-identical
  * (tests, bench.py's replica checksum) -- every entry point works on it, on its own engine. */
