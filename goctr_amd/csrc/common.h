@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -93,6 +94,8 @@ struct Engine {
   bool prof = false;
   double prof_ms[GOCTR_K_COUNT] = {0};
   int64_t prof_n[GOCTR_K_COUNT] = {0};
+  // launches on a serving slot's stream while profiling is on: counted, not timed (goctr_prof_get adds them to n)
+  std::atomic<int64_t> prof_n_slot[GOCTR_K_COUNT] = {};
   const char* prof_kernel[GOCTR_K_COUNT] = {nullptr};   // symbol of the kernel a family's last launch ran (goctr_prof_kernel)
   struct Pending { int id; hipEvent_t a, b; };
   std::vector<Pending> pending;
@@ -168,9 +171,10 @@ inline int env_int_set(const char* name, int dflt) {
 // handed out again by malloc; its uid never is)
 uint64_t next_uid();
 
-// timing scope used around every launch of a kernel family when profiling is on
+// timing scope used around every launch of a kernel family when profiling is on.  `on`: the launch is timed (main-stream
+// launches); `note`: profiling is on, whatever the stream -- a serving slot's launch is counted and its symbol noted, not timed
 struct ProfScope {
-  int id; bool on; hipEvent_t a = nullptr, b = nullptr;
+  int id; bool on; bool note; hipEvent_t a = nullptr, b = nullptr;
   explicit ProfScope(int kernel_id);
   ~ProfScope();
 };
@@ -184,7 +188,9 @@ struct StreamScope {
 };
 // remembers which kernel symbol a profiled family's launch ran (bench.py matches it against the committed rocprofv3
 // summary before it quotes that summary's counters)
-inline void prof_note_kernel(int id, const char* symbol) { engine().prof_kernel[id] = symbol; }
+// (`symbol` outlives the call: a literal, or prof_intern's copy of a composed name -- serving threads note symbols side by side)
+inline void prof_note_kernel(int id, const char* symbol) { __atomic_store_n(&engine().prof_kernel[id], symbol, __ATOMIC_RELAXED); }
+const char* prof_intern(const char* symbol);
 
 // Device memory comes from ONE large hipMalloc'd arena (first-fit free list) so that every buffer of
 // the engine sits in the same 2 MiB-fragment mapping (few TLB entries) instead of dozens of small

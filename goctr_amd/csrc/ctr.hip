@@ -202,7 +202,7 @@ bool chain_x3_ok(const goctr_model* m, const StepOpts& o, int B) {
   if (m->x3_nch0 == 0) return false;
   if (o.train) return o.drop_mode != 1;
   const int cus = engine().compute_units > 0 ? engine().compute_units : 256;
-  return cdiv(B, 32) >= cus;
+  return cdiv(o.rows_for_dispatch(B), 32) >= cus;
 }
 
 int serve16_attributes() {
@@ -321,15 +321,15 @@ int goctr::launch_attn_fwd(const AttnArgs& a) {
   const bool small_table = (unsigned long long)(a.src.V + 1) * (unsigned long long)a.D * 4ull < (1ull << 32);
   const int fast = !(vec4 && small_table && groups * 4 == a.D && (groups & (groups - 1)) == 0) ? 0
                    : a.kind != GOCTR_DIN ? 1 : (a.att == GOCTR_ATT_COSINE ? 2 : 3);
-  if (ps.on) {   // the symbol the dispatch below selects (goctr_prof_kernel)
-    static char sym[48];
+  if (ps.note) {   // the symbol the dispatch below selects (goctr_prof_kernel)
+    char sym[48];
     int L = 1;
     while (L < groups) L *= 2;
     if (!vec4 && L < 8) L = 8;
     if (a.src.k_users) snprintf(sym, sizeof sym, "attn_fwd_keys_kernel<%d,%d>", std::min(L, 64), fast);
     else if (!vec4 && groups > 64) snprintf(sym, sizeof sym, "attn_fwd_wide_kernel<%d>", groups <= 128 ? 2 : 4);
     else snprintf(sym, sizeof sym, "attn_fwd_kernel<%d,%d,%d>", vec4 ? 4 : 1, std::min(L, 64), (fast && groups <= 16) ? fast : 0);
-    prof_note_kernel(GOCTR_K_ATTN_FWD, sym);
+    prof_note_kernel(GOCTR_K_ATTN_FWD, prof_intern(sym));
   }
   if (a.src.k_users) {
     // serving pass in key mode (serve_keys_pass): only the compile-time shapes have a key variant -- the caller checked
@@ -486,7 +486,7 @@ int launch_chain_x3(goctr_model* m, const RowSource& src, int B, const StepOpts&
   // forward only: four wavefronts per tile and two workgroups per CU (ctr_fwd4.h; GOCTR_FWD4=0: the 8-wavefront kernel)
   // (a launch of at most one tile per CU keeps the 8-wavefront kernel: 470 against 459 M rows/s at 256 tiles per launch; 512 tiles 551 -> 575 M,
   // 1024 tiles 608 -> 637 M -- profiles/r06_fwd4.txt)
-  const bool fwd4 = !o.train && ntiles > e.compute_units && env_int("GOCTR_FWD4", 1) != 0;
+  const bool fwd4 = !o.train && (int)cdiv(o.rows_for_dispatch(B), 32) > e.compute_units && env_int("GOCTR_FWD4", 1) != 0;
   const dim3 grid((unsigned)(persist ? std::min(ntiles, (fwd4 ? 2 : 1) * e.compute_units) : ntiles));
   static const char* const kSym[3][2] = {{"ctr_chain_x3_kernel<2,false>", "ctr_chain_x3_kernel<2,true>"},
                                          {"ctr_chain_x3_kernel<9,false>", "ctr_chain_x3_kernel<9,true>"},
@@ -494,7 +494,7 @@ int launch_chain_x3(goctr_model* m, const RowSource& src, int B, const StepOpts&
   // (Round 4 also built a 16-row tile kernel -- two workgroups per CU -- which lost, 25.8 against 20.9 us at cfg3: a 16-row
   // tile's dependent pipeline is as long as a 32-row tile's.  The kernel left the tree in round 5; DESIGN_HISTORY.md and
   // profiles/r04_chain_x16_ab.txt keep the record, git keeps csrc/ctr_chain_x16.h.)
-  if (ps.on) prof_note_kernel(GOCTR_K_CHAIN, fwd4 ? (m->x3_nch0 == 2 ? "ctr_fwd4_kernel<2,false>" : m->x3_nch0 == 9 ? "ctr_fwd4_kernel<9,false>" : "ctr_fwd4_kernel<15,true>")
+  if (ps.note) prof_note_kernel(GOCTR_K_CHAIN, fwd4 ? (m->x3_nch0 == 2 ? "ctr_fwd4_kernel<2,false>" : m->x3_nch0 == 9 ? "ctr_fwd4_kernel<9,false>" : "ctr_fwd4_kernel<15,true>")
                                                   : kSym[m->x3_nch0 == 2 ? 0 : m->x3_nch0 == 9 ? 1 : 2][o.train ? 0 : 1]);
   if (fwd4) launch_fwd4(m->x3_nch0, a, grid, e.active);
   else
@@ -555,13 +555,13 @@ int launch_chain(goctr_model* m, const RowSource& src, int B, const StepOpts& o,
   const size_t lds = chain_lds_bytes<5>(m->Ip, m->H1p, m->H2p);
   const int dmode = (a.d0.mode || a.d1.mode) ? o.drop_mode : 0;
   // forward only and too few rows to give every CU a 32-row workgroup: 16-row workgroups, H1 split over 4 wavefronts
-  if (!o.train && cdiv(B, 32) < e.compute_units) {
-    if (ps.on) prof_note_kernel(GOCTR_K_CHAIN, "ctr_fwd16_kernel<4,5>");
+  if (!o.train && cdiv(o.rows_for_dispatch(B), 32) < e.compute_units) {
+    if (ps.note) prof_note_kernel(GOCTR_K_CHAIN, "ctr_fwd16_kernel<4,5>");
     hipLaunchKernelGGL((ctr_fwd16_kernel<4, 5>), dim3((unsigned)cdiv(B, 16)), dim3(512), lds, e.active, a);
   } else
-  if (dmode == 0) { if (ps.on) prof_note_kernel(GOCTR_K_CHAIN, "ctr_chain_kernel<7,5,0>"); hipLaunchKernelGGL((ctr_chain_kernel<7, 5, 0>), grid, dim3(512), lds, e.active, a); }
-  else if (dmode == 1) { if (ps.on) prof_note_kernel(GOCTR_K_CHAIN, "ctr_chain_kernel<7,5,1>"); hipLaunchKernelGGL((ctr_chain_kernel<7, 5, 1>), grid, dim3(512), lds, e.active, a); }
-  else { if (ps.on) prof_note_kernel(GOCTR_K_CHAIN, "ctr_chain_kernel<7,5,2>"); hipLaunchKernelGGL((ctr_chain_kernel<7, 5, 2>), grid, dim3(512), lds, e.active, a); }
+  if (dmode == 0) { if (ps.note) prof_note_kernel(GOCTR_K_CHAIN, "ctr_chain_kernel<7,5,0>"); hipLaunchKernelGGL((ctr_chain_kernel<7, 5, 0>), grid, dim3(512), lds, e.active, a); }
+  else if (dmode == 1) { if (ps.note) prof_note_kernel(GOCTR_K_CHAIN, "ctr_chain_kernel<7,5,1>"); hipLaunchKernelGGL((ctr_chain_kernel<7, 5, 1>), grid, dim3(512), lds, e.active, a); }
+  else { if (ps.note) prof_note_kernel(GOCTR_K_CHAIN, "ctr_chain_kernel<7,5,2>"); hipLaunchKernelGGL((ctr_chain_kernel<7, 5, 2>), grid, dim3(512), lds, e.active, a); }
   GOCTR_HIP(hipGetLastError());
   if (dbg) {
     unsigned long long h[CHAIN_NSTAMP];
@@ -597,6 +597,12 @@ int launch_serve16(goctr_model* m, const RowSource& src, int B, const StepState*
   const size_t lds = chain_lds_bytes<5>(m->Ip, m->H1p, m->H2p);
   const dim3 grid((unsigned)cdiv(B, 16)), blk(1024);
   hipStream_t s = engine().active;
+  ProfScope ps(GOCTR_K_CHAIN);
+  if (ps.note) {   // (as launch_chain does; on a slot's stream the launch is counted, not timed)
+    char sym[48];
+    snprintf(sym, sizeof sym, "ctr_serve16_kernel<%d,%d,%d>", groups == 2 || groups == 4 ? groups : 16, fast, m->Ip <= 160 ? 10 : 15);
+    prof_note_kernel(GOCTR_K_CHAIN, prof_intern(sym));
+  }
 #define GOCTR_SERVE16_H(L, H)                                                                          \
   do {                                                                                                 \
     if (fast == 1) hipLaunchKernelGGL((ctr_serve16_kernel<L, 1, H>), grid, blk, lds, s, aa, a);        \

@@ -232,6 +232,11 @@ struct StepOpts {
   // pipelined steps (graph replay, single GPU): a step's h0 was computed by the PREVIOUS step's last launch
   // (reduce_attn_kernel, ctr_kernels.h) -- launch_forward skips attn_fwd, launch_backward ends with the merged launch
   bool pipelined = false;
+  // forward only: the row count the KERNELS are chosen for when that is more than the launch's own rows -- the last, short pass
+  // of a serving request that was cut into several passes runs the kernels of its full passes, so that every row of one request
+  // is scored by the same kernels (the 16-row and the bf16-split forward kernels differ in the last bit)
+  int dispatch_rows = 0;
+  int rows_for_dispatch(int B) const { return dispatch_rows > B ? dispatch_rows : B; }
 };
 
 // ---------------------------------------------------------------- the dense step (ctr.hip)

@@ -165,8 +165,9 @@ static const char* kNames[GOCTR_K_COUNT] = {
     "attn_fwd", "gemm_fwd0", "gemm_fwd1", "gemm_out", "bwd_dz1", "bwd_dz0", "bwd_dp",
     "attn_bwd", "dW0", "dW1", "dW2", "reduce", "allreduce", "adam", "chain", "emb_train", "emb_grad", "emb_plan"};
 
-// (main-stream launches only: the event pool is not shared with the serving slots' threads)
-ProfScope::ProfScope(int kernel_id) : id(kernel_id), on(engine().prof && t_active == nullptr) {
+// (timed: main-stream launches only -- the event pool is not shared with the serving slots' threads; a slot's launch is counted)
+ProfScope::ProfScope(int kernel_id) : id(kernel_id), on(engine().prof && t_active == nullptr), note(engine().prof) {
+  if (note && !on) engine().prof_n_slot[id].fetch_add(1, std::memory_order_relaxed);
   if (!on) return;
   Engine& e = engine();
   auto get = [&]() {
@@ -184,6 +185,12 @@ ProfScope::~ProfScope() {
   (void)hipEventRecord(b, e.active);
   e.pending.push_back({id, a, b});
   if (e.pending.size() > 4096) prof_flush();
+}
+const char* prof_intern(const char* symbol) {
+  static std::mutex mu;
+  static std::map<std::string, int> pool;        // (a map's keys never move)
+  std::lock_guard<std::mutex> lk(mu);
+  return pool.emplace(symbol, 0).first->first.c_str();
 }
 void prof_flush() {
   Engine& e = engine();
@@ -434,7 +441,7 @@ int goctr_prof_enable(int on) {
 int goctr_prof_reset(void) {
   GOCTR_ENTER();
   prof_flush();
-  for (int i = 0; i < GOCTR_K_COUNT; ++i) { engine().prof_ms[i] = 0; engine().prof_n[i] = 0; }
+  for (int i = 0; i < GOCTR_K_COUNT; ++i) { engine().prof_ms[i] = 0; engine().prof_n[i] = 0; engine().prof_n_slot[i].store(0); }
   return 0;
 }
 int goctr_prof_get(int id, double* ms, int64_t* n) {
@@ -442,7 +449,7 @@ int goctr_prof_get(int id, double* ms, int64_t* n) {
   GOCTR_CHECK(id >= 0 && id < GOCTR_K_COUNT, "goctr_prof_get: bad kernel id %d", id);
   prof_flush();
   if (ms) *ms = engine().prof_ms[id];
-  if (n) *n = engine().prof_n[id];
+  if (n) *n = engine().prof_n[id] + engine().prof_n_slot[id].load();
   return 0;
 }
 const char* goctr_prof_name(int id) { return id >= 0 && id < GOCTR_K_COUNT ? kNames[id] : "?"; }

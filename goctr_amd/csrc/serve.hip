@@ -210,7 +210,7 @@ int serve_wait_rows(goctr_emb* e) {
 // ensure_keys / ws.ensure for N rows and waited for pending weight / row writes.  host_visible: dscore is pinned host memory, so
 // a one-launch pass may stamp its workgroups' completion there (*n_stamps of them; 0: wait on the stream).
 int serve_score_keys(goctr_model* m, goctr_recsys* r, ServeSlot* s, const long long* dts, const int32_t* dus, const int32_t* dit,
-                     int64_t N, float* dscore, unsigned char* dfail, bool host_visible, unsigned* n_stamps) {
+                     int64_t N, float* dscore, unsigned char* dfail, bool host_visible, unsigned* n_stamps, int64_t dispatch_rows = 0) {
   const int T = m->cfg.T;
   goctr_ubcache* const c = r->ub;
   StreamScope on_slot(s->stream);
@@ -235,12 +235,13 @@ int serve_score_keys(goctr_model* m, goctr_recsys* r, ServeSlot* s, const long l
   fb.yhat = dscore;
   StepOpts op;
   op.train = false;
+  op.dispatch_rows = (int)dispatch_rows;             // (the short last pass of a request of several passes: StepOpts says why)
   // A zero-copy pass of one launch: the kernel's workgroups stamp this pass's number into the pinned buffer behind their scores,
   // and the host watches the stamps instead of waiting for the stream's completion signal -- for passes of up to
   // GOCTR_SERVE_POLL_ROWS rows (default 512; 0 = never): the release fence in front of a stamp writes back the rows' h0 from the
   // L2, which costs a 2048-row pass more than the wait saves (profiles/r05_serve_poll.txt; 256 rows until the keys went over the BAR).
   *n_stamps = 0;
-  if (fuse && serve16_ok(m, src, (int)N)) {          // key lookup + attention + forward chain: one launch
+  if (fuse && serve16_ok(m, src, op.rows_for_dispatch((int)N))) {          // key lookup + attention + forward chain: one launch
     const bool poll = host_visible && N <= (int64_t)env_int("GOCTR_SERVE_POLL_ROWS", 512);
     if (poll) { if (++s->epoch == 0) s->epoch = 1; *n_stamps = (unsigned)cdiv(N, 16); }
     if (launch_serve16(m, src, (int)N, s->st.p, fb, poll ? s->h_done : nullptr, s->epoch)) return -1;
@@ -250,8 +251,8 @@ int serve_score_keys(goctr_model* m, goctr_recsys* r, ServeSlot* s, const long l
 }
 
 // One pass: the keys of `segs` (N rows in all, N <= SERVE_PASS_ROWS) -> scores / failed flags of every segment.
-// Caller holds m->mu shared and owns the slot.
-int serve_keys_pass(goctr_model* m, goctr_recsys* r, ServeSlot* s, KeySeg* const* segs, int nseg) {
+// Caller holds m->mu shared and owns the slot.  dispatch_rows: StepOpts::dispatch_rows (0: the pass's own rows).
+int serve_keys_pass(goctr_model* m, goctr_recsys* r, ServeSlot* s, KeySeg* const* segs, int nseg, int64_t dispatch_rows = 0) {
   int64_t N = 0;
   for (int k = 0; k < nseg; ++k) N += segs[k]->n;
   const int T = m->cfg.T;
@@ -294,7 +295,7 @@ int serve_keys_pass(goctr_model* m, goctr_recsys* r, ServeSlot* s, KeySeg* const
   unsigned char* dfail = reinterpret_cast<unsigned char*>(out_base + 4 * Br);
   UbRead image(r->ub, s->stream);                     // one pass, one image of the cache: held until the wait below
   unsigned n_stamps = 0;
-  if (serve_score_keys(m, r, s, dts, dus, dit, N, dscore, dfail, zc, &n_stamps)) return -1;
+  if (serve_score_keys(m, r, s, dts, dus, dit, N, dscore, dfail, zc, &n_stamps, dispatch_rows)) return -1;
   bool want_failed = false;
   for (int k = 0; k < nseg; ++k) want_failed = want_failed || segs[k]->failed || segs[k]->n_failed >= 0;
   // scores and flags are adjacent: one copy back (the gap between them is < 128 bytes)
@@ -348,7 +349,8 @@ int serve_keys_direct(goctr_model* m, goctr_recsys* r, KeySeg& g) {
     if (g.failed) part.failed = g.failed + o;
     part.n_failed = want_failed;
     KeySeg* one = &part;
-    if (serve_keys_pass(m, r, lease.s, &one, 1)) return -1;
+    // (a request of several passes: its short last pass runs the kernels of the full ones -- one request, one set of kernels)
+    if (serve_keys_pass(m, r, lease.s, &one, 1, g.n > SERVE_PASS_ROWS ? SERVE_PASS_ROWS : 0)) return -1;
     if (part.n_failed > 0) total_failed += part.n_failed;
   }
   g.n_failed = total_failed;

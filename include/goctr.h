@@ -1108,7 +1108,8 @@ enum { GOCTR_K_ATTN_FWD = 0, GOCTR_K_GEMM_FWD0, GOCTR_K_GEMM_FWD1, GOCTR_K_GEMM_
        GOCTR_K_COUNT };
 int goctr_prof_enable(int on);
 int goctr_prof_reset(void);
-/* total milliseconds and launch count per kernel family since the last reset */
+/* total milliseconds and launch count per kernel family since the last reset.  Launches of the serving entry points (on a
+ * serving slot's stream) are counted and their symbol is noted, but they are not timed: total_ms covers the main stream only. */
 int goctr_prof_get(int kernel_id, double* total_ms, int64_t* launches);
 const char* goctr_prof_name(int kernel_id);
 /* symbol (name + template arguments, e.g. "ctr_chain_x3_kernel<9,false>") of the kernel the family's last profiled launch

@@ -85,6 +85,14 @@ SHAPE_CASES = {
     # beyond the issue's list: dense rows wider than 192 columns, so that the widest scalar-lane instantiation (four columns per
     # lane) runs with its fourth column in use
     "k": ("dense", 5, 6, 200, 3, (200, 80), [(0, 0)]),
+    # the widths the fused chain kernels accept (chain_ok: H1p = 208 or 224, H2p = 80, Ip <= 240) away from 200 / 80 and from the
+    # two K phases of Ip = 48 .. 160; tests/test_gpu_ctr_shapes.py has the host arithmetic of each
+    "l": ("id", 20, 8, 16, 10, (224, 80), [(0, 0), (1, 0)]),        # 14 tiles of H1, no pad column
+    "m": ("id", 20, 8, 16, 10, (220, 70), [(0, 0), (0, 1)]),        # 14 tiles, pad columns in H1 and H2
+    "n": ("id", 52, 8, 16, 53, (195, 66), [(0, 0), (1, 0)]),        # Ip = 144, H1p = 208: the bf16-split chain with pad columns
+    "o": ("id", 60, 8, 16, 70, (200, 80), [(0, 0), (1, 0)]),        # Ip = 176: three K phases
+    "p": ("id", 100, 8, 16, 108, (200, 80), [(0, 0)]),              # I = Ip = 240: the bf16-split chain at its widest
+    "q": ("id", 20, 8, 16, 28, (200, 80), [(0, 0)]),                # I = Ip = 80: exactly one full K phase
 }
 SHAPE_PARAMS = [(name, kind, att) for name, c in SHAPE_CASES.items() for kind, att in c[6]]
 SHAPE_B, SHAPE_VALID, SHAPE_TRAIN_ROWS, SHAPE_V = 64, 50, 150, 300
@@ -112,7 +120,8 @@ SHAPE_LR = {name: 0.001 if name == "j" else 0.01 for name in SHAPE_CASES}
 SHAPE_SEED_CANDIDATES = 7
 SHAPE_SEED_PICK = {("a", 0, 0): 6, ("a", 0, 1): 4, ("a", 1, 0): 2, ("b", 0, 0): 4, ("c", 0, 0): 3, ("c", 0, 1): 6, ("d", 0, 0): 6,
                    ("d", 1, 0): 3, ("e", 0, 0): 1, ("f", 0, 0): 0, ("f", 1, 0): 6, ("g", 1, 0): 6, ("g", 0, 0): 0, ("h", 0, 0): 4,
-                   ("i", 0, 0): 0, ("j", 0, 0): 5, ("k", 0, 0): 5}
+                   ("i", 0, 0): 0, ("j", 0, 0): 5, ("k", 0, 0): 5, ("l", 0, 0): 4, ("l", 1, 0): 6, ("m", 0, 0): 5, ("m", 0, 1): 4,
+                   ("n", 0, 0): 4, ("n", 1, 0): 6, ("o", 0, 0): 4, ("o", 1, 0): 4, ("p", 0, 0): 1, ("q", 0, 0): 1}
 
 
 def shape_seed(name, kind, att, pick=None):

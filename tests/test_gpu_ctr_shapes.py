@@ -27,6 +27,25 @@ launch_weight_grads takes launch_dw_separate when max(H1p, H2p, DIN: Tp) / 16 > 
      parameter buffer is longer than one 256-thread block of the reduce / Adam launches
   j  D = 256, H = 1024 / 1024: all of d, f, g at the oracle's limits (NT = 64: grid.y = 3; every operand takes several K phases)
   k  dense D = 200 (not in the issue's list): attn_fwd_wide_kernel<4> / attn_bwd_kernel<4,64,2> with their fourth column (192 .. 199) in use
+
+The widths the fused chain kernels ACCEPT (chain_ok: H1p / 16 = 13 or 14, H2p = 80, Ip <= 16 CHAIN_HV = 240, DIN: Dp <= 32) away from
+the 200 / 80 and Ip = 48 .. 160 every other test has; all id mode, T = 8, D = 16 (four 4-column lanes: attn_fwd_kernel<4,4,fast>).
+ctr_chain_kernel takes 80 rows of W0 per K phase (CHAIN_KPH0), so ceil(Ip / 80) phases: one up to 80, two up to 160 (every
+shape tested so far), three from 176; the bf16-split chain
+(chain_x3_shape_ok: H1p = 208 and Ip / 16 = 2, 9 or 15) runs training steps unless the masks are explicit (dropout mode 1):
+  l  H = 224 / 80, I = 20 + 32 + 10 = 62 -> Ip = 64: H1p = 224, 14 tiles of H1 -- the wavefronts' 4,4,3,3 split with no pad column;
+     224 != 208 -> ctr_chain_kernel<7,5,0>, one K phase of 64 rows
+  m  H = 220 / 70: H1p = 224 with 4 pad columns, H2p = 80 with 10 (masked by n < H1, n < H2; the dropout masks' stride is H1 = 220,
+     not H1p) -> ctr_chain_kernel<7,5,0>
+  n  H = 195 / 66, U = 52, Cc = 53: I = 137 -> Ip = 144, H1p = 208 -> ctr_chain_x3_kernel<9,false> with 13 pad columns of H1 and 14
+     of H2.  DIN, frozen table, D = 16, T <= 64: the attention backward rides in that launch (attn_bwd_in_chain) -- no attn_bwd
+     launch in the training step; with explicit masks the step is ctr_chain_kernel<7,5,1> at Ip = 144 (two K phases)
+  o  U = 60, Cc = 70: I = 162 -> Ip = 176, 11 fragments: no bf16-split images -> ctr_chain_kernel<7,5,0> with three K phases
+  p  U = 100, Cc = 108: I = 240 = Ip = 16 CHAIN_HV: ctr_chain_x3_kernel<15,false> run by DIN (until now only YouTube's D = 64
+     shape had 15 fragments), attention backward in the chain launch as at n
+  q  U = 20, Cc = 28: I = 80 = Ip: no pad column in h0, exactly one full K phase
+One-step checks run on the dense assembly of the rows (goctr_loss_grad_dense): the same chain kernels behind the scalar-lane
+attention kernels; predict and training run in id mode, training through the captured, pipelined step graphs (pipeline_ok).
 """
 import functools
 import os
@@ -45,7 +64,8 @@ pytestmark = pytest.mark.gpu
 B, VALID, ROWS = R.SHAPE_B, R.SHAPE_VALID, R.SHAPE_TRAIN_ROWS
 
 # name -> (attention forward symbol by kind [DIN cosine, DIN euclid, YouTube], attention backward symbol,
-#          launch_dw_separate?, generic per-layer GEMM launches (no chain kernel) for certain?)
+#          launch_dw_separate?, generic per-layer GEMM launches (no chain kernel) for certain?[, the chain symbol of a training step])
+# attention backward symbol None: DIN's attention backward is no launch of its own, it rides in the chain launch (attn_bwd_in_chain)
 FAST = ("attn_fwd_kernel<4,%d,2>", "attn_fwd_kernel<4,%d,3>", "attn_fwd_kernel<4,%d,1>")
 KERNELS = {
     "a": (("attn_fwd_wide_kernel<2>",) * 3, "attn_bwd_kernel<2,64,2>", False, False),
@@ -59,6 +79,12 @@ KERNELS = {
     "i": (tuple(s % 1 for s in FAST), "attn_bwd_kernel<4,1,1>", True, False),
     "j": (("attn_fwd_kernel<4,64,0>",) * 3, "attn_bwd_kernel<4,64,0>", True, True),
     "k": (("attn_fwd_wide_kernel<4>",) * 3, "attn_bwd_kernel<4,64,2>", False, False),
+    "l": (tuple(s % 4 for s in FAST), "attn_bwd_kernel<4,4,1>", False, False, "ctr_chain_kernel<7,5,0>"),
+    "m": (tuple(s % 4 for s in FAST), "attn_bwd_kernel<4,4,1>", False, False, "ctr_chain_kernel<7,5,0>"),
+    "n": (tuple(s % 4 for s in FAST), None, False, False, "ctr_chain_x3_kernel<9,false>"),
+    "o": (tuple(s % 4 for s in FAST), "attn_bwd_kernel<4,4,1>", False, False, "ctr_chain_kernel<7,5,0>"),
+    "p": (tuple(s % 4 for s in FAST), None, False, False, "ctr_chain_x3_kernel<15,false>"),
+    "q": (tuple(s % 4 for s in FAST), "attn_bwd_kernel<4,4,1>", False, False, "ctr_chain_kernel<7,5,0>"),
 }
 
 
@@ -157,6 +183,45 @@ def test_one_step_with_dropout_wide_dense_rows(kind, att):
         gm.loss_grad(dm, si, X, Y, cfg=runs[0][0], m0=m0[:, :-1], m1=m1)
 
 
+CHAIN_DROP = [(name, kind, att) for name in ("m", "n") for kind, att in R.SHAPE_CASES[name][6]]
+
+
+@pytest.mark.parametrize("name,kind,att", CHAIN_DROP, ids=[case_id(p) for p in CHAIN_DROP])
+def test_one_step_with_dropout_in_the_chain_kernels(name, kind, att):
+    """cases m (220 / 70) and n (195 / 66 at Ip = 144) with dropout, as the test above: explicit masks [B, H1] / [B, H2], whose row
+    stride H1 is 4 / 13 short of H1p and H2 10 / 14 short of H2p (ctr_chain_kernel<7,5,1>; the bf16-split kernel declines explicit
+    masks, so case n takes that kernel too), and the counter hash (ctr_chain_kernel<7,5,2> at m, the bf16-split
+    kernel at n), held to the oracle by grad_close -- and the chain symbol each run reports"""
+    from goctr_amd import capi, model as gm
+    ref = reference(name, kind, att)
+    dm, si = device_model(ref)
+    H1, H2 = ref.hidden
+    X, Y = ref.X[:B], ref.Y[:B]
+    rng = np.random.default_rng(56)
+    m0 = (rng.random((B, H1)) < 0.75).astype(np.float32); m1 = (rng.random((B, H2)) < 0.5).astype(np.float32)
+    runs = ((capi.default_train_cfg(batch=B, dropout_mode=1, p0=0.25, p1=0.5), dict(m0=m0, m1=m1), 0, dict(mode=1, p0=0.25, p1=0.5, m0=m0, m1=m1),
+             "ctr_chain_kernel<7,5,1>"),
+            (capi.default_train_cfg(batch=B, dropout_mode=2, p0=0.25, p1=0.5, seed=1234), {}, 7, dict(mode=2, p0=0.25, p1=0.5, seed=1234, step=7),
+             "ctr_chain_kernel<7,5,2>" if name == "m" else "ctr_chain_x3_kernel<9,false>"))
+    for cfg, masks, step, drop, chain_sym in runs:
+        capi.prof_enable(True)
+        try:
+            capi.prof_reset()
+            cost, g, y = gm.loss_grad(dm, si, X, Y, cfg=cfg, step=step, **masks)
+            n_chain, sym = capi.prof_get()["chain"][1], capi.prof_kernels()["chain"]
+        finally:
+            capi.prof_enable(False)
+        assert n_chain >= 1 and sym == chain_sym
+        rcost, rg, ry = ref.om.loss_grad(X, Y, drop=drop)
+        print(f"\ncase {case_id((name, kind, att))} dropout mode {drop['mode']}: logits {np.max(np.abs(y - ry)):.2e} cost {abs(cost - rcost):.2e}")
+        assert np.max(np.abs(y - ry)) <= LOGIT_TOL and abs(cost - rcost) <= LOSS_TOL
+        assert grad_close(g["mlp0"], rg["W0"]) and grad_close(g["mlp1"], rg["W1"]) and grad_close(g["mlp2"].ravel(), rg["W2"].ravel())
+        if kind == 0:
+            assert np.max(np.abs(rg["att0"])) > 0 and grad_close(g["att0"].ravel(), rg["att0"])
+    with pytest.raises(ValueError):
+        gm.loss_grad(dm, si, X, Y, cfg=runs[0][0], m0=m0[:, :-1], m1=m1)
+
+
 @CASES
 def test_predict(name, kind, att):
     from goctr_amd import model as gm
@@ -206,7 +271,8 @@ def test_the_case_runs_the_kernel_it_is_here_for(name, kind, att):
     ref = reference(name, kind, att)
     dm, si = device_model(ref)
     ds, tab = device_dataset(ref, si)
-    fwd_syms, bwd_sym, separate, generic = KERNELS[name]
+    fwd_syms, bwd_sym, separate, generic = KERNELS[name][:4]
+    chain_sym = KERNELS[name][4] if len(KERNELS[name]) > 4 else None
     fwd_sym = fwd_syms[2 if kind == 1 else att]
     capi.prof_enable(True)
     try:
@@ -220,10 +286,13 @@ def test_the_case_runs_the_kernel_it_is_here_for(name, kind, att):
     finally:
         capi.prof_enable(False)
     assert n["attn_fwd"] >= 1 and syms["attn_fwd"] == fwd_sym
-    if kind == 0:
+    if kind == 0 and bwd_sym is not None:
         assert n["attn_bwd"] == 1 and syms["attn_bwd"] == bwd_sym
     else:
         assert n["attn_bwd"] == 0
+    if chain_sym is not None:
+        assert n["chain"] >= 1 and syms["chain"] == chain_sym
+        assert n["gemm_fwd0"] == 0 and n["gemm_fwd1"] == 0 and n["gemm_out"] == 0 and n["bwd_dz0"] == 0
     assert (n["dW1"] > 0) == separate                   # (only launch_dw_separate launches under that family)
     if separate:
         assert n["dW0"] == 1 and n["dW1"] == 1 and n["dW2"] == (2 if kind == 0 else 1)

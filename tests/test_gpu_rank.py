@@ -8,7 +8,9 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def build(oracle, rng, kind, n_users=40, n_items=300, n_emb_only=20, T=10, D=16, U=7, Cc=9, max_hist=30):
+def build(oracle, rng, kind, n_users=40, n_items=300, n_emb_only=20, T=10, D=16, U=7, Cc=9, max_hist=30, att=0, hidden=None):
+    """att: DIN's attention (0 cosine, 1 Euclidean); hidden: (H1, H2), default the reference's 200 / 80 -- both go to the oracle
+    model and to the device model (tests/test_gpu_serve_shapes.py)"""
     from goctr_amd import model as gm, recommend as gr, ubcache
     # ids are arbitrary ints like in the reference (not dense): users 1000+3k, items 7+5k
     uids = [1000 + 3 * k for k in range(n_users)]
@@ -24,13 +26,15 @@ def build(oracle, rng, kind, n_users=40, n_items=300, n_emb_only=20, T=10, D=16,
         its = rng.choice(iids + extra + [999_999], size=n)           # incl. an item unknown to every table
         ubc.Set(u, ubcache.TimeSeq(ts.tolist(), [int(x) for x in its]))
     rs = gr.DeviceRecSys(ufeat, ifeat, iemb, ubc, T=T)
-    om = oracle.CtrModel(kind, U, T, D, Cc)
+    H1, H2 = hidden if hidden is not None else (200, 80)
+    om = oracle.CtrModel(kind, U, T, D, Cc, H1=H1, H2=H2, att=att)
     om.W0[:] = (rng.standard_normal(om.W0.shape) * 0.2).astype(np.float32)
     om.W1[:] = (rng.standard_normal(om.W1.shape) * 0.2).astype(np.float32)
     om.W2[:] = (rng.standard_normal(om.W2.shape) * 0.2).astype(np.float32)
     if kind == 0:
         om.att0[:] = (1 + 0.3 * rng.standard_normal(T)).astype(np.float32)
-    net = (gm.DinNet if kind == 0 else gm.YoutubeDnn)(U, T, D, D, Cc)
+    kw = {} if hidden is None else {"hidden": hidden}
+    net = gm.DinNet(U, T, D, D, Cc, att=att, **kw) if kind == 0 else gm.YoutubeDnn(U, T, D, D, Cc, **kw)
     for n, w in (("mlp0", om.W0), ("mlp1", om.W1), ("mlp2", om.W2)):
         net.set_weights(n, w)
     if kind == 0:
@@ -40,7 +44,12 @@ def build(oracle, rng, kind, n_users=40, n_items=300, n_emb_only=20, T=10, D=16,
 
 def oracle_scores(oracle, rs, om, keys, batch):
     """the reference's BatchPredict with the oracle's pieces: keys -> dense indices -> rows -> predict"""
-    users, items, ts = rs.keys(keys)
+    X, failed = oracle_rows(oracle, rs, *rs.keys(keys))
+    return om.predict(X, batch), failed
+
+
+def oracle_rows(oracle, rs, users, items, ts):
+    """the rows BatchPredict assembles for these dense-index keys (a failing key: the all-zero row) and the failed flags"""
     dc = rs._dense_cache
     ids = sorted(dc.ub)
     off = np.zeros(len(ids) + 1, np.int64)
@@ -48,9 +57,7 @@ def oracle_scores(oracle, rs, om, keys, batch):
         off[k + 1] = off[k] + len(dc.ub[u].Ts)
     seq_items = np.concatenate([np.asarray(dc.ub[u].Items, np.int32) for u in ids])
     seq_ts = np.concatenate([np.asarray(dc.ub[u].Ts, np.int64) for u in ids])
-    X, failed = oracle.batch_predict_rows(rs.emb.get_rows(), off, seq_items, seq_ts, rs.user_table, rs.item_table, users, items,
-                                          ts, rs.T)
-    return om.predict(X, batch), failed
+    return oracle.batch_predict_rows(rs.emb.get_rows(), off, seq_items, seq_ts, rs.user_table, rs.item_table, users, items, ts, rs.T)
 
 
 @pytest.mark.parametrize("kind", [0, 1])

@@ -191,8 +191,19 @@ def test_targets(fx):
 
 
 def test_default_pass_crosses_the_forward_kernel_switch(oracle):
+    default_pass_against_the_oracle(oracle)
+
+
+def test_default_pass_with_euclidean_attention_and_pad_columns_in_the_chain(oracle):
+    """the same call off the reference's model: Euclidean attention, hidden widths 220 / 70 (14 tiles of H1, pad columns in both
+    layers inside the fused chain) -- the catalogue scorer is serve_score_keys' second caller, its keys are written on the device
+    and its scores are not host-visible (tests/test_gpu_serve_shapes.py has the first caller at these shapes)"""
+    default_pass_against_the_oracle(oracle, att=1, hidden=(220, 70))
+
+
+def default_pass_against_the_oracle(oracle, **kw):
     from goctr_amd import recommend as gr
-    f = Fix(oracle, 901, n_items=1000)
+    f = Fix(oracle, 901, n_items=1000, **kw)
     rng = np.random.default_rng(3)
     users = rng.integers(0, f.n_users, size=20).astype(np.int32)
     ts = rng.integers(0, 1100, size=20).astype(np.int64)
