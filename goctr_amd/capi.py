@@ -523,132 +523,33 @@ def device_info():
     return name.value.decode(), cus.value, hbm.value
 
 
-def default_train_cfg(**kw) -> TrainCfg:
-    c = TrainCfg()
-    load().goctr_train_cfg_default(C.byref(c))
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
+def _default(struct, symbol):
+    """a ``default_*_cfg``: ``struct`` as the library's ``symbol`` fills it, then the caller's fields"""
+    def default(**kw) -> struct:
+        c = struct()
+        getattr(load(), symbol)(C.byref(c))
+        for k, v in kw.items():
+            setattr(c, k, v)
+        return c
+    return default
 
 
-def default_curve_cfg(**kw) -> CurveCfg:
-    c = CurveCfg()
-    load().goctr_curve_cfg_default(C.byref(c))
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
-
-
-def default_multiclass_cfg(**kw) -> MulticlassCfg:
-    c = MulticlassCfg()
-    load().goctr_multiclass_cfg_default(C.byref(c))
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
-
-
-def default_negsample_cfg(**kw) -> NegSampleCfg:
-    c = NegSampleCfg()
-    load().goctr_negsample_cfg_default(C.byref(c))
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
-
-
-def default_topn_cfg(**kw) -> TopnCfg:
-    c = TopnCfg()
-    load().goctr_topn_cfg_default(C.byref(c))
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
-
-
-def default_itemcf_cfg(**kw) -> ItemcfCfg:
-    c = ItemcfCfg()
-    load().goctr_itemcf_cfg_default(C.byref(c))
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
-
-
-def default_recall_cfg(**kw) -> RecallCfg:
-    c = RecallCfg()
-    load().goctr_recall_cfg_default(C.byref(c))
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
-
-
-def default_itemnbr_cfg(**kw) -> ItemnbrCfg:
-    c = ItemnbrCfg()
-    load().goctr_itemnbr_cfg_default(C.byref(c))
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
-
-
-def default_swing_cfg(**kw) -> SwingCfg:
-    c = SwingCfg()
-    load().goctr_swing_cfg_default(C.byref(c))
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
-
-
-def default_mmr_cfg(**kw) -> MmrCfg:
-    c = MmrCfg()
-    load().goctr_mmr_cfg_default(C.byref(c))
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
-
-
-def default_uservec_cfg(**kw) -> UservecCfg:
-    c = UservecCfg()
-    load().goctr_uservec_cfg_default(C.byref(c))
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
-
-
-def default_uservec_multi_cfg(**kw) -> UservecMultiCfg:
-    c = UservecMultiCfg()
-    load().goctr_uservec_multi_cfg_default(C.byref(c))
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
-
-
-def default_ivf_cfg(**kw) -> IvfCfg:
-    c = IvfCfg()
-    load().goctr_ivf_cfg_default(C.byref(c))
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
-
-
-def default_uservec_ivf_cfg(**kw) -> UservecIvfCfg:
-    c = UservecIvfCfg()
-    load().goctr_uservec_ivf_cfg_default(C.byref(c))
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
-
-
-def default_list_cfg(**kw) -> ListCfg:
-    c = ListCfg()
-    load().goctr_list_cfg_default(C.byref(c))
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
-
-
-def default_popular_cfg(**kw) -> PopularCfg:
-    c = PopularCfg()
-    load().goctr_popular_cfg_default(C.byref(c))
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
+default_train_cfg = _default(TrainCfg, "goctr_train_cfg_default")
+default_curve_cfg = _default(CurveCfg, "goctr_curve_cfg_default")
+default_multiclass_cfg = _default(MulticlassCfg, "goctr_multiclass_cfg_default")
+default_negsample_cfg = _default(NegSampleCfg, "goctr_negsample_cfg_default")
+default_topn_cfg = _default(TopnCfg, "goctr_topn_cfg_default")
+default_itemcf_cfg = _default(ItemcfCfg, "goctr_itemcf_cfg_default")
+default_recall_cfg = _default(RecallCfg, "goctr_recall_cfg_default")
+default_itemnbr_cfg = _default(ItemnbrCfg, "goctr_itemnbr_cfg_default")
+default_swing_cfg = _default(SwingCfg, "goctr_swing_cfg_default")
+default_mmr_cfg = _default(MmrCfg, "goctr_mmr_cfg_default")
+default_uservec_cfg = _default(UservecCfg, "goctr_uservec_cfg_default")
+default_uservec_multi_cfg = _default(UservecMultiCfg, "goctr_uservec_multi_cfg_default")
+default_ivf_cfg = _default(IvfCfg, "goctr_ivf_cfg_default")
+default_uservec_ivf_cfg = _default(UservecIvfCfg, "goctr_uservec_ivf_cfg_default")
+default_list_cfg = _default(ListCfg, "goctr_list_cfg_default")
+default_popular_cfg = _default(PopularCfg, "goctr_popular_cfg_default")
 
 
 PROF_COUNT = 18          # GOCTR_K_COUNT (include/goctr.h)

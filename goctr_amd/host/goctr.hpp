@@ -479,6 +479,22 @@ struct TopN {
   std::vector<int64_t> target_rank;              // per request row when targets were given: 0-based rank, -1 = not ranked
   int64_t n_failed = 0;
 };
+namespace detail {
+// what every Recommend*Batch function checks first, in this order; `fn` names it in the message
+inline void check_request(const char* fn, size_t n_users, size_t n_ts, size_t n_targets, int n) {
+  if (n_ts && n_ts != n_users) throw std::invalid_argument(std::string(fn) + ": one timestamp per user");
+  if (n_targets && n_targets != n_users) throw std::invalid_argument(std::string(fn) + ": one target per user");
+  if (n < 1) throw std::invalid_argument(std::string(fn) + ": n must be positive");
+}
+// a recommend entry's items / scores [n_req, n] and count [n_req] as one list per request row
+inline std::vector<std::vector<ItemScore>> gather_lists(const std::vector<int32_t>& items, const std::vector<float>& scores,
+                                                        const std::vector<int32_t>& count, int n) {
+  std::vector<std::vector<ItemScore>> lists(count.size());
+  for (size_t q = 0; q < count.size(); ++q)
+    for (int j = 0; j < count[q]; ++j) lists[q].push_back(ItemScore{items[q * n + j], scores[q * n + j]});
+  return lists;
+}
+}  // namespace detail
 inline TopN RecommendBatch(model::CtrNet& net, RecSys& rs, const std::vector<int32_t>& users, int n = 10,
                            const std::vector<int64_t>& ts = {}, const std::vector<int32_t>& pool = {},
                            int exclude = GOCTR_TOPN_DROP_ALL_SEEN, const std::vector<int32_t>& targets = {}, int64_t pass_rows = 0) {
@@ -486,9 +502,7 @@ inline TopN RecommendBatch(model::CtrNet& net, RecSys& rs, const std::vector<int
   goctr_topn_cfg_default(&cfg);
   cfg.k = n; cfg.exclude = exclude; cfg.pass_rows = pass_rows;
   const int64_t nq = (int64_t)users.size(), np = pool.empty() ? rs.n_items() : (int64_t)pool.size();
-  if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("RecommendBatch: one timestamp per user");
-  if (!targets.empty() && targets.size() != users.size()) throw std::invalid_argument("RecommendBatch: one target per user");
-  if (n < 1) throw std::invalid_argument("RecommendBatch: n must be positive");
+  detail::check_request("RecommendBatch", users.size(), ts.size(), targets.size(), n);
   std::vector<int32_t> items((size_t)nq * n), count((size_t)nq);
   std::vector<float> scores((size_t)nq * n);
   TopN out;
@@ -497,10 +511,7 @@ inline TopN RecommendBatch(model::CtrNet& net, RecSys& rs, const std::vector<int
                              pool.empty() ? nullptr : pool.data(), np, targets.empty() ? nullptr : targets.data(), &cfg,
                              items.data(), scores.data(), count.data(), targets.empty() ? nullptr : out.target_rank.data(),
                              nullptr, nullptr, &out.n_failed));
-  out.lists.resize((size_t)nq);
-  for (int64_t q = 0; q < nq; ++q)
-    for (int j = 0; j < count[(size_t)q]; ++j)
-      out.lists[(size_t)q].push_back(ItemScore{items[(size_t)q * n + j], scores[(size_t)q * n + j]});
+  out.lists = detail::gather_lists(items, scores, count, n);
   return out;
 }
 inline std::vector<ItemScore> Recommend(model::CtrNet& net, RecSys& rs, int userId, int n, int64_t now,
@@ -586,9 +597,7 @@ inline TopN RecommendItemCFBatch(model::CtrNet& net, RecSys& rs, const ItemCF& i
                                  const std::vector<int64_t>& ts = {}, const goctr_recall_cfg& rcfg = ItemCF::DefaultRecallCfg(),
                                  const std::vector<int32_t>& targets = {}, int64_t pass_rows = 0) {
   const int64_t nq = (int64_t)users.size();
-  if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("RecommendItemCFBatch: one timestamp per user");
-  if (!targets.empty() && targets.size() != users.size()) throw std::invalid_argument("RecommendItemCFBatch: one target per user");
-  if (n < 1) throw std::invalid_argument("RecommendItemCFBatch: n must be positive");
+  detail::check_request("RecommendItemCFBatch", users.size(), ts.size(), targets.size(), n);
   std::vector<int32_t> items((size_t)nq * n), count((size_t)nq);
   std::vector<float> scores((size_t)nq * n);
   TopN out;
@@ -597,10 +606,7 @@ inline TopN RecommendItemCFBatch(model::CtrNet& net, RecSys& rs, const ItemCF& i
                                targets.empty() ? nullptr : targets.data(), &rcfg, n, pass_rows, items.data(), scores.data(),
                                count.data(), nullptr, nullptr, targets.empty() ? nullptr : out.target_rank.data(), nullptr, nullptr,
                                nullptr, &out.n_failed));
-  out.lists.resize((size_t)nq);
-  for (int64_t q = 0; q < nq; ++q)
-    for (int j = 0; j < count[(size_t)q]; ++j)
-      out.lists[(size_t)q].push_back(ItemScore{items[(size_t)q * n + j], scores[(size_t)q * n + j]});
+  out.lists = detail::gather_lists(items, scores, count, n);
   return out;
 }
 inline std::vector<ItemScore> RecommendItemCF(model::CtrNet& net, RecSys& rs, const ItemCF& icf, int userId, int n, int64_t now,
@@ -671,10 +677,7 @@ inline TopN RecommendBlendBatch(model::CtrNet& net, RecSys& rs, const ItemCF* ic
                               extra.empty() ? nullptr : extra.data(), n_extra, &rcfg, quota_pop, n, pass_rows, items.data(), scores.data(),
                               count.data(), nullptr, nullptr, nullptr, targets.empty() ? nullptr : out.target_rank.data(), nullptr,
                               nullptr, nullptr, nullptr, &out.n_failed));
-  out.lists.resize((size_t)nq);
-  for (int64_t q = 0; q < nq; ++q)
-    for (int j = 0; j < count[(size_t)q]; ++j)
-      out.lists[(size_t)q].push_back(ItemScore{items[(size_t)q * n + j], scores[(size_t)q * n + j]});
+  out.lists = detail::gather_lists(items, scores, count, n);
   return out;
 }
 inline std::vector<ItemScore> RecommendBlend(model::CtrNet& net, RecSys& rs, const ItemCF* icf, const Popular* pop, int userId, int n,
@@ -729,10 +732,7 @@ inline TopN RecommendDiverseBatch(model::CtrNet& net, RecSys& rs, const ItemCF* 
                                   items.data(), scores.data(), count.data(), nullptr, nullptr, nullptr,
                                   targets.empty() ? nullptr : out.target_rank.data(), nullptr, nullptr, nullptr, nullptr, &out.n_failed,
                                   nullptr, nullptr, nullptr));
-  out.lists.resize((size_t)nq);
-  for (int64_t q = 0; q < nq; ++q)
-    for (int j = 0; j < count[(size_t)q]; ++j)
-      out.lists[(size_t)q].push_back(ItemScore{items[(size_t)q * n + j], scores[(size_t)q * n + j]});
+  out.lists = detail::gather_lists(items, scores, count, n);
   return out;
 }
 
@@ -756,9 +756,7 @@ inline TopN RecommendVectorBatch(model::CtrNet& net, RecSys& rs, const ItemVecto
                                  const goctr_uservec_cfg& ucfg = DefaultUservecCfg(), const std::vector<int32_t>& targets = {},
                                  int64_t pass_rows = 0) {
   const int64_t nq = (int64_t)users.size();
-  if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("RecommendVectorBatch: one timestamp per user");
-  if (!targets.empty() && targets.size() != users.size()) throw std::invalid_argument("RecommendVectorBatch: one target per user");
-  if (n < 1) throw std::invalid_argument("RecommendVectorBatch: n must be positive");
+  detail::check_request("RecommendVectorBatch", users.size(), ts.size(), targets.size(), n);
   std::vector<int32_t> items((size_t)nq * n), count((size_t)nq);
   std::vector<float> scores((size_t)nq * n);
   TopN out;
@@ -767,10 +765,7 @@ inline TopN RecommendVectorBatch(model::CtrNet& net, RecSys& rs, const ItemVecto
                                 targets.empty() ? nullptr : targets.data(), &rcfg, &ucfg, n, pass_rows, items.data(), scores.data(),
                                 count.data(), nullptr, nullptr, targets.empty() ? nullptr : out.target_rank.data(), nullptr, nullptr,
                                 nullptr, &out.n_failed));
-  out.lists.resize((size_t)nq);
-  for (int64_t q = 0; q < nq; ++q)
-    for (int j = 0; j < count[(size_t)q]; ++j)
-      out.lists[(size_t)q].push_back(ItemScore{items[(size_t)q * n + j], scores[(size_t)q * n + j]});
+  out.lists = detail::gather_lists(items, scores, count, n);
   return out;
 }
 inline std::vector<ItemScore> RecommendVector(model::CtrNet& net, RecSys& rs, const ItemVectors& vec, int userId, int n, int64_t now,
@@ -825,9 +820,7 @@ inline TopN RecommendVectorIndexedBatch(model::CtrNet& net, RecSys& rs, const Ve
                                         const goctr_uservec_ivf_cfg& icfg = VectorIndex::DefaultRecallCfg(),
                                         const std::vector<int32_t>& targets = {}, int64_t pass_rows = 0) {
   const int64_t nq = (int64_t)users.size();
-  if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("RecommendVectorIndexedBatch: one timestamp per user");
-  if (!targets.empty() && targets.size() != users.size()) throw std::invalid_argument("RecommendVectorIndexedBatch: one target per user");
-  if (n < 1) throw std::invalid_argument("RecommendVectorIndexedBatch: n must be positive");
+  detail::check_request("RecommendVectorIndexedBatch", users.size(), ts.size(), targets.size(), n);
   std::vector<int32_t> items((size_t)nq * n), count((size_t)nq);
   std::vector<float> scores((size_t)nq * n);
   TopN out;
@@ -836,10 +829,7 @@ inline TopN RecommendVectorIndexedBatch(model::CtrNet& net, RecSys& rs, const Ve
                                     targets.empty() ? nullptr : targets.data(), &rcfg, &icfg, n, pass_rows, items.data(), scores.data(),
                                     count.data(), nullptr, nullptr, targets.empty() ? nullptr : out.target_rank.data(), nullptr,
                                     nullptr, nullptr, &out.n_failed));
-  out.lists.resize((size_t)nq);
-  for (int64_t q = 0; q < nq; ++q)
-    for (int j = 0; j < count[(size_t)q]; ++j)
-      out.lists[(size_t)q].push_back(ItemScore{items[(size_t)q * n + j], scores[(size_t)q * n + j]});
+  out.lists = detail::gather_lists(items, scores, count, n);
   return out;
 }
 inline std::vector<ItemScore> RecommendVectorIndexed(model::CtrNet& net, RecSys& rs, const VectorIndex& index, int userId, int n,
@@ -879,9 +869,7 @@ inline TopN RecommendMultiInterestBatch(model::CtrNet& net, RecSys& rs, const It
                                         const goctr_uservec_multi_cfg& mcfg = DefaultUservecMultiCfg(),
                                         const std::vector<int32_t>& targets = {}, int64_t pass_rows = 0) {
   const int64_t nq = (int64_t)users.size();
-  if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("RecommendMultiInterestBatch: one timestamp per user");
-  if (!targets.empty() && targets.size() != users.size()) throw std::invalid_argument("RecommendMultiInterestBatch: one target per user");
-  if (n < 1) throw std::invalid_argument("RecommendMultiInterestBatch: n must be positive");
+  detail::check_request("RecommendMultiInterestBatch", users.size(), ts.size(), targets.size(), n);
   std::vector<int32_t> items((size_t)nq * n), count((size_t)nq);
   std::vector<float> scores((size_t)nq * n);
   TopN out;
@@ -891,10 +879,7 @@ inline TopN RecommendMultiInterestBatch(model::CtrNet& net, RecSys& rs, const It
                                       scores.data(), count.data(), nullptr, nullptr,
                                       targets.empty() ? nullptr : out.target_rank.data(), nullptr, nullptr, nullptr, &out.n_failed,
                                       nullptr, nullptr));
-  out.lists.resize((size_t)nq);
-  for (int64_t q = 0; q < nq; ++q)
-    for (int j = 0; j < count[(size_t)q]; ++j)
-      out.lists[(size_t)q].push_back(ItemScore{items[(size_t)q * n + j], scores[(size_t)q * n + j]});
+  out.lists = detail::gather_lists(items, scores, count, n);
   return out;
 }
 
@@ -922,10 +907,7 @@ inline TopN RecommendBlendVectorBatch(model::CtrNet& net, RecSys& rs, const Item
                                       scores.data(), count.data(), nullptr, nullptr, nullptr,
                                       targets.empty() ? nullptr : out.target_rank.data(), nullptr, nullptr, nullptr, nullptr, &out.n_failed,
                                       nullptr, nullptr, nullptr));
-  out.lists.resize((size_t)nq);
-  for (int64_t q = 0; q < nq; ++q)
-    for (int j = 0; j < count[(size_t)q]; ++j)
-      out.lists[(size_t)q].push_back(ItemScore{items[(size_t)q * k + j], scores[(size_t)q * k + j]});
+  out.lists = detail::gather_lists(items, scores, count, k);
   return out;
 }
 

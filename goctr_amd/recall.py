@@ -35,118 +35,76 @@ import numpy as np
 from . import capi
 
 EXCLUDE = {"keep": capi.TOPN_KEEP_SEEN, "all": capi.TOPN_DROP_ALL_SEEN, "before": capi.TOPN_DROP_SEEN_BEFORE}
-_BUILD_FIELDS = {"window", "max_len", "n_nbr", "min_co", "pair_budget"}
-_RECALL_FIELDS = {"history", "n_cand", "exclude"}
-_POPULAR_FIELDS = {"half_life", "ts_ref", "ts_lo", "ts_hi", "n_list"}
-_NBR_FIELDS = {"n_nbr", "min_w", "pass_items"}
-_SWING_FIELDS = {"max_len", "max_users", "alpha_q", "n_nbr", "min_pairs", "seed", "pair_budget"}
-_MMR_FIELDS = {"k", "pool", "lambda_q", "max_per_group"}
-_LIST_FIELDS = {"k", "tail_cnt"}
-_USERVEC_FIELDS = {"min_w", "chunk_items"}
-_USERVEC_MULTI_FIELDS = {"min_w", "max_interests", "iters", "split_w", "mix", "chunk_items"}
-_IVF_FIELDS = {"n_lists", "iters", "train_items", "pass_items"}
-_USERVEC_IVF_FIELDS = {"min_w", "nprobe", "chunk_items"}
 MIX = {"max": capi.UVMIX_MAX, "quota": capi.UVMIX_QUOTA}
 
 
-def make_cfg(**kw) -> capi.ItemcfCfg:
-    """goctr_itemcf_cfg from keywords (integers; the ranges are the library's to refuse)"""
-    unknown = set(kw) - _BUILD_FIELDS
-    if unknown:
-        raise TypeError(f"goctr_itemcf_cfg has no field {sorted(unknown)}")
-    return capi.default_itemcf_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
+def _fields(struct):
+    """the keywords a cfg struct takes: its fields but the padding"""
+    return {name for name, _ in struct._fields_} - {"reserved"}
 
 
-def make_recall_cfg(**kw) -> capi.RecallCfg:
-    """goctr_recall_cfg from keywords; ``exclude`` may be given by name ("keep", "all", "before")"""
-    unknown = set(kw) - _RECALL_FIELDS
-    if unknown:
-        raise TypeError(f"goctr_recall_cfg has no field {sorted(unknown)}")
-    if isinstance(kw.get("exclude"), str):
-        if kw["exclude"] not in EXCLUDE:
-            raise ValueError(f"exclude = {kw['exclude']!r} is none of {sorted(EXCLUDE)}")
-        kw["exclude"] = EXCLUDE[kw["exclude"]]
-    return capi.default_recall_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
-
-
-def make_nbr_cfg(**kw) -> capi.ItemnbrCfg:
-    """goctr_itemnbr_cfg from keywords (integers; the ranges are the library's to refuse)"""
-    unknown = set(kw) - _NBR_FIELDS
-    if unknown:
-        raise TypeError(f"goctr_itemnbr_cfg has no field {sorted(unknown)}")
-    return capi.default_itemnbr_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
-
-
-def make_swing_cfg(**kw) -> capi.SwingCfg:
-    """goctr_swing_cfg from keywords (integers; the ranges are the library's to refuse)"""
-    unknown = set(kw) - _SWING_FIELDS
-    if unknown:
-        raise TypeError(f"goctr_swing_cfg has no field {sorted(unknown)}")
-    return capi.default_swing_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
-
-
-def make_mmr_cfg(**kw) -> capi.MmrCfg:
-    """goctr_mmr_cfg from keywords (integers; the ranges are the library's to refuse)"""
-    unknown = set(kw) - _MMR_FIELDS
-    if unknown:
-        raise TypeError(f"goctr_mmr_cfg has no field {sorted(unknown)}")
-    return capi.default_mmr_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
-
-
-def make_uservec_cfg(**kw) -> capi.UservecCfg:
-    """goctr_uservec_cfg from keywords (integers; the ranges are the library's to refuse)"""
-    unknown = set(kw) - _USERVEC_FIELDS
-    if unknown:
-        raise TypeError(f"goctr_uservec_cfg has no field {sorted(unknown)}")
-    return capi.default_uservec_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
-
-
-def make_uservec_multi_cfg(**kw) -> capi.UservecMultiCfg:
-    """goctr_uservec_multi_cfg from keywords (integers; ``mix`` also "max" / "quota"; the ranges are the library's to refuse)"""
-    unknown = set(kw) - _USERVEC_MULTI_FIELDS
-    if unknown:
-        raise TypeError(f"goctr_uservec_multi_cfg has no field {sorted(unknown)}")
-    if isinstance(kw.get("mix"), str):
-        kw["mix"] = MIX[kw["mix"]]
-    return capi.default_uservec_multi_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
-
-
-def make_ivf_cfg(**kw) -> capi.IvfCfg:
-    """goctr_ivf_cfg from keywords (integers; the ranges are the library's to refuse)"""
-    unknown = set(kw) - _IVF_FIELDS
-    if unknown:
-        raise TypeError(f"goctr_ivf_cfg has no field {sorted(unknown)}")
-    return capi.default_ivf_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
-
-
-def make_uservec_ivf_cfg(**kw) -> capi.UservecIvfCfg:
-    """goctr_uservec_ivf_cfg from keywords (integers; the ranges are the library's to refuse)"""
-    unknown = set(kw) - _USERVEC_IVF_FIELDS
-    if unknown:
-        raise TypeError(f"goctr_uservec_ivf_cfg has no field {sorted(unknown)}")
-    return capi.default_uservec_ivf_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
-
-
-def make_list_cfg(**kw) -> capi.ListCfg:
-    """goctr_list_cfg from keywords (integers; the ranges are the library's to refuse)"""
-    unknown = set(kw) - _LIST_FIELDS
-    if unknown:
-        raise TypeError(f"goctr_list_cfg has no field {sorted(unknown)}")
-    return capi.default_list_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
-
-
-def make_popular_cfg(**kw) -> capi.PopularCfg:
-    """goctr_popular_cfg from keywords (integers; the ranges are the library's to refuse)"""
-    unknown = set(kw) - _POPULAR_FIELDS
-    if unknown:
-        raise TypeError(f"goctr_popular_cfg has no field {sorted(unknown)}")
-    return capi.default_popular_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
+_BUILD_FIELDS = _fields(capi.ItemcfCfg)
+_RECALL_FIELDS = _fields(capi.RecallCfg)
+_POPULAR_FIELDS = _fields(capi.PopularCfg)
+_NBR_FIELDS = _fields(capi.ItemnbrCfg)
+_SWING_FIELDS = _fields(capi.SwingCfg)
+_MMR_FIELDS = _fields(capi.MmrCfg)
+_LIST_FIELDS = _fields(capi.ListCfg)
+_USERVEC_FIELDS = _fields(capi.UservecCfg)
+_USERVEC_MULTI_FIELDS = _fields(capi.UservecMultiCfg)
+_IVF_FIELDS = _fields(capi.IvfCfg)
+_USERVEC_IVF_FIELDS = _fields(capi.UservecIvfCfg)
 
 
 def _as_int(name, v):
     if isinstance(v, bool) or int(v) != v:
         raise TypeError(f"{name} = {v!r} is not an integer")
     return int(v)
+
+
+def _make(c_name, fields, default):
+    """a make_*_cfg: the struct ``c_name`` from keywords -- integers, ``exclude`` also by name ("keep", "all", "before"), ``mix``
+    also "max" / "quota"; the ranges are the library's to refuse"""
+    def make(**kw):
+        unknown = set(kw) - fields
+        if unknown:
+            raise TypeError(f"{c_name} has no field {sorted(unknown)}")
+        if isinstance(kw.get("exclude"), str):
+            if kw["exclude"] not in EXCLUDE:
+                raise ValueError(f"exclude = {kw['exclude']!r} is none of {sorted(EXCLUDE)}")
+            kw["exclude"] = EXCLUDE[kw["exclude"]]
+        if isinstance(kw.get("mix"), str):
+            kw["mix"] = MIX[kw["mix"]]
+        return default(**{k: _as_int(k, v) for k, v in kw.items()})
+    return make
+
+
+make_cfg = _make("goctr_itemcf_cfg", _BUILD_FIELDS, capi.default_itemcf_cfg)
+make_recall_cfg = _make("goctr_recall_cfg", _RECALL_FIELDS, capi.default_recall_cfg)
+make_popular_cfg = _make("goctr_popular_cfg", _POPULAR_FIELDS, capi.default_popular_cfg)
+make_nbr_cfg = _make("goctr_itemnbr_cfg", _NBR_FIELDS, capi.default_itemnbr_cfg)
+make_swing_cfg = _make("goctr_swing_cfg", _SWING_FIELDS, capi.default_swing_cfg)
+make_mmr_cfg = _make("goctr_mmr_cfg", _MMR_FIELDS, capi.default_mmr_cfg)
+make_list_cfg = _make("goctr_list_cfg", _LIST_FIELDS, capi.default_list_cfg)
+make_uservec_cfg = _make("goctr_uservec_cfg", _USERVEC_FIELDS, capi.default_uservec_cfg)
+make_uservec_multi_cfg = _make("goctr_uservec_multi_cfg", _USERVEC_MULTI_FIELDS, capi.default_uservec_multi_cfg)
+make_ivf_cfg = _make("goctr_ivf_cfg", _IVF_FIELDS, capi.default_ivf_cfg)
+make_uservec_ivf_cfg = _make("goctr_uservec_ivf_cfg", _USERVEC_IVF_FIELDS, capi.default_uservec_ivf_cfg)
+
+
+def _cfg_or_kw(cfg, kw, make, name="cfg"):
+    """a call's one cfg: the caller's struct, or ``make`` of the caller's keywords"""
+    if cfg is not None and kw:
+        raise TypeError(f"give either {name} or keywords")
+    return cfg if cfg is not None else make(**kw)
+
+
+def _split_kw(recall_cfg, second_cfg, kw, fields, make):
+    """a call's two cfgs from structs or keywords: (goctr_recall_cfg, the struct ``make`` builds, whose keywords are ``fields``)"""
+    skw = {k: kw.pop(k) for k in list(kw) if k in fields}
+    if (recall_cfg is not None and kw) or (second_cfg is not None and skw):
+        raise TypeError("give either a cfg or its keywords")
+    return (recall_cfg if recall_cfg is not None else make_recall_cfg(**kw)), (second_cfg if second_cfg is not None else make(**skw))
 
 
 def request_columns(users, ts, targets):
@@ -161,18 +119,76 @@ def request_columns(users, ts, targets):
     return users, ts, targets
 
 
-class ItemCF:
+def _request_args(users, ts):
+    """const int32_t* users, const int64_t* ts, int64_t n_req"""
+    return capi.ptr(users, C.c_int32), capi.ptr(ts, C.c_int64), C.c_int64(users.size)
+
+
+# what an output array holds before the call: a value no call writes, so that an entry the device skipped shows
+_UNWRITTEN = {np.int8: -2, np.int16: -2, np.int32: -2, np.int64: -2, np.uint8: 254, np.uint32: 0xffffffff,
+              np.uint64: 0xffffffffffffffff, np.float32: np.nan}
+
+
+def _unwritten(shape, dtype):
+    return np.full(shape, _UNWRITTEN[dtype], dtype)
+
+
+def _ptr(a):
+    """an output array (or None) as the pointer to its own element type"""
+    return None if a is None else a.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(a.dtype)))
+
+
+def _recall_buffers(nq, n_cand, targets, src=False, p_shape=None):
+    """the arrays every recall-only call returns: items, w, count; src for the blend; target_pos when targets are given; with
+    ``p_shape`` (the call validates) p of that shape and s, one per vector"""
+    nc = max(int(n_cand), 1)
+    out = dict(items=_unwritten((nq, nc), np.int32), w=_unwritten((nq, nc), np.uint32), count=_unwritten(nq, np.int32))
+    if src:
+        out["src"] = _unwritten((nq, nc), np.uint8)
+    if targets is not None:
+        out["target_pos"] = _unwritten(nq, np.int32)
+    if p_shape is not None:
+        out["p"], out["s"] = _unwritten(p_shape, np.int16), _unwritten(p_shape[:-1], np.uint64)
+    return out
+
+
+def _recall_args(out, targets):
+    """out_items, out_w, [out_src,] out_count, targets, out_target_pos: how every recall-only entry declares them"""
+    return (_ptr(out["items"]), _ptr(out["w"]), *([_ptr(out["src"])] if "src" in out else []), _ptr(out["count"]),
+            capi.ptr(targets, C.c_int32), _ptr(out.get("target_pos")))
+
+
+def _cache_handle(ubc):
+    """a ubcache.UserBehaviorCache (its device image is read), a raw goctr_ubcache handle, or None"""
+    return ubc.device() if hasattr(ubc, "device") else ubc
+
+
+class _Handle:
+    """a library object this one owns: ``_h``, destroyed once by the symbol ``_destroy``"""
+    _destroy = None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(capi.load(), self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ItemCF(_Handle):
     """goctr_itemcf: neighbour lists resident in HBM, immutable after the build and independent of the cache"""
+    _destroy = "goctr_itemcf_destroy"
 
     def __init__(self, ubc, n_items: int, cfg: capi.ItemcfCfg | None = None, **kw):
         """ubc: a ubcache.UserBehaviorCache (its device image is read) or a raw goctr_ubcache handle"""
-        if cfg is not None and kw:
-            raise TypeError("give either cfg or keywords")
-        cfg = cfg if cfg is not None else make_cfg(**kw)
+        cfg = _cfg_or_kw(cfg, kw, make_cfg)
         self.n_items = int(n_items)
         self._h = C.c_void_p()
-        h = ubc.device() if hasattr(ubc, "device") else ubc
-        capi.check(capi.load().goctr_itemcf_build(h, C.c_int64(self.n_items), C.byref(cfg), C.byref(self._h)))
+        capi.check(capi.load().goctr_itemcf_build(_cache_handle(ubc), C.c_int64(self.n_items), C.byref(cfg), C.byref(self._h)))
         self.n_nbr = self.info()["n_nbr"]
 
     @classmethod
@@ -187,9 +203,7 @@ class ItemCF:
     def from_vectors(cls, rows, cfg: capi.ItemnbrCfg | None = None, **kw) -> "ItemCF":
         """goctr_itemcf_build_vectors: neighbour lists from item vectors (``rows`` [n_items, D], taken as float64) by quantised
         cosine; ``kw``: goctr_itemnbr_cfg fields.  Every method works on the result as on a co-occurrence build"""
-        if cfg is not None and kw:
-            raise TypeError("give either cfg or keywords")
-        cfg = cfg if cfg is not None else make_nbr_cfg(**kw)
+        cfg = _cfg_or_kw(cfg, kw, make_nbr_cfg)
         rows = np.ascontiguousarray(rows, np.float64)
         if rows.ndim != 2:
             raise ValueError("rows takes one vector per item: [n_items, D]")
@@ -203,9 +217,7 @@ class ItemCF:
     def from_embedding(cls, table, n_items: int, cfg: capi.ItemnbrCfg | None = None, **kw) -> "ItemCF":
         """goctr_itemcf_build_emb: the same over rows 0 .. n_items - 1 of an embedding table resident in HBM (a model.EmbeddingTable
         or a raw goctr_emb handle), read as a serving pass reads them"""
-        if cfg is not None and kw:
-            raise TypeError("give either cfg or keywords")
-        cfg = cfg if cfg is not None else make_nbr_cfg(**kw)
+        cfg = _cfg_or_kw(cfg, kw, make_nbr_cfg)
         h = C.c_void_p()
         e = table._h if hasattr(table, "_h") else table
         capi.check(capi.load().goctr_itemcf_build_emb(e, C.c_int64(_as_int("n_items", n_items)), C.byref(cfg), C.byref(h)))
@@ -216,12 +228,10 @@ class ItemCF:
         """goctr_itemcf_build_swing: neighbour lists from user-pair overlap (Swing) over ``ubc``'s device image (a
         ubcache.UserBehaviorCache or a raw goctr_ubcache handle); ``kw``: goctr_swing_cfg fields.  Every method works on the result
         as on a co-occurrence build; nbr_co holds np, the user pairs that voted"""
-        if cfg is not None and kw:
-            raise TypeError("give either cfg or keywords")
-        cfg = cfg if cfg is not None else make_swing_cfg(**kw)
+        cfg = _cfg_or_kw(cfg, kw, make_swing_cfg)
         h = C.c_void_p()
-        c = ubc.device() if hasattr(ubc, "device") else ubc
-        capi.check(capi.load().goctr_itemcf_build_swing(c, C.c_int64(_as_int("n_items", n_items)), C.byref(cfg), C.byref(h)))
+        capi.check(capi.load().goctr_itemcf_build_swing(_cache_handle(ubc), C.c_int64(_as_int("n_items", n_items)), C.byref(cfg),
+                                                        C.byref(h)))
         return cls._adopt(h)
 
     def info(self) -> dict:
@@ -241,32 +251,12 @@ class ItemCF:
     def recall(self, ubc, users, ts=None, targets=None, cfg: capi.RecallCfg | None = None, **kw) -> dict:
         """goctr_itemcf_recall over DENSE user rows of ``ubc``'s image: dict(items int32 [nq, n_cand] (-1 = unused), w uint32
         [nq, n_cand], count int32 [nq], target_pos int32 [nq] when targets are given)"""
-        if cfg is not None and kw:
-            raise TypeError("give either cfg or keywords")
-        cfg = cfg if cfg is not None else make_recall_cfg(**kw)
+        cfg = _cfg_or_kw(cfg, kw, make_recall_cfg)
         users, ts, targets = request_columns(users, ts, targets)
-        nq, nc = users.size, max(int(cfg.n_cand), 1)
-        out = dict(items=np.full((nq, nc), -2, np.int32), w=np.full((nq, nc), 0xffffffff, np.uint32), count=np.full(nq, -2, np.int32))
-        tpos = np.full(nq, -2, np.int32) if targets is not None else None
-        h = ubc.device() if hasattr(ubc, "device") else ubc
-        capi.check(capi.load().goctr_itemcf_recall(self._h, h, capi.ptr(users, C.c_int32), capi.ptr(ts, C.c_int64), C.c_int64(nq),
-                                                   C.byref(cfg), capi.ptr(out["items"], C.c_int32), capi.ptr(out["w"], C.c_uint32),
-                                                   capi.ptr(out["count"], C.c_int32), capi.ptr(targets, C.c_int32),
-                                                   capi.ptr(tpos, C.c_int32)))
-        if tpos is not None:
-            out["target_pos"] = tpos
+        out = _recall_buffers(users.size, cfg.n_cand, targets)
+        capi.check(capi.load().goctr_itemcf_recall(self._h, _cache_handle(ubc), *_request_args(users, ts), C.byref(cfg),
+                                                   *_recall_args(out, targets)))
         return out
-
-    def close(self):
-        if getattr(self, "_h", None):
-            capi.load().goctr_itemcf_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def merge(a: ItemCF, b: ItemCF, mul_a=128, mul_b=128, n_nbr=64) -> ItemCF:
@@ -278,19 +268,17 @@ def merge(a: ItemCF, b: ItemCF, mul_a=128, mul_b=128, n_nbr=64) -> ItemCF:
     return ItemCF._adopt(h)
 
 
-class Popular:
+class Popular(_Handle):
     """goctr_popular: per-item counts, decayed scores and the popularity list, resident in HBM, immutable after the build and
     independent of the cache"""
+    _destroy = "goctr_popular_destroy"
 
     def __init__(self, ubc, n_items: int, cfg: capi.PopularCfg | None = None, **kw):
         """ubc: a ubcache.UserBehaviorCache (its device image is read) or a raw goctr_ubcache handle"""
-        if cfg is not None and kw:
-            raise TypeError("give either cfg or keywords")
-        cfg = cfg if cfg is not None else make_popular_cfg(**kw)
+        cfg = _cfg_or_kw(cfg, kw, make_popular_cfg)
         self.n_items = int(n_items)
         self._h = C.c_void_p()
-        h = ubc.device() if hasattr(ubc, "device") else ubc
-        capi.check(capi.load().goctr_popular_build(h, C.c_int64(self.n_items), C.byref(cfg), C.byref(self._h)))
+        capi.check(capi.load().goctr_popular_build(_cache_handle(ubc), C.c_int64(self.n_items), C.byref(cfg), C.byref(self._h)))
         self.n_list = self.info()["n_list"]
 
     def info(self) -> dict:
@@ -307,17 +295,6 @@ class Popular:
                                                     capi.ptr(out["list_items"], C.c_int32), capi.ptr(out["list_score"], C.c_uint64)))
         return out
 
-    def close(self):
-        if getattr(self, "_h", None):
-            capi.load().goctr_popular_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def extra_columns(extra, nq):
     """the caller's candidate lists as the C-ABI takes them: (int32 [nq, n_extra] or None, n_extra)"""
@@ -333,23 +310,14 @@ def blend(icf, pop, ubc, users, ts=None, targets=None, extra=None, quota_pop=0, 
     """goctr_blend_recall over DENSE user rows of ``ubc``'s image (``icf``, ``pop`` and ``ubc`` may each be None; ``extra`` int32
     [nq, n_extra] or None): dict(items int32 [nq, n_cand] (-1 = unused), w uint32 [nq, n_cand], src uint8 [nq, n_cand] (0 ItemCF,
     1 extra, 2 popularity, 255 = unused), count int32 [nq], target_pos int32 [nq] when targets are given)"""
-    if cfg is not None and kw:
-        raise TypeError("give either cfg or keywords")
-    cfg = cfg if cfg is not None else make_recall_cfg(**kw)
+    cfg = _cfg_or_kw(cfg, kw, make_recall_cfg)
     users, ts, targets = request_columns(users, ts, targets)
-    nq, nc = users.size, max(int(cfg.n_cand), 1)
-    extra, n_extra = extra_columns(extra, nq)
-    out = dict(items=np.full((nq, nc), -2, np.int32), w=np.full((nq, nc), 0xffffffff, np.uint32), src=np.full((nq, nc), 254, np.uint8),
-               count=np.full(nq, -2, np.int32))
-    tpos = np.full(nq, -2, np.int32) if targets is not None else None
-    h = None if ubc is None else ubc.device() if hasattr(ubc, "device") else ubc
+    extra, n_extra = extra_columns(extra, users.size)
+    out = _recall_buffers(users.size, cfg.n_cand, targets, src=True)
     capi.check(capi.load().goctr_blend_recall(
-        icf._h if icf is not None else None, pop._h if pop is not None else None, h, capi.ptr(users, C.c_int32),
-        capi.ptr(ts, C.c_int64), C.c_int64(nq), capi.ptr(extra, C.c_int32), C.c_int32(n_extra), C.byref(cfg),
-        C.c_int32(_as_int("quota_pop", quota_pop)), capi.ptr(out["items"], C.c_int32), capi.ptr(out["w"], C.c_uint32),
-        capi.ptr(out["src"], C.c_uint8), capi.ptr(out["count"], C.c_int32), capi.ptr(targets, C.c_int32), capi.ptr(tpos, C.c_int32)))
-    if tpos is not None:
-        out["target_pos"] = tpos
+        icf._h if icf is not None else None, pop._h if pop is not None else None, _cache_handle(ubc), *_request_args(users, ts),
+        capi.ptr(extra, C.c_int32), C.c_int32(n_extra), C.byref(cfg), C.c_int32(_as_int("quota_pop", quota_pop)),
+        *_recall_args(out, targets)))
     return out
 
 
@@ -362,8 +330,9 @@ def _groups_column(groups, n_items):
     return groups
 
 
-class ItemVectors:
+class ItemVectors(_Handle):
     """goctr_itemvec: the items' quantised vectors (and optional group ids) resident in HBM, immutable after the build"""
+    _destroy = "goctr_itemvec_destroy"
 
     def __init__(self, handle: C.c_void_p):
         self._h = handle
@@ -415,50 +384,25 @@ class ItemVectors:
         catalogue.  ``kw``: goctr_recall_cfg fields and goctr_uservec_cfg's (min_w, chunk_items).  dict(items int32 [nq, n_cand]
         (-1 = unused), w uint32 [nq, n_cand], count int32 [nq], target_pos int32 [nq] when targets are given; with ``validate``
         p int16 [nq, D] (the request vectors) and s uint64 [nq] (the pooled vectors' squared lengths))"""
-        ukw = {k: kw.pop(k) for k in list(kw) if k in _USERVEC_FIELDS}
-        if (cfg is not None and kw) or (ucfg is not None and ukw):
-            raise TypeError("give either a cfg or its keywords")
-        cfg = cfg if cfg is not None else make_recall_cfg(**kw)
-        ucfg = ucfg if ucfg is not None else make_uservec_cfg(**ukw)
+        cfg, ucfg = _split_kw(cfg, ucfg, kw, _USERVEC_FIELDS, make_uservec_cfg)
         users, ts, targets = request_columns(users, ts, targets)
-        nq, nc = users.size, max(int(cfg.n_cand), 1)
-        out = dict(items=np.full((nq, nc), -2, np.int32), w=np.full((nq, nc), 0xffffffff, np.uint32), count=np.full(nq, -2, np.int32))
-        tpos = np.full(nq, -2, np.int32) if targets is not None else None
-        p = np.full((nq, self.D), -2, np.int16) if validate else None
-        s = np.full(nq, 0xffffffffffffffff, np.uint64) if validate else None
-        h = None if ubc is None else ubc.device() if hasattr(ubc, "device") else ubc
-        capi.check(capi.load().goctr_uservec_recall(self._h, h, capi.ptr(users, C.c_int32), capi.ptr(ts, C.c_int64), C.c_int64(nq),
-                                                    C.byref(cfg), C.byref(ucfg), capi.ptr(out["items"], C.c_int32),
-                                                    capi.ptr(out["w"], C.c_uint32), capi.ptr(out["count"], C.c_int32),
-                                                    capi.ptr(targets, C.c_int32), capi.ptr(tpos, C.c_int32), capi.ptr(p, C.c_int16),
-                                                    capi.ptr(s, C.c_uint64)))
-        if tpos is not None:
-            out["target_pos"] = tpos
-        if validate:
-            out["p"], out["s"] = p, s
+        out = _recall_buffers(users.size, cfg.n_cand, targets, p_shape=(users.size, self.D) if validate else None)
+        capi.check(capi.load().goctr_uservec_recall(self._h, _cache_handle(ubc), *_request_args(users, ts), C.byref(cfg), C.byref(ucfg),
+                                                    *_recall_args(out, targets), _ptr(out.get("p")), _ptr(out.get("s"))))
         return out
-
-    def _multi_cfgs(self, cfg, mcfg, kw):
-        mkw = {k: kw.pop(k) for k in list(kw) if k in _USERVEC_MULTI_FIELDS}
-        if (cfg is not None and kw) or (mcfg is not None and mkw):
-            raise TypeError("give either a cfg or its keywords")
-        return (cfg if cfg is not None else make_recall_cfg(**kw)), (mcfg if mcfg is not None else make_uservec_multi_cfg(**mkw))
 
     def interests(self, ubc, users, ts=None, cfg: capi.RecallCfg | None = None, mcfg: capi.UservecMultiCfg | None = None, **kw) -> dict:
         """goctr_uservec_interests over DENSE user rows of ``ubc``'s image: the clustering of every row's history alone.  ``kw``:
         goctr_recall_cfg fields (history is the one read) and goctr_uservec_multi_cfg's.  dict(n_int int32 [nq], assign int8
         [nq, history] (the entry's interest rank, -1 = none), cnt int32 [nq, max_interests], p int16 [nq, max_interests, D],
         s uint64 [nq, max_interests]), interests in rank order"""
-        cfg, mcfg = self._multi_cfgs(cfg, mcfg, kw)
+        cfg, mcfg = _split_kw(cfg, mcfg, kw, _USERVEC_MULTI_FIELDS, make_uservec_multi_cfg)
         users, ts, _ = request_columns(users, ts, None)
         nq, K, H = users.size, max(int(mcfg.max_interests), 1), max(int(cfg.history), 1)
-        out = dict(n_int=np.full(nq, -2, np.int32), assign=np.full((nq, H), -2, np.int8), cnt=np.full((nq, K), -2, np.int32),
-                   p=np.full((nq, K, self.D), -2, np.int16), s=np.full((nq, K), 0xffffffffffffffff, np.uint64))
-        h = None if ubc is None else ubc.device() if hasattr(ubc, "device") else ubc
-        capi.check(capi.load().goctr_uservec_interests(self._h, h, capi.ptr(users, C.c_int32), capi.ptr(ts, C.c_int64), C.c_int64(nq),
-                                                       C.byref(cfg), C.byref(mcfg), capi.ptr(out["n_int"], C.c_int32),
-                                                       capi.ptr(out["assign"], C.c_int8), capi.ptr(out["cnt"], C.c_int32),
-                                                       capi.ptr(out["p"], C.c_int16), capi.ptr(out["s"], C.c_uint64)))
+        out = dict(n_int=_unwritten(nq, np.int32), assign=_unwritten((nq, H), np.int8), cnt=_unwritten((nq, K), np.int32),
+                   p=_unwritten((nq, K, self.D), np.int16), s=_unwritten((nq, K), np.uint64))
+        capi.check(capi.load().goctr_uservec_interests(self._h, _cache_handle(ubc), *_request_args(users, ts), C.byref(cfg), C.byref(mcfg),
+                                                       *(_ptr(out[key]) for key in ("n_int", "assign", "cnt", "p", "s"))))
         return out
 
     def recall_users_multi(self, ubc, users, ts=None, targets=None, cfg: capi.RecallCfg | None = None,
@@ -467,50 +411,28 @@ class ItemVectors:
         vectors, one list each against the whole catalogue, mixed into one.  ``kw``: goctr_recall_cfg fields and
         goctr_uservec_multi_cfg's.  ``recall_users``'s dict plus interest uint8 [nq, n_cand] (the owner's rank, 255 = unused) and
         n_int int32 [nq]; with ``validate`` p is int16 [nq, max_interests, D] and s uint64 [nq, max_interests]"""
-        cfg, mcfg = self._multi_cfgs(cfg, mcfg, kw)
+        cfg, mcfg = _split_kw(cfg, mcfg, kw, _USERVEC_MULTI_FIELDS, make_uservec_multi_cfg)
         users, ts, targets = request_columns(users, ts, targets)
-        nq, nc, K = users.size, max(int(cfg.n_cand), 1), max(int(mcfg.max_interests), 1)
-        out = dict(items=np.full((nq, nc), -2, np.int32), w=np.full((nq, nc), 0xffffffff, np.uint32), count=np.full(nq, -2, np.int32),
-                   interest=np.full((nq, nc), 254, np.uint8), n_int=np.full(nq, -2, np.int32))
-        tpos = np.full(nq, -2, np.int32) if targets is not None else None
-        p = np.full((nq, K, self.D), -2, np.int16) if validate else None
-        s = np.full((nq, K), 0xffffffffffffffff, np.uint64) if validate else None
-        h = None if ubc is None else ubc.device() if hasattr(ubc, "device") else ubc
+        nq, K = users.size, max(int(mcfg.max_interests), 1)
+        out = _recall_buffers(nq, cfg.n_cand, targets, p_shape=(nq, K, self.D) if validate else None)
+        out.update(interest=_unwritten(out["items"].shape, np.uint8), n_int=_unwritten(nq, np.int32))
         capi.check(capi.load().goctr_uservec_recall_multi(
-            self._h, h, capi.ptr(users, C.c_int32), capi.ptr(ts, C.c_int64), C.c_int64(nq), C.byref(cfg), C.byref(mcfg),
-            capi.ptr(out["items"], C.c_int32), capi.ptr(out["w"], C.c_uint32), capi.ptr(out["count"], C.c_int32),
-            capi.ptr(targets, C.c_int32), capi.ptr(tpos, C.c_int32), capi.ptr(p, C.c_int16), capi.ptr(s, C.c_uint64),
-            capi.ptr(out["interest"], C.c_uint8), capi.ptr(out["n_int"], C.c_int32)))
-        if tpos is not None:
-            out["target_pos"] = tpos
-        if validate:
-            out["p"], out["s"] = p, s
+            self._h, _cache_handle(ubc), *_request_args(users, ts), C.byref(cfg), C.byref(mcfg), *_recall_args(out, targets),
+            _ptr(out.get("p")), _ptr(out.get("s")), _ptr(out["interest"]), _ptr(out["n_int"])))
         return out
 
     def build_index(self, cfg: capi.IvfCfg | None = None, **kw) -> "VectorIndex":
         """goctr_itemvec_index_build: a k-means inverted file over the valid rows.  ``kw``: goctr_ivf_cfg fields (n_lists, iters,
         train_items, pass_items).  The index is self-contained: it outlives this handle"""
-        if cfg is not None and kw:
-            raise TypeError("give either cfg or keywords")
-        cfg = cfg if cfg is not None else make_ivf_cfg(**kw)
+        cfg = _cfg_or_kw(cfg, kw, make_ivf_cfg)
         h = C.c_void_p()
         capi.check(capi.load().goctr_itemvec_index_build(self._h, C.byref(cfg), C.byref(h)))
         return VectorIndex(h)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            capi.load().goctr_itemvec_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class VectorIndex:
+class VectorIndex(_Handle):
     """goctr_itemvec_index: the valid rows of an ItemVectors clustered into lists, resident in HBM, immutable after the build"""
+    _destroy = "goctr_itemvec_index_destroy"
 
     def __init__(self, handle: C.c_void_p):
         self._h = handle
@@ -539,49 +461,22 @@ class VectorIndex:
         nearest every row's request vector.  ``kw``: goctr_recall_cfg fields and goctr_uservec_ivf_cfg's (min_w, nprobe,
         chunk_items).  That call's dict plus lists int32 [nq, nprobe] (the probed lists in rank order, -1 = unused) and scanned
         int64 [nq] (the items in them)"""
-        ikw = {k: kw.pop(k) for k in list(kw) if k in _USERVEC_IVF_FIELDS}
-        if (cfg is not None and kw) or (icfg is not None and ikw):
-            raise TypeError("give either a cfg or its keywords")
-        cfg = cfg if cfg is not None else make_recall_cfg(**kw)
-        icfg = icfg if icfg is not None else make_uservec_ivf_cfg(**ikw)
+        cfg, icfg = _split_kw(cfg, icfg, kw, _USERVEC_IVF_FIELDS, make_uservec_ivf_cfg)
         users, ts, targets = request_columns(users, ts, targets)
-        nq, nc, npr = users.size, max(int(cfg.n_cand), 1), min(max(int(icfg.nprobe), 1), 1024)
-        out = dict(items=np.full((nq, nc), -2, np.int32), w=np.full((nq, nc), 0xffffffff, np.uint32), count=np.full(nq, -2, np.int32),
-                   lists=np.full((nq, npr), -2, np.int32), scanned=np.full(nq, -2, np.int64))
-        tpos = np.full(nq, -2, np.int32) if targets is not None else None
-        p = np.full((nq, self.D), -2, np.int16) if validate else None
-        s = np.full(nq, 0xffffffffffffffff, np.uint64) if validate else None
-        h = None if ubc is None else ubc.device() if hasattr(ubc, "device") else ubc
+        nq, npr = users.size, min(max(int(icfg.nprobe), 1), 1024)
+        out = _recall_buffers(nq, cfg.n_cand, targets, p_shape=(nq, self.D) if validate else None)
+        out.update(lists=_unwritten((nq, npr), np.int32), scanned=_unwritten(nq, np.int64))
         capi.check(capi.load().goctr_uservec_recall_ivf(
-            self._h, h, capi.ptr(users, C.c_int32), capi.ptr(ts, C.c_int64), C.c_int64(nq), C.byref(cfg), C.byref(icfg),
-            capi.ptr(out["items"], C.c_int32), capi.ptr(out["w"], C.c_uint32), capi.ptr(out["count"], C.c_int32),
-            capi.ptr(targets, C.c_int32), capi.ptr(tpos, C.c_int32), capi.ptr(p, C.c_int16), capi.ptr(s, C.c_uint64),
-            capi.ptr(out["lists"], C.c_int32), capi.ptr(out["scanned"], C.c_int64)))
-        if tpos is not None:
-            out["target_pos"] = tpos
-        if validate:
-            out["p"], out["s"] = p, s
+            self._h, _cache_handle(ubc), *_request_args(users, ts), C.byref(cfg), C.byref(icfg), *_recall_args(out, targets),
+            _ptr(out.get("p")), _ptr(out.get("s")), _ptr(out["lists"]), _ptr(out["scanned"])))
         return out
-
-    def close(self):
-        if getattr(self, "_h", None):
-            capi.load().goctr_itemvec_index_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def rerank_mmr(vectors: ItemVectors, items, scores, count=None, cfg: capi.MmrCfg | None = None, **kw) -> dict:
     """goctr_rerank_mmr over host arrays: ``items`` int32 [nq, n_cand], ``scores`` float32 [nq, n_cand], ``count`` int32 [nq] (None:
     every row is full); ``kw``: goctr_mmr_cfg fields.  dict(pos int32 [nq, k] (the selected candidates' places, -1 = unused), obj
     int32 [nq, k], pen uint32 [nq, k], count int32 [nq], n_failed)"""
-    if cfg is not None and kw:
-        raise TypeError("give either cfg or keywords")
-    cfg = cfg if cfg is not None else make_mmr_cfg(**kw)
+    cfg = _cfg_or_kw(cfg, kw, make_mmr_cfg)
     items, scores = capi.i32(items), capi.f32(scores)
     if items.ndim != 2 or items.shape != scores.shape or items.size == 0:
         raise ValueError("items and scores take one row of candidates per request row: [nq, n_cand]")
@@ -590,12 +485,11 @@ def rerank_mmr(vectors: ItemVectors, items, scores, count=None, cfg: capi.MmrCfg
     if count.size != nq:
         raise ValueError("count takes one entry per request row")
     kk = max(int(cfg.k), 1)
-    out = dict(pos=np.full((nq, kk), -2, np.int32), obj=np.full((nq, kk), -2, np.int32), pen=np.full((nq, kk), 0xffffffff, np.uint32),
-               count=np.full(nq, -2, np.int32))
+    out = dict(pos=_unwritten((nq, kk), np.int32), obj=_unwritten((nq, kk), np.int32), pen=_unwritten((nq, kk), np.uint32),
+               count=_unwritten(nq, np.int32))
     nf = C.c_int64(-2)
     capi.check(capi.load().goctr_rerank_mmr(vectors._h, capi.ptr(items, C.c_int32), capi.ptr(scores, C.c_float), capi.ptr(count, C.c_int32),
-                                            C.c_int64(nq), C.c_int32(nc), C.byref(cfg), capi.ptr(out["pos"], C.c_int32),
-                                            capi.ptr(out["obj"], C.c_int32), capi.ptr(out["pen"], C.c_uint32),
-                                            capi.ptr(out["count"], C.c_int32), C.byref(nf)))
+                                            C.c_int64(nq), C.c_int32(nc), C.byref(cfg), _ptr(out["pos"]), _ptr(out["obj"]),
+                                            _ptr(out["pen"]), _ptr(out["count"]), C.byref(nf)))
     out["n_failed"] = nf.value
     return out

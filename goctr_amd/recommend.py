@@ -19,13 +19,17 @@ goctr_batch_predict / goctr_rank for serving.  All arithmetic is behind include/
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import time
 from dataclasses import dataclass, field
 
 import numpy as np
 
-from . import capi
+from . import capi, metrics, sampling
+from .recall import (EXCLUDE, _USERVEC_FIELDS, _USERVEC_IVF_FIELDS, _USERVEC_MULTI_FIELDS, ItemCF, ItemVectors, Popular, _as_int,
+                     _cfg_or_kw, _ptr, _request_args, _split_kw, _unwritten, extra_columns, make_mmr_cfg, make_recall_cfg,
+                     make_uservec_cfg, make_uservec_ivf_cfg, make_uservec_multi_cfg, merge, request_columns)
 
 # recommend/rcmd.go:19-28
 SampleAssembler = 16
@@ -352,6 +356,21 @@ def TrainChain(user_features, item_features, ubcache, samples, net, itemEmbeddin
     return pred, costs
 
 
+def _dense_cache(recSys, what):
+    """the recSys's own behaviour cache over dense item rows, or the error of a recSys that has none"""
+    if recSys.ubcache is None:
+        raise RuntimeError(f"this recSys has no behaviour cache to {what} (it does not implement UserBehavior, rcmd.go:512)")
+    return recSys._dense_cache
+
+
+def _samples(recSys, what, cfg):
+    """sampling.Samples over the recSys's own cache and the rows of its item feature table; a draw without a row is an error"""
+    smp = sampling.Samples(_dense_cache(recSys, what), recSys.item_table.shape[0], **cfg)
+    if smp.rows == 0:
+        raise SampleVectorError("the behaviour cache holds no entry that qualifies as a positive")
+    return smp
+
+
 def SampleFromBehavior(recSys: DeviceRecSys, **cfg):
     """EXTENSION (the reference leaves SampleGenerator to the user): labelled samples drawn on the device from the recSys's own
     behaviour cache -- every selected entry a positive with the history strictly before it, followed by sampled items the
@@ -359,12 +378,7 @@ def SampleFromBehavior(recSys: DeviceRecSys, **cfg):
     Items are drawn among the rows of the item feature table.  Returns (model.Dataset, SampleInfo, Samples); no key and
     no label passes through the host."""
     from . import model as gm
-    from .sampling import Samples
-    if recSys.ubcache is None:
-        raise RuntimeError("this recSys has no behaviour cache to sample from (it does not implement UserBehavior, rcmd.go:512)")
-    smp = Samples(recSys._dense_cache, recSys.item_table.shape[0], **cfg)
-    if smp.rows == 0:
-        raise SampleVectorError("the behaviour cache holds no entry that qualifies as a positive")
+    smp = _samples(recSys, "sample from", cfg)
     ds = gm.Dataset.samples(recSys._dense_cache, recSys.user_table, recSys.item_table, smp, recSys.T)
     return ds, SampleInfo.from_dims(recSys.U, recSys.T, recSys.D, recSys.C), smp
 
@@ -433,14 +447,12 @@ def Rank(model: Predictor, userId: int, itemIds, now=None):
     return [ItemScore(int(i), float(y[k, 0])) for k, i in enumerate(itemIds)]
 
 
-EXCLUDE = {"keep": capi.TOPN_KEEP_SEEN, "all": capi.TOPN_DROP_ALL_SEEN, "before": capi.TOPN_DROP_SEEN_BEFORE}
-
-
 def topn(model: Predictor, users, ts=None, pool=None, targets=None, k=10, exclude="all", pass_rows=0, validate=False):
     """goctr_recommend_topn over DENSE indices (users [nq], ts [nq] or None, pool [np] or None = every row of the item feature
     table, targets [nq] or None): dict(items [nq, k], scores [nq, k], count [nq], n_failed, target_rank [nq] when targets are
     given, all_scores / all_flags [nq, np] when ``validate``).  What Recommend / RecommendBatch / EvaluateLeaveOneOutFull call."""
     rs = model.recSys
+    # (not request_columns: a call without a request row is the library's to refuse here)
     users = capi.i32(users).ravel()
     nq = users.size
     ts = None if ts is None else np.ascontiguousarray(ts, np.int64).ravel()
@@ -452,127 +464,74 @@ def topn(model: Predictor, users, ts=None, pool=None, targets=None, k=10, exclud
     cfg = capi.default_topn_cfg(k=int(k), exclude=EXCLUDE[exclude] if isinstance(exclude, str) else int(exclude),
                                 pass_rows=int(pass_rows))
     kk = max(int(k), 1)
-    out = dict(items=np.full((nq, kk), -2, np.int32), scores=np.full((nq, kk), np.nan, np.float32), count=np.full(nq, -2, np.int32))
-    rank = np.full(nq, -2, np.int64) if targets is not None else None
-    all_scores = np.full((nq, n_pool), np.nan, np.float32) if validate else None
-    all_flags = np.full((nq, n_pool), 255, np.uint8) if validate else None
+    out = dict(items=_unwritten((nq, kk), np.int32), scores=_unwritten((nq, kk), np.float32), count=_unwritten(nq, np.int32))
+    if targets is not None:
+        out["target_rank"] = _unwritten(nq, np.int64)
+    if validate:
+        out["all_scores"], out["all_flags"] = _unwritten((nq, n_pool), np.float32), np.full((nq, n_pool), 255, np.uint8)
     nf = C.c_int64(-2)
     capi.check(capi.load().goctr_recommend_topn(
-        model.net._h, rs._h, capi.ptr(users, C.c_int32), capi.ptr(ts, C.c_int64), C.c_int64(nq), capi.ptr(pool, C.c_int32),
-        C.c_int64(n_pool), capi.ptr(targets, C.c_int32), C.byref(cfg), capi.ptr(out["items"], C.c_int32),
-        capi.ptr(out["scores"], C.c_float), capi.ptr(out["count"], C.c_int32), capi.ptr(rank, C.c_int64),
-        capi.ptr(all_scores, C.c_float), capi.ptr(all_flags, C.c_uint8), C.byref(nf)))
+        model.net._h, rs._h, *_request_args(users, ts), capi.ptr(pool, C.c_int32), C.c_int64(n_pool), capi.ptr(targets, C.c_int32),
+        C.byref(cfg), _ptr(out["items"]), _ptr(out["scores"]), _ptr(out["count"]), _ptr(out.get("target_rank")),
+        _ptr(out.get("all_scores")), _ptr(out.get("all_flags")), C.byref(nf)))
     out["n_failed"] = nf.value
-    if rank is not None:
-        out["target_rank"] = rank
-    if validate:
-        out["all_scores"], out["all_flags"] = all_scores, all_flags
     return out
 
 
-def RecommendBatch(model: Predictor, userIds, n=10, now=None, pool=None, exclude="all"):
-    """Recommend for several users in one device call: [[ItemScore]] in the order of userIds.  ``now``: one timestamp for all,
-    or one per user.  An unknown user raises SampleVectorError like Rank's failing first key."""
-    rs = model.recSys
-    userIds = list(userIds)
-    users = np.array([rs.user_index(u) for u in userIds], np.int32)
-    if users.size == 0:
-        return []
-    if (users < 0).any():
-        bad = userIds[int(np.flatnonzero(users < 0)[0])]
-        raise SampleVectorError(f"get sample vector error: user {bad} has no features")
-    ts = np.broadcast_to(np.asarray(int(time.time()) if now is None else now, np.int64), users.shape)
-    # an id unknown to the item feature table becomes a position that fails (index -1), like Rank's zero row
-    dense_pool = None if pool is None else np.array([rs.item_index(i) for i in pool], np.int32)
-    if dense_pool is not None and dense_pool.size == 0:
-        return [[] for _ in userIds]
-    try:
-        r = topn(model, users, ts, dense_pool, None, n, exclude)
-    except capi.GoctrError as e:
-        raise SampleVectorError(str(e)) from None
-    raw = rs._row_keys
-    return [[ItemScore(int(raw[r["items"][q, j]]), float(r["scores"][q, j])) for j in range(int(r["count"][q]))]
-            for q in range(users.size)]
+# ---- the recall-then-rank entries.  Each ends with the same block of outputs; what an entry adds to it, and where, is this table,
+# written from the declarations in include/goctr.h (tests/test_recommend_binding_host.py holds the header's order against it).
+# A new recall channel is one line here, one wrapper below and one row in that test.
+_RANKED = ("items", "scores", "count", "cand_count", "target_pos", "target_rank", "cand_items", "cand_w", "cand_scores", "n_failed")
+_BLENDED = ("items", "scores", "count", "src", "cand_count", "target_pos", "target_rank", "cand_items", "cand_w", "cand_scores",
+            "cand_src", "n_failed")
+_OUTPUTS = {
+    "goctr_recommend_itemcf": _RANKED,
+    "goctr_recommend_uservec": _RANKED,
+    "goctr_recommend_uservec_ivf": _RANKED,
+    "goctr_recommend_uservec_multi": _RANKED + ("cand_interest", "n_int"),
+    "goctr_recommend_blend": _BLENDED,
+    "goctr_recommend_blend_mmr": _BLENDED + ("obj", "pen", "target_place"),
+    "goctr_recommend_blend_uservec": _BLENDED + ("obj", "pen", "target_place"),
+}
+# key: (dtype, entries per request row -- "k", "n_cand" or one --, what the call must have for the array to exist)
+_COLUMNS = {
+    "items": (np.int32, "k", ()), "scores": (np.float32, "k", ()), "src": (np.uint8, "k", ()), "count": (np.int32, None, ()),
+    "cand_count": (np.int32, None, ()), "n_int": (np.int32, None, ()),
+    "target_pos": (np.int32, None, ("targets",)), "target_rank": (np.int64, None, ("targets",)),
+    "cand_items": (np.int32, "n_cand", ("validate",)), "cand_w": (np.uint32, "n_cand", ("validate",)),
+    "cand_scores": (np.float32, "n_cand", ("validate",)), "cand_src": (np.uint8, "n_cand", ("validate",)),
+    "cand_interest": (np.uint8, "n_cand", ("validate",)),
+    "obj": (np.int32, "k", ("mmr",)), "pen": (np.uint32, "k", ("mmr",)), "target_place": (np.int32, None, ("mmr", "targets")),
+}
 
 
-def Recommend(model: Predictor, userId: int, n=10, now=None, pool=None, exclude="all"):
-    """EXTENSION -- what the endpoint's empty-itemIdList branch (recommend/api.go:115-118, "todo: some default recall
-    algorithm") would call: the ``n`` best items for the user among ``pool`` (item ids; None = every item with a feature row),
-    scored by the model and selected on the device (goctr_recommend_topn), best first, ties by pool position.
-    ``exclude``: "all" leaves out every item of the user's behaviour sequence, "before" those at or before ``now``
-    (TimeSeq.Filter's entries), "keep" none.  Ids are mapped through the DeviceRecSys like Rank's."""
-    return RecommendBatch(model, [userId], n, now, pool, exclude)[0]
-
-
-def EvaluateLeaveOneOutFull(model: Predictor, k=10, sample_kw=None, details=False, pass_rows=0):
-    """EvaluateLeaveOneOut's held-out items -- every user's newest entry, goctr_samples with n_neg = 0, which = newest, whose key
-    timestamp is already ts - 1 -- ranked against the WHOLE catalogue instead of sampled negatives: one goctr_recommend_topn
-    call in DROP_SEEN_BEFORE mode (the items of the history the key sees are left out, the target itself stays in) returns
-    each user's exact integer rank; from those, in float64 on the host,
-        hit_rate = mean(rank < k)    ndcg = mean(1 / log2(rank + 2) if rank < k else 0)    mrr = mean(1 / (rank + 1))
-    over the users that have a rank; users whose rank is -1 (the target is no row of the item table) are left out and counted.
-    Returns dict(users, skipped, k, hit_rate, ndcg, mrr); details=True adds ranks, user and target columns (dense indices).
-    ``pass_rows``: goctr_topn_cfg.pass_rows (0 = full serving passes)."""
-    from .sampling import Samples
-    rs = model.recSys
-    if rs.ubcache is None:
-        raise RuntimeError("this recSys has no behaviour cache to hold items out of (it does not implement UserBehavior, rcmd.go:512)")
-    kw = dict(n_neg=0, which="newest")
-    kw.update(sample_kw or {})
-    smp = Samples(rs._dense_cache, rs.item_table.shape[0], **kw)
-    if smp.rows == 0:
-        raise SampleVectorError("the behaviour cache holds no entry that qualifies as a positive")
-    users, targets, ts, _y = smp.export()
-    r = topn(model, users, ts, None, targets, k, "before", pass_rows)
-    rank = r["target_rank"].astype(np.int64)
-    ok = rank >= 0
-    rk = rank[ok].astype(np.float64)
-    n = int(ok.sum())
-    nan = float("nan")
-    out = dict(users=n, skipped=int((~ok).sum()), k=int(k),
-               hit_rate=float(np.mean(rk < k)) if n else nan,
-               ndcg=float(np.mean(np.where(rk < k, 1.0 / np.log2(rk + 2.0), 0.0))) if n else nan,
-               mrr=float(np.mean(1.0 / (rk + 1.0))) if n else nan)
-    if details:
-        out.update(rank=rank, user_index=users, target_index=targets, ts=ts)
+def _ranked_call(entry, head, nq, k, n_cand, targets, validate, mmr=True):
+    """one recall-then-rank entry: ``head`` (its arguments through pass_rows) followed by ``_OUTPUTS[entry]`` -- every array
+    allocated, filled with what no call writes, and passed, or NULL where the call has not what the array needs.  The dict of the
+    arrays that exist, and n_failed"""
+    width = {"k": max(int(k), 1), "n_cand": max(int(n_cand), 1)}
+    has = dict(targets=targets is not None, validate=bool(validate), mmr=mmr)
+    out, nf, args = {}, C.c_int64(-2), list(head)
+    for key in _OUTPUTS[entry]:
+        if key == "n_failed":
+            args.append(C.byref(nf))
+            continue
+        dtype, per_row, needs = _COLUMNS[key]
+        if all(has[n] for n in needs):
+            out[key] = _unwritten((nq, width[per_row]) if per_row else nq, dtype)
+        args.append(_ptr(out.get(key)))
+    capi.check(getattr(capi.load(), entry)(*args))
+    out["n_failed"] = nf.value
     return out
 
 
-def BuildItemCF(recSys: DeviceRecSys, **cfg):
-    """EXTENSION: the ItemCF neighbour lists (recall.ItemCF; ``cfg``: goctr_itemcf_cfg fields) of the recSys's own behaviour cache
-    over the rows of its item feature table -- what RecommendItemCF recalls from.  The lists are those of the cache's image at
-    THIS call; rebuild them when enough new behaviour has come in."""
-    from .recall import ItemCF
-    if recSys.ubcache is None:
-        raise RuntimeError("this recSys has no behaviour cache to build neighbour lists from (it does not implement UserBehavior, rcmd.go:512)")
-    return ItemCF(recSys._dense_cache, recSys.item_table.shape[0], **cfg)
+def _request_head(model, *recall_handles):
+    """goctr_model* m, goctr_recsys* r and the entry's recall handles (each an object with _h, or None)"""
+    return (model.net._h, model.recSys._h, *(None if h is None else h._h for h in recall_handles))
 
 
-def BuildSwing(recSys: DeviceRecSys, **cfg):
-    """EXTENSION: Swing neighbour lists (recall.ItemCF.swing; ``cfg``: goctr_swing_cfg fields) of the recSys's own behaviour cache
-    over the rows of its item feature table: item similarity from user-pair overlap, which a pair that many heavy users touched by
-    accident does not win.  Every RecommendItemCF / RecommendBlend / MergeItemCF call takes the handle like BuildItemCF's.  The
-    lists are those of the cache's image at THIS call."""
-    from .recall import ItemCF
-    if recSys.ubcache is None:
-        raise RuntimeError("this recSys has no behaviour cache to build neighbour lists from (it does not implement UserBehavior, rcmd.go:512)")
-    return ItemCF.swing(recSys._dense_cache, recSys.item_table.shape[0], **cfg)
-
-
-def BuildItemNeighbours(recSys: DeviceRecSys, **cfg):
-    """EXTENSION: neighbour lists from the recSys's item VECTORS (recall.ItemCF.from_embedding; ``cfg``: goctr_itemnbr_cfg fields):
-    the rows of its embedding table in HBM, over the rows of its item feature table -- the n_items BuildItemCF uses, so every
-    RecommendItemCF / RecommendBlend call takes either handle.  An item that never occurs in the behaviour cache has no
-    co-occurrence neighbours; it has these.  The lists are those of the table's rows at THIS call."""
-    from .recall import ItemCF
-    return ItemCF.from_embedding(recSys.emb, recSys.item_table.shape[0], **cfg)
-
-
-def MergeItemCF(a, b, mul_a=128, mul_b=128, n_nbr=64):
-    """EXTENSION: one handle from two (recall.merge), say BuildItemCF's and BuildItemNeighbours's, so that a request recalls from
-    both sources in one call; the weights are mixed as (mul_a * w_a + mul_b * w_b) >> 8 over the stored lists"""
-    from .recall import merge
-    return merge(a, b, mul_a, mul_b, n_nbr)
+def _k_pass(k, pass_rows):
+    return C.c_int32(int(k)), C.c_int64(int(pass_rows))
 
 
 def itemcf(model: Predictor, icf, users, ts=None, targets=None, k=10, pass_rows=0, validate=False, recall_cfg=None, **recall_kw):
@@ -580,110 +539,46 @@ def itemcf(model: Predictor, icf, users, ts=None, targets=None, k=10, pass_rows=
     [nq, k], count [nq], cand_count [nq], n_failed, target_pos / target_rank [nq] when targets are given, cand_items / cand_w /
     cand_scores [nq, n_cand] when ``validate``).  ``recall_kw``: goctr_recall_cfg fields (history, n_cand, exclude -- also by
     name).  What RecommendItemCF / RecommendItemCFBatch / EvaluateLeaveOneOutRecall call."""
-    from .recall import make_recall_cfg, request_columns
-    if recall_cfg is not None and recall_kw:
-        raise TypeError("give either recall_cfg or keywords")
-    cfg = recall_cfg if recall_cfg is not None else make_recall_cfg(**recall_kw)
-    rs = model.recSys
+    cfg = _cfg_or_kw(recall_cfg, recall_kw, make_recall_cfg, "recall_cfg")
     users, ts, targets = request_columns(users, ts, targets)
-    nq, kk, nc = users.size, max(int(k), 1), max(int(cfg.n_cand), 1)
-    out = dict(items=np.full((nq, kk), -2, np.int32), scores=np.full((nq, kk), np.nan, np.float32), count=np.full(nq, -2, np.int32),
-               cand_count=np.full(nq, -2, np.int32))
-    tpos = np.full(nq, -2, np.int32) if targets is not None else None
-    rank = np.full(nq, -2, np.int64) if targets is not None else None
-    cand_items = np.full((nq, nc), -2, np.int32) if validate else None
-    cand_w = np.full((nq, nc), 0xffffffff, np.uint32) if validate else None
-    cand_scores = np.full((nq, nc), np.nan, np.float32) if validate else None
-    nf = C.c_int64(-2)
-    capi.check(capi.load().goctr_recommend_itemcf(
-        model.net._h, rs._h, icf._h, capi.ptr(users, C.c_int32), capi.ptr(ts, C.c_int64), C.c_int64(nq),
-        capi.ptr(targets, C.c_int32), C.byref(cfg), C.c_int32(int(k)), C.c_int64(int(pass_rows)), capi.ptr(out["items"], C.c_int32),
-        capi.ptr(out["scores"], C.c_float), capi.ptr(out["count"], C.c_int32), capi.ptr(out["cand_count"], C.c_int32),
-        capi.ptr(tpos, C.c_int32), capi.ptr(rank, C.c_int64), capi.ptr(cand_items, C.c_int32), capi.ptr(cand_w, C.c_uint32),
-        capi.ptr(cand_scores, C.c_float), C.byref(nf)))
-    out["n_failed"] = nf.value
-    if targets is not None:
-        out["target_pos"], out["target_rank"] = tpos, rank
-    if validate:
-        out["cand_items"], out["cand_w"], out["cand_scores"] = cand_items, cand_w, cand_scores
-    return out
+    head = (*_request_head(model, icf), *_request_args(users, ts), capi.ptr(targets, C.c_int32), C.byref(cfg), *_k_pass(k, pass_rows))
+    return _ranked_call("goctr_recommend_itemcf", head, users.size, k, cfg.n_cand, targets, validate)
 
 
-def RecommendItemCFBatch(model: Predictor, icf, userIds, n=10, now=None, **recall_kw):
-    """RecommendItemCF for several users in one device call: [[ItemScore]] in the order of userIds.  ``now``: one timestamp for
-    all, or one per user.  An unknown user raises SampleVectorError like Rank's failing first key; a user without history gets
-    an empty list (there is no popularity fill: fall back to RecommendBatch, or use RecommendBlendBatch)."""
-    rs = model.recSys
-    userIds = list(userIds)
-    users = np.array([rs.user_index(u) for u in userIds], np.int32)
-    if users.size == 0:
-        return []
-    if (users < 0).any():
-        bad = userIds[int(np.flatnonzero(users < 0)[0])]
-        raise SampleVectorError(f"get sample vector error: user {bad} has no features")
-    ts = np.broadcast_to(np.asarray(int(time.time()) if now is None else now, np.int64), users.shape)
-    try:
-        r = itemcf(model, icf, users, ts, None, n, **recall_kw)
-    except capi.GoctrError as e:
-        raise SampleVectorError(str(e)) from None
-    raw = rs._row_keys
-    return [[ItemScore(int(raw[r["items"][q, j]]), float(r["scores"][q, j])) for j in range(int(r["count"][q]))]
-            for q in range(users.size)]
+def _uservec_call(entry, model, handle, users, ts, targets, k, pass_rows, validate, cfg, second_cfg):
+    """the three user-vector entries: itemcf's arguments with the channel's own cfg after goctr_recall_cfg"""
+    users, ts, targets = request_columns(users, ts, targets)
+    head = (*_request_head(model, handle), *_request_args(users, ts), capi.ptr(targets, C.c_int32), C.byref(cfg), C.byref(second_cfg),
+            *_k_pass(k, pass_rows))
+    return _ranked_call(entry, head, users.size, k, cfg.n_cand, targets, validate)
 
 
-def RecommendItemCF(model: Predictor, icf, userId: int, n=10, now=None, **recall_kw):
-    """EXTENSION -- recall, then rank: the candidates are the ItemCF neighbours (``icf``: BuildItemCF) of the user's newest
-    ``history`` behaviours at or before ``now``, at most ``n_cand`` of them by summed neighbour weight; the model scores those and
-    the ``n`` best come back, best first, ties by the candidate's place in the recalled list.  ``exclude`` as Recommend's.  Unlike
-    Recommend the cost does not grow with the catalogue."""
-    return RecommendItemCFBatch(model, icf, [userId], n, now, **recall_kw)[0]
+def uservec(model: Predictor, vectors, users, ts=None, targets=None, k=10, pass_rows=0, validate=False, recall_cfg=None, ucfg=None,
+            **recall_kw):
+    """goctr_recommend_uservec over DENSE indices: ``itemcf`` with the user-vector recall over ``vectors`` (recall.ItemVectors) as the
+    recall stage; the same dict.  ``recall_kw``: goctr_recall_cfg fields and goctr_uservec_cfg's (min_w, chunk_items).  What
+    RecommendVector / RecommendVectorBatch / EvaluateLeaveOneOutVector call."""
+    cfg, ucfg = _split_kw(recall_cfg, ucfg, recall_kw, _USERVEC_FIELDS, make_uservec_cfg)
+    return _uservec_call("goctr_recommend_uservec", model, vectors, users, ts, targets, k, pass_rows, validate, cfg, ucfg)
 
 
-def EvaluateLeaveOneOutRecall(model: Predictor, icf, k=10, sample_kw=None, details=False, pass_rows=0, **recall_kw):
-    """EvaluateLeaveOneOutFull's protocol over RECALLED candidates: every user's newest entry is held out (key timestamp ts - 1,
-    DROP_SEEN_BEFORE unless ``exclude`` says otherwise), the ItemCF recall proposes ``n_cand`` candidates from the history the key
-    sees and the model ranks them.  In float64 on the host, over the users whose held-out item is a row of the item table,
-        recall = mean(target_pos >= 0)        the recall stage alone: recall@n_cand
-        hit_rate = mean(0 <= rank < k)    ndcg = mean(1 / log2(rank + 2) if 0 <= rank < k else 0)
-    where rank is the target's rank among the recalled candidates (-1: not recalled -- a miss, unlike EvaluateLeaveOneOutFull,
-    where every target has a rank).  ``icf`` should be built without the held-out entries for an honest figure; that is the
-    caller's choice.  Returns dict(users, skipped, k, n_cand, recall, hit_rate, ndcg); details=True adds the columns."""
-    from .recall import make_recall_cfg
-    from .sampling import Samples
-    rs = model.recSys
-    if rs.ubcache is None:
-        raise RuntimeError("this recSys has no behaviour cache to hold items out of (it does not implement UserBehavior, rcmd.go:512)")
-    kw = dict(n_neg=0, which="newest")
-    kw.update(sample_kw or {})
-    smp = Samples(rs._dense_cache, rs.item_table.shape[0], **kw)
-    if smp.rows == 0:
-        raise SampleVectorError("the behaviour cache holds no entry that qualifies as a positive")
-    users, targets, ts, _y = smp.export()
-    recall_kw.setdefault("exclude", "before")
-    cfg = make_recall_cfg(**recall_kw)
-    r = itemcf(model, icf, users, ts, targets, k, pass_rows, recall_cfg=cfg)
-    ok = (targets >= 0) & (targets < rs.item_table.shape[0])
-    pos, rank = r["target_pos"][ok].astype(np.int64), r["target_rank"][ok].astype(np.float64)
-    n = int(ok.sum())
-    hit = (rank >= 0) & (rank < k)
-    nan = float("nan")
-    out = dict(users=n, skipped=int((~ok).sum()), k=int(k), n_cand=int(cfg.n_cand),
-               recall=float(np.mean(pos >= 0)) if n else nan,
-               hit_rate=float(np.mean(hit)) if n else nan,
-               ndcg=float(np.mean(np.where(hit, 1.0 / np.log2(np.where(hit, rank, 0.0) + 2.0), 0.0))) if n else nan)
-    if details:
-        out.update(target_pos=r["target_pos"], rank=r["target_rank"], user_index=users, target_index=targets, ts=ts)
-    return out
+def uservec_ivf(model: Predictor, index, users, ts=None, targets=None, k=10, pass_rows=0, validate=False, recall_cfg=None, icfg=None,
+                **recall_kw):
+    """goctr_recommend_uservec_ivf over DENSE indices: ``uservec`` with the recall over ``index`` (recall.VectorIndex) as the recall
+    stage; the same dict.  ``recall_kw``: goctr_recall_cfg fields and goctr_uservec_ivf_cfg's (min_w, nprobe, chunk_items).  What
+    RecommendVectorIndexed / RecommendVectorIndexedBatch / EvaluateLeaveOneOutVectorIndexed call."""
+    cfg, icfg = _split_kw(recall_cfg, icfg, recall_kw, _USERVEC_IVF_FIELDS, make_uservec_ivf_cfg)
+    return _uservec_call("goctr_recommend_uservec_ivf", model, index, users, ts, targets, k, pass_rows, validate, cfg, icfg)
 
 
-def BuildPopular(recSys: DeviceRecSys, **cfg):
-    """EXTENSION: the popularity list (recall.Popular; ``cfg``: goctr_popular_cfg fields) of the recSys's own behaviour cache over the
-    rows of its item feature table -- the channel RecommendBlend fills a short or empty ItemCF recall from.  The list is that of
-    the cache's image at THIS call; rebuild it when enough new behaviour has come in."""
-    from .recall import Popular
-    if recSys.ubcache is None:
-        raise RuntimeError("this recSys has no behaviour cache to count popularity from (it does not implement UserBehavior, rcmd.go:512)")
-    return Popular(recSys._dense_cache, recSys.item_table.shape[0], **cfg)
+def uservec_multi(model: Predictor, vectors, users, ts=None, targets=None, k=10, pass_rows=0, validate=False, recall_cfg=None,
+                  mcfg=None, **recall_kw):
+    """goctr_recommend_uservec_multi over DENSE indices: ``uservec`` with the multi-interest recall as the recall stage; the same
+    dict plus n_int int32 [nq] and, with ``validate``, cand_interest uint8 [nq, n_cand].  ``recall_kw``: goctr_recall_cfg fields and
+    goctr_uservec_multi_cfg's (min_w, max_interests, iters, split_w, mix, chunk_items).  What RecommendMultiInterest /
+    RecommendMultiInterestBatch / EvaluateLeaveOneOutMultiInterest call."""
+    cfg, mcfg = _split_kw(recall_cfg, mcfg, recall_kw, _USERVEC_MULTI_FIELDS, make_uservec_multi_cfg)
+    return _uservec_call("goctr_recommend_uservec_multi", model, vectors, users, ts, targets, k, pass_rows, validate, cfg, mcfg)
 
 
 def blend(model: Predictor, icf, pop, users, ts=None, targets=None, extra=None, quota_pop=0, k=10, pass_rows=0, validate=False,
@@ -702,79 +597,116 @@ def diverse(model: Predictor, icf, pop, vectors, users, ts=None, targets=None, e
     last step.  blend's dict plus obj int32 [nq, k], pen uint32 [nq, k] and, when targets are given, target_place int32 [nq] (the
     target's index in the returned list, or -1; target_rank stays the model's rank among the eligible candidates).  What
     RecommendDiverse / RecommendDiverseBatch / EvaluateLeaveOneOutDiverse call."""
-    from .recall import make_mmr_cfg
     mmr = (vectors, make_mmr_cfg(k=k, pool=pool, lambda_q=lambda_q, max_per_group=max_per_group))
     return _blend_call(model, icf, pop, users, ts, targets, extra, quota_pop, k, pass_rows, validate, recall_cfg, recall_kw, mmr)
 
 
 def _blend_call(model, icf, pop, users, ts, targets, extra, quota_pop, k, pass_rows, validate, recall_cfg, recall_kw, mmr):
-    """goctr_recommend_blend, or with ``mmr`` = (recall.ItemVectors, capi.MmrCfg) goctr_recommend_blend_mmr: the two differ in the
-    selection arguments and the latter's three further outputs"""
-    from .recall import _as_int, extra_columns, make_recall_cfg, request_columns
-    if recall_cfg is not None and recall_kw:
-        raise TypeError("give either recall_cfg or keywords")
-    cfg = recall_cfg if recall_cfg is not None else make_recall_cfg(**recall_kw)
-    rs = model.recSys
+    """goctr_recommend_blend, or with ``mmr`` = (recall.ItemVectors, capi.MmrCfg) goctr_recommend_blend_mmr: the latter takes the
+    selection's arguments where the former takes k"""
+    cfg = _cfg_or_kw(recall_cfg, recall_kw, make_recall_cfg, "recall_cfg")
     users, ts, targets = request_columns(users, ts, targets)
-    nq, kk, nc = users.size, max(int(k), 1), max(int(cfg.n_cand), 1)
-    extra, n_extra = extra_columns(extra, nq)
-    out = dict(items=np.full((nq, kk), -2, np.int32), scores=np.full((nq, kk), np.nan, np.float32), src=np.full((nq, kk), 254, np.uint8),
-               count=np.full(nq, -2, np.int32), cand_count=np.full(nq, -2, np.int32))
-    tpos = np.full(nq, -2, np.int32) if targets is not None else None
-    rank = np.full(nq, -2, np.int64) if targets is not None else None
-    cand_items = np.full((nq, nc), -2, np.int32) if validate else None
-    cand_w = np.full((nq, nc), 0xffffffff, np.uint32) if validate else None
-    cand_scores = np.full((nq, nc), np.nan, np.float32) if validate else None
-    cand_src = np.full((nq, nc), 254, np.uint8) if validate else None
-    nf = C.c_int64(-2)
-    head = (model.net._h, rs._h, icf._h if icf is not None else None, pop._h if pop is not None else None, capi.ptr(users, C.c_int32),
-            capi.ptr(ts, C.c_int64), C.c_int64(nq), capi.ptr(targets, C.c_int32), capi.ptr(extra, C.c_int32), C.c_int32(n_extra),
-            C.byref(cfg), C.c_int32(_as_int("quota_pop", quota_pop)))
-    outs = (capi.ptr(out["items"], C.c_int32), capi.ptr(out["scores"], C.c_float), capi.ptr(out["count"], C.c_int32),
-            capi.ptr(out["src"], C.c_uint8), capi.ptr(out["cand_count"], C.c_int32), capi.ptr(tpos, C.c_int32), capi.ptr(rank, C.c_int64),
-            capi.ptr(cand_items, C.c_int32), capi.ptr(cand_w, C.c_uint32), capi.ptr(cand_scores, C.c_float), capi.ptr(cand_src, C.c_uint8),
-            C.byref(nf))
+    extra, n_extra = extra_columns(extra, users.size)
+    head = (*_request_head(model, icf, pop), *_request_args(users, ts), capi.ptr(targets, C.c_int32), capi.ptr(extra, C.c_int32),
+            C.c_int32(n_extra), C.byref(cfg), C.c_int32(_as_int("quota_pop", quota_pop)))
     if mmr is None:
-        capi.check(capi.load().goctr_recommend_blend(*head, C.c_int32(int(k)), C.c_int64(int(pass_rows)), *outs))
-    else:
-        vectors, mcfg = mmr
-        out["obj"], out["pen"] = np.full((nq, kk), -2, np.int32), np.full((nq, kk), 0xffffffff, np.uint32)
-        tplace = np.full(nq, -2, np.int32) if targets is not None else None
-        capi.check(capi.load().goctr_recommend_blend_mmr(*head, vectors._h, C.byref(mcfg), C.c_int64(int(pass_rows)), *outs,
-                                                         capi.ptr(out["obj"], C.c_int32), capi.ptr(out["pen"], C.c_uint32),
-                                                         capi.ptr(tplace, C.c_int32)))
-        if targets is not None:
-            out["target_place"] = tplace
-    out["n_failed"] = nf.value
-    if targets is not None:
-        out["target_pos"], out["target_rank"] = tpos, rank
-    if validate:
-        out["cand_items"], out["cand_w"], out["cand_scores"], out["cand_src"] = cand_items, cand_w, cand_scores, cand_src
-    return out
+        return _ranked_call("goctr_recommend_blend", (*head, *_k_pass(k, pass_rows)), users.size, k, cfg.n_cand, targets, validate)
+    vectors, mcfg = mmr
+    return _ranked_call("goctr_recommend_blend_mmr", (*head, vectors._h, C.byref(mcfg), C.c_int64(int(pass_rows))), users.size, k,
+                        cfg.n_cand, targets, validate)
+
+
+def blend_uservec(model: Predictor, icf, pop, uv, users, ts=None, targets=None, n_vec=64, quota_pop=0, k=10, vectors=None, pool=64,
+                  lambda_q=192, max_per_group=0, pass_rows=0, validate=False, recall_cfg=None, ucfg=None, **recall_kw):
+    """goctr_recommend_blend_uservec over DENSE indices: ``blend`` whose part X is the user-vector recall over ``uv``
+    (recall.ItemVectors), ``n_vec`` entries a row, written and read on the device; with ``vectors`` the MMR selection of ``diverse``
+    is the last step (pool, lambda_q, max_per_group).  The dict of ``blend``, or of ``diverse``.  What RecommendBlendVectorBatch
+    and EvaluateLeaveOneOutBlendVector call."""
+    cfg, ucfg = _split_kw(recall_cfg, ucfg, recall_kw, _USERVEC_FIELDS, make_uservec_cfg)
+    users, ts, targets = request_columns(users, ts, targets)
+    mcfg = None if vectors is None else make_mmr_cfg(k=k, pool=pool, lambda_q=lambda_q, max_per_group=max_per_group)
+    head = (*_request_head(model, icf, pop), *_request_args(users, ts), capi.ptr(targets, C.c_int32), uv._h, C.byref(ucfg),
+            C.c_int32(_as_int("n_vec", n_vec)), C.byref(cfg), C.c_int32(_as_int("quota_pop", quota_pop)),
+            vectors._h if vectors is not None else None, C.byref(mcfg) if mcfg is not None else None, *_k_pass(k, pass_rows))
+    return _ranked_call("goctr_recommend_blend_uservec", head, users.size, k, cfg.n_cand, targets, validate, mmr=mcfg is not None)
+
+
+# ---- raw ids in, [[ItemScore]] out: what every Recommend*Batch function does around its device call
+def _request_rows(model, userIds, now):
+    """dense user rows and one timestamp per row for a batch of user ids (an unknown user raises like Rank's failing first key)"""
+    rs = model.recSys
+    userIds = list(userIds)
+    users = np.array([rs.user_index(u) for u in userIds], np.int32)
+    if users.size and (users < 0).any():
+        bad = userIds[int(np.flatnonzero(users < 0)[0])]
+        raise SampleVectorError(f"get sample vector error: user {bad} has no features")
+    ts = np.broadcast_to(np.asarray(int(time.time()) if now is None else now, np.int64), users.shape)
+    return users, ts
+
+
+def _serve(model, nq, call):
+    """[[ItemScore]] of ``call``'s dict over ``nq`` request rows -- raw item ids, ``count`` entries a row; no row, no call; the
+    library's refusal is a SampleVectorError like BatchPredict's"""
+    if nq == 0:
+        return []
+    try:
+        r = call()
+    except capi.GoctrError as e:
+        raise SampleVectorError(str(e)) from None
+    raw = model.recSys._row_keys
+    return [[ItemScore(int(raw[r["items"][q, j]]), float(r["scores"][q, j])) for j in range(int(r["count"][q]))] for q in range(nq)]
+
+
+def _dense_extra(model, extra, nq):
+    """the callers' lists of item ids as dense rows [nq, n_extra]: an id unknown to the item feature table becomes an entry out of
+    range (index -1), which the blend skips"""
+    rs = model.recSys
+    return None if extra is None else np.array([[rs.item_index(i) for i in row] for row in extra], np.int32).reshape(nq, -1)
+
+
+def RecommendBatch(model: Predictor, userIds, n=10, now=None, pool=None, exclude="all"):
+    """Recommend for several users in one device call: [[ItemScore]] in the order of userIds.  ``now``: one timestamp for all,
+    or one per user.  An unknown user raises SampleVectorError like Rank's failing first key."""
+    users, ts = _request_rows(model, userIds, now)
+    # an id unknown to the item feature table becomes a position that fails (index -1), like Rank's zero row
+    dense_pool = None if pool is None else np.array([model.recSys.item_index(i) for i in pool], np.int32)
+    if users.size and dense_pool is not None and dense_pool.size == 0:
+        return [[] for _ in users]
+    return _serve(model, users.size, lambda: topn(model, users, ts, dense_pool, None, n, exclude))
+
+
+def Recommend(model: Predictor, userId: int, n=10, now=None, pool=None, exclude="all"):
+    """EXTENSION -- what the endpoint's empty-itemIdList branch (recommend/api.go:115-118, "todo: some default recall
+    algorithm") would call: the ``n`` best items for the user among ``pool`` (item ids; None = every item with a feature row),
+    scored by the model and selected on the device (goctr_recommend_topn), best first, ties by pool position.
+    ``exclude``: "all" leaves out every item of the user's behaviour sequence, "before" those at or before ``now``
+    (TimeSeq.Filter's entries), "keep" none.  Ids are mapped through the DeviceRecSys like Rank's."""
+    return RecommendBatch(model, [userId], n, now, pool, exclude)[0]
+
+
+def RecommendItemCFBatch(model: Predictor, icf, userIds, n=10, now=None, **recall_kw):
+    """RecommendItemCF for several users in one device call: [[ItemScore]] in the order of userIds.  ``now``: one timestamp for
+    all, or one per user.  An unknown user raises SampleVectorError like Rank's failing first key; a user without history gets
+    an empty list (there is no popularity fill: fall back to RecommendBatch, or use RecommendBlendBatch)."""
+    users, ts = _request_rows(model, userIds, now)
+    return _serve(model, users.size, lambda: itemcf(model, icf, users, ts, None, n, **recall_kw))
+
+
+def RecommendItemCF(model: Predictor, icf, userId: int, n=10, now=None, **recall_kw):
+    """EXTENSION -- recall, then rank: the candidates are the ItemCF neighbours (``icf``: BuildItemCF) of the user's newest
+    ``history`` behaviours at or before ``now``, at most ``n_cand`` of them by summed neighbour weight; the model scores those and
+    the ``n`` best come back, best first, ties by the candidate's place in the recalled list.  ``exclude`` as Recommend's.  Unlike
+    Recommend the cost does not grow with the catalogue."""
+    return RecommendItemCFBatch(model, icf, [userId], n, now, **recall_kw)[0]
 
 
 def RecommendBlendBatch(model: Predictor, icf, pop, userIds, n=10, now=None, extra=None, quota_pop=0, **recall_kw):
     """RecommendBlend for several users in one device call: [[ItemScore]] in the order of userIds.  ``now``: one timestamp for all,
     or one per user; ``extra``: one list of item ids per user (equal lengths), or None.  An unknown user raises SampleVectorError
     like Rank's failing first key; a user without history gets the popularity channel's items, not an empty list."""
-    rs = model.recSys
-    userIds = list(userIds)
-    users = np.array([rs.user_index(u) for u in userIds], np.int32)
-    if users.size == 0:
-        return []
-    if (users < 0).any():
-        bad = userIds[int(np.flatnonzero(users < 0)[0])]
-        raise SampleVectorError(f"get sample vector error: user {bad} has no features")
-    ts = np.broadcast_to(np.asarray(int(time.time()) if now is None else now, np.int64), users.shape)
-    # an id unknown to the item feature table becomes an entry out of range (index -1), which the blend skips
-    dense_extra = None if extra is None else np.array([[rs.item_index(i) for i in row] for row in extra], np.int32).reshape(users.size, -1)
-    try:
-        r = blend(model, icf, pop, users, ts, None, dense_extra, quota_pop, n, **recall_kw)
-    except capi.GoctrError as e:
-        raise SampleVectorError(str(e)) from None
-    raw = rs._row_keys
-    return [[ItemScore(int(raw[r["items"][q, j]]), float(r["scores"][q, j])) for j in range(int(r["count"][q]))]
-            for q in range(users.size)]
+    users, ts = _request_rows(model, userIds, now)
+    return _serve(model, users.size, lambda: blend(model, icf, pop, users, ts, None, _dense_extra(model, extra, users.size), quota_pop, n,
+                                                   **recall_kw))
 
 
 def RecommendBlend(model: Predictor, icf, pop, userId: int, n=10, now=None, extra=None, quota_pop=0, **recall_kw):
@@ -786,83 +718,13 @@ def RecommendBlend(model: Predictor, icf, pop, userId: int, n=10, now=None, extr
     return RecommendBlendBatch(model, icf, pop, [userId], n, now, None if extra is None else [extra], quota_pop, **recall_kw)[0]
 
 
-def EvaluateLeaveOneOutBlend(model: Predictor, icf, pop=None, k=10, sample_kw=None, details=False, pass_rows=0, quota_pop=0,
-                             pop_kw=None, **recall_kw):
-    """EvaluateLeaveOneOutRecall's protocol over the BLENDED candidates (goctr_recommend_blend): every user's newest entry is held
-    out (key timestamp ts - 1, DROP_SEEN_BEFORE unless ``exclude`` says otherwise), the ItemCF recall proposes at most
-    ``n_cand - quota_pop`` candidates from the history the key sees, the popularity list fills the row up to ``n_cand`` and the
-    model ranks the blended list.  ``pop`` None: the popularity list is built here with ``ts_hi`` BELOW the held-out events -- the
-    smallest held-out key timestamp, so no held-out entry (and nothing newer) is counted -- from ``pop_kw`` (goctr_popular_cfg
-    fields); a caller's own ``pop`` is used as it is.  Figures and return value as EvaluateLeaveOneOutRecall's; with
-    ``quota_pop`` = 0 the ItemCF part is a prefix of the blended list, so ``recall`` is never below EvaluateLeaveOneOutRecall's."""
-    from .recall import make_recall_cfg
-    from .sampling import Samples
-    rs = model.recSys
-    if rs.ubcache is None:
-        raise RuntimeError("this recSys has no behaviour cache to hold items out of (it does not implement UserBehavior, rcmd.go:512)")
-    kw = dict(n_neg=0, which="newest")
-    kw.update(sample_kw or {})
-    smp = Samples(rs._dense_cache, rs.item_table.shape[0], **kw)
-    if smp.rows == 0:
-        raise SampleVectorError("the behaviour cache holds no entry that qualifies as a positive")
-    users, targets, ts, _y = smp.export()
-    own = pop is None
-    if own:
-        pkw = dict(pop_kw or {})
-        pkw.setdefault("ts_hi", int(ts.min()))            # the keys carry ts - 1: at or below every held-out event's predecessor
-        pop = BuildPopular(rs, **pkw)
-    recall_kw.setdefault("exclude", "before")
-    cfg = make_recall_cfg(**recall_kw)
-    try:
-        r = blend(model, icf, pop, users, ts, targets, None, quota_pop, k, pass_rows, recall_cfg=cfg)
-    finally:
-        if own:
-            pop.close()
-    ok = (targets >= 0) & (targets < rs.item_table.shape[0])
-    pos, rank = r["target_pos"][ok].astype(np.int64), r["target_rank"][ok].astype(np.float64)
-    n = int(ok.sum())
-    hit = (rank >= 0) & (rank < k)
-    nan = float("nan")
-    out = dict(users=n, skipped=int((~ok).sum()), k=int(k), n_cand=int(cfg.n_cand),
-               recall=float(np.mean(pos >= 0)) if n else nan,
-               hit_rate=float(np.mean(hit)) if n else nan,
-               ndcg=float(np.mean(np.where(hit, 1.0 / np.log2(np.where(hit, rank, 0.0) + 2.0), 0.0))) if n else nan)
-    if details:
-        out.update(target_pos=r["target_pos"], rank=r["target_rank"], src=r["src"], user_index=users, target_index=targets, ts=ts)
-    return out
-
-
-def BuildItemVectors(recSys: DeviceRecSys, groups=None):
-    """EXTENSION: the recSys's item VECTORS, quantised and resident (recall.ItemVectors.from_embedding): the rows of its embedding
-    table in HBM over the rows of its item feature table -- what RecommendDiverse measures similarity with.  ``groups``: one
-    category id per item-table row (negative = none) for ``max_per_group``, or None.  The vectors are those of the table's rows at
-    THIS call."""
-    from .recall import ItemVectors
-    return ItemVectors.from_embedding(recSys.emb, recSys.item_table.shape[0], groups)
-
-
 def RecommendDiverseBatch(model: Predictor, icf, pop, vectors, userIds, n=10, now=None, extra=None, quota_pop=0, lambda_q=192, pool=64,
                           max_per_group=0, **recall_kw):
     """RecommendDiverse for several users in one device call: [[ItemScore]] in the order of userIds, in the order of selection (not
     by score).  Arguments as RecommendBlendBatch's plus the re-rank's."""
-    rs = model.recSys
-    userIds = list(userIds)
-    users = np.array([rs.user_index(u) for u in userIds], np.int32)
-    if users.size == 0:
-        return []
-    if (users < 0).any():
-        bad = userIds[int(np.flatnonzero(users < 0)[0])]
-        raise SampleVectorError(f"get sample vector error: user {bad} has no features")
-    ts = np.broadcast_to(np.asarray(int(time.time()) if now is None else now, np.int64), users.shape)
-    # an id unknown to the item feature table becomes an entry out of range (index -1), which the blend skips
-    dense_extra = None if extra is None else np.array([[rs.item_index(i) for i in row] for row in extra], np.int32).reshape(users.size, -1)
-    try:
-        r = diverse(model, icf, pop, vectors, users, ts, None, dense_extra, quota_pop, n, pool, lambda_q, max_per_group, **recall_kw)
-    except capi.GoctrError as e:
-        raise SampleVectorError(str(e)) from None
-    raw = rs._row_keys
-    return [[ItemScore(int(raw[r["items"][q, j]]), float(r["scores"][q, j])) for j in range(int(r["count"][q]))]
-            for q in range(users.size)]
+    users, ts = _request_rows(model, userIds, now)
+    return _serve(model, users.size, lambda: diverse(model, icf, pop, vectors, users, ts, None, _dense_extra(model, extra, users.size),
+                                                     quota_pop, n, pool, lambda_q, max_per_group, **recall_kw))
 
 
 def RecommendDiverse(model: Predictor, icf, pop, vectors, userId: int, n=10, now=None, extra=None, quota_pop=0, lambda_q=192, pool=64,
@@ -873,6 +735,238 @@ def RecommendDiverse(model: Predictor, icf, pop, vectors, userId: int, n=10, now
     ``max_per_group`` items of one group come back (0 = no cap).  ``lambda_q`` = 256 without a cap is RecommendBlend."""
     return RecommendDiverseBatch(model, icf, pop, vectors, [userId], n, now, None if extra is None else [extra], quota_pop, lambda_q,
                                  pool, max_per_group, **recall_kw)[0]
+
+
+def RecommendVectorBatch(model: Predictor, vectors, userIds, n=10, now=None, **recall_kw):
+    """RecommendVector for several users in one device call: [[ItemScore]] in the order of userIds.  ``now``: one timestamp for all,
+    or one per user.  A user without history (or whose history's vectors cancel) gets an empty list."""
+    users, ts = _request_rows(model, userIds, now)
+    return _serve(model, users.size, lambda: uservec(model, vectors, users, ts, None, n, **recall_kw))
+
+
+def RecommendVector(model: Predictor, vectors, userId: int, n=10, now=None, **recall_kw):
+    """EXTENSION -- user-to-item recall, then rank: the vectors (``vectors``: BuildItemVectors) of the user's newest ``history``
+    behaviours at or before ``now`` are summed into one interest vector, EVERY item of the catalogue is a candidate by its quantised
+    cosine to it (at least ``min_w`` / 65536), the ``n_cand`` closest are scored by the model and the ``n`` best come back.  Unlike
+    RecommendItemCF a candidate need not be in any history item's stored neighbour list; unlike Recommend the model scores n_cand
+    rows, not the catalogue."""
+    return RecommendVectorBatch(model, vectors, [userId], n, now, **recall_kw)[0]
+
+
+def RecommendVectorIndexedBatch(model: Predictor, index, userIds, n=10, now=None, **recall_kw):
+    """RecommendVectorIndexed for several users in one device call: [[ItemScore]] in the order of userIds."""
+    users, ts = _request_rows(model, userIds, now)
+    return _serve(model, users.size, lambda: uservec_ivf(model, index, users, ts, None, n, **recall_kw))
+
+
+def RecommendVectorIndexed(model: Predictor, index, userId: int, n=10, now=None, **recall_kw):
+    """EXTENSION -- RecommendVector over an index (``index``: BuildVectorIndex): the candidates come from the ``nprobe`` lists whose
+    centres lie nearest the user's interest vector, not from the whole catalogue, so a request's cost follows the lists it scans.
+    With ``nprobe`` at or above the number of non-empty lists the result is RecommendVector's."""
+    return RecommendVectorIndexedBatch(model, index, [userId], n, now, **recall_kw)[0]
+
+
+def RecommendMultiInterestBatch(model: Predictor, vectors, userIds, n=10, now=None, **recall_kw):
+    """RecommendMultiInterest for several users in one device call: [[ItemScore]] in the order of userIds.  ``now``: one timestamp
+    for all, or one per user.  A user without history (or whose history's vectors are all invalid) gets an empty list."""
+    users, ts = _request_rows(model, userIds, now)
+    return _serve(model, users.size, lambda: uservec_multi(model, vectors, users, ts, None, n, **recall_kw))
+
+
+def RecommendMultiInterest(model: Predictor, vectors, userId: int, n=10, now=None, **recall_kw):
+    """EXTENSION -- RecommendVector for a user with several tastes: the history's vectors are clustered into up to
+    ``max_interests`` interest vectors (a new one starts where an entry's quantised cosine to every centre so far is below
+    ``split_w`` / 65536), each proposes its closest items of the whole catalogue, and the lists are mixed into ``n_cand``
+    candidates -- by turns in proportion to the interests' sizes (``mix="quota"``, the default) or by the best weight
+    (``mix="max"``) -- before the model scores them and the ``n`` best come back."""
+    return RecommendMultiInterestBatch(model, vectors, [userId], n, now, **recall_kw)[0]
+
+
+def RecommendBlendVectorBatch(model: Predictor, icf, pop, uv, userIds, n=10, now=None, n_vec=64, quota_pop=0, vectors=None, pool=64,
+                              lambda_q=192, max_per_group=0, **recall_kw):
+    """EXTENSION -- RecommendBlendBatch with the user-vector recall as the caller's list: ItemCF's candidates, then the ``n_vec``
+    items closest to the user's pooled history vector (``uv``: BuildItemVectors), then the popularity list; with ``vectors`` the
+    diversity re-rank of RecommendDiverse picks the ``n`` returned.  One device call; the vector channel's list never leaves HBM."""
+    users, ts = _request_rows(model, userIds, now)
+    return _serve(model, users.size, lambda: blend_uservec(model, icf, pop, uv, users, ts, None, n_vec, quota_pop, n, vectors, pool,
+                                                           lambda_q, max_per_group, **recall_kw))
+
+
+# ---- what the recall channels are built from
+def BuildItemCF(recSys: DeviceRecSys, **cfg):
+    """EXTENSION: the ItemCF neighbour lists (recall.ItemCF; ``cfg``: goctr_itemcf_cfg fields) of the recSys's own behaviour cache
+    over the rows of its item feature table -- what RecommendItemCF recalls from.  The lists are those of the cache's image at
+    THIS call; rebuild them when enough new behaviour has come in."""
+    return ItemCF(_dense_cache(recSys, "build neighbour lists from"), recSys.item_table.shape[0], **cfg)
+
+
+def BuildSwing(recSys: DeviceRecSys, **cfg):
+    """EXTENSION: Swing neighbour lists (recall.ItemCF.swing; ``cfg``: goctr_swing_cfg fields) of the recSys's own behaviour cache
+    over the rows of its item feature table: item similarity from user-pair overlap, which a pair that many heavy users touched by
+    accident does not win.  Every RecommendItemCF / RecommendBlend / MergeItemCF call takes the handle like BuildItemCF's.  The
+    lists are those of the cache's image at THIS call."""
+    return ItemCF.swing(_dense_cache(recSys, "build neighbour lists from"), recSys.item_table.shape[0], **cfg)
+
+
+def BuildItemNeighbours(recSys: DeviceRecSys, **cfg):
+    """EXTENSION: neighbour lists from the recSys's item VECTORS (recall.ItemCF.from_embedding; ``cfg``: goctr_itemnbr_cfg fields):
+    the rows of its embedding table in HBM, over the rows of its item feature table -- the n_items BuildItemCF uses, so every
+    RecommendItemCF / RecommendBlend call takes either handle.  An item that never occurs in the behaviour cache has no
+    co-occurrence neighbours; it has these.  The lists are those of the table's rows at THIS call."""
+    return ItemCF.from_embedding(recSys.emb, recSys.item_table.shape[0], **cfg)
+
+
+def MergeItemCF(a, b, mul_a=128, mul_b=128, n_nbr=64):
+    """EXTENSION: one handle from two (recall.merge), say BuildItemCF's and BuildItemNeighbours's, so that a request recalls from
+    both sources in one call; the weights are mixed as (mul_a * w_a + mul_b * w_b) >> 8 over the stored lists"""
+    return merge(a, b, mul_a, mul_b, n_nbr)
+
+
+def BuildPopular(recSys: DeviceRecSys, **cfg):
+    """EXTENSION: the popularity list (recall.Popular; ``cfg``: goctr_popular_cfg fields) of the recSys's own behaviour cache over the
+    rows of its item feature table -- the channel RecommendBlend fills a short or empty ItemCF recall from.  The list is that of
+    the cache's image at THIS call; rebuild it when enough new behaviour has come in."""
+    return Popular(_dense_cache(recSys, "count popularity from"), recSys.item_table.shape[0], **cfg)
+
+
+def BuildItemVectors(recSys: DeviceRecSys, groups=None):
+    """EXTENSION: the recSys's item VECTORS, quantised and resident (recall.ItemVectors.from_embedding): the rows of its embedding
+    table in HBM over the rows of its item feature table -- what RecommendDiverse measures similarity with.  ``groups``: one
+    category id per item-table row (negative = none) for ``max_per_group``, or None.  The vectors are those of the table's rows at
+    THIS call."""
+    return ItemVectors.from_embedding(recSys.emb, recSys.item_table.shape[0], groups)
+
+
+def BuildVectorIndex(vectors, **index_kw):
+    """EXTENSION: an inverted-file index over ``vectors`` (BuildItemVectors): the valid vectors clustered into ``n_lists`` lists by
+    ``iters`` rounds of integer k-means over ``train_items`` of them (recall.ItemVectors.build_index).  The index keeps its own copy
+    of the vectors: ``vectors`` may be closed afterwards."""
+    return vectors.build_index(**index_kw)
+
+
+# ---- the leave-one-out protocol: held-out rows, (the popularity list below them,) one call with targets, figures on the host
+def _held_out_rows(model, sample_kw):
+    """the leave-one-out protocol's request rows: every user's newest entry held out -> (users, targets, ts), dense indices"""
+    kw = dict(n_neg=0, which="newest")
+    kw.update(sample_kw or {})
+    users, targets, ts, _y = _samples(model.recSys, "hold items out of", kw).export()
+    return users, targets, ts
+
+
+@contextlib.contextmanager
+def _popular_below(model, pop, ts, pop_kw):
+    """the caller's ``pop`` as it is, or with None a popularity list built here (``pop_kw``: goctr_popular_cfg fields) with ``ts_hi``
+    BELOW the held-out events -- the smallest held-out key timestamp; the keys carry ts - 1, so no held-out entry and nothing newer
+    is counted -- and closed on the way out"""
+    if pop is not None:
+        yield pop
+        return
+    pkw = dict(pop_kw or {})
+    pkw.setdefault("ts_hi", int(ts.min()))
+    own = BuildPopular(model.recSys, **pkw)
+    try:
+        yield own
+    finally:
+        own.close()
+
+
+def _judged(r, targets, n_items, k, n_cand, at, hit):
+    """the figures every evaluator but the full one returns, over the rows whose held-out item is a row of the item table: ``at`` is
+    each row's 0-based place of the target, ``hit`` whether that place counts"""
+    ok = (targets >= 0) & (targets < n_items)
+    pos, at, hit = r["target_pos"][ok].astype(np.int64), at[ok].astype(np.float64), hit[ok]
+    n = int(ok.sum())
+    nan = float("nan")
+    return dict(users=n, skipped=int((~ok).sum()), k=int(k), n_cand=int(n_cand),
+                recall=float(np.mean(pos >= 0)) if n else nan,
+                hit_rate=float(np.mean(hit)) if n else nan,
+                ndcg=float(np.mean(np.where(hit, 1.0 / np.log2(np.where(hit, at, 0.0) + 2.0), 0.0))) if n else nan)
+
+
+def _loo_figures(r, targets, n_items, k, n_cand):
+    """EvaluateLeaveOneOutRecall's figures from a call's target_pos / target_rank"""
+    rank = r["target_rank"]
+    return _judged(r, targets, n_items, k, n_cand, rank, (rank >= 0) & (rank < k))
+
+
+def _place_figures(r, targets, n_items, k, n_cand):
+    """EvaluateLeaveOneOutDiverse's figures from a call's target_pos / target_place and pen / count"""
+    place = r["target_place"]
+    out = _judged(r, targets, n_items, k, n_cand, place, place >= 0)
+    j = np.arange(r["pen"].shape[1])[None, :]
+    later = (j >= 1) & (j < r["count"][:, None])
+    out["list_similarity"] = float(np.mean(r["pen"][later].astype(np.float64) / 65536.0)) if later.any() else float("nan")
+    return out
+
+
+def _details(r, users, targets, ts, *more):
+    """the columns ``details`` adds: the call's target_pos and target_rank (as rank), the request rows, and ``more`` of the call's"""
+    return dict(target_pos=r["target_pos"], rank=r["target_rank"], user_index=users, target_index=targets, ts=ts,
+                **{key: r[key] for key in more})
+
+
+def EvaluateLeaveOneOutFull(model: Predictor, k=10, sample_kw=None, details=False, pass_rows=0):
+    """EvaluateLeaveOneOut's held-out items -- every user's newest entry, goctr_samples with n_neg = 0, which = newest, whose key
+    timestamp is already ts - 1 -- ranked against the WHOLE catalogue instead of sampled negatives: one goctr_recommend_topn
+    call in DROP_SEEN_BEFORE mode (the items of the history the key sees are left out, the target itself stays in) returns
+    each user's exact integer rank; from those, in float64 on the host,
+        hit_rate = mean(rank < k)    ndcg = mean(1 / log2(rank + 2) if rank < k else 0)    mrr = mean(1 / (rank + 1))
+    over the users that have a rank; users whose rank is -1 (the target is no row of the item table) are left out and counted.
+    Returns dict(users, skipped, k, hit_rate, ndcg, mrr); details=True adds ranks, user and target columns (dense indices).
+    ``pass_rows``: goctr_topn_cfg.pass_rows (0 = full serving passes)."""
+    users, targets, ts = _held_out_rows(model, sample_kw)
+    r = topn(model, users, ts, None, targets, k, "before", pass_rows)
+    rank = r["target_rank"].astype(np.int64)
+    ok = rank >= 0
+    rk = rank[ok].astype(np.float64)
+    n = int(ok.sum())
+    nan = float("nan")
+    out = dict(users=n, skipped=int((~ok).sum()), k=int(k),
+               hit_rate=float(np.mean(rk < k)) if n else nan,
+               ndcg=float(np.mean(np.where(rk < k, 1.0 / np.log2(rk + 2.0), 0.0))) if n else nan,
+               mrr=float(np.mean(1.0 / (rk + 1.0))) if n else nan)
+    if details:
+        out.update(rank=rank, user_index=users, target_index=targets, ts=ts)
+    return out
+
+
+def EvaluateLeaveOneOutRecall(model: Predictor, icf, k=10, sample_kw=None, details=False, pass_rows=0, **recall_kw):
+    """EvaluateLeaveOneOutFull's protocol over RECALLED candidates: every user's newest entry is held out (key timestamp ts - 1,
+    DROP_SEEN_BEFORE unless ``exclude`` says otherwise), the ItemCF recall proposes ``n_cand`` candidates from the history the key
+    sees and the model ranks them.  In float64 on the host, over the users whose held-out item is a row of the item table,
+        recall = mean(target_pos >= 0)        the recall stage alone: recall@n_cand
+        hit_rate = mean(0 <= rank < k)    ndcg = mean(1 / log2(rank + 2) if 0 <= rank < k else 0)
+    where rank is the target's rank among the recalled candidates (-1: not recalled -- a miss, unlike EvaluateLeaveOneOutFull,
+    where every target has a rank).  ``icf`` should be built without the held-out entries for an honest figure; that is the
+    caller's choice.  Returns dict(users, skipped, k, n_cand, recall, hit_rate, ndcg); details=True adds the columns."""
+    users, targets, ts = _held_out_rows(model, sample_kw)
+    recall_kw.setdefault("exclude", "before")
+    cfg = make_recall_cfg(**recall_kw)
+    r = itemcf(model, icf, users, ts, targets, k, pass_rows, recall_cfg=cfg)
+    out = _loo_figures(r, targets, model.recSys.item_table.shape[0], k, cfg.n_cand)
+    if details:
+        out.update(_details(r, users, targets, ts))
+    return out
+
+
+def EvaluateLeaveOneOutBlend(model: Predictor, icf, pop=None, k=10, sample_kw=None, details=False, pass_rows=0, quota_pop=0,
+                             pop_kw=None, **recall_kw):
+    """EvaluateLeaveOneOutRecall's protocol over the BLENDED candidates (goctr_recommend_blend): every user's newest entry is held
+    out (key timestamp ts - 1, DROP_SEEN_BEFORE unless ``exclude`` says otherwise), the ItemCF recall proposes at most
+    ``n_cand - quota_pop`` candidates from the history the key sees, the popularity list fills the row up to ``n_cand`` and the
+    model ranks the blended list.  ``pop`` None: the popularity list is built here with ``ts_hi`` BELOW the held-out events -- the
+    smallest held-out key timestamp, so no held-out entry (and nothing newer) is counted -- from ``pop_kw`` (goctr_popular_cfg
+    fields); a caller's own ``pop`` is used as it is.  Figures and return value as EvaluateLeaveOneOutRecall's; with
+    ``quota_pop`` = 0 the ItemCF part is a prefix of the blended list, so ``recall`` is never below EvaluateLeaveOneOutRecall's."""
+    users, targets, ts = _held_out_rows(model, sample_kw)
+    with _popular_below(model, pop, ts, pop_kw) as pop:
+        recall_kw.setdefault("exclude", "before")
+        cfg = make_recall_cfg(**recall_kw)
+        r = blend(model, icf, pop, users, ts, targets, None, quota_pop, k, pass_rows, recall_cfg=cfg)
+    out = _loo_figures(r, targets, model.recSys.item_table.shape[0], k, cfg.n_cand)
+    if details:
+        out.update(_details(r, users, targets, ts, "src"))
+    return out
 
 
 def EvaluateLeaveOneOutDiverse(model: Predictor, icf, vectors, pop=None, k=10, lambda_q=192, pool=64, max_per_group=0, sample_kw=None,
@@ -886,102 +980,40 @@ def EvaluateLeaveOneOutDiverse(model: Predictor, icf, vectors, pop=None, k=10, l
     the mean over all returned items but every list's first of the largest similarity to an item in front of it (nan when no list
     has two items).  Compare with EvaluateLeaveOneOutBlend's figures for what the diversity costs in accuracy.  Returns dict(users,
     skipped, k, n_cand, recall, hit_rate, ndcg, list_similarity); details=True adds the columns."""
-    from .recall import make_recall_cfg
-    from .sampling import Samples
-    rs = model.recSys
-    if rs.ubcache is None:
-        raise RuntimeError("this recSys has no behaviour cache to hold items out of (it does not implement UserBehavior, rcmd.go:512)")
-    kw = dict(n_neg=0, which="newest")
-    kw.update(sample_kw or {})
-    smp = Samples(rs._dense_cache, rs.item_table.shape[0], **kw)
-    if smp.rows == 0:
-        raise SampleVectorError("the behaviour cache holds no entry that qualifies as a positive")
-    users, targets, ts, _y = smp.export()
-    own = pop is None
-    if own:
-        pkw = dict(pop_kw or {})
-        pkw.setdefault("ts_hi", int(ts.min()))            # as EvaluateLeaveOneOutBlend: nothing at or after a held-out event counts
-        pop = BuildPopular(rs, **pkw)
-    recall_kw.setdefault("exclude", "before")
-    cfg = make_recall_cfg(**recall_kw)
-    try:
+    users, targets, ts = _held_out_rows(model, sample_kw)
+    with _popular_below(model, pop, ts, pop_kw) as pop:
+        recall_kw.setdefault("exclude", "before")
+        cfg = make_recall_cfg(**recall_kw)
         r = diverse(model, icf, pop, vectors, users, ts, targets, None, quota_pop, k, pool, lambda_q, max_per_group, pass_rows,
                     recall_cfg=cfg)
-    finally:
-        if own:
-            pop.close()
-    ok = (targets >= 0) & (targets < rs.item_table.shape[0])
-    pos, place = r["target_pos"][ok].astype(np.int64), r["target_place"][ok].astype(np.float64)
-    n = int(ok.sum())
-    hit = place >= 0
-    later = (np.arange(r["pen"].shape[1])[None, :] >= 1) & (np.arange(r["pen"].shape[1])[None, :] < r["count"][:, None])
-    nan = float("nan")
-    out = dict(users=n, skipped=int((~ok).sum()), k=int(k), n_cand=int(cfg.n_cand),
-               recall=float(np.mean(pos >= 0)) if n else nan,
-               hit_rate=float(np.mean(hit)) if n else nan,
-               ndcg=float(np.mean(np.where(hit, 1.0 / np.log2(np.where(hit, place, 0.0) + 2.0), 0.0))) if n else nan,
-               list_similarity=float(np.mean(r["pen"][later].astype(np.float64) / 65536.0)) if later.any() else nan)
+    out = _place_figures(r, targets, model.recSys.item_table.shape[0], k, cfg.n_cand)
     if details:
-        out.update(target_pos=r["target_pos"], rank=r["target_rank"], target_place=r["target_place"], items=r["items"], pen=r["pen"],
-                   count=r["count"], src=r["src"], user_index=users, target_index=targets, ts=ts)
+        out.update(_details(r, users, targets, ts, "target_place", "items", "pen", "count", "src"))
     return out
-
-
-def _held_out_rows(model, sample_kw):
-    """the leave-one-out protocol's request rows: every user's newest entry held out -> (users, targets, ts), dense indices"""
-    from .sampling import Samples
-    rs = model.recSys
-    if rs.ubcache is None:
-        raise RuntimeError("this recSys has no behaviour cache to hold items out of (it does not implement UserBehavior, rcmd.go:512)")
-    kw = dict(n_neg=0, which="newest")
-    kw.update(sample_kw or {})
-    smp = Samples(rs._dense_cache, rs.item_table.shape[0], **kw)
-    if smp.rows == 0:
-        raise SampleVectorError("the behaviour cache holds no entry that qualifies as a positive")
-    users, targets, ts, _y = smp.export()
-    return users, targets, ts
 
 
 def _list_quality(model, icf, vectors, pop, users, ts, targets, cfg, k, lambda_q, pool, max_per_group, pass_rows, quota_pop, tail_cnt,
                   details):
     """one evaluation over prepared request rows: EvaluateLeaveOneOutBlend's figures (lambda_q = 256 without a cap, through
-    ``blend``) or EvaluateLeaveOneOutDiverse's (anything else, through ``diverse``), each by that function's own expressions, plus
-    metrics.list_metrics over the returned lists"""
-    from .metrics import list_metrics
-    rs = model.recSys
+    ``blend``) or EvaluateLeaveOneOutDiverse's (anything else, through ``diverse``), plus metrics.list_metrics over the returned
+    lists"""
+    n_items = model.recSys.item_table.shape[0]
     plain = int(lambda_q) == 256 and int(max_per_group) == 0
-    ok = (targets >= 0) & (targets < rs.item_table.shape[0])
-    n = int(ok.sum())
-    nan = float("nan")
     if plain:
         r = blend(model, icf, pop, users, ts, targets, None, quota_pop, k, pass_rows, recall_cfg=cfg)
-        pos, rank = r["target_pos"][ok].astype(np.int64), r["target_rank"][ok].astype(np.float64)
-        hit = (rank >= 0) & (rank < k)
-        out = dict(users=n, skipped=int((~ok).sum()), k=int(k), n_cand=int(cfg.n_cand),
-                   recall=float(np.mean(pos >= 0)) if n else nan,
-                   hit_rate=float(np.mean(hit)) if n else nan,
-                   ndcg=float(np.mean(np.where(hit, 1.0 / np.log2(np.where(hit, rank, 0.0) + 2.0), 0.0))) if n else nan)
+        out = _loo_figures(r, targets, n_items, k, cfg.n_cand)
     else:
         r = diverse(model, icf, pop, vectors, users, ts, targets, None, quota_pop, k, pool, lambda_q, max_per_group, pass_rows,
                     recall_cfg=cfg)
-        pos, place = r["target_pos"][ok].astype(np.int64), r["target_place"][ok].astype(np.float64)
-        hit = place >= 0
-        later = (np.arange(r["pen"].shape[1])[None, :] >= 1) & (np.arange(r["pen"].shape[1])[None, :] < r["count"][:, None])
-        out = dict(users=n, skipped=int((~ok).sum()), k=int(k), n_cand=int(cfg.n_cand),
-                   recall=float(np.mean(pos >= 0)) if n else nan,
-                   hit_rate=float(np.mean(hit)) if n else nan,
-                   ndcg=float(np.mean(np.where(hit, 1.0 / np.log2(np.where(hit, place, 0.0) + 2.0), 0.0))) if n else nan,
-                   list_similarity=float(np.mean(r["pen"][later].astype(np.float64) / 65536.0)) if later.any() else nan)
+        out = _place_figures(r, targets, n_items, k, cfg.n_cand)
     out.update(lambda_q=int(lambda_q), pool=int(pool), max_per_group=int(max_per_group))
-    lm = list_metrics(r["items"], r["count"], vectors, pop, rs.item_table.shape[0], tail_cnt, rows=details, expo=details)
+    lm = metrics.list_metrics(r["items"], r["count"], vectors, pop, n_items, tail_cnt, rows=details, expo=details)
     rows, expo = lm.pop("rows", None), lm.pop("expo", None)
     lm.pop("n_req"), lm.pop("n_items")
     out.update(lm)
     if details:
-        out.update(items=r["items"], count=r["count"], src=r["src"], target_pos=r["target_pos"], rank=r["target_rank"],
-                   list_rows=rows, expo=expo, user_index=users, target_index=targets, ts=ts)
-        if not plain:
-            out.update(target_place=r["target_place"], pen=r["pen"])
+        out.update(_details(r, users, targets, ts, "items", "count", "src", *(() if plain else ("target_place", "pen"))),
+                   list_rows=rows, expo=expo)
     return out
 
 
@@ -998,180 +1030,27 @@ def EvaluateListQuality(model: Predictor, icf, vectors, pop=None, k=10, lambda_q
     together with the integers they are quotients of.  ``vectors`` (BuildItemVectors) measures the similarity whatever the path;
     ``pop`` None: built here below the held-out events, as EvaluateLeaveOneOutBlend does.  details=True adds the columns, the
     per-row records (``list_rows``) and the exposure histogram (``expo``)."""
-    from .recall import make_recall_cfg
-    users, targets, ts = _held_out_rows(model, sample_kw)
-    own = pop is None
-    if own:
-        pkw = dict(pop_kw or {})
-        pkw.setdefault("ts_hi", int(ts.min()))            # as EvaluateLeaveOneOutBlend: nothing at or after a held-out event counts
-        pop = BuildPopular(model.recSys, **pkw)
-    recall_kw.setdefault("exclude", "before")
-    cfg = make_recall_cfg(**recall_kw)
-    try:
-        return _list_quality(model, icf, vectors, pop, users, ts, targets, cfg, k, lambda_q, pool, max_per_group, pass_rows, quota_pop,
-                             tail_cnt, details)
-    finally:
-        if own:
-            pop.close()
+    return _quality_sweep(model, icf, vectors, (lambda_q,), pop, k, pool, max_per_group, sample_kw, pass_rows, quota_pop, pop_kw, tail_cnt,
+                          details, recall_kw)[0]
 
 
 def DiversityTradeoff(model: Predictor, icf, vectors, lambdas=(256, 224, 192, 128), pop=None, k=10, pool=64, max_per_group=0,
                       sample_kw=None, pass_rows=0, quota_pop=0, pop_kw=None, tail_cnt=0, **recall_kw):
     """EXTENSION: EvaluateListQuality's figures for every ``lambda_q`` of ``lambdas`` -- one dict per value, in their order -- over
     ONE set of held-out rows and ONE popularity list, so that the rows differ in the re-rank alone"""
-    from .recall import make_recall_cfg
+    return _quality_sweep(model, icf, vectors, lambdas, pop, k, pool, max_per_group, sample_kw, pass_rows, quota_pop, pop_kw, tail_cnt,
+                          False, recall_kw)
+
+
+def _quality_sweep(model, icf, vectors, lambdas, pop, k, pool, max_per_group, sample_kw, pass_rows, quota_pop, pop_kw, tail_cnt, details,
+                   recall_kw):
+    """_list_quality for every ``lambda_q`` of ``lambdas`` over one set of held-out rows and one popularity list"""
     users, targets, ts = _held_out_rows(model, sample_kw)
-    own = pop is None
-    if own:
-        pkw = dict(pop_kw or {})
-        pkw.setdefault("ts_hi", int(ts.min()))
-        pop = BuildPopular(model.recSys, **pkw)
-    recall_kw.setdefault("exclude", "before")
-    cfg = make_recall_cfg(**recall_kw)
-    try:
+    with _popular_below(model, pop, ts, pop_kw) as pop:
+        recall_kw.setdefault("exclude", "before")
+        cfg = make_recall_cfg(**recall_kw)
         return [_list_quality(model, icf, vectors, pop, users, ts, targets, cfg, k, lam, pool, max_per_group, pass_rows, quota_pop,
-                              tail_cnt, False) for lam in lambdas]
-    finally:
-        if own:
-            pop.close()
-
-
-def _split_uservec_kw(recall_cfg, ucfg, kw):
-    """(goctr_recall_cfg, goctr_uservec_cfg) from cfgs or keywords (min_w and chunk_items are the latter's)"""
-    from .recall import _USERVEC_FIELDS, make_recall_cfg, make_uservec_cfg
-    ukw = {k: kw.pop(k) for k in list(kw) if k in _USERVEC_FIELDS}
-    if (recall_cfg is not None and kw) or (ucfg is not None and ukw):
-        raise TypeError("give either a cfg or its keywords")
-    return (recall_cfg if recall_cfg is not None else make_recall_cfg(**kw)), (ucfg if ucfg is not None else make_uservec_cfg(**ukw))
-
-
-def uservec(model: Predictor, vectors, users, ts=None, targets=None, k=10, pass_rows=0, validate=False, recall_cfg=None, ucfg=None,
-            **recall_kw):
-    """goctr_recommend_uservec over DENSE indices: ``itemcf`` with the user-vector recall over ``vectors`` (recall.ItemVectors) as the
-    recall stage; the same dict.  ``recall_kw``: goctr_recall_cfg fields and goctr_uservec_cfg's (min_w, chunk_items).  What
-    RecommendVector / RecommendVectorBatch / EvaluateLeaveOneOutVector call."""
-    from .recall import request_columns
-    cfg, ucfg = _split_uservec_kw(recall_cfg, ucfg, recall_kw)
-    rs = model.recSys
-    users, ts, targets = request_columns(users, ts, targets)
-    nq, kk, nc = users.size, max(int(k), 1), max(int(cfg.n_cand), 1)
-    out = dict(items=np.full((nq, kk), -2, np.int32), scores=np.full((nq, kk), np.nan, np.float32), count=np.full(nq, -2, np.int32),
-               cand_count=np.full(nq, -2, np.int32))
-    tpos = np.full(nq, -2, np.int32) if targets is not None else None
-    rank = np.full(nq, -2, np.int64) if targets is not None else None
-    cand_items = np.full((nq, nc), -2, np.int32) if validate else None
-    cand_w = np.full((nq, nc), 0xffffffff, np.uint32) if validate else None
-    cand_scores = np.full((nq, nc), np.nan, np.float32) if validate else None
-    nf = C.c_int64(-2)
-    capi.check(capi.load().goctr_recommend_uservec(
-        model.net._h, rs._h, vectors._h, capi.ptr(users, C.c_int32), capi.ptr(ts, C.c_int64), C.c_int64(nq),
-        capi.ptr(targets, C.c_int32), C.byref(cfg), C.byref(ucfg), C.c_int32(int(k)), C.c_int64(int(pass_rows)),
-        capi.ptr(out["items"], C.c_int32), capi.ptr(out["scores"], C.c_float), capi.ptr(out["count"], C.c_int32),
-        capi.ptr(out["cand_count"], C.c_int32), capi.ptr(tpos, C.c_int32), capi.ptr(rank, C.c_int64), capi.ptr(cand_items, C.c_int32),
-        capi.ptr(cand_w, C.c_uint32), capi.ptr(cand_scores, C.c_float), C.byref(nf)))
-    out["n_failed"] = nf.value
-    if targets is not None:
-        out["target_pos"], out["target_rank"] = tpos, rank
-    if validate:
-        out["cand_items"], out["cand_w"], out["cand_scores"] = cand_items, cand_w, cand_scores
-    return out
-
-
-def blend_uservec(model: Predictor, icf, pop, uv, users, ts=None, targets=None, n_vec=64, quota_pop=0, k=10, vectors=None, pool=64,
-                  lambda_q=192, max_per_group=0, pass_rows=0, validate=False, recall_cfg=None, ucfg=None, **recall_kw):
-    """goctr_recommend_blend_uservec over DENSE indices: ``blend`` whose part X is the user-vector recall over ``uv``
-    (recall.ItemVectors), ``n_vec`` entries a row, written and read on the device; with ``vectors`` the MMR selection of ``diverse``
-    is the last step (pool, lambda_q, max_per_group).  The dict of ``blend``, or of ``diverse``.  What RecommendBlendVectorBatch
-    and EvaluateLeaveOneOutBlendVector call."""
-    from .recall import _as_int, make_mmr_cfg, request_columns
-    cfg, ucfg = _split_uservec_kw(recall_cfg, ucfg, recall_kw)
-    rs = model.recSys
-    users, ts, targets = request_columns(users, ts, targets)
-    nq, kk, nc = users.size, max(int(k), 1), max(int(cfg.n_cand), 1)
-    mcfg = None if vectors is None else make_mmr_cfg(k=k, pool=pool, lambda_q=lambda_q, max_per_group=max_per_group)
-    out = dict(items=np.full((nq, kk), -2, np.int32), scores=np.full((nq, kk), np.nan, np.float32), src=np.full((nq, kk), 254, np.uint8),
-               count=np.full(nq, -2, np.int32), cand_count=np.full(nq, -2, np.int32))
-    tpos = np.full(nq, -2, np.int32) if targets is not None else None
-    rank = np.full(nq, -2, np.int64) if targets is not None else None
-    cand_items = np.full((nq, nc), -2, np.int32) if validate else None
-    cand_w = np.full((nq, nc), 0xffffffff, np.uint32) if validate else None
-    cand_scores = np.full((nq, nc), np.nan, np.float32) if validate else None
-    cand_src = np.full((nq, nc), 254, np.uint8) if validate else None
-    obj = np.full((nq, kk), -2, np.int32) if mcfg is not None else None
-    pen = np.full((nq, kk), 0xffffffff, np.uint32) if mcfg is not None else None
-    tplace = np.full(nq, -2, np.int32) if mcfg is not None and targets is not None else None
-    nf = C.c_int64(-2)
-    capi.check(capi.load().goctr_recommend_blend_uservec(
-        model.net._h, rs._h, icf._h if icf is not None else None, pop._h if pop is not None else None, capi.ptr(users, C.c_int32),
-        capi.ptr(ts, C.c_int64), C.c_int64(nq), capi.ptr(targets, C.c_int32), uv._h, C.byref(ucfg), C.c_int32(_as_int("n_vec", n_vec)),
-        C.byref(cfg), C.c_int32(_as_int("quota_pop", quota_pop)), vectors._h if vectors is not None else None,
-        C.byref(mcfg) if mcfg is not None else None, C.c_int32(int(k)), C.c_int64(int(pass_rows)),
-        capi.ptr(out["items"], C.c_int32), capi.ptr(out["scores"], C.c_float), capi.ptr(out["count"], C.c_int32),
-        capi.ptr(out["src"], C.c_uint8), capi.ptr(out["cand_count"], C.c_int32), capi.ptr(tpos, C.c_int32), capi.ptr(rank, C.c_int64),
-        capi.ptr(cand_items, C.c_int32), capi.ptr(cand_w, C.c_uint32), capi.ptr(cand_scores, C.c_float), capi.ptr(cand_src, C.c_uint8),
-        C.byref(nf), capi.ptr(obj, C.c_int32), capi.ptr(pen, C.c_uint32), capi.ptr(tplace, C.c_int32)))
-    out["n_failed"] = nf.value
-    if mcfg is not None:
-        out["obj"], out["pen"] = obj, pen
-        if targets is not None:
-            out["target_place"] = tplace
-    if targets is not None:
-        out["target_pos"], out["target_rank"] = tpos, rank
-    if validate:
-        out["cand_items"], out["cand_w"], out["cand_scores"], out["cand_src"] = cand_items, cand_w, cand_scores, cand_src
-    return out
-
-
-def _request_rows(model, userIds, now):
-    """dense user rows and one timestamp per row for a batch of user ids (an unknown user raises like Rank's failing first key)"""
-    rs = model.recSys
-    userIds = list(userIds)
-    users = np.array([rs.user_index(u) for u in userIds], np.int32)
-    if users.size and (users < 0).any():
-        bad = userIds[int(np.flatnonzero(users < 0)[0])]
-        raise SampleVectorError(f"get sample vector error: user {bad} has no features")
-    ts = np.broadcast_to(np.asarray(int(time.time()) if now is None else now, np.int64), users.shape)
-    return users, ts
-
-
-def _item_scores(model, r, nq):
-    raw = model.recSys._row_keys
-    return [[ItemScore(int(raw[r["items"][q, j]]), float(r["scores"][q, j])) for j in range(int(r["count"][q]))] for q in range(nq)]
-
-
-def RecommendVectorBatch(model: Predictor, vectors, userIds, n=10, now=None, **recall_kw):
-    """RecommendVector for several users in one device call: [[ItemScore]] in the order of userIds.  ``now``: one timestamp for all,
-    or one per user.  A user without history (or whose history's vectors cancel) gets an empty list."""
-    users, ts = _request_rows(model, userIds, now)
-    if users.size == 0:
-        return []
-    try:
-        r = uservec(model, vectors, users, ts, None, n, **recall_kw)
-    except capi.GoctrError as e:
-        raise SampleVectorError(str(e)) from None
-    return _item_scores(model, r, users.size)
-
-
-def RecommendVector(model: Predictor, vectors, userId: int, n=10, now=None, **recall_kw):
-    """EXTENSION -- user-to-item recall, then rank: the vectors (``vectors``: BuildItemVectors) of the user's newest ``history``
-    behaviours at or before ``now`` are summed into one interest vector, EVERY item of the catalogue is a candidate by its quantised
-    cosine to it (at least ``min_w`` / 65536), the ``n_cand`` closest are scored by the model and the ``n`` best come back.  Unlike
-    RecommendItemCF a candidate need not be in any history item's stored neighbour list; unlike Recommend the model scores n_cand
-    rows, not the catalogue."""
-    return RecommendVectorBatch(model, vectors, [userId], n, now, **recall_kw)[0]
-
-
-def _loo_figures(r, targets, n_items, k, n_cand):
-    """EvaluateLeaveOneOutRecall's figures from a call's target_pos / target_rank"""
-    ok = (targets >= 0) & (targets < n_items)
-    pos, rank = r["target_pos"][ok].astype(np.int64), r["target_rank"][ok].astype(np.float64)
-    n = int(ok.sum())
-    hit = (rank >= 0) & (rank < k)
-    nan = float("nan")
-    return dict(users=n, skipped=int((~ok).sum()), k=int(k), n_cand=int(n_cand),
-                recall=float(np.mean(pos >= 0)) if n else nan,
-                hit_rate=float(np.mean(hit)) if n else nan,
-                ndcg=float(np.mean(np.where(hit, 1.0 / np.log2(np.where(hit, rank, 0.0) + 2.0), 0.0))) if n else nan)
+                              tail_cnt, details) for lam in lambdas]
 
 
 def EvaluateLeaveOneOutVector(model: Predictor, vectors, k=10, sample_kw=None, details=False, pass_rows=0, **recall_kw):
@@ -1181,79 +1060,12 @@ def EvaluateLeaveOneOutVector(model: Predictor, vectors, k=10, sample_kw=None, d
     embedding trained without the held-out entries for an honest figure; that is the caller's choice."""
     users, targets, ts = _held_out_rows(model, sample_kw)
     recall_kw.setdefault("exclude", "before")
-    cfg, ucfg = _split_uservec_kw(None, None, recall_kw)
+    cfg, ucfg = _split_kw(None, None, recall_kw, _USERVEC_FIELDS, make_uservec_cfg)
     r = uservec(model, vectors, users, ts, targets, k, pass_rows, recall_cfg=cfg, ucfg=ucfg)
     out = _loo_figures(r, targets, model.recSys.item_table.shape[0], k, cfg.n_cand)
     if details:
-        out.update(target_pos=r["target_pos"], rank=r["target_rank"], user_index=users, target_index=targets, ts=ts)
+        out.update(_details(r, users, targets, ts))
     return out
-
-
-def _split_uservec_ivf_kw(recall_cfg, icfg, kw):
-    """(goctr_recall_cfg, goctr_uservec_ivf_cfg) from cfgs or keywords (min_w, nprobe and chunk_items are the latter's)"""
-    from .recall import _USERVEC_IVF_FIELDS, make_recall_cfg, make_uservec_ivf_cfg
-    ikw = {k: kw.pop(k) for k in list(kw) if k in _USERVEC_IVF_FIELDS}
-    if (recall_cfg is not None and kw) or (icfg is not None and ikw):
-        raise TypeError("give either a cfg or its keywords")
-    return (recall_cfg if recall_cfg is not None else make_recall_cfg(**kw)), (icfg if icfg is not None else make_uservec_ivf_cfg(**ikw))
-
-
-def uservec_ivf(model: Predictor, index, users, ts=None, targets=None, k=10, pass_rows=0, validate=False, recall_cfg=None, icfg=None,
-                **recall_kw):
-    """goctr_recommend_uservec_ivf over DENSE indices: ``uservec`` with the recall over ``index`` (recall.VectorIndex) as the recall
-    stage; the same dict.  ``recall_kw``: goctr_recall_cfg fields and goctr_uservec_ivf_cfg's (min_w, nprobe, chunk_items).  What
-    RecommendVectorIndexed / RecommendVectorIndexedBatch / EvaluateLeaveOneOutVectorIndexed call."""
-    from .recall import request_columns
-    cfg, icfg = _split_uservec_ivf_kw(recall_cfg, icfg, recall_kw)
-    rs = model.recSys
-    users, ts, targets = request_columns(users, ts, targets)
-    nq, kk, nc = users.size, max(int(k), 1), max(int(cfg.n_cand), 1)
-    out = dict(items=np.full((nq, kk), -2, np.int32), scores=np.full((nq, kk), np.nan, np.float32), count=np.full(nq, -2, np.int32),
-               cand_count=np.full(nq, -2, np.int32))
-    tpos = np.full(nq, -2, np.int32) if targets is not None else None
-    rank = np.full(nq, -2, np.int64) if targets is not None else None
-    cand_items = np.full((nq, nc), -2, np.int32) if validate else None
-    cand_w = np.full((nq, nc), 0xffffffff, np.uint32) if validate else None
-    cand_scores = np.full((nq, nc), np.nan, np.float32) if validate else None
-    nf = C.c_int64(-2)
-    capi.check(capi.load().goctr_recommend_uservec_ivf(
-        model.net._h, rs._h, index._h, capi.ptr(users, C.c_int32), capi.ptr(ts, C.c_int64), C.c_int64(nq),
-        capi.ptr(targets, C.c_int32), C.byref(cfg), C.byref(icfg), C.c_int32(int(k)), C.c_int64(int(pass_rows)),
-        capi.ptr(out["items"], C.c_int32), capi.ptr(out["scores"], C.c_float), capi.ptr(out["count"], C.c_int32),
-        capi.ptr(out["cand_count"], C.c_int32), capi.ptr(tpos, C.c_int32), capi.ptr(rank, C.c_int64), capi.ptr(cand_items, C.c_int32),
-        capi.ptr(cand_w, C.c_uint32), capi.ptr(cand_scores, C.c_float), C.byref(nf)))
-    out["n_failed"] = nf.value
-    if targets is not None:
-        out["target_pos"], out["target_rank"] = tpos, rank
-    if validate:
-        out["cand_items"], out["cand_w"], out["cand_scores"] = cand_items, cand_w, cand_scores
-    return out
-
-
-def BuildVectorIndex(vectors, **index_kw):
-    """EXTENSION: an inverted-file index over ``vectors`` (BuildItemVectors): the valid vectors clustered into ``n_lists`` lists by
-    ``iters`` rounds of integer k-means over ``train_items`` of them (recall.ItemVectors.build_index).  The index keeps its own copy
-    of the vectors: ``vectors`` may be closed afterwards."""
-    return vectors.build_index(**index_kw)
-
-
-def RecommendVectorIndexedBatch(model: Predictor, index, userIds, n=10, now=None, **recall_kw):
-    """RecommendVectorIndexed for several users in one device call: [[ItemScore]] in the order of userIds."""
-    users, ts = _request_rows(model, userIds, now)
-    if users.size == 0:
-        return []
-    try:
-        r = uservec_ivf(model, index, users, ts, None, n, **recall_kw)
-    except capi.GoctrError as e:
-        raise SampleVectorError(str(e)) from None
-    return _item_scores(model, r, users.size)
-
-
-def RecommendVectorIndexed(model: Predictor, index, userId: int, n=10, now=None, **recall_kw):
-    """EXTENSION -- RecommendVector over an index (``index``: BuildVectorIndex): the candidates come from the ``nprobe`` lists whose
-    centres lie nearest the user's interest vector, not from the whole catalogue, so a request's cost follows the lists it scans.
-    With ``nprobe`` at or above the number of non-empty lists the result is RecommendVector's."""
-    return RecommendVectorIndexedBatch(model, index, [userId], n, now, **recall_kw)[0]
 
 
 def EvaluateLeaveOneOutVectorIndexed(model: Predictor, index, k=10, sample_kw=None, details=False, pass_rows=0, **recall_kw):
@@ -1261,78 +1073,12 @@ def EvaluateLeaveOneOutVectorIndexed(model: Predictor, index, k=10, sample_kw=No
     what the index costs in recall shows as the difference between the two."""
     users, targets, ts = _held_out_rows(model, sample_kw)
     recall_kw.setdefault("exclude", "before")
-    cfg, icfg = _split_uservec_ivf_kw(None, None, recall_kw)
+    cfg, icfg = _split_kw(None, None, recall_kw, _USERVEC_IVF_FIELDS, make_uservec_ivf_cfg)
     r = uservec_ivf(model, index, users, ts, targets, k, pass_rows, recall_cfg=cfg, icfg=icfg)
     out = _loo_figures(r, targets, model.recSys.item_table.shape[0], k, cfg.n_cand)
     if details:
-        out.update(target_pos=r["target_pos"], rank=r["target_rank"], user_index=users, target_index=targets, ts=ts)
+        out.update(_details(r, users, targets, ts))
     return out
-
-
-def _split_uservec_multi_kw(recall_cfg, mcfg, kw):
-    """(goctr_recall_cfg, goctr_uservec_multi_cfg) from cfgs or keywords"""
-    from .recall import _USERVEC_MULTI_FIELDS, make_recall_cfg, make_uservec_multi_cfg
-    mkw = {k: kw.pop(k) for k in list(kw) if k in _USERVEC_MULTI_FIELDS}
-    if (recall_cfg is not None and kw) or (mcfg is not None and mkw):
-        raise TypeError("give either a cfg or its keywords")
-    return (recall_cfg if recall_cfg is not None else make_recall_cfg(**kw)), (mcfg if mcfg is not None else make_uservec_multi_cfg(**mkw))
-
-
-def uservec_multi(model: Predictor, vectors, users, ts=None, targets=None, k=10, pass_rows=0, validate=False, recall_cfg=None,
-                  mcfg=None, **recall_kw):
-    """goctr_recommend_uservec_multi over DENSE indices: ``uservec`` with the multi-interest recall as the recall stage; the same
-    dict plus n_int int32 [nq] and, with ``validate``, cand_interest uint8 [nq, n_cand].  ``recall_kw``: goctr_recall_cfg fields and
-    goctr_uservec_multi_cfg's (min_w, max_interests, iters, split_w, mix, chunk_items).  What RecommendMultiInterest /
-    RecommendMultiInterestBatch / EvaluateLeaveOneOutMultiInterest call."""
-    from .recall import request_columns
-    cfg, mcfg = _split_uservec_multi_kw(recall_cfg, mcfg, recall_kw)
-    rs = model.recSys
-    users, ts, targets = request_columns(users, ts, targets)
-    nq, kk, nc = users.size, max(int(k), 1), max(int(cfg.n_cand), 1)
-    out = dict(items=np.full((nq, kk), -2, np.int32), scores=np.full((nq, kk), np.nan, np.float32), count=np.full(nq, -2, np.int32),
-               cand_count=np.full(nq, -2, np.int32), n_int=np.full(nq, -2, np.int32))
-    tpos = np.full(nq, -2, np.int32) if targets is not None else None
-    rank = np.full(nq, -2, np.int64) if targets is not None else None
-    cand_items = np.full((nq, nc), -2, np.int32) if validate else None
-    cand_w = np.full((nq, nc), 0xffffffff, np.uint32) if validate else None
-    cand_scores = np.full((nq, nc), np.nan, np.float32) if validate else None
-    cand_interest = np.full((nq, nc), 254, np.uint8) if validate else None
-    nf = C.c_int64(-2)
-    capi.check(capi.load().goctr_recommend_uservec_multi(
-        model.net._h, rs._h, vectors._h, capi.ptr(users, C.c_int32), capi.ptr(ts, C.c_int64), C.c_int64(nq),
-        capi.ptr(targets, C.c_int32), C.byref(cfg), C.byref(mcfg), C.c_int32(int(k)), C.c_int64(int(pass_rows)),
-        capi.ptr(out["items"], C.c_int32), capi.ptr(out["scores"], C.c_float), capi.ptr(out["count"], C.c_int32),
-        capi.ptr(out["cand_count"], C.c_int32), capi.ptr(tpos, C.c_int32), capi.ptr(rank, C.c_int64), capi.ptr(cand_items, C.c_int32),
-        capi.ptr(cand_w, C.c_uint32), capi.ptr(cand_scores, C.c_float), C.byref(nf), capi.ptr(cand_interest, C.c_uint8),
-        capi.ptr(out["n_int"], C.c_int32)))
-    out["n_failed"] = nf.value
-    if targets is not None:
-        out["target_pos"], out["target_rank"] = tpos, rank
-    if validate:
-        out["cand_items"], out["cand_w"], out["cand_scores"], out["cand_interest"] = cand_items, cand_w, cand_scores, cand_interest
-    return out
-
-
-def RecommendMultiInterestBatch(model: Predictor, vectors, userIds, n=10, now=None, **recall_kw):
-    """RecommendMultiInterest for several users in one device call: [[ItemScore]] in the order of userIds.  ``now``: one timestamp
-    for all, or one per user.  A user without history (or whose history's vectors are all invalid) gets an empty list."""
-    users, ts = _request_rows(model, userIds, now)
-    if users.size == 0:
-        return []
-    try:
-        r = uservec_multi(model, vectors, users, ts, None, n, **recall_kw)
-    except capi.GoctrError as e:
-        raise SampleVectorError(str(e)) from None
-    return _item_scores(model, r, users.size)
-
-
-def RecommendMultiInterest(model: Predictor, vectors, userId: int, n=10, now=None, **recall_kw):
-    """EXTENSION -- RecommendVector for a user with several tastes: the history's vectors are clustered into up to
-    ``max_interests`` interest vectors (a new one starts where an entry's quantised cosine to every centre so far is below
-    ``split_w`` / 65536), each proposes its closest items of the whole catalogue, and the lists are mixed into ``n_cand``
-    candidates -- by turns in proportion to the interests' sizes (``mix="quota"``, the default) or by the best weight
-    (``mix="max"``) -- before the model scores them and the ``n`` best come back."""
-    return RecommendMultiInterestBatch(model, vectors, [userId], n, now, **recall_kw)[0]
 
 
 def EvaluateLeaveOneOutMultiInterest(model: Predictor, vectors, k=10, sample_kw=None, details=False, pass_rows=0, **recall_kw):
@@ -1340,27 +1086,12 @@ def EvaluateLeaveOneOutMultiInterest(model: Predictor, vectors, k=10, sample_kw=
     (goctr_recommend_uservec_multi); ``details`` adds n_int, the interests every row's history was split into."""
     users, targets, ts = _held_out_rows(model, sample_kw)
     recall_kw.setdefault("exclude", "before")
-    cfg, mcfg = _split_uservec_multi_kw(None, None, recall_kw)
+    cfg, mcfg = _split_kw(None, None, recall_kw, _USERVEC_MULTI_FIELDS, make_uservec_multi_cfg)
     r = uservec_multi(model, vectors, users, ts, targets, k, pass_rows, recall_cfg=cfg, mcfg=mcfg)
     out = _loo_figures(r, targets, model.recSys.item_table.shape[0], k, cfg.n_cand)
     if details:
-        out.update(target_pos=r["target_pos"], rank=r["target_rank"], user_index=users, target_index=targets, ts=ts, n_int=r["n_int"])
+        out.update(_details(r, users, targets, ts, "n_int"))
     return out
-
-
-def RecommendBlendVectorBatch(model: Predictor, icf, pop, uv, userIds, n=10, now=None, n_vec=64, quota_pop=0, vectors=None, pool=64,
-                              lambda_q=192, max_per_group=0, **recall_kw):
-    """EXTENSION -- RecommendBlendBatch with the user-vector recall as the caller's list: ItemCF's candidates, then the ``n_vec``
-    items closest to the user's pooled history vector (``uv``: BuildItemVectors), then the popularity list; with ``vectors`` the
-    diversity re-rank of RecommendDiverse picks the ``n`` returned.  One device call; the vector channel's list never leaves HBM."""
-    users, ts = _request_rows(model, userIds, now)
-    if users.size == 0:
-        return []
-    try:
-        r = blend_uservec(model, icf, pop, uv, users, ts, None, n_vec, quota_pop, n, vectors, pool, lambda_q, max_per_group, **recall_kw)
-    except capi.GoctrError as e:
-        raise SampleVectorError(str(e)) from None
-    return _item_scores(model, r, users.size)
 
 
 def EvaluateLeaveOneOutBlendVector(model: Predictor, icf, uv, pop=None, k=10, n_vec=64, sample_kw=None, details=False, pass_rows=0,
@@ -1368,21 +1099,12 @@ def EvaluateLeaveOneOutBlendVector(model: Predictor, icf, uv, pop=None, k=10, n_
     """EvaluateLeaveOneOutBlend's protocol and figures with the user-vector recall (``uv``, ``n_vec`` entries a row) as the blend's
     second channel (goctr_recommend_blend_uservec, best k by score); ``pop`` None builds the popularity list below the held-out
     events as there."""
-    rs = model.recSys
     users, targets, ts = _held_out_rows(model, sample_kw)
-    own = pop is None
-    if own:
-        pkw = dict(pop_kw or {})
-        pkw.setdefault("ts_hi", int(ts.min()))            # as EvaluateLeaveOneOutBlend: nothing at or after a held-out event counts
-        pop = BuildPopular(rs, **pkw)
-    recall_kw.setdefault("exclude", "before")
-    cfg, ucfg = _split_uservec_kw(None, None, recall_kw)
-    try:
+    with _popular_below(model, pop, ts, pop_kw) as pop:
+        recall_kw.setdefault("exclude", "before")
+        cfg, ucfg = _split_kw(None, None, recall_kw, _USERVEC_FIELDS, make_uservec_cfg)
         r = blend_uservec(model, icf, pop, uv, users, ts, targets, n_vec, quota_pop, k, pass_rows=pass_rows, recall_cfg=cfg, ucfg=ucfg)
-    finally:
-        if own:
-            pop.close()
-    out = _loo_figures(r, targets, rs.item_table.shape[0], k, cfg.n_cand)
+    out = _loo_figures(r, targets, model.recSys.item_table.shape[0], k, cfg.n_cand)
     if details:
-        out.update(target_pos=r["target_pos"], rank=r["target_rank"], src=r["src"], user_index=users, target_index=targets, ts=ts)
+        out.update(_details(r, users, targets, ts, "src"))
     return out
