@@ -261,6 +261,7 @@ SYMBOLS = [
     "goctr_metrics_multiclass", "goctr_metrics_multiclass_f64", "goctr_mlp_evaluate_resident_regression",
     "goctr_mlp_evaluate_resident_multiclass",
     "goctr_emb_load_w2v", "goctr_w2v_copy_word_vectors", "goctr_searcher_create_from_w2v", "goctr_searcher_load_w2v",
+    "goctr_searcher_search_ignore_sets",
     "goctr_corpus_append_ubcache",
     "goctr_negsample_cfg_default", "goctr_samples_create", "goctr_samples_destroy", "goctr_samples_info", "goctr_samples_export",
     "goctr_samples_get_weights", "goctr_dataset_create_samples",
@@ -344,6 +345,8 @@ def load() -> C.CDLL:
         _lib.goctr_w2v_copy_word_vectors.argtypes = [C.c_void_p, C.c_void_p]
         _lib.goctr_searcher_create_from_w2v.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
         _lib.goctr_searcher_load_w2v.argtypes = [C.c_void_p, C.c_void_p]
+        _f64 = C.POINTER(C.c_double)
+        _lib.goctr_searcher_search_ignore_sets.argtypes = [C.c_void_p, _f64, C.c_int, C.c_int, _i64, _i64, _i64, _f64, _i32]
         _lib.goctr_corpus_append_ubcache.argtypes = [C.c_void_p, C.c_void_p, C.c_int, _i64]
         _f32, _u64 = C.POINTER(C.c_float), C.POINTER(C.c_uint64)
         _lib.goctr_negsample_cfg_default.argtypes = [C.POINTER(NegSampleCfg)]

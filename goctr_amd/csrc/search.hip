@@ -38,6 +38,14 @@
 //                      member of C in the k-array, so replaying any superset of C in item order leaves the same array as the
 //                      full loop -- bit-exact results from an approximate filter.  More than 2048 candidates or a bound <= 0
 //                      (fewer than k positive group maxima, masses of equal similarities): the call falls back to the tile kernels.
+//
+// A SET of skipped items per query (goctr_searcher_search_ignore_sets, search.go:92 `ignoreWord ...string`; search_ignore.h): the
+// kernels above as SETS instantiations take the pass's sorted runs where they take `ignore [Q]` -- the tile kernels test a bit mask
+// of the run's slice inside the tile, the collect kernel bisects the run for its survivors -- and knn_repair_kernel runs between
+// scan and collect: it takes the skipped items out of the scan's maxima, so the bound stays the k-th largest group maximum for a set
+// of any size (with one item the (k + 1)-th does; with m items the (k + m)-th does too, and a pass whose runs all have
+// k + m <= 64 takes that bound WITHOUT the repair launch -- beyond that 4 (k + m) maxima do not fit gmax[256]).
+// goctr_searcher_search launches the instantiations it always has; nothing in them depends on a set.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -45,6 +53,7 @@
 #include <vector>
 
 #include "common.h"
+#include "search_ignore.h"
 #include "staging.h"
 #include "w2v_model.h"
 
@@ -67,6 +76,7 @@ struct goctr_searcher {
   // in front of the scan kernel.  bar_state: 0 untried, 1 allocated, -1 refused by the runtime (the staged copy stays)
   BarBuf in_bar; int bar_state = 0;
   bool lds_ok = false;
+  std::vector<long long> run_pack, run_work, run_tmp;   // goctr_searcher_search_ignore_sets: a pass's cleaned runs, its repair work list, sort scratch (search_ignore.h)
   std::mutex mu;
 };
 
@@ -126,6 +136,9 @@ __device__ __forceinline__ void knn_block_best(double& s, long long& i, double* 
     if (knn_before(sh_s[w], sh_i[w], s, i)) { s = sh_s[w]; i = sh_i[w]; }
 }
 
+// SETS: `ignore` is the pass's run pack (search_ignore.h) and a query skips its whole run; the one-item instantiation is the kernel
+// goctr_searcher_search has always launched
+template <bool SETS>
 __global__ __launch_bounds__(256) void knn_tile_kernel(const double* __restrict__ items, const double* __restrict__ norms,
                                                        long long V, int D, const double* __restrict__ queries,
                                                        const long long* __restrict__ ignore, int k, int ntiles,
@@ -135,22 +148,24 @@ __global__ __launch_bounds__(256) void knn_tile_kernel(const double* __restrict_
   double* sc = knn_smem + D;             // [KNN_TILE] scores of the tile (<= 0: not a candidate)
   __shared__ double sh_s[4];
   __shared__ long long sh_i[4];
+  __shared__ unsigned skip[SETS ? KNN_TILE / 32 : 1];      // SETS: the run's slice inside this tile, one bit per item
   const int tile = blockIdx.x, q = blockIdx.y;
   const double* query = queries + (size_t)q * D;
   for (int d = threadIdx.x; d < D; d += 256) qv[d] = query[d];
+  if constexpr (SETS) knn_tile_mask(skip, ignore + gridDim.y + 1, ignore[q], ignore[q + 1], (long long)tile * KNN_TILE, KNN_TILE);
   __syncthreads();
   // the query norm, like every thread of the reference would compute it (embutil.Norm, search.go:86-90)
   double qn = 0;
   for (int d = 0; d < D; ++d) qn += qv[d] * qv[d];
   qn = sqrt(qn);
-  const long long ig = ignore ? ignore[q] : -1;
+  const long long ig = !SETS && ignore ? ignore[q] : -1;
   const long long base = (long long)tile * KNN_TILE;
 #pragma unroll
   for (int j = 0; j < KNN_PER; ++j) {
     const int li = j * 256 + threadIdx.x;
     const long long it = base + li;
     double score = 0;
-    if (it < V && it != ig) {
+    if (it < V && (SETS ? !knn_mask_has(skip, li) : it != ig)) {
       const double n2 = norms[it];
       if (qn != 0 && n2 != 0) {
         const double* v = items + (size_t)it * D;
@@ -217,6 +232,7 @@ __device__ __forceinline__ void knn_insert(double* nb_s, long long* nb_i, int k,
   low = nb_s[k - 1];
 }
 
+template <bool SETS>
 __global__ __launch_bounds__(256) void knn_merge_kernel(const double* __restrict__ items, const double* __restrict__ norms,
                                                         long long V, int D, const double* __restrict__ queries,
                                                         const long long* __restrict__ ignore, const double* cand_sim,
@@ -233,6 +249,7 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const double* __restrict
   __shared__ long long sh_i[4];
   __shared__ int sh_t[4];
   __shared__ unsigned involved[8192 / 32];      // tiles holding members of the candidate set
+  __shared__ unsigned skip[SETS ? KNN_TILE / 32 : 1];      // SETS: the run's slice inside the tile being re-scored
   const int q = blockIdx.x;
   const double* cs = cand_sim + (size_t)q * ntiles * k;
   const long long* ci = cand_idx + (size_t)q * ntiles * k;
@@ -244,7 +261,7 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const double* __restrict
   double qn = 0;
   for (int d = 0; d < D; ++d) qn += qv[d] * qv[d];
   qn = sqrt(qn);
-  const long long ig = ignore ? ignore[q] : -1;
+  const long long ig = !SETS && ignore ? ignore[q] : -1;
 
   // ---- phase A: k-way merge of the tile lists -> similarity of the k-th best (the threshold of C)
   constexpr int MAXT = 32;                      // tiles per thread: 8192 tiles = 16.7 M items
@@ -318,11 +335,12 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const double* __restrict
       const bool rescan = cc[t] != 0 && ts[k - 1] >= thr && ts[k - 1] > 0;
       if (rescan) {
         const long long base = (long long)t * KNN_TILE;
+        if constexpr (SETS) knn_tile_mask(skip, ignore + gridDim.x + 1, ignore[q], ignore[q + 1], base, KNN_TILE);
 #pragma unroll
         for (int j = 0; j < KNN_PER; ++j) {
           const int li = j * 256 + threadIdx.x;
           const long long it = base + li;
-          sc[li] = (it < V && it != ig) ? knn_score(items, norms, it, D, qv, qn) : 0.0;
+          sc[li] = (it < V && (SETS ? !knn_mask_has(skip, li) : it != ig)) ? knn_score(items, norms, it, D, qv, qn) : 0.0;
         }
         __syncthreads();
         if (threadIdx.x == 0)
@@ -565,7 +583,11 @@ __device__ __forceinline__ double knn_wave_shr1(double x) {
 // sb_mode 0: sub-block b of a tile = items 32 b .. 32 b + 31 (the matrix-core scan kernels); 1: items j 256 + 16 b + i, j < tile / 256,
 // i < 16 (the VALU scan kernel: the rows of 16 adjacent threads)
 constexpr int KNN2_MYT = 256;      // listed tiles per query
+// SETS (goctr_searcher_search_ignore_sets): `ignore` is the pass's run pack (search_ignore.h), knn_repair_kernel has already taken the
+// skipped items out of the maxima -- so every group maximum belongs to an item that counts and the bound is the k-th largest,
+// whatever the size of the set -- and a survivor of the float32 filter is dropped when a bisection finds it in the query's run.
 constexpr int KNN2_MYB = 1024;     // listed sub-blocks per query
+template <bool SETS>
 __global__ __launch_bounds__(256) void knn_collect_kernel(const double* __restrict__ items, const double* __restrict__ norms,
                                                           const float* __restrict__ items32, long long V, int D,
                                                           const double* __restrict__ queries, const float* __restrict__ q32,
@@ -594,7 +616,9 @@ __global__ __launch_bounds__(256) void knn_collect_kernel(const double* __restri
   // One round of requests at the launch's cold start: the ignore index and the query's elements (into registers), the tile maxima, and only
   // then the query's copy into LDS and the maximum.  (In the order "copy the query; maxima" the LDS writes waited for the query before the
   // maxima were even asked for: two dependent round trips where one does, ~1.9 k of the launch's ~29 k ticks.)
-  long long ig_v = ignore[q];
+  long long ig_v = ignore[q];                                    // (SETS: where the query's run begins in the pack's entries)
+  long long run_end = 0;
+  if constexpr (SETS) run_end = ignore[q + 1];
   const int d0 = (int)threadIdx.x;
   double q64v = 0.0; float q32v = 0.f;
   if (d0 < D) { q64v = queries[(size_t)q * D + d0]; q32v = q32[(size_t)q * D + d0]; }
@@ -607,7 +631,7 @@ __global__ __launch_bounds__(256) void knn_collect_kernel(const double* __restri
     tmv[u] = t < nt ? tm[t] : 0.f;
   }
   asm volatile("" : "+v"(ig_v));       // (pinned with this round: left alone, the load sinks to its use behind the maxima's wait)
-  const long long ig = ig_v;
+  const long long ig = SETS ? -1 : ig_v;
   if (d0 < D) { knn_cq[d0] = q64v; cq32[d0] = q32v; }
   for (int d = 256 + threadIdx.x; d < D; d += 256) { knn_cq[d] = queries[(size_t)q * D + d]; cq32[d] = q32[(size_t)q * D + d]; }
   float m = 0.f;
@@ -619,7 +643,10 @@ __global__ __launch_bounds__(256) void knn_collect_kernel(const double* __restri
     // (256 broadcast LDS reads and ~5 instructions each per thread: 12.6 k of the launch's 43 k cycles, GOCTR_DBG=knn).  Now every
     // wavefront peels off its own `rounds` largest -- a DPP maximum over the rows, four v_readlane, the first lane that holds the
     // maximum drops out -- and the 4 x rounds survivors are ranked among themselves: the same value, ~2 k cycles.
-    const int rounds = k + (ig >= 0 ? 1 : 0);                          // <= 64 (knn_scan_usable)
+    // (SETS, host_polls bit 1: no repair launch ran -- every run of the pass has k + m <= 64 -- and up to m of the maxima may
+    // belong to skipped items: the (k + m)-th largest still leaves k maxima of items that count)
+    const int rounds = SETS ? k + ((host_polls & 2) ? (int)(run_end - ig_v) : 0)
+                            : k + (ig >= 0 ? 1 : 0);                   // <= 64 (knn_scan_usable)
     float mine = m;
     for (int r = 0; r < rounds; ++r) {
       float v = mine;
@@ -633,7 +660,10 @@ __global__ __launch_bounds__(256) void knn_collect_kernel(const double* __restri
       if (lane == (int)__builtin_ctzll(hold | (1ull << 63))) mine = -1.f;     // (maxima are >= 0: -1 = peeled off)
       if (lane == 0) gmax[wave * rounds + r] = wmax;                          // (the four lists back to back: 4 x rounds <= 256)
     }
-    if (threadIdx.x == 64) {
+    // (SETS: by a thread of wavefront 0, which wrote knn_cq above -- D <= 64 on this path -- so program order alone puts the
+    // writes first.  Thread 64 reads them with no barrier in between and relies on its wavefront's `rounds` peeling steps taking
+    // longer than wavefront 0's wait for the query; with k = 1 and the run's second offset to wait for, that was seen to fail.)
+    if (threadIdx.x == (SETS ? 0 : 64)) {
       double qn = 0;
       for (int d = 0; d < D; ++d) qn += knn_cq[d] * knn_cq[d];           // embutil.Norm (search.go:86-90)
       knn_cq[D] = sqrt(qn);
@@ -727,6 +757,7 @@ __global__ __launch_bounds__(256) void knn_collect_kernel(const double* __restri
       const int tile = blk / SB, b = blk - tile * SB;
       const long long it = sb_mode == 0 ? (long long)tile * tile_items + 32 * b + e
                                         : (long long)tile * tile_items + (e >> 4) * 256 + 16 * b + (e & 15);
+      if constexpr (SETS) return (it < V && !knn_run_has(ignore + gridDim.x + 1, ig_v, run_end, it)) ? it : -1;
       return (it < V && it != ig) ? it : -1;
     };
     auto exact = [&](long long it) {
@@ -872,7 +903,7 @@ __global__ __launch_bounds__(256) void knn_collect_kernel(const double* __restri
   int cnt = 0;
   for (int r = 0; r < k; ++r) cnt += nb_i[r] >= 0;
   const int n_out = cnt < k ? k - 1 : k;                      // search.go:126-131 (see knn_merge_kernel)
-  if (host_polls) {
+  if (SETS ? (host_polls & 1) : host_polls) {
     // the host watches out_cnt[q] in the pinned buffer (knn_search_scan): the neighbours must be there before the count is.
     // Round 6: the neighbours leave as system-scope stores (written through when issued, nothing left dirty), each writer waits for
     // its stores' acknowledgements, and the count follows behind the barrier -- no release fence, whose write-back walk of the
@@ -915,20 +946,33 @@ static bool knn_scan_usable(const goctr_searcher* s, int k) {
   const int tile = knn_scan_tile(s->D);
   return tile > 0 && s->items32.p && k + 1 <= 64 && cdiv(s->V, tile) <= (1 << 20);
 }
+// a pass's cleaned runs on the host (knn_clean_runs): [Q + 1] offsets | `total` entries; null = the one-item `ignore [Q]` of
+// goctr_searcher_search.  The set path is taken only with total > 0.
+struct KnnPassRuns { const long long* pack; size_t total; };
+
 // 0 = done, -1 = error, 1 = fall back to the tile kernels
-static int knn_search_scan(goctr_searcher* s, const double* queries, int Q, int k, const int64_t* ignore, int64_t* out_idx,
-                           double* out_sim, int* out_count) {
+static int knn_search_scan(goctr_searcher* s, const double* queries, int Q, int k, const int64_t* ignore, const KnnPassRuns* runs,
+                           int64_t* out_idx, double* out_sim, int* out_count) {
   Engine& e = engine();
   const int D = s->D, tile_items = knn_scan_tile(D), nt = (int)cdiv(s->V, tile_items), nqb = (int)cdiv(Q, KNN2_QB);
   const size_t lds_r = sizeof(double) * (2 * (size_t)KNN2_CAP + 2 * (size_t)k);
   if (!s->lds_ok) {
-    GOCTR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(knn_collect_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(sizeof(double) * (2 * (size_t)KNN2_CAP + 2 * (size_t)KNN_MAX_K + 1024 + 2))));
+    const int lds_max = (int)(sizeof(double) * (2 * (size_t)KNN2_CAP + 2 * (size_t)KNN_MAX_K + 1024 + 2));
+    GOCTR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(knn_collect_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+    GOCTR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(knn_collect_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
     s->lds_ok = true;
   }
   // one upload: [Q x D queries | Q ignore | the queries normalised, float32, padded with zero rows to whole 64-query blocks],
-  // one download: [Q x k idx | Q x k sim | Q count]
-  const size_t in_q = sizeof(double) * (size_t)Q * D, in_ig = sizeof(long long) * (size_t)Q;
+  // one download: [Q x k idx | Q x k sim | Q count].  With sets the ignore part is [the run pack | the repair work list] instead.
+  // Small sets (k + m <= 64 for every run of the pass): the bound widened to the (k + m)-th largest maximum, no repair launch --
+  // 12 us of launch for a handful of items.  Anything larger: the repair launch's work list.
+  bool widen = runs != nullptr;
+  for (int i = 0; i < Q && widen; ++i) widen = k + (runs->pack[i + 1] - runs->pack[i]) <= 64;
+  if (runs && !widen) knn_repair_work(runs->pack, Q, tile_items, s->run_work);
+  else s->run_work.clear();
+  const size_t in_runs = runs ? sizeof(long long) * ((size_t)Q + 1 + runs->total) : 0;
+  const size_t in_q = sizeof(double) * (size_t)Q * D;
+  const size_t in_ig = runs ? in_runs + sizeof(long long) * s->run_work.size() : sizeof(long long) * (size_t)Q;
   const size_t in_q32 = sizeof(float) * (size_t)nqb * KNN2_QB * D;
   const bool bf = knn_scan_mfma(s, Q);               // the bf16-plane matrix-core filter (from 12 queries per call on, D = 16 / 32)
   const size_t in_qbf = bf ? sizeof(unsigned short) * 2 * (size_t)nqb * KNN2_QB * D : 0, in_bytes = in_q + in_ig + in_q32 + in_qbf;
@@ -947,6 +991,10 @@ static int knn_search_scan(goctr_searcher* s, const double* queries, int Q, int 
   unsigned char* const d_in = bar ? reinterpret_cast<unsigned char*>(s->in_bar.p) : s->in_pack.p;
   memcpy(s->h_in.p, queries, in_q);
   long long* h_ig = reinterpret_cast<long long*>(s->h_in.p + in_q);
+  if (runs) {
+    memcpy(h_ig, runs->pack, in_runs);
+    memcpy(s->h_in.p + in_q + in_runs, s->run_work.data(), in_ig - in_runs);
+  } else
   for (int i = 0; i < Q; ++i) h_ig[i] = ignore ? (long long)ignore[i] : -1;
   float* h_q32 = reinterpret_cast<float*>(s->h_in.p + in_q + in_ig);
   memset(h_q32, 0, in_q32);
@@ -1010,12 +1058,22 @@ static int knn_search_scan(goctr_searcher* s, const double* queries, int Q, int 
   // collect + exact refine + replay: one workgroup per query (sub-block layout: 32 consecutive items from the matrix-core scan
   // kernels, the rows of 16 adjacent threads from the VALU one)
   const int sb_mode = bf ? 0 : 1;
+  if (runs && !s->run_work.empty()) {                 // the skipped items out of the maxima: one wavefront per (query, tile) holding one
+    hipLaunchKernelGGL(knn_repair_kernel, dim3((unsigned)s->run_work.size()), dim3(64), 0, e.stream, s->items32.p, (long long)s->V, D,
+                       d_q32, d_ig, Q, reinterpret_cast<const long long*>(d_in + in_q + in_runs), nt, tile_items, sb_mode, qpad,
+                       s->tmax.p, s->bmax.p);
+    GOCTR_HIP(hipGetLastError());
+  }
   static DevBuf<unsigned long long> knn_dbg;
   const bool want_dbg = dbg_on("knn");
   if (want_dbg && !knn_dbg.p && knn_dbg.alloc(16)) return -1;
   unsigned long long* kdbg = want_dbg ? knn_dbg.p : nullptr;
   const size_t lds_q = sizeof(double) * ((size_t)D + 1 + ((size_t)D + 1) / 2);      // [D] query | norm | [D] floats (rounded up to doubles)
-  hipLaunchKernelGGL(knn_collect_kernel, dim3(Q), dim3(256), lds_q + lds_r, e.stream, s->items.p, s->norms.p, s->items32.p, (long long)s->V, D,
+  if (runs)
+    hipLaunchKernelGGL(knn_collect_kernel<true>, dim3(Q), dim3(256), lds_q + lds_r, e.stream, s->items.p, s->norms.p, s->items32.p, (long long)s->V, D,
+                       d_q, d_q32, d_ig, s->tmax.p, s->bmax.p, qpad, nt, tile_items, sb_mode, k, E, d_oi, d_os, d_oc, (poll ? 1 : 0) | (widen ? 2 : 0), kdbg);
+  else
+  hipLaunchKernelGGL(knn_collect_kernel<false>, dim3(Q), dim3(256), lds_q + lds_r, e.stream, s->items.p, s->norms.p, s->items32.p, (long long)s->V, D,
                      d_q, d_q32, d_ig, s->tmax.p, s->bmax.p, qpad, nt, tile_items, sb_mode, k, E, d_oi, d_os, d_oc, poll ? 1 : 0, kdbg);
   GOCTR_HIP(hipGetLastError());
   if (kdbg) {
@@ -1072,17 +1130,21 @@ static int searcher_derive(goctr_searcher* s) {
 }
 
 // one device pass of Q <= KNN_PASS_MAXQ queries: the scan path, or (not usable / it handed a query back) the exact tile kernels
-static int searcher_search_pass(goctr_searcher* s, const double* queries, int Q, int k, const int64_t* ignore, int64_t* out_idx,
-                                double* out_sim, int* out_count) {
+// (runs: the pass's sets instead of `ignore` -- both paths carry them, so a query handed back by the collect kernel keeps its run)
+static int searcher_search_pass(goctr_searcher* s, const double* queries, int Q, int k, const int64_t* ignore, const KnnPassRuns* runs,
+                                int64_t* out_idx, double* out_sim, int* out_count) {
   Engine& e = engine();
   if (knn_scan_usable(s, k)) {
-    const int rc = knn_search_scan(s, queries, Q, k, ignore, out_idx, out_sim, out_count);
+    const int rc = knn_search_scan(s, queries, Q, k, ignore, runs, out_idx, out_sim, out_count);
     if (rc <= 0) return rc;                  // (1: a query had more candidates than the replay takes -- the tile kernels below)
   }
   const int ntiles = (int)cdiv(s->V, KNN_TILE);
   if (s->q.ensure((size_t)Q * s->D, false) || s->q.upload(queries, (size_t)Q * s->D)) return -1;
-  if (s->ignore.ensure((size_t)Q, false)) return -1;
-  {
+  const size_t n_ig = runs ? (size_t)Q + 1 + runs->total : (size_t)Q;
+  if (s->ignore.ensure(n_ig, false)) return -1;
+  if (runs) {
+    if (s->ignore.upload(runs->pack, n_ig)) return -1;
+  } else {
     std::vector<long long> ig(Q, -1);
     if (ignore) for (int i = 0; i < Q; ++i) ig[i] = ignore[i];
     if (s->ignore.upload(ig.data(), Q)) return -1;
@@ -1091,13 +1153,16 @@ static int searcher_search_pass(goctr_searcher* s, const double* queries, int Q,
       s->cand_cut.ensure((size_t)Q * ntiles, false)) return -1;
   if (s->out_sim.ensure((size_t)Q * k, false) || s->out_idx.ensure((size_t)Q * k, false) || s->out_cnt.ensure(Q, false)) return -1;
   const size_t lds = sizeof(double) * ((size_t)s->D + KNN_TILE);
-  hipLaunchKernelGGL(knn_tile_kernel, dim3(ntiles, Q), dim3(256), lds, e.stream, s->items.p, s->norms.p, (long long)s->V, s->D,
-                     s->q.p, s->ignore.p, k, ntiles, s->cand_sim.p, s->cand_idx.p, s->cand_cut.p);
-  GOCTR_HIP(hipGetLastError());
   const size_t lds_m = sizeof(double) * ((size_t)s->D + KNN_TILE + 4 * (size_t)k);
-  hipLaunchKernelGGL(knn_merge_kernel, dim3(Q), dim3(256), lds_m, e.stream, s->items.p, s->norms.p, (long long)s->V, s->D, s->q.p,
-                     s->ignore.p, s->cand_sim.p, s->cand_idx.p, s->cand_cut.p, ntiles, k, s->out_idx.p, s->out_sim.p, s->out_cnt.p);
-  GOCTR_HIP(hipGetLastError());
+#define GOCTR_KNN_TILES(SETS)                                                                                                       \
+  hipLaunchKernelGGL(knn_tile_kernel<SETS>, dim3(ntiles, Q), dim3(256), lds, e.stream, s->items.p, s->norms.p, (long long)s->V, s->D, \
+                     s->q.p, s->ignore.p, k, ntiles, s->cand_sim.p, s->cand_idx.p, s->cand_cut.p);                                  \
+  GOCTR_HIP(hipGetLastError());                                                                                                     \
+  hipLaunchKernelGGL(knn_merge_kernel<SETS>, dim3(Q), dim3(256), lds_m, e.stream, s->items.p, s->norms.p, (long long)s->V, s->D, s->q.p, \
+                     s->ignore.p, s->cand_sim.p, s->cand_idx.p, s->cand_cut.p, ntiles, k, s->out_idx.p, s->out_sim.p, s->out_cnt.p); \
+  GOCTR_HIP(hipGetLastError())
+  if (runs) { GOCTR_KNN_TILES(true); } else { GOCTR_KNN_TILES(false); }
+#undef GOCTR_KNN_TILES
   std::vector<long long> oi((size_t)Q * k);
   if (s->out_idx.download(oi.data(), oi.size()) || s->out_sim.download(out_sim, (size_t)Q * k) || s->out_cnt.download(out_count, Q))
     return -1;
@@ -1156,7 +1221,45 @@ int goctr_searcher_search(goctr_searcher* s, const double* queries, int Q, int k
   std::lock_guard<std::mutex> lk(s->mu);
   for (int q0 = 0; q0 < Q; q0 += KNN_PASS_MAXQ) {
     const int n = Q - q0 < KNN_PASS_MAXQ ? Q - q0 : KNN_PASS_MAXQ;
-    if (searcher_search_pass(s, queries + (size_t)q0 * s->D, n, k, ignore ? ignore + q0 : nullptr, out_idx + (size_t)q0 * k,
+    if (searcher_search_pass(s, queries + (size_t)q0 * s->D, n, k, ignore ? ignore + q0 : nullptr, nullptr, out_idx + (size_t)q0 * k,
+                             out_sim + (size_t)q0 * k, out_count + q0)) return -1;
+  }
+  return 0;
+}
+
+int goctr_searcher_search_ignore_sets(goctr_searcher* s, const double* queries, int Q, int k, const int64_t* ign_off,
+                                      const int64_t* ign_idx, int64_t* out_idx, double* out_sim, int* out_count) {
+  GOCTR_ENTER_H(s);
+  GOCTR_CHECK(s && queries && out_idx && out_sim && out_count, "goctr_searcher_search_ignore_sets: null argument");
+  GOCTR_CHECK(Q > 0 && k > 0 && k <= KNN_MAX_K, "goctr_searcher_search_ignore_sets: Q %d, k %d (k <= %d)", Q, k, KNN_MAX_K);
+  if (ign_off) {                               // (before anything is written: a refused call leaves the outputs alone)
+    GOCTR_CHECK(ign_off[0] == 0, "goctr_searcher_search_ignore_sets: ign_off[0] is %lld, not 0", (long long)ign_off[0]);
+    for (int q = 0; q < Q; ++q)
+      GOCTR_CHECK(ign_off[q + 1] >= ign_off[q], "goctr_searcher_search_ignore_sets: ign_off decreases at query %d", q);
+    GOCTR_CHECK(ign_idx || ign_off[Q] == 0, "goctr_searcher_search_ignore_sets: ign_idx is null with %lld entries", (long long)ign_off[Q]);
+  }
+  std::lock_guard<std::mutex> lk(s->mu);
+  for (int q0 = 0; q0 < Q; q0 += KNN_PASS_MAXQ) {
+    const int n = Q - q0 < KNN_PASS_MAXQ ? Q - q0 : KNN_PASS_MAXQ;
+    // the pass's slice of the runs, cleaned; a pass whose runs are all empty is goctr_searcher_search's pass without `ignore`
+    KnnPassRuns runs{nullptr, 0};
+    if (ign_off && ign_off[q0 + n] > ign_off[q0]) {
+      runs.total = knn_clean_runs(ign_off, ign_idx, q0, n, s->V, s->run_pack, s->run_tmp);
+      runs.pack = s->run_pack.data();
+    }
+    // no run longer than one item: goctr_searcher_search's pass with its `ignore [Q]` -- the bound widened by one and no repair
+    // launch (7.6 us per 64-query call less than the set path at m = 1, 5.3 us per one-query call)
+    std::vector<int64_t> one;
+    if (runs.total) {
+      bool single = true;
+      for (int i = 0; i < n && single; ++i) single = runs.pack[i + 1] - runs.pack[i] <= 1;
+      if (single) {
+        one.assign((size_t)n, -1);
+        for (int i = 0; i < n; ++i) if (runs.pack[i + 1] > runs.pack[i]) one[i] = runs.pack[n + 1 + runs.pack[i]];
+      }
+    }
+    if (searcher_search_pass(s, queries + (size_t)q0 * s->D, n, k, one.empty() ? nullptr : one.data(),
+                             runs.total && one.empty() ? &runs : nullptr, out_idx + (size_t)q0 * k,
                              out_sim + (size_t)q0 * k, out_count + q0)) return -1;
   }
   return 0;

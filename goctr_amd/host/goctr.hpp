@@ -1256,20 +1256,32 @@ class Searcher {
   ~Searcher() { if (h_) goctr_searcher_destroy(h_); }
   Searcher(const Searcher&) = delete;
   Searcher& operator=(const Searcher&) = delete;
-  Neighbors SearchVector(const std::vector<double>& query, int k) { return search(query.data(), k, -1); }
+  Neighbors SearchVector(const std::vector<double>& query, int k) { return Search(query, k, {}); }
+  // search.go:92-134 with its variadic ignoreWord: every row carrying one of the words is skipped (:101-103)
+  Neighbors Search(const std::vector<double>& query, int k, const std::vector<std::string>& ignoreWord) {
+    return search(query.data(), k, rows_of(ignoreWord));
+  }
   Neighbors SearchInternal(const std::string& word, int k) {
     if (vec_.empty()) throw std::runtime_error("this searcher's items live on the device only: query by vector");
-    for (size_t i = 0; i < words_.size(); ++i)
-      if (words_[i] == word) return search(vec_.data() + i * (size_t)dim_, k, (int64_t)i);
+    for (size_t i = 0; i < words_.size(); ++i)      // the FIRST row with the word is the query (:67-72), all its rows are skipped (:79)
+      if (words_[i] == word) return search(vec_.data() + i * (size_t)dim_, k, rows_of({word}));
     throw std::runtime_error(word + " is not found in searcher");   // search.go:73-75
   }
 
  private:
-  Neighbors search(const double* q, int k, int64_t ignore) {
+  std::vector<int64_t> rows_of(const std::vector<std::string>& ignoreWord) const {
+    std::vector<int64_t> rows;
+    for (const std::string& w : ignoreWord)
+      for (size_t i = 0; i < words_.size(); ++i)
+        if (words_[i] == w) rows.push_back((int64_t)i);
+    return rows;
+  }
+  Neighbors search(const double* q, int k, const std::vector<int64_t>& skip) {
     std::vector<int64_t> idx(k);
     std::vector<double> sim(k);
     int count = 0;
-    check(goctr_searcher_search(h_, q, 1, k, ignore >= 0 ? &ignore : nullptr, idx.data(), sim.data(), &count));
+    const int64_t off[2] = {0, (int64_t)skip.size()};
+    check(goctr_searcher_search_ignore_sets(h_, q, 1, k, off, skip.data(), idx.data(), sim.data(), &count));
     Neighbors out(count);
     for (int r = 0; r < count; ++r)
       if (idx[r] >= 0) out[r] = Neighbor{words_[(size_t)idx[r]], (unsigned)r + 1, sim[r]};

@@ -1317,6 +1317,19 @@ void goctr_searcher_destroy(goctr_searcher* s);
  * items qualify, the surplus entries empty).  k <= 256. */
 int goctr_searcher_search(goctr_searcher* s, const double* queries, int Q, int k, const int64_t* ignore,
                           int64_t* out_idx, double* out_sim, int* out_count);
+/* Searcher.Search with its variadic ignoreWord (:92, :101-103): query q skips item i iff i occurs in
+ * ign_idx[ign_off[q] .. ign_off[q + 1]).  A run may be in any order and hold duplicates; entries < 0 or >= V name no item
+ * (goctr_searcher_search's -1).  ign_off [Q + 1] starts at 0 and never decreases; ign_off == NULL means no sets, and
+ * ign_idx may be NULL when ign_off[Q] == 0.  The outputs are goctr_searcher_search's: the reference loop over the items that
+ * are not skipped, its tie order, its guard-loop count.  Skipping is `continue`, so the loop over V items with the set S equals
+ * the loop over the matrix with S's rows deleted, the indices mapped back -- which is what the tests compare with.  With every
+ * run of length <= 1 the call returns, byte for byte, what goctr_searcher_search returns for the corresponding ignore [Q].
+ * The size of a set changes the work (a bisection per candidate, a repair of the scan's maxima per skipped sub-block), never
+ * the path.  Refused with -1, the outputs untouched: what goctr_searcher_search refuses, ign_off[0] != 0, a decreasing
+ * ign_off, ign_idx == NULL with ign_off[Q] > 0.  Host work and upload are proportional to the sets, not to V. */
+int goctr_searcher_search_ignore_sets(goctr_searcher* s, const double* queries, int Q, int k,
+                                      const int64_t* ign_off /* [Q + 1] or NULL */, const int64_t* ign_idx /* [ign_off[Q]] */,
+                                      int64_t* out_idx, double* out_sim, int* out_count);
 
 /* ---------------------------------------------------------------- binary metrics on the device
  * Replaces utils.RocAuc32 / RocAuc (utils/util.go:116-148 -> metrics.ROCAUCScore(yTrue, yScore, "", nil),
