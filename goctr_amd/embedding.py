@@ -41,9 +41,10 @@ class Word2Vec:
 
     def __init__(self, window=5, dim=16, iter=1, optimizer="hs", min_count=5, max_count=-1, init_lr=0.025,
                  subsample_threshold=1e-3, deterministic=False, streams=8192, slices=16, update_lr_batch=100000, rng=None,
-                 model="skipgram", devices=0, exchange_every=0):
+                 model="skipgram", devices=0, exchange_every=0, neg_samples=5, max_depth=100):
         # options.go:38-58 defaults; wordemb.go:10-18 fixes SkipGram + HS + DocInMemory
         self.window, self.dim, self.iter, self.optimizer = window, dim, iter, optimizer
+        self.neg_samples, self.max_depth = neg_samples, max_depth           # options.go:51, :46
         self.min_count, self.max_count, self.init_lr = min_count, max_count, init_lr
         self.threshold = subsample_threshold
         self.deterministic, self.streams = deterministic, streams
@@ -80,6 +81,7 @@ class Word2Vec:
         capi.load().goctr_w2v_cfg_default(C.byref(c))
         c.dim, c.window, c.optimizer = self.dim, self.window, 0 if self.optimizer == "hs" else 1
         c.model = 0 if self.model == "skipgram" else 1
+        c.neg_samples, c.max_depth = self.neg_samples, self.max_depth
         c.init_lr, c.min_lr = self.init_lr, self.init_lr * 1.0e-4           # options.go:42,49
         c.update_lr_batch = self.update_lr_batch
         c.deterministic, c.streams, c.slices = int(self.deterministic), self.streams, self.slices
