@@ -96,6 +96,23 @@ class CalibBins(C.Structure):
     _fields_ = [("count", C.POINTER(C.c_int64)), ("pos", C.POINTER(C.c_int64)), ("score_sum", C.POINTER(C.c_double))]
 
 
+class CalibCfg(C.Structure):
+    """goctr_calib_cfg (include/goctr.h)"""
+    _fields_ = [("w_pos", C.c_int32), ("w_neg", C.c_int32), ("interp", C.c_int32), ("tile", C.c_int32), ("clip_eps", C.c_double)]
+
+
+class CalibBlock(C.Structure):
+    """goctr_calib_block (include/goctr.h)"""
+    _fields_ = [("lo", C.c_double), ("hi", C.c_double), ("value", C.c_double), ("num", C.c_uint64), ("den", C.c_uint64),
+                ("rows", C.c_int64), ("pos", C.c_int64)]
+
+
+class CalibInfo(C.Structure):
+    """goctr_calib_info (include/goctr.h)"""
+    _fields_ = [("n", C.c_int64), ("positives", C.c_int64), ("negatives", C.c_int64), ("groups", C.c_int64),
+                ("blocks", C.c_int64), ("rounds", C.c_int64)]
+
+
 class RegressionMetrics(C.Structure):
     """goctr_regression_metrics (include/goctr.h)"""
     _fields_ = [("n", C.c_int64), ("k", C.c_int64), ("constant_columns", C.c_int64), ("mse_uniform", C.c_double),
@@ -227,6 +244,7 @@ class ListMetrics(C.Structure):
 TOPN_KEEP_SEEN, TOPN_DROP_ALL_SEEN, TOPN_DROP_SEEN_BEFORE = 0, 1, 2   # goctr_topn_cfg.exclude
 NS_UNIFORM, NS_POPULARITY, NS_POPULARITY_075 = 0, 1, 2      # goctr_negsample_cfg.weighting
 NS_ALL, NS_NEWEST, NS_ALL_BUT_NEWEST = 0, 1, 2              # goctr_negsample_cfg.which
+CALIB_STEP, CALIB_LINEAR = 0, 1                             # goctr_calib_cfg.interp
 UVMIX_MAX, UVMIX_QUOTA = 0, 1                               # goctr_uservec_multi_cfg.mix
 
 
@@ -257,6 +275,10 @@ SYMBOLS = [
     "goctr_mlp_evaluate_resident_grouped",
     "goctr_curve_cfg_default", "goctr_metrics_curve", "goctr_metrics_curve_f64", "goctr_evaluate_dataset_curve",
     "goctr_mlp_evaluate_resident_curve",
+    "goctr_calib_cfg_default", "goctr_calibrator_fit", "goctr_calibrator_fit_f64", "goctr_calibrator_fit_dataset",
+    "goctr_mlp_calibrator_fit_resident", "goctr_calibrator_create", "goctr_calibrator_destroy", "goctr_calibrator_info",
+    "goctr_calibrator_export", "goctr_calibrator_apply", "goctr_calibrator_apply_f64", "goctr_predict_dataset_calibrated",
+    "goctr_evaluate_dataset_curve_calibrated", "goctr_mlp_evaluate_resident_curve_calibrated",
     "goctr_metrics_regression", "goctr_metrics_regression_f64", "goctr_metrics_confusion", "goctr_multiclass_cfg_default",
     "goctr_metrics_multiclass", "goctr_metrics_multiclass_f64", "goctr_mlp_evaluate_resident_regression",
     "goctr_mlp_evaluate_resident_multiclass",
@@ -304,7 +326,8 @@ def load() -> C.CDLL:
                      "goctr_multiclass_cfg_default", "goctr_popular_cfg_default", "goctr_popular_destroy",
                      "goctr_itemnbr_cfg_default", "goctr_mmr_cfg_default", "goctr_itemvec_destroy", "goctr_list_cfg_default",
                      "goctr_swing_cfg_default", "goctr_uservec_cfg_default", "goctr_uservec_multi_cfg_default",
-                     "goctr_ivf_cfg_default", "goctr_uservec_ivf_cfg_default", "goctr_itemvec_index_destroy"):
+                     "goctr_ivf_cfg_default", "goctr_uservec_ivf_cfg_default", "goctr_itemvec_index_destroy",
+                     "goctr_calib_cfg_default", "goctr_calibrator_destroy"):
             getattr(_lib, name).restype = None
         _bm = C.POINTER(BinaryMetrics)
         _lib.goctr_metrics_binary.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, _bm]
@@ -324,6 +347,23 @@ def load() -> C.CDLL:
         _lib.goctr_metrics_curve_f64.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64, _cc, _cm, _cp, _cb]
         _lib.goctr_evaluate_dataset_curve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _cc, _cm, _cp, _cb]
         _lib.goctr_mlp_evaluate_resident_curve.argtypes = [C.c_void_p, _cc, _cm, _cp, _cb]
+        _kc, _kb, _kh = C.POINTER(CalibCfg), C.POINTER(CalibBlock), C.POINTER(C.c_void_p)
+        _lib.goctr_calib_cfg_default.argtypes = [_kc]
+        _lib.goctr_calibrator_fit.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, _kc, _kh]
+        _lib.goctr_calibrator_fit_f64.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64, _kc, _kh]
+        _lib.goctr_calibrator_fit_dataset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _kc, _kh]
+        _lib.goctr_mlp_calibrator_fit_resident.argtypes = [C.c_void_p, _kc, _kh]
+        _lib.goctr_calibrator_create.argtypes = [_kb, C.c_int64, _kc, _kh]
+        _lib.goctr_calibrator_destroy.argtypes = [C.c_void_p]
+        _lib.goctr_calibrator_info.argtypes = [C.c_void_p, C.POINTER(CalibInfo)]
+        _lib.goctr_calibrator_export.argtypes = [C.c_void_p, _kb, C.c_int64]
+        _lib.goctr_calibrator_apply.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_float)]
+        _lib.goctr_calibrator_apply_f64.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double)]
+        _lib.goctr_predict_dataset_calibrated.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                          C.POINTER(C.c_float)]
+        _lib.goctr_evaluate_dataset_curve_calibrated.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _cc, _cm,
+                                                                 _cp, _cb]
+        _lib.goctr_mlp_evaluate_resident_curve_calibrated.argtypes = [C.c_void_p, C.c_void_p, _cc, _cm, _cp, _cb]
         _rm, _rc, _fm, _cs = C.POINTER(RegressionMetrics), C.POINTER(RegressionCol), C.POINTER(ConfusionMetrics), C.POINTER(ClassStat)
         _mc, _mm, _cells = C.POINTER(MulticlassCfg), C.POINTER(MulticlassMetrics), C.POINTER(C.c_uint64)
         _lib.goctr_metrics_regression.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, C.c_int, _rm, _rc]
@@ -539,6 +579,7 @@ def _default(struct, symbol):
 
 default_train_cfg = _default(TrainCfg, "goctr_train_cfg_default")
 default_curve_cfg = _default(CurveCfg, "goctr_curve_cfg_default")
+default_calib_cfg = _default(CalibCfg, "goctr_calib_cfg_default")
 default_multiclass_cfg = _default(MulticlassCfg, "goctr_multiclass_cfg_default")
 default_negsample_cfg = _default(NegSampleCfg, "goctr_negsample_cfg_default")
 default_topn_cfg = _default(TopnCfg, "goctr_topn_cfg_default")

@@ -6,6 +6,7 @@
 #include <memory>
 #include <shared_mutex>
 
+#include "calibrate.h"
 #include "ctr_model.h"
 #include "metrics.h"
 #include "negsample.h"
@@ -847,6 +848,44 @@ int goctr_evaluate_dataset_curve(goctr_model* m, goctr_emb* emb, goctr_dataset* 
   std::unique_lock<std::shared_mutex> lk(m->mu); ++m->gen;
   // goctr_evaluate_dataset's predict, then the curve pipeline over the same resident scores and labels (metrics_curve.hip)
   if (predict_batches(m, emb, d, batch, 0, cdiv(d->rows, batch), true, nullptr)) return -1;
+  return metrics_curve_dev(m->yall.p, d->Y.p, d->rows, cfg, out, pts, bins, who);
+}
+
+// the three calibrated forms: goctr_predict_dataset's scoring left in m->yall, then calibrate.hip over it in device memory
+int goctr_calibrator_fit_dataset(goctr_model* m, goctr_emb* emb, goctr_dataset* d, int batch, const goctr_calib_cfg* cfg,
+                                 goctr_calibrator** out) {
+  GOCTR_ENTER_H(m);
+  const char* who = "goctr_calibrator_fit_dataset";
+  GOCTR_CHECK(m && d && out && batch > 0, "%s: bad arguments", who);
+  GOCTR_CHECK(d->has_y && d->Y.p, "%s: the dataset has no labels", who);
+  if (metrics_check_rows(d->rows, who) || calib_cfg_check(cfg, who)) return -1;
+  std::unique_lock<std::shared_mutex> lk(m->mu); ++m->gen;
+  if (predict_batches(m, emb, d, batch, 0, cdiv(d->rows, batch), true, nullptr)) return -1;
+  return calib_fit_dev<float, float>(m->yall.p, d->Y.p, d->rows, cfg, who, nullptr, nullptr, out);
+}
+
+int goctr_predict_dataset_calibrated(goctr_model* m, goctr_emb* emb, goctr_dataset* d, int batch, goctr_calibrator* h, float* y_out) {
+  GOCTR_ENTER_H(m);
+  GOCTR_CHECK(m && d && h && y_out && batch > 0, "goctr_predict_dataset_calibrated: bad arguments");
+  GOCTR_SAME_ENGINE(m, h);
+  std::unique_lock<std::shared_mutex> lk(m->mu); ++m->gen;
+  if (predict_batches(m, emb, d, batch, 0, cdiv(d->rows, batch), true, nullptr)) return -1;
+  if (calib_apply_dev(h, m->yall.p, d->rows, m->yall.p)) return -1;
+  return m->yall.download(y_out, (size_t)d->rows);
+}
+
+int goctr_evaluate_dataset_curve_calibrated(goctr_model* m, goctr_emb* emb, goctr_dataset* d, int batch, goctr_calibrator* h,
+                                            const goctr_curve_cfg* cfg, goctr_curve_metrics* out, goctr_curve_points* pts,
+                                            goctr_calib_bins* bins) {
+  GOCTR_ENTER_H(m);
+  const char* who = "goctr_evaluate_dataset_curve_calibrated";
+  GOCTR_CHECK(m && d && h && out && batch > 0, "%s: bad arguments", who);
+  GOCTR_SAME_ENGINE(m, h);
+  GOCTR_CHECK(d->has_y && d->Y.p, "%s: the dataset has no labels", who);
+  if (metrics_check_rows(d->rows, who) || metrics_curve_check(cfg, pts, bins, who)) return -1;
+  std::unique_lock<std::shared_mutex> lk(m->mu); ++m->gen;
+  if (predict_batches(m, emb, d, batch, 0, cdiv(d->rows, batch), true, nullptr)) return -1;
+  if (calib_apply_dev(h, m->yall.p, d->rows, m->yall.p)) return -1;
   return metrics_curve_dev(m->yall.p, d->Y.p, d->rows, cfg, out, pts, bins, who);
 }
 

@@ -4,6 +4,7 @@
 #include <memory>
 #include <vector>
 
+#include "calibrate.h"
 #include "metrics.h"
 #include "mlp_model.h"
 
@@ -280,6 +281,40 @@ int goctr_mlp_evaluate_resident_curve(goctr_mlp* p, const goctr_curve_cfg* cfg, 
   std::lock_guard<std::mutex> lk(p->mu);
   DevBuf<double> score;
   if (score.alloc((size_t)p->rows, false) || predict_resident64(p, score.p)) return -1;
+  return metrics_curve_dev(score.p, p->Yr.p, p->rows, cfg, out, pts, bins, who);
+}
+
+// single-output heads only, as the binary metrics
+static int calib_head_check(goctr_mlp* p, const char* who) {
+  GOCTR_CHECK(p->rows > 0, "%s: upload rows first", who);
+  GOCTR_CHECK(p->units[p->nl] == 1 && p->cfg.out_activation != GOCTR_OUT_SOFTMAX,
+              "%s: calibration needs a single-output head (this one has %d output units%s)", who, p->units[p->nl],
+              p->cfg.out_activation == GOCTR_OUT_SOFTMAX ? ", softmax" : "");
+  return metrics_check_rows(p->rows, who);
+}
+
+int goctr_mlp_calibrator_fit_resident(goctr_mlp* p, const goctr_calib_cfg* cfg, goctr_calibrator** out) {
+  GOCTR_ENTER_H(p);
+  const char* who = "goctr_mlp_calibrator_fit_resident";
+  GOCTR_CHECK(p && out, "%s: bad arguments", who);
+  if (calib_head_check(p, who) || calib_cfg_check(cfg, who)) return -1;
+  std::lock_guard<std::mutex> lk(p->mu);
+  DevBuf<double> score;
+  if (score.alloc((size_t)p->rows, false) || predict_resident64(p, score.p)) return -1;
+  return calib_fit_dev<double, float>(score.p, p->Yr.p, p->rows, cfg, who, nullptr, nullptr, out);
+}
+
+int goctr_mlp_evaluate_resident_curve_calibrated(goctr_mlp* p, goctr_calibrator* h, const goctr_curve_cfg* cfg,
+                                                 goctr_curve_metrics* out, goctr_curve_points* pts, goctr_calib_bins* bins) {
+  GOCTR_ENTER_H(p);
+  const char* who = "goctr_mlp_evaluate_resident_curve_calibrated";
+  GOCTR_CHECK(p && h && out, "%s: bad arguments", who);
+  GOCTR_SAME_ENGINE(p, h);
+  if (calib_head_check(p, who) || metrics_curve_check(cfg, pts, bins, who)) return -1;
+  std::lock_guard<std::mutex> lk(p->mu);
+  DevBuf<double> score;
+  if (score.alloc((size_t)p->rows, false) || predict_resident64(p, score.p)) return -1;
+  if (calib_apply_dev(h, score.p, p->rows, score.p)) return -1;
   return metrics_curve_dev(score.p, p->Yr.p, p->rows, cfg, out, pts, bins, who);
 }
 

@@ -1023,6 +1023,7 @@ class MLPClassifier {
       return goctr_mlp_evaluate_resident_multiclass(h_, c, m, pc, cm);
     });
   }
+  goctr_mlp* Handle() const { return h_; }   // for goctr::Calibrator
 
  private:
   goctr_mlp* h_ = nullptr;
@@ -1096,6 +1097,91 @@ class MLPRegressor {
   int ycols_ = 1;
 };
 }  // namespace mlp
+
+// Isotonic score calibration (include/goctr.h, "isotonic score calibration on the device"; no reference counterpart): the fitted
+// block table and the map of scores through it.  cfg == nullptr: the defaults (weights 1, 1; linear interpolation; no clip).
+class Calibrator {
+ public:
+  Calibrator(const Calibrator&) = delete;
+  Calibrator& operator=(const Calibrator&) = delete;
+  Calibrator(Calibrator&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  ~Calibrator() { goctr_calibrator_destroy(h_); }
+  static Calibrator Fit(const float* score, const float* y, int64_t n, const goctr_calib_cfg* cfg = nullptr) {
+    ensure_init();
+    Calibrator c;
+    check(goctr_calibrator_fit(score, y, n, cfg, &c.h_));
+    return c;
+  }
+  static Calibrator Fit(const double* score, const double* y, int64_t n, const goctr_calib_cfg* cfg = nullptr) {
+    ensure_init();
+    Calibrator c;
+    check(goctr_calibrator_fit_f64(score, y, n, cfg, &c.h_));
+    return c;
+  }
+  // model.Predict's scores of a resident dataset against its labels, on the device
+  static Calibrator FitDataset(model::CtrNet& m, goctr_dataset* d, int batchSize, goctr_emb* emb = nullptr,
+                               const goctr_calib_cfg* cfg = nullptr) {
+    Calibrator c;
+    check(goctr_calibrator_fit_dataset(m.Vm(), emb, d, batchSize, cfg, &c.h_));
+    return c;
+  }
+  // the rows MLPClassifier::Fit left resident
+  static Calibrator FitResident(mlp::MLPClassifier& p, const goctr_calib_cfg* cfg = nullptr) {
+    Calibrator c;
+    check(goctr_mlp_calibrator_fit_resident(p.Handle(), cfg, &c.h_));
+    return c;
+  }
+  // a saved table (Blocks())
+  static Calibrator FromBlocks(const std::vector<goctr_calib_block>& blocks, const goctr_calib_cfg* cfg = nullptr) {
+    ensure_init();
+    Calibrator c;
+    check(goctr_calibrator_create(blocks.data(), (int64_t)blocks.size(), cfg, &c.h_));
+    return c;
+  }
+  goctr_calib_info Info() const {
+    goctr_calib_info i{};
+    check(goctr_calibrator_info(h_, &i));
+    return i;
+  }
+  std::vector<goctr_calib_block> Blocks() const {
+    std::vector<goctr_calib_block> b((size_t)Info().blocks);
+    check(goctr_calibrator_export(h_, b.data(), (int64_t)b.size()));
+    return b;
+  }
+  std::vector<float> Apply(const std::vector<float>& score) const {
+    std::vector<float> out(score.size());
+    check(goctr_calibrator_apply(h_, score.data(), (int64_t)score.size(), out.data()));
+    return out;
+  }
+  std::vector<double> Apply(const std::vector<double>& score) const {
+    std::vector<double> out(score.size());
+    check(goctr_calibrator_apply_f64(h_, score.data(), (int64_t)score.size(), out.data()));
+    return out;
+  }
+  // model.Predict over a resident dataset, calibrated on the device (rows = the dataset's)
+  std::vector<float> PredictDataset(model::CtrNet& m, goctr_dataset* d, int64_t rows, int batchSize, goctr_emb* emb = nullptr) const {
+    std::vector<float> y((size_t)rows);
+    check(goctr_predict_dataset_calibrated(m.Vm(), emb, d, batchSize, h_, y.data()));
+    return y;
+  }
+  // model::EvaluateDatasetCurve / MLPClassifier::EvaluateResidentCurve over the calibrated scores
+  utils::CurveResult EvaluateDatasetCurve(model::CtrNet& m, goctr_dataset* d, int batchSize, goctr_emb* emb = nullptr,
+                                          const goctr_curve_cfg* cfg = nullptr, int64_t points = 0) const {
+    return utils::curveCall(cfg, points, [&](const goctr_curve_cfg* c, goctr_curve_metrics* r, goctr_curve_points* p, goctr_calib_bins* b) {
+      return goctr_evaluate_dataset_curve_calibrated(m.Vm(), emb, d, batchSize, h_, c, r, p, b);
+    });
+  }
+  utils::CurveResult EvaluateResidentCurve(mlp::MLPClassifier& p, const goctr_curve_cfg* cfg = nullptr, int64_t points = 0) const {
+    return utils::curveCall(cfg, points, [&](const goctr_curve_cfg* c, goctr_curve_metrics* r, goctr_curve_points* pt, goctr_calib_bins* b) {
+      return goctr_mlp_evaluate_resident_curve_calibrated(p.Handle(), h_, c, r, pt, b);
+    });
+  }
+  goctr_calibrator* Handle() const { return h_; }
+
+ private:
+  Calibrator() = default;
+  goctr_calibrator* h_ = nullptr;
+};
 
 namespace embedding {
 // TrainEmbedding's device half (wordemb.go:9-32): the caller owns the dictionary and passes counts + id doc

@@ -413,6 +413,41 @@ def EvaluateLeaveOneOut(model: Predictor, n_neg=99, k=10, seed=1, sample_kw=None
     return (out, ds, smp) if details else out
 
 
+def _calib_dataset(model: Predictor, samples_or_dataset):
+    """a model.Dataset as it is, or the dataset GetSample assembles from Sample keys with labels"""
+    from . import model as gm
+    if isinstance(samples_or_dataset, gm.Dataset):
+        return samples_or_dataset
+    return GetSample(model.recSys, samples_or_dataset)[0]
+
+
+def FitCalibrator(model: Predictor, samples_or_dataset, **cfg):
+    """EXTENSION (no reference counterpart): an isotonic calibrator of the model's scores, fitted on the device over labelled
+    samples (TrainSample keys, or a model.Dataset with labels such as SampleFromBehavior's) -- calibrate.IsotonicCalibrator
+    .fit_dataset; ``cfg``: goctr_calib_cfg fields.  A model trained with n_neg sampled negatives per positive (TrainImplicit)
+    over-predicts by construction: ``w_neg`` = the real negatives one sampled negative stands for undoes that."""
+    from .calibrate import IsotonicCalibrator
+    return IsotonicCalibrator.fit_dataset(model.net, _calib_dataset(model, samples_or_dataset), model.PredBatchSize,
+                                          emb=model.recSys.emb, **cfg)
+
+
+def PredictCalibrated(model: Predictor, calibrator, samples_or_dataset):
+    """the model's scores of the samples mapped through ``calibrator`` on the device (goctr_predict_dataset_calibrated): float32 [n].
+    The order of the scores is the uncalibrated one's, apart from new ties."""
+    return calibrator.predict_dataset(model.net, _calib_dataset(model, samples_or_dataset), model.PredBatchSize, emb=model.recSys.emb)
+
+
+def EvaluateCalibrated(model: Predictor, calibrator, samples_or_dataset, bins=10, threshold=0.5):
+    """what ``calibrator`` buys on one labelled dataset: {"before": CurveMetrics, "after": CurveMetrics} of the raw and of the
+    calibrated scores (goctr_evaluate_dataset_curve / _calibrated; log-loss, ne, ece and calibration_ratio move, the AUC only by
+    the ties the map adds), both computed on the device"""
+    from . import model as gm
+    ds = _calib_dataset(model, samples_or_dataset)
+    before = gm.evaluate_dataset_curve(model.net, ds, model.PredBatchSize, emb=model.recSys.emb, bins=bins, threshold=threshold)
+    after = calibrator.evaluate_dataset_curve(model.net, ds, model.PredBatchSize, emb=model.recSys.emb, bins=bins, threshold=threshold)
+    return {"before": before, "after": after}
+
+
 def BatchPredict(model: Predictor, sampleKeys):
     """rcmd.go:277-337: scores [n, 1] float32 for n Sample keys.
 

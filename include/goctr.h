@@ -1467,6 +1467,74 @@ int goctr_evaluate_dataset_curve(goctr_model* m, goctr_emb* emb, goctr_dataset* 
 int goctr_mlp_evaluate_resident_curve(goctr_mlp* p, const goctr_curve_cfg* cfg, goctr_curve_metrics* out, goctr_curve_points* pts,
                                       goctr_calib_bins* bins);
 
+/* ---------------------------------------------------------------- isotonic score calibration on the device
+ * The curve metrics above measure miscalibration (bins, ece, calibration_ratio, ne); these calls correct it: the weighted
+ * least-squares NON-DECREASING fit of the labels against the scores (isotonic regression, by pool-adjacent-violators), kept as a
+ * table of blocks, and the map of any score through that table.  A model trained on down-sampled negatives (goctr_samples_create)
+ * over-predicts by construction; w_neg undoes it.  The reference has no counterpart.  Integer arithmetic up to the last quotient:
+ * every output is defined bit for bit, and two calls on the same input return the same bytes.
+ * Rows exactly as in goctr_metrics_binary: positive iff y > 0.5; a NaN score refuses the fit (*out untouched); equal scores form
+ * one threshold group (-0 == +0); 1 <= n < 2^31.  Groups g = 0 .. G-1 here in ASCENDING score, pos_g positives, neg_g negatives.
+ * Weights: w_pos, w_neg in 1 .. 65535 (default 1, 1): a_g = w_pos pos_g, n_g = a_g + w_neg neg_g -- each sampled negative stands
+ * for w_neg real ones.  Sums stay below 2^47; means are compared exactly (128-bit cross-multiplication).
+ * Blocks: the unique partition of 0 .. G-1 into K runs of consecutive groups whose means a_j / n_j increase STRICTLY from block to
+ * block while inside a block every proper prefix of groups has a mean >= the block's: what the stack algorithm (append a group,
+ * pool the top two blocks while mean(prev) >= mean(top)) ends with, and any other maximal sequence of such merges.
+ * Per block (goctr_calib_block): lo / hi = the score of its lowest / highest group widened exactly to double (a zero is +0);
+ * num = a_j, den = n_j; rows, pos = unweighted counts; value = num / den correctly rounded.  P == 0 or N == 0 is no error: one
+ * block of value 0 or 1.
+ * Apply, for a score s with pd = (double)s:  a NaN stays that NaN (apply never refuses a score);  else j = (blocks with lo <= pd) - 1;
+ *   j == -1 -> r = value_0;   j == K-1 or pd <= hi_j -> r = value_j;   else pd lies in the gap between hi_j and lo_j+1:
+ *   GOCTR_CALIB_STEP -> r = value_j;   GOCTR_CALIB_LINEAR -> d = lo_j+1 - hi_j; d not finite -> r = value_j; else
+ *   t = (pd - hi_j) / d, r = value_j + t (value_j+1 - value_j), r = min(max(r, value_j), value_j+1), each one IEEE double
+ *   operation, nothing fused.  Then, with clip_eps > 0, r = min(max(r, clip_eps), 1 - clip_eps) (log-loss stays finite when a block
+ *   is all-positive or all-negative).  The float form returns (float)r.  The map is non-decreasing in s.
+ * Refused (-1, goctr_last_error, nothing written): NULL arguments; weights, interp, tile or clip_eps outside their ranges; handles
+ * of different engines; everything goctr_metrics_binary refuses. */
+enum { GOCTR_CALIB_STEP = 0, GOCTR_CALIB_LINEAR = 1 };
+typedef struct {
+  int32_t w_pos, w_neg;   /* 1 .. 65535 (default 1, 1) */
+  int32_t interp;         /* GOCTR_CALIB_STEP | GOCTR_CALIB_LINEAR (default) */
+  int32_t tile;           /* groups per workgroup of the fit's local pass: 0 = default, or a power of two 64 .. 4096; NO output
+                             byte depends on it (only goctr_calib_info.rounds does) */
+  double  clip_eps;       /* 0 <= clip_eps < 0.5 (default 0: no clip) */
+} goctr_calib_cfg;
+typedef struct { double lo, hi, value; uint64_t num, den; int64_t rows, pos; } goctr_calib_block;
+typedef struct {
+  int64_t n, positives, negatives, groups, blocks;   /* a table from goctr_calibrator_create: the sums of its rows / pos; groups 0 */
+  int64_t rounds;         /* global merge rounds the fit ran; diagnostic, depends on tile, not part of the defined bytes */
+} goctr_calib_info;
+typedef struct goctr_calibrator goctr_calibrator;
+
+void goctr_calib_cfg_default(goctr_calib_cfg* cfg);    /* weights 1, 1; LINEAR; tile 0; clip_eps 0 */
+/* host arrays score [n], y [n] (copied to the device); cfg NULL = the defaults */
+int  goctr_calibrator_fit(const float* score, const float* y, int64_t n, const goctr_calib_cfg* cfg, goctr_calibrator** out);
+int  goctr_calibrator_fit_f64(const double* score, const double* y, int64_t n, const goctr_calib_cfg* cfg, goctr_calibrator** out);
+/* goctr_predict_dataset's scores, left on the device, against d's resident labels: equal to goctr_calibrator_fit over them */
+int  goctr_calibrator_fit_dataset(goctr_model* m, goctr_emb* emb, goctr_dataset* d, int batch, const goctr_calib_cfg* cfg,
+                                  goctr_calibrator** out);
+/* goctr_mlp_evaluate_resident's scores (float64) against the resident Y; a softmax head is refused */
+int  goctr_mlp_calibrator_fit_resident(goctr_mlp* p, const goctr_calib_cfg* cfg, goctr_calibrator** out);
+/* a saved table (goctr_calibrator_export's blocks): only lo, hi, value and the cfg's interp / clip_eps take part in apply.  Refused:
+ * K < 1; lo / hi not ordered (lo_j <= hi_j < lo_j+1); values that decrease; a NaN */
+int  goctr_calibrator_create(const goctr_calib_block* blocks, int64_t K, const goctr_calib_cfg* cfg, goctr_calibrator** out);
+void goctr_calibrator_destroy(goctr_calibrator* h);
+int  goctr_calibrator_info(goctr_calibrator* h, goctr_calib_info* out);
+/* the first min(blocks, cap) blocks, lowest first */
+int  goctr_calibrator_export(goctr_calibrator* h, goctr_calib_block* blocks, int64_t cap);
+/* host arrays score [n], out [n] (may be the same array); n == 0 is fine */
+int  goctr_calibrator_apply(goctr_calibrator* h, const float* score, int64_t n, float* out);
+int  goctr_calibrator_apply_f64(goctr_calibrator* h, const double* score, int64_t n, double* out);
+/* goctr_predict_dataset's scores through h on the device: equal to goctr_calibrator_apply of goctr_predict_dataset's output */
+int  goctr_predict_dataset_calibrated(goctr_model* m, goctr_emb* emb, goctr_dataset* d, int batch, goctr_calibrator* h, float* y_out);
+/* goctr_evaluate_dataset_curve / goctr_mlp_evaluate_resident_curve over the CALIBRATED scores (predict, apply and the curve
+ * pipeline all in device memory): equal, byte for byte, to goctr_metrics_curve(_f64) over the calibrated predictions */
+int  goctr_evaluate_dataset_curve_calibrated(goctr_model* m, goctr_emb* emb, goctr_dataset* d, int batch, goctr_calibrator* h,
+                                             const goctr_curve_cfg* cfg, goctr_curve_metrics* out, goctr_curve_points* pts,
+                                             goctr_calib_bins* bins);
+int  goctr_mlp_evaluate_resident_curve_calibrated(goctr_mlp* p, goctr_calibrator* h, const goctr_curve_cfg* cfg,
+                                                  goctr_curve_metrics* out, goctr_curve_points* pts, goctr_calib_bins* bins);
+
 /* ---------------------------------------------------------------- multi-output metrics on the device
  * The reference's remaining metric functions, over [n][K] predictions and [n][C] probabilities: R2Score / MeanSquaredError /
  * MeanAbsoluteError (nn/metrics/regression.go) and r2Score64 (basemlp64.go:1116-1141); AccuracyScore, ConfusionMatrix,
