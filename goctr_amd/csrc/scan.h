@@ -4,6 +4,8 @@
 // (emb_plan.hip), the Huffman path offsets (huffman.hip), the metrics' label / tie / group scans (metrics.hip, metrics_group.hip)
 // and, in 64 bits, the sampler's CDF and row offsets (negsample.hip); ubcache.hip's ub_plan_kernel uses the workgroup scan alone,
 // on signed 64-bit deltas.
+// Precondition: `in` is 16-byte aligned (scan_load4 fetches four words at once from in + i, i a multiple of 4), so a caller that
+// scans a slice of a larger buffer starts it at a multiple of four words -- ctr_emb.hip rounds emb_Vw up to 4 for this.
 #pragma once
 #include <algorithm>
 

@@ -28,7 +28,8 @@ def test_hand_derived_kat(oracle):
 
 @pytest.mark.parametrize("n,vocab,mn,mx,batches", [
     (1, 1, -1, -1, 1), (2, 1, 5, -1, 1), (257, 3, 0, 0, 2), (4096, 4096, -1, -1, 1), (4097, 50, 5, 200, 3),
-    (100_000, 3000, 5, -1, 7), (1_000_003, 200_000, 5, 5000, 4)])
+    (100_000, 3000, 5, -1, 7), (1_000_003, 200_000, 5, 5000, 4),
+    (2_200_003, 300_000, 5, 5000, 3)])                                   # > 256 scan tiles: the tile-offset loop's second chunk
 def test_matches_oracle(oracle, n, vocab, mn, mx, batches):
     rng = np.random.default_rng(n)
     p = 1.0 / np.arange(1, vocab + 1) ** 1.1
