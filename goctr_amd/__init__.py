@@ -17,7 +17,7 @@ Package layout (only what the path needs):
   corpus.py        host mirror of the in-memory corpus and dictionary, backed by the device
   search.py        host mirror of feature/embedding/search (the k-NN Searcher)
   emb_io.py        go-ctr's embedding text format (host only)
-  metrics.py       host mirror of utils.RocAuc32 / RocAuc / Accuracy32 over the device metrics; grouped, curve, multi-output
+  metrics.py       host mirror of utils.RocAuc32 / RocAuc / Accuracy32 over the device metrics; grouped, curve, bootstrap, multi-output
                    and list-quality metrics
   launch.py        one process per GPU: launcher and rendezvous for the data-parallel path
   host/goctr.hpp   the C++ twin of the same surface (header only; compile-checked)

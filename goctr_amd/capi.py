@@ -113,6 +113,30 @@ class CalibInfo(C.Structure):
                 ("blocks", C.c_int64), ("rounds", C.c_int64)]
 
 
+class BootCfg(C.Structure):
+    """goctr_boot_cfg (include/goctr.h)"""
+    _fields_ = [("replicates", C.c_int32), ("chunk_rows", C.c_int32), ("rep_tile", C.c_int32), ("reserved", C.c_int32),
+                ("seed", C.c_uint64), ("level", C.c_double)]
+
+
+class BootCi(C.Structure):
+    """goctr_boot_ci (include/goctr.h)"""
+    _fields_ = [(f, C.c_double) for f in ("point", "mean", "sd", "lo", "hi")]
+
+
+class BootRep(C.Structure):
+    """goctr_boot_rep (include/goctr.h)"""
+    _fields_ = [(f, C.c_uint64) for f in ("n_w", "pos_w", "neg_w", "s_a", "s_b", "correct_a", "correct_b")] + \
+               [("ll_a", C.c_double), ("ll_b", C.c_double)]
+
+
+class BootMetrics(C.Structure):
+    """goctr_boot_metrics (include/goctr.h)"""
+    _fields_ = [(f, C.c_int64) for f in ("n", "replicates", "valid", "a_wins", "b_wins", "ties")] + \
+               [("paired", C.c_int32), ("clustered", C.c_int32), ("point_a", BinaryMetrics), ("point_b", BinaryMetrics)] + \
+               [(f, BootCi) for f in ("auc_a", "acc_a", "logloss_a", "auc_b", "acc_b", "logloss_b", "d_auc", "d_acc", "d_logloss")]
+
+
 class RegressionMetrics(C.Structure):
     """goctr_regression_metrics (include/goctr.h)"""
     _fields_ = [("n", C.c_int64), ("k", C.c_int64), ("constant_columns", C.c_int64), ("mse_uniform", C.c_double),
@@ -279,6 +303,8 @@ SYMBOLS = [
     "goctr_mlp_calibrator_fit_resident", "goctr_calibrator_create", "goctr_calibrator_destroy", "goctr_calibrator_info",
     "goctr_calibrator_export", "goctr_calibrator_apply", "goctr_calibrator_apply_f64", "goctr_predict_dataset_calibrated",
     "goctr_evaluate_dataset_curve_calibrated", "goctr_mlp_evaluate_resident_curve_calibrated",
+    "goctr_boot_cfg_default", "goctr_metrics_bootstrap", "goctr_metrics_bootstrap_f64", "goctr_evaluate_dataset_bootstrap",
+    "goctr_mlp_evaluate_resident_bootstrap", "goctr_bootstrap_weights",
     "goctr_metrics_regression", "goctr_metrics_regression_f64", "goctr_metrics_confusion", "goctr_multiclass_cfg_default",
     "goctr_metrics_multiclass", "goctr_metrics_multiclass_f64", "goctr_mlp_evaluate_resident_regression",
     "goctr_mlp_evaluate_resident_multiclass",
@@ -327,7 +353,7 @@ def load() -> C.CDLL:
                      "goctr_itemnbr_cfg_default", "goctr_mmr_cfg_default", "goctr_itemvec_destroy", "goctr_list_cfg_default",
                      "goctr_swing_cfg_default", "goctr_uservec_cfg_default", "goctr_uservec_multi_cfg_default",
                      "goctr_ivf_cfg_default", "goctr_uservec_ivf_cfg_default", "goctr_itemvec_index_destroy",
-                     "goctr_calib_cfg_default", "goctr_calibrator_destroy"):
+                     "goctr_calib_cfg_default", "goctr_calibrator_destroy", "goctr_boot_cfg_default"):
             getattr(_lib, name).restype = None
         _bm = C.POINTER(BinaryMetrics)
         _lib.goctr_metrics_binary.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, _bm]
@@ -364,6 +390,16 @@ def load() -> C.CDLL:
         _lib.goctr_evaluate_dataset_curve_calibrated.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _cc, _cm,
                                                                  _cp, _cb]
         _lib.goctr_mlp_evaluate_resident_curve_calibrated.argtypes = [C.c_void_p, C.c_void_p, _cc, _cm, _cp, _cb]
+        _bc, _bo, _br = C.POINTER(BootCfg), C.POINTER(BootMetrics), C.POINTER(BootRep)
+        _lib.goctr_boot_cfg_default.argtypes = [_bc]
+        _lib.goctr_metrics_bootstrap.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), _i32, C.c_int64,
+                                                 _bc, _bo, _br]
+        _lib.goctr_metrics_bootstrap_f64.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _i32,
+                                                     C.c_int64, _bc, _bo, _br]
+        _lib.goctr_evaluate_dataset_bootstrap.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _i32,
+                                                          C.c_int, _bc, _bo, _br]
+        _lib.goctr_mlp_evaluate_resident_bootstrap.argtypes = [C.c_void_p, C.c_void_p, _i32, _bc, _bo, _br]
+        _lib.goctr_bootstrap_weights.argtypes = [C.c_uint64, C.c_int32, C.c_int32, _i32, C.c_int64, C.POINTER(C.c_uint8)]
         _rm, _rc, _fm, _cs = C.POINTER(RegressionMetrics), C.POINTER(RegressionCol), C.POINTER(ConfusionMetrics), C.POINTER(ClassStat)
         _mc, _mm, _cells = C.POINTER(MulticlassCfg), C.POINTER(MulticlassMetrics), C.POINTER(C.c_uint64)
         _lib.goctr_metrics_regression.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, C.c_int, _rm, _rc]
@@ -580,6 +616,7 @@ def _default(struct, symbol):
 default_train_cfg = _default(TrainCfg, "goctr_train_cfg_default")
 default_curve_cfg = _default(CurveCfg, "goctr_curve_cfg_default")
 default_calib_cfg = _default(CalibCfg, "goctr_calib_cfg_default")
+default_boot_cfg = _default(BootCfg, "goctr_boot_cfg_default")
 default_multiclass_cfg = _default(MulticlassCfg, "goctr_multiclass_cfg_default")
 default_negsample_cfg = _default(NegSampleCfg, "goctr_negsample_cfg_default")
 default_topn_cfg = _default(TopnCfg, "goctr_topn_cfg_default")

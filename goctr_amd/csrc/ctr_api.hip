@@ -9,6 +9,7 @@
 #include "calibrate.h"
 #include "ctr_model.h"
 #include "metrics.h"
+#include "metrics_boot.h"
 #include "negsample.h"
 #include "ubcache.h"
 
@@ -914,6 +915,37 @@ int goctr_evaluate_dataset_grouped(goctr_model* m, goctr_emb* emb, goctr_dataset
   if (all) *all = pooled;
   *out = grouped;
   return 0;
+}
+
+// goctr_predict_dataset's scoring of each model, left in that model's own yall, then metrics_boot.hip over both columns
+int goctr_evaluate_dataset_bootstrap(goctr_model* ma, goctr_emb* ea, goctr_model* mb, goctr_emb* eb, goctr_dataset* d, int batch,
+                                     const int32_t* cluster, int by_user, const goctr_boot_cfg* cfg, goctr_boot_metrics* out,
+                                     goctr_boot_rep* reps) {
+  GOCTR_ENTER_H(ma);
+  const char* who = "goctr_evaluate_dataset_bootstrap";
+  GOCTR_CHECK(ma && d && out && batch > 0, "%s: bad arguments", who);
+  GOCTR_SAME_ENGINE(ma, mb);
+  GOCTR_CHECK(d->has_y && d->Y.p, "%s: the dataset has no labels", who);
+  GOCTR_CHECK(cluster || !by_user || d->users.p, "%s: group is NULL and the dataset keeps no users column (only "
+              "goctr_dataset_create_keys datasets do): pass the group of every row", who);
+  if (boot_check_rows(d->rows, who) || boot_cfg_check(cfg, who)) return -1;
+  // the two model locks in address order (one lock where both are the same model)
+  goctr_model* lo = mb && mb < ma ? mb : ma;
+  goctr_model* hi = mb && mb != ma ? (lo == ma ? mb : ma) : nullptr;
+  std::unique_lock<std::shared_mutex> lk0(lo->mu);
+  std::unique_lock<std::shared_mutex> lk1;
+  if (hi) lk1 = std::unique_lock<std::shared_mutex>(hi->mu);
+  ++ma->gen;
+  if (hi) ++mb->gen;
+  DevBuf<int32_t> cdev;
+  const int32_t* c = by_user ? d->users.p : nullptr;
+  if (cluster) {
+    if (cdev.alloc((size_t)d->rows, false) || cdev.upload(cluster, (size_t)d->rows)) return -1;
+    c = cdev.p;
+  }
+  if (predict_batches(ma, ea, d, batch, 0, cdiv(d->rows, batch), true, nullptr)) return -1;
+  if (hi && predict_batches(mb, eb, d, batch, 0, cdiv(d->rows, batch), true, nullptr)) return -1;
+  return metrics_bootstrap_dev<float, float>(ma->yall.p, mb ? mb->yall.p : nullptr, d->Y.p, c, d->rows, cfg, out, reps, who);
 }
 
 }  // extern "C"

@@ -126,6 +126,15 @@ __device__ __forceinline__ unsigned long long score_key(double s, bool* nan) {
   return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 
+// utils.Accuracy32: math.Round(float64(p - y)) == 0 with p - y in float32, i.e. |fl32(p - y)| < 0.5 (NaN: no hit); utils.Accuracy
+// (and the MLP's float64 head) take the difference in float64
+__device__ __forceinline__ bool hit(float p, float y) { const float d = p - y; return fabsf(d) < 0.5f; }
+__device__ __forceinline__ bool hit(double p, double y) { return fabs(p - y) < 0.5; }
+__device__ __forceinline__ bool hit(double p, float y) { return fabs(p - (double)y) < 0.5; }
+
+// a row's log-loss term: cost.go's formula; float32(1 + 1e-8) is 1.0f; no clamp
+__device__ __forceinline__ double logloss_term(double pd, double td) { return -(td * log(pd) + (1.0 - td) * log(1.0 - pd)); }
+
 // a key back to its score, widened exactly to double (the key of -0 is +0's)
 __device__ __forceinline__ double key_score(unsigned int k) {
   return (double)__uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);

@@ -37,12 +37,6 @@
 namespace goctr {
 namespace {
 
-// utils.Accuracy32: math.Round(float64(p - y)) == 0 with p - y in float32, i.e. |fl32(p - y)| < 0.5 (NaN: no hit); utils.Accuracy
-// (and the MLP's float64 head) take the difference in float64
-__device__ __forceinline__ bool hit(float p, float y) { const float d = p - y; return fabsf(d) < 0.5f; }
-__device__ __forceinline__ bool hit(double p, double y) { return fabs(p - y) < 0.5; }
-__device__ __forceinline__ bool hit(double p, float y) { return fabs(p - (double)y) < 0.5; }
-
 // the key build's sums per workgroup
 struct MetricsPart {
   unsigned long long pos, correct, nan;
@@ -64,7 +58,7 @@ __global__ __launch_bounds__(MB) void metrics_key_kernel(const TS* score, const 
     const K k = score_key(p, &isnan);
     const bool positive = t > (TL)0.5;                 // a NaN label is negative
     const double pd = (double)p, td = (double)t;
-    a.ll += -(td * log(pd) + (1.0 - td) * log(1.0 - pd));   // cost.go's formula; float32(1 + 1e-8) is 1.0f; no clamp
+    a.ll += logloss_term(pd, td);
     a.pos += positive ? 1 : 0;
     a.correct += hit(p, t) ? 1 : 0;
     a.nan += isnan ? 1 : 0;

@@ -6,6 +6,7 @@
 
 #include "calibrate.h"
 #include "metrics.h"
+#include "metrics_boot.h"
 #include "mlp_model.h"
 
 // a padded flat parameter buffer (W or G) in the packed [ b_i | W_i ]... order of goctr_mlp_set_params
@@ -316,6 +317,38 @@ int goctr_mlp_evaluate_resident_curve_calibrated(goctr_mlp* p, goctr_calibrator*
   if (score.alloc((size_t)p->rows, false) || predict_resident64(p, score.p)) return -1;
   if (calib_apply_dev(h, score.p, p->rows, score.p)) return -1;
   return metrics_curve_dev(score.p, p->Yr.p, p->rows, cfg, out, pts, bins, who);
+}
+
+int goctr_mlp_evaluate_resident_bootstrap(goctr_mlp* p, goctr_mlp* q, const int32_t* cluster, const goctr_boot_cfg* cfg,
+                                          goctr_boot_metrics* out, goctr_boot_rep* reps) {
+  GOCTR_ENTER_H(p);
+  const char* who = "goctr_mlp_evaluate_resident_bootstrap";
+  GOCTR_CHECK(p && out, "%s: bad arguments", who);
+  GOCTR_SAME_ENGINE(p, q);
+  goctr_mlp* both[2] = {p, q && q != p ? q : nullptr};
+  for (goctr_mlp* h : both) {
+    if (!h) continue;
+    GOCTR_CHECK(h->rows > 0, "%s: upload rows first", who);
+    GOCTR_CHECK(h->units[h->nl] == 1 && h->cfg.out_activation != GOCTR_OUT_SOFTMAX,
+                "%s: binary metrics need a single-output head (this one has %d output units%s)", who, h->units[h->nl],
+                h->cfg.out_activation == GOCTR_OUT_SOFTMAX ? ", softmax" : "");
+  }
+  GOCTR_CHECK(!q || q->rows == p->rows, "%s: the second model holds %lld resident rows, the first %lld", who,
+              (long long)(q ? q->rows : 0), (long long)p->rows);
+  if (boot_check_rows(p->rows, who) || boot_cfg_check(cfg, who)) return -1;
+  // the two model locks in address order
+  goctr_mlp* lo = both[1] && both[1] < p ? both[1] : p;
+  goctr_mlp* hi = both[1] ? (lo == p ? both[1] : p) : nullptr;
+  std::unique_lock<std::mutex> lk0(lo->mu);
+  std::unique_lock<std::mutex> lk1;
+  if (hi) lk1 = std::unique_lock<std::mutex>(hi->mu);
+  DevBuf<double> sp, sq;
+  DevBuf<int32_t> cdev;
+  if (cluster && (cdev.alloc((size_t)p->rows, false) || cdev.upload(cluster, (size_t)p->rows))) return -1;
+  if (sp.alloc((size_t)p->rows, false) || predict_resident64(p, sp.p)) return -1;
+  if (both[1] && (sq.alloc((size_t)p->rows, false) || predict_resident64(q, sq.p))) return -1;
+  const double* b = !q ? nullptr : (q == p ? sp.p : sq.p);
+  return metrics_bootstrap_dev<double, float>(sp.p, b, p->Yr.p, cluster ? cdev.p : nullptr, p->rows, cfg, out, reps, who);
 }
 
 int goctr_mlp_evaluate_resident_grouped(goctr_mlp* p, const int32_t* group, int k, goctr_binary_metrics* all,

@@ -104,6 +104,48 @@ inline goctr_group_metrics GroupedMetrics(const double* score, const double* y, 
   if (perGroup) perGroup->resize((size_t)m.groups);
   return m;
 }
+// bootstrap intervals and paired comparison (goctr_metrics_bootstrap): `replicates` weighted re-evaluations of the AUC, accuracy and
+// log-loss out of one sort per column.  m: the head with the nine goctr_boot_ci; reps: every replicate's integers when asked for
+struct BootResult {
+  goctr_boot_metrics m{};
+  std::vector<goctr_boot_rep> reps;
+};
+template <class Call>
+inline BootResult bootCall(const goctr_boot_cfg* cfg, bool reps, Call call) {
+  goctr_boot_cfg c;
+  goctr_boot_cfg_default(&c);
+  if (cfg) c = *cfg;
+  BootResult r;
+  if (reps) r.reps.resize((size_t)std::min(std::max(c.replicates, 1), 4096));
+  check(call(&c, &r.m, reps ? r.reps.data() : nullptr));
+  return r;
+}
+// is model a better than model b on these rows, or is the gap noise?  Both columns get the same weights (a paired bootstrap):
+// m.d_auc / d_acc / d_logloss are the intervals of a - b, m.a_wins / b_wins / ties the replicates' verdicts.  cluster (may be
+// null): the resample unit of every row -- its user: whole users are drawn
+inline BootResult CompareModels(const float* score_a, const float* score_b, const float* y, int64_t n, const int32_t* cluster = nullptr,
+                                const goctr_boot_cfg* cfg = nullptr, bool reps = false) {
+  ensure_init();
+  return bootCall(cfg, reps, [&](const goctr_boot_cfg* c, goctr_boot_metrics* m, goctr_boot_rep* r) {
+    return goctr_metrics_bootstrap(score_a, score_b, y, cluster, n, c, m, r);
+  });
+}
+inline BootResult CompareModels(const double* score_a, const double* score_b, const double* y, int64_t n,
+                                const int32_t* cluster = nullptr, const goctr_boot_cfg* cfg = nullptr, bool reps = false) {
+  ensure_init();
+  return bootCall(cfg, reps, [&](const goctr_boot_cfg* c, goctr_boot_metrics* m, goctr_boot_rep* r) {
+    return goctr_metrics_bootstrap_f64(score_a, score_b, y, cluster, n, c, m, r);
+  });
+}
+// the intervals of one column
+inline BootResult Bootstrap(const float* score, const float* y, int64_t n, const int32_t* cluster = nullptr,
+                            const goctr_boot_cfg* cfg = nullptr, bool reps = false) {
+  return CompareModels(score, nullptr, y, n, cluster, cfg, reps);
+}
+inline BootResult Bootstrap(const double* score, const double* y, int64_t n, const int32_t* cluster = nullptr,
+                            const goctr_boot_cfg* cfg = nullptr, bool reps = false) {
+  return CompareModels(score, nullptr, y, n, cluster, cfg, reps);
+}
 // the curve pipeline (goctr_metrics_curve): BinaryMetrics' figures as .base plus tp / fp / precision / recall / f1 at cfg.threshold,
 // average precision, KS, the F1-optimal cut and calibration bins; with `points` >= 2 also binaryClfCurve's arrays (every group, or
 // an even decimation down to `points` of them)
@@ -311,6 +353,19 @@ inline goctr_group_metrics EvaluateDatasetGrouped(CtrNet& m, goctr_dataset* d, i
   goctr_group_metrics r{};
   check(goctr_evaluate_dataset_grouped(m.Vm(), emb, d, batchSize, group, k, all, &r));
   return r;
+}
+// the same scores of model a (and of b, or null) through the bootstrap (goctr_evaluate_dataset_bootstrap): cluster [rows] or null --
+// then byUser takes the users a goctr_dataset_create_keys dataset keeps resident, and without it rows are drawn
+inline utils::BootResult CompareModels(CtrNet& a, CtrNet* b, goctr_dataset* d, int batchSize, goctr_emb* emb_a = nullptr,
+                                       goctr_emb* emb_b = nullptr, const int32_t* cluster = nullptr, bool byUser = true,
+                                       const goctr_boot_cfg* cfg = nullptr, bool reps = false) {
+  return utils::bootCall(cfg, reps, [&](const goctr_boot_cfg* c, goctr_boot_metrics* m, goctr_boot_rep* r) {
+    return goctr_evaluate_dataset_bootstrap(a.Vm(), emb_a, b ? b->Vm() : nullptr, emb_b, d, batchSize, cluster, byUser ? 1 : 0, c, m, r);
+  });
+}
+inline utils::BootResult Bootstrap(CtrNet& a, goctr_dataset* d, int batchSize, goctr_emb* emb = nullptr, const int32_t* cluster = nullptr,
+                                   bool byUser = true, const goctr_boot_cfg* cfg = nullptr, bool reps = false) {
+  return CompareModels(a, nullptr, d, batchSize, emb, nullptr, cluster, byUser, cfg, reps);
 }
 }  // namespace model
 
@@ -1379,5 +1434,12 @@ class Searcher {
   goctr_searcher* h_ = nullptr;
 };
 }  // namespace search
+
+// goctr::Bootstrap / goctr::CompareModels: the host-array forms (utils) and the dataset forms (model), by their arguments
+using utils::BootResult;
+using utils::Bootstrap;
+using utils::CompareModels;
+using model::Bootstrap;
+using model::CompareModels;
 
 }  // namespace goctr

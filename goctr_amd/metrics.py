@@ -363,6 +363,142 @@ def Accuracy32(pred, y) -> np.float32:
     return accuracy32_from_hits(m.correct, m.n)
 
 
+# ---------------------------------------------------------------- bootstrap intervals and paired comparison (goctr_metrics_bootstrap)
+BOOT_REP_DTYPE = np.dtype([(f, np.uint64) for f in ("n_w", "pos_w", "neg_w", "s_a", "s_b", "correct_a", "correct_b")] +
+                          [("ll_a", np.float64), ("ll_b", np.float64)])                     # goctr_boot_rep
+BOOT_MAX_REPLICATES, BOOT_MAX_ROWS = 4096, 1 << 28
+
+
+@dataclass(frozen=True)
+class BootCI:
+    """goctr_boot_ci: the figure of the unweighted rows and the mean, sample deviation and percentile interval of its valid
+    replicates"""
+    point: float
+    mean: float
+    sd: float
+    lo: float
+    hi: float
+
+
+@dataclass(frozen=True, eq=False)
+class BootstrapMetrics:
+    """goctr_boot_metrics: `valid` of `replicates` replicates had both classes; point_a / point_b are binary_metrics of each
+    column (point_b None without a second column); auc_* / acc_* / logloss_* the intervals per model, d_* those of the paired
+    difference a - b; a_wins / b_wins / ties count the sign of the AUC difference over the valid replicates.  reps: the
+    replicates' integers and sums (BOOT_REP_DTYPE [replicates]) or None.  raw: the C struct's bytes."""
+    n: int
+    replicates: int
+    valid: int
+    a_wins: int
+    b_wins: int
+    ties: int
+    paired: bool
+    clustered: bool
+    point_a: BinaryMetrics
+    point_b: BinaryMetrics | None
+    auc_a: BootCI
+    acc_a: BootCI
+    logloss_a: BootCI
+    auc_b: BootCI
+    acc_b: BootCI
+    logloss_b: BootCI
+    d_auc: BootCI
+    d_acc: BootCI
+    d_logloss: BootCI
+    reps: np.ndarray | None
+    raw: bytes
+
+    def tobytes(self) -> bytes:
+        """every field and replicate, as the device call returned them"""
+        return self.raw + (b"" if self.reps is None else self.reps.tobytes())
+
+
+BOOT_CI_FIELDS = ("auc_a", "acc_a", "logloss_a", "auc_b", "acc_b", "logloss_b", "d_auc", "d_acc", "d_logloss")
+
+
+def make_boot_cfg(replicates=200, seed=0, level=0.95, chunk_rows=0, rep_tile=0) -> capi.BootCfg:
+    """a goctr_boot_cfg from the arguments every bootstrap call takes; the ranges are checked here, before any device work"""
+    B, cr, rt, lv = int(replicates), int(chunk_rows), int(rep_tile), float(level)
+    if not 1 <= B <= BOOT_MAX_REPLICATES:
+        raise ValueError(f"replicates must be 1 .. {BOOT_MAX_REPLICATES}, got {B}")
+    if cr and not (256 <= cr <= 65536 and cr % 256 == 0):
+        raise ValueError(f"chunk_rows must be 0 or a multiple of 256 in 256 .. 65536, got {cr}")
+    if not 0 <= rt <= 64:
+        raise ValueError(f"rep_tile must be 0 .. 64, got {rt}")
+    if not 0.0 < lv < 1.0:
+        raise ValueError(f"level must be inside (0, 1), got {lv}")
+    if not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("seed must fit 64 unsigned bits")
+    return capi.BootCfg(B, cr, rt, 0, int(seed), lv)
+
+
+class BootCall:
+    """the cfg / out / reps arguments of one goctr_*_bootstrap call, and its result"""
+
+    def __init__(self, reps=False, **cfg):
+        self.cfg = make_boot_cfg(**cfg)
+        self.out = capi.BootMetrics()
+        self.reps = np.zeros(self.cfg.replicates, BOOT_REP_DTYPE) if reps else None
+
+    def args(self):
+        return (C.byref(self.cfg), C.byref(self.out),
+                None if self.reps is None else self.reps.ctypes.data_as(C.POINTER(capi.BootRep)))
+
+    def result(self) -> BootstrapMetrics:
+        o = self.out
+        ci = [BootCI(*(getattr(getattr(o, f), k) for k, _ in capi.BootCi._fields_)) for f in BOOT_CI_FIELDS]
+        return BootstrapMetrics(o.n, o.replicates, o.valid, o.a_wins, o.b_wins, o.ties, bool(o.paired), bool(o.clustered),
+                                BinaryMetrics.from_c(o.point_a), BinaryMetrics.from_c(o.point_b) if o.paired else None, *ci,
+                                self.reps, bytes(o))
+
+
+def cluster_ids(cluster, n) -> np.ndarray:
+    """the resample unit of n rows (class_ids); a negative id is refused here as the device refuses it"""
+    g = class_ids(cluster, n, "cluster ids", "scores")
+    if g.size and int(g.min()) < 0:
+        raise ValueError("cluster ids must be >= 0")
+    return g
+
+
+def bootstrap_metrics(score, y, score_b=None, cluster=None, replicates=200, seed=0, level=0.95, reps=False, chunk_rows=0,
+                      rep_tile=0) -> BootstrapMetrics:
+    """`replicates` bootstrap replicates of the AUC, accuracy and log-loss of `score` (and of `score_b`, and of their paired
+    difference) against `y` on the device, out of one sort per column (goctr_metrics_bootstrap for float32 scores, else _f64).
+    cluster: the resample unit of every row (its user: whole users are drawn); None draws rows.  Both columns get the same
+    weights.  reps: also every replicate's integers.  chunk_rows / rep_tile steer the device pass and change no output byte."""
+    fn, ty, dt = _abi(score, "metrics_bootstrap")
+    s, t = _score_label(score, y, dt)
+    if not 1 <= s.size <= BOOT_MAX_ROWS:
+        raise ValueError(f"1 .. 2^28 rows are accepted, got {s.size}")
+    sb = None
+    if score_b is not None:
+        sb = np.ascontiguousarray(score_b, dt).ravel()
+        if sb.size != s.size:
+            raise ValueError(f"{s.size} scores but {sb.size} scores of the second model")
+    g = None if cluster is None else cluster_ids(cluster, s.size)
+    call = BootCall(reps, replicates=replicates, seed=seed, level=level, chunk_rows=chunk_rows, rep_tile=rep_tile)
+    capi.check(fn(capi.ptr(s, ty), capi.ptr(sb, ty), capi.ptr(t, ty), capi.ptr(g, C.c_int32), s.size, *call.args()))
+    return call.result()
+
+
+def bootstrap_weights(units, seed=0, b0=0, nb=1) -> np.ndarray:
+    """the weights of replicates b0 .. b0 + nb - 1 for `units`, computed by the kernels' own device function
+    (goctr_bootstrap_weights): uint8 [nb][n]"""
+    u = np.asarray(units).ravel()
+    if not 1 <= u.size <= BOOT_MAX_ROWS:
+        raise ValueError(f"1 .. 2^28 units are accepted, got {u.size}")
+    b0, nb = int(b0), int(nb)
+    if b0 < 0 or nb < 1 or b0 + nb > BOOT_MAX_REPLICATES:
+        raise ValueError(f"replicates b0 .. b0 + nb - 1 must lie inside 0 .. {BOOT_MAX_REPLICATES - 1}")
+    if not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("seed must fit 64 unsigned bits")
+    g = class_ids(u, u.size, "unit ids", "units")
+    w = np.zeros((nb, g.size), np.uint8)
+    capi.check(capi.load().goctr_bootstrap_weights(C.c_uint64(int(seed)), b0, nb, capi.ptr(g, C.c_int32), g.size,
+                                                   capi.ptr(w, C.c_uint8)))
+    return w
+
+
 # ---------------------------------------------------------------- multi-output metrics (goctr_metrics_regression / _confusion / _multiclass)
 REGRESSION_COL_DTYPE = np.dtype([(f, np.float64) for f, _ in capi.RegressionCol._fields_])          # goctr_regression_col
 CLASS_STAT_DTYPE = np.dtype([("support", np.int64), ("predicted", np.int64), ("tp", np.int64), ("precision", np.float64),

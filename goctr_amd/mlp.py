@@ -274,6 +274,23 @@ class _BaseMLP:
         gm = GroupMetrics.from_c(out)
         return (BinaryMetrics.from_c(allm), gm) if pooled else gm
 
+    def EvaluateResidentBootstrap(self, other=None, cluster=None, reps=False, **cfg):
+        """EvaluateResident's scores (and those of `other`, a second model holding as many resident rows: a paired comparison)
+        through the bootstrap (goctr_mlp_evaluate_resident_bootstrap): a metrics.BootstrapMetrics against THIS model's resident Y.
+        cluster: the resample unit of every resident row, or None (rows are drawn).  ``cfg``: replicates, seed, level, chunk_rows,
+        rep_tile.  Single-output heads only."""
+        from .metrics import BootCall, cluster_ids
+        call = BootCall(reps, **cfg)
+        g = None
+        if cluster is not None:
+            rows = getattr(self, "_resident_rows", None)
+            if rows is None:
+                raise ValueError("EvaluateResidentBootstrap: upload() the rows first (the cluster column is matched against them)")
+            g = cluster_ids(cluster, rows)
+        capi.check(capi.load().goctr_mlp_evaluate_resident_bootstrap(self._h, other._h if other is not None else None,
+                                                                     capi.ptr(g, C.c_int32), *call.args()))
+        return call.result()
+
     def EvaluateResidentRegression(self):
         """every column of the head over the resident rows against the resident Y, on the device
         (goctr_mlp_evaluate_resident_regression): a metrics.RegressionMetrics.  Any head."""

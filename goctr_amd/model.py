@@ -520,6 +520,21 @@ def evaluate_dataset_grouped(m: _CtrNet, ds: Dataset, batch, group=None, k=10, e
     return (BinaryMetrics.from_c(allm), gm) if pooled else gm
 
 
+def evaluate_dataset_bootstrap(m: _CtrNet, ds: Dataset, batch, m_b: _CtrNet | None = None, cluster=None, by_user=True,
+                               emb: EmbeddingTable | None = None, emb_b: EmbeddingTable | None = None, reps=False, **cfg):
+    """predict_dataset's scores of `m` (and of `m_b`: a paired comparison over the same rows), left on the device, through the
+    bootstrap (goctr_evaluate_dataset_bootstrap): a metrics.BootstrapMetrics.  cluster: the resample unit of every row; None with
+    by_user: the users a Dataset.keys dataset keeps resident (whole users are drawn); None without: rows are drawn.
+    ``cfg``: replicates, seed, level, chunk_rows, rep_tile."""
+    from .metrics import BootCall, cluster_ids
+    call = BootCall(reps, **cfg)
+    g = None if cluster is None else cluster_ids(cluster, ds.rows)
+    capi.check(capi.load().goctr_evaluate_dataset_bootstrap(m._h, emb._h if emb else None, m_b._h if m_b is not None else None,
+                                                            emb_b._h if emb_b else None, ds._h, C.c_int(batch),
+                                                            capi.ptr(g, C.c_int32), C.c_int(1 if by_user else 0), *call.args()))
+    return call.result()
+
+
 def predict_steps(m: _CtrNet, ds: Dataset, batch, n_batches, first_batch=0, emb: EmbeddingTable | None = None):
     capi.check(capi.load().goctr_predict_steps(m._h, emb._h if emb else None, ds._h, C.c_int(batch),
                                                C.c_int64(first_batch), C.c_int(n_batches)))

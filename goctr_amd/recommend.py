@@ -448,6 +448,26 @@ def EvaluateCalibrated(model: Predictor, calibrator, samples_or_dataset, bins=10
     return {"before": before, "after": after}
 
 
+def EvaluateBootstrap(model: Predictor, samples_or_dataset, by_user=True, **cfg):
+    """EXTENSION (no reference counterpart): bootstrap intervals around the model's AUC, accuracy and log-loss on labelled samples
+    (TrainSample keys, or a model.Dataset with labels), on the device -- a metrics.BootstrapMetrics.  by_user: whole users are
+    resampled (the rows of one user are correlated), taken from the users a keys dataset keeps resident; False resamples rows.
+    ``cfg``: replicates, seed, level, reps, cluster, chunk_rows, rep_tile."""
+    return CompareModels(model, None, samples_or_dataset, by_user=by_user, **cfg)
+
+
+def CompareModels(model_a: Predictor, model_b: Predictor | None, samples_or_dataset, by_user=True, **cfg):
+    """EXTENSION: is model_a better than model_b on these samples, or is the gap noise?  A paired bootstrap of both models over the
+    same rows with the same weights (goctr_evaluate_dataset_bootstrap): the BootstrapMetrics' d_auc / d_acc / d_logloss are the
+    intervals of a - b, a_wins / b_wins / ties the replicates' verdicts.  Both models score the dataset model_a's recSys
+    assembles."""
+    from . import model as gm
+    ds = _calib_dataset(model_a, samples_or_dataset)
+    return gm.evaluate_dataset_bootstrap(model_a.net, ds, model_a.PredBatchSize, m_b=model_b.net if model_b is not None else None,
+                                         by_user=by_user, emb=model_a.recSys.emb,
+                                         emb_b=model_b.recSys.emb if model_b is not None else None, **cfg)
+
+
 def BatchPredict(model: Predictor, sampleKeys):
     """rcmd.go:277-337: scores [n, 1] float32 for n Sample keys.
 

@@ -1535,6 +1535,71 @@ int  goctr_evaluate_dataset_curve_calibrated(goctr_model* m, goctr_emb* emb, goc
 int  goctr_mlp_evaluate_resident_curve_calibrated(goctr_mlp* p, goctr_calibrator* h, const goctr_curve_cfg* cfg,
                                                   goctr_curve_metrics* out, goctr_curve_points* pts, goctr_calib_bins* bins);
 
+/* ---------------------------------------------------------------- bootstrap confidence intervals and paired model comparison
+ * Is model A better than model B, or is the gap noise?  B bootstrap replicates of the pooled AUC, accuracy and log-loss of one
+ * or two columns of scores over the same rows, out of ONE sort per column: a replicate is the weighted metric (the reference's
+ * sampleWeight of ROCAUCScore, nn/metrics/ranking.go:106) with integer Poisson(1) weights that are regenerated from a counter
+ * hash and never stored.  All integer up to the final quotients (DESIGN.md 4.9 states every definition):
+ *   unit of row i     c = cluster[i] (int32 >= 0, the user of the row: whole users are resampled) or c = i without clusters;
+ *                     both columns get the SAME weights (a paired bootstrap)
+ *   weight of unit c in replicate b (0 <= b < B), in uint64 arithmetic:
+ *                     z = seed + 0x9E3779B97F4A7C15 * ((((uint64)(b >> 1)) << 32 | (uint32)c) + 1)
+ *                     z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;  z *= 0x94D049BB133111EB;  z ^= z >> 31
+ *                     u = (b & 1) ? (uint32)z : (uint32)(z >> 32);   w = #{ k in 0..12 : u >= T[k] },
+ *                     T[k] = floor(2^32 sum_{j<=k} e^-1 / j!) = 5e2d58d8 bc5ab1b1 eb715e1d fb239797 ff1025f5 ffd90f3b fffa8b71
+ *                     ffff540c ffffed1f fffffe21 ffffffd4 fffffffc ffffffff   (w <= 13)
+ *   per replicate (goctr_boot_rep), positives and hits as goctr_metrics_binary counts them:
+ *                     n_w = sum w, pos_w, neg_w;  correct_m = sum w hit;  ll_m = sum over w > 0 of (double)w * (the row's
+ *                     log-loss term), the product formed before any add, summed in the metrics' fixed order over a grid that
+ *                     depends on n alone;  s_m = sum over m's threshold groups of negw_g (2 posw_above_g + posw_g)
+ *   a replicate is VALID iff pos_w > 0 and neg_w > 0; its values: auc = s / (2 pos_w neg_w) and acc = correct / n_w correctly
+ *                     rounded, logloss = ll / n_w; deltas: d_auc = +-(|s_a - s_b| / den) rounded once, d_acc the same over correct,
+ *                     d_logloss = ll_a / n_w - ll_b / n_w;  a_wins / b_wins / ties count the sign of s_a - s_b
+ *   summaries (goctr_boot_ci) over the V valid replicates in ascending b: point = the figure of the unweighted rows; mean = the
+ *                     left-to-right double sum / V; sd = the two-pass sample deviation (divisor V - 1; NaN for V < 2);
+ *                     lo = v[k], hi = v[V - 1 - k] of the sorted values, k = floor(((1 - level) / 2) V) in double (NaN for V = 0);
+ *                     a NaN among the valid values makes all four NaN.  Without score_b every field of model b and of the
+ *                     deltas is 0 (integers, point_b) or NaN (goctr_boot_ci).
+ * 1 <= n <= 2^28 (so every sum of weights is < 2^32 and every s < 2^63).  Refused with -1, *out and reps untouched: a NaN score
+ * in either column, a negative cluster id, n out of range, a bad cfg.  chunk_rows and rep_tile steer the sorted pass only: no
+ * output byte depends on them. */
+typedef struct {
+  int32_t  replicates;   /* B: 1 .. 4096 (default 200) */
+  int32_t  chunk_rows;   /* sorted rows per workgroup of the sorted pass: 0 = default, else a multiple of 256 in 256 .. 65536 */
+  int32_t  rep_tile;     /* replicates per sorted pass: 0 = default, else 1 .. 64 */
+  int32_t  reserved;     /* 0 */
+  uint64_t seed;         /* default 0 */
+  double   level;        /* 0 < level < 1 (default 0.95) */
+} goctr_boot_cfg;
+typedef struct { double point, mean, sd, lo, hi; } goctr_boot_ci;
+typedef struct { uint64_t n_w, pos_w, neg_w, s_a, s_b, correct_a, correct_b; double ll_a, ll_b; } goctr_boot_rep;
+typedef struct {
+  int64_t n, replicates, valid, a_wins, b_wins, ties;
+  int32_t paired, clustered;
+  goctr_binary_metrics point_a, point_b;          /* goctr_metrics_binary's bytes for each model */
+  goctr_boot_ci auc_a, acc_a, logloss_a, auc_b, acc_b, logloss_b, d_auc, d_acc, d_logloss;
+} goctr_boot_metrics;
+
+void goctr_boot_cfg_default(goctr_boot_cfg* cfg);
+/* host arrays score_a, y [n]; score_b [n] or NULL (one model); cluster [n] or NULL (every row its own unit); reps [B] or NULL */
+int goctr_metrics_bootstrap(const float* score_a, const float* score_b, const float* y, const int32_t* cluster, int64_t n,
+                            const goctr_boot_cfg* cfg, goctr_boot_metrics* out, goctr_boot_rep* reps);
+int goctr_metrics_bootstrap_f64(const double* score_a, const double* score_b, const double* y, const int32_t* cluster, int64_t n,
+                                const goctr_boot_cfg* cfg, goctr_boot_metrics* out, goctr_boot_rep* reps);
+/* goctr_predict_dataset's scoring of each model, left in that model's own device buffer, against d's resident labels; mb NULL:
+ * one model.  cluster: host [rows], or NULL -- then by_user = 1 takes the resident `users` column of a goctr_dataset_create_keys
+ * dataset (refused where the dataset keeps none) and by_user = 0 resamples rows.  Both models on one engine. */
+int goctr_evaluate_dataset_bootstrap(goctr_model* ma, goctr_emb* ea, goctr_model* mb, goctr_emb* eb, goctr_dataset* d, int batch,
+                                     const int32_t* cluster, int by_user, const goctr_boot_cfg* cfg, goctr_boot_metrics* out,
+                                     goctr_boot_rep* reps);
+/* goctr_mlp_evaluate_resident's scores of p (and of q, or NULL) against p's resident Y; q's resident row count must equal p's;
+ * cluster: host [resident rows] or NULL; a softmax head is refused */
+int goctr_mlp_evaluate_resident_bootstrap(goctr_mlp* p, goctr_mlp* q, const int32_t* cluster, const goctr_boot_cfg* cfg,
+                                          goctr_boot_metrics* out, goctr_boot_rep* reps);
+/* the weights of replicates b0 .. b0 + nb - 1 (0 <= b0, b0 + nb <= 4096) for the units [n] (host), by the kernels' own device
+ * function: w [nb][n] (host).  The validation output for the weights. */
+int goctr_bootstrap_weights(uint64_t seed, int32_t b0, int32_t nb, const int32_t* units, int64_t n, uint8_t* w);
+
 /* ---------------------------------------------------------------- multi-output metrics on the device
  * The reference's remaining metric functions, over [n][K] predictions and [n][C] probabilities: R2Score / MeanSquaredError /
  * MeanAbsoluteError (nn/metrics/regression.go) and r2Score64 (basemlp64.go:1116-1141); AccuracyScore, ConfusionMatrix,
