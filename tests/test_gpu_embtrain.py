@@ -196,10 +196,14 @@ def test_one_step_matches_oracle_at_cfg4_batch_size(oracle, kind):
     assert np.array_equal(got[~touched], E[~touched])
 
 
-def test_one_step_matches_oracle_large_vocabulary(oracle):
-    """same check as test_one_step_matches_oracle with V >> B (T+1): the in-place path for single ids is on"""
+@pytest.mark.parametrize("D", [16, 24])
+def test_one_step_matches_oracle_large_vocabulary(oracle, D):
+    """same check as test_one_step_matches_oracle with V >> B (T+1).  D = 16 takes the id-major plan path (launch_emb_train returns at
+    m->plan.valid, long before `singles` is computed): a plan whose slots are nearly all runs of one pair, next to a block of heavily
+    repeated ids.  D = 24 is outside the plan's list for DIN, so it takes the atomics path, and there V > B (T+1) switches the
+    in-place path for single ids on (emb_mark2_kernel, p + 1 marks, emb_grad_kernel<32,1> writing the row itself)"""
     from goctr_amd import capi, model as gm
-    U, Cc, V, B, T, D = 52, 53, 60000, 256, 10, 16
+    U, Cc, V, B, T = 52, 53, 60000, 256, 10
     rows = B - 11
     om, m, E, ub, items, uf, cf, y = _setup(oracle, "din", 0, U, T, D, Cc, V, rows, seed=77)
     ub[5:40] = (ub[5:40] % 50)                                          # plus a block of heavily repeated ids
