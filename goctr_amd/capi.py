@@ -217,6 +217,17 @@ class SwingCfg(C.Structure):
                 ("min_pairs", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64), ("pair_budget", C.c_int64)]
 
 
+class WalkGraphCfg(C.Structure):
+    """goctr_walkgraph_cfg (include/goctr.h)"""
+    _fields_ = [("max_len", C.c_int32), ("reserved", C.c_int32), ("ts_lo", C.c_int64), ("ts_hi", C.c_int64)]
+
+
+class WalkCfg(C.Structure):
+    """goctr_walk_cfg (include/goctr.h)"""
+    _fields_ = [("n_walks", C.c_int32), ("n_steps", C.c_int32), ("boost", C.c_int32), ("min_visits", C.c_int32),
+                ("seed", C.c_uint64), ("reserved", C.c_int64)]
+
+
 class MmrCfg(C.Structure):
     """goctr_mmr_cfg (include/goctr.h)"""
     _fields_ = [("k", C.c_int32), ("pool", C.c_int32), ("lambda_q", C.c_int32), ("max_per_group", C.c_int32)]
@@ -323,6 +334,8 @@ SYMBOLS = [
     "goctr_itemvec_export", "goctr_rerank_mmr", "goctr_recommend_blend_mmr",
     "goctr_list_cfg_default", "goctr_metrics_lists",
     "goctr_swing_cfg_default", "goctr_itemcf_build_swing",
+    "goctr_walkgraph_cfg_default", "goctr_walkgraph_build", "goctr_walkgraph_destroy", "goctr_walkgraph_info", "goctr_walkgraph_export",
+    "goctr_walk_cfg_default", "goctr_walk_recall", "goctr_recommend_walk", "goctr_recommend_blend_walk",
     "goctr_uservec_cfg_default", "goctr_uservec_recall", "goctr_recommend_uservec", "goctr_recommend_blend_uservec",
     "goctr_uservec_multi_cfg_default", "goctr_uservec_interests", "goctr_uservec_recall_multi", "goctr_recommend_uservec_multi",
     "goctr_ivf_cfg_default", "goctr_itemvec_index_build", "goctr_itemvec_index_destroy", "goctr_itemvec_index_info",
@@ -353,7 +366,8 @@ def load() -> C.CDLL:
                      "goctr_itemnbr_cfg_default", "goctr_mmr_cfg_default", "goctr_itemvec_destroy", "goctr_list_cfg_default",
                      "goctr_swing_cfg_default", "goctr_uservec_cfg_default", "goctr_uservec_multi_cfg_default",
                      "goctr_ivf_cfg_default", "goctr_uservec_ivf_cfg_default", "goctr_itemvec_index_destroy",
-                     "goctr_calib_cfg_default", "goctr_calibrator_destroy", "goctr_boot_cfg_default"):
+                     "goctr_calib_cfg_default", "goctr_calibrator_destroy", "goctr_boot_cfg_default",
+                     "goctr_walkgraph_cfg_default", "goctr_walk_cfg_default", "goctr_walkgraph_destroy"):
             getattr(_lib, name).restype = None
         _bm = C.POINTER(BinaryMetrics)
         _lib.goctr_metrics_binary.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, _bm]
@@ -488,6 +502,22 @@ def load() -> C.CDLL:
                                                        C.c_void_p, _uv, C.c_int32, C.POINTER(RecallCfg), C.c_int32, C.c_void_p, _mmr,
                                                        C.c_int32, C.c_int64, _i32, _f32, _i32, _u8, _i32, _i32, _i64, _i32, _u32, _f32,
                                                        _u8, _i64, _i32, _u32, _i32]
+        _wg, _wk = C.POINTER(WalkGraphCfg), C.POINTER(WalkCfg)
+        _lib.goctr_walkgraph_cfg_default.argtypes = [_wg]
+        _lib.goctr_walk_cfg_default.argtypes = [_wk]
+        _lib.goctr_walkgraph_build.argtypes = [C.c_void_p, C.c_int64, _wg, C.POINTER(C.c_void_p)]
+        _lib.goctr_walkgraph_destroy.argtypes = [C.c_void_p]
+        _lib.goctr_walkgraph_info.argtypes = [C.c_void_p, _i64, _i64, _i64, _u64]
+        _lib.goctr_walkgraph_export.argtypes = [C.c_void_p, _i64, _i32, _i64, _i32]
+        _lib.goctr_walk_recall.argtypes = [C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, C.POINTER(RecallCfg), _wk, _i32, _u32, _i32,
+                                           _i32, _i32, _i32]
+        _lib.goctr_recommend_walk.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32,
+                                              C.POINTER(RecallCfg), _wk, C.c_int32, C.c_int64, _i32, _f32, _i32, _i32, _i32, _i64,
+                                              _i32, _u32, _f32, _i64]
+        _lib.goctr_recommend_blend_walk.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32,
+                                                    C.c_void_p, _wk, C.c_int32, C.POINTER(RecallCfg), C.c_int32, C.c_void_p, _mmr,
+                                                    C.c_int32, C.c_int64, _i32, _f32, _i32, _u8, _i32, _i32, _i64, _i32, _u32, _f32,
+                                                    _u8, _i64, _i32, _u32, _i32]
         _um = C.POINTER(UservecMultiCfg)
         _lib.goctr_uservec_multi_cfg_default.argtypes = [_um]
         _lib.goctr_uservec_interests.argtypes = [C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, C.POINTER(RecallCfg), _um, _i32,
@@ -631,6 +661,8 @@ default_ivf_cfg = _default(IvfCfg, "goctr_ivf_cfg_default")
 default_uservec_ivf_cfg = _default(UservecIvfCfg, "goctr_uservec_ivf_cfg_default")
 default_list_cfg = _default(ListCfg, "goctr_list_cfg_default")
 default_popular_cfg = _default(PopularCfg, "goctr_popular_cfg_default")
+default_walkgraph_cfg = _default(WalkGraphCfg, "goctr_walkgraph_cfg_default")
+default_walk_cfg = _default(WalkCfg, "goctr_walk_cfg_default")
 
 
 PROF_COUNT = 18          # GOCTR_K_COUNT (include/goctr.h)

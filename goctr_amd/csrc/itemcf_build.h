@@ -1,7 +1,10 @@
-// itemcf_build.h -- the pieces of a neighbour-list build that goctr_itemcf_build (itemcf.hip) and goctr_itemcf_build_swing
-// (swing.hip) share: the heads / runs reduction of a sorted key list, the merge scratch, and the last two launches (starts, emit)
-// over the stable sort by (i << 24 | 2^24 - 1 - w).  Included only by those two translation units, behind radix_sort.h and scan.h.
+// itemcf_build.h -- the pieces of a build over the cache's entries that goctr_itemcf_build (itemcf.hip), goctr_itemcf_build_swing
+// (swing.hip) and goctr_walkgraph_build (walk.hip) share: the heads / runs reduction of a sorted key list, the merge scratch, the
+// (user, item) keys of the considered entries, and the last two launches (starts, emit) over the stable sort by
+// (i << 24 | 2^24 - 1 - w).  Included only by those translation units, behind radix_sort.h and scan.h.
 #pragma once
+#include <climits>
+
 #include "itemcf.h"
 #include "radix_sort.h"
 #include "scan.h"
@@ -36,6 +39,32 @@ __global__ __launch_bounds__(256) void icf_runs_kernel(const u64* __restrict__ k
       if (keys[mid] > key) hi = mid; else lo = mid + 1;
     }
     ocnt[r] = (u64)(lo - i);
+  }
+}
+
+// one wavefront per user: (u << 32 | i) of every considered entry, the sentinel elsewhere.  Considered: the valid entries in
+// sequence order, the first max_len of them (0: all) and, with seq_ts, of those the ones with ts_lo <= ts <= ts_hi (swing.hip has no
+// window, walk.hip has one)
+__global__ __launch_bounds__(256) void ub_entry_keys_kernel(const long long* __restrict__ off, const int32_t* __restrict__ items,
+                                                            const long long* __restrict__ seq_ts, long long n_users, long long n_items,
+                                                            long long max_len, long long ts_lo, long long ts_hi, u64 sentinel,
+                                                            u64* __restrict__ keys) {
+  const long long u = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (u >= n_users) return;                 // (whole wavefronts leave: the ballots below see full ones)
+  const int lane = threadIdx.x & 63;
+  const long long lo = off[u], len = off[u + 1] - lo;
+  const long long cap = max_len > 0 ? max_len : LLONG_MAX;
+  long long k = 0;
+  for (long long p0 = 0; p0 < len; p0 += 64) {
+    const long long p = p0 + lane;
+    const int it = p < len ? items[lo + p] : -1;
+    const bool valid = it >= 0 && it < n_items;
+    const u64 b = __ballot(valid);
+    const long long r = k + __popcll(b & ((1ull << lane) - 1ull));
+    bool take = valid && r < cap;
+    if (take && seq_ts) { const long long t = seq_ts[lo + p]; take = t >= ts_lo && t <= ts_hi; }
+    if (p < len) keys[lo + p] = take ? ((u64)u << 32) | (u64)(unsigned int)it : sentinel;
+    k += __popcll(b);
   }
 }
 

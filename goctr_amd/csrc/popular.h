@@ -4,6 +4,7 @@
 #pragma once
 #include "itemcf.h"
 #include "uservec.h"
+#include "walk.h"
 
 // time-decayed item popularity resident in HBM; immutable after the build, independent of the cache it was built from
 struct goctr_popular {
@@ -26,6 +27,8 @@ struct BlendArgs {
   const int32_t* extra; int n_extra, quota_pop;
   // goctr_recommend_blend_uservec's alone: part X's list is the user-vector recall's (n_extra entries a row), written on the device
   const goctr_itemvec* uv = nullptr; goctr_uservec_cfg ucfg{};
+  // goctr_recommend_blend_walk's alone: part X's list is the random-walk recall's, written the same way
+  const goctr_walkgraph* wg = nullptr; goctr_walk_cfg wcfg{};
 };
 
 // the refusals that need no slot (sets the error text); `who`: the entry's name, goctr_recommend_blend or goctr_recommend_blend_mmr

@@ -252,7 +252,7 @@ int blend_launch(const BlendArgs& b, const CacheImage& im, long long n_items, co
 int blend_check(const char* who, const BlendArgs& b, const goctr_recall_cfg& cfg, long long n_items_dflt, long long* n_items) {
   GOCTR_CHECK(b.quota_pop >= 0 && b.quota_pop <= cfg.n_cand, "%s: quota_pop = %d is outside 0 .. n_cand = %d", who, b.quota_pop, cfg.n_cand);
   GOCTR_CHECK(b.n_extra >= 0 && b.n_extra <= 1024, "%s: n_extra = %d is outside 0 .. 1024", who, b.n_extra);
-  GOCTR_CHECK(b.n_extra == 0 || b.extra || b.uv, "%s: n_extra = %d without a list", who, b.n_extra);
+  GOCTR_CHECK(b.n_extra == 0 || b.extra || b.uv || b.wg, "%s: n_extra = %d without a list", who, b.n_extra);
   GOCTR_CHECK(b.icf || b.pop || b.n_extra > 0, "%s: no recall channel (no neighbour lists, no popularity list, no extra entries)", who);
   GOCTR_CHECK(!b.icf || !b.pop || b.icf->n_items == b.pop->n_items, "%s: the neighbour lists cover %lld items, the popularity list %lld",
               who, b.icf ? (long long)b.icf->n_items : 0LL, b.pop ? (long long)b.pop->n_items : 0LL);
@@ -283,6 +283,12 @@ int blend_recommend_run(const TopnScorer& sc, const char* who, const BlendArgs& 
       const goctr_recall_cfg xcfg{a.rcfg.history, b.n_extra, a.rcfg.exclude};
       if (uservec_launch(b.uv, sc.ub_off, sc.ub_items, sc.ub_ts, in, a.targets != nullptr, a.n_req, xcfg, b.ucfg, b.n_extra,
                          d_extra.p, x_w.p, x_count.p, nullptr, nullptr, nullptr, uv_ws, st)) return -1;
+    } else if (b.wg) {                        // ... or from the random-walk recall
+      const size_t n = (size_t)a.n_req * (size_t)b.n_extra;
+      if (d_extra.alloc(n, false) || x_w.alloc(n, false) || x_count.alloc((size_t)a.n_req, false)) return -1;
+      const goctr_recall_cfg xcfg{a.rcfg.history, b.n_extra, a.rcfg.exclude};
+      if (walk_launch(b.wg, sc.ub_off, sc.ub_items, sc.ub_ts, in, a.targets != nullptr, a.n_req, xcfg, b.wcfg, b.n_extra, d_extra.p,
+                      x_w.p, x_count.p, nullptr, nullptr, st)) return -1;
     } else if (b.n_extra > 0) {
       const size_t n = (size_t)a.n_req * (size_t)b.n_extra;
       if (d_extra.alloc(n, false)) return -1;

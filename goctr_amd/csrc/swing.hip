@@ -3,8 +3,9 @@
 // take the maximum of integers, so no arrival order can show.
 //
 // Build (engine stream, engine lock, the cache's image held):
-//   sw_keys_kernel       one wavefront per user: (u << 32 | i) of every considered entry, the sentinel elsewhere; one sort, the
-//                        heads, and a scan whose sink writes every distinct (u, i) as (i << 32 | key(i,u)) -> u and counts cnt[i]
+//   ub_entry_keys_kernel (itemcf_build.h, shared with walk.hip) one wavefront per user: (u << 32 | i) of every considered entry, the
+//                        sentinel elsewhere; one sort, the heads, and a scan whose sink writes every distinct (u, i) as
+//                        (i << 32 | key(i,u)) -> u and counts cnt[i]
 //   holders              a stable sort by (i, key) leaves every item's users by key, then u; sw_keep_kernel cuts each run at
 //                        max_users and a second sort by (i << 32 | u) orders what is kept: H [n_h], item i's list at hoff[i]
 //   sw_nup_kernel        per user the user pairs in which it is the smaller: its position in each of its items' lists
@@ -38,26 +39,6 @@ constexpr u64 SW_NP_ONE = 1ull << 40;          // a value is s + np * 2^40: s < 
 constexpr u64 SW_S_MASK = SW_NP_ONE - 1;
 
 __device__ __forceinline__ u64 sw_emitted(unsigned int ov) { return ov < 2u ? 0ull : (u64)ov * (u64)(ov - 1u); }
-
-__global__ __launch_bounds__(256) void sw_keys_kernel(const long long* __restrict__ off, const int32_t* __restrict__ items,
-                                                      long long n_users, long long n_items, long long max_len, u64 sentinel,
-                                                      u64* __restrict__ keys) {
-  const long long u = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (u >= n_users) return;                 // (whole wavefronts leave: the ballots below see full ones)
-  const int lane = threadIdx.x & 63;
-  const long long lo = off[u], len = off[u + 1] - lo;
-  const long long cap = max_len > 0 ? max_len : LLONG_MAX;
-  long long k = 0;
-  for (long long p0 = 0; p0 < len; p0 += 64) {
-    const long long p = p0 + lane;
-    const int it = p < len ? items[lo + p] : -1;
-    const bool valid = it >= 0 && it < n_items;
-    const u64 b = __ballot(valid);
-    const long long r = k + __popcll(b & ((1ull << lane) - 1ull));
-    if (p < len) keys[lo + p] = valid && r < cap ? ((u64)u << 32) | (u64)(unsigned int)it : sentinel;
-    k += __popcll(b);
-  }
-}
 
 // the scan's sink over the heads of the sorted (u, i) keys: the rank-th distinct entry
 struct SwDistinctSink {
@@ -362,8 +343,9 @@ int goctr_itemcf_build_swing(goctr_ubcache* c, int64_t n_items, const goctr_swin
   if (nu > 0 && nnz > 0) {
     if (ws.keys.alloc((size_t)nnz, false) || ws.keys_sorted.alloc((size_t)nnz, false) || ws.head.alloc((size_t)nnz, false) ||
         ws.hk.alloc((size_t)nnz, false) || ws.hv.alloc((size_t)nnz, false)) return -1;
-    hipLaunchKernelGGL(sw_keys_kernel, dim3((unsigned)cdiv(nu, 4)), dim3(256), 0, s, c->off.p, c->items.p, nu, (long long)n_items,
-                       (long long)cfg->max_len, user_sentinel, ws.keys.p);
+    hipLaunchKernelGGL(ub_entry_keys_kernel, dim3((unsigned)cdiv(nu, 4)), dim3(256), 0, s, c->off.p, c->items.p,
+                       (const long long*)nullptr /* no timestamp window */, nu, (long long)n_items, (long long)cfg->max_len, 0LL, 0LL,
+                       user_sentinel, ws.keys.p);
     GOCTR_HIP(hipGetLastError());
     if (radix_sort_keys(ws.temp, ws.keys.p, ws.keys_sorted.p, (size_t)nnz, user_bits, s)) return -1;
     hipLaunchKernelGGL(icf_heads_kernel, grid256(nnz), dim3(256), 0, s, ws.keys_sorted.p, nnz, user_sentinel, ws.head.p);

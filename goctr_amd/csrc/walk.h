@@ -1,0 +1,36 @@
+// walk.h -- the handle of goctr_walkgraph_build (walk.hip) and what goctr_walk_recall's launch lends to the serving entries:
+// goctr_recommend_walk runs it as the recall stage of itemcf.h's recall_rank_run, and goctr_recommend_blend_walk (popular.hip's
+// driver) has it write the list the blend's part X reads.  include/goctr.h states the semantics ("Random-walk recall");
+// tests/walk_ref.py restates them.
+#pragma once
+#include "itemcf.h"
+
+// the bipartite user-item graph as two CSRs resident in HBM; immutable after the build, independent of the cache it was built from.
+// A node is {first edge, degree} in ONE 8-byte word (edges < 2^31), so that a walk step fetches both with one load
+struct goctr_walkgraph {
+  goctr::Engine* const eng = &goctr::engine();   // the engine (device, streams, arena) the handle was created on
+  int64_t n_users = 0, n_items = 0;
+  uint64_t n_edges = 0;
+  uint64_t cache_version = 0;                    // version of the cache image the graph was built from
+  goctr::DevBuf<uint2> unode, inode;             // [n_users], [n_items]
+  goctr::DevBuf<int32_t> uitems, iusers;         // [n_edges] each: I_u ascending by (u, i), U_i ascending by (i, u)
+};
+
+namespace goctr {
+
+// the cfg's ranges (sets the error text)
+int walk_check_cfg(const goctr_walk_cfg* wcfg, const char* who);
+
+// walk_recall_kernel over nq rows on `st`: row q's first cfg.n_cand slots at q * stride (stride >= cfg.n_cand) of o_items / o_w,
+// o_count[q], o_tpos[q] (may be null); o_trace [nq, n_walks * n_steps] may be null.  The cache arrays may be null together (no
+// cache: every row comes back empty).  Waits for nothing
+int walk_launch(const goctr_walkgraph* g, const long long* off, const int32_t* seq_items, const long long* seq_ts,
+                const RecallInputs& in, bool has_targets, int64_t nq, const goctr_recall_cfg& cfg, const goctr_walk_cfg& wcfg,
+                int stride, int32_t* o_items, unsigned int* o_w, int32_t* o_count, int32_t* o_tpos, int32_t* o_trace, hipStream_t st);
+
+// goctr_recommend_walk's refusals that need no slot, and the whole call over a prepared slot
+int walk_check_recommend(const char* who, const goctr_walkgraph* g, const goctr_walk_cfg* wcfg, const ItemcfRecArgs& a,
+                         int64_t n_users, int64_t n_items);
+int walk_recommend_run(const TopnScorer& sc, const goctr_walkgraph* g, const goctr_walk_cfg& wcfg, const ItemcfRecArgs& a);
+
+}  // namespace goctr

@@ -1,0 +1,415 @@
+// walk.hip -- goctr_walkgraph_* and goctr_walk_recall: the bipartite user-item graph of one image of the behaviour cache as two CSRs,
+// and Pixie-style random walks over it as a recall channel (include/goctr.h states the semantics; tests/walk_ref.py restates them
+// on the host, bit for bit).  All arithmetic is integer.
+//
+// Build (goctr_walkgraph_build; engine stream, engine lock, the cache's image held):
+//   ub_entry_keys_kernel  (itemcf_build.h) one wavefront per user: (u << 32 | i) of every considered entry, the sentinel elsewhere
+//   radix_sort_keys       + icf_heads_kernel + a scan whose sink writes the rank-th distinct (u, i): uitems[rank] = i, the key
+//                         (i << 32 | u) of the second sort, and the two degrees (integer counts: no arrival order can show)
+//   radix_sort_keys       by (i, u); wk_low_words_kernel keeps the users: iusers
+//   two scans             of the degrees; their sinks write a node's {first edge, degree} as one 8-byte word
+// Recall (walk_recall_kernel): one workgroup per request row, below.
+#include <climits>
+#include <memory>
+#include <vector>
+
+#include "itemcf_build.h"
+#include "negsample.h"
+#include "ubcache.h"
+#include "walk.h"
+
+using namespace goctr;
+
+namespace {
+
+// ---------------------------------------------------------------------------------------------------------------- build
+// the scan's sink over the heads of the sorted (u, i) keys: the rank-th distinct entry
+struct WkDistinctSink {
+  const u64* keys; int32_t* uitems; u64* ikeys; unsigned int* udeg; unsigned int* ideg;
+  __device__ __forceinline__ void operator()(long long e, unsigned int head, unsigned int rank) const {
+    if (!head) return;
+    const u64 key = keys[e], u = key >> 32, i = key & 0xffffffffull;
+    uitems[rank] = (int32_t)i;
+    ikeys[rank] = (i << 32) | u;
+    atomicAdd(udeg + u, 1u);
+    atomicAdd(ideg + i, 1u);
+  }
+};
+
+// the scan's sink over the degrees: node e = {its exclusive prefix, its degree}
+struct WkNodeSink {
+  uint2* node;
+  __device__ __forceinline__ void operator()(long long e, unsigned int deg, unsigned int first) const { node[e] = make_uint2(first, deg); }
+};
+
+__global__ __launch_bounds__(256) void wk_low_words_kernel(const u64* __restrict__ keys, long long n, int32_t* __restrict__ out) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e < n) out[e] = (int32_t)(unsigned int)keys[e];
+}
+
+// scratch of one build (declared in front of the cache hold, so that an error return drains the stream before it is freed)
+struct WkScratch {
+  DevBuf<u64> keys, keys_sorted, ikeys, ikeys_sorted, total;
+  DevBuf<unsigned int> head, udeg, ideg, tiles;
+  DevBuf<char> temp;
+};
+
+inline dim3 grid256(long long n) { return dim3((unsigned)cdiv(n, 256)); }
+
+// --------------------------------------------------------------------------------------------------------------- recall
+// One workgroup of SEL_THREADS per request row; threads own walks (w = tid, tid + SEL_THREADS).
+//   1. the history (lds_gather_history)
+//   2. the walks.  A step is four dependent loads -- inode[i], iusers[.], unode[u], uitems[.] -- and nothing else of weight, so the
+//      kernel is bound by their latency: a node's first edge and degree come in ONE 8-byte load, and both hash words of a step are
+//      computed in the shadow of the first.  Visit (w, s) has its own place w * n_steps + s in the LDS list vkey[]: the key
+//      ((item + 1) << 8 | slot), 0 for a step that recorded nothing.  No atomic, so no arrival order
+//   3. ONE descending bitonic sort of the list (lds_sort_desc): an item's visits are a run, a slot's visits a run inside it.  The
+//      thread at an item's first position folds the item: every slot's run length c_t by a gallop and a bisection, r_t, R, S
+//   4. seen: the sequence entries the mode looks at find their item's first position by bisection and set its bit
+//   5. the kept items join the row's list by the key (S << 32) | ~item (sel_append / sel_sort_trim), which sel_write_row writes
+// The list holds WK_MAX_VISITS keys whatever the walk's shape: 90 KB of LDS, one workgroup per CU.  (A second instance with a 2048-key
+// list, whose 42 KB admit two workgroups per CU, ran the default 512 x 4 walks 0.7 % faster -- 4.40 against 4.43 ms for 16 384
+// rows -- and was not kept.)
+constexpr int WK_MAX_H = 256;                  // recall_check_cfg's limit on cfg.history
+constexpr int WK_MAX_VISITS = 8192;
+
+struct WalkArgs {
+  const long long* off; const int32_t* seq_items; const long long* seq_ts;   // the cache's image (null: no cache)
+  long long n_items;
+  const uint2* unode; const uint2* inode; const int32_t* uitems; const int32_t* iusers;
+  const int32_t* users; const long long* ts; const int32_t* targets;          // device; targets may be null
+  int H, n_cand, exclude;
+  int stride;                                                                 // row q's slots start at q * stride (>= n_cand)
+  int n_walks, n_steps, boost, min_visits;
+  u64 seed;
+  int32_t* out_items; unsigned int* out_w; int32_t* out_count; int32_t* out_tpos; int32_t* out_trace;   // tpos, trace may be null
+};
+
+__device__ __forceinline__ unsigned int wk_pick(u64 x, unsigned int d) { return (unsigned int)(((x >> 32) * (u64)d) >> 32); }
+
+// the largest r with r * r <= c * 2^32 (c <= 8192: the argument is exact in a double, the two loops settle the last unit)
+__device__ __forceinline__ u64 wk_root(unsigned int c) {
+  const u64 x = (u64)c << 32;
+  u64 r = (u64)sqrt((double)x);
+  while (r * r > x) --r;
+  while ((r + 1) * (r + 1) <= x) ++r;
+  return r;
+}
+
+__global__ __launch_bounds__(SEL_THREADS) void walk_recall_kernel(WalkArgs a) {
+  constexpr int KCAP = WK_MAX_VISITS, PER = KCAP / SEL_THREADS;   // the list's capacity; list positions per thread
+  __shared__ unsigned long long vkey[KCAP];
+  __shared__ unsigned long long skey[SEL_CAP];
+  __shared__ unsigned sraw[SEL_CAP];
+  __shared__ unsigned int seen[KCAP / 32];
+  __shared__ int hist[WK_MAX_H];
+  __shared__ int wcnt[SEL_THREADS / 64];
+  __shared__ int s_fill, s_tpos;
+  __shared__ unsigned long long s_thr;
+  const int tid = threadIdx.x;
+  const long long q = blockIdx.x;
+  const bool has_t = a.targets != nullptr;
+  const int tgt = has_t ? a.targets[q] : -1;
+  const int user = a.users[q];
+  long long lo_e = 0, len = 0;
+  if (a.off) { lo_e = a.off[user]; len = a.off[user + 1] - lo_e; }
+  const long long mts = a.ts[q];
+  const int total = a.n_walks * a.n_steps;     // <= KCAP (walk_check_cfg)
+  int n2 = 64;
+  while (n2 < total) n2 <<= 1;
+
+  // 1. history
+  const int nh = lds_gather_history<SEL_THREADS / 64>(a.seq_items, a.seq_ts, lo_e, len, mts, a.n_items, a.H, hist, wcnt);
+  if (tid == 0) { s_fill = 0; s_thr = 0ull; s_tpos = -1; }
+  for (int i = tid; i < KCAP / 32; i += SEL_THREADS) seen[i] = 0u;
+  for (int i = total + tid; i < n2; i += SEL_THREADS) vkey[i] = 0ull;
+  __syncthreads();
+
+  // 2. the walks
+  for (int w = tid; w < a.n_walks; w += SEL_THREADS) {
+    const int t = nh > 0 ? w % nh : 0;
+    bool alive = nh > 0;
+    int i = alive ? hist[t] : 0;
+    const u64 hw = ((u64)(unsigned int)user << 32) | (u64)(unsigned int)w;
+    for (int s = 0; s < a.n_steps; ++s) {
+      int j = -1;
+      if (alive) {
+        const uint2 ni = a.inode[i];
+        const u64 hs = (u64)(unsigned int)s << 32;
+        const u64 x0 = ns_mix(a.seed ^ ns_mix(hw ^ ns_mix(hs))), x1 = ns_mix(a.seed ^ ns_mix(hw ^ ns_mix(hs | 1ull)));
+        if (ni.y == 0u) {
+          alive = false;
+        } else {
+          const int u = a.iusers[ni.x + wk_pick(x0, ni.y)];
+          if (u != user) {
+            const uint2 nu = a.unode[u];       // (u holds i: its degree is at least 1)
+            j = a.uitems[nu.x + wk_pick(x1, nu.y)];
+            i = j;
+          }
+        }
+      }
+      const int at = w * a.n_steps + s;
+      vkey[at] = j >= 0 ? ((u64)(unsigned int)(j + 1) << 8) | (u64)t : 0ull;
+      if (a.out_trace) a.out_trace[q * total + at] = j;
+    }
+  }
+  __syncthreads();
+
+  // 3. sort; an item's first position folds the item
+  lds_sort_desc(vkey, n2, tid, SEL_THREADS);
+  u64 ckey[PER];
+#pragma unroll
+  for (int k = 0; k < PER; ++k) {
+    const int p = k * SEL_THREADS + tid;
+    ckey[k] = 0ull;
+    if (p >= n2) continue;
+    const u64 key = vkey[p], itk = key >> 8;
+    if (key == 0ull || (p > 0 && (vkey[p - 1] >> 8) == itk)) continue;
+    unsigned int c = 0u;
+    u64 R = 0ull;
+    int e = p;
+    while (e < n2 && (vkey[e] >> 8) == itk) {              // one slot's run from e on
+      const u64 k0 = vkey[e];
+      int step = 1;                                        // gallop, then bisect: most runs are short
+      while (e + step < n2 && vkey[e + step] == k0) step <<= 1;
+      int lo = e + (step >> 1) + 1, hi = e + step < n2 ? e + step : n2;   // the first index with another key is in [lo, hi]
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (vkey[mid] != k0) hi = mid; else lo = mid + 1;
+      }
+      const unsigned int ct = (unsigned int)(lo - e);
+      c += ct;
+      if (a.boost) R += wk_root(ct);
+      e = lo;
+    }
+    const u64 S = a.boost ? (R * R + (1ull << 31)) >> 32 : (u64)c;
+    if (c >= (unsigned int)a.min_visits) ckey[k] = (S << 32) | (u64)(~((unsigned int)itk - 1u));
+  }
+
+  // 4. seen (vkey[] is only read from here on)
+  if (a.exclude != GOCTR_TOPN_KEEP_SEEN && nh > 0) {
+    const bool before = a.exclude == GOCTR_TOPN_DROP_SEEN_BEFORE;
+    for (long long p = tid; p < len; p += SEL_THREADS) {
+      const int it = a.seq_items[lo_e + p];
+      if (it < 0 || it >= a.n_items) continue;
+      if (before && mts != 0 && a.seq_ts[lo_e + p] > mts) continue;
+      const u64 want = (u64)(unsigned int)(it + 1);
+      int lo = 0, hi = n2;                                 // the first position whose item key is <= want (keys descending)
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((vkey[mid] >> 8) > want) lo = mid + 1; else hi = mid;
+      }
+      if (lo < n2 && (vkey[lo] >> 8) == want) atomicOr(&seen[lo >> 5], 1u << (lo & 31));
+    }
+  }
+  __syncthreads();
+
+  // 5. the kept items join the row's list
+#pragma unroll
+  for (int k = 0; k < PER; ++k) {
+    if (k * SEL_THREADS >= n2) break;                      // (uniform)
+    const int p = k * SEL_THREADS + tid;
+    u64 key = ckey[k];
+    if (key != 0ull) {
+      const int item = (int)~(unsigned int)key;
+      if (((seen[p >> 5] >> (p & 31)) & 1u) && !(has_t && item == tgt)) key = 0ull;
+      if (key <= s_thr) key = 0ull;
+    }
+    sel_append(skey, sraw, &s_fill, &s_thr, a.n_cand, key, 0u);
+  }
+  sel_sort_trim(skey, sraw, &s_fill, &s_thr, a.n_cand);
+  sel_write_row(skey, s_fill, a.n_cand, q * a.stride, q, has_t, tgt, &s_tpos, a.out_items, a.out_w, a.out_count, a.out_tpos);
+}
+
+}  // namespace
+
+namespace goctr {
+
+int walk_check_cfg(const goctr_walk_cfg* w, const char* who) {
+  GOCTR_CHECK(w->n_walks >= 1 && w->n_walks <= 2048, "%s: n_walks = %d is outside 1 .. 2048", who, w->n_walks);
+  GOCTR_CHECK(w->n_steps >= 1 && w->n_steps <= 16, "%s: n_steps = %d is outside 1 .. 16", who, w->n_steps);
+  GOCTR_CHECK(w->n_walks * w->n_steps <= WK_MAX_VISITS, "%s: n_walks * n_steps = %d is over %d", who, w->n_walks * w->n_steps,
+              WK_MAX_VISITS);
+  GOCTR_CHECK(w->boost == 0 || w->boost == 1, "%s: boost = %d is neither 0 nor 1", who, w->boost);
+  GOCTR_CHECK(w->min_visits >= 1 && w->min_visits <= WK_MAX_VISITS, "%s: min_visits = %d is outside 1 .. %d", who, w->min_visits,
+              WK_MAX_VISITS);
+  GOCTR_CHECK(w->reserved == 0, "%s: reserved = %lld (must be 0)", who, (long long)w->reserved);
+  return 0;
+}
+
+int walk_launch(const goctr_walkgraph* g, const long long* off, const int32_t* seq_items, const long long* seq_ts,
+                const RecallInputs& in, bool has_targets, int64_t nq, const goctr_recall_cfg& cfg, const goctr_walk_cfg& wcfg,
+                int stride, int32_t* o_items, unsigned int* o_w, int32_t* o_count, int32_t* o_tpos, int32_t* o_trace, hipStream_t st) {
+  WalkArgs a{};
+  a.off = off; a.seq_items = seq_items; a.seq_ts = seq_ts;
+  a.n_items = g->n_items;
+  a.unode = g->unode.p; a.inode = g->inode.p; a.uitems = g->uitems.p; a.iusers = g->iusers.p;
+  a.users = in.users.p; a.ts = in.ts.p; a.targets = has_targets ? in.targets.p : nullptr;
+  a.H = cfg.history; a.n_cand = cfg.n_cand; a.exclude = cfg.exclude; a.stride = stride;
+  a.n_walks = wcfg.n_walks; a.n_steps = wcfg.n_steps; a.boost = wcfg.boost; a.min_visits = wcfg.min_visits; a.seed = wcfg.seed;
+  a.out_items = o_items; a.out_w = o_w; a.out_count = o_count; a.out_tpos = o_tpos; a.out_trace = o_trace;
+  hipLaunchKernelGGL(walk_recall_kernel, dim3((unsigned)nq), dim3(SEL_THREADS), 0, st, a);
+  GOCTR_HIP(hipGetLastError());
+  return 0;
+}
+
+int walk_check_recommend(const char* who, const goctr_walkgraph* g, const goctr_walk_cfg* wcfg, const ItemcfRecArgs& a,
+                         int64_t n_users, int64_t n_items) {
+  GOCTR_CHECK(g && wcfg, "%s: bad arguments", who);
+  if (walk_check_cfg(wcfg, who)) return -1;
+  GOCTR_CHECK(g->n_items == n_items, "%s: the walk graph covers %lld items, the recsys %lld", who, (long long)g->n_items,
+              (long long)n_items);
+  GOCTR_CHECK(g->n_users == n_users, "%s: the walk graph has %lld users, the recsys %lld", who, (long long)g->n_users,
+              (long long)n_users);
+  return recall_check_recommend(who, a, n_users);
+}
+
+int walk_recommend_run(const TopnScorer& sc, const goctr_walkgraph* g, const goctr_walk_cfg& wcfg, const ItemcfRecArgs& a) {
+  return recall_rank_run(sc, "goctr_recommend_walk", a, false, [&](const RecallInputs& in, const RecallRows& o, hipStream_t st) {
+    return walk_launch(g, sc.ub_off, sc.ub_items, sc.ub_ts, in, a.targets != nullptr, a.n_req, a.rcfg, wcfg, a.rcfg.n_cand, o.items,
+                       o.w, o.count, o.tpos, nullptr, st);
+  });
+}
+
+}  // namespace goctr
+
+extern "C" {
+
+void goctr_walkgraph_cfg_default(goctr_walkgraph_cfg* c) {
+  if (!c) return;
+  c->max_len = 0; c->reserved = 0; c->ts_lo = INT64_MIN; c->ts_hi = INT64_MAX;
+}
+
+void goctr_walk_cfg_default(goctr_walk_cfg* c) {
+  if (!c) return;
+  c->n_walks = 512; c->n_steps = 4; c->boost = 1; c->min_visits = 1; c->seed = 0; c->reserved = 0;
+}
+
+int goctr_walkgraph_build(goctr_ubcache* c, int64_t n_items, const goctr_walkgraph_cfg* cfg, goctr_walkgraph** out) {
+  GOCTR_ENTER_H(c);
+  const char* who = "goctr_walkgraph_build";
+  GOCTR_CHECK(c && cfg && out, "%s: null argument (cache, cfg, out)", who);
+  GOCTR_CHECK(n_items > 0 && n_items <= INT32_MAX, "%s: n_items = %lld (1 .. 2^31 - 1)", who, (long long)n_items);
+  GOCTR_CHECK(cfg->max_len >= 0, "%s: max_len = %d (>= 0)", who, cfg->max_len);
+  GOCTR_CHECK(cfg->reserved == 0, "%s: reserved = %d (must be 0)", who, cfg->reserved);
+  GOCTR_CHECK(cfg->ts_lo <= cfg->ts_hi, "%s: ts_lo = %lld is above ts_hi = %lld", who, (long long)cfg->ts_lo, (long long)cfg->ts_hi);
+  hipStream_t s = engine().stream;
+  std::unique_ptr<goctr_walkgraph> g(new goctr_walkgraph);
+  WkScratch ws;
+  UbRead image(c, s);                         // one image of the cache for the whole build
+  const long long nu = c->n_users, nnz = c->nnz;
+  GOCTR_CHECK(nnz < (1LL << 31), "%s: the cache image holds %lld entries (limit 2^31 - 1: edges are 32-bit)", who, nnz);
+  GOCTR_CHECK(nu < (1LL << 31), "%s: the cache has %lld users (limit 2^31 - 1)", who, nu);
+  const u64 user_sentinel = (u64)nu << 32;
+  const unsigned int user_bits = 32u + (unsigned int)bits_for(nu + 1), item_bits = 32u + (unsigned int)bits_for(n_items);
+  g->n_users = nu; g->n_items = n_items; g->cache_version = c->version;
+  if (g->unode.alloc((size_t)nu) || g->inode.alloc((size_t)n_items) || ws.udeg.alloc((size_t)nu) || ws.ideg.alloc((size_t)n_items) ||
+      ws.total.alloc(1)) return -1;
+  u64 n_e = 0;
+  if (nu > 0 && nnz > 0) {
+    if (ws.keys.alloc((size_t)nnz, false) || ws.keys_sorted.alloc((size_t)nnz, false) || ws.head.alloc((size_t)nnz, false) ||
+        ws.ikeys.alloc((size_t)nnz, false) || g->uitems.alloc((size_t)nnz, false)) return -1;
+    hipLaunchKernelGGL(ub_entry_keys_kernel, dim3((unsigned)cdiv(nu, 4)), dim3(256), 0, s, c->off.p, c->items.p, c->ts.p, nu,
+                       (long long)n_items, (long long)cfg->max_len, (long long)cfg->ts_lo, (long long)cfg->ts_hi, user_sentinel,
+                       ws.keys.p);
+    GOCTR_HIP(hipGetLastError());
+    if (radix_sort_keys(ws.temp, ws.keys.p, ws.keys_sorted.p, (size_t)nnz, user_bits, s)) return -1;
+    hipLaunchKernelGGL(icf_heads_kernel, grid256(nnz), dim3(256), 0, s, ws.keys_sorted.p, nnz, user_sentinel, ws.head.p);
+    GOCTR_HIP(hipGetLastError());
+    if (exclusive_scan_sink<unsigned int>(ws.head.p, nnz, ws.tiles, ws.total.p, ScanIdentity{},
+                                          WkDistinctSink{ws.keys_sorted.p, g->uitems.p, ws.ikeys.p, ws.udeg.p, ws.ideg.p})) return -1;
+    if (ws.total.download(&n_e, 1)) return -1;
+  }
+  if (n_e) {
+    if (ws.ikeys_sorted.alloc((size_t)n_e, false) || g->iusers.alloc((size_t)n_e, false)) return -1;
+    if (radix_sort_keys(ws.temp, ws.ikeys.p, ws.ikeys_sorted.p, (size_t)n_e, item_bits, s)) return -1;
+    hipLaunchKernelGGL(wk_low_words_kernel, grid256((long long)n_e), dim3(256), 0, s, ws.ikeys_sorted.p, (long long)n_e, g->iusers.p);
+    GOCTR_HIP(hipGetLastError());
+    if (nu > 0 && exclusive_scan_sink<unsigned int>(ws.udeg.p, nu, ws.tiles, ws.total.p, ScanIdentity{}, WkNodeSink{g->unode.p})) return -1;
+    GOCTR_HIP(hipStreamSynchronize(s));       // (the next scan may grow the tile sums this one reads)
+    if (exclusive_scan_sink<unsigned int>(ws.ideg.p, n_items, ws.tiles, ws.total.p, ScanIdentity{}, WkNodeSink{g->inode.p})) return -1;
+  }
+  GOCTR_HIP(hipStreamSynchronize(s));         // the scratch goes out of scope; the image is released
+  image.done();
+  g->n_edges = n_e;
+  *out = g.release();
+  return 0;
+}
+
+void goctr_walkgraph_destroy(goctr_walkgraph* g) {
+  if (!g) return;
+  EngineScope on(g->eng);
+  std::lock_guard<std::recursive_mutex> lk(g->eng->mu);
+  delete g;
+}
+
+int goctr_walkgraph_info(goctr_walkgraph* g, int64_t* n_users, int64_t* n_items, int64_t* n_edges, uint64_t* cache_version) {
+  GOCTR_ENTER_H(g);
+  GOCTR_CHECK(g, "goctr_walkgraph_info: null handle");
+  if (n_users) *n_users = g->n_users;
+  if (n_items) *n_items = g->n_items;
+  if (n_edges) *n_edges = (int64_t)g->n_edges;
+  if (cache_version) *cache_version = g->cache_version;
+  return 0;
+}
+
+int goctr_walkgraph_export(goctr_walkgraph* g, int64_t* uoff, int32_t* uitems, int64_t* ioff, int32_t* iusers) {
+  GOCTR_ENTER_H(g);
+  GOCTR_CHECK(g, "goctr_walkgraph_export: null handle");
+  const size_t ne = (size_t)g->n_edges;
+  // the offsets are the nodes' first edges (a node without edges keeps its exclusive prefix: an unbuilt graph's nodes are zero)
+  auto offsets = [&](const DevBuf<uint2>& node, size_t n, int64_t* o) {
+    std::vector<uint2> h(n);
+    if (n && node.download(h.data(), n)) return -1;
+    for (size_t e = 0; e < n; ++e) o[e] = (int64_t)h[e].x;
+    o[n] = (int64_t)ne;
+    return 0;
+  };
+  if (uoff && offsets(g->unode, (size_t)g->n_users, uoff)) return -1;
+  if (ioff && offsets(g->inode, (size_t)g->n_items, ioff)) return -1;
+  if (uitems && ne && g->uitems.download(uitems, ne)) return -1;
+  if (iusers && ne && g->iusers.download(iusers, ne)) return -1;
+  return 0;
+}
+
+int goctr_walk_recall(goctr_walkgraph* g, goctr_ubcache* c, const int32_t* users, const int64_t* ts, int64_t n_req,
+                      const goctr_recall_cfg* cfg, const goctr_walk_cfg* wcfg, int32_t* out_items, uint32_t* out_w, int32_t* out_count,
+                      const int32_t* targets, int32_t* out_target_pos, int32_t* out_trace) {
+  GOCTR_ENTER_H(g);
+  const char* who = "goctr_walk_recall";
+  GOCTR_CHECK(g && c && users && cfg && wcfg && out_items && out_w && out_count, "%s: null argument", who);
+  GOCTR_SAME_ENGINE(g, c);
+  if (recall_check_cfg(cfg, who) || walk_check_cfg(wcfg, who)) return -1;
+  GOCTR_CHECK(g->n_users == c->n_users, "%s: the walk graph has %lld users, the cache %lld", who, (long long)g->n_users,
+              (long long)c->n_users);
+  if (recall_check_users(users, n_req, c->n_users, who)) return -1;
+  hipStream_t s = engine().stream;
+  const size_t nq = (size_t)n_req, nc = (size_t)cfg->n_cand, nt = (size_t)wcfg->n_walks * (size_t)wcfg->n_steps;
+  RecallInputs in;
+  DevBuf<int32_t> o_items, o_count, o_tpos, o_trace;
+  DevBuf<unsigned int> o_w;
+  // the results are staged on the host so that a failing copy leaves the caller's arrays as they were
+  std::vector<int32_t> h_items(nq * nc), h_count(nq), h_tpos(nq), h_trace(out_trace ? nq * nt : 0);
+  std::vector<unsigned int> h_w(nq * nc);
+  UbRead image(c, s);                         // (behind the buffers: an error return drains the stream before they are freed)
+  if (in.stage(users, ts, targets, n_req, s)) return -1;
+  if (o_items.alloc(nq * nc, false) || o_w.alloc(nq * nc, false) || o_count.alloc(nq, false) || o_tpos.alloc(nq, false)) return -1;
+  if (out_trace && o_trace.alloc(nq * nt, false)) return -1;
+  if (walk_launch(g, c->off.p, c->items.p, c->ts.p, in, targets != nullptr, n_req, *cfg, *wcfg, cfg->n_cand, o_items.p, o_w.p,
+                  o_count.p, o_tpos.p, out_trace ? o_trace.p : nullptr, s)) return -1;
+  GOCTR_HIP(hipMemcpyAsync(h_items.data(), o_items.p, sizeof(int32_t) * nq * nc, hipMemcpyDeviceToHost, s));
+  GOCTR_HIP(hipMemcpyAsync(h_w.data(), o_w.p, sizeof(unsigned int) * nq * nc, hipMemcpyDeviceToHost, s));
+  GOCTR_HIP(hipMemcpyAsync(h_count.data(), o_count.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));
+  GOCTR_HIP(hipMemcpyAsync(h_tpos.data(), o_tpos.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));
+  if (out_trace) GOCTR_HIP(hipMemcpyAsync(h_trace.data(), o_trace.p, sizeof(int32_t) * nq * nt, hipMemcpyDeviceToHost, s));
+  GOCTR_HIP(hipStreamSynchronize(s));
+  image.done();
+  memcpy(out_items, h_items.data(), sizeof(int32_t) * nq * nc);
+  memcpy(out_w, h_w.data(), sizeof(unsigned int) * nq * nc);
+  memcpy(out_count, h_count.data(), sizeof(int32_t) * nq);
+  if (out_target_pos) for (size_t q = 0; q < nq; ++q) out_target_pos[q] = targets ? h_tpos[q] : -1;
+  if (out_trace) memcpy(out_trace, h_trace.data(), sizeof(int32_t) * nq * nt);
+  return 0;
+}
+
+}  // extern "C"

@@ -966,6 +966,91 @@ inline TopN RecommendBlendVectorBatch(model::CtrNet& net, RecSys& rs, const Item
   return out;
 }
 
+// the bipartite user-item graph of a cache image (goctr_walkgraph_build) and random walks over it as a recall channel
+// (goctr_walk_recall): a candidate may be several co-occurrence hops from the history
+class WalkGraph {
+ public:
+  static goctr_walkgraph_cfg DefaultCfg() { goctr_walkgraph_cfg c; goctr_walkgraph_cfg_default(&c); return c; }
+  static goctr_walk_cfg DefaultWalkCfg() { goctr_walk_cfg c; goctr_walk_cfg_default(&c); return c; }
+  static WalkGraph Build(goctr_ubcache* cache, int64_t n_items, const goctr_walkgraph_cfg& cfg = DefaultCfg()) {
+    WalkGraph g;
+    check(goctr_walkgraph_build(cache, n_items, &cfg, &g.h_));
+    return g;
+  }
+  WalkGraph(const WalkGraph&) = delete;
+  WalkGraph& operator=(const WalkGraph&) = delete;
+  WalkGraph(WalkGraph&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  ~WalkGraph() { goctr_walkgraph_destroy(h_); }
+  goctr_walkgraph* handle() const { return h_; }
+  struct Info { int64_t n_users, n_items, n_edges; uint64_t cache_version; };
+  Info info() const {
+    Info i{};
+    check(goctr_walkgraph_info(h_, &i.n_users, &i.n_items, &i.n_edges, &i.cache_version));
+    return i;
+  }
+  // items / w [nq, cfg.n_cand] (w: the walk scores), count [nq]
+  void Recall(goctr_ubcache* cache, const std::vector<int32_t>& users, const std::vector<int64_t>& ts, const goctr_recall_cfg& cfg,
+              std::vector<int32_t>& items, std::vector<uint32_t>& w, std::vector<int32_t>& count,
+              const goctr_walk_cfg& wcfg = DefaultWalkCfg()) const {
+    if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("WalkGraph::Recall: one timestamp per user");
+    const size_t nq = users.size(), nc = (size_t)std::max(cfg.n_cand, 1);
+    items.resize(nq * nc); w.resize(nq * nc); count.resize(nq);
+    check(goctr_walk_recall(h_, cache, users.data(), ts.empty() ? nullptr : ts.data(), (int64_t)nq, &cfg, &wcfg, items.data(), w.data(),
+                            count.data(), nullptr, nullptr, nullptr));
+  }
+
+ private:
+  WalkGraph() = default;
+  goctr_walkgraph* h_ = nullptr;
+};
+
+// RecommendItemCFBatch with the random-walk recall as the recall stage (goctr_recommend_walk)
+inline TopN RecommendWalkBatch(model::CtrNet& net, RecSys& rs, const WalkGraph& graph, const std::vector<int32_t>& users, int n = 10,
+                               const std::vector<int64_t>& ts = {}, const goctr_recall_cfg& rcfg = ItemCF::DefaultRecallCfg(),
+                               const goctr_walk_cfg& wcfg = WalkGraph::DefaultWalkCfg(), const std::vector<int32_t>& targets = {},
+                               int64_t pass_rows = 0) {
+  const int64_t nq = (int64_t)users.size();
+  detail::check_request("RecommendWalkBatch", users.size(), ts.size(), targets.size(), n);
+  std::vector<int32_t> items((size_t)nq * n), count((size_t)nq);
+  std::vector<float> scores((size_t)nq * n);
+  TopN out;
+  if (!targets.empty()) out.target_rank.resize((size_t)nq);
+  check(goctr_recommend_walk(net.Vm(), rs.handle(), graph.handle(), users.data(), ts.empty() ? nullptr : ts.data(), nq,
+                             targets.empty() ? nullptr : targets.data(), &rcfg, &wcfg, n, pass_rows, items.data(), scores.data(),
+                             count.data(), nullptr, nullptr, targets.empty() ? nullptr : out.target_rank.data(), nullptr, nullptr,
+                             nullptr, &out.n_failed));
+  out.lists = detail::gather_lists(items, scores, count, n);
+  return out;
+}
+
+// RecommendBlendBatch with the random-walk recall as the caller's list (goctr_recommend_blend_walk): ItemCF's candidates, the n_walk
+// items the walks visit most (written and read in HBM), then the popularity list; with `rerank` and `mcfg` the diversity re-rank
+// picks the mcfg->k returned
+inline TopN RecommendBlendWalkBatch(model::CtrNet& net, RecSys& rs, const ItemCF* icf, const Popular* pop, const WalkGraph& graph,
+                                    const std::vector<int32_t>& users, int n = 10, int n_walk = 64, const std::vector<int64_t>& ts = {},
+                                    const goctr_recall_cfg& rcfg = ItemCF::DefaultRecallCfg(), int quota_pop = 0,
+                                    const goctr_walk_cfg& wcfg = WalkGraph::DefaultWalkCfg(), const ItemVectors* rerank = nullptr,
+                                    const goctr_mmr_cfg* mcfg = nullptr, const std::vector<int32_t>& targets = {}, int64_t pass_rows = 0) {
+  const int64_t nq = (int64_t)users.size();
+  const int k = rerank && mcfg ? mcfg->k : n;
+  if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("RecommendBlendWalkBatch: one timestamp per user");
+  if (!targets.empty() && targets.size() != users.size()) throw std::invalid_argument("RecommendBlendWalkBatch: one target per user");
+  if ((rerank == nullptr) != (mcfg == nullptr)) throw std::invalid_argument("RecommendBlendWalkBatch: the re-rank takes vectors and cfg");
+  if (k < 1) throw std::invalid_argument("RecommendBlendWalkBatch: n must be positive");
+  std::vector<int32_t> items((size_t)nq * k), count((size_t)nq);
+  std::vector<float> scores((size_t)nq * k);
+  TopN out;
+  if (!targets.empty()) out.target_rank.resize((size_t)nq);
+  check(goctr_recommend_blend_walk(net.Vm(), rs.handle(), icf ? icf->handle() : nullptr, pop ? pop->handle() : nullptr, users.data(),
+                                   ts.empty() ? nullptr : ts.data(), nq, targets.empty() ? nullptr : targets.data(), graph.handle(), &wcfg,
+                                   n_walk, &rcfg, quota_pop, rerank ? rerank->handle() : nullptr, mcfg, k, pass_rows, items.data(),
+                                   scores.data(), count.data(), nullptr, nullptr, nullptr,
+                                   targets.empty() ? nullptr : out.target_rank.data(), nullptr, nullptr, nullptr, nullptr, &out.n_failed,
+                                   nullptr, nullptr, nullptr));
+  out.lists = detail::gather_lists(items, scores, count, k);
+  return out;
+}
+
 // List-quality figures of returned lists (goctr_metrics_lists): `items` holds nq rows of k entries, `count` the entries in use
 // per row (empty: every row is full); vec / pop may be null (include/goctr.h says which figures are then 0 or NaN)
 struct ListQuality {

@@ -14,6 +14,10 @@ device, so that a row without history still gets candidates (tests/popular_ref.p
 ``ItemCF.swing`` is a third source of neighbour lists: Swing, item similarity from user-pair overlap, in integers throughout
 (tests/swing_ref.py is the host restatement).
 
+``WalkGraph`` is the multi-hop channel: the user-item graph of one image of the cache as two CSRs, and ``WalkGraph.recall`` walks it
+from a request row's history -- item, holder, one of the holder's items, a few steps at a time -- and ranks the items by where the
+walks land (tests/walk_ref.py is the host restatement).  ``recommend.RecommendWalk`` ranks the result with the model.
+
 ``ItemVectors`` holds the catalogue's quantised vectors (and optionally a group id per item) in HBM, and ``rerank_mmr`` picks k of
 every row's scored candidates greedily, trading relevance against similarity to what it has picked, with a cap per group
 (tests/mmr_ref.py is the host restatement).  ``recommend.RecommendDiverse`` runs it as the last step of RecommendBlend.
@@ -54,6 +58,8 @@ _USERVEC_FIELDS = _fields(capi.UservecCfg)
 _USERVEC_MULTI_FIELDS = _fields(capi.UservecMultiCfg)
 _IVF_FIELDS = _fields(capi.IvfCfg)
 _USERVEC_IVF_FIELDS = _fields(capi.UservecIvfCfg)
+_WALKGRAPH_FIELDS = _fields(capi.WalkGraphCfg)
+_WALK_FIELDS = _fields(capi.WalkCfg)
 
 
 def _as_int(name, v):
@@ -90,6 +96,8 @@ make_uservec_cfg = _make("goctr_uservec_cfg", _USERVEC_FIELDS, capi.default_user
 make_uservec_multi_cfg = _make("goctr_uservec_multi_cfg", _USERVEC_MULTI_FIELDS, capi.default_uservec_multi_cfg)
 make_ivf_cfg = _make("goctr_ivf_cfg", _IVF_FIELDS, capi.default_ivf_cfg)
 make_uservec_ivf_cfg = _make("goctr_uservec_ivf_cfg", _USERVEC_IVF_FIELDS, capi.default_uservec_ivf_cfg)
+make_walkgraph_cfg = _make("goctr_walkgraph_cfg", _WALKGRAPH_FIELDS, capi.default_walkgraph_cfg)
+make_walk_cfg = _make("goctr_walk_cfg", _WALK_FIELDS, capi.default_walk_cfg)
 
 
 def _cfg_or_kw(cfg, kw, make, name="cfg"):
@@ -293,6 +301,49 @@ class Popular(_Handle):
                    list_score=np.empty(nl, np.uint64))
         capi.check(capi.load().goctr_popular_export(self._h, capi.ptr(out["cnt"], C.c_uint32), capi.ptr(out["score"], C.c_uint64),
                                                     capi.ptr(out["list_items"], C.c_int32), capi.ptr(out["list_score"], C.c_uint64)))
+        return out
+
+
+class WalkGraph(_Handle):
+    """goctr_walkgraph: the bipartite user-item graph resident in HBM, immutable after the build and independent of the cache"""
+    _destroy = "goctr_walkgraph_destroy"
+
+    def __init__(self, ubc, n_items: int, cfg: capi.WalkGraphCfg | None = None, **kw):
+        """ubc: a ubcache.UserBehaviorCache (its device image is read) or a raw goctr_ubcache handle; ``kw``: goctr_walkgraph_cfg
+        fields (max_len, ts_lo, ts_hi)"""
+        cfg = _cfg_or_kw(cfg, kw, make_walkgraph_cfg)
+        self._h = C.c_void_p()
+        capi.check(capi.load().goctr_walkgraph_build(_cache_handle(ubc), C.c_int64(_as_int("n_items", n_items)), C.byref(cfg),
+                                                     C.byref(self._h)))
+        i = self.info()
+        self.n_users, self.n_items, self.n_edges = i["n_users"], i["n_items"], i["n_edges"]
+
+    def info(self) -> dict:
+        nu, ni, ne, v = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_uint64(0)
+        capi.check(capi.load().goctr_walkgraph_info(self._h, C.byref(nu), C.byref(ni), C.byref(ne), C.byref(v)))
+        return dict(n_users=nu.value, n_items=ni.value, n_edges=ne.value, cache_version=v.value)
+
+    def export(self) -> dict:
+        """dict(uoff int64 [n_users + 1], uitems int32 [n_edges], ioff int64 [n_items + 1], iusers int32 [n_edges])"""
+        out = dict(uoff=np.empty(self.n_users + 1, np.int64), uitems=np.empty(self.n_edges, np.int32),
+                   ioff=np.empty(self.n_items + 1, np.int64), iusers=np.empty(self.n_edges, np.int32))
+        capi.check(capi.load().goctr_walkgraph_export(self._h, capi.ptr(out["uoff"], C.c_int64), capi.ptr(out["uitems"], C.c_int32),
+                                                      capi.ptr(out["ioff"], C.c_int64), capi.ptr(out["iusers"], C.c_int32)))
+        return out
+
+    def recall(self, ubc, users, ts=None, targets=None, cfg: capi.RecallCfg | None = None, wcfg: capi.WalkCfg | None = None,
+               trace=False, **kw) -> dict:
+        """goctr_walk_recall over DENSE user rows of ``ubc``'s image.  ``kw``: goctr_recall_cfg fields and goctr_walk_cfg's (n_walks,
+        n_steps, boost, min_visits, seed).  dict(items int32 [nq, n_cand] (-1 = unused), w uint32 [nq, n_cand] (the scores S), count
+        int32 [nq], target_pos int32 [nq] when targets are given; with ``trace`` trace int32 [nq, n_walks * n_steps] (the item every
+        step recorded, or -1))"""
+        cfg, wcfg = _split_kw(cfg, wcfg, kw, _WALK_FIELDS, make_walk_cfg)
+        users, ts, targets = request_columns(users, ts, targets)
+        out = _recall_buffers(users.size, cfg.n_cand, targets)
+        if trace:
+            out["trace"] = _unwritten((users.size, min(max(int(wcfg.n_walks), 1) * max(int(wcfg.n_steps), 1), 8192)), np.int32)
+        capi.check(capi.load().goctr_walk_recall(self._h, _cache_handle(ubc), *_request_args(users, ts), C.byref(cfg), C.byref(wcfg),
+                                                 *_recall_args(out, targets), _ptr(out.get("trace"))))
         return out
 
 

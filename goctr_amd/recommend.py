@@ -27,9 +27,10 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import capi, metrics, sampling
-from .recall import (EXCLUDE, _USERVEC_FIELDS, _USERVEC_IVF_FIELDS, _USERVEC_MULTI_FIELDS, ItemCF, ItemVectors, Popular, _as_int,
-                     _cfg_or_kw, _ptr, _request_args, _split_kw, _unwritten, extra_columns, make_mmr_cfg, make_recall_cfg,
-                     make_uservec_cfg, make_uservec_ivf_cfg, make_uservec_multi_cfg, merge, request_columns)
+from .recall import (EXCLUDE, _USERVEC_FIELDS, _USERVEC_IVF_FIELDS, _USERVEC_MULTI_FIELDS, _WALK_FIELDS, ItemCF, ItemVectors, Popular,
+                     WalkGraph, _as_int, _cfg_or_kw, _ptr, _request_args, _split_kw, _unwritten, extra_columns, make_mmr_cfg,
+                     make_recall_cfg, make_uservec_cfg, make_uservec_ivf_cfg, make_uservec_multi_cfg, make_walk_cfg, merge,
+                     request_columns)
 
 # recommend/rcmd.go:19-28
 SampleAssembler = 16
@@ -547,6 +548,8 @@ _OUTPUTS = {
     "goctr_recommend_blend": _BLENDED,
     "goctr_recommend_blend_mmr": _BLENDED + ("obj", "pen", "target_place"),
     "goctr_recommend_blend_uservec": _BLENDED + ("obj", "pen", "target_place"),
+    "goctr_recommend_walk": _RANKED,
+    "goctr_recommend_blend_walk": _BLENDED + ("obj", "pen", "target_place"),
 }
 # key: (dtype, entries per request row -- "k", "n_cand" or one --, what the call must have for the array to exist)
 _COLUMNS = {
@@ -684,6 +687,30 @@ def blend_uservec(model: Predictor, icf, pop, uv, users, ts=None, targets=None, 
             C.c_int32(_as_int("n_vec", n_vec)), C.byref(cfg), C.c_int32(_as_int("quota_pop", quota_pop)),
             vectors._h if vectors is not None else None, C.byref(mcfg) if mcfg is not None else None, *_k_pass(k, pass_rows))
     return _ranked_call("goctr_recommend_blend_uservec", head, users.size, k, cfg.n_cand, targets, validate, mmr=mcfg is not None)
+
+
+def walk(model: Predictor, graph, users, ts=None, targets=None, k=10, pass_rows=0, validate=False, recall_cfg=None, wcfg=None,
+         **recall_kw):
+    """goctr_recommend_walk over DENSE indices: ``itemcf`` with the random-walk recall over ``graph`` (recall.WalkGraph) as the recall
+    stage; the same dict (cand_w holds the walk scores).  ``recall_kw``: goctr_recall_cfg fields and goctr_walk_cfg's (n_walks,
+    n_steps, boost, min_visits, seed).  What RecommendWalk / RecommendWalkBatch / EvaluateLeaveOneOutWalk call."""
+    cfg, wcfg = _split_kw(recall_cfg, wcfg, recall_kw, _WALK_FIELDS, make_walk_cfg)
+    return _uservec_call("goctr_recommend_walk", model, graph, users, ts, targets, k, pass_rows, validate, cfg, wcfg)
+
+
+def blend_walk(model: Predictor, icf, pop, graph, users, ts=None, targets=None, n_walk=64, quota_pop=0, k=10, vectors=None, pool=64,
+               lambda_q=192, max_per_group=0, pass_rows=0, validate=False, recall_cfg=None, wcfg=None, **recall_kw):
+    """goctr_recommend_blend_walk over DENSE indices: ``blend`` whose part X is the random-walk recall over ``graph``
+    (recall.WalkGraph), ``n_walk`` entries a row, written and read on the device; with ``vectors`` the MMR selection of ``diverse``
+    is the last step (pool, lambda_q, max_per_group).  The dict of ``blend``, or of ``diverse``.  What RecommendBlendWalkBatch
+    calls."""
+    cfg, wcfg = _split_kw(recall_cfg, wcfg, recall_kw, _WALK_FIELDS, make_walk_cfg)
+    users, ts, targets = request_columns(users, ts, targets)
+    mcfg = None if vectors is None else make_mmr_cfg(k=k, pool=pool, lambda_q=lambda_q, max_per_group=max_per_group)
+    head = (*_request_head(model, icf, pop), *_request_args(users, ts), capi.ptr(targets, C.c_int32), graph._h, C.byref(wcfg),
+            C.c_int32(_as_int("n_walk", n_walk)), C.byref(cfg), C.c_int32(_as_int("quota_pop", quota_pop)),
+            vectors._h if vectors is not None else None, C.byref(mcfg) if mcfg is not None else None, *_k_pass(k, pass_rows))
+    return _ranked_call("goctr_recommend_blend_walk", head, users.size, k, cfg.n_cand, targets, validate, mmr=mcfg is not None)
 
 
 # ---- raw ids in, [[ItemScore]] out: what every Recommend*Batch function does around its device call
@@ -847,7 +874,41 @@ def RecommendBlendVectorBatch(model: Predictor, icf, pop, uv, userIds, n=10, now
                                                            lambda_q, max_per_group, **recall_kw))
 
 
+def RecommendWalkBatch(model: Predictor, graph, userIds, n=10, now=None, **recall_kw):
+    """RecommendWalk for several users in one device call: [[ItemScore]] in the order of userIds.  ``now``: one timestamp for all, or
+    one per user.  A user without history, or whose history items nobody else holds, gets an empty list."""
+    users, ts = _request_rows(model, userIds, now)
+    return _serve(model, users.size, lambda: walk(model, graph, users, ts, None, n, **recall_kw))
+
+
+def RecommendWalk(model: Predictor, graph, userId: int, n=10, now=None, **recall_kw):
+    """EXTENSION -- multi-hop recall, then rank: ``n_walks`` random walks of ``n_steps`` steps start at the user's newest ``history``
+    behaviours at or before ``now`` and hop item -> a holder of it -> one of that holder's items over ``graph`` (BuildWalkGraph); the
+    ``n_cand`` items the walks visit most (with ``boost`` the visits from several history items count for more) are scored by the
+    model and the ``n`` best come back.  Unlike RecommendItemCF a candidate may be several co-occurrence hops from the history, and
+    no neighbour list was cut when the graph was built."""
+    return RecommendWalkBatch(model, graph, [userId], n, now, **recall_kw)[0]
+
+
+def RecommendBlendWalkBatch(model: Predictor, icf, pop, graph, userIds, n=10, now=None, n_walk=64, quota_pop=0, vectors=None, pool=64,
+                            lambda_q=192, max_per_group=0, **recall_kw):
+    """EXTENSION -- RecommendBlendBatch with the random-walk recall as the caller's list: ItemCF's candidates, then the ``n_walk``
+    items the walks over ``graph`` (BuildWalkGraph) visit most, then the popularity list; with ``vectors`` the diversity re-rank of
+    RecommendDiverse picks the ``n`` returned.  One device call; the walk channel's list never leaves HBM."""
+    users, ts = _request_rows(model, userIds, now)
+    return _serve(model, users.size, lambda: blend_walk(model, icf, pop, graph, users, ts, None, n_walk, quota_pop, n, vectors, pool,
+                                                        lambda_q, max_per_group, **recall_kw))
+
+
 # ---- what the recall channels are built from
+def BuildWalkGraph(recSys: DeviceRecSys, **cfg):
+    """EXTENSION: the user-item graph (recall.WalkGraph; ``cfg``: goctr_walkgraph_cfg fields -- max_len, ts_lo, ts_hi) of the recSys's
+    own behaviour cache over the rows of its item feature table -- what RecommendWalk walks.  Two sorts and two scans of the distinct
+    (user, item) entries, no pair expansion: cheap enough to rebuild after every AppendUserBehavior.  The graph is that of the cache's
+    image at THIS call."""
+    return WalkGraph(_dense_cache(recSys, "build the walk graph from"), recSys.item_table.shape[0], **cfg)
+
+
 def BuildItemCF(recSys: DeviceRecSys, **cfg):
     """EXTENSION: the ItemCF neighbour lists (recall.ItemCF; ``cfg``: goctr_itemcf_cfg fields) of the recSys's own behaviour cache
     over the rows of its item feature table -- what RecommendItemCF recalls from.  The lists are those of the cache's image at
@@ -1162,4 +1223,31 @@ def EvaluateLeaveOneOutBlendVector(model: Predictor, icf, uv, pop=None, k=10, n_
     out = _loo_figures(r, targets, model.recSys.item_table.shape[0], k, cfg.n_cand)
     if details:
         out.update(_details(r, users, targets, ts, "src"))
+    return out
+
+
+def EvaluateLeaveOneOutWalk(model: Predictor, graph=None, k=10, sample_kw=None, details=False, pass_rows=0, graph_kw=None, **recall_kw):
+    """EvaluateLeaveOneOutRecall's protocol and figures with the random-walk recall as the recall stage (goctr_recommend_walk): every
+    user's newest entry is held out (key timestamp ts - 1, DROP_SEEN_BEFORE unless ``exclude`` says otherwise) and walks from the
+    history the key sees propose ``n_cand`` candidates.  ``graph`` None: the graph is built here (``graph_kw``: goctr_walkgraph_cfg
+    fields) with a window that keeps the held-out events out of it -- ``ts_hi`` is ``sample_kw``'s ``ts_lo`` - 1 when the held-out
+    rows were drawn from a window, else the smallest held-out key timestamp (the keys carry ts - 1, so no held-out entry and nothing
+    newer is an edge) -- and closed on the way out; a caller's own ``graph`` is used as it is.  The walk itself never follows the
+    request user's own edges, so even a graph that holds the target does not hand it back in one step."""
+    users, targets, ts = _held_out_rows(model, sample_kw)
+    recall_kw.setdefault("exclude", "before")
+    cfg, wcfg = _split_kw(None, None, recall_kw, _WALK_FIELDS, make_walk_cfg)
+    own = None
+    if graph is None:
+        gkw = dict(graph_kw or {})
+        gkw.setdefault("ts_hi", int((sample_kw or {})["ts_lo"]) - 1 if "ts_lo" in (sample_kw or {}) else int(ts.min()))
+        graph = own = BuildWalkGraph(model.recSys, **gkw)
+    try:
+        r = walk(model, graph, users, ts, targets, k, pass_rows, recall_cfg=cfg, wcfg=wcfg)
+    finally:
+        if own is not None:
+            own.close()
+    out = _loo_figures(r, targets, model.recSys.item_table.shape[0], k, cfg.n_cand)
+    if details:
+        out.update(_details(r, users, targets, ts))
     return out

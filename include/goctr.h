@@ -673,6 +673,81 @@ typedef struct {
 void goctr_swing_cfg_default(goctr_swing_cfg* c);
 int  goctr_itemcf_build_swing(goctr_ubcache* c, int64_t n_items, const goctr_swing_cfg* cfg, goctr_itemcf** out);
 
+/* ---- Random-walk recall: walks over the bipartite user-item graph (no reference counterpart).  Every channel above and below
+ * reaches a candidate in ONE hop from the history: it sits in the stored list of a history item, or close to a pooled vector.  A
+ * Pixie-style walk hops item -> holder -> one of that holder's items a few steps at a time and counts where it lands, so an item
+ * two or more co-occurrence hops away is found, and nothing is cut at n_nbr when the graph is built.  The graph is two CSRs made
+ * by two sorts and two scans of the distinct (user, item) entries: no pair expansion, so a rebuild after goctr_ubcache_append is
+ * cheap.  Every output is defined bit for bit (tests/walk_ref.py is the host restatement); all arithmetic is integer.
+ *
+ * goctr_walkgraph_build:
+ *   considered     goctr_itemcf_build's rule, applied in this order: of every user the valid entries (0 <= item < n_items), newest
+ *                  first; with max_len > 0 only the first max_len of them; of those the ones with ts_lo <= ts <= ts_hi (the window
+ *                  lets an evaluation build the graph from the events before a split time).  All over ONE image of the cache
+ *   I_u            the distinct considered items of user u, ascending: uitems[uoff[u] .. uoff[u+1]); u is the dense row
+ *   U_i            the distinct users that hold i, ascending: iusers[ioff[i] .. ioff[i+1])
+ *   n_edges        the sum of |I_u| = the sum of |U_i|
+ *   info           n_users = the image's rows, cache_version = the image's
+ *   refused        (-1, *out untouched) a cfg outside its ranges, reserved != 0, ts_lo > ts_hi; n_items <= 0 or > 2^31 - 1; an
+ *                  image of 2^31 or more entries or users
+ * An empty cache is not an error.  The handle is immutable and independent of the cache.  No output byte depends on a tile or pass
+ * size or on the arrival order of atomics (they count integers). */
+typedef struct {
+  int32_t max_len;        /* >= 0; 0 = all                         default 0 */
+  int32_t reserved;       /* must be 0 */
+  int64_t ts_lo, ts_hi;   /* entries with ts_lo <= ts <= ts_hi     default INT64_MIN, INT64_MAX */
+} goctr_walkgraph_cfg;
+void goctr_walkgraph_cfg_default(goctr_walkgraph_cfg* c);
+typedef struct goctr_walkgraph goctr_walkgraph;
+int  goctr_walkgraph_build(goctr_ubcache* c, int64_t n_items, const goctr_walkgraph_cfg* cfg, goctr_walkgraph** out);
+void goctr_walkgraph_destroy(goctr_walkgraph* g);
+/* each may be NULL */
+int  goctr_walkgraph_info(goctr_walkgraph* g, int64_t* n_users, int64_t* n_items, int64_t* n_edges, uint64_t* cache_version);
+/* each may be NULL */
+int  goctr_walkgraph_export(goctr_walkgraph* g, int64_t* uoff /*[n_users+1]*/, int32_t* uitems /*[n_edges]*/,
+                            int64_t* ioff /*[n_items+1]*/, int32_t* iusers /*[n_edges]*/);
+
+/* goctr_walk_recall, for request row q over the ONE image of the cache the call holds:
+ *   history        exactly goctr_itemcf_recall's with n_items = the graph's: h_0 .. h_{H-1}; a repeated item takes a slot each
+ *                  time.  With H = 0 the row returns count 0
+ *   random word    X(w,s,a) = mix(seed ^ mix((((uint64)(uint32) users[q] << 32) | w) ^ mix(((uint64) s << 32) | a))), mix = the
+ *                  negative sampler's single splitmix64 step.  The word depends on the user, not on q: the same user in two rows
+ *                  walks the same walks
+ *   pick           idx(x, d) = ((x >> 32) * d) >> 32
+ *   walk w         (0 .. n_walks-1) slot t = w mod H, current item i = h_t.  For s = 0 .. n_steps-1: d = |U_i| in the graph; d = 0
+ *                  ends the walk (an item the graph does not know is a dead end); u = U_i[idx(X(w,s,0), d)]; if u = users[q] no
+ *                  visit is recorded, i stays and the step is spent -- the request's own edges never hand the user its own items
+ *                  back, nor in leave-one-out the held-out target; otherwise j = I_u[idx(X(w,s,1), |I_u|)], one visit of j is
+ *                  recorded for slot t and i = j.  out_trace[q][w * n_steps + s] = j for a recorded step, -1 for a spent step or
+ *                  a step behind the walk's end
+ *   counts         c_t(j) = the recorded visits of j from slot t; c(j) = their sum over t, at most 8192
+ *   score          boost 0: S(j) = c(j).  boost 1: r_t = the largest integer with r_t^2 <= c_t(j) 2^32, R = the sum of r_t over
+ *                  t, S(j) = (R^2 + 2^31) >> 32 in 64-bit integers.  R^2 <= 2^32 H c(j) <= 2^53 and S <= 2^21.  Visits from one slot
+ *                  give S = c(j) exactly; visits spread over several history slots outrank the same number from one
+ *   candidates     every j with c(j) >= min_visits that is not seen; seen is goctr_itemcf_recall's rule under cfg->exclude, the
+ *                  target exemption included
+ *   order          S descending, then item ascending; the first cfg->n_cand are kept.  Outputs and padding as goctr_itemcf_recall's
+ *   refused        (-1, nothing touched) goctr_itemcf_recall's refusals; a NULL graph or cache; a wcfg outside its ranges, n_walks *
+ *                  n_steps over 8192, reserved != 0; a graph whose n_users differs from the cache's or on another engine
+ * One workgroup walks a row; threads own walks.  No output byte depends on how walks are dealt to threads, on the workgroup size
+ * or on an arrival order: a visit has a fixed place (w * n_steps + s) and the counts are run lengths of one sorted list.  Host
+ * arrays, the engine stream and the engine lock, like goctr_itemcf_recall.
+ * Not covered: degree-weighted walk allocation, restarts and early stopping, edge weights, pruning of high-degree nodes. */
+typedef struct {
+  int32_t  n_walks;     /* 1 .. 2048                                  default 512 */
+  int32_t  n_steps;     /* 1 .. 16; n_walks * n_steps <= 8192         default 4   */
+  int32_t  boost;       /* 0 = visit counts, 1 = multi-hit boost      default 1   */
+  int32_t  min_visits;  /* 1 .. 8192                                  default 1   */
+  uint64_t seed;        /*                                            default 0   */
+  int64_t  reserved;    /* must be 0 */
+} goctr_walk_cfg;
+void goctr_walk_cfg_default(goctr_walk_cfg* c);
+int  goctr_walk_recall(goctr_walkgraph* g, goctr_ubcache* c, const int32_t* users, const int64_t* ts /* NULL = 0 */,
+                       int64_t n_req, const goctr_recall_cfg* cfg, const goctr_walk_cfg* wcfg,
+                       int32_t* out_items /*[n_req,n_cand]*/, uint32_t* out_w /*[n_req,n_cand]*/, int32_t* out_count /*[n_req]*/,
+                       const int32_t* targets /*[n_req] or NULL*/, int32_t* out_target_pos /*[n_req] or NULL*/,
+                       int32_t* out_trace /*[n_req, n_walks*n_steps] or NULL*/);
+
 /* ---- Diversity re-rank: maximal marginal relevance over item vectors, with group caps (no reference counterpart).  The recall
  * channels above return items close to the user's history, so the best k by score are typically one cluster.  A goctr_itemvec holds
  * the catalogue's quantised vectors (and optionally a group id per item) in HBM; goctr_rerank_mmr picks k of a row's scored
@@ -898,6 +973,39 @@ int goctr_recommend_blend_uservec(goctr_model* m, goctr_recsys* r, goctr_itemcf*
                                   uint8_t* out_src, int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank,
                                   int32_t* cand_items, uint32_t* cand_w, float* cand_scores, uint8_t* cand_src, int64_t* n_failed,
                                   int32_t* out_obj, uint32_t* out_pen, int32_t* out_target_place);
+
+/* goctr_recommend_walk: goctr_recommend_itemcf with the random-walk recall (goctr_walk_recall above) as its recall stage, over the
+ * recsys's cache image.  The outputs and every documented property of that call hold unchanged: scores bit-identical to
+ * goctr_batch_predict below 8192 rows per pass, failed candidates, out_target_rank, and a recsys without a cache returns empty rows.
+ *   refused        goctr_recommend_itemcf's refusals, the wcfg refusals above, and a graph whose n_items or n_users differs from
+ *                  the recsys's */
+int goctr_recommend_walk(goctr_model* m, goctr_recsys* r, goctr_walkgraph* g,
+                         const int32_t* users, const int64_t* ts /* NULL = 0 */, int64_t n_req,
+                         const int32_t* targets /* [n_req] or NULL */, const goctr_recall_cfg* recall_cfg,
+                         const goctr_walk_cfg* wcfg, int32_t k, int64_t pass_rows,
+                         int32_t* out_items /* [n_req,k] */, float* out_scores /* [n_req,k] */, int32_t* out_count,
+                         int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank,
+                         int32_t* cand_items, uint32_t* cand_w, float* cand_scores, int64_t* n_failed);
+
+/* goctr_recommend_blend_walk: the blend with the random-walk recall as its part X, defined by composition as
+ * goctr_recommend_blend_uservec is.  The result equals goctr_recommend_blend (v and cfg both NULL) or goctr_recommend_blend_mmr (both
+ * given; k is then ignored, cfg->k holds) called with n_extra = n_walk and extra row q = the items of goctr_walk_recall's row q for
+ * the same users, ts and targets under {recall_cfg->history, n_cand = n_walk, recall_cfg->exclude} and wcfg, over the same cache
+ * image, padded with -1.  The list never leaves the device: the recall writes into the buffer the blend's part X reads.  Items from
+ * this channel carry source 1.  Without the re-rank out_obj, out_pen and out_target_place are not touched.
+ *   refused        goctr_recommend_blend's (or _blend_mmr's) refusals; the wcfg refusals above; a NULL g or wcfg; n_walk outside
+ *                  1 .. 1024; v without cfg or cfg without v; a graph whose n_items or n_users differs from the recsys's
+ * A recsys without a cache has no history: part X is empty. */
+int goctr_recommend_blend_walk(goctr_model* m, goctr_recsys* r, goctr_itemcf* icf /* may be NULL */, goctr_popular* pop /* may be NULL */,
+                               const int32_t* users, const int64_t* ts /* NULL = 0 */, int64_t n_req,
+                               const int32_t* targets /* [n_req] or NULL */,
+                               goctr_walkgraph* g, const goctr_walk_cfg* wcfg, int32_t n_walk /* 1 .. 1024 */,
+                               const goctr_recall_cfg* recall_cfg, int32_t quota_pop /* 0 .. recall_cfg->n_cand */,
+                               goctr_itemvec* v /* or NULL */, const goctr_mmr_cfg* cfg /* or NULL */, int32_t k, int64_t pass_rows,
+                               int32_t* out_items /* [n_req,k] */, float* out_scores /* [n_req,k] */, int32_t* out_count,
+                               uint8_t* out_src, int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank,
+                               int32_t* cand_items, uint32_t* cand_w, float* cand_scores, uint8_t* cand_src, int64_t* n_failed,
+                               int32_t* out_obj, uint32_t* out_pen, int32_t* out_target_place);
 
 /* ---- Multi-interest user-vector recall: the history clustered into up to 8 interest vectors, one list each, mixed into one (no
  * reference counterpart).  A user with two tastes pools to a vector between them and the larger taste takes the whole list; here
