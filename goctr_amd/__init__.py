@@ -8,7 +8,7 @@ Package layout (only what the path needs):
   recommend.py     host mirror of the recommend package: SampleInfo / TrainSample / Fitter / PredictAbstract, GetSample, Train,
                    BatchPredict, Rank; and what the reference leaves open: Recommend* (top-N and recall-then-rank over raw
                    ids), the Build* of the recall channels, the EvaluateLeaveOneOut* protocol
-  recall.py        the recall channels over dense rows: ItemCF / Popular / WalkGraph / ItemVectors / VectorIndex handles, the blend, the
+  recall.py        the recall channels over dense rows: ItemCF / Popular / WalkGraph / ALS / ItemVectors / VectorIndex handles, the blend, the
                    MMR re-rank, every make_*_cfg; recommend.py's recall-then-rank calls are built from its helpers
   sampling.py      labelled sample keys drawn on the device from the behaviour cache (Samples)
   ubcache.py       host mirror of feature/ubcache (TimeSeq, UserBehaviorCache) with its image in HBM

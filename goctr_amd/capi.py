@@ -228,6 +228,12 @@ class WalkCfg(C.Structure):
                 ("seed", C.c_uint64), ("reserved", C.c_int64)]
 
 
+class AlsCfg(C.Structure):
+    """goctr_als_cfg (include/goctr.h)"""
+    _fields_ = [("D", C.c_int32), ("n_iters", C.c_int32), ("alpha", C.c_double), ("lambda_", C.c_double), ("seed", C.c_uint64),
+                ("reserved", C.c_int64)]
+
+
 class MmrCfg(C.Structure):
     """goctr_mmr_cfg (include/goctr.h)"""
     _fields_ = [("k", C.c_int32), ("pool", C.c_int32), ("lambda_q", C.c_int32), ("max_per_group", C.c_int32)]
@@ -336,6 +342,9 @@ SYMBOLS = [
     "goctr_swing_cfg_default", "goctr_itemcf_build_swing",
     "goctr_walkgraph_cfg_default", "goctr_walkgraph_build", "goctr_walkgraph_destroy", "goctr_walkgraph_info", "goctr_walkgraph_export",
     "goctr_walk_cfg_default", "goctr_walk_recall", "goctr_recommend_walk", "goctr_recommend_blend_walk",
+    "goctr_als_cfg_default", "goctr_als_create", "goctr_als_destroy", "goctr_als_step", "goctr_als_fit", "goctr_als_loss", "goctr_als_info",
+    "goctr_als_export", "goctr_als_set_factors", "goctr_itemvec_build_als", "goctr_itemcf_build_als", "goctr_als_foldin",
+    "goctr_als_recall", "goctr_recommend_als", "goctr_recommend_blend_als",
     "goctr_uservec_cfg_default", "goctr_uservec_recall", "goctr_recommend_uservec", "goctr_recommend_blend_uservec",
     "goctr_uservec_multi_cfg_default", "goctr_uservec_interests", "goctr_uservec_recall_multi", "goctr_recommend_uservec_multi",
     "goctr_ivf_cfg_default", "goctr_itemvec_index_build", "goctr_itemvec_index_destroy", "goctr_itemvec_index_info",
@@ -367,7 +376,8 @@ def load() -> C.CDLL:
                      "goctr_swing_cfg_default", "goctr_uservec_cfg_default", "goctr_uservec_multi_cfg_default",
                      "goctr_ivf_cfg_default", "goctr_uservec_ivf_cfg_default", "goctr_itemvec_index_destroy",
                      "goctr_calib_cfg_default", "goctr_calibrator_destroy", "goctr_boot_cfg_default",
-                     "goctr_walkgraph_cfg_default", "goctr_walk_cfg_default", "goctr_walkgraph_destroy"):
+                     "goctr_walkgraph_cfg_default", "goctr_walk_cfg_default", "goctr_walkgraph_destroy",
+                     "goctr_als_cfg_default", "goctr_als_destroy"):
             getattr(_lib, name).restype = None
         _bm = C.POINTER(BinaryMetrics)
         _lib.goctr_metrics_binary.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, _bm]
@@ -518,6 +528,28 @@ def load() -> C.CDLL:
                                                     C.c_void_p, _wk, C.c_int32, C.POINTER(RecallCfg), C.c_int32, C.c_void_p, _mmr,
                                                     C.c_int32, C.c_int64, _i32, _f32, _i32, _u8, _i32, _i32, _i64, _i32, _u32, _f32,
                                                     _u8, _i64, _i32, _u32, _i32]
+        _als, _f64, _i16 = C.POINTER(AlsCfg), C.POINTER(C.c_double), C.POINTER(C.c_int16)
+        _lib.goctr_als_cfg_default.argtypes = [_als]
+        _lib.goctr_als_create.argtypes = [C.c_void_p, _als, C.POINTER(C.c_void_p)]
+        _lib.goctr_als_destroy.argtypes = [C.c_void_p]
+        _lib.goctr_als_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        _lib.goctr_als_fit.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.goctr_als_loss.argtypes = [C.c_void_p, C.c_void_p, _f64]
+        _lib.goctr_als_info.argtypes = [C.c_void_p, _i64, _i64, _i32, _i64]
+        _lib.goctr_als_export.argtypes = [C.c_void_p, _f64, _f64]
+        _lib.goctr_als_set_factors.argtypes = [C.c_void_p, _f64, _f64]
+        _lib.goctr_itemvec_build_als.argtypes = [C.c_void_p, _i32, C.POINTER(C.c_void_p)]
+        _lib.goctr_itemcf_build_als.argtypes = [C.c_void_p, C.POINTER(ItemnbrCfg), C.POINTER(C.c_void_p)]
+        _lib.goctr_als_foldin.argtypes = [C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, C.c_int32, _f64, _i16, _i32]
+        _lib.goctr_als_recall.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, C.POINTER(RecallCfg), _uv, _i32,
+                                          _u32, _i32, _i32, _i32, _i16, _f64]
+        _lib.goctr_recommend_als.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32,
+                                             C.POINTER(RecallCfg), _uv, C.c_int32, C.c_int64, _i32, _f32, _i32, _i32, _i32, _i64,
+                                             _i32, _u32, _f32, _i64]
+        _lib.goctr_recommend_blend_als.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32,
+                                                   C.c_void_p, C.c_void_p, _uv, C.c_int32, C.POINTER(RecallCfg), C.c_int32, C.c_void_p,
+                                                   _mmr, C.c_int32, C.c_int64, _i32, _f32, _i32, _u8, _i32, _i32, _i64, _i32, _u32,
+                                                   _f32, _u8, _i64, _i32, _u32, _i32]
         _um = C.POINTER(UservecMultiCfg)
         _lib.goctr_uservec_multi_cfg_default.argtypes = [_um]
         _lib.goctr_uservec_interests.argtypes = [C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, C.POINTER(RecallCfg), _um, _i32,
@@ -663,6 +695,8 @@ default_list_cfg = _default(ListCfg, "goctr_list_cfg_default")
 default_popular_cfg = _default(PopularCfg, "goctr_popular_cfg_default")
 default_walkgraph_cfg = _default(WalkGraphCfg, "goctr_walkgraph_cfg_default")
 default_walk_cfg = _default(WalkCfg, "goctr_walk_cfg_default")
+default_als_cfg = _default(AlsCfg, "goctr_als_cfg_default")
+ALS_USERS, ALS_ITEMS = 0, 1                 # goctr_als_step's sides
 
 
 PROF_COUNT = 18          # GOCTR_K_COUNT (include/goctr.h)

@@ -22,6 +22,7 @@
 #include <shared_mutex>
 
 #define GOCTR_NO_PLAIN_KERNELS      // the kernel headers' plain kernels belong to ctr.hip
+#include "als.h"
 #include "itemcf.h"
 #include "itemvec.h"
 
@@ -316,6 +317,20 @@ int goctr_itemcf_build_emb(goctr_emb* e, int64_t n_items, const goctr_itemnbr_cf
   EmbRowsRead rd(e);                           // (behind the buffers: itemvec.h says what it holds and in which order it lets go)
   if (rd.wait(e)) return -1;
   if (build_from_rows<float>(e->rows.p, n_items, e->D, cfg, ws, r.get(), [&] { return rd.done(); })) return -1;
+  *out = r.release();
+  return 0;
+}
+
+// the item factors of an ALS handle, device to device (the engine lock keeps a step from writing them meanwhile)
+int goctr_itemcf_build_als(goctr_als* a, const goctr_itemnbr_cfg* cfg, goctr_itemcf** out) {
+  GOCTR_ENTER_H(a);
+  const char* who = "goctr_itemcf_build_als";
+  GOCTR_CHECK(a && cfg && out, "%s: null argument", who);
+  if (check_cfg(cfg, who) || iv_check_shape(a->n_items, a->D, who)) return -1;
+  std::unique_ptr<goctr_itemcf> r(new goctr_itemcf);
+  NbrBuild ws;
+  StreamDrain drain{engine().stream};          // (behind the buffers: runs before they are released)
+  if (build_from_rows<double>(a->Y.p, a->n_items, a->D, cfg, ws, r.get(), [] { return 0; })) return -1;
   *out = r.release();
   return 0;
 }

@@ -5,6 +5,7 @@
 #include "itemcf.h"
 #include "uservec.h"
 #include "walk.h"
+#include "als.h"
 
 // time-decayed item popularity resident in HBM; immutable after the build, independent of the cache it was built from
 struct goctr_popular {
@@ -29,6 +30,8 @@ struct BlendArgs {
   const goctr_itemvec* uv = nullptr; goctr_uservec_cfg ucfg{};
   // goctr_recommend_blend_walk's alone: part X's list is the random-walk recall's, written the same way
   const goctr_walkgraph* wg = nullptr; goctr_walk_cfg wcfg{};
+  // goctr_recommend_blend_als's alone: part X's list is the fold-in recall's over uv under ucfg, written the same way
+  const goctr_als* als = nullptr;
 };
 
 // the refusals that need no slot (sets the error text); `who`: the entry's name, goctr_recommend_blend or goctr_recommend_blend_mmr

@@ -277,7 +277,13 @@ int blend_recommend_run(const TopnScorer& sc, const char* who, const BlendArgs& 
   DevBuf<unsigned int> x_w;
   UvScratch uv_ws;
   return recall_rank_run(sc, who, a, true, [&](const RecallInputs& in, const RecallRows& o, hipStream_t st) {
-    if (b.uv) {                               // part X's list comes from the user-vector recall, straight into d_extra
+    if (b.als) {                              // part X's list comes from the ALS fold-in recall over b.uv, straight into d_extra
+      const size_t n = (size_t)a.n_req * (size_t)b.n_extra;
+      if (d_extra.alloc(n, false) || x_w.alloc(n, false) || x_count.alloc((size_t)a.n_req, false)) return -1;
+      const goctr_recall_cfg xcfg{a.rcfg.history, b.n_extra, a.rcfg.exclude};
+      if (als_launch(b.als, b.uv, sc.ub_off, sc.ub_items, sc.ub_ts, in, a.targets != nullptr, a.n_req, xcfg, b.ucfg, b.n_extra,
+                     d_extra.p, x_w.p, x_count.p, nullptr, nullptr, nullptr, uv_ws, st)) return -1;
+    } else if (b.uv) {                        // ... or from the user-vector recall
       const size_t n = (size_t)a.n_req * (size_t)b.n_extra;
       if (d_extra.alloc(n, false) || x_w.alloc(n, false) || x_count.alloc((size_t)a.n_req, false)) return -1;
       const goctr_recall_cfg xcfg{a.rcfg.history, b.n_extra, a.rcfg.exclude};

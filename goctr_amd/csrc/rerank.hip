@@ -21,6 +21,7 @@
 #include <vector>
 
 #define GOCTR_NO_PLAIN_KERNELS      // the kernel headers' plain kernels belong to ctr.hip
+#include "als.h"
 #include "itemcf.h"
 #include "itemvec.h"
 
@@ -289,6 +290,19 @@ int goctr_itemvec_build_emb(goctr_emb* e, int64_t n_items, const int32_t* groups
   EmbRowsRead rd(e);                           // (behind the handle's buffers: itemvec.h says what it holds and in which order it lets go)
   if (rd.wait(e)) return -1;
   if (build_from_rows<float>(e->rows.p, n_items, e->D, groups, r.get(), [&] { return rd.done(); })) return -1;
+  *out = r.release();
+  return 0;
+}
+
+// the item factors of an ALS handle, device to device (the engine lock keeps a step from writing them meanwhile)
+int goctr_itemvec_build_als(goctr_als* a, const int32_t* groups, goctr_itemvec** out) {
+  GOCTR_ENTER_H(a);
+  const char* who = "goctr_itemvec_build_als";
+  GOCTR_CHECK(a && out, "%s: null argument", who);
+  if (iv_check_shape(a->n_items, a->D, who)) return -1;
+  std::unique_ptr<goctr_itemvec> r(new goctr_itemvec);
+  StreamDrain drain{engine().stream};          // (behind the buffers: runs before they are released)
+  if (build_from_rows<double>(a->Y.p, a->n_items, a->D, groups, r.get(), [] { return 0; })) return -1;
   *out = r.release();
   return 0;
 }

@@ -23,6 +23,7 @@
 #include "uservec_ivf.h"
 #include "uservec_multi.h"
 #include "walk.h"
+#include "als.h"
 
 // ------------------------------------------------------------------ serving: recommend.BatchPredict / Rank / Predict
 // recommend/rcmd.go:248-337: sample keys -> GetSampleVector rows -> PredictAbstract.Predict -> scores, called from concurrent
@@ -769,6 +770,64 @@ int goctr_recommend_blend_walk(goctr_model* m, goctr_recsys* r, goctr_itemcf* ic
                         out_cand_count, out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed, out_src, cand_src};
   BlendArgs b{icf, pop, nullptr, n_walk, quota_pop};
   b.wg = g; b.wcfg = *wcfg;
+  if (blend_check_recommend(who, b, a, r->n_users, r->n_items)) return -1;
+  if (!v) return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return blend_recommend_run(sc, who, b, a); });
+  const RerankStage rr{v, *cfg, out_obj, out_pen, out_target_place};
+  return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return blend_recommend_run(sc, who, b, a, &rr); });
+}
+
+// goctr_recommend_itemcf with the ALS fold-in recall (als.hip) as the driver's recall stage
+int goctr_recommend_als(goctr_model* m, goctr_recsys* r, goctr_als* als, goctr_itemvec* v, const int32_t* users, const int64_t* ts,
+                        int64_t n_req, const int32_t* targets, const goctr_recall_cfg* recall_cfg, const goctr_uservec_cfg* ucfg,
+                        int32_t k, int64_t pass_rows, int32_t* out_items, float* out_scores, int32_t* out_count,
+                        int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank, int32_t* cand_items,
+                        uint32_t* cand_w, float* cand_scores, int64_t* n_failed) {
+  EngineScope on(handle_engine(m));
+  if (require_engine()) return -1;
+  const char* who = "goctr_recommend_als";
+  GOCTR_CHECK(m && r && als && v && recall_cfg && ucfg, "%s: bad arguments", who);
+  GOCTR_SAME_ENGINE(m, r);
+  GOCTR_SAME_ENGINE(m, als);
+  GOCTR_SAME_ENGINE(m, v);
+  if (check_recsys_dims(who, m, r)) return -1;
+  const ItemcfRecArgs a{users, ts, n_req, targets, *recall_cfg, k, pass_rows, out_items, out_scores, out_count, out_cand_count,
+                        out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed};
+  if (als_check_recommend(who, als, v, ucfg, a, r->n_users, r->n_items)) return -1;
+  return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return als_recommend_run(sc, als, v, *ucfg, a); });
+}
+
+// goctr_recommend_blend / _blend_mmr with the ALS fold-in recall writing part X's list on the device
+int goctr_recommend_blend_als(goctr_model* m, goctr_recsys* r, goctr_itemcf* icf, goctr_popular* pop, const int32_t* users,
+                              const int64_t* ts, int64_t n_req, const int32_t* targets, goctr_als* als, goctr_itemvec* uv,
+                              const goctr_uservec_cfg* ucfg, int32_t n_als, const goctr_recall_cfg* recall_cfg, int32_t quota_pop,
+                              goctr_itemvec* v, const goctr_mmr_cfg* cfg, int32_t k, int64_t pass_rows, int32_t* out_items,
+                              float* out_scores, int32_t* out_count, uint8_t* out_src, int32_t* out_cand_count,
+                              int32_t* out_target_pos, int64_t* out_target_rank, int32_t* cand_items, uint32_t* cand_w,
+                              float* cand_scores, uint8_t* cand_src, int64_t* n_failed, int32_t* out_obj, uint32_t* out_pen,
+                              int32_t* out_target_place) {
+  EngineScope on(handle_engine(m));
+  if (require_engine()) return -1;
+  const char* who = "goctr_recommend_blend_als";
+  GOCTR_CHECK(m && r && recall_cfg && als && uv && ucfg, "%s: bad arguments", who);
+  GOCTR_CHECK((v != nullptr) == (cfg != nullptr), "%s: the re-rank takes both the item vectors and the cfg, or neither", who);
+  GOCTR_SAME_ENGINE(m, r);
+  GOCTR_SAME_ENGINE(m, icf);
+  GOCTR_SAME_ENGINE(m, pop);
+  GOCTR_SAME_ENGINE(m, als);
+  GOCTR_SAME_ENGINE(m, uv);
+  GOCTR_SAME_ENGINE(m, v);
+  if (check_recsys_dims(who, m, r)) return -1;
+  GOCTR_CHECK(n_als >= 1 && n_als <= 1024, "%s: n_als = %d is outside 1 .. 1024", who, n_als);
+  if (uservec_check_cfg(ucfg, who) || als_check_vectors(who, als, uv, r->n_items)) return -1;
+  if (v) {
+    if (mmr_check_cfg(v, cfg, who)) return -1;
+    GOCTR_CHECK(v->n_items == r->n_items, "%s: the item vectors cover %lld items, the recsys %lld", who, (long long)v->n_items,
+                (long long)r->n_items);
+  }
+  const ItemcfRecArgs a{users, ts, n_req, targets, *recall_cfg, v ? cfg->k : k, pass_rows, out_items, out_scores, out_count,
+                        out_cand_count, out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed, out_src, cand_src};
+  BlendArgs b{icf, pop, nullptr, n_als, quota_pop};
+  b.uv = uv; b.ucfg = *ucfg; b.als = als;
   if (blend_check_recommend(who, b, a, r->n_users, r->n_items)) return -1;
   if (!v) return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return blend_recommend_run(sc, who, b, a); });
   const RerankStage rr{v, *cfg, out_obj, out_pen, out_target_place};

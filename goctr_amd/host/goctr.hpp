@@ -1051,6 +1051,107 @@ inline TopN RecommendBlendWalkBatch(model::CtrNet& net, RecSys& rs, const ItemCF
   return out;
 }
 
+// Implicit-feedback ALS factors over a WalkGraph's edges (goctr_als_*): fitted here, the item factors quantised device to device
+// (goctr_itemvec_build_als), a request row folded in from the cache at request time and ranked by cosine against them.  The graph
+// must outlive Fit(); the serving calls need only this object
+class ALS {
+ public:
+  static goctr_als_cfg DefaultCfg() { goctr_als_cfg c; goctr_als_cfg_default(&c); return c; }
+  static goctr_uservec_cfg DefaultScanCfg() { goctr_uservec_cfg c; goctr_uservec_cfg_default(&c); return c; }
+  explicit ALS(const WalkGraph& graph, const goctr_als_cfg& cfg = DefaultCfg()) : graph_(graph.handle()) {
+    check(goctr_als_create(graph_, &cfg, &h_));
+  }
+  ALS(const ALS&) = delete;
+  ALS& operator=(const ALS&) = delete;
+  ALS(ALS&& o) noexcept : h_(o.h_), graph_(o.graph_), vec_(o.vec_) { o.h_ = nullptr; o.vec_ = nullptr; }
+  ~ALS() { goctr_itemvec_destroy(vec_); goctr_als_destroy(h_); }
+  goctr_als* handle() const { return h_; }
+  goctr_itemvec* vectors() const { return vec_; }             // null before Fit()
+  // cfg.n_iters iterations, then the item factors as quantised vectors
+  void Fit() {
+    check(goctr_als_fit(h_, graph_));
+    goctr_itemvec_destroy(vec_);
+    vec_ = nullptr;
+    check(goctr_itemvec_build_als(h_, nullptr, &vec_));
+  }
+  void Step(int32_t side) { check(goctr_als_step(h_, graph_, side)); }
+  double Loss() const { double v = 0; check(goctr_als_loss(h_, graph_, &v)); return v; }
+  struct Info { int64_t n_users, n_items; int32_t D; int64_t half_steps; };
+  Info info() const {
+    Info i{};
+    check(goctr_als_info(h_, &i.n_users, &i.n_items, &i.D, &i.half_steps));
+    return i;
+  }
+  // X [n_users, D], Y [n_items, D]
+  void Export(std::vector<double>& X, std::vector<double>& Y) const {
+    const Info i = info();
+    X.resize((size_t)i.n_users * i.D); Y.resize((size_t)i.n_items * i.D);
+    check(goctr_als_export(h_, X.data(), Y.data()));
+  }
+  // x [nq, D]: every row's vector from its `history` newest entries at or before ts
+  void FoldIn(goctr_ubcache* cache, const std::vector<int32_t>& users, const std::vector<int64_t>& ts, int history,
+              std::vector<double>& x, std::vector<int32_t>& n_used) const {
+    if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("ALS::FoldIn: one timestamp per user");
+    x.resize(users.size() * (size_t)info().D); n_used.resize(users.size());
+    check(goctr_als_foldin(h_, cache, users.data(), ts.empty() ? nullptr : ts.data(), (int64_t)users.size(), history, x.data(), nullptr,
+                           n_used.data()));
+  }
+
+ private:
+  goctr_als* h_ = nullptr;
+  goctr_walkgraph* graph_ = nullptr;
+  goctr_itemvec* vec_ = nullptr;
+};
+
+// RecommendItemCFBatch with the ALS fold-in recall as the recall stage (goctr_recommend_als); `als` has been fitted
+inline TopN RecommendALSBatch(model::CtrNet& net, RecSys& rs, const ALS& als, const std::vector<int32_t>& users, int n = 10,
+                              const std::vector<int64_t>& ts = {}, const goctr_recall_cfg& rcfg = ItemCF::DefaultRecallCfg(),
+                              const goctr_uservec_cfg& ucfg = ALS::DefaultScanCfg(), const std::vector<int32_t>& targets = {},
+                              int64_t pass_rows = 0) {
+  const int64_t nq = (int64_t)users.size();
+  detail::check_request("RecommendALSBatch", users.size(), ts.size(), targets.size(), n);
+  if (!als.vectors()) throw std::invalid_argument("RecommendALSBatch: the factors have not been fitted");
+  std::vector<int32_t> items((size_t)nq * n), count((size_t)nq);
+  std::vector<float> scores((size_t)nq * n);
+  TopN out;
+  if (!targets.empty()) out.target_rank.resize((size_t)nq);
+  check(goctr_recommend_als(net.Vm(), rs.handle(), als.handle(), als.vectors(), users.data(), ts.empty() ? nullptr : ts.data(), nq,
+                            targets.empty() ? nullptr : targets.data(), &rcfg, &ucfg, n, pass_rows, items.data(), scores.data(),
+                            count.data(), nullptr, nullptr, targets.empty() ? nullptr : out.target_rank.data(), nullptr, nullptr,
+                            nullptr, &out.n_failed));
+  out.lists = detail::gather_lists(items, scores, count, n);
+  return out;
+}
+
+// RecommendBlendBatch with the ALS fold-in recall as the caller's list (goctr_recommend_blend_als): ItemCF's candidates, the n_als
+// items closest to the folded-in vector (written and read in HBM), then the popularity list, which carries the popularity part
+// the cosine ranking drops; with `rerank` and `mcfg` the diversity re-rank picks the mcfg->k returned
+inline TopN RecommendBlendALSBatch(model::CtrNet& net, RecSys& rs, const ItemCF* icf, const Popular* pop, const ALS& als,
+                                   const std::vector<int32_t>& users, int n = 10, int n_als = 64, const std::vector<int64_t>& ts = {},
+                                   const goctr_recall_cfg& rcfg = ItemCF::DefaultRecallCfg(), int quota_pop = 0,
+                                   const goctr_uservec_cfg& ucfg = ALS::DefaultScanCfg(), const ItemVectors* rerank = nullptr,
+                                   const goctr_mmr_cfg* mcfg = nullptr, const std::vector<int32_t>& targets = {}, int64_t pass_rows = 0) {
+  const int64_t nq = (int64_t)users.size();
+  const int k = rerank && mcfg ? mcfg->k : n;
+  if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("RecommendBlendALSBatch: one timestamp per user");
+  if (!targets.empty() && targets.size() != users.size()) throw std::invalid_argument("RecommendBlendALSBatch: one target per user");
+  if ((rerank == nullptr) != (mcfg == nullptr)) throw std::invalid_argument("RecommendBlendALSBatch: the re-rank takes vectors and cfg");
+  if (k < 1) throw std::invalid_argument("RecommendBlendALSBatch: n must be positive");
+  if (!als.vectors()) throw std::invalid_argument("RecommendBlendALSBatch: the factors have not been fitted");
+  std::vector<int32_t> items((size_t)nq * k), count((size_t)nq);
+  std::vector<float> scores((size_t)nq * k);
+  TopN out;
+  if (!targets.empty()) out.target_rank.resize((size_t)nq);
+  check(goctr_recommend_blend_als(net.Vm(), rs.handle(), icf ? icf->handle() : nullptr, pop ? pop->handle() : nullptr, users.data(),
+                                  ts.empty() ? nullptr : ts.data(), nq, targets.empty() ? nullptr : targets.data(), als.handle(),
+                                  als.vectors(), &ucfg, n_als, &rcfg, quota_pop, rerank ? rerank->handle() : nullptr, mcfg, k, pass_rows,
+                                  items.data(), scores.data(), count.data(), nullptr, nullptr, nullptr,
+                                  targets.empty() ? nullptr : out.target_rank.data(), nullptr, nullptr, nullptr, nullptr, &out.n_failed,
+                                  nullptr, nullptr, nullptr));
+  out.lists = detail::gather_lists(items, scores, count, k);
+  return out;
+}
+
 // List-quality figures of returned lists (goctr_metrics_lists): `items` holds nq rows of k entries, `count` the entries in use
 // per row (empty: every row is full); vec / pop may be null (include/goctr.h says which figures are then 0 or NaN)
 struct ListQuality {

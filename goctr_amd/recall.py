@@ -347,6 +347,111 @@ class WalkGraph(_Handle):
         return out
 
 
+_ALS_FIELDS = _fields(capi.AlsCfg)
+
+
+def make_als_cfg(**kw) -> capi.AlsCfg:
+    """goctr_als_cfg from keywords: D, n_iters, seed (integers), alpha, lambda_ (numbers; ``lambda`` is Python's word, and
+    ``**{"lambda": x}`` is taken too); the ranges are the library's to refuse"""
+    if "lambda" in kw:
+        kw["lambda_"] = kw.pop("lambda")
+    unknown = set(kw) - _ALS_FIELDS
+    if unknown:
+        raise TypeError(f"goctr_als_cfg has no field {sorted(unknown)}")
+    return capi.default_als_cfg(**{k: float(v) if k in ("alpha", "lambda_") else _as_int(k, v) for k, v in kw.items()})
+
+
+class ALS(_Handle):
+    """goctr_als: implicit-feedback ALS factors X [n_users, D] and Y [n_items, D] resident in HBM, trained over a WalkGraph's two
+    CSRs (tests/als_ref.py is the host restatement).  The handle keeps the graph it was created over alive and passes it to every
+    training call"""
+    _destroy = "goctr_als_destroy"
+
+    def __init__(self, graph: WalkGraph, cfg: capi.AlsCfg | None = None, **kw):
+        """``kw``: goctr_als_cfg fields (D, n_iters, alpha, lambda_, seed).  Allocates and initialises; runs no iteration"""
+        cfg = _cfg_or_kw(cfg, kw, make_als_cfg)
+        self.graph = graph
+        self._h = C.c_void_p()
+        capi.check(capi.load().goctr_als_create(graph._h, C.byref(cfg), C.byref(self._h)))
+        i = self.info()
+        self.n_users, self.n_items, self.D = i["n_users"], i["n_items"], i["D"]
+
+    def info(self) -> dict:
+        nu, ni, d, hs = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int64(0)
+        capi.check(capi.load().goctr_als_info(self._h, C.byref(nu), C.byref(ni), C.byref(d), C.byref(hs)))
+        return dict(n_users=nu.value, n_items=ni.value, D=d.value, half_steps=hs.value)
+
+    def step(self, side) -> "ALS":
+        """goctr_als_step: one half-step; ``side`` "users" (X from Y) or "items" (Y from X), or capi.ALS_USERS / ALS_ITEMS"""
+        side = {"users": capi.ALS_USERS, "items": capi.ALS_ITEMS}.get(side, side)
+        capi.check(capi.load().goctr_als_step(self._h, self.graph._h, C.c_int32(_as_int("side", side))))
+        return self
+
+    def fit(self) -> "ALS":
+        """goctr_als_fit: cfg.n_iters iterations, a user step and an item step each"""
+        capi.check(capi.load().goctr_als_fit(self._h, self.graph._h))
+        return self
+
+    def loss(self) -> float:
+        """goctr_als_loss: the implicit objective over ALL pairs"""
+        v = C.c_double(0.0)
+        capi.check(capi.load().goctr_als_loss(self._h, self.graph._h, C.byref(v)))
+        return v.value
+
+    def export(self) -> dict:
+        """dict(X float64 [n_users, D], Y float64 [n_items, D])"""
+        out = dict(X=np.empty((self.n_users, self.D), np.float64), Y=np.empty((self.n_items, self.D), np.float64))
+        capi.check(capi.load().goctr_als_export(self._h, capi.ptr(out["X"], C.c_double), capi.ptr(out["Y"], C.c_double)))
+        return out
+
+    def set_factors(self, X=None, Y=None) -> "ALS":
+        """goctr_als_set_factors: either may be None (kept as it is)"""
+        X = None if X is None else np.ascontiguousarray(X, np.float64)
+        Y = None if Y is None else np.ascontiguousarray(Y, np.float64)
+        if (X is not None and X.shape != (self.n_users, self.D)) or (Y is not None and Y.shape != (self.n_items, self.D)):
+            raise ValueError("X is [n_users, D] and Y is [n_items, D]")
+        capi.check(capi.load().goctr_als_set_factors(self._h, capi.ptr(X, C.c_double), capi.ptr(Y, C.c_double)))
+        return self
+
+    def item_vectors(self, groups=None) -> "ItemVectors":
+        """goctr_itemvec_build_als: the item factors quantised device to device; what ``recall_users`` scans"""
+        groups = _groups_column(groups, self.n_items)
+        h = C.c_void_p()
+        capi.check(capi.load().goctr_itemvec_build_als(self._h, capi.ptr(groups, C.c_int32), C.byref(h)))
+        return ItemVectors(h)
+
+    def item_neighbours(self, cfg: capi.ItemnbrCfg | None = None, **kw) -> ItemCF:
+        """goctr_itemcf_build_als: neighbour lists from the item factors by quantised cosine; ``kw``: goctr_itemnbr_cfg fields"""
+        cfg = _cfg_or_kw(cfg, kw, make_nbr_cfg)
+        h = C.c_void_p()
+        capi.check(capi.load().goctr_itemcf_build_als(self._h, C.byref(cfg), C.byref(h)))
+        return ItemCF._adopt(h)
+
+    def foldin(self, ubc, users, ts=None, history=50) -> dict:
+        """goctr_als_foldin over DENSE user rows of ``ubc``'s image: dict(x float64 [nq, D], p int16 [nq, D], n int32 [nq] (the
+        distinct items used))"""
+        users, ts, _ = request_columns(users, ts, None)
+        nq = users.size
+        out = dict(x=np.full((nq, self.D), np.nan, np.float64), p=_unwritten((nq, self.D), np.int16), n=_unwritten(nq, np.int32))
+        capi.check(capi.load().goctr_als_foldin(self._h, _cache_handle(ubc), *_request_args(users, ts), C.c_int32(_as_int("history", history)),
+                                                _ptr(out["x"]), _ptr(out["p"]), _ptr(out["n"])))
+        return out
+
+    def recall_users(self, vectors: "ItemVectors", ubc, users, ts=None, targets=None, cfg: capi.RecallCfg | None = None,
+                     ucfg: capi.UservecCfg | None = None, validate=False, **kw) -> dict:
+        """goctr_als_recall over DENSE user rows of ``ubc``'s image: every row's folded-in vector against ``vectors``
+        (``item_vectors()``'s), ranked by cosine.  ``kw``: goctr_recall_cfg fields and goctr_uservec_cfg's.  ``ItemVectors.recall_users``'s
+        dict; with ``validate`` p int16 [nq, D] and x float64 [nq, D]"""
+        cfg, ucfg = _split_kw(cfg, ucfg, kw, _USERVEC_FIELDS, make_uservec_cfg)
+        users, ts, targets = request_columns(users, ts, targets)
+        out = _recall_buffers(users.size, cfg.n_cand, targets)
+        if validate:
+            out["p"], out["x"] = _unwritten((users.size, self.D), np.int16), np.full((users.size, self.D), np.nan, np.float64)
+        capi.check(capi.load().goctr_als_recall(self._h, vectors._h, _cache_handle(ubc), *_request_args(users, ts), C.byref(cfg),
+                                                C.byref(ucfg), *_recall_args(out, targets), _ptr(out.get("p")), _ptr(out.get("x"))))
+        return out
+
+
 def extra_columns(extra, nq):
     """the caller's candidate lists as the C-ABI takes them: (int32 [nq, n_extra] or None, n_extra)"""
     if extra is None:

@@ -27,7 +27,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import capi, metrics, sampling
-from .recall import (EXCLUDE, _USERVEC_FIELDS, _USERVEC_IVF_FIELDS, _USERVEC_MULTI_FIELDS, _WALK_FIELDS, ItemCF, ItemVectors, Popular,
+from .recall import (ALS, EXCLUDE, _USERVEC_FIELDS, _USERVEC_IVF_FIELDS, _USERVEC_MULTI_FIELDS, _WALK_FIELDS, ItemCF, ItemVectors, Popular,
                      WalkGraph, _as_int, _cfg_or_kw, _ptr, _request_args, _split_kw, _unwritten, extra_columns, make_mmr_cfg,
                      make_recall_cfg, make_uservec_cfg, make_uservec_ivf_cfg, make_uservec_multi_cfg, make_walk_cfg, merge,
                      request_columns)
@@ -550,6 +550,8 @@ _OUTPUTS = {
     "goctr_recommend_blend_uservec": _BLENDED + ("obj", "pen", "target_place"),
     "goctr_recommend_walk": _RANKED,
     "goctr_recommend_blend_walk": _BLENDED + ("obj", "pen", "target_place"),
+    "goctr_recommend_als": _RANKED,
+    "goctr_recommend_blend_als": _BLENDED + ("obj", "pen", "target_place"),
 }
 # key: (dtype, entries per request row -- "k", "n_cand" or one --, what the call must have for the array to exist)
 _COLUMNS = {
@@ -711,6 +713,41 @@ def blend_walk(model: Predictor, icf, pop, graph, users, ts=None, targets=None, 
             C.c_int32(_as_int("n_walk", n_walk)), C.byref(cfg), C.c_int32(_as_int("quota_pop", quota_pop)),
             vectors._h if vectors is not None else None, C.byref(mcfg) if mcfg is not None else None, *_k_pass(k, pass_rows))
     return _ranked_call("goctr_recommend_blend_walk", head, users.size, k, cfg.n_cand, targets, validate, mmr=mcfg is not None)
+
+
+def _als_vectors(factors, vectors):
+    """the item vectors an ALS call scans: the caller's, or the handle's own (BuildALS keeps them in ``factors.vectors``)"""
+    vectors = vectors if vectors is not None else getattr(factors, "vectors", None)
+    if vectors is None:
+        raise TypeError("the ALS handle has no item vectors: pass als_vectors, or build it with BuildALS")
+    return vectors
+
+
+def als(model: Predictor, factors, users, ts=None, targets=None, k=10, pass_rows=0, validate=False, recall_cfg=None, ucfg=None,
+        als_vectors=None, **recall_kw):
+    """goctr_recommend_als over DENSE indices: ``uservec`` with the fold-in of ``factors`` (recall.ALS) in the place of the pooled
+    vector, scanned against ``als_vectors`` (default: ``factors.vectors``); the same dict.  ``recall_kw``: goctr_recall_cfg fields
+    and goctr_uservec_cfg's.  What RecommendALS / RecommendALSBatch / EvaluateLeaveOneOutALS call."""
+    cfg, ucfg = _split_kw(recall_cfg, ucfg, recall_kw, _USERVEC_FIELDS, make_uservec_cfg)
+    users, ts, targets = request_columns(users, ts, targets)
+    head = (*_request_head(model, factors, _als_vectors(factors, als_vectors)), *_request_args(users, ts), capi.ptr(targets, C.c_int32),
+            C.byref(cfg), C.byref(ucfg), *_k_pass(k, pass_rows))
+    return _ranked_call("goctr_recommend_als", head, users.size, k, cfg.n_cand, targets, validate)
+
+
+def blend_als(model: Predictor, icf, pop, factors, users, ts=None, targets=None, n_als=64, quota_pop=0, k=10, vectors=None, pool=64,
+              lambda_q=192, max_per_group=0, pass_rows=0, validate=False, recall_cfg=None, ucfg=None, als_vectors=None, **recall_kw):
+    """goctr_recommend_blend_als over DENSE indices: ``blend`` whose part X is the fold-in recall of ``factors`` (recall.ALS) over
+    ``als_vectors`` (default: ``factors.vectors``), ``n_als`` entries a row, written and read on the device; with ``vectors`` the MMR
+    selection of ``diverse`` is the last step.  The dict of ``blend``, or of ``diverse``.  What RecommendBlendALSBatch calls."""
+    cfg, ucfg = _split_kw(recall_cfg, ucfg, recall_kw, _USERVEC_FIELDS, make_uservec_cfg)
+    users, ts, targets = request_columns(users, ts, targets)
+    mcfg = None if vectors is None else make_mmr_cfg(k=k, pool=pool, lambda_q=lambda_q, max_per_group=max_per_group)
+    head = (*_request_head(model, icf, pop), *_request_args(users, ts), capi.ptr(targets, C.c_int32), factors._h,
+            _als_vectors(factors, als_vectors)._h, C.byref(ucfg), C.c_int32(_as_int("n_als", n_als)), C.byref(cfg),
+            C.c_int32(_as_int("quota_pop", quota_pop)), vectors._h if vectors is not None else None,
+            C.byref(mcfg) if mcfg is not None else None, *_k_pass(k, pass_rows))
+    return _ranked_call("goctr_recommend_blend_als", head, users.size, k, cfg.n_cand, targets, validate, mmr=mcfg is not None)
 
 
 # ---- raw ids in, [[ItemScore]] out: what every Recommend*Batch function does around its device call
@@ -900,7 +937,41 @@ def RecommendBlendWalkBatch(model: Predictor, icf, pop, graph, userIds, n=10, no
                                                         lambda_q, max_per_group, **recall_kw))
 
 
+def RecommendALSBatch(model: Predictor, factors, userIds, n=10, now=None, **recall_kw):
+    """RecommendALS for several users in one device call: [[ItemScore]] in the order of userIds.  ``now``: one timestamp for all, or
+    one per user.  A user without history gets an empty list."""
+    users, ts = _request_rows(model, userIds, now)
+    return _serve(model, users.size, lambda: als(model, factors, users, ts, None, n, **recall_kw))
+
+
+def RecommendALS(model: Predictor, factors, userId: int, n=10, now=None, **recall_kw):
+    """EXTENSION -- matrix-factorisation recall, then rank: the user's vector is FOLDED IN at request time from the newest ``history``
+    behaviours at or before ``now`` through ALS's user equation against the trained item factors (BuildALS), the ``n_cand`` items
+    whose factors are closest by cosine are scored by the model and the ``n`` best come back.  An appended behaviour moves the vector
+    without a refit."""
+    return RecommendALSBatch(model, factors, [userId], n, now, **recall_kw)[0]
+
+
+def RecommendBlendALSBatch(model: Predictor, icf, pop, factors, userIds, n=10, now=None, n_als=64, quota_pop=0, vectors=None, pool=64,
+                           lambda_q=192, max_per_group=0, **recall_kw):
+    """EXTENSION -- RecommendBlendBatch with the ALS fold-in recall as the caller's list: ItemCF's candidates, then the ``n_als`` items
+    closest to the folded-in vector, then the popularity list (which carries the popularity part the cosine ranking drops); with
+    ``vectors`` the diversity re-rank of RecommendDiverse picks the ``n`` returned.  One device call."""
+    users, ts = _request_rows(model, userIds, now)
+    return _serve(model, users.size, lambda: blend_als(model, icf, pop, factors, users, ts, None, n_als, quota_pop, n, vectors, pool,
+                                                       lambda_q, max_per_group, **recall_kw))
+
+
 # ---- what the recall channels are built from
+def BuildALS(recSys: DeviceRecSys, graph=None, graph_kw=None, **cfg):
+    """EXTENSION: implicit-feedback ALS factors (recall.ALS; ``cfg``: goctr_als_cfg fields -- D, n_iters, alpha, lambda_, seed) fitted
+    over ``graph`` (default: BuildWalkGraph of the recSys's cache, ``graph_kw`` its cfg), with the quantised item factors in
+    ``.vectors`` -- what RecommendALS folds in against and scans."""
+    factors = ALS(graph if graph is not None else BuildWalkGraph(recSys, **(graph_kw or {})), **cfg).fit()
+    factors.vectors = factors.item_vectors()
+    return factors
+
+
 def BuildWalkGraph(recSys: DeviceRecSys, **cfg):
     """EXTENSION: the user-item graph (recall.WalkGraph; ``cfg``: goctr_walkgraph_cfg fields -- max_len, ts_lo, ts_hi) of the recSys's
     own behaviour cache over the rows of its item feature table -- what RecommendWalk walks.  Two sorts and two scans of the distinct
@@ -1247,6 +1318,34 @@ def EvaluateLeaveOneOutWalk(model: Predictor, graph=None, k=10, sample_kw=None, 
     finally:
         if own is not None:
             own.close()
+    out = _loo_figures(r, targets, model.recSys.item_table.shape[0], k, cfg.n_cand)
+    if details:
+        out.update(_details(r, users, targets, ts))
+    return out
+
+
+def EvaluateLeaveOneOutALS(model: Predictor, factors=None, k=10, sample_kw=None, details=False, pass_rows=0, graph_kw=None, als_kw=None,
+                           **recall_kw):
+    """EvaluateLeaveOneOutRecall's protocol and figures with the ALS fold-in recall as the recall stage (goctr_recommend_als).  The
+    request vector is folded in from the history the key sees (key timestamp ts - 1), so it never holds the held-out item; the ITEM
+    factors would, if they were trained on it.  ``factors`` None: the factors are fitted here (``als_kw``: goctr_als_cfg fields) over
+    a graph windowed below the held-out events as EvaluateLeaveOneOutWalk's is (``graph_kw``), and closed on the way out; a caller's
+    own ``factors`` are used as they are."""
+    users, targets, ts = _held_out_rows(model, sample_kw)
+    recall_kw.setdefault("exclude", "before")
+    cfg, ucfg = _split_kw(None, None, recall_kw, _USERVEC_FIELDS, make_uservec_cfg)
+    own = None
+    if factors is None:
+        gkw = dict(graph_kw or {})
+        gkw.setdefault("ts_hi", int((sample_kw or {})["ts_lo"]) - 1 if "ts_lo" in (sample_kw or {}) else int(ts.min()))
+        factors = own = BuildALS(model.recSys, graph_kw=gkw, **(als_kw or {}))
+    try:
+        r = als(model, factors, users, ts, targets, k, pass_rows, recall_cfg=cfg, ucfg=ucfg)
+    finally:
+        if own is not None:
+            own.vectors.close()
+            own.close()
+            own.graph.close()
     out = _loo_figures(r, targets, model.recSys.item_table.shape[0], k, cfg.n_cand)
     if details:
         out.update(_details(r, users, targets, ts))

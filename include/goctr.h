@@ -1007,6 +1007,120 @@ int goctr_recommend_blend_walk(goctr_model* m, goctr_recsys* r, goctr_itemcf* ic
                                int32_t* cand_items, uint32_t* cand_w, float* cand_scores, uint8_t* cand_src, int64_t* n_failed,
                                int32_t* out_obj, uint32_t* out_pen, int32_t* out_target_place);
 
+/* ---- Implicit-feedback ALS: matrix factorisation of the user-item matrix (Hu, Koren and Volinsky; no reference counterpart).
+ * Every vector channel above takes its vectors from item2vec or from the CTR embedding table; this one trains factors on the
+ * interaction data itself, over the two CSRs of a goctr_walkgraph (tests/als_ref.py is the host restatement).  All arithmetic is
+ * float64.
+ *
+ * Edges are binary: the graph's distinct (user, item) edges, uniform confidence.  With X [n_users,D], Y [n_items,D], G_Y = Y^T Y
+ * and I_u the items of user u (the graph's uitems row):
+ *   user step      A_u = G_Y + alpha * sum_{i in I_u} y_i y_i^T + lambda * I
+ *                  b_u = (1 + alpha) * sum_{i in I_u} y_i
+ *                  x_u = A_u^{-1} b_u by a Cholesky factorisation and two triangular solves
+ *   item step      the same with the roles swapped: U_i (the graph's iusers row), G_X, X
+ *   empty rows     a row without edges gets the zero vector.  An item's zero row is an invalid row of a goctr_itemvec (the
+ *                  quantisation rule of "Item neighbours from vectors": s = 0)
+ *   iteration      a user step, then an item step
+ *   initial Y      y[i][d] = (((h >> 11) * 2^-53) - 0.5) / D with h = mix(seed ^ mix((i << 32) | d)), mix the counter hash of the
+ *                  negative sampler (one splitmix64 step); every operation is exact but the division, which is rounded to
+ *                  nearest: the initial Y is defined byte for byte.  X starts at zero
+ *   loss           sum over ALL pairs (u,i) of c_ui (p_ui - x_u.y_i)^2 + lambda (|X|^2 + |Y|^2), with p_ui = 1, c_ui = 1 + alpha
+ *                  on an edge and p_ui = 0, c_ui = 1 elsewhere.  It is computed as <G_X, G_Y> + the sum over the edges of
+ *                  (1 + alpha) (1 - s)^2 - s^2, s = x_u.y_i, + lambda (tr G_X + tr G_Y): the sum of (x_u.y_i)^2 over all pairs
+ *                  is <G_X, G_Y>
+ *   summation      the sums are float64 and their order is FIXED: a row's tree depends on the row and its degree alone (segments
+ *                  of 256 edges in CSR order, folded ascending; a Gram matrix: tiles of 256 rows, folded ascending).  Two fits
+ *                  of the same graph and cfg give the same bytes; no output byte depends on how rows or segments are dealt to
+ *                  workgroups.  The ORDER itself is the implementation's: the restatement agrees within rounding, not bit for bit
+ *   refused        (-1, nothing touched, the error text set) a NULL argument; D outside 4 .. 64; n_iters < 0; alpha or lambda not
+ *                  a finite number above 0; reserved != 0; a graph without users or items; a graph on another engine than the
+ *                  handle's, or (step, fit, loss) a graph whose n_users, n_items or n_edges differ from the one of create
+ * The engine stream and the engine lock, like goctr_walkgraph_build.  The handle is independent of the graph after every call. */
+typedef struct {
+  int32_t D;            /* 4 .. 64: factors per row                            default 32 */
+  int32_t n_iters;      /* >= 0: iterations of goctr_als_fit                   default 10 */
+  double  alpha;        /* > 0: confidence of an edge is 1 + alpha             default 40 */
+  double  lambda;       /* > 0: every A is positive definite                   default 0.1 */
+  uint64_t seed;        /* of the initial Y                                    default 0 */
+  int64_t reserved;     /* must be 0 */
+} goctr_als_cfg;
+void goctr_als_cfg_default(goctr_als_cfg* c);
+
+typedef struct goctr_als goctr_als;
+#define GOCTR_ALS_USERS 0
+#define GOCTR_ALS_ITEMS 1
+/* allocates X (zero) and Y (the initial Y); runs no iteration */
+int  goctr_als_create(goctr_walkgraph* g, const goctr_als_cfg* cfg, goctr_als** out);
+void goctr_als_destroy(goctr_als* a);
+/* one half-step: side = GOCTR_ALS_USERS (X from Y) or GOCTR_ALS_ITEMS (Y from X); any other side is refused */
+int  goctr_als_step(goctr_als* a, goctr_walkgraph* g, int32_t side);
+/* cfg.n_iters iterations */
+int  goctr_als_fit(goctr_als* a, goctr_walkgraph* g);
+int  goctr_als_loss(goctr_als* a, goctr_walkgraph* g, double* loss);
+/* each output may be NULL; half_steps: the half-steps run so far (set_factors does not reset it) */
+int  goctr_als_info(goctr_als* a, int64_t* n_users, int64_t* n_items, int32_t* D, int64_t* half_steps);
+/* X [n_users,D], Y [n_items,D] in host memory; either may be NULL */
+int  goctr_als_export(goctr_als* a, double* X, double* Y);
+int  goctr_als_set_factors(goctr_als* a, const double* X, const double* Y);
+
+/* the item factors, device to device, into the existing builds: the results equal goctr_itemvec_build_vectors /
+ * goctr_itemcf_build_vectors called with goctr_als_export's Y, byte for byte (the same quantise launch reads the same doubles) */
+int  goctr_itemvec_build_als(goctr_als* a, const int32_t* groups /* [n_items] or NULL */, goctr_itemvec** out);
+int  goctr_itemcf_build_als(goctr_als* a, const goctr_itemnbr_cfg* cfg, goctr_itemcf** out);
+
+/* goctr_als_foldin: a request row's vector from its history in the cache at request time, through the user equation against the
+ * trained Y and G_Y -- an appended event moves the vector without a refit, and a leave-one-out evaluation under a ts below the
+ * held-out event cannot see the held-out item (a stored x_u would have been trained on it).
+ *   history        goctr_itemcf_recall's with n_items = the handle's: the entries TimeSeq.Filter(ts[q], 0) keeps, of those the valid
+ *                  ones, of those the first `history` (1 .. 256) in sequence order
+ *   items          the DISTINCT items of the history (a repeated item counts once); out_n[q] is their number
+ *   vector         x = A^{-1} b as in the user step over those items; out_x [n_req,D] float64.  A row without history gets zeros
+ *   planes         out_p [n_req,D] int16 = the quantisation rule of "Item neighbours from vectors" (s, valid, q_d) applied to x
+ *                  with the same pinned operations; zeros for a row without history
+ *   refused        a NULL handle, cache or users; history outside 1 .. 256; a user outside the cache; handles on different engines
+ * out_x, out_p and out_n may each be NULL.  Host arrays, the engine stream and the engine lock, like goctr_itemcf_recall. */
+int  goctr_als_foldin(goctr_als* a, goctr_ubcache* c, const int32_t* users, const int64_t* ts /* NULL = 0 */, int64_t n_req,
+                      int32_t history, double* out_x /*[n_req,D] or NULL*/, int16_t* out_p /*[n_req,D] or NULL*/,
+                      int32_t* out_n /*[n_req] or NULL*/);
+
+/* goctr_als_recall: goctr_uservec_recall with the folded-in vector's planes in the place of the pooled vector's: weight, seen,
+ * candidates, order and outputs are that call's, over the item vectors v (goctr_itemvec_build_als's, as a rule).
+ * THE SCAN RANKS BY THE COSINE of the folded-in vector against the item factors, not by ALS's raw dot product x.y_i: both sides
+ * are normalised by the quantisation.  It therefore drops the item-norm part of ALS's score, which is mostly popularity; the
+ * blend's popularity list carries that part.
+ *   refused        goctr_uservec_recall's and goctr_als_foldin's refusals; v's D or n_items different from the handle's */
+int  goctr_als_recall(goctr_als* a, goctr_itemvec* v, goctr_ubcache* c, const int32_t* users, const int64_t* ts /* NULL = 0 */,
+                      int64_t n_req, const goctr_recall_cfg* cfg, const goctr_uservec_cfg* ucfg,
+                      int32_t* out_items /*[n_req,n_cand]*/, uint32_t* out_w /*[n_req,n_cand]*/, int32_t* out_count /*[n_req]*/,
+                      const int32_t* targets /*[n_req] or NULL*/, int32_t* out_target_pos /*[n_req] or NULL*/,
+                      int16_t* out_p /*[n_req,D] or NULL*/, double* out_x /*[n_req,D] or NULL*/);
+
+/* goctr_recommend_als: goctr_recommend_itemcf with goctr_als_recall as its recall stage, over the recsys's cache image; every
+ * documented property of that call holds unchanged.
+ *   refused        goctr_recommend_itemcf's refusals, the ucfg refusals, v or the handle not matching the recsys's n_items */
+int goctr_recommend_als(goctr_model* m, goctr_recsys* r, goctr_als* als, goctr_itemvec* v,
+                        const int32_t* users, const int64_t* ts /* NULL = 0 */, int64_t n_req,
+                        const int32_t* targets /* [n_req] or NULL */, const goctr_recall_cfg* recall_cfg,
+                        const goctr_uservec_cfg* ucfg, int32_t k, int64_t pass_rows,
+                        int32_t* out_items /* [n_req,k] */, float* out_scores /* [n_req,k] */, int32_t* out_count,
+                        int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank,
+                        int32_t* cand_items, uint32_t* cand_w, float* cand_scores, int64_t* n_failed);
+
+/* goctr_recommend_blend_als: the blend with goctr_als_recall as its part X, defined by composition as goctr_recommend_blend_uservec
+ * is: n_extra = n_als, extra row q = the items of goctr_als_recall's row q under {recall_cfg->history, n_cand = n_als,
+ * recall_cfg->exclude} and ucfg over uv.  The list never leaves the device.
+ *   refused        goctr_recommend_blend_uservec's refusals with the handle and uv in uv's place */
+int goctr_recommend_blend_als(goctr_model* m, goctr_recsys* r, goctr_itemcf* icf /* may be NULL */, goctr_popular* pop /* may be NULL */,
+                              const int32_t* users, const int64_t* ts /* NULL = 0 */, int64_t n_req,
+                              const int32_t* targets /* [n_req] or NULL */,
+                              goctr_als* als, goctr_itemvec* uv, const goctr_uservec_cfg* ucfg, int32_t n_als /* 1 .. 1024 */,
+                              const goctr_recall_cfg* recall_cfg, int32_t quota_pop /* 0 .. recall_cfg->n_cand */,
+                              goctr_itemvec* v /* or NULL */, const goctr_mmr_cfg* cfg /* or NULL */, int32_t k, int64_t pass_rows,
+                              int32_t* out_items /* [n_req,k] */, float* out_scores /* [n_req,k] */, int32_t* out_count,
+                              uint8_t* out_src, int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank,
+                              int32_t* cand_items, uint32_t* cand_w, float* cand_scores, uint8_t* cand_src, int64_t* n_failed,
+                              int32_t* out_obj, uint32_t* out_pen, int32_t* out_target_place);
+
 /* ---- Multi-interest user-vector recall: the history clustered into up to 8 interest vectors, one list each, mixed into one (no
  * reference counterpart).  A user with two tastes pools to a vector between them and the larger taste takes the whole list; here
  * every taste gets a vector of its own and a share of the list.  Every output is defined bit for bit
