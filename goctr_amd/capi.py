@@ -234,6 +234,18 @@ class AlsCfg(C.Structure):
                 ("reserved", C.c_int64)]
 
 
+class EaseCfg(C.Structure):
+    """goctr_ease_cfg (include/goctr.h)"""
+    _fields_ = [("n_nbr", C.c_int32), ("max_items", C.c_int32), ("min_degree", C.c_int32), ("scale", C.c_int32),
+                ("lambda_", C.c_double), ("reserved", C.c_int64)]
+
+
+class EaseDump(C.Structure):
+    """goctr_ease_dump (include/goctr.h): validation outputs in host memory, each may be NULL"""
+    _fields_ = [("n_active", C.POINTER(C.c_int32)), ("active", C.POINTER(C.c_int32)), ("G", C.POINTER(C.c_uint32)),
+                ("P", C.POINTER(C.c_double)), ("B", C.POINTER(C.c_double)), ("b_max", C.POINTER(C.c_double))]
+
+
 class MmrCfg(C.Structure):
     """goctr_mmr_cfg (include/goctr.h)"""
     _fields_ = [("k", C.c_int32), ("pool", C.c_int32), ("lambda_q", C.c_int32), ("max_per_group", C.c_int32)]
@@ -345,6 +357,7 @@ SYMBOLS = [
     "goctr_als_cfg_default", "goctr_als_create", "goctr_als_destroy", "goctr_als_step", "goctr_als_fit", "goctr_als_loss", "goctr_als_info",
     "goctr_als_export", "goctr_als_set_factors", "goctr_itemvec_build_als", "goctr_itemcf_build_als", "goctr_als_foldin",
     "goctr_als_recall", "goctr_recommend_als", "goctr_recommend_blend_als",
+    "goctr_ease_cfg_default", "goctr_ease_block_size", "goctr_itemcf_build_ease",
     "goctr_uservec_cfg_default", "goctr_uservec_recall", "goctr_recommend_uservec", "goctr_recommend_blend_uservec",
     "goctr_uservec_multi_cfg_default", "goctr_uservec_interests", "goctr_uservec_recall_multi", "goctr_recommend_uservec_multi",
     "goctr_ivf_cfg_default", "goctr_itemvec_index_build", "goctr_itemvec_index_destroy", "goctr_itemvec_index_info",
@@ -377,7 +390,7 @@ def load() -> C.CDLL:
                      "goctr_ivf_cfg_default", "goctr_uservec_ivf_cfg_default", "goctr_itemvec_index_destroy",
                      "goctr_calib_cfg_default", "goctr_calibrator_destroy", "goctr_boot_cfg_default",
                      "goctr_walkgraph_cfg_default", "goctr_walk_cfg_default", "goctr_walkgraph_destroy",
-                     "goctr_als_cfg_default", "goctr_als_destroy"):
+                     "goctr_als_cfg_default", "goctr_als_destroy", "goctr_ease_cfg_default"):
             getattr(_lib, name).restype = None
         _bm = C.POINTER(BinaryMetrics)
         _lib.goctr_metrics_binary.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, _bm]
@@ -550,6 +563,10 @@ def load() -> C.CDLL:
                                                    C.c_void_p, C.c_void_p, _uv, C.c_int32, C.POINTER(RecallCfg), C.c_int32, C.c_void_p,
                                                    _mmr, C.c_int32, C.c_int64, _i32, _f32, _i32, _u8, _i32, _i32, _i64, _i32, _u32,
                                                    _f32, _u8, _i64, _i32, _u32, _i32]
+        _lib.goctr_ease_cfg_default.argtypes = [C.POINTER(EaseCfg)]
+        _lib.goctr_ease_block_size.argtypes = []
+        _lib.goctr_ease_block_size.restype = C.c_int32
+        _lib.goctr_itemcf_build_ease.argtypes = [C.c_void_p, C.POINTER(EaseCfg), C.POINTER(C.c_void_p), C.POINTER(EaseDump)]
         _um = C.POINTER(UservecMultiCfg)
         _lib.goctr_uservec_multi_cfg_default.argtypes = [_um]
         _lib.goctr_uservec_interests.argtypes = [C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, C.POINTER(RecallCfg), _um, _i32,
@@ -697,6 +714,8 @@ default_walkgraph_cfg = _default(WalkGraphCfg, "goctr_walkgraph_cfg_default")
 default_walk_cfg = _default(WalkCfg, "goctr_walk_cfg_default")
 default_als_cfg = _default(AlsCfg, "goctr_als_cfg_default")
 ALS_USERS, ALS_ITEMS = 0, 1                 # goctr_als_step's sides
+default_ease_cfg = _default(EaseCfg, "goctr_ease_cfg_default")
+EASE_SCALE_GLOBAL, EASE_SCALE_ROW = 0, 1    # goctr_ease_cfg.scale
 
 
 PROF_COUNT = 18          # GOCTR_K_COUNT (include/goctr.h)

@@ -593,6 +593,14 @@ class ItemCF {
     return ItemCF(h);
   }
   static ItemCF Swing(RecSys& rs, const goctr_swing_cfg& cfg = DefaultSwingCfg()) { return Swing(rs.cache(), rs.n_items(), cfg); }
+  // EASE neighbour lists (goctr_itemcf_build_ease): the item-item weights -P_ij / P_jj of P = (X^T X + lambda I)^-1 over the
+  // graph's edges (WalkGraph::handle()), float64 on the device; `dump` (may be null) takes the validation outputs
+  static goctr_ease_cfg DefaultEaseCfg() { goctr_ease_cfg c; goctr_ease_cfg_default(&c); return c; }
+  static ItemCF Ease(goctr_walkgraph* graph, const goctr_ease_cfg& cfg = DefaultEaseCfg(), const goctr_ease_dump* dump = nullptr) {
+    goctr_itemcf* h = nullptr;
+    check(goctr_itemcf_build_ease(graph, &cfg, &h, dump));
+    return ItemCF(h);
+  }
   // neighbour lists from item VECTORS (goctr_itemcf_build_vectors / _emb): quantised cosine in units of 2^-16, the scale of the
   // co-occurrence weights, so every consumer takes either kind of handle
   static goctr_itemnbr_cfg DefaultNbrCfg() { goctr_itemnbr_cfg c; goctr_itemnbr_cfg_default(&c); return c; }

@@ -14,6 +14,9 @@ device, so that a row without history still gets candidates (tests/popular_ref.p
 ``ItemCF.swing`` is a third source of neighbour lists: Swing, item similarity from user-pair overlap, in integers throughout
 (tests/swing_ref.py is the host restatement).
 
+``ItemCF.ease`` is a fourth: EASE, the item-item weights learned jointly as -P_ij / P_jj of P = (X^T X + lambda I)^-1 over a
+``WalkGraph``'s edges, in float64 through a blocked Cholesky on the device (tests/ease_ref.py is the host restatement).
+
 ``WalkGraph`` is the multi-hop channel: the user-item graph of one image of the cache as two CSRs, and ``WalkGraph.recall`` walks it
 from a request row's history -- item, holder, one of the holder's items, a few steps at a time -- and ranks the items by where the
 walks land (tests/walk_ref.py is the host restatement).  ``recommend.RecommendWalk`` ranks the result with the model.
@@ -98,6 +101,25 @@ make_ivf_cfg = _make("goctr_ivf_cfg", _IVF_FIELDS, capi.default_ivf_cfg)
 make_uservec_ivf_cfg = _make("goctr_uservec_ivf_cfg", _USERVEC_IVF_FIELDS, capi.default_uservec_ivf_cfg)
 make_walkgraph_cfg = _make("goctr_walkgraph_cfg", _WALKGRAPH_FIELDS, capi.default_walkgraph_cfg)
 make_walk_cfg = _make("goctr_walk_cfg", _WALK_FIELDS, capi.default_walk_cfg)
+
+
+_EASE_FIELDS = _fields(capi.EaseCfg)
+EASE_SCALE = {"global": capi.EASE_SCALE_GLOBAL, "row": capi.EASE_SCALE_ROW}
+
+
+def make_ease_cfg(**kw) -> capi.EaseCfg:
+    """goctr_ease_cfg from keywords: n_nbr, max_items, min_degree, scale (integers; ``scale`` also "global" / "row"), lambda_ (a
+    number; ``**{"lambda": x}`` is taken too); the ranges are the library's to refuse"""
+    if "lambda" in kw:
+        kw["lambda_"] = kw.pop("lambda")
+    unknown = set(kw) - _EASE_FIELDS
+    if unknown:
+        raise TypeError(f"goctr_ease_cfg has no field {sorted(unknown)}")
+    if isinstance(kw.get("scale"), str):
+        if kw["scale"] not in EASE_SCALE:
+            raise ValueError(f"scale = {kw['scale']!r} is none of {sorted(EASE_SCALE)}")
+        kw["scale"] = EASE_SCALE[kw["scale"]]
+    return capi.default_ease_cfg(**{k: float(v) if k == "lambda_" else _as_int(k, v) for k, v in kw.items()})
 
 
 def _cfg_or_kw(cfg, kw, make, name="cfg"):
@@ -242,6 +264,29 @@ class ItemCF(_Handle):
                                                         C.byref(h)))
         return cls._adopt(h)
 
+    @classmethod
+    def ease(cls, graph: "WalkGraph", cfg: capi.EaseCfg | None = None, dump=False, **kw):
+        """goctr_itemcf_build_ease: neighbour lists from the EASE item-item model over ``graph``'s distinct edges; ``kw``:
+        goctr_ease_cfg fields (n_nbr, max_items, min_degree, scale -- also "global" / "row" --, lambda_).  Every method works on the
+        result as on a co-occurrence build; nbr_co holds G, the users who hold both items.  With ``dump`` returns (handle,
+        dict(n_active, active int32 [n_active], G uint32, P, B float64 [n_active, n_active], b_max float64 [1] or [n_active],
+        slots int32 [min(max_items, n_items)]: the whole active array, -1 behind n_active))"""
+        cfg = _cfg_or_kw(cfg, kw, make_ease_cfg)
+        h = C.c_void_p()
+        if not dump:
+            capi.check(capi.load().goctr_itemcf_build_ease(graph._h, C.byref(cfg), C.byref(h), None))
+            return cls._adopt(h)
+        cap = max(min(int(cfg.max_items), graph.n_items), 1)
+        n = C.c_int32(-2)
+        active, G = _unwritten(cap, np.int32), np.zeros((cap, cap), np.uint32)
+        P, B, b_max = np.full((cap, cap), np.nan), np.full((cap, cap), np.nan), np.full(cap, np.nan)
+        d = capi.EaseDump(C.pointer(n), _ptr(active), _ptr(G), _ptr(P), _ptr(B), _ptr(b_max))
+        capi.check(capi.load().goctr_itemcf_build_ease(graph._h, C.byref(cfg), C.byref(h), C.byref(d)))
+        na = n.value
+        packed = lambda a: a.ravel()[:na * na].reshape(na, na).copy()       # (the library packs at stride n_active)
+        return cls._adopt(h), dict(n_active=na, active=active[:na].copy(), G=packed(G), P=packed(P), B=packed(B),
+                                   b_max=b_max[:na if cfg.scale == capi.EASE_SCALE_ROW else 1].copy(), slots=active)
+
     def info(self) -> dict:
         n, m, d, t, v = C.c_int64(0), C.c_int32(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         capi.check(capi.load().goctr_itemcf_info(self._h, C.byref(n), C.byref(m), C.byref(d), C.byref(t), C.byref(v)))
@@ -265,6 +310,11 @@ class ItemCF(_Handle):
         capi.check(capi.load().goctr_itemcf_recall(self._h, _cache_handle(ubc), *_request_args(users, ts), C.byref(cfg),
                                                    *_recall_args(out, targets)))
         return out
+
+
+def ease_block_size() -> int:
+    """goctr_ease_block_size: the block size of ``ItemCF.ease``'s factorisation"""
+    return int(capi.load().goctr_ease_block_size())
 
 
 def merge(a: ItemCF, b: ItemCF, mul_a=128, mul_b=128, n_nbr=64) -> ItemCF:

@@ -972,6 +972,14 @@ def BuildALS(recSys: DeviceRecSys, graph=None, graph_kw=None, **cfg):
     return factors
 
 
+def BuildEASE(recSys: DeviceRecSys, graph=None, graph_kw=None, **cfg):
+    """EXTENSION: EASE neighbour lists (recall.ItemCF.ease; ``cfg``: goctr_ease_cfg fields -- n_nbr, max_items, min_degree, scale,
+    lambda_) over ``graph`` (default: BuildWalkGraph of the recSys's cache, ``graph_kw`` its cfg): the item-item weights learned
+    jointly, so a pair linked only through a hub is not weighted as if the link were direct.  Every RecommendItemCF / RecommendBlend /
+    EvaluateLeaveOneOut* / MergeItemCF call takes the handle like BuildItemCF's; it is independent of the graph afterwards."""
+    return ItemCF.ease(graph if graph is not None else BuildWalkGraph(recSys, **(graph_kw or {})), **cfg)
+
+
 def BuildWalkGraph(recSys: DeviceRecSys, **cfg):
     """EXTENSION: the user-item graph (recall.WalkGraph; ``cfg``: goctr_walkgraph_cfg fields -- max_len, ts_lo, ts_hi) of the recSys's
     own behaviour cache over the rows of its item feature table -- what RecommendWalk walks.  Two sorts and two scans of the distinct

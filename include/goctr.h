@@ -1121,6 +1121,75 @@ int goctr_recommend_blend_als(goctr_model* m, goctr_recsys* r, goctr_itemcf* icf
                               int32_t* cand_items, uint32_t* cand_w, float* cand_scores, uint8_t* cand_src, int64_t* n_failed,
                               int32_t* out_obj, uint32_t* out_pen, int32_t* out_target_place);
 
+/* ---- EASE item neighbours: a learned item-item model as a fourth source of goctr_itemcf handles (Steck 2019, "Embarrassingly
+ * Shallow Autoencoders"; no reference counterpart).  The three sources above set a pair's weight by a local rule; EASE learns all
+ * weights jointly, so a pair that co-occurs only because both items co-occur with a hub is not weighted as if the link were direct.
+ * With X the binary user-item matrix of the graph's distinct edges: P = (X^T X + lambda I)^-1, B_ij = -P_ij / P_jj, B_jj = 0, and a
+ * user's score for j is the sum of B_ij over the history -- the sum goctr_itemcf_recall computes over stored lists.  The result is a
+ * goctr_itemcf like goctr_itemcf_build's: recall, blend, recommend, merge, info, export and destroy take it unchanged
+ * (tests/ease_ref.py is the host restatement).  The selection and G are integer work and defined bit for bit; A, P and B are float64.
+ *
+ * goctr_itemcf_build_ease:
+ *   active items   the items ordered by degree |U_i| in the graph, descending, then by item id ascending; the first
+ *                  n_active = min(max_items, #{i : |U_i| >= min_degree}) are the model rows 0 .. n_active-1, a(r) the item of row r.
+ *                  Every other item has an empty list and occurs in no list.  The order is part of the definition: it is the pivot
+ *                  order, which decides the float64 bytes
+ *   G              G_rs = |U_a(r) n U_a(s)|, an exact uint32; the diagonal is the degree.  No byte depends on an arrival order
+ *                  (integer atomics)
+ *   A, P           A = (double) G + lambda I: the conversion is exact, the diagonal is rounded once.  P = A^-1 by a blocked Cholesky
+ *                  A = L L^T, a blocked triangular inverse and P = L^-T L^-1, all float64; P is stored symmetric
+ *   B              B_rs = -P_rs / P_ss for r != s, one correctly rounded division; B_rr = 0
+ *   weights        GOCTR_EASE_SCALE_GLOBAL: m = the maximum over all B_rs (r != s), w = (uint32) floor((B_rs / m) * 4194304.0).
+ *                  GOCTR_EASE_SCALE_ROW: m_r = the maximum over row r, w = (uint32) floor((B_rs / m_r) * 65536.0): a non-empty list
+ *                  then starts at 65536, the scale of Swing's and the vector source's weights, so goctr_itemcf_merge mixes them at
+ *                  par.  The division comes first, then the product, nothing contracted: the maximal element maps to the scale
+ *                  exactly.  An entry with B <= 0, or whose scaled value is below 1, has w = 0 and is not stored.  A row whose
+ *                  maximum is <= 0 (GLOBAL: every row, when no B is above 0) has an empty list.  w <= 2^22 respects the recall's
+ *                  2^31 sum bound
+ *   neighbours     of a(r): the entries with w > 0, by w descending, then item id ascending; the first n_nbr are stored:
+ *                  nbr_items = a(s), nbr_w = w, nbr_co = G_rs, padding -1 / 0 / 0
+ *   info           cnt[i] = |U_i| for every item, active or not; distinct_pairs = the directed pairs with w > 0 (before the cut at
+ *                  n_nbr); total_pairs = the sum over users of C(|I_u n active|, 2); cache_version = the graph's
+ *   summation      every float64 sum has a FIXED order: a tile product's k ascends, tiles and panels are folded ascending, and there
+ *                  are no floating-point atomics.  Two builds of the same graph and cfg give the same bytes in P, B and the handle.
+ *                  The ORDER itself is the implementation's (it depends on the block size goctr_ease_block_size reports): the
+ *                  restatement agrees within rounding, not bit for bit
+ *   dump           validation outputs in host memory, written on success only; the struct and each member may be NULL.  G, P and B
+ *                  are packed at stride n_active; the caller sizes them for min(max_items, n_items)^2.  b_max = the maximum or
+ *                  maxima the weights were divided by (0 where a row, or the model, has no off-diagonal element)
+ *   refused        (-1, *out and the dump untouched, the error text set) a NULL g, cfg or out; a cfg outside its ranges; lambda not
+ *                  a finite number above 0; reserved != 0; a graph without items; device memory for the n_active^2 matrices (one
+ *                  uint32, two float64) that cannot be had.  A pivot of the factorisation that is not a positive finite number is
+ *                  the same loud error, never a list of NaNs
+ * A graph with no active item (min_degree above every degree, or no edge) is not an error: every list is empty, n_active = 0.
+ * The engine stream and the engine lock of the graph's engine, like goctr_walkgraph_build.  The handle is independent of the graph
+ * afterwards.  Not covered: B's negative weights, a dense scoring call over whole rows of B, more than 32768 active items, per-edge
+ * confidence or recency weights, an incremental update of P after goctr_ubcache_append, a lambda per item. */
+#define GOCTR_EASE_SCALE_GLOBAL 0
+#define GOCTR_EASE_SCALE_ROW    1
+typedef struct {
+  int32_t n_nbr;       /* 1 .. 256                                 default 64   */
+  int32_t max_items;   /* 1 .. 32768: size of the dense model      default 8192 */
+  int32_t min_degree;  /* >= 1: holders an item needs to be active default 1    */
+  int32_t scale;       /* GOCTR_EASE_SCALE_*                       default GLOBAL */
+  double  lambda;      /* finite, > 0                              default 500  */
+  int64_t reserved;    /* must be 0 */
+} goctr_ease_cfg;
+void goctr_ease_cfg_default(goctr_ease_cfg* c);
+
+typedef struct {       /* validation outputs in host memory; the struct and each member may be NULL */
+  int32_t*  n_active;  /* [1] */
+  int32_t*  active;    /* [min(max_items, n_items)]: item of model row r, -1 behind n_active */
+  uint32_t* G;         /* [n_active, n_active] packed at stride n_active; caller sizes for min(max_items, n_items)^2 */
+  double*   P;         /* same shape */
+  double*   B;         /* same shape */
+  double*   b_max;     /* GLOBAL: [1]; ROW: [n_active] */
+} goctr_ease_dump;
+
+/* the block size of the factorisation (a multiple of 16): what the tests size their cases against */
+int32_t goctr_ease_block_size(void);
+int  goctr_itemcf_build_ease(goctr_walkgraph* g, const goctr_ease_cfg* cfg, goctr_itemcf** out, const goctr_ease_dump* dump);
+
 /* ---- Multi-interest user-vector recall: the history clustered into up to 8 interest vectors, one list each, mixed into one (no
  * reference counterpart).  A user with two tastes pools to a vector between them and the larger taste takes the whole list; here
  * every taste gets a vector of its own and a share of the list.  Every output is defined bit for bit
