@@ -1,5 +1,5 @@
 // als.h -- the handle of goctr_als_create (als.hip) and what the fold-in recall lends to the serving entries: goctr_recommend_als
-// runs it as the recall stage of itemcf.h's recall_rank_run, and goctr_recommend_blend_als (popular.hip's driver) has it write the
+// runs it as the recall stage of recall.h's recall_rank_run, and goctr_recommend_blend_als (popular.hip's driver) has it write the
 // list the blend's part X reads.  include/goctr.h states the semantics ("Implicit-feedback ALS"); tests/als_ref.py restates them.
 #pragma once
 #include <vector>
@@ -35,17 +35,16 @@ struct goctr_als {
 namespace goctr {
 
 // als_foldin_kernel over nq rows on `st`: sizes ws.p_hi / p_lo for nq rows ([nq + UV_PAD_ROWS, Dp], the pad rows zero) and writes
-// every row's planes into them; o_x [nq, D], o_p [nq, D] and o_n [nq] may be null.  The cache arrays may be null together (no
-// cache: every row is empty).  Waits for nothing
-int als_foldin_launch(const goctr_als* a, const long long* off, const int32_t* seq_items, const long long* seq_ts,
-                      const int32_t* users, const long long* ts, int64_t nq, int history, double* o_x, int16_t* o_p, int32_t* o_n,
-                      UvScratch& ws, hipStream_t st);
+// every row's planes into them; o_x [nq, D], o_p [nq, D] and o_n [nq] may be null.  Waits for nothing
+int als_foldin_launch(const goctr_als* a, const CacheSeq& seq, const int32_t* users, const long long* ts, int64_t nq, int history,
+                      double* o_x, int16_t* o_p, int32_t* o_n, UvScratch& ws, hipStream_t st);
 
-// fold-in, then uservec_scan_planes over v: row q's first cfg.n_cand slots at q * stride of o_items / o_w, o_count[q], o_tpos[q]
-int als_launch(const goctr_als* a, const goctr_itemvec* v, const long long* off, const int32_t* seq_items, const long long* seq_ts,
-               const RecallInputs& in, bool has_targets, int64_t nq, const goctr_recall_cfg& cfg, const goctr_uservec_cfg& ucfg,
-               int stride, int32_t* o_items, unsigned int* o_w, int32_t* o_count, int32_t* o_tpos, double* o_x, int16_t* o_p,
-               UvScratch& ws, hipStream_t st);
+// the folded-in vectors a call may return beside the rows: x [nq, D] and its planes p [nq, D]; each may be null
+struct AlsVecOut { double* x; int16_t* p; };
+
+// fold-in, then uservec_scan_planes over v, over r.nq rows on `st`.  Waits for nothing
+int als_launch(const goctr_als* a, const goctr_itemvec* v, const RecallCall& r, const goctr_uservec_cfg& ucfg, const RecallRows& out,
+               const AlsVecOut& vec, UvScratch& ws, hipStream_t st);
 
 // the handle against the item vectors and the catalogue (sets the error text)
 int als_check_vectors(const char* who, const goctr_als* a, const goctr_itemvec* v, int64_t n_items);

@@ -505,9 +505,8 @@ int als_half_step(goctr_als* a, const goctr_walkgraph* g, int side) {
 
 namespace goctr {
 
-int als_foldin_launch(const goctr_als* a, const long long* off, const int32_t* seq_items, const long long* seq_ts,
-                      const int32_t* users, const long long* ts, int64_t nq, int history, double* o_x, int16_t* o_p, int32_t* o_n,
-                      UvScratch& ws, hipStream_t st) {
+int als_foldin_launch(const goctr_als* a, const CacheSeq& seq, const int32_t* users, const long long* ts, int64_t nq, int history,
+                      double* o_x, int16_t* o_p, int32_t* o_n, UvScratch& ws, hipStream_t st) {
   const int Dp = round_up(a->D, IV_K);
   const size_t plane = ((size_t)nq + UV_PAD_ROWS) * Dp;
   if (ws.p_hi.alloc(plane, false) || ws.p_lo.alloc(plane, false)) return -1;
@@ -515,7 +514,7 @@ int als_foldin_launch(const goctr_als* a, const long long* off, const int32_t* s
   GOCTR_HIP(hipMemsetAsync(ws.p_lo.p + (size_t)nq * Dp, 0, (size_t)UV_PAD_ROWS * Dp, st));
   if (nq == 0) return 0;
   FoldinArgs f{};
-  f.off = off; f.seq_items = seq_items; f.seq_ts = seq_ts; f.n_items = a->n_items; f.users = users; f.ts = ts;
+  f.off = seq.off; f.seq_items = seq.items; f.seq_ts = seq.ts; f.n_items = a->n_items; f.users = users; f.ts = ts;
   f.H = history; f.D = a->D; f.Dp = Dp; f.alpha = a->cfg.alpha; f.lambda = a->cfg.lambda; f.Y = a->Y.p; f.G = a->GY.p;
   f.p_hi = ws.p_hi.p; f.p_lo = ws.p_lo.p; f.out_x = o_x; f.out_p = o_p; f.out_n = o_n;
   hipLaunchKernelGGL(als_foldin_kernel, dim3((unsigned)nq), dim3(ALS_THREADS), 0, st, f);
@@ -523,13 +522,11 @@ int als_foldin_launch(const goctr_als* a, const long long* off, const int32_t* s
   return 0;
 }
 
-int als_launch(const goctr_als* a, const goctr_itemvec* v, const long long* off, const int32_t* seq_items, const long long* seq_ts,
-               const RecallInputs& in, bool has_targets, int64_t nq, const goctr_recall_cfg& cfg, const goctr_uservec_cfg& ucfg,
-               int stride, int32_t* o_items, unsigned int* o_w, int32_t* o_count, int32_t* o_tpos, double* o_x, int16_t* o_p,
-               UvScratch& ws, hipStream_t st) {
-  if (als_foldin_launch(a, off, seq_items, seq_ts, in.users.p, in.ts.p, nq, cfg.history, o_x, o_p, nullptr, ws, st)) return -1;
-  return uservec_scan_planes(v, off, seq_items, seq_ts, UvCols{in.users.p, in.ts.p, has_targets ? in.targets.p : nullptr}, nq, cfg, ucfg,
-                             ws.p_hi.p, ws.p_lo.p, stride, o_items, o_w, o_count, o_tpos, ws, st);
+int als_launch(const goctr_als* a, const goctr_itemvec* v, const RecallCall& r, const goctr_uservec_cfg& ucfg, const RecallRows& out,
+               const AlsVecOut& vec, UvScratch& ws, hipStream_t st) {
+  if (als_foldin_launch(a, r.seq, r.in.users.p, r.in.ts.p, r.nq, r.cfg.history, vec.x, vec.p, nullptr, ws, st)) return -1;
+  return uservec_scan_planes(v, r.seq, UvCols{r.in.users.p, r.in.ts.p, r.targets()}, r.nq, r.cfg, ucfg, ws.p_hi.p, ws.p_lo.p, out,
+                             r.stride, ws, st);
 }
 
 int als_check_vectors(const char* who, const goctr_als* a, const goctr_itemvec* v, int64_t n_items) {
@@ -552,8 +549,7 @@ int als_recommend_run(const TopnScorer& sc, const goctr_als* a, const goctr_item
                       const ItemcfRecArgs& args) {
   UvScratch ws;                               // (outlives the run, which drains the stream on every path)
   return recall_rank_run(sc, "goctr_recommend_als", args, false, [&](const RecallInputs& in, const RecallRows& o, hipStream_t st) {
-    return als_launch(a, v, sc.ub_off, sc.ub_items, sc.ub_ts, in, args.targets != nullptr, args.n_req, args.rcfg, ucfg,
-                      args.rcfg.n_cand, o.items, o.w, o.count, o.tpos, nullptr, nullptr, ws, st);
+    return als_launch(a, v, recall_call(sc, args, in), ucfg, o, AlsVecOut{}, ws, st);
   });
 }
 
@@ -688,28 +684,21 @@ int goctr_als_foldin(goctr_als* a, goctr_ubcache* c, const int32_t* users, const
   if (recall_check_users(users, n_req, c->n_users, who)) return -1;
   hipStream_t s = engine().stream;
   const size_t nq = (size_t)n_req, D = (size_t)a->D;
+  HostStage out(s);
   RecallInputs in;
   UvScratch ws;
   DevBuf<double> o_x;
   DevBuf<int16_t> o_p;
   DevBuf<int32_t> o_n;
-  // the results are staged on the host so that a failing copy leaves the caller's arrays as they were
-  std::vector<double> h_x(out_x ? nq * D : 0);
-  std::vector<int16_t> h_p(out_p ? nq * D : 0);
-  std::vector<int32_t> h_n(out_n ? nq : 0);
   UbRead image(c, s);                         // (behind the buffers: an error return drains the stream before they are freed)
   if (in.stage(users, ts, nullptr, n_req, s)) return -1;
   if ((out_x && o_x.alloc(nq * D, false)) || (out_p && o_p.alloc(nq * D, false)) || (out_n && o_n.alloc(nq, false))) return -1;
-  if (als_foldin_launch(a, c->off.p, c->items.p, c->ts.p, in.users.p, in.ts.p, n_req, history, out_x ? o_x.p : nullptr,
-                        out_p ? o_p.p : nullptr, out_n ? o_n.p : nullptr, ws, s)) return -1;
-  if (out_x && nq) GOCTR_HIP(hipMemcpyAsync(h_x.data(), o_x.p, sizeof(double) * nq * D, hipMemcpyDeviceToHost, s));
-  if (out_p && nq) GOCTR_HIP(hipMemcpyAsync(h_p.data(), o_p.p, sizeof(int16_t) * nq * D, hipMemcpyDeviceToHost, s));
-  if (out_n && nq) GOCTR_HIP(hipMemcpyAsync(h_n.data(), o_n.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));
+  if (als_foldin_launch(a, CacheSeq(c), in.users.p, in.ts.p, n_req, history, o_x.p, o_p.p, o_n.p, ws, s)) return -1;
+  if (out.add(out_x, o_x.p, sizeof(double) * nq * D) || out.add(out_p, o_p.p, sizeof(int16_t) * nq * D) ||
+      out.add(out_n, o_n.p, sizeof(int32_t) * nq)) return -1;
   GOCTR_HIP(hipStreamSynchronize(s));
   image.done();
-  if (out_x) memcpy(out_x, h_x.data(), sizeof(double) * nq * D);
-  if (out_p) memcpy(out_p, h_p.data(), sizeof(int16_t) * nq * D);
-  if (out_n) memcpy(out_n, h_n.data(), sizeof(int32_t) * nq);
+  out.commit();
   return 0;
 }
 
@@ -723,40 +712,17 @@ int goctr_als_recall(goctr_als* a, goctr_itemvec* v, goctr_ubcache* c, const int
   GOCTR_SAME_ENGINE(a, c);
   if (recall_check_cfg(cfg, who) || uservec_check_cfg(ucfg, who) || als_check_vectors(who, a, v, -1) ||
       recall_check_users(users, n_req, c->n_users, who)) return -1;
-  hipStream_t s = engine().stream;
-  const size_t nq = (size_t)n_req, nc = (size_t)cfg->n_cand, D = (size_t)a->D;
-  RecallInputs in;
+  const size_t nq = (size_t)n_req, D = (size_t)a->D;
+  HostStage out(engine().stream);
   UvScratch ws;
-  DevBuf<int32_t> o_items, o_count, o_tpos;
-  DevBuf<unsigned int> o_w;
   DevBuf<int16_t> o_p;
   DevBuf<double> o_x;
-  // the results are staged on the host so that a failing copy leaves the caller's arrays as they were
-  std::vector<int32_t> h_items(nq * nc), h_count(nq), h_tpos(nq);
-  std::vector<unsigned int> h_w(nq * nc);
-  std::vector<int16_t> h_p(out_p ? nq * D : 0);
-  std::vector<double> h_x(out_x ? nq * D : 0);
-  UbRead image(c, s);                         // (behind the buffers: an error return drains the stream before they are freed)
-  if (in.stage(users, ts, targets, n_req, s)) return -1;
-  if (o_items.alloc(nq * nc, false) || o_w.alloc(nq * nc, false) || o_count.alloc(nq, false) || o_tpos.alloc(nq, false) ||
-      (out_p && o_p.alloc(nq * D, false)) || (out_x && o_x.alloc(nq * D, false))) return -1;
-  if (als_launch(a, v, c->off.p, c->items.p, c->ts.p, in, targets != nullptr, n_req, *cfg, *ucfg, cfg->n_cand, o_items.p, o_w.p,
-                 o_count.p, o_tpos.p, out_x ? o_x.p : nullptr, out_p ? o_p.p : nullptr, ws, s)) return -1;
-  GOCTR_HIP(hipMemcpyAsync(h_items.data(), o_items.p, sizeof(int32_t) * nq * nc, hipMemcpyDeviceToHost, s));
-  GOCTR_HIP(hipMemcpyAsync(h_w.data(), o_w.p, sizeof(unsigned int) * nq * nc, hipMemcpyDeviceToHost, s));
-  GOCTR_HIP(hipMemcpyAsync(h_count.data(), o_count.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));
-  GOCTR_HIP(hipMemcpyAsync(h_tpos.data(), o_tpos.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));
-  if (out_p) GOCTR_HIP(hipMemcpyAsync(h_p.data(), o_p.p, sizeof(int16_t) * nq * D, hipMemcpyDeviceToHost, s));
-  if (out_x) GOCTR_HIP(hipMemcpyAsync(h_x.data(), o_x.p, sizeof(double) * nq * D, hipMemcpyDeviceToHost, s));
-  GOCTR_HIP(hipStreamSynchronize(s));
-  image.done();
-  memcpy(out_items, h_items.data(), sizeof(int32_t) * nq * nc);
-  memcpy(out_w, h_w.data(), sizeof(unsigned int) * nq * nc);
-  memcpy(out_count, h_count.data(), sizeof(int32_t) * nq);
-  if (out_target_pos) for (size_t q = 0; q < nq; ++q) out_target_pos[q] = targets ? h_tpos[q] : -1;
-  if (out_p) memcpy(out_p, h_p.data(), sizeof(int16_t) * nq * D);
-  if (out_x) memcpy(out_x, h_x.data(), sizeof(double) * nq * D);
-  return 0;
+  return recall_only_run(c, users, ts, targets, n_req, cfg->n_cand, [&](const RecallInputs& in, const RecallRows& o, hipStream_t st) {
+    if ((out_p && o_p.alloc(nq * D, false)) || (out_x && o_x.alloc(nq * D, false))) return -1;
+    if (als_launch(a, v, RecallCall{CacheSeq(c), in, targets != nullptr, n_req, *cfg, cfg->n_cand}, *ucfg, o, AlsVecOut{o_x.p, o_p.p}, ws, st))
+      return -1;
+    return out.add(out_p, o_p.p, sizeof(int16_t) * nq * D) || out.add(out_x, o_x.p, sizeof(double) * nq * D) ? -1 : 0;
+  }, out, out_items, out_w, nullptr, out_count, out_target_pos);
 }
 
 }  // extern "C"

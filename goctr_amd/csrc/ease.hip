@@ -36,6 +36,7 @@
 #include <vector>
 
 #define GOCTR_NO_PLAIN_KERNELS      // the kernel headers' plain kernels belong to ctr.hip
+#include "itemcf.h"
 #include "walk.h"
 #include "lds_lists.h"
 #include "mfma_gemm.h"

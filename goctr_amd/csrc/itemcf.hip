@@ -14,9 +14,10 @@
 //   icf_weight_kernel     co, cnt -> w; the sort key (i << 24 | 2^24 - 1 - w) -- one stable sort leaves every item's pairs by w
 //                         descending and, among equal w, in the order they had: j ascending
 //   icf_starts_kernel, icf_emit_kernel   the first n_nbr pairs of every item with w > 0
-// Recall (icf_recall_kernel): one workgroup per request row, below.  Recommend: recall_rank_run at the end of the file, the driver
-// goctr_recommend_itemcf and goctr_recommend_blend (popular.hip) share: they differ in the recall stage alone.  goctr_recommend_blend_mmr
-// hands the driver a re-rank stage: rerank.hip's selection then runs in place of icf_select_kernel.
+// Recall (icf_recall_kernel): one workgroup per request row, below.  The two drivers of recall.h are at the end of the file:
+// recall_only_run, which every stand-alone goctr_*_recall entry goes through, and recall_rank_run, which every goctr_recommend_*
+// entry behind goctr_recommend_topn goes through; the entries differ in the recall stage alone.  goctr_recommend_blend_mmr hands
+// recall_rank_run a re-rank stage: rerank.hip's selection then runs in place of icf_select_kernel.
 #include <algorithm>
 #include <climits>
 #include <memory>
@@ -345,16 +346,14 @@ int RecallInputs::stage(const int32_t* h_users, const int64_t* h_ts, const int32
   return 0;
 }
 
-int recall_launch(const goctr_itemcf* h, const long long* off, const int32_t* seq_items, const long long* seq_ts,
-                  const RecallInputs& in, bool has_targets, int64_t nq, const goctr_recall_cfg& cfg, int stride, int32_t* o_items,
-                  unsigned int* o_w, int32_t* o_count, int32_t* o_tpos, hipStream_t st) {
+int recall_launch(const goctr_itemcf* h, const RecallCall& r, const RecallRows& out, hipStream_t st) {
   RecallArgs a{};
-  a.off = off; a.seq_items = seq_items; a.seq_ts = seq_ts;
+  a.off = r.seq.off; a.seq_items = r.seq.items; a.seq_ts = r.seq.ts;
   a.n_items = h->n_items; a.M = h->M; a.nbr_items = h->nbr_items.p; a.nbr_w = h->nbr_w.p;
-  a.users = in.users.p; a.ts = in.ts.p; a.targets = has_targets ? in.targets.p : nullptr;
-  a.H = cfg.history; a.n_cand = cfg.n_cand; a.exclude = cfg.exclude; a.stride = stride;
-  a.out_items = o_items; a.out_w = o_w; a.out_count = o_count; a.out_tpos = o_tpos;
-  hipLaunchKernelGGL(icf_recall_kernel, dim3((unsigned)nq), dim3(SEL_THREADS), 0, st, a);
+  a.users = r.in.users.p; a.ts = r.in.ts.p; a.targets = r.targets();
+  a.H = r.cfg.history; a.n_cand = r.cfg.n_cand; a.exclude = r.cfg.exclude; a.stride = r.stride;
+  a.out_items = out.items; a.out_w = out.w; a.out_count = out.count; a.out_tpos = out.tpos;
+  hipLaunchKernelGGL(icf_recall_kernel, dim3((unsigned)r.nq), dim3(SEL_THREADS), 0, st, a);
   GOCTR_HIP(hipGetLastError());
   return 0;
 }
@@ -376,6 +375,36 @@ int itemcf_check_recommend(const goctr_itemcf* h, const ItemcfRecArgs& a, int64_
   return recall_check_recommend(who, a, n_users);
 }
 
+// out_target_pos's rule, the one place: the stage's column when the call has targets, -1 throughout when it has none
+static int stage_target_pos(HostStage& out, int32_t* out_target_pos, const int32_t* targets, const int32_t* d_tpos, int64_t nq) {
+  if (targets) return out.add(out_target_pos, d_tpos, sizeof(int32_t) * (size_t)nq);
+  out.fill(out_target_pos, 0xff, sizeof(int32_t) * (size_t)nq);
+  return 0;
+}
+
+int recall_only_run(goctr_ubcache* c, const int32_t* users, const int64_t* ts, const int32_t* targets, int64_t n_req, int n_cand,
+                    const RecallStage& stage, HostStage& out, int32_t* out_items, uint32_t* out_w, uint8_t* out_src,
+                    int32_t* out_count, int32_t* out_target_pos) {
+  hipStream_t s = engine().stream;
+  const size_t nq = (size_t)n_req, n = nq * (size_t)n_cand;
+  RecallInputs in;
+  DevBuf<int32_t> o_items, o_count, o_tpos;
+  DevBuf<unsigned int> o_w;
+  DevBuf<unsigned char> o_src;
+  UbRead image(c, s);                         // (behind the buffers: an error return drains the stream before they are freed)
+  if (in.stage(users, ts, targets, n_req, s)) return -1;
+  if (o_items.alloc(n, false) || o_w.alloc(n, false) || o_count.alloc(nq, false) || o_tpos.alloc(nq, false) ||
+      (out_src && o_src.alloc(n, false))) return -1;
+  if (stage(in, RecallRows{o_items.p, o_w.p, o_count.p, o_tpos.p, o_src.p}, s)) return -1;
+  if (out.add(out_items, o_items.p, sizeof(int32_t) * n) || out.add(out_w, o_w.p, sizeof(unsigned int) * n) ||
+      out.add(out_src, o_src.p, n) || out.add(out_count, o_count.p, sizeof(int32_t) * nq) ||
+      stage_target_pos(out, out_target_pos, targets, o_tpos.p, n_req)) return -1;
+  GOCTR_HIP(hipStreamSynchronize(s));
+  image.done();
+  out.commit();
+  return 0;
+}
+
 int recall_rank_run(const TopnScorer& sc, const char* who, const ItemcfRecArgs& a, bool with_src, const RecallStage& recall,
                     const RerankStage* rerank) {
   const int64_t nq = a.n_req;
@@ -383,6 +412,7 @@ int recall_rank_run(const TopnScorer& sc, const char* who, const ItemcfRecArgs& 
   const int64_t P = a.pass_rows ? a.pass_rows : TOPN_DEFAULT_PASS_ROWS;
   GOCTR_CHECK(P <= sc.max_rows, "%s: the serving slot holds %lld rows, the pass needs %lld", who, (long long)sc.max_rows, (long long)P);
   hipStream_t st = sc.stream;
+  HostStage out(st);                                      // (in front of the buffers and the drain: freed once the stream is idle)
   RecallInputs in;
   DevBuf<int32_t> c_items, c_count, c_tpos, o_items, o_count;
   DevBuf<unsigned int> c_w, o_scores;
@@ -392,12 +422,8 @@ int recall_rank_run(const TopnScorer& sc, const char* who, const ItemcfRecArgs& 
   DevBuf<unsigned long long> d_nfailed;
   DevBuf<int32_t> r_obj, r_tplace;                        // the re-rank's own outputs
   DevBuf<unsigned int> r_pen;
-  std::vector<int32_t> h_count((size_t)nq), h_tpos((size_t)nq), h_items((size_t)nq * k), h_ocount((size_t)nq), h_citems, h_robj, h_rtplace;
-  std::vector<unsigned> h_scores((size_t)nq * k), h_cw, h_rpen;
-  std::vector<float> h_cscores;
-  std::vector<unsigned char> h_osrc, h_csrc;
-  std::vector<long long> h_pre((size_t)nq + 1), h_rank((size_t)nq);
-  unsigned long long h_nfailed = 0;
+  std::vector<int32_t> h_count((size_t)nq);
+  std::vector<long long> h_pre((size_t)nq + 1);
   StreamDrain drain{st};                                  // (declared behind the buffers: runs before they are released)
   if (in.stage(a.users, a.ts, a.targets, nq, st)) return -1;
   if (c_items.alloc((size_t)nq * nc, false) || c_w.alloc((size_t)nq * nc, false) || c_count.alloc((size_t)nq, false) ||
@@ -445,44 +471,24 @@ int recall_rank_run(const TopnScorer& sc, const char* who, const ItemcfRecArgs& 
     hipLaunchKernelGGL(icf_select_kernel, dim3((unsigned)nq), dim3(SEL_THREADS), 0, st, s);
     GOCTR_HIP(hipGetLastError());
   }
-  // the results are staged on the host so that a failing copy leaves the caller's arrays as they were
-  GOCTR_HIP(hipMemcpyAsync(h_items.data(), o_items.p, sizeof(int32_t) * h_items.size(), hipMemcpyDeviceToHost, st));
-  GOCTR_HIP(hipMemcpyAsync(h_scores.data(), o_scores.p, sizeof(unsigned) * h_scores.size(), hipMemcpyDeviceToHost, st));
-  GOCTR_HIP(hipMemcpyAsync(h_ocount.data(), o_count.p, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, st));
-  GOCTR_HIP(hipMemcpyAsync(h_rank.data(), o_rank.p, sizeof(long long) * (size_t)nq, hipMemcpyDeviceToHost, st));
-  GOCTR_HIP(hipMemcpyAsync(h_tpos.data(), c_tpos.p, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, st));
-  GOCTR_HIP(hipMemcpyAsync(&h_nfailed, d_nfailed.p, sizeof h_nfailed, hipMemcpyDeviceToHost, st));
-  if (a.cand_items) { h_citems.resize((size_t)nq * nc); GOCTR_HIP(hipMemcpyAsync(h_citems.data(), c_items.p, sizeof(int32_t) * h_citems.size(), hipMemcpyDeviceToHost, st)); }
-  if (a.cand_w) { h_cw.resize((size_t)nq * nc); GOCTR_HIP(hipMemcpyAsync(h_cw.data(), c_w.p, sizeof(unsigned) * h_cw.size(), hipMemcpyDeviceToHost, st)); }
-  if (a.cand_scores) { h_cscores.resize((size_t)nq * nc); GOCTR_HIP(hipMemcpyAsync(h_cscores.data(), c_scores.p, sizeof(float) * h_cscores.size(), hipMemcpyDeviceToHost, st)); }
-  if (with_src && a.out_src) { h_osrc.resize((size_t)nq * k); GOCTR_HIP(hipMemcpyAsync(h_osrc.data(), o_src.p, h_osrc.size(), hipMemcpyDeviceToHost, st)); }
-  if (with_src && a.cand_src) { h_csrc.resize((size_t)nq * nc); GOCTR_HIP(hipMemcpyAsync(h_csrc.data(), c_src.p, h_csrc.size(), hipMemcpyDeviceToHost, st)); }
-  if (rerank && rerank->out_obj) { h_robj.resize((size_t)nq * k); GOCTR_HIP(hipMemcpyAsync(h_robj.data(), r_obj.p, sizeof(int32_t) * h_robj.size(), hipMemcpyDeviceToHost, st)); }
-  if (rerank && rerank->out_pen) { h_rpen.resize((size_t)nq * k); GOCTR_HIP(hipMemcpyAsync(h_rpen.data(), r_pen.p, sizeof(unsigned) * h_rpen.size(), hipMemcpyDeviceToHost, st)); }
-  if (rerank && rerank->out_target_place) { h_rtplace.resize((size_t)nq); GOCTR_HIP(hipMemcpyAsync(h_rtplace.data(), r_tplace.p, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, st)); }
+  const size_t rows = (size_t)nq, nk = rows * (size_t)k, nn = rows * (size_t)nc;
+  if (out.add(a.out_items, o_items.p, sizeof(int32_t) * nk) || out.add(a.out_scores, o_scores.p, sizeof(float) * nk) ||
+      out.add(a.out_count, o_count.p, sizeof(int32_t) * rows) || out.add(a.out_target_rank, o_rank.p, sizeof(int64_t) * rows) ||
+      stage_target_pos(out, a.out_target_pos, a.targets, c_tpos.p, nq) || out.add(a.n_failed, d_nfailed.p, sizeof(int64_t)) ||
+      out.add(a.cand_items, c_items.p, sizeof(int32_t) * nn) || out.add(a.cand_w, c_w.p, sizeof(uint32_t) * nn) ||
+      out.add(a.cand_scores, c_scores.p, sizeof(float) * nn)) return -1;
+  if (with_src && (out.add(a.out_src, o_src.p, nk) || out.add(a.cand_src, c_src.p, nn))) return -1;
+  if (rerank && (out.add(rerank->out_obj, r_obj.p, sizeof(int32_t) * nk) || out.add(rerank->out_pen, r_pen.p, sizeof(uint32_t) * nk) ||
+                 out.add(rerank->out_target_place, r_tplace.p, sizeof(int32_t) * rows))) return -1;
   GOCTR_HIP(hipStreamSynchronize(st));
-  memcpy(a.out_items, h_items.data(), sizeof(int32_t) * h_items.size());
-  memcpy(a.out_scores, h_scores.data(), sizeof(unsigned) * h_scores.size());
-  memcpy(a.out_count, h_ocount.data(), sizeof(int32_t) * (size_t)nq);
-  if (a.out_cand_count) memcpy(a.out_cand_count, h_count.data(), sizeof(int32_t) * (size_t)nq);
-  if (a.out_target_pos) for (int64_t q = 0; q < nq; ++q) a.out_target_pos[q] = a.targets ? h_tpos[q] : -1;
-  if (a.out_target_rank) memcpy(a.out_target_rank, h_rank.data(), sizeof(long long) * (size_t)nq);
-  if (a.cand_items) memcpy(a.cand_items, h_citems.data(), sizeof(int32_t) * h_citems.size());
-  if (a.cand_w) memcpy(a.cand_w, h_cw.data(), sizeof(unsigned) * h_cw.size());
-  if (a.cand_scores) memcpy(a.cand_scores, h_cscores.data(), sizeof(float) * h_cscores.size());
-  if (!h_osrc.empty()) memcpy(a.out_src, h_osrc.data(), h_osrc.size());
-  if (!h_csrc.empty()) memcpy(a.cand_src, h_csrc.data(), h_csrc.size());
-  if (!h_robj.empty()) memcpy(rerank->out_obj, h_robj.data(), sizeof(int32_t) * h_robj.size());
-  if (!h_rpen.empty()) memcpy(rerank->out_pen, h_rpen.data(), sizeof(unsigned) * h_rpen.size());
-  if (!h_rtplace.empty()) memcpy(rerank->out_target_place, h_rtplace.data(), sizeof(int32_t) * (size_t)nq);
-  if (a.n_failed) *a.n_failed = (int64_t)h_nfailed;
+  out.commit();
+  if (a.out_cand_count) memcpy(a.out_cand_count, h_count.data(), sizeof(int32_t) * rows);   // (came back with the first wait)
   return 0;
 }
 
 int itemcf_recommend_run(const TopnScorer& sc, const goctr_itemcf* h, const ItemcfRecArgs& a) {
   return recall_rank_run(sc, "goctr_recommend_itemcf", a, false, [&](const RecallInputs& in, const RecallRows& o, hipStream_t st) {
-    return recall_launch(h, sc.ub_off, sc.ub_items, sc.ub_ts, in, a.targets != nullptr, a.n_req, a.rcfg, a.rcfg.n_cand, o.items, o.w,
-                         o.count, o.tpos, st);
+    return recall_launch(h, recall_call(sc, a, in), o, st);
   });
 }
 
@@ -629,30 +635,10 @@ int goctr_itemcf_recall(goctr_itemcf* h, goctr_ubcache* c, const int32_t* users,
   GOCTR_CHECK(h && c && users && cfg && out_items && out_w && out_count, "%s: null argument", who);
   GOCTR_SAME_ENGINE(h, c);
   if (recall_check_cfg(cfg, who) || recall_check_users(users, n_req, c->n_users, who)) return -1;
-  hipStream_t s = engine().stream;
-  const size_t nq = (size_t)n_req, nc = (size_t)cfg->n_cand;
-  RecallInputs in;
-  DevBuf<int32_t> o_items, o_count, o_tpos;
-  DevBuf<unsigned int> o_w;
-  // the results are staged on the host so that a failing copy leaves the caller's arrays as they were
-  std::vector<int32_t> h_items(nq * nc), h_count(nq), h_tpos(nq);
-  std::vector<unsigned int> h_w(nq * nc);
-  UbRead image(c, s);                         // (behind the buffers: an error return drains the stream before they are freed)
-  if (in.stage(users, ts, targets, n_req, s)) return -1;
-  if (o_items.alloc(nq * nc, false) || o_w.alloc(nq * nc, false) || o_count.alloc(nq, false) || o_tpos.alloc(nq, false)) return -1;
-  if (recall_launch(h, c->off.p, c->items.p, c->ts.p, in, targets != nullptr, n_req, *cfg, cfg->n_cand, o_items.p, o_w.p, o_count.p,
-                    o_tpos.p, s)) return -1;
-  GOCTR_HIP(hipMemcpyAsync(h_items.data(), o_items.p, sizeof(int32_t) * nq * nc, hipMemcpyDeviceToHost, s));
-  GOCTR_HIP(hipMemcpyAsync(h_w.data(), o_w.p, sizeof(unsigned int) * nq * nc, hipMemcpyDeviceToHost, s));
-  GOCTR_HIP(hipMemcpyAsync(h_count.data(), o_count.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));
-  GOCTR_HIP(hipMemcpyAsync(h_tpos.data(), o_tpos.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));
-  GOCTR_HIP(hipStreamSynchronize(s));
-  image.done();
-  memcpy(out_items, h_items.data(), sizeof(int32_t) * nq * nc);
-  memcpy(out_w, h_w.data(), sizeof(unsigned int) * nq * nc);
-  memcpy(out_count, h_count.data(), sizeof(int32_t) * nq);
-  if (out_target_pos) for (size_t q = 0; q < nq; ++q) out_target_pos[q] = targets ? h_tpos[q] : -1;
-  return 0;
+  HostStage out(engine().stream);
+  return recall_only_run(c, users, ts, targets, n_req, cfg->n_cand, [&](const RecallInputs& in, const RecallRows& o, hipStream_t st) {
+    return recall_launch(h, RecallCall{CacheSeq(c), in, targets != nullptr, n_req, *cfg, cfg->n_cand}, o, st);
+  }, out, out_items, out_w, nullptr, out_count, out_target_pos);
 }
 
 }  // extern "C"

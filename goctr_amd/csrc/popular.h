@@ -1,6 +1,6 @@
 // popular.h -- the handle of goctr_popular_build (popular.hip) and what goctr_recommend_blend's two halves share: serve.hip has
 // the entry point and lends the same TopnScorer as to top-N and ItemCF (with_scorer); popular.hip has the popularity build, the
-// blend of the recall channels and the call's driver, which is itemcf.h's recall_rank_run with the blend as its recall stage.
+// blend of the recall channels and the call's driver, which is recall.h's recall_rank_run with the blend as its recall stage.
 #pragma once
 #include "itemcf.h"
 #include "uservec.h"

@@ -9,7 +9,7 @@
 //   radix_sort_pairs    (score, item index) by score descending; stable, so equal scores stay by item ascending
 //   pop_cut_kernel      the first n_list entries with a positive score; n_listed
 // Blend (blend_fill_kernel): one workgroup per request row, behind icf_recall_kernel (part A) on the same stream.  Recommend:
-// blend_recommend_run at the end of the file -- itemcf.h's recall_rank_run with these two launches as its recall stage.
+// blend_recommend_run at the end of the file -- recall.h's recall_rank_run with these two launches as its recall stage.
 #include <algorithm>
 #include <climits>
 #include <memory>
@@ -224,26 +224,21 @@ __global__ __launch_bounds__(SEL_THREADS) void blend_fill_kernel(BlendFillArgs a
   }
 }
 
-// the cache's image as the kernels take it (null together: no cache)
-struct CacheImage { const long long* off; const int32_t* items; const long long* ts; };
-
 // the recall stage of a blend on `st`: part A by icf_recall_kernel into the rows' first n_cand - quota_pop slots, then the fill
-int blend_launch(const BlendArgs& b, const CacheImage& im, long long n_items, const RecallInputs& in, bool has_targets, int64_t nq,
-                 const goctr_recall_cfg& cfg, const int32_t* d_extra, const RecallRows& o, hipStream_t st) {
-  goctr_recall_cfg cfg_a = cfg;
-  cfg_a.n_cand = cfg.n_cand - b.quota_pop;
-  const bool have_a = b.icf && im.off && cfg_a.n_cand > 0;
-  if (have_a && recall_launch(b.icf, im.off, im.items, im.ts, in, has_targets, nq, cfg_a, cfg.n_cand, o.items, o.w, o.count, o.tpos, st))
-    return -1;
+int blend_launch(const BlendArgs& b, const RecallCall& r, long long n_items, const int32_t* d_extra, const RecallRows& o, hipStream_t st) {
+  RecallCall part_a = r;
+  part_a.cfg.n_cand = r.cfg.n_cand - b.quota_pop;
+  const bool have_a = b.icf && r.seq.off && part_a.cfg.n_cand > 0;
+  if (have_a && recall_launch(b.icf, part_a, o, st)) return -1;
   BlendFillArgs a{};
-  a.off = im.off; a.seq_items = im.items; a.seq_ts = im.ts;
+  a.off = r.seq.off; a.seq_items = r.seq.items; a.seq_ts = r.seq.ts;
   a.n_items = n_items;
-  a.users = in.users.p; a.ts = in.ts.p; a.targets = has_targets ? in.targets.p : nullptr;
+  a.users = r.in.users.p; a.ts = r.in.ts.p; a.targets = r.targets();
   a.extra = b.n_extra > 0 ? d_extra : nullptr; a.n_extra = b.n_extra;
   a.list_items = b.pop ? b.pop->list_items.p : nullptr; a.n_listed = b.pop ? b.pop->n_listed : 0;
-  a.n_cand = cfg.n_cand; a.quota_pop = b.quota_pop; a.exclude = cfg.exclude; a.have_a = have_a ? 1 : 0;
+  a.n_cand = r.cfg.n_cand; a.quota_pop = b.quota_pop; a.exclude = r.cfg.exclude; a.have_a = have_a ? 1 : 0;
   a.out_items = o.items; a.out_w = o.w; a.out_src = o.src; a.out_count = o.count; a.out_tpos = o.tpos;
-  hipLaunchKernelGGL(blend_fill_kernel, dim3((unsigned)nq), dim3(SEL_THREADS), 0, st, a);
+  hipLaunchKernelGGL(blend_fill_kernel, dim3((unsigned)r.nq), dim3(SEL_THREADS), 0, st, a);
   GOCTR_HIP(hipGetLastError());
   return 0;
 }
@@ -277,31 +272,21 @@ int blend_recommend_run(const TopnScorer& sc, const char* who, const BlendArgs& 
   DevBuf<unsigned int> x_w;
   UvScratch uv_ws;
   return recall_rank_run(sc, who, a, true, [&](const RecallInputs& in, const RecallRows& o, hipStream_t st) {
-    if (b.als) {                              // part X's list comes from the ALS fold-in recall over b.uv, straight into d_extra
-      const size_t n = (size_t)a.n_req * (size_t)b.n_extra;
+    const RecallCall r = recall_call(sc, a, in);
+    const size_t n = (size_t)a.n_req * (size_t)b.n_extra;
+    if (b.uv || b.wg) {                       // part X's list comes from a recall channel, straight into d_extra
       if (d_extra.alloc(n, false) || x_w.alloc(n, false) || x_count.alloc((size_t)a.n_req, false)) return -1;
-      const goctr_recall_cfg xcfg{a.rcfg.history, b.n_extra, a.rcfg.exclude};
-      if (als_launch(b.als, b.uv, sc.ub_off, sc.ub_items, sc.ub_ts, in, a.targets != nullptr, a.n_req, xcfg, b.ucfg, b.n_extra,
-                     d_extra.p, x_w.p, x_count.p, nullptr, nullptr, nullptr, uv_ws, st)) return -1;
-    } else if (b.uv) {                        // ... or from the user-vector recall
-      const size_t n = (size_t)a.n_req * (size_t)b.n_extra;
-      if (d_extra.alloc(n, false) || x_w.alloc(n, false) || x_count.alloc((size_t)a.n_req, false)) return -1;
-      const goctr_recall_cfg xcfg{a.rcfg.history, b.n_extra, a.rcfg.exclude};
-      if (uservec_launch(b.uv, sc.ub_off, sc.ub_items, sc.ub_ts, in, a.targets != nullptr, a.n_req, xcfg, b.ucfg, b.n_extra,
-                         d_extra.p, x_w.p, x_count.p, nullptr, nullptr, nullptr, uv_ws, st)) return -1;
-    } else if (b.wg) {                        // ... or from the random-walk recall
-      const size_t n = (size_t)a.n_req * (size_t)b.n_extra;
-      if (d_extra.alloc(n, false) || x_w.alloc(n, false) || x_count.alloc((size_t)a.n_req, false)) return -1;
-      const goctr_recall_cfg xcfg{a.rcfg.history, b.n_extra, a.rcfg.exclude};
-      if (walk_launch(b.wg, sc.ub_off, sc.ub_items, sc.ub_ts, in, a.targets != nullptr, a.n_req, xcfg, b.wcfg, b.n_extra, d_extra.p,
-                      x_w.p, x_count.p, nullptr, nullptr, st)) return -1;
+      RecallCall x = r;
+      x.cfg.n_cand = x.stride = b.n_extra;
+      const RecallRows rows{d_extra.p, x_w.p, x_count.p, nullptr, nullptr};
+      if (b.als ? als_launch(b.als, b.uv, x, b.ucfg, rows, AlsVecOut{}, uv_ws, st)        // the ALS fold-in recall over b.uv
+          : b.uv ? uservec_launch(b.uv, x, b.ucfg, rows, UvVecOut{}, uv_ws, st)           // ... the user-vector recall
+                 : walk_launch(b.wg, x, b.wcfg, rows, nullptr, st)) return -1;            // ... the random-walk recall
     } else if (b.n_extra > 0) {
-      const size_t n = (size_t)a.n_req * (size_t)b.n_extra;
       if (d_extra.alloc(n, false)) return -1;
       GOCTR_HIP(hipMemcpyAsync(d_extra.p, b.extra, sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
     }
-    return blend_launch(b, CacheImage{sc.ub_off, sc.ub_items, sc.ub_ts}, sc.n_items, in, a.targets != nullptr, a.n_req, a.rcfg,
-                        d_extra.p, o, st);
+    return blend_launch(b, r, sc.n_items, d_extra.p, o, st);
   }, rerank);
 }
 
@@ -417,40 +402,16 @@ int goctr_blend_recall(goctr_itemcf* icf, goctr_popular* pop, goctr_ubcache* c, 
   GOCTR_CHECK(n_extra >= 0 && n_extra <= 1024, "%s: n_extra = %d is outside 0 .. 1024", who, n_extra);
   long long n_items = 0;
   if (blend_check(who, b, *cfg, (long long)INT32_MAX, &n_items)) return -1;   // (no handle: the largest n_items a handle can have)
-  hipStream_t s = engine().stream;
-  const size_t nq = (size_t)n_req, nc = (size_t)cfg->n_cand;
-  RecallInputs in;
-  DevBuf<int32_t> o_items, o_count, o_tpos, d_extra;
-  DevBuf<unsigned int> o_w;
-  DevBuf<unsigned char> o_src;
-  // the results are staged on the host so that a failing copy leaves the caller's arrays as they were
-  std::vector<int32_t> h_items(nq * nc), h_count(nq), h_tpos(nq);
-  std::vector<unsigned int> h_w(nq * nc);
-  std::vector<unsigned char> h_src(nq * nc);
-  UbRead image(c, s);                         // (behind the buffers: an error return drains the stream before they are freed)
-  if (in.stage(users, ts, targets, n_req, s)) return -1;
-  if (o_items.alloc(nq * nc, false) || o_w.alloc(nq * nc, false) || o_src.alloc(nq * nc, false) || o_count.alloc(nq, false) ||
-      o_tpos.alloc(nq, false)) return -1;
-  if (b.n_extra > 0) {
-    if (d_extra.alloc(nq * (size_t)b.n_extra, false)) return -1;
-    GOCTR_HIP(hipMemcpyAsync(d_extra.p, extra, sizeof(int32_t) * nq * (size_t)b.n_extra, hipMemcpyHostToDevice, s));
-  }
-  const CacheImage im{c ? c->off.p : nullptr, c ? c->items.p : nullptr, c ? c->ts.p : nullptr};
-  if (blend_launch(b, im, n_items, in, targets != nullptr, n_req, *cfg, d_extra.p, RecallRows{o_items.p, o_w.p, o_count.p, o_tpos.p, o_src.p}, s))
-    return -1;
-  GOCTR_HIP(hipMemcpyAsync(h_items.data(), o_items.p, sizeof(int32_t) * nq * nc, hipMemcpyDeviceToHost, s));
-  GOCTR_HIP(hipMemcpyAsync(h_w.data(), o_w.p, sizeof(unsigned int) * nq * nc, hipMemcpyDeviceToHost, s));
-  GOCTR_HIP(hipMemcpyAsync(h_src.data(), o_src.p, nq * nc, hipMemcpyDeviceToHost, s));
-  GOCTR_HIP(hipMemcpyAsync(h_count.data(), o_count.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));
-  GOCTR_HIP(hipMemcpyAsync(h_tpos.data(), o_tpos.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));
-  GOCTR_HIP(hipStreamSynchronize(s));
-  image.done();
-  memcpy(out_items, h_items.data(), sizeof(int32_t) * nq * nc);
-  memcpy(out_w, h_w.data(), sizeof(unsigned int) * nq * nc);
-  memcpy(out_src, h_src.data(), nq * nc);
-  memcpy(out_count, h_count.data(), sizeof(int32_t) * nq);
-  if (out_target_pos) for (size_t q = 0; q < nq; ++q) out_target_pos[q] = targets ? h_tpos[q] : -1;
-  return 0;
+  HostStage out(engine().stream);
+  DevBuf<int32_t> d_extra;
+  return recall_only_run(c, users, ts, targets, n_req, cfg->n_cand, [&](const RecallInputs& in, const RecallRows& o, hipStream_t st) {
+    const size_t n = (size_t)n_req * (size_t)b.n_extra;
+    if (b.n_extra > 0) {
+      if (d_extra.alloc(n, false)) return -1;
+      GOCTR_HIP(hipMemcpyAsync(d_extra.p, extra, sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
+    }
+    return blend_launch(b, RecallCall{CacheSeq(c), in, targets != nullptr, n_req, *cfg, cfg->n_cand}, n_items, d_extra.p, o, st);
+  }, out, out_items, out_w, out_src, out_count, out_target_pos);
 }
 
 }  // extern "C"

@@ -358,14 +358,11 @@ int goctr_rerank_mmr(goctr_itemvec* v, const int32_t* items, const float* scores
                 count[q], n_cand);
   hipStream_t st = engine().stream;
   const size_t nq = (size_t)n_req, nc = (size_t)n_cand, k = (size_t)cfg->k;
+  HostStage out(st);
   DevBuf<int32_t> d_items, d_count, o_pos, o_obj, o_count;
   DevBuf<float> d_scores;
   DevBuf<unsigned int> o_pen;
   DevBuf<u64> d_nfailed;
-  // the results are staged on the host so that a failing copy leaves the caller's arrays as they were
-  std::vector<int32_t> h_pos(nq * k), h_obj(nq * k), h_count(nq);
-  std::vector<unsigned int> h_pen(nq * k);
-  u64 h_nfailed = 0;
   StreamDrain drain{engine().stream};          // (behind the buffers: an error return drains the stream before they are freed)
   if (d_items.alloc(nq * nc, false) || d_scores.alloc(nq * nc, false) || d_count.alloc(nq, false) || o_pos.alloc(nq * k, false) ||
       o_obj.alloc(nq * k, false) || o_pen.alloc(nq * k, false) || o_count.alloc(nq, false) || d_nfailed.alloc(1)) return -1;
@@ -376,17 +373,11 @@ int goctr_rerank_mmr(goctr_itemvec* v, const int32_t* items, const float* scores
   s.cand = d_items.p; s.count = d_count.p; s.scores = d_scores.p; s.n_cand = n_cand; s.k = cfg->k;
   s.out_count = o_count.p; s.n_failed = d_nfailed.p;
   if (mmr_launch(v, *cfg, s, MmrOut{o_pos.p, o_obj.p, o_pen.p, nullptr}, n_req, st)) return -1;
-  GOCTR_HIP(hipMemcpyAsync(h_pos.data(), o_pos.p, sizeof(int32_t) * nq * k, hipMemcpyDeviceToHost, st));
-  GOCTR_HIP(hipMemcpyAsync(h_obj.data(), o_obj.p, sizeof(int32_t) * nq * k, hipMemcpyDeviceToHost, st));
-  GOCTR_HIP(hipMemcpyAsync(h_pen.data(), o_pen.p, sizeof(unsigned int) * nq * k, hipMemcpyDeviceToHost, st));
-  GOCTR_HIP(hipMemcpyAsync(h_count.data(), o_count.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, st));
-  GOCTR_HIP(hipMemcpyAsync(&h_nfailed, d_nfailed.p, sizeof h_nfailed, hipMemcpyDeviceToHost, st));
+  if (out.add(out_pos, o_pos.p, sizeof(int32_t) * nq * k) || out.add(out_obj, o_obj.p, sizeof(int32_t) * nq * k) ||
+      out.add(out_pen, o_pen.p, sizeof(uint32_t) * nq * k) || out.add(out_count, o_count.p, sizeof(int32_t) * nq) ||
+      out.add(n_failed, d_nfailed.p, sizeof(int64_t))) return -1;
   GOCTR_HIP(hipStreamSynchronize(st));
-  memcpy(out_pos, h_pos.data(), sizeof(int32_t) * nq * k);
-  if (out_obj) memcpy(out_obj, h_obj.data(), sizeof(int32_t) * nq * k);
-  if (out_pen) memcpy(out_pen, h_pen.data(), sizeof(unsigned int) * nq * k);
-  memcpy(out_count, h_count.data(), sizeof(int32_t) * nq);
-  if (n_failed) *n_failed = (int64_t)h_nfailed;
+  out.commit();
   return 0;
 }
 

@@ -472,6 +472,40 @@ int with_scorer(goctr_model* m, goctr_recsys* r, int64_t pass_rows, Run run) {
   return 0;
 }
 
+// What every goctr_recommend_* entry refuses first, in this order, behind its EngineScope: a thread without a device; `have` false
+// (the entry's own null test); a re-rank given by half (the blend entries that take one optionally); a handle of `handles` -- the
+// engines of the entry's other handles, null for an absent one -- that lives on another engine than the model; a recsys of other
+// widths than the model
+int recommend_enter(const char* who, bool have, const goctr_model* m, const goctr_recsys* r,
+                    std::initializer_list<const Engine*> handles, bool rerank_paired = true) {
+  if (require_engine()) return -1;
+  GOCTR_CHECK(have, "%s: bad arguments", who);
+  GOCTR_CHECK(rerank_paired, "%s: the re-rank takes both the item vectors and the cfg, or neither", who);
+  GOCTR_CHECK(r->eng == m->eng, "%s: the handles were created on different engines (devices)", who);
+  for (const Engine* e : handles) GOCTR_CHECK(!e || e == m->eng, "%s: the handles were created on different engines (devices)", who);
+  return check_recsys_dims(who, m, r);
+}
+
+// goctr_recommend_blend_uservec / _walk / _als behind recommend_enter: goctr_recommend_blend -- with v and cfg _blend_mmr -- whose
+// part X, b.n_extra entries a row (the entry's parameter `n_name`), a recall channel writes on the device.  check_x: the channel's
+// own refusals; a.k is the entry's k, which the re-rank's cfg overrides
+template <class CheckX>
+int recommend_blend_x(const char* who, goctr_model* m, goctr_recsys* r, const BlendArgs& b, const char* n_name, CheckX check_x,
+                      goctr_itemvec* v, const goctr_mmr_cfg* cfg, ItemcfRecArgs a, int32_t* out_obj, uint32_t* out_pen,
+                      int32_t* out_target_place) {
+  GOCTR_CHECK(b.n_extra >= 1 && b.n_extra <= 1024, "%s: %s = %d is outside 1 .. 1024", who, n_name, b.n_extra);
+  if (check_x()) return -1;
+  if (v) {
+    if (mmr_check_cfg(v, cfg, who)) return -1;
+    GOCTR_CHECK(v->n_items == r->n_items, "%s: the item vectors cover %lld items, the recsys %lld", who, (long long)v->n_items,
+                (long long)r->n_items);
+    a.k = cfg->k;
+  }
+  if (blend_check_recommend(who, b, a, r->n_users, r->n_items)) return -1;
+  const RerankStage rr{v, v ? *cfg : goctr_mmr_cfg{}, out_obj, out_pen, out_target_place};
+  return with_scorer(m, r, a.pass_rows, [&](const TopnScorer& sc) { return blend_recommend_run(sc, who, b, a, v ? &rr : nullptr); });
+}
+
 }  // namespace
 
 extern "C" {
@@ -540,29 +574,22 @@ int goctr_recommend_topn(goctr_model* m, goctr_recsys* r, const int32_t* users, 
                          int32_t* out_items, float* out_scores, int32_t* out_count, int64_t* out_target_rank, float* all_scores,
                          uint8_t* all_flags, int64_t* n_failed) {
   EngineScope on(handle_engine(m));
-  if (require_engine()) return -1;
-  GOCTR_CHECK(m && r && cfg, "goctr_recommend_topn: bad arguments");
-  GOCTR_SAME_ENGINE(m, r);
-  if (check_recsys_dims("goctr_recommend_topn", m, r)) return -1;
+  if (recommend_enter("goctr_recommend_topn", m && r && cfg, m, r, {})) return -1;
   const TopnArgs a{users, ts, n_users_req, pool, n_pool, targets, *cfg, out_items, out_scores, out_count, out_target_rank,
                    all_scores, all_flags, n_failed};
   if (topn_check_args(a, r->n_users)) return -1;
   return with_scorer(m, r, cfg->pass_rows, [&](const TopnScorer& sc) { return topn_run(sc, a); });
 }
 
-// Recall, then rank (itemcf.hip has the recall, the key generator, the selection and the driver): as goctr_recommend_topn above,
-// the recall and every pass under with_scorer's ONE image of the cache.
+// Recall, then rank (recall.h; itemcf.hip has the ItemCF recall, the key generator, the selection and the driver): as
+// goctr_recommend_topn above, the recall and every pass under with_scorer's ONE image of the cache.
 int goctr_recommend_itemcf(goctr_model* m, goctr_recsys* r, goctr_itemcf* h, const int32_t* users, const int64_t* ts, int64_t n_req,
                            const int32_t* targets, const goctr_recall_cfg* recall_cfg, int32_t k, int64_t pass_rows,
                            int32_t* out_items, float* out_scores, int32_t* out_count, int32_t* out_cand_count,
                            int32_t* out_target_pos, int64_t* out_target_rank, int32_t* cand_items, uint32_t* cand_w,
                            float* cand_scores, int64_t* n_failed) {
   EngineScope on(handle_engine(m));
-  if (require_engine()) return -1;
-  GOCTR_CHECK(m && r && h && recall_cfg, "goctr_recommend_itemcf: bad arguments");
-  GOCTR_SAME_ENGINE(m, r);
-  GOCTR_SAME_ENGINE(m, h);
-  if (check_recsys_dims("goctr_recommend_itemcf", m, r)) return -1;
+  if (recommend_enter("goctr_recommend_itemcf", m && r && h && recall_cfg, m, r, {handle_engine(h)})) return -1;
   const ItemcfRecArgs a{users, ts, n_req, targets, *recall_cfg, k, pass_rows, out_items, out_scores, out_count, out_cand_count,
                         out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed};
   if (itemcf_check_recommend(h, a, r->n_users, r->n_items)) return -1;
@@ -578,18 +605,14 @@ int goctr_recommend_blend(goctr_model* m, goctr_recsys* r, goctr_itemcf* icf, go
                           int64_t* out_target_rank, int32_t* cand_items, uint32_t* cand_w, float* cand_scores, uint8_t* cand_src,
                           int64_t* n_failed) {
   EngineScope on(handle_engine(m));
-  if (require_engine()) return -1;
-  GOCTR_CHECK(m && r && recall_cfg, "goctr_recommend_blend: bad arguments");
-  GOCTR_SAME_ENGINE(m, r);
-  GOCTR_SAME_ENGINE(m, icf);
-  GOCTR_SAME_ENGINE(m, pop);
-  if (check_recsys_dims("goctr_recommend_blend", m, r)) return -1;
-  GOCTR_CHECK(n_extra >= 0 && n_extra <= 1024, "goctr_recommend_blend: n_extra = %d is outside 0 .. 1024", n_extra);
+  const char* who = "goctr_recommend_blend";
+  if (recommend_enter(who, m && r && recall_cfg, m, r, {handle_engine(icf), handle_engine(pop)})) return -1;
+  GOCTR_CHECK(n_extra >= 0 && n_extra <= 1024, "%s: n_extra = %d is outside 0 .. 1024", who, n_extra);
   const ItemcfRecArgs a{users, ts, n_req, targets, *recall_cfg, k, pass_rows, out_items, out_scores, out_count, out_cand_count,
                         out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed, out_src, cand_src};
   const BlendArgs b{icf, pop, extra, extra ? n_extra : 0, quota_pop};
-  if (blend_check_recommend("goctr_recommend_blend", b, a, r->n_users, r->n_items)) return -1;
-  return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return blend_recommend_run(sc, "goctr_recommend_blend", b, a); });
+  if (blend_check_recommend(who, b, a, r->n_users, r->n_items)) return -1;
+  return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return blend_recommend_run(sc, who, b, a); });
 }
 
 // goctr_recommend_blend with the MMR selection (rerank.hip) as the driver's last step; everything in front of it is the call above
@@ -601,14 +624,8 @@ int goctr_recommend_blend_mmr(goctr_model* m, goctr_recsys* r, goctr_itemcf* icf
                               uint32_t* cand_w, float* cand_scores, uint8_t* cand_src, int64_t* n_failed, int32_t* out_obj,
                               uint32_t* out_pen, int32_t* out_target_place) {
   EngineScope on(handle_engine(m));
-  if (require_engine()) return -1;
   const char* who = "goctr_recommend_blend_mmr";
-  GOCTR_CHECK(m && r && recall_cfg && v && cfg, "%s: bad arguments", who);
-  GOCTR_SAME_ENGINE(m, r);
-  GOCTR_SAME_ENGINE(m, icf);
-  GOCTR_SAME_ENGINE(m, pop);
-  GOCTR_SAME_ENGINE(m, v);
-  if (check_recsys_dims(who, m, r)) return -1;
+  if (recommend_enter(who, m && r && recall_cfg && v && cfg, m, r, {handle_engine(icf), handle_engine(pop), handle_engine(v)})) return -1;
   GOCTR_CHECK(n_extra >= 0 && n_extra <= 1024, "%s: n_extra = %d is outside 0 .. 1024", who, n_extra);
   if (mmr_check_cfg(v, cfg, who)) return -1;
   GOCTR_CHECK(v->n_items == r->n_items, "%s: the item vectors cover %lld items, the recsys %lld", who, (long long)v->n_items,
@@ -628,11 +645,7 @@ int goctr_recommend_uservec(goctr_model* m, goctr_recsys* r, goctr_itemvec* v, c
                             int32_t* out_target_pos, int64_t* out_target_rank, int32_t* cand_items, uint32_t* cand_w,
                             float* cand_scores, int64_t* n_failed) {
   EngineScope on(handle_engine(m));
-  if (require_engine()) return -1;
-  GOCTR_CHECK(m && r && v && recall_cfg && ucfg, "goctr_recommend_uservec: bad arguments");
-  GOCTR_SAME_ENGINE(m, r);
-  GOCTR_SAME_ENGINE(m, v);
-  if (check_recsys_dims("goctr_recommend_uservec", m, r)) return -1;
+  if (recommend_enter("goctr_recommend_uservec", m && r && v && recall_cfg && ucfg, m, r, {handle_engine(v)})) return -1;
   const ItemcfRecArgs a{users, ts, n_req, targets, *recall_cfg, k, pass_rows, out_items, out_scores, out_count, out_cand_count,
                         out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed};
   if (uservec_check_recommend(v, ucfg, a, r->n_users, r->n_items)) return -1;
@@ -646,11 +659,7 @@ int goctr_recommend_uservec_ivf(goctr_model* m, goctr_recsys* r, goctr_itemvec_i
                                 int32_t* out_count, int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank,
                                 int32_t* cand_items, uint32_t* cand_w, float* cand_scores, int64_t* n_failed) {
   EngineScope on(handle_engine(m));
-  if (require_engine()) return -1;
-  GOCTR_CHECK(m && r && x && recall_cfg && icfg, "goctr_recommend_uservec_ivf: bad arguments");
-  GOCTR_SAME_ENGINE(m, r);
-  GOCTR_SAME_ENGINE(m, x);
-  if (check_recsys_dims("goctr_recommend_uservec_ivf", m, r)) return -1;
+  if (recommend_enter("goctr_recommend_uservec_ivf", m && r && x && recall_cfg && icfg, m, r, {handle_engine(x)})) return -1;
   const ItemcfRecArgs a{users, ts, n_req, targets, *recall_cfg, k, pass_rows, out_items, out_scores, out_count, out_cand_count,
                         out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed};
   if (uservec_ivf_check_recommend(x, icfg, a, r->n_users, r->n_items)) return -1;
@@ -666,11 +675,7 @@ int goctr_recommend_uservec_multi(goctr_model* m, goctr_recsys* r, goctr_itemvec
                                   int64_t* out_target_rank, int32_t* cand_items, uint32_t* cand_w, float* cand_scores,
                                   int64_t* n_failed, uint8_t* cand_interest, int32_t* out_n_int) {
   EngineScope on(handle_engine(m));
-  if (require_engine()) return -1;
-  GOCTR_CHECK(m && r && v && recall_cfg && mcfg, "goctr_recommend_uservec_multi: bad arguments");
-  GOCTR_SAME_ENGINE(m, r);
-  GOCTR_SAME_ENGINE(m, v);
-  if (check_recsys_dims("goctr_recommend_uservec_multi", m, r)) return -1;
+  if (recommend_enter("goctr_recommend_uservec_multi", m && r && v && recall_cfg && mcfg, m, r, {handle_engine(v)})) return -1;
   const ItemcfRecArgs a{users, ts, n_req, targets, *recall_cfg, k, pass_rows, out_items, out_scores, out_count, out_cand_count,
                         out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed, nullptr, cand_interest};
   if (uservec_multi_check_recommend(v, mcfg, a, r->n_users, r->n_items)) return -1;
@@ -687,33 +692,23 @@ int goctr_recommend_blend_uservec(goctr_model* m, goctr_recsys* r, goctr_itemcf*
                                   float* cand_scores, uint8_t* cand_src, int64_t* n_failed, int32_t* out_obj, uint32_t* out_pen,
                                   int32_t* out_target_place) {
   EngineScope on(handle_engine(m));
-  if (require_engine()) return -1;
   const char* who = "goctr_recommend_blend_uservec";
-  GOCTR_CHECK(m && r && recall_cfg && uv && ucfg, "%s: bad arguments", who);
-  GOCTR_CHECK((v != nullptr) == (cfg != nullptr), "%s: the re-rank takes both the item vectors and the cfg, or neither", who);
-  GOCTR_SAME_ENGINE(m, r);
-  GOCTR_SAME_ENGINE(m, icf);
-  GOCTR_SAME_ENGINE(m, pop);
-  GOCTR_SAME_ENGINE(m, uv);
-  GOCTR_SAME_ENGINE(m, v);
-  if (check_recsys_dims(who, m, r)) return -1;
-  GOCTR_CHECK(n_vec >= 1 && n_vec <= 1024, "%s: n_vec = %d is outside 1 .. 1024", who, n_vec);
-  if (uservec_check_cfg(ucfg, who)) return -1;
-  GOCTR_CHECK(uv->n_items == r->n_items, "%s: the user-vector recall's item vectors cover %lld items, the recsys %lld", who,
-              (long long)uv->n_items, (long long)r->n_items);
-  if (v) {
-    if (mmr_check_cfg(v, cfg, who)) return -1;
-    GOCTR_CHECK(v->n_items == r->n_items, "%s: the item vectors cover %lld items, the recsys %lld", who, (long long)v->n_items,
-                (long long)r->n_items);
-  }
-  const ItemcfRecArgs a{users, ts, n_req, targets, *recall_cfg, v ? cfg->k : k, pass_rows, out_items, out_scores, out_count,
-                        out_cand_count, out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed, out_src, cand_src};
+  if (recommend_enter(who, m && r && recall_cfg && uv && ucfg, m, r,
+                      {handle_engine(icf), handle_engine(pop), handle_engine(uv), handle_engine(v)}, (v != nullptr) == (cfg != nullptr)))
+    return -1;
   BlendArgs b{icf, pop, nullptr, n_vec, quota_pop};
   b.uv = uv; b.ucfg = *ucfg;
-  if (blend_check_recommend(who, b, a, r->n_users, r->n_items)) return -1;
-  if (!v) return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return blend_recommend_run(sc, who, b, a); });
-  const RerankStage rr{v, *cfg, out_obj, out_pen, out_target_place};
-  return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return blend_recommend_run(sc, who, b, a, &rr); });
+  const auto check_x = [&] {
+    if (uservec_check_cfg(ucfg, who)) return -1;
+    GOCTR_CHECK(uv->n_items == r->n_items, "%s: the user-vector recall's item vectors cover %lld items, the recsys %lld", who,
+                (long long)uv->n_items, (long long)r->n_items);
+    return 0;
+  };
+  return recommend_blend_x(who, m, r, b, "n_vec", check_x, v, cfg,
+                           ItemcfRecArgs{users, ts, n_req, targets, *recall_cfg, k, pass_rows, out_items, out_scores, out_count,
+                                         out_cand_count, out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed,
+                                         out_src, cand_src},
+                           out_obj, out_pen, out_target_place);
 }
 
 // goctr_recommend_itemcf with the random-walk recall (walk.hip) as the driver's recall stage
@@ -723,12 +718,8 @@ int goctr_recommend_walk(goctr_model* m, goctr_recsys* r, goctr_walkgraph* g, co
                          int32_t* out_target_pos, int64_t* out_target_rank, int32_t* cand_items, uint32_t* cand_w, float* cand_scores,
                          int64_t* n_failed) {
   EngineScope on(handle_engine(m));
-  if (require_engine()) return -1;
   const char* who = "goctr_recommend_walk";
-  GOCTR_CHECK(m && r && g && recall_cfg && wcfg, "%s: bad arguments", who);
-  GOCTR_SAME_ENGINE(m, r);
-  GOCTR_SAME_ENGINE(m, g);
-  if (check_recsys_dims(who, m, r)) return -1;
+  if (recommend_enter(who, m && r && g && recall_cfg && wcfg, m, r, {handle_engine(g)})) return -1;
   const ItemcfRecArgs a{users, ts, n_req, targets, *recall_cfg, k, pass_rows, out_items, out_scores, out_count, out_cand_count,
                         out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed};
   if (walk_check_recommend(who, g, wcfg, a, r->n_users, r->n_items)) return -1;
@@ -745,35 +736,25 @@ int goctr_recommend_blend_walk(goctr_model* m, goctr_recsys* r, goctr_itemcf* ic
                                float* cand_scores, uint8_t* cand_src, int64_t* n_failed, int32_t* out_obj, uint32_t* out_pen,
                                int32_t* out_target_place) {
   EngineScope on(handle_engine(m));
-  if (require_engine()) return -1;
   const char* who = "goctr_recommend_blend_walk";
-  GOCTR_CHECK(m && r && recall_cfg && g && wcfg, "%s: bad arguments", who);
-  GOCTR_CHECK((v != nullptr) == (cfg != nullptr), "%s: the re-rank takes both the item vectors and the cfg, or neither", who);
-  GOCTR_SAME_ENGINE(m, r);
-  GOCTR_SAME_ENGINE(m, icf);
-  GOCTR_SAME_ENGINE(m, pop);
-  GOCTR_SAME_ENGINE(m, g);
-  GOCTR_SAME_ENGINE(m, v);
-  if (check_recsys_dims(who, m, r)) return -1;
-  GOCTR_CHECK(n_walk >= 1 && n_walk <= 1024, "%s: n_walk = %d is outside 1 .. 1024", who, n_walk);
-  if (walk_check_cfg(wcfg, who)) return -1;
-  GOCTR_CHECK(g->n_items == r->n_items, "%s: the walk graph covers %lld items, the recsys %lld", who, (long long)g->n_items,
-              (long long)r->n_items);
-  GOCTR_CHECK(g->n_users == r->n_users, "%s: the walk graph has %lld users, the recsys %lld", who, (long long)g->n_users,
-              (long long)r->n_users);
-  if (v) {
-    if (mmr_check_cfg(v, cfg, who)) return -1;
-    GOCTR_CHECK(v->n_items == r->n_items, "%s: the item vectors cover %lld items, the recsys %lld", who, (long long)v->n_items,
-                (long long)r->n_items);
-  }
-  const ItemcfRecArgs a{users, ts, n_req, targets, *recall_cfg, v ? cfg->k : k, pass_rows, out_items, out_scores, out_count,
-                        out_cand_count, out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed, out_src, cand_src};
+  if (recommend_enter(who, m && r && recall_cfg && g && wcfg, m, r,
+                      {handle_engine(icf), handle_engine(pop), handle_engine(g), handle_engine(v)}, (v != nullptr) == (cfg != nullptr)))
+    return -1;
   BlendArgs b{icf, pop, nullptr, n_walk, quota_pop};
   b.wg = g; b.wcfg = *wcfg;
-  if (blend_check_recommend(who, b, a, r->n_users, r->n_items)) return -1;
-  if (!v) return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return blend_recommend_run(sc, who, b, a); });
-  const RerankStage rr{v, *cfg, out_obj, out_pen, out_target_place};
-  return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return blend_recommend_run(sc, who, b, a, &rr); });
+  const auto check_x = [&] {
+    if (walk_check_cfg(wcfg, who)) return -1;
+    GOCTR_CHECK(g->n_items == r->n_items, "%s: the walk graph covers %lld items, the recsys %lld", who, (long long)g->n_items,
+                (long long)r->n_items);
+    GOCTR_CHECK(g->n_users == r->n_users, "%s: the walk graph has %lld users, the recsys %lld", who, (long long)g->n_users,
+                (long long)r->n_users);
+    return 0;
+  };
+  return recommend_blend_x(who, m, r, b, "n_walk", check_x, v, cfg,
+                           ItemcfRecArgs{users, ts, n_req, targets, *recall_cfg, k, pass_rows, out_items, out_scores, out_count,
+                                         out_cand_count, out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed,
+                                         out_src, cand_src},
+                           out_obj, out_pen, out_target_place);
 }
 
 // goctr_recommend_itemcf with the ALS fold-in recall (als.hip) as the driver's recall stage
@@ -783,13 +764,8 @@ int goctr_recommend_als(goctr_model* m, goctr_recsys* r, goctr_als* als, goctr_i
                         int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank, int32_t* cand_items,
                         uint32_t* cand_w, float* cand_scores, int64_t* n_failed) {
   EngineScope on(handle_engine(m));
-  if (require_engine()) return -1;
   const char* who = "goctr_recommend_als";
-  GOCTR_CHECK(m && r && als && v && recall_cfg && ucfg, "%s: bad arguments", who);
-  GOCTR_SAME_ENGINE(m, r);
-  GOCTR_SAME_ENGINE(m, als);
-  GOCTR_SAME_ENGINE(m, v);
-  if (check_recsys_dims(who, m, r)) return -1;
+  if (recommend_enter(who, m && r && als && v && recall_cfg && ucfg, m, r, {handle_engine(als), handle_engine(v)})) return -1;
   const ItemcfRecArgs a{users, ts, n_req, targets, *recall_cfg, k, pass_rows, out_items, out_scores, out_count, out_cand_count,
                         out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed};
   if (als_check_recommend(who, als, v, ucfg, a, r->n_users, r->n_items)) return -1;
@@ -806,32 +782,18 @@ int goctr_recommend_blend_als(goctr_model* m, goctr_recsys* r, goctr_itemcf* icf
                               float* cand_scores, uint8_t* cand_src, int64_t* n_failed, int32_t* out_obj, uint32_t* out_pen,
                               int32_t* out_target_place) {
   EngineScope on(handle_engine(m));
-  if (require_engine()) return -1;
   const char* who = "goctr_recommend_blend_als";
-  GOCTR_CHECK(m && r && recall_cfg && als && uv && ucfg, "%s: bad arguments", who);
-  GOCTR_CHECK((v != nullptr) == (cfg != nullptr), "%s: the re-rank takes both the item vectors and the cfg, or neither", who);
-  GOCTR_SAME_ENGINE(m, r);
-  GOCTR_SAME_ENGINE(m, icf);
-  GOCTR_SAME_ENGINE(m, pop);
-  GOCTR_SAME_ENGINE(m, als);
-  GOCTR_SAME_ENGINE(m, uv);
-  GOCTR_SAME_ENGINE(m, v);
-  if (check_recsys_dims(who, m, r)) return -1;
-  GOCTR_CHECK(n_als >= 1 && n_als <= 1024, "%s: n_als = %d is outside 1 .. 1024", who, n_als);
-  if (uservec_check_cfg(ucfg, who) || als_check_vectors(who, als, uv, r->n_items)) return -1;
-  if (v) {
-    if (mmr_check_cfg(v, cfg, who)) return -1;
-    GOCTR_CHECK(v->n_items == r->n_items, "%s: the item vectors cover %lld items, the recsys %lld", who, (long long)v->n_items,
-                (long long)r->n_items);
-  }
-  const ItemcfRecArgs a{users, ts, n_req, targets, *recall_cfg, v ? cfg->k : k, pass_rows, out_items, out_scores, out_count,
-                        out_cand_count, out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed, out_src, cand_src};
+  if (recommend_enter(who, m && r && recall_cfg && als && uv && ucfg, m, r,
+                      {handle_engine(icf), handle_engine(pop), handle_engine(als), handle_engine(uv), handle_engine(v)},
+                      (v != nullptr) == (cfg != nullptr))) return -1;
   BlendArgs b{icf, pop, nullptr, n_als, quota_pop};
   b.uv = uv; b.ucfg = *ucfg; b.als = als;
-  if (blend_check_recommend(who, b, a, r->n_users, r->n_items)) return -1;
-  if (!v) return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return blend_recommend_run(sc, who, b, a); });
-  const RerankStage rr{v, *cfg, out_obj, out_pen, out_target_place};
-  return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return blend_recommend_run(sc, who, b, a, &rr); });
+  const auto check_x = [&] { return uservec_check_cfg(ucfg, who) || als_check_vectors(who, als, uv, r->n_items) ? -1 : 0; };
+  return recommend_blend_x(who, m, r, b, "n_als", check_x, v, cfg,
+                           ItemcfRecArgs{users, ts, n_req, targets, *recall_cfg, k, pass_rows, out_items, out_scores, out_count,
+                                         out_cand_count, out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed,
+                                         out_src, cand_src},
+                           out_obj, out_pen, out_target_place);
 }
 
 // model.Predict's own convention (model/model.go:242-352): `rows` dense TrainSample rows in HOST memory -> y_out [rows].

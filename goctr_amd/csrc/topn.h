@@ -1,6 +1,7 @@
 // topn.h -- what goctr_recommend_topn's two halves share: serve.hip has the entry and (with_scorer) the serving slot, the locks and
 // the scoring path ("score N keys at these device pointers"), topn.hip the key generator, the seen test, the selection and the driver.
 // The order rule and the LDS candidate list (order_key, sel_append, sel_sort_trim) are lds_lists.h's, which this header brings along.
+// The recall-then-rank entries borrow the same TopnScorer; what they share among themselves is recall.h's.
 #pragma once
 #include <functional>
 

@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <climits>
 
+#include "host_stage.h"
 #include "topn.h"
 
 namespace goctr {
@@ -261,20 +262,21 @@ int topn_seen_launch(const long long* off, const int32_t* seq_items, const long 
 }
 
 int topn_check_args(const TopnArgs& a, int64_t n_users) {
-  GOCTR_CHECK(a.users && a.out_items && a.out_scores && a.out_count, "goctr_recommend_topn: bad arguments");
-  GOCTR_CHECK(a.n_users_req > 0 && a.n_pool > 0, "goctr_recommend_topn: n_users_req (%lld) and n_pool (%lld) must be positive",
+  const char* who = "goctr_recommend_topn";
+  GOCTR_CHECK(a.users && a.out_items && a.out_scores && a.out_count, "%s: bad arguments", who);
+  GOCTR_CHECK(a.n_users_req > 0 && a.n_pool > 0, "%s: n_users_req (%lld) and n_pool (%lld) must be positive", who,
               (long long)a.n_users_req, (long long)a.n_pool);
   GOCTR_CHECK(a.n_pool < ((int64_t)1 << 31) && a.n_users_req <= ((int64_t)1 << 24) &&
               a.n_users_req * a.n_pool < ((int64_t)1 << 40),
-              "goctr_recommend_topn: %lld request rows (at most 2^24) x %lld pool positions (below 2^31) is not below 2^40 rows",
+              "%s: %lld request rows (at most 2^24) x %lld pool positions (below 2^31) is not below 2^40 rows", who,
               (long long)a.n_users_req, (long long)a.n_pool);
-  GOCTR_CHECK(a.cfg.k >= 1 && a.cfg.k <= 256, "goctr_recommend_topn: k = %d is outside 1 .. 256", a.cfg.k);
+  GOCTR_CHECK(a.cfg.k >= 1 && a.cfg.k <= 256, "%s: k = %d is outside 1 .. 256", who, a.cfg.k);
   GOCTR_CHECK(a.cfg.exclude >= GOCTR_TOPN_KEEP_SEEN && a.cfg.exclude <= GOCTR_TOPN_DROP_SEEN_BEFORE,
-              "goctr_recommend_topn: exclude = %d is no GOCTR_TOPN_* mode", a.cfg.exclude);
+              "%s: exclude = %d is no GOCTR_TOPN_* mode", who, a.cfg.exclude);
   GOCTR_CHECK(a.cfg.pass_rows == 0 || (a.cfg.pass_rows >= 16 && a.cfg.pass_rows <= TOPN_DEFAULT_PASS_ROWS),
-              "goctr_recommend_topn: pass_rows = %lld is neither 0 nor in 16 .. 65536", (long long)a.cfg.pass_rows);
+              "%s: pass_rows = %lld is neither 0 nor in 16 .. 65536", who, (long long)a.cfg.pass_rows);
   for (int64_t q = 0; q < a.n_users_req; ++q)
-    GOCTR_CHECK(a.users[q] >= 0 && a.users[q] < n_users, "goctr_recommend_topn: request row %lld: user %d is outside [0, %lld)",
+    GOCTR_CHECK(a.users[q] >= 0 && a.users[q] < n_users, "%s: request row %lld: user %d is outside [0, %lld)", who,
                 (long long)q, a.users[q], (long long)n_users);
   return 0;
 }
@@ -282,8 +284,9 @@ int topn_check_args(const TopnArgs& a, int64_t n_users) {
 int topn_run(const TopnScorer& sc, const TopnArgs& a) {
   const int64_t nq = a.n_users_req, np = a.n_pool;
   const int k = a.cfg.k;
+  const char* who = "goctr_recommend_topn";
   const int64_t P = a.cfg.pass_rows ? a.cfg.pass_rows : TOPN_DEFAULT_PASS_ROWS;
-  GOCTR_CHECK(P <= sc.max_rows, "goctr_recommend_topn: the serving slot holds %lld rows, the pass needs %lld",
+  GOCTR_CHECK(P <= sc.max_rows, "%s: the serving slot holds %lld rows, the pass needs %lld", who,
               (long long)sc.max_rows, (long long)P);
   hipStream_t st = sc.stream;
   const bool seen_test = a.cfg.exclude != GOCTR_TOPN_KEEP_SEEN && sc.ub_off != nullptr;
@@ -291,17 +294,13 @@ int topn_run(const TopnScorer& sc, const TopnArgs& a) {
   const int64_t W = (sc.n_items + 31) / 32;
   const int64_t group_rows = seen_test ? std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(TOPN_BITMAP_BYTES / ((size_t)W * 4)))) : nq;
 
+  HostStage out(st);                                      // (in front of the buffers and the drain: freed once the stream is idle)
   DevBuf<int32_t> d_users, d_pool, d_targets, o_items, o_count, r_count;
   DevBuf<long long> d_ts, d_tpos, o_rank;
   DevBuf<unsigned long long> r_key, d_rank, d_nfailed;
   DevBuf<unsigned> r_raw, o_scores, d_bitmap;
   DevBuf<unsigned char> d_flags;
   DevBuf<unsigned long long> p_key; DevBuf<unsigned> p_raw; DevBuf<int> p_count;   // chunk mode's partial lists
-  // the n_users_req * k results are staged on the host so that a failing copy leaves the caller's arrays as they were
-  std::vector<int32_t> h_items, h_count;
-  std::vector<unsigned> h_scores;
-  std::vector<long long> h_rank;
-  unsigned long long h_nfailed = 0;
   StreamDrain drain{st};                                  // (declared behind the buffers: runs before they are released)
   if (d_users.alloc(nq, false) || d_ts.alloc(nq, false) || r_key.alloc((size_t)nq * k, false) || r_raw.alloc((size_t)nq * k, false) ||
       r_count.alloc(nq, false) || d_rank.alloc(nq, false) || d_nfailed.alloc(1, false) || o_items.alloc((size_t)nq * k, false) ||
@@ -382,18 +381,13 @@ int topn_run(const TopnScorer& sc, const TopnArgs& a) {
                      pool, a.targets ? d_targets.p : (const int32_t*)nullptr, a.targets ? d_tpos.p : (const long long*)nullptr,
                      (long long)nq, k, (long long)sc.n_items, o_items.p, o_scores.p, o_count.p, o_rank.p);
   GOCTR_HIP(hipGetLastError());
-  h_items.resize((size_t)nq * k); h_count.resize(nq); h_scores.resize((size_t)nq * k); h_rank.resize(nq);
-  GOCTR_HIP(hipMemcpyAsync(h_items.data(), o_items.p, sizeof(int32_t) * h_items.size(), hipMemcpyDeviceToHost, st));
-  GOCTR_HIP(hipMemcpyAsync(h_scores.data(), o_scores.p, sizeof(unsigned) * h_scores.size(), hipMemcpyDeviceToHost, st));
-  GOCTR_HIP(hipMemcpyAsync(h_count.data(), o_count.p, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, st));
-  GOCTR_HIP(hipMemcpyAsync(h_rank.data(), o_rank.p, sizeof(long long) * (size_t)nq, hipMemcpyDeviceToHost, st));
-  GOCTR_HIP(hipMemcpyAsync(&h_nfailed, d_nfailed.p, sizeof h_nfailed, hipMemcpyDeviceToHost, st));
+  // the n_users_req * k results: all of them reach the caller's arrays, or none
+  const size_t rows = (size_t)nq, nk = rows * (size_t)k;
+  if (out.add(a.out_items, o_items.p, sizeof(int32_t) * nk) || out.add(a.out_scores, o_scores.p, sizeof(float) * nk) ||
+      out.add(a.out_count, o_count.p, sizeof(int32_t) * rows) || out.add(a.out_target_rank, o_rank.p, sizeof(int64_t) * rows) ||
+      out.add(a.n_failed, d_nfailed.p, sizeof(int64_t))) return -1;
   GOCTR_HIP(hipStreamSynchronize(st));
-  memcpy(a.out_items, h_items.data(), sizeof(int32_t) * h_items.size());
-  memcpy(a.out_scores, h_scores.data(), sizeof(unsigned) * h_scores.size());
-  memcpy(a.out_count, h_count.data(), sizeof(int32_t) * (size_t)nq);
-  if (a.out_target_rank) memcpy(a.out_target_rank, h_rank.data(), sizeof(long long) * (size_t)nq);
-  if (a.n_failed) *a.n_failed = (int64_t)h_nfailed;
+  out.commit();
   return 0;
 }
 

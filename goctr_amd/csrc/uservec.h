@@ -1,8 +1,8 @@
 // uservec.h -- what goctr_uservec_recall's launches (uservec.hip) lend to the serving entries: goctr_recommend_uservec runs them as
-// the recall stage of itemcf.h's recall_rank_run, and goctr_recommend_blend_uservec (popular.hip's driver) has them write the list
+// the recall stage of recall.h's recall_rank_run, and goctr_recommend_blend_uservec (popular.hip's driver) has them write the list
 // the blend's part X reads.  include/goctr.h states the semantics ("User-vector recall"); tests/uservec_ref.py restates them.
 #pragma once
-#include "itemcf.h"
+#include "recall.h"
 
 namespace goctr {
 
@@ -28,30 +28,27 @@ struct UvPlanes { const signed char* hi; const signed char* lo; const int32_t* r
 
 // uservec_launch's first half -- sizes ws.p_hi / p_lo for nq rows, zeroes the pad rows and pools every row's history into them.
 // o_p [nq, D] and o_s [nq] may be null
-int uservec_pool_launch(const UvPlanes& pl, const long long* off, const int32_t* seq_items, const long long* seq_ts,
-                        const int32_t* users, const long long* ts, int64_t nq, int history, int16_t* o_p, unsigned long long* o_s,
-                        UvScratch& ws, hipStream_t st);
+int uservec_pool_launch(const UvPlanes& pl, const CacheSeq& seq, const int32_t* users, const long long* ts, int64_t nq, int history,
+                        int16_t* o_p, unsigned long long* o_s, UvScratch& ws, hipStream_t st);
 
 // uv_merge_kernel over g_rows rows: row r's n_chunks descending lists of n_cand keys at lists + r * n_chunks * n_cand (0 = unused)
-// into the outputs of request row q0 + r
+// into request row q0 + r of `out`, whose rows are `stride` slots apart
 int uservec_merge_launch(const unsigned long long* lists, int n_chunks, int n_cand, long long q0, int g_rows, const int32_t* targets,
-                         int stride, int32_t* o_items, unsigned int* o_w, int32_t* o_count, int32_t* o_tpos, hipStream_t st);
+                         const RecallRows& out, int stride, hipStream_t st);
 
 // uservec_launch's second half -- seen, scan and merge over the nq request planes given, [nq + UV_PAD_ROWS, Dp] laid out like the
 // item planes with the pad rows zero: what the multi-interest recall (uservec_multi.hip) runs over its n_req x max_interests
 // virtual rows.  A zero plane row comes back empty
-int uservec_scan_planes(const goctr_itemvec* v, const long long* off, const int32_t* seq_items, const long long* seq_ts,
-                        const UvCols& in, int64_t nq, const goctr_recall_cfg& cfg, const goctr_uservec_cfg& ucfg,
-                        const signed char* p_hi, const signed char* p_lo, int stride, int32_t* o_items, unsigned int* o_w,
-                        int32_t* o_count, int32_t* o_tpos, UvScratch& ws, hipStream_t st);
+int uservec_scan_planes(const goctr_itemvec* v, const CacheSeq& seq, const UvCols& in, int64_t nq, const goctr_recall_cfg& cfg,
+                        const goctr_uservec_cfg& ucfg, const signed char* p_hi, const signed char* p_lo, const RecallRows& out,
+                        int stride, UvScratch& ws, hipStream_t st);
 
-// pool, then uservec_scan_planes, over nq rows on `st`: row q's first cfg.n_cand slots at q * stride (stride >= cfg.n_cand) of o_items /
-// o_w, o_count[q], o_tpos[q].  o_p [nq, D] and o_s [nq] may be null.  The cache arrays may be null together (no cache: every row
-// comes back empty).  Waits for nothing
-int uservec_launch(const goctr_itemvec* v, const long long* off, const int32_t* seq_items, const long long* seq_ts,
-                   const RecallInputs& in, bool has_targets, int64_t nq, const goctr_recall_cfg& cfg, const goctr_uservec_cfg& ucfg,
-                   int stride, int32_t* o_items, unsigned int* o_w, int32_t* o_count, int32_t* o_tpos, int16_t* o_p,
-                   unsigned long long* o_s, UvScratch& ws, hipStream_t st);
+// the request vectors a call may return beside the rows: p [nq, D] and s [nq], the pooled vectors' squared lengths; each may be null
+struct UvVecOut { int16_t* p; unsigned long long* s; };
+
+// pool, then uservec_scan_planes, over r.nq rows on `st`.  Waits for nothing
+int uservec_launch(const goctr_itemvec* v, const RecallCall& r, const goctr_uservec_cfg& ucfg, const RecallRows& out, const UvVecOut& vec,
+                   UvScratch& ws, hipStream_t st);
 
 // goctr_recommend_uservec's refusals that need no slot, and the whole call over a prepared slot
 int uservec_check_recommend(const goctr_itemvec* v, const goctr_uservec_cfg* ucfg, const ItemcfRecArgs& a, int64_t n_users,

@@ -291,19 +291,16 @@ int uservec_check_cfg(const goctr_uservec_cfg* ucfg, const char* who) {
   return 0;
 }
 
-int uservec_launch(const goctr_itemvec* v, const long long* off, const int32_t* seq_items, const long long* seq_ts,
-                   const RecallInputs& in, bool has_targets, int64_t nq, const goctr_recall_cfg& cfg, const goctr_uservec_cfg& ucfg,
-                   int stride, int32_t* o_items, unsigned int* o_w, int32_t* o_count, int32_t* o_tpos, int16_t* o_p,
-                   unsigned long long* o_s, UvScratch& ws, hipStream_t st) {
-  if (uservec_pool_launch(UvPlanes{v->hi.p, v->lo.p, nullptr, v->n_items, v->D, v->Dp}, off, seq_items, seq_ts, in.users.p, in.ts.p,
-                          nq, cfg.history, o_p, o_s, ws, st)) return -1;
-  return uservec_scan_planes(v, off, seq_items, seq_ts, UvCols{in.users.p, in.ts.p, has_targets ? in.targets.p : nullptr}, nq, cfg, ucfg,
-                             ws.p_hi.p, ws.p_lo.p, stride, o_items, o_w, o_count, o_tpos, ws, st);
+int uservec_launch(const goctr_itemvec* v, const RecallCall& r, const goctr_uservec_cfg& ucfg, const RecallRows& out, const UvVecOut& vec,
+                   UvScratch& ws, hipStream_t st) {
+  if (uservec_pool_launch(UvPlanes{v->hi.p, v->lo.p, nullptr, v->n_items, v->D, v->Dp}, r.seq, r.in.users.p, r.in.ts.p, r.nq,
+                          r.cfg.history, vec.p, vec.s, ws, st)) return -1;
+  return uservec_scan_planes(v, r.seq, UvCols{r.in.users.p, r.in.ts.p, r.targets()}, r.nq, r.cfg, ucfg, ws.p_hi.p, ws.p_lo.p, out,
+                             r.stride, ws, st);
 }
 
-int uservec_pool_launch(const UvPlanes& pl, const long long* off, const int32_t* seq_items, const long long* seq_ts,
-                        const int32_t* users, const long long* ts, int64_t nq, int history, int16_t* o_p, unsigned long long* o_s,
-                        UvScratch& ws, hipStream_t st) {
+int uservec_pool_launch(const UvPlanes& pl, const CacheSeq& seq, const int32_t* users, const long long* ts, int64_t nq, int history,
+                        int16_t* o_p, unsigned long long* o_s, UvScratch& ws, hipStream_t st) {
   const int Dp = pl.Dp;
   // the request planes
   const size_t plane = ((size_t)nq + UV_PAD_ROWS) * Dp;
@@ -311,7 +308,7 @@ int uservec_pool_launch(const UvPlanes& pl, const long long* off, const int32_t*
   GOCTR_HIP(hipMemsetAsync(ws.p_hi.p + (size_t)nq * Dp, 0, (size_t)UV_PAD_ROWS * Dp, st));
   GOCTR_HIP(hipMemsetAsync(ws.p_lo.p + (size_t)nq * Dp, 0, (size_t)UV_PAD_ROWS * Dp, st));
   PoolArgs p{};
-  p.off = off; p.seq_items = seq_items; p.seq_ts = seq_ts; p.n_items = pl.n_items; p.users = users; p.ts = ts;
+  p.off = seq.off; p.seq_items = seq.items; p.seq_ts = seq.ts; p.n_items = pl.n_items; p.users = users; p.ts = ts;
   p.H = history; p.D = pl.D; p.Dp = Dp; p.hi = pl.hi; p.lo = pl.lo; p.row_of = pl.row_of; p.p_hi = ws.p_hi.p; p.p_lo = ws.p_lo.p;
   p.out_p = o_p; p.out_s = o_s;
   hipLaunchKernelGGL(uv_pool_kernel, dim3((unsigned)nq), dim3(UV_THREADS), 0, st, p);
@@ -320,22 +317,21 @@ int uservec_pool_launch(const UvPlanes& pl, const long long* off, const int32_t*
 }
 
 int uservec_merge_launch(const unsigned long long* lists, int n_chunks, int n_cand, long long q0, int g_rows, const int32_t* targets,
-                         int stride, int32_t* o_items, unsigned int* o_w, int32_t* o_count, int32_t* o_tpos, hipStream_t st) {
+                         const RecallRows& out, int stride, hipStream_t st) {
   MergeArgs m{};
   m.lists = lists; m.n_chunks = n_chunks; m.n_cand = n_cand; m.q0 = q0; m.targets = targets;
-  m.stride = stride; m.out_items = o_items; m.out_w = o_w; m.out_count = o_count; m.out_tpos = o_tpos;
+  m.stride = stride; m.out_items = out.items; m.out_w = out.w; m.out_count = out.count; m.out_tpos = out.tpos;
   hipLaunchKernelGGL(uv_merge_kernel, dim3((unsigned)g_rows), dim3(SEL_THREADS), 0, st, m);
   GOCTR_HIP(hipGetLastError());
   return 0;
 }
 
-int uservec_scan_planes(const goctr_itemvec* v, const long long* off, const int32_t* seq_items, const long long* seq_ts,
-                        const UvCols& in, int64_t nq, const goctr_recall_cfg& cfg, const goctr_uservec_cfg& ucfg,
-                        const signed char* p_hi, const signed char* p_lo, int stride, int32_t* o_items, unsigned int* o_w,
-                        int32_t* o_count, int32_t* o_tpos, UvScratch& ws, hipStream_t st) {
+int uservec_scan_planes(const goctr_itemvec* v, const CacheSeq& seq, const UvCols& in, int64_t nq, const goctr_recall_cfg& cfg,
+                        const goctr_uservec_cfg& ucfg, const signed char* p_hi, const signed char* p_lo, const RecallRows& out,
+                        int stride, UvScratch& ws, hipStream_t st) {
   const int Dp = v->Dp, nc = cfg.n_cand, cap = uv_cap(nc), R = uv_rows(cap, nq);
   const int64_t V = v->n_items;
-  const bool seen = cfg.exclude != GOCTR_TOPN_KEEP_SEEN && off != nullptr;
+  const bool seen = cfg.exclude != GOCTR_TOPN_KEEP_SEEN && seq.off != nullptr;
   const int64_t words = cdiv(V, 32);
   // the scratch budget decides the rows of a group; the chunks follow from the row tiles the first group brings, so that a
   // single request row still fills the chip
@@ -366,7 +362,7 @@ int uservec_scan_planes(const goctr_itemvec* v, const long long* off, const int3
     const int g_rows = (int)std::min<int64_t>(G, nq - q0);
     if (seen) {
       GOCTR_HIP(hipMemsetAsync(ws.bitmap.p, 0, (size_t)g_rows * words * 4, st));
-      if (topn_seen_launch(off, seq_items, seq_ts, in.users, in.ts, q0, g_rows, V, words, cfg.exclude == GOCTR_TOPN_DROP_SEEN_BEFORE,
+      if (topn_seen_launch(seq.off, seq.items, seq.ts, in.users, in.ts, q0, g_rows, V, words, cfg.exclude == GOCTR_TOPN_DROP_SEEN_BEFORE,
                            ws.bitmap.p, st)) return -1;
     }
     ScanArgs a{};
@@ -380,7 +376,7 @@ int uservec_scan_planes(const goctr_itemvec* v, const long long* off, const int3
     if (R == 32) rc = one_k ? scan_launch(uv_scan_kernel<true, 2>, grid, lds, st, a) : scan_launch(uv_scan_kernel<false, 2>, grid, lds, st, a);
     else rc = one_k ? scan_launch(uv_scan_kernel<true, 1>, grid, lds, st, a) : scan_launch(uv_scan_kernel<false, 1>, grid, lds, st, a);
     if (rc) return -1;
-    if (uservec_merge_launch(ws.lists.p, (int)n_chunks, nc, q0, g_rows, in.targets, stride, o_items, o_w, o_count, o_tpos, st)) return -1;
+    if (uservec_merge_launch(ws.lists.p, (int)n_chunks, nc, q0, g_rows, in.targets, out, stride, st)) return -1;
   }
   return 0;
 }
@@ -398,8 +394,7 @@ int uservec_check_recommend(const goctr_itemvec* v, const goctr_uservec_cfg* ucf
 int uservec_recommend_run(const TopnScorer& sc, const goctr_itemvec* v, const goctr_uservec_cfg& ucfg, const ItemcfRecArgs& a) {
   UvScratch ws;                               // (outlives the run, which drains the stream on every path)
   return recall_rank_run(sc, "goctr_recommend_uservec", a, false, [&](const RecallInputs& in, const RecallRows& o, hipStream_t st) {
-    return uservec_launch(v, sc.ub_off, sc.ub_items, sc.ub_ts, in, a.targets != nullptr, a.n_req, a.rcfg, ucfg, a.rcfg.n_cand,
-                          o.items, o.w, o.count, o.tpos, nullptr, nullptr, ws, st);
+    return uservec_launch(v, recall_call(sc, a, in), ucfg, o, UvVecOut{}, ws, st);
   });
 }
 
@@ -420,40 +415,17 @@ int goctr_uservec_recall(goctr_itemvec* v, goctr_ubcache* c, const int32_t* user
   GOCTR_CHECK(v && c && users && cfg && ucfg && out_items && out_w && out_count, "%s: null argument", who);
   GOCTR_SAME_ENGINE(v, c);
   if (recall_check_cfg(cfg, who) || uservec_check_cfg(ucfg, who) || recall_check_users(users, n_req, c->n_users, who)) return -1;
-  hipStream_t s = engine().stream;
-  const size_t nq = (size_t)n_req, nc = (size_t)cfg->n_cand, D = (size_t)v->D;
-  RecallInputs in;
+  const size_t nq = (size_t)n_req, D = (size_t)v->D;
+  HostStage out(engine().stream);
   UvScratch ws;
-  DevBuf<int32_t> o_items, o_count, o_tpos;
-  DevBuf<unsigned int> o_w;
   DevBuf<int16_t> o_p;
   DevBuf<u64> o_s;
-  // the results are staged on the host so that a failing copy leaves the caller's arrays as they were
-  std::vector<int32_t> h_items(nq * nc), h_count(nq), h_tpos(nq);
-  std::vector<unsigned int> h_w(nq * nc);
-  std::vector<int16_t> h_p(out_p ? nq * D : 0);
-  std::vector<u64> h_s(out_s ? nq : 0);
-  UbRead image(c, s);                         // (behind the buffers: an error return drains the stream before they are freed)
-  if (in.stage(users, ts, targets, n_req, s)) return -1;
-  if (o_items.alloc(nq * nc, false) || o_w.alloc(nq * nc, false) || o_count.alloc(nq, false) || o_tpos.alloc(nq, false) ||
-      (out_p && o_p.alloc(nq * D, false)) || (out_s && o_s.alloc(nq, false))) return -1;
-  if (uservec_launch(v, c->off.p, c->items.p, c->ts.p, in, targets != nullptr, n_req, *cfg, *ucfg, cfg->n_cand, o_items.p, o_w.p,
-                     o_count.p, o_tpos.p, out_p ? o_p.p : nullptr, out_s ? o_s.p : nullptr, ws, s)) return -1;
-  GOCTR_HIP(hipMemcpyAsync(h_items.data(), o_items.p, sizeof(int32_t) * nq * nc, hipMemcpyDeviceToHost, s));
-  GOCTR_HIP(hipMemcpyAsync(h_w.data(), o_w.p, sizeof(unsigned int) * nq * nc, hipMemcpyDeviceToHost, s));
-  GOCTR_HIP(hipMemcpyAsync(h_count.data(), o_count.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));
-  GOCTR_HIP(hipMemcpyAsync(h_tpos.data(), o_tpos.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));
-  if (out_p) GOCTR_HIP(hipMemcpyAsync(h_p.data(), o_p.p, sizeof(int16_t) * nq * D, hipMemcpyDeviceToHost, s));
-  if (out_s) GOCTR_HIP(hipMemcpyAsync(h_s.data(), o_s.p, sizeof(u64) * nq, hipMemcpyDeviceToHost, s));
-  GOCTR_HIP(hipStreamSynchronize(s));
-  image.done();
-  memcpy(out_items, h_items.data(), sizeof(int32_t) * nq * nc);
-  memcpy(out_w, h_w.data(), sizeof(unsigned int) * nq * nc);
-  memcpy(out_count, h_count.data(), sizeof(int32_t) * nq);
-  if (out_target_pos) for (size_t q = 0; q < nq; ++q) out_target_pos[q] = targets ? h_tpos[q] : -1;
-  if (out_p) memcpy(out_p, h_p.data(), sizeof(int16_t) * nq * D);
-  if (out_s) memcpy(out_s, h_s.data(), sizeof(u64) * nq);
-  return 0;
+  return recall_only_run(c, users, ts, targets, n_req, cfg->n_cand, [&](const RecallInputs& in, const RecallRows& o, hipStream_t st) {
+    if ((out_p && o_p.alloc(nq * D, false)) || (out_s && o_s.alloc(nq, false))) return -1;
+    if (uservec_launch(v, RecallCall{CacheSeq(c), in, targets != nullptr, n_req, *cfg, cfg->n_cand}, *ucfg, o, UvVecOut{o_p.p, o_s.p}, ws, st))
+      return -1;
+    return out.add(out_p, o_p.p, sizeof(int16_t) * nq * D) || out.add(out_s, o_s.p, sizeof(u64) * nq) ? -1 : 0;
+  }, out, out_items, out_w, nullptr, out_count, out_target_pos);
 }
 
 }  // extern "C"

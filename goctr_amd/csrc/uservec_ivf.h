@@ -1,5 +1,5 @@
 // uservec_ivf.h -- the handle of goctr_itemvec_index_build and what goctr_uservec_recall_ivf's launches (uservec_ivf.hip) lend to the
-// serving entry: goctr_recommend_uservec_ivf runs them as the recall stage of itemcf.h's recall_rank_run.  include/goctr.h states the
+// serving entry: goctr_recommend_uservec_ivf runs them as the recall stage of recall.h's recall_rank_run.  include/goctr.h states the
 // semantics ("Inverted-file index for user-vector recall"); tests/uservec_ivf_ref.py restates them.
 #pragma once
 #include <vector>
@@ -44,16 +44,14 @@ int uservec_ivf_np(const goctr_itemvec_index* x, const goctr_uservec_ivf_cfg& ic
 // probe, seen, scan and merge over the nq request planes given, [nq + UV_PAD_ROWS, Dp] laid out like the item planes with the pad
 // rows zero, s[q] = 0 marking a row without a vector: shaped like uservec_scan_planes so that a multi-interest or blend variant can
 // run it over its own planes.  Fills ws.probed and ws.scanned as well
-int uservec_ivf_scan_planes(const goctr_itemvec_index* x, const long long* off, const int32_t* seq_items, const long long* seq_ts,
-                            const UvCols& in, int64_t nq, const goctr_recall_cfg& cfg, const goctr_uservec_ivf_cfg& icfg,
-                            const signed char* p_hi, const signed char* p_lo, const unsigned long long* s, int stride,
-                            int32_t* o_items, unsigned int* o_w, int32_t* o_count, int32_t* o_tpos, IvfScratch& ws, hipStream_t st);
+int uservec_ivf_scan_planes(const goctr_itemvec_index* x, const CacheSeq& seq, const UvCols& in, int64_t nq, const goctr_recall_cfg& cfg,
+                            const goctr_uservec_ivf_cfg& icfg, const signed char* p_hi, const signed char* p_lo,
+                            const unsigned long long* s, const RecallRows& out, int stride, IvfScratch& ws, hipStream_t st);
 
-// pool (from the index's own planes), then uservec_ivf_scan_planes, as uservec_launch.  Waits for nothing
-int uservec_ivf_launch(const goctr_itemvec_index* x, const long long* off, const int32_t* seq_items, const long long* seq_ts,
-                       const RecallInputs& in, bool has_targets, int64_t nq, const goctr_recall_cfg& cfg,
-                       const goctr_uservec_ivf_cfg& icfg, int stride, int32_t* o_items, unsigned int* o_w, int32_t* o_count,
-                       int32_t* o_tpos, int16_t* o_p, IvfScratch& ws, hipStream_t st);
+// pool (from the index's own planes), then uservec_ivf_scan_planes, as uservec_launch; o_p [nq, D] may be null (the squared
+// lengths are ws.s).  Waits for nothing
+int uservec_ivf_launch(const goctr_itemvec_index* x, const RecallCall& r, const goctr_uservec_ivf_cfg& icfg, const RecallRows& out,
+                       int16_t* o_p, IvfScratch& ws, hipStream_t st);
 
 // goctr_recommend_uservec_ivf's refusals that need no slot, and the whole call over a prepared slot
 int uservec_ivf_check_recommend(const goctr_itemvec_index* x, const goctr_uservec_ivf_cfg* icfg, const ItemcfRecArgs& a, int64_t n_users,

@@ -474,13 +474,12 @@ int uservec_ivf_np(const goctr_itemvec_index* x, const goctr_uservec_ivf_cfg& ic
   return std::max(1, std::min(icfg.nprobe, x->n_nonempty));
 }
 
-int uservec_ivf_scan_planes(const goctr_itemvec_index* x, const long long* off, const int32_t* seq_items, const long long* seq_ts,
-                            const UvCols& in, int64_t nq, const goctr_recall_cfg& cfg, const goctr_uservec_ivf_cfg& icfg,
-                            const signed char* p_hi, const signed char* p_lo, const unsigned long long* s, int stride,
-                            int32_t* o_items, unsigned int* o_w, int32_t* o_count, int32_t* o_tpos, IvfScratch& ws, hipStream_t st) {
+int uservec_ivf_scan_planes(const goctr_itemvec_index* x, const CacheSeq& seq, const UvCols& in, int64_t nq, const goctr_recall_cfg& cfg,
+                            const goctr_uservec_ivf_cfg& icfg, const signed char* p_hi, const signed char* p_lo,
+                            const unsigned long long* s, const RecallRows& out, int stride, IvfScratch& ws, hipStream_t st) {
   const char* who = "goctr_uservec_recall_ivf";
   const int Dp = x->Dp, nc = cfg.n_cand, np = uservec_ivf_np(x, icfg);
-  const bool any = x->n_nonempty > 0 && off != nullptr;   // (no lists, or no cache and so no vectors: every row comes back empty)
+  const bool any = x->n_nonempty > 0 && seq.off != nullptr;   // (no lists, or no cache and so no vectors: every row comes back empty)
   const int64_t V = x->n_items, words = cdiv(V, 32);
   const bool seen = any && cfg.exclude != GOCTR_TOPN_KEEP_SEEN;
   if (ws.probed.alloc((size_t)nq * np, false) || ws.scanned.alloc((size_t)nq, false)) return -1;
@@ -524,7 +523,7 @@ int uservec_ivf_scan_planes(const goctr_itemvec_index* x, const long long* off, 
     if (any) {
       if (seen) {
         GOCTR_HIP(hipMemsetAsync(ws.uv.bitmap.p, 0, (size_t)g_rows * words * 4, st));
-        if (topn_seen_launch(off, seq_items, seq_ts, in.users, in.ts, q0, g_rows, V, words, cfg.exclude == GOCTR_TOPN_DROP_SEEN_BEFORE,
+        if (topn_seen_launch(seq.off, seq.items, seq.ts, in.users, in.ts, q0, g_rows, V, words, cfg.exclude == GOCTR_TOPN_DROP_SEEN_BEFORE,
                              ws.uv.bitmap.p, st)) return -1;
       }
       const unsigned int P = (unsigned int)((int64_t)g_rows * np);
@@ -555,20 +554,18 @@ int uservec_ivf_scan_planes(const goctr_itemvec_index* x, const long long* off, 
       hipLaunchKernelGGL(ivf_scan_kernel, dim3((unsigned)grid), dim3(IVF_THREADS), ivf_lds(R, cap), st, a);
       GOCTR_HIP(hipGetLastError());
     }
-    if (uservec_merge_launch(ws.uv.lists.p, (int)n_chunks, nc, q0, g_rows, in.targets, stride, o_items, o_w, o_count, o_tpos, st)) return -1;
+    if (uservec_merge_launch(ws.uv.lists.p, (int)n_chunks, nc, q0, g_rows, in.targets, out, stride, st)) return -1;
   }
   return 0;
 }
 
-int uservec_ivf_launch(const goctr_itemvec_index* x, const long long* off, const int32_t* seq_items, const long long* seq_ts,
-                       const RecallInputs& in, bool has_targets, int64_t nq, const goctr_recall_cfg& cfg,
-                       const goctr_uservec_ivf_cfg& icfg, int stride, int32_t* o_items, unsigned int* o_w, int32_t* o_count,
-                       int32_t* o_tpos, int16_t* o_p, IvfScratch& ws, hipStream_t st) {
-  if (ws.s.alloc((size_t)nq, false)) return -1;
-  if (uservec_pool_launch(UvPlanes{x->hi.p, x->lo.p, x->pos.p, x->n_items, x->D, x->Dp}, off, seq_items, seq_ts, in.users.p, in.ts.p,
-                          nq, cfg.history, o_p, ws.s.p, ws.uv, st)) return -1;
-  return uservec_ivf_scan_planes(x, off, seq_items, seq_ts, UvCols{in.users.p, in.ts.p, has_targets ? in.targets.p : nullptr}, nq, cfg,
-                                 icfg, ws.uv.p_hi.p, ws.uv.p_lo.p, ws.s.p, stride, o_items, o_w, o_count, o_tpos, ws, st);
+int uservec_ivf_launch(const goctr_itemvec_index* x, const RecallCall& r, const goctr_uservec_ivf_cfg& icfg, const RecallRows& out,
+                       int16_t* o_p, IvfScratch& ws, hipStream_t st) {
+  if (ws.s.alloc((size_t)r.nq, false)) return -1;
+  if (uservec_pool_launch(UvPlanes{x->hi.p, x->lo.p, x->pos.p, x->n_items, x->D, x->Dp}, r.seq, r.in.users.p, r.in.ts.p, r.nq,
+                          r.cfg.history, o_p, ws.s.p, ws.uv, st)) return -1;
+  return uservec_ivf_scan_planes(x, r.seq, UvCols{r.in.users.p, r.in.ts.p, r.targets()}, r.nq, r.cfg, icfg, ws.uv.p_hi.p, ws.uv.p_lo.p,
+                                 ws.s.p, out, r.stride, ws, st);
 }
 
 int uservec_ivf_check_recommend(const goctr_itemvec_index* x, const goctr_uservec_ivf_cfg* icfg, const ItemcfRecArgs& a, int64_t n_users,
@@ -584,8 +581,7 @@ int uservec_ivf_recommend_run(const TopnScorer& sc, const goctr_itemvec_index* x
                               const ItemcfRecArgs& a) {
   IvfScratch ws;                              // (outlives the run, which drains the stream on every path)
   return recall_rank_run(sc, "goctr_recommend_uservec_ivf", a, false, [&](const RecallInputs& in, const RecallRows& o, hipStream_t st) {
-    return uservec_ivf_launch(x, sc.ub_off, sc.ub_items, sc.ub_ts, in, a.targets != nullptr, a.n_req, a.rcfg, icfg, a.rcfg.n_cand,
-                              o.items, o.w, o.count, o.tpos, nullptr, ws, st);
+    return uservec_ivf_launch(x, recall_call(sc, a, in), icfg, o, nullptr, ws, st);
   });
 }
 
@@ -739,46 +735,25 @@ int goctr_uservec_recall_ivf(goctr_itemvec_index* x, goctr_ubcache* c, const int
   GOCTR_CHECK(x && c && users && cfg && icfg && out_items && out_w && out_count, "%s: null argument", who);
   GOCTR_SAME_ENGINE(x, c);
   if (recall_check_cfg(cfg, who) || uservec_ivf_check_cfg(icfg, who) || recall_check_users(users, n_req, c->n_users, who)) return -1;
-  hipStream_t s = engine().stream;
-  const size_t nq = (size_t)n_req, nc = (size_t)cfg->n_cand, D = (size_t)x->D, np = (size_t)uservec_ivf_np(x, *icfg),
-               npo = (size_t)icfg->nprobe;
-  RecallInputs in;
+  const size_t nq = (size_t)n_req, D = (size_t)x->D, np = (size_t)uservec_ivf_np(x, *icfg), npo = (size_t)icfg->nprobe;
+  HostStage out(engine().stream);
   IvfScratch ws;
-  DevBuf<int32_t> o_items, o_count, o_tpos;
-  DevBuf<unsigned int> o_w;
   DevBuf<int16_t> o_p;
-  // the results are staged on the host so that a failing copy leaves the caller's arrays as they were
-  std::vector<int32_t> h_items(nq * nc), h_count(nq), h_tpos(nq), h_lists(out_lists ? nq * np : 0);
-  std::vector<unsigned int> h_w(nq * nc);
-  std::vector<int16_t> h_p(out_p ? nq * D : 0);
-  std::vector<u64> h_s(out_s ? nq : 0);
-  std::vector<long long> h_scanned(out_scanned ? nq : 0);
-  UbRead image(c, s);                         // (behind the buffers: an error return drains the stream before they are freed)
-  if (in.stage(users, ts, targets, n_req, s)) return -1;
-  if (o_items.alloc(nq * nc, false) || o_w.alloc(nq * nc, false) || o_count.alloc(nq, false) || o_tpos.alloc(nq, false) ||
-      (out_p && o_p.alloc(nq * D, false))) return -1;
-  if (uservec_ivf_launch(x, c->off.p, c->items.p, c->ts.p, in, targets != nullptr, n_req, *cfg, *icfg, cfg->n_cand, o_items.p, o_w.p,
-                         o_count.p, o_tpos.p, out_p ? o_p.p : nullptr, ws, s)) return -1;
-  GOCTR_HIP(hipMemcpyAsync(h_items.data(), o_items.p, sizeof(int32_t) * nq * nc, hipMemcpyDeviceToHost, s));
-  GOCTR_HIP(hipMemcpyAsync(h_w.data(), o_w.p, sizeof(unsigned int) * nq * nc, hipMemcpyDeviceToHost, s));
-  GOCTR_HIP(hipMemcpyAsync(h_count.data(), o_count.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));
-  GOCTR_HIP(hipMemcpyAsync(h_tpos.data(), o_tpos.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));
-  if (out_p) GOCTR_HIP(hipMemcpyAsync(h_p.data(), o_p.p, sizeof(int16_t) * nq * D, hipMemcpyDeviceToHost, s));
-  if (out_s) GOCTR_HIP(hipMemcpyAsync(h_s.data(), ws.s.p, sizeof(u64) * nq, hipMemcpyDeviceToHost, s));
-  if (out_lists) GOCTR_HIP(hipMemcpyAsync(h_lists.data(), ws.probed.p, sizeof(int32_t) * nq * np, hipMemcpyDeviceToHost, s));
-  if (out_scanned) GOCTR_HIP(hipMemcpyAsync(h_scanned.data(), ws.scanned.p, sizeof(long long) * nq, hipMemcpyDeviceToHost, s));
-  GOCTR_HIP(hipStreamSynchronize(s));
-  image.done();
-  memcpy(out_items, h_items.data(), sizeof(int32_t) * nq * nc);
-  memcpy(out_w, h_w.data(), sizeof(unsigned int) * nq * nc);
-  memcpy(out_count, h_count.data(), sizeof(int32_t) * nq);
-  if (out_target_pos) for (size_t q = 0; q < nq; ++q) out_target_pos[q] = targets ? h_tpos[q] : -1;
-  if (out_p) memcpy(out_p, h_p.data(), sizeof(int16_t) * nq * D);
-  if (out_s) memcpy(out_s, h_s.data(), sizeof(u64) * nq);
+  // the probed lists come back as rows of np; the caller's rows hold nprobe.  h_lists stands in for the caller's array on the stage
+  // (commit fills it), and out_lists is written from it, padded, only after the whole call has succeeded
+  std::vector<int32_t> h_lists(out_lists ? nq * np : 0);
+  const int rc = recall_only_run(c, users, ts, targets, n_req, cfg->n_cand, [&](const RecallInputs& in, const RecallRows& o, hipStream_t st) {
+    if (out_p && o_p.alloc(nq * D, false)) return -1;
+    if (uservec_ivf_launch(x, RecallCall{CacheSeq(c), in, targets != nullptr, n_req, *cfg, cfg->n_cand}, *icfg, o, o_p.p, ws, st)) return -1;
+    const bool failed = out.add(out_p, o_p.p, sizeof(int16_t) * nq * D) || out.add(out_s, ws.s.p, sizeof(u64) * nq) ||
+                        out.add(h_lists.data(), ws.probed.p, sizeof(int32_t) * h_lists.size()) ||
+                        out.add(out_scanned, ws.scanned.p, sizeof(int64_t) * nq);
+    return failed ? -1 : 0;
+  }, out, out_items, out_w, nullptr, out_count, out_target_pos);
+  if (rc) return rc;
   if (out_lists)
     for (size_t q = 0; q < nq; ++q)
       for (size_t t = 0; t < npo; ++t) out_lists[q * npo + t] = t < np ? h_lists[q * np + t] : -1;
-  if (out_scanned) for (size_t q = 0; q < nq; ++q) out_scanned[q] = (int64_t)h_scanned[q];
   return 0;
 }
 

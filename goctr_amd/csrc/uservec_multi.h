@@ -1,5 +1,5 @@
 // uservec_multi.h -- what the multi-interest user-vector recall (uservec_multi.hip) lends to goctr_recommend_uservec_multi
-// (serve.hip): the clustering launch, uservec.h's scan over the virtual rows and the mixing launch as the recall stage of itemcf.h's
+// (serve.hip): the clustering launch, uservec.h's scan over the virtual rows and the mixing launch as the recall stage of recall.h's
 // recall_rank_run.  include/goctr.h states the semantics ("Multi-interest user-vector recall"); tests/uservec_multi_ref.py restates
 // them.
 #pragma once
@@ -15,23 +15,18 @@ struct UvMultiScratch {
   DevBuf<unsigned int> v_w;
 };
 
-// the device arrays a call fills, all over the nq request rows: row q's first n_cand slots at q * stride of items / w / owner.
-// n_int [nq] and cnt [nq, max_interests] are always given (the mix reads them); owner, tpos, assign [nq, history], p [nq,
-// max_interests, D] and s [nq, max_interests] may be null.  Without `recall` only n_int, cnt, assign, p and s are written
-struct UvMultiOut {
-  int stride; int32_t* items; unsigned int* w; unsigned char* owner; int32_t* count; int32_t* tpos;
-  int32_t* n_int; int32_t* cnt; signed char* assign; int16_t* p; unsigned long long* s;
-};
+// the device arrays a call fills beside the rows, all over the nq request rows: n_int [nq] and cnt [nq, max_interests] are always
+// given (the mix reads them); assign [nq, history], p [nq, max_interests, D] and s [nq, max_interests] may be null
+struct UvMultiOut { int32_t* n_int; int32_t* cnt; signed char* assign; int16_t* p; unsigned long long* s; };
 
 // the cfg's ranges, and the call's row limit (each sets the error text)
 int uservec_multi_check_cfg(const goctr_uservec_multi_cfg* mcfg, const char* who);
 int uservec_multi_check_rows(int64_t n_req, const char* who);
 
-// clustering, then (with `recall`) scan and mix, over nq rows on `st`.  The cache arrays may be null together (no cache: every row
-// comes back empty).  Waits for nothing
-int uservec_multi_launch(const goctr_itemvec* v, const long long* off, const int32_t* seq_items, const long long* seq_ts,
-                         const RecallInputs& in, bool has_targets, int64_t nq, const goctr_recall_cfg& cfg,
-                         const goctr_uservec_multi_cfg& mcfg, bool recall, const UvMultiOut& o, UvMultiScratch& ws, hipStream_t st);
+// clustering, then (with `recall`) scan and mix, over r.nq rows on `st`: the rows' src column takes the candidates' owners, it and
+// tpos may be null.  Without `recall` only `o` is written and `out` is not looked at.  Waits for nothing
+int uservec_multi_launch(const goctr_itemvec* v, const RecallCall& r, const goctr_uservec_multi_cfg& mcfg, bool recall,
+                         const RecallRows& out, const UvMultiOut& o, UvMultiScratch& ws, hipStream_t st);
 
 // goctr_recommend_uservec_multi's refusals that need no slot, and the whole call over a prepared slot (out_n_int host [n_req] or null)
 int uservec_multi_check_recommend(const goctr_itemvec* v, const goctr_uservec_multi_cfg* mcfg, const ItemcfRecArgs& a, int64_t n_users,

@@ -455,9 +455,10 @@ int uservec_multi_check_rows(int64_t n_req, const char* who) {
   return 0;
 }
 
-int uservec_multi_launch(const goctr_itemvec* v, const long long* off, const int32_t* seq_items, const long long* seq_ts,
-                         const RecallInputs& in, bool has_targets, int64_t nq, const goctr_recall_cfg& cfg,
-                         const goctr_uservec_multi_cfg& mcfg, bool recall, const UvMultiOut& o, UvMultiScratch& ws, hipStream_t st) {
+int uservec_multi_launch(const goctr_itemvec* v, const RecallCall& r, const goctr_uservec_multi_cfg& mcfg, bool recall,
+                         const RecallRows& out, const UvMultiOut& o, UvMultiScratch& ws, hipStream_t st) {
+  const goctr_recall_cfg& cfg = r.cfg;
+  const int64_t nq = r.nq;
   const int Dp = v->Dp, D = v->D, K = mcfg.max_interests, nc = cfg.n_cand, H = cfg.history;
   // request rows of a block: the virtual rows' planes, merged lists and columns within the scan's scratch budget
   const int64_t budget = (int64_t)std::max(0, env_int("GOCTR_USERVEC_SCRATCH_MB", 256)) << 20;
@@ -465,7 +466,7 @@ int uservec_multi_launch(const goctr_itemvec* v, const long long* off, const int
   const int64_t B = std::min<int64_t>(nq, std::max<int64_t>(UM_MIN_BLOCK, budget / per_row));
   const size_t BK = (size_t)B * K, plane = (BK + UV_PAD_ROWS) * Dp;
   if (ws.scan.p_hi.alloc(plane, false) || ws.scan.p_lo.alloc(plane, false)) return -1;
-  if (recall && (ws.v_users.alloc(BK, false) || ws.v_ts.alloc(BK, false) || (has_targets && ws.v_targets.alloc(BK, false)) ||
+  if (recall && (ws.v_users.alloc(BK, false) || ws.v_ts.alloc(BK, false) || (r.has_targets && ws.v_targets.alloc(BK, false)) ||
                  ws.v_items.alloc(BK * nc, false) || ws.v_w.alloc(BK * nc, false) || ws.v_count.alloc(BK, false) ||
                  ws.v_tpos.alloc(BK, false))) return -1;
   const bool stage = (size_t)2 * H * Dp <= (size_t)UM_STAGE_BYTES;
@@ -480,25 +481,25 @@ int uservec_multi_launch(const goctr_itemvec* v, const long long* off, const int
     GOCTR_HIP(hipMemsetAsync(ws.scan.p_hi.p + vrows * Dp, 0, (size_t)UV_PAD_ROWS * Dp, st));
     GOCTR_HIP(hipMemsetAsync(ws.scan.p_lo.p + vrows * Dp, 0, (size_t)UV_PAD_ROWS * Dp, st));
     IntArgs a{};
-    a.off = off; a.seq_items = seq_items; a.seq_ts = seq_ts; a.n_items = v->n_items;
-    a.users = in.users.p + b0; a.ts = in.ts.p + b0; a.targets = has_targets ? in.targets.p + b0 : nullptr;
+    a.off = r.seq.off; a.seq_items = r.seq.items; a.seq_ts = r.seq.ts; a.n_items = v->n_items;
+    a.users = r.in.users.p + b0; a.ts = r.in.ts.p + b0; a.targets = r.has_targets ? r.in.targets.p + b0 : nullptr;
     a.H = H; a.D = D; a.Dp = Dp; a.K = K; a.iters = mcfg.iters; a.split_w = (unsigned int)mcfg.split_w; a.stage = stage ? 1 : 0;
     a.hi = v->hi.p; a.lo = v->lo.p; a.valid = v->valid.p; a.p_hi = ws.scan.p_hi.p; a.p_lo = ws.scan.p_lo.p;
-    if (recall) { a.v_users = ws.v_users.p; a.v_ts = ws.v_ts.p; a.v_targets = has_targets ? ws.v_targets.p : nullptr; }
+    if (recall) { a.v_users = ws.v_users.p; a.v_ts = ws.v_ts.p; a.v_targets = r.has_targets ? ws.v_targets.p : nullptr; }
     a.n_int = o.n_int + b0; a.cnt = o.cnt + (size_t)b0 * K;
     a.o_assign = o.assign ? o.assign + (size_t)b0 * H : nullptr;
     a.o_p = o.p ? o.p + (size_t)b0 * K * D : nullptr; a.o_s = o.s ? o.s + (size_t)b0 * K : nullptr;
     hipLaunchKernelGGL(uv_interests_kernel, dim3((unsigned)rows), dim3(UM_THREADS), lds_int, st, a);
     GOCTR_HIP(hipGetLastError());
     if (!recall) continue;
-    if (uservec_scan_planes(v, off, seq_items, seq_ts, UvCols{ws.v_users.p, ws.v_ts.p, a.v_targets}, (int64_t)vrows, cfg, ucfg,
-                            ws.scan.p_hi.p, ws.scan.p_lo.p, nc, ws.v_items.p, ws.v_w.p, ws.v_count.p, ws.v_tpos.p, ws.scan, st)) return -1;
+    if (uservec_scan_planes(v, r.seq, UvCols{ws.v_users.p, ws.v_ts.p, a.v_targets}, (int64_t)vrows, cfg, ucfg, ws.scan.p_hi.p,
+                            ws.scan.p_lo.p, RecallRows{ws.v_items.p, ws.v_w.p, ws.v_count.p, ws.v_tpos.p, nullptr}, nc, ws.scan, st)) return -1;
     MixArgs m{};
     m.v_items = ws.v_items.p; m.v_w = ws.v_w.p; m.v_count = ws.v_count.p; m.n_int = a.n_int; m.cnt = a.cnt; m.targets = a.targets;
-    m.K = K; m.n_cand = nc; m.mix = mcfg.mix; m.stride = o.stride;
-    m.out_items = o.items + (size_t)b0 * o.stride; m.out_w = o.w + (size_t)b0 * o.stride;
-    m.out_owner = o.owner ? o.owner + (size_t)b0 * o.stride : nullptr;
-    m.out_count = o.count + b0; m.out_tpos = o.tpos ? o.tpos + b0 : nullptr;
+    m.K = K; m.n_cand = nc; m.mix = mcfg.mix; m.stride = r.stride;
+    m.out_items = out.items + (size_t)b0 * r.stride; m.out_w = out.w + (size_t)b0 * r.stride;
+    m.out_owner = out.src ? out.src + (size_t)b0 * r.stride : nullptr;
+    m.out_count = out.count + b0; m.out_tpos = out.tpos ? out.tpos + b0 : nullptr;
     hipLaunchKernelGGL(uv_mix_kernel, dim3((unsigned)rows), dim3(UM_THREADS), lds_mix, st, m);
     GOCTR_HIP(hipGetLastError());
   }
@@ -518,21 +519,18 @@ int uservec_multi_check_recommend(const goctr_itemvec* v, const goctr_uservec_mu
 
 int uservec_multi_recommend_run(const TopnScorer& sc, const goctr_itemvec* v, const goctr_uservec_multi_cfg& mcfg, const ItemcfRecArgs& a,
                                 int32_t* out_n_int) {
-  UvMultiScratch ws;                          // (outlives the run, which drains the stream on every path)
+  HostStage n_int(sc.stream);                 // (all of these outlive the run, which drains the stream on every path)
+  UvMultiScratch ws;
   DevBuf<int32_t> d_nint, d_cnt;
-  std::vector<int32_t> h_nint(out_n_int ? (size_t)a.n_req : 0);
   if (d_nint.alloc((size_t)a.n_req, false) || d_cnt.alloc((size_t)a.n_req * mcfg.max_interests, false)) return -1;
   const int rc = recall_rank_run(sc, "goctr_recommend_uservec_multi", a, a.cand_src != nullptr,
                                  [&](const RecallInputs& in, const RecallRows& o, hipStream_t st) {
-    UvMultiOut mo{};
-    mo.stride = a.rcfg.n_cand; mo.items = o.items; mo.w = o.w; mo.owner = o.src; mo.count = o.count; mo.tpos = o.tpos;
-    mo.n_int = d_nint.p; mo.cnt = d_cnt.p;
-    if (uservec_multi_launch(v, sc.ub_off, sc.ub_items, sc.ub_ts, in, a.targets != nullptr, a.n_req, a.rcfg, mcfg, true, mo, ws, st)) return -1;
-    if (out_n_int) GOCTR_HIP(hipMemcpyAsync(h_nint.data(), d_nint.p, sizeof(int32_t) * (size_t)a.n_req, hipMemcpyDeviceToHost, st));
-    return 0;
+    if (uservec_multi_launch(v, recall_call(sc, a, in), mcfg, true, o, UvMultiOut{d_nint.p, d_cnt.p, nullptr, nullptr, nullptr}, ws, st))
+      return -1;
+    return n_int.add(out_n_int, d_nint.p, sizeof(int32_t) * (size_t)a.n_req);
   });
   if (rc) return rc;
-  if (out_n_int) memcpy(out_n_int, h_nint.data(), sizeof(int32_t) * (size_t)a.n_req);   // (the run drained the stream)
+  n_int.commit();
   return 0;
 }
 
@@ -553,61 +551,32 @@ static int uservec_multi_call(const char* who, bool recall, goctr_itemvec* v, go
   if (recall_check_cfg(cfg, who) || uservec_multi_check_cfg(mcfg, who) || recall_check_users(users, n_req, c->n_users, who) ||
       uservec_multi_check_rows(n_req, who)) return -1;
   hipStream_t s = engine().stream;
-  const size_t nq = (size_t)n_req, nc = recall ? (size_t)cfg->n_cand : 0, D = (size_t)v->D, K = (size_t)mcfg->max_interests,
-               H = (size_t)cfg->history;
-  RecallInputs in;
+  const size_t nq = (size_t)n_req, D = (size_t)v->D, K = (size_t)mcfg->max_interests, H = (size_t)cfg->history;
+  HostStage out(s);
   UvMultiScratch ws;
-  DevBuf<int32_t> o_items, o_count, o_tpos, o_nint, o_cnt;
-  DevBuf<unsigned int> o_w;
-  DevBuf<unsigned char> o_own;
+  DevBuf<int32_t> o_nint, o_cnt;
   DevBuf<signed char> o_asg;
   DevBuf<int16_t> o_p;
   DevBuf<u64> o_s;
-  // the results are staged on the host so that a failing copy leaves the caller's arrays as they were
-  std::vector<int32_t> h_items(nq * nc), h_count(recall ? nq : 0), h_tpos(recall ? nq : 0), h_nint(out_n_int ? nq : 0),
-      h_cnt(out_cnt ? nq * K : 0);
-  std::vector<unsigned int> h_w(nq * nc);
-  std::vector<unsigned char> h_own(out_interest ? nq * nc : 0);
-  std::vector<signed char> h_asg(out_assign ? nq * H : 0);
-  std::vector<int16_t> h_p(out_p ? nq * K * D : 0);
-  std::vector<u64> h_s(out_s ? nq * K : 0);
+  const RecallStage stage = [&](const RecallInputs& in, const RecallRows& o, hipStream_t st) {
+    if (o_nint.alloc(nq, false) || o_cnt.alloc(nq * K, false) || (out_assign && o_asg.alloc(nq * H, false)) ||
+        (out_p && o_p.alloc(nq * K * D, false)) || (out_s && o_s.alloc(nq * K, false))) return -1;
+    if (uservec_multi_launch(v, RecallCall{CacheSeq(c), in, targets != nullptr, n_req, *cfg, cfg->n_cand}, *mcfg, recall, o,
+                             UvMultiOut{o_nint.p, o_cnt.p, o_asg.p, o_p.p, o_s.p}, ws, st)) return -1;
+    const bool failed = out.add(out_n_int, o_nint.p, sizeof(int32_t) * nq) || out.add(out_cnt, o_cnt.p, sizeof(int32_t) * nq * K) ||
+                        out.add(out_assign, o_asg.p, nq * H) || out.add(out_p, o_p.p, sizeof(int16_t) * nq * K * D) ||
+                        out.add(out_s, o_s.p, sizeof(u64) * nq * K);
+    return failed ? -1 : 0;
+  };
+  if (recall)
+    return recall_only_run(c, users, ts, targets, n_req, cfg->n_cand, stage, out, out_items, out_w, out_interest, out_count, out_target_pos);
+  // the clustering alone: no candidate rows, the same staging
+  RecallInputs in;
   UbRead image(c, s);                         // (behind the buffers: an error return drains the stream before they are freed)
-  if (in.stage(users, ts, targets, n_req, s)) return -1;
-  if (o_nint.alloc(nq, false) || o_cnt.alloc(nq * K, false) || (out_assign && o_asg.alloc(nq * H, false)) ||
-      (out_p && o_p.alloc(nq * K * D, false)) || (out_s && o_s.alloc(nq * K, false))) return -1;
-  if (recall && (o_items.alloc(nq * nc, false) || o_w.alloc(nq * nc, false) || o_count.alloc(nq, false) || o_tpos.alloc(nq, false) ||
-                 (out_interest && o_own.alloc(nq * nc, false)))) return -1;
-  UvMultiOut mo{};
-  mo.stride = (int)nc; mo.items = o_items.p; mo.w = o_w.p; mo.owner = out_interest ? o_own.p : nullptr; mo.count = o_count.p;
-  mo.tpos = o_tpos.p; mo.n_int = o_nint.p; mo.cnt = o_cnt.p; mo.assign = out_assign ? o_asg.p : nullptr;
-  mo.p = out_p ? o_p.p : nullptr; mo.s = out_s ? o_s.p : nullptr;
-  if (uservec_multi_launch(v, c->off.p, c->items.p, c->ts.p, in, targets != nullptr, n_req, *cfg, *mcfg, recall, mo, ws, s)) return -1;
-  if (recall) {
-    GOCTR_HIP(hipMemcpyAsync(h_items.data(), o_items.p, sizeof(int32_t) * nq * nc, hipMemcpyDeviceToHost, s));
-    GOCTR_HIP(hipMemcpyAsync(h_w.data(), o_w.p, sizeof(unsigned int) * nq * nc, hipMemcpyDeviceToHost, s));
-    GOCTR_HIP(hipMemcpyAsync(h_count.data(), o_count.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));
-    GOCTR_HIP(hipMemcpyAsync(h_tpos.data(), o_tpos.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));
-    if (out_interest) GOCTR_HIP(hipMemcpyAsync(h_own.data(), o_own.p, nq * nc, hipMemcpyDeviceToHost, s));
-  }
-  if (out_n_int) GOCTR_HIP(hipMemcpyAsync(h_nint.data(), o_nint.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));
-  if (out_cnt) GOCTR_HIP(hipMemcpyAsync(h_cnt.data(), o_cnt.p, sizeof(int32_t) * nq * K, hipMemcpyDeviceToHost, s));
-  if (out_assign) GOCTR_HIP(hipMemcpyAsync(h_asg.data(), o_asg.p, nq * H, hipMemcpyDeviceToHost, s));
-  if (out_p) GOCTR_HIP(hipMemcpyAsync(h_p.data(), o_p.p, sizeof(int16_t) * nq * K * D, hipMemcpyDeviceToHost, s));
-  if (out_s) GOCTR_HIP(hipMemcpyAsync(h_s.data(), o_s.p, sizeof(u64) * nq * K, hipMemcpyDeviceToHost, s));
+  if (in.stage(users, ts, nullptr, n_req, s) || stage(in, RecallRows{}, s)) return -1;
   GOCTR_HIP(hipStreamSynchronize(s));
   image.done();
-  if (recall) {
-    memcpy(out_items, h_items.data(), sizeof(int32_t) * nq * nc);
-    memcpy(out_w, h_w.data(), sizeof(unsigned int) * nq * nc);
-    memcpy(out_count, h_count.data(), sizeof(int32_t) * nq);
-    if (out_target_pos) for (size_t q = 0; q < nq; ++q) out_target_pos[q] = targets ? h_tpos[q] : -1;
-    if (out_interest) memcpy(out_interest, h_own.data(), nq * nc);
-  }
-  if (out_n_int) memcpy(out_n_int, h_nint.data(), sizeof(int32_t) * nq);
-  if (out_cnt) memcpy(out_cnt, h_cnt.data(), sizeof(int32_t) * nq * K);
-  if (out_assign) memcpy(out_assign, h_asg.data(), nq * H);
-  if (out_p) memcpy(out_p, h_p.data(), sizeof(int16_t) * nq * K * D);
-  if (out_s) memcpy(out_s, h_s.data(), sizeof(u64) * nq * K);
+  out.commit();
   return 0;
 }
 

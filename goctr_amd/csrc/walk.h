@@ -1,9 +1,9 @@
 // walk.h -- the handle of goctr_walkgraph_build (walk.hip) and what goctr_walk_recall's launch lends to the serving entries:
-// goctr_recommend_walk runs it as the recall stage of itemcf.h's recall_rank_run, and goctr_recommend_blend_walk (popular.hip's
+// goctr_recommend_walk runs it as the recall stage of recall.h's recall_rank_run, and goctr_recommend_blend_walk (popular.hip's
 // driver) has it write the list the blend's part X reads.  include/goctr.h states the semantics ("Random-walk recall");
 // tests/walk_ref.py restates them.
 #pragma once
-#include "itemcf.h"
+#include "recall.h"
 
 // the bipartite user-item graph as two CSRs resident in HBM; immutable after the build, independent of the cache it was built from.
 // A node is {first edge, degree} in ONE 8-byte word (edges < 2^31), so that a walk step fetches both with one load
@@ -21,12 +21,9 @@ namespace goctr {
 // the cfg's ranges (sets the error text)
 int walk_check_cfg(const goctr_walk_cfg* wcfg, const char* who);
 
-// walk_recall_kernel over nq rows on `st`: row q's first cfg.n_cand slots at q * stride (stride >= cfg.n_cand) of o_items / o_w,
-// o_count[q], o_tpos[q] (may be null); o_trace [nq, n_walks * n_steps] may be null.  The cache arrays may be null together (no
-// cache: every row comes back empty).  Waits for nothing
-int walk_launch(const goctr_walkgraph* g, const long long* off, const int32_t* seq_items, const long long* seq_ts,
-                const RecallInputs& in, bool has_targets, int64_t nq, const goctr_recall_cfg& cfg, const goctr_walk_cfg& wcfg,
-                int stride, int32_t* o_items, unsigned int* o_w, int32_t* o_count, int32_t* o_tpos, int32_t* o_trace, hipStream_t st);
+// walk_recall_kernel over r.nq rows on `st`; out.tpos may be null, o_trace [nq, n_walks * n_steps] may be null.  Waits for nothing
+int walk_launch(const goctr_walkgraph* g, const RecallCall& r, const goctr_walk_cfg& wcfg, const RecallRows& out, int32_t* o_trace,
+                hipStream_t st);
 
 // goctr_recommend_walk's refusals that need no slot, and the whole call over a prepared slot
 int walk_check_recommend(const char* who, const goctr_walkgraph* g, const goctr_walk_cfg* wcfg, const ItemcfRecArgs& a,

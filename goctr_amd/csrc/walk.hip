@@ -237,18 +237,17 @@ int walk_check_cfg(const goctr_walk_cfg* w, const char* who) {
   return 0;
 }
 
-int walk_launch(const goctr_walkgraph* g, const long long* off, const int32_t* seq_items, const long long* seq_ts,
-                const RecallInputs& in, bool has_targets, int64_t nq, const goctr_recall_cfg& cfg, const goctr_walk_cfg& wcfg,
-                int stride, int32_t* o_items, unsigned int* o_w, int32_t* o_count, int32_t* o_tpos, int32_t* o_trace, hipStream_t st) {
+int walk_launch(const goctr_walkgraph* g, const RecallCall& r, const goctr_walk_cfg& wcfg, const RecallRows& out, int32_t* o_trace,
+                hipStream_t st) {
   WalkArgs a{};
-  a.off = off; a.seq_items = seq_items; a.seq_ts = seq_ts;
+  a.off = r.seq.off; a.seq_items = r.seq.items; a.seq_ts = r.seq.ts;
   a.n_items = g->n_items;
   a.unode = g->unode.p; a.inode = g->inode.p; a.uitems = g->uitems.p; a.iusers = g->iusers.p;
-  a.users = in.users.p; a.ts = in.ts.p; a.targets = has_targets ? in.targets.p : nullptr;
-  a.H = cfg.history; a.n_cand = cfg.n_cand; a.exclude = cfg.exclude; a.stride = stride;
+  a.users = r.in.users.p; a.ts = r.in.ts.p; a.targets = r.targets();
+  a.H = r.cfg.history; a.n_cand = r.cfg.n_cand; a.exclude = r.cfg.exclude; a.stride = r.stride;
   a.n_walks = wcfg.n_walks; a.n_steps = wcfg.n_steps; a.boost = wcfg.boost; a.min_visits = wcfg.min_visits; a.seed = wcfg.seed;
-  a.out_items = o_items; a.out_w = o_w; a.out_count = o_count; a.out_tpos = o_tpos; a.out_trace = o_trace;
-  hipLaunchKernelGGL(walk_recall_kernel, dim3((unsigned)nq), dim3(SEL_THREADS), 0, st, a);
+  a.out_items = out.items; a.out_w = out.w; a.out_count = out.count; a.out_tpos = out.tpos; a.out_trace = o_trace;
+  hipLaunchKernelGGL(walk_recall_kernel, dim3((unsigned)r.nq), dim3(SEL_THREADS), 0, st, a);
   GOCTR_HIP(hipGetLastError());
   return 0;
 }
@@ -266,8 +265,7 @@ int walk_check_recommend(const char* who, const goctr_walkgraph* g, const goctr_
 
 int walk_recommend_run(const TopnScorer& sc, const goctr_walkgraph* g, const goctr_walk_cfg& wcfg, const ItemcfRecArgs& a) {
   return recall_rank_run(sc, "goctr_recommend_walk", a, false, [&](const RecallInputs& in, const RecallRows& o, hipStream_t st) {
-    return walk_launch(g, sc.ub_off, sc.ub_items, sc.ub_ts, in, a.targets != nullptr, a.n_req, a.rcfg, wcfg, a.rcfg.n_cand, o.items,
-                       o.w, o.count, o.tpos, nullptr, st);
+    return walk_launch(g, recall_call(sc, a, in), wcfg, o, nullptr, st);
   });
 }
 
@@ -383,33 +381,14 @@ int goctr_walk_recall(goctr_walkgraph* g, goctr_ubcache* c, const int32_t* users
   GOCTR_CHECK(g->n_users == c->n_users, "%s: the walk graph has %lld users, the cache %lld", who, (long long)g->n_users,
               (long long)c->n_users);
   if (recall_check_users(users, n_req, c->n_users, who)) return -1;
-  hipStream_t s = engine().stream;
-  const size_t nq = (size_t)n_req, nc = (size_t)cfg->n_cand, nt = (size_t)wcfg->n_walks * (size_t)wcfg->n_steps;
-  RecallInputs in;
-  DevBuf<int32_t> o_items, o_count, o_tpos, o_trace;
-  DevBuf<unsigned int> o_w;
-  // the results are staged on the host so that a failing copy leaves the caller's arrays as they were
-  std::vector<int32_t> h_items(nq * nc), h_count(nq), h_tpos(nq), h_trace(out_trace ? nq * nt : 0);
-  std::vector<unsigned int> h_w(nq * nc);
-  UbRead image(c, s);                         // (behind the buffers: an error return drains the stream before they are freed)
-  if (in.stage(users, ts, targets, n_req, s)) return -1;
-  if (o_items.alloc(nq * nc, false) || o_w.alloc(nq * nc, false) || o_count.alloc(nq, false) || o_tpos.alloc(nq, false)) return -1;
-  if (out_trace && o_trace.alloc(nq * nt, false)) return -1;
-  if (walk_launch(g, c->off.p, c->items.p, c->ts.p, in, targets != nullptr, n_req, *cfg, *wcfg, cfg->n_cand, o_items.p, o_w.p,
-                  o_count.p, o_tpos.p, out_trace ? o_trace.p : nullptr, s)) return -1;
-  GOCTR_HIP(hipMemcpyAsync(h_items.data(), o_items.p, sizeof(int32_t) * nq * nc, hipMemcpyDeviceToHost, s));
-  GOCTR_HIP(hipMemcpyAsync(h_w.data(), o_w.p, sizeof(unsigned int) * nq * nc, hipMemcpyDeviceToHost, s));
-  GOCTR_HIP(hipMemcpyAsync(h_count.data(), o_count.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));
-  GOCTR_HIP(hipMemcpyAsync(h_tpos.data(), o_tpos.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));
-  if (out_trace) GOCTR_HIP(hipMemcpyAsync(h_trace.data(), o_trace.p, sizeof(int32_t) * nq * nt, hipMemcpyDeviceToHost, s));
-  GOCTR_HIP(hipStreamSynchronize(s));
-  image.done();
-  memcpy(out_items, h_items.data(), sizeof(int32_t) * nq * nc);
-  memcpy(out_w, h_w.data(), sizeof(unsigned int) * nq * nc);
-  memcpy(out_count, h_count.data(), sizeof(int32_t) * nq);
-  if (out_target_pos) for (size_t q = 0; q < nq; ++q) out_target_pos[q] = targets ? h_tpos[q] : -1;
-  if (out_trace) memcpy(out_trace, h_trace.data(), sizeof(int32_t) * nq * nt);
-  return 0;
+  const size_t n_trace = (size_t)n_req * (size_t)wcfg->n_walks * (size_t)wcfg->n_steps;
+  HostStage out(engine().stream);
+  DevBuf<int32_t> o_trace;
+  return recall_only_run(c, users, ts, targets, n_req, cfg->n_cand, [&](const RecallInputs& in, const RecallRows& o, hipStream_t st) {
+    if (out_trace && o_trace.alloc(n_trace, false)) return -1;
+    if (walk_launch(g, RecallCall{CacheSeq(c), in, targets != nullptr, n_req, *cfg, cfg->n_cand}, *wcfg, o, o_trace.p, st)) return -1;
+    return out.add(out_trace, o_trace.p, sizeof(int32_t) * n_trace);
+  }, out, out_items, out_w, nullptr, out_count, out_target_pos);
 }
 
 }  // extern "C"
