@@ -273,6 +273,17 @@ class UservecIvfCfg(C.Structure):
     _fields_ = [("min_w", C.c_int32), ("nprobe", C.c_int32), ("chunk_items", C.c_int64), ("reserved", C.c_int32)]
 
 
+class FuseChannel(C.Structure):
+    """goctr_fuse_channel (include/goctr.h)"""
+    _fields_ = [("kind", C.c_int32), ("n_list", C.c_int32), ("weight", C.c_uint32), ("reserve", C.c_int32),
+                ("handle", C.c_void_p), ("handle2", C.c_void_p), ("cfg", C.c_void_p), ("list", C.POINTER(C.c_int32))]
+
+
+class FuseCfg(C.Structure):
+    """goctr_fuse_cfg (include/goctr.h)"""
+    _fields_ = [("mode", C.c_int32), ("rrf_k", C.c_int32)]
+
+
 class ListCfg(C.Structure):
     """goctr_list_cfg (include/goctr.h)"""
     _fields_ = [("k", C.c_int32), ("tail_cnt", C.c_int32)]
@@ -299,6 +310,10 @@ NS_UNIFORM, NS_POPULARITY, NS_POPULARITY_075 = 0, 1, 2      # goctr_negsample_cf
 NS_ALL, NS_NEWEST, NS_ALL_BUT_NEWEST = 0, 1, 2              # goctr_negsample_cfg.which
 CALIB_STEP, CALIB_LINEAR = 0, 1                             # goctr_calib_cfg.interp
 UVMIX_MAX, UVMIX_QUOTA = 0, 1                               # goctr_uservec_multi_cfg.mix
+(FUSE_ITEMCF, FUSE_WALK, FUSE_USERVEC, FUSE_USERVEC_IVF, FUSE_ALS, FUSE_POPULAR,
+ FUSE_LIST) = range(7)                                      # goctr_fuse_channel.kind
+FUSE_RRF, FUSE_ROUND_ROBIN = 0, 1                           # goctr_fuse_cfg.mode
+FUSE_MAX_CHAN, FUSE_MAX_LISTED = 7, 4096                    # n_chan, the sum of n_list
 
 
 # every symbol include/goctr.h declares (tests/test_capi_symbols.py checks the list against the header)
@@ -362,6 +377,7 @@ SYMBOLS = [
     "goctr_uservec_multi_cfg_default", "goctr_uservec_interests", "goctr_uservec_recall_multi", "goctr_recommend_uservec_multi",
     "goctr_ivf_cfg_default", "goctr_itemvec_index_build", "goctr_itemvec_index_destroy", "goctr_itemvec_index_info",
     "goctr_itemvec_index_export", "goctr_uservec_ivf_cfg_default", "goctr_uservec_recall_ivf", "goctr_recommend_uservec_ivf",
+    "goctr_fuse_cfg_default", "goctr_fuse_recall", "goctr_recommend_fused",
 ]
 
 _lib = None
@@ -390,7 +406,7 @@ def load() -> C.CDLL:
                      "goctr_ivf_cfg_default", "goctr_uservec_ivf_cfg_default", "goctr_itemvec_index_destroy",
                      "goctr_calib_cfg_default", "goctr_calibrator_destroy", "goctr_boot_cfg_default",
                      "goctr_walkgraph_cfg_default", "goctr_walk_cfg_default", "goctr_walkgraph_destroy",
-                     "goctr_als_cfg_default", "goctr_als_destroy", "goctr_ease_cfg_default"):
+                     "goctr_als_cfg_default", "goctr_als_destroy", "goctr_ease_cfg_default", "goctr_fuse_cfg_default"):
             getattr(_lib, name).restype = None
         _bm = C.POINTER(BinaryMetrics)
         _lib.goctr_metrics_binary.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, _bm]
@@ -588,6 +604,13 @@ def load() -> C.CDLL:
         _lib.goctr_recommend_uservec_ivf.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32,
                                                      C.POINTER(RecallCfg), _ui, C.c_int32, C.c_int64, _i32, _f32, _i32, _i32, _i32,
                                                      _i64, _i32, _u32, _f32, _i64]
+        _fc, _fcfg = C.POINTER(FuseChannel), C.POINTER(FuseCfg)
+        _lib.goctr_fuse_cfg_default.argtypes = [_fcfg]
+        _lib.goctr_fuse_recall.argtypes = [_fc, C.c_int32, C.c_void_p, _i32, _i64, C.c_int64, C.POINTER(RecallCfg), _fcfg, _i32, _u32,
+                                           _u8, _i32, _i32, _i32, _u64, _i32, _i32, C.POINTER(_i32)]
+        _lib.goctr_recommend_fused.argtypes = [C.c_void_p, C.c_void_p, _fc, C.c_int32, _i32, _i64, C.c_int64, _i32,
+                                               C.POINTER(RecallCfg), _fcfg, C.c_void_p, _mmr, C.c_int32, C.c_int64, _i32, _f32, _i32,
+                                               _u8, _i32, _i32, _i64, _i32, _u32, _f32, _u8, _i64, _i32, _u32, _i32]
         _lib.goctr_list_cfg_default.argtypes = [C.POINTER(ListCfg)]
         _lib.goctr_metrics_lists.argtypes = [C.c_void_p, C.c_void_p, _i32, _i32, C.c_int64, C.c_int64, C.POINTER(ListCfg),
                                              C.POINTER(ListMetrics), C.POINTER(ListRow), _u32, _u32]
@@ -713,6 +736,7 @@ default_popular_cfg = _default(PopularCfg, "goctr_popular_cfg_default")
 default_walkgraph_cfg = _default(WalkGraphCfg, "goctr_walkgraph_cfg_default")
 default_walk_cfg = _default(WalkCfg, "goctr_walk_cfg_default")
 default_als_cfg = _default(AlsCfg, "goctr_als_cfg_default")
+default_fuse_cfg = _default(FuseCfg, "goctr_fuse_cfg_default")
 ALS_USERS, ALS_ITEMS = 0, 1                 # goctr_als_step's sides
 default_ease_cfg = _default(EaseCfg, "goctr_ease_cfg_default")
 EASE_SCALE_GLOBAL, EASE_SCALE_ROW = 0, 1    # goctr_ease_cfg.scale

@@ -1,5 +1,6 @@
 // lds_lists.h -- the device building blocks the recall and list kernels share (topn.hip, itemcf.hip, popular.hip, itemnbr.hip,
-// rerank.hip, uservec.hip, uservec_multi.hip): lists of u64 order keys in LDS, places within a workgroup, a table of items in LDS.
+// rerank.hip, uservec.hip, uservec_multi.hip, fuse.hip): lists of u64 order keys in LDS, places within a workgroup, a table of
+// items in LDS.
 // The bit-exact tests rest on three rules, each kept here once:
 //   - a list is ordered by its keys alone.  Keys of one list are distinct and 0 means "no entry"; the lists are sorted by ONE
 //     descending bitonic network, so no arrival order, tile size or pass size can show;
@@ -36,6 +37,28 @@ __device__ __forceinline__ void lds_sort_desc(u64* key, P* pay, int n, int t0, i
     }
 }
 __device__ __forceinline__ void lds_sort_desc(u64* key, int n, int t0, int nt) { lds_sort_desc<void>(key, nullptr, n, t0, nt); }
+
+// The same network over two-word keys (hi[i], lo[i]), compared hi first, for an order rule that needs more than 64 bits (fuse.hip:
+// a 62-bit sum, then the item).  The pairs of one list are distinct and (0, 0) means "no entry"; everything else is as above
+template <class P>
+__device__ __forceinline__ void lds_sort_desc2(u64* hi, unsigned int* lo, P* pay, int n, int t0, int nt) {
+  for (int size = 2; size <= n; size <<= 1)
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = t0; t < (n >> 1); t += nt) {
+        const int l = 2 * t - (t & (stride - 1)), h = l + stride;
+        const bool desc = (l & size) == 0;
+        const u64 a = hi[l], b = hi[h];
+        const unsigned int al = lo[l], bl = lo[h];
+        const bool a_less = a < b || (a == b && al < bl), a_more = a > b || (a == b && al > bl);
+        if (desc ? a_less : a_more) {
+          hi[l] = b; hi[h] = a;
+          lo[l] = bl; lo[h] = al;
+          if constexpr (!std::is_void<P>::value) { const P pa = pay[l]; pay[l] = pay[h]; pay[h] = pa; }
+        }
+      }
+      __syncthreads();
+    }
+}
 
 // ------------------------------------------------------------- the order rule and the candidate list of a whole workgroup
 constexpr int SEL_THREADS = 1024;               // one position per thread and tile

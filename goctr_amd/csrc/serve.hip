@@ -13,6 +13,7 @@
 #include <shared_mutex>
 
 #include "ctr_model.h"
+#include "fuse.h"
 #include "itemcf.h"
 #include "itemvec.h"
 #include "popular.h"
@@ -794,6 +795,39 @@ int goctr_recommend_blend_als(goctr_model* m, goctr_recsys* r, goctr_itemcf* icf
                                          out_cand_count, out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed,
                                          out_src, cand_src},
                            out_obj, out_pen, out_target_place);
+}
+
+// Recall from up to 7 channels, fuse by rank (fuse.hip has the check, the stage and the kernel), then rank: the blend entries' shape
+// with FuseStage as the recall stage; out_src / cand_src carry the channel masks through the selection unchanged.
+int goctr_recommend_fused(goctr_model* m, goctr_recsys* r, const goctr_fuse_channel* chan, int32_t n_chan, const int32_t* users,
+                          const int64_t* ts, int64_t n_req, const int32_t* targets, const goctr_recall_cfg* recall_cfg,
+                          const goctr_fuse_cfg* fuse_cfg, goctr_itemvec* v, const goctr_mmr_cfg* cfg, int32_t k, int64_t pass_rows,
+                          int32_t* out_items, float* out_scores, int32_t* out_count, uint8_t* out_src, int32_t* out_cand_count,
+                          int32_t* out_target_pos, int64_t* out_target_rank, int32_t* cand_items, uint32_t* cand_w,
+                          float* cand_scores, uint8_t* cand_src, int64_t* n_failed, int32_t* out_obj, uint32_t* out_pen,
+                          int32_t* out_target_place) {
+  EngineScope on(handle_engine(m));
+  const char* who = "goctr_recommend_fused";
+  if (recommend_enter(who, m && r && chan && recall_cfg && fuse_cfg, m, r, {handle_engine(v)}, (v != nullptr) == (cfg != nullptr)))
+    return -1;
+  ItemcfRecArgs a{users, ts, n_req, targets, *recall_cfg, k, pass_rows, out_items, out_scores, out_count, out_cand_count,
+                  out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed, out_src, cand_src};
+  if (v) {
+    if (mmr_check_cfg(v, cfg, who)) return -1;
+    GOCTR_CHECK(v->n_items == r->n_items, "%s: the item vectors cover %lld items, the recsys %lld", who, (long long)v->n_items,
+                (long long)r->n_items);
+    a.k = cfg->k;
+  }
+  if (recall_check_recommend(who, a, r->n_users)) return -1;
+  FuseArgs f{};
+  if (fuse_check(who, chan, n_chan, *recall_cfg, fuse_cfg, r->n_users, r->n_items, m->eng, &f)) return -1;
+  const RerankStage rr{v, v ? *cfg : goctr_mmr_cfg{}, out_obj, out_pen, out_target_place};
+  return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) {
+    FuseStage stage;                          // (recall_rank_run drains the slot's stream on every path before it returns)
+    return recall_rank_run(sc, who, a, true, [&](const RecallInputs& in, const RecallRows& o, hipStream_t st) {
+      return stage.launch(f, recall_call(sc, a, in), o, st);
+    }, v ? &rr : nullptr);
+  });
 }
 
 // model.Predict's own convention (model/model.go:242-352): `rows` dense TrainSample rows in HOST memory -> y_out [rows].

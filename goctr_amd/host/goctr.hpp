@@ -11,6 +11,7 @@
 #include <array>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <random>
 #include <stdexcept>
@@ -1159,6 +1160,110 @@ inline TopN RecommendBlendALSBatch(model::CtrNet& net, RecSys& rs, const ItemCF*
   out.lists = detail::gather_lists(items, scores, count, k);
   return out;
 }
+
+// Up to 7 recall channels for the same request rows, their lists merged by rank (goctr_fuse_recall / goctr_recommend_fused):
+// reciprocal rank fusion or a round robin, a weight and a guaranteed quota (`reserve`) per channel, and per candidate a bit mask of
+// the channels that found it.  The object borrows its handles: they must outlive the calls.  A channel's own cfg is copied
+class Fused {
+ public:
+  static goctr_fuse_cfg DefaultCfg() { goctr_fuse_cfg c; goctr_fuse_cfg_default(&c); return c; }
+  explicit Fused(const goctr_fuse_cfg& cfg = DefaultCfg()) : cfg_(cfg) {}
+  Fused& Add(const ItemCF& icf, int n_list, uint32_t weight = 1, int reserve = 0) {
+    return push(GOCTR_FUSE_ITEMCF, n_list, weight, reserve, icf.handle(), nullptr, nullptr, 0);
+  }
+  Fused& Add(const WalkGraph& g, int n_list, uint32_t weight = 1, int reserve = 0, const goctr_walk_cfg& wcfg = WalkGraph::DefaultWalkCfg()) {
+    return push(GOCTR_FUSE_WALK, n_list, weight, reserve, g.handle(), nullptr, &wcfg, sizeof wcfg);
+  }
+  Fused& Add(const ItemVectors& v, int n_list, uint32_t weight = 1, int reserve = 0, const goctr_uservec_cfg& ucfg = ALS::DefaultScanCfg()) {
+    return push(GOCTR_FUSE_USERVEC, n_list, weight, reserve, v.handle(), nullptr, &ucfg, sizeof ucfg);
+  }
+  Fused& Add(const VectorIndex& x, int n_list, uint32_t weight = 1, int reserve = 0,
+             const goctr_uservec_ivf_cfg& icfg = VectorIndex::DefaultRecallCfg()) {
+    return push(GOCTR_FUSE_USERVEC_IVF, n_list, weight, reserve, x.handle(), nullptr, &icfg, sizeof icfg);
+  }
+  // `als` has been fitted: its own item vectors are what the fold-in is ranked against
+  Fused& Add(const ALS& als, int n_list, uint32_t weight = 1, int reserve = 0, const goctr_uservec_cfg& ucfg = ALS::DefaultScanCfg()) {
+    if (!als.vectors()) throw std::invalid_argument("Fused::Add: the factors have not been fitted");
+    return push(GOCTR_FUSE_ALS, n_list, weight, reserve, als.handle(), als.vectors(), &ucfg, sizeof ucfg);
+  }
+  Fused& Add(const Popular& pop, int n_list, uint32_t weight = 1, int reserve = 0) {
+    return push(GOCTR_FUSE_POPULAR, n_list, weight, reserve, pop.handle(), nullptr, nullptr, 0);
+  }
+  // a list of the caller's: rows [nq, n_list] of dense items, -1 = no entry; copied, one row per request row of the later call
+  Fused& AddList(const std::vector<int32_t>& rows, int n_list, uint32_t weight = 1, int reserve = 0) {
+    lists_.push_back(rows);
+    return push(GOCTR_FUSE_LIST, n_list, weight, reserve, nullptr, nullptr, nullptr, 0);
+  }
+  size_t channels() const { return chan_.size(); }
+
+  // the fused candidates alone: items / w / src [nq, cfg.n_cand] (src: the channel masks, 255 = unused), count [nq]
+  void Recall(goctr_ubcache* cache, const std::vector<int32_t>& users, const std::vector<int64_t>& ts, const goctr_recall_cfg& rcfg,
+              std::vector<int32_t>& items, std::vector<uint32_t>& w, std::vector<uint8_t>& src, std::vector<int32_t>& count) const {
+    if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("Fused::Recall: one timestamp per user");
+    const size_t nq = users.size(), nc = (size_t)std::max(rcfg.n_cand, 1);
+    const std::vector<goctr_fuse_channel> c = bound(nq);
+    items.resize(nq * nc); w.resize(nq * nc); src.resize(nq * nc); count.resize(nq);
+    check(goctr_fuse_recall(c.data(), (int32_t)c.size(), cache, users.data(), ts.empty() ? nullptr : ts.data(), (int64_t)nq, &rcfg, &cfg_,
+                            items.data(), w.data(), src.data(), count.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+  }
+
+  // recall from every channel, fuse, rank with the model; with `rerank` and `mcfg` the diversity re-rank picks the mcfg->k returned.
+  // `masks` (may be null) receives [nq, k] the channel mask of every returned item
+  TopN RecommendBatch(model::CtrNet& net, RecSys& rs, const std::vector<int32_t>& users, int n = 10, const std::vector<int64_t>& ts = {},
+                      const goctr_recall_cfg& rcfg = ItemCF::DefaultRecallCfg(), const ItemVectors* rerank = nullptr,
+                      const goctr_mmr_cfg* mcfg = nullptr, const std::vector<int32_t>& targets = {}, int64_t pass_rows = 0,
+                      std::vector<uint8_t>* masks = nullptr) const {
+    const int64_t nq = (int64_t)users.size();
+    const int k = rerank && mcfg ? mcfg->k : n;
+    if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("Fused::RecommendBatch: one timestamp per user");
+    if (!targets.empty() && targets.size() != users.size()) throw std::invalid_argument("Fused::RecommendBatch: one target per user");
+    if ((rerank == nullptr) != (mcfg == nullptr)) throw std::invalid_argument("Fused::RecommendBatch: the re-rank takes vectors and cfg");
+    if (k < 1) throw std::invalid_argument("Fused::RecommendBatch: n must be positive");
+    const std::vector<goctr_fuse_channel> c = bound((size_t)nq);
+    std::vector<int32_t> items((size_t)nq * k), count((size_t)nq);
+    std::vector<float> scores((size_t)nq * k);
+    if (masks) masks->resize((size_t)nq * k);
+    TopN out;
+    if (!targets.empty()) out.target_rank.resize((size_t)nq);
+    check(goctr_recommend_fused(net.Vm(), rs.handle(), c.data(), (int32_t)c.size(), users.data(), ts.empty() ? nullptr : ts.data(), nq,
+                                targets.empty() ? nullptr : targets.data(), &rcfg, &cfg_, rerank ? rerank->handle() : nullptr, mcfg, k,
+                                pass_rows, items.data(), scores.data(), count.data(), masks ? masks->data() : nullptr, nullptr, nullptr,
+                                targets.empty() ? nullptr : out.target_rank.data(), nullptr, nullptr, nullptr, nullptr, &out.n_failed,
+                                nullptr, nullptr, nullptr));
+    out.lists = detail::gather_lists(items, scores, count, k);
+    return out;
+  }
+
+ private:
+  union AnyCfg { goctr_walk_cfg w; goctr_uservec_cfg u; goctr_uservec_ivf_cfg i; };
+  Fused& push(int32_t kind, int n_list, uint32_t weight, int reserve, const void* h, const void* h2, const void* cfg, size_t cfg_bytes) {
+    if (chan_.size() >= 7) throw std::invalid_argument("Fused::Add: at most 7 channels");
+    AnyCfg a{};
+    if (cfg) memcpy(&a, cfg, cfg_bytes);
+    cfgs_.push_back(a);
+    has_cfg_.push_back(cfg != nullptr);
+    chan_.push_back(goctr_fuse_channel{kind, n_list, weight, reserve, h, h2, nullptr, nullptr});
+    return *this;
+  }
+  // the channels with their cfg and list pointers set (the vectors may have moved since Add), the lists checked against nq rows
+  std::vector<goctr_fuse_channel> bound(size_t nq) const {
+    std::vector<goctr_fuse_channel> c = chan_;
+    size_t l = 0;
+    for (size_t i = 0; i < c.size(); ++i) {
+      if (has_cfg_[i]) c[i].cfg = &cfgs_[i];
+      if (c[i].kind != GOCTR_FUSE_LIST) continue;
+      const std::vector<int32_t>& rows = lists_[l++];
+      if (c[i].n_list < 1 || rows.size() != nq * (size_t)c[i].n_list) throw std::invalid_argument("Fused: a list holds n_list entries per request row");
+      c[i].list = rows.data();
+    }
+    return c;
+  }
+  goctr_fuse_cfg cfg_;
+  std::vector<goctr_fuse_channel> chan_;
+  std::vector<AnyCfg> cfgs_;
+  std::vector<bool> has_cfg_;
+  std::vector<std::vector<int32_t>> lists_;
+};
 
 // List-quality figures of returned lists (goctr_metrics_lists): `items` holds nq rows of k entries, `count` the entries in use
 // per row (empty: every row is full); vec / pop may be null (include/goctr.h says which figures are then 0 or NaN)

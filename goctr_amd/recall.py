@@ -32,6 +32,11 @@ against the whole catalogue, so an item close to many history items but in no si
 ``ItemVectors.build_index`` clusters the valid vectors into an inverted file, and ``VectorIndex.recall_users`` is the same channel
 over the ``nprobe`` lists whose centres lie nearest the request vector instead of over the whole catalogue
 (tests/uservec_ivf_ref.py is the host restatement).  ``recommend.RecommendVectorIndexed`` ranks the result with the model.
+
+``fuse`` asks up to 7 ``Channel``s -- any of the above, a popularity list, a list of the caller's -- for the same request rows and
+merges their lists by rank (reciprocal rank fusion or a round robin), with a weight and a guaranteed quota per channel and a bit
+mask of the channels that found every item (tests/fuse_ref.py is the host restatement).  ``recommend.RecommendFused`` ranks the
+result with the model.
 """
 from __future__ import annotations
 
@@ -63,6 +68,8 @@ _IVF_FIELDS = _fields(capi.IvfCfg)
 _USERVEC_IVF_FIELDS = _fields(capi.UservecIvfCfg)
 _WALKGRAPH_FIELDS = _fields(capi.WalkGraphCfg)
 _WALK_FIELDS = _fields(capi.WalkCfg)
+_FUSE_FIELDS = _fields(capi.FuseCfg)
+FUSE_MODE = {"rrf": capi.FUSE_RRF, "round_robin": capi.FUSE_ROUND_ROBIN}
 
 
 def _as_int(name, v):
@@ -101,6 +108,18 @@ make_ivf_cfg = _make("goctr_ivf_cfg", _IVF_FIELDS, capi.default_ivf_cfg)
 make_uservec_ivf_cfg = _make("goctr_uservec_ivf_cfg", _USERVEC_IVF_FIELDS, capi.default_uservec_ivf_cfg)
 make_walkgraph_cfg = _make("goctr_walkgraph_cfg", _WALKGRAPH_FIELDS, capi.default_walkgraph_cfg)
 make_walk_cfg = _make("goctr_walk_cfg", _WALK_FIELDS, capi.default_walk_cfg)
+
+
+def make_fuse_cfg(**kw) -> capi.FuseCfg:
+    """goctr_fuse_cfg from keywords: mode (an integer, or "rrf" / "round_robin"), rrf_k"""
+    unknown = set(kw) - _FUSE_FIELDS
+    if unknown:
+        raise TypeError(f"goctr_fuse_cfg has no field {sorted(unknown)}")
+    if isinstance(kw.get("mode"), str):
+        if kw["mode"] not in FUSE_MODE:
+            raise ValueError(f"mode = {kw['mode']!r} is none of {sorted(FUSE_MODE)}")
+        kw["mode"] = FUSE_MODE[kw["mode"]]
+    return capi.default_fuse_cfg(**{k: _as_int(k, v) for k, v in kw.items()})
 
 
 _EASE_FIELDS = _fields(capi.EaseCfg)
@@ -698,4 +717,116 @@ def rerank_mmr(vectors: ItemVectors, items, scores, count=None, cfg: capi.MmrCfg
                                             C.c_int64(nq), C.c_int32(nc), C.byref(cfg), _ptr(out["pos"]), _ptr(out["obj"]),
                                             _ptr(out["pen"]), _ptr(out["count"]), C.byref(nf)))
     out["n_failed"] = nf.value
+    return out
+
+
+class Channel:
+    """one goctr_fuse_channel of ``fuse`` / ``recommend.RecommendFused``: a recall channel, how many entries it is asked for per row
+    (``n_list``), its weight under reciprocal rank fusion and how many of its first entries are guaranteed a place (``reserve``).
+    Made by the constructors below, one per kind; it keeps its handles and its cfg alive"""
+
+    def __init__(self, kind, n_list, weight=1, reserve=0, handle=None, handle2=None, cfg=None, entries=None):
+        self.kind, self.n_list = _as_int("kind", kind), _as_int("n_list", n_list)
+        self.weight, self.reserve = _as_int("weight", weight), _as_int("reserve", reserve)
+        self.handle, self.handle2, self.cfg, self.entries = handle, handle2, cfg, entries
+
+    @classmethod
+    def itemcf(cls, icf: ItemCF, n_list, weight=1, reserve=0) -> "Channel":
+        """``ItemCF.recall``'s list"""
+        return cls(capi.FUSE_ITEMCF, n_list, weight, reserve, icf)
+
+    @classmethod
+    def walk(cls, graph: WalkGraph, n_list, weight=1, reserve=0, wcfg: capi.WalkCfg | None = None, **kw) -> "Channel":
+        """``WalkGraph.recall``'s list; ``kw``: goctr_walk_cfg fields"""
+        return cls(capi.FUSE_WALK, n_list, weight, reserve, graph, cfg=_cfg_or_kw(wcfg, kw, make_walk_cfg, "wcfg"))
+
+    @classmethod
+    def uservec(cls, vectors: "ItemVectors", n_list, weight=1, reserve=0, ucfg: capi.UservecCfg | None = None, **kw) -> "Channel":
+        """``ItemVectors.recall_users``'s list; ``kw``: goctr_uservec_cfg fields"""
+        return cls(capi.FUSE_USERVEC, n_list, weight, reserve, vectors, cfg=_cfg_or_kw(ucfg, kw, make_uservec_cfg, "ucfg"))
+
+    @classmethod
+    def uservec_ivf(cls, index: "VectorIndex", n_list, weight=1, reserve=0, icfg: capi.UservecIvfCfg | None = None, **kw) -> "Channel":
+        """``VectorIndex.recall_users``'s list; ``kw``: goctr_uservec_ivf_cfg fields"""
+        return cls(capi.FUSE_USERVEC_IVF, n_list, weight, reserve, index, cfg=_cfg_or_kw(icfg, kw, make_uservec_ivf_cfg, "icfg"))
+
+    @classmethod
+    def als(cls, als: ALS, vectors: "ItemVectors", n_list, weight=1, reserve=0, ucfg: capi.UservecCfg | None = None, **kw) -> "Channel":
+        """``ALS.recall_users``'s list against ``vectors``; ``kw``: goctr_uservec_cfg fields"""
+        return cls(capi.FUSE_ALS, n_list, weight, reserve, als, vectors, _cfg_or_kw(ucfg, kw, make_uservec_cfg, "ucfg"))
+
+    @classmethod
+    def popular(cls, pop: Popular, n_list, weight=1, reserve=0) -> "Channel":
+        """the first ``n_list`` unseen entries of the popularity list"""
+        return cls(capi.FUSE_POPULAR, n_list, weight, reserve, pop)
+
+    @classmethod
+    def rows(cls, rows, weight=1, reserve=0) -> "Channel":
+        """a list of the caller's per request row: ``rows`` int32 [nq, n_list], -1 = no entry"""
+        rows = capi.i32(rows)
+        if rows.ndim != 2:
+            raise ValueError("rows takes one row of candidates per request row: [nq, n_list]")
+        return cls(capi.FUSE_LIST, rows.shape[1], weight, reserve, entries=rows)
+
+
+def fuse_channels(channels, nq, n_cand):
+    """the channels as the C-ABI takes them: (goctr_fuse_channel[n_chan], n_chan).  Every field's range and the two sums are checked
+    here, before the library is reached"""
+    channels = list(channels)
+    if not 1 <= len(channels) <= capi.FUSE_MAX_CHAN:
+        raise ValueError(f"{len(channels)} channels: fuse takes 1 .. {capi.FUSE_MAX_CHAN}")
+    arr = (capi.FuseChannel * len(channels))()
+    for c, (ch, a) in enumerate(zip(channels, arr)):
+        if not isinstance(ch, Channel):
+            raise TypeError(f"channel {c} is no recall.Channel")
+        if not capi.FUSE_ITEMCF <= ch.kind <= capi.FUSE_LIST:
+            raise ValueError(f"channel {c}: kind = {ch.kind} is no capi.FUSE_* kind")
+        if not 1 <= ch.n_list <= 1024:
+            raise ValueError(f"channel {c}: n_list = {ch.n_list} is outside 1 .. 1024")
+        if not 0 <= ch.weight <= 65535:
+            raise ValueError(f"channel {c}: weight = {ch.weight} is outside 0 .. 65535")
+        if not 0 <= ch.reserve <= ch.n_list:
+            raise ValueError(f"channel {c}: reserve = {ch.reserve} is outside 0 .. n_list = {ch.n_list}")
+        if ch.kind == capi.FUSE_LIST and (ch.entries is None or ch.entries.shape != (nq, ch.n_list)):
+            raise ValueError(f"channel {c}: rows takes one row of n_list candidates per request row")
+        a.kind, a.n_list, a.weight, a.reserve = ch.kind, ch.n_list, ch.weight, ch.reserve
+        a.handle = None if ch.handle is None else getattr(ch.handle, "_h", ch.handle)
+        a.handle2 = None if ch.handle2 is None else getattr(ch.handle2, "_h", ch.handle2)
+        a.cfg = None if ch.cfg is None else C.cast(C.pointer(ch.cfg), C.c_void_p)
+        a.list = None if ch.entries is None else capi.ptr(ch.entries, C.c_int32)
+    if sum(ch.n_list for ch in channels) > capi.FUSE_MAX_LISTED:
+        raise ValueError(f"the channels' n_list add up to {sum(ch.n_list for ch in channels)} (limit {capi.FUSE_MAX_LISTED})")
+    if sum(ch.reserve for ch in channels) > n_cand:
+        raise ValueError(f"the channels' reserves add up to {sum(ch.reserve for ch in channels)}, over n_cand = {n_cand}")
+    return arr, len(channels)
+
+
+def check_fuse_cfg(fcfg: capi.FuseCfg) -> capi.FuseCfg:
+    if fcfg.mode not in (capi.FUSE_RRF, capi.FUSE_ROUND_ROBIN):
+        raise ValueError(f"mode = {fcfg.mode} is neither capi.FUSE_RRF nor capi.FUSE_ROUND_ROBIN")
+    if not 1 <= fcfg.rrf_k <= 1024:
+        raise ValueError(f"rrf_k = {fcfg.rrf_k} is outside 1 .. 1024")
+    return fcfg
+
+
+def fuse(channels, ubc, users, ts=None, targets=None, cfg: capi.RecallCfg | None = None, fcfg: capi.FuseCfg | None = None, **kw) -> dict:
+    """goctr_fuse_recall over DENSE user rows of ``ubc``'s image (None: no history, nothing seen): every ``Channel``'s list for the
+    rows, merged by rank.  ``kw``: goctr_recall_cfg fields and goctr_fuse_cfg's (mode -- also "rrf" / "round_robin" --, rrf_k).
+    dict(items int32 [nq, n_cand] (-1 = unused), w uint32 [nq, n_cand], src uint8 [nq, n_cand] (bit c: channel c holds the item; 255 =
+    unused), count int32 [nq], target_pos int32 [nq] when targets are given, s uint64 [nq, n_cand] (the full sums), chan_count int32
+    [nq, n_chan], chan_target_pos int32 [nq, n_chan] (-1 throughout without targets), chan_items: a list of int32 [nq, n_list_c],
+    the channels' own lists)"""
+    cfg, fcfg = _split_kw(cfg, fcfg, kw, _FUSE_FIELDS, make_fuse_cfg)
+    users, ts, targets = request_columns(users, ts, targets)
+    nq = users.size
+    arr, n_chan = fuse_channels(channels, nq, int(cfg.n_cand))
+    check_fuse_cfg(fcfg)
+    out = _recall_buffers(nq, cfg.n_cand, targets, src=True)
+    out.update(s=_unwritten(out["items"].shape, np.uint64), chan_count=_unwritten((nq, n_chan), np.int32),
+               chan_target_pos=_unwritten((nq, n_chan), np.int32),
+               chan_items=[_unwritten((nq, a.n_list), np.int32) for a in arr])
+    lists = (C.POINTER(C.c_int32) * n_chan)(*(_ptr(a) for a in out["chan_items"]))
+    capi.check(capi.load().goctr_fuse_recall(arr, C.c_int32(n_chan), _cache_handle(ubc), *_request_args(users, ts), C.byref(cfg),
+                                             C.byref(fcfg), *_recall_args(out, targets), _ptr(out["s"]), _ptr(out["chan_count"]),
+                                             _ptr(out["chan_target_pos"]), lists))
     return out

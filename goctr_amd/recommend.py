@@ -30,7 +30,7 @@ from . import capi, metrics, sampling
 from .recall import (ALS, EXCLUDE, _USERVEC_FIELDS, _USERVEC_IVF_FIELDS, _USERVEC_MULTI_FIELDS, _WALK_FIELDS, ItemCF, ItemVectors, Popular,
                      WalkGraph, _as_int, _cfg_or_kw, _ptr, _request_args, _split_kw, _unwritten, extra_columns, make_mmr_cfg,
                      make_recall_cfg, make_uservec_cfg, make_uservec_ivf_cfg, make_uservec_multi_cfg, make_walk_cfg, merge,
-                     request_columns)
+                     request_columns, Channel, _FUSE_FIELDS, check_fuse_cfg, fuse_channels, make_fuse_cfg)
 
 # recommend/rcmd.go:19-28
 SampleAssembler = 16
@@ -552,6 +552,7 @@ _OUTPUTS = {
     "goctr_recommend_blend_walk": _BLENDED + ("obj", "pen", "target_place"),
     "goctr_recommend_als": _RANKED,
     "goctr_recommend_blend_als": _BLENDED + ("obj", "pen", "target_place"),
+    "goctr_recommend_fused": _BLENDED + ("obj", "pen", "target_place"),
 }
 # key: (dtype, entries per request row -- "k", "n_cand" or one --, what the call must have for the array to exist)
 _COLUMNS = {
@@ -748,6 +749,25 @@ def blend_als(model: Predictor, icf, pop, factors, users, ts=None, targets=None,
             C.c_int32(_as_int("quota_pop", quota_pop)), vectors._h if vectors is not None else None,
             C.byref(mcfg) if mcfg is not None else None, *_k_pass(k, pass_rows))
     return _ranked_call("goctr_recommend_blend_als", head, users.size, k, cfg.n_cand, targets, validate, mmr=mcfg is not None)
+
+
+def fused(model: Predictor, channels, users, ts=None, targets=None, k=10, vectors=None, pool=64, lambda_q=192, max_per_group=0,
+          pass_rows=0, validate=False, recall_cfg=None, fcfg=None, **recall_kw):
+    """goctr_recommend_fused over DENSE indices: ``itemcf`` with the lists of up to 7 ``channels`` (recall.Channel) fused by rank as the
+    recall stage; with ``vectors`` the MMR selection of ``diverse`` is the last step (pool, lambda_q, max_per_group).  The dict of
+    ``blend``, or of ``diverse``, with src / cand_src holding channel MASKS (bit c: channel c's list holds the item; 255 = unused).
+    ``recall_kw``: goctr_recall_cfg fields and goctr_fuse_cfg's (mode -- also "rrf" / "round_robin" --, rrf_k).  Every channel field
+    and the two sums are checked before the library is reached.  What RecommendFused / RecommendFusedBatch /
+    EvaluateLeaveOneOutFused call."""
+    cfg, fcfg = _split_kw(recall_cfg, fcfg, recall_kw, _FUSE_FIELDS, make_fuse_cfg)
+    users, ts, targets = request_columns(users, ts, targets)
+    arr, n_chan = fuse_channels(channels, users.size, int(cfg.n_cand))
+    check_fuse_cfg(fcfg)
+    mcfg = None if vectors is None else make_mmr_cfg(k=k, pool=pool, lambda_q=lambda_q, max_per_group=max_per_group)
+    head = (*_request_head(model), arr, C.c_int32(n_chan), *_request_args(users, ts), capi.ptr(targets, C.c_int32), C.byref(cfg),
+            C.byref(fcfg), vectors._h if vectors is not None else None, C.byref(mcfg) if mcfg is not None else None,
+            *_k_pass(k, pass_rows))
+    return _ranked_call("goctr_recommend_fused", head, users.size, k, cfg.n_cand, targets, validate, mmr=mcfg is not None)
 
 
 # ---- raw ids in, [[ItemScore]] out: what every Recommend*Batch function does around its device call
@@ -1357,4 +1377,55 @@ def EvaluateLeaveOneOutALS(model: Predictor, factors=None, k=10, sample_kw=None,
     out = _loo_figures(r, targets, model.recSys.item_table.shape[0], k, cfg.n_cand)
     if details:
         out.update(_details(r, users, targets, ts))
+    return out
+
+
+def RecommendFusedBatch(model: Predictor, channels, userIds, n=10, now=None, vectors=None, lambda_q=192, pool=64, max_per_group=0,
+                        **recall_kw):
+    """RecommendFused for several users in one device call: [[ItemScore]] in the order of userIds.  ``now``: one timestamp for all,
+    or one per user.  A ``Channel.rows`` channel takes DENSE item rows, one row per user in the order of userIds."""
+    users, ts = _request_rows(model, userIds, now)
+    return _serve(model, users.size, lambda: fused(model, channels, users, ts, None, n, vectors, pool, lambda_q, max_per_group,
+                                                   **recall_kw))
+
+
+def RecommendFused(model: Predictor, channels, userId: int, n=10, now=None, vectors=None, lambda_q=192, pool=64, max_per_group=0,
+                   **recall_kw):
+    """EXTENSION -- N-channel recall merged by rank, then rank: every ``recall.Channel`` of ``channels`` (ItemCF, random walks, user
+    vectors over the catalogue or an index, ALS fold-in, the popularity list, a list of the caller's; at most 7) proposes its own
+    list for the user, the lists are fused on the device by reciprocal rank fusion (``mode`` "rrf": an item's sum of weight /
+    (rrf_k + place) over the channels that found it) or a round robin, a channel's first ``reserve`` entries are guaranteed a place
+    among the ``n_cand`` fused candidates, the model scores those and the ``n`` best come back.  With ``vectors`` the diversity
+    re-rank of RecommendDiverse is the last step."""
+    return RecommendFusedBatch(model, channels, [userId], n, now, vectors, lambda_q, pool, max_per_group, **recall_kw)[0]
+
+
+def EvaluateLeaveOneOutFused(model: Predictor, channels, k=10, sample_kw=None, details=False, pass_rows=0, **recall_kw):
+    """EvaluateLeaveOneOutRecall's protocol and figures over the FUSED candidates (goctr_recommend_fused), plus what the call's
+    provenance masks say about every channel -- all from the one call, over the users whose held-out item is a row of the item table:
+        chan_recall[c]   the share of users whose target is a fused candidate that channel c's list holds
+        chan_unique[c]   ... that channel c's list holds and no other channel's
+        chan_share[c]    the share of RETURNED items (the best k of every row) that carry channel c's bit
+    A target a channel found but the cut dropped from the fused list counts for nobody: with n_cand at or above the sum of the
+    channels' n_list nothing is cut.  The channels' handles should be built without the held-out entries for an honest figure; that
+    is the caller's choice.  Returns EvaluateLeaveOneOutRecall's dict plus the three lists; details=True adds the columns and the
+    target's mask per row (``target_mask``, 0 = not recalled)."""
+    users, targets, ts = _held_out_rows(model, sample_kw)
+    recall_kw.setdefault("exclude", "before")
+    cfg, fcfg = _split_kw(None, None, recall_kw, _FUSE_FIELDS, make_fuse_cfg)
+    channels = list(channels)
+    r = fused(model, channels, users, ts, targets, k, pass_rows=pass_rows, validate=True, recall_cfg=cfg, fcfg=fcfg)
+    n_items = model.recSys.item_table.shape[0]
+    out = _loo_figures(r, targets, n_items, k, cfg.n_cand)
+    ok = (targets >= 0) & (targets < n_items)
+    pos = r["target_pos"].astype(np.int64)
+    mask = np.where(pos >= 0, r["cand_src"][np.arange(users.size), np.maximum(pos, 0)], 0).astype(np.int64)
+    listed = np.arange(r["src"].shape[1])[None, :] < r["count"][:, None]
+    n, n_ret, nan = int(ok.sum()), int(listed.sum()), float("nan")
+    bits = [1 << c for c in range(len(channels))]
+    out["chan_recall"] = [float(np.mean((mask[ok] & b) != 0)) if n else nan for b in bits]
+    out["chan_unique"] = [float(np.mean(mask[ok] == b)) if n else nan for b in bits]
+    out["chan_share"] = [float(np.mean((r["src"][listed].astype(np.int64) & b) != 0)) if n_ret else nan for b in bits]
+    if details:
+        out.update(_details(r, users, targets, ts, "src"), target_mask=mask)
     return out

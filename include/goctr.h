@@ -1370,6 +1370,91 @@ int goctr_recommend_uservec_ivf(goctr_model* m, goctr_recsys* r, goctr_itemvec_i
                                 int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank,
                                 int32_t* cand_items, uint32_t* cand_w, float* cand_scores, int64_t* n_failed);
 
+/* ---- Fusion of N recall channels by rank (no reference counterpart).  The blend above fills three fixed parts one after the
+ * other; here up to 7 channels of any kind answer the same request rows, and their lists are merged by the PLACES the items have
+ * in them -- reciprocal rank fusion, or a round robin -- with a weight and a guaranteed quota per channel and a bit mask that says
+ * which channels found an item.  Everything is integer and defined bit for bit (tests/fuse_ref.py is the host restatement); no
+ * output depends on thread counts, tiles or the order in which entries arrive.
+ *
+ * For request row q, channel c (0 .. n_chan - 1) yields a list L_c of at most n_list_c distinct items:
+ *   ITEMCF, WALK, USERVEC, USERVEC_IVF, ALS
+ *                  byte for byte the items goctr_itemcf_recall / goctr_walk_recall / goctr_uservec_recall /
+ *                  goctr_uservec_recall_ivf / goctr_als_recall return for the row under {recall_cfg->history, n_cand = n_list_c,
+ *                  recall_cfg->exclude} and the channel's cfg, for the same users, ts and targets over the same image of the cache
+ *   POPULAR        the handle's stored list in list order; an entry is skipped if it is seen (goctr_blend_recall's rule) unless
+ *                  it equals targets[q]; the list is cut at n_list_c KEPT entries
+ *   LIST           the caller's row `list[q * n_list_c ..]` in its order; an entry is skipped if it is outside [0, n_items), if
+ *                  it is seen unless it equals targets[q], or if an equal entry stands in front of it
+ *   place          p_c(j) >= 0: the number of L_c's entries in front of item j (kept entries only)
+ *   n_items        the handles' (they must agree); with LIST channels alone 2^31 - 1
+ * Reciprocal rank fusion (mode GOCTR_FUSE_RRF):
+ *   S(j)           the sum over the channels whose list holds j of weight_c * floor(2^32 / (rrf_k + p_c(j))): uint64, below 2^51
+ *   out_w          (uint32)(S >> 19)
+ * Round robin (mode GOCTR_FUSE_ROUND_ROBIN; the weights are ignored):
+ *   turn(j)        the minimum over the channels whose list holds j of p_c(j) * n_chan + c
+ *   S(j)           2^32 - 1 - turn(j);  out_w = (uint32)S
+ * Both:
+ *   order          S descending, then item ascending
+ *   protected      item j is protected if it is among the first reserve_c entries of some L_c
+ *   output         every protected item, then the best other items by the order rule until the list holds n_cand entries; the
+ *                  whole list sorted by the order rule.  out_count[q] = its length, out_target_pos[q] = the target's place or -1
+ *   out_src        a bit mask: bit c is set iff L_c holds the item; padding 255 (item -1, weight 0)
+ *   out_s          [n_req,n_cand] or NULL: the full S, padding 0
+ *   chan_count     [n_req,n_chan] or NULL: the length of L_c
+ *   chan_target_pos [n_req,n_chan] or NULL: the target's place in L_c, or -1 (-1 throughout without targets)
+ *   chan_items     NULL, or n_chan host pointers, each NULL or [n_req,n_list_c]: the lists themselves, padding -1
+ *   refused        (-1, nothing touched) the recall entries' own refusals; n_chan outside 1 .. 7; a kind that is no GOCTR_FUSE_*;
+ *                  n_list outside 1 .. 1024, weight above 65535, reserve outside 0 .. n_list; the sum of n_list above 4096; the
+ *                  sum of reserve above recall_cfg->n_cand; mode or rrf_k outside their ranges; a handle, handle2, cfg or list
+ *                  missing for its kind or given where the kind takes none; a channel cfg its own entry refuses; handles on
+ *                  different engines; handles whose n_items differ, a walk graph whose n_users differs from the cache's
+ * c == NULL: there is no history and nothing is seen, so only POPULAR and LIST channels yield entries.  The two sums are limits of
+ * the implementation: the union of a row's lists and its hash table sit in one workgroup's LDS. */
+enum { GOCTR_FUSE_ITEMCF = 0, GOCTR_FUSE_WALK, GOCTR_FUSE_USERVEC, GOCTR_FUSE_USERVEC_IVF, GOCTR_FUSE_ALS, GOCTR_FUSE_POPULAR,
+       GOCTR_FUSE_LIST };
+enum { GOCTR_FUSE_RRF = 0, GOCTR_FUSE_ROUND_ROBIN = 1 };
+typedef struct {
+  int32_t  kind;        /* GOCTR_FUSE_*                                                            */
+  int32_t  n_list;      /* 1 .. 1024: entries asked of the channel per row                         */
+  uint32_t weight;      /* 0 .. 65535 (RRF only)                                                   */
+  int32_t  reserve;     /* 0 .. n_list: the channel's first `reserve` kept entries are guaranteed  */
+  const void* handle;   /* goctr_itemcf* | goctr_walkgraph* | goctr_itemvec* | goctr_itemvec_index* |
+                           goctr_als* | goctr_popular* | NULL (LIST)                               */
+  const void* handle2;  /* ALS: the goctr_itemvec* it ranks against; else NULL                     */
+  const void* cfg;      /* goctr_walk_cfg* | goctr_uservec_cfg* (USERVEC, ALS) |
+                           goctr_uservec_ivf_cfg* | NULL                                           */
+  const int32_t* list;  /* LIST: host [n_req, n_list], -1 = no entry; else NULL                    */
+} goctr_fuse_channel;
+typedef struct {
+  int32_t mode;         /* GOCTR_FUSE_RRF | GOCTR_FUSE_ROUND_ROBIN                   default RRF */
+  int32_t rrf_k;        /* 1 .. 1024                                                 default 60  */
+} goctr_fuse_cfg;
+void goctr_fuse_cfg_default(goctr_fuse_cfg* c);
+int  goctr_fuse_recall(const goctr_fuse_channel* chan, int32_t n_chan /* 1 .. 7 */, goctr_ubcache* c /* may be NULL */,
+                       const int32_t* users, const int64_t* ts /* NULL = 0 */, int64_t n_req,
+                       const goctr_recall_cfg* recall_cfg, const goctr_fuse_cfg* fuse_cfg,
+                       int32_t* out_items /*[n_req,n_cand]*/, uint32_t* out_w /*same*/, uint8_t* out_src /*same*/,
+                       int32_t* out_count /*[n_req]*/, const int32_t* targets /* or NULL */, int32_t* out_target_pos /* or NULL */,
+                       uint64_t* out_s /* or NULL */, int32_t* chan_count /* or NULL */, int32_t* chan_target_pos /* or NULL */,
+                       int32_t* const* chan_items /* or NULL */);
+
+/* goctr_recommend_fused: recall from the channels, fuse, then rank -- goctr_recommend_blend_walk's shape with the fused list of
+ * goctr_fuse_recall (over the recsys's cache image, n_items = the recsys's) as the recall stage.  Scores, failed candidates,
+ * n_failed, out_cand_count, out_target_pos and out_target_rank are as documented for goctr_recommend_itemcf; out_src / cand_src
+ * carry the channel masks.  With v and cfg the MMR selection replaces the last step (k is then ignored, cfg->k holds); without
+ * them out_obj, out_pen and out_target_place are not touched.
+ *   refused        goctr_recommend_itemcf's refusals, goctr_fuse_recall's, v without cfg or cfg without v, and a handle whose
+ *                  n_items (a walk graph's n_users) differs from the recsys's */
+int goctr_recommend_fused(goctr_model* m, goctr_recsys* r, const goctr_fuse_channel* chan, int32_t n_chan /* 1 .. 7 */,
+                          const int32_t* users, const int64_t* ts /* NULL = 0 */, int64_t n_req,
+                          const int32_t* targets /* [n_req] or NULL */, const goctr_recall_cfg* recall_cfg,
+                          const goctr_fuse_cfg* fuse_cfg,
+                          goctr_itemvec* v /* or NULL */, const goctr_mmr_cfg* cfg /* or NULL */, int32_t k, int64_t pass_rows,
+                          int32_t* out_items /* [n_req,k] */, float* out_scores /* [n_req,k] */, int32_t* out_count,
+                          uint8_t* out_src, int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank,
+                          int32_t* cand_items, uint32_t* cand_w, float* cand_scores, uint8_t* cand_src, int64_t* n_failed,
+                          int32_t* out_obj, uint32_t* out_pen, int32_t* out_target_place);
+
 /* The replica a multi-device training call (cfg.devices = n) keeps on engine `rank` (rank 0: the handle itself); NULL before
  * the first such call.  Borrowed: owned by the handle it was asked from.  For checks that the replicas are bit-identical
  * (tests, bench.py's replica checksum) -- every entry point works on it, on its own engine. */
