@@ -284,6 +284,17 @@ class FuseCfg(C.Structure):
     _fields_ = [("mode", C.c_int32), ("rrf_k", C.c_int32)]
 
 
+class ItemPred(C.Structure):
+    """goctr_item_pred (include/goctr.h)"""
+    _fields_ = [("require_all", C.c_uint64), ("require_any", C.c_uint64), ("forbid", C.c_uint64), ("born_min", C.c_int64),
+                ("born_max", C.c_int64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ItemFilter(C.Structure):
+    """goctr_item_filter (include/goctr.h)"""
+    _fields_ = [("attrs", C.c_void_p), ("preds", C.POINTER(ItemPred)), ("n_pred", C.c_int32), ("pred_of", C.POINTER(C.c_int32))]
+
+
 class ListCfg(C.Structure):
     """goctr_list_cfg (include/goctr.h)"""
     _fields_ = [("k", C.c_int32), ("tail_cnt", C.c_int32)]
@@ -314,6 +325,7 @@ UVMIX_MAX, UVMIX_QUOTA = 0, 1                               # goctr_uservec_mult
  FUSE_LIST) = range(7)                                      # goctr_fuse_channel.kind
 FUSE_RRF, FUSE_ROUND_ROBIN = 0, 1                           # goctr_fuse_cfg.mode
 FUSE_MAX_CHAN, FUSE_MAX_LISTED = 7, 4096                    # n_chan, the sum of n_list
+PRED_BORN_MIN, PRED_BORN_MAX, PRED_BORN_BEFORE_TS = 1, 2, 4 # goctr_item_pred.flags
 
 
 # every symbol include/goctr.h declares (tests/test_capi_symbols.py checks the list against the header)
@@ -378,6 +390,8 @@ SYMBOLS = [
     "goctr_ivf_cfg_default", "goctr_itemvec_index_build", "goctr_itemvec_index_destroy", "goctr_itemvec_index_info",
     "goctr_itemvec_index_export", "goctr_uservec_ivf_cfg_default", "goctr_uservec_recall_ivf", "goctr_recommend_uservec_ivf",
     "goctr_fuse_cfg_default", "goctr_fuse_recall", "goctr_recommend_fused",
+    "goctr_itemattr_create", "goctr_itemattr_destroy", "goctr_itemattr_info", "goctr_itemattr_export", "goctr_itemattr_update",
+    "goctr_itemattr_count", "goctr_fuse_recall_filtered", "goctr_recommend_fused_filtered",
 ]
 
 _lib = None
@@ -406,7 +420,8 @@ def load() -> C.CDLL:
                      "goctr_ivf_cfg_default", "goctr_uservec_ivf_cfg_default", "goctr_itemvec_index_destroy",
                      "goctr_calib_cfg_default", "goctr_calibrator_destroy", "goctr_boot_cfg_default",
                      "goctr_walkgraph_cfg_default", "goctr_walk_cfg_default", "goctr_walkgraph_destroy",
-                     "goctr_als_cfg_default", "goctr_als_destroy", "goctr_ease_cfg_default", "goctr_fuse_cfg_default"):
+                     "goctr_als_cfg_default", "goctr_als_destroy", "goctr_ease_cfg_default", "goctr_fuse_cfg_default",
+                     "goctr_itemattr_destroy"):
             getattr(_lib, name).restype = None
         _bm = C.POINTER(BinaryMetrics)
         _lib.goctr_metrics_binary.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, _bm]
@@ -611,6 +626,15 @@ def load() -> C.CDLL:
         _lib.goctr_recommend_fused.argtypes = [C.c_void_p, C.c_void_p, _fc, C.c_int32, _i32, _i64, C.c_int64, _i32,
                                                C.POINTER(RecallCfg), _fcfg, C.c_void_p, _mmr, C.c_int32, C.c_int64, _i32, _f32, _i32,
                                                _u8, _i32, _i32, _i64, _i32, _u32, _f32, _u8, _i64, _i32, _u32, _i32]
+        _ip, _if = C.POINTER(ItemPred), C.POINTER(ItemFilter)
+        _lib.goctr_itemattr_create.argtypes = [C.c_int64, _u64, _i64, C.POINTER(C.c_void_p)]
+        _lib.goctr_itemattr_destroy.argtypes = [C.c_void_p]
+        _lib.goctr_itemattr_info.argtypes = [C.c_void_p, _i64, _i32, _u64]
+        _lib.goctr_itemattr_export.argtypes = [C.c_void_p, _u64, _i64]
+        _lib.goctr_itemattr_update.argtypes = [C.c_void_p, _i32, C.c_int64, _u64, _u64, _i64]
+        _lib.goctr_itemattr_count.argtypes = [C.c_void_p, _ip, C.c_int32, _i64]
+        _lib.goctr_fuse_recall_filtered.argtypes = [_if] + _lib.goctr_fuse_recall.argtypes
+        _lib.goctr_recommend_fused_filtered.argtypes = [_if] + _lib.goctr_recommend_fused.argtypes
         _lib.goctr_list_cfg_default.argtypes = [C.POINTER(ListCfg)]
         _lib.goctr_metrics_lists.argtypes = [C.c_void_p, C.c_void_p, _i32, _i32, C.c_int64, C.c_int64, C.POINTER(ListCfg),
                                              C.POINTER(ListMetrics), C.POINTER(ListRow), _u32, _u32]

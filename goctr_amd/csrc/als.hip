@@ -526,7 +526,7 @@ int als_launch(const goctr_als* a, const goctr_itemvec* v, const RecallCall& r, 
                const AlsVecOut& vec, UvScratch& ws, hipStream_t st) {
   if (als_foldin_launch(a, r.seq, r.in.users.p, r.in.ts.p, r.nq, r.cfg.history, vec.x, vec.p, nullptr, ws, st)) return -1;
   return uservec_scan_planes(v, r.seq, UvCols{r.in.users.p, r.in.ts.p, r.targets()}, r.nq, r.cfg, ucfg, ws.p_hi.p, ws.p_lo.p, out,
-                             r.stride, ws, st);
+                             r.stride, ws, st, r.flt);
 }
 
 int als_check_vectors(const char* who, const goctr_als* a, const goctr_itemvec* v, int64_t n_items) {

@@ -15,6 +15,7 @@ struct FuseArgs {
   const goctr_fuse_channel* chan; int n_chan;
   goctr_fuse_cfg fcfg;
   long long n_items;
+  const goctr_item_filter* filter = nullptr;    // a filtered call's filter behind filter_check (itemattr.h); null: the call does not filter
 };
 
 // the optional host outputs beside the rows (each may be null): include/goctr.h names them
@@ -23,8 +24,11 @@ struct FuseOut { uint64_t* s; int32_t* chan_count; int32_t* chan_tpos; int32_t* 
 // every refusal of the channels and the two cfgs that needs no device (sets the error text).  n_users / n_items: what the walk
 // graphs' users and the handles' items must equal, negative = nothing to compare with (then the handles must still agree with each
 // other, and with no handle n_items becomes 2^31 - 1); eng: the engine every handle must live on, null = the first handle's
+// flt, n_req: a _filtered entry's filter (null, or null attrs: none) and its rows -- filter_check's refusals against the same engine
+// and n_items; with LIST channels alone n_items becomes the attributes'
 int fuse_check(const char* who, const goctr_fuse_channel* chan, int n_chan, const goctr_recall_cfg& rcfg, const goctr_fuse_cfg* fcfg,
-               long long n_users, long long n_items, const Engine* eng, FuseArgs* out);
+               long long n_users, long long n_items, const Engine* eng, FuseArgs* out, const goctr_item_filter* flt = nullptr,
+               int64_t n_req = 0);
 // the engine of the first channel that has a handle, or null
 Engine* fuse_engine(const goctr_fuse_channel* chan, int n_chan);
 
@@ -38,7 +42,9 @@ struct FuseStage {
   IvfScratch ivf_ws[FUSE_MAX_CHAN];
   DevBuf<int32_t> c_count, c_tpos;              // [nq, n_chan]
   DevBuf<unsigned long long> o_s;               // [nq, n_cand]
-  // the channels' launchers into l_items at stride n_list, then fuse_kernel into `o`, all on `st`.  Waits for nothing
+  FilterStage flt;                              // a filtered call's predicates, effective targets and bitmaps; holds the attributes
+  // the channels' launchers into l_items at stride n_list, then fuse_kernel into `o`, all on `st`.  Waits for nothing.  With
+  // f.filter the view is staged first and every launcher, and fuse_kernel, runs under it
   int launch(const FuseArgs& f, const RecallCall& r, const RecallRows& o, hipStream_t st);
   // queues the optional outputs on `out` (behind launch)
   int add_outputs(const FuseArgs& f, const FuseOut& h, int64_t nq, int n_cand, bool has_targets, HostStage& out);

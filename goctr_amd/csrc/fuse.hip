@@ -55,8 +55,10 @@ struct FuseKernelArgs {
   u64* out_s;                                                                 // [nq, n_cand]
 };
 
-template <int BITS>
-__global__ __launch_bounds__(SEL_THREADS) void fuse_kernel(FuseKernelArgs a) {
+// FILT: the row's predicate joins the `ok` of a POPULAR or LIST entry (item_eligible, itemattr.h) -- an ineligible entry is skipped
+// as a seen one is; the model channels' rows arrive filtered.  FILT = false is the kernel every unfiltered entry runs
+template <int BITS, bool FILT>
+__global__ __launch_bounds__(SEL_THREADS) void fuse_kernel(FuseKernelArgs a, FilterArg<FILT> f) {
   using Tab = LdsItemTable<BITS>;
   constexpr int N = Tab::SIZE;
   static_assert(N % SEL_THREADS == 0 && N >= 1024, "whole rounds over the table; an output row fits");
@@ -76,6 +78,8 @@ __global__ __launch_bounds__(SEL_THREADS) void fuse_kernel(FuseKernelArgs a) {
   const long long mts = a.ts[q];
   const bool look = a.exclude != GOCTR_TOPN_KEEP_SEEN && len > 0, before = a.exclude == GOCTR_TOPN_DROP_SEEN_BEFORE && mts != 0;
   const bool rrf = a.mode == GOCTR_FUSE_RRF;
+  const goctr_item_pred* pred = nullptr;                   // the row's predicate: read where a candidate is accepted, not held
+  if constexpr (FILT) pred = f.preds + f.pred_of[q];
 
   for (int i = tid; i < N; i += SEL_THREADS) { u_key[i] = Tab::EMPTY; u_s[i] = 0ull; }
   for (int i = tid; i < N / 4; i += SEL_THREADS) u_flag[i] = 0u;
@@ -133,6 +137,7 @@ __global__ __launch_bounds__(SEL_THREADS) void fuse_kernel(FuseKernelArgs a) {
         const bool seen = (tkey[slot] >> 31) != 0u;
         // (a LIST is one tile and a stored popularity list holds distinct items: an item's first position in its tile is its first)
         ok = tpos[slot] == (unsigned int)tid && (!seen || (has_t && item == tgt));
+        if constexpr (FILT) ok = ok && item_eligible(f, *pred, (long long)item, mts);
       }
       int tot;
       const int r = fill + lds_block_rank<SEL_THREADS / 64>(ok, wcnt, &tot);
@@ -235,7 +240,7 @@ Engine* fuse_engine(const goctr_fuse_channel* chan, int n_chan) {
 }
 
 int fuse_check(const char* who, const goctr_fuse_channel* chan, int n_chan, const goctr_recall_cfg& rcfg, const goctr_fuse_cfg* fcfg,
-               long long n_users, long long n_items, const Engine* eng, FuseArgs* out) {
+               long long n_users, long long n_items, const Engine* eng, FuseArgs* out, const goctr_item_filter* flt, int64_t n_req) {
   GOCTR_CHECK(chan && fcfg, "%s: null argument", who);
   GOCTR_CHECK(n_chan >= 1 && n_chan <= FUSE_MAX_CHAN, "%s: n_chan = %d is outside 1 .. %d", who, n_chan, FUSE_MAX_CHAN);
   GOCTR_CHECK(fcfg->mode == GOCTR_FUSE_RRF || fcfg->mode == GOCTR_FUSE_ROUND_ROBIN, "%s: mode = %d is no GOCTR_FUSE_* rule", who, fcfg->mode);
@@ -279,12 +284,24 @@ int fuse_check(const char* who, const goctr_fuse_channel* chan, int n_chan, cons
   }
   GOCTR_CHECK(sum_list <= FUSE_MAX_LISTED, "%s: the channels' n_list add up to %lld (limit %d)", who, sum_list, FUSE_MAX_LISTED);
   GOCTR_CHECK(sum_reserve <= rcfg.n_cand, "%s: the channels' reserves add up to %lld, over n_cand = %d", who, sum_reserve, rcfg.n_cand);
+  bool filters;
+  if (filter_check(who, flt, n_req, n_items, eng, &filters)) return -1;
+  if (filters && n_items < 0) n_items = flt->attrs->n_items;
   out->chan = chan; out->n_chan = n_chan; out->fcfg = *fcfg;
   out->n_items = n_items < 0 ? (long long)INT32_MAX : n_items;     // (no handle: the largest n_items a handle can have)
+  out->filter = filters ? flt : nullptr;
   return 0;
 }
 
-int FuseStage::launch(const FuseArgs& f, const RecallCall& r, const RecallRows& o, hipStream_t st) {
+int FuseStage::launch(const FuseArgs& f, const RecallCall& r0, const RecallRows& o, hipStream_t st) {
+  RecallCall r = r0;
+  if (f.filter) {                                                      // the view first: the call's targets are its effective ones
+    bool scans = false;                                                // a channel that blocks through the seen bitmap
+    for (int c = 0; c < f.n_chan; ++c)
+      scans = scans || f.chan[c].kind == GOCTR_FUSE_USERVEC || f.chan[c].kind == GOCTR_FUSE_USERVEC_IVF || f.chan[c].kind == GOCTR_FUSE_ALS;
+    if (flt.stage(*f.filter, r.has_targets ? r.in.targets.p : nullptr, r.in.ts.p, r.nq, scans && r.seq.off != nullptr, st)) return -1;
+    r.flt = &flt.view;
+  }
   const size_t nq = (size_t)r.nq;
   FuseKernelArgs k{};
   k.off = r.seq.off; k.seq_items = r.seq.items; k.seq_ts = r.seq.ts;
@@ -342,8 +359,14 @@ int FuseStage::launch(const FuseArgs& f, const RecallCall& r, const RecallRows& 
   }
   k.chan_count = c_count.p; k.chan_tpos = c_tpos.p;
   k.out_items = o.items; k.out_w = o.w; k.out_src = o.src; k.out_count = o.count; k.out_tpos = o.tpos; k.out_s = o_s.p;
-  if (sum_list <= 1024) hipLaunchKernelGGL(fuse_kernel<11>, dim3((unsigned)r.nq), dim3(SEL_THREADS), 0, st, k);
-  else hipLaunchKernelGGL(fuse_kernel<13>, dim3((unsigned)r.nq), dim3(SEL_THREADS), 0, st, k);
+  const dim3 grid((unsigned)r.nq), block(SEL_THREADS);
+  if (r.flt) {
+    if (sum_list <= 1024) hipLaunchKernelGGL((fuse_kernel<11, true>), grid, block, 0, st, k, *r.flt);
+    else hipLaunchKernelGGL((fuse_kernel<13, true>), grid, block, 0, st, k, *r.flt);
+  } else {
+    if (sum_list <= 1024) hipLaunchKernelGGL((fuse_kernel<11, false>), grid, block, 0, st, k, NoItemFilter{});
+    else hipLaunchKernelGGL((fuse_kernel<13, false>), grid, block, 0, st, k, NoItemFilter{});
+  }
   GOCTR_HIP(hipGetLastError());
   return 0;
 }
@@ -372,14 +395,24 @@ int goctr_fuse_recall(const goctr_fuse_channel* chan, int32_t n_chan, goctr_ubca
                       int64_t n_req, const goctr_recall_cfg* recall_cfg, const goctr_fuse_cfg* fuse_cfg, int32_t* out_items,
                       uint32_t* out_w, uint8_t* out_src, int32_t* out_count, const int32_t* targets, int32_t* out_target_pos,
                       uint64_t* out_s, int32_t* chan_count, int32_t* chan_target_pos, int32_t* const* chan_items) {
+  return goctr_fuse_recall_filtered(nullptr, chan, n_chan, c, users, ts, n_req, recall_cfg, fuse_cfg, out_items, out_w, out_src, out_count,
+                                    targets, out_target_pos, out_s, chan_count, chan_target_pos, chan_items);
+}
+
+int goctr_fuse_recall_filtered(const goctr_item_filter* flt, const goctr_fuse_channel* chan, int32_t n_chan, goctr_ubcache* c,
+                               const int32_t* users, const int64_t* ts, int64_t n_req, const goctr_recall_cfg* recall_cfg,
+                               const goctr_fuse_cfg* fuse_cfg, int32_t* out_items, uint32_t* out_w, uint8_t* out_src,
+                               int32_t* out_count, const int32_t* targets, int32_t* out_target_pos, uint64_t* out_s,
+                               int32_t* chan_count, int32_t* chan_target_pos, int32_t* const* chan_items) {
   Engine* const first = fuse_engine(chan, n_chan);
-  GOCTR_ENTER_ON(first ? first : c ? c->eng : nullptr);
-  const char* who = "goctr_fuse_recall";
+  GOCTR_ENTER_ON(first ? first : c ? c->eng : flt && flt->attrs ? flt->attrs->eng : nullptr);
+  const char* who = flt ? "goctr_fuse_recall_filtered" : "goctr_fuse_recall";
   GOCTR_CHECK(chan && users && recall_cfg && fuse_cfg && out_items && out_w && out_src && out_count, "%s: null argument", who);
   // (without a cache there is no user table to check against: any non-negative row passes, and no kernel reads through it)
   if (recall_check_cfg(recall_cfg, who) || recall_check_users(users, n_req, c ? c->n_users : (int64_t)INT32_MAX + 1, who)) return -1;
   FuseArgs f{};
-  if (fuse_check(who, chan, n_chan, *recall_cfg, fuse_cfg, c ? (long long)c->n_users : -1LL, -1LL, c ? c->eng : nullptr, &f)) return -1;
+  if (fuse_check(who, chan, n_chan, *recall_cfg, fuse_cfg, c ? (long long)c->n_users : -1LL, -1LL, c ? c->eng : nullptr, &f, flt, n_req))
+    return -1;
   HostStage out(engine().stream);
   FuseStage stage;
   const FuseOut ho{out_s, chan_count, chan_target_pos, chan_items};

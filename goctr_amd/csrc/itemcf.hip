@@ -154,7 +154,10 @@ struct RecallArgs {
   int32_t* out_items; unsigned int* out_w; int32_t* out_count; int32_t* out_tpos;   // device; out_tpos may be null
 };
 
-__global__ __launch_bounds__(SEL_THREADS) void icf_recall_kernel(RecallArgs a) {
+// FILT: the row's predicate decides at step 4 which candidates may join the list (item_eligible, itemattr.h): a gather of the
+// candidate's tag word (and birth time) per distinct candidate.  FILT = false is the kernel every unfiltered entry runs
+template <bool FILT>
+__global__ __launch_bounds__(SEL_THREADS) void icf_recall_kernel(RecallArgs a, FilterArg<FILT> f) {
   __shared__ unsigned int tkey[RC_TABLE], tsum[RC_TABLE];
   __shared__ unsigned long long skey[SEL_CAP];
   __shared__ unsigned sraw[SEL_CAP];
@@ -170,6 +173,8 @@ __global__ __launch_bounds__(SEL_THREADS) void icf_recall_kernel(RecallArgs a) {
   long long lo_e = 0, len = 0;
   if (a.off) { const int u = a.users[q]; lo_e = a.off[u]; len = a.off[u + 1] - lo_e; }
   const long long mts = a.ts[q];
+  const goctr_item_pred* pred = nullptr;                   // the row's predicate: read where a candidate is accepted, not held
+  if constexpr (FILT) pred = f.preds + f.pred_of[q];
 
   // 1. history
   const int nh = lds_gather_history<SEL_THREADS / 64>(a.seq_items, a.seq_ts, lo_e, len, mts, a.n_items, a.H, hist, wcnt);
@@ -240,6 +245,7 @@ __global__ __launch_bounds__(SEL_THREADS) void icf_recall_kernel(RecallArgs a) {
         if (!(k >> 31) || (has_t && (int)j == tgt)) {
           key = ((unsigned long long)tsum[s0 + tid] << 32) | (unsigned long long)(~j);
           if (key <= thr) key = 0ull;
+          if constexpr (FILT) { if (key != 0ull && !item_eligible(f, *pred, (long long)j, mts)) key = 0ull; }
         }
       }
       sel_append(skey, sraw, &s_fill, &s_thr, a.n_cand, key, 0u);
@@ -353,7 +359,8 @@ int recall_launch(const goctr_itemcf* h, const RecallCall& r, const RecallRows& 
   a.users = r.in.users.p; a.ts = r.in.ts.p; a.targets = r.targets();
   a.H = r.cfg.history; a.n_cand = r.cfg.n_cand; a.exclude = r.cfg.exclude; a.stride = r.stride;
   a.out_items = out.items; a.out_w = out.w; a.out_count = out.count; a.out_tpos = out.tpos;
-  hipLaunchKernelGGL(icf_recall_kernel, dim3((unsigned)r.nq), dim3(SEL_THREADS), 0, st, a);
+  if (r.flt) hipLaunchKernelGGL(icf_recall_kernel<true>, dim3((unsigned)r.nq), dim3(SEL_THREADS), 0, st, a, *r.flt);
+  else hipLaunchKernelGGL(icf_recall_kernel<false>, dim3((unsigned)r.nq), dim3(SEL_THREADS), 0, st, a, NoItemFilter{});
   GOCTR_HIP(hipGetLastError());
   return 0;
 }

@@ -7,6 +7,7 @@
 // struct when there is more than one, scratch, stream) and hands it to a driver as a RecallStage.
 #pragma once
 #include "host_stage.h"
+#include "itemattr.h"
 #include "topn.h"
 #include "ubcache.h"
 
@@ -30,10 +31,13 @@ struct RecallInputs {
   int stage(const int32_t* h_users, const int64_t* h_ts, const int32_t* h_targets, int64_t nq, hipStream_t st);
 };
 
-// one recall over nq request rows: row q's first cfg.n_cand slots go to q * stride (stride >= cfg.n_cand) of the output rows
+// one recall over nq request rows: row q's first cfg.n_cand slots go to q * stride (stride >= cfg.n_cand) of the output rows.
+// flt: the staged filter of a filtered call (itemattr.h), null: no filter -- every launcher then runs what it ran before there was
+// one.  With a filter the whole call uses its effective targets in place of the request's
 struct RecallCall {
   CacheSeq seq; const RecallInputs& in; bool has_targets; int64_t nq; goctr_recall_cfg cfg; int stride;
-  const int32_t* targets() const { return has_targets ? in.targets.p : nullptr; }
+  const ItemFilterView* flt = nullptr;
+  const int32_t* targets() const { return !has_targets ? nullptr : flt ? flt->targets : in.targets.p; }
 };
 
 // the device arrays a recall stage fills for every request row: [nq, n_cand] candidates (padding -1 / 0 / 255), the row's count and

@@ -806,8 +806,23 @@ int goctr_recommend_fused(goctr_model* m, goctr_recsys* r, const goctr_fuse_chan
                           int32_t* out_target_pos, int64_t* out_target_rank, int32_t* cand_items, uint32_t* cand_w,
                           float* cand_scores, uint8_t* cand_src, int64_t* n_failed, int32_t* out_obj, uint32_t* out_pen,
                           int32_t* out_target_place) {
+  return goctr_recommend_fused_filtered(nullptr, m, r, chan, n_chan, users, ts, n_req, targets, recall_cfg, fuse_cfg, v, cfg, k, pass_rows,
+                                        out_items, out_scores, out_count, out_src, out_cand_count, out_target_pos, out_target_rank,
+                                        cand_items, cand_w, cand_scores, cand_src, n_failed, out_obj, out_pen, out_target_place);
+}
+
+// The same under an eligibility filter (itemattr.h; null: none): fuse_check refuses what the filter adds, FuseStage::launch stages it.
+// The attributes' reader lock is taken inside the slot, behind the model's, the embedding's and the cache's
+int goctr_recommend_fused_filtered(const goctr_item_filter* flt, goctr_model* m, goctr_recsys* r, const goctr_fuse_channel* chan,
+                                   int32_t n_chan, const int32_t* users, const int64_t* ts, int64_t n_req, const int32_t* targets,
+                                   const goctr_recall_cfg* recall_cfg, const goctr_fuse_cfg* fuse_cfg, goctr_itemvec* v,
+                                   const goctr_mmr_cfg* cfg, int32_t k, int64_t pass_rows, int32_t* out_items, float* out_scores,
+                                   int32_t* out_count, uint8_t* out_src, int32_t* out_cand_count, int32_t* out_target_pos,
+                                   int64_t* out_target_rank, int32_t* cand_items, uint32_t* cand_w, float* cand_scores,
+                                   uint8_t* cand_src, int64_t* n_failed, int32_t* out_obj, uint32_t* out_pen,
+                                   int32_t* out_target_place) {
   EngineScope on(handle_engine(m));
-  const char* who = "goctr_recommend_fused";
+  const char* who = flt ? "goctr_recommend_fused_filtered" : "goctr_recommend_fused";
   if (recommend_enter(who, m && r && chan && recall_cfg && fuse_cfg, m, r, {handle_engine(v)}, (v != nullptr) == (cfg != nullptr)))
     return -1;
   ItemcfRecArgs a{users, ts, n_req, targets, *recall_cfg, k, pass_rows, out_items, out_scores, out_count, out_cand_count,
@@ -820,7 +835,7 @@ int goctr_recommend_fused(goctr_model* m, goctr_recsys* r, const goctr_fuse_chan
   }
   if (recall_check_recommend(who, a, r->n_users)) return -1;
   FuseArgs f{};
-  if (fuse_check(who, chan, n_chan, *recall_cfg, fuse_cfg, r->n_users, r->n_items, m->eng, &f)) return -1;
+  if (fuse_check(who, chan, n_chan, *recall_cfg, fuse_cfg, r->n_users, r->n_items, m->eng, &f, flt, n_req)) return -1;
   const RerankStage rr{v, v ? *cfg : goctr_mmr_cfg{}, out_obj, out_pen, out_target_place};
   return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) {
     FuseStage stage;                          // (recall_rank_run drains the slot's stream on every path before it returns)

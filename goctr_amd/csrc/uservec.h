@@ -38,10 +38,12 @@ int uservec_merge_launch(const unsigned long long* lists, int n_chunks, int n_ca
 
 // uservec_launch's second half -- seen, scan and merge over the nq request planes given, [nq + UV_PAD_ROWS, Dp] laid out like the
 // item planes with the pad rows zero: what the multi-interest recall (uservec_multi.hip) runs over its n_req x max_interests
-// virtual rows.  A zero plane row comes back empty
+// virtual rows.  A zero plane row comes back empty.  flt (a filtered call's view, its blocked bitmaps staged; in.targets are then its
+// effective targets): the group's bitmap exists with a seen rule OR a filter, and attr_block_launch ORs every row's ineligible
+// items into it behind topn_seen_launch -- the scan kernel does not change
 int uservec_scan_planes(const goctr_itemvec* v, const CacheSeq& seq, const UvCols& in, int64_t nq, const goctr_recall_cfg& cfg,
                         const goctr_uservec_cfg& ucfg, const signed char* p_hi, const signed char* p_lo, const RecallRows& out,
-                        int stride, UvScratch& ws, hipStream_t st);
+                        int stride, UvScratch& ws, hipStream_t st, const ItemFilterView* flt = nullptr);
 
 // the request vectors a call may return beside the rows: p [nq, D] and s [nq], the pooled vectors' squared lengths; each may be null
 struct UvVecOut { int16_t* p; unsigned long long* s; };

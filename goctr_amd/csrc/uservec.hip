@@ -296,7 +296,7 @@ int uservec_launch(const goctr_itemvec* v, const RecallCall& r, const goctr_user
   if (uservec_pool_launch(UvPlanes{v->hi.p, v->lo.p, nullptr, v->n_items, v->D, v->Dp}, r.seq, r.in.users.p, r.in.ts.p, r.nq,
                           r.cfg.history, vec.p, vec.s, ws, st)) return -1;
   return uservec_scan_planes(v, r.seq, UvCols{r.in.users.p, r.in.ts.p, r.targets()}, r.nq, r.cfg, ucfg, ws.p_hi.p, ws.p_lo.p, out,
-                             r.stride, ws, st);
+                             r.stride, ws, st, r.flt);
 }
 
 int uservec_pool_launch(const UvPlanes& pl, const CacheSeq& seq, const int32_t* users, const long long* ts, int64_t nq, int history,
@@ -328,10 +328,11 @@ int uservec_merge_launch(const unsigned long long* lists, int n_chunks, int n_ca
 
 int uservec_scan_planes(const goctr_itemvec* v, const CacheSeq& seq, const UvCols& in, int64_t nq, const goctr_recall_cfg& cfg,
                         const goctr_uservec_cfg& ucfg, const signed char* p_hi, const signed char* p_lo, const RecallRows& out,
-                        int stride, UvScratch& ws, hipStream_t st) {
+                        int stride, UvScratch& ws, hipStream_t st, const ItemFilterView* flt) {
   const int Dp = v->Dp, nc = cfg.n_cand, cap = uv_cap(nc), R = uv_rows(cap, nq);
   const int64_t V = v->n_items;
-  const bool seen = cfg.exclude != GOCTR_TOPN_KEEP_SEEN && seq.off != nullptr;
+  const bool seen_rule = cfg.exclude != GOCTR_TOPN_KEEP_SEEN && seq.off != nullptr;
+  const bool seen = seen_rule || flt != nullptr;          // the group has a bitmap: seen entries, ineligible items, or both
   const int64_t words = cdiv(V, 32);
   // the scratch budget decides the rows of a group; the chunks follow from the row tiles the first group brings, so that a
   // single request row still fills the chip
@@ -362,8 +363,9 @@ int uservec_scan_planes(const goctr_itemvec* v, const CacheSeq& seq, const UvCol
     const int g_rows = (int)std::min<int64_t>(G, nq - q0);
     if (seen) {
       GOCTR_HIP(hipMemsetAsync(ws.bitmap.p, 0, (size_t)g_rows * words * 4, st));
-      if (topn_seen_launch(seq.off, seq.items, seq.ts, in.users, in.ts, q0, g_rows, V, words, cfg.exclude == GOCTR_TOPN_DROP_SEEN_BEFORE,
-                           ws.bitmap.p, st)) return -1;
+      if (seen_rule && topn_seen_launch(seq.off, seq.items, seq.ts, in.users, in.ts, q0, g_rows, V, words,
+                                        cfg.exclude == GOCTR_TOPN_DROP_SEEN_BEFORE, ws.bitmap.p, st)) return -1;
+      if (flt && attr_block_launch(*flt, in.ts, q0, g_rows, ws.bitmap.p, st)) return -1;
     }
     ScanArgs a{};
     a.p_hi = p_hi; a.p_lo = p_lo; a.hi = v->hi.p; a.lo = v->lo.p; a.Dp = Dp; a.n_items = V; a.chunk = chunk;

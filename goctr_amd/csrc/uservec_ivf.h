@@ -46,7 +46,8 @@ int uservec_ivf_np(const goctr_itemvec_index* x, const goctr_uservec_ivf_cfg& ic
 // run it over its own planes.  Fills ws.probed and ws.scanned as well
 int uservec_ivf_scan_planes(const goctr_itemvec_index* x, const CacheSeq& seq, const UvCols& in, int64_t nq, const goctr_recall_cfg& cfg,
                             const goctr_uservec_ivf_cfg& icfg, const signed char* p_hi, const signed char* p_lo,
-                            const unsigned long long* s, const RecallRows& out, int stride, IvfScratch& ws, hipStream_t st);
+                            const unsigned long long* s, const RecallRows& out, int stride, IvfScratch& ws, hipStream_t st,
+                            const ItemFilterView* flt = nullptr);   // (flt: as uservec_scan_planes)
 
 // pool (from the index's own planes), then uservec_ivf_scan_planes, as uservec_launch; o_p [nq, D] may be null (the squared
 // lengths are ws.s).  Waits for nothing

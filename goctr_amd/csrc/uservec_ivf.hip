@@ -476,12 +476,14 @@ int uservec_ivf_np(const goctr_itemvec_index* x, const goctr_uservec_ivf_cfg& ic
 
 int uservec_ivf_scan_planes(const goctr_itemvec_index* x, const CacheSeq& seq, const UvCols& in, int64_t nq, const goctr_recall_cfg& cfg,
                             const goctr_uservec_ivf_cfg& icfg, const signed char* p_hi, const signed char* p_lo,
-                            const unsigned long long* s, const RecallRows& out, int stride, IvfScratch& ws, hipStream_t st) {
+                            const unsigned long long* s, const RecallRows& out, int stride, IvfScratch& ws, hipStream_t st,
+                            const ItemFilterView* flt) {
   const char* who = "goctr_uservec_recall_ivf";
   const int Dp = x->Dp, nc = cfg.n_cand, np = uservec_ivf_np(x, icfg);
   const bool any = x->n_nonempty > 0 && seq.off != nullptr;   // (no lists, or no cache and so no vectors: every row comes back empty)
   const int64_t V = x->n_items, words = cdiv(V, 32);
-  const bool seen = any && cfg.exclude != GOCTR_TOPN_KEEP_SEEN;
+  const bool seen_rule = any && cfg.exclude != GOCTR_TOPN_KEEP_SEEN;
+  const bool seen = seen_rule || (any && flt != nullptr);   // the group has a bitmap: seen entries, ineligible items, or both
   if (ws.probed.alloc((size_t)nq * np, false) || ws.scanned.alloc((size_t)nq, false)) return -1;
   if (!any) {
     GOCTR_HIP(hipMemsetAsync(ws.probed.p, 0xff, sizeof(int32_t) * (size_t)nq * np, st));
@@ -523,8 +525,9 @@ int uservec_ivf_scan_planes(const goctr_itemvec_index* x, const CacheSeq& seq, c
     if (any) {
       if (seen) {
         GOCTR_HIP(hipMemsetAsync(ws.uv.bitmap.p, 0, (size_t)g_rows * words * 4, st));
-        if (topn_seen_launch(seq.off, seq.items, seq.ts, in.users, in.ts, q0, g_rows, V, words, cfg.exclude == GOCTR_TOPN_DROP_SEEN_BEFORE,
-                             ws.uv.bitmap.p, st)) return -1;
+        if (seen_rule && topn_seen_launch(seq.off, seq.items, seq.ts, in.users, in.ts, q0, g_rows, V, words,
+                                          cfg.exclude == GOCTR_TOPN_DROP_SEEN_BEFORE, ws.uv.bitmap.p, st)) return -1;
+        if (flt && attr_block_launch(*flt, in.ts, q0, g_rows, ws.uv.bitmap.p, st)) return -1;
       }
       const unsigned int P = (unsigned int)((int64_t)g_rows * np);
       TableArgs t{};
@@ -565,7 +568,7 @@ int uservec_ivf_launch(const goctr_itemvec_index* x, const RecallCall& r, const 
   if (uservec_pool_launch(UvPlanes{x->hi.p, x->lo.p, x->pos.p, x->n_items, x->D, x->Dp}, r.seq, r.in.users.p, r.in.ts.p, r.nq,
                           r.cfg.history, o_p, ws.s.p, ws.uv, st)) return -1;
   return uservec_ivf_scan_planes(x, r.seq, UvCols{r.in.users.p, r.in.ts.p, r.targets()}, r.nq, r.cfg, icfg, ws.uv.p_hi.p, ws.uv.p_lo.p,
-                                 ws.s.p, out, r.stride, ws, st);
+                                 ws.s.p, out, r.stride, ws, st, r.flt);
 }
 
 int uservec_ivf_check_recommend(const goctr_itemvec_index* x, const goctr_uservec_ivf_cfg* icfg, const ItemcfRecArgs& a, int64_t n_users,

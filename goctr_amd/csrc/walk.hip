@@ -96,7 +96,10 @@ __device__ __forceinline__ u64 wk_root(unsigned int c) {
   return r;
 }
 
-__global__ __launch_bounds__(SEL_THREADS) void walk_recall_kernel(WalkArgs a) {
+// FILT: the row's predicate decides at step 5 which of the visited items may join the list (item_eligible, itemattr.h); the walks
+// themselves pass through ineligible items.  FILT = false is the kernel every unfiltered entry runs
+template <bool FILT>
+__global__ __launch_bounds__(SEL_THREADS) void walk_recall_kernel(WalkArgs a, FilterArg<FILT> f) {
   constexpr int KCAP = WK_MAX_VISITS, PER = KCAP / SEL_THREADS;   // the list's capacity; list positions per thread
   __shared__ unsigned long long vkey[KCAP];
   __shared__ unsigned long long skey[SEL_CAP];
@@ -114,6 +117,8 @@ __global__ __launch_bounds__(SEL_THREADS) void walk_recall_kernel(WalkArgs a) {
   long long lo_e = 0, len = 0;
   if (a.off) { lo_e = a.off[user]; len = a.off[user + 1] - lo_e; }
   const long long mts = a.ts[q];
+  const goctr_item_pred* pred = nullptr;                   // the row's predicate: read where a candidate is accepted, not held
+  if constexpr (FILT) pred = f.preds + f.pred_of[q];
   const int total = a.n_walks * a.n_steps;     // <= KCAP (walk_check_cfg)
   int n2 = 64;
   while (n2 < total) n2 <<= 1;
@@ -214,6 +219,7 @@ __global__ __launch_bounds__(SEL_THREADS) void walk_recall_kernel(WalkArgs a) {
       const int item = (int)~(unsigned int)key;
       if (((seen[p >> 5] >> (p & 31)) & 1u) && !(has_t && item == tgt)) key = 0ull;
       if (key <= s_thr) key = 0ull;
+      if constexpr (FILT) { if (key != 0ull && !item_eligible(f, *pred, (long long)item, mts)) key = 0ull; }
     }
     sel_append(skey, sraw, &s_fill, &s_thr, a.n_cand, key, 0u);
   }
@@ -247,7 +253,8 @@ int walk_launch(const goctr_walkgraph* g, const RecallCall& r, const goctr_walk_
   a.H = r.cfg.history; a.n_cand = r.cfg.n_cand; a.exclude = r.cfg.exclude; a.stride = r.stride;
   a.n_walks = wcfg.n_walks; a.n_steps = wcfg.n_steps; a.boost = wcfg.boost; a.min_visits = wcfg.min_visits; a.seed = wcfg.seed;
   a.out_items = out.items; a.out_w = out.w; a.out_count = out.count; a.out_tpos = out.tpos; a.out_trace = o_trace;
-  hipLaunchKernelGGL(walk_recall_kernel, dim3((unsigned)r.nq), dim3(SEL_THREADS), 0, st, a);
+  if (r.flt) hipLaunchKernelGGL(walk_recall_kernel<true>, dim3((unsigned)r.nq), dim3(SEL_THREADS), 0, st, a, *r.flt);
+  else hipLaunchKernelGGL(walk_recall_kernel<false>, dim3((unsigned)r.nq), dim3(SEL_THREADS), 0, st, a, NoItemFilter{});
   GOCTR_HIP(hipGetLastError());
   return 0;
 }

@@ -1161,6 +1161,50 @@ inline TopN RecommendBlendALSBatch(model::CtrNet& net, RecSys& rs, const ItemCF*
   return out;
 }
 
+// Item attributes for eligibility filters (goctr_itemattr): 64 caller-defined tag bits per dense item and, with `born`, a birth time
+// per item on the cache's timestamp scale, resident in HBM and updated in place.  A recall call that filters through the object
+// (Fused::Filter) sees a whole Update or none of it
+class ItemAttrs {
+ public:
+  // tags [n_items] or empty (all 0); born [n_items] or empty (the object has no birth times)
+  ItemAttrs(int64_t n_items, const std::vector<uint64_t>& tags = {}, const std::vector<int64_t>& born = {}) : n_items_(n_items) {
+    if ((!tags.empty() && (int64_t)tags.size() != n_items) || (!born.empty() && (int64_t)born.size() != n_items))
+      throw std::invalid_argument("ItemAttrs: tags and born take one entry per item");
+    check(goctr_itemattr_create(n_items, tags.empty() ? nullptr : tags.data(), born.empty() ? nullptr : born.data(), &h_));
+  }
+  ItemAttrs(const ItemAttrs&) = delete;
+  ItemAttrs& operator=(const ItemAttrs&) = delete;
+  ItemAttrs(ItemAttrs&& o) noexcept : h_(o.h_), n_items_(o.n_items_) { o.h_ = nullptr; }
+  ~ItemAttrs() { goctr_itemattr_destroy(h_); }
+  goctr_itemattr* handle() const { return h_; }
+  int64_t n_items() const { return n_items_; }
+  bool has_born() const { int32_t b = 0; check(goctr_itemattr_info(h_, nullptr, &b, nullptr)); return b != 0; }
+  uint64_t version() const { uint64_t v = 0; check(goctr_itemattr_info(h_, nullptr, nullptr, &v)); return v; }
+  // tags'[j] = (tags[j] & every and_mask of j's entries) | every or_mask of them; born[j] = the born of j's entries.  Each of the three
+  // columns is empty (and_mask: all ones, or_mask: 0, born: unchanged) or holds one entry per item of `items`
+  void Update(const std::vector<int32_t>& items, const std::vector<uint64_t>& and_mask = {}, const std::vector<uint64_t>& or_mask = {},
+              const std::vector<int64_t>& born = {}) {
+    for (size_t n : {and_mask.size(), or_mask.size(), born.size()})
+      if (n && n != items.size()) throw std::invalid_argument("ItemAttrs::Update: one entry per updated item");
+    check(goctr_itemattr_update(h_, items.data(), (int64_t)items.size(), and_mask.empty() ? nullptr : and_mask.data(),
+                                or_mask.empty() ? nullptr : or_mask.data(), born.empty() ? nullptr : born.data()));
+  }
+  // the number of eligible items under every predicate (none may carry GOCTR_PRED_BORN_BEFORE_TS): the selectivity probe
+  std::vector<int64_t> Count(const std::vector<goctr_item_pred>& preds) const {
+    std::vector<int64_t> out(preds.size());
+    check(goctr_itemattr_count(h_, preds.data(), (int32_t)preds.size(), out.data()));
+    return out;
+  }
+  void Export(std::vector<uint64_t>& tags, std::vector<int64_t>* born = nullptr) const {
+    tags.resize((size_t)n_items_);
+    if (born) born->resize((size_t)n_items_);
+    check(goctr_itemattr_export(h_, tags.data(), born ? born->data() : nullptr));
+  }
+
+ private:
+  goctr_itemattr* h_ = nullptr; int64_t n_items_ = 0;
+};
+
 // Up to 7 recall channels for the same request rows, their lists merged by rank (goctr_fuse_recall / goctr_recommend_fused):
 // reciprocal rank fusion or a round robin, a weight and a guaranteed quota (`reserve`) per channel, and per candidate a bit mask of
 // the channels that found it.  The object borrows its handles: they must outlive the calls.  A channel's own cfg is copied
@@ -1195,6 +1239,15 @@ class Fused {
     return push(GOCTR_FUSE_LIST, n_list, weight, reserve, nullptr, nullptr, nullptr, 0);
   }
   size_t channels() const { return chan_.size(); }
+  // Only items eligible under the request row's predicate are returned from here on (goctr_fuse_recall_filtered /
+  // goctr_recommend_fused_filtered).  `attrs` is borrowed; preds holds one predicate for every row, or with an empty pred_of one per
+  // request row of the later call, or pred_of [nq] indexes it.  ClearFilter undoes it
+  Fused& Filter(const ItemAttrs& attrs, const std::vector<goctr_item_pred>& preds, const std::vector<int32_t>& pred_of = {}) {
+    if (preds.empty()) throw std::invalid_argument("Fused::Filter: at least one predicate");
+    attrs_ = attrs.handle(); preds_ = preds; pred_of_ = pred_of;
+    return *this;
+  }
+  Fused& ClearFilter() { attrs_ = nullptr; preds_.clear(); pred_of_.clear(); return *this; }
 
   // the fused candidates alone: items / w / src [nq, cfg.n_cand] (src: the channel masks, 255 = unused), count [nq]
   void Recall(goctr_ubcache* cache, const std::vector<int32_t>& users, const std::vector<int64_t>& ts, const goctr_recall_cfg& rcfg,
@@ -1203,7 +1256,8 @@ class Fused {
     const size_t nq = users.size(), nc = (size_t)std::max(rcfg.n_cand, 1);
     const std::vector<goctr_fuse_channel> c = bound(nq);
     items.resize(nq * nc); w.resize(nq * nc); src.resize(nq * nc); count.resize(nq);
-    check(goctr_fuse_recall(c.data(), (int32_t)c.size(), cache, users.data(), ts.empty() ? nullptr : ts.data(), (int64_t)nq, &rcfg, &cfg_,
+    const goctr_item_filter flt = filter(nq);
+    check(goctr_fuse_recall_filtered(attrs_ ? &flt : nullptr, c.data(), (int32_t)c.size(), cache, users.data(), ts.empty() ? nullptr : ts.data(), (int64_t)nq, &rcfg, &cfg_,
                             items.data(), w.data(), src.data(), count.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
   }
 
@@ -1225,7 +1279,8 @@ class Fused {
     if (masks) masks->resize((size_t)nq * k);
     TopN out;
     if (!targets.empty()) out.target_rank.resize((size_t)nq);
-    check(goctr_recommend_fused(net.Vm(), rs.handle(), c.data(), (int32_t)c.size(), users.data(), ts.empty() ? nullptr : ts.data(), nq,
+    const goctr_item_filter flt = filter((size_t)nq);
+    check(goctr_recommend_fused_filtered(attrs_ ? &flt : nullptr, net.Vm(), rs.handle(), c.data(), (int32_t)c.size(), users.data(), ts.empty() ? nullptr : ts.data(), nq,
                                 targets.empty() ? nullptr : targets.data(), &rcfg, &cfg_, rerank ? rerank->handle() : nullptr, mcfg, k,
                                 pass_rows, items.data(), scores.data(), count.data(), masks ? masks->data() : nullptr, nullptr, nullptr,
                                 targets.empty() ? nullptr : out.target_rank.data(), nullptr, nullptr, nullptr, nullptr, &out.n_failed,
@@ -1258,6 +1313,14 @@ class Fused {
     }
     return c;
   }
+  // the filter of a call over nq rows (no Filter: the entries are handed a null filter and run the unfiltered call)
+  goctr_item_filter filter(size_t nq) const {
+    if (attrs_ && !pred_of_.empty() && pred_of_.size() != nq) throw std::invalid_argument("Fused: pred_of holds one entry per request row");
+    return goctr_item_filter{attrs_, preds_.data(), (int32_t)preds_.size(), pred_of_.empty() ? nullptr : pred_of_.data()};
+  }
+  goctr_itemattr* attrs_ = nullptr;
+  std::vector<goctr_item_pred> preds_;
+  std::vector<int32_t> pred_of_;
   goctr_fuse_cfg cfg_;
   std::vector<goctr_fuse_channel> chan_;
   std::vector<AnyCfg> cfgs_;

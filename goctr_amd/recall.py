@@ -37,6 +37,10 @@ over the ``nprobe`` lists whose centres lie nearest the request vector instead o
 merges their lists by rank (reciprocal rank fusion or a round robin), with a weight and a guaranteed quota per channel and a bit
 mask of the channels that found every item (tests/fuse_ref.py is the host restatement).  ``recommend.RecommendFused`` ranks the
 result with the model.
+
+``ItemAttrs`` holds 64 tag bits (and optionally a birth time) per item in HBM, updated in place, and ``fuse(..., attrs=, preds=,
+pred_of=)`` returns only the items that are eligible under the request row's predicate (``make_pred``): the rule is applied inside
+the kernels that cut a list, so a list refills from deeper places (tests/filter_ref.py is the host restatement).
 """
 from __future__ import annotations
 
@@ -809,16 +813,124 @@ def check_fuse_cfg(fcfg: capi.FuseCfg) -> capi.FuseCfg:
     return fcfg
 
 
-def fuse(channels, ubc, users, ts=None, targets=None, cfg: capi.RecallCfg | None = None, fcfg: capi.FuseCfg | None = None, **kw) -> dict:
+_PRED_FIELDS = _fields(capi.ItemPred)
+PRED_FLAGS = {"born_min": capi.PRED_BORN_MIN, "born_max": capi.PRED_BORN_MAX, "born_before_ts": capi.PRED_BORN_BEFORE_TS}
+_U64 = (1 << 64) - 1
+
+
+def make_pred(**kw) -> capi.ItemPred:
+    """goctr_item_pred from keywords: require_all, require_any, forbid (64-bit masks; a negative integer is taken modulo 2^64),
+    born_min / born_max (each sets its flag), born_before_ts=True (the flag), or flags given outright"""
+    unknown = set(kw) - _PRED_FIELDS - {"born_before_ts"}
+    if unknown:
+        raise TypeError(f"goctr_item_pred has no field {sorted(unknown)}")
+    p = capi.ItemPred()
+    for name in ("require_all", "require_any", "forbid"):
+        setattr(p, name, _as_int(name, kw.get(name, 0)) & _U64)
+    flags = _as_int("flags", kw.get("flags", 0))
+    for name in ("born_min", "born_max"):
+        if name in kw:
+            setattr(p, name, _as_int(name, kw[name]))
+            flags |= PRED_FLAGS[name]
+    if kw.get("born_before_ts"):
+        flags |= capi.PRED_BORN_BEFORE_TS
+    p.flags = flags
+    return p
+
+
+def _pred_array(preds):
+    preds = [preds] if isinstance(preds, capi.ItemPred) else list(preds)
+    if not preds or not all(isinstance(p, capi.ItemPred) for p in preds):
+        raise TypeError("preds takes one capi.ItemPred (make_pred) or a non-empty sequence of them")
+    return (capi.ItemPred * len(preds))(*preds)
+
+
+class ItemAttrs(_Handle):
+    """goctr_itemattr: one uint64 of caller-defined tag bits per item, and with ``born`` one int64 birth time per item on the
+    cache's timestamp scale, resident in HBM and updated in place.  A recall call that filters through it sees a whole update or
+    none of it"""
+    _destroy = "goctr_itemattr_destroy"
+
+    def __init__(self, n_items: int, tags=None, born=None):
+        self.n_items = _as_int("n_items", n_items)
+        tags = None if tags is None else np.ascontiguousarray(tags, np.uint64).ravel()
+        born = None if born is None else np.ascontiguousarray(born, np.int64).ravel()
+        if (tags is not None and tags.size != self.n_items) or (born is not None and born.size != self.n_items):
+            raise ValueError("tags and born take one entry per item")
+        self.has_born = born is not None
+        self._h = C.c_void_p()
+        capi.init()
+        capi.check(capi.load().goctr_itemattr_create(C.c_int64(self.n_items), capi.ptr(tags, C.c_uint64), capi.ptr(born, C.c_int64),
+                                                     C.byref(self._h)))
+
+    def info(self) -> dict:
+        n, hb, ver = C.c_int64(), C.c_int32(), C.c_uint64()
+        capi.check(capi.load().goctr_itemattr_info(self._h, C.byref(n), C.byref(hb), C.byref(ver)))
+        return dict(n_items=n.value, has_born=bool(hb.value), version=ver.value)
+
+    def export(self) -> dict:
+        out = dict(tags=_unwritten(self.n_items, np.uint64))
+        if self.has_born:
+            out["born"] = _unwritten(self.n_items, np.int64)
+        capi.check(capi.load().goctr_itemattr_export(self._h, _ptr(out["tags"]), _ptr(out.get("born"))))
+        return out
+
+    def update(self, items, and_mask=None, or_mask=None, born=None) -> "ItemAttrs":
+        """tags'[j] = (tags[j] & every and_mask of j's entries) | every or_mask of them; born[j] = born of j's entries"""
+        items = capi.i32(items).ravel()
+        cols = [None if a is None else np.ascontiguousarray(a, dt).ravel()
+                for a, dt in ((and_mask, np.uint64), (or_mask, np.uint64), (born, np.int64))]
+        if any(a is not None and a.size != items.size for a in cols):
+            raise ValueError("and_mask, or_mask and born take one entry per updated item")
+        capi.check(capi.load().goctr_itemattr_update(self._h, capi.ptr(items, C.c_int32), C.c_int64(items.size),
+                                                     capi.ptr(cols[0], C.c_uint64), capi.ptr(cols[1], C.c_uint64),
+                                                     capi.ptr(cols[2], C.c_int64)))
+        return self
+
+    def count(self, preds) -> np.ndarray:
+        """the number of eligible items under each predicate (no BORN_BEFORE_TS: there is no request row): int64 [n_pred]"""
+        arr = _pred_array(preds)
+        out = _unwritten(len(arr), np.int64)
+        capi.check(capi.load().goctr_itemattr_count(self._h, arr, C.c_int32(len(arr)), _ptr(out)))
+        return out
+
+
+def item_filter(attrs, preds, pred_of, nq):
+    """the three filter keywords of a call as (a reference to a goctr_item_filter or None, what must stay alive during the call).
+    attrs None: no filter (preds and pred_of must then be None too).  preds: one predicate, or a sequence -- with pred_of None
+    it holds 1 entry (every row) or nq (row q takes preds[q]); pred_of int32 [nq] indexes it"""
+    if attrs is None:
+        if preds is not None or pred_of is not None:
+            raise TypeError("preds and pred_of need attrs")
+        return None, None
+    if preds is None:
+        raise TypeError("attrs needs preds")
+    arr = _pred_array(preds)
+    if pred_of is not None:
+        pred_of = capi.i32(pred_of).ravel()
+        if pred_of.size != nq:
+            raise ValueError("pred_of takes one entry per request row")
+        if pred_of.min() < 0 or pred_of.max() >= len(arr):
+            raise ValueError(f"pred_of holds a value outside [0, {len(arr)})")
+    elif len(arr) not in (1, nq):
+        raise ValueError(f"without pred_of preds holds 1 or n_req = {nq} predicates, not {len(arr)}")
+    flt = capi.ItemFilter(getattr(attrs, "_h", attrs), arr, len(arr), capi.ptr(pred_of, C.c_int32))
+    return C.byref(flt), (flt, arr, pred_of, attrs)
+
+
+def fuse(channels, ubc, users, ts=None, targets=None, cfg: capi.RecallCfg | None = None, fcfg: capi.FuseCfg | None = None,
+         attrs: ItemAttrs | None = None, preds=None, pred_of=None, **kw) -> dict:
     """goctr_fuse_recall over DENSE user rows of ``ubc``'s image (None: no history, nothing seen): every ``Channel``'s list for the
     rows, merged by rank.  ``kw``: goctr_recall_cfg fields and goctr_fuse_cfg's (mode -- also "rrf" / "round_robin" --, rrf_k).
     dict(items int32 [nq, n_cand] (-1 = unused), w uint32 [nq, n_cand], src uint8 [nq, n_cand] (bit c: channel c holds the item; 255 =
     unused), count int32 [nq], target_pos int32 [nq] when targets are given, s uint64 [nq, n_cand] (the full sums), chan_count int32
     [nq, n_chan], chan_target_pos int32 [nq, n_chan] (-1 throughout without targets), chan_items: a list of int32 [nq, n_list_c],
-    the channels' own lists)"""
+    the channels' own lists).  With ``attrs`` (an ``ItemAttrs``) it is goctr_fuse_recall_filtered: only items eligible under the
+    row's predicate are returned (``item_filter`` says how preds and pred_of name it)"""
     cfg, fcfg = _split_kw(cfg, fcfg, kw, _FUSE_FIELDS, make_fuse_cfg)
     users, ts, targets = request_columns(users, ts, targets)
     nq = users.size
+    flt, _alive = item_filter(attrs, preds, pred_of, nq)
     arr, n_chan = fuse_channels(channels, nq, int(cfg.n_cand))
     check_fuse_cfg(fcfg)
     out = _recall_buffers(nq, cfg.n_cand, targets, src=True)
@@ -826,7 +938,10 @@ def fuse(channels, ubc, users, ts=None, targets=None, cfg: capi.RecallCfg | None
                chan_target_pos=_unwritten((nq, n_chan), np.int32),
                chan_items=[_unwritten((nq, a.n_list), np.int32) for a in arr])
     lists = (C.POINTER(C.c_int32) * n_chan)(*(_ptr(a) for a in out["chan_items"]))
-    capi.check(capi.load().goctr_fuse_recall(arr, C.c_int32(n_chan), _cache_handle(ubc), *_request_args(users, ts), C.byref(cfg),
-                                             C.byref(fcfg), *_recall_args(out, targets), _ptr(out["s"]), _ptr(out["chan_count"]),
-                                             _ptr(out["chan_target_pos"]), lists))
+    args = (arr, C.c_int32(n_chan), _cache_handle(ubc), *_request_args(users, ts), C.byref(cfg), C.byref(fcfg),
+            *_recall_args(out, targets), _ptr(out["s"]), _ptr(out["chan_count"]), _ptr(out["chan_target_pos"]), lists)
+    if flt is None:
+        capi.check(capi.load().goctr_fuse_recall(*args))
+    else:
+        capi.check(capi.load().goctr_fuse_recall_filtered(flt, *args))
     return out

@@ -30,7 +30,7 @@ from . import capi, metrics, sampling
 from .recall import (ALS, EXCLUDE, _USERVEC_FIELDS, _USERVEC_IVF_FIELDS, _USERVEC_MULTI_FIELDS, _WALK_FIELDS, ItemCF, ItemVectors, Popular,
                      WalkGraph, _as_int, _cfg_or_kw, _ptr, _request_args, _split_kw, _unwritten, extra_columns, make_mmr_cfg,
                      make_recall_cfg, make_uservec_cfg, make_uservec_ivf_cfg, make_uservec_multi_cfg, make_walk_cfg, merge,
-                     request_columns, Channel, _FUSE_FIELDS, check_fuse_cfg, fuse_channels, make_fuse_cfg)
+                     request_columns, Channel, _FUSE_FIELDS, check_fuse_cfg, fuse_channels, make_fuse_cfg, ItemAttrs, item_filter, make_pred)
 
 # recommend/rcmd.go:19-28
 SampleAssembler = 16
@@ -553,6 +553,7 @@ _OUTPUTS = {
     "goctr_recommend_als": _RANKED,
     "goctr_recommend_blend_als": _BLENDED + ("obj", "pen", "target_place"),
     "goctr_recommend_fused": _BLENDED + ("obj", "pen", "target_place"),
+    "goctr_recommend_fused_filtered": _BLENDED + ("obj", "pen", "target_place"),
 }
 # key: (dtype, entries per request row -- "k", "n_cand" or one --, what the call must have for the array to exist)
 _COLUMNS = {
@@ -752,21 +753,26 @@ def blend_als(model: Predictor, icf, pop, factors, users, ts=None, targets=None,
 
 
 def fused(model: Predictor, channels, users, ts=None, targets=None, k=10, vectors=None, pool=64, lambda_q=192, max_per_group=0,
-          pass_rows=0, validate=False, recall_cfg=None, fcfg=None, **recall_kw):
+          pass_rows=0, validate=False, recall_cfg=None, fcfg=None, attrs=None, preds=None, pred_of=None, **recall_kw):
     """goctr_recommend_fused over DENSE indices: ``itemcf`` with the lists of up to 7 ``channels`` (recall.Channel) fused by rank as the
     recall stage; with ``vectors`` the MMR selection of ``diverse`` is the last step (pool, lambda_q, max_per_group).  The dict of
     ``blend``, or of ``diverse``, with src / cand_src holding channel MASKS (bit c: channel c's list holds the item; 255 = unused).
     ``recall_kw``: goctr_recall_cfg fields and goctr_fuse_cfg's (mode -- also "rrf" / "round_robin" --, rrf_k).  Every channel field
-    and the two sums are checked before the library is reached.  What RecommendFused / RecommendFusedBatch /
-    EvaluateLeaveOneOutFused call."""
+    and the two sums are checked before the library is reached.  With ``attrs`` (recall.ItemAttrs) it is
+    goctr_recommend_fused_filtered: only items eligible under the row's predicate are recalled (recall.item_filter says how
+    ``preds`` and ``pred_of`` name it).  What RecommendFused / RecommendFusedBatch / EvaluateLeaveOneOutFused call."""
     cfg, fcfg = _split_kw(recall_cfg, fcfg, recall_kw, _FUSE_FIELDS, make_fuse_cfg)
     users, ts, targets = request_columns(users, ts, targets)
+    flt, _alive = item_filter(attrs, preds, pred_of, users.size)
     arr, n_chan = fuse_channels(channels, users.size, int(cfg.n_cand))
     check_fuse_cfg(fcfg)
     mcfg = None if vectors is None else make_mmr_cfg(k=k, pool=pool, lambda_q=lambda_q, max_per_group=max_per_group)
     head = (*_request_head(model), arr, C.c_int32(n_chan), *_request_args(users, ts), capi.ptr(targets, C.c_int32), C.byref(cfg),
             C.byref(fcfg), vectors._h if vectors is not None else None, C.byref(mcfg) if mcfg is not None else None,
             *_k_pass(k, pass_rows))
+    if flt is not None:
+        return _ranked_call("goctr_recommend_fused_filtered", (flt, *head), users.size, k, cfg.n_cand, targets, validate,
+                            mmr=mcfg is not None)
     return _ranked_call("goctr_recommend_fused", head, users.size, k, cfg.n_cand, targets, validate, mmr=mcfg is not None)
 
 
@@ -1381,26 +1387,30 @@ def EvaluateLeaveOneOutALS(model: Predictor, factors=None, k=10, sample_kw=None,
 
 
 def RecommendFusedBatch(model: Predictor, channels, userIds, n=10, now=None, vectors=None, lambda_q=192, pool=64, max_per_group=0,
-                        **recall_kw):
+                        attrs=None, preds=None, pred_of=None, **recall_kw):
     """RecommendFused for several users in one device call: [[ItemScore]] in the order of userIds.  ``now``: one timestamp for all,
-    or one per user.  A ``Channel.rows`` channel takes DENSE item rows, one row per user in the order of userIds."""
+    or one per user.  A ``Channel.rows`` channel takes DENSE item rows, one row per user in the order of userIds; ``pred_of`` and
+    per-row ``preds`` follow the same order."""
     users, ts = _request_rows(model, userIds, now)
     return _serve(model, users.size, lambda: fused(model, channels, users, ts, None, n, vectors, pool, lambda_q, max_per_group,
-                                                   **recall_kw))
+                                                   attrs=attrs, preds=preds, pred_of=pred_of, **recall_kw))
 
 
 def RecommendFused(model: Predictor, channels, userId: int, n=10, now=None, vectors=None, lambda_q=192, pool=64, max_per_group=0,
-                   **recall_kw):
+                   attrs=None, preds=None, pred_of=None, **recall_kw):
     """EXTENSION -- N-channel recall merged by rank, then rank: every ``recall.Channel`` of ``channels`` (ItemCF, random walks, user
     vectors over the catalogue or an index, ALS fold-in, the popularity list, a list of the caller's; at most 7) proposes its own
     list for the user, the lists are fused on the device by reciprocal rank fusion (``mode`` "rrf": an item's sum of weight /
     (rrf_k + place) over the channels that found it) or a round robin, a channel's first ``reserve`` entries are guaranteed a place
     among the ``n_cand`` fused candidates, the model scores those and the ``n`` best come back.  With ``vectors`` the diversity
-    re-rank of RecommendDiverse is the last step."""
-    return RecommendFusedBatch(model, channels, [userId], n, now, vectors, lambda_q, pool, max_per_group, **recall_kw)[0]
+    re-rank of RecommendDiverse is the last step.  With ``attrs`` (recall.ItemAttrs over DENSE item indices) and ``preds`` only items
+    eligible under the predicate are recalled: in stock, one market, not a withdrawn brand."""
+    return RecommendFusedBatch(model, channels, [userId], n, now, vectors, lambda_q, pool, max_per_group, attrs, preds, pred_of,
+                               **recall_kw)[0]
 
 
-def EvaluateLeaveOneOutFused(model: Predictor, channels, k=10, sample_kw=None, details=False, pass_rows=0, **recall_kw):
+def EvaluateLeaveOneOutFused(model: Predictor, channels, k=10, sample_kw=None, details=False, pass_rows=0, attrs=None, preds=None,
+                             pred_of=None, born_before_ts=False, **recall_kw):
     """EvaluateLeaveOneOutRecall's protocol and figures over the FUSED candidates (goctr_recommend_fused), plus what the call's
     provenance masks say about every channel -- all from the one call, over the users whose held-out item is a row of the item table:
         chan_recall[c]   the share of users whose target is a fused candidate that channel c's list holds
@@ -1409,12 +1419,24 @@ def EvaluateLeaveOneOutFused(model: Predictor, channels, k=10, sample_kw=None, d
     A target a channel found but the cut dropped from the fused list counts for nobody: with n_cand at or above the sum of the
     channels' n_list nothing is cut.  The channels' handles should be built without the held-out entries for an honest figure; that
     is the caller's choice.  Returns EvaluateLeaveOneOutRecall's dict plus the three lists; details=True adds the columns and the
-    target's mask per row (``target_mask``, 0 = not recalled)."""
+    target's mask per row (``target_mask``, 0 = not recalled).  ``attrs`` / ``preds`` / ``pred_of`` filter as in ``fused`` (a held-out
+    item that is ineligible counts as not recalled); ``born_before_ts=True`` is the no-time-travel evaluation: every predicate
+    (none given: an open one) also demands that a candidate's birth time in ``attrs`` is not after the key's timestamp."""
     users, targets, ts = _held_out_rows(model, sample_kw)
     recall_kw.setdefault("exclude", "before")
     cfg, fcfg = _split_kw(None, None, recall_kw, _FUSE_FIELDS, make_fuse_cfg)
     channels = list(channels)
-    r = fused(model, channels, users, ts, targets, k, pass_rows=pass_rows, validate=True, recall_cfg=cfg, fcfg=fcfg)
+    if born_before_ts:
+        if attrs is None:
+            raise TypeError("born_before_ts needs attrs with birth times")
+        given = [make_pred()] if preds is None else [preds] if isinstance(preds, capi.ItemPred) else list(preds)
+        preds = []
+        for p in given:
+            q = capi.ItemPred.from_buffer_copy(p)
+            q.flags |= capi.PRED_BORN_BEFORE_TS
+            preds.append(q)
+    r = fused(model, channels, users, ts, targets, k, pass_rows=pass_rows, validate=True, recall_cfg=cfg, fcfg=fcfg, attrs=attrs,
+              preds=preds, pred_of=pred_of)
     n_items = model.recSys.item_table.shape[0]
     out = _loo_figures(r, targets, n_items, k, cfg.n_cand)
     ok = (targets >= 0) & (targets < n_items)

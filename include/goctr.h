@@ -1455,6 +1455,83 @@ int goctr_recommend_fused(goctr_model* m, goctr_recsys* r, const goctr_fuse_chan
                           int32_t* cand_items, uint32_t* cand_w, float* cand_scores, uint8_t* cand_src, int64_t* n_failed,
                           int32_t* out_obj, uint32_t* out_pen, int32_t* out_target_place);
 
+/* ---- Eligibility filters for recall: item tags and per-request predicates (no reference counterpart).  Which items a recall may
+ * RETURN at all -- in stock, one market, not a withdrawn brand, published before the request -- is request-time state: a
+ * goctr_itemattr holds one 64-bit word of caller-defined tag bits per item in HBM, and optionally one int64 birth time per item on
+ * the cache's timestamp scale, and is updated in place.  A request row names a predicate over them; the two _filtered entries apply
+ * it inside the kernels that cut a list to its length, so a list refills from deeper places.  tests/filter_ref.py restates it all.
+ *
+ *   eligible       item j is eligible for request row q iff 0 <= j < n_items and, with p the row's predicate and t = tags[j]:
+ *                  (t & p.require_all) == p.require_all;  p.require_any == 0 or (t & p.require_any) != 0;  (t & p.forbid) == 0;
+ *                  under GOCTR_PRED_BORN_MIN born[j] >= p.born_min;  under GOCTR_PRED_BORN_MAX born[j] <= p.born_max;  under
+ *                  GOCTR_PRED_BORN_BEFORE_TS born[j] <= ts[q] when ts[q] != 0 (ts[q] == 0, "from the newest", leaves it open)
+ *   update         tags'[j] = (tags[j] & AND of and_mask[i] over the i with items[i] == j) | OR of or_mask[i] over the same i: all
+ *                  the ANDs are applied, then all the ORs, so a repeated item is well defined and nothing depends on the order of
+ *                  arrival.  born[items[i]] = born[i].  version += 1
+ *   count          out_count[p] = the number of items eligible under preds[p]: the selectivity probe
+ *   refused        (-1, nothing touched, the error text set) create: n_items <= 0 or > 2^31 - 1.  update: an item outside
+ *                  [0, n_items); born on a handle created without birth times; an item repeated with two different born values;
+ *                  n < 0.  count and the filtered entries: n_pred < 1, reserved != 0, a flag that is no GOCTR_PRED_*, any BORN flag on
+ *                  a handle without birth times; count also refuses GOCTR_PRED_BORN_BEFORE_TS (there is no request row)
+ * Concurrency: a recall call that uses the handle holds a reader lock on it from staging its predicates until its kernels have
+ * drained; goctr_itemattr_update takes the writer side, so a call sees a whole update or none of it.  Lock order: model lock,
+ * embedding lock, cache lock, attribute lock; an update takes the engine's lock and the attribute lock alone. */
+typedef struct goctr_itemattr goctr_itemattr;
+enum { GOCTR_PRED_BORN_MIN = 1, GOCTR_PRED_BORN_MAX = 2, GOCTR_PRED_BORN_BEFORE_TS = 4 };
+typedef struct {
+  uint64_t require_all;   /* (tags & require_all) == require_all                 */
+  uint64_t require_any;   /* 0: no condition; else (tags & require_any) != 0     */
+  uint64_t forbid;        /* (tags & forbid) == 0                                */
+  int64_t  born_min, born_max;   /* read only under their flags: born_min <= born[j] <= born_max */
+  uint32_t flags;         /* GOCTR_PRED_*; BORN_BEFORE_TS: born[j] <= ts[q] when ts[q] != 0 */
+  uint32_t reserved;      /* must be 0 */
+} goctr_item_pred;        /* 48 bytes */
+typedef struct {
+  goctr_itemattr* attrs;            /* NULL: no filter; preds, n_pred and pred_of are then ignored */
+  const goctr_item_pred* preds;     /* host [n_pred] */
+  int32_t n_pred;                   /* >= 1 */
+  const int32_t* pred_of;           /* host [n_req] in [0, n_pred), or NULL: n_pred == 1 (all rows) or n_pred == n_req (row q takes preds[q]) */
+} goctr_item_filter;
+int  goctr_itemattr_create(int64_t n_items, const uint64_t* tags /*[n_items] or NULL = all 0*/,
+                           const int64_t* born /*[n_items] or NULL = the handle has no birth times*/, goctr_itemattr** out);
+void goctr_itemattr_destroy(goctr_itemattr* h);
+int  goctr_itemattr_info(goctr_itemattr* h, int64_t* n_items, int32_t* has_born, uint64_t* version);   /* each may be NULL */
+int  goctr_itemattr_export(goctr_itemattr* h, uint64_t* tags, int64_t* born);                          /* each may be NULL */
+int  goctr_itemattr_update(goctr_itemattr* h, const int32_t* items, int64_t n, const uint64_t* and_mask /* or NULL = ~0 */,
+                           const uint64_t* or_mask /* or NULL = 0 */, const int64_t* born /* or NULL = unchanged */);
+int  goctr_itemattr_count(goctr_itemattr* h, const goctr_item_pred* preds, int32_t n_pred, int64_t* out_count /*[n_pred]*/);
+
+/* goctr_fuse_recall / goctr_recommend_fused under a filter.  A fused call with one channel returns that channel's stand-alone
+ * bytes, so these two are the filtered form of every recall entry.
+ *   a channel's list   for every kind L_c is the channel's list under the unfiltered rules taken to full length, with the entries
+ *                  that are ineligible for the row removed, cut at n_list_c.  The filter decides only what may be RETURNED:
+ *                  histories, pooled vectors, the fold-in and the probed lists of an index are unchanged, and walks pass through
+ *                  ineligible items.  (An index probed with a small nprobe under a selective filter returns short lists.)
+ *   POPULAR, LIST  an ineligible entry is skipped exactly as a seen one is; reserve counts kept entries
+ *   targets        a target that is ineligible for its row counts as no target for that row: no seen-exemption, out_target_pos,
+ *                  chan_target_pos (and out_target_rank, out_target_place) are -1
+ *   no filter      flt == NULL, flt->attrs == NULL or predicates that are all zeros: every output byte equals the unfiltered entry's
+ *   cost           a predicate is evaluated per distinct candidate inside the ItemCF, walk and fuse kernels (8 bytes of tags, 16
+ *                  with born); for the user-vector, index and ALS channels the ineligible items are ORed into the row's seen
+ *                  bitmap: a predicate is evaluated over the catalogue ONCE per call, except for the rows whose predicate carries
+ *                  GOCTR_PRED_BORN_BEFORE_TS and whose ts is not 0, which cost a pass over born each
+ *   refused        (-1, nothing touched) the unfiltered entry's refusals; attrs->n_items different from the handles' (the
+ *                  recsys's); n_pred < 1; a NULL pred_of with n_pred neither 1 nor n_req; a pred_of value outside [0, n_pred);
+ *                  a NULL preds; the predicate refusals above; attrs created on another engine */
+int goctr_fuse_recall_filtered(const goctr_item_filter* flt, const goctr_fuse_channel* chan, int32_t n_chan, goctr_ubcache* c,
+                               const int32_t* users, const int64_t* ts, int64_t n_req, const goctr_recall_cfg* recall_cfg,
+                               const goctr_fuse_cfg* fuse_cfg, int32_t* out_items, uint32_t* out_w, uint8_t* out_src,
+                               int32_t* out_count, const int32_t* targets, int32_t* out_target_pos, uint64_t* out_s,
+                               int32_t* chan_count, int32_t* chan_target_pos, int32_t* const* chan_items);
+int goctr_recommend_fused_filtered(const goctr_item_filter* flt, goctr_model* m, goctr_recsys* r, const goctr_fuse_channel* chan,
+                                   int32_t n_chan, const int32_t* users, const int64_t* ts, int64_t n_req, const int32_t* targets,
+                                   const goctr_recall_cfg* recall_cfg, const goctr_fuse_cfg* fuse_cfg, goctr_itemvec* v,
+                                   const goctr_mmr_cfg* cfg, int32_t k, int64_t pass_rows, int32_t* out_items, float* out_scores,
+                                   int32_t* out_count, uint8_t* out_src, int32_t* out_cand_count, int32_t* out_target_pos,
+                                   int64_t* out_target_rank, int32_t* cand_items, uint32_t* cand_w, float* cand_scores,
+                                   uint8_t* cand_src, int64_t* n_failed, int32_t* out_obj, uint32_t* out_pen,
+                                   int32_t* out_target_place);
+
 /* The replica a multi-device training call (cfg.devices = n) keeps on engine `rank` (rank 0: the handle itself); NULL before
  * the first such call.  Borrowed: owned by the handle it was asked from.  For checks that the replicas are bit-identical
  * (tests, bench.py's replica checksum) -- every entry point works on it, on its own engine. */
