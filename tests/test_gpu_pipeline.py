@@ -16,6 +16,7 @@ import os
 import numpy as np
 import pytest
 
+from optim_cases import near_zero_scheme
 from test_gpu_fullsize import LOGIT_TOL, LOSS_TOL, models, synth
 
 pytestmark = pytest.mark.gpu
@@ -61,14 +62,9 @@ def _free_running_steps_vs_oracle(oracle, kind, U, T, D, Cc, V, B, steps, seed, 
     pairs = [("mlp0", "W0"), ("mlp1", "W1"), ("mlp2", "W2")] + ([("att0", "att0")] if kind == 0 else [])
     for dn, on in pairs:
         d = np.abs(dm.get_weights(dn).reshape(getattr(om, on).shape) - getattr(om, on))
-        out = d > 1e-5
-        frac, unexplained = float(out.mean()), int(np.sum(out & ~near_zero[on]))
-        print(f"  {on}: max {d.max():.2e}  q99.9 {np.quantile(d, 0.999):.2e}  entries > 1e-5: {int(out.sum())} ({frac:.2%}), "
-              f"of them NOT near a zero gradient: {unexplained};  near-zero entries {float(near_zero[on].mean()):.2%}")
-        # every entry the two runs disagree on passed, at some step, within float32 noise of a zero gradient ...
-        assert unexplained == 0, (on, unexplained)
-        # ... and there are few of them
-        assert np.quantile(d, 0.999) <= 1e-5 or frac <= 0.01, (on, frac)
+        # every entry the two runs disagree on passed, at some step, within float32 noise of a zero gradient, and there are few of
+        # them (the rule tests/test_gpu_optim.py applies with other Adam cfgs)
+        near_zero_scheme(on, d, near_zero[on], 1e-5)
     if kind == 0:
         assert np.max(np.abs(dm.get_weights("att0").ravel() - om.att0.ravel())) <= 1e-6
 
