@@ -228,6 +228,17 @@ class WalkCfg(C.Structure):
                 ("seed", C.c_uint64), ("reserved", C.c_int64)]
 
 
+class UsercfCfg(C.Structure):
+    """goctr_usercf_cfg (include/goctr.h)"""
+    _fields_ = [("max_holders", C.c_int32), ("n_nbr", C.c_int32), ("min_overlap", C.c_int32), ("reserved", C.c_int32),
+                ("seed", C.c_uint64)]
+
+
+class UsercfRecallCfg(C.Structure):
+    """goctr_usercf_recall_cfg (include/goctr.h)"""
+    _fields_ = [("n_use", C.c_int32), ("per_user", C.c_int32)]
+
+
 class AlsCfg(C.Structure):
     """goctr_als_cfg (include/goctr.h)"""
     _fields_ = [("D", C.c_int32), ("n_iters", C.c_int32), ("alpha", C.c_double), ("lambda_", C.c_double), ("seed", C.c_uint64),
@@ -322,7 +333,7 @@ NS_ALL, NS_NEWEST, NS_ALL_BUT_NEWEST = 0, 1, 2              # goctr_negsample_cf
 CALIB_STEP, CALIB_LINEAR = 0, 1                             # goctr_calib_cfg.interp
 UVMIX_MAX, UVMIX_QUOTA = 0, 1                               # goctr_uservec_multi_cfg.mix
 (FUSE_ITEMCF, FUSE_WALK, FUSE_USERVEC, FUSE_USERVEC_IVF, FUSE_ALS, FUSE_POPULAR,
- FUSE_LIST) = range(7)                                      # goctr_fuse_channel.kind
+ FUSE_LIST, FUSE_USERCF) = range(8)                         # goctr_fuse_channel.kind
 FUSE_RRF, FUSE_ROUND_ROBIN = 0, 1                           # goctr_fuse_cfg.mode
 FUSE_MAX_CHAN, FUSE_MAX_LISTED = 7, 4096                    # n_chan, the sum of n_list
 PRED_BORN_MIN, PRED_BORN_MAX, PRED_BORN_BEFORE_TS = 1, 2, 4 # goctr_item_pred.flags
@@ -392,6 +403,8 @@ SYMBOLS = [
     "goctr_fuse_cfg_default", "goctr_fuse_recall", "goctr_recommend_fused",
     "goctr_itemattr_create", "goctr_itemattr_destroy", "goctr_itemattr_info", "goctr_itemattr_export", "goctr_itemattr_update",
     "goctr_itemattr_count", "goctr_fuse_recall_filtered", "goctr_recommend_fused_filtered",
+    "goctr_usercf_cfg_default", "goctr_usercf_build", "goctr_usercf_destroy", "goctr_usercf_info", "goctr_usercf_export",
+    "goctr_usercf_recall_cfg_default", "goctr_usercf_recall", "goctr_recommend_usercf",
 ]
 
 _lib = None
@@ -421,7 +434,7 @@ def load() -> C.CDLL:
                      "goctr_calib_cfg_default", "goctr_calibrator_destroy", "goctr_boot_cfg_default",
                      "goctr_walkgraph_cfg_default", "goctr_walk_cfg_default", "goctr_walkgraph_destroy",
                      "goctr_als_cfg_default", "goctr_als_destroy", "goctr_ease_cfg_default", "goctr_fuse_cfg_default",
-                     "goctr_itemattr_destroy"):
+                     "goctr_itemattr_destroy", "goctr_usercf_cfg_default", "goctr_usercf_recall_cfg_default", "goctr_usercf_destroy"):
             getattr(_lib, name).restype = None
         _bm = C.POINTER(BinaryMetrics)
         _lib.goctr_metrics_binary.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, _bm]
@@ -572,6 +585,18 @@ def load() -> C.CDLL:
                                                     C.c_void_p, _wk, C.c_int32, C.POINTER(RecallCfg), C.c_int32, C.c_void_p, _mmr,
                                                     C.c_int32, C.c_int64, _i32, _f32, _i32, _u8, _i32, _i32, _i64, _i32, _u32, _f32,
                                                     _u8, _i64, _i32, _u32, _i32]
+        _uc, _ur = C.POINTER(UsercfCfg), C.POINTER(UsercfRecallCfg)
+        _lib.goctr_usercf_cfg_default.argtypes = [_uc]
+        _lib.goctr_usercf_recall_cfg_default.argtypes = [_ur]
+        _lib.goctr_usercf_build.argtypes = [C.c_void_p, _uc, C.POINTER(C.c_void_p)]
+        _lib.goctr_usercf_destroy.argtypes = [C.c_void_p]
+        _lib.goctr_usercf_info.argtypes = [C.c_void_p, _i64, _i64, _i32, _u64, _u64]
+        _lib.goctr_usercf_export.argtypes = [C.c_void_p, _u32, _i32, _u32, _u32]
+        _lib.goctr_usercf_recall.argtypes = [C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, C.POINTER(RecallCfg), _ur, _i32, _u32, _i32,
+                                             _i32, _i32]
+        _lib.goctr_recommend_usercf.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32,
+                                                C.POINTER(RecallCfg), _ur, C.c_int32, C.c_int64, _i32, _f32, _i32, _i32, _i32, _i64,
+                                                _i32, _u32, _f32, _i64]
         _als, _f64, _i16 = C.POINTER(AlsCfg), C.POINTER(C.c_double), C.POINTER(C.c_int16)
         _lib.goctr_als_cfg_default.argtypes = [_als]
         _lib.goctr_als_create.argtypes = [C.c_void_p, _als, C.POINTER(C.c_void_p)]
@@ -759,6 +784,8 @@ default_list_cfg = _default(ListCfg, "goctr_list_cfg_default")
 default_popular_cfg = _default(PopularCfg, "goctr_popular_cfg_default")
 default_walkgraph_cfg = _default(WalkGraphCfg, "goctr_walkgraph_cfg_default")
 default_walk_cfg = _default(WalkCfg, "goctr_walk_cfg_default")
+default_usercf_cfg = _default(UsercfCfg, "goctr_usercf_cfg_default")
+default_usercf_recall_cfg = _default(UsercfRecallCfg, "goctr_usercf_recall_cfg_default")
 default_als_cfg = _default(AlsCfg, "goctr_als_cfg_default")
 default_fuse_cfg = _default(FuseCfg, "goctr_fuse_cfg_default")
 ALS_USERS, ALS_ITEMS = 0, 1                 # goctr_als_step's sides

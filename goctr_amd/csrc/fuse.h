@@ -3,6 +3,7 @@
 // semantics ("Fusion of N recall channels by rank"); tests/fuse_ref.py restates them.
 #pragma once
 #include "popular.h"
+#include "usercf.h"
 #include "uservec_ivf.h"
 
 namespace goctr {

@@ -4,7 +4,8 @@
 // tests/fuse_ref.py restates them on the host, bit for bit).  All arithmetic is integer.
 //
 // Launches of one call, back to back on one stream (FuseStage::launch):
-//   the model channels' own launchers (recall_launch, walk_launch, uservec_launch, uservec_ivf_launch, als_launch), unchanged, each
+//   the model channels' own launchers (recall_launch, walk_launch, uservec_launch, uservec_ivf_launch, als_launch, usercf_launch),
+//   unchanged, each
 //   into a scratch list of its own at stride n_list -- the bytes the channel's stand-alone entry returns
 //   fuse_kernel    one workgroup per request row:
 //     1. a POPULAR or LIST channel's entries are walked in tiles of SEL_THREADS source positions as blend_fill_kernel walks its
@@ -204,9 +205,9 @@ __global__ __launch_bounds__(SEL_THREADS) void fuse_kernel(FuseKernelArgs a, Fil
   }
 }
 
-bool fuse_is_model(int kind) { return kind >= GOCTR_FUSE_ITEMCF && kind <= GOCTR_FUSE_ALS; }
+bool fuse_is_model(int kind) { return (kind >= GOCTR_FUSE_ITEMCF && kind <= GOCTR_FUSE_ALS) || kind == GOCTR_FUSE_USERCF; }
 
-// the engine, the items and (a walk graph's, else -1) the users of a channel's handle; LIST has none
+// the engine, the items and (a walk graph's or user neighbour lists', else -1) the users of a channel's handle; LIST has none
 void fuse_handle_info(const goctr_fuse_channel& ch, Engine** eng, long long* n_items, long long* n_users) {
   *eng = nullptr; *n_items = -1; *n_users = -1;
   switch (ch.kind) {
@@ -220,6 +221,11 @@ void fuse_handle_info(const goctr_fuse_channel& ch, Engine** eng, long long* n_i
     case GOCTR_FUSE_USERVEC_IVF: { auto h = static_cast<const goctr_itemvec_index*>(ch.handle); *eng = h->eng; *n_items = h->n_items; break; }
     case GOCTR_FUSE_ALS: { auto h = static_cast<const goctr_als*>(ch.handle); *eng = h->eng; *n_items = h->n_items; break; }
     case GOCTR_FUSE_POPULAR: { auto h = static_cast<const goctr_popular*>(ch.handle); *eng = h->eng; *n_items = h->n_items; break; }
+    case GOCTR_FUSE_USERCF: {
+      auto h = static_cast<const goctr_usercf*>(ch.handle);
+      *eng = h->eng; *n_items = h->n_items; *n_users = h->n_users;
+      break;
+    }
     default: break;
   }
 }
@@ -231,7 +237,7 @@ namespace goctr {
 Engine* fuse_engine(const goctr_fuse_channel* chan, int n_chan) {
   if (!chan || n_chan < 1 || n_chan > FUSE_MAX_CHAN) return nullptr;
   for (int c = 0; c < n_chan; ++c) {
-    if (chan[c].kind < GOCTR_FUSE_ITEMCF || chan[c].kind > GOCTR_FUSE_POPULAR || !chan[c].handle) continue;
+    if (chan[c].kind < GOCTR_FUSE_ITEMCF || chan[c].kind > GOCTR_FUSE_USERCF || chan[c].kind == GOCTR_FUSE_LIST || !chan[c].handle) continue;
     Engine* e; long long ni, nu;
     fuse_handle_info(chan[c], &e, &ni, &nu);
     return e;
@@ -248,13 +254,13 @@ int fuse_check(const char* who, const goctr_fuse_channel* chan, int n_chan, cons
   long long sum_list = 0, sum_reserve = 0;
   for (int c = 0; c < n_chan; ++c) {
     const goctr_fuse_channel& ch = chan[c];
-    GOCTR_CHECK(ch.kind >= GOCTR_FUSE_ITEMCF && ch.kind <= GOCTR_FUSE_LIST, "%s: channel %d: kind = %d is no GOCTR_FUSE_* kind", who, c, ch.kind);
+    GOCTR_CHECK(ch.kind >= GOCTR_FUSE_ITEMCF && ch.kind <= GOCTR_FUSE_USERCF, "%s: channel %d: kind = %d is no GOCTR_FUSE_* kind", who, c, ch.kind);
     GOCTR_CHECK(ch.n_list >= 1 && ch.n_list <= 1024, "%s: channel %d: n_list = %d is outside 1 .. 1024", who, c, ch.n_list);
     GOCTR_CHECK(ch.weight <= 65535u, "%s: channel %d: weight = %u is outside 0 .. 65535", who, c, ch.weight);
     GOCTR_CHECK(ch.reserve >= 0 && ch.reserve <= ch.n_list, "%s: channel %d: reserve = %d is outside 0 .. n_list = %d", who, c, ch.reserve,
                 ch.n_list);
-    const bool is_list = ch.kind == GOCTR_FUSE_LIST, is_als = ch.kind == GOCTR_FUSE_ALS;
-    const bool takes_cfg = ch.kind == GOCTR_FUSE_WALK || ch.kind == GOCTR_FUSE_USERVEC || ch.kind == GOCTR_FUSE_USERVEC_IVF || is_als;
+    const bool is_list = ch.kind == GOCTR_FUSE_LIST, is_als = ch.kind == GOCTR_FUSE_ALS, is_ucf = ch.kind == GOCTR_FUSE_USERCF;
+    const bool takes_cfg = ch.kind == GOCTR_FUSE_WALK || ch.kind == GOCTR_FUSE_USERVEC || ch.kind == GOCTR_FUSE_USERVEC_IVF || is_als || is_ucf;
     GOCTR_CHECK((ch.handle != nullptr) == !is_list, "%s: channel %d: %s", who, c, is_list ? "a LIST channel takes no handle" : "the handle is missing");
     GOCTR_CHECK((ch.handle2 != nullptr) == is_als, "%s: channel %d: %s", who, c,
                 is_als ? "the ALS channel's item vectors (handle2) are missing" : "handle2 belongs to an ALS channel alone");
@@ -264,6 +270,7 @@ int fuse_check(const char* who, const goctr_fuse_channel* chan, int n_chan, cons
     if (ch.kind == GOCTR_FUSE_WALK && walk_check_cfg(static_cast<const goctr_walk_cfg*>(ch.cfg), who)) return -1;
     if ((ch.kind == GOCTR_FUSE_USERVEC || is_als) && uservec_check_cfg(static_cast<const goctr_uservec_cfg*>(ch.cfg), who)) return -1;
     if (ch.kind == GOCTR_FUSE_USERVEC_IVF && uservec_ivf_check_cfg(static_cast<const goctr_uservec_ivf_cfg*>(ch.cfg), who)) return -1;
+    if (is_ucf && usercf_check_cfg(static_cast<const goctr_usercf_recall_cfg*>(ch.cfg), who)) return -1;
     if (is_list) continue;
     Engine* e; long long ni, nu;
     fuse_handle_info(ch, &e, &ni, &nu);
@@ -277,8 +284,8 @@ int fuse_check(const char* who, const goctr_fuse_channel* chan, int n_chan, cons
     GOCTR_CHECK(n_items < 0 || ni == n_items, "%s: channel %d covers %lld items, the others (or the recsys) %lld", who, c, ni, n_items);
     n_items = ni;
     if (nu >= 0) {
-      GOCTR_CHECK(n_users < 0 || nu == n_users, "%s: channel %d: the walk graph has %lld users, the cache (or another graph) %lld", who, c,
-                  nu, n_users);
+      GOCTR_CHECK(n_users < 0 || nu == n_users, "%s: channel %d: the %s %lld users, the cache (or another handle) %lld", who, c,
+                  is_ucf ? "user neighbour lists cover" : "walk graph has", nu, n_users);
       n_users = nu;
     }
   }
@@ -341,6 +348,9 @@ int FuseStage::launch(const FuseArgs& f, const RecallCall& r0, const RecallRows&
         case GOCTR_FUSE_USERVEC_IVF:
           rc = uservec_ivf_launch(static_cast<const goctr_itemvec_index*>(ch.handle), x, *static_cast<const goctr_uservec_ivf_cfg*>(ch.cfg),
                                   rows, nullptr, ivf_ws[c], st);
+          break;
+        case GOCTR_FUSE_USERCF:
+          rc = usercf_launch(static_cast<const goctr_usercf*>(ch.handle), x, *static_cast<const goctr_usercf_recall_cfg*>(ch.cfg), rows, st);
           break;
         default:
           rc = als_launch(static_cast<const goctr_als*>(ch.handle), static_cast<const goctr_itemvec*>(ch.handle2), x,

@@ -23,6 +23,7 @@
 #include <memory>
 
 #include "itemcf_build.h"
+#include "recall_tiles.h"
 #include "ubcache.h"
 
 using namespace goctr;
@@ -128,21 +129,9 @@ struct IcfScratch : IcfReduceScratch {
 // --------------------------------------------------------------------------------------------------------------- recall
 // One workgroup per request row.
 //   1. the history: the first H valid entries the timestamp filter keeps, in sequence order (lds_gather_history)
-//   2. the row's n_h * M list entries are summed per candidate in an LDS hash table (RC_TABLE slots, linear probing, the item
-//      claimed by a compare-and-swap, the weight added by an atomic: an integer sum, so the arrival order cannot show).  The
-//      table holds at most RC_LIMIT candidates, so the candidates are taken in TILES, ranges [lo, hi) of item ids: a range is
-//      accumulated whole -- every entry of the row's lists whose item falls in it -- and a range that overflows is dropped and
-//      split in two.  A candidate's sum is complete whatever range it came in, so no output depends on the tiling.
-//   3. the sequence entries the exclusion mode looks at mark their table slot (bit 31 of the slot's item)
-//   4. the table's candidates join the row's running list by the key (S << 32) | ~item (lds_lists.h: sel_append / sel_sort_trim)
-constexpr int RC_TABLE_BITS = 13, RC_LIMIT = 6144, RC_STACK = 48;
-using RcTable = LdsItemTable<RC_TABLE_BITS>;
-constexpr int RC_TABLE = RcTable::SIZE;
-constexpr unsigned int RC_EMPTY = RcTable::EMPTY;
-constexpr int RC_MAX_H = 256, RC_MAX_CAND = 1024;
-static_assert(SEL_CAP >= RC_MAX_CAND + SEL_THREADS, "a trimmed list and one tile of the table must fit");
-static_assert(RC_LIMIT + SEL_THREADS < RC_TABLE, "threads that pass the limit together must still find free slots");
-static_assert(RC_TABLE % SEL_THREADS == 0, "the table is read in whole tiles");
+//   2. to 4. the row's n_h * M list entries are summed per candidate and the candidates that are not seen join the row's list:
+//      rc_tiles (recall_tiles.h, shared with usercf.hip's ucf_recall_kernel) -- the LDS table, its tiles, the seen marks, the list
+constexpr int RC_MAX_H = 256;
 
 struct RecallArgs {
   const long long* off; const int32_t* seq_items; const long long* seq_ts;   // the cache's image (null: no cache)
@@ -180,80 +169,20 @@ __global__ __launch_bounds__(SEL_THREADS) void icf_recall_kernel(RecallArgs a, F
   const int nh = lds_gather_history<SEL_THREADS / 64>(a.seq_items, a.seq_ts, lo_e, len, mts, a.n_items, a.H, hist, wcnt);
   const int n_entries = nh * a.M;
   const int step_t = SEL_THREADS / a.M, step_c = SEL_THREADS - step_t * a.M;
-  if (tid == 0) {
-    s_fill = 0; s_thr = 0ull; s_sp = 0; s_tpos = -1;
-    if (n_entries > 0) {                       // the first tiles: equal ranges, few enough entries each on average
-      const int parts = (n_entries + RC_LIMIT - 1) / RC_LIMIT;
-      const long long width = (a.n_items + parts - 1) / parts;
-      for (int p = parts - 1; p >= 0; --p) {
-        const long long lo = p * width, hi = lo + width < a.n_items ? lo + width : a.n_items;
-        if (lo < hi) { st_lo[s_sp] = (int)lo; st_hi[s_sp] = (int)hi; ++s_sp; }
-      }
-    }
-  }
-  __syncthreads();
-
-  while (s_sp > 0) {                           // (uniform: read behind a barrier)
-    const int lo = st_lo[s_sp - 1], hi = st_hi[s_sp - 1];
-    __syncthreads();                           // everyone has read the top
-    if (tid == 0) { --s_sp; s_distinct = 0; s_over = 0; }
-    for (int i = tid; i < RC_TABLE; i += SEL_THREADS) { tkey[i] = RC_EMPTY; tsum[i] = 0u; }
-    __syncthreads();
-    // 2. accumulate the range
-    // entry e = list position c of history entry t; (t, c) advance by the stride's quotient and remainder: no division per entry
+  const RcLds s{tkey, tsum, skey, sraw, st_lo, st_hi, &s_sp, &s_fill, &s_distinct, &s_over, &s_tpos, &s_thr};
+  const RcRow r{a.seq_items, a.seq_ts, lo_e, len, mts, a.n_items, a.n_cand, a.exclude, has_t, tgt};
+  // 2. to 4.  entry e = list position c of history entry t; (t, c) advance by the stride's quotient and remainder: no division per entry
+  rc_tiles<FILT>(s, r, n_entries, f, pred, [&](int lo, int hi) {
     int t = tid / a.M, c = tid - t * a.M;
     for (int e = tid; e < n_entries; e += SEL_THREADS, t += step_t, c += step_c) {
       if (c >= a.M) { c -= a.M; ++t; }
-      if (*(volatile int*)&s_over) break;
+      if (rc_over(s)) break;
       const long long at = (long long)hist[t] * a.M + c;
       const int j = a.nbr_items[at];
       if (j < lo || j >= hi) continue;         // (padding is -1 < lo)
-      const unsigned int w = a.nbr_w[at];
-      bool fresh;
-      const unsigned int slot = RcTable::claim(tkey, (unsigned int)j, &fresh);
-      if (fresh && atomicAdd(&s_distinct, 1) >= RC_LIMIT) s_over = 1;
-      atomicAdd(&tsum[slot], w);
+      rc_add(s, j, a.nbr_w[at]);
     }
-    __syncthreads();
-    if (s_over) {                              // (uniform) too many candidates for one tile: halve the range
-      if (tid == 0) {                          // (hi - lo >= 2: one item is one candidate; depth <= 31 + the first tiles)
-        const int mid = lo + (hi - lo) / 2;
-        st_lo[s_sp] = mid; st_hi[s_sp] = hi; ++s_sp;
-        st_lo[s_sp] = lo; st_hi[s_sp] = mid; ++s_sp;
-      }
-      __syncthreads();
-      continue;
-    }
-    // 3. seen
-    if (a.exclude != GOCTR_TOPN_KEEP_SEEN) {
-      const bool before = a.exclude == GOCTR_TOPN_DROP_SEEN_BEFORE;
-      for (long long p = tid; p < len; p += SEL_THREADS) {
-        const int it = a.seq_items[lo_e + p];
-        if (it < lo || it >= hi || it >= a.n_items) continue;
-        if (before && mts != 0 && a.seq_ts[lo_e + p] > mts) continue;
-        RcTable::mark_seen(tkey, (unsigned int)it);
-      }
-      __syncthreads();
-    }
-    // 4. the tile's candidates join the running list
-    for (int s0 = 0; s0 < RC_TABLE; s0 += SEL_THREADS) {
-      const unsigned long long thr = s_thr;
-      const unsigned int k = tkey[s0 + tid];
-      unsigned long long key = 0ull;
-      if (k != RC_EMPTY) {
-        const unsigned int j = k & 0x7fffffffu;
-        if (!(k >> 31) || (has_t && (int)j == tgt)) {
-          key = ((unsigned long long)tsum[s0 + tid] << 32) | (unsigned long long)(~j);
-          if (key <= thr) key = 0ull;
-          if constexpr (FILT) { if (key != 0ull && !item_eligible(f, *pred, (long long)j, mts)) key = 0ull; }
-        }
-      }
-      sel_append(skey, sraw, &s_fill, &s_thr, a.n_cand, key, 0u);
-    }
-    __syncthreads();
-  }
-
-  sel_sort_trim(skey, sraw, &s_fill, &s_thr, a.n_cand);
+  });
   sel_write_row(skey, s_fill, a.n_cand, q * a.stride, q, has_t, tgt, &s_tpos, a.out_items, a.out_w, a.out_count, a.out_tpos);
 }
 

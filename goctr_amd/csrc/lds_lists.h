@@ -1,5 +1,5 @@
 // lds_lists.h -- the device building blocks the recall and list kernels share (topn.hip, itemcf.hip, popular.hip, itemnbr.hip,
-// rerank.hip, uservec.hip, uservec_multi.hip, fuse.hip): lists of u64 order keys in LDS, places within a workgroup, a table of
+// rerank.hip, uservec.hip, uservec_multi.hip, fuse.hip, usercf.hip): lists of u64 order keys in LDS, places within a workgroup, a table of
 // items in LDS.
 // The bit-exact tests rest on three rules, each kept here once:
 //   - a list is ordered by its keys alone.  Keys of one list are distinct and 0 means "no entry"; the lists are sorted by ONE

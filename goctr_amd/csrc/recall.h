@@ -1,7 +1,7 @@
 // recall.h -- what a recall call is, whatever channel answers it (ItemCF itemcf.h, the blend popular.h, random walks walk.h, user
-// vectors uservec*.h, ALS als.h): the request as the launchers take it, the rows a recall stage fills, and the two drivers every
-// entry goes through -- recall_only_run for the stand-alone goctr_*_recall entries, recall_rank_run for the goctr_recommend_*
-// entries, which serve.hip runs under with_scorer's slot (topn.h: TopnScorer).  Both drivers are in itemcf.hip.
+// vectors uservec*.h, ALS als.h, UserCF usercf.h): the request as the launchers take it, the rows a recall stage fills, and the two
+// drivers every entry goes through -- recall_only_run for the stand-alone goctr_*_recall entries, recall_rank_run for the
+// goctr_recommend_* entries, which serve.hip runs under with_scorer's slot (topn.h: TopnScorer).  Both drivers are in itemcf.hip.
 //
 // A channel brings a launcher of the shape (handle(s), const RecallCall&, its own cfg, const RecallRows& out, its extras as ONE
 // struct when there is more than one, scratch, stream) and hands it to a driver as a RecallStage.

@@ -6,8 +6,9 @@
 //   ub_entry_keys_kernel (itemcf_build.h, shared with walk.hip) one wavefront per user: (u << 32 | i) of every considered entry, the
 //                        sentinel elsewhere; one sort, the heads, and a scan whose sink writes every distinct (u, i) as
 //                        (i << 32 | key(i,u)) -> u and counts cnt[i]
-//   holders              a stable sort by (i, key) leaves every item's users by key, then u; sw_keep_kernel cuts each run at
-//                        max_users and a second sort by (i << 32 | u) orders what is kept: H [n_h], item i's list at hoff[i]
+//   holders              holder_lists (holders.h, shared with usercf.hip): a stable sort by (i, key) leaves every item's users by
+//                        key, then u; sw_keep_kernel cuts each run at max_users and a second sort by (i << 32 | u) orders what is
+//                        kept: H [n_h], item i's list at hoff[i]
 //   sw_nup_kernel        per user the user pairs in which it is the smaller: its position in each of its items' lists
 //   per group of consecutive smaller users whose user pairs fit the budget
 //     sw_upcount_kernel  + scan: every H entry's pairs inside the group, their offsets
@@ -26,8 +27,7 @@
 #include <memory>
 #include <vector>
 
-#include "itemcf_build.h"
-#include "negsample.h"
+#include "holders.h"
 #include "ubcache.h"
 
 using namespace goctr;
@@ -46,30 +46,15 @@ struct SwDistinctSink {
   __device__ __forceinline__ void operator()(long long e, unsigned int head, u64 rank) const {
     if (!head) return;
     const u64 key = keys[e], u = key >> 32, i = key & 0xffffffffull;
-    hk[rank] = (i << 32) | (ns_mix(seed ^ ns_mix((i << 32) | u)) >> 32);
+    hk[rank] = (i << 32) | holder_key(seed, i, u);
     hv[rank] = (unsigned int)u;
     atomicAdd(cnt + i, 1u);
   }
 };
 
-struct SwCapMap {
-  unsigned int cap;
-  __device__ __forceinline__ unsigned int operator()(unsigned int v) const { return v < cap ? v : cap; }
-};
-
 struct SwOvMap {
   __device__ __forceinline__ u64 operator()(unsigned int v) const { return sw_emitted(v); }
 };
-
-// entries by (i, key, u); coff = exclusive prefix of cnt: the first max_users of every item's run stay
-__global__ __launch_bounds__(256) void sw_keep_kernel(const u64* __restrict__ hk, const unsigned int* __restrict__ hv, long long n,
-                                                      const u64* __restrict__ coff, unsigned int max_users, u64 sentinel,
-                                                      u64* __restrict__ out) {
-  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (e >= n) return;
-  const u64 i = hk[e] >> 32;
-  out[e] = (u64)e - coff[i] < (u64)max_users ? (i << 32) | (u64)hv[e] : sentinel;
-}
 
 // H entry e = (i << 32 | u) at place p of item i's list of len users: the len - 1 - p users behind it are its partners
 __device__ __forceinline__ unsigned int sw_partners(u64 h, long long e, const u64* hoff, const unsigned int* cnt, unsigned int max_users) {
@@ -239,9 +224,9 @@ __global__ __launch_bounds__(256) void sw_weight_kernel(const u64* __restrict__ 
 }
 
 // scratch of one build (declared in front of the cache hold, so that an error return drains the stream before it is freed)
-struct SwScratch : IcfReduceScratch {
-  DevBuf<u64> keys, keys_sorted, hk, hk_sorted, H, coff, hoff, nup, uoff, gk, gk_sorted, eoff, cuts, n_cuts, n_pairs, rowmax;
-  DevBuf<unsigned int> hv, hv_sorted, c, gv, gv_sorted, ovh;
+struct SwScratch : IcfReduceScratch, HolderBufs {
+  DevBuf<u64> keys, keys_sorted, nup, uoff, gk, gk_sorted, eoff, cuts, n_cuts, n_pairs, rowmax;
+  DevBuf<unsigned int> c, gv, gv_sorted, ovh;
   DevBuf<u64> ek, ev, ek_sorted, ev_sorted;
   DevBuf<u64> a_keys, a_val, p_keys, p_val, m_keys, m_val, m_keys_sorted, m_val_sorted, start;
   DevBuf<char> temp;
@@ -360,16 +345,8 @@ int goctr_itemcf_build_swing(goctr_ubcache* c, int64_t n_items, const goctr_swin
   std::vector<u64> pre((size_t)nu + 1, 0);    // pre[u] = the user pairs whose smaller user is below u
   if (n_d) {
     const long long nd = (long long)n_d;
-    if (ws.hk_sorted.alloc((size_t)nd, false) || ws.hv_sorted.alloc((size_t)nd, false) || ws.H.alloc((size_t)nd, false) ||
-        ws.coff.alloc((size_t)n_items, false) || ws.hoff.alloc((size_t)n_items, false) || ws.nup.alloc((size_t)nu)) return -1;
-    if (radix_sort_pairs(ws.temp, ws.hk.p, ws.hk_sorted.p, ws.hv.p, ws.hv_sorted.p, (size_t)nd, item_bits, s)) return -1;
-    if (exclusive_scan<u64>(r->cnt.p, n_items, ws.coff.p, ws.tiles, ws.total.p)) return -1;
-    hipLaunchKernelGGL(sw_keep_kernel, grid256(nd), dim3(256), 0, s, ws.hk_sorted.p, ws.hv_sorted.p, nd, ws.coff.p, max_users,
-                       item_sentinel, ws.hk.p);
-    GOCTR_HIP(hipGetLastError());
-    if (radix_sort_keys(ws.temp, ws.hk.p, ws.H.p, (size_t)nd, item_bits, s)) return -1;
-    if (exclusive_scan_sink<u64>(r->cnt.p, n_items, ws.tiles, ws.total.p, SwCapMap{max_users}, ScanStore<u64>{ws.hoff.p})) return -1;
-    if (ws.total.download(&n_h, 1)) return -1;
+    if (holder_lists(ws, ws.temp, ws.tiles, ws.total, r->cnt.p, nd, n_items, max_users, item_bits, item_sentinel, &n_h, s)) return -1;
+    if (ws.nup.alloc((size_t)nu)) return -1;
     // 3. the passes
     hipLaunchKernelGGL(sw_nup_kernel, grid256((long long)n_h), dim3(256), 0, s, ws.H.p, (long long)n_h, ws.hoff.p, r->cnt.p, max_users,
                        ws.nup.p);

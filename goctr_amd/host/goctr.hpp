@@ -1032,6 +1032,70 @@ inline TopN RecommendWalkBatch(model::CtrNet& net, RecSys& rs, const WalkGraph& 
   return out;
 }
 
+// every user's nearest users by item overlap (goctr_usercf_build over a WalkGraph) and their newest items as a recall channel
+// (goctr_usercf_recall): the lists are fixed at the build, the items are read from the live cache image of every call
+class UserCF {
+ public:
+  static goctr_usercf_cfg DefaultCfg() { goctr_usercf_cfg c; goctr_usercf_cfg_default(&c); return c; }
+  static goctr_usercf_recall_cfg DefaultRecallCfg() { goctr_usercf_recall_cfg c; goctr_usercf_recall_cfg_default(&c); return c; }
+  static UserCF Build(const WalkGraph& graph, const goctr_usercf_cfg& cfg = DefaultCfg()) {
+    UserCF u;
+    check(goctr_usercf_build(graph.handle(), &cfg, &u.h_));
+    return u;
+  }
+  UserCF(const UserCF&) = delete;
+  UserCF& operator=(const UserCF&) = delete;
+  UserCF(UserCF&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  ~UserCF() { goctr_usercf_destroy(h_); }
+  goctr_usercf* handle() const { return h_; }
+  struct Info { int64_t n_users, n_items; int32_t n_nbr; uint64_t pairs, cache_version; };
+  Info info() const {
+    Info i{};
+    check(goctr_usercf_info(h_, &i.n_users, &i.n_items, &i.n_nbr, &i.pairs, &i.cache_version));
+    return i;
+  }
+  // "similar users": nbr_users / nbr_w / nbr_ov [n_users, n_nbr] (-1 / 0 / 0 = unused), deg [n_users]
+  void Export(std::vector<uint32_t>& deg, std::vector<int32_t>& nbr_users, std::vector<uint32_t>& nbr_w, std::vector<uint32_t>& nbr_ov) const {
+    const Info i = info();
+    const size_t n = (size_t)i.n_users, nm = n * (size_t)i.n_nbr;
+    deg.assign(n, 0u); nbr_users.assign(nm, -1); nbr_w.assign(nm, 0u); nbr_ov.assign(nm, 0u);
+    check(goctr_usercf_export(h_, deg.data(), nbr_users.data(), nbr_w.data(), nbr_ov.data()));
+  }
+  // items / w [nq, cfg.n_cand] (w: the summed neighbour weights), count [nq]; cache may be null (every row is empty)
+  void Recall(goctr_ubcache* cache, const std::vector<int32_t>& users, const std::vector<int64_t>& ts, const goctr_recall_cfg& cfg,
+              std::vector<int32_t>& items, std::vector<uint32_t>& w, std::vector<int32_t>& count,
+              const goctr_usercf_recall_cfg& ucfg = DefaultRecallCfg()) const {
+    if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("UserCF::Recall: one timestamp per user");
+    const size_t nq = users.size(), nc = (size_t)std::max(cfg.n_cand, 1);
+    items.resize(nq * nc); w.resize(nq * nc); count.resize(nq);
+    check(goctr_usercf_recall(h_, cache, users.data(), ts.empty() ? nullptr : ts.data(), (int64_t)nq, &cfg, &ucfg, items.data(), w.data(),
+                              count.data(), nullptr, nullptr));
+  }
+
+ private:
+  UserCF() = default;
+  goctr_usercf* h_ = nullptr;
+};
+
+// RecommendItemCFBatch with the UserCF recall as the recall stage (goctr_recommend_usercf)
+inline TopN RecommendUserCFBatch(model::CtrNet& net, RecSys& rs, const UserCF& ucf, const std::vector<int32_t>& users, int n = 10,
+                                 const std::vector<int64_t>& ts = {}, const goctr_recall_cfg& rcfg = ItemCF::DefaultRecallCfg(),
+                                 const goctr_usercf_recall_cfg& ucfg = UserCF::DefaultRecallCfg(), const std::vector<int32_t>& targets = {},
+                                 int64_t pass_rows = 0) {
+  const int64_t nq = (int64_t)users.size();
+  detail::check_request("RecommendUserCFBatch", users.size(), ts.size(), targets.size(), n);
+  std::vector<int32_t> items((size_t)nq * n), count((size_t)nq);
+  std::vector<float> scores((size_t)nq * n);
+  TopN out;
+  if (!targets.empty()) out.target_rank.resize((size_t)nq);
+  check(goctr_recommend_usercf(net.Vm(), rs.handle(), ucf.handle(), users.data(), ts.empty() ? nullptr : ts.data(), nq,
+                               targets.empty() ? nullptr : targets.data(), &rcfg, &ucfg, n, pass_rows, items.data(), scores.data(),
+                               count.data(), nullptr, nullptr, targets.empty() ? nullptr : out.target_rank.data(), nullptr, nullptr,
+                               nullptr, &out.n_failed));
+  out.lists = detail::gather_lists(items, scores, count, n);
+  return out;
+}
+
 // RecommendBlendBatch with the random-walk recall as the caller's list (goctr_recommend_blend_walk): ItemCF's candidates, the n_walk
 // items the walks visit most (written and read in HBM), then the popularity list; with `rerank` and `mcfg` the diversity re-rank
 // picks the mcfg->k returned
@@ -1230,6 +1294,14 @@ class Fused {
     if (!als.vectors()) throw std::invalid_argument("Fused::Add: the factors have not been fitted");
     return push(GOCTR_FUSE_ALS, n_list, weight, reserve, als.handle(), als.vectors(), &ucfg, sizeof ucfg);
   }
+  Fused& Add(const UserCF& ucf, int n_list, uint32_t weight = 1, int reserve = 0,
+             const goctr_usercf_recall_cfg& ucfg = UserCF::DefaultRecallCfg()) {
+    return push(GOCTR_FUSE_USERCF, n_list, weight, reserve, ucf.handle(), nullptr, &ucfg, sizeof ucfg);
+  }
+  Fused& usercf(const UserCF& ucf, int n_list, uint32_t weight = 1, int reserve = 0,
+                const goctr_usercf_recall_cfg& ucfg = UserCF::DefaultRecallCfg()) {
+    return Add(ucf, n_list, weight, reserve, ucfg);
+  }
   Fused& Add(const Popular& pop, int n_list, uint32_t weight = 1, int reserve = 0) {
     return push(GOCTR_FUSE_POPULAR, n_list, weight, reserve, pop.handle(), nullptr, nullptr, 0);
   }
@@ -1290,7 +1362,7 @@ class Fused {
   }
 
  private:
-  union AnyCfg { goctr_walk_cfg w; goctr_uservec_cfg u; goctr_uservec_ivf_cfg i; };
+  union AnyCfg { goctr_walk_cfg w; goctr_uservec_cfg u; goctr_uservec_ivf_cfg i; goctr_usercf_recall_cfg c; };
   Fused& push(int32_t kind, int n_list, uint32_t weight, int reserve, const void* h, const void* h2, const void* cfg, size_t cfg_bytes) {
     if (chan_.size() >= 7) throw std::invalid_argument("Fused::Add: at most 7 channels");
     AnyCfg a{};

@@ -21,6 +21,11 @@ device, so that a row without history still gets candidates (tests/popular_ref.p
 from a request row's history -- item, holder, one of the holder's items, a few steps at a time -- and ranks the items by where the
 walks land (tests/walk_ref.py is the host restatement).  ``recommend.RecommendWalk`` ranks the result with the model.
 
+``UserCF`` is the user-to-user half of collaborative filtering: every user's nearest users by item overlap, built once from a
+``WalkGraph``, and ``UserCF.recall_users`` sums the neighbours' weights over their newest items in the LIVE cache image, so an
+appended event is a candidate without a rebuild (tests/usercf_ref.py is the host restatement).  ``recommend.RecommendUserCF`` ranks
+the result with the model, ``recommend.SimilarUsers`` returns the neighbours themselves.
+
 ``ItemVectors`` holds the catalogue's quantised vectors (and optionally a group id per item) in HBM, and ``rerank_mmr`` picks k of
 every row's scored candidates greedily, trading relevance against similarity to what it has picked, with a cap per group
 (tests/mmr_ref.py is the host restatement).  ``recommend.RecommendDiverse`` runs it as the last step of RecommendBlend.
@@ -72,6 +77,8 @@ _IVF_FIELDS = _fields(capi.IvfCfg)
 _USERVEC_IVF_FIELDS = _fields(capi.UservecIvfCfg)
 _WALKGRAPH_FIELDS = _fields(capi.WalkGraphCfg)
 _WALK_FIELDS = _fields(capi.WalkCfg)
+_USERCF_FIELDS = _fields(capi.UsercfCfg)
+_USERCF_RECALL_FIELDS = _fields(capi.UsercfRecallCfg)
 _FUSE_FIELDS = _fields(capi.FuseCfg)
 FUSE_MODE = {"rrf": capi.FUSE_RRF, "round_robin": capi.FUSE_ROUND_ROBIN}
 
@@ -112,6 +119,8 @@ make_ivf_cfg = _make("goctr_ivf_cfg", _IVF_FIELDS, capi.default_ivf_cfg)
 make_uservec_ivf_cfg = _make("goctr_uservec_ivf_cfg", _USERVEC_IVF_FIELDS, capi.default_uservec_ivf_cfg)
 make_walkgraph_cfg = _make("goctr_walkgraph_cfg", _WALKGRAPH_FIELDS, capi.default_walkgraph_cfg)
 make_walk_cfg = _make("goctr_walk_cfg", _WALK_FIELDS, capi.default_walk_cfg)
+make_usercf_cfg = _make("goctr_usercf_cfg", _USERCF_FIELDS, capi.default_usercf_cfg)
+make_usercf_recall_cfg = _make("goctr_usercf_recall_cfg", _USERCF_RECALL_FIELDS, capi.default_usercf_recall_cfg)
 
 
 def make_fuse_cfg(**kw) -> capi.FuseCfg:
@@ -417,6 +426,60 @@ class WalkGraph(_Handle):
             out["trace"] = _unwritten((users.size, min(max(int(wcfg.n_walks), 1) * max(int(wcfg.n_steps), 1), 8192)), np.int32)
         capi.check(capi.load().goctr_walk_recall(self._h, _cache_handle(ubc), *_request_args(users, ts), C.byref(cfg), C.byref(wcfg),
                                                  *_recall_args(out, targets), _ptr(out.get("trace"))))
+        return out
+
+
+class UserCF(_Handle):
+    """goctr_usercf: every user's nearest users by item overlap, resident in HBM, immutable after the build and independent of the
+    graph and the cache.  ``recall_users`` reads the neighbours' newest items from the cache image the call holds, so an appended
+    event is a candidate on the next call without a rebuild"""
+    _destroy = "goctr_usercf_destroy"
+
+    def __init__(self, graph: WalkGraph, cfg: capi.UsercfCfg | None = None, **kw):
+        """graph: a WalkGraph (or a raw goctr_walkgraph handle); ``kw``: goctr_usercf_cfg fields (max_holders, n_nbr, min_overlap,
+        seed)"""
+        cfg = _cfg_or_kw(cfg, kw, make_usercf_cfg)
+        self._h = C.c_void_p()
+        capi.check(capi.load().goctr_usercf_build(getattr(graph, "_h", graph), C.byref(cfg), C.byref(self._h)))
+        i = self.info()
+        self.n_users, self.n_items, self.n_nbr = i["n_users"], i["n_items"], i["n_nbr"]
+
+    @classmethod
+    def build(cls, graph: WalkGraph, cfg: capi.UsercfCfg | None = None, **kw) -> "UserCF":
+        return cls(graph, cfg, **kw)
+
+    def info(self) -> dict:
+        nu, ni, m, p, v = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_uint64(0), C.c_uint64(0)
+        capi.check(capi.load().goctr_usercf_info(self._h, C.byref(nu), C.byref(ni), C.byref(m), C.byref(p), C.byref(v)))
+        return dict(n_users=nu.value, n_items=ni.value, n_nbr=m.value, pairs=p.value, cache_version=v.value)
+
+    def export(self) -> dict:
+        """dict(deg uint32 [n_users], nbr_users int32 [n_users, n_nbr] (-1 = unused), nbr_w, nbr_ov uint32 [n_users, n_nbr])"""
+        shape = (self.n_users, self.n_nbr)
+        out = dict(deg=np.zeros(self.n_users, np.uint32), nbr_users=np.full(shape, -1, np.int32), nbr_w=np.zeros(shape, np.uint32),
+                   nbr_ov=np.zeros(shape, np.uint32))
+        capi.check(capi.load().goctr_usercf_export(self._h, capi.ptr(out["deg"], C.c_uint32), capi.ptr(out["nbr_users"], C.c_int32),
+                                                   capi.ptr(out["nbr_w"], C.c_uint32), capi.ptr(out["nbr_ov"], C.c_uint32)))
+        return out
+
+    def neighbours(self, user: int) -> list:
+        """[(user, w, ov)] of DENSE row ``user``, best first (the whole table comes to the host: for many users call export once)"""
+        e, u = self.export(), _as_int("user", user)
+        if not 0 <= u < self.n_users:
+            raise ValueError(f"user = {u} is outside [0, {self.n_users})")
+        n = int((e["nbr_users"][u] >= 0).sum())
+        return [(int(e["nbr_users"][u, k]), int(e["nbr_w"][u, k]), int(e["nbr_ov"][u, k])) for k in range(n)]
+
+    def recall_users(self, ubc, users, ts=None, targets=None, cfg: capi.RecallCfg | None = None,
+                     ucfg: capi.UsercfRecallCfg | None = None, **kw) -> dict:
+        """goctr_usercf_recall over DENSE user rows of ``ubc``'s image (None: no cache, every row is empty).  ``kw``: goctr_recall_cfg
+        fields and goctr_usercf_recall_cfg's (n_use, per_user).  dict(items int32 [nq, n_cand] (-1 = unused), w uint32 [nq, n_cand]
+        (the sums S), count int32 [nq], target_pos int32 [nq] when targets are given)"""
+        cfg, ucfg = _split_kw(cfg, ucfg, kw, _USERCF_RECALL_FIELDS, make_usercf_recall_cfg)
+        users, ts, targets = request_columns(users, ts, targets)
+        out = _recall_buffers(users.size, cfg.n_cand, targets)
+        capi.check(capi.load().goctr_usercf_recall(self._h, None if ubc is None else _cache_handle(ubc), *_request_args(users, ts),
+                                                   C.byref(cfg), C.byref(ucfg), *_recall_args(out, targets)))
         return out
 
 
@@ -765,6 +828,11 @@ class Channel:
         return cls(capi.FUSE_POPULAR, n_list, weight, reserve, pop)
 
     @classmethod
+    def usercf(cls, ucf: "UserCF", n_list, weight=1, reserve=0, ucfg: capi.UsercfRecallCfg | None = None, **kw) -> "Channel":
+        """``UserCF.recall_users``'s list; ``kw``: goctr_usercf_recall_cfg fields"""
+        return cls(capi.FUSE_USERCF, n_list, weight, reserve, ucf, cfg=_cfg_or_kw(ucfg, kw, make_usercf_recall_cfg, "ucfg"))
+
+    @classmethod
     def rows(cls, rows, weight=1, reserve=0) -> "Channel":
         """a list of the caller's per request row: ``rows`` int32 [nq, n_list], -1 = no entry"""
         rows = capi.i32(rows)
@@ -783,8 +851,10 @@ def fuse_channels(channels, nq, n_cand):
     for c, (ch, a) in enumerate(zip(channels, arr)):
         if not isinstance(ch, Channel):
             raise TypeError(f"channel {c} is no recall.Channel")
-        if not capi.FUSE_ITEMCF <= ch.kind <= capi.FUSE_LIST:
+        if not capi.FUSE_ITEMCF <= ch.kind <= capi.FUSE_USERCF:
             raise ValueError(f"channel {c}: kind = {ch.kind} is no capi.FUSE_* kind")
+        if ch.kind == capi.FUSE_USERCF and not isinstance(ch.cfg, capi.UsercfRecallCfg):
+            raise ValueError(f"channel {c}: a USERCF channel takes a goctr_usercf_recall_cfg (Channel.usercf makes one)")
         if not 1 <= ch.n_list <= 1024:
             raise ValueError(f"channel {c}: n_list = {ch.n_list} is outside 1 .. 1024")
         if not 0 <= ch.weight <= 65535:

@@ -27,8 +27,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import capi, metrics, sampling
-from .recall import (ALS, EXCLUDE, _USERVEC_FIELDS, _USERVEC_IVF_FIELDS, _USERVEC_MULTI_FIELDS, _WALK_FIELDS, ItemCF, ItemVectors, Popular,
-                     WalkGraph, _as_int, _cfg_or_kw, _ptr, _request_args, _split_kw, _unwritten, extra_columns, make_mmr_cfg,
+from .recall import (ALS, EXCLUDE, _USERCF_RECALL_FIELDS, _USERVEC_FIELDS, _USERVEC_IVF_FIELDS, _USERVEC_MULTI_FIELDS, _WALK_FIELDS, ItemCF,
+                     ItemVectors, Popular, UserCF, WalkGraph, make_usercf_recall_cfg, _as_int, _cfg_or_kw, _ptr, _request_args, _split_kw, _unwritten, extra_columns, make_mmr_cfg,
                      make_recall_cfg, make_uservec_cfg, make_uservec_ivf_cfg, make_uservec_multi_cfg, make_walk_cfg, merge,
                      request_columns, Channel, _FUSE_FIELDS, check_fuse_cfg, fuse_channels, make_fuse_cfg, ItemAttrs, item_filter, make_pred)
 
@@ -549,6 +549,7 @@ _OUTPUTS = {
     "goctr_recommend_blend_mmr": _BLENDED + ("obj", "pen", "target_place"),
     "goctr_recommend_blend_uservec": _BLENDED + ("obj", "pen", "target_place"),
     "goctr_recommend_walk": _RANKED,
+    "goctr_recommend_usercf": _RANKED,
     "goctr_recommend_blend_walk": _BLENDED + ("obj", "pen", "target_place"),
     "goctr_recommend_als": _RANKED,
     "goctr_recommend_blend_als": _BLENDED + ("obj", "pen", "target_place"),
@@ -700,6 +701,15 @@ def walk(model: Predictor, graph, users, ts=None, targets=None, k=10, pass_rows=
     n_steps, boost, min_visits, seed).  What RecommendWalk / RecommendWalkBatch / EvaluateLeaveOneOutWalk call."""
     cfg, wcfg = _split_kw(recall_cfg, wcfg, recall_kw, _WALK_FIELDS, make_walk_cfg)
     return _uservec_call("goctr_recommend_walk", model, graph, users, ts, targets, k, pass_rows, validate, cfg, wcfg)
+
+
+def usercf(model: Predictor, ucf, users, ts=None, targets=None, k=10, pass_rows=0, validate=False, recall_cfg=None, ucfg=None,
+           **recall_kw):
+    """goctr_recommend_usercf over DENSE indices: ``itemcf`` with the UserCF recall over ``ucf`` (recall.UserCF) as the recall stage;
+    the same dict (cand_w holds the sums S).  ``recall_kw``: goctr_recall_cfg fields and goctr_usercf_recall_cfg's (n_use, per_user).
+    What RecommendUserCF / RecommendUserCFBatch / EvaluateLeaveOneOutUserCF call."""
+    cfg, ucfg = _split_kw(recall_cfg, ucfg, recall_kw, _USERCF_RECALL_FIELDS, make_usercf_recall_cfg)
+    return _uservec_call("goctr_recommend_usercf", model, ucf, users, ts, targets, k, pass_rows, validate, cfg, ucfg)
 
 
 def blend_walk(model: Predictor, icf, pop, graph, users, ts=None, targets=None, n_walk=64, quota_pop=0, k=10, vectors=None, pool=64,
@@ -953,6 +963,29 @@ def RecommendWalk(model: Predictor, graph, userId: int, n=10, now=None, **recall
     return RecommendWalkBatch(model, graph, [userId], n, now, **recall_kw)[0]
 
 
+def RecommendUserCFBatch(model: Predictor, ucf, userIds, n=10, now=None, **recall_kw):
+    """RecommendUserCF for several users in one device call: [[ItemScore]] in the order of userIds.  ``now``: one timestamp for all, or
+    one per user."""
+    users, ts = _request_rows(model, userIds, now)
+    return _serve(model, users.size, lambda: usercf(model, ucf, users, ts, None, n, **recall_kw))
+
+
+def RecommendUserCF(model: Predictor, ucf, userId: int, n=10, now=None, **recall_kw):
+    """EXTENSION -- user-to-user recall, then rank: the first ``n_use`` stored neighbours of the user in ``ucf`` (BuildUserCF) each
+    bring their ``per_user`` newest behaviours at or before ``now`` out of the LIVE behaviour cache, an item scores the sum of the
+    weights of the neighbours' entries that hold it, and the ``n_cand`` best unseen items are scored by the model.  What a neighbour
+    did after the build is a candidate without a rebuild."""
+    return RecommendUserCFBatch(model, ucf, [userId], n, now, **recall_kw)[0]
+
+
+def SimilarUsers(model: Predictor, ucf, userId: int, n=10):
+    """EXTENSION -- look-alike users: [(userId, w, overlap)] of the stored neighbours of ``userId`` in ``ucf`` (BuildUserCF), best
+    first, at most ``n``; w is the cosine of the two users' item sets in units of 2^-16."""
+    row = int(_request_rows(model, [userId], 0)[0][0])
+    raw = {k: u for u, k in model.recSys._uidx.items()}
+    return [(raw[v], w, ov) for v, w, ov in ucf.neighbours(row)[:n]]
+
+
 def RecommendBlendWalkBatch(model: Predictor, icf, pop, graph, userIds, n=10, now=None, n_walk=64, quota_pop=0, vectors=None, pool=64,
                             lambda_q=192, max_per_group=0, **recall_kw):
     """EXTENSION -- RecommendBlendBatch with the random-walk recall as the caller's list: ItemCF's candidates, then the ``n_walk``
@@ -1004,6 +1037,19 @@ def BuildEASE(recSys: DeviceRecSys, graph=None, graph_kw=None, **cfg):
     jointly, so a pair linked only through a hub is not weighted as if the link were direct.  Every RecommendItemCF / RecommendBlend /
     EvaluateLeaveOneOut* / MergeItemCF call takes the handle like BuildItemCF's; it is independent of the graph afterwards."""
     return ItemCF.ease(graph if graph is not None else BuildWalkGraph(recSys, **(graph_kw or {})), **cfg)
+
+
+def BuildUserCF(recSys: DeviceRecSys, graph=None, graph_kw=None, **cfg):
+    """EXTENSION: every user's nearest users by item overlap (recall.UserCF; ``cfg``: goctr_usercf_cfg fields -- max_holders, n_nbr,
+    min_overlap, seed) over ``graph`` (default: BuildWalkGraph of the recSys's cache, ``graph_kw`` its cfg, closed on the way out) --
+    what RecommendUserCF and SimilarUsers read.  The lists are fixed at the build; the items they lead to are the cache's live ones."""
+    if graph is not None:
+        return UserCF(graph, **cfg)
+    own = BuildWalkGraph(recSys, **(graph_kw or {}))
+    try:
+        return UserCF(own, **cfg)
+    finally:
+        own.close()
 
 
 def BuildWalkGraph(recSys: DeviceRecSys, **cfg):
@@ -1349,6 +1395,36 @@ def EvaluateLeaveOneOutWalk(model: Predictor, graph=None, k=10, sample_kw=None, 
         graph = own = BuildWalkGraph(model.recSys, **gkw)
     try:
         r = walk(model, graph, users, ts, targets, k, pass_rows, recall_cfg=cfg, wcfg=wcfg)
+    finally:
+        if own is not None:
+            own.close()
+    out = _loo_figures(r, targets, model.recSys.item_table.shape[0], k, cfg.n_cand)
+    if details:
+        out.update(_details(r, users, targets, ts))
+    return out
+
+
+def EvaluateLeaveOneOutUserCF(model: Predictor, ucf=None, k=10, sample_kw=None, details=False, pass_rows=0, graph_kw=None, build_kw=None,
+                              **recall_kw):
+    """EvaluateLeaveOneOutRecall's protocol and figures with the UserCF recall as the recall stage (goctr_recommend_usercf).  The
+    recall reads a neighbour's entries at or before the row's key timestamp (ts - 1), so it never sees the future; the neighbour
+    LISTS would, if they were built over the held-out events.  ``ucf`` None: the lists are built here (``build_kw``: goctr_usercf_cfg
+    fields) over a graph windowed below the held-out events as EvaluateLeaveOneOutWalk's is (``graph_kw``), and closed on the way out;
+    a caller's own ``ucf`` is used as it is."""
+    users, targets, ts = _held_out_rows(model, sample_kw)
+    recall_kw.setdefault("exclude", "before")
+    cfg, ucfg = _split_kw(None, None, recall_kw, _USERCF_RECALL_FIELDS, make_usercf_recall_cfg)
+    own = None
+    if ucf is None:
+        gkw = dict(graph_kw or {})
+        gkw.setdefault("ts_hi", int((sample_kw or {})["ts_lo"]) - 1 if "ts_lo" in (sample_kw or {}) else int(ts.min()))
+        graph = BuildWalkGraph(model.recSys, **gkw)
+        try:
+            ucf = own = UserCF(graph, **(build_kw or {}))
+        finally:
+            graph.close()
+    try:
+        r = usercf(model, ucf, users, ts, targets, k, pass_rows, recall_cfg=cfg, ucfg=ucfg)
     finally:
         if own is not None:
             own.close()

@@ -748,6 +748,77 @@ int  goctr_walk_recall(goctr_walkgraph* g, goctr_ubcache* c, const int32_t* user
                        const int32_t* targets /*[n_req] or NULL*/, int32_t* out_target_pos /*[n_req] or NULL*/,
                        int32_t* out_trace /*[n_req, n_walks*n_steps] or NULL*/);
 
+/* ---- UserCF recall: user neighbours, then their recent items (no reference counterpart).  Every channel above reaches a candidate
+ * from the request user's own history; this one asks which users are like this one and what they have just taken.  The neighbour
+ * lists of every user are built once from a goctr_walkgraph and stored; the ITEMS come from the neighbours' sequences in the live
+ * image of the cache the recall holds, so an event goctr_ubcache_append adds to a neighbour is a candidate on the next call, with no
+ * rebuild.  goctr_usercf_export answers "similar users" on its own.  Every output is defined bit for bit (tests/usercf_ref.py is the
+ * host restatement): all arithmetic is integer except the weight, which is pinned to correctly rounded double operations as
+ * goctr_itemcf_build's is, and no output byte depends on a tile or chunk size or on the arrival order of atomics (they count
+ * integers).
+ *
+ * goctr_usercf_build:
+ *   I_u, U_i       the graph's sets (goctr_walkgraph_build above): max_len and the timestamp window are the graph's
+ *   deg[u]         |I_u|, uncapped
+ *   holders U'_i   exactly Swing's rule (goctr_itemcf_build_swing above) with max_holders in place of max_users: all of U_i when
+ *                  there are at most max_holders, otherwise the max_holders with the smallest key(i,u) = mix(seed ^ mix(((uint64) i
+ *                  << 32) | u)) >> 32, equal keys by the smaller u
+ *   ov(u,v)        for u != v the number of items i with both u and v in U'_i; symmetric.  Without a cap in effect |I_u n I_v|
+ *   w(u,v)         (uint32) floor((double) ov / sqrt((double)(deg_u * deg_v)) * 65536.0): the product is exact in uint64, the
+ *                  conversions round to nearest, sqrt and the division are correctly rounded.  ov <= min(deg), so w <= 65536
+ *   neighbours     of u: every v with ov >= min_overlap and w > 0, by w descending, then v ascending; the first n_nbr are stored:
+ *                  nbr_users = v, nbr_w = w, nbr_ov = ov, padding -1 / 0 / 0
+ *   info           pairs = the ordered pairs (u, v) with ov >= min_overlap and w > 0, before the cut at n_nbr; n_users, n_items and
+ *                  cache_version are the graph's
+ *   refused        (-1, *out untouched) a cfg outside its ranges, reserved != 0, a NULL argument
+ * An empty graph is no error: every list is empty.  The handle is immutable and independent of the graph and the cache.  One
+ * workgroup computes one user's row from the kept holder lists of the user's items; both directions of a pair are computed.
+ * Cost: the sum over users u of the sum over i in I_u (u kept) of |U'_i| table updates; no user-pair key is ever sorted. */
+typedef struct {
+  int32_t  max_holders;  /* 2 .. 1024: holders of one item that take part      default 256 */
+  int32_t  n_nbr;        /* 1 .. 128: neighbours stored per user               default 64  */
+  int32_t  min_overlap;  /* >= 1                                               default 2   */
+  int32_t  reserved;     /* must be 0 */
+  uint64_t seed;         /* of the holder sample                               default 0   */
+} goctr_usercf_cfg;
+void goctr_usercf_cfg_default(goctr_usercf_cfg* c);
+typedef struct goctr_usercf goctr_usercf;
+int  goctr_usercf_build(goctr_walkgraph* g, const goctr_usercf_cfg* cfg, goctr_usercf** out);
+void goctr_usercf_destroy(goctr_usercf* h);
+/* each may be NULL */
+int  goctr_usercf_info(goctr_usercf* h, int64_t* n_users, int64_t* n_items, int32_t* n_nbr, uint64_t* pairs, uint64_t* cache_version);
+/* each may be NULL */
+int  goctr_usercf_export(goctr_usercf* h, uint32_t* deg /*[n_users]*/, int32_t* nbr_users /*[n_users,n_nbr]*/,
+                         uint32_t* nbr_w /*same*/, uint32_t* nbr_ov /*same*/);
+
+/* goctr_usercf_recall, for request row q over the ONE image of the cache the call holds:
+ *   neighbours     the first min(n_use, stored) entries of users[q]'s list
+ *   considered     of neighbour v: the entries of v's sequence that TimeSeq.Filter(ts[q], 0) keeps (ts[q] = 0: all; else those
+ *                  with ts <= ts[q] -- a row cannot see a neighbour's future, which is what a leave-one-out evaluation needs); of
+ *                  these the valid ones (0 <= item < n_items), and of those the first per_user, newest first.  A repeated item
+ *                  counts each time, as in goctr_itemcf_recall's history
+ *   S(q,j)         the sum of w(users[q], v) over every considered entry of every neighbour v that holds j: a uint32 sum of at most
+ *                  2^7 * 2^7 * 2^16 = 2^30, exact
+ *   candidates     every j with S > 0 that is not seen; seen is goctr_itemcf_recall's rule under cfg->exclude over the REQUEST
+ *                  user's sequence, the target exemption included
+ *   order          S descending, then item ascending; the first cfg->n_cand are kept.  Outputs and padding as goctr_itemcf_recall's;
+ *                  cfg->history is not used (its range is still checked)
+ *   refused        (-1, nothing touched) goctr_itemcf_recall's refusals (a NULL cache excepted); a NULL handle or ucfg; a ucfg
+ *                  outside its ranges; a cache whose n_users differs from the handle's or on another engine
+ * c == NULL, or a user with an empty list, gives count 0.  One workgroup serves a row; it shares the table, tiling, seen and list
+ * steps with goctr_itemcf_recall's kernel.  Host arrays, the engine stream and the engine lock, like goctr_itemcf_recall.
+ * Not covered: see DESIGN section 9 (no de-duplication per neighbour, no recency decay, no IUF weights, no neighbours for users
+ * that arrived after the build, no update of the LISTS after an append -- only the items are live). */
+typedef struct {
+  int32_t n_use;     /* 1 .. 128: stored neighbours that take part (the first n_use)          default 32 */
+  int32_t per_user;  /* 1 .. 128: entries of each neighbour's sequence that take part          default 20 */
+} goctr_usercf_recall_cfg;
+void goctr_usercf_recall_cfg_default(goctr_usercf_recall_cfg* c);
+int  goctr_usercf_recall(goctr_usercf* h, goctr_ubcache* c /* may be NULL */, const int32_t* users, const int64_t* ts /* NULL = 0 */,
+                         int64_t n_req, const goctr_recall_cfg* cfg, const goctr_usercf_recall_cfg* ucfg,
+                         int32_t* out_items /*[n_req,n_cand]*/, uint32_t* out_w /*[n_req,n_cand]*/, int32_t* out_count /*[n_req]*/,
+                         const int32_t* targets /*[n_req] or NULL*/, int32_t* out_target_pos /*[n_req] or NULL*/);
+
 /* ---- Diversity re-rank: maximal marginal relevance over item vectors, with group caps (no reference counterpart).  The recall
  * channels above return items close to the user's history, so the best k by score are typically one cluster.  A goctr_itemvec holds
  * the catalogue's quantised vectors (and optionally a group id per item) in HBM; goctr_rerank_mmr picks k of a row's scored
@@ -986,6 +1057,19 @@ int goctr_recommend_walk(goctr_model* m, goctr_recsys* r, goctr_walkgraph* g,
                          int32_t* out_items /* [n_req,k] */, float* out_scores /* [n_req,k] */, int32_t* out_count,
                          int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank,
                          int32_t* cand_items, uint32_t* cand_w, float* cand_scores, int64_t* n_failed);
+
+/* goctr_recommend_usercf: goctr_recommend_itemcf with the UserCF recall (goctr_usercf_recall above) as its recall stage, over the
+ * recsys's cache image.  Arguments and outputs are goctr_recommend_walk's with the handle and ucfg in place of the graph and wcfg;
+ * every documented property of that call holds unchanged, and a recsys without a cache returns empty rows.
+ *   refused        goctr_recommend_itemcf's refusals, the ucfg refusals above, and a handle whose n_items or n_users differs from
+ *                  the recsys's */
+int goctr_recommend_usercf(goctr_model* m, goctr_recsys* r, goctr_usercf* h,
+                           const int32_t* users, const int64_t* ts /* NULL = 0 */, int64_t n_req,
+                           const int32_t* targets /* [n_req] or NULL */, const goctr_recall_cfg* recall_cfg,
+                           const goctr_usercf_recall_cfg* ucfg, int32_t k, int64_t pass_rows,
+                           int32_t* out_items /* [n_req,k] */, float* out_scores /* [n_req,k] */, int32_t* out_count,
+                           int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank,
+                           int32_t* cand_items, uint32_t* cand_w, float* cand_scores, int64_t* n_failed);
 
 /* goctr_recommend_blend_walk: the blend with the random-walk recall as its part X, defined by composition as
  * goctr_recommend_blend_uservec is.  The result equals goctr_recommend_blend (v and cfg both NULL) or goctr_recommend_blend_mmr (both
@@ -1377,9 +1461,9 @@ int goctr_recommend_uservec_ivf(goctr_model* m, goctr_recsys* r, goctr_itemvec_i
  * output depends on thread counts, tiles or the order in which entries arrive.
  *
  * For request row q, channel c (0 .. n_chan - 1) yields a list L_c of at most n_list_c distinct items:
- *   ITEMCF, WALK, USERVEC, USERVEC_IVF, ALS
+ *   ITEMCF, WALK, USERVEC, USERVEC_IVF, ALS, USERCF
  *                  byte for byte the items goctr_itemcf_recall / goctr_walk_recall / goctr_uservec_recall /
- *                  goctr_uservec_recall_ivf / goctr_als_recall return for the row under {recall_cfg->history, n_cand = n_list_c,
+ *                  goctr_uservec_recall_ivf / goctr_als_recall / goctr_usercf_recall return for the row under {recall_cfg->history, n_cand = n_list_c,
  *                  recall_cfg->exclude} and the channel's cfg, for the same users, ts and targets over the same image of the cache
  *   POPULAR        the handle's stored list in list order; an entry is skipped if it is seen (goctr_blend_recall's rule) unless
  *                  it equals targets[q]; the list is cut at n_list_c KEPT entries
@@ -1407,11 +1491,12 @@ int goctr_recommend_uservec_ivf(goctr_model* m, goctr_recsys* r, goctr_itemvec_i
  *                  n_list outside 1 .. 1024, weight above 65535, reserve outside 0 .. n_list; the sum of n_list above 4096; the
  *                  sum of reserve above recall_cfg->n_cand; mode or rrf_k outside their ranges; a handle, handle2, cfg or list
  *                  missing for its kind or given where the kind takes none; a channel cfg its own entry refuses; handles on
- *                  different engines; handles whose n_items differ, a walk graph whose n_users differs from the cache's
+ *                  different engines; handles whose n_items differ, a walk graph or user neighbour lists (USERCF) whose n_users
+ *                  differs from the cache's
  * c == NULL: there is no history and nothing is seen, so only POPULAR and LIST channels yield entries.  The two sums are limits of
  * the implementation: the union of a row's lists and its hash table sit in one workgroup's LDS. */
 enum { GOCTR_FUSE_ITEMCF = 0, GOCTR_FUSE_WALK, GOCTR_FUSE_USERVEC, GOCTR_FUSE_USERVEC_IVF, GOCTR_FUSE_ALS, GOCTR_FUSE_POPULAR,
-       GOCTR_FUSE_LIST };
+       GOCTR_FUSE_LIST, GOCTR_FUSE_USERCF /* appended: no earlier value moves */ };
 enum { GOCTR_FUSE_RRF = 0, GOCTR_FUSE_ROUND_ROBIN = 1 };
 typedef struct {
   int32_t  kind;        /* GOCTR_FUSE_*                                                            */
@@ -1419,10 +1504,10 @@ typedef struct {
   uint32_t weight;      /* 0 .. 65535 (RRF only)                                                   */
   int32_t  reserve;     /* 0 .. n_list: the channel's first `reserve` kept entries are guaranteed  */
   const void* handle;   /* goctr_itemcf* | goctr_walkgraph* | goctr_itemvec* | goctr_itemvec_index* |
-                           goctr_als* | goctr_popular* | NULL (LIST)                               */
+                           goctr_als* | goctr_popular* | NULL (LIST) | goctr_usercf*               */
   const void* handle2;  /* ALS: the goctr_itemvec* it ranks against; else NULL                     */
   const void* cfg;      /* goctr_walk_cfg* | goctr_uservec_cfg* (USERVEC, ALS) |
-                           goctr_uservec_ivf_cfg* | NULL                                           */
+                           goctr_uservec_ivf_cfg* | goctr_usercf_recall_cfg* | NULL                */
   const int32_t* list;  /* LIST: host [n_req, n_list], -1 = no entry; else NULL                    */
 } goctr_fuse_channel;
 typedef struct {
