@@ -222,6 +222,11 @@ class WalkGraphCfg(C.Structure):
     _fields_ = [("max_len", C.c_int32), ("reserved", C.c_int32), ("ts_lo", C.c_int64), ("ts_hi", C.c_int64)]
 
 
+class EdgeWeightCfg(C.Structure):
+    """goctr_edgeweight_cfg (include/goctr.h)"""
+    _fields_ = [("half_life", C.c_int64), ("ts_ref", C.c_int64), ("cap", C.c_uint32), ("reserved", C.c_int32)]
+
+
 class WalkCfg(C.Structure):
     """goctr_walk_cfg (include/goctr.h)"""
     _fields_ = [("n_walks", C.c_int32), ("n_steps", C.c_int32), ("boost", C.c_int32), ("min_visits", C.c_int32),
@@ -391,10 +396,12 @@ SYMBOLS = [
     "goctr_list_cfg_default", "goctr_metrics_lists",
     "goctr_swing_cfg_default", "goctr_itemcf_build_swing",
     "goctr_walkgraph_cfg_default", "goctr_walkgraph_build", "goctr_walkgraph_destroy", "goctr_walkgraph_info", "goctr_walkgraph_export",
+    "goctr_edgeweight_cfg_default", "goctr_walkgraph_build_weighted", "goctr_walkgraph_weights",
     "goctr_walk_cfg_default", "goctr_walk_recall", "goctr_recommend_walk", "goctr_recommend_blend_walk",
     "goctr_als_cfg_default", "goctr_als_create", "goctr_als_destroy", "goctr_als_step", "goctr_als_fit", "goctr_als_loss", "goctr_als_info",
     "goctr_als_export", "goctr_als_set_factors", "goctr_itemvec_build_als", "goctr_itemcf_build_als", "goctr_als_foldin",
     "goctr_als_recall", "goctr_recommend_als", "goctr_recommend_blend_als",
+    "goctr_als_create_weighted", "goctr_als_weights", "goctr_als_foldin_weights",
     "goctr_ease_cfg_default", "goctr_ease_block_size", "goctr_itemcf_build_ease",
     "goctr_uservec_cfg_default", "goctr_uservec_recall", "goctr_recommend_uservec", "goctr_recommend_blend_uservec",
     "goctr_uservec_multi_cfg_default", "goctr_uservec_interests", "goctr_uservec_recall_multi", "goctr_recommend_uservec_multi",
@@ -433,6 +440,7 @@ def load() -> C.CDLL:
                      "goctr_ivf_cfg_default", "goctr_uservec_ivf_cfg_default", "goctr_itemvec_index_destroy",
                      "goctr_calib_cfg_default", "goctr_calibrator_destroy", "goctr_boot_cfg_default",
                      "goctr_walkgraph_cfg_default", "goctr_walk_cfg_default", "goctr_walkgraph_destroy",
+                     "goctr_edgeweight_cfg_default",
                      "goctr_als_cfg_default", "goctr_als_destroy", "goctr_ease_cfg_default", "goctr_fuse_cfg_default",
                      "goctr_itemattr_destroy", "goctr_usercf_cfg_default", "goctr_usercf_recall_cfg_default", "goctr_usercf_destroy"):
             getattr(_lib, name).restype = None
@@ -576,6 +584,10 @@ def load() -> C.CDLL:
         _lib.goctr_walkgraph_destroy.argtypes = [C.c_void_p]
         _lib.goctr_walkgraph_info.argtypes = [C.c_void_p, _i64, _i64, _i64, _u64]
         _lib.goctr_walkgraph_export.argtypes = [C.c_void_p, _i64, _i32, _i64, _i32]
+        _ew = C.POINTER(EdgeWeightCfg)
+        _lib.goctr_edgeweight_cfg_default.argtypes = [_ew]
+        _lib.goctr_walkgraph_build_weighted.argtypes = [C.c_void_p, C.c_int64, _wg, _ew, C.POINTER(C.c_void_p)]
+        _lib.goctr_walkgraph_weights.argtypes = [C.c_void_p, _i32, _ew, _i64, _u32, _u32]
         _lib.goctr_walk_recall.argtypes = [C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, C.POINTER(RecallCfg), _wk, _i32, _u32, _i32,
                                            _i32, _i32, _i32]
         _lib.goctr_recommend_walk.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32,
@@ -610,6 +622,9 @@ def load() -> C.CDLL:
         _lib.goctr_itemvec_build_als.argtypes = [C.c_void_p, _i32, C.POINTER(C.c_void_p)]
         _lib.goctr_itemcf_build_als.argtypes = [C.c_void_p, C.POINTER(ItemnbrCfg), C.POINTER(C.c_void_p)]
         _lib.goctr_als_foldin.argtypes = [C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, C.c_int32, _f64, _i16, _i32]
+        _lib.goctr_als_create_weighted.argtypes = [C.c_void_p, _als, C.POINTER(C.c_void_p)]
+        _lib.goctr_als_weights.argtypes = [C.c_void_p, _i32, _ew, _i64]
+        _lib.goctr_als_foldin_weights.argtypes = [C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, C.c_int32, _i32, _u32, _i32]
         _lib.goctr_als_recall.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, C.POINTER(RecallCfg), _uv, _i32,
                                           _u32, _i32, _i32, _i32, _i16, _f64]
         _lib.goctr_recommend_als.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32,
@@ -783,6 +798,7 @@ default_uservec_ivf_cfg = _default(UservecIvfCfg, "goctr_uservec_ivf_cfg_default
 default_list_cfg = _default(ListCfg, "goctr_list_cfg_default")
 default_popular_cfg = _default(PopularCfg, "goctr_popular_cfg_default")
 default_walkgraph_cfg = _default(WalkGraphCfg, "goctr_walkgraph_cfg_default")
+default_edgeweight_cfg = _default(EdgeWeightCfg, "goctr_edgeweight_cfg_default")
 default_walk_cfg = _default(WalkCfg, "goctr_walk_cfg_default")
 default_usercf_cfg = _default(UsercfCfg, "goctr_usercf_cfg_default")
 default_usercf_recall_cfg = _default(UsercfRecallCfg, "goctr_usercf_recall_cfg_default")

@@ -27,6 +27,11 @@ struct goctr_als {
   int D = 0;
   int long_thr = 0;                              // a row of more edges goes the segment way
   int64_t half_steps = 0;
+  // goctr_als_create_weighted's: the graph's weight rule and reference time, which step / fit / loss hold a graph against and the
+  // fold-in computes a request row's weights by
+  bool weighted = false;
+  goctr_edgeweight_cfg rule{};
+  int64_t ts_ref_used = 0;
   goctr::DevBuf<double> X, Y;                    // [n_users, D], [n_items, D]
   goctr::DevBuf<double> GX, GY;                  // [D, D] each; GX is a step's or a loss's scratch
   goctr_als_long long_users, long_items;

@@ -12,6 +12,12 @@
 // als_segment() is the one place the first rule lives: the solve kernel runs it for the rows it keeps, the part kernel for the
 // segments of long rows and for the Gram tiles, the fold-in kernel for a request row.
 //
+// PER-EDGE CONFIDENCE (a handle of goctr_als_create_weighted; include/goctr.h, tests/alsw_ref.py): an edge has the integer weight r
+// of the graph's uw / iw, rho = r / 65536.  The kernels are templates on a bool W; W = true is the same tree with P = N^T diag(rho) N
+// (the MFMA's A operand scaled by rho_e at every K step), s = the sum of (1 + alpha rho_e) * row e, and b = t as it stands.  The
+// W = false instantiations are the unweighted kernels, unchanged.  The fold-in of a weighted handle takes a request row's weights
+// from the row's own history (als_weighted_history): integer sums over the runs of one LDS sort.
+//
 // Launches of a half-step (the engine stream):
 //   als_part_kernel + als_gram_fold_kernel   G of the other side's factors (the user step reads the handle's G_Y as it is)
 //   als_solve_kernel   one workgroup per row: gathers the row's neighbour factor rows into LDS 64 edges at a time, accumulates the
@@ -36,6 +42,7 @@
 #include "lds_lists.h"
 #include "mfma_gemm.h"
 #include "negsample.h"
+#include "ts_decay.h"
 #include "ubcache.h"
 
 using namespace goctr;
@@ -63,6 +70,15 @@ struct AlsLds {
   double col[ALS_MAXD], diag[ALS_MAXD];
 };
 
+// the weighted segment's LDS: beside the rows, every staged edge's rho = r / 65536 and its row-sum factor 1 + alpha rho (1 KB).
+// The unweighted kernels keep AlsLds as it is
+template <bool W>
+struct AlsLdsT : AlsLds {};
+template <>
+struct AlsLdsT<true> : AlsLds {
+  double rho[ALS_CH], cw[ALS_CH];
+};
+
 // the p-th tile pair (ti <= tj) of T tiles a side, row by row
 __device__ __forceinline__ void als_pair(int p, int T, int& ti, int& tj) {
   ti = 0;
@@ -72,9 +88,12 @@ __device__ __forceinline__ void als_pair(int p, int T, int& ti, int& tj) {
 }
 
 // One segment: the ne <= 256 rows F[idx[e0 + e]] (idx null: F[e0 + e]) of D doubles.  acc[k] = the tile pair wave + 4 k of N^T N,
-// *bseg (threads below D) = the sum of the rows.  Every thread of the workgroup enters; the first statement is a barrier
-__device__ __forceinline__ void als_segment(const double* __restrict__ F, const int32_t* idx, long long e0, int ne, int D, int T,
-                                            AlsLds& s, acc_t (&acc)[ALS_PAIRS], double& bseg) {
+// *bseg (threads below D) = the sum of the rows.  Every thread of the workgroup enters; the first statement is a barrier.
+// W: edge e0 + e has the weight wts[e0 + e], rho = wts / 65536 (exact).  acc = N^T diag(rho) N -- the MFMA's A operand is scaled by
+// rho_e at every K step, one more rounding a summand -- and *bseg = the sum of (1 + alpha rho_e) * row e, in the same tree
+template <bool W>
+__device__ __forceinline__ void als_segment(const double* __restrict__ F, const int32_t* idx, const uint32_t* wts, long long e0, int ne,
+                                            int D, int T, double alpha, AlsLdsT<W>& s, acc_t (&acc)[ALS_PAIRS], double& bseg) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int Dp = T * 16, NS = tn_lds_stride(Dp), npairs = T * (T + 1) / 2;
 #pragma unroll
@@ -92,6 +111,13 @@ __device__ __forceinline__ void als_segment(const double* __restrict__ F, const 
       }
       s.N[e * NS + d] = v;
     }
+    if constexpr (W) {
+      if (tid < ALS_CH) {
+        const double rho = tid < nc ? (double)wts[e0 + c0 + tid] * 0x1.0p-16 : 0.0;
+        s.rho[tid] = rho;
+        s.cw[tid] = tid < nc ? 1.0 + alpha * rho : 0.0;
+      }
+    }
     __syncthreads();
     const int steps = (nc + 3) >> 2;
 #pragma unroll
@@ -102,14 +128,22 @@ __device__ __forceinline__ void als_segment(const double* __restrict__ F, const 
         als_pair(p, T, ti, tj);
         const double* pa = s.N + (lane >> 4) * NS + ti * 16 + (lane & 15);
         const double* pb = s.N + (lane >> 4) * NS + tj * 16 + (lane & 15);
-        for (int st = 0; st < steps; ++st) acc[k] = Mfma<double>::mma(pa[st * 4 * NS], pb[st * 4 * NS], acc[k]);
+        if constexpr (W) {
+          const double* pr = s.rho + (lane >> 4);            // a lane's edge of step st is st * 4 + (lane >> 4)
+          for (int st = 0; st < steps; ++st) acc[k] = Mfma<double>::mma(pr[st * 4] * pa[st * 4 * NS], pb[st * 4 * NS], acc[k]);
+        } else {
+          for (int st = 0; st < steps; ++st) acc[k] = Mfma<double>::mma(pa[st * 4 * NS], pb[st * 4 * NS], acc[k]);
+        }
       }
     }
     {
       const int d = lane, e1 = wave * 16 + 16;
       double r = 0.0;
       if (d < D)
-        for (int e = wave * 16; e < e1; ++e) r = r + s.N[e * NS + d];
+        for (int e = wave * 16; e < e1; ++e) {
+          if constexpr (W) r = r + s.cw[e] * s.N[e * NS + d];
+          else r = r + s.N[e * NS + d];
+        }
       s.bp[wave * ALS_MAXD + d] = r;
     }
     __syncthreads();
@@ -188,15 +222,17 @@ __device__ __forceinline__ double als_chol_solve(AlsLds& s, double bval, int D) 
 
 // ------------------------------------------------------------------------------------------------------------- the parts
 // part blockIdx.x = {P [D, D], s [D]} of one segment.  seg_row null: the Gram tile t0 + blockIdx.x of F's n rows; else the segment
-// seg_no[b] of row seg_row[b], whose edges index F
+// seg_no[b] of row seg_row[b], whose edges index F.  W (a weighted handle's long rows): the edges' weights w, and alpha for the sum
 struct PartArgs {
   const double* F; long long n, t0;
   const uint2* node; const int32_t* edges; const int32_t* seg_row; const int32_t* seg_no;
   int D; double* parts;
+  const uint32_t* w; double alpha;
 };
 
+template <bool W>
 __global__ __launch_bounds__(ALS_THREADS) void als_part_kernel(PartArgs a) {
-  __shared__ AlsLds s;
+  __shared__ AlsLdsT<W> s;
   const int T = (a.D + 15) >> 4;
   const long long b = blockIdx.x;
   const int32_t* idx = nullptr;
@@ -214,7 +250,7 @@ __global__ __launch_bounds__(ALS_THREADS) void als_part_kernel(PartArgs a) {
   }
   acc_t acc[ALS_PAIRS];
   double bseg;
-  als_segment(a.F, idx, e0, ne, a.D, T, s, acc, bseg);
+  als_segment<W>(a.F, idx, a.w, e0, ne, a.D, T, a.alpha, s, acc, bseg);
   double* out = a.parts + (size_t)b * ((size_t)a.D * a.D + a.D);
   const int D = a.D;
   als_acc_each(acc, D, T, [&](int i, int j, double v) { out[i * D + j] = v; });
@@ -239,10 +275,13 @@ struct SolveArgs {
   int D, long_thr; double alpha, lambda;
   double* out;                                 // this side's factors
   const int32_t* long_rows; const int32_t* long_first; const double* parts;   // the second form's: null together
+  const uint32_t* w;                           // W: the edges' weights, parallel to edges
 };
 
+// W: b is the row's sum as it stands -- the segments have (1 + alpha rho_e) in it
+template <bool W>
 __global__ __launch_bounds__(ALS_THREADS) void als_solve_kernel(SolveArgs a) {
-  __shared__ AlsLds s;
+  __shared__ AlsLdsT<W> s;
   const int tid = threadIdx.x, D = a.D, T = (D + 15) >> 4;
   const long long row = a.long_rows ? (long long)a.long_rows[blockIdx.x] : (long long)blockIdx.x;
   const uint2 nd = a.node[row];
@@ -260,7 +299,7 @@ __global__ __launch_bounds__(ALS_THREADS) void als_solve_kernel(SolveArgs a) {
       acc_t acc[ALS_PAIRS];
       double bseg;
       const int ne = (int)std::min<long long>(ALS_SEG, deg - sg * ALS_SEG);
-      als_segment(a.F, a.edges, (long long)nd.x + sg * ALS_SEG, ne, D, T, s, acc, bseg);
+      als_segment<W>(a.F, a.edges, a.w, (long long)nd.x + sg * ALS_SEG, ne, D, T, a.alpha, s, acc, bseg);
       als_fold_acc(s, acc, D, T, a.alpha);
       brow = brow + bseg;
     }
@@ -276,7 +315,7 @@ __global__ __launch_bounds__(ALS_THREADS) void als_solve_kernel(SolveArgs a) {
       if (tid < D) brow = brow + part[D * D + tid];
     }
   }
-  const double x = als_chol_solve(s, (1.0 + a.alpha) * brow, D);
+  const double x = als_chol_solve(s, W ? brow : (1.0 + a.alpha) * brow, D);
   if (tid < D) a.out[(size_t)row * D + tid] = x;
 }
 
@@ -289,13 +328,83 @@ struct FoldinArgs {
   const double* Y; const double* G;
   signed char* p_hi; signed char* p_lo;        // [nq + pad, Dp]
   double* out_x; int16_t* out_p; int32_t* out_n;             // each may be null
+  u64 half_life, cap; long long ts_ref;        // W: the handle's weight rule (cap as it applies) and reference time
 };
 
-__global__ __launch_bounds__(ALS_THREADS) void als_foldin_kernel(FoldinArgs a) {
-  __shared__ AlsLds s;
+// The weighted history of a request row.  The history is lds_gather_history's -- the first H valid entries the timestamp filter
+// keeps -- with every entry's contribution 2^(16 - b) against ts_ref beside it; one descending sort of (item + 1) << 32 | contribution
+// makes an item's entries a run, whose first position adds the run up: uniq[rank] = the item (descending, as the unweighted
+// kernel's), uwt[rank] = min(cap, the sum).  Integer sums: the order inside a run cannot show.  Returns the distinct items; every
+// thread of the workgroup enters, uniq[] and uwt[] are complete behind the caller's next barrier
+__device__ inline int als_weighted_history(const int32_t* seq_items, const long long* seq_ts, long long lo_e, long long len,
+                                           long long mts, long long n_items, int H, u64 half_life, long long ts_ref, u64 cap,
+                                           unsigned long long* key, int* uniq, uint32_t* uwt, int* wcnt) {
+  const int tid = threadIdx.x;
+  key[tid] = 0ull;
+  __syncthreads();
+  int nh = 0;
+  for (long long p0 = 0; p0 < len && nh < H; p0 += ALS_THREADS) {
+    const long long p = p0 + tid;
+    int it = -1;
+    long long t = 0;
+    if (p < len) {
+      t = seq_ts[lo_e + p];                                  // (a cache image always has its timestamps)
+      if (mts == 0 || t <= mts) it = seq_items[lo_e + p];
+    }
+    const bool valid = it >= 0 && it < n_items;
+    int tot;
+    const int r = nh + lds_block_rank<ALS_WAVES>(valid, wcnt, &tot);
+    if (valid && r < H) {
+      const u64 b = decay_bucket(half_life, t, ts_ref);
+      key[r] = ((unsigned long long)(unsigned int)(it + 1) << 32) | (b <= 16 ? 1ull << (16 - b) : 0ull);
+    }
+    nh += tot;
+    __syncthreads();
+  }
+  lds_sort_desc(key, ALS_MAX_H, tid, ALS_THREADS);
+  const unsigned long long mine = key[tid] >> 32;
+  const bool head = mine != 0ull && (tid == 0 || (key[tid - 1] >> 32) != mine);
+  int nu;
+  const int rank = lds_block_rank<ALS_WAVES>(head, wcnt, &nu);
+  if (head) {
+    u64 sum = 0;
+    for (int e = tid; e < ALS_MAX_H && (key[e] >> 32) == mine; ++e) sum += key[e] & 0xffffffffull;
+    uniq[rank] = (int)mine - 1;
+    uwt[rank] = (uint32_t)(sum < cap ? sum : cap);
+  }
+  return nu;
+}
+
+// goctr_als_foldin_weights: row q's distinct items ascending and their weights, padded with -1 / 0
+__global__ __launch_bounds__(ALS_THREADS) void als_foldin_weights_kernel(FoldinArgs a, int32_t* __restrict__ out_items,
+                                                                         uint32_t* __restrict__ out_r) {
   __shared__ unsigned long long key[ALS_MAX_H];
-  __shared__ int hist[ALS_MAX_H];
   __shared__ int uniq[ALS_MAX_H];
+  __shared__ uint32_t uwt[ALS_MAX_H];
+  __shared__ int wcnt[ALS_WAVES];
+  const int tid = threadIdx.x;
+  const long long q = blockIdx.x;
+  const int user = a.users[q];
+  long long lo_e = 0, len = 0;
+  if (a.off) { lo_e = a.off[user]; len = a.off[user + 1] - lo_e; }
+  const int nu = als_weighted_history(a.seq_items, a.seq_ts, lo_e, len, a.ts[q], a.n_items, a.H, a.half_life, a.ts_ref, a.cap, key,
+                                      uniq, uwt, wcnt);
+  __syncthreads();
+  if (tid < a.H) {
+    out_items[q * a.H + tid] = tid < nu ? uniq[nu - 1 - tid] : -1;
+    out_r[q * a.H + tid] = tid < nu ? uwt[nu - 1 - tid] : 0u;
+  }
+  if (tid == 0 && a.out_n) a.out_n[q] = nu;
+}
+
+// W: a weighted handle's fold-in -- the row's weights from its own history (als_weighted_history), the user step's weighted equations
+template <bool W>
+__global__ __launch_bounds__(ALS_THREADS) void als_foldin_kernel(FoldinArgs a) {
+  __shared__ AlsLdsT<W> s;
+  __shared__ unsigned long long key[ALS_MAX_H];
+  __shared__ int hist[W ? 1 : ALS_MAX_H];
+  __shared__ int uniq[ALS_MAX_H];
+  __shared__ uint32_t uwt[W ? ALS_MAX_H : 1];
   __shared__ int wcnt[ALS_WAVES];
   __shared__ double sx[ALS_MAXD];
   __shared__ double s_r;
@@ -304,24 +413,29 @@ __global__ __launch_bounds__(ALS_THREADS) void als_foldin_kernel(FoldinArgs a) {
   const int user = a.users[q];
   long long lo_e = 0, len = 0;
   if (a.off) { lo_e = a.off[user]; len = a.off[user + 1] - lo_e; }
-  const int nh = lds_gather_history<ALS_WAVES>(a.seq_items, a.seq_ts, lo_e, len, a.ts[q], a.n_items, a.H, hist, wcnt);
-  __syncthreads();
-  // the distinct items: one descending sort, the first of every run keeps its place in run order
-  key[tid] = tid < nh ? (unsigned long long)(unsigned int)(hist[tid] + 1) : 0ull;
-  __syncthreads();
-  lds_sort_desc(key, ALS_MAX_H, tid, ALS_THREADS);
-  const bool head = key[tid] != 0ull && (tid == 0 || key[tid - 1] != key[tid]);
   int nu;
-  const int rank = lds_block_rank<ALS_WAVES>(head, wcnt, &nu);
-  if (head) uniq[rank] = (int)key[tid] - 1;
+  if constexpr (W) {
+    nu = als_weighted_history(a.seq_items, a.seq_ts, lo_e, len, a.ts[q], a.n_items, a.H, a.half_life, a.ts_ref, a.cap, key, uniq, uwt,
+                              wcnt);
+  } else {
+    const int nh = lds_gather_history<ALS_WAVES>(a.seq_items, a.seq_ts, lo_e, len, a.ts[q], a.n_items, a.H, hist, wcnt);
+    __syncthreads();
+    // the distinct items: one descending sort, the first of every run keeps its place in run order
+    key[tid] = tid < nh ? (unsigned long long)(unsigned int)(hist[tid] + 1) : 0ull;
+    __syncthreads();
+    lds_sort_desc(key, ALS_MAX_H, tid, ALS_THREADS);
+    const bool head = key[tid] != 0ull && (tid == 0 || key[tid - 1] != key[tid]);
+    const int rank = lds_block_rank<ALS_WAVES>(head, wcnt, &nu);
+    if (head) uniq[rank] = (int)key[tid] - 1;
+  }
   double x = 0.0;
   if (nu > 0) {                                // (uniform)
     als_init_a(s, a.G, D, a.lambda);
     acc_t acc[ALS_PAIRS];
     double bseg;
-    als_segment(a.Y, uniq, 0, nu, D, T, s, acc, bseg);      // (its first barrier completes uniq[] and A)
+    als_segment<W>(a.Y, uniq, uwt, 0, nu, D, T, a.alpha, s, acc, bseg);      // (its first barrier completes uniq[], uwt[] and A)
     als_fold_acc(s, acc, D, T, a.alpha);
-    x = als_chol_solve(s, (1.0 + a.alpha) * (0.0 + bseg), D);
+    x = als_chol_solve(s, W ? 0.0 + bseg : (1.0 + a.alpha) * (0.0 + bseg), D);
   }
   if (tid < D) sx[tid] = x;
   __syncthreads();
@@ -358,10 +472,13 @@ __global__ __launch_bounds__(256) void als_init_kernel(double* __restrict__ Y, l
   Y[e] = __ddiv_rn(v, (double)D);
 }
 
-// usum[u] = the sum over u's edges of (1 + alpha) (1 - s)^2 - s^2: a wavefront per user, a lane's edges ascending, then a butterfly
+// usum[u] = the sum over u's edges of (1 + alpha) (1 - s)^2 - s^2: a wavefront per user, a lane's edges ascending, then a butterfly.
+// W: (1 + alpha rho) in the place of (1 + alpha), rho = uw / 65536
+template <bool W>
 __global__ __launch_bounds__(256) void als_edge_loss_kernel(const double* __restrict__ X, const double* __restrict__ Y,
                                                             const uint2* __restrict__ unode, const int32_t* __restrict__ uitems,
-                                                            long long n_users, int D, double alpha, double* __restrict__ usum) {
+                                                            const uint32_t* __restrict__ uw, long long n_users, int D, double alpha,
+                                                            double* __restrict__ usum) {
   const int lane = threadIdx.x & 63;
   const long long u = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (u >= n_users) return;
@@ -373,7 +490,9 @@ __global__ __launch_bounds__(256) void als_edge_loss_kernel(const double* __rest
     double sd = 0.0;
     for (int d = 0; d < D; ++d) sd = sd + x[d] * y[d];
     const double m = 1.0 - sd;
-    acc = acc + (((1.0 + alpha) * m) * m - sd * sd);
+    double c = 1.0 + alpha;
+    if constexpr (W) c = 1.0 + alpha * ((double)uw[nd.x + e] * 0x1.0p-16);
+    acc = acc + ((c * m) * m - sd * sd);
   }
   for (int o = 32; o > 0; o >>= 1) acc = acc + __shfl_xor(acc, o);
   if (lane == 0) usum[u] = acc;
@@ -412,6 +531,13 @@ int als_check_graph(const goctr_als* a, const goctr_walkgraph* g, const char* wh
               "%s: the graph (%lld users, %lld items, %llu edges) is not the one of goctr_als_create (%lld, %lld, %llu)", who,
               (long long)g->n_users, (long long)g->n_items, (unsigned long long)g->n_edges, (long long)a->n_users,
               (long long)a->n_items, (unsigned long long)a->n_edges);
+  if (!a->weighted) return 0;                  // (an unweighted handle ignores a graph's weights)
+  GOCTR_CHECK(g->weighted, "%s: the handle is weighted (goctr_als_create_weighted), the graph has no edge weights", who);
+  GOCTR_CHECK(g->rule.half_life == a->rule.half_life && g->rule.ts_ref == a->rule.ts_ref && g->rule.cap == a->rule.cap &&
+                  g->ts_ref_used == a->ts_ref_used,
+              "%s: the graph's weight rule (half_life %lld, ts_ref %lld, cap %u, reference time %lld) is not the handle's (%lld, %lld, "
+              "%u, %lld)", who, (long long)g->rule.half_life, (long long)g->rule.ts_ref, g->rule.cap, (long long)g->ts_ref_used,
+              (long long)a->rule.half_life, (long long)a->rule.ts_ref, a->rule.cap, (long long)a->ts_ref_used);
   return 0;
 }
 
@@ -453,12 +579,21 @@ int als_gram(const double* F, int64_t n, int D, double* G) {
     const int64_t nb = std::min<int64_t>(ALS_MAX_PARTS, tiles - t0);
     PartArgs p{};
     p.F = F; p.n = n; p.t0 = t0; p.D = D; p.parts = ws.parts.p;
-    hipLaunchKernelGGL(als_part_kernel, dim3((unsigned)nb), dim3(ALS_THREADS), 0, st, p);
+    hipLaunchKernelGGL(als_part_kernel<false>, dim3((unsigned)nb), dim3(ALS_THREADS), 0, st, p);
     GOCTR_HIP(hipGetLastError());
     hipLaunchKernelGGL(als_gram_fold_kernel, dim3(1), dim3(ALS_THREADS), 0, st, ws.parts.p, (long long)nb, D, t0 == 0 ? 1 : 0, G);
     GOCTR_HIP(hipGetLastError());
   }
   return 0;
+}
+
+// the rule a fold-in weighs a request row by: the handle's, or for an unweighted handle the one under which every item has r = 65536
+void als_foldin_rule(const goctr_als* a, FoldinArgs& f) {
+  if (a->weighted) {
+    f.half_life = (u64)a->rule.half_life; f.cap = a->rule.cap ? (u64)a->rule.cap : 0xffffffffull; f.ts_ref = a->ts_ref_used;
+  } else {
+    f.half_life = 0; f.cap = 65536; f.ts_ref = 0;
+  }
 }
 
 // one half-step, queued and waited for
@@ -472,8 +607,11 @@ int als_half_step(goctr_als* a, const goctr_walkgraph* g, int side) {
   s.node = users ? g->unode.p : g->inode.p; s.edges = users ? g->uitems.p : g->iusers.p;
   s.D = D; s.long_thr = a->long_thr; s.alpha = a->cfg.alpha; s.lambda = a->cfg.lambda;
   s.out = users ? a->X.p : a->Y.p;
+  const bool W = a->weighted;
+  if (W) s.w = users ? g->uw.p : g->iw.p;
   const int64_t n_rows = users ? a->n_users : a->n_items;
-  hipLaunchKernelGGL(als_solve_kernel, dim3((unsigned)n_rows), dim3(ALS_THREADS), 0, st, s);
+  if (W) hipLaunchKernelGGL(als_solve_kernel<true>, dim3((unsigned)n_rows), dim3(ALS_THREADS), 0, st, s);
+  else hipLaunchKernelGGL(als_solve_kernel<false>, dim3((unsigned)n_rows), dim3(ALS_THREADS), 0, st, s);
   GOCTR_HIP(hipGetLastError());
   const goctr_als_long& L = users ? a->long_users : a->long_items;
   if (!L.batches.empty()) {
@@ -486,12 +624,14 @@ int als_half_step(goctr_als* a, const goctr_walkgraph* g, int side) {
     for (const auto& b : L.batches) {
       PartArgs p{};
       p.F = s.F; p.node = s.node; p.edges = s.edges; p.seg_row = L.seg_row.p + b.s0; p.seg_no = L.seg_no.p + b.s0; p.D = D;
-      p.parts = ws.parts.p;
-      hipLaunchKernelGGL(als_part_kernel, dim3((unsigned)(b.s1 - b.s0)), dim3(ALS_THREADS), 0, st, p);
+      p.parts = ws.parts.p; p.w = s.w; p.alpha = s.alpha;
+      if (W) hipLaunchKernelGGL(als_part_kernel<true>, dim3((unsigned)(b.s1 - b.s0)), dim3(ALS_THREADS), 0, st, p);
+      else hipLaunchKernelGGL(als_part_kernel<false>, dim3((unsigned)(b.s1 - b.s0)), dim3(ALS_THREADS), 0, st, p);
       GOCTR_HIP(hipGetLastError());
       SolveArgs l = s;
       l.long_rows = L.rows.p + b.r0; l.long_first = L.first.p + b.r0; l.parts = ws.parts.p;
-      hipLaunchKernelGGL(als_solve_kernel, dim3((unsigned)(b.r1 - b.r0)), dim3(ALS_THREADS), 0, st, l);
+      if (W) hipLaunchKernelGGL(als_solve_kernel<true>, dim3((unsigned)(b.r1 - b.r0)), dim3(ALS_THREADS), 0, st, l);
+      else hipLaunchKernelGGL(als_solve_kernel<false>, dim3((unsigned)(b.r1 - b.r0)), dim3(ALS_THREADS), 0, st, l);
       GOCTR_HIP(hipGetLastError());
     }
   }
@@ -517,7 +657,12 @@ int als_foldin_launch(const goctr_als* a, const CacheSeq& seq, const int32_t* us
   f.off = seq.off; f.seq_items = seq.items; f.seq_ts = seq.ts; f.n_items = a->n_items; f.users = users; f.ts = ts;
   f.H = history; f.D = a->D; f.Dp = Dp; f.alpha = a->cfg.alpha; f.lambda = a->cfg.lambda; f.Y = a->Y.p; f.G = a->GY.p;
   f.p_hi = ws.p_hi.p; f.p_lo = ws.p_lo.p; f.out_x = o_x; f.out_p = o_p; f.out_n = o_n;
-  hipLaunchKernelGGL(als_foldin_kernel, dim3((unsigned)nq), dim3(ALS_THREADS), 0, st, f);
+  if (a->weighted) {
+    als_foldin_rule(a, f);
+    hipLaunchKernelGGL(als_foldin_kernel<true>, dim3((unsigned)nq), dim3(ALS_THREADS), 0, st, f);
+  } else {
+    hipLaunchKernelGGL(als_foldin_kernel<false>, dim3((unsigned)nq), dim3(ALS_THREADS), 0, st, f);
+  }
   GOCTR_HIP(hipGetLastError());
   return 0;
 }
@@ -562,16 +707,17 @@ void goctr_als_cfg_default(goctr_als_cfg* c) {
   c->D = 32; c->n_iters = 10; c->alpha = 40.0; c->lambda = 0.1; c->seed = 0; c->reserved = 0;
 }
 
-int goctr_als_create(goctr_walkgraph* g, const goctr_als_cfg* cfg, goctr_als** out) {
-  GOCTR_ENTER_H(g);
-  const char* who = "goctr_als_create";
+// the create behind goctr_als_create and goctr_als_create_weighted (the caller has entered the graph's engine)
+static int als_create(goctr_walkgraph* g, const goctr_als_cfg* cfg, bool weighted, goctr_als** out, const char* who) {
   GOCTR_CHECK(g && cfg && out, "%s: null argument (graph, cfg, out)", who);
+  GOCTR_CHECK(!weighted || g->weighted, "%s: the graph has no edge weights (goctr_walkgraph_build_weighted makes them)", who);
   if (als_check_cfg(cfg, who) || iv_check_shape(g->n_items, cfg->D, who)) return -1;
   GOCTR_CHECK(g->n_users > 0, "%s: the graph has no users", who);
   hipStream_t st = engine().stream;
   std::unique_ptr<goctr_als> a(new goctr_als);
   StreamDrain drain{st};                       // (behind the handle: an error return drains the stream before its buffers go)
   a->n_users = g->n_users; a->n_items = g->n_items; a->n_edges = g->n_edges; a->cfg = *cfg; a->D = cfg->D;
+  if (weighted) { a->weighted = true; a->rule = g->rule; a->ts_ref_used = g->ts_ref_used; }
   a->long_thr = std::max(ALS_SEG, env_int("GOCTR_ALS_LONG_ROW", 4096));
   const size_t D = (size_t)cfg->D;
   if (a->X.alloc((size_t)a->n_users * D) || a->Y.alloc((size_t)a->n_items * D, false) || a->GX.alloc(D * D) || a->GY.alloc(D * D)) return -1;
@@ -584,6 +730,26 @@ int goctr_als_create(goctr_walkgraph* g, const goctr_als_cfg* cfg, goctr_als** o
   if (als_gram(a->Y.p, a->n_items, (int)D, a->GY.p)) return -1;
   GOCTR_HIP(hipStreamSynchronize(st));
   *out = a.release();
+  return 0;
+}
+
+int goctr_als_create(goctr_walkgraph* g, const goctr_als_cfg* cfg, goctr_als** out) {
+  GOCTR_ENTER_H(g);
+  return als_create(g, cfg, false, out, "goctr_als_create");
+}
+
+int goctr_als_create_weighted(goctr_walkgraph* g, const goctr_als_cfg* cfg, goctr_als** out) {
+  GOCTR_ENTER_H(g);
+  return als_create(g, cfg, true, out, "goctr_als_create_weighted");
+}
+
+int goctr_als_weights(goctr_als* a, int32_t* weighted, goctr_edgeweight_cfg* rule, int64_t* ts_ref_used) {
+  GOCTR_ENTER_H(a);
+  GOCTR_CHECK(a, "goctr_als_weights: null handle");
+  if (weighted) *weighted = a->weighted ? 1 : 0;
+  if (!a->weighted) return 0;
+  if (rule) *rule = a->rule;
+  if (ts_ref_used) *ts_ref_used = a->ts_ref_used;
   return 0;
 }
 
@@ -629,8 +795,12 @@ int goctr_als_loss(goctr_als* a, goctr_walkgraph* g, double* loss) {
   AlsScratch& ws = engine_scratch<AlsScratch>();
   if (als_gram(a->X.p, a->n_users, D, a->GX.p)) return -1;
   if (ws.usum.ensure((size_t)a->n_users, false) || ws.total.ensure(1, false)) return -1;
-  hipLaunchKernelGGL(als_edge_loss_kernel, dim3((unsigned)cdiv(a->n_users, 4)), dim3(256), 0, st, a->X.p, a->Y.p, g->unode.p,
-                     g->uitems.p, (long long)a->n_users, D, a->cfg.alpha, ws.usum.p);
+  if (a->weighted)
+    hipLaunchKernelGGL(als_edge_loss_kernel<true>, dim3((unsigned)cdiv(a->n_users, 4)), dim3(256), 0, st, a->X.p, a->Y.p, g->unode.p,
+                       g->uitems.p, g->uw.p, (long long)a->n_users, D, a->cfg.alpha, ws.usum.p);
+  else
+    hipLaunchKernelGGL(als_edge_loss_kernel<false>, dim3((unsigned)cdiv(a->n_users, 4)), dim3(256), 0, st, a->X.p, a->Y.p, g->unode.p,
+                       g->uitems.p, (const uint32_t*)nullptr, (long long)a->n_users, D, a->cfg.alpha, ws.usum.p);
   GOCTR_HIP(hipGetLastError());
   hipLaunchKernelGGL(als_sum_kernel, dim3(1), dim3(256), 0, st, ws.usum.p, (long long)a->n_users, ws.total.p);
   GOCTR_HIP(hipGetLastError());
@@ -695,6 +865,40 @@ int goctr_als_foldin(goctr_als* a, goctr_ubcache* c, const int32_t* users, const
   if ((out_x && o_x.alloc(nq * D, false)) || (out_p && o_p.alloc(nq * D, false)) || (out_n && o_n.alloc(nq, false))) return -1;
   if (als_foldin_launch(a, CacheSeq(c), in.users.p, in.ts.p, n_req, history, o_x.p, o_p.p, o_n.p, ws, s)) return -1;
   if (out.add(out_x, o_x.p, sizeof(double) * nq * D) || out.add(out_p, o_p.p, sizeof(int16_t) * nq * D) ||
+      out.add(out_n, o_n.p, sizeof(int32_t) * nq)) return -1;
+  GOCTR_HIP(hipStreamSynchronize(s));
+  image.done();
+  out.commit();
+  return 0;
+}
+
+int goctr_als_foldin_weights(goctr_als* a, goctr_ubcache* c, const int32_t* users, const int64_t* ts, int64_t n_req, int32_t history,
+                             int32_t* out_items, uint32_t* out_r, int32_t* out_n) {
+  GOCTR_ENTER_H(a);
+  const char* who = "goctr_als_foldin_weights";
+  GOCTR_CHECK(a && c && users && out_items && out_r, "%s: null argument", who);
+  GOCTR_SAME_ENGINE(a, c);
+  GOCTR_CHECK(history >= 1 && history <= ALS_MAX_H, "%s: history = %d is outside 1 .. %d", who, history, ALS_MAX_H);
+  if (recall_check_users(users, n_req, c->n_users, who)) return -1;
+  hipStream_t s = engine().stream;
+  const size_t nq = (size_t)n_req, H = (size_t)history;
+  HostStage out(s);
+  RecallInputs in;
+  DevBuf<int32_t> o_items, o_n;
+  DevBuf<uint32_t> o_r;
+  UbRead image(c, s);                         // (behind the buffers: an error return drains the stream before they are freed)
+  if (in.stage(users, ts, nullptr, n_req, s)) return -1;
+  if (o_items.alloc(nq * H, false) || o_r.alloc(nq * H, false) || (out_n && o_n.alloc(nq, false))) return -1;
+  if (n_req > 0) {
+    const CacheSeq seq(c);
+    FoldinArgs f{};
+    f.off = seq.off; f.seq_items = seq.items; f.seq_ts = seq.ts; f.n_items = a->n_items; f.users = in.users.p; f.ts = in.ts.p;
+    f.H = history; f.out_n = o_n.p;
+    als_foldin_rule(a, f);
+    hipLaunchKernelGGL(als_foldin_weights_kernel, dim3((unsigned)n_req), dim3(ALS_THREADS), 0, s, f, o_items.p, o_r.p);
+    GOCTR_HIP(hipGetLastError());
+  }
+  if (out.add(out_items, o_items.p, sizeof(int32_t) * nq * H) || out.add(out_r, o_r.p, sizeof(uint32_t) * nq * H) ||
       out.add(out_n, o_n.p, sizeof(int32_t) * nq)) return -1;
   GOCTR_HIP(hipStreamSynchronize(s));
   image.done();

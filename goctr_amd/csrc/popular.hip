@@ -16,6 +16,7 @@
 
 #include "popular.h"
 #include "radix_sort.h"
+#include "ts_decay.h"
 #include "ubcache.h"
 
 using namespace goctr;
@@ -23,35 +24,19 @@ using namespace goctr;
 namespace {
 
 // ---------------------------------------------------------------------------------------------------------------- build
-constexpr int POP_BLOCK = 256, POP_MAX_GRID = 2048;
+constexpr int POP_BLOCK = TSREF_BLOCK;          // the accumulation runs the reference reduction's grid
 
-__device__ inline u64 ts_order(long long t) { return (u64)t ^ 0x8000000000000000ull; }   // unsigned order = signed order
+// the entries a build counts: a valid item inside the timestamp window
+struct PopCounted {
+  const int32_t* items; long long n_items, ts_lo, ts_hi;
+  __device__ __forceinline__ bool operator()(long long i, long long t) const {
+    const int it = items[i];
+    return it >= 0 && it < n_items && t >= ts_lo && t <= ts_hi;
+  }
+};
 
 __device__ inline bool pop_counted(int it, long long t, long long n_items, long long ts_lo, long long ts_hi) {
   return it >= 0 && it < n_items && t >= ts_lo && t <= ts_hi;
-}
-
-// stat[0] += counted entries; stat[1] = max ts_order over them (0 before)
-__global__ __launch_bounds__(POP_BLOCK) void pop_ref_kernel(const int32_t* __restrict__ items, const long long* __restrict__ ts,
-                                                            long long n, long long n_items, long long ts_lo, long long ts_hi,
-                                                            u64* __restrict__ stat) {
-  __shared__ u64 w_cnt[POP_BLOCK / 64], w_max[POP_BLOCK / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  u64 c = 0, m = 0;
-  for (long long i = (long long)blockIdx.x * POP_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * POP_BLOCK) {
-    const long long t = ts[i];
-    if (pop_counted(items[i], t, n_items, ts_lo, ts_hi)) { ++c; m = max(m, ts_order(t)); }
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    c += __shfl_down(c, o, 64);
-    m = max(m, __shfl_down(m, o, 64));
-  }
-  if (lane == 0) { w_cnt[wave] = c; w_max[wave] = m; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < POP_BLOCK / 64; ++w) { c += w_cnt[w]; m = max(m, w_max[w]); }
-    if (c) { atomicAdd(stat, c); atomicMax(stat + 1, m); }
-  }
 }
 
 // one entry per lane and round; the lanes of a wavefront that hold the same item add up first (the leader is the lowest such lane)
@@ -69,8 +54,7 @@ __global__ __launch_bounds__(POP_BLOCK) void pop_accum_kernel(const int32_t* __r
     const bool c = i < n && pop_counted(it, t, n_items, ts_lo, ts_hi);
     u64 add = 0;
     if (c) {
-      // the age as a mathematical integer: it fits uint64 whatever the two signed values are
-      const u64 b = half_life && t < ts_ref ? ((u64)ts_ref - (u64)t) / half_life : 0ull;
+      const u64 b = decay_bucket(half_life, t, ts_ref);
       add = b <= 32 ? 1ull << (32 - b) : 0ull;
     }
     u64 todo = __ballot(c);
@@ -321,16 +305,16 @@ int goctr_popular_build(goctr_ubcache* c, int64_t n_items, const goctr_popular_c
   if (r->cnt.alloc((size_t)n_items) || r->score.alloc((size_t)n_items) || r->list_items.alloc((size_t)n_list, false) ||
       r->list_score.alloc((size_t)n_list) || stat.alloc(2)) return -1;
   GOCTR_HIP(hipMemsetAsync(r->list_items.p, 0xff, sizeof(int32_t) * (size_t)n_list, s));
-  const unsigned grid = (unsigned)std::min<long long>(POP_MAX_GRID, std::max<long long>(1, cdiv(nnz, POP_BLOCK)));
+  const unsigned grid = ts_ref_grid(nnz);
   u64 h_stat[2] = {0, 0};
   if (nnz > 0) {
-    hipLaunchKernelGGL(pop_ref_kernel, dim3(grid), dim3(POP_BLOCK), 0, s, c->items.p, c->ts.p, nnz, (long long)n_items,
-                       (long long)cfg->ts_lo, (long long)cfg->ts_hi, stat.p);
+    hipLaunchKernelGGL(ts_ref_kernel<PopCounted>, dim3(grid), dim3(TSREF_BLOCK), 0, s, c->ts.p, nnz,
+                       PopCounted{c->items.p, (long long)n_items, (long long)cfg->ts_lo, (long long)cfg->ts_hi}, stat.p);
     GOCTR_HIP(hipGetLastError());
   }
   if (stat.download(h_stat, 2)) return -1;    // the reference timestamp is an argument of the next launch
   const u64 counted = h_stat[0];
-  const long long ts_ref = !counted ? 0 : cfg->ts_ref ? (long long)cfg->ts_ref : (long long)(h_stat[1] ^ 0x8000000000000000ull);
+  const long long ts_ref = !counted ? 0 : cfg->ts_ref ? (long long)cfg->ts_ref : ts_of_order(h_stat[1]);
   int n_listed = 0;
   if (counted) {
     hipLaunchKernelGGL(pop_accum_kernel, dim3(grid), dim3(POP_BLOCK), 0, s, c->items.p, c->ts.p, nnz, (long long)n_items,

@@ -14,6 +14,11 @@ struct goctr_walkgraph {
   uint64_t cache_version = 0;                    // version of the cache image the graph was built from
   goctr::DevBuf<uint2> unode, inode;             // [n_users], [n_items]
   goctr::DevBuf<int32_t> uitems, iusers;         // [n_edges] each: I_u ascending by (u, i), U_i ascending by (i, u)
+  // goctr_walkgraph_build_weighted's: r(u, i) beside either edge list.  Nothing but ALS's weighted handle reads them
+  bool weighted = false;
+  goctr_edgeweight_cfg rule{};                   // as given (cap 0 = 2^32 - 1)
+  int64_t ts_ref_used = 0;
+  goctr::DevBuf<uint32_t> uw, iw;                // [n_edges] each: parallel to uitems, to iusers
 };
 
 namespace goctr {

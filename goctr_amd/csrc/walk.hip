@@ -8,6 +8,12 @@
 //                         (i << 32 | u) of the second sort, and the two degrees (integer counts: no arrival order can show)
 //   radix_sort_keys       by (i, u); wk_low_words_kernel keeps the users: iusers
 //   two scans             of the degrees; their sinks write a node's {first edge, degree} as one 8-byte word
+// Weighted build (goctr_walkgraph_build_weighted; the same launches, and between them):
+//   ts_ref_kernel         (ts_decay.h, popular.hip's) with ts_ref = 0: the largest ts of a considered entry -- a key below the sentinel
+//   wk_contrib_kernel     an entry's contribution 2^(16 - b), 0 for a key at the sentinel; the first sort carries it as its value
+//   one 64-bit scan       of the sorted contributions; the heads' sink keeps the prefix at every run's head, and an edge's weight is
+//                         the difference of two neighbouring heads (the last one's against the total), cut at cap.  No atomic adds a
+//                         weight.  The second sort carries the weight as its value: iw
 // Recall (walk_recall_kernel): one workgroup per request row, below.
 #include <climits>
 #include <memory>
@@ -15,6 +21,7 @@
 
 #include "itemcf_build.h"
 #include "negsample.h"
+#include "ts_decay.h"
 #include "ubcache.h"
 #include "walk.h"
 
@@ -23,18 +30,51 @@ using namespace goctr;
 namespace {
 
 // ---------------------------------------------------------------------------------------------------------------- build
-// the scan's sink over the heads of the sorted (u, i) keys: the rank-th distinct entry
+// the scan's sink over the heads of the sorted (u, i) keys: the rank-th distinct entry.  W: wfirst[rank] = the sum of the sorted
+// contributions in front of the run (cex: their exclusive scan)
+template <bool W>
 struct WkDistinctSink {
   const u64* keys; int32_t* uitems; u64* ikeys; unsigned int* udeg; unsigned int* ideg;
+  const u64* cex; u64* wfirst;
   __device__ __forceinline__ void operator()(long long e, unsigned int head, unsigned int rank) const {
     if (!head) return;
     const u64 key = keys[e], u = key >> 32, i = key & 0xffffffffull;
     uitems[rank] = (int32_t)i;
     ikeys[rank] = (i << 32) | u;
+    if constexpr (W) wfirst[rank] = cex[e];
     atomicAdd(udeg + u, 1u);
     atomicAdd(ideg + i, 1u);
   }
 };
+
+// the entries of the image a build considers: ub_entry_keys_kernel gave them a key below the sentinel
+struct WkConsidered {
+  const u64* keys; u64 sentinel;
+  __device__ __forceinline__ bool operator()(long long e, long long) const { return keys[e] < sentinel; }
+};
+
+// contrib[e] = 2^(16 - b) of a considered entry (b: ts_decay.h's bucket against ts_ref), 0 for b > 16 and for every other entry
+__global__ __launch_bounds__(256) void wk_contrib_kernel(const u64* __restrict__ keys, const long long* __restrict__ ts, long long n,
+                                                         u64 sentinel, u64 half_life, long long ts_ref,
+                                                         unsigned int* __restrict__ contrib) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n) return;
+  unsigned int v = 0u;
+  if (keys[e] < sentinel) {
+    const u64 b = decay_bucket(half_life, ts[e], ts_ref);
+    v = b <= 16 ? 1u << (16 - b) : 0u;
+  }
+  contrib[e] = v;
+}
+
+// uw[e] = min(cap, the contributions of edge e's run): wfirst[e + 1] - wfirst[e], the last edge's against the total
+__global__ __launch_bounds__(256) void wk_weights_kernel(const u64* __restrict__ wfirst, const u64* __restrict__ total, long long n_e,
+                                                         u64 cap, unsigned int* __restrict__ uw) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n_e) return;
+  const u64 sum = (e + 1 < n_e ? wfirst[e + 1] : *total) - wfirst[e];
+  uw[e] = (unsigned int)(sum < cap ? sum : cap);
+}
 
 // the scan's sink over the degrees: node e = {its exclusive prefix, its degree}
 struct WkNodeSink {
@@ -52,6 +92,9 @@ struct WkScratch {
   DevBuf<u64> keys, keys_sorted, ikeys, ikeys_sorted, total;
   DevBuf<unsigned int> head, udeg, ideg, tiles;
   DevBuf<char> temp;
+  // the weighted build's
+  DevBuf<unsigned int> contrib, contrib_sorted;
+  DevBuf<u64> cex, wfirst, tiles64, wtotal, stat;
 };
 
 inline dim3 grid256(long long n) { return dim3((unsigned)cdiv(n, 256)); }
@@ -278,21 +321,10 @@ int walk_recommend_run(const TopnScorer& sc, const goctr_walkgraph* g, const goc
 
 }  // namespace goctr
 
-extern "C" {
-
-void goctr_walkgraph_cfg_default(goctr_walkgraph_cfg* c) {
-  if (!c) return;
-  c->max_len = 0; c->reserved = 0; c->ts_lo = INT64_MIN; c->ts_hi = INT64_MAX;
-}
-
-void goctr_walk_cfg_default(goctr_walk_cfg* c) {
-  if (!c) return;
-  c->n_walks = 512; c->n_steps = 4; c->boost = 1; c->min_visits = 1; c->seed = 0; c->reserved = 0;
-}
-
-int goctr_walkgraph_build(goctr_ubcache* c, int64_t n_items, const goctr_walkgraph_cfg* cfg, goctr_walkgraph** out) {
-  GOCTR_ENTER_H(c);
-  const char* who = "goctr_walkgraph_build";
+// the build behind goctr_walkgraph_build (wcfg null) and goctr_walkgraph_build_weighted: the caller has entered the cache's engine
+// and checked wcfg.  The unweighted build runs the launches it always ran
+static int wk_build(goctr_ubcache* c, int64_t n_items, const goctr_walkgraph_cfg* cfg, const goctr_edgeweight_cfg* wcfg,
+                    goctr_walkgraph** out, const char* who) {
   GOCTR_CHECK(c && cfg && out, "%s: null argument (cache, cfg, out)", who);
   GOCTR_CHECK(n_items > 0 && n_items <= INT32_MAX, "%s: n_items = %lld (1 .. 2^31 - 1)", who, (long long)n_items);
   GOCTR_CHECK(cfg->max_len >= 0, "%s: max_len = %d (>= 0)", who, cfg->max_len);
@@ -308,6 +340,7 @@ int goctr_walkgraph_build(goctr_ubcache* c, int64_t n_items, const goctr_walkgra
   const u64 user_sentinel = (u64)nu << 32;
   const unsigned int user_bits = 32u + (unsigned int)bits_for(nu + 1), item_bits = 32u + (unsigned int)bits_for(n_items);
   g->n_users = nu; g->n_items = n_items; g->cache_version = c->version;
+  long long ts_ref = wcfg ? (long long)wcfg->ts_ref : 0;
   if (g->unode.alloc((size_t)nu) || g->inode.alloc((size_t)n_items) || ws.udeg.alloc((size_t)nu) || ws.ideg.alloc((size_t)n_items) ||
       ws.total.alloc(1)) return -1;
   u64 n_e = 0;
@@ -318,16 +351,50 @@ int goctr_walkgraph_build(goctr_ubcache* c, int64_t n_items, const goctr_walkgra
                        (long long)n_items, (long long)cfg->max_len, (long long)cfg->ts_lo, (long long)cfg->ts_hi, user_sentinel,
                        ws.keys.p);
     GOCTR_HIP(hipGetLastError());
-    if (radix_sort_keys(ws.temp, ws.keys.p, ws.keys_sorted.p, (size_t)nnz, user_bits, s)) return -1;
+    if (wcfg) {
+      if (ws.contrib.alloc((size_t)nnz, false) || ws.contrib_sorted.alloc((size_t)nnz, false) || ws.cex.alloc((size_t)nnz, false) ||
+          ws.wfirst.alloc((size_t)nnz, false) || ws.wtotal.alloc(1) || ws.stat.alloc(2)) return -1;
+      if (!ts_ref) {                          // the largest ts of a considered entry (0: none); an argument of the next launch
+        hipLaunchKernelGGL(ts_ref_kernel<WkConsidered>, dim3(ts_ref_grid(nnz)), dim3(TSREF_BLOCK), 0, s, c->ts.p, nnz,
+                           WkConsidered{ws.keys.p, user_sentinel}, ws.stat.p);
+        GOCTR_HIP(hipGetLastError());
+        u64 h_stat[2] = {0, 0};
+        if (ws.stat.download(h_stat, 2)) return -1;
+        ts_ref = h_stat[0] ? ts_of_order(h_stat[1]) : 0;
+      }
+      hipLaunchKernelGGL(wk_contrib_kernel, grid256(nnz), dim3(256), 0, s, ws.keys.p, c->ts.p, nnz, user_sentinel,
+                         (u64)wcfg->half_life, ts_ref, ws.contrib.p);
+      GOCTR_HIP(hipGetLastError());
+      if (radix_sort_pairs(ws.temp, ws.keys.p, ws.keys_sorted.p, ws.contrib.p, ws.contrib_sorted.p, (size_t)nnz, user_bits, s)) return -1;
+      if (exclusive_scan<u64>(ws.contrib_sorted.p, nnz, ws.cex.p, ws.tiles64, ws.wtotal.p)) return -1;
+    } else if (radix_sort_keys(ws.temp, ws.keys.p, ws.keys_sorted.p, (size_t)nnz, user_bits, s)) {
+      return -1;
+    }
     hipLaunchKernelGGL(icf_heads_kernel, grid256(nnz), dim3(256), 0, s, ws.keys_sorted.p, nnz, user_sentinel, ws.head.p);
     GOCTR_HIP(hipGetLastError());
-    if (exclusive_scan_sink<unsigned int>(ws.head.p, nnz, ws.tiles, ws.total.p, ScanIdentity{},
-                                          WkDistinctSink{ws.keys_sorted.p, g->uitems.p, ws.ikeys.p, ws.udeg.p, ws.ideg.p})) return -1;
+    if (wcfg) {
+      if (exclusive_scan_sink<unsigned int>(ws.head.p, nnz, ws.tiles, ws.total.p, ScanIdentity{},
+                                            WkDistinctSink<true>{ws.keys_sorted.p, g->uitems.p, ws.ikeys.p, ws.udeg.p, ws.ideg.p,
+                                                                 ws.cex.p, ws.wfirst.p})) return -1;
+    } else if (exclusive_scan_sink<unsigned int>(ws.head.p, nnz, ws.tiles, ws.total.p, ScanIdentity{},
+                                                 WkDistinctSink<false>{ws.keys_sorted.p, g->uitems.p, ws.ikeys.p, ws.udeg.p, ws.ideg.p,
+                                                                       nullptr, nullptr})) {
+      return -1;
+    }
     if (ws.total.download(&n_e, 1)) return -1;
   }
   if (n_e) {
     if (ws.ikeys_sorted.alloc((size_t)n_e, false) || g->iusers.alloc((size_t)n_e, false)) return -1;
-    if (radix_sort_keys(ws.temp, ws.ikeys.p, ws.ikeys_sorted.p, (size_t)n_e, item_bits, s)) return -1;
+    if (wcfg) {
+      const u64 cap = wcfg->cap ? (u64)wcfg->cap : 0xffffffffull;
+      if (g->uw.alloc((size_t)n_e, false) || g->iw.alloc((size_t)n_e, false)) return -1;
+      hipLaunchKernelGGL(wk_weights_kernel, grid256((long long)n_e), dim3(256), 0, s, ws.wfirst.p, ws.wtotal.p, (long long)n_e, cap,
+                         g->uw.p);
+      GOCTR_HIP(hipGetLastError());
+      if (radix_sort_pairs(ws.temp, ws.ikeys.p, ws.ikeys_sorted.p, g->uw.p, g->iw.p, (size_t)n_e, item_bits, s)) return -1;
+    } else if (radix_sort_keys(ws.temp, ws.ikeys.p, ws.ikeys_sorted.p, (size_t)n_e, item_bits, s)) {
+      return -1;
+    }
     hipLaunchKernelGGL(wk_low_words_kernel, grid256((long long)n_e), dim3(256), 0, s, ws.ikeys_sorted.p, (long long)n_e, g->iusers.p);
     GOCTR_HIP(hipGetLastError());
     if (nu > 0 && exclusive_scan_sink<unsigned int>(ws.udeg.p, nu, ws.tiles, ws.total.p, ScanIdentity{}, WkNodeSink{g->unode.p})) return -1;
@@ -337,7 +404,54 @@ int goctr_walkgraph_build(goctr_ubcache* c, int64_t n_items, const goctr_walkgra
   GOCTR_HIP(hipStreamSynchronize(s));         // the scratch goes out of scope; the image is released
   image.done();
   g->n_edges = n_e;
+  if (wcfg) { g->weighted = true; g->rule = *wcfg; g->ts_ref_used = ts_ref; }
   *out = g.release();
+  return 0;
+}
+
+extern "C" {
+
+void goctr_walkgraph_cfg_default(goctr_walkgraph_cfg* c) {
+  if (!c) return;
+  c->max_len = 0; c->reserved = 0; c->ts_lo = INT64_MIN; c->ts_hi = INT64_MAX;
+}
+
+void goctr_walk_cfg_default(goctr_walk_cfg* c) {
+  if (!c) return;
+  c->n_walks = 512; c->n_steps = 4; c->boost = 1; c->min_visits = 1; c->seed = 0; c->reserved = 0;
+}
+
+int goctr_walkgraph_build(goctr_ubcache* c, int64_t n_items, const goctr_walkgraph_cfg* cfg, goctr_walkgraph** out) {
+  GOCTR_ENTER_H(c);
+  return wk_build(c, n_items, cfg, nullptr, out, "goctr_walkgraph_build");
+}
+
+void goctr_edgeweight_cfg_default(goctr_edgeweight_cfg* c) {
+  if (!c) return;
+  c->half_life = 0; c->ts_ref = 0; c->cap = 0; c->reserved = 0;
+}
+
+int goctr_walkgraph_build_weighted(goctr_ubcache* c, int64_t n_items, const goctr_walkgraph_cfg* cfg, const goctr_edgeweight_cfg* wcfg,
+                                   goctr_walkgraph** out) {
+  GOCTR_ENTER_H(c);
+  const char* who = "goctr_walkgraph_build_weighted";
+  GOCTR_CHECK(wcfg, "%s: null argument (wcfg)", who);
+  GOCTR_CHECK(wcfg->half_life >= 0, "%s: half_life = %lld (>= 0)", who, (long long)wcfg->half_life);
+  GOCTR_CHECK(wcfg->reserved == 0, "%s: reserved = %d (must be 0)", who, wcfg->reserved);
+  return wk_build(c, n_items, cfg, wcfg, out, who);
+}
+
+int goctr_walkgraph_weights(goctr_walkgraph* g, int32_t* weighted, goctr_edgeweight_cfg* rule, int64_t* ts_ref_used, uint32_t* uw,
+                            uint32_t* iw) {
+  GOCTR_ENTER_H(g);
+  GOCTR_CHECK(g, "goctr_walkgraph_weights: null handle");
+  if (weighted) *weighted = g->weighted ? 1 : 0;
+  if (!g->weighted) return 0;
+  if (rule) *rule = g->rule;
+  if (ts_ref_used) *ts_ref_used = g->ts_ref_used;
+  const size_t ne = (size_t)g->n_edges;
+  if (uw && ne && g->uw.download(uw, ne)) return -1;
+  if (iw && ne && g->iw.download(iw, ne)) return -1;
   return 0;
 }
 

@@ -986,6 +986,27 @@ class WalkGraph {
     check(goctr_walkgraph_build(cache, n_items, &cfg, &g.h_));
     return g;
   }
+  // the same graph with an integer weight per edge from the repeats and ages of its entries (goctr_walkgraph_build_weighted)
+  static goctr_edgeweight_cfg DefaultWeightCfg() { goctr_edgeweight_cfg c; goctr_edgeweight_cfg_default(&c); return c; }
+  static WalkGraph BuildWeighted(goctr_ubcache* cache, int64_t n_items, const goctr_edgeweight_cfg& wcfg = DefaultWeightCfg(),
+                                 const goctr_walkgraph_cfg& cfg = DefaultCfg()) {
+    WalkGraph g;
+    check(goctr_walkgraph_build_weighted(cache, n_items, &cfg, &wcfg, &g.h_));
+    return g;
+  }
+  struct EdgeWeights { bool weighted; goctr_edgeweight_cfg rule; int64_t ts_ref_used; std::vector<uint32_t> uw, iw; };
+  // uw parallel to the user side's edges, iw to the item side's; an unweighted graph: weighted = false, the rest empty
+  EdgeWeights Weights() const {
+    EdgeWeights w{};
+    int32_t flag = 0;
+    check(goctr_walkgraph_weights(h_, &flag, nullptr, nullptr, nullptr, nullptr));
+    w.weighted = flag != 0;
+    if (!w.weighted) return w;
+    const size_t ne = (size_t)info().n_edges;
+    w.uw.resize(ne); w.iw.resize(ne);
+    check(goctr_walkgraph_weights(h_, &flag, &w.rule, &w.ts_ref_used, w.uw.data(), w.iw.data()));
+    return w;
+  }
   WalkGraph(const WalkGraph&) = delete;
   WalkGraph& operator=(const WalkGraph&) = delete;
   WalkGraph(WalkGraph&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
@@ -1134,6 +1155,14 @@ class ALS {
   explicit ALS(const WalkGraph& graph, const goctr_als_cfg& cfg = DefaultCfg()) : graph_(graph.handle()) {
     check(goctr_als_create(graph_, &cfg, &h_));
   }
+  // per-edge confidence 1 + alpha r / 65536 over a graph of WalkGraph::BuildWeighted (goctr_als_create_weighted); every fold-in of
+  // the handle weighs the request row by the repeats and ages of its history
+  static ALS CreateWeighted(const WalkGraph& graph, const goctr_als_cfg& cfg = DefaultCfg()) {
+    ALS a;
+    a.graph_ = graph.handle();
+    check(goctr_als_create_weighted(a.graph_, &cfg, &a.h_));
+    return a;
+  }
   ALS(const ALS&) = delete;
   ALS& operator=(const ALS&) = delete;
   ALS(ALS&& o) noexcept : h_(o.h_), graph_(o.graph_), vec_(o.vec_) { o.h_ = nullptr; o.vec_ = nullptr; }
@@ -1171,6 +1200,7 @@ class ALS {
   }
 
  private:
+  ALS() = default;                                             // (CreateWeighted's)
   goctr_als* h_ = nullptr;
   goctr_walkgraph* graph_ = nullptr;
   goctr_itemvec* vec_ = nullptr;

@@ -119,6 +119,21 @@ make_ivf_cfg = _make("goctr_ivf_cfg", _IVF_FIELDS, capi.default_ivf_cfg)
 make_uservec_ivf_cfg = _make("goctr_uservec_ivf_cfg", _USERVEC_IVF_FIELDS, capi.default_uservec_ivf_cfg)
 make_walkgraph_cfg = _make("goctr_walkgraph_cfg", _WALKGRAPH_FIELDS, capi.default_walkgraph_cfg)
 make_walk_cfg = _make("goctr_walk_cfg", _WALK_FIELDS, capi.default_walk_cfg)
+make_edgeweight_cfg = _make("goctr_edgeweight_cfg", _fields(capi.EdgeWeightCfg), capi.default_edgeweight_cfg)
+
+
+def edgeweight_cfg(weights) -> capi.EdgeWeightCfg | None:
+    """a ``weights=`` argument as the struct: None stays None (no weights), a dict is goctr_edgeweight_cfg's keywords (half_life,
+    ts_ref, cap), a struct is taken as it is"""
+    if weights is None or isinstance(weights, capi.EdgeWeightCfg):
+        return weights
+    if isinstance(weights, dict):
+        return make_edgeweight_cfg(**weights)
+    raise TypeError(f"weights = {weights!r} is neither an EdgeWeightCfg, a dict nor None")
+
+
+def _weights_dict(weighted, rule, ts_ref):
+    return dict(weighted=bool(weighted.value), half_life=rule.half_life, ts_ref=rule.ts_ref, cap=rule.cap, ts_ref_used=ts_ref.value)
 make_usercf_cfg = _make("goctr_usercf_cfg", _USERCF_FIELDS, capi.default_usercf_cfg)
 make_usercf_recall_cfg = _make("goctr_usercf_recall_cfg", _USERCF_RECALL_FIELDS, capi.default_usercf_recall_cfg)
 
@@ -390,15 +405,33 @@ class WalkGraph(_Handle):
     """goctr_walkgraph: the bipartite user-item graph resident in HBM, immutable after the build and independent of the cache"""
     _destroy = "goctr_walkgraph_destroy"
 
-    def __init__(self, ubc, n_items: int, cfg: capi.WalkGraphCfg | None = None, **kw):
+    def __init__(self, ubc, n_items: int, cfg: capi.WalkGraphCfg | None = None, weights=None, **kw):
         """ubc: a ubcache.UserBehaviorCache (its device image is read) or a raw goctr_ubcache handle; ``kw``: goctr_walkgraph_cfg
-        fields (max_len, ts_lo, ts_hi)"""
+        fields (max_len, ts_lo, ts_hi).  ``weights``: an EdgeWeightCfg or a dict of its fields (half_life, ts_ref, cap) builds the
+        graph with edge weights (goctr_walkgraph_build_weighted); None builds it without"""
         cfg = _cfg_or_kw(cfg, kw, make_walkgraph_cfg)
+        wcfg = edgeweight_cfg(weights)
         self._h = C.c_void_p()
-        capi.check(capi.load().goctr_walkgraph_build(_cache_handle(ubc), C.c_int64(_as_int("n_items", n_items)), C.byref(cfg),
-                                                     C.byref(self._h)))
+        if wcfg is None:
+            capi.check(capi.load().goctr_walkgraph_build(_cache_handle(ubc), C.c_int64(_as_int("n_items", n_items)), C.byref(cfg),
+                                                         C.byref(self._h)))
+        else:
+            capi.check(capi.load().goctr_walkgraph_build_weighted(_cache_handle(ubc), C.c_int64(_as_int("n_items", n_items)),
+                                                                  C.byref(cfg), C.byref(wcfg), C.byref(self._h)))
+        self.weighted = wcfg is not None
         i = self.info()
         self.n_users, self.n_items, self.n_edges = i["n_users"], i["n_items"], i["n_edges"]
+
+    def weights(self) -> dict:
+        """goctr_walkgraph_weights: dict(weighted bool, half_life, ts_ref, cap (the rule as given), ts_ref_used, uw uint32 [n_edges]
+        (parallel to export()'s uitems), iw uint32 [n_edges] (parallel to iusers)); an unweighted graph: dict(weighted=False)"""
+        w, rule, ref = C.c_int32(0), capi.EdgeWeightCfg(), C.c_int64(0)
+        uw, iw = np.empty(self.n_edges, np.uint32), np.empty(self.n_edges, np.uint32)
+        capi.check(capi.load().goctr_walkgraph_weights(self._h, C.byref(w), C.byref(rule), C.byref(ref), capi.ptr(uw, C.c_uint32),
+                                                       capi.ptr(iw, C.c_uint32)))
+        if not w.value:
+            return dict(weighted=False)
+        return dict(_weights_dict(w, rule, ref), uw=uw, iw=iw)
 
     def info(self) -> dict:
         nu, ni, ne, v = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_uint64(0)
@@ -503,12 +536,20 @@ class ALS(_Handle):
     training call"""
     _destroy = "goctr_als_destroy"
 
-    def __init__(self, graph: WalkGraph, cfg: capi.AlsCfg | None = None, **kw):
-        """``kw``: goctr_als_cfg fields (D, n_iters, alpha, lambda_, seed).  Allocates and initialises; runs no iteration"""
+    def __init__(self, graph: WalkGraph, cfg: capi.AlsCfg | None = None, weighted=None, **kw):
+        """``kw``: goctr_als_cfg fields (D, n_iters, alpha, lambda_, seed).  Allocates and initialises; runs no iteration.
+        ``weighted``: None = exactly when the graph is; True on a graph without weights raises; False ignores a graph's weights"""
+        graph_weighted = bool(getattr(graph, "weighted", False))
+        if weighted is None:
+            weighted = graph_weighted
+        if weighted and not graph_weighted:
+            raise ValueError("weighted=True needs a graph built with weights (WalkGraph(..., weights=...))")
         cfg = _cfg_or_kw(cfg, kw, make_als_cfg)
         self.graph = graph
+        self.weighted = bool(weighted)
         self._h = C.c_void_p()
-        capi.check(capi.load().goctr_als_create(graph._h, C.byref(cfg), C.byref(self._h)))
+        create = capi.load().goctr_als_create_weighted if self.weighted else capi.load().goctr_als_create
+        capi.check(create(graph._h, C.byref(cfg), C.byref(self._h)))
         i = self.info()
         self.n_users, self.n_items, self.D = i["n_users"], i["n_items"], i["D"]
 
@@ -516,6 +557,24 @@ class ALS(_Handle):
         nu, ni, d, hs = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int64(0)
         capi.check(capi.load().goctr_als_info(self._h, C.byref(nu), C.byref(ni), C.byref(d), C.byref(hs)))
         return dict(n_users=nu.value, n_items=ni.value, D=d.value, half_steps=hs.value)
+
+    def weights(self) -> dict:
+        """goctr_als_weights: dict(weighted bool, half_life, ts_ref, cap, ts_ref_used) -- the graph's rule as the handle keeps it;
+        an unweighted handle: dict(weighted=False)"""
+        w, rule, ref = C.c_int32(0), capi.EdgeWeightCfg(), C.c_int64(0)
+        capi.check(capi.load().goctr_als_weights(self._h, C.byref(w), C.byref(rule), C.byref(ref)))
+        return _weights_dict(w, rule, ref) if w.value else dict(weighted=False)
+
+    def foldin_weights(self, ubc, users, ts=None, history=50) -> dict:
+        """goctr_als_foldin_weights over DENSE user rows of ``ubc``'s image: dict(items int32 [nq, history] (every row's distinct
+        history items ascending, -1 behind them), r uint32 [nq, history] (their weights, 0 behind them), n int32 [nq])"""
+        users, ts, _ = request_columns(users, ts, None)
+        nq, H = users.size, _as_int("history", history)
+        shape = (nq, min(max(H, 1), 256))
+        out = dict(items=_unwritten(shape, np.int32), r=_unwritten(shape, np.uint32), n=_unwritten(nq, np.int32))
+        capi.check(capi.load().goctr_als_foldin_weights(self._h, _cache_handle(ubc), *_request_args(users, ts), C.c_int32(H),
+                                                        _ptr(out["items"]), _ptr(out["r"]), _ptr(out["n"])))
+        return out
 
     def step(self, side) -> "ALS":
         """goctr_als_step: one half-step; ``side`` "users" (X from Y) or "items" (Y from X), or capi.ALS_USERS / ALS_ITEMS"""

@@ -1022,11 +1022,15 @@ def RecommendBlendALSBatch(model: Predictor, icf, pop, factors, userIds, n=10, n
 
 
 # ---- what the recall channels are built from
-def BuildALS(recSys: DeviceRecSys, graph=None, graph_kw=None, **cfg):
+def BuildALS(recSys: DeviceRecSys, graph=None, graph_kw=None, weight_kw=None, **cfg):
     """EXTENSION: implicit-feedback ALS factors (recall.ALS; ``cfg``: goctr_als_cfg fields -- D, n_iters, alpha, lambda_, seed) fitted
     over ``graph`` (default: BuildWalkGraph of the recSys's cache, ``graph_kw`` its cfg), with the quantised item factors in
-    ``.vectors`` -- what RecommendALS folds in against and scans."""
-    factors = ALS(graph if graph is not None else BuildWalkGraph(recSys, **(graph_kw or {})), **cfg).fit()
+    ``.vectors`` -- what RecommendALS folds in against and scans.  ``weight_kw`` (goctr_edgeweight_cfg fields -- half_life, ts_ref,
+    cap; {} for the defaults) builds the graph with edge weights and fits with per-edge confidence 1 + alpha r / 65536; a caller's
+    own ``graph`` is fitted weighted exactly when it has weights."""
+    if graph is not None and weight_kw is not None:
+        raise TypeError("give either a graph or weight_kw (the weights are the graph's)")
+    factors = ALS(graph if graph is not None else BuildWalkGraph(recSys, weights=weight_kw, **(graph_kw or {})), **cfg).fit()
     factors.vectors = factors.item_vectors()
     return factors
 
@@ -1052,12 +1056,13 @@ def BuildUserCF(recSys: DeviceRecSys, graph=None, graph_kw=None, **cfg):
         own.close()
 
 
-def BuildWalkGraph(recSys: DeviceRecSys, **cfg):
+def BuildWalkGraph(recSys: DeviceRecSys, weights=None, **cfg):
     """EXTENSION: the user-item graph (recall.WalkGraph; ``cfg``: goctr_walkgraph_cfg fields -- max_len, ts_lo, ts_hi) of the recSys's
     own behaviour cache over the rows of its item feature table -- what RecommendWalk walks.  Two sorts and two scans of the distinct
     (user, item) entries, no pair expansion: cheap enough to rebuild after every AppendUserBehavior.  The graph is that of the cache's
-    image at THIS call."""
-    return WalkGraph(_dense_cache(recSys, "build the walk graph from"), recSys.item_table.shape[0], **cfg)
+    image at THIS call.  ``weights`` (an EdgeWeightCfg or a dict of half_life, ts_ref, cap) keeps an integer weight per edge from
+    the repeats and ages of its entries; BuildALS reads it."""
+    return WalkGraph(_dense_cache(recSys, "build the walk graph from"), recSys.item_table.shape[0], weights=weights, **cfg)
 
 
 def BuildItemCF(recSys: DeviceRecSys, **cfg):
@@ -1435,12 +1440,13 @@ def EvaluateLeaveOneOutUserCF(model: Predictor, ucf=None, k=10, sample_kw=None, 
 
 
 def EvaluateLeaveOneOutALS(model: Predictor, factors=None, k=10, sample_kw=None, details=False, pass_rows=0, graph_kw=None, als_kw=None,
-                           **recall_kw):
+                           weight_kw=None, **recall_kw):
     """EvaluateLeaveOneOutRecall's protocol and figures with the ALS fold-in recall as the recall stage (goctr_recommend_als).  The
     request vector is folded in from the history the key sees (key timestamp ts - 1), so it never holds the held-out item; the ITEM
     factors would, if they were trained on it.  ``factors`` None: the factors are fitted here (``als_kw``: goctr_als_cfg fields) over
     a graph windowed below the held-out events as EvaluateLeaveOneOutWalk's is (``graph_kw``), and closed on the way out; a caller's
-    own ``factors`` are used as they are."""
+    own ``factors`` are used as they are.  ``weight_kw`` (BuildALS's) fits them with per-edge confidence: the graph stays windowed
+    below the held-out events, so the default ts_ref = 0 makes the newest event below the cut the reference time."""
     users, targets, ts = _held_out_rows(model, sample_kw)
     recall_kw.setdefault("exclude", "before")
     cfg, ucfg = _split_kw(None, None, recall_kw, _USERVEC_FIELDS, make_uservec_cfg)
@@ -1448,7 +1454,7 @@ def EvaluateLeaveOneOutALS(model: Predictor, factors=None, k=10, sample_kw=None,
     if factors is None:
         gkw = dict(graph_kw or {})
         gkw.setdefault("ts_hi", int((sample_kw or {})["ts_lo"]) - 1 if "ts_lo" in (sample_kw or {}) else int(ts.min()))
-        factors = own = BuildALS(model.recSys, graph_kw=gkw, **(als_kw or {}))
+        factors = own = BuildALS(model.recSys, graph_kw=gkw, weight_kw=weight_kw, **(als_kw or {}))
     try:
         r = als(model, factors, users, ts, targets, k, pass_rows, recall_cfg=cfg, ucfg=ucfg)
     finally:

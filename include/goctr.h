@@ -707,6 +707,36 @@ int  goctr_walkgraph_info(goctr_walkgraph* g, int64_t* n_users, int64_t* n_items
 int  goctr_walkgraph_export(goctr_walkgraph* g, int64_t* uoff /*[n_users+1]*/, int32_t* uitems /*[n_edges]*/,
                             int64_t* ioff /*[n_items+1]*/, int32_t* iusers /*[n_edges]*/);
 
+/* Edge weights: goctr_walkgraph_build_weighted is goctr_walkgraph_build that also keeps, for every edge, an integer weight made of
+ * the repeats and the ages of the entries behind it.  All arithmetic is integer; tests/edgew_ref.py restates it.
+ *   considered     exactly goctr_walkgraph_build's entries under cfg: valid item, max_len, the ts_lo .. ts_hi window, ONE image
+ *   ts_ref_used    wcfg->ts_ref, or when that is 0 the largest ts of a considered entry (0 when there is none)
+ *   bucket         goctr_popular_build's rule: b = 0 when half_life == 0 or ts >= ts_ref_used; otherwise
+ *                  b = floor((ts_ref_used - ts) / half_life), the difference taken as a mathematical integer
+ *   contribution   of an entry: 2^(16 - b) for b <= 16, else 0.  65536 is one fresh event
+ *   weight         r(u,i) = min(cap, the sum of the contributions of the considered entries of u that hold i) as a uint32; cap 0
+ *                  stands for 2^32 - 1.  The sum is taken in 64 bits (below 2^47 under the build's limit of 2^31 entries)
+ *   weight 0       an edge whose entries are all older than 16 half-lives has r = 0 and STAYS an edge
+ *   CSR arrays     uoff / uitems / ioff / iusers, n_edges and cache_version are byte for byte goctr_walkgraph_build's under cfg
+ *   uw, iw         uw[e] = r of edge e in uitems order, iw[e] in iusers order: the same edge carries the same value in both
+ *   refused        (-1, *out untouched) goctr_walkgraph_build's refusals; a NULL wcfg; half_life < 0; reserved != 0
+ * A weight is a difference of one 64-bit prefix sum over the sorted entries: no atomic adds it, and no output byte depends on a
+ * tile or pass size.  A weighted graph is a graph: goctr_walk_recall, goctr_usercf_build, goctr_itemcf_build_ease and
+ * goctr_als_create (with its step, fit and loss) ignore the weights and return the bytes they return for the unweighted graph.
+ * goctr_als_create_weighted is the one reader. */
+typedef struct {
+  int64_t  half_life;  /* >= 0; 0 = no decay                                  default 0 */
+  int64_t  ts_ref;     /* 0 = the largest ts of a considered entry             default 0 */
+  uint32_t cap;        /* 0 = 2^32 - 1; else r saturates here (>= 1)           default 0 */
+  int32_t  reserved;   /* must be 0 */
+} goctr_edgeweight_cfg;
+void goctr_edgeweight_cfg_default(goctr_edgeweight_cfg* c);
+int  goctr_walkgraph_build_weighted(goctr_ubcache* c, int64_t n_items, const goctr_walkgraph_cfg* cfg,
+                                    const goctr_edgeweight_cfg* wcfg, goctr_walkgraph** out);
+/* each output may be NULL; uw is parallel to uitems, iw to iusers; an unweighted graph: *weighted = 0, the rest untouched */
+int  goctr_walkgraph_weights(goctr_walkgraph* g, int32_t* weighted, goctr_edgeweight_cfg* rule, int64_t* ts_ref_used,
+                             uint32_t* uw /*[n_edges]*/, uint32_t* iw /*[n_edges]*/);
+
 /* goctr_walk_recall, for request row q over the ONE image of the cache the call holds:
  *   history        exactly goctr_itemcf_recall's with n_items = the graph's: h_0 .. h_{H-1}; a repeated item takes a slot each
  *                  time.  With H = 0 the row returns count 0
@@ -1096,7 +1126,8 @@ int goctr_recommend_blend_walk(goctr_model* m, goctr_recsys* r, goctr_itemcf* ic
  * interaction data itself, over the two CSRs of a goctr_walkgraph (tests/als_ref.py is the host restatement).  All arithmetic is
  * float64.
  *
- * Edges are binary: the graph's distinct (user, item) edges, uniform confidence.  With X [n_users,D], Y [n_items,D], G_Y = Y^T Y
+ * Edges are binary: the graph's distinct (user, item) edges, uniform confidence ("Per-edge confidence" below, goctr_als_create_weighted,
+ * gives every edge a confidence of its own from the graph's weights).  With X [n_users,D], Y [n_items,D], G_Y = Y^T Y
  * and I_u the items of user u (the graph's uitems row):
  *   user step      A_u = G_Y + alpha * sum_{i in I_u} y_i y_i^T + lambda * I
  *                  b_u = (1 + alpha) * sum_{i in I_u} y_i
@@ -1147,6 +1178,26 @@ int  goctr_als_info(goctr_als* a, int64_t* n_users, int64_t* n_items, int32_t* D
 int  goctr_als_export(goctr_als* a, double* X, double* Y);
 int  goctr_als_set_factors(goctr_als* a, const double* X, const double* Y);
 
+/* Per-edge confidence: goctr_als_create_weighted is goctr_als_create over a WEIGHTED graph (goctr_walkgraph_build_weighted); the
+ * handle keeps the graph's rule and ts_ref_used.  With rho_ui = r(u,i) / 65536, which is exact in a double, c_ui = 1 + alpha rho_ui:
+ *   user step      A_u = G_Y + alpha * sum_{i in I_u} rho_ui y_i y_i^T + lambda * I,  b_u = sum_{i in I_u} (1 + alpha rho_ui) y_i;
+ *                  the Cholesky and the two triangular solves are unchanged.  The item step swaps the roles and reads iw
+ *   loss           <G_X, G_Y> + the sum over the edges of (1 + alpha rho) (1 - s)^2 - s^2 + lambda (tr G_X + tr G_Y)
+ *   weight 0       an edge with rho = 0 adds y_i to b and nothing to A: a preference of confidence 1.  The objective is continuous
+ *                  in rho
+ *   summation      the rule above stays: segments of 256 edges in CSR order, folded ascending; a weighted summand takes one more
+ *                  rounding (rho y) than an unweighted one.  Two fits give the same bytes
+ *   fold-in        every call that folds in (goctr_als_foldin, goctr_als_recall, goctr_recommend_als, goctr_recommend_blend_als,
+ *                  the ALS channel of goctr_fuse_recall* / goctr_recommend_fused*) weighs the request row by the history it gathers:
+ *                  rho of a distinct item = min(cap, the sum of the contributions of ITS history entries) / 65536, the buckets
+ *                  taken against the HANDLE's ts_ref_used (an entry newer than that has b = 0); the equations are the user step's
+ *   refused        goctr_als_create's refusals; an unweighted graph; (step, fit, loss of a weighted handle) a graph without
+ *                  weights, or one whose rule or ts_ref_used differs from the handle's
+ * A handle of goctr_als_create over a weighted graph ignores the weights. */
+int  goctr_als_create_weighted(goctr_walkgraph* g, const goctr_als_cfg* cfg, goctr_als** out);
+/* each may be NULL; a handle of goctr_als_create: *weighted = 0, the rest untouched */
+int  goctr_als_weights(goctr_als* a, int32_t* weighted, goctr_edgeweight_cfg* rule, int64_t* ts_ref_used);
+
 /* the item factors, device to device, into the existing builds: the results equal goctr_itemvec_build_vectors /
  * goctr_itemcf_build_vectors called with goctr_als_export's Y, byte for byte (the same quantise launch reads the same doubles) */
 int  goctr_itemvec_build_als(goctr_als* a, const int32_t* groups /* [n_items] or NULL */, goctr_itemvec** out);
@@ -1166,6 +1217,12 @@ int  goctr_itemcf_build_als(goctr_als* a, const goctr_itemnbr_cfg* cfg, goctr_it
 int  goctr_als_foldin(goctr_als* a, goctr_ubcache* c, const int32_t* users, const int64_t* ts /* NULL = 0 */, int64_t n_req,
                       int32_t history, double* out_x /*[n_req,D] or NULL*/, int16_t* out_p /*[n_req,D] or NULL*/,
                       int32_t* out_n /*[n_req] or NULL*/);
+/* the integer half of the fold-in: the distinct history items of every row, ascending, and their weights r (the rule of "Per-edge
+ * confidence: fold-in"); rows padded with -1 / 0; out_n (may be NULL) their number.  A handle of goctr_als_create: r = 65536.
+ * Refusals as goctr_als_foldin's, and a NULL out_items or out_r */
+int  goctr_als_foldin_weights(goctr_als* a, goctr_ubcache* c, const int32_t* users, const int64_t* ts /* NULL = 0 */, int64_t n_req,
+                              int32_t history, int32_t* out_items /*[n_req,history]*/, uint32_t* out_r /*same*/,
+                              int32_t* out_n /*[n_req] or NULL*/);
 
 /* goctr_als_recall: goctr_uservec_recall with the folded-in vector's planes in the place of the pooled vector's: weight, seen,
  * candidates, order and outputs are that call's, over the item vectors v (goctr_itemvec_build_als's, as a rule).
