@@ -58,6 +58,7 @@ struct Engine {
     size_t size = 0;
     std::map<size_t, size_t> free_blocks;   // offset -> length
     std::map<size_t, size_t> used;          // offset -> length
+    size_t n_outside = 0;                   // requests that fell back to a plain hipMalloc so far (the tests' harness reads it)
     std::mutex mu;
   } arena;
   bool kernel_attrs_done = false, mlp_attrs_done = false;   // hipFuncSetAttribute is per device: once per engine
@@ -247,10 +248,17 @@ struct StreamDrain {
 
 // The calling thread's engine's instance of the scratch type Ws (device buffers that grow to a high-water mark and stay), created
 // on first use.  Never destroyed: the engines' arenas may be gone by the time static destructors run at exit.
+// Every scratch type lists a function that destroys its instances (their buffers go back to the arena), so that the tests' harness
+// (selftest.hip: goctr_selftest_arena_drop_scratch) can have the next call grow its scratch anew, out of whatever the arena's
+// free blocks hold then.  engine_scratch_drop_all is for that harness alone: a call in flight holds a reference to its instance.
+void engine_scratch_register(void (*drop)());
+void engine_scratch_drop_all();
 template <class Ws>
 Ws& engine_scratch() {
   static std::mutex mu;
   static auto* const all = new std::map<Engine*, Ws>;
+  static const bool listed = (engine_scratch_register(+[] { std::lock_guard<std::mutex> lk(mu); all->clear(); }), true);
+  (void)listed;
   std::lock_guard<std::mutex> lk(mu);
   return (*all)[&engine()];
 }

@@ -232,6 +232,7 @@ void* arena_alloc(size_t bytes) {
     }
   }
   void* p = nullptr;
+  ++a.n_outside;
   if (hipMalloc(&p, need) != hipSuccess) {
     (void)hipGetLastError();
     set_error("device allocation of %zu bytes failed", need);
@@ -263,6 +264,23 @@ void arena_free(Engine* owner, void* p) {
     }
   }
   (void)hipFree(p);
+}
+
+// the scratch types of the process (common.h: engine_scratch), each by the function that destroys its instances
+namespace {
+std::mutex g_scratch_mu;
+std::vector<void (*)()>& scratch_drops() {
+  static auto* const v = new std::vector<void (*)()>;
+  return *v;
+}
+}  // namespace
+void engine_scratch_register(void (*drop)()) {
+  std::lock_guard<std::mutex> lk(g_scratch_mu);
+  scratch_drops().push_back(drop);
+}
+void engine_scratch_drop_all() {
+  std::lock_guard<std::mutex> lk(g_scratch_mu);
+  for (void (*drop)() : scratch_drops()) drop();
 }
 
 int engine_bind(Engine& e, int device_ordinal) {

@@ -1,7 +1,9 @@
-// selftest.hip -- a test harness over the shared device headers: scan.h, radix_sort.h, lds_lists.h and metrics_reduce.h.  Built
-// into its own shared object (libgoctr_selftest.so, linked against libgoctr_hip.so for the engine, DevBuf and the error text);
-// the goctr_amd package never loads it and include/goctr.h does not declare it: only tests/test_gpu_primitives.py does, through
-// ctypes, after goctr_init.
+// selftest.hip -- a test harness over the shared device headers: scan.h, radix_sort.h, lds_lists.h and metrics_reduce.h, and over
+// the engine's device arena (engine.hip: arena_alloc / arena_free).  Built into its own shared object (libgoctr_selftest.so, linked
+// against libgoctr_hip.so for the engine, DevBuf and the error text); the goctr_amd package never loads it and include/goctr.h does
+// not declare it: only tests do, through ctypes, after goctr_init -- tests/test_gpu_primitives.py for the header entries, and
+// tests/test_gpu_arena_poison.py (with its child processes, tests/arena_child.py) for the goctr_selftest_arena_* entries at the end
+// of this file, which write a pattern over the arena's free blocks, report its state and replay allocation traces.
 //
 // The headers keep their code in anonymous namespaces or as inline device functions, so what runs here is the header text AS
 // INSTANTIATED IN THIS TRANSLATION UNIT (with the library's compile flags), not the copies inlined into the users' kernels: a
@@ -566,6 +568,109 @@ int goctr_selftest_fold(int kind, const void* vals, long long n, int G, void* pa
   if (kind == 0) return fold_run<Sums<float, 1>, float, 1>(vals, n, G, parts_out, out);
   if (kind == 1) return fold_run<Sums<double, 2>, double, 2>(vals, n, G, parts_out, out);
   return fold_run<SelfBest, u64, 2>(vals, n, G, parts_out, out);
+}
+
+// --------------------------------------------------------------------------------------------------------------- the arena
+// The engine's arena from the outside: what a test needs to run a call on memory that holds a chosen pattern instead of whatever
+// the last call left there, and to check the allocator itself.  MAX_SLOTS / MAX_OPS bound a trace.
+constexpr int AR_MAX_SLOTS = 4096, AR_MAX_OPS = 1 << 16;
+constexpr long long AR_MAX_BYTES = 1ll << 36, AR_MAX_PROBE_WORDS = 1ll << 26;
+
+// Writes `word` over every free block of the calling thread's engine's arena.  Both engine streams are drained first (a block
+// may have been released with work on it still queued); the arena's mutex is held from the first look at the free list to the
+// end of the last write, so no block changes hands in between and no used block is touched.  out[0] = bytes written, out[1] =
+// free blocks.  No arena (GOCTR_ARENA_MB=0, or its hipMalloc failed): -1
+int goctr_selftest_arena_fill(unsigned int word, unsigned long long* out) {
+  GOCTR_ENTER();
+  GOCTR_CHECK(out, "goctr_selftest_arena_fill: null array");
+  Engine& e = engine();
+  GOCTR_HIP(hipStreamSynchronize(e.stream));
+  GOCTR_HIP(hipStreamSynchronize(e.side));
+  { DevBuf<char> first; if (first.alloc(1, false)) return -1; }        // (the arena is made by the first request)
+  Engine::Arena& a = e.arena;
+  std::lock_guard<std::mutex> lk(a.mu);
+  GOCTR_CHECK(a.base, "goctr_selftest_arena_fill: this engine has no arena (GOCTR_ARENA_MB=0, or it could not be allocated)");
+  u64 bytes = 0, blocks = 0;
+  hipError_t err = hipSuccess;
+  for (const auto& b : a.free_blocks) {                                // (offsets and lengths are multiples of 256)
+    if (b.first > a.size || b.second > a.size - b.first) { err = hipErrorInvalidValue; break; }
+    err = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a.base + b.first), (int)word, b.second / 4, e.stream);
+    if (err != hipSuccess) break;
+    bytes += b.second; ++blocks;
+  }
+  const hipError_t serr = hipStreamSynchronize(e.stream);              // before the mutex goes, on the error path too
+  GOCTR_HIP(err);
+  GOCTR_HIP(serr);
+  out[0] = bytes; out[1] = blocks;
+  return 0;
+}
+
+// Gives back the per-engine scratch of every family that keeps one (engine_scratch: the metrics, the calibrator, the bootstrap,
+// ALS, this file's own): it stays allocated from a family's first call on and grows by high-water marks, so a fill -- which leaves
+// used blocks alone -- would never reach it, and a call would run on the values its predecessor left there.  After this entry
+// the next call of a family allocates its scratch anew, from the free blocks.  Both engine streams are drained first; the caller
+// has no call in flight on another thread
+int goctr_selftest_arena_drop_scratch(void) {
+  GOCTR_ENTER();
+  GOCTR_HIP(hipStreamSynchronize(engine().stream));
+  GOCTR_HIP(hipStreamSynchronize(engine().side));
+  engine_scratch_drop_all();
+  return 0;
+}
+
+// out[0..6) = the arena's size, its free bytes, its largest free block, its used blocks, its free blocks, and the requests that
+// fell back to hipMalloc since the process began.  Before the first request, or without an arena, the first five are 0
+int goctr_selftest_arena_stats(unsigned long long* out) {
+  GOCTR_ENTER();
+  GOCTR_CHECK(out, "goctr_selftest_arena_stats: null array");
+  Engine::Arena& a = engine().arena;
+  std::lock_guard<std::mutex> lk(a.mu);
+  u64 free_bytes = 0, largest = 0;
+  for (const auto& b : a.free_blocks) { free_bytes += b.second; largest = std::max<u64>(largest, b.second); }
+  out[0] = a.size; out[1] = free_bytes; out[2] = largest; out[3] = a.used.size(); out[4] = a.free_blocks.size(); out[5] = a.n_outside;
+  return 0;
+}
+
+// A non-zeroed DevBuf of n words as a caller gets it: words[n] = its contents, *offset = its place in the arena (-1: outside)
+int goctr_selftest_arena_probe(long long n, unsigned int* words, long long* offset) {
+  GOCTR_ENTER();
+  GOCTR_CHECK(n >= 1 && n <= AR_MAX_PROBE_WORDS, "goctr_selftest_arena_probe: n = %lld is outside [1, %lld]", n, AR_MAX_PROBE_WORDS);
+  GOCTR_CHECK(words && offset, "goctr_selftest_arena_probe: null array");
+  DevBuf<unsigned int> d;
+  StreamDrain drain{engine().stream};
+  if (d.alloc((size_t)n, false)) return -1;
+  const Engine::Arena& a = engine().arena;
+  const char* c = reinterpret_cast<const char*>(d.p);
+  *offset = a.base && c >= a.base && c < a.base + a.size ? (long long)(c - a.base) : -1;
+  return d.download(words, (size_t)n);
+}
+
+// Replays n_ops operations through DevBuf<char>: ops[i] = {slot, bytes}; bytes >= 0 allocates that many (non-zeroed) into the
+// slot, which must be empty, bytes < 0 releases the slot, which must be full.  offsets[i] = the allocation's offset from the
+// arena's base, -1 where it lies outside the arena, -2 for a release.  Whatever is live at the end is released
+int goctr_selftest_arena_trace(const long long* ops, int n_ops, int n_slots, long long* offsets) {
+  GOCTR_ENTER();
+  GOCTR_CHECK(n_ops >= 0 && n_ops <= AR_MAX_OPS, "goctr_selftest_arena_trace: n_ops = %d is outside [0, %d]", n_ops, AR_MAX_OPS);
+  GOCTR_CHECK(n_slots >= 1 && n_slots <= AR_MAX_SLOTS, "goctr_selftest_arena_trace: n_slots = %d is outside [1, %d]", n_slots, AR_MAX_SLOTS);
+  GOCTR_CHECK((ops && offsets) || n_ops == 0, "goctr_selftest_arena_trace: null array");
+  std::vector<DevBuf<char>> slots(n_slots);
+  for (int i = 0; i < n_ops; ++i) {
+    const long long slot = ops[2 * i], bytes = ops[2 * i + 1];
+    GOCTR_CHECK(slot >= 0 && slot < n_slots, "goctr_selftest_arena_trace: op %d names slot %lld of %d", i, slot, n_slots);
+    GOCTR_CHECK(bytes <= AR_MAX_BYTES, "goctr_selftest_arena_trace: op %d asks for %lld bytes (at most %lld)", i, bytes, AR_MAX_BYTES);
+    DevBuf<char>& d = slots[(size_t)slot];
+    if (bytes < 0) {
+      GOCTR_CHECK(d.p, "goctr_selftest_arena_trace: op %d releases the empty slot %lld", i, slot);
+      d.release();
+      offsets[i] = -2;
+      continue;
+    }
+    GOCTR_CHECK(!d.p, "goctr_selftest_arena_trace: op %d allocates into the full slot %lld", i, slot);
+    if (d.alloc((size_t)bytes, false)) return -1;
+    const Engine::Arena& a = engine().arena;
+    offsets[i] = a.base && d.p >= a.base && d.p < a.base + a.size ? (long long)(d.p - a.base) : -1;
+  }
+  return 0;
 }
 
 }  // extern "C"
