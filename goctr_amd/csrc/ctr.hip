@@ -349,12 +349,12 @@ int goctr::launch_attn_fwd(const AttnArgs& a) {
     GOCTR_HIP(hipGetLastError());
     return 0;
   }
-#define GOCTR_ATTN_FWD(V, L) hipLaunchKernelGGL((attn_fwd_kernel<V, L, 0>), grid, blk, 0, st, a)
+#define GOCTR_ATTN_FWD(V, L) hipLaunchKernelGGL((attn_fwd_kernel<V, L, 0>), grid, blk, 0, st, ATTN_HEAD_ARGS(a), a)
 #define GOCTR_ATTN_FWD_FAST(L)                                                                     \
   do {                                                                                             \
-    if (fast == 1) hipLaunchKernelGGL((attn_fwd_kernel<4, L, 1>), grid, blk, 0, st, a);            \
-    else if (fast == 2) hipLaunchKernelGGL((attn_fwd_kernel<4, L, 2>), grid, blk, 0, st, a);       \
-    else hipLaunchKernelGGL((attn_fwd_kernel<4, L, 3>), grid, blk, 0, st, a);                      \
+    if (fast == 1) hipLaunchKernelGGL((attn_fwd_kernel<4, L, 1>), grid, blk, 0, st, ATTN_HEAD_ARGS(a), a);            \
+    else if (fast == 2) hipLaunchKernelGGL((attn_fwd_kernel<4, L, 2>), grid, blk, 0, st, ATTN_HEAD_ARGS(a), a);       \
+    else hipLaunchKernelGGL((attn_fwd_kernel<4, L, 3>), grid, blk, 0, st, ATTN_HEAD_ARGS(a), a);                      \
   } while (0)
   if (fast && groups <= 16) {
     if (groups == 1) GOCTR_ATTN_FWD_FAST(1);
@@ -437,7 +437,7 @@ ChainArgs make_chain_args(goctr_model* m, const RowSource& src, int B, const Ste
 template <int NCH0>
 void launch_chain_x3_n(const ChainX3Args& a, dim3 grid, hipStream_t s, bool fwd) {
   if (fwd) launch_chain_x3_fwd(NCH0, a, grid, s);       // (ctr_fwd.hip: its own translation unit, see there)
-  else hipLaunchKernelGGL((ctr_chain_x3_kernel<NCH0, false>), grid, dim3(512), chain_x3_lds_bytes<NCH0>(), s, a);
+  else hipLaunchKernelGGL((ctr_chain_x3_kernel<NCH0, false>), grid, dim3(512), chain_x3_lds_bytes<NCH0>(), s, CX_HEAD_ARGS(a), a);
 }
 
 int launch_chain_x3(goctr_model* m, const RowSource& src, int B, const StepOpts& o, const StepState* st, const FwdBufs& fb) {
@@ -729,9 +729,9 @@ int launch_reduce_attn(goctr_model* m, const RowSource& src, int B, const StepOp
   hipStream_t st = engine().active;
 #define GOCTR_RA(L)                                                                                        \
   do {                                                                                                     \
-    if (fast == 1) hipLaunchKernelGGL((reduce_attn_kernel<4, L, 1>), grid, blk, 0, st, p, aa, nred);       \
-    else if (fast == 2) hipLaunchKernelGGL((reduce_attn_kernel<4, L, 2>), grid, blk, 0, st, p, aa, nred);  \
-    else hipLaunchKernelGGL((reduce_attn_kernel<4, L, 3>), grid, blk, 0, st, p, aa, nred);                 \
+    if (fast == 1) hipLaunchKernelGGL((reduce_attn_kernel<4, L, 1>), grid, blk, 0, st, ATTN_HEAD_ARGS(aa), nred, p, aa);       \
+    else if (fast == 2) hipLaunchKernelGGL((reduce_attn_kernel<4, L, 2>), grid, blk, 0, st, ATTN_HEAD_ARGS(aa), nred, p, aa);  \
+    else hipLaunchKernelGGL((reduce_attn_kernel<4, L, 3>), grid, blk, 0, st, ATTN_HEAD_ARGS(aa), nred, p, aa);                 \
   } while (0)
   if (groups == 4) GOCTR_RA(4);
   else GOCTR_RA(16);
@@ -754,7 +754,7 @@ int launch_reduce_part(goctr_model* m, const RowSource& src, int B, const StepOp
     if (o.pipelined) {
       if (launch_reduce_attn(m, src, B, o, p)) return -1;     // + attn_fwd of the next step's batch
     } else {
-      hipLaunchKernelGGL(reduce_adam_kernel, dim3((unsigned)cdiv((int64_t)m->nflat * 2, 256) + 1), dim3(256), 0, e.stream, p);
+      hipLaunchKernelGGL(reduce_adam_kernel, dim3((unsigned)cdiv((int64_t)m->nflat * 2, 256) + 1), dim3(256), 0, e.stream, REDUCE_ADAM_HEAD_ARGS(p), p);
       GOCTR_HIP(hipGetLastError());
     }
     m->stp ^= 1;   // the step is closed: later launches read the slot just written
@@ -881,14 +881,14 @@ int launch_dw_wide(goctr_model* m, int B, const StepOpts& o, bool fuse_update, i
     if (m->att0_early) {      // (one more workgroup, the last: att0's sum and update)
       if (ps.on) prof_note_kernel(GOCTR_K_DW0, tw.ktw0 == 9 ? "gemm_tn_multi_x3w_att0_kernel<9,5>" : "gemm_tn_multi_x3w_att0_kernel<8,5>");
       if (tw.ktw0 == 9)
-        hipLaunchKernelGGL((gemm_tn_multi_x3w_att0_kernel<9, 5>), dim3((unsigned)nblk + 1), dim3(512), gemm_tn_multi_x3w_lds_bytes<9>(), e.stream, tm, ae);
+        hipLaunchKernelGGL((gemm_tn_multi_x3w_att0_kernel<9, 5>), dim3((unsigned)nblk + 1), dim3(512), gemm_tn_multi_x3w_lds_bytes<9>(), e.stream, ae.st, ae.tile_att0, TNW_HEAD_ARGS(tm), nblk, tm, ae);
       else
-        hipLaunchKernelGGL((gemm_tn_multi_x3w_att0_kernel<8, 5>), dim3((unsigned)nblk + 1), dim3(512), gemm_tn_multi_x3w_lds_bytes<8>(), e.stream, tm, ae);
+        hipLaunchKernelGGL((gemm_tn_multi_x3w_att0_kernel<8, 5>), dim3((unsigned)nblk + 1), dim3(512), gemm_tn_multi_x3w_lds_bytes<8>(), e.stream, ae.st, ae.tile_att0, TNW_HEAD_ARGS(tm), nblk, tm, ae);
     } else
     if (tw.ktw0 == 9)
-      hipLaunchKernelGGL((gemm_tn_multi_x3w_kernel<9, 5>), dim3((unsigned)nblk), dim3(512), gemm_tn_multi_x3w_lds_bytes<9>(), e.stream, tm);
+      hipLaunchKernelGGL((gemm_tn_multi_x3w_kernel<9, 5>), dim3((unsigned)nblk), dim3(512), gemm_tn_multi_x3w_lds_bytes<9>(), e.stream, TNW_HEAD_ARGS(tm), tm);
     else
-      hipLaunchKernelGGL((gemm_tn_multi_x3w_kernel<8, 5>), dim3((unsigned)nblk), dim3(512), gemm_tn_multi_x3w_lds_bytes<8>(), e.stream, tm);
+      hipLaunchKernelGGL((gemm_tn_multi_x3w_kernel<8, 5>), dim3((unsigned)nblk), dim3(512), gemm_tn_multi_x3w_lds_bytes<8>(), e.stream, TNW_HEAD_ARGS(tm), tm);
     GOCTR_HIP(hipGetLastError());
   }
   if (tm.dbg) {

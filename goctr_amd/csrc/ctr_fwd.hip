@@ -24,9 +24,9 @@ int chain_x3_fwd_attributes() {
 
 void launch_chain_x3_fwd(int nch0, const ChainX3Args& a, dim3 grid, hipStream_t s) {
   switch (nch0) {
-    case 2: hipLaunchKernelGGL((ctr_chain_x3_kernel<2, true>), grid, dim3(512), chain_x3_lds_bytes<2>(), s, a); break;
-    case 9: hipLaunchKernelGGL((ctr_chain_x3_kernel<9, true>), grid, dim3(512), chain_x3_lds_bytes<9>(), s, a); break;
-    default: hipLaunchKernelGGL((ctr_chain_x3_kernel<15, true>), grid, dim3(512), chain_x3_lds_bytes<15>(), s, a); break;
+    case 2: hipLaunchKernelGGL((ctr_chain_x3_kernel<2, true>), grid, dim3(512), chain_x3_lds_bytes<2>(), s, CX_HEAD_ARGS(a), a); break;
+    case 9: hipLaunchKernelGGL((ctr_chain_x3_kernel<9, true>), grid, dim3(512), chain_x3_lds_bytes<9>(), s, CX_HEAD_ARGS(a), a); break;
+    default: hipLaunchKernelGGL((ctr_chain_x3_kernel<15, true>), grid, dim3(512), chain_x3_lds_bytes<15>(), s, CX_HEAD_ARGS(a), a); break;
   }
 }
 
@@ -40,9 +40,9 @@ int fwd4_attributes() {
 // (Ip = 144 with the exchange one H2 tile at a time measured the same as with one exchange: 626 / 627 / 614 against 631 / 612 / 608 M
 // rows/s; Ip = 240 needs it to fit two workgroups per CU)
 void launch_fwd4(int nch0, const ChainX3Args& a, dim3 grid, hipStream_t s) {
-  if (nch0 == 2) hipLaunchKernelGGL((ctr_fwd4_kernel<2, false>), grid, dim3(256), (fwd4_lds_bytes<2, false>()), s, a);
-  else if (nch0 == 9) hipLaunchKernelGGL((ctr_fwd4_kernel<9, false>), grid, dim3(256), (fwd4_lds_bytes<9, false>()), s, a);
-  else hipLaunchKernelGGL((ctr_fwd4_kernel<15, true>), grid, dim3(256), (fwd4_lds_bytes<15, true>()), s, a);
+  if (nch0 == 2) hipLaunchKernelGGL((ctr_fwd4_kernel<2, false>), grid, dim3(256), (fwd4_lds_bytes<2, false>()), s, CX_HEAD_ARGS(a), a);
+  else if (nch0 == 9) hipLaunchKernelGGL((ctr_fwd4_kernel<9, false>), grid, dim3(256), (fwd4_lds_bytes<9, false>()), s, CX_HEAD_ARGS(a), a);
+  else hipLaunchKernelGGL((ctr_fwd4_kernel<15, true>), grid, dim3(256), (fwd4_lds_bytes<15, true>()), s, CX_HEAD_ARGS(a), a);
 }
 
 }  // namespace goctr

@@ -40,7 +40,8 @@ inline size_t fwd4_lds_bytes() {
 }
 
 template <int NCH0, bool XU>
-__global__ __launch_bounds__(256, 2) void ctr_fwd4_kernel(ChainX3Args a) {
+__global__ __launch_bounds__(256, 2) void ctr_fwd4_kernel(CX_HEAD_PARAMS, ChainX3Args as) {
+  const ChainX3Args a = cx_with_head(as, CX_HEAD_NAMES);     // (the hot values from the preloaded leading arguments: ctr_chain_x3.h)
   extern __shared__ __attribute__((aligned(16))) unsigned char f4_smem[];
   unsigned char* const h0img = f4_smem;                                              // [NCH0][3][64 lanes][16 B]
   float* const xch = reinterpret_cast<float*>(f4_smem + (size_t)NCH0 * 3 * 1024);   // [4 waves][NU][4 g][64][4]

@@ -474,8 +474,21 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a, int blk, long l
     hrow[a.U + 2 * D + j] = KEYS ? (kirow ? kirow[j] : 0.f) : (valid ? (idm ? s.cfeat[gr * a.C + j] : s.X[gr * (long long)s.xcols + s.r_c + j]) : 0.f);
 }
 
+// Round 7 (see CX_HEAD_PARAMS, ctr_chain_x3.h): the values in front of an attention wavefront's first requests -- the step state, then
+// the sample's ids, then their rows -- as plain leading kernel arguments, which arrive in SGPRs with the wavefront; with `st` there the
+// state load leaves with the kernel's first instruction, beside the load of the argument struct instead of behind it.  12 dwords.
+#define ATTN_HEAD_PARAMS const StepState* st_, long long rows_, const int32_t* ub_ids_, const int32_t* item_ids_, const float* emb_, int B_, int T_
+#define ATTN_HEAD_ARGS(a) (a).st, (a).src.rows, (a).src.ub_ids, (a).src.item_ids, (a).src.emb, (a).B, (a).T
+#define ATTN_HEAD_NAMES st_, rows_, ub_ids_, item_ids_, emb_, B_, T_
+__device__ __forceinline__ AttnArgs attn_with_head(const AttnArgs& as, ATTN_HEAD_PARAMS) {
+  AttnArgs a = as;
+  a.st = st_; a.src.rows = rows_; a.src.ub_ids = ub_ids_; a.src.item_ids = item_ids_; a.src.emb = emb_; a.B = B_; a.T = T_;
+  return a;
+}
+
 template <int VEC, int LPR, int FAST>
-__global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
+__global__ __launch_bounds__(256) void attn_fwd_kernel(ATTN_HEAD_PARAMS, AttnArgs as) {
+  const AttnArgs a = attn_with_head(as, ATTN_HEAD_NAMES);
   const int grp = xcd_unit_of_block((int)blockIdx.x, (a.B + 3) >> 2, 32);
   attn_fwd_body<VEC, LPR, FAST>(a, grp, a.st->batch_idx, a.att0);
 }
@@ -950,9 +963,16 @@ __global__ void step_state_corr_kernel(StepState* st, double beta1, double beta2
 #endif
 
 #ifndef GOCTR_NO_PLAIN_KERNELS   // (the other CTR translation units include this header for its types and templates only)
-__global__ __launch_bounds__(256) void reduce_adam_kernel(ReduceAdamArgs p) {
+// (round 7, leading arguments as in ATTN_HEAD_PARAMS: what a reduce block's first requests stand behind -- the state with the bias
+// corrections, its parameters and moments, and the tests that say which are its own; 12 dwords)
+__global__ __launch_bounds__(256) void reduce_adam_kernel(const StepState* st_, float* W_, float* Mo_, float* Vo_, int nflat_, int skip_begin_,
+                                                          int skip_len_, int ra_block_, ReduceAdamArgs ps) {
+  ReduceAdamArgs p = ps;
+  p.r.st = st_; p.ad.W = W_; p.ad.Mo = Mo_; p.ad.Vo = Vo_; p.r.nflat = nflat_; p.skip_begin = skip_begin_; p.skip_len = skip_len_;
+  p.ra_block = ra_block_;
   reduce_adam_body(p, (int)blockIdx.x, (int)gridDim.x);
 }
+#define REDUCE_ADAM_HEAD_ARGS(p) (p).r.st, (p).ad.W, (p).ad.Mo, (p).ad.Vo, (p).r.nflat, (p).skip_begin, (p).skip_len, (p).ra_block
 #endif
 
 // ---------------------------------------------------------------- the step's last launch merged with the NEXT step's first
@@ -966,7 +986,12 @@ __global__ __launch_bounds__(256) void reduce_adam_kernel(ReduceAdamArgs p) {
 // cost little more than the longer one, and the step loses a launch boundary.
 // tests/test_gpu_ctr.py::test_graph_replay_equals_eager compares this (graph) path with the unmerged eager one bit by bit.
 template <int VEC, int LPR, int FAST>
-__global__ __launch_bounds__(256) void reduce_attn_kernel(ReduceAdamArgs p, AttnArgs a, int nred) {
+__global__ __launch_bounds__(256) void reduce_attn_kernel(ATTN_HEAD_PARAMS, int nred, ReduceAdamArgs ps, AttnArgs as) {
+  // (the leading arguments: the attention part's, then the split between the two parts -- 13 dwords; the state pointer is the one both
+  // parts read, launch_reduce_attn builds the attention arguments on p.r.st)
+  ReduceAdamArgs p = ps;
+  p.r.st = st_;
+  const AttnArgs a = attn_with_head(as, ATTN_HEAD_NAMES);
   if ((int)blockIdx.x < nred) { reduce_adam_body(p, (int)blockIdx.x, nred); return; }
   const ReduceArgs& r = p.r;
   long long nb = r.st->batch_idx + 1;                          // advance_state()'s cursor

@@ -424,6 +424,9 @@ struct TnProblem {
   int nbt;
 };
 struct TnMulti { TnProblem p[4]; int np; int M; unsigned long long* dbg; };
+// what the bodies below read of the launch's arguments besides their problem: passed on its own, so that a kernel can hand them the
+// values of its preloaded leading arguments (TNW_HEAD_PARAMS) instead of members of the by-value struct
+struct TnHot { int M; unsigned long long* dbg; };
 // does the multi-problem launch take problems whose widest D operand has nt_max 16-column tiles?
 inline bool gemm_tn_multi_fits(int nt_max) { return nt_max <= 16; }
 
@@ -460,7 +463,7 @@ __device__ __forceinline__ void tn_split3_pk(float x0, float x1, unsigned int& h
 // WT (the wide launch): every slab store goes THROUGH the L2 (global_store ... sc1) instead of staying dirty in it until the
 // launch ends.
 template <int KTW, int NTW, bool WT>
-__device__ __forceinline__ void tn_multi_body_x3(const TnMulti& a, const TnProblem& P, int kb, int n0t, int nb_t, int split,
+__device__ __forceinline__ void tn_multi_body_x3(const TnHot& a, const TnProblem& P, int kb, int n0t, int nb_t, int split,
                                                  unsigned char* smem) {
   typedef float acc_t __attribute__((ext_vector_type(4)));
   typedef float vec_t __attribute__((ext_vector_type(4)));
@@ -719,10 +722,11 @@ __global__ __launch_bounds__(512) void gemm_tn_multi_x3_kernel(TnMulti a) {
 #pragma unroll
   for (int k = 1; k < 4; ++k) if (k < a.np && (int)blockIdx.x >= a.p[k].first) pi = k;
   const TnProblem& P = a.p[pi];
+  const TnHot hot{a.M, a.dbg};
   const int local = blockIdx.x - P.first;
   const int kb = local / P.S, split = local - kb * P.S;
-  if (P.KT == 1) tn_multi_body_x3<1, NTW, false>(a, P, kb, 0, P.NT, split, goctr_smem);
-  else tn_multi_body_x3<KTW, NTW, false>(a, P, kb, 0, P.NT, split, goctr_smem);
+  if (P.KT == 1) tn_multi_body_x3<1, NTW, false>(hot, P, kb, 0, P.NT, split, goctr_smem);
+  else tn_multi_body_x3<KTW, NTW, false>(hot, P, kb, 0, P.NT, split, goctr_smem);
 }
 
 // Round 6: "sum problems" (TnProblem::KT == 0).  Where the chain launch has already summed a gradient over the 32 rows of each of
@@ -731,7 +735,7 @@ __global__ __launch_bounds__(512) void gemm_tn_multi_x3_kernel(TnMulti a) {
 // D = the partials [tiles][lda], workgroup `split` adds tiles [split * rows, (split + 1) * rows) in ascending order (16 loads in
 // flight) and writes slab `split` in the layout the MFMA problem wrote: transposed (dW2): out[idx * ld_out + 0] with the other
 // ld_out - 1 entries of the row zero; untransposed (att0): out[idx] (row 0 of the slab, the only one the reduce reads).
-__device__ __forceinline__ void tn_tile_sum_body(const TnMulti& a, const TnProblem& P, int split) {
+__device__ __forceinline__ void tn_tile_sum_body(const TnHot& a, const TnProblem& P, int split) {
   const int ntiles = (a.M + 31) >> 5;
   const int t0 = split * P.rows;
   int t1 = t0 + P.rows; if (t1 > ntiles) t1 = ntiles;
@@ -762,27 +766,39 @@ __device__ __forceinline__ void tn_tile_sum_body(const TnMulti& a, const TnProbl
 // 3-tile k-block: dz0 three times, A0 twice), and the slabs of the two problems get their own heights so that the
 // differently sized blocks cost the same.  One-tile problems keep the <1, 4> body.
 // (the kernel's body as a function: ctr_chain_x3.h's gemm_tn_multi_x3w_att0_kernel runs it in all of its workgroups but the last)
+// Round 7: what a workgroup needs to find its problem -- the problem count and the first block of problems 1..3 -- with the batch
+// height and the stamp buffer as plain leading kernel arguments: they arrive in SGPRs with the wavefront (see CX_HEAD_PARAMS,
+// ctr_chain_x3.h), so the problem is known at the first instruction.  Its descriptor is then copied BY VALUE in one group of scalar
+// loads: read member by member through a reference, each use in a new basic block was its own load and wait -- first / S, KT, rows / M,
+// the operand pointers, dbg: with the grid size and the first-block table seven dependent trips to the argument buffer before the
+// first row request (profiles/r07_arg_preload.txt).
+#define TNW_HEAD_PARAMS unsigned long long* dbg_, int M_, int np_, int first1_, int first2_, int first3_
+#define TNW_HEAD_ARGS(a) (a).dbg, (a).M, (a).np, (a).p[1].first, (a).p[2].first, (a).p[3].first
+#define TNW_HEAD_NAMES dbg_, M_, np_, first1_, first2_, first3_
 template <int KTW0, int KTW1>
-__device__ __forceinline__ void tn_multi_x3w_block(const TnMulti& a, unsigned char* goctr_smem) {
+__device__ __forceinline__ void tn_multi_x3w_block(const TnMulti& a, TNW_HEAD_PARAMS, unsigned char* goctr_smem) {
+  const int bid = (int)blockIdx.x;
   int pi = 0;
-#pragma unroll
-  for (int k = 1; k < 4; ++k) if (k < a.np && (int)blockIdx.x >= a.p[k].first) pi = k;
-  const TnProblem& P = a.p[pi];
-  const int local = blockIdx.x - P.first;
+  if (1 < np_ && bid >= first1_) pi = 1;
+  if (2 < np_ && bid >= first2_) pi = 2;
+  if (3 < np_ && bid >= first3_) pi = 3;
+  const TnProblem P = a.p[pi];
+  const TnHot hot{M_, dbg_};
+  const int local = bid - P.first;
   const int blk = local / P.S, split = local - blk * P.S;
-  if (P.KT == 0) { tn_tile_sum_body(a, P, local); return; }
-  if (P.KT == 1) { tn_multi_body_x3<1, 4, true>(a, P, blk, 0, P.NT, split, goctr_smem); return; }
+  if (P.KT == 0) { tn_tile_sum_body(hot, P, local); return; }
+  if (P.KT == 1) { tn_multi_body_x3<1, 4, true>(hot, P, blk, 0, P.NT, split, goctr_smem); return; }
   const int nnb = P.nnb > 0 ? P.nnb : 1;
   const int kb = blk / nnb, nb = blk - kb * nnb;
   const int n0t = nb * P.nbt;
   int nb_t = P.NT - n0t; if (nb_t > P.nbt) nb_t = P.nbt;
-  if (pi == 0) tn_multi_body_x3<KTW0, 2, true>(a, P, kb, n0t, nb_t, split, goctr_smem);
-  else tn_multi_body_x3<KTW1, 2, true>(a, P, kb, n0t, nb_t, split, goctr_smem);
+  if (pi == 0) tn_multi_body_x3<KTW0, 2, true>(hot, P, kb, n0t, nb_t, split, goctr_smem);
+  else tn_multi_body_x3<KTW1, 2, true>(hot, P, kb, n0t, nb_t, split, goctr_smem);
 }
 template <int KTW0, int KTW1>
-__global__ __launch_bounds__(512) void gemm_tn_multi_x3w_kernel(TnMulti a) {
+__global__ __launch_bounds__(512) void gemm_tn_multi_x3w_kernel(TNW_HEAD_PARAMS, TnMulti a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char goctr_smem[];
-  tn_multi_x3w_block<KTW0, KTW1>(a, goctr_smem);
+  tn_multi_x3w_block<KTW0, KTW1>(a, TNW_HEAD_NAMES, goctr_smem);
 }
 template <int KTW>
 inline size_t gemm_tn_multi_x3w_lds_bytes() {

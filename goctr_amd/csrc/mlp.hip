@@ -184,11 +184,11 @@ int backward(goctr_mlp* p, int n, bool do_update, bool advance, int valid = -1) 
     GOCTR_CHECK(valid == n, "the data-parallel MLP step takes whole batches only");
     a.world = e.eff_world(); a.n = n * e.eff_world();
     a.mode = 3; a.do_update = 0;
-    hipLaunchKernelGGL(mlp_reduce_update_kernel, dim3(nblk + 1), dim3(256), 0, e.stream, a);
+    hipLaunchKernelGGL(mlp_reduce_update_kernel, dim3(nblk + 1), dim3(256), 0, e.stream, MLP_REDUCE_HEAD_ARGS(a), a);
     GOCTR_HIP(hipGetLastError());
     if (comm_allreduce_f64_dev(p->G.p, (size_t)p->nflat + 1)) return -1;
     a.mode = 1; a.do_update = 1;
-    hipLaunchKernelGGL(mlp_reduce_update_kernel, dim3(nblk + 1), dim3(256), 0, e.stream, a);
+    hipLaunchKernelGGL(mlp_reduce_update_kernel, dim3(nblk + 1), dim3(256), 0, e.stream, MLP_REDUCE_HEAD_ARGS(a), a);
     GOCTR_HIP(hipGetLastError());
     return 0;
   }
@@ -208,7 +208,7 @@ int backward(goctr_mlp* p, int n, bool do_update, bool advance, int valid = -1) 
     // prefetch fills is the memory-side cache); at B 200 (13 workgroups) it is the best (24.9 against 25.3 us per update)
     a.pf_xcd_shift = cdiv(p->cfg.batch, 16) >= 64 ? 4 : 0;
   }
-  hipLaunchKernelGGL(mlp_reduce_update_kernel, dim3(nblk + 1 + pf_blocks), dim3(256), 0, e.stream, a);   // block nblk: loss + state
+  hipLaunchKernelGGL(mlp_reduce_update_kernel, dim3(nblk + 1 + pf_blocks), dim3(256), 0, e.stream, MLP_REDUCE_HEAD_ARGS(a), a);   // block nblk: loss + state
   GOCTR_HIP(hipGetLastError());
   if (dbg) {
     unsigned long long h[18];
@@ -229,7 +229,7 @@ int refresh_sumsq(goctr_mlp* p, const MlpState* st) {
     a.L[l] = {p->units[l], p->units[l + 1], p->up[l], p->up[l + 1], p->woff[l], p->poff[l], nullptr, 0, nullptr, 0};
   a.nflat = p->nflat; a.nparams = p->nparams; a.W = p->W.p; a.st = st; a.sumsq_part = p->sumsq_part.p;
   a.mode = 2; a.nblk = (int)cdiv(p->nflat, 256);
-  hipLaunchKernelGGL(mlp_reduce_update_kernel, dim3(a.nblk), dim3(256), 0, engine().stream, a);
+  hipLaunchKernelGGL(mlp_reduce_update_kernel, dim3(a.nblk), dim3(256), 0, engine().stream, MLP_REDUCE_HEAD_ARGS(a), a);
   GOCTR_HIP(hipGetLastError());
   return 0;
 }
@@ -304,11 +304,11 @@ int train_step_resident(goctr_mlp* p, bool use_state, long long start, bool gene
 #define GOCTR_CHAIN(ACT)                                                                                        \
     do {                                                                                                        \
       if (x64) {                                                                                                \
-        if (s17) hipLaunchKernelGGL((mlp_chain_kernel<ACT, 17, true>), cg, cb, 0, engine().stream, c);          \
-        else hipLaunchKernelGGL((mlp_chain_kernel<ACT, -1, true>), cg, cb, 0, engine().stream, c);              \
+        if (s17) hipLaunchKernelGGL((mlp_chain_kernel<ACT, 17, true>), cg, cb, 0, engine().stream, MLP_CHAIN_HEAD_ARGS(c), c);          \
+        else hipLaunchKernelGGL((mlp_chain_kernel<ACT, -1, true>), cg, cb, 0, engine().stream, MLP_CHAIN_HEAD_ARGS(c), c);              \
       } else {                                                                                                  \
-        if (s17) hipLaunchKernelGGL((mlp_chain_kernel<ACT, 17>), cg, cb, 0, engine().stream, c);                \
-        else hipLaunchKernelGGL((mlp_chain_kernel<ACT, -1>), cg, cb, 0, engine().stream, c);                    \
+        if (s17) hipLaunchKernelGGL((mlp_chain_kernel<ACT, 17>), cg, cb, 0, engine().stream, MLP_CHAIN_HEAD_ARGS(c), c);                \
+        else hipLaunchKernelGGL((mlp_chain_kernel<ACT, -1>), cg, cb, 0, engine().stream, MLP_CHAIN_HEAD_ARGS(c), c);                    \
       }                                                                                                         \
     } while (0)
     switch (p->cfg.activation) {

@@ -234,17 +234,24 @@ constexpr int MLP_PF_BLOCKS = 64;
 
 // grad = slab sum / n + alpha/n * W (coefs), mean(delta) (intercepts)  [computeLossGrad :322-330]; then the
 // optimizer step in packed-parameter order semantics.
-__global__ __launch_bounds__(256) void mlp_reduce_update_kernel(MlpReduceArgs a) {
+// Leading arguments (MLP_REDUCE_HEAD_ARGS: the same values the struct holds): the state pointer, the stamp buffer, the block's role
+// and what its first requests -- the parameter and its moments -- need.  Plain arguments are preloaded into SGPRs at wavefront start,
+// members of the by-value struct are loads from the argument buffer: 580-790 cycles after the first instruction here, in front of a
+// state load that is cold itself (profiles/r06_mlp_prefetch.txt section 7, profiles/r07_arg_preload.txt).  The body reads these eight
+// from the arguments; the struct is not copied (its layer table is indexed at run time).  14 dwords: all the user-SGPR budget leaves.
+#define MLP_REDUCE_HEAD_ARGS(a) (a).st, (a).dbg, (a).W, (a).Mo, (a).Vo, (a).nflat, (a).nblk, (a).mode
+__global__ __launch_bounds__(256) void mlp_reduce_update_kernel(const MlpState* st_, unsigned long long* dbg_, double* W_, double* Mo_, double* Vo_,
+                                                                long long nflat_, int nblk_, int mode_, MlpReduceArgs a) {
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   __shared__ double red[256];
-  const unsigned long long ts0 = a.dbg ? __builtin_amdgcn_s_memtime() : 0;
-  if ((int)blockIdx.x > a.nblk) {
+  const unsigned long long ts0 = dbg_ ? __builtin_amdgcn_s_memtime() : 0;
+  if ((int)blockIdx.x > nblk_) {
     // the rows the next step's chain launch starts with: its prologue is three dependent memory latencies (state -> permutation ->
     // row, 6.5 k cycles at cfg2); this launch leaves 100+ CUs idle, so eight blocks per XCD walk the same chain one step ahead and
     // leave the lines in the L2 their readers sit on.  Four threads per row, every 128-byte piece of it (and its label) touched once.
-    const int k = ((int)blockIdx.x - a.nblk - 1) >> 3, xcd = ((int)blockIdx.x + a.pf_xcd_shift) & 7;
-    long long nb = a.st->batch_idx + 1;
-    if (nb >= a.st->n_batches) nb = 0;
+    const int k = ((int)blockIdx.x - nblk_ - 1) >> 3, xcd = ((int)blockIdx.x + a.pf_xcd_shift) & 7;
+    long long nb = st_->batch_idx + 1;
+    if (nb >= st_->n_batches) nb = 0;
     const int t = k * 256 + (int)threadIdx.x, sub = t & 3, rl = t >> 2;
     for (int w = xcd + 8 * (rl >> 4); w * 16 < a.pf_batch; w += 8 * (MLP_PF_BLOCKS / 8) * 4) {
       const int row = w * 16 + (rl & 15);
@@ -262,18 +269,18 @@ __global__ __launch_bounds__(256) void mlp_reduce_update_kernel(MlpReduceArgs a)
       }
       if (acc == 1.2345678e-30f) a.pf_sink[t] = acc;    // (keeps the loads; a scratch word nobody reads)
     }
-    if (a.dbg && (int)blockIdx.x == a.nblk + 1 && threadIdx.x == 0) { a.dbg[12] = ts0; a.dbg[13] = __builtin_amdgcn_s_memtime(); }
+    if (dbg_ && (int)blockIdx.x == nblk_ + 1 && threadIdx.x == 0) { dbg_[12] = ts0; dbg_[13] = __builtin_amdgcn_s_memtime(); }
     return;
   }
   // The step state is read through a per-lane copy of its address: the compiler turns a load from a uniform address into load +
   // wait + readfirstlane WHERE IT STANDS -- a whole memory latency (3.4 k cycles at a launch's start, GOCTR_DBG=mlp) in front of
   // every other request of the block.  As a vector load it is waited for where its value is used: at the block's end.
-  unsigned long long st_va = reinterpret_cast<unsigned long long>(a.st);
+  unsigned long long st_va = reinterpret_cast<unsigned long long>(st_);
   asm volatile("" : "+v"(st_va));
   const MlpState* stv = reinterpret_cast<const MlpState*>(st_va);
   const long long st_t = stv->t;
   const double st_lr = stv->lr;
-  if ((int)blockIdx.x == a.nblk) {
+  if ((int)blockIdx.x == nblk_) {
     // loss = sum(terms)/n + 0.5*alpha*sum(W^2)/n (basemlp64.go:359-361) over the weights the forward pass used: their
     // squares were summed per block by the launch that wrote them (parity `par`); closes the step
     // every request of the block (state, both parities of the per-block sums of squares, the all-reduced term sum, the loss terms) is
@@ -283,11 +290,11 @@ __global__ __launch_bounds__(256) void mlp_reduce_update_kernel(MlpReduceArgs a)
     const unsigned int st_slot = stv->slot;
     const long long st_bi = stv->batch_idx, st_nb = stv->n_batches;
     double q0 = 0, q1 = 0;
-    if (a.mode != 3)
-      for (int i = threadIdx.x; i < a.nblk; i += 256) { q0 += a.sumsq_part[i]; q1 += a.sumsq_part[(size_t)a.nblk + i]; }
-    const double g_l = a.mode == 1 ? a.G[a.nflat] : 0.0;
+    if (mode_ != 3)
+      for (int i = threadIdx.x; i < nblk_; i += 256) { q0 += a.sumsq_part[i]; q1 += a.sumsq_part[(size_t)nblk_ + i]; }
+    const double g_l = mode_ == 1 ? a.G[nflat_] : 0.0;
     double s = 0;
-    const int real = a.mode == 1 ? 0 : a.n_local * a.no;      // only the `no` real columns of each padded row carry a term
+    const int real = mode_ == 1 ? 0 : a.n_local * a.no;      // only the `no` real columns of each padded row carry a term
     for (int i0 = threadIdx.x; i0 < real; i0 += 256 * 16) {
       double v[16];
 #pragma unroll
@@ -307,11 +314,11 @@ __global__ __launch_bounds__(256) void mlp_reduce_update_kernel(MlpReduceArgs a)
       __syncthreads();
     }
     double lsum = red[0];
-    if (a.mode == 3) {                         // data-parallel first half: the local term sum travels with the gradient
-      if (threadIdx.x == 0) a.G[a.nflat] = lsum;
+    if (mode_ == 3) {                         // data-parallel first half: the local term sum travels with the gradient
+      if (threadIdx.x == 0) a.G[nflat_] = lsum;
       return;
     }
-    if (a.mode == 1) lsum = g_l;
+    if (mode_ == 1) lsum = g_l;
     if (threadIdx.x == 0) {
       a.ring[st_slot % MLP_LOSS_RING] = lsum / (double)(a.n_loss ? a.n_loss : a.n) + (0.5 * a.alpha) * redq[0] / (double)a.n;
       if (a.advance) {
@@ -324,7 +331,7 @@ __global__ __launch_bounds__(256) void mlp_reduce_update_kernel(MlpReduceArgs a)
         ns.batch_idx = nb >= st_nb ? 0 : nb;
         *a.st_master = ns;
       }
-      if (a.dbg) { a.dbg[6] = ts0; a.dbg[7] = __builtin_amdgcn_s_memtime(); }
+      if (dbg_) { dbg_[6] = ts0; dbg_[7] = __builtin_amdgcn_s_memtime(); }
     }
     return;
   }
@@ -338,18 +345,18 @@ __global__ __launch_bounds__(256) void mlp_reduce_update_kernel(MlpReduceArgs a)
   const long long idx0 = (long long)blockIdx.x * 256;
   // (round 6: the parameter and its moments are requested HERE, in front of the slab sums -- behind them they were two more dependent
   // round trips of a launch that is nothing but round trips: state -> slabs -> W -> moments -> stores)
-  const bool pre = idx < a.nflat && a.mode != 2;
-  const double w_pre = pre ? a.W[idx] : 0.0;
-  const double m_pre = pre && a.do_update && a.solver == GOCTR_SOLVER_ADAM ? a.Mo[idx] : 0.0;
-  const double v_pre = pre && a.do_update && a.solver == GOCTR_SOLVER_ADAM ? a.Vo[idx] : 0.0;
+  const bool pre = idx < nflat_ && mode_ != 2;
+  const double w_pre = pre ? W_[idx] : 0.0;
+  const double m_pre = pre && a.do_update && a.solver == GOCTR_SOLVER_ADAM ? Mo_[idx] : 0.0;
+  const double v_pre = pre && a.do_update && a.solver == GOCTR_SOLVER_ADAM ? Vo_[idx] : 0.0;
   const double vel_pre = pre && a.do_update && a.solver != GOCTR_SOLVER_ADAM ? a.Vel[idx] : 0.0;
   double coop_sum = 0; bool coop_have = false;
   unsigned long long ts1 = 0, ts2 = 0, ts3 = 0;
-  if (a.dbg) { ts1 = __builtin_amdgcn_s_memtime(); }
-  if (a.mode == 0 || a.mode == 3) {
+  if (dbg_) { ts1 = __builtin_amdgcn_s_memtime(); }
+  if (mode_ == 0 || mode_ == 3) {
     __shared__ double red2[256];
     double part = 0; bool lead = false; int upo = 1;
-    if (idx < a.nflat) {
+    if (idx < nflat_) {
       int l = 0;
 #pragma unroll
       for (int k = 1; k < 7; ++k) if (k < a.nl && idx0 >= a.L[k].woff) l = k;
@@ -382,18 +389,18 @@ __global__ __launch_bounds__(256) void mlp_reduce_update_kernel(MlpReduceArgs a)
       coop_have = true;
     }
   }
-  if (a.mode == 2) {          // (re)build the partial sums of squares of the current weights
-    if (idx < a.nflat) {
+  if (mode_ == 2) {          // (re)build the partial sums of squares of the current weights
+    if (idx < nflat_) {
       int l = 0;
 #pragma unroll
       for (int k = 1; k < 7; ++k) if (k < a.nl && idx0 >= a.L[k].woff) l = k;
       const MlpLayerDesc& d = a.L[l];
       const long long e = idx - d.woff;
       const int r = (int)(e / d.upo), c = (int)(e - (long long)r * d.upo);
-      if (r < d.fi && c < d.fo) { const double w = a.W[idx]; sq = w * w; }
+      if (r < d.fi && c < d.fo) { const double w = W_[idx]; sq = w * w; }
     }
   } else
-  if (idx < a.nflat) {
+  if (idx < nflat_) {
     int l = 0;
 #pragma unroll
     for (int k = 1; k < 7; ++k) if (k < a.nl && idx0 >= a.L[k].woff) l = k;
@@ -405,7 +412,7 @@ __global__ __launch_bounds__(256) void mlp_reduce_update_kernel(MlpReduceArgs a)
       double s = 0;
       if (coop_have) s = coop_sum;
       else
-      if (a.mode != 1) {   // same left-to-right order as a plain loop, but 8 loads in flight at a time
+      if (mode_ != 1) {   // same left-to-right order as a plain loop, but 8 loads in flight at a time
         const size_t sstr = (size_t)d.upi * d.upo;
         const int ei = (int)e;
         for (int j0 = 0; j0 < d.nslabs; j0 += 48) {           // unconditional loads (clamped), all in flight at once
@@ -422,8 +429,8 @@ __global__ __launch_bounds__(256) void mlp_reduce_update_kernel(MlpReduceArgs a)
       }
       const double w = w_pre;
       double g;
-      if (a.dbg) ts2 = __builtin_amdgcn_s_memtime() + (s == 1.234e-300 ? 1 : 0);
-      if (a.mode == 1) {
+      if (dbg_) ts2 = __builtin_amdgcn_s_memtime() + (s == 1.234e-300 ? 1 : 0);
+      if (mode_ == 1) {
         g = a.G[idx];                                         // summed over the ranks by the all-reduce
       } else {
         g = s * (1 / (double)(is_b && a.n_bias ? a.n_bias : a.n));   // gemm alpha = 1/n (and mean for the bias row)
@@ -436,7 +443,7 @@ __global__ __launch_bounds__(256) void mlp_reduce_update_kernel(MlpReduceArgs a)
         if (a.solver == GOCTR_SOLVER_ADAM) {
           const double m = a.beta1 * m_pre + (1 - a.beta1) * g;
           const double v = a.beta2 * v_pre + (1 - a.beta2) * g * g;
-          a.Mo[idx] = m; a.Vo[idx] = v;
+          Mo_[idx] = m; Vo_[idx] = v;
           // quirk Q7: beta powers advance once per parameter: exponent (t-1)*n + i + 1
           const double ex = (double)(st_t * a.nparams + pidx + 1);
           // beta^ex < 2^-54 makes (1 - beta^ex) round to exactly 1: the two pow calls (most of this thread's instructions)
@@ -449,27 +456,27 @@ __global__ __launch_bounds__(256) void mlp_reduce_update_kernel(MlpReduceArgs a)
           a.Vel[idx] = upd;
           wn = a.nesterov ? w + (a.momentum * upd - st_lr * g) : w + upd;
         }
-        a.W[idx] = wn;
+        W_[idx] = wn;
         if (is_w) { d.WT[(size_t)c * d.upi + r] = wn; sq = wn * wn; }   // squares of the NEW weights: next step's penalty
         if (l == 0 && a.W0img) a.W0img[mlp_img_index(r, c, d.upi)] = wn;
       }
-    } else if (a.mode != 1) {
+    } else if (mode_ != 1) {
       a.G[idx] = 0;
     }
   }
-  if (a.dbg) ts3 = __builtin_amdgcn_s_memtime();
+  if (dbg_) ts3 = __builtin_amdgcn_s_memtime();
   red[threadIdx.x] = sq;
   __syncthreads();
   for (int s = 128; s > 0; s >>= 1) { if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s]; __syncthreads(); }
-  if (a.dbg && blockIdx.x == 0 && threadIdx.x == 0) {
-    a.dbg[0] = ts0; a.dbg[1] = ts1; a.dbg[2] = ts2; a.dbg[3] = ts3; a.dbg[4] = __builtin_amdgcn_s_memtime();
+  if (dbg_ && blockIdx.x == 0 && threadIdx.x == 0) {
+    dbg_[0] = ts0; dbg_[1] = ts1; dbg_[2] = ts2; dbg_[3] = ts3; dbg_[4] = __builtin_amdgcn_s_memtime();
   }
   // mode 2 refreshes this step's parity; an update writes the parity the NEXT step will read; a pure gradient
   // evaluation leaves the weights -- and therefore both buffers -- alone
   const int par = (int)(st_t & 1);
   if (threadIdx.x == 0) {
-    if (a.mode == 2) a.sumsq_part[(size_t)par * a.nblk + blockIdx.x] = red[0];
-    else if (a.do_update) a.sumsq_part[(size_t)(par ^ 1) * a.nblk + blockIdx.x] = red[0];
+    if (mode_ == 2) a.sumsq_part[(size_t)par * nblk_ + blockIdx.x] = red[0];
+    else if (a.do_update) a.sumsq_part[(size_t)(par ^ 1) * nblk_ + blockIdx.x] = red[0];
   }
 }
 
@@ -741,11 +748,19 @@ struct MlpChainArgs {
   unsigned long long* dbg;    // GOCTR_DBG=mlp: cycle stamps of workgroup 0, [wave][5]
 };
 
+// Leading arguments (see MLP_REDUCE_HEAD_ARGS): the weight stream's base and extent -- the kernel's first requests --, the state the
+// row chain starts from and its frozen copy, the stamp buffer, the output layer's column.  14 dwords.
+#define MLP_CHAIN_HEAD_PARAMS const double* W0img_, const MlpState* st_, MlpState* st_step_, unsigned long long* dbg_, const double* W2_, int up0_, int up1_, int upL_, int use_state_
+#define MLP_CHAIN_HEAD_ARGS(c) (c).W0img, (c).st, (c).st_step, (c).dbg, (c).W2, (c).up0, (c).up1, (c).upL, (c).use_state
 // NFULL >= 0: the number of full 16-k chunks of a row (F / 16) is a compile-time constant and the product loop is
 // straight-line code (no selects, no clamps, accumulators never leave the AGPRs); NFULL < 0: run-time loop, any F.
 // X64: the float64 image of the resident rows exists (goctr_mlp::X64): no A0 copy, the batch's row indices instead.
 template <int ACT, int NFULL, bool X64 = false>
-__global__ __launch_bounds__(256) void mlp_chain_kernel(MlpChainArgs a) {
+__global__ __launch_bounds__(256) void mlp_chain_kernel(MLP_CHAIN_HEAD_PARAMS, MlpChainArgs as) {
+  MlpChainArgs a_ = as;
+  a_.W0img = W0img_; a_.st = st_; a_.st_step = st_step_; a_.dbg = dbg_; a_.W2 = W2_; a_.up0 = up0_; a_.up1 = up1_; a_.upL = upL_;
+  a_.use_state = use_state_;
+  const MlpChainArgs& a = a_;
   typedef double d2 __attribute__((ext_vector_type(2)));
   typedef double d4 __attribute__((ext_vector_type(4)));
   typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));   // rows of F floats are only 4-byte aligned
@@ -996,8 +1011,8 @@ constexpr int TN64_KTW = 3;
 template <int KTW, bool IDX = false>
 __global__ __launch_bounds__(256, 2) void mlp_tn64_kernel(const double* __restrict__ A, int lda, int KT,
                                                           const double* __restrict__ Dm, int ldd, int NT, int M, int rows,
-                                                          double* __restrict__ slabs, size_t slab_stride,
-                                                          const int* __restrict__ ridx) {
+                                                          const int* __restrict__ ridx, double* __restrict__ slabs,
+                                                          size_t slab_stride) {
   typedef double d2 __attribute__((ext_vector_type(2)));
   typedef double d4 __attribute__((ext_vector_type(4)));
   typedef int i4u __attribute__((ext_vector_type(4), aligned(4)));
@@ -1185,10 +1200,10 @@ int launch_tn64(const double* A, int lda, int KT, const double* Dm, int ldd, int
     const size_t lds = sizeof(double) * 2 * TN64_CHS * (size_t)(TN64_KTW * 16 + NT * 16);
     if (ridx)
       hipLaunchKernelGGL((mlp_tn64_kernel<TN64_KTW, true>), grid, dim3(256), lds, engine().stream, A, lda, KT, Dm, ldd, NT, M,
-                         rows_per_wg, slabs, (size_t)KT * 16 * NT * 16, ridx);
+                         rows_per_wg, ridx, slabs, (size_t)KT * 16 * NT * 16);
     else
       hipLaunchKernelGGL(mlp_tn64_kernel<TN64_KTW>, grid, dim3(256), lds, engine().stream, A, lda, KT, Dm, ldd, NT, M,
-                         rows_per_wg, slabs, (size_t)KT * 16 * NT * 16, (const int*)nullptr);
+                         rows_per_wg, (const int*)nullptr, slabs, (size_t)KT * 16 * NT * 16);
     GOCTR_HIP(hipGetLastError());
     return 0;
   }

@@ -32,15 +32,15 @@ int main() {
   CK(hipFuncSetAttribute((const void*)ctr_chain_x3_kernel<9>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   const size_t lds = chain_x3_lds_bytes<9>();
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-  for (int i = 0; i < 5; ++i) hipLaunchKernelGGL(ctr_chain_x3_kernel<9>, dim3(B / 32), dim3(512), lds, 0, a);
+  for (int i = 0; i < 5; ++i) hipLaunchKernelGGL(ctr_chain_x3_kernel<9>, dim3(B / 32), dim3(512), lds, 0, CX_HEAD_ARGS(a), a);
   CK(hipDeviceSynchronize());
   CK(hipEventRecord(e0));
   const int N = 100;
-  for (int i = 0; i < N; ++i) hipLaunchKernelGGL(ctr_chain_x3_kernel<9>, dim3(B / 32), dim3(512), lds, 0, a);
+  for (int i = 0; i < N; ++i) hipLaunchKernelGGL(ctr_chain_x3_kernel<9>, dim3(B / 32), dim3(512), lds, 0, CX_HEAD_ARGS(a), a);
   CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
   float ms; CK(hipEventElapsedTime(&ms, e0, e1));
   a.dbg = dbg;
-  hipLaunchKernelGGL(ctr_chain_x3_kernel<9>, dim3(B / 32), dim3(512), lds, 0, a);
+  hipLaunchKernelGGL(ctr_chain_x3_kernel<9>, dim3(B / 32), dim3(512), lds, 0, CX_HEAD_ARGS(a), a);
   CK(hipDeviceSynchronize());
   unsigned long long h[8][16]; CK(hipMemcpy(h, dbg, sizeof h, hipMemcpyDeviceToHost));
   printf("%.2f us/launch (back to back); per wavefront, cycles since the workgroup's first stamp at: b1(h0 image) F0 epi0 F1 b2(Z1 xchg) b4(dz1 image) B0 BP end\n", ms * 1e3 / N);
