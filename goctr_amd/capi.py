@@ -233,6 +233,16 @@ class WalkCfg(C.Structure):
                 ("seed", C.c_uint64), ("reserved", C.c_int64)]
 
 
+class WalkSamplerCfg(C.Structure):
+    """goctr_walksampler_cfg (include/goctr.h)"""
+    _fields_ = [("damp_item", C.c_int32), ("damp_user", C.c_int32), ("reserved", C.c_int64)]
+
+
+class WalkPolicyCfg(C.Structure):
+    """goctr_walkp_cfg (include/goctr.h)"""
+    _fields_ = [("walk", WalkCfg), ("alloc", C.c_int32), ("restart_q", C.c_int32), ("reserved", C.c_int64)]
+
+
 class UsercfCfg(C.Structure):
     """goctr_usercf_cfg (include/goctr.h)"""
     _fields_ = [("max_holders", C.c_int32), ("n_nbr", C.c_int32), ("min_overlap", C.c_int32), ("reserved", C.c_int32),
@@ -338,7 +348,7 @@ NS_ALL, NS_NEWEST, NS_ALL_BUT_NEWEST = 0, 1, 2              # goctr_negsample_cf
 CALIB_STEP, CALIB_LINEAR = 0, 1                             # goctr_calib_cfg.interp
 UVMIX_MAX, UVMIX_QUOTA = 0, 1                               # goctr_uservec_multi_cfg.mix
 (FUSE_ITEMCF, FUSE_WALK, FUSE_USERVEC, FUSE_USERVEC_IVF, FUSE_ALS, FUSE_POPULAR,
- FUSE_LIST, FUSE_USERCF) = range(8)                         # goctr_fuse_channel.kind
+ FUSE_LIST, FUSE_USERCF, FUSE_WALK_POLICY) = range(9)       # goctr_fuse_channel.kind
 FUSE_RRF, FUSE_ROUND_ROBIN = 0, 1                           # goctr_fuse_cfg.mode
 FUSE_MAX_CHAN, FUSE_MAX_LISTED = 7, 4096                    # n_chan, the sum of n_list
 PRED_BORN_MIN, PRED_BORN_MAX, PRED_BORN_BEFORE_TS = 1, 2, 4 # goctr_item_pred.flags
@@ -412,6 +422,8 @@ SYMBOLS = [
     "goctr_itemattr_count", "goctr_fuse_recall_filtered", "goctr_recommend_fused_filtered",
     "goctr_usercf_cfg_default", "goctr_usercf_build", "goctr_usercf_destroy", "goctr_usercf_info", "goctr_usercf_export",
     "goctr_usercf_recall_cfg_default", "goctr_usercf_recall", "goctr_recommend_usercf",
+    "goctr_walksampler_cfg_default", "goctr_walksampler_build", "goctr_walksampler_destroy", "goctr_walksampler_info",
+    "goctr_walksampler_export", "goctr_walkp_cfg_default", "goctr_walk_recall_policy", "goctr_recommend_walk_policy",
 ]
 
 _lib = None
@@ -442,7 +454,8 @@ def load() -> C.CDLL:
                      "goctr_walkgraph_cfg_default", "goctr_walk_cfg_default", "goctr_walkgraph_destroy",
                      "goctr_edgeweight_cfg_default",
                      "goctr_als_cfg_default", "goctr_als_destroy", "goctr_ease_cfg_default", "goctr_fuse_cfg_default",
-                     "goctr_itemattr_destroy", "goctr_usercf_cfg_default", "goctr_usercf_recall_cfg_default", "goctr_usercf_destroy"):
+                     "goctr_itemattr_destroy", "goctr_usercf_cfg_default", "goctr_usercf_recall_cfg_default", "goctr_usercf_destroy",
+                     "goctr_walksampler_cfg_default", "goctr_walkp_cfg_default", "goctr_walksampler_destroy"):
             getattr(_lib, name).restype = None
         _bm = C.POINTER(BinaryMetrics)
         _lib.goctr_metrics_binary.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, _bm]
@@ -597,6 +610,18 @@ def load() -> C.CDLL:
                                                     C.c_void_p, _wk, C.c_int32, C.POINTER(RecallCfg), C.c_int32, C.c_void_p, _mmr,
                                                     C.c_int32, C.c_int64, _i32, _f32, _i32, _u8, _i32, _i32, _i64, _i32, _u32, _f32,
                                                     _u8, _i64, _i32, _u32, _i32]
+        _ws, _wp = C.POINTER(WalkSamplerCfg), C.POINTER(WalkPolicyCfg)
+        _lib.goctr_walksampler_cfg_default.argtypes = [_ws]
+        _lib.goctr_walkp_cfg_default.argtypes = [_wp]
+        _lib.goctr_walksampler_build.argtypes = [C.c_void_p, _ws, C.POINTER(C.c_void_p)]
+        _lib.goctr_walksampler_destroy.argtypes = [C.c_void_p]
+        _lib.goctr_walksampler_info.argtypes = [C.c_void_p, _i64, _i64, _i64, _u64, _i32, _ws]
+        _lib.goctr_walksampler_export.argtypes = [C.c_void_p, _u64, _u64]
+        _lib.goctr_walk_recall_policy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, C.POINTER(RecallCfg), _wp,
+                                                  _i32, _u32, _i32, _i32, _i32, _i32]
+        _lib.goctr_recommend_walk_policy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32,
+                                                     C.POINTER(RecallCfg), _wp, C.c_int32, C.c_int64, _i32, _f32, _i32, _i32, _i32,
+                                                     _i64, _i32, _u32, _f32, _i64]
         _uc, _ur = C.POINTER(UsercfCfg), C.POINTER(UsercfRecallCfg)
         _lib.goctr_usercf_cfg_default.argtypes = [_uc]
         _lib.goctr_usercf_recall_cfg_default.argtypes = [_ur]
@@ -800,6 +825,8 @@ default_popular_cfg = _default(PopularCfg, "goctr_popular_cfg_default")
 default_walkgraph_cfg = _default(WalkGraphCfg, "goctr_walkgraph_cfg_default")
 default_edgeweight_cfg = _default(EdgeWeightCfg, "goctr_edgeweight_cfg_default")
 default_walk_cfg = _default(WalkCfg, "goctr_walk_cfg_default")
+default_walksampler_cfg = _default(WalkSamplerCfg, "goctr_walksampler_cfg_default")
+default_walkp_cfg = _default(WalkPolicyCfg, "goctr_walkp_cfg_default")
 default_usercf_cfg = _default(UsercfCfg, "goctr_usercf_cfg_default")
 default_usercf_recall_cfg = _default(UsercfRecallCfg, "goctr_usercf_recall_cfg_default")
 default_als_cfg = _default(AlsCfg, "goctr_als_cfg_default")

@@ -4,8 +4,8 @@
 // tests/fuse_ref.py restates them on the host, bit for bit).  All arithmetic is integer.
 //
 // Launches of one call, back to back on one stream (FuseStage::launch):
-//   the model channels' own launchers (recall_launch, walk_launch, uservec_launch, uservec_ivf_launch, als_launch, usercf_launch),
-//   unchanged, each
+//   the model channels' own launchers (recall_launch, walk_launch, walkp_launch, uservec_launch, uservec_ivf_launch, als_launch,
+//   usercf_launch), unchanged, each
 //   into a scratch list of its own at stride n_list -- the bytes the channel's stand-alone entry returns
 //   fuse_kernel    one workgroup per request row:
 //     1. a POPULAR or LIST channel's entries are walked in tiles of SEL_THREADS source positions as blend_fill_kernel walks its
@@ -205,14 +205,17 @@ __global__ __launch_bounds__(SEL_THREADS) void fuse_kernel(FuseKernelArgs a, Fil
   }
 }
 
-bool fuse_is_model(int kind) { return (kind >= GOCTR_FUSE_ITEMCF && kind <= GOCTR_FUSE_ALS) || kind == GOCTR_FUSE_USERCF; }
+bool fuse_is_model(int kind) {
+  return (kind >= GOCTR_FUSE_ITEMCF && kind <= GOCTR_FUSE_ALS) || kind == GOCTR_FUSE_USERCF || kind == GOCTR_FUSE_WALK_POLICY;
+}
 
 // the engine, the items and (a walk graph's or user neighbour lists', else -1) the users of a channel's handle; LIST has none
 void fuse_handle_info(const goctr_fuse_channel& ch, Engine** eng, long long* n_items, long long* n_users) {
   *eng = nullptr; *n_items = -1; *n_users = -1;
   switch (ch.kind) {
     case GOCTR_FUSE_ITEMCF: { auto h = static_cast<const goctr_itemcf*>(ch.handle); *eng = h->eng; *n_items = h->n_items; break; }
-    case GOCTR_FUSE_WALK: {
+    case GOCTR_FUSE_WALK:
+    case GOCTR_FUSE_WALK_POLICY: {
       auto h = static_cast<const goctr_walkgraph*>(ch.handle);
       *eng = h->eng; *n_items = h->n_items; *n_users = h->n_users;
       break;
@@ -237,7 +240,7 @@ namespace goctr {
 Engine* fuse_engine(const goctr_fuse_channel* chan, int n_chan) {
   if (!chan || n_chan < 1 || n_chan > FUSE_MAX_CHAN) return nullptr;
   for (int c = 0; c < n_chan; ++c) {
-    if (chan[c].kind < GOCTR_FUSE_ITEMCF || chan[c].kind > GOCTR_FUSE_USERCF || chan[c].kind == GOCTR_FUSE_LIST || !chan[c].handle) continue;
+    if (chan[c].kind < GOCTR_FUSE_ITEMCF || chan[c].kind > GOCTR_FUSE_WALK_POLICY || chan[c].kind == GOCTR_FUSE_LIST || !chan[c].handle) continue;
     Engine* e; long long ni, nu;
     fuse_handle_info(chan[c], &e, &ni, &nu);
     return e;
@@ -254,20 +257,24 @@ int fuse_check(const char* who, const goctr_fuse_channel* chan, int n_chan, cons
   long long sum_list = 0, sum_reserve = 0;
   for (int c = 0; c < n_chan; ++c) {
     const goctr_fuse_channel& ch = chan[c];
-    GOCTR_CHECK(ch.kind >= GOCTR_FUSE_ITEMCF && ch.kind <= GOCTR_FUSE_USERCF, "%s: channel %d: kind = %d is no GOCTR_FUSE_* kind", who, c, ch.kind);
+    GOCTR_CHECK(ch.kind >= GOCTR_FUSE_ITEMCF && ch.kind <= GOCTR_FUSE_WALK_POLICY, "%s: channel %d: kind = %d is no GOCTR_FUSE_* kind", who, c, ch.kind);
     GOCTR_CHECK(ch.n_list >= 1 && ch.n_list <= 1024, "%s: channel %d: n_list = %d is outside 1 .. 1024", who, c, ch.n_list);
     GOCTR_CHECK(ch.weight <= 65535u, "%s: channel %d: weight = %u is outside 0 .. 65535", who, c, ch.weight);
     GOCTR_CHECK(ch.reserve >= 0 && ch.reserve <= ch.n_list, "%s: channel %d: reserve = %d is outside 0 .. n_list = %d", who, c, ch.reserve,
                 ch.n_list);
     const bool is_list = ch.kind == GOCTR_FUSE_LIST, is_als = ch.kind == GOCTR_FUSE_ALS, is_ucf = ch.kind == GOCTR_FUSE_USERCF;
-    const bool takes_cfg = ch.kind == GOCTR_FUSE_WALK || ch.kind == GOCTR_FUSE_USERVEC || ch.kind == GOCTR_FUSE_USERVEC_IVF || is_als || is_ucf;
+    const bool is_wp = ch.kind == GOCTR_FUSE_WALK_POLICY;
+    const bool takes_cfg = ch.kind == GOCTR_FUSE_WALK || ch.kind == GOCTR_FUSE_USERVEC || ch.kind == GOCTR_FUSE_USERVEC_IVF || is_als || is_ucf || is_wp;
     GOCTR_CHECK((ch.handle != nullptr) == !is_list, "%s: channel %d: %s", who, c, is_list ? "a LIST channel takes no handle" : "the handle is missing");
-    GOCTR_CHECK((ch.handle2 != nullptr) == is_als, "%s: channel %d: %s", who, c,
-                is_als ? "the ALS channel's item vectors (handle2) are missing" : "handle2 belongs to an ALS channel alone");
+    GOCTR_CHECK(is_wp || (ch.handle2 != nullptr) == is_als, "%s: channel %d: %s", who, c,
+                is_als ? "the ALS channel's item vectors (handle2) are missing"
+                       : "handle2 belongs to an ALS channel (or, as the sampler, to a WALK_POLICY channel) alone");
     GOCTR_CHECK((ch.cfg != nullptr) == takes_cfg, "%s: channel %d: %s", who, c, takes_cfg ? "the channel's cfg is missing" : "the kind takes no cfg");
     GOCTR_CHECK((ch.list != nullptr) == is_list, "%s: channel %d: %s", who, c, is_list ? "the LIST channel's list is missing" : "the kind takes no list");
     sum_list += ch.n_list; sum_reserve += ch.reserve;
     if (ch.kind == GOCTR_FUSE_WALK && walk_check_cfg(static_cast<const goctr_walk_cfg*>(ch.cfg), who)) return -1;
+    if (is_wp && walkp_check(who, static_cast<const goctr_walkgraph*>(ch.handle), static_cast<const goctr_walksampler*>(ch.handle2),
+                             static_cast<const goctr_walkp_cfg*>(ch.cfg))) return -1;
     if ((ch.kind == GOCTR_FUSE_USERVEC || is_als) && uservec_check_cfg(static_cast<const goctr_uservec_cfg*>(ch.cfg), who)) return -1;
     if (ch.kind == GOCTR_FUSE_USERVEC_IVF && uservec_ivf_check_cfg(static_cast<const goctr_uservec_ivf_cfg*>(ch.cfg), who)) return -1;
     if (is_ucf && usercf_check_cfg(static_cast<const goctr_usercf_recall_cfg*>(ch.cfg), who)) return -1;
@@ -340,6 +347,10 @@ int FuseStage::launch(const FuseArgs& f, const RecallCall& r0, const RecallRows&
         case GOCTR_FUSE_ITEMCF: rc = recall_launch(static_cast<const goctr_itemcf*>(ch.handle), x, rows, st); break;
         case GOCTR_FUSE_WALK:
           rc = walk_launch(static_cast<const goctr_walkgraph*>(ch.handle), x, *static_cast<const goctr_walk_cfg*>(ch.cfg), rows, nullptr, st);
+          break;
+        case GOCTR_FUSE_WALK_POLICY:
+          rc = walkp_launch(static_cast<const goctr_walkgraph*>(ch.handle), static_cast<const goctr_walksampler*>(ch.handle2), x,
+                            *static_cast<const goctr_walkp_cfg*>(ch.cfg), rows, nullptr, st);
           break;
         case GOCTR_FUSE_USERVEC:
           rc = uservec_launch(static_cast<const goctr_itemvec*>(ch.handle), x, *static_cast<const goctr_uservec_cfg*>(ch.cfg), rows,

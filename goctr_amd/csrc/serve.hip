@@ -728,6 +728,21 @@ int goctr_recommend_walk(goctr_model* m, goctr_recsys* r, goctr_walkgraph* g, co
   return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return walk_recommend_run(sc, g, *wcfg, a); });
 }
 
+// goctr_recommend_walk under a walk policy (goctr_walk_recall_policy's recall; s may be null)
+int goctr_recommend_walk_policy(goctr_model* m, goctr_recsys* r, goctr_walkgraph* g, goctr_walksampler* s, const int32_t* users,
+                                const int64_t* ts, int64_t n_req, const int32_t* targets, const goctr_recall_cfg* recall_cfg,
+                                const goctr_walkp_cfg* pcfg, int32_t k, int64_t pass_rows, int32_t* out_items, float* out_scores,
+                                int32_t* out_count, int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank,
+                                int32_t* cand_items, uint32_t* cand_w, float* cand_scores, int64_t* n_failed) {
+  EngineScope on(handle_engine(m));
+  const char* who = "goctr_recommend_walk_policy";
+  if (recommend_enter(who, m && r && g && recall_cfg && pcfg, m, r, {handle_engine(g), handle_engine(s)})) return -1;
+  const ItemcfRecArgs a{users, ts, n_req, targets, *recall_cfg, k, pass_rows, out_items, out_scores, out_count, out_cand_count,
+                        out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed};
+  if (walkp_check(who, g, s, pcfg) || walk_check_recommend(who, g, &pcfg->walk, a, r->n_users, r->n_items)) return -1;
+  return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return walkp_recommend_run(sc, g, s, *pcfg, a); });
+}
+
 // goctr_recommend_itemcf with the UserCF recall (usercf.hip) as the driver's recall stage
 int goctr_recommend_usercf(goctr_model* m, goctr_recsys* r, goctr_usercf* h, const int32_t* users, const int64_t* ts, int64_t n_req,
                            const int32_t* targets, const goctr_recall_cfg* recall_cfg, const goctr_usercf_recall_cfg* ucfg, int32_t k,

@@ -14,7 +14,11 @@
 //   one 64-bit scan       of the sorted contributions; the heads' sink keeps the prefix at every run's head, and an edge's weight is
 //                         the difference of two neighbouring heads (the last one's against the total), cut at cap.  No atomic adds a
 //                         weight.  The second sort carries the weight as its value: iw
-// Recall (walk_recall_kernel): one workgroup per request row, below.
+// Sampler build (goctr_walksampler_build; tests/walkp_ref.py restates it and the policy walk):
+//   wk_omega_kernel       twice: an edge's hop weight from its weight and the degree of the node it lands on
+//   two 64-bit scans      (scan.h) of the hop weights: ucum over uitems, icum over iusers, the total behind the last prefix
+// Recall (walk_recall_kernel): one workgroup per request row, below.  goctr_walk_recall_policy runs its POL instantiations: the walk
+// of step 2 with a weighted pick (a bisection of the node's run of cum), restarts, and the walks dealt to slots by degree.
 #include <climits>
 #include <memory>
 #include <vector>
@@ -99,6 +103,31 @@ struct WkScratch {
 
 inline dim3 grid256(long long n) { return dim3((unsigned)cdiv(n, 256)); }
 
+// the smallest s with s * s >= d (d < 2^32: exact in a double, the two loops settle the last unit)
+__device__ __forceinline__ unsigned int wk_ceil_root(unsigned int d) {
+  unsigned int s = (unsigned int)sqrt((double)d);
+  while ((u64)s * s < (u64)d) ++s;
+  while (s > 0u && (u64)(s - 1u) * (s - 1u) >= (u64)d) --s;
+  return s;
+}
+
+// goctr_walksampler_build: omega[e] = max(1, min(r, 2^24 - 1) * 256 / D) of edge e, whose landing node is land[e]; r = w[e] (w null:
+// 65536), D = 1, wk_ceil_root(d) or d by damp, d = the landing node's degree (at least 1: the edge ends there)
+__global__ __launch_bounds__(256) void wk_omega_kernel(const int32_t* __restrict__ land, const uint2* __restrict__ node,
+                                                       const unsigned int* __restrict__ w, long long n_e, int damp,
+                                                       unsigned int* __restrict__ omega) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n_e) return;
+  const unsigned int r = w ? w[e] : 65536u;
+  unsigned int D = 1u;
+  if (damp) {
+    const unsigned int d = node[land[e]].y;
+    D = damp == 1 ? wk_ceil_root(d) : d;
+  }
+  const unsigned int v = ((r < 0xffffffu ? r : 0xffffffu) << 8) / D;
+  omega[e] = v ? v : 1u;
+}
+
 // --------------------------------------------------------------------------------------------------------------- recall
 // One workgroup of SEL_THREADS per request row; threads own walks (w = tid, tid + SEL_THREADS).
 //   1. the history (lds_gather_history)
@@ -139,10 +168,34 @@ __device__ __forceinline__ u64 wk_root(unsigned int c) {
   return r;
 }
 
+// what goctr_walk_recall_policy adds to a walk (POL = true); the default path carries the empty struct and none of the code
+struct WalkPolicy {
+  const u64* ucum; const u64* icum;            // the sampler's prefix sums over uitems / iusers (null: uniform hops)
+  int alloc, restart_q;
+};
+struct NoWalkPolicy {};
+template <bool POL> using PolicyArg = std::conditional_t<POL, WalkPolicy, NoWalkPolicy>;
+
+// the weighted pick in the run [first, first + d) of cum: the edge e with cum[e] <= cum[first] + y < cum[e + 1], y = the high 64
+// bits of (x with its low word cleared) * T.  cum rises strictly (a hop weight is at least 1), so e is unique whatever the shape of
+// the search.  Plain bisection: a chain of ceil(log2 d) dependent 8-byte loads.  (A k-ary round -- k - 1 independent probes in
+// flight, log_k d rounds -- was measured against it and not kept: DESIGN 4.6 "Walk policy" has the figures)
+__device__ __forceinline__ unsigned int wk_pick_weighted(const u64* __restrict__ cum, unsigned int first, unsigned int d, u64 x) {
+  const u64 base = cum[first], top = cum[first + d];
+  const u64 want = base + __umul64hi(x & 0xffffffff00000000ull, top - base);
+  unsigned int lo = first, hi = first + d;     // cum[lo] <= want < cum[hi]
+  while (hi - lo > 1u) {
+    const unsigned int mid = lo + ((hi - lo) >> 1);
+    if (cum[mid] <= want) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
 // FILT: the row's predicate decides at step 5 which of the visited items may join the list (item_eligible, itemattr.h); the walks
 // themselves pass through ineligible items.  FILT = false is the kernel every unfiltered entry runs
-template <bool FILT>
-__global__ __launch_bounds__(SEL_THREADS) void walk_recall_kernel(WalkArgs a, FilterArg<FILT> f) {
+// POL: the walks follow a WalkPolicy (below, step 2); POL = false is goctr_walk_recall's walk, instruction for instruction
+template <bool FILT, bool POL>
+__global__ __launch_bounds__(SEL_THREADS) void walk_recall_kernel(WalkArgs a, FilterArg<FILT> f, PolicyArg<POL> pol) {
   constexpr int KCAP = WK_MAX_VISITS, PER = KCAP / SEL_THREADS;   // the list's capacity; list positions per thread
   __shared__ unsigned long long vkey[KCAP];
   __shared__ unsigned long long skey[SEL_CAP];
@@ -173,25 +226,78 @@ __global__ __launch_bounds__(SEL_THREADS) void walk_recall_kernel(WalkArgs a, Fi
   for (int i = total + tid; i < n2; i += SEL_THREADS) vkey[i] = 0ull;
   __syncthreads();
 
-  // 2. the walks
+  // 2. the walks: one loop for both paths; what a policy adds is under `if constexpr (POL)` and leaves the default instantiations
+  // as they were.  POL, alloc 1: aslot[t] = A_t, the prefix sums of the slots' shares a_t = wk_ceil_root(|U_{h_t}|)
+  __shared__ unsigned int aslot[POL ? WK_MAX_H + 1 : 1];
+  __shared__ unsigned int awave[POL ? WK_MAX_H / 64 : 1];
+  bool weighted = false;
+  u64 a_all = 0ull;
+  if constexpr (POL) {
+    if (pol.alloc && nh > 0) {                             // (uniform)
+      unsigned int inc = 0u;
+      if (tid < WK_MAX_H) {
+        inc = tid < nh ? wk_ceil_root(a.inode[hist[tid]].y) : 0u;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+          const unsigned int up = __shfl_up(inc, o, 64);
+          if ((tid & 63) >= o) inc += up;
+        }
+        if ((tid & 63) == 63) awave[tid >> 6] = inc;
+      }
+      __syncthreads();
+      if (tid < WK_MAX_H) {
+        for (int v = 0; v < (tid >> 6); ++v) inc += awave[v];
+        if (tid < nh) aslot[tid + 1] = inc;
+        if (tid == 0) aslot[0] = 0u;
+      }
+      __syncthreads();
+      a_all = (u64)aslot[nh];
+    }
+    weighted = pol.ucum != nullptr;
+  }
+  // the edge a hop draws in node n's run: by weight under a sampler (to_user: the item -> user side, icum), else uniform
+  const auto edge = [&](bool to_user, uint2 n, u64 x) -> unsigned int {
+    if constexpr (POL) {
+      if (weighted) return wk_pick_weighted(to_user ? pol.icum : pol.ucum, n.x, n.y, x);
+    }
+    return n.x + wk_pick(x, n.y);
+  };
   for (int w = tid; w < a.n_walks; w += SEL_THREADS) {
-    const int t = nh > 0 ? w % nh : 0;
+    int t = nh > 0 ? w % nh : 0;
     bool alive = nh > 0;
+    if constexpr (POL) {
+      if (pol.alloc) {                                     // the slot with A_t <= place < A_{t+1}; A_H = 0: no walk
+        alive = a_all > 0ull;
+        t = 0;
+        if (alive) {
+          const unsigned int place = (unsigned int)(((u64)(unsigned int)w * a_all) / (u64)(unsigned int)a.n_walks);
+          int lo = 0, hi = nh;                             // A_lo <= place < A_hi
+          while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (aslot[mid] <= place) lo = mid; else hi = mid;
+          }
+          t = lo;
+        }
+      }
+    }
     int i = alive ? hist[t] : 0;
     const u64 hw = ((u64)(unsigned int)user << 32) | (u64)(unsigned int)w;
     for (int s = 0; s < a.n_steps; ++s) {
       int j = -1;
       if (alive) {
-        const uint2 ni = a.inode[i];
         const u64 hs = (u64)(unsigned int)s << 32;
+        if constexpr (POL) {
+          if (pol.restart_q && s > 0 && (ns_mix(a.seed ^ ns_mix(hw ^ ns_mix(hs | 2ull))) >> 56) < (u64)pol.restart_q) i = hist[t];
+        }
+        const uint2 ni = a.inode[i];
         const u64 x0 = ns_mix(a.seed ^ ns_mix(hw ^ ns_mix(hs))), x1 = ns_mix(a.seed ^ ns_mix(hw ^ ns_mix(hs | 1ull)));
         if (ni.y == 0u) {
           alive = false;
         } else {
-          const int u = a.iusers[ni.x + wk_pick(x0, ni.y)];
+          const int u = a.iusers[edge(true, ni, x0)];
           if (u != user) {
             const uint2 nu = a.unode[u];       // (u holds i: its degree is at least 1)
-            j = a.uitems[nu.x + wk_pick(x1, nu.y)];
+            j = a.uitems[edge(false, nu, x1)];
             i = j;
           }
         }
@@ -286,8 +392,24 @@ int walk_check_cfg(const goctr_walk_cfg* w, const char* who) {
   return 0;
 }
 
-int walk_launch(const goctr_walkgraph* g, const RecallCall& r, const goctr_walk_cfg& wcfg, const RecallRows& out, int32_t* o_trace,
-                hipStream_t st) {
+int walkp_check(const char* who, const goctr_walkgraph* g, const goctr_walksampler* s, const goctr_walkp_cfg* p) {
+  GOCTR_CHECK(g && p, "%s: bad arguments", who);
+  if (walk_check_cfg(&p->walk, who)) return -1;
+  GOCTR_CHECK(p->alloc == 0 || p->alloc == 1, "%s: alloc = %d is neither 0 nor 1", who, p->alloc);
+  GOCTR_CHECK(p->restart_q >= 0 && p->restart_q <= 255, "%s: restart_q = %d is outside 0 .. 255", who, p->restart_q);
+  GOCTR_CHECK(p->reserved == 0, "%s: reserved = %lld (must be 0)", who, (long long)p->reserved);
+  if (!s) return 0;
+  GOCTR_CHECK(s->eng == g->eng, "%s: the handles were created on different engines (devices)", who);
+  GOCTR_CHECK(s->n_users == g->n_users && s->n_items == g->n_items && s->n_edges == g->n_edges && s->cache_version == g->cache_version,
+              "%s: the sampler was built from another graph (%lld users, %lld items, %llu edges, cache version %llu against %lld, "
+              "%lld, %llu, %llu)", who, (long long)s->n_users, (long long)s->n_items, (unsigned long long)s->n_edges,
+              (unsigned long long)s->cache_version, (long long)g->n_users, (long long)g->n_items, (unsigned long long)g->n_edges,
+              (unsigned long long)g->cache_version);
+  return 0;
+}
+
+static WalkArgs walk_args(const goctr_walkgraph* g, const RecallCall& r, const goctr_walk_cfg& wcfg, const RecallRows& out,
+                          int32_t* o_trace) {
   WalkArgs a{};
   a.off = r.seq.off; a.seq_items = r.seq.items; a.seq_ts = r.seq.ts;
   a.n_items = g->n_items;
@@ -296,8 +418,31 @@ int walk_launch(const goctr_walkgraph* g, const RecallCall& r, const goctr_walk_
   a.H = r.cfg.history; a.n_cand = r.cfg.n_cand; a.exclude = r.cfg.exclude; a.stride = r.stride;
   a.n_walks = wcfg.n_walks; a.n_steps = wcfg.n_steps; a.boost = wcfg.boost; a.min_visits = wcfg.min_visits; a.seed = wcfg.seed;
   a.out_items = out.items; a.out_w = out.w; a.out_count = out.count; a.out_tpos = out.tpos; a.out_trace = o_trace;
-  if (r.flt) hipLaunchKernelGGL(walk_recall_kernel<true>, dim3((unsigned)r.nq), dim3(SEL_THREADS), 0, st, a, *r.flt);
-  else hipLaunchKernelGGL(walk_recall_kernel<false>, dim3((unsigned)r.nq), dim3(SEL_THREADS), 0, st, a, NoItemFilter{});
+  return a;
+}
+
+int walkp_launch(const goctr_walkgraph* g, const goctr_walksampler* s, const RecallCall& r, const goctr_walkp_cfg& pcfg,
+                 const RecallRows& out, int32_t* o_trace, hipStream_t st) {
+  const WalkArgs a = walk_args(g, r, pcfg.walk, out, o_trace);
+  const WalkPolicy pol{s ? s->ucum.p : nullptr, s ? s->icum.p : nullptr, pcfg.alloc, pcfg.restart_q};
+  if (r.flt) hipLaunchKernelGGL((walk_recall_kernel<true, true>), dim3((unsigned)r.nq), dim3(SEL_THREADS), 0, st, a, *r.flt, pol);
+  else hipLaunchKernelGGL((walk_recall_kernel<false, true>), dim3((unsigned)r.nq), dim3(SEL_THREADS), 0, st, a, NoItemFilter{}, pol);
+  GOCTR_HIP(hipGetLastError());
+  return 0;
+}
+
+int walkp_recommend_run(const TopnScorer& sc, const goctr_walkgraph* g, const goctr_walksampler* s, const goctr_walkp_cfg& pcfg,
+                        const ItemcfRecArgs& a) {
+  return recall_rank_run(sc, "goctr_recommend_walk_policy", a, false, [&](const RecallInputs& in, const RecallRows& o, hipStream_t st) {
+    return walkp_launch(g, s, recall_call(sc, a, in), pcfg, o, nullptr, st);
+  });
+}
+
+int walk_launch(const goctr_walkgraph* g, const RecallCall& r, const goctr_walk_cfg& wcfg, const RecallRows& out, int32_t* o_trace,
+                hipStream_t st) {
+  const WalkArgs a = walk_args(g, r, wcfg, out, o_trace);
+  if (r.flt) hipLaunchKernelGGL((walk_recall_kernel<true, false>), dim3((unsigned)r.nq), dim3(SEL_THREADS), 0, st, a, *r.flt, NoWalkPolicy{});
+  else hipLaunchKernelGGL((walk_recall_kernel<false, false>), dim3((unsigned)r.nq), dim3(SEL_THREADS), 0, st, a, NoItemFilter{}, NoWalkPolicy{});
   GOCTR_HIP(hipGetLastError());
   return 0;
 }
@@ -508,6 +653,103 @@ int goctr_walk_recall(goctr_walkgraph* g, goctr_ubcache* c, const int32_t* users
   return recall_only_run(c, users, ts, targets, n_req, cfg->n_cand, [&](const RecallInputs& in, const RecallRows& o, hipStream_t st) {
     if (out_trace && o_trace.alloc(n_trace, false)) return -1;
     if (walk_launch(g, RecallCall{CacheSeq(c), in, targets != nullptr, n_req, *cfg, cfg->n_cand}, *wcfg, o, o_trace.p, st)) return -1;
+    return out.add(out_trace, o_trace.p, sizeof(int32_t) * n_trace);
+  }, out, out_items, out_w, nullptr, out_count, out_target_pos);
+}
+
+void goctr_walksampler_cfg_default(goctr_walksampler_cfg* c) {
+  if (!c) return;
+  c->damp_item = 0; c->damp_user = 0; c->reserved = 0;
+}
+
+void goctr_walkp_cfg_default(goctr_walkp_cfg* c) {
+  if (!c) return;
+  goctr_walk_cfg_default(&c->walk);
+  c->alloc = 0; c->restart_q = 0; c->reserved = 0;
+}
+
+int goctr_walksampler_build(goctr_walkgraph* g, const goctr_walksampler_cfg* cfg, goctr_walksampler** out) {
+  GOCTR_ENTER_H(g);
+  const char* who = "goctr_walksampler_build";
+  GOCTR_CHECK(g && cfg && out, "%s: null argument (graph, cfg, out)", who);
+  GOCTR_CHECK(cfg->damp_item >= 0 && cfg->damp_item <= 2, "%s: damp_item = %d is outside 0 .. 2", who, cfg->damp_item);
+  GOCTR_CHECK(cfg->damp_user >= 0 && cfg->damp_user <= 2, "%s: damp_user = %d is outside 0 .. 2", who, cfg->damp_user);
+  GOCTR_CHECK(cfg->reserved == 0, "%s: reserved = %lld (must be 0)", who, (long long)cfg->reserved);
+  hipStream_t st = engine().stream;
+  std::unique_ptr<goctr_walksampler> s(new goctr_walksampler);
+  DevBuf<unsigned int> omega_u, omega_i;       // the hop weights: scratch, only their prefix sums are kept
+  DevBuf<u64> tiles_u, tiles_i;                // (one each: the second scan does not wait for the first)
+  s->n_users = g->n_users; s->n_items = g->n_items; s->n_edges = g->n_edges; s->cache_version = g->cache_version;
+  s->weighted = g->weighted; s->cfg = *cfg;
+  const long long ne = (long long)g->n_edges;
+  if (s->ucum.alloc((size_t)ne + 1) || s->icum.alloc((size_t)ne + 1)) return -1;      // (zeroed: an empty graph's {0})
+  if (ne > 0) {
+    if (omega_u.alloc((size_t)ne, false) || omega_i.alloc((size_t)ne, false)) return -1;
+    hipLaunchKernelGGL(wk_omega_kernel, grid256(ne), dim3(256), 0, st, g->uitems.p, g->inode.p, g->weighted ? g->uw.p : nullptr, ne,
+                       cfg->damp_item, omega_u.p);
+    hipLaunchKernelGGL(wk_omega_kernel, grid256(ne), dim3(256), 0, st, g->iusers.p, g->unode.p, g->weighted ? g->iw.p : nullptr, ne,
+                       cfg->damp_user, omega_i.p);
+    // the total lands behind the last prefix: cum[n_edges].  Whatever fails behind a launch, the stream is drained before the
+    // scratch goes out of scope
+    const hipError_t launched = hipGetLastError();
+    int rc = launched == hipSuccess ? 0 : -1;
+    rc = rc || exclusive_scan<u64>(omega_u.p, ne, s->ucum.p, tiles_u, s->ucum.p + ne);
+    rc = rc || exclusive_scan<u64>(omega_i.p, ne, s->icum.p, tiles_i, s->icum.p + ne);
+    const hipError_t drained = hipStreamSynchronize(st);
+    GOCTR_HIP(launched);
+    if (rc) return -1;                         // (the scan said why)
+    GOCTR_HIP(drained);
+  }
+  *out = s.release();
+  return 0;
+}
+
+void goctr_walksampler_destroy(goctr_walksampler* s) {
+  if (!s) return;
+  EngineScope on(s->eng);
+  std::lock_guard<std::recursive_mutex> lk(s->eng->mu);
+  delete s;
+}
+
+int goctr_walksampler_info(goctr_walksampler* s, int64_t* n_users, int64_t* n_items, int64_t* n_edges, uint64_t* cache_version,
+                           int32_t* weighted, goctr_walksampler_cfg* cfg) {
+  GOCTR_ENTER_H(s);
+  GOCTR_CHECK(s, "goctr_walksampler_info: null handle");
+  if (n_users) *n_users = s->n_users;
+  if (n_items) *n_items = s->n_items;
+  if (n_edges) *n_edges = (int64_t)s->n_edges;
+  if (cache_version) *cache_version = s->cache_version;
+  if (weighted) *weighted = s->weighted ? 1 : 0;
+  if (cfg) *cfg = s->cfg;
+  return 0;
+}
+
+int goctr_walksampler_export(goctr_walksampler* s, uint64_t* ucum, uint64_t* icum) {
+  GOCTR_ENTER_H(s);
+  GOCTR_CHECK(s, "goctr_walksampler_export: null handle");
+  const size_t n = (size_t)s->n_edges + 1;
+  if (ucum && s->ucum.download(reinterpret_cast<unsigned long long*>(ucum), n)) return -1;
+  if (icum && s->icum.download(reinterpret_cast<unsigned long long*>(icum), n)) return -1;
+  return 0;
+}
+
+int goctr_walk_recall_policy(goctr_walkgraph* g, goctr_walksampler* s, goctr_ubcache* c, const int32_t* users, const int64_t* ts,
+                             int64_t n_req, const goctr_recall_cfg* cfg, const goctr_walkp_cfg* pcfg, int32_t* out_items,
+                             uint32_t* out_w, int32_t* out_count, const int32_t* targets, int32_t* out_target_pos, int32_t* out_trace) {
+  GOCTR_ENTER_H(g);
+  const char* who = "goctr_walk_recall_policy";
+  GOCTR_CHECK(g && c && users && cfg && pcfg && out_items && out_w && out_count, "%s: null argument", who);
+  GOCTR_SAME_ENGINE(g, c);
+  if (recall_check_cfg(cfg, who) || walkp_check(who, g, s, pcfg)) return -1;
+  GOCTR_CHECK(g->n_users == c->n_users, "%s: the walk graph has %lld users, the cache %lld", who, (long long)g->n_users,
+              (long long)c->n_users);
+  if (recall_check_users(users, n_req, c->n_users, who)) return -1;
+  const size_t n_trace = (size_t)n_req * (size_t)pcfg->walk.n_walks * (size_t)pcfg->walk.n_steps;
+  HostStage out(engine().stream);
+  DevBuf<int32_t> o_trace;
+  return recall_only_run(c, users, ts, targets, n_req, cfg->n_cand, [&](const RecallInputs& in, const RecallRows& o, hipStream_t st) {
+    if (out_trace && o_trace.alloc(n_trace, false)) return -1;
+    if (walkp_launch(g, s, RecallCall{CacheSeq(c), in, targets != nullptr, n_req, *cfg, cfg->n_cand}, *pcfg, o, o_trace.p, st)) return -1;
     return out.add(out_trace, o_trace.p, sizeof(int32_t) * n_trace);
   }, out, out_items, out_w, nullptr, out_count, out_target_pos);
 }

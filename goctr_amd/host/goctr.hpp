@@ -1053,6 +1053,75 @@ inline TopN RecommendWalkBatch(model::CtrNet& net, RecSys& rs, const WalkGraph& 
   return out;
 }
 
+// the hop sampler over a graph (goctr_walksampler_build): the prefix sums of the edges' hop weights -- the edge weight divided by
+// the landing node's degree to the power damp / 2 -- that the policy walk (goctr_walk_recall_policy) draws its hops from
+class WalkSampler {
+ public:
+  static goctr_walksampler_cfg DefaultCfg() { goctr_walksampler_cfg c; goctr_walksampler_cfg_default(&c); return c; }
+  static goctr_walkp_cfg DefaultPolicyCfg() { goctr_walkp_cfg c; goctr_walkp_cfg_default(&c); return c; }
+  static WalkSampler Build(const WalkGraph& graph, const goctr_walksampler_cfg& cfg = DefaultCfg()) {
+    WalkSampler s;
+    check(goctr_walksampler_build(graph.handle(), &cfg, &s.h_));
+    return s;
+  }
+  WalkSampler(const WalkSampler&) = delete;
+  WalkSampler& operator=(const WalkSampler&) = delete;
+  WalkSampler(WalkSampler&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  ~WalkSampler() { goctr_walksampler_destroy(h_); }
+  goctr_walksampler* handle() const { return h_; }
+  struct Info { int64_t n_users, n_items, n_edges; uint64_t cache_version; bool weighted; goctr_walksampler_cfg cfg; };
+  Info info() const {
+    Info i{};
+    int32_t w = 0;
+    check(goctr_walksampler_info(h_, &i.n_users, &i.n_items, &i.n_edges, &i.cache_version, &w, &i.cfg));
+    i.weighted = w != 0;
+    return i;
+  }
+  // ucum over the user side's edges, icum over the item side's: [n_edges + 1] each
+  void Export(std::vector<uint64_t>& ucum, std::vector<uint64_t>& icum) const {
+    const size_t n = (size_t)info().n_edges + 1;
+    ucum.resize(n); icum.resize(n);
+    check(goctr_walksampler_export(h_, ucum.data(), icum.data()));
+  }
+
+ private:
+  WalkSampler() = default;
+  goctr_walksampler* h_ = nullptr;
+};
+
+// WalkGraph::Recall under a walk policy (goctr_walk_recall_policy); sampler null: uniform hops
+inline void WalkRecallPolicy(const WalkGraph& graph, const WalkSampler* sampler, goctr_ubcache* cache, const std::vector<int32_t>& users,
+                             const std::vector<int64_t>& ts, const goctr_recall_cfg& cfg, std::vector<int32_t>& items,
+                             std::vector<uint32_t>& w, std::vector<int32_t>& count,
+                             const goctr_walkp_cfg& pcfg = WalkSampler::DefaultPolicyCfg()) {
+  if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("WalkRecallPolicy: one timestamp per user");
+  const size_t nq = users.size(), nc = (size_t)std::max(cfg.n_cand, 1);
+  items.resize(nq * nc); w.resize(nq * nc); count.resize(nq);
+  check(goctr_walk_recall_policy(graph.handle(), sampler ? sampler->handle() : nullptr, cache, users.data(),
+                                 ts.empty() ? nullptr : ts.data(), (int64_t)nq, &cfg, &pcfg, items.data(), w.data(), count.data(), nullptr,
+                                 nullptr, nullptr));
+}
+
+// RecommendWalkBatch under a walk policy (goctr_recommend_walk_policy); sampler null: uniform hops
+inline TopN RecommendWalkPolicyBatch(model::CtrNet& net, RecSys& rs, const WalkGraph& graph, const WalkSampler* sampler,
+                                     const std::vector<int32_t>& users, int n = 10, const std::vector<int64_t>& ts = {},
+                                     const goctr_recall_cfg& rcfg = ItemCF::DefaultRecallCfg(),
+                                     const goctr_walkp_cfg& pcfg = WalkSampler::DefaultPolicyCfg(), const std::vector<int32_t>& targets = {},
+                                     int64_t pass_rows = 0) {
+  const int64_t nq = (int64_t)users.size();
+  detail::check_request("RecommendWalkPolicyBatch", users.size(), ts.size(), targets.size(), n);
+  std::vector<int32_t> items((size_t)nq * n), count((size_t)nq);
+  std::vector<float> scores((size_t)nq * n);
+  TopN out;
+  if (!targets.empty()) out.target_rank.resize((size_t)nq);
+  check(goctr_recommend_walk_policy(net.Vm(), rs.handle(), graph.handle(), sampler ? sampler->handle() : nullptr, users.data(),
+                                    ts.empty() ? nullptr : ts.data(), nq, targets.empty() ? nullptr : targets.data(), &rcfg, &pcfg, n,
+                                    pass_rows, items.data(), scores.data(), count.data(), nullptr, nullptr,
+                                    targets.empty() ? nullptr : out.target_rank.data(), nullptr, nullptr, nullptr, &out.n_failed));
+  out.lists = detail::gather_lists(items, scores, count, n);
+  return out;
+}
+
 // every user's nearest users by item overlap (goctr_usercf_build over a WalkGraph) and their newest items as a recall channel
 // (goctr_usercf_recall): the lists are fixed at the build, the items are read from the live cache image of every call
 class UserCF {
@@ -1332,6 +1401,11 @@ class Fused {
                 const goctr_usercf_recall_cfg& ucfg = UserCF::DefaultRecallCfg()) {
     return Add(ucf, n_list, weight, reserve, ucfg);
   }
+  // the policy walk's list (goctr_walk_recall_policy); sampler null: uniform hops
+  Fused& walk_policy(const WalkGraph& g, const WalkSampler* sampler, int n_list, uint32_t weight = 1, int reserve = 0,
+                     const goctr_walkp_cfg& pcfg = WalkSampler::DefaultPolicyCfg()) {
+    return push(GOCTR_FUSE_WALK_POLICY, n_list, weight, reserve, g.handle(), sampler ? sampler->handle() : nullptr, &pcfg, sizeof pcfg);
+  }
   Fused& Add(const Popular& pop, int n_list, uint32_t weight = 1, int reserve = 0) {
     return push(GOCTR_FUSE_POPULAR, n_list, weight, reserve, pop.handle(), nullptr, nullptr, 0);
   }
@@ -1392,7 +1466,7 @@ class Fused {
   }
 
  private:
-  union AnyCfg { goctr_walk_cfg w; goctr_uservec_cfg u; goctr_uservec_ivf_cfg i; goctr_usercf_recall_cfg c; };
+  union AnyCfg { goctr_walk_cfg w; goctr_uservec_cfg u; goctr_uservec_ivf_cfg i; goctr_usercf_recall_cfg c; goctr_walkp_cfg p; };
   Fused& push(int32_t kind, int n_list, uint32_t weight, int reserve, const void* h, const void* h2, const void* cfg, size_t cfg_bytes) {
     if (chan_.size() >= 7) throw std::invalid_argument("Fused::Add: at most 7 channels");
     AnyCfg a{};

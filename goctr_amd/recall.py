@@ -120,6 +120,30 @@ make_uservec_ivf_cfg = _make("goctr_uservec_ivf_cfg", _USERVEC_IVF_FIELDS, capi.
 make_walkgraph_cfg = _make("goctr_walkgraph_cfg", _WALKGRAPH_FIELDS, capi.default_walkgraph_cfg)
 make_walk_cfg = _make("goctr_walk_cfg", _WALK_FIELDS, capi.default_walk_cfg)
 make_edgeweight_cfg = _make("goctr_edgeweight_cfg", _fields(capi.EdgeWeightCfg), capi.default_edgeweight_cfg)
+make_walksampler_cfg = _make("goctr_walksampler_cfg", _fields(capi.WalkSamplerCfg), capi.default_walksampler_cfg)
+_WALKP_FIELDS = _WALK_FIELDS | {"alloc", "restart_q"}
+
+
+def make_walkp_cfg(**kw) -> capi.WalkPolicyCfg:
+    """goctr_walkp_cfg from keywords: goctr_walk_cfg's fields (n_walks, n_steps, boost, min_visits, seed), alloc, restart_q.  alloc
+    and restart_q are checked here, before the library is reached; the walk's ranges are the library's to refuse"""
+    unknown = set(kw) - _WALKP_FIELDS
+    if unknown:
+        raise TypeError(f"goctr_walkp_cfg has no field {sorted(unknown)}")
+    p = capi.default_walkp_cfg()
+    for k, v in kw.items():
+        setattr(p.walk if k in _WALK_FIELDS else p, k, _as_int(k, v))
+    return check_walkp_cfg(p)
+
+
+def check_walkp_cfg(p: capi.WalkPolicyCfg) -> capi.WalkPolicyCfg:
+    if p.alloc not in (0, 1):
+        raise ValueError(f"alloc = {p.alloc} is neither 0 nor 1")
+    if not 0 <= p.restart_q <= 255:
+        raise ValueError(f"restart_q = {p.restart_q} is outside 0 .. 255")
+    if p.reserved != 0:
+        raise ValueError(f"reserved = {p.reserved} (must be 0)")
+    return p
 
 
 def edgeweight_cfg(weights) -> capi.EdgeWeightCfg | None:
@@ -459,6 +483,57 @@ class WalkGraph(_Handle):
             out["trace"] = _unwritten((users.size, min(max(int(wcfg.n_walks), 1) * max(int(wcfg.n_steps), 1), 8192)), np.int32)
         capi.check(capi.load().goctr_walk_recall(self._h, _cache_handle(ubc), *_request_args(users, ts), C.byref(cfg), C.byref(wcfg),
                                                  *_recall_args(out, targets), _ptr(out.get("trace"))))
+        return out
+
+    def recall_policy(self, ubc, users, ts=None, targets=None, cfg: capi.RecallCfg | None = None,
+                      pcfg: capi.WalkPolicyCfg | None = None, sampler: "WalkSampler | None" = None, trace=False, **kw) -> dict:
+        """goctr_walk_recall_policy: ``recall`` whose hops are drawn by ``sampler``'s weights (None: uniform hops), with restarts and
+        walks dealt to history slots by degree.  ``kw``: goctr_recall_cfg fields and goctr_walkp_cfg's (the walk's, alloc,
+        restart_q).  ``recall``'s dict"""
+        cfg, pcfg = _split_kw(cfg, pcfg, kw, _WALKP_FIELDS, make_walkp_cfg)
+        check_walkp_cfg(pcfg)
+        users, ts, targets = request_columns(users, ts, targets)
+        out = _recall_buffers(users.size, cfg.n_cand, targets)
+        if trace:
+            out["trace"] = _unwritten((users.size, min(max(int(pcfg.walk.n_walks), 1) * max(int(pcfg.walk.n_steps), 1), 8192)), np.int32)
+        capi.check(capi.load().goctr_walk_recall_policy(self._h, _sampler_handle(sampler), _cache_handle(ubc), *_request_args(users, ts),
+                                                        C.byref(cfg), C.byref(pcfg), *_recall_args(out, targets), _ptr(out.get("trace"))))
+        return out
+
+
+def _sampler_handle(sampler):
+    """a WalkSampler, a raw goctr_walksampler handle, or None"""
+    return None if sampler is None else getattr(sampler, "_h", sampler)
+
+
+class WalkSampler(_Handle):
+    """goctr_walksampler: the prefix sums of a graph's hop weights -- the edge weight, divided by the landing node's degree to the
+    power damp / 2 -- that ``WalkGraph.recall_policy`` draws its hops from.  Immutable; rebuilt with the graph"""
+    _destroy = "goctr_walksampler_destroy"
+
+    def __init__(self, graph: WalkGraph, cfg: capi.WalkSamplerCfg | None = None, **kw):
+        """graph: a WalkGraph (or a raw goctr_walkgraph handle); ``kw``: goctr_walksampler_cfg fields (damp_item, damp_user: 0, 1, 2)"""
+        cfg = _cfg_or_kw(cfg, kw, make_walksampler_cfg)
+        for name in ("damp_item", "damp_user"):
+            if not 0 <= getattr(cfg, name) <= 2:
+                raise ValueError(f"{name} = {getattr(cfg, name)} is outside 0 .. 2")
+        if cfg.reserved != 0:
+            raise ValueError(f"reserved = {cfg.reserved} (must be 0)")
+        self._h = C.c_void_p()
+        capi.check(capi.load().goctr_walksampler_build(getattr(graph, "_h", graph), C.byref(cfg), C.byref(self._h)))
+        self.n_edges = self.info()["n_edges"]
+
+    def info(self) -> dict:
+        nu, ni, ne, v, w, cfg = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_uint64(0), C.c_int32(0), capi.WalkSamplerCfg()
+        capi.check(capi.load().goctr_walksampler_info(self._h, C.byref(nu), C.byref(ni), C.byref(ne), C.byref(v), C.byref(w), C.byref(cfg)))
+        return dict(n_users=nu.value, n_items=ni.value, n_edges=ne.value, cache_version=v.value, weighted=bool(w.value),
+                    damp_item=cfg.damp_item, damp_user=cfg.damp_user)
+
+    def export(self) -> dict:
+        """dict(ucum uint64 [n_edges + 1], icum uint64 [n_edges + 1]): the exclusive prefix sums of the hop weights over the graph's
+        uitems and iusers"""
+        out = dict(ucum=np.empty(self.n_edges + 1, np.uint64), icum=np.empty(self.n_edges + 1, np.uint64))
+        capi.check(capi.load().goctr_walksampler_export(self._h, capi.ptr(out["ucum"], C.c_uint64), capi.ptr(out["icum"], C.c_uint64)))
         return out
 
 
@@ -867,6 +942,13 @@ class Channel:
         return cls(capi.FUSE_WALK, n_list, weight, reserve, graph, cfg=_cfg_or_kw(wcfg, kw, make_walk_cfg, "wcfg"))
 
     @classmethod
+    def walk_policy(cls, graph: WalkGraph, sampler: "WalkSampler | None", n_list, weight=1, reserve=0,
+                    pcfg: capi.WalkPolicyCfg | None = None, **kw) -> "Channel":
+        """``WalkGraph.recall_policy``'s list under ``sampler`` (None: uniform hops); ``kw``: goctr_walkp_cfg fields"""
+        return cls(capi.FUSE_WALK_POLICY, n_list, weight, reserve, graph, sampler,
+                   check_walkp_cfg(_cfg_or_kw(pcfg, kw, make_walkp_cfg, "pcfg")))
+
+    @classmethod
     def uservec(cls, vectors: "ItemVectors", n_list, weight=1, reserve=0, ucfg: capi.UservecCfg | None = None, **kw) -> "Channel":
         """``ItemVectors.recall_users``'s list; ``kw``: goctr_uservec_cfg fields"""
         return cls(capi.FUSE_USERVEC, n_list, weight, reserve, vectors, cfg=_cfg_or_kw(ucfg, kw, make_uservec_cfg, "ucfg"))
@@ -910,8 +992,10 @@ def fuse_channels(channels, nq, n_cand):
     for c, (ch, a) in enumerate(zip(channels, arr)):
         if not isinstance(ch, Channel):
             raise TypeError(f"channel {c} is no recall.Channel")
-        if not capi.FUSE_ITEMCF <= ch.kind <= capi.FUSE_USERCF:
+        if not capi.FUSE_ITEMCF <= ch.kind <= capi.FUSE_WALK_POLICY:
             raise ValueError(f"channel {c}: kind = {ch.kind} is no capi.FUSE_* kind")
+        if ch.kind == capi.FUSE_WALK_POLICY and not isinstance(ch.cfg, capi.WalkPolicyCfg):
+            raise ValueError(f"channel {c}: a WALK_POLICY channel takes a goctr_walkp_cfg (Channel.walk_policy makes one)")
         if ch.kind == capi.FUSE_USERCF and not isinstance(ch.cfg, capi.UsercfRecallCfg):
             raise ValueError(f"channel {c}: a USERCF channel takes a goctr_usercf_recall_cfg (Channel.usercf makes one)")
         if not 1 <= ch.n_list <= 1024:

@@ -30,6 +30,7 @@ from . import capi, metrics, sampling
 from .recall import (ALS, EXCLUDE, _USERCF_RECALL_FIELDS, _USERVEC_FIELDS, _USERVEC_IVF_FIELDS, _USERVEC_MULTI_FIELDS, _WALK_FIELDS, ItemCF,
                      ItemVectors, Popular, UserCF, WalkGraph, make_usercf_recall_cfg, _as_int, _cfg_or_kw, _ptr, _request_args, _split_kw, _unwritten, extra_columns, make_mmr_cfg,
                      make_recall_cfg, make_uservec_cfg, make_uservec_ivf_cfg, make_uservec_multi_cfg, make_walk_cfg, merge,
+                     WalkSampler, _WALKP_FIELDS, check_walkp_cfg, make_walkp_cfg,
                      request_columns, Channel, _FUSE_FIELDS, check_fuse_cfg, fuse_channels, make_fuse_cfg, ItemAttrs, item_filter, make_pred)
 
 # recommend/rcmd.go:19-28
@@ -549,6 +550,7 @@ _OUTPUTS = {
     "goctr_recommend_blend_mmr": _BLENDED + ("obj", "pen", "target_place"),
     "goctr_recommend_blend_uservec": _BLENDED + ("obj", "pen", "target_place"),
     "goctr_recommend_walk": _RANKED,
+    "goctr_recommend_walk_policy": _RANKED,
     "goctr_recommend_usercf": _RANKED,
     "goctr_recommend_blend_walk": _BLENDED + ("obj", "pen", "target_place"),
     "goctr_recommend_als": _RANKED,
@@ -701,6 +703,20 @@ def walk(model: Predictor, graph, users, ts=None, targets=None, k=10, pass_rows=
     n_steps, boost, min_visits, seed).  What RecommendWalk / RecommendWalkBatch / EvaluateLeaveOneOutWalk call."""
     cfg, wcfg = _split_kw(recall_cfg, wcfg, recall_kw, _WALK_FIELDS, make_walk_cfg)
     return _uservec_call("goctr_recommend_walk", model, graph, users, ts, targets, k, pass_rows, validate, cfg, wcfg)
+
+
+def walk_policy(model: Predictor, graph, sampler, users, ts=None, targets=None, k=10, pass_rows=0, validate=False, recall_cfg=None,
+                pcfg=None, **recall_kw):
+    """goctr_recommend_walk_policy over DENSE indices: ``walk`` whose recall stage is goctr_walk_recall_policy -- hops drawn by
+    ``sampler``'s weights (recall.WalkSampler; None: uniform hops), restarts, walks dealt to history slots by degree; the same dict.
+    ``recall_kw``: goctr_recall_cfg fields and goctr_walkp_cfg's (the walk's, alloc, restart_q).  What RecommendWalkPolicy /
+    RecommendWalkPolicyBatch / EvaluateLeaveOneOutWalkPolicy call."""
+    cfg, pcfg = _split_kw(recall_cfg, pcfg, recall_kw, _WALKP_FIELDS, make_walkp_cfg)
+    check_walkp_cfg(pcfg)
+    users, ts, targets = request_columns(users, ts, targets)
+    head = (*_request_head(model, graph, sampler), *_request_args(users, ts), capi.ptr(targets, C.c_int32), C.byref(cfg), C.byref(pcfg),
+            *_k_pass(k, pass_rows))
+    return _ranked_call("goctr_recommend_walk_policy", head, users.size, k, cfg.n_cand, targets, validate)
 
 
 def usercf(model: Predictor, ucf, users, ts=None, targets=None, k=10, pass_rows=0, validate=False, recall_cfg=None, ucfg=None,
@@ -963,6 +979,22 @@ def RecommendWalk(model: Predictor, graph, userId: int, n=10, now=None, **recall
     return RecommendWalkBatch(model, graph, [userId], n, now, **recall_kw)[0]
 
 
+def RecommendWalkPolicyBatch(model: Predictor, graph, sampler, userIds, n=10, now=None, **recall_kw):
+    """RecommendWalkPolicy for several users in one device call: [[ItemScore]] in the order of userIds.  ``now``: one timestamp for
+    all, or one per user."""
+    users, ts = _request_rows(model, userIds, now)
+    return _serve(model, users.size, lambda: walk_policy(model, graph, sampler, users, ts, None, n, **recall_kw))
+
+
+def RecommendWalkPolicy(model: Predictor, graph, sampler, userId: int, n=10, now=None, **recall_kw):
+    """EXTENSION -- RecommendWalk whose walks follow a policy: every hop is drawn by the edges' weights under ``sampler``
+    (BuildWalkSampler: repeats and recency of the behaviour behind an edge, damped by the degree of the node the hop lands on, so
+    that a catalogue hub soaks up fewer walks); with ``restart_q`` a walk returns to its history item with probability restart_q /
+    256 per step; with ``alloc`` = 1 the walks are dealt to the history items by the root of their degree.  ``sampler`` None:
+    uniform hops."""
+    return RecommendWalkPolicyBatch(model, graph, sampler, [userId], n, now, **recall_kw)[0]
+
+
 def RecommendUserCFBatch(model: Predictor, ucf, userIds, n=10, now=None, **recall_kw):
     """RecommendUserCF for several users in one device call: [[ItemScore]] in the order of userIds.  ``now``: one timestamp for all, or
     one per user."""
@@ -1063,6 +1095,13 @@ def BuildWalkGraph(recSys: DeviceRecSys, weights=None, **cfg):
     image at THIS call.  ``weights`` (an EdgeWeightCfg or a dict of half_life, ts_ref, cap) keeps an integer weight per edge from
     the repeats and ages of its entries; BuildALS reads it."""
     return WalkGraph(_dense_cache(recSys, "build the walk graph from"), recSys.item_table.shape[0], weights=weights, **cfg)
+
+
+def BuildWalkSampler(graph: WalkGraph, **cfg):
+    """EXTENSION: the hop sampler (recall.WalkSampler; ``cfg``: goctr_walksampler_cfg fields -- damp_item, damp_user) over ``graph``
+    (BuildWalkGraph, with ``weights`` for hops by repeats and recency) -- what RecommendWalkPolicy draws its hops from.  One pass
+    over the edges and two scans; it is rebuilt with the graph."""
+    return WalkSampler(graph, **cfg)
 
 
 def BuildItemCF(recSys: DeviceRecSys, **cfg):
@@ -1403,6 +1442,34 @@ def EvaluateLeaveOneOutWalk(model: Predictor, graph=None, k=10, sample_kw=None, 
     finally:
         if own is not None:
             own.close()
+    out = _loo_figures(r, targets, model.recSys.item_table.shape[0], k, cfg.n_cand)
+    if details:
+        out.update(_details(r, users, targets, ts))
+    return out
+
+
+def EvaluateLeaveOneOutWalkPolicy(model: Predictor, graph=None, sampler=None, k=10, sample_kw=None, details=False, pass_rows=0,
+                                  graph_kw=None, weights=None, sampler_kw=None, **recall_kw):
+    """EvaluateLeaveOneOutWalk with goctr_recommend_walk_policy as the recall stage.  ``graph`` None: the graph (``graph_kw``,
+    ``weights``: BuildWalkGraph's) and the sampler over it (``sampler_kw``: goctr_walksampler_cfg fields) are built here under
+    EvaluateLeaveOneOutWalk's window, which keeps the held-out events out of both, and closed on the way out; a caller's own
+    ``graph`` and ``sampler`` (None: uniform hops) are used as they are."""
+    users, targets, ts = _held_out_rows(model, sample_kw)
+    recall_kw.setdefault("exclude", "before")
+    cfg, pcfg = _split_kw(None, None, recall_kw, _WALKP_FIELDS, make_walkp_cfg)
+    own = []
+    try:
+        if graph is None:
+            gkw = dict(graph_kw or {})
+            gkw.setdefault("ts_hi", int((sample_kw or {})["ts_lo"]) - 1 if "ts_lo" in (sample_kw or {}) else int(ts.min()))
+            graph = BuildWalkGraph(model.recSys, weights, **gkw)
+            own.append(graph)
+            sampler = BuildWalkSampler(graph, **(sampler_kw or {}))
+            own.append(sampler)
+        r = walk_policy(model, graph, sampler, users, ts, targets, k, pass_rows, recall_cfg=cfg, pcfg=pcfg)
+    finally:
+        for h in reversed(own):
+            h.close()
     out = _loo_figures(r, targets, model.recSys.item_table.shape[0], k, cfg.n_cand)
     if details:
         out.update(_details(r, users, targets, ts))

@@ -762,7 +762,8 @@ int  goctr_walkgraph_weights(goctr_walkgraph* g, int32_t* weighted, goctr_edgewe
  * One workgroup walks a row; threads own walks.  No output byte depends on how walks are dealt to threads, on the workgroup size
  * or on an arrival order: a visit has a fixed place (w * n_steps + s) and the counts are run lengths of one sorted list.  Host
  * arrays, the engine stream and the engine lock, like goctr_itemcf_recall.
- * Not covered: degree-weighted walk allocation, restarts and early stopping, edge weights, pruning of high-degree nodes. */
+ * Hops by edge weight, hub damping, restarts and walk allocation by degree: goctr_walk_recall_policy below.  This call draws every
+ * edge of a node alike and deals walks to slots in turn. */
 typedef struct {
   int32_t  n_walks;     /* 1 .. 2048                                  default 512 */
   int32_t  n_steps;     /* 1 .. 16; n_walks * n_steps <= 8192         default 4   */
@@ -777,6 +778,74 @@ int  goctr_walk_recall(goctr_walkgraph* g, goctr_ubcache* c, const int32_t* user
                        int32_t* out_items /*[n_req,n_cand]*/, uint32_t* out_w /*[n_req,n_cand]*/, int32_t* out_count /*[n_req]*/,
                        const int32_t* targets /*[n_req] or NULL*/, int32_t* out_target_pos /*[n_req] or NULL*/,
                        int32_t* out_trace /*[n_req, n_walks*n_steps] or NULL*/);
+
+/* Walk policy: hops drawn by edge weight with hub damping, restarts, and walks dealt to history slots by degree.  goctr_walk_recall
+ * above draws every edge of a node alike; goctr_walk_recall_policy is that call with three rules changed, each of them off by
+ * default.  All arithmetic is integer and every output is defined bit for bit (tests/walkp_ref.py is the host restatement).
+ *
+ * goctr_walksampler_build, over a graph g:
+ *   r              the graph's edge weight (uw[e] / iw[e]); on an unweighted graph r = 65536 for every edge
+ *   d              the graph degree of the node the hop LANDS on: |U_j| for a user -> item edge (u, j), |I_u| for an item -> user
+ *                  edge (i, u); d >= 1 for an edge's endpoint
+ *   D              by the damping of that side (damp_item for user -> item edges, damp_user for item -> user edges): damp 0: 1;
+ *                  damp 1: the smallest s with s^2 >= d; damp 2: d.  damp_item is RP3beta's popularity penalty at beta = 1/2 or
+ *                  1, damp_user down-weights heavy users as Swing's alpha does
+ *   hop weight     omega = max(1, floor(min(r, 2^24 - 1) * 256 / D)) as a uint32.  omega >= 1: an edge of weight 0 stays drawable
+ *                  and no node of degree >= 1 becomes a dead end
+ *   ucum, icum     the exclusive prefix sums of omega over the whole uitems and the whole iusers edge array, in uint64:
+ *                  cum[0] = 0, cum[e + 1] = cum[e] + omega(e); [n_edges + 1] each (a total stays below 2^63)
+ *   info           n_users, n_items, n_edges and cache_version are the graph's; weighted = the graph had weights; cfg as given
+ *   refused        (-1, *out untouched) a NULL argument; a damp outside 0 .. 2; reserved != 0
+ * An empty graph builds an empty sampler (ucum = icum = {0}).  The sampler keeps nothing of the graph but the four info values; it
+ * is immutable, lives on the graph's engine, and two builds give the same bytes.  The engine stream and the engine lock, like
+ * goctr_walkgraph_build.
+ *
+ * goctr_walk_recall_policy: history, random word X(w,s,a), dead ends, the self-skip rule, counts, score, seen, order, outputs,
+ * padding and trace are goctr_walk_recall's.  What differs:
+ *   weighted pick  (a sampler is given) a node's run is [first, first + d) of its edge array and T = cum[first + d] - cum[first].
+ *                  y = the high 64 bits of (((x >> 32) << 32) * T) = ((x >> 32) * T) >> 32, and the drawn edge is the one e of the
+ *                  run with cum[e] <= cum[first] + y < cum[e + 1].  The item -> user hop reads icum with X(w,s,0), the user ->
+ *                  item hop ucum with X(w,s,1).  With equal weights W on a node floor(floor(x_hi d W / 2^32) / W) =
+ *                  floor(x_hi d / 2^32) = idx(x, d): a damp 0 / 0 sampler over an unweighted graph returns goctr_walk_recall's
+ *                  bytes.  No output byte depends on how the run is searched
+ *   restart        (restart_q 1 .. 255) at every step s >= 1 of a live walk, before the hop: if (X(w,s,2) >> 56) < restart_q the
+ *                  current item becomes h_t again.  With restart_q = 0 the word is not drawn
+ *   allocation     alloc 0: slot t = w mod H.  alloc 1: a_t = the smallest s with s^2 >= |U_{h_t}| (0 for an item the graph does
+ *                  not know), A_0 = 0, A_{t+1} = A_t + a_t, and walk w belongs to the slot with A_t <= floor(w A_H / n_walks) <
+ *                  A_{t+1}: no draw, and no walk is spent on a dead-end start.  A_H = 0: the row records nothing (count 0, trace -1)
+ *   refused        (-1, nothing touched) goctr_walk_recall's refusals with pcfg->walk in wcfg's place; alloc outside 0 .. 1;
+ *                  restart_q outside 0 .. 255; reserved != 0; a sampler whose n_users, n_items, n_edges or cache_version differ
+ *                  from the graph's, or on another engine
+ * A NULL sampler draws uniform hops; with alloc 0 and restart_q 0 the call then returns goctr_walk_recall's bytes.
+ * Not covered: a goctr_recommend_blend_walk variant; early stopping; edge pruning (damping stands in for it); allocation by the
+ * recency of a history entry (the history gather carries no timestamps); updating a sampler after goctr_ubcache_append (it is
+ * rebuilt with the graph). */
+typedef struct {
+  int32_t damp_item;   /* 0, 1, 2: the landing item's degree to the power 0, 1/2, 1 divides the weight     default 0 */
+  int32_t damp_user;   /* 0, 1, 2: the landing user's                                                      default 0 */
+  int64_t reserved;    /* must be 0 */
+} goctr_walksampler_cfg;
+void goctr_walksampler_cfg_default(goctr_walksampler_cfg* c);
+typedef struct goctr_walksampler goctr_walksampler;
+int  goctr_walksampler_build(goctr_walkgraph* g, const goctr_walksampler_cfg* cfg, goctr_walksampler** out);
+void goctr_walksampler_destroy(goctr_walksampler* s);
+/* each may be NULL */
+int  goctr_walksampler_info(goctr_walksampler* s, int64_t* n_users, int64_t* n_items, int64_t* n_edges, uint64_t* cache_version,
+                            int32_t* weighted, goctr_walksampler_cfg* cfg);
+/* each may be NULL */
+int  goctr_walksampler_export(goctr_walksampler* s, uint64_t* ucum /*[n_edges+1]*/, uint64_t* icum /*[n_edges+1]*/);
+typedef struct {
+  goctr_walk_cfg walk;  /* default goctr_walk_cfg_default's */
+  int32_t  alloc;       /* 0 = w mod H, 1 = by the root of the slot's degree   default 0 */
+  int32_t  restart_q;   /* 0 .. 255: restart with probability restart_q / 256  default 0 */
+  int64_t  reserved;    /* must be 0 */
+} goctr_walkp_cfg;
+void goctr_walkp_cfg_default(goctr_walkp_cfg* c);
+int  goctr_walk_recall_policy(goctr_walkgraph* g, goctr_walksampler* s /* NULL = uniform hops */, goctr_ubcache* c,
+                              const int32_t* users, const int64_t* ts /* NULL = 0 */, int64_t n_req, const goctr_recall_cfg* cfg,
+                              const goctr_walkp_cfg* pcfg, int32_t* out_items /*[n_req,n_cand]*/, uint32_t* out_w /*[n_req,n_cand]*/,
+                              int32_t* out_count /*[n_req]*/, const int32_t* targets /*[n_req] or NULL*/,
+                              int32_t* out_target_pos /*[n_req] or NULL*/, int32_t* out_trace /*[n_req, n_walks*n_steps] or NULL*/);
 
 /* ---- UserCF recall: user neighbours, then their recent items (no reference counterpart).  Every channel above reaches a candidate
  * from the request user's own history; this one asks which users are like this one and what they have just taken.  The neighbour
@@ -1087,6 +1156,18 @@ int goctr_recommend_walk(goctr_model* m, goctr_recsys* r, goctr_walkgraph* g,
                          int32_t* out_items /* [n_req,k] */, float* out_scores /* [n_req,k] */, int32_t* out_count,
                          int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank,
                          int32_t* cand_items, uint32_t* cand_w, float* cand_scores, int64_t* n_failed);
+
+/* goctr_recommend_walk_policy: goctr_recommend_walk with goctr_walk_recall_policy as its recall stage: the sampler (NULL = uniform
+ * hops) behind the graph and pcfg in wcfg's place.  Every other argument, output and documented property is goctr_recommend_walk's.
+ *   refused        goctr_recommend_walk's refusals with pcfg->walk in wcfg's place, and goctr_walk_recall_policy's of pcfg and of
+ *                  the sampler */
+int goctr_recommend_walk_policy(goctr_model* m, goctr_recsys* r, goctr_walkgraph* g, goctr_walksampler* s /* may be NULL */,
+                                const int32_t* users, const int64_t* ts /* NULL = 0 */, int64_t n_req,
+                                const int32_t* targets /* [n_req] or NULL */, const goctr_recall_cfg* recall_cfg,
+                                const goctr_walkp_cfg* pcfg, int32_t k, int64_t pass_rows,
+                                int32_t* out_items /* [n_req,k] */, float* out_scores /* [n_req,k] */, int32_t* out_count,
+                                int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank,
+                                int32_t* cand_items, uint32_t* cand_w, float* cand_scores, int64_t* n_failed);
 
 /* goctr_recommend_usercf: goctr_recommend_itemcf with the UserCF recall (goctr_usercf_recall above) as its recall stage, over the
  * recsys's cache image.  Arguments and outputs are goctr_recommend_walk's with the handle and ucfg in place of the graph and wcfg;
@@ -1522,6 +1603,8 @@ int goctr_recommend_uservec_ivf(goctr_model* m, goctr_recsys* r, goctr_itemvec_i
  *                  byte for byte the items goctr_itemcf_recall / goctr_walk_recall / goctr_uservec_recall /
  *                  goctr_uservec_recall_ivf / goctr_als_recall / goctr_usercf_recall return for the row under {recall_cfg->history, n_cand = n_list_c,
  *                  recall_cfg->exclude} and the channel's cfg, for the same users, ts and targets over the same image of the cache
+ *   WALK_POLICY    byte for byte the items goctr_walk_recall_policy returns in the same way: handle = the graph, handle2 = the
+ *                  sampler or NULL, cfg = a goctr_walkp_cfg
  *   POPULAR        the handle's stored list in list order; an entry is skipped if it is seen (goctr_blend_recall's rule) unless
  *                  it equals targets[q]; the list is cut at n_list_c KEPT entries
  *   LIST           the caller's row `list[q * n_list_c ..]` in its order; an entry is skipped if it is outside [0, n_items), if
@@ -1553,7 +1636,7 @@ int goctr_recommend_uservec_ivf(goctr_model* m, goctr_recsys* r, goctr_itemvec_i
  * c == NULL: there is no history and nothing is seen, so only POPULAR and LIST channels yield entries.  The two sums are limits of
  * the implementation: the union of a row's lists and its hash table sit in one workgroup's LDS. */
 enum { GOCTR_FUSE_ITEMCF = 0, GOCTR_FUSE_WALK, GOCTR_FUSE_USERVEC, GOCTR_FUSE_USERVEC_IVF, GOCTR_FUSE_ALS, GOCTR_FUSE_POPULAR,
-       GOCTR_FUSE_LIST, GOCTR_FUSE_USERCF /* appended: no earlier value moves */ };
+       GOCTR_FUSE_LIST, GOCTR_FUSE_USERCF /* appended: no earlier value moves */, GOCTR_FUSE_WALK_POLICY /* = 8, appended */ };
 enum { GOCTR_FUSE_RRF = 0, GOCTR_FUSE_ROUND_ROBIN = 1 };
 typedef struct {
   int32_t  kind;        /* GOCTR_FUSE_*                                                            */
@@ -1561,10 +1644,13 @@ typedef struct {
   uint32_t weight;      /* 0 .. 65535 (RRF only)                                                   */
   int32_t  reserve;     /* 0 .. n_list: the channel's first `reserve` kept entries are guaranteed  */
   const void* handle;   /* goctr_itemcf* | goctr_walkgraph* | goctr_itemvec* | goctr_itemvec_index* |
-                           goctr_als* | goctr_popular* | NULL (LIST) | goctr_usercf*               */
-  const void* handle2;  /* ALS: the goctr_itemvec* it ranks against; else NULL                     */
+                           goctr_als* | goctr_popular* | NULL (LIST) | goctr_usercf* |
+                           goctr_walkgraph* (WALK_POLICY)                                         */
+  const void* handle2;  /* ALS: the goctr_itemvec* it ranks against; WALK_POLICY: the
+                           goctr_walksampler* or NULL; else NULL                                   */
   const void* cfg;      /* goctr_walk_cfg* | goctr_uservec_cfg* (USERVEC, ALS) |
-                           goctr_uservec_ivf_cfg* | goctr_usercf_recall_cfg* | NULL                */
+                           goctr_uservec_ivf_cfg* | goctr_usercf_recall_cfg* | NULL |
+                           goctr_walkp_cfg* (WALK_POLICY)                                          */
   const int32_t* list;  /* LIST: host [n_req, n_list], -1 = no entry; else NULL                    */
 } goctr_fuse_channel;
 typedef struct {
