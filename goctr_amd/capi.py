@@ -260,6 +260,11 @@ class AlsCfg(C.Structure):
                 ("reserved", C.c_int64)]
 
 
+class AlsCgCfg(C.Structure):
+    """goctr_als_cg_cfg (include/goctr.h)"""
+    _fields_ = [("als", AlsCfg), ("cg_steps", C.c_int32), ("foldin_steps", C.c_int32), ("reserved", C.c_int64)]
+
+
 class EaseCfg(C.Structure):
     """goctr_ease_cfg (include/goctr.h)"""
     _fields_ = [("n_nbr", C.c_int32), ("max_items", C.c_int32), ("min_degree", C.c_int32), ("scale", C.c_int32),
@@ -412,6 +417,7 @@ SYMBOLS = [
     "goctr_als_export", "goctr_als_set_factors", "goctr_itemvec_build_als", "goctr_itemcf_build_als", "goctr_als_foldin",
     "goctr_als_recall", "goctr_recommend_als", "goctr_recommend_blend_als",
     "goctr_als_create_weighted", "goctr_als_weights", "goctr_als_foldin_weights",
+    "goctr_als_cg_cfg_default", "goctr_als_create_cg", "goctr_als_solver",
     "goctr_ease_cfg_default", "goctr_ease_block_size", "goctr_itemcf_build_ease",
     "goctr_uservec_cfg_default", "goctr_uservec_recall", "goctr_recommend_uservec", "goctr_recommend_blend_uservec",
     "goctr_uservec_multi_cfg_default", "goctr_uservec_interests", "goctr_uservec_recall_multi", "goctr_recommend_uservec_multi",
@@ -453,7 +459,7 @@ def load() -> C.CDLL:
                      "goctr_calib_cfg_default", "goctr_calibrator_destroy", "goctr_boot_cfg_default",
                      "goctr_walkgraph_cfg_default", "goctr_walk_cfg_default", "goctr_walkgraph_destroy",
                      "goctr_edgeweight_cfg_default",
-                     "goctr_als_cfg_default", "goctr_als_destroy", "goctr_ease_cfg_default", "goctr_fuse_cfg_default",
+                     "goctr_als_cfg_default", "goctr_als_cg_cfg_default", "goctr_als_destroy", "goctr_ease_cfg_default", "goctr_fuse_cfg_default",
                      "goctr_itemattr_destroy", "goctr_usercf_cfg_default", "goctr_usercf_recall_cfg_default", "goctr_usercf_destroy",
                      "goctr_walksampler_cfg_default", "goctr_walkp_cfg_default", "goctr_walksampler_destroy"):
             getattr(_lib, name).restype = None
@@ -649,6 +655,9 @@ def load() -> C.CDLL:
         _lib.goctr_als_foldin.argtypes = [C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, C.c_int32, _f64, _i16, _i32]
         _lib.goctr_als_create_weighted.argtypes = [C.c_void_p, _als, C.POINTER(C.c_void_p)]
         _lib.goctr_als_weights.argtypes = [C.c_void_p, _i32, _ew, _i64]
+        _lib.goctr_als_cg_cfg_default.argtypes = [C.POINTER(AlsCgCfg)]
+        _lib.goctr_als_create_cg.argtypes = [C.c_void_p, C.POINTER(AlsCgCfg), C.c_int32, C.POINTER(C.c_void_p)]
+        _lib.goctr_als_solver.argtypes = [C.c_void_p, _i32, _i32, _i32]
         _lib.goctr_als_foldin_weights.argtypes = [C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, C.c_int32, _i32, _u32, _i32]
         _lib.goctr_als_recall.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, C.POINTER(RecallCfg), _uv, _i32,
                                           _u32, _i32, _i32, _i32, _i16, _f64]
@@ -830,6 +839,8 @@ default_walkp_cfg = _default(WalkPolicyCfg, "goctr_walkp_cfg_default")
 default_usercf_cfg = _default(UsercfCfg, "goctr_usercf_cfg_default")
 default_usercf_recall_cfg = _default(UsercfRecallCfg, "goctr_usercf_recall_cfg_default")
 default_als_cfg = _default(AlsCfg, "goctr_als_cfg_default")
+default_als_cg_cfg = _default(AlsCgCfg, "goctr_als_cg_cfg_default")
+ALS_CHOLESKY, ALS_CG = 0, 1                 # goctr_als_solver's solvers
 default_fuse_cfg = _default(FuseCfg, "goctr_fuse_cfg_default")
 ALS_USERS, ALS_ITEMS = 0, 1                 # goctr_als_step's sides
 default_ease_cfg = _default(EaseCfg, "goctr_ease_cfg_default")

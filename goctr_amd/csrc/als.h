@@ -35,9 +35,22 @@ struct goctr_als {
   goctr::DevBuf<double> X, Y;                    // [n_users, D], [n_items, D]
   goctr::DevBuf<double> GX, GY;                  // [D, D] each; GX is a step's or a loss's scratch
   goctr_als_long long_users, long_items;
+  // goctr_als_create_cg's: the solver a half-step and a fold-in dispatch on, and the steps of either (als_cg.hip)
+  int solver = GOCTR_ALS_CHOLESKY;
+  int cg_steps = 0, foldin_steps = 0;
 };
 
 namespace goctr {
+
+// ---- the conjugate-gradient solver (als_cg.hip), what als.hip's two dispatch points call.  All queue on `st` / the engine stream
+// and wait for nothing
+struct FoldinArgs;                               // als_kernels.h
+// G = F^T F over F's n rows for D above the Cholesky kernels' 64, by their tile rule
+int als_gram_wide(const double* F, int64_t n, int D, double* G);
+// the row launches of one half-step of a CG handle: this side's factors from the other side's and their Gram matrix
+int als_cg_rows(const goctr_als* a, const goctr_walkgraph* g, int side);
+// the fold-in launch of a CG handle over nq request rows
+int als_cg_foldin(const goctr_als* a, const FoldinArgs& f, int64_t nq, hipStream_t st);
 
 // als_foldin_kernel over nq rows on `st`: sizes ws.p_hi / p_lo for nq rows ([nq + UV_PAD_ROWS, Dp], the pad rows zero) and writes
 // every row's planes into them; o_x [nq, D], o_p [nq, D] and o_n [nq] may be null.  Waits for nothing

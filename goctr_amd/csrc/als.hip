@@ -27,6 +27,8 @@
 //                      the whole launch.  als_part_kernel takes its segments, one workgroup each, and parks P and s in scratch; the
 //                      solve kernel's second form folds them in segment order.  The bytes are those of the first form: both run
 //                      als_segment and the same fold
+// A handle of goctr_als_create_cg (solver = GOCTR_ALS_CG) leaves this file at two places, als_half_step and als_foldin_launch, for
+// als_cg.hip's conjugate-gradient kernels, and als_gram for the wide Gram above D = 64; everything else here serves both solvers.
 // Of the three alternatives left open -- a wavefront per short row, A's symmetry in the MFMA accumulation, a blocked Cholesky --
 // the symmetry is taken: a wavefront computes the tile pairs ti <= tj only (10 of 16 at D = 64) and writes both halves.  None of
 // the three has been timed against the others.
@@ -38,6 +40,7 @@
 
 #define GOCTR_NO_PLAIN_KERNELS      // the kernel headers' plain kernels belong to ctr.hip
 #include "als.h"
+#include "als_kernels.h"
 #include "itemvec.h"
 #include "lds_lists.h"
 #include "mfma_gemm.h"
@@ -49,16 +52,13 @@ using namespace goctr;
 
 namespace {
 
-constexpr int ALS_THREADS = 256, ALS_WAVES = ALS_THREADS / 64;
-constexpr int ALS_SEG = 256;                   // edges of a segment: the summation tree's unit
 constexpr int ALS_CH = 64;                     // edges staged in LDS at a time
 constexpr int ALS_MAXD = 64;
+constexpr int ALS_CG_MAXD = 256;               // a CG handle's (als_cg.hip: four components a lane)
 constexpr int ALS_AS = ALS_MAXD + 1;           // A's row stride in LDS: a column walk hits every bank
 constexpr int ALS_NS = 80;                     // the largest staged row stride (tn_lds_stride(64))
 constexpr int ALS_PAIRS = 3;                   // tile pairs a wavefront holds: ceil(10 / 4)
-constexpr int ALS_MAX_H = 256;                 // goctr_als_foldin's limit on history: one segment
 constexpr int64_t ALS_MAX_PARTS = 2048;        // parts (D * D + D doubles each) the scratch holds: 68 MB at D = 64
-static_assert(ALS_MAX_H <= ALS_SEG, "a request row is one segment");
 static_assert(ALS_MAXD <= 64, "the triangular solves give every component a lane of one wavefront");
 
 using acc_t = Mfma<double>::acc_t;
@@ -78,14 +78,6 @@ template <>
 struct AlsLdsT<true> : AlsLds {
   double rho[ALS_CH], cw[ALS_CH];
 };
-
-// the p-th tile pair (ti <= tj) of T tiles a side, row by row
-__device__ __forceinline__ void als_pair(int p, int T, int& ti, int& tj) {
-  ti = 0;
-  int len = T;
-  while (p >= len) { p -= len; ++ti; --len; }
-  tj = ti + p;
-}
 
 // One segment: the ne <= 256 rows F[idx[e0 + e]] (idx null: F[e0 + e]) of D doubles.  acc[k] = the tile pair wave + 4 k of N^T N,
 // *bseg (threads below D) = the sum of the rows.  Every thread of the workgroup enters; the first statement is a barrier.
@@ -320,61 +312,6 @@ __global__ __launch_bounds__(ALS_THREADS) void als_solve_kernel(SolveArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------------------ the fold-in
-struct FoldinArgs {
-  const long long* off; const int32_t* seq_items; const long long* seq_ts;   // the cache's image (null: no cache)
-  long long n_items;
-  const int32_t* users; const long long* ts;
-  int H, D, Dp; double alpha, lambda;
-  const double* Y; const double* G;
-  signed char* p_hi; signed char* p_lo;        // [nq + pad, Dp]
-  double* out_x; int16_t* out_p; int32_t* out_n;             // each may be null
-  u64 half_life, cap; long long ts_ref;        // W: the handle's weight rule (cap as it applies) and reference time
-};
-
-// The weighted history of a request row.  The history is lds_gather_history's -- the first H valid entries the timestamp filter
-// keeps -- with every entry's contribution 2^(16 - b) against ts_ref beside it; one descending sort of (item + 1) << 32 | contribution
-// makes an item's entries a run, whose first position adds the run up: uniq[rank] = the item (descending, as the unweighted
-// kernel's), uwt[rank] = min(cap, the sum).  Integer sums: the order inside a run cannot show.  Returns the distinct items; every
-// thread of the workgroup enters, uniq[] and uwt[] are complete behind the caller's next barrier
-__device__ inline int als_weighted_history(const int32_t* seq_items, const long long* seq_ts, long long lo_e, long long len,
-                                           long long mts, long long n_items, int H, u64 half_life, long long ts_ref, u64 cap,
-                                           unsigned long long* key, int* uniq, uint32_t* uwt, int* wcnt) {
-  const int tid = threadIdx.x;
-  key[tid] = 0ull;
-  __syncthreads();
-  int nh = 0;
-  for (long long p0 = 0; p0 < len && nh < H; p0 += ALS_THREADS) {
-    const long long p = p0 + tid;
-    int it = -1;
-    long long t = 0;
-    if (p < len) {
-      t = seq_ts[lo_e + p];                                  // (a cache image always has its timestamps)
-      if (mts == 0 || t <= mts) it = seq_items[lo_e + p];
-    }
-    const bool valid = it >= 0 && it < n_items;
-    int tot;
-    const int r = nh + lds_block_rank<ALS_WAVES>(valid, wcnt, &tot);
-    if (valid && r < H) {
-      const u64 b = decay_bucket(half_life, t, ts_ref);
-      key[r] = ((unsigned long long)(unsigned int)(it + 1) << 32) | (b <= 16 ? 1ull << (16 - b) : 0ull);
-    }
-    nh += tot;
-    __syncthreads();
-  }
-  lds_sort_desc(key, ALS_MAX_H, tid, ALS_THREADS);
-  const unsigned long long mine = key[tid] >> 32;
-  const bool head = mine != 0ull && (tid == 0 || (key[tid - 1] >> 32) != mine);
-  int nu;
-  const int rank = lds_block_rank<ALS_WAVES>(head, wcnt, &nu);
-  if (head) {
-    u64 sum = 0;
-    for (int e = tid; e < ALS_MAX_H && (key[e] >> 32) == mine; ++e) sum += key[e] & 0xffffffffull;
-    uniq[rank] = (int)mine - 1;
-    uwt[rank] = (uint32_t)(sum < cap ? sum : cap);
-  }
-  return nu;
-}
-
 // goctr_als_foldin_weights: row q's distinct items ascending and their weights, padded with -1 / 0
 __global__ __launch_bounds__(ALS_THREADS) void als_foldin_weights_kernel(FoldinArgs a, int32_t* __restrict__ out_items,
                                                                          uint32_t* __restrict__ out_r) {
@@ -517,8 +454,8 @@ struct AlsScratch {
   DevBuf<double> parts, usum, total;
 };
 
-int als_check_cfg(const goctr_als_cfg* c, const char* who) {
-  GOCTR_CHECK(c->D >= 4 && c->D <= ALS_MAXD, "%s: D = %d is outside 4 .. %d", who, c->D, ALS_MAXD);
+int als_check_cfg(const goctr_als_cfg* c, const char* who, int max_d = ALS_MAXD) {
+  GOCTR_CHECK(c->D >= 4 && c->D <= max_d, "%s: D = %d is outside 4 .. %d", who, c->D, max_d);
   GOCTR_CHECK(c->n_iters >= 0, "%s: n_iters = %d (>= 0)", who, c->n_iters);
   GOCTR_CHECK(std::isfinite(c->alpha) && c->alpha > 0.0, "%s: alpha = %g (a finite number above 0)", who, c->alpha);
   GOCTR_CHECK(std::isfinite(c->lambda) && c->lambda > 0.0, "%s: lambda = %g (a finite number above 0)", who, c->lambda);
@@ -570,6 +507,7 @@ int als_plan_long(const std::vector<uint2>& node, int long_thr, goctr_als_long& 
 
 // G = F^T F over F's n rows (queued on the engine stream; the scratch is the engine's)
 int als_gram(const double* F, int64_t n, int D, double* G) {
+  if (D > ALS_MAXD) return als_gram_wide(F, n, D, G);        // (a CG handle's: als_segment holds 3 tile pairs a wavefront)
   hipStream_t st = engine().stream;
   AlsScratch& ws = engine_scratch<AlsScratch>();
   const int64_t tiles = cdiv(n, ALS_SEG);
@@ -602,6 +540,13 @@ int als_half_step(goctr_als* a, const goctr_walkgraph* g, int side) {
   const bool users = side == GOCTR_ALS_USERS;
   const int D = a->D;
   if (!users && als_gram(a->X.p, a->n_users, D, a->GX.p)) return -1;
+  if (a->solver == GOCTR_ALS_CG) {
+    if (als_cg_rows(a, g, side)) return -1;
+    if (!users && als_gram(a->Y.p, a->n_items, D, a->GY.p)) return -1;       // G_Y follows every write of Y
+    GOCTR_HIP(hipStreamSynchronize(st));
+    a->half_steps += 1;
+    return 0;
+  }
   SolveArgs s{};
   s.F = users ? a->Y.p : a->X.p; s.G = users ? a->GY.p : a->GX.p;
   s.node = users ? g->unode.p : g->inode.p; s.edges = users ? g->uitems.p : g->iusers.p;
@@ -657,6 +602,10 @@ int als_foldin_launch(const goctr_als* a, const CacheSeq& seq, const int32_t* us
   f.off = seq.off; f.seq_items = seq.items; f.seq_ts = seq.ts; f.n_items = a->n_items; f.users = users; f.ts = ts;
   f.H = history; f.D = a->D; f.Dp = Dp; f.alpha = a->cfg.alpha; f.lambda = a->cfg.lambda; f.Y = a->Y.p; f.G = a->GY.p;
   f.p_hi = ws.p_hi.p; f.p_lo = ws.p_lo.p; f.out_x = o_x; f.out_p = o_p; f.out_n = o_n;
+  if (a->solver == GOCTR_ALS_CG) {
+    als_foldin_rule(a, f);
+    return als_cg_foldin(a, f, nq, st);
+  }
   if (a->weighted) {
     als_foldin_rule(a, f);
     hipLaunchKernelGGL(als_foldin_kernel<true>, dim3((unsigned)nq), dim3(ALS_THREADS), 0, st, f);
@@ -708,16 +657,24 @@ void goctr_als_cfg_default(goctr_als_cfg* c) {
 }
 
 // the create behind goctr_als_create and goctr_als_create_weighted (the caller has entered the graph's engine)
-static int als_create(goctr_walkgraph* g, const goctr_als_cfg* cfg, bool weighted, goctr_als** out, const char* who) {
+// cg: goctr_als_create_cg's cfg around `cfg` (null: the Cholesky solver)
+static int als_create(goctr_walkgraph* g, const goctr_als_cfg* cfg, bool weighted, goctr_als** out, const char* who,
+                      const goctr_als_cg_cfg* cg = nullptr) {
   GOCTR_CHECK(g && cfg && out, "%s: null argument (graph, cfg, out)", who);
   GOCTR_CHECK(!weighted || g->weighted, "%s: the graph has no edge weights (goctr_walkgraph_build_weighted makes them)", who);
-  if (als_check_cfg(cfg, who) || iv_check_shape(g->n_items, cfg->D, who)) return -1;
+  if (als_check_cfg(cfg, who, cg ? ALS_CG_MAXD : ALS_MAXD) || iv_check_shape(g->n_items, cfg->D, who)) return -1;
+  if (cg) {
+    GOCTR_CHECK(cg->cg_steps >= 1 && cg->cg_steps <= 64, "%s: cg_steps = %d is outside 1 .. 64", who, cg->cg_steps);
+    GOCTR_CHECK(cg->foldin_steps >= 1 && cg->foldin_steps <= 64, "%s: foldin_steps = %d is outside 1 .. 64", who, cg->foldin_steps);
+    GOCTR_CHECK(cg->reserved == 0, "%s: reserved = %lld (must be 0)", who, (long long)cg->reserved);
+  }
   GOCTR_CHECK(g->n_users > 0, "%s: the graph has no users", who);
   hipStream_t st = engine().stream;
   std::unique_ptr<goctr_als> a(new goctr_als);
   StreamDrain drain{st};                       // (behind the handle: an error return drains the stream before its buffers go)
   a->n_users = g->n_users; a->n_items = g->n_items; a->n_edges = g->n_edges; a->cfg = *cfg; a->D = cfg->D;
   if (weighted) { a->weighted = true; a->rule = g->rule; a->ts_ref_used = g->ts_ref_used; }
+  if (cg) { a->solver = GOCTR_ALS_CG; a->cg_steps = cg->cg_steps; a->foldin_steps = cg->foldin_steps; }
   a->long_thr = std::max(ALS_SEG, env_int("GOCTR_ALS_LONG_ROW", 4096));
   const size_t D = (size_t)cfg->D;
   if (a->X.alloc((size_t)a->n_users * D) || a->Y.alloc((size_t)a->n_items * D, false) || a->GX.alloc(D * D) || a->GY.alloc(D * D)) return -1;
@@ -741,6 +698,26 @@ int goctr_als_create(goctr_walkgraph* g, const goctr_als_cfg* cfg, goctr_als** o
 int goctr_als_create_weighted(goctr_walkgraph* g, const goctr_als_cfg* cfg, goctr_als** out) {
   GOCTR_ENTER_H(g);
   return als_create(g, cfg, true, out, "goctr_als_create_weighted");
+}
+
+void goctr_als_cg_cfg_default(goctr_als_cg_cfg* c) {
+  if (!c) return;
+  goctr_als_cfg_default(&c->als);
+  c->cg_steps = 3; c->foldin_steps = 10; c->reserved = 0;
+}
+
+int goctr_als_create_cg(goctr_walkgraph* g, const goctr_als_cg_cfg* cfg, int32_t weighted, goctr_als** out) {
+  GOCTR_ENTER_H(g);
+  return als_create(g, cfg ? &cfg->als : nullptr, weighted != 0, out, "goctr_als_create_cg", cfg);
+}
+
+int goctr_als_solver(goctr_als* a, int32_t* solver, int32_t* cg_steps, int32_t* foldin_steps) {
+  GOCTR_ENTER_H(a);
+  GOCTR_CHECK(a, "goctr_als_solver: null handle");
+  if (solver) *solver = a->solver;
+  if (cg_steps) *cg_steps = a->cg_steps;
+  if (foldin_steps) *foldin_steps = a->foldin_steps;
+  return 0;
 }
 
 int goctr_als_weights(goctr_als* a, int32_t* weighted, goctr_edgeweight_cfg* rule, int64_t* ts_ref_used) {

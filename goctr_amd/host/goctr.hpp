@@ -1232,6 +1232,17 @@ class ALS {
     check(goctr_als_create_weighted(a.graph_, &cfg, &a.h_));
     return a;
   }
+  // rows solved by conjugate gradient (goctr_als_create_cg): D up to 256, cfg.cg_steps steps a training row, cfg.foldin_steps a
+  // fold-in; weighted as CreateWeighted.  Every other member works on the handle as on a Cholesky one
+  static goctr_als_cg_cfg DefaultCgCfg() { goctr_als_cg_cfg c; goctr_als_cg_cfg_default(&c); return c; }
+  static ALS CreateCG(const WalkGraph& graph, const goctr_als_cg_cfg& cfg = DefaultCgCfg(), bool weighted = false) {
+    ALS a;
+    a.graph_ = graph.handle();
+    check(goctr_als_create_cg(a.graph_, &cfg, weighted ? 1 : 0, &a.h_));
+    return a;
+  }
+  // GOCTR_ALS_CHOLESKY or GOCTR_ALS_CG
+  int32_t Solver() const { int32_t s = 0; check(goctr_als_solver(h_, &s, nullptr, nullptr)); return s; }
   ALS(const ALS&) = delete;
   ALS& operator=(const ALS&) = delete;
   ALS(ALS&& o) noexcept : h_(o.h_), graph_(o.graph_), vec_(o.vec_) { o.h_ = nullptr; o.vec_ = nullptr; }

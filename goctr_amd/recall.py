@@ -611,9 +611,16 @@ class ALS(_Handle):
     training call"""
     _destroy = "goctr_als_destroy"
 
-    def __init__(self, graph: WalkGraph, cfg: capi.AlsCfg | None = None, weighted=None, **kw):
+    def __init__(self, graph: WalkGraph, cfg: capi.AlsCfg | None = None, weighted=None, solver="cholesky", cg_steps=None,
+                 foldin_steps=None, **kw):
         """``kw``: goctr_als_cfg fields (D, n_iters, alpha, lambda_, seed).  Allocates and initialises; runs no iteration.
-        ``weighted``: None = exactly when the graph is; True on a graph without weights raises; False ignores a graph's weights"""
+        ``weighted``: None = exactly when the graph is; True on a graph without weights raises; False ignores a graph's weights.
+        ``solver``: "cholesky" (D 4 .. 64) or "cg" (goctr_als_create_cg: D 4 .. 256, ``cg_steps`` conjugate-gradient steps a row of a
+        training half-step, default 3, and ``foldin_steps`` of a fold-in, default 10)"""
+        if solver not in ("cholesky", "cg"):
+            raise ValueError('solver is "cholesky" or "cg"')
+        if solver != "cg" and (cg_steps is not None or foldin_steps is not None):
+            raise TypeError('cg_steps and foldin_steps belong to solver="cg"')
         graph_weighted = bool(getattr(graph, "weighted", False))
         if weighted is None:
             weighted = graph_weighted
@@ -623,8 +630,13 @@ class ALS(_Handle):
         self.graph = graph
         self.weighted = bool(weighted)
         self._h = C.c_void_p()
-        create = capi.load().goctr_als_create_weighted if self.weighted else capi.load().goctr_als_create
-        capi.check(create(graph._h, C.byref(cfg), C.byref(self._h)))
+        if solver == "cg":
+            steps = {k: _as_int(k, v) for k, v in (("cg_steps", cg_steps), ("foldin_steps", foldin_steps)) if v is not None}
+            cg = capi.default_als_cg_cfg(als=cfg, **steps)
+            capi.check(capi.load().goctr_als_create_cg(graph._h, C.byref(cg), C.c_int32(int(self.weighted)), C.byref(self._h)))
+        else:
+            create = capi.load().goctr_als_create_weighted if self.weighted else capi.load().goctr_als_create
+            capi.check(create(graph._h, C.byref(cfg), C.byref(self._h)))
         i = self.info()
         self.n_users, self.n_items, self.D = i["n_users"], i["n_items"], i["D"]
 
@@ -632,6 +644,12 @@ class ALS(_Handle):
         nu, ni, d, hs = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int64(0)
         capi.check(capi.load().goctr_als_info(self._h, C.byref(nu), C.byref(ni), C.byref(d), C.byref(hs)))
         return dict(n_users=nu.value, n_items=ni.value, D=d.value, half_steps=hs.value)
+
+    def solver(self) -> dict:
+        """goctr_als_solver: dict(solver "cholesky" | "cg", cg_steps, foldin_steps) -- the steps are 0 on a Cholesky handle"""
+        s, cs, fs = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        capi.check(capi.load().goctr_als_solver(self._h, C.byref(s), C.byref(cs), C.byref(fs)))
+        return dict(solver="cg" if s.value == capi.ALS_CG else "cholesky", cg_steps=cs.value, foldin_steps=fs.value)
 
     def weights(self) -> dict:
         """goctr_als_weights: dict(weighted bool, half_life, ts_ref, cap, ts_ref_used) -- the graph's rule as the handle keeps it;

@@ -1055,7 +1055,8 @@ def RecommendBlendALSBatch(model: Predictor, icf, pop, factors, userIds, n=10, n
 
 # ---- what the recall channels are built from
 def BuildALS(recSys: DeviceRecSys, graph=None, graph_kw=None, weight_kw=None, **cfg):
-    """EXTENSION: implicit-feedback ALS factors (recall.ALS; ``cfg``: goctr_als_cfg fields -- D, n_iters, alpha, lambda_, seed) fitted
+    """EXTENSION: implicit-feedback ALS factors (recall.ALS; ``cfg``: goctr_als_cfg fields -- D, n_iters, alpha, lambda_, seed -- and
+    recall.ALS's ``solver``: solver="cg", cg_steps, foldin_steps fit by conjugate gradient, D up to 256) fitted
     over ``graph`` (default: BuildWalkGraph of the recSys's cache, ``graph_kw`` its cfg), with the quantised item factors in
     ``.vectors`` -- what RecommendALS folds in against and scans.  ``weight_kw`` (goctr_edgeweight_cfg fields -- half_life, ts_ref,
     cap; {} for the defaults) builds the graph with edge weights and fits with per-edge confidence 1 + alpha r / 65536; a caller's

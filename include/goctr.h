@@ -1279,6 +1279,43 @@ int  goctr_als_create_weighted(goctr_walkgraph* g, const goctr_als_cfg* cfg, goc
 /* each may be NULL; a handle of goctr_als_create: *weighted = 0, the rest untouched */
 int  goctr_als_weights(goctr_als* a, int32_t* weighted, goctr_edgeweight_cfg* rule, int64_t* ts_ref_used);
 
+/* Conjugate-gradient solves: goctr_als_create_cg is goctr_als_create (weighted = 0) or goctr_als_create_weighted (weighted != 0) whose
+ * rows are solved by a fixed number of conjugate-gradient steps (Takacs, Pilaszy and Tikk 2011) instead of a Cholesky factorisation.
+ * A_u is never formed, a row's live state is a few vectors, and D goes to 256 (tests/alscg_ref.py is the host restatement).  The
+ * result is an ordinary goctr_als: every entry that takes a handle takes this one, at every D.
+ * A row has the edges e = 0 .. m-1 in CSR order, y_e the neighbour rows of the other side's factors F, G = F^T F, and
+ *   rho_e = 1 (an unweighted handle) or r_e / 65536 (a weighted one),  kappa_e = alpha rho_e,  c_e = 1 + kappa_e
+ *   E(v)           sum_e kappa_e (y_e . v) y_e
+ *   M(v)           (G v + lambda v) + E(v)                       -- A_u v without A_u
+ *   start          x = x0,  r = sum_e (c_e - kappa_e (y_e . x)) y_e - (G x + lambda x)  (one pass over the edges),  p = r,  rs = r . r
+ *   a step         q = M(p),  a = rs / (p . q),  x += a p,  r -= a q,  rs' = r . r,  p = r + (rs' / rs) p,  rs = rs'
+ *   steps          cfg->cg_steps of a training half-step's row, cfg->foldin_steps of a fold-in; a row stops early once rs < 2^-100
+ *   x0             a training step: the row's current factors.  X starts at zero, so the first user step starts cold and every
+ *                  later step is warm-started; goctr_als_set_factors therefore also sets the start.  A fold-in: 0
+ *   empty rows     the zero vector, as above
+ *   arithmetic     float64, every product and sum rounded once.  Finite inputs never fault; lambda > 0 keeps p . q > 0 while rs > 0
+ *   summation      FIXED, and a row's depends on the row and D alone: edge sums run in segments of 256 edges in CSR order, each
+ *                  from zero and ascending, the segments folded ascending (the rule above); a dot product over D is a tree that
+ *                  depends on D only; G v sums k ascending in steps of 4; the Gram matrix follows the rule above.  Two fits give
+ *                  the same bytes, and no output byte depends on which rows share a workgroup, on the grid or on the long-row
+ *                  threshold.  The ORDER itself is the implementation's: the restatement agrees within rounding, not bit for bit
+ *   fold-in        the history, the distinct items, their order and (a weighted handle) their weights are goctr_als_foldin's;
+ *                  the vector is CG from zero, the planes the same quantisation of it
+ *   refused        (-1, nothing touched, the error text set) goctr_als_create's refusals with D outside 4 .. 256 in the place of
+ *                  4 .. 64; cg_steps or foldin_steps outside 1 .. 64; reserved != 0; weighted != 0 over a graph without weights */
+typedef struct {
+  goctr_als_cfg als;      /* as goctr_als_create's, but D 4 .. 256 */
+  int32_t cg_steps;       /* 1 .. 64: steps of a training half-step's rows       default 3 */
+  int32_t foldin_steps;   /* 1 .. 64: steps of a fold-in (cold start)            default 10 */
+  int64_t reserved;       /* must be 0 */
+} goctr_als_cg_cfg;
+void goctr_als_cg_cfg_default(goctr_als_cg_cfg* c);
+#define GOCTR_ALS_CHOLESKY 0
+#define GOCTR_ALS_CG 1
+int  goctr_als_create_cg(goctr_walkgraph* g, const goctr_als_cg_cfg* cfg, int32_t weighted, goctr_als** out);
+/* each may be NULL; a handle of goctr_als_create / _create_weighted: *solver = GOCTR_ALS_CHOLESKY, the steps 0 */
+int  goctr_als_solver(goctr_als* a, int32_t* solver, int32_t* cg_steps, int32_t* foldin_steps);
+
 /* the item factors, device to device, into the existing builds: the results equal goctr_itemvec_build_vectors /
  * goctr_itemcf_build_vectors called with goctr_als_export's Y, byte for byte (the same quantise launch reads the same doubles) */
 int  goctr_itemvec_build_als(goctr_als* a, const int32_t* groups /* [n_items] or NULL */, goctr_itemvec** out);

@@ -6,18 +6,23 @@ goctr_als_recall) on walk_bench.py's cache.
                  max_len 50: the edges, the largest degrees, the rows above the long-row threshold on either side
     als_build    ms of goctr_walkgraph_build, and with --half-life of goctr_walkgraph_build_weighted (the handle closed inside
                  the timed call)
-    als_step     per D: ms of a user step and of an item step after one untimed iteration, with the algorithmic figures of the
+    als_step     (a cg line counts cg's own work: cg_steps + 1 passes of a gather, rows x D^2 dense and 2 x edges x D edge multiply-adds)
+                 per D: ms of a user step and of an item step after one untimed iteration, with the algorithmic figures of the
                  step -- the factor bytes gathered (edges x D x 8), the products of the accumulation (edges x D^2 multiply-adds;
                  the kernel computes the tile pairs ti <= tj only) and of the factorisations (rows x D^3 / 3)
     als_long     the item step again with GOCTR_ALS_LONG_ROW above the largest degree: every row stays in its workgroup, so the
                  hottest item's workgroup runs alone at the end of the launch -- what the segment path is for
     als_loss     ms of goctr_als_loss
+    als_fit      with --fit-iters N: the loss after N iterations from the initial Y (a fresh handle), what the solvers are compared by
     als_foldin   goctr_als_foldin and goctr_als_recall over the handle's own item vectors at history 50 / 256 candidates: request
                  rows per second; goctr_uservec_recall over the same vectors as the yardstick
 
 With --half-life H (and --cap C, 0 = none) every section after als_graph runs a second time over the weighted graph and a weighted
 handle (per-edge confidence from counts and recency; the fold-in weighs its history): the lines carry "weighted": true and, for the
 graph, the share of edges with weight 0 and the largest rho.
+
+With --solvers cholesky cg every section from als_step on runs for either solver in turn at every D (interleaved, so that both see
+the same session), the lines carry "solver"; D above 64 runs under cg alone.  --cg-steps sets goctr_als_cg_cfg.cg_steps.
 
 Random histories carry no taste, so there is no quality figure here.  Seeded; reads nothing outside the tree; fails without a
 device.  Every timed call is synchronous; one untimed call of each path comes first.  Prints one JSON line per section."""
@@ -26,6 +31,7 @@ import ctypes as C
 import json
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -48,6 +54,9 @@ def main():
     ap.add_argument("--half-life", type=int, default=None,
                     help="adds the weighted lines: goctr_edgeweight_cfg.half_life (0 = counts only)")
     ap.add_argument("--cap", type=int, default=0, help="goctr_edgeweight_cfg.cap of the weighted lines (0 = none)")
+    ap.add_argument("--solvers", nargs="+", default=["cholesky"], choices=["cholesky", "cg"])
+    ap.add_argument("--cg-steps", type=int, default=3)
+    ap.add_argument("--fit-iters", type=int, default=0, help="adds the als_fit lines: the loss after this many iterations")
     a = ap.parse_args()
     from goctr_amd import capi, recall as gl
     L = capi.init()
@@ -76,32 +85,47 @@ def main():
                               zero_weight_share=float((w["uw"] == 0).mean()), max_rho=float(w["uw"].max()) / 65536, **t)), flush=True)
         graphs.append((gw, True))
     for g, weighted in graphs:
-        for D in a.dims:
-            h = gl.ALS(g, D=D, n_iters=1).fit()
+        for D, solver in ((D, s) for D in a.dims for s in a.solvers if s == "cg" or D <= 64):
+            skw = dict(solver=solver, **(dict(cg_steps=a.cg_steps) if solver == "cg" else {}))
+            h = gl.ALS(g, D=D, n_iters=1, **skw).fit()
             for side, rows in (("users", int((du > 0).sum())), ("items", int((di > 0).sum()))):
                 t = timed(lambda: h.step(side), a.repeats)
                 sec = t["ms_median"] * 1e-3
                 gather, acc, chol = g.n_edges * D * 8, g.n_edges * D * D, rows * D ** 3 // 3
-                print(json.dumps(dict(bench="als_step", weighted=weighted, D=D, side=side, solved_rows=rows, gather_bytes=gather,
-                                      gather_GBps=gather / sec / 1e9, accumulate_fma=acc, factor_fma=chol,
-                                      GFMAps=(acc + chol) / sec / 1e9, **t)), flush=True)
+                if solver == "cg":           # cg_steps + 1 passes (no early stop counted): G v per row, a dot and an update per edge
+                    passes = a.cg_steps + 1
+                    work = dict(gather_bytes=passes * gather, gather_GBps=passes * gather / sec / 1e9, dense_fma=passes * rows * D * D,
+                                edge_fma=passes * 2 * g.n_edges * D, GFMAps=passes * (rows * D * D + 2 * g.n_edges * D) / sec / 1e9)
+                else:
+                    work = dict(gather_bytes=gather, gather_GBps=gather / sec / 1e9, accumulate_fma=acc, factor_fma=chol,
+                                GFMAps=(acc + chol) / sec / 1e9)
+                print(json.dumps(dict(bench="als_step", weighted=weighted, solver=solver, D=D, side=side, solved_rows=rows, **work, **t)),
+                      flush=True)
             os.environ["GOCTR_ALS_LONG_ROW"] = str(int(di.max()) + 1)
             try:
-                flat = gl.ALS(g, D=D, n_iters=1).set_factors(**h.export())
+                flat = gl.ALS(g, D=D, n_iters=1, **skw).set_factors(**h.export())
             finally:
                 os.environ.pop("GOCTR_ALS_LONG_ROW")
             t = timed(lambda: flat.step("items"), a.repeats)
-            print(json.dumps(dict(bench="als_long", weighted=weighted, D=D, side="items", long_rows_in_their_workgroups=True, **t)),
+            print(json.dumps(dict(bench="als_long", weighted=weighted, solver=solver, D=D, side="items", long_rows_in_their_workgroups=True, **t)),
                   flush=True)
             flat.close()
             t = timed(h.loss, a.repeats)
-            print(json.dumps(dict(bench="als_loss", weighted=weighted, D=D, loss=h.loss(), **t)), flush=True)
+            print(json.dumps(dict(bench="als_loss", weighted=weighted, solver=solver, D=D, loss=h.loss(), **t)), flush=True)
+            if a.fit_iters:
+                f = gl.ALS(g, D=D, n_iters=a.fit_iters, **skw)                   # (one fit, timed as it is: a second would go on
+                t0 = time.perf_counter()                                         # from the first's factors)
+                f.fit()
+                ms = (time.perf_counter() - t0) * 1e3
+                print(json.dumps(dict(bench="als_fit", weighted=weighted, solver=solver, D=D, iters=a.fit_iters, loss=f.loss(), ms=ms)),
+                      flush=True)
+                f.close()
             v = h.item_vectors()
             kw = dict(history=50, n_cand=256)
             for name, fn in (("foldin", lambda: h.foldin(ub, users, history=50)), ("als_recall", lambda: h.recall_users(v, ub, users, **kw)),
                              ("uservec_recall", lambda: v.recall_users(ub, users, **kw))):
                 t = timed(fn, a.repeats)
-                print(json.dumps(dict(bench="als_foldin", weighted=weighted, call=name, D=D, rows=a.recall_rows, **kw,
+                print(json.dumps(dict(bench="als_foldin", weighted=weighted, solver=solver, call=name, D=D, rows=a.recall_rows, **kw,
                                       rows_per_s_median=a.recall_rows / (t["ms_median"] * 1e-3), **t)), flush=True)
             v.close()
             h.close()
