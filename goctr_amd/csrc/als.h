@@ -45,8 +45,9 @@ namespace goctr {
 // ---- the conjugate-gradient solver (als_cg.hip), what als.hip's two dispatch points call.  All queue on `st` / the engine stream
 // and wait for nothing
 struct FoldinArgs;                               // als_kernels.h
-// G = F^T F over F's n rows for D above the Cholesky kernels' 64, by their tile rule
-int als_gram_wide(const double* F, int64_t n, int D, double* G);
+// G = F^T F over F's n rows for D above the Cholesky kernels' 64, by their tile rule.  *max_parts_out (may be null) = the tiles of 256
+// rows that one batch of the parts scratch holds at this D
+int als_gram_wide(const double* F, int64_t n, int D, double* G, int64_t* max_parts_out = nullptr);
 // the row launches of one half-step of a CG handle: this side's factors from the other side's and their Gram matrix
 int als_cg_rows(const goctr_als* a, const goctr_walkgraph* g, int side);
 // the fold-in launch of a CG handle over nq request rows

@@ -533,12 +533,13 @@ int cg_allow_lds() {
 
 namespace goctr {
 
-int als_gram_wide(const double* F, int64_t n, int D, double* G) {
+int als_gram_wide(const double* F, int64_t n, int D, double* G, int64_t* max_parts_out) {
   hipStream_t st = engine().stream;
   CgScratch& ws = engine_scratch<CgScratch>();
   const int64_t tiles = cdiv(n, ALS_SEG);
   const size_t psz = (size_t)D * D;
   const int64_t max_parts = std::max<int64_t>(1, (int64_t)(CG_PARTS_BYTES / (psz * sizeof(double))));
+  if (max_parts_out) *max_parts_out = max_parts;
   const int T = cg_tiles(D), rounds = (int)cdiv(T * (T + 1) / 2, ALS_WAVES * CG_GPAIRS);
   if (ws.parts.ensure((size_t)std::min<int64_t>(tiles, max_parts) * psz, false)) return -1;
   for (int64_t t0 = 0; t0 < tiles; t0 += max_parts) {

@@ -3,7 +3,8 @@
 // against libgoctr_hip.so for the engine, DevBuf and the error text); the goctr_amd package never loads it and include/goctr.h does
 // not declare it: only tests do, through ctypes, after goctr_init -- tests/test_gpu_primitives.py for the header entries, and
 // tests/test_gpu_arena_poison.py (with its child processes, tests/arena_child.py) for the goctr_selftest_arena_* entries at the end
-// of this file, which write a pattern over the arena's free blocks, report its state and replay allocation traces.
+// of this file, which write a pattern over the arena's free blocks, report its state and replay allocation traces.  One entry runs
+// a library function no C-ABI call reaches alone: goctr_selftest_als_gram_wide (tests/test_gpu_als_gram_wide.py).
 //
 // The headers keep their code in anonymous namespaces or as inline device functions, so what runs here is the header text AS
 // INSTANTIATED IN THIS TRANSLATION UNIT (with the library's compile flags), not the copies inlined into the users' kernels: a
@@ -22,6 +23,7 @@
 #include "radix_sort.h"
 #include "lds_lists.h"
 #include "metrics_reduce.h"
+#include "als.h"
 
 using namespace goctr;
 
@@ -568,6 +570,27 @@ int goctr_selftest_fold(int kind, const void* vals, long long n, int G, void* pa
   if (kind == 0) return fold_run<Sums<float, 1>, float, 1>(vals, n, G, parts_out, out);
   if (kind == 1) return fold_run<Sums<double, 2>, double, 2>(vals, n, G, parts_out, out);
   return fold_run<SelfBest, u64, 2>(vals, n, G, parts_out, out);
+}
+
+// ------------------------------------------------------------------------------------------------------------ the wide Gram
+// goctr::als_gram_wide (als_cg.hip: the library's own copy, not header text): G_out [D, D] = F^T F over F [n, D], D in 65 .. 256.
+// G's device buffer holds 0xff bytes before the call, so an element the call does not write, or a sum that starts from what was
+// there, comes back as a NaN.  *max_parts_out = the tiles of 256 rows a batch of the parts scratch holds at this D: n above
+// 256 * max_parts takes a second batch.  The parts scratch is the engine's and stays across calls
+constexpr long long GW_MAX_N = 1ll << 17;
+
+int goctr_selftest_als_gram_wide(const double* F, long long n, int D, double* G_out, long long* max_parts_out) {
+  GOCTR_ENTER();
+  GOCTR_CHECK(n >= 1 && n <= GW_MAX_N, "goctr_selftest_als_gram_wide: n = %lld is outside [1, %lld]", n, GW_MAX_N);
+  GOCTR_CHECK(D >= 65 && D <= 256, "goctr_selftest_als_gram_wide: D = %d is outside [65, 256]", D);
+  GOCTR_CHECK(F && G_out && max_parts_out, "goctr_selftest_als_gram_wide: null array");
+  DevBuf<double> d_f, d_g;
+  StreamDrain drain{engine().stream};
+  if (stage(d_f, F, (size_t)n * D) || fill_bytes(d_g, (size_t)D * D, 0xff)) return -1;
+  int64_t max_parts = 0;
+  if (als_gram_wide(d_f.p, (int64_t)n, D, d_g.p, &max_parts)) return -1;
+  *max_parts_out = (long long)max_parts;
+  return d_g.download(G_out, (size_t)D * D);
 }
 
 // --------------------------------------------------------------------------------------------------------------- the arena

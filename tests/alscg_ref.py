@@ -47,14 +47,16 @@ def _edges(F, nbrs, kap, v, res, order):
     return acc
 
 
-def cg_row(F, G, nbrs, r, alpha, lam, x0, steps, order="csr", dtype=np.float64):
-    """one row: ``r`` the integer edge weights (None: unweighted), F and G already in ``dtype``"""
+def cg_row(F, G, nbrs, r, alpha, lam, x0, steps, order="csr", dtype=np.float64, trace=False):
+    """one row: ``r`` the integer edge weights (None: unweighted), F and G already in ``dtype``.  ``trace``: (x, the steps taken --
+    0: rs was below 2^-100 behind the residual pass, ``steps``: the row never stopped early --, the last rs)"""
     nbrs = list(nbrs)
     rho = np.ones(len(nbrs), dtype) if r is None else np.asarray(r, np.uint32).astype(dtype) * dtype(2.0 ** -16)
     kap, lam = dtype(alpha) * rho, dtype(lam)
     x = np.array(x0, dtype)
     res = _edges(F, nbrs, kap, x, True, order) - (_gv(G, x, order) + lam * x)
     p, rs = res.copy(), _dot(res, res, order)
+    taken = 0
     for _ in range(steps):
         if rs < TINY:
             break
@@ -63,7 +65,8 @@ def cg_row(F, G, nbrs, r, alpha, lam, x0, steps, order="csr", dtype=np.float64):
         x, res = x + a * p, res - a * q
         rs2 = _dot(res, res, order)
         p, rs = res + (rs2 / rs) * p, rs2
-    return x
+        taken += 1
+    return (x, taken, rs) if trace else x
 
 
 def solve_rows(F, off, edges, wts, alpha, lam, X0, steps, order="csr", dtype=np.float64):

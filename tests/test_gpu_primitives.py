@@ -512,7 +512,11 @@ def test_bad_arguments_are_refused(H):
     z32, z64, i32 = np.zeros(4096, U32), np.zeros(4096, U64), np.zeros(4096, I32)
     L = H.lib
     t = C.c_ulonglong(0)
+    f64, parts = np.zeros(257 * 257), LL(0)
     bad = [
+        L.goctr_selftest_als_gram_wide(_p(f64), LL(0), INT(72), _p(f64), C.byref(parts)),                                   # n < 1
+        L.goctr_selftest_als_gram_wide(_p(f64), LL(1), INT(64), _p(f64), C.byref(parts)),                                   # D below 65
+        L.goctr_selftest_als_gram_wide(_p(f64), LL(1), INT(257), _p(f64), C.byref(parts)),                                  # D above 256
         L.goctr_selftest_scan(INT(0), INT(0), C.c_uint(0), INT(0), _p(z32), LL(-1), _p(z32), C.byref(t)),
         L.goctr_selftest_scan(INT(0), INT(0), C.c_uint(0), INT(1), _p(np.full(8, 9, U32)), LL(8), _p(z32), C.byref(t)),   # a compaction past n
         L.goctr_selftest_block_scan(INT(3), _p(z32), _p(z32), _p(z32), _p(z32)),
@@ -527,3 +531,6 @@ def test_bad_arguments_are_refused(H):
     ]
     assert bad == [-1] * len(bad)
     assert b"goctr_selftest_fold" in H.capi.load().goctr_last_error()
+    for n, D in ((0, 72), (1, 64), (1, 257)):
+        assert L.goctr_selftest_als_gram_wide(_p(f64), LL(n), INT(D), _p(f64), C.byref(parts)) == -1
+        assert b"goctr_selftest_als_gram_wide" in H.capi.load().goctr_last_error() and parts.value == 0
