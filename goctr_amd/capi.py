@@ -265,6 +265,11 @@ class AlsCgCfg(C.Structure):
     _fields_ = [("als", AlsCfg), ("cg_steps", C.c_int32), ("foldin_steps", C.c_int32), ("reserved", C.c_int64)]
 
 
+class AlsDotCfg(C.Structure):
+    """goctr_als_dot_cfg (include/goctr.h)"""
+    _fields_ = [("source", C.c_int32), ("reserved", C.c_int32), ("min_score", C.c_double), ("chunk_items", C.c_int64)]
+
+
 class EaseCfg(C.Structure):
     """goctr_ease_cfg (include/goctr.h)"""
     _fields_ = [("n_nbr", C.c_int32), ("max_items", C.c_int32), ("min_degree", C.c_int32), ("scale", C.c_int32),
@@ -418,6 +423,7 @@ SYMBOLS = [
     "goctr_als_recall", "goctr_recommend_als", "goctr_recommend_blend_als",
     "goctr_als_create_weighted", "goctr_als_weights", "goctr_als_foldin_weights",
     "goctr_als_cg_cfg_default", "goctr_als_create_cg", "goctr_als_solver",
+    "goctr_als_dot_cfg_default", "goctr_als_recall_dot", "goctr_recommend_als_dot",
     "goctr_ease_cfg_default", "goctr_ease_block_size", "goctr_itemcf_build_ease",
     "goctr_uservec_cfg_default", "goctr_uservec_recall", "goctr_recommend_uservec", "goctr_recommend_blend_uservec",
     "goctr_uservec_multi_cfg_default", "goctr_uservec_interests", "goctr_uservec_recall_multi", "goctr_recommend_uservec_multi",
@@ -459,7 +465,7 @@ def load() -> C.CDLL:
                      "goctr_calib_cfg_default", "goctr_calibrator_destroy", "goctr_boot_cfg_default",
                      "goctr_walkgraph_cfg_default", "goctr_walk_cfg_default", "goctr_walkgraph_destroy",
                      "goctr_edgeweight_cfg_default",
-                     "goctr_als_cfg_default", "goctr_als_cg_cfg_default", "goctr_als_destroy", "goctr_ease_cfg_default", "goctr_fuse_cfg_default",
+                     "goctr_als_cfg_default", "goctr_als_cg_cfg_default", "goctr_als_dot_cfg_default", "goctr_als_destroy", "goctr_ease_cfg_default", "goctr_fuse_cfg_default",
                      "goctr_itemattr_destroy", "goctr_usercf_cfg_default", "goctr_usercf_recall_cfg_default", "goctr_usercf_destroy",
                      "goctr_walksampler_cfg_default", "goctr_walkp_cfg_default", "goctr_walksampler_destroy"):
             getattr(_lib, name).restype = None
@@ -664,6 +670,12 @@ def load() -> C.CDLL:
         _lib.goctr_recommend_als.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32,
                                              C.POINTER(RecallCfg), _uv, C.c_int32, C.c_int64, _i32, _f32, _i32, _i32, _i32, _i64,
                                              _i32, _u32, _f32, _i64]
+        _ad = C.POINTER(AlsDotCfg)
+        _lib.goctr_als_dot_cfg_default.argtypes = [_ad]
+        _lib.goctr_als_recall_dot.argtypes = [C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, C.POINTER(RecallCfg), _ad, _i32, _u32, _i32,
+                                              _i32, _i32, _f64]
+        _lib.goctr_recommend_als_dot.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32, C.POINTER(RecallCfg),
+                                                 _ad, C.c_int32, C.c_int64, _i32, _f32, _i32, _i32, _i32, _i64, _i32, _u32, _f32, _i64]
         _lib.goctr_recommend_blend_als.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32,
                                                    C.c_void_p, C.c_void_p, _uv, C.c_int32, C.POINTER(RecallCfg), C.c_int32, C.c_void_p,
                                                    _mmr, C.c_int32, C.c_int64, _i32, _f32, _i32, _u8, _i32, _i32, _i64, _i32, _u32,
@@ -841,6 +853,8 @@ default_usercf_recall_cfg = _default(UsercfRecallCfg, "goctr_usercf_recall_cfg_d
 default_als_cfg = _default(AlsCfg, "goctr_als_cfg_default")
 default_als_cg_cfg = _default(AlsCgCfg, "goctr_als_cg_cfg_default")
 ALS_CHOLESKY, ALS_CG = 0, 1                 # goctr_als_solver's solvers
+default_als_dot_cfg = _default(AlsDotCfg, "goctr_als_dot_cfg_default")
+ALS_X_FOLDIN, ALS_X_STORED = 0, 1           # goctr_als_dot_cfg.source
 default_fuse_cfg = _default(FuseCfg, "goctr_fuse_cfg_default")
 ALS_USERS, ALS_ITEMS = 0, 1                 # goctr_als_step's sides
 default_ease_cfg = _default(EaseCfg, "goctr_ease_cfg_default")

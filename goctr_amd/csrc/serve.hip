@@ -26,6 +26,7 @@
 #include "usercf.h"
 #include "walk.h"
 #include "als.h"
+#include "als_dot.h"
 
 // ------------------------------------------------------------------ serving: recommend.BatchPredict / Rank / Predict
 // recommend/rcmd.go:248-337: sample keys -> GetSampleVector rows -> PredictAbstract.Predict -> scores, called from concurrent
@@ -802,6 +803,21 @@ int goctr_recommend_als(goctr_model* m, goctr_recsys* r, goctr_als* als, goctr_i
                         out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed};
   if (als_check_recommend(who, als, v, ucfg, a, r->n_users, r->n_items)) return -1;
   return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return als_recommend_run(sc, als, v, *ucfg, a); });
+}
+
+// goctr_recommend_itemcf with the ALS dot-product recall (als_dot.hip) as the driver's recall stage
+int goctr_recommend_als_dot(goctr_model* m, goctr_recsys* r, goctr_als* als, const int32_t* users, const int64_t* ts, int64_t n_req,
+                            const int32_t* targets, const goctr_recall_cfg* recall_cfg, const goctr_als_dot_cfg* dcfg, int32_t k,
+                            int64_t pass_rows, int32_t* out_items, float* out_scores, int32_t* out_count, int32_t* out_cand_count,
+                            int32_t* out_target_pos, int64_t* out_target_rank, int32_t* cand_items, uint32_t* cand_w,
+                            float* cand_scores, int64_t* n_failed) {
+  EngineScope on(handle_engine(m));
+  const char* who = "goctr_recommend_als_dot";
+  if (recommend_enter(who, m && r && als && recall_cfg && dcfg, m, r, {handle_engine(als)})) return -1;
+  const ItemcfRecArgs a{users, ts, n_req, targets, *recall_cfg, k, pass_rows, out_items, out_scores, out_count, out_cand_count,
+                        out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed};
+  if (alsdot_check_recommend(who, als, dcfg, a, r->n_users, r->n_items)) return -1;
+  return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return alsdot_recommend_run(sc, als, *dcfg, a); });
 }
 
 // goctr_recommend_blend / _blend_mmr with the ALS fold-in recall writing part X's list on the device

@@ -1278,6 +1278,23 @@ class ALS {
     check(goctr_als_foldin(h_, cache, users.data(), ts.empty() ? nullptr : ts.data(), (int64_t)users.size(), history, x.data(), nullptr,
                            n_used.data()));
   }
+  static goctr_als_dot_cfg DefaultDotCfg() { goctr_als_dot_cfg c; goctr_als_dot_cfg_default(&c); return c; }
+  // the float32 score behind a weight of RecallDot (or a cand_w of goctr_recommend_als_dot): the inverse of the header's image
+  static float DotScore(uint32_t w) {
+    const uint32_t b = (w & 0x80000000u) ? (w ^ 0x80000000u) : ~w;
+    float f;
+    std::memcpy(&f, &b, sizeof f);
+    return f;
+  }
+  // goctr_als_recall_dot: every row's n_cand best items by the raw dot product x . y_j against the handle's own Y, items / w
+  // [nq, n_cand] (padding -1 / 0) and count [nq]; dcfg.source picks the folded-in vector or the stored row X[user]
+  void RecallDot(goctr_ubcache* cache, const std::vector<int32_t>& users, const std::vector<int64_t>& ts, const goctr_recall_cfg& rcfg,
+                 const goctr_als_dot_cfg& dcfg, std::vector<int32_t>& items, std::vector<uint32_t>& w, std::vector<int32_t>& count) const {
+    if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("ALS::RecallDot: one timestamp per user");
+    items.resize(users.size() * (size_t)rcfg.n_cand); w.resize(items.size()); count.resize(users.size());
+    check(goctr_als_recall_dot(h_, cache, users.data(), ts.empty() ? nullptr : ts.data(), (int64_t)users.size(), &rcfg, &dcfg,
+                               items.data(), w.data(), count.data(), nullptr, nullptr, nullptr));
+  }
 
  private:
   ALS() = default;                                             // (CreateWeighted's)
@@ -1302,6 +1319,25 @@ inline TopN RecommendALSBatch(model::CtrNet& net, RecSys& rs, const ALS& als, co
                             targets.empty() ? nullptr : targets.data(), &rcfg, &ucfg, n, pass_rows, items.data(), scores.data(),
                             count.data(), nullptr, nullptr, targets.empty() ? nullptr : out.target_rank.data(), nullptr, nullptr,
                             nullptr, &out.n_failed));
+  out.lists = detail::gather_lists(items, scores, count, n);
+  return out;
+}
+
+// RecommendALSBatch ranked by ALS's own score (goctr_recommend_als_dot): the raw dot product against the handle's Y, no item vectors
+inline TopN RecommendAlsDot(model::CtrNet& net, RecSys& rs, const ALS& als, const std::vector<int32_t>& users, int n = 10,
+                            const std::vector<int64_t>& ts = {}, const goctr_recall_cfg& rcfg = ItemCF::DefaultRecallCfg(),
+                            const goctr_als_dot_cfg& dcfg = ALS::DefaultDotCfg(), const std::vector<int32_t>& targets = {},
+                            int64_t pass_rows = 0) {
+  const int64_t nq = (int64_t)users.size();
+  detail::check_request("RecommendAlsDot", users.size(), ts.size(), targets.size(), n);
+  std::vector<int32_t> items((size_t)nq * n), count((size_t)nq);
+  std::vector<float> scores((size_t)nq * n);
+  TopN out;
+  if (!targets.empty()) out.target_rank.resize((size_t)nq);
+  check(goctr_recommend_als_dot(net.Vm(), rs.handle(), als.handle(), users.data(), ts.empty() ? nullptr : ts.data(), nq,
+                                targets.empty() ? nullptr : targets.data(), &rcfg, &dcfg, n, pass_rows, items.data(), scores.data(),
+                                count.data(), nullptr, nullptr, targets.empty() ? nullptr : out.target_rank.data(), nullptr, nullptr,
+                                nullptr, &out.n_failed));
   out.lists = detail::gather_lists(items, scores, count, n);
   return out;
 }

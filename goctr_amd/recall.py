@@ -605,6 +605,35 @@ def make_als_cfg(**kw) -> capi.AlsCfg:
     return capi.default_als_cfg(**{k: float(v) if k in ("alpha", "lambda_") else _as_int(k, v) for k, v in kw.items()})
 
 
+ALS_SOURCE = {"foldin": capi.ALS_X_FOLDIN, "stored": capi.ALS_X_STORED}
+
+
+def make_als_dot_cfg(source="foldin", min_score=None, chunk_items=0) -> capi.AlsDotCfg:
+    """goctr_als_dot_cfg from keywords: ``source`` "foldin" / "stored" (or capi.ALS_X_*), ``min_score`` (a number that is not NaN;
+    None: the library's -inf), ``chunk_items`` (0, or 64 .. 2^22).  A value outside these raises here: it never reaches the library"""
+    if isinstance(source, str):
+        if source not in ALS_SOURCE:
+            raise ValueError(f"source = {source!r} is none of {sorted(ALS_SOURCE)}")
+        source = ALS_SOURCE[source]
+    if _as_int("source", source) not in ALS_SOURCE.values():
+        raise ValueError(f"source = {source!r} is no capi.ALS_X_* value")
+    kw = dict(source=int(source), chunk_items=_as_int("chunk_items", chunk_items))
+    if kw["chunk_items"] != 0 and not 64 <= kw["chunk_items"] <= 1 << 22:
+        raise ValueError(f"chunk_items = {chunk_items!r} is neither 0 nor in 64 .. 2^22")
+    if min_score is not None:
+        kw["min_score"] = float(min_score)
+        if kw["min_score"] != kw["min_score"]:
+            raise ValueError("min_score is not a number")
+    return capi.default_als_dot_cfg(**kw)
+
+
+def als_dot_scores(w) -> np.ndarray:
+    """the float32 scores behind goctr_als_recall_dot's weights: the inverse of the header's image (w = b ^ 0x80000000 for a clear
+    sign bit of b, else ~b), exact.  The padding's w = 0 decodes to NaN"""
+    w = np.ascontiguousarray(w, np.uint32)
+    return np.where(w >> 31 != 0, w ^ np.uint32(0x80000000), ~w).astype(np.uint32).view(np.float32)
+
+
 class ALS(_Handle):
     """goctr_als: implicit-feedback ALS factors X [n_users, D] and Y [n_items, D] resident in HBM, trained over a WalkGraph's two
     CSRs (tests/als_ref.py is the host restatement).  The handle keeps the graph it was created over alive and passes it to every
@@ -737,6 +766,22 @@ class ALS(_Handle):
             out["p"], out["x"] = _unwritten((users.size, self.D), np.int16), np.full((users.size, self.D), np.nan, np.float64)
         capi.check(capi.load().goctr_als_recall(self._h, vectors._h, _cache_handle(ubc), *_request_args(users, ts), C.byref(cfg),
                                                 C.byref(ucfg), *_recall_args(out, targets), _ptr(out.get("p")), _ptr(out.get("x"))))
+        return out
+
+    def recall_dot(self, ubc, users, ts=None, targets=None, cfg: capi.RecallCfg | None = None, source="foldin", min_score=None,
+                   chunk_items=0, dcfg: capi.AlsDotCfg | None = None, **kw) -> dict:
+        """goctr_als_recall_dot over DENSE user rows of ``ubc``'s image: the catalogue ranked by the raw dot product x . y_j in
+        float64 against the handle's own Y -- no item vectors.  ``source`` "foldin": the request vector is ``foldin``'s;
+        "stored": the trained X[user].  ``kw``: goctr_recall_cfg fields.  dict(items, w, scores float32 [nq, n_cand] (w decoded,
+        NaN in the padding), count, target_pos when targets are given, x float64 [nq, D])"""
+        dcfg = dcfg if dcfg is not None else make_als_dot_cfg(source, min_score, chunk_items)
+        cfg = _cfg_or_kw(cfg, kw, make_recall_cfg)
+        users, ts, targets = request_columns(users, ts, targets)
+        out = _recall_buffers(users.size, cfg.n_cand, targets)
+        out["x"] = np.full((users.size, self.D), np.nan, np.float64)
+        capi.check(capi.load().goctr_als_recall_dot(self._h, _cache_handle(ubc), *_request_args(users, ts), C.byref(cfg), C.byref(dcfg),
+                                                    *_recall_args(out, targets), _ptr(out["x"])))
+        out["scores"] = als_dot_scores(out["w"])
         return out
 
 

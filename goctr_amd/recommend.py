@@ -29,7 +29,7 @@ import numpy as np
 from . import capi, metrics, sampling
 from .recall import (ALS, EXCLUDE, _USERCF_RECALL_FIELDS, _USERVEC_FIELDS, _USERVEC_IVF_FIELDS, _USERVEC_MULTI_FIELDS, _WALK_FIELDS, ItemCF,
                      ItemVectors, Popular, UserCF, WalkGraph, make_usercf_recall_cfg, _as_int, _cfg_or_kw, _ptr, _request_args, _split_kw, _unwritten, extra_columns, make_mmr_cfg,
-                     make_recall_cfg, make_uservec_cfg, make_uservec_ivf_cfg, make_uservec_multi_cfg, make_walk_cfg, merge,
+                     make_als_dot_cfg, make_recall_cfg, make_uservec_cfg, make_uservec_ivf_cfg, make_uservec_multi_cfg, make_walk_cfg, merge,
                      WalkSampler, _WALKP_FIELDS, check_walkp_cfg, make_walkp_cfg,
                      request_columns, Channel, _FUSE_FIELDS, check_fuse_cfg, fuse_channels, make_fuse_cfg, ItemAttrs, item_filter, make_pred)
 
@@ -554,6 +554,7 @@ _OUTPUTS = {
     "goctr_recommend_usercf": _RANKED,
     "goctr_recommend_blend_walk": _BLENDED + ("obj", "pen", "target_place"),
     "goctr_recommend_als": _RANKED,
+    "goctr_recommend_als_dot": _RANKED,
     "goctr_recommend_blend_als": _BLENDED + ("obj", "pen", "target_place"),
     "goctr_recommend_fused": _BLENDED + ("obj", "pen", "target_place"),
     "goctr_recommend_fused_filtered": _BLENDED + ("obj", "pen", "target_place"),
@@ -761,6 +762,20 @@ def als(model: Predictor, factors, users, ts=None, targets=None, k=10, pass_rows
     head = (*_request_head(model, factors, _als_vectors(factors, als_vectors)), *_request_args(users, ts), capi.ptr(targets, C.c_int32),
             C.byref(cfg), C.byref(ucfg), *_k_pass(k, pass_rows))
     return _ranked_call("goctr_recommend_als", head, users.size, k, cfg.n_cand, targets, validate)
+
+
+def als_dot(model: Predictor, factors, users, ts=None, targets=None, k=10, pass_rows=0, validate=False, recall_cfg=None, dcfg=None,
+            source="foldin", min_score=None, chunk_items=0, **recall_kw):
+    """goctr_recommend_als_dot over DENSE indices: ``als`` with the raw dot-product scan of ``factors``' own Y as the recall stage
+    (recall.ALS.recall_dot) -- no item vectors; the same dict, cand_w being the score's weight image (recall.als_dot_scores decodes
+    it).  ``source``, ``min_score``, ``chunk_items``: recall.make_als_dot_cfg's; ``recall_kw``: goctr_recall_cfg fields.  What
+    RecommendALSDot / RecommendALSDotBatch / EvaluateLeaveOneOutALSDot call."""
+    dcfg = dcfg if dcfg is not None else make_als_dot_cfg(source, min_score, chunk_items)
+    cfg = _cfg_or_kw(recall_cfg, recall_kw, make_recall_cfg, "recall_cfg")
+    users, ts, targets = request_columns(users, ts, targets)
+    head = (*_request_head(model, factors), *_request_args(users, ts), capi.ptr(targets, C.c_int32), C.byref(cfg), C.byref(dcfg),
+            *_k_pass(k, pass_rows))
+    return _ranked_call("goctr_recommend_als_dot", head, users.size, k, cfg.n_cand, targets, validate)
 
 
 def blend_als(model: Predictor, icf, pop, factors, users, ts=None, targets=None, n_als=64, quota_pop=0, k=10, vectors=None, pool=64,
@@ -1041,6 +1056,20 @@ def RecommendALS(model: Predictor, factors, userId: int, n=10, now=None, **recal
     whose factors are closest by cosine are scored by the model and the ``n`` best come back.  An appended behaviour moves the vector
     without a refit."""
     return RecommendALSBatch(model, factors, [userId], n, now, **recall_kw)[0]
+
+
+def RecommendALSDotBatch(model: Predictor, factors, userIds, n=10, now=None, **recall_kw):
+    """RecommendALSDot for several users in one device call: [[ItemScore]] in the order of userIds.  ``now``: one timestamp for all,
+    or one per user.  A user without a vector (no history to fold in, or an all-zero stored row) gets an empty list."""
+    users, ts = _request_rows(model, userIds, now)
+    return _serve(model, users.size, lambda: als_dot(model, factors, users, ts, None, n, **recall_kw))
+
+
+def RecommendALSDot(model: Predictor, factors, userId: int, n=10, now=None, **recall_kw):
+    """EXTENSION -- RecommendALS ranked by ALS's own score: the ``n_cand`` items with the largest dot product x . y_i in float64
+    (the item norm, mostly popularity, stays in) are scored by the model and the ``n`` best come back.  ``source="stored"`` takes the
+    trained row of the user in the place of the folded-in vector: the classic "recommend for user u"."""
+    return RecommendALSDotBatch(model, factors, [userId], n, now, **recall_kw)[0]
 
 
 def RecommendBlendALSBatch(model: Predictor, icf, pop, factors, userIds, n=10, now=None, n_als=64, quota_pop=0, vectors=None, pool=64,
@@ -1525,6 +1554,34 @@ def EvaluateLeaveOneOutALS(model: Predictor, factors=None, k=10, sample_kw=None,
         factors = own = BuildALS(model.recSys, graph_kw=gkw, weight_kw=weight_kw, **(als_kw or {}))
     try:
         r = als(model, factors, users, ts, targets, k, pass_rows, recall_cfg=cfg, ucfg=ucfg)
+    finally:
+        if own is not None:
+            own.vectors.close()
+            own.close()
+            own.graph.close()
+    out = _loo_figures(r, targets, model.recSys.item_table.shape[0], k, cfg.n_cand)
+    if details:
+        out.update(_details(r, users, targets, ts))
+    return out
+
+
+def EvaluateLeaveOneOutALSDot(model: Predictor, factors=None, k=10, sample_kw=None, details=False, pass_rows=0, graph_kw=None,
+                              als_kw=None, weight_kw=None, **recall_kw):
+    """EvaluateLeaveOneOutALS with the raw dot-product recall as the recall stage (goctr_recommend_als_dot): the same window, the
+    same figures.  ``source="stored"`` is refused here: a stored row was trained on the held-out item."""
+    dcfg = make_als_dot_cfg(**{key: recall_kw.pop(key) for key in ("source", "min_score", "chunk_items") if key in recall_kw})
+    if dcfg.source != capi.ALS_X_FOLDIN:
+        raise ValueError("a leave-one-out evaluation folds the request vector in: a stored row has seen the held-out item")
+    users, targets, ts = _held_out_rows(model, sample_kw)
+    recall_kw.setdefault("exclude", "before")
+    cfg = make_recall_cfg(**recall_kw)
+    own = None
+    if factors is None:
+        gkw = dict(graph_kw or {})
+        gkw.setdefault("ts_hi", int((sample_kw or {})["ts_lo"]) - 1 if "ts_lo" in (sample_kw or {}) else int(ts.min()))
+        factors = own = BuildALS(model.recSys, graph_kw=gkw, weight_kw=weight_kw, **(als_kw or {}))
+    try:
+        r = als_dot(model, factors, users, ts, targets, k, pass_rows, recall_cfg=cfg, dcfg=dcfg)
     finally:
         if own is not None:
             own.vectors.close()

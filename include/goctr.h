@@ -1380,6 +1380,51 @@ int goctr_recommend_blend_als(goctr_model* m, goctr_recsys* r, goctr_itemcf* icf
                               int32_t* cand_items, uint32_t* cand_w, float* cand_scores, uint8_t* cand_src, int64_t* n_failed,
                               int32_t* out_obj, uint32_t* out_pen, int32_t* out_target_place);
 
+/* ALS recall by the raw dot product: goctr_als_recall_dot ranks the whole catalogue by s(q,j) = x_q . y_j, the score the factors
+ * were trained to give, over the handle's Y as it stands (tests/alsdot_ref.py is the host restatement).  No goctr_itemvec is
+ * involved and nothing is quantised: the item norm stays in the score.
+ *   request vector source = GOCTR_ALS_X_FOLDIN: exactly goctr_als_foldin's out_x for the row (the same launch writes the same bytes;
+ *                  a Cholesky, weighted or CG handle).  GOCTR_ALS_X_STORED: the handle's X[users[q]], the trained row.  Under
+ *                  either source history, seen and ts come from the cache as in goctr_als_recall.  A row whose x is all zeros
+ *                  has no vector and returns count 0
+ *   score          s(q,j) = sum_d x_d y_jd in float64, every product and sum rounded once
+ *   summation      the order of the sum is the implementation's, FIXED, and depends on D alone.  No output byte depends on
+ *                  chunk_items, on how request rows are grouped or tiled, or on thread arrival order; two calls give the same bytes
+ *   weight         f = s rounded to float32 (to nearest even), -0 taken as +0; b = the bits of f; w = b ^ 0x80000000 when the sign
+ *                  bit of b is clear, else ~b: a uint32 that grows with the score and is never 0 for a finite or infinite f.
+ *                  out_w carries it; the inverse map recovers f exactly.  An item whose score is NaN is no candidate
+ *   candidates     every item j with w >= the image of (float)min_score, but the seen items (goctr_itemcf_recall's rule under
+ *                  cfg->exclude, the target exemption included) and the items whose factor row is all zeros (items without edges:
+ *                  goctr_als_create's invalid rows).  Negative scores are candidates
+ *   order          w descending, then item ascending; the first n_cand are kept; padding -1 / 0
+ *   refused        goctr_als_recall's refusals where they apply; a source outside the two values; a NaN min_score; reserved != 0;
+ *                  chunk_items out of range; (STORED) a user >= the handle's n_users.  A refused call touches nothing
+ * out_x [n_req,D] (may be NULL): the request vectors as scanned. */
+#define GOCTR_ALS_X_FOLDIN 0
+#define GOCTR_ALS_X_STORED 1
+typedef struct {
+  int32_t source;       /* GOCTR_ALS_X_FOLDIN 0 | GOCTR_ALS_X_STORED 1          default FOLDIN */
+  int32_t reserved;     /* must be 0 */
+  double  min_score;    /* not NaN; a candidate needs f >= (float)min_score     default -inf   */
+  int64_t chunk_items;  /* 0 = the implementation's choice, else 64 .. 2^22     default 0      */
+} goctr_als_dot_cfg;
+void goctr_als_dot_cfg_default(goctr_als_dot_cfg* c);
+int  goctr_als_recall_dot(goctr_als* a, goctr_ubcache* c, const int32_t* users, const int64_t* ts /* NULL = 0 */, int64_t n_req,
+                          const goctr_recall_cfg* cfg, const goctr_als_dot_cfg* dcfg,
+                          int32_t* out_items /*[n_req,n_cand]*/, uint32_t* out_w /*[n_req,n_cand]*/, int32_t* out_count /*[n_req]*/,
+                          const int32_t* targets /*[n_req] or NULL*/, int32_t* out_target_pos /*[n_req] or NULL*/,
+                          double* out_x /*[n_req,D] or NULL*/);
+
+/* goctr_recommend_als_dot: goctr_recommend_als with goctr_als_recall_dot as its recall stage; cand_w is the weight defined above.
+ *   refused        goctr_recommend_itemcf's refusals, the dcfg refusals, the handle not matching the recsys's n_items */
+int goctr_recommend_als_dot(goctr_model* m, goctr_recsys* r, goctr_als* als,
+                            const int32_t* users, const int64_t* ts /* NULL = 0 */, int64_t n_req,
+                            const int32_t* targets /* [n_req] or NULL */, const goctr_recall_cfg* recall_cfg,
+                            const goctr_als_dot_cfg* dcfg, int32_t k, int64_t pass_rows,
+                            int32_t* out_items /* [n_req,k] */, float* out_scores /* [n_req,k] */, int32_t* out_count,
+                            int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank,
+                            int32_t* cand_items, uint32_t* cand_w, float* cand_scores, int64_t* n_failed);
+
 /* ---- EASE item neighbours: a learned item-item model as a fourth source of goctr_itemcf handles (Steck 2019, "Embarrassingly
  * Shallow Autoencoders"; no reference counterpart).  The three sources above set a pair's weight by a local rule; EASE learns all
  * weights jointly, so a pair that co-occurs only because both items co-occur with a hub is not weighted as if the link were direct.
