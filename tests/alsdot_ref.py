@@ -2,7 +2,8 @@
 the weight image and its inverse, the candidates, the order, the cut.  The scores are the caller's (an exact integer product, or a
 longdouble reference with its bound): the order of the device's float64 sum is its own.
   weight      f = the score rounded to float32 (nearest even), -0 taken as +0; b = the bits of f; w = b ^ 0x80000000 when the sign bit
-              of b is clear, else ~b.  Strictly increasing in f, never 0 for a finite or infinite f
+              of b is clear, else ~b.  Strictly increasing in f, never 0 for a finite or infinite f.  A NaN score (inf - inf, 0 * inf)
+              has w = 0 and is no candidate under any min_score: -inf's image is 0x007fffff
   candidates  every item j with w >= image(float32(min_score)), but the seen items (topn_ref.seen_items under the mode; the row's
               target is exempt), the items whose factor row is all zeros, and every item of a row whose x is all zeros
   order       w descending, then item ascending; the first n_cand; padding -1 / 0"""
@@ -12,10 +13,11 @@ import topn_ref as T
 
 
 def image(f):
-    """uint32 weights of float32 scores (any shape)"""
+    """uint32 weights of float32 scores (any shape); a NaN of either sign has the weight 0, below the image of every min_score"""
     b = np.ascontiguousarray(f, np.float32).view(np.uint32).copy()
     b[b == 0x80000000] = 0
-    return np.where(b >> 31 != 0, ~b, b ^ np.uint32(0x80000000)).astype(np.uint32)
+    w = np.where(b >> 31 != 0, ~b, b ^ np.uint32(0x80000000)).astype(np.uint32)
+    return np.where((b & np.uint32(0x7fffffff)) > 0x7f800000, np.uint32(0), w).astype(np.uint32)
 
 
 def inverse(w):
@@ -53,7 +55,8 @@ def select(w, ok, targets, n_cand):
 
 def recall(S, x, Y, seqs, users, ts=None, targets=None, n_cand=256, exclude=T.DROP_ALL_SEEN, min_score=-np.inf):
     """the whole rule over scores S [nq, n_items] (rounded to float32 here) of the request vectors x against the factors Y"""
-    w = image(np.asarray(S).astype(np.float32))
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):           # (a score past FLT_MAX is +-inf, by the rule)
+        w = image(np.asarray(S).astype(np.float32))
     ok = (w >= image(np.float32(min_score))) & ~blocked(seqs, users, ts, targets, Y.shape[0], exclude)
     ok &= (Y != 0).any(axis=1)[None, :] & (x != 0).any(axis=1)[:, None]
     return select(w, ok, targets, n_cand)

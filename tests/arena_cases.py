@@ -605,6 +605,62 @@ def als_fit():
     return {"X": raw(e["X"]), "Y": raw(e["Y"]), "loss": raw(np.float64(got_loss))}
 
 
+def als_cg_fit():
+    """the narrowest fit of tests/alscg_cases.py (D = 64 on the base scene, two conjugate-gradient steps a row) within 16 e0 of the
+    restatement, e0 its own spread (tests/test_gpu_als_cg_shapes.py's check 1), and the device's own bytes: the order is fixed"""
+    import als_cases as AK
+    import als_ref as AR
+    import alscg_cases as S
+    from goctr_amd import recall as gl
+    from test_gpu_als_cg import spread
+    from test_gpu_itemcf import Cache
+    D = min(S.WIDTHS)
+    runs = S.base_fit_runs(D, False)
+    e0 = spread(runs)
+    alpha, lam = S.BASE_ALPHA_LAMBDA
+    c = Cache(AK.scene("base")[0])
+    h = gl.ALS(gl.WalkGraph(c.c, AK.N_ITEMS), D=D, n_iters=S.N_ITERS, alpha=alpha, lambda_=lam, seed=S.SEED, solver="cg",
+               cg_steps=S.CG_STEPS).fit()
+    e = h.export()
+    got_loss = h.loss()
+    errs = [AR.rel_diff(got, want) for got, want in zip((e["X"], e["Y"], np.array([got_loss])), runs[2])]
+    assert h.solver()["cg_steps"] == S.CG_STEPS and h.info()["half_steps"] == 2 * S.N_ITERS and e["X"][0].tobytes() == bytes(8 * D)
+    assert 0 < e0 < 1e-11 and all(err <= 16 * e0 for err in errs), (errs, e0)
+    return {"X": raw(e["X"]), "Y": raw(e["Y"]), "loss": raw(np.float64(got_loss))}
+
+
+def als_dot_recall():
+    """goctr_als_recall_dot with the request fragments in LDS (D = 66: four vector blocks and a tail of 8-byte loads): a stored-source
+    call of two row tiles and three chunks against tests/alsdot_ref.py, a fold-in call on a freshly fitted handle, and a stored call
+    of 5 rows whose smaller buffers land on the first call's leftovers (tests/test_gpu_als_dot_shapes.py's widths check)"""
+    import alsdot_cases as S
+    import alsdot_ref as AD
+    import test_gpu_als_dot as K
+    import topn_ref as T
+    from goctr_amd import recall as gl
+    from test_gpu_itemcf import Cache
+    D, n_items, call = S.GROUP_D, S.WIDTH_CALL["n_items"], S.WIDTH_CALL
+    c = Cache(_memo("alsdot_seqs", lambda: K.scene(n_items)[0].seqs))            # (every handle is made after the fill)
+    graph = gl.WalkGraph(c.c, n_items)
+    X, Y = K.factors(n_items, D, D + n_items)
+    users, ts, targets = K.rows(call["n_req"], n_items, call["n_req"])
+    want = _memo("alsdot_want", lambda: AD.recall(X[users].astype(np.int64) @ Y.astype(np.int64).T, X[users], Y, c.seqs, users, ts, targets,
+                                                  call["n_cand"], T.DROP_ALL_SEEN))
+    kw = dict(source="stored", chunk_items=call["chunk"], n_cand=call["n_cand"], exclude="all")
+    h = gl.ALS(graph, D=D, n_iters=1, solver="cg").set_factors(X, Y)
+    first = h.recall_dot(c.c, users, ts, targets, **kw)
+    K.same(first, want, "stored")
+    assert first["x"].tobytes() == X[users].tobytes() and (first["count"] > 0).any()
+    fitted = gl.ALS(graph, D=D, n_iters=1, solver="cg").fit()
+    every, now = np.arange(K.N_USERS, dtype=np.int32), np.full(K.N_USERS, 60, np.int64)
+    folded = fitted.recall_dot(c.c, every, now, None, n_cand=32, history=9, exclude="before")
+    assert folded["x"].tobytes() == fitted.foldin(c.c, every, now, 9)["x"].tobytes() and folded["count"][0] == 0 and (folded["count"][1:] > 0).all()
+    few = h.recall_dot(c.c, users[:5], ts[:5], targets[:5], **kw)               # 8 rows a workgroup, on the leftovers of 32
+    assert all(few[key].tobytes() == want[key][:5].tobytes() for key in K.KEYS) and few["x"].tobytes() == X[users[:5]].tobytes()
+    keys = K.KEYS + ("x",)
+    return {f"{name}/{key}": raw(out[key]) for name, out in (("stored", first), ("foldin", folded), ("few", few)) for key in keys if key in out}
+
+
 # -------------------------------------------------------------------------------------------------------------- the table
 CASES = {"recall_entries": recall_entries}
 CASES.update({f"metrics_{n}": metrics_frozen(n) for n in metric_names()})
@@ -613,7 +669,7 @@ CASES.update({f"knn_V{V}_D{D}_k{k}_Q{Q}_{route}": knn_search(V, D, k, Q, route) 
 CASES.update(knn_ignore_700=knn_ignore_700, itemcf_build=itemcf_build, swing_build=swing_build, vector_neighbours=vector_neighbours,
              ease_build=ease_build, usercf_build=usercf_build, popular_build=popular_build, weighted_graph=weighted_graph,
              ivf_index_build=ivf_index_build, item_tags_filtered_recall=item_tags_filtered_recall, negative_sampling=negative_sampling,
-             ubcache_updates_then_rank=ubcache_updates_then_rank, als_fit=als_fit)
+             ubcache_updates_then_rank=ubcache_updates_then_rank, als_fit=als_fit, als_cg_fit=als_cg_fit, als_dot_recall=als_dot_recall)
 CASES.update({f"ctr_{('din', 'youtube')[kind]}_{('graph', 'eager')[eager]}": ctr_training(kind, eager) for kind in (0, 1) for eager in (0, 1)})
 CASES.update(mlp_fused_f64_rows=mlp_fit("a", True), mlp_fused_f32_rows=mlp_fit("a", False), mlp_layers=mlp_fit("e", True),
              embedding_training=embedding_training("E"),

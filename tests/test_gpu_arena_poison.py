@@ -29,7 +29,11 @@ Covered: the recall and recommend entries of scripts/record_recall_entries.py (t
 order); every metrics_frozen.json case up to 65 537 rows as a case of its own, one calibrator fit / apply, one paired
 bootstrap; goctr_searcher_search at four shapes, each through the default dispatch, the VALU scan, the bf16 scan and the tile
 kernels on a searcher of its own (where a shape has no scan path -- D = 8, k = 256 -- all four are the tile kernels), and one
-goctr_searcher_search_ignore_sets call on the repair launch; one whole ALS fit (goctr_als_fit, _loss, _export); the
+goctr_searcher_search_ignore_sets call on the repair launch; one whole ALS fit by the Cholesky solver at D = 8 and one by
+conjugate gradient at D = 64 (goctr_als_fit, _loss, _export; goctr_als_create_cg); goctr_als_recall_dot with the request fragments
+in LDS (D = 66: a stored-source call of two row tiles and three chunks, a fold-in call on a freshly fitted handle, a stored call
+of 5 rows on the first one's leftovers -- the request block, its flags, the zero-row bitmap, the seen bitmap and the partial lists
+are all allocated uncleared); the
 builds goctr_itemcf_build, _build_swing, _build_vectors, _build_ease, goctr_usercf_build, goctr_popular_build,
 goctr_walkgraph_build_weighted, goctr_itemvec_index_build, goctr_itemattr_* with one goctr_fuse_recall_filtered,
 goctr_samples_create, goctr_ubcache_batch_set / _delete / _append with goctr_rank behind them; goctr_train_dataset (DIN and
@@ -55,8 +59,10 @@ The pinned host staging (csrc/host_stage.h, csrc/staging.h) and the BAR buffers 
 of scope.
 
 Cost on the MI355X (one process, the default 2 GiB arena, all of it free): one fill takes 0.9 ms on a fresh arena and 9 to 19 ms
-on later calls, the two stream waits and the call included (2 GiB of hipMemsetD32Async); the 421 tests of the file take 5.8 s,
-about 415 fills among them, the slowest test 0.8 s (each child process; 3 s inside the whole suite).  A fill costs about as much
+on later calls, the two stream waits and the call included (2 GiB of hipMemsetD32Async); the 429 tests of the file take 3.7 to
+4.4 s, about 423 fills among them, the slowest test 0.5 s (each child process).  The 421 tests before als_cg_fit and
+als_dot_recall took 3.9 to 4.6 s in the same call, alternated twice: the two cases cost less than the spread between runs (5.8 s
+was measured when the file was written).  A fill costs about as much
 as a small case, but the file stays under six seconds, so every case fills for itself.
 
 Planted defects when the file was written, each run once and then taken out again:
