@@ -282,6 +282,11 @@ class EaseDump(C.Structure):
                 ("P", C.POINTER(C.c_double)), ("B", C.POINTER(C.c_double)), ("b_max", C.POINTER(C.c_double))]
 
 
+class EaseRecallCfg(C.Structure):
+    """goctr_ease_recall_cfg (include/goctr.h)"""
+    _fields_ = [("min_score", C.c_double), ("chunk_items", C.c_int64), ("reserved", C.c_int64)]
+
+
 class MmrCfg(C.Structure):
     """goctr_mmr_cfg (include/goctr.h)"""
     _fields_ = [("k", C.c_int32), ("pool", C.c_int32), ("lambda_q", C.c_int32), ("max_per_group", C.c_int32)]
@@ -425,6 +430,8 @@ SYMBOLS = [
     "goctr_als_cg_cfg_default", "goctr_als_create_cg", "goctr_als_solver",
     "goctr_als_dot_cfg_default", "goctr_als_recall_dot", "goctr_recommend_als_dot",
     "goctr_ease_cfg_default", "goctr_ease_block_size", "goctr_itemcf_build_ease",
+    "goctr_ease_recall_cfg_default", "goctr_ease_build", "goctr_ease_destroy", "goctr_ease_info", "goctr_ease_recall",
+    "goctr_recommend_ease",
     "goctr_uservec_cfg_default", "goctr_uservec_recall", "goctr_recommend_uservec", "goctr_recommend_blend_uservec",
     "goctr_uservec_multi_cfg_default", "goctr_uservec_interests", "goctr_uservec_recall_multi", "goctr_recommend_uservec_multi",
     "goctr_ivf_cfg_default", "goctr_itemvec_index_build", "goctr_itemvec_index_destroy", "goctr_itemvec_index_info",
@@ -466,6 +473,7 @@ def load() -> C.CDLL:
                      "goctr_walkgraph_cfg_default", "goctr_walk_cfg_default", "goctr_walkgraph_destroy",
                      "goctr_edgeweight_cfg_default",
                      "goctr_als_cfg_default", "goctr_als_cg_cfg_default", "goctr_als_dot_cfg_default", "goctr_als_destroy", "goctr_ease_cfg_default", "goctr_fuse_cfg_default",
+                     "goctr_ease_recall_cfg_default", "goctr_ease_destroy",
                      "goctr_itemattr_destroy", "goctr_usercf_cfg_default", "goctr_usercf_recall_cfg_default", "goctr_usercf_destroy",
                      "goctr_walksampler_cfg_default", "goctr_walkp_cfg_default", "goctr_walksampler_destroy"):
             getattr(_lib, name).restype = None
@@ -684,6 +692,16 @@ def load() -> C.CDLL:
         _lib.goctr_ease_block_size.argtypes = []
         _lib.goctr_ease_block_size.restype = C.c_int32
         _lib.goctr_itemcf_build_ease.argtypes = [C.c_void_p, C.POINTER(EaseCfg), C.POINTER(C.c_void_p), C.POINTER(EaseDump)]
+        _er = C.POINTER(EaseRecallCfg)
+        _lib.goctr_ease_recall_cfg_default.argtypes = [_er]
+        _lib.goctr_ease_build.argtypes = [C.c_void_p, C.POINTER(EaseCfg), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                          C.POINTER(EaseDump)]
+        _lib.goctr_ease_destroy.argtypes = [C.c_void_p]
+        _lib.goctr_ease_info.argtypes = [C.c_void_p, _i64, _i32, _i32, _f64, _u64]
+        _lib.goctr_ease_recall.argtypes = [C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, C.POINTER(RecallCfg), _er, _i32, _u32, _i32,
+                                           _i32, _i32, _i32, _i32, _f64]
+        _lib.goctr_recommend_ease.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32, C.POINTER(RecallCfg),
+                                              _er, C.c_int32, C.c_int64, _i32, _f32, _i32, _i32, _i32, _i64, _i32, _u32, _f32, _i64]
         _um = C.POINTER(UservecMultiCfg)
         _lib.goctr_uservec_multi_cfg_default.argtypes = [_um]
         _lib.goctr_uservec_interests.argtypes = [C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, C.POINTER(RecallCfg), _um, _i32,
@@ -859,6 +877,7 @@ default_fuse_cfg = _default(FuseCfg, "goctr_fuse_cfg_default")
 ALS_USERS, ALS_ITEMS = 0, 1                 # goctr_als_step's sides
 default_ease_cfg = _default(EaseCfg, "goctr_ease_cfg_default")
 EASE_SCALE_GLOBAL, EASE_SCALE_ROW = 0, 1    # goctr_ease_cfg.scale
+default_ease_recall_cfg = _default(EaseRecallCfg, "goctr_ease_recall_cfg_default")
 
 
 PROF_COUNT = 18          # GOCTR_K_COUNT (include/goctr.h)

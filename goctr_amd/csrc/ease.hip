@@ -29,6 +29,10 @@
 //   ease_b_kernel           one workgroup per row: B, the row's maximum, the global maximum
 //   ease_list_kernel        one workgroup per row: the weights, the best n_nbr of them by one descending sort network in LDS
 // What bounds them is in DESIGN 4.6.
+//
+// goctr_ease_build is the same build (ease_build below is the one body of both entries) that KEEPS the model: B, the active order
+// and its inverse move into a goctr_ease handle (ease_dense.h), which goctr_ease_recall scans (ease_dense.hip); the lists are then
+// an option, and ease_list_kernel runs only when they are asked for.
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -36,6 +40,7 @@
 #include <vector>
 
 #define GOCTR_NO_PLAIN_KERNELS      // the kernel headers' plain kernels belong to ctr.hip
+#include "ease_dense.h"
 #include "itemcf.h"
 #include "walk.h"
 #include "lds_lists.h"
@@ -436,8 +441,9 @@ struct EaseNoSink {
   __device__ __forceinline__ void operator()(long long, unsigned int, u64) const {}
 };
 
-int ease_check_cfg(const goctr_ease_cfg* c, const char* who) {
-  GOCTR_CHECK(c->n_nbr >= 1 && c->n_nbr <= EASE_MAX_NBR, "%s: n_nbr = %d (1 .. %d)", who, c->n_nbr, EASE_MAX_NBR);
+// lists: the call builds neighbour lists (n_nbr is read with them alone)
+int ease_check_cfg(const goctr_ease_cfg* c, bool lists, const char* who) {
+  GOCTR_CHECK(!lists || (c->n_nbr >= 1 && c->n_nbr <= EASE_MAX_NBR), "%s: n_nbr = %d (1 .. %d)", who, c->n_nbr, EASE_MAX_NBR);
   GOCTR_CHECK(c->max_items >= 1 && c->max_items <= EASE_MAX_ITEMS, "%s: max_items = %d (1 .. %d)", who, c->max_items, EASE_MAX_ITEMS);
   GOCTR_CHECK(c->min_degree >= 1, "%s: min_degree = %d (>= 1)", who, c->min_degree);
   GOCTR_CHECK(c->scale == GOCTR_EASE_SCALE_GLOBAL || c->scale == GOCTR_EASE_SCALE_ROW,
@@ -481,26 +487,28 @@ int ease_alloc(DevBuf<T>& b, size_t count, bool zero, const char* who, const cha
   return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-void goctr_ease_cfg_default(goctr_ease_cfg* c) {
-  if (!c) return;
-  c->n_nbr = 64; c->max_items = 8192; c->min_degree = 1; c->scale = GOCTR_EASE_SCALE_GLOBAL; c->lambda = 500.0; c->reserved = 0;
+// dst takes src's buffer (a DevBuf is neither copied nor moved: the arena wants one owner)
+template <class T>
+void ease_take(DevBuf<T>& dst, DevBuf<T>& src) {
+  dst.release();
+  dst.p = src.p; dst.n = src.n; dst.owner = src.owner;
+  src.p = nullptr; src.n = 0;
 }
 
-int32_t goctr_ease_block_size(void) { return EASE_NB; }
+}  // namespace
 
-int goctr_itemcf_build_ease(goctr_walkgraph* g, const goctr_ease_cfg* cfg, goctr_itemcf** out, const goctr_ease_dump* dump) {
-  GOCTR_ENTER_H(g);
-  const char* who = "goctr_itemcf_build_ease";
-  GOCTR_CHECK(g && cfg && out, "%s: null argument (graph, cfg, out)", who);
-  if (ease_check_cfg(cfg, who)) return -1;
+namespace goctr {
+
+// the caller holds the engine lock of the graph's engine and has checked g, cfg and the outputs it wants for null
+int ease_build(const char* who, goctr_walkgraph* g, const goctr_ease_cfg* cfg, goctr_itemcf** out_lists, goctr_ease** out_model,
+               const goctr_ease_dump* dump) {
+  const bool lists = out_lists != nullptr;
+  if (ease_check_cfg(cfg, lists, who)) return -1;
   GOCTR_CHECK(g->n_items > 0, "%s: the graph has no items", who);
   hipStream_t st = engine().stream;
   const long long n_items = g->n_items;
-  const int M = cfg->n_nbr, row_scale = cfg->scale == GOCTR_EASE_SCALE_ROW ? 1 : 0;
+  const int M = lists ? cfg->n_nbr : 0, row_scale = cfg->scale == GOCTR_EASE_SCALE_ROW ? 1 : 0;
+  std::unique_ptr<goctr_ease> model(out_model ? new goctr_ease : nullptr);
   std::unique_ptr<goctr_itemcf> r(new goctr_itemcf);
   DevBuf<u64> key, sorted, tiles, total, pairs, n_distinct, rowmax, gmax;
   DevBuf<unsigned int> elig, G, flag;
@@ -511,9 +519,12 @@ int goctr_itemcf_build_ease(goctr_walkgraph* g, const goctr_ease_cfg* cfg, goctr
   StreamDrain drain{st};                       // (behind the buffers: an error return drains the stream before they go)
   ph.on = dbg_on("ease"); ph.st = st;
   r->n_items = n_items; r->M = M; r->cache_version = g->cache_version;
-  if (r->cnt.alloc((size_t)n_items, false) || r->nbr_items.alloc((size_t)n_items * M, false) || r->nbr_w.alloc((size_t)n_items * M) ||
-      r->nbr_co.alloc((size_t)n_items * M)) return -1;
-  GOCTR_HIP(hipMemsetAsync(r->nbr_items.p, 0xff, sizeof(int32_t) * (size_t)n_items * M, st));
+  if (r->cnt.alloc((size_t)n_items, false)) return -1;
+  if (lists) {
+    if (r->nbr_items.alloc((size_t)n_items * M, false) || r->nbr_w.alloc((size_t)n_items * M) || r->nbr_co.alloc((size_t)n_items * M))
+      return -1;
+    GOCTR_HIP(hipMemsetAsync(r->nbr_items.p, 0xff, sizeof(int32_t) * (size_t)n_items * M, st));
+  }
 
   // 1. the active items: degree descending, then id ascending
   ph.mark("start");
@@ -572,9 +583,11 @@ int goctr_itemcf_build_ease(goctr_walkgraph* g, const goctr_ease_cfg* cfg, goctr
     // 5. B, the maxima, the lists
     hipLaunchKernelGGL(ease_b_kernel, dim3((unsigned)n), dim3(EASE_THREADS), 0, st, a.p, n, ld, b.p, rowmax.p, gmax.p);
     GOCTR_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ease_list_kernel, dim3((unsigned)n), dim3(EASE_THREADS), 0, st, b.p, G.p, active.p, row_of.p, rowmax.p, gmax.p,
-                       row_scale, n, ld, M, r->nbr_items.p, r->nbr_w.p, r->nbr_co.p, n_distinct.p);
-    GOCTR_HIP(hipGetLastError());
+    if (lists) {
+      hipLaunchKernelGGL(ease_list_kernel, dim3((unsigned)n), dim3(EASE_THREADS), 0, st, b.p, G.p, active.p, row_of.p, rowmax.p, gmax.p,
+                         row_scale, n, ld, M, r->nbr_items.p, r->nbr_w.p, r->nbr_co.p, n_distinct.p);
+      GOCTR_HIP(hipGetLastError());
+    }
     ph.mark("lists");
     unsigned int h_flag = 0;
     if (flag.download(&h_flag, 1) || pairs.download(&h_pairs, 1) || n_distinct.download(&h_distinct, 1)) return -1;
@@ -608,7 +621,57 @@ int goctr_itemcf_build_ease(goctr_walkgraph* g, const goctr_ease_cfg* cfg, goctr
     if (dump->b_max) memcpy(dump->b_max, h_max.data(), sizeof(double) * h_max.size());
   }
   r->n_distinct = h_distinct; r->total_pairs = h_pairs;
-  *out = r.release();
+  if (model) {                                 // (the stream is drained on every path that reaches this line)
+    model->n_items = n_items; model->n_users = g->n_users; model->n_active = n; model->ld = n > 0 ? ld : 0;
+    model->lambda = cfg->lambda; model->cache_version = g->cache_version;
+    ease_take(model->B, b); ease_take(model->active, active); ease_take(model->row_of, row_of);
+    *out_model = model.release();
+  }
+  if (lists) *out_lists = r.release();
+  return 0;
+}
+
+}  // namespace goctr
+
+extern "C" {
+
+void goctr_ease_cfg_default(goctr_ease_cfg* c) {
+  if (!c) return;
+  c->n_nbr = 64; c->max_items = 8192; c->min_degree = 1; c->scale = GOCTR_EASE_SCALE_GLOBAL; c->lambda = 500.0; c->reserved = 0;
+}
+
+int32_t goctr_ease_block_size(void) { return EASE_NB; }
+
+int goctr_itemcf_build_ease(goctr_walkgraph* g, const goctr_ease_cfg* cfg, goctr_itemcf** out, const goctr_ease_dump* dump) {
+  GOCTR_ENTER_H(g);
+  const char* who = "goctr_itemcf_build_ease";
+  GOCTR_CHECK(g && cfg && out, "%s: null argument (graph, cfg, out)", who);
+  return ease_build(who, g, cfg, out, nullptr, dump);
+}
+
+int goctr_ease_build(goctr_walkgraph* g, const goctr_ease_cfg* cfg, goctr_ease** out, goctr_itemcf** out_lists,
+                     const goctr_ease_dump* dump) {
+  GOCTR_ENTER_H(g);
+  const char* who = "goctr_ease_build";
+  GOCTR_CHECK(g && cfg && out, "%s: null argument (graph, cfg, out)", who);
+  return ease_build(who, g, cfg, out_lists, out, dump);
+}
+
+void goctr_ease_destroy(goctr_ease* e) {
+  if (!e) return;
+  EngineScope on(e->eng);
+  std::lock_guard<std::recursive_mutex> lk(e->eng->mu);
+  delete e;
+}
+
+int goctr_ease_info(goctr_ease* e, int64_t* n_items, int32_t* n_active, int32_t* ld, double* lambda, uint64_t* cache_version) {
+  GOCTR_ENTER_H(e);
+  GOCTR_CHECK(e, "goctr_ease_info: null handle");
+  if (n_items) *n_items = e->n_items;
+  if (n_active) *n_active = e->n_active;
+  if (ld) *ld = e->ld;
+  if (lambda) *lambda = e->lambda;
+  if (cache_version) *cache_version = e->cache_version;
   return 0;
 }
 

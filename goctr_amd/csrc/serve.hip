@@ -27,6 +27,7 @@
 #include "walk.h"
 #include "als.h"
 #include "als_dot.h"
+#include "ease_dense.h"
 
 // ------------------------------------------------------------------ serving: recommend.BatchPredict / Rank / Predict
 // recommend/rcmd.go:248-337: sample keys -> GetSampleVector rows -> PredictAbstract.Predict -> scores, called from concurrent
@@ -818,6 +819,21 @@ int goctr_recommend_als_dot(goctr_model* m, goctr_recsys* r, goctr_als* als, con
                         out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed};
   if (alsdot_check_recommend(who, als, dcfg, a, r->n_users, r->n_items)) return -1;
   return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return alsdot_recommend_run(sc, als, *dcfg, a); });
+}
+
+// goctr_recommend_itemcf with the EASE dense scan (ease_dense.hip) as the driver's recall stage
+int goctr_recommend_ease(goctr_model* m, goctr_recsys* r, goctr_ease* e, const int32_t* users, const int64_t* ts, int64_t n_req,
+                         const int32_t* targets, const goctr_recall_cfg* recall_cfg, const goctr_ease_recall_cfg* ecfg, int32_t k,
+                         int64_t pass_rows, int32_t* out_items, float* out_scores, int32_t* out_count, int32_t* out_cand_count,
+                         int32_t* out_target_pos, int64_t* out_target_rank, int32_t* cand_items, uint32_t* cand_w,
+                         float* cand_scores, int64_t* n_failed) {
+  EngineScope on(handle_engine(m));
+  const char* who = "goctr_recommend_ease";
+  if (recommend_enter(who, m && r && e && recall_cfg && ecfg, m, r, {handle_engine(e)})) return -1;
+  const ItemcfRecArgs a{users, ts, n_req, targets, *recall_cfg, k, pass_rows, out_items, out_scores, out_count, out_cand_count,
+                        out_target_pos, out_target_rank, cand_items, cand_w, cand_scores, n_failed};
+  if (ease_check_recommend(who, e, ecfg, a, r->n_users, r->n_items)) return -1;
+  return with_scorer(m, r, pass_rows, [&](const TopnScorer& sc) { return ease_recommend_run(sc, e, *ecfg, a); });
 }
 
 // goctr_recommend_blend / _blend_mmr with the ALS fold-in recall writing part X's list on the device

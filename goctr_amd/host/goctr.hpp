@@ -1342,6 +1342,49 @@ inline TopN RecommendAlsDot(model::CtrNet& net, RecSys& rs, const ALS& als, cons
   return out;
 }
 
+// The EASE model kept in HBM (goctr_ease_build) and its dense scoring scan: whole rows of B, negative weights included.
+// ItemCF::Ease serves the same model through each row's best n_nbr positive entries
+class EaseModel {
+ public:
+  explicit EaseModel(goctr_walkgraph* graph, const goctr_ease_cfg& cfg = ItemCF::DefaultEaseCfg(), const goctr_ease_dump* dump = nullptr) {
+    check(goctr_ease_build(graph, &cfg, &h_, nullptr, dump));
+  }
+  ~EaseModel() { goctr_ease_destroy(h_); }
+  EaseModel(const EaseModel&) = delete;
+  EaseModel& operator=(const EaseModel&) = delete;
+  goctr_ease* handle() const { return h_; }
+  static goctr_ease_recall_cfg DefaultRecallCfg() { goctr_ease_recall_cfg c; goctr_ease_recall_cfg_default(&c); return c; }
+  // goctr_ease_recall: every row's n_cand best active items by the sum of B[i][j] over its history, items / w [nq, n_cand]
+  // (padding -1 / 0; ALS::DotScore decodes w) and count [nq]
+  void Recall(goctr_ubcache* cache, const std::vector<int32_t>& users, const std::vector<int64_t>& ts, const goctr_recall_cfg& rcfg,
+              const goctr_ease_recall_cfg& ecfg, std::vector<int32_t>& items, std::vector<uint32_t>& w, std::vector<int32_t>& count) const {
+    if (!ts.empty() && ts.size() != users.size()) throw std::invalid_argument("EaseModel::Recall: one timestamp per user");
+    items.resize(users.size() * (size_t)rcfg.n_cand); w.resize(items.size()); count.resize(users.size());
+    check(goctr_ease_recall(h_, cache, users.data(), ts.empty() ? nullptr : ts.data(), (int64_t)users.size(), &rcfg, &ecfg, items.data(),
+                            w.data(), count.data(), nullptr, nullptr, nullptr, nullptr, nullptr));
+  }
+  // goctr_recommend_ease: RecommendItemCFBatch with the dense scan as the recall stage
+  TopN Recommend(model::CtrNet& net, RecSys& rs, const std::vector<int32_t>& users, int n = 10, const std::vector<int64_t>& ts = {},
+                 const goctr_recall_cfg& rcfg = ItemCF::DefaultRecallCfg(), const goctr_ease_recall_cfg& ecfg = DefaultRecallCfg(),
+                 const std::vector<int32_t>& targets = {}, int64_t pass_rows = 0) const {
+    const int64_t nq = (int64_t)users.size();
+    detail::check_request("EaseModel::Recommend", users.size(), ts.size(), targets.size(), n);
+    std::vector<int32_t> items((size_t)nq * n), count((size_t)nq);
+    std::vector<float> scores((size_t)nq * n);
+    TopN out;
+    if (!targets.empty()) out.target_rank.resize((size_t)nq);
+    check(goctr_recommend_ease(net.Vm(), rs.handle(), h_, users.data(), ts.empty() ? nullptr : ts.data(), nq,
+                               targets.empty() ? nullptr : targets.data(), &rcfg, &ecfg, n, pass_rows, items.data(), scores.data(),
+                               count.data(), nullptr, nullptr, targets.empty() ? nullptr : out.target_rank.data(), nullptr, nullptr,
+                               nullptr, &out.n_failed));
+    out.lists = detail::gather_lists(items, scores, count, n);
+    return out;
+  }
+
+ private:
+  goctr_ease* h_ = nullptr;
+};
+
 // RecommendBlendBatch with the ALS fold-in recall as the caller's list (goctr_recommend_blend_als): ItemCF's candidates, the n_als
 // items closest to the folded-in vector (written and read in HBM), then the popularity list, which carries the popularity part
 // the cosine ranking drops; with `rerank` and `mcfg` the diversity re-rank picks the mcfg->k returned

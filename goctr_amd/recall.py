@@ -785,6 +785,77 @@ class ALS(_Handle):
         return out
 
 
+def make_ease_recall_cfg(min_score=None, chunk_items=0) -> capi.EaseRecallCfg:
+    """goctr_ease_recall_cfg from keywords: ``min_score`` (a number that is not NaN; None: the library's -inf), ``chunk_items`` (0,
+    or 64 .. 2^22).  A value outside these raises here: it never reaches the library"""
+    kw = dict(chunk_items=_as_int("chunk_items", chunk_items))
+    if kw["chunk_items"] != 0 and not 64 <= kw["chunk_items"] <= 1 << 22:
+        raise ValueError(f"chunk_items = {chunk_items!r} is neither 0 nor in 64 .. 2^22")
+    if min_score is not None:
+        kw["min_score"] = float(min_score)
+        if kw["min_score"] != kw["min_score"]:
+            raise ValueError("min_score is not a number")
+    return capi.default_ease_recall_cfg(**kw)
+
+
+class EASE(_Handle):
+    """goctr_ease: the EASE model kept in HBM -- B float64 over the active items, whole rows, negative weights included -- and its
+    dense scoring scan (tests/ease_dense_ref.py is the host restatement).  ``ItemCF.ease`` serves the same model through each row's
+    best n_nbr positive entries; ``lists=True`` returns those too, from the one factorisation, in ``.lists``"""
+    _destroy = "goctr_ease_destroy"
+
+    def __init__(self, graph: "WalkGraph", lists=False, dump=False, cfg: capi.EaseCfg | None = None, **ease_cfg):
+        """goctr_ease_build over ``graph``'s distinct edges; ``ease_cfg``: goctr_ease_cfg fields (max_items, min_degree, scale,
+        lambda_, and n_nbr, which is read only with ``lists``).  ``dump``: ``.dump`` is ``ItemCF.ease``'s dict (n_active, active, G,
+        P, B, b_max, slots)"""
+        cfg = _cfg_or_kw(cfg, ease_cfg, make_ease_cfg)
+        self._h, self.lists, self.dump = C.c_void_p(), None, None
+        lh = C.c_void_p()
+        d = arrays = None
+        if dump:
+            cap = max(min(int(cfg.max_items), graph.n_items), 1)
+            n = C.c_int32(-2)
+            arrays = dict(active=_unwritten(cap, np.int32), G=np.zeros((cap, cap), np.uint32), P=np.full((cap, cap), np.nan),
+                          B=np.full((cap, cap), np.nan), b_max=np.full(cap, np.nan))
+            d = capi.EaseDump(C.pointer(n), *(_ptr(arrays[k]) for k in ("active", "G", "P", "B", "b_max")))
+        capi.check(capi.load().goctr_ease_build(graph._h, C.byref(cfg), C.byref(self._h), C.byref(lh) if lists else None,
+                                                C.byref(d) if dump else None))
+        if lists:
+            self.lists = ItemCF._adopt(lh)
+        if dump:
+            na = n.value
+            packed = lambda a: a.ravel()[:na * na].reshape(na, na).copy()       # (the library packs at stride n_active)
+            self.dump = dict(n_active=na, active=arrays["active"][:na].copy(), G=packed(arrays["G"]), P=packed(arrays["P"]),
+                             B=packed(arrays["B"]), b_max=arrays["b_max"][:na if cfg.scale == capi.EASE_SCALE_ROW else 1].copy(),
+                             slots=arrays["active"])
+        i = self.info()
+        self.n_items, self.n_active = i["n_items"], i["n_active"]
+
+    def info(self) -> dict:
+        n, na, ld, lam, v = C.c_int64(0), C.c_int32(0), C.c_int32(0), C.c_double(0.0), C.c_uint64(0)
+        capi.check(capi.load().goctr_ease_info(self._h, C.byref(n), C.byref(na), C.byref(ld), C.byref(lam), C.byref(v)))
+        return dict(n_items=n.value, n_active=na.value, ld=ld.value, lambda_=lam.value, cache_version=v.value)
+
+    def recall(self, ubc, users, ts=None, targets=None, validate=False, cfg: capi.RecallCfg | None = None, min_score=None,
+               chunk_items=0, ecfg: capi.EaseRecallCfg | None = None, **kw) -> dict:
+        """goctr_ease_recall over DENSE user rows of ``ubc``'s image: the active items ranked by the model's own score, the sum of
+        B[i][j] over the row's distinct active history items in float64.  ``kw``: goctr_recall_cfg fields.  dict(items, w, scores
+        float32 [nq, n_cand] (w decoded, NaN in the padding), count, target_pos when targets are given; with ``validate`` rows int32
+        [nq, history] (the ordered model rows, -1 behind them), n int32 [nq], dense float64 [nq, n_items]: every item's score)"""
+        ecfg = ecfg if ecfg is not None else make_ease_recall_cfg(min_score, chunk_items)
+        cfg = _cfg_or_kw(cfg, kw, make_recall_cfg)
+        users, ts, targets = request_columns(users, ts, targets)
+        out = _recall_buffers(users.size, cfg.n_cand, targets)
+        if validate:
+            out["rows"], out["n"] = _unwritten((users.size, max(int(cfg.history), 1)), np.int32), _unwritten(users.size, np.int32)
+            out["dense"] = np.full((users.size, self.n_items), np.nan, np.float64)
+        capi.check(capi.load().goctr_ease_recall(self._h, _cache_handle(ubc), *_request_args(users, ts), C.byref(cfg), C.byref(ecfg),
+                                                 *_recall_args(out, targets), _ptr(out.get("rows")), _ptr(out.get("n")),
+                                                 _ptr(out.get("dense"))))
+        out["scores"] = als_dot_scores(out["w"])
+        return out
+
+
 def extra_columns(extra, nq):
     """the caller's candidate lists as the C-ABI takes them: (int32 [nq, n_extra] or None, n_extra)"""
     if extra is None:

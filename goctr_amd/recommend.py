@@ -27,7 +27,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import capi, metrics, sampling
-from .recall import (ALS, EXCLUDE, _USERCF_RECALL_FIELDS, _USERVEC_FIELDS, _USERVEC_IVF_FIELDS, _USERVEC_MULTI_FIELDS, _WALK_FIELDS, ItemCF,
+from .recall import (ALS, EASE, EXCLUDE, make_ease_recall_cfg, _USERCF_RECALL_FIELDS, _USERVEC_FIELDS, _USERVEC_IVF_FIELDS, _USERVEC_MULTI_FIELDS, _WALK_FIELDS, ItemCF,
                      ItemVectors, Popular, UserCF, WalkGraph, make_usercf_recall_cfg, _as_int, _cfg_or_kw, _ptr, _request_args, _split_kw, _unwritten, extra_columns, make_mmr_cfg,
                      make_als_dot_cfg, make_recall_cfg, make_uservec_cfg, make_uservec_ivf_cfg, make_uservec_multi_cfg, make_walk_cfg, merge,
                      WalkSampler, _WALKP_FIELDS, check_walkp_cfg, make_walkp_cfg,
@@ -555,6 +555,7 @@ _OUTPUTS = {
     "goctr_recommend_blend_walk": _BLENDED + ("obj", "pen", "target_place"),
     "goctr_recommend_als": _RANKED,
     "goctr_recommend_als_dot": _RANKED,
+    "goctr_recommend_ease": _RANKED,
     "goctr_recommend_blend_als": _BLENDED + ("obj", "pen", "target_place"),
     "goctr_recommend_fused": _BLENDED + ("obj", "pen", "target_place"),
     "goctr_recommend_fused_filtered": _BLENDED + ("obj", "pen", "target_place"),
@@ -776,6 +777,20 @@ def als_dot(model: Predictor, factors, users, ts=None, targets=None, k=10, pass_
     head = (*_request_head(model, factors), *_request_args(users, ts), capi.ptr(targets, C.c_int32), C.byref(cfg), C.byref(dcfg),
             *_k_pass(k, pass_rows))
     return _ranked_call("goctr_recommend_als_dot", head, users.size, k, cfg.n_cand, targets, validate)
+
+
+def ease(model: Predictor, ease_model, users, ts=None, targets=None, k=10, pass_rows=0, validate=False, recall_cfg=None, ecfg=None,
+         min_score=None, chunk_items=0, **recall_kw):
+    """goctr_recommend_ease over DENSE indices: ``itemcf`` with the dense scan of ``ease_model``'s B (recall.EASE.recall) as the
+    recall stage; the same dict, cand_w being the score's weight image (recall.als_dot_scores decodes it).  ``min_score``,
+    ``chunk_items``: recall.make_ease_recall_cfg's; ``recall_kw``: goctr_recall_cfg fields.  What RecommendEASE /
+    RecommendEASEBatch / EvaluateLeaveOneOutEASE call."""
+    ecfg = ecfg if ecfg is not None else make_ease_recall_cfg(min_score, chunk_items)
+    cfg = _cfg_or_kw(recall_cfg, recall_kw, make_recall_cfg, "recall_cfg")
+    users, ts, targets = request_columns(users, ts, targets)
+    head = (*_request_head(model, ease_model), *_request_args(users, ts), capi.ptr(targets, C.c_int32), C.byref(cfg), C.byref(ecfg),
+            *_k_pass(k, pass_rows))
+    return _ranked_call("goctr_recommend_ease", head, users.size, k, cfg.n_cand, targets, validate)
 
 
 def blend_als(model: Predictor, icf, pop, factors, users, ts=None, targets=None, n_als=64, quota_pop=0, k=10, vectors=None, pool=64,
@@ -1072,6 +1087,20 @@ def RecommendALSDot(model: Predictor, factors, userId: int, n=10, now=None, **re
     return RecommendALSDotBatch(model, factors, [userId], n, now, **recall_kw)[0]
 
 
+def RecommendEASEBatch(model: Predictor, ease_model, userIds, n=10, now=None, **recall_kw):
+    """RecommendEASE for several users in one device call: [[ItemScore]] in the order of userIds.  ``now``: one timestamp for all, or
+    one per user.  A user whose history holds no active item gets an empty list."""
+    users, ts = _request_rows(model, userIds, now)
+    return _serve(model, users.size, lambda: ease(model, ease_model, users, ts, None, n, **recall_kw))
+
+
+def RecommendEASE(model: Predictor, ease_model, userId: int, n=10, now=None, **recall_kw):
+    """EXTENSION -- RecommendItemCF ranked by EASE's own score over WHOLE rows of B (BuildEASEModel): the ``n_cand`` active items
+    with the largest sum of B[i][j] over the user's newest ``history`` behaviours at or before ``now`` -- the negative weights pull
+    an item down, and no entry is lost behind a list's cut -- are scored by the model and the ``n`` best come back."""
+    return RecommendEASEBatch(model, ease_model, [userId], n, now, **recall_kw)[0]
+
+
 def RecommendBlendALSBatch(model: Predictor, icf, pop, factors, userIds, n=10, now=None, n_als=64, quota_pop=0, vectors=None, pool=64,
                            lambda_q=192, max_per_group=0, **recall_kw):
     """EXTENSION -- RecommendBlendBatch with the ALS fold-in recall as the caller's list: ItemCF's candidates, then the ``n_als`` items
@@ -1103,6 +1132,13 @@ def BuildEASE(recSys: DeviceRecSys, graph=None, graph_kw=None, **cfg):
     jointly, so a pair linked only through a hub is not weighted as if the link were direct.  Every RecommendItemCF / RecommendBlend /
     EvaluateLeaveOneOut* / MergeItemCF call takes the handle like BuildItemCF's; it is independent of the graph afterwards."""
     return ItemCF.ease(graph if graph is not None else BuildWalkGraph(recSys, **(graph_kw or {})), **cfg)
+
+
+def BuildEASEModel(recSys: DeviceRecSys, graph=None, graph_kw=None, lists=False, **cfg):
+    """EXTENSION: the EASE model itself (recall.EASE; ``cfg``: goctr_ease_cfg fields) over ``graph`` (default: BuildWalkGraph of the
+    recSys's cache, ``graph_kw`` its cfg) -- B stays in HBM, what RecommendEASE scans.  ``lists``: BuildEASE's handle too, from the
+    same factorisation, in ``.lists``.  The model is independent of the graph afterwards."""
+    return EASE(graph if graph is not None else BuildWalkGraph(recSys, **(graph_kw or {})), lists=lists, **cfg)
 
 
 def BuildUserCF(recSys: DeviceRecSys, graph=None, graph_kw=None, **cfg):
@@ -1587,6 +1623,35 @@ def EvaluateLeaveOneOutALSDot(model: Predictor, factors=None, k=10, sample_kw=No
             own.vectors.close()
             own.close()
             own.graph.close()
+    out = _loo_figures(r, targets, model.recSys.item_table.shape[0], k, cfg.n_cand)
+    if details:
+        out.update(_details(r, users, targets, ts))
+    return out
+
+
+def EvaluateLeaveOneOutEASE(model: Predictor, ease_model=None, k=10, sample_kw=None, details=False, pass_rows=0, graph_kw=None,
+                            ease_kw=None, **recall_kw):
+    """EvaluateLeaveOneOutRecall's protocol and figures with the EASE dense scan as the recall stage (goctr_recommend_ease).
+    ``ease_model`` None: the model is built here (``ease_kw``: goctr_ease_cfg fields) over a graph windowed below the held-out events
+    as EvaluateLeaveOneOutWalk's is (``graph_kw``), and closed on the way out; a caller's own model is used as it is."""
+    ecfg = make_ease_recall_cfg(**{key: recall_kw.pop(key) for key in ("min_score", "chunk_items") if key in recall_kw})
+    users, targets, ts = _held_out_rows(model, sample_kw)
+    recall_kw.setdefault("exclude", "before")
+    cfg = make_recall_cfg(**recall_kw)
+    own = None
+    if ease_model is None:
+        gkw = dict(graph_kw or {})
+        gkw.setdefault("ts_hi", int((sample_kw or {})["ts_lo"]) - 1 if "ts_lo" in (sample_kw or {}) else int(ts.min()))
+        graph = BuildWalkGraph(model.recSys, **gkw)
+        try:
+            ease_model = own = EASE(graph, **(ease_kw or {}))
+        finally:
+            graph.close()
+    try:
+        r = ease(model, ease_model, users, ts, targets, k, pass_rows, recall_cfg=cfg, ecfg=ecfg)
+    finally:
+        if own is not None:
+            own.close()
     out = _loo_figures(r, targets, model.recSys.item_table.shape[0], k, cfg.n_cand)
     if details:
         out.update(_details(r, users, targets, ts))

@@ -1467,7 +1467,8 @@ int goctr_recommend_als_dot(goctr_model* m, goctr_recsys* r, goctr_als* als,
  *                  the same loud error, never a list of NaNs
  * A graph with no active item (min_degree above every degree, or no edge) is not an error: every list is empty, n_active = 0.
  * The engine stream and the engine lock of the graph's engine, like goctr_walkgraph_build.  The handle is independent of the graph
- * afterwards.  Not covered: B's negative weights, a dense scoring call over whole rows of B, more than 32768 active items, per-edge
+ * afterwards.  The lists keep each row's best n_nbr POSITIVE entries; B's negative weights and whole rows of B are served by
+ * goctr_ease_build / goctr_ease_recall ("EASE dense scoring" below).  Not covered: more than 32768 active items, per-edge
  * confidence or recency weights, an incremental update of P after goctr_ubcache_append, a lambda per item. */
 #define GOCTR_EASE_SCALE_GLOBAL 0
 #define GOCTR_EASE_SCALE_ROW    1
@@ -1493,6 +1494,70 @@ typedef struct {       /* validation outputs in host memory; the struct and each
 /* the block size of the factorisation (a multiple of 16): what the tests size their cases against */
 int32_t goctr_ease_block_size(void);
 int  goctr_itemcf_build_ease(goctr_walkgraph* g, const goctr_ease_cfg* cfg, goctr_itemcf** out, const goctr_ease_dump* dump);
+
+/* ---- EASE dense scoring: the model's own score over WHOLE rows of B, negative weights included (no reference counterpart).
+ * goctr_itemcf_build_ease serves EASE through a truncation of itself; a goctr_ease handle keeps the model in HBM -- B [n_active, ld]
+ * float64 exactly as the build wrote it, the active order, its inverse -- and goctr_ease_recall ranks every active item by
+ * s(u,j) = sum of B[i][j] over the history, so "holders of i avoid j" lowers j (tests/ease_dense_ref.py is the host restatement).
+ *
+ * goctr_ease_build: goctr_itemcf_build_ease's build, refusals and dump; *out is the model.  With out_lists != NULL the SAME
+ *   factorisation also gives the list handle goctr_itemcf_build_ease returns for the graph and cfg, byte for byte; cfg->n_nbr is
+ *   read only then.  A graph with no active item is a model whose every request row comes back empty.
+ * goctr_ease_info: n_items, n_active, ld (B's leading dimension: n_active rounded up to goctr_ease_block_size, 0 without an active
+ *   item), lambda and the graph's cache_version; each pointer may be NULL.
+ *
+ * goctr_ease_recall:
+ *   history        goctr_itemcf_recall's history for the row: the first cfg->history valid entries the timestamp rule keeps.  Of
+ *                  these the DISTINCT items that are active (X is binary: a repeat counts once; an item outside the model adds
+ *                  nothing), as model rows ordered ascending by ITEM id: h_1 .. h_m.  A row with m = 0 has no vector and
+ *                  returns count 0
+ *   score          for every active item j: s = (((+0.0 + B[h_1][j]) + B[h_2][j]) + ...) + B[h_m][j] in float64, sequential in
+ *                  that order.  Only additions occur, so s is defined BIT FOR BIT given B; no output byte depends on chunk_items,
+ *                  on how request rows are grouped or tiled, or on thread arrival order
+ *   weight         goctr_als_recall_dot's image of s: f = s rounded to float32, -0 taken as +0; w = b ^ 0x80000000 when the sign
+ *                  bit of f's bits b is clear, else ~b
+ *   candidates     every ACTIVE item j with w >= the image of (float)min_score, but the seen items (goctr_itemcf_recall's rule
+ *                  under cfg->exclude, the target exemption included).  Negative scores are candidates; the history's own items
+ *                  are candidates under GOCTR_TOPN_KEEP_SEEN; an item outside the model never is
+ *   order          w descending, then item ascending; the first n_cand are kept; padding -1 / 0
+ *   out_rows       [n_req, cfg->history] (may be NULL): h_1 .. h_m, -1 behind them.  out_n [n_req] (may be NULL): m
+ *   out_scores     [n_req, n_items] float64 (may be NULL): the dense score of EVERY item, seen ones included -- the dense scoring
+ *                  call itself, for a caller who wants the vector and not a list; 0.0 for an item outside the model and for every
+ *                  item of a row with m = 0
+ *   refused        goctr_als_recall_dot's refusals where they apply; a NaN min_score; reserved != 0; chunk_items out of range; a
+ *                  cache that is not the graph's (the cache records no item count: its n_users is compared with the graph's;
+ *                  goctr_recommend_ease compares the recsys's n_items with the model's).  A refused call touches nothing; results
+ *                  reach the caller's arrays all together or not at all
+ * What bounds a call: it reads m rows of n_active doubles per request row, sum_q m_q * n_active * 8 bytes, and nothing else of B.
+ * Not covered: a fusion channel kind or a blend variant over this recall, a float32 copy of B, the exact rank of a target among all
+ * items, an export of the model (the build's dump has B), weighted X. */
+typedef struct goctr_ease goctr_ease;
+typedef struct {
+  double  min_score;    /* not NaN; a candidate needs f >= (float)min_score     default -inf   */
+  int64_t chunk_items;  /* 0 = the implementation's choice, else 64 .. 2^22     default 0      */
+  int64_t reserved;     /* must be 0 */
+} goctr_ease_recall_cfg;
+void goctr_ease_recall_cfg_default(goctr_ease_recall_cfg* c);
+int  goctr_ease_build(goctr_walkgraph* g, const goctr_ease_cfg* cfg, goctr_ease** out, goctr_itemcf** out_lists /* or NULL */,
+                      const goctr_ease_dump* dump /* or NULL */);
+void goctr_ease_destroy(goctr_ease* e);
+int  goctr_ease_info(goctr_ease* e, int64_t* n_items, int32_t* n_active, int32_t* ld, double* lambda, uint64_t* cache_version);
+int  goctr_ease_recall(goctr_ease* e, goctr_ubcache* c, const int32_t* users, const int64_t* ts /* NULL = 0 */, int64_t n_req,
+                       const goctr_recall_cfg* cfg, const goctr_ease_recall_cfg* ecfg,
+                       int32_t* out_items /*[n_req,n_cand]*/, uint32_t* out_w /*[n_req,n_cand]*/, int32_t* out_count /*[n_req]*/,
+                       const int32_t* targets /*[n_req] or NULL*/, int32_t* out_target_pos /*[n_req] or NULL*/,
+                       int32_t* out_rows /*[n_req,history] or NULL*/, int32_t* out_n /*[n_req] or NULL*/,
+                       double* out_scores /*[n_req,n_items] or NULL*/);
+
+/* goctr_recommend_ease: goctr_recommend_als_dot with goctr_ease_recall as its recall stage; cand_w is the weight defined above.
+ *   refused        goctr_recommend_itemcf's refusals, the ecfg refusals, the model not matching the recsys's n_items */
+int goctr_recommend_ease(goctr_model* m, goctr_recsys* r, goctr_ease* e,
+                         const int32_t* users, const int64_t* ts /* NULL = 0 */, int64_t n_req,
+                         const int32_t* targets /* [n_req] or NULL */, const goctr_recall_cfg* recall_cfg,
+                         const goctr_ease_recall_cfg* ecfg, int32_t k, int64_t pass_rows,
+                         int32_t* out_items /* [n_req,k] */, float* out_scores /* [n_req,k] */, int32_t* out_count,
+                         int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank,
+                         int32_t* cand_items, uint32_t* cand_w, float* cand_scores, int64_t* n_failed);
 
 /* ---- Multi-interest user-vector recall: the history clustered into up to 8 interest vectors, one list each, mixed into one (no
  * reference counterpart).  A user with two tastes pools to a vector between them and the larger taste takes the whole list; here
