@@ -270,6 +270,12 @@ class AlsDotCfg(C.Structure):
     _fields_ = [("source", C.c_int32), ("reserved", C.c_int32), ("min_score", C.c_double), ("chunk_items", C.c_int64)]
 
 
+class BprCfg(C.Structure):
+    """goctr_bpr_cfg (include/goctr.h)"""
+    _fields_ = [("epochs", C.c_int32), ("first_epoch", C.c_int32), ("batch", C.c_int32), ("lr", C.c_double), ("lambda_", C.c_double),
+                ("neg_tries", C.c_int32), ("neg_source", C.c_int32), ("seed", C.c_uint64), ("reserved", C.c_int64)]
+
+
 class EaseCfg(C.Structure):
     """goctr_ease_cfg (include/goctr.h)"""
     _fields_ = [("n_nbr", C.c_int32), ("max_items", C.c_int32), ("min_degree", C.c_int32), ("scale", C.c_int32),
@@ -429,6 +435,7 @@ SYMBOLS = [
     "goctr_als_create_weighted", "goctr_als_weights", "goctr_als_foldin_weights",
     "goctr_als_cg_cfg_default", "goctr_als_create_cg", "goctr_als_solver",
     "goctr_als_dot_cfg_default", "goctr_als_recall_dot", "goctr_recommend_als_dot",
+    "goctr_bpr_cfg_default", "goctr_bpr_fit",
     "goctr_ease_cfg_default", "goctr_ease_block_size", "goctr_itemcf_build_ease",
     "goctr_ease_recall_cfg_default", "goctr_ease_build", "goctr_ease_destroy", "goctr_ease_info", "goctr_ease_recall",
     "goctr_recommend_ease",
@@ -472,7 +479,7 @@ def load() -> C.CDLL:
                      "goctr_calib_cfg_default", "goctr_calibrator_destroy", "goctr_boot_cfg_default",
                      "goctr_walkgraph_cfg_default", "goctr_walk_cfg_default", "goctr_walkgraph_destroy",
                      "goctr_edgeweight_cfg_default",
-                     "goctr_als_cfg_default", "goctr_als_cg_cfg_default", "goctr_als_dot_cfg_default", "goctr_als_destroy", "goctr_ease_cfg_default", "goctr_fuse_cfg_default",
+                     "goctr_als_cfg_default", "goctr_als_cg_cfg_default", "goctr_als_dot_cfg_default", "goctr_als_destroy", "goctr_bpr_cfg_default", "goctr_ease_cfg_default", "goctr_fuse_cfg_default",
                      "goctr_ease_recall_cfg_default", "goctr_ease_destroy",
                      "goctr_itemattr_destroy", "goctr_usercf_cfg_default", "goctr_usercf_recall_cfg_default", "goctr_usercf_destroy",
                      "goctr_walksampler_cfg_default", "goctr_walkp_cfg_default", "goctr_walksampler_destroy"):
@@ -678,6 +685,8 @@ def load() -> C.CDLL:
         _lib.goctr_recommend_als.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, _i32,
                                              C.POINTER(RecallCfg), _uv, C.c_int32, C.c_int64, _i32, _f32, _i32, _i32, _i32, _i64,
                                              _i32, _u32, _f32, _i64]
+        _lib.goctr_bpr_cfg_default.argtypes = [C.POINTER(BprCfg)]
+        _lib.goctr_bpr_fit.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BprCfg), _f64, _f64, _i64, _i32]
         _ad = C.POINTER(AlsDotCfg)
         _lib.goctr_als_dot_cfg_default.argtypes = [_ad]
         _lib.goctr_als_recall_dot.argtypes = [C.c_void_p, C.c_void_p, _i32, _i64, C.c_int64, C.POINTER(RecallCfg), _ad, _i32, _u32, _i32,
@@ -873,6 +882,8 @@ default_als_cg_cfg = _default(AlsCgCfg, "goctr_als_cg_cfg_default")
 ALS_CHOLESKY, ALS_CG = 0, 1                 # goctr_als_solver's solvers
 default_als_dot_cfg = _default(AlsDotCfg, "goctr_als_dot_cfg_default")
 ALS_X_FOLDIN, ALS_X_STORED = 0, 1           # goctr_als_dot_cfg.source
+default_bpr_cfg = _default(BprCfg, "goctr_bpr_cfg_default")
+BPR_NEG_UNIFORM, BPR_NEG_POPULAR = 0, 1     # goctr_bpr_cfg.neg_source
 default_fuse_cfg = _default(FuseCfg, "goctr_fuse_cfg_default")
 ALS_USERS, ALS_ITEMS = 0, 1                 # goctr_als_step's sides
 default_ease_cfg = _default(EaseCfg, "goctr_ease_cfg_default")

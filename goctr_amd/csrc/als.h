@@ -65,6 +65,10 @@ struct AlsVecOut { double* x; int16_t* p; };
 int als_launch(const goctr_als* a, const goctr_itemvec* v, const RecallCall& r, const goctr_uservec_cfg& ucfg, const RecallRows& out,
                const AlsVecOut& vec, UvScratch& ws, hipStream_t st);
 
+// G_Y = Y^T Y of the handle's Y as it stands, by the Gram launches of its D (the handle's invariant behind a write of Y that is
+// not a half-step's: bpr.hip).  Queues on the engine stream and waits for nothing
+int als_refresh_gram_y(goctr_als* a);
+
 // the handle against the item vectors and the catalogue (sets the error text)
 int als_check_vectors(const char* who, const goctr_als* a, const goctr_itemvec* v, int64_t n_items);
 // goctr_recommend_als's refusals that need no slot, and the whole call over a prepared slot

@@ -590,6 +590,8 @@ int als_half_step(goctr_als* a, const goctr_walkgraph* g, int side) {
 
 namespace goctr {
 
+int als_refresh_gram_y(goctr_als* a) { return als_gram(a->Y.p, a->n_items, a->D, a->GY.p); }
+
 int als_foldin_launch(const goctr_als* a, const CacheSeq& seq, const int32_t* users, const long long* ts, int64_t nq, int history,
                       double* o_x, int16_t* o_p, int32_t* o_n, UvScratch& ws, hipStream_t st) {
   const int Dp = round_up(a->D, IV_K);

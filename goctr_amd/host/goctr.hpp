@@ -1256,6 +1256,19 @@ class ALS {
     vec_ = nullptr;
     check(goctr_itemvec_build_als(h_, nullptr, &vec_));
   }
+  // goctr_bpr_fit: cfg.epochs epochs of batch-synchronous pairwise SGD on X and Y as they stand (a fresh handle, or a fitted one as
+  // a warm start), then the item factors as quantised vectors.  loss, auc, skipped: one value per epoch
+  static goctr_bpr_cfg DefaultBprCfg() { goctr_bpr_cfg c; goctr_bpr_cfg_default(&c); return c; }
+  struct BprCurves { std::vector<double> loss, auc; std::vector<int64_t> skipped; };
+  BprCurves FitBpr(const goctr_bpr_cfg& cfg = DefaultBprCfg()) {
+    const size_t ne = cfg.epochs > 0 ? (size_t)cfg.epochs : 0;
+    BprCurves c{std::vector<double>(ne), std::vector<double>(ne), std::vector<int64_t>(ne)};
+    check(goctr_bpr_fit(h_, graph_, &cfg, c.loss.data(), c.auc.data(), c.skipped.data(), nullptr));
+    goctr_itemvec_destroy(vec_);
+    vec_ = nullptr;
+    check(goctr_itemvec_build_als(h_, nullptr, &vec_));
+    return c;
+  }
   void Step(int32_t side) { check(goctr_als_step(h_, graph_, side)); }
   double Loss() const { double v = 0; check(goctr_als_loss(h_, graph_, &v)); return v; }
   struct Info { int64_t n_users, n_items; int32_t D; int64_t half_steps; };

@@ -605,6 +605,25 @@ def make_als_cfg(**kw) -> capi.AlsCfg:
     return capi.default_als_cfg(**{k: float(v) if k in ("alpha", "lambda_") else _as_int(k, v) for k, v in kw.items()})
 
 
+_BPR_FIELDS = _fields(capi.BprCfg)
+BPR_NEG_SOURCE = {"uniform": capi.BPR_NEG_UNIFORM, "popular": capi.BPR_NEG_POPULAR}
+
+
+def make_bpr_cfg(**kw) -> capi.BprCfg:
+    """goctr_bpr_cfg from keywords: epochs, first_epoch, batch, neg_tries, seed (integers), lr, lambda_ (numbers; ``lambda`` is
+    taken too), ``neg_source`` "uniform" / "popular" (or capi.BPR_NEG_*); the ranges are the library's to refuse"""
+    if "lambda" in kw:
+        kw["lambda_"] = kw.pop("lambda")
+    unknown = set(kw) - _BPR_FIELDS
+    if unknown:
+        raise TypeError(f"goctr_bpr_cfg has no field {sorted(unknown)}")
+    if isinstance(kw.get("neg_source"), str):
+        if kw["neg_source"] not in BPR_NEG_SOURCE:
+            raise ValueError(f"neg_source = {kw['neg_source']!r} is none of {sorted(BPR_NEG_SOURCE)}")
+        kw["neg_source"] = BPR_NEG_SOURCE[kw["neg_source"]]
+    return capi.default_bpr_cfg(**{k: float(v) if k in ("lr", "lambda_") else _as_int(k, v) for k, v in kw.items()})
+
+
 ALS_SOURCE = {"foldin": capi.ALS_X_FOLDIN, "stored": capi.ALS_X_STORED}
 
 
@@ -708,6 +727,19 @@ class ALS(_Handle):
         """goctr_als_fit: cfg.n_iters iterations, a user step and an item step each"""
         capi.check(capi.load().goctr_als_fit(self._h, self.graph._h))
         return self
+
+    def fit_bpr(self, cfg: capi.BprCfg | None = None, triples=False, **kw) -> dict:
+        """goctr_bpr_fit: BPR epochs of batch-synchronous pairwise SGD that refine X and Y in place from their current values (a
+        fresh handle, or a fitted one as a warm start).  ``kw``: goctr_bpr_cfg fields (``make_bpr_cfg``).  dict(loss float64 [epochs],
+        auc float64 [epochs], skipped int64 [epochs]; with ``triples`` also triples int32 [epochs, n_edges, 3], j = -1 = skipped)"""
+        cfg = _cfg_or_kw(cfg, kw, make_bpr_cfg)
+        ne = max(int(cfg.epochs), 0)
+        out = dict(loss=np.full(ne, np.nan, np.float64), auc=np.full(ne, np.nan, np.float64), skipped=_unwritten(ne, np.int64))
+        if triples:
+            out["triples"] = _unwritten((ne, self.graph.n_edges, 3), np.int32)
+        capi.check(capi.load().goctr_bpr_fit(self._h, self.graph._h, C.byref(cfg), _ptr(out["loss"]), _ptr(out["auc"]),
+                                             _ptr(out["skipped"]), _ptr(out.get("triples"))))
+        return out
 
     def loss(self) -> float:
         """goctr_als_loss: the implicit objective over ALL pairs"""

@@ -1126,6 +1126,22 @@ def BuildALS(recSys: DeviceRecSys, graph=None, graph_kw=None, weight_kw=None, **
     return factors
 
 
+def BuildBPR(recSys: DeviceRecSys, graph=None, warm_start_iters=0, **cfg):
+    """EXTENSION: factors trained by BPR (recall.ALS.fit_bpr; ``cfg``: goctr_bpr_cfg fields -- epochs, batch, lr, lambda_, neg_tries,
+    neg_source, seed -- and recall.ALS's ``D``) over ``graph`` (default: BuildWalkGraph of the recSys's cache): the pairwise ranking
+    objective in the place of ALS's least squares.  ``warm_start_iters`` ALS iterations (conjugate gradient, any D) run first.  Returns
+    the ALS handle with the quantised item factors in ``.vectors`` and fit_bpr's curves in ``.bpr``: every RecommendALS* call takes it,
+    RecommendALSDot ranks by the score BPR trains."""
+    D = cfg.pop("D", None)
+    factors = ALS(graph if graph is not None else BuildWalkGraph(recSys), solver="cg", n_iters=_as_int("warm_start_iters", warm_start_iters),
+                  **({} if D is None else {"D": D}))
+    if warm_start_iters:
+        factors.fit()
+    factors.bpr = factors.fit_bpr(**cfg)
+    factors.vectors = factors.item_vectors()
+    return factors
+
+
 def BuildEASE(recSys: DeviceRecSys, graph=None, graph_kw=None, **cfg):
     """EXTENSION: EASE neighbour lists (recall.ItemCF.ease; ``cfg``: goctr_ease_cfg fields -- n_nbr, max_items, min_degree, scale,
     lambda_) over ``graph`` (default: BuildWalkGraph of the recSys's cache, ``graph_kw`` its cfg): the item-item weights learned

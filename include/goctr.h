@@ -1425,6 +1425,52 @@ int goctr_recommend_als_dot(goctr_model* m, goctr_recsys* r, goctr_als* als,
                             int32_t* out_cand_count, int32_t* out_target_pos, int64_t* out_target_rank,
                             int32_t* cand_items, uint32_t* cand_w, float* cand_scores, int64_t* n_failed);
 
+/* ---- BPR: Bayesian personalised ranking (Rendle et al. 2009) as a second objective for the factors of a goctr_als; no reference
+ * counterpart.  goctr_bpr_fit maximises the sum of ln sigma(x_u.y_i - x_u.y_j) over sampled triples (user u, held item i, not-held
+ * item j) by batch-synchronous SGD, and refines the handle's X and Y IN PLACE from their current values: a fresh handle (X zero, Y
+ * the initial Y) or an ALS-fitted one as a warm start; a Cholesky, weighted or CG handle alike (weights are ignored), D whatever the
+ * handle has, 4 .. 256.  Every entry that takes a handle then serves the result unchanged (goctr_als_recall_dot ranks by the score
+ * BPR trains).  All arithmetic is float64; tests/bpr_ref.py is the host restatement.
+ *   epoch          e = first_epoch + k, k = 0 .. epochs - 1, has n_edges triples n = 0 .. n_edges - 1.  The hash of a triple is
+ *                  h(s) = mix(seed ^ mix((e << 45) | (n << 5) | s)), mix the initial Y's (one splitmix64 step)
+ *   positive       p = h(0) mod n_edges, u the user whose uitems run holds position p, i = uitems[p]: with replacement
+ *   negative       try r = 0 .. neg_tries - 1: j = h(1 + r) mod n_items (UNIFORM) or j = uitems[h(1 + r) mod n_edges] (POPULAR); a
+ *                  try is accepted when item j has at least one edge and j is not in I_u; the first accepted try is the negative,
+ *                  and with none the triple is SKIPPED.  An item without edges is never trained: its row stays as it was
+ *   batch          the triples of equal floor(n / batch); the last of an epoch may be short.  EVERY GRADIENT OF A BATCH IS TAKEN AT
+ *                  THE FACTORS AS THEY STOOD WHEN THE BATCH BEGAN.  A non-skipped triple: z = x_u.(y_i - y_j), g = 1 / (1 + exp(z))
+ *   update         x_u <- x_u + lr (S_u - c_u lambda x_u), S_u the sum of g (y_i - y_j) over the batch's c_u triples of user u;
+ *                  y_r <- y_r + lr (T_r - c_r lambda y_r), T_r the sum of +g x_u over the triples where r is the positive and of
+ *                  -g x_u where it is the negative, c_r their number.  Rows without contributions are not touched
+ *   summation      FIXED: a row's contributions ascending in n (a triple's positive before its negative), in segments of 256, each
+ *                  from zero, the segments folded ascending; z is a tree over D that depends on D alone.  Two fits give the same
+ *                  bytes; no byte depends on the grid, on how rows are dealt to workgroups or on scratch contents.  The ORDER itself
+ *                  is the implementation's: the restatement agrees within rounding, not bit for bit
+ *   out_loss[k]    the mean of ln(1 + exp(-z)) over epoch k's non-skipped triples at the batch-start factors (0 without any)
+ *   out_auc[k]     the share of those triples with z > 0 (0 without any)
+ *   out_skipped[k] the skipped triples of epoch k, exact
+ *   out_triples    [(k n_edges + n) 3 ..] = (u, i, j), j = -1 for a skipped triple, exact
+ *   afterwards     G_Y is current; goctr_als_info's half_steps is unchanged.  epochs = 0 is a successful no-op
+ *   refused        (-1, nothing touched, the error text set) a NULL handle, graph or cfg; a cfg value outside its range; n_edges = 0
+ *                  or >= 2^40; a graph on another engine than the handle's; a graph whose sizes differ from the handle's */
+#define GOCTR_BPR_NEG_UNIFORM 0
+#define GOCTR_BPR_NEG_POPULAR 1
+typedef struct {
+  int32_t epochs;       /* >= 0                                                default 10 */
+  int32_t first_epoch;  /* >= 0, first_epoch + epochs <= 2^19                  default 0 */
+  int32_t batch;        /* 256 .. 2^22: triples of one synchronous step        default 65536 */
+  double  lr;           /* finite, > 0                                         default 0.05 */
+  double  lambda;       /* finite, >= 0                                        default 0.01 */
+  int32_t neg_tries;    /* 1 .. 16                                             default 8 */
+  int32_t neg_source;   /* GOCTR_BPR_NEG_UNIFORM 0 | GOCTR_BPR_NEG_POPULAR 1   default UNIFORM */
+  uint64_t seed;        /*                                                     default 0 */
+  int64_t reserved;     /* must be 0 */
+} goctr_bpr_cfg;
+void goctr_bpr_cfg_default(goctr_bpr_cfg* c);
+/* every output may be NULL: out_loss, out_auc, out_skipped [epochs]; out_triples [epochs, n_edges, 3] */
+int  goctr_bpr_fit(goctr_als* a, goctr_walkgraph* g, const goctr_bpr_cfg* cfg, double* out_loss, double* out_auc,
+                   int64_t* out_skipped, int32_t* out_triples);
+
 /* ---- EASE item neighbours: a learned item-item model as a fourth source of goctr_itemcf handles (Steck 2019, "Embarrassingly
  * Shallow Autoencoders"; no reference counterpart).  The three sources above set a pair's weight by a local rule; EASE learns all
  * weights jointly, so a pair that co-occurs only because both items co-occur with a hub is not weighted as if the link were direct.
